@@ -18,6 +18,13 @@ exchange, SpMV, p.Ap, x and r updates -- all of it, nothing skipped, on data alr
 Exactly K steps are timed between barrier+sync pairs; the max over ranks is taken; rank 0 prints ONE
 JSON line.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what `value` needs: set-up (generator, conversion, upload with
+its placement tuner), warm-up (the `sustained` leg's steps in one go, then W untimed steps in front of every timed segment), the K
+timed steps of the loop `value` is quoted on, the --dump-outputs files if asked for, the line.  Everything else below -- roofline,
+phases_us, structure_exploiting, sustained, cpu_baseline, preflight, rccl_only and the push-inside leg, the device's streaming
+rate, the median of 9 windows for K < 100 -- runs under --full.  Options given explicitly (--passes, --loops, ...) apply in both.
+--dump-outputs DIR writes x and the r.r / p.Ap histories of the timed loop's last segment as DIR/<name>.npy (float64, <= 64 MB).
+
   value        = N_gpus * K / seconds of the loop whose SpMV STREAMS THE REFERENCE'S OWN ARRAYS (spmv_scs64 / spmv_crs_split,
                  12 B per stored element): the loop SURVEY 8d's roofline is defined on (brick CG iterations per second summed
                  over all GPUs; at N=1 plain CG iterations/s).  ms_per_step, phases_us, sustained describe the same loop.
@@ -215,7 +222,7 @@ def run_rank(args):
     irregular = args.workload == "irregular"
     n = args.n if args.n > 0 else (80 if irregular else 128)
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu:
+    if world == 1 and rank == 0 and args.full and not args.no_cpu:
         cpu = cpu_baseline(args.workload, n, args.cpu_iters)  # before the GPU is initialised
     from sparsebench_amd.bench import context, hpcg, irregular as irregular_wl
     ctx = context.RankContext(args)
@@ -225,7 +232,18 @@ def run_rank(args):
     ctx.finalize()
 
 
-def main():
+def plain_or_full(args):
+    """A plain run does only what `value` needs; --full adds every other leg.  Options given explicitly keep their meaning in both."""
+    if args.loops is None:
+        args.loops = "both" if args.full else "reference"
+    if args.passes is None:
+        args.passes = {"clean", "events", "phases"} if args.full else {"clean"}
+    args.preflight_skipped = "--no-preflight" if args.no_preflight else None if args.full else "plain run (--full runs it)"
+    if not args.full:
+        args.no_preflight = args.no_rccl_leg = args.no_push_inside_leg = True
+
+
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=480)
@@ -254,22 +272,37 @@ def main():
     ap.add_argument("--transport", default="rccl", choices=["rccl", "host"],
                     help="N > 1 data plane: rccl (production) or host (gloo-staged; lets N ranks share one GPU "
                          "to rehearse the multi-rank flow -- its numbers are not a benchmark)")
-    ap.add_argument("--loops", default="both", choices=["both", "reference", "structure"],
-                    help="which CG loops to time: both (default: `value` on the reference-layout SpMV, the compressed-mirror loop in "
-                         "`structure_exploiting`), reference (only the former), structure (lab use: only the latter; the line says so)")
+    ap.add_argument("--loops", default=None, choices=["both", "reference", "structure"],
+                    help="which CG loops to time: both (--full's default: `value` on the reference-layout SpMV, the compressed-mirror "
+                         "loop in `structure_exploiting`), reference (only the former; the plain run's default), structure (lab use: "
+                         "only the latter; the line says so)")
     ap.add_argument("--no-rccl-leg", action="store_true", help="N > 1: do not time the second data plane (rccl_only)")
     ap.add_argument("--no-push-inside-leg", action="store_true", help="N > 1: do not time the push-inside-the-SpMV variant")
     ap.add_argument("--no-preflight", action="store_true", help="skip the known-answer checks (lab use; the line says so)")
-    ap.add_argument("--passes", type=lambda v: set(v.split(",")), default={"clean", "events", "phases"},
+    ap.add_argument("--passes", type=lambda v: set(v.split(",")), default=None,
                     help="which timed passes to run besides the clean one: events (HIP events around every SpMV launch: the roofline "
-                         "leg), phases (an event after every launch: the per-kernel breakdown).  `--passes clean` under rocprofv3 "
-                         "profiles exactly the loop `value` is quoted on")
-    ap.add_argument("--sustained-steps", type=int, default=4800, help="also time the clean loop over this many steps in one go "
-                                                                       "(reported as `sustained`; 0: off)")
+                         "leg), phases (an event after every launch: the per-kernel breakdown); --full's default clean,events,phases, "
+                         "the plain run's clean.  `--passes clean` under rocprofv3 profiles exactly the loop `value` is quoted on")
+    ap.add_argument("--sustained-steps", type=int, default=4800, help="run the clean loop over this many steps in one go before the "
+                                                                       "K-step windows (the device settles under load; reported as "
+                                                                       "`sustained` under --full; 0: off)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=60)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: CPU baseline, pre-flight checks, the compressed-mirror loop, the "
+                         "roofline and per-kernel passes, the sustained figure, the device's streaming rate, median of 9 windows for "
+                         "K < 100, and (N > 1) the second data plane and the push-inside leg.  Without it a run sets up, warms up, "
+                         "times exactly --steps steps of the loop `value` is quoted on and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed loop computed in its last step (x and the r.r / p.Ap histories) "
+                         "as DIR/<name>.npy, float64, at most 64 MB in all")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = parser().parse_args()
+    plain_or_full(args)
     if args.cpu_baseline_child:
         n = args.n if args.n > 0 else (80 if args.workload == "irregular" else 128)
         print(json.dumps(cpu_baseline_child(args.workload, n, args.cpu_iters)), flush=True)

@@ -51,7 +51,8 @@ class RankContext:
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
         self.local = int(os.environ.get("LOCAL_RANK", "0"))
         self.K, self.W = args.steps, args.warmup
-        self.repeats = 1 if self.K >= 100 else 9  # a 1 ms window moves by a few per cent from run to run: median of 9
+        # a 1 ms window moves by a few per cent from run to run: --full takes the median of 9; a plain run times exactly K steps
+        self.repeats = 1 if self.K >= 100 or not args.full else 9
         self.supervised = bool(os.environ.get("SB_BENCH_RANK_PROCESS"))
         self.dist = None
         rank, world = self.rank, self.world

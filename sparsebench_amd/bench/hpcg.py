@@ -15,6 +15,7 @@ import json
 import os
 import sys
 
+from . import outputs
 from .context import quiet_stdout
 from .line import HBM_PEAK_GBS, PARITY, kernel_name, phase_table, pmc_traffic, roofline_block, vector_bytes
 from .preflight import fail_preflight, load_goldens, preflight
@@ -80,7 +81,7 @@ def run(ctx, cpu):
             r = roofline_block(kern_of(rec), moved, alg, rec["spmv_us"], rec["launches"], *tr, on_moved_bytes=True)
             r["frac_of_hbm_peak_on_moved_bytes"] = r.pop("frac")
             blk["roofline_on_moved_bytes"] = r
-        if rec.get("t_sus"):
+        if rec.get("t_sus") and a.full:
             ks = a.sustained_steps
             blk["sustained"] = {"steps": ks, "value": world * ks / rec["t_sus"], "ms_per_step": 1e3 * rec["t_sus"] / ks}
         return blk
@@ -166,6 +167,8 @@ def run(ctx, cpu):
         return None
 
     res = measure(ctx, prob, modes, sustained=True)
+    if a.dump_outputs:
+        outputs.write(a.dump_outputs, res[primary]["outputs"], "" if world == 1 else "_rank%d" % rank)
     # third leg, peer-mapped halo and structure-exploiting kernel only: the halo push inside the SpMV launch (one launch fewer per
     # body).  Which variant is faster can only be decided with one rank per GPU, i.e. by this very run on a real node; validated
     # by its own pre-flight, and a failure here does not invalidate `value` (the variant is simply reported as failed).
@@ -193,7 +196,7 @@ def run(ctx, cpu):
         d = res[primary]
         it_s = K / d["t_clean"]
         kern = kern_of(d)
-        tr = pmc_traffic(workload, kern) if world == 1 else (None, None, "N > 1")
+        tr = pmc_traffic(workload, kern) if world == 1 and d["launches"] else (None, None, "N > 1")
         roof = roofline_block(kern, d["alg"], d["alg"], d["spmv_us"], d["launches"], *tr)
         cg_alg = 96.0 * prob.nr + d["alg"]  # the reference's unfused op list on its own layout
         cg_moved = d["moved"] + vector_bytes(prob.nr, d["vector_phase"])
@@ -205,7 +208,7 @@ def run(ctx, cpu):
         else:
             roof["note"] = ("the SpMV streams the reference's own %s arrays (12 B per stored element): bytes = SURVEY 8d's algorithmic "
                             "figure, no use of the matrix's structure" % ("CRS" if a.fmt == "crs" else "Sell-C-sigma"))
-        if world == 1 and roof["achieved"] > 0:
+        if world == 1 and a.full and roof["achieved"] > 0:
             # informational: what THIS device streams (a plain read of a fresh 1 GiB buffer, best of three allocations) next to the
             # 8 TB/s of the data sheet that `frac` is taken against -- measured after all timed passes
             stream = max(L.sb_debug_stream_read_gbs(1 << 30, 20) for _ in range(3))
@@ -248,7 +251,7 @@ def run(ctx, cpu):
             "timed_repeats": ctx.repeats,
             "ms_per_step_repeats": [1e3 * t / K for t in d["t_repeats"]],
             "global_iterations_per_s": it_s,
-            "roofline": roof,
+            "roofline": roof if d["launches"] else None,  # (no SpMV events timed: --passes without `events`, a plain run)
             "cg_reference_oplist_bytes_per_iteration": cg_alg,
             "cg_frac_of_roofline": (it_s * cg_alg / 1e9 / HBM_PEAK_GBS) if primary == 0 else None,
             "cg_roofline_iterations_per_s_per_gpu": HBM_PEAK_GBS * 1e9 / cg_alg,
@@ -258,12 +261,12 @@ def run(ctx, cpu):
             "phases_us": phase_table(d["phases"]),
             "preflight": ({"ok": not coll_problems, "checks": checks,
                            **({"problems": coll_problems, "ok_on_the_plane_value_is_quoted_on": True} if coll_problems else {})}
-                          if not a.no_preflight else {"ok": None, "skipped": "--no-preflight"}),
+                          if not a.no_preflight else {"ok": None, "skipped": a.preflight_skipped}),
             "compression": prob.pack_info(),
             "device": L.sb_device_name().decode(),
             "parity": PARITY,
         }
-        if d.get("t_sus"):
+        if d.get("t_sus") and a.full:
             ks = a.sustained_steps
             out["sustained"] = {"steps": ks, "value": world * ks / d["t_sus"], "ms_per_step": 1e3 * d["t_sus"] / ks,
                                 "note": "the same loop, clean, over %d steps in one go, run BEFORE the K-step windows (informational; `value` is "
@@ -328,7 +331,8 @@ def run(ctx, cpu):
                                "problems": coll_problems}
         elif res_coll is None and world > 1:
             out["rccl_only"] = {"note": "not timed separately: " + (
-                "--no-rccl-leg" if a.no_rccl_leg else "the peer-mapped paths are off, `value` IS the communicator's data plane")}
+                "plain run (--full times it)" if not a.full else "--no-rccl-leg" if a.no_rccl_leg else
+                "the peer-mapped paths are off, `value` IS the communicator's data plane")}
         out["cpu_baseline"] = cpu
     prob.free()
     return out

@@ -9,6 +9,7 @@ and Sell-64-1 (same row order, same dot order) with identical bits."""
 import json
 import os
 
+from . import outputs
 from .context import quiet_stdout
 from .line import HBM_PEAK_GBS, ROOT, kernel_name, phase_table, pmc_traffic, roofline_block, vector_bytes
 from .preflight import fail_preflight
@@ -56,7 +57,7 @@ def run(ctx, cpu):
                     irr_problems.append("%s: k = %d (reference %d), deviation %.3g from the reference's history (bound 1e-12)" % (label, kk, gold["k"], dev))
             if irr_problems:
                 fail_preflight(ctx, irr_checks, irr_problems, "irregular_fe_%d^3_nodes" % n)
-    meta = {}
+    meta, dumped = {}, {}
     for fmt, sigma in specs:
         with quiet_stdout():
             prob = hostapi.Problem("irregular", n, n, n, fmt=fmt, Cc=64, sigma=sigma)
@@ -64,9 +65,11 @@ def run(ctx, cpu):
         res = measure(ctx, prob, [default])
         d = res[default]
         name = "crs" if fmt == "crs" else "scs_C64_sigma%d" % sigma
+        if a.dump_outputs:
+            dumped.update({"%s_%s" % (name, k): v for k, v in d["outputs"].items()})
         workload = "irregular_fe_%d^3_nodes_%s" % (n, name)
         kern = kernel_name(fmt, default, bool(L.sb_matrix_crs_kernel(prob.matrix)))
-        tr = pmc_traffic(workload, kern)
+        tr = pmc_traffic(workload, kern) if d["launches"] else (None, None, None)
         # (a native CRS kernel without the fused p.Ap adds a dot pass over p and Ap: 16 B/row)
         dot_pass = bool(d["phases"] and "dot_pass" in d["phases"])
         cg_moved = d["moved"] + vector_bytes(prob.nr, d["vector_phase"]) + (16.0 * prob.nr if dot_pass else 0.0)
@@ -74,7 +77,7 @@ def run(ctx, cpu):
         formats[name] = {
             "cg_iterations_per_s": it, "ms_per_step": 1e3 * d["t_clean"] / K,
             "fill": (prob.nnzTrue / prob.nElems) if fmt == "scs" else 1.0,
-            "roofline": roofline_block(kern, d["alg"], d["alg"], d["spmv_us"], d["launches"], *tr),
+            "roofline": roofline_block(kern, d["alg"], d["alg"], d["spmv_us"], d["launches"], *tr) if d["launches"] else None,
             "spmv_useful_GBs": ((12.0 * prob.nnzTrue + 16.0 * prob.nr) / (d["spmv_us"] * 1e-6) / 1e9) if d["launches"] else None,
             "separate_dot_pass": dot_pass, "launches_per_iteration": d["launches_per_body"], "phases_us": phase_table(d["phases"]),
             "cg_frac_of_roofline": it * (96.0 * prob.nr + d["alg"]) / 1e9 / HBM_PEAK_GBS,
@@ -84,6 +87,8 @@ def run(ctx, cpu):
             best = name
             meta = {"rows": prob.nr, "nnz": prob.nnzTrue}
         prob.free()
+    if a.dump_outputs:
+        outputs.write(a.dump_outputs, dumped)
     b = formats[best]
     return {
         "metric": "cg_iterations_per_s", "value": b["cg_iterations_per_s"], "ok": True,
@@ -96,6 +101,7 @@ def run(ctx, cpu):
         "timed_repeats": ctx.repeats,
         "roofline": b["roofline"], "cg_frac_of_roofline": b["cg_frac_of_roofline"], "formats": formats,
         "device": L.sb_device_name().decode(),
-        "preflight": ({"ok": True, "checks": irr_checks} if irr_checks else {"ok": None, "skipped": "--no-preflight or no golden"}),
+        "preflight": ({"ok": True, "checks": irr_checks} if irr_checks else
+                      {"ok": None, "skipped": a.preflight_skipped or "no golden"}),
         "cpu_baseline": cpu,
     }

@@ -3,8 +3,11 @@
 A "step" is one CG iteration (loop body of solveCG, src/CGSolver.c:107-129).  Exactly K steps are timed between barrier + sync
 pairs, in segments restarted from x0 = 0 outside the clock (r.r stays far from underflow); the max over ranks is taken.  Passes:
 clean (no events: the rates), events (HIP events around every SpMV launch, on the layer's stream: the roofline legs), phases (an
-event after every launch: the per-kernel breakdown), sustained (the clean loop over thousands of steps in one go)."""
+event after every launch: the per-kernel breakdown), sustained (the clean loop over thousands of steps in one go).  With
+--dump-outputs the clean pass of the first mode also keeps what its last segment computed (outputs.capture, after the clock)."""
 import time
+
+from . import outputs
 
 SEGMENT = 120  # iterations per timed segment
 
@@ -16,8 +19,9 @@ def measure(ctx, prob, modes, clean_all=True, phases=True, sustained=False):
     prob.use_packed(modes[0])
     cg = ctx.new_cg(prob)
 
-    def timed_pass(with_spmv_events, with_phases=False, steps=None):
-        """exactly K loop bodies (`steps`: the sustained leg's count), in segments restarted from x0 = 0 outside the clock"""
+    def timed_pass(with_spmv_events, with_phases=False, steps=None, keep=None):
+        """exactly K loop bodies (`steps`: the sustained leg's count), in segments restarted from x0 = 0 outside the clock;
+        `keep` (a dict): receives what the last segment computed"""
         total, left, spmv_ms, spmv_n = 0.0, (steps or K), 0.0, 0
         phase_acc = {}
         while left > 0:
@@ -44,6 +48,8 @@ def measure(ctx, prob, modes, clean_all=True, phases=True, sustained=False):
                     acc[1] += cnt
             cg.phase_timing(False)
             cg.finish()
+            if keep is not None and left == seg:
+                keep.update(outputs.capture(cg))
             if after["stop"] and after["iters"] != W + 1 + seg:
                 raise RuntimeError("bench: the loop exited early: %r" % after)
             if after["n_pAp"] - before["n_pAp"] != seg or after["iters"] != W + 1 + seg:
@@ -64,6 +70,7 @@ def measure(ctx, prob, modes, clean_all=True, phases=True, sustained=False):
             continue
         t_clean = t_mine = None
         all_reps = []
+        kept = {}
         # the same loop over thousands of steps in one go (`sustained`), BEFORE the K-step windows: after idle time (the upload,
         # the host side of the pre-flight) the device runs the loop ~5 % slower for its first 50-150 ms under load, on fixed
         # memory, then settles (profiles/r04_placement_lab9.txt) -- a window of K = 20 steps is 3 ms of GPU work, so the windows
@@ -73,8 +80,8 @@ def measure(ctx, prob, modes, clean_all=True, phases=True, sustained=False):
             t_sus = ctx.rank_max(timed_pass(False, steps=a.sustained_steps)[0])
         if i == 0 or clean_all:
             mine, agreed = [], []
-            for _ in range(repeats):
-                dt = timed_pass(False)[0]
+            for r in range(repeats):
+                dt = timed_pass(False, keep=kept if i == 0 and r == repeats - 1 and a.dump_outputs else None)[0]
                 mine.append(dt)
                 agreed.append(ctx.rank_max(dt))  # the step ends when the slowest rank is done
             order = sorted(range(repeats), key=lambda j: agreed[j])
@@ -88,7 +95,7 @@ def measure(ctx, prob, modes, clean_all=True, phases=True, sustained=False):
                      "t_sus": t_sus, "spmv_us": 1e3 * ms / max(cnt, 1), "launches": cnt,
                      "launches_per_body": cg.launches_per_body(), "collectives_per_body": cg.collectives_per_body(),
                      "vector_phase": cg.vector_phase(),
-                     "moved": prob.stream_bytes(), "alg": prob.spmv_bytes(), "phases": ph}
+                     "moved": prob.stream_bytes(), "alg": prob.spmv_bytes(), "phases": ph, "outputs": kept or None}
     prob.use_packed(modes[0])
     cg.free()
     return res

@@ -33,7 +33,7 @@ def check_fractions(d):
 
 def test_two_ranks_as_typed(gpu):
     """exactly the command VERDICT asks for"""
-    d, err = run_bench("--gpus", "2", "--transport", "host", "--steps", "10", "--n", "32")
+    d, err = run_bench("--full", "--gpus", "2", "--transport", "host", "--steps", "10", "--n", "32")
     assert d["n_gpus"] == 2 and d["steps"] == 10 and d["value"] > 0 and d["scaling"] == "weak"
     assert d["config"]["transport"].startswith("host_staged") and d["config"]["parallelism"] == "1d_block_row_x2"
     assert d["config"]["dot_allreduce"] in ("in_kernel_peer_mapped", "host_staged_gloo")
@@ -80,14 +80,14 @@ def test_two_ranks_as_typed(gpu):
 def test_a_wrong_halo_value_fails_the_preflight_and_nothing_is_timed(gpu):
     """SB_TEST_CORRUPT_HALO=1: rank 1 sends another row's value in its first halo slot (library test hook).  The
     closed-form p.Ap of the first body and the golden history must catch it: exit code 4, no rate in the line."""
-    d, err = run_bench("--gpus", "2", "--transport", "host", "--steps", "10", "--n", "32", "--no-cpu",
+    d, err = run_bench("--full", "--gpus", "2", "--transport", "host", "--steps", "10", "--n", "32", "--no-cpu",
                        env={"SB_TEST_CORRUPT_HALO": "1"}, want_rc=4)
     assert "PRE-FLIGHT FAILED" in err and "SB_TEST_CORRUPT_HALO" in err
     assert d is not None and d["value"] is None and d["preflight"]["ok"] is False
     assert any("p.Ap of the first body" in p for p in d["preflight"]["problems"])
     assert any("golden" in p for p in d["preflight"]["problems"])
     # ... at a size without a committed golden the closed form alone must fire (and does on both bricks' sizes)
-    d, err = run_bench("--gpus", "3", "--transport", "host", "--steps", "10", "--n", "16", "--no-cpu",
+    d, err = run_bench("--full", "--gpus", "3", "--transport", "host", "--steps", "10", "--n", "16", "--no-cpu",
                        env={"SB_TEST_CORRUPT_HALO": "2"}, want_rc=4)
     assert d["value"] is None and any("closed form" in p for p in d["preflight"]["problems"])
 
@@ -109,10 +109,10 @@ def test_a_peer_mapped_plane_that_delivers_wrong_values_degrades_to_the_validate
     """first contact with real links must yield a line if ANY validated plane works: SB_TEST_CORRUPT_P2P_HALO=1 makes rank
     1's peer-mapped push swap two values (the communicator's plane is untouched).  The communicator's plane passes its
     pre-flight and is timed first; the peer-mapped plane fails its own: the line is quoted on the former, says so, exit 0."""
-    ok, _ = run_bench("--gpus", "2", "--transport", "host", "--steps", "10", "--n", "32", "--no-cpu", "--no-push-inside-leg")
+    ok, _ = run_bench("--full", "--gpus", "2", "--transport", "host", "--steps", "10", "--n", "32", "--no-cpu", "--no-push-inside-leg")
     if ok["config"]["halo_exchange"] != "peer_mapped_push_pull":
         pytest.skip("the peer-mapped halo did not come up on this box: nothing to degrade from")
-    d, err = run_bench("--gpus", "2", "--transport", "host", "--steps", "10", "--n", "32", "--no-cpu",
+    d, err = run_bench("--full", "--gpus", "2", "--transport", "host", "--steps", "10", "--n", "32", "--no-cpu",
                        env={"SB_TEST_CORRUPT_P2P_HALO": "1"})
     assert d["value"] > 0 and d["config"]["data_plane"] == "host_staged_gloo data plane"
     dg = d["degraded"]
@@ -130,7 +130,7 @@ def test_a_communicator_plane_that_delivers_wrong_values_leaves_the_peer_mapped_
     """... and the other way round: SB_TEST_CORRUPT_HOST_EXCHANGE=1 makes rank 1's staged send / recv swap two values (the
     peer-mapped push is untouched).  Nothing is timed on the communicator's plane, no checkpoint; the peer-mapped plane passes its
     own pre-flight and carries `value`; the line says which plane failed.  Both wrong (SB_TEST_CORRUPT_HALO) stays exit code 4."""
-    d, err = run_bench("--gpus", "2", "--transport", "host", "--steps", "10", "--n", "32", "--no-cpu", "--no-push-inside-leg",
+    d, err = run_bench("--full", "--gpus", "2", "--transport", "host", "--steps", "10", "--n", "32", "--no-cpu", "--no-push-inside-leg",
                        env={"SB_TEST_CORRUPT_HOST_EXCHANGE": "1"})
     if d["config"]["halo_exchange"] != "peer_mapped_push_pull":
         pytest.skip("the peer-mapped halo did not come up on this box: `value` IS the communicator's plane (and rc would be 4)")
@@ -143,7 +143,7 @@ def test_a_communicator_plane_that_delivers_wrong_values_leaves_the_peer_mapped_
 
 
 def test_a_crash_in_the_peer_mapped_legs_still_yields_the_validated_line(gpu):
-    d, err = run_bench("--gpus", "2", "--transport", "host", "--steps", "10", "--n", "32", "--no-cpu",
+    d, err = run_bench("--full", "--gpus", "2", "--transport", "host", "--steps", "10", "--n", "32", "--no-cpu",
                        env={"SB_BENCH_TEST_DIE_AFTER_CHECKPOINT": "1"})
     if "degraded" not in d:
         pytest.skip("one data plane only on this box (no checkpoint): %s" % d["config"].get("dot_allreduce_reason"))
@@ -160,11 +160,11 @@ def test_a_rank_whose_wait_runs_out_takes_the_others_with_it_at_once(gpu):
     400 ms, the all-reduce's at 60 s.  Rank 1 (waiting for rank 2's block) reports the cause, the others leave with it within
     seconds -- and, the communicator's plane having been validated and timed first, the run still yields its degraded line."""
     import time
-    ok, _ = run_bench("--gpus", "3", "--transport", "host", "--steps", "10", "--n", "32", "--no-cpu", "--no-push-inside-leg")
+    ok, _ = run_bench("--full", "--gpus", "3", "--transport", "host", "--steps", "10", "--n", "32", "--no-cpu", "--no-push-inside-leg")
     if ok["config"]["halo_exchange"] != "peer_mapped_push_pull":
         pytest.skip("the peer-mapped halo did not come up on this box")
     t0 = time.time()
-    d, err = run_bench("--gpus", "3", "--transport", "host", "--steps", "10", "--n", "32", "--no-cpu",
+    d, err = run_bench("--full", "--gpus", "3", "--transport", "host", "--steps", "10", "--n", "32", "--no-cpu",
                        env={"SB_TEST_DROP_PUSH_RANK": "2", "SB_TEST_DROP_PUSH_AT": "7", "SB_TEST_HALO_TIMEOUT_MS": "400",
                             "SB_P2P_TIMEOUT_MS": "60000"})
     took = time.time() - t0
@@ -183,7 +183,7 @@ def test_as_the_driver_launches_it_under_torch_distributed_run(gpu):
     port = s.getsockname()[1]
     s.close()
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                          "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--transport",
+                          "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--transport",
                           "host", "--steps", "10", "--warmup", "3", "--grid", "32", "--no-cpu"], stdout=subprocess.PIPE,  # ("--n" is an ambiguous prefix for torchrun's own parser)
                          stderr=subprocess.PIPE, timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert out.returncode == 0, out.stderr.decode()[-3000:]
@@ -196,7 +196,7 @@ def test_as_the_driver_launches_it_under_torch_distributed_run(gpu):
 def test_five_ranks_next_to_the_test_process(gpu):
     """the pool allows 6 processes per GPU and this test process holds one of them: 5 ranks here; N = 6 is rehearsed from the
     command line (profiles/r03_bench_rehearsal_n6.json), where bench.py's parent stays off the GPU"""
-    d, _ = run_bench("--gpus", "5", "--transport", "host", "--steps", "6", "--warmup", "2", "--n", "32", "--no-cpu")
+    d, _ = run_bench("--full", "--gpus", "5", "--transport", "host", "--steps", "6", "--warmup", "2", "--n", "32", "--no-cpu")
     assert d["n_gpus"] == 5 and d["value"] > 0 and d["preflight"]["ok"]
     assert all(c["golden"] == "hpcg32_x5_scs_C64_sigma256" for c in d["preflight"]["checks"])
     assert len(d["per_rank"]["ms_per_step"]) == 5 and len(d["config"]["spmv_kernel_mode_structure_exploiting_by_rank"]) == 5
@@ -204,7 +204,7 @@ def test_five_ranks_next_to_the_test_process(gpu):
 
 @pytest.mark.parametrize("n_ranks,p2p", [(4, "1"), (4, "0"), (3, "1")])
 def test_more_ranks_and_both_data_planes(gpu, n_ranks, p2p):
-    d, _ = run_bench("--gpus", str(n_ranks), "--transport", "host", "--steps", "10", "--n", "16", "--no-cpu",
+    d, _ = run_bench("--full", "--gpus", str(n_ranks), "--transport", "host", "--steps", "10", "--n", "16", "--no-cpu",
                      env={"SB_P2P": p2p, "SB_P2P_HALO": p2p})
     assert d["n_gpus"] == n_ranks and d["value"] > 0
     assert len(d["config"]["spmv_kernel_mode_structure_exploiting_by_rank"]) == n_ranks  # which mirror kernel every rank's brick got
@@ -215,7 +215,7 @@ def test_more_ranks_and_both_data_planes(gpu, n_ranks, p2p):
 
 
 def test_single_gpu_line_has_the_contract_keys(gpu):
-    d, _ = run_bench("--steps", "40", "--warmup", "5", "--n", "48", "--cpu-iters", "10")
+    d, _ = run_bench("--full", "--steps", "40", "--warmup", "5", "--n", "48", "--cpu-iters", "10")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -249,7 +249,7 @@ def test_single_gpu_line_has_the_contract_keys(gpu):
 
 
 def test_irregular_workload_line(gpu):
-    d, _ = run_bench("--workload", "irregular", "--n", "16", "--steps", "30", "--warmup", "5", "--no-cpu", "--irr-sigmas", "1,512")
+    d, _ = run_bench("--full", "--workload", "irregular", "--n", "16", "--steps", "30", "--warmup", "5", "--no-cpu", "--irr-sigmas", "1,512")
     assert "Flan_1565 not available" in d["config"]["workload"]
     assert set(d["formats"]) == {"crs", "scs_C64_sigma1", "scs_C64_sigma512"}
     for f in d["formats"].values():
@@ -264,7 +264,7 @@ def test_irregular_workload_line(gpu):
 def test_the_benchmark_size_line_says_what_the_placement_tuner_saw(gpu):
     """at the benchmark's own size the upload chooses by measurement which device memory the streamed arrays and the loop's vectors
     occupy; the line carries what that search saw, and the kernel `value` is quoted on is the reference-layout one"""
-    d, _ = run_bench("--n", "128", "--steps", "10", "--warmup", "3", "--no-cpu", "--loops", "reference", "--passes", "clean,events",
+    d, _ = run_bench("--full", "--n", "128", "--steps", "10", "--warmup", "3", "--no-cpu", "--loops", "reference", "--passes", "clean,events",
                      "--sustained-steps", "0")
     pl = d["config"]["placement"]
     assert pl and pl["probes_timed"] >= 3 and pl["us_kept"] <= pl["us_first_pair"] <= pl["us_slowest"] * 1.0001
@@ -274,3 +274,28 @@ def test_the_benchmark_size_line_says_what_the_placement_tuner_saw(gpu):
     assert 4000 < d["roofline"]["device_stream_read_GBs"] < 8000 and 0.6 < d["roofline"]["achieved_over_device_stream_read"] < 1.05
     assert d["preflight"]["ok"] and [c["golden"] for c in d["preflight"]["checks"] if "bench bricks" in c["case"]] == ["hpcg128_x1_scs_C64_sigma256"]
     check_fractions(d)
+
+
+def test_plain_run_times_exactly_k_steps_and_dumps_what_the_loop_computed(gpu, tmp_path):
+    """the plain run (no --full): set-up, warm-up, exactly K timed steps of the loop `value` is quoted on, the line -- nothing else.
+    --dump-outputs writes what that loop computed in its last segment (restarted from x0 = 0 with W + 1 untimed bodies in front of
+    the K = 30 timed ones): bit for bit what the oracle computes under the GPU's dot order"""
+    import numpy as np
+    from oracle import pyoracle as po
+    out = tmp_path / "outputs"
+    d, _ = run_bench("--gpus", "1", "--steps", "30", "--warmup", "3", "--n", "32", "--dump-outputs", str(out))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["metric"] == "cg_iterations_per_s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["value"] > 0
+    assert d["steps"] == 30 and d["warmup"] == 3 and d["timed_repeats"] == 1 and len(d["ms_per_step_repeats"]) == 1
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-9 * d["value"] and d["config"]["spmv_kernel"] == "spmv_scs64"
+    # the other legs stay behind --full
+    assert d["cpu_baseline"] is None and d["preflight"]["ok"] is None and d["roofline"] is None and d["phases_us"] is None
+    assert "structure_exploiting" not in d and "sustained" not in d
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["pAp_history.npy", "rr_history.npy", "x.npy"], files
+    x, rr, pap = (np.load(str(out / f)) for f in ("x.npy", "rr_history.npy", "pAp_history.npy"))
+    assert x.dtype == rr.dtype == pap.dtype == np.float64 and x.shape == (32 ** 3,)
+    o = po.cg(po.GMatrix.generate(32, 32, 32), itermax=3 + 2 + 30, fmt="scs", Cc=64, sigma=256, dot="tree", want_x=True)
+    assert np.array_equal(rr, o["rr"]) and np.array_equal(pap, o["pAp"])
+    assert np.array_equal(x, o["x"][0])

@@ -7,7 +7,7 @@ import re
 import numpy as np
 import pytest
 
-from conftest import REFDATA, load_json
+from conftest import GOLDEN, REFDATA, load_json
 from oracle import pyoracle as po
 
 
@@ -135,24 +135,38 @@ def test_multirank_band_klein_matches_mpi_reference(golden_mpi):
     assert np.array_equal(o["rr"], np.array([float(v) for v in gd["rr"]]))
 
 
-@pytest.mark.skipif(not po.ref_available("crs"), reason="oracle/_ref not built here")
+def _fingerprint(rp, col, val):
+    import hashlib
+    h = hashlib.sha256()
+    for a in (rp.astype(np.uint32), col.astype(np.uint32), val.astype(np.float64)):
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
 def test_live_reference_build_agrees():
-    ref = po.Ref("crs")
-    ref.setup("generate", 12, 10, 9)
+    """the oracle against what the reference build computes (tests/golden/ref_live.npz, make_golden_live_ref.py) on HPCG
+    12 x 10 x 9: CRS arrays, SpMV, waxpby, ddot, 40 CG iterations -- bit for bit; and, where oracle/_ref was built, the live
+    reference against the same values"""
+    fx = np.load(os.path.join(GOLDEN, "ref_live.npz"))
     g = po.GMatrix.generate(12, 10, 9)
-    rp, col, val = ref.csr()
-    assert np.array_equal(rp, g.rowPtr) and np.array_equal(col, g.col) and np.array_equal(val, g.val)
     rng = np.random.default_rng(7)
     x = rng.standard_normal(g.nc)
     y = rng.standard_normal(g.nr)
-    assert np.array_equal(ref.spmv(x), g.spmv(x))
-    assert np.array_equal(ref.waxpby(1.0, y, -0.37, x), po.waxpby(1.0, y, -0.37, x))
-    assert np.array_equal(ref.waxpby(2.5, y, 1.0, x), po.waxpby(2.5, y, 1.0, x))
-    assert np.array_equal(ref.waxpby(2.5, y, -3.0, x), po.waxpby(2.5, y, -3.0, x))
-    assert ref.ddot(x, y) == po.ddot_seq(x, y)
-    h = ref.solve_cg(40)
-    o = po.cg(g, itermax=40)
-    assert h["k"] == o["k"] and np.array_equal(h["rr"], o["rr"]) and np.array_equal(h["pAp"], o["pAp"])
+
+    def agrees(csr, spmv, waxpby, ddot, cg):
+        assert _fingerprint(*csr) == str(fx["gen_csr_sha256"])
+        assert np.array_equal(spmv(x), fx["gen_spmv"])
+        assert np.array_equal(waxpby(1.0, y, -0.37, x), fx["gen_waxpby"][0])
+        assert np.array_equal(waxpby(2.5, y, 1.0, x), fx["gen_waxpby"][1])
+        assert np.array_equal(waxpby(2.5, y, -3.0, x), fx["gen_waxpby"][2])
+        assert ddot(x, y) == float(fx["gen_ddot"])
+        h = cg(40)
+        assert h["k"] == int(fx["gen_cg_k"]) and np.array_equal(h["rr"], fx["gen_cg_rr"]) and np.array_equal(h["pAp"], fx["gen_cg_pAp"])
+    agrees((g.rowPtr, g.col, g.val), g.spmv, po.waxpby, po.ddot_seq, lambda k: po.cg(g, itermax=k))
+    if po.ref_available("crs"):
+        ref = po.Ref("crs")
+        ref.setup("generate", 12, 10, 9)
+        agrees(ref.csr(), ref.spmv, ref.waxpby, ref.ddot, ref.solve_cg)
 
 
 def test_tree_dot_is_within_the_sequential_sums_own_error():
@@ -240,9 +254,10 @@ def test_irregular_stand_in_history_bit_identical_to_the_reference(n):
     g.free()
 
 
-@pytest.mark.skipif(not po.ref_available("crs"), reason="oracle/_ref not built (no /root/reference here)")
 def test_live_reference_on_the_irregular_stand_in(tmp_path):
-    """the same link live: export 12^3 as .mtx now, let the reference read and solve it, compare with the committed history"""
+    """the same link as a file: export 12^3 as .mtx now, read it back -- with the oracle's reader, and with the reference's where
+    oracle/_ref was built -- and find the CRS arrays the reference built from that file (tests/golden/ref_live.npz) and the
+    generator's; the reference's solve on it gives the committed history"""
     import importlib.util
     spec = importlib.util.spec_from_file_location("mk", os.path.join(os.path.dirname(REFDATA), "make_golden_irregular_ref.py"))
     mk = importlib.util.module_from_spec(spec)
@@ -250,10 +265,17 @@ def test_live_reference_on_the_irregular_stand_in(tmp_path):
     nr, nc, rp, col, val = mk.stand_in(12)
     path = str(tmp_path / "irregular_12.mtx")
     mk.write_mtx(path, nr, rp, col, val)
-    ref = po.Ref("crs")
-    ref.setup(path)
-    rrp, rcol, rval = ref.csr()
-    assert np.array_equal(rrp, rp) and np.array_equal(rcol, col) and np.array_equal(rval, val)
-    h = ref.solve_cg(40)
+    want = str(np.load(os.path.join(GOLDEN, "ref_live.npz"))["irr12_csr_sha256"])
     e = load_json("cg_hist_irregular_ref.json")["irregular12"]
-    assert np.array_equal(h["rr"], np.array([float(v) for v in e["rr"]])) and h["k"] == e["k"]
+    assert _fingerprint(rp, col, val) == want == e["matrix_sha256"]
+    g = po.GMatrix.from_mtx(path, 0, 1)
+    assert _fingerprint(g.rowPtr, g.col, g.val) == want
+    o = po.cg(g, itermax=e["itermax"], dot="seq")
+    assert np.array_equal(o["rr"], np.array([float(v) for v in e["rr"]])) and o["k"] == e["k"]
+    if po.ref_available("crs"):
+        ref = po.Ref("crs")
+        ref.setup(path)
+        rrp, rcol, rval = ref.csr()
+        assert np.array_equal(rrp, rp) and np.array_equal(rcol, col) and np.array_equal(rval, val)
+        h = ref.solve_cg(40)
+        assert np.array_equal(h["rr"], np.array([float(v) for v in e["rr"]])) and h["k"] == e["k"]

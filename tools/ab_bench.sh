@@ -7,7 +7,7 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do extra+=("$1"); shift; done
 [ "${1:-}" = "--" ] && shift
 for v in "$@"; do
   printf "%-34s" "$v"
-  env $v python bench.py --no-cpu "${extra[@]}" | python -c "
+  env $v python bench.py --full --no-cpu "${extra[@]}" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 q=d.get('roofline_reference_layout')

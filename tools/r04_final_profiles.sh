@@ -9,10 +9,10 @@ set -o pipefail
 O=gpurun_out/r04
 mkdir -p $O gpurun_out/prof
 python3 -c "from sparsebench_amd import srchash; print(srchash.csrc_hash())" > $O/source_hash.txt
-b() { local name=$1; shift; python3 bench.py "$@" > $O/r04_bench_$name.json 2>> $O/bench.err; echo "bench $name rc=$?"; }
+b() { local name=$1; shift; python3 bench.py --full "$@" > $O/r04_bench_$name.json 2>> $O/bench.err; echo "bench $name rc=$?"; }
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
 # PMC passes of the default bench (both loops: spmv_scs64 and spmv_prog_fusep in one process)
-tools/prof_run.sh r04_hpcg128 bench.py --no-cpu --steps 60 --warmup 5 --no-preflight --sustained-steps 0
+tools/prof_run.sh r04_hpcg128 bench.py --full --no-cpu --steps 60 --warmup 5 --no-preflight --sustained-steps 0
 # the native CRS kernel inside CG, and the irregular stand-in: kernel trace + FETCH / WRITE passes + the size split of the memory-side reads
 for spec in "r04_hpcg128_crs:--fmt crs --loops reference --steps 40" "r04_irregular:--workload irregular --irr-sigmas 1,256 --steps 40"; do
   tag=${spec%%:*}; extra=${spec#*:}; out=gpurun_out/prof/$tag; mkdir -p $out

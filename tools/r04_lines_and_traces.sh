@@ -1,5 +1,5 @@
 O=gpurun_out/r04; mkdir -p $O
-b() { local name=$1; shift; python3 bench.py "$@" > $O/r04_bench_$name.json 2>> $O/bench.err; echo "bench $name rc=$?"; }
+b() { local name=$1; shift; python3 bench.py --full "$@" > $O/r04_bench_$name.json 2>> $O/bench.err; echo "bench $name rc=$?"; }
 b n1_128_scs_sigma256
 b n1_as_the_driver_types_it --gpus 1 --steps 20 --warmup 5
 b n1_128_scs_sigma1 --sigma 1 --no-cpu
