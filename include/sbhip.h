@@ -184,6 +184,15 @@ double sb_ddot(uint32_t n, const double* x, const double* y); /* synchronises */
  * levels 1-2 over m = ceil(n/256) groups of four partials */
 void sb_ddot_partials(uint32_t n, const double* x, const double* y, double* partials_dev);
 void sb_reduce_final(uint32_t m, const double* partials_dev, double* result_dev);
+/* The dot order of sb_ddot, sb_ddot_async and of every solver that does not choose its own (sb_cg_set_dot_order):
+ * 0 = tree, the fixed order above (the default); 1 = seq, the reference's own ddot (src/solver.c:41-62 as shipped,
+ * ENABLE_OPENMP = false): per rank ONE left-to-right sum `sum = 0.0; sum += x[i] * y[i]` over its rows in original row
+ * order, every product rounded before its add, the ranks' sums then combined as in tree order.  seq runs on one
+ * workgroup (a dependent add per element) and exists for validation: with it the GPU reproduces the reference's
+ * numbers bit for bit.  SB_DOT_ORDER=tree|seq sets the default at the first call (any other value ends the process with
+ * a message); sb_dot_order works before sb_init.  sb_ddot_partials / sb_reduce_final stay the tree order's stages. */
+void sb_set_dot_order(int order);
+int sb_dot_order(void);
 
 /* ---- multi-GPU (one rank per GPU, RCCL over xGMI) ---------------------------- */
 /* replaces MPI_Init / MPI_COMM_WORLD.  id = 128-byte ncclUniqueId made by rank 0
@@ -283,6 +292,15 @@ void sb_cg_debug_ptrs(const sb_cg* s, unsigned long long out[8]); /* lab: device
  * registers; otherwise it behaves as 1; 3: the two scalar steps ride in front of their consumers (workgroup 0 of the
  * r / p update takes them and publishes alpha / beta through a flag; 3 launches per body; one rank only, otherwise as 1).  (2 and 3 measured slower than 1 at 128^3: sbhip_cg.inc.h.)  Same bits in every mode. */
 void sb_cg_set_fused(sb_cg* s, int fused);
+/* The dot order of this solver's dots (r.r, p.Ap), src/solver.c:41-62: 0 = tree, 1 = seq (see sb_set_dot_order), -1 =
+ * the process default (sb_dot_order; the initial setting).  seq runs the reference's op list (fused = 0: the region
+ * table of sb_cg_region_ms is filled, sb_cg_launches_per_body is 0, sb_cg_fuse_p 0) with every dot as the sequential
+ * sum: the history is the reference's solveCG history bit for bit.  The fused level set with sb_cg_set_fused is kept and
+ * applies again under tree.  The order is latched by sb_cg_start for the whole solve; a change made between
+ * sb_cg_start and sb_cg_finish takes effect with the next sb_cg_start.  sb_cg_dot_order: the order the solve
+ * uses (or, outside a solve, will use). */
+void sb_cg_set_dot_order(sb_cg* s, int order);
+int sb_cg_dot_order(const sb_cg* s);
 /* spans per wave of the one-launch vector phase the solver will use, 0 if it will not use it */
 int sb_cg_vector_phase(sb_cg* s);
 /* launches per loop body the loop will use: 5 (p update | SpMV | alpha | r update | beta), 3 (fused = 3), 2 (fused = 2);

@@ -35,6 +35,7 @@ SYMBOLS = [
     "sb_cg_set_fuse_p", "sb_cg_fuse_p", "sb_cg_set_fuse_alpha", "sb_cg_set_fuse_beta",
     "sb_malloc_host_visible", "sb_host_visible_reason", "sb_malloc_pinned_host", "sb_free_pinned_host", "sb_copy_counters",
     "sb_region_begin", "sb_region_end", "sb_region_seconds", "sb_region_reset",
+    "sb_set_dot_order", "sb_dot_order", "sb_cg_set_dot_order", "sb_cg_dot_order",
     "sb_matrix_place", "sb_matrix_place_at", "sb_matrix_place_home", "sb_placement_arena_bytes", "sb_placement_probe", "sb_matrix_place_fresh", "sb_matrix_place_commit", "sb_matrix_placement", "sb_matrix_placement_report", "sb_matrix_debug_ptrs", "sb_cg_debug_ptrs",
 ]
 
@@ -173,6 +174,10 @@ def load():
         "sb_matrix_debug_ptrs": (None, [vp, C.POINTER(C.c_uint64)]),
         "sb_matrix_placement_report": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "sb_cg_debug_ptrs": (None, [vp, C.POINTER(C.c_uint64)]),
+        "sb_set_dot_order": (None, [C.c_int]),
+        "sb_dot_order": (C.c_int, []),
+        "sb_cg_set_dot_order": (None, [vp, C.c_int]),
+        "sb_cg_dot_order": (C.c_int, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -820,6 +820,83 @@ __global__ __launch_bounds__(1024) void reduce_final_k(uint32_t m, const double*
 }
 
 // =============================================================================
+// The reference's own dot order (sb_set_dot_order(1) / SB_DOT_ORDER=seq; a validation mode, never the default, never timed):
+//   sum = 0.0; for i = 0 .. n-1: sum += a[i] * b[i]          (src/solver.c:41-62, ENABLE_OPENMP = false)
+// in the caller's row order: perm != NULL walks a[perm[i]] * b[perm[i]] (the CG vectors of a permuted Sell-C-sigma matrix sit
+// at oldToNewPerm[i]).  Every product is rounded before its add -- the products cross LDS between the multiply and
+// the add, so no FMA can form.  The add chain cannot be split without changing bits: ONE workgroup.  Waves 1-15 load the
+// operands (coalesced, several loads in flight per lane) and store the products into one of two LDS blocks while lane 0 of
+// wave 0 adds the other block, reading LDS 16 elements ahead of the chain; one barrier per block.  The sum starts from +0.0,
+// as the reference's does, so it is never -0.0 and n = 0 gives +0.0.  The result goes to out[0]: where that is the CG
+// loop's partial array, the scalar step reads it as the one level-1 value of the dot (m = 1; x + 0.0 == x for every x that
+// is not -0.0), so alpha, beta, the loop test, the history and the all-reduce are the tree order's code.
+// =============================================================================
+constexpr uint32_t DOT_SEQ_BLK  = 8192;                           // doubles per LDS block (two blocks: 128 KiB of 160 KiB)
+constexpr uint32_t DOT_SEQ_PROD = 1024 - 64;                      // producer threads (waves 1-15)
+constexpr int DOT_SEQ_PER       = (DOT_SEQ_BLK + DOT_SEQ_PROD - 1) / DOT_SEQ_PROD; // products per producer thread and block
+__global__ __launch_bounds__(1024) void dot_seq_k(uint32_t n, const double* __restrict__ a, const double* __restrict__ b,
+    const uint32_t* __restrict__ perm, double* __restrict__ out, const int* __restrict__ stop)
+{
+  __shared__ __attribute__((aligned(16))) double blk[2][DOT_SEQ_BLK];
+  if (stop && *stop) return;
+  const uint32_t nBlk = (uint32_t)(((uint64_t)n + DOT_SEQ_BLK - 1) / DOT_SEQ_BLK);
+  auto count = [&](uint32_t t) { return (uint32_t)min((uint64_t)DOT_SEQ_BLK, (uint64_t)n - (uint64_t)t * DOT_SEQ_BLK); };
+  double sum = 0.0;
+  // step t: the producers fill block t into blk[t & 1] while the adder consumes block t - 1 from blk[(t - 1) & 1]; the barrier
+  // at the end of step t makes block t visible and frees block t - 1's buffer for block t + 1
+  for (uint32_t t = 0; t <= nBlk; t++) {
+    if (threadIdx.x >= 64u) {
+      if (t < nBlk) {
+        const uint64_t base = (uint64_t)t * DOT_SEQ_BLK;
+        const uint32_t cnt  = count(t), j0 = threadIdx.x - 64u;
+        uint32_t k[DOT_SEQ_PER];
+#pragma unroll
+        for (int u = 0; u < DOT_SEQ_PER; u++) {
+          const uint32_t j = j0 + (uint32_t)u * DOT_SEQ_PROD;
+          k[u]             = j < cnt ? (perm ? perm[base + j] : (uint32_t)(base + j)) : 0u;
+        }
+        double v[DOT_SEQ_PER];
+#pragma unroll
+        for (int u = 0; u < DOT_SEQ_PER; u++) v[u] = j0 + (uint32_t)u * DOT_SEQ_PROD < cnt ? a[k[u]] * b[k[u]] : 0.0;
+#pragma unroll
+        for (int u = 0; u < DOT_SEQ_PER; u++)
+          if (j0 + (uint32_t)u * DOT_SEQ_PROD < cnt) blk[t & 1u][j0 + (uint32_t)u * DOT_SEQ_PROD] = v[u];
+      }
+    } else if (threadIdx.x == 0 && t > 0) {
+      const double* src  = blk[(t - 1u) & 1u];
+      const uint32_t cnt = count(t - 1u);
+      const double2* s2  = reinterpret_cast<const double2*>(src);
+      uint32_t j         = 0;
+      if (cnt >= 16u) {
+        double2 c[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) c[u] = s2[u];
+        for (j = 16u; j + 16u <= cnt; j += 16u) {
+          double2 d[8]; // the next 16 products in flight while the chain adds these
+#pragma unroll
+          for (int u = 0; u < 8; u++) d[u] = s2[j / 2u + (uint32_t)u];
+#pragma unroll
+          for (int u = 0; u < 8; u++) {
+            sum = sum + c[u].x;
+            sum = sum + c[u].y;
+          }
+#pragma unroll
+          for (int u = 0; u < 8; u++) c[u] = d[u];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+          sum = sum + c[u].x;
+          sum = sum + c[u].y;
+        }
+      }
+      for (; j < cnt; j++) sum = sum + src[j];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *out = sum;
+}
+
+// =============================================================================
 // In-kernel all-reduce of ONE double over peer-mapped memory (several ranks).
 // A dot product on P ranks is: local reduce | all-reduce of 8 bytes | scalar step.  Through
 // RCCL that is three dependent launches (~25 us); here the scalar step's own workgroup does

@@ -302,6 +302,9 @@ struct sb_cg {
   int fuseAlphaWant = -1; // sb_cg_set_fuse_alpha: 1 / 0, -1: SB_FUSE_ALPHA or the library default (on)
   int fuseBetaWant  = -1; // sb_cg_set_fuse_beta
   int betaFold      = 0;  // 1 / 2: the last enqueued body left its beta step to the next p update (fold mode)
+  int fusedWant     = 1;  // sb_cg_set_fused: the caller's level; `fused` is what runs (0 while the dot order is seq)
+  int dotOrderWant  = -1; // sb_cg_set_dot_order: 0 tree / 1 seq, -1: the process default (sb_dot_order)
+  int seqLatched    = -1; // the dot order of the solve that is running (set by sb_cg_start, cleared by sb_cg_finish)
   CgScalars* S;
   double* partials;
   uint32_t nPartials;

@@ -62,6 +62,8 @@ static void cg_point_vectors(sb_cg* s, char* slab, bool hasExact)
   s->xexact  = hasExact ? at(L.xexact) : nullptr;
 }
 
+static void apply_dot_order(sb_cg* s);
+
 sb_cg* sb_cg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host)
 {
   need_init();
@@ -121,6 +123,7 @@ sb_cg* sb_cg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, con
   HIP_CHECK(hipEventCreate(&s->evLoop0));
   HIP_CHECK(hipEventCreate(&s->evLoop1));
   for (double& v : s->region_ms) v = 0.0;
+  apply_dot_order(s);
   return s;
 }
 
@@ -157,6 +160,31 @@ static void drop_graph(sb_cg* s)
   s->iterGraph = nullptr, s->graphReady = false;
 }
 
+// The dot order of the loop: tree (0, the fixed order of every fused kernel) or seq (1, the reference's sequential sum,
+// dot_seq_k).  seq runs the reference's op list (fused = 0) with each of its dots -- r.r of the prologue and of every body,
+// p.Ap -- as dot_seq_k; every fused dot, the fused p update, the folded scalar steps and the lab plans are bypassed because
+// fused is 0.  The caller's fused level is kept (fusedWant) and runs again when the order returns to tree.  Decided once per
+// solve, like the fused-p plan: sb_cg_start latches it, so the pieces of one solve never mix orders; a change in between
+// takes effect with the next sb_cg_start.
+static bool cg_seq(const sb_cg* s)
+{
+  if (s->seqLatched >= 0) return s->seqLatched > 0;
+  return (s->dotOrderWant >= 0 ? s->dotOrderWant : sb_dot_order()) == 1;
+}
+static void apply_dot_order(sb_cg* s)
+{ // what runs: the caller's level, or the reference's op list under seq
+  const int fused = cg_seq(s) ? 0 : s->fusedWant;
+  if (s->fused != fused) drop_graph(s), s->vSP = -1, s->leadPlan = -1, s->fusepPlan = -1;
+  s->fused = fused;
+}
+void sb_cg_set_dot_order(sb_cg* s, int order)
+{
+  if (order < -1 || order > 1) SB_FATAL("sb_cg_set_dot_order(%d): expected -1 (process default), 0 (tree) or 1 (seq)", order);
+  s->dotOrderWant = order;
+  if (s->seqLatched < 0) apply_dot_order(s);
+}
+int sb_cg_dot_order(const sb_cg* s) { return cg_seq(s) ? 1 : 0; }
+
 void sb_cg_set_fused(sb_cg* s, int fused)
 { // 0: the reference's op list; 1 (default): dots fused into their producers (5 launches per body).  Lab builds (-DSB_LAB)
   // additionally: 2: the vector phase of a body as one launch where that is possible (2 launches per body); 3: the two
@@ -165,8 +193,8 @@ void sb_cg_set_fused(sb_cg* s, int fused)
 #ifndef SB_LAB
   fused = fused ? 1 : 0;
 #endif
-  if (s->fused != fused) drop_graph(s), s->vSP = -1, s->leadPlan = -1, s->fusepPlan = -1;
-  s->fused = fused;
+  s->fusedWant = fused;
+  apply_dot_order(s);
 }
 
 #ifdef SB_LAB
@@ -259,6 +287,7 @@ static bool fusep_plan(sb_cg* s)
 // themselves are counted by sb_cg_collectives_per_body.
 int sb_cg_launches_per_body(sb_cg* s)
 {
+  if (s->seqLatched < 0) apply_dot_order(s); // (the process default may have changed since the last call)
   int base = vphase_plan(s) ? 2 : lead_plan(s) ? 3 : fusep_plan(s) ? 4 : s->fused ? 5 : 0;
   if (base >= 4 && fusealpha_plan(s, fusep_plan(s) ? 1 : pAp_is_level1(s), 1024u)) base -= 1; // (alpha step inside the r update)
   if (base >= 4 && fusebeta_plan(s, 1024u)) base -= 1;                                          // (beta step inside the p update)
@@ -276,6 +305,7 @@ int sb_cg_launches_per_body(sb_cg* s)
 // communicator calls per loop body (RCCL / transport): 2 all-reduces + 1 send-recv group without the peer-mapped paths
 int sb_cg_collectives_per_body(sb_cg* s)
 {
+  if (s->seqLatched < 0) apply_dot_order(s);
   if (!multi_rank() || !s->fused) return 0;
   return (p2p_dots() ? 0 : 2) + (s->halo && !halo_p2p_active(s->halo) ? 1 : 0);
 }
@@ -350,7 +380,11 @@ void sb_cg_set_fuse_p(sb_cg* s, int on)
   s->fusepWant = on < 0 ? -1 : on != 0;
   s->fusepPlan = -1;
 }
-int sb_cg_fuse_p(sb_cg* s) { return fusep_plan(s) ? 1 : 0; }
+int sb_cg_fuse_p(sb_cg* s)
+{
+  if (s->seqLatched < 0) apply_dot_order(s);
+  return fusep_plan(s) ? 1 : 0;
+}
 
 void sb_cg_set_graph(sb_cg* s, int use_graph)
 {
@@ -438,14 +472,16 @@ static bool spmv_can_fuse_dot(const sb_cg* s)
 template <int MODE> static void scalar_launch(sb_cg* s, int defer_x, const double* q, int l1)
 {
   if (!q) q = s->partials;
+  uint32_t m = s->nPartials;
+  if (s->seqLatched > 0) m = 1, l1 = 1; // (seq: the rank's whole sum is q[0], cg_dot)
   if (multi_rank() && p2p_dots()) { // local reduce, in-kernel all-reduce and scalar step in ONE launch
-    hipLaunchKernelGGL((cg_scalar_p2p_k<MODE>), dim3(1), dim3(1024), 0, g.stream, s->nPartials, q,
+    hipLaunchKernelGGL((cg_scalar_p2p_k<MODE>), dim3(1), dim3(1024), 0, g.stream, m, q,
         s->S, s->rr_hist, s->pAp_hist, defer_x, (const P2PView*)g.p2pView, ++g.p2pSeq, l1,
         (const int*)(s->halo && s->halo->p2p ? s->halo->err : nullptr));
     HIP_CHECK(hipGetLastError());
     return;
   }
-  hipLaunchKernelGGL((cg_scalar_k<MODE, true>), dim3(1), dim3(1024), 0, g.stream, s->nPartials, q,
+  hipLaunchKernelGGL((cg_scalar_k<MODE, true>), dim3(1), dim3(1024), 0, g.stream, m, q,
       s->S, s->rr_hist, s->pAp_hist, multi_rank() ? 1 : 0, defer_x, l1);
   HIP_CHECK(hipGetLastError());
   if (multi_rank()) {
@@ -608,6 +644,14 @@ static void spmv_time_end(sb_cg* s)
   else spmv_event(s);
 }
 
+// a dot of the reference's op list into `partials`: the tree order's level-0 partials, or (seq) the rank's sequential sum over
+// its nr rows in original row order as the one value the scalar step reads (scalar_launch)
+static void cg_dot(sb_cg* s, const double* a, const double* b, const int* stop)
+{
+  if (s->seqLatched > 0) launch_dot_seq(s->nr, a, b, s->A->permuted ? s->A->oldToNew : nullptr, s->partials, stop);
+  else launch_dot_spans(0, s->nr, a, b, nullptr, nullptr, s->S, s->partials, stop);
+}
+
 // Ap = A p and the level-0 partials of p.Ap (src/CGSolver.c:123-125): fused into the SpMV epilogue
 // where the kernel is wave-per-chunk, otherwise SpMV then a dot pass
 static void spmv_and_pAp(sb_cg* s, const int* stop)
@@ -630,7 +674,7 @@ static void spmv_and_pAp(sb_cg* s, const int* stop)
       hipLaunchKernelGGL(dot_l1_k, dim3(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * 2u, (nGroups + 15u) / 16u))), dim3(1024), 0,
           g.stream, n, (const double*)s->p, (const double*)s->Ap, s->partials, stop);
       HIP_CHECK(hipGetLastError());
-    } else launch_dot_spans(0, n, s->p, s->Ap, nullptr, nullptr, s->S, s->partials, stop);
+    } else cg_dot(s, s->p, s->Ap, stop);
     phase_mark(s, PH_DOT_PASS);
   }
 }
@@ -694,7 +738,7 @@ static void loop_body(sb_cg* s, int k)
     phase_mark(s, PH_P_UPDATE);
   } else {
     if (!s->fused) { // rtrans = r.r ; beta (:111-113)
-      launch_dot_spans(0, n, s->r, s->r, nullptr, nullptr, s->S, s->partials, stop);
+      cg_dot(s, s->r, s->r, stop);
       phase_mark(s, PH_DOT_PASS);
       scalar_launch<1>(s, 0, nullptr);
       mark(s, R_DDOT);
@@ -839,6 +883,9 @@ void sb_cg_start(sb_cg* s, int itermax, double eps)
   need_init();
   const uint32_t n = s->nr;
   s->started      = false;
+  s->seqLatched   = -1;
+  s->seqLatched   = cg_seq(s) ? 1 : 0; // the dot order, decided once per solve (cg_seq) ...
+  apply_dot_order(s);                  // ... and the op list it runs
   s->fusepLatched = fusep_plan(s) ? 1 : 0; // decided once per solve (fusep_plan)
   if (s->halo && s->halo->p2p && s->halo->push.p2pErr != &s->S->p2p_error) {
     // the push kernels of THIS solve also look at its control block's failure flag (poisoning: kernels.hip.h).  Set per solve,
@@ -874,7 +921,7 @@ void sb_cg_start(sb_cg* s, int itermax, double eps)
   } else {
     launch_waxpby(n, 1.0, s->b, -1.0, s->Ap, s->r, nullptr);
     mark(s, R_WAXPBY);
-    launch_dot_spans(0, n, s->r, s->r, nullptr, nullptr, s->S, s->partials, nullptr);
+    cg_dot(s, s->r, s->r, nullptr);
   }
   scalar_launch<0>(s, 0, nullptr);
   mark(s, R_DDOT);
@@ -949,6 +996,8 @@ int sb_cg_finish(sb_cg* s)
   }
   s->timing       = false;
   s->fusepLatched = -1; // the solve is over: the next sb_cg_start decides anew
+  s->seqLatched   = -1;
+  apply_dot_order(s); // (a dot order or fused level asked for during the solve)
   return h.iters + 1; // the value of k when the reference's for loop exits (:107,:140)
 }
 

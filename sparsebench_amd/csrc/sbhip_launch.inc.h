@@ -348,13 +348,43 @@ void sb_reduce_final(uint32_t m, const double* partials_dev, double* result_dev)
   HIP_CHECK(hipGetLastError());
 }
 
+// The process default dot order (include/sbhip.h: sb_dot_order): 0 the fixed tree order, 1 the reference's sequential sum
+// (dot_seq_k).  SB_DOT_ORDER=tree|seq, read on first use -- before sb_init too; anything else ends the process.
+static int g_dotOrder = -1; // -1: not read yet
+int sb_dot_order(void)
+{
+  if (g_dotOrder < 0) {
+    const char* e = getenv("SB_DOT_ORDER");
+    if (!e || !*e || strcmp(e, "tree") == 0) g_dotOrder = 0;
+    else if (strcmp(e, "seq") == 0) g_dotOrder = 1;
+    else SB_FATAL("SB_DOT_ORDER=%s: expected tree or seq", e);
+  }
+  return g_dotOrder;
+}
+void sb_set_dot_order(int order)
+{
+  if (order != 0 && order != 1) SB_FATAL("sb_set_dot_order(%d): expected 0 (tree) or 1 (seq)", order);
+  g_dotOrder = order;
+}
+
+// the reference's sequential sum (kernels.hip.h: dot_seq_k) into out[0]; perm: the caller's row order over permuted storage
+static void launch_dot_seq(uint32_t n, const double* a, const double* b, const uint32_t* perm, double* out, const int* stop)
+{
+  hipLaunchKernelGGL(dot_seq_k, dim3(1), dim3(1024), 0, g.stream, n, a, b, perm, out, stop);
+  HIP_CHECK(hipGetLastError());
+}
+
 void sb_ddot_async(uint32_t n, const double* x, const double* y, double* result_dev)
 {
   need_init();
-  const uint32_t m = (n + 255u) / 256u;
-  double* q        = scratch_partials(4 * (size_t)m);
-  sb_ddot_partials(n, x, y, q);
-  sb_reduce_final(m, q, result_dev);
+  if (sb_dot_order() == 1) {
+    launch_dot_seq(n, x, y, nullptr, result_dev, nullptr);
+  } else {
+    const uint32_t m = (n + 255u) / 256u;
+    double* q        = scratch_partials(4 * (size_t)m);
+    sb_ddot_partials(n, x, y, q);
+    sb_reduce_final(m, q, result_dev);
+  }
   if (multi_rank()) sb_comm_reduction(result_dev, 1);
 }
 

@@ -76,7 +76,7 @@ void ddot(const CG_UINT n, const CG_FLOAT* restrict x, const CG_FLOAT* restrict 
 {
   staged_vec sx = stage_in(x, n, 1);
   staged_vec sy = (y == x) ? sx : stage_in(y, n, 1);
-  *result       = sb_ddot(n, sx.dev, sy.dev); /* includes the SUM all-reduce (src/solver.c:60) */
+  *result       = sb_ddot(n, sx.dev, sy.dev); /* process default dot order; includes the SUM all-reduce (src/solver.c:60) */
   if (sy.staged && y != x) sb_free(sy.dev);
   if (sx.staged) sb_free(sx.dev);
 }
@@ -111,6 +111,8 @@ static int sbh_solve(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
     }
   }
   sbh_comm_attach_halo(comm, nr, oldToNewPerm);
+  /* the dot order is the process default (SB_DOT_ORDER / sb_set_dot_order): seq runs the reference's op list with its
+   * sequential ddot, and the history -- the lines printed below -- is then the reference's bit for bit */
   sb_cg* cg = sb_cg_create((const sb_matrix*)dev_matrix, (sb_halo*)comm->dev, b, xexact);
   const char* fused = getenv("SB_FUSED");
   const char* graph = getenv("SB_GRAPH");
@@ -149,7 +151,7 @@ static int sbh_solve(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
     _t[WAXPBY] += 1e-3 * ms[0], _t[SPMVM] += 1e-3 * ms[1], _t[DDOT] += 1e-3 * ms[2], _t[COMM] += 1e-3 * ms[3];
   } else {
     /* fused run: regions overlap inside kernels; attribute the loop to the SpMV row so
-     * the table still adds up (run with SB_FUSED=0 for the per-region split) */
+     * the table still adds up (run with SB_FUSED=0 or SB_DOT_ORDER=seq for the per-region split) */
     _t[SPMVM] += 1e-3 * sb_cg_loop_ms(cg);
   }
   sb_cg_free(cg);

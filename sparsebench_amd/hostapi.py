@@ -195,7 +195,7 @@ class Problem:
 class CG:
     """solveCG on the GPU (sb_cg_*): state in HBM, loop without host round trips."""
 
-    def __init__(self, problem, fused=True, graph=False, fuse_p=-1, fuse_alpha=-1, fuse_beta=-1):
+    def __init__(self, problem, fused=True, graph=False, fuse_p=-1, fuse_alpha=-1, fuse_beta=-1, dot_order=None):
         self.L = capi.load()
         self.problem = problem
         b, xe = problem.rhs()
@@ -208,7 +208,23 @@ class CG:
         self.L.sb_cg_set_fuse_p(self.ptr, int(fuse_p))  # -1: default; 1 / 0: the p update inside the SpMV where possible / not
         self.L.sb_cg_set_fuse_alpha(self.ptr, int(fuse_alpha))  # -1: default; 1 / 0: the alpha step inside the r update (one rank) / not
         self.L.sb_cg_set_fuse_beta(self.ptr, int(fuse_beta))  # the beta step at the head of the p update where that is a launch of its own
+        if dot_order is not None:  # None: the process default (sb_dot_order, SB_DOT_ORDER)
+            self.set_dot_order(dot_order)
         self.itermax = 0
+
+    DOT_ORDERS = {"tree": 0, "seq": 1, None: -1}
+
+    def set_dot_order(self, order):
+        """"tree" / 0: the fixed tree order; "seq" / 1: the reference's sequential sum (validation, the reference's op
+        list); None / -1: the process default.  Takes effect with the next solve / start."""
+        code = self.DOT_ORDERS[order] if order in self.DOT_ORDERS else int(order)
+        if code not in (-1, 0, 1):
+            raise ValueError("dot_order %r: expected 'tree', 'seq' or None" % (order,))
+        self.L.sb_cg_set_dot_order(self.ptr, code)
+
+    def dot_order(self):
+        """"tree" or "seq": the order the solve uses"""
+        return "seq" if self.L.sb_cg_dot_order(self.ptr) else "tree"
 
     def vector_phase(self):
         """spans per wave of the one-launch vector phase, 0 if the solver uses the separate launches"""
