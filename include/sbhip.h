@@ -121,18 +121,13 @@ double sb_matrix_spmv_bytes(const sb_matrix* m);
  * Stays in force until replaced (n = 0 clears); uploads whose nc - nr differs from n ignore it. */
 void sb_set_external_ids(const uint32_t* global_ids, uint32_t n);
 int sb_matrix_pack_level(const sb_matrix* m);
-/* select the SpMV kernel at run time.  The product has two: 0 the reference-layout stream, 5 the masked row programs
- * (level 6) where the matrix has them (the default then); any other request falls to the next lower of the two.
- * Lab builds (sb_lab_build) also run the intermediate levels as kernels of their own: 1 packed stream with x
- * gathered through the cache, 2 packed stream with each workgroup's x window staged in LDS
- * (built when every tile's window fits; SB_PACK=2 stops at mode 1), 3 one-byte pattern
- * codes naming (value, window-slot delta) pairs + LDS window (built when every tile has
- * <= 255 distinct pairs; SB_PACK=3 stops at mode 2), 5 the same tiles with every chunk stored as a
- * masked row program (built when >= 98 % of the chunks' rows are sub-sequences of a row of their tile;
- * SB_PACK=5 stops at mode 3; there is no mode 4).  Clamped to what the matrix has: a mode it lacks
- * falls to the next lower one.  Default = 5 where built, else 3 for matrices of more than one round of
- * resident workgroups (8 tiles of 256 rows per CU) and 2 below that.  All modes give bit-identical results. */
-/* CRS matrices: 0 = native CRS kernel, 3 / 5 = product through a device-private Sell-64-1 pattern mirror whose
+/* select the SpMV kernel at run time.  There are two: 0 the reference-layout stream, 5 the masked row programs (level 6:
+ * every chunk of a tile stored as a masked row program; built when >= 98 % of the chunks' rows are sub-sequences of a row
+ * of their tile; SB_PACK < 6 builds none) where the matrix has them (the default then).  Any request below 5, or 5 on a
+ * matrix without row programs, selects 0.  Levels 1-5 are still built on the way to level 6 (sb_matrix_pack_level and the
+ * counts below report them); their own kernels were measured slower and removed.  Both kernels give
+ * bit-identical results. */
+/* CRS matrices: 0 = native CRS kernel, 5 = product through a device-private Sell-64-1 pattern mirror whose
  * padding is not added (exactly the CRS loop's sums); built when the matrix has repeating row patterns. */
 void sb_matrix_use_packed(sb_matrix* m, int mode);
 int sb_matrix_packed_mode(const sb_matrix* m);
@@ -163,9 +158,8 @@ void sb_spmv_native(const sb_matrix* m, const double* x, double* y);
  * DESIGN 4.3 (rows of the device's order) -- what the CG loop does for p . Ap.  Returns which values partials_dev holds:
  *   0  nothing: the selected kernel has no fused dot (Sell-C-sigma with C != 64, native CRS);
  *   2  LEVEL-1 values, one per aligned 256 rows = ((q0 + q1) + q2) + q3 of four level-0 partials: ceil(nr / 256) doubles
- *      (the product's kernels: reference-layout Sell-64 stream and masked row programs -- a block / tile combines its
- *      chunks itself, so the scalar step that follows reads a quarter of the bytes through its single CU);
- *   1  level-0 partials, one per 64 rows: 4 * ceil(nr / 256) doubles (lab-only kernels).
+ *      (reference-layout Sell-64 stream and masked row programs -- a block / tile combines its chunks itself, so the
+ *      scalar step that follows reads a quarter of the bytes through its single CU).
  * partials_dev: 4 * ceil(nr / 256) doubles, zero-filled by the caller (entries behind the last group stay +0.0). */
 int sb_spmv_native_dot(const sb_matrix* m, const double* x, double* y, double* partials_dev);
 /* vector <-> permuted order of an SCS matrix: out[new] = in[old] / out[old] = in[new] */
@@ -285,13 +279,8 @@ sb_cg* sb_cg_create(const sb_matrix* m, sb_halo* halo, const double* b_host,
 void sb_cg_free(sb_cg* s);
 void sb_cg_debug_ptrs(const sb_cg* s, unsigned long long out[8]); /* lab: device addresses of r, p, p', Ap, x, b, partials, control block */
 /* fused = 0: the reference's op list (waxpby, spMVM, ddot as separate launches); 1 (default): dots fused into the
- * SpMV / update kernels (5 launches per loop body); 2: additionally the vector phase of a body
- * (alpha | x, r update + r.r | beta, loop test | p update; src/CGSolver.c:124-128 and :107-116) as ONE launch
- * whose workgroups wait for each other -- used when this rank has its GPU to itself (SB_SHARED_GPU=1 says it
- * has not), the all-reduce is the in-kernel one (or there is one rank) and the rows fit the resident grid's
- * registers; otherwise it behaves as 1; 3: the two scalar steps ride in front of their consumers (workgroup 0 of the
- * r / p update takes them and publishes alpha / beta through a flag; 3 launches per body; one rank only, otherwise as 1).  (2 and 3 measured slower than 1 at 128^3: sbhip_cg.inc.h.)  Same bits in every mode. */
-void sb_cg_set_fused(sb_cg* s, int fused);
+ * SpMV / update kernels (5 launches per loop body, fewer with the folds below).  Same bits in both. */
+void sb_cg_set_fused(sb_cg* s, int fused); /* every non-zero level is 1 (levels 2 and 3 were removed: DESIGN 4.6) */
 /* The dot order of this solver's dots (r.r, p.Ap), src/solver.c:41-62: 0 = tree, 1 = seq (see sb_set_dot_order), -1 =
  * the process default (sb_dot_order; the initial setting).  seq runs the reference's op list (fused = 0: the region
  * table of sb_cg_region_ms is filled, sb_cg_launches_per_body is 0, sb_cg_fuse_p 0) with every dot as the sequential
@@ -301,10 +290,9 @@ void sb_cg_set_fused(sb_cg* s, int fused);
  * uses (or, outside a solve, will use). */
 void sb_cg_set_dot_order(sb_cg* s, int order);
 int sb_cg_dot_order(const sb_cg* s);
-/* spans per wave of the one-launch vector phase the solver will use, 0 if it will not use it */
-int sb_cg_vector_phase(sb_cg* s);
-/* launches per loop body the loop will use: 5 (p update | SpMV | alpha | r update | beta), 3 (fused = 3), 2 (fused = 2);
- * 0 for the reference's op list */
+int sb_cg_vector_phase(sb_cg* s); /* always 0: the one-launch vector phase was removed */
+/* launches per loop body the loop will use: 5 (p update | SpMV | alpha | r update | beta), 4 with the p update inside the
+ * SpMV, one fewer for each scalar step folded into its consumer; 0 for the reference's op list */
 int sb_cg_launches_per_body(sb_cg* s);
 /* several ranks: the count above includes the halo kernels (peer-mapped push: +1, or +0 riding in the SpMV launch; pack
  * kernel in front of a send / recv group: +1) and, without the in-kernel all-reduce, one more kernel per dot (+2);
@@ -329,7 +317,7 @@ void sb_cg_set_fuse_alpha(sb_cg* s, int on);
  * (as for alpha: sb_cg_set_fuse_alpha).  Every sb_cg_run_iters call still leaves the loop state complete (a step left owing at
  * its end is taken by a launch of its own).  on = 1 / 0, -1 = default (SB_FUSE_BETA, else on).  Same bits. */
 void sb_cg_set_fuse_beta(sb_cg* s, int on);
-void sb_cg_set_graph(sb_cg* s, int use_graph);
+void sb_cg_set_graph(sb_cg* s, int use_graph); /* accepts and ignores use_graph: hipGraph replay was removed */
 /* Runs solveCG's whole loop without host synchronisation; returns k exactly as
  * the reference does (src/CGSolver.c:140).  Blocking. */
 int sb_cg_solve(sb_cg* s, int itermax, double eps);
@@ -376,11 +364,7 @@ void sb_cg_counters(const sb_cg* s, int out[5]);
 double sb_debug_stream_read_gbs(size_t bytes, int reps);
 
 const char* sb_version(void);
-/* 1: a lab build (-DSB_LAB, `make lab`): the product plus the alternatives that were measured slower and are kept for
- * the record -- compressed-mirror levels 1-5 as SpMV kernels of their own (sb_matrix_use_packed 1-3),
- * sb_cg_set_fused 2 / 3, sb_cg_set_graph, SB_HALO_OVERLAP.  0: the product, in which those requests fall back to
- * what ships (modes 0 / 5, fused 0 / 1, no graph). */
-int sb_lab_build(void);
+int sb_lab_build(void); /* always 0: there is one build (the lab build was removed) */
 
 #ifdef __cplusplus
 }

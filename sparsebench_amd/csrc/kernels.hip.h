@@ -725,7 +725,7 @@ __global__ __launch_bounds__(1024) void dot_l1_k(uint32_t n, const double* __res
 // ALPHA (one rank, 1024-thread workgroups, the p.Ap producer emits level-1 values): the alpha step rides in this launch --
 // EVERY workgroup reduces the m level-1 values of p.Ap itself (reduce_final_1024: the canonical order, so all of them
 // hold the same bits), divides, and goes on; workgroup 0 also records the step in the control block (cg_apply<2>).  Nobody
-// waits for anybody -- unlike the lead kernels of `fused = 3`, where workgroup 0 published and the others polled --, the
+// waits for anybody -- unlike the lead kernels once tried, where workgroup 0 published and the others polled --, the
 // price is m * 8 bytes of L2 reads per workgroup (64 KB at 128^3, 512 workgroups) behind the first group's r / Ap loads,
 // which are already in flight.  One launch and its boundary fewer per loop body; same operations, same order, same bits.
 // ALPHA = 2 (several ranks on the communicator's collectives): p.Ap is already reduced and all-reduced into S->local by the
@@ -1163,397 +1163,6 @@ __global__ __launch_bounds__(1024) void cg_scalar_p2p_k(uint32_t m, const double
   }
   if (threadIdx.x == 0) cg_apply<MODE>(S, in, total, rr_hist, pAp_hist, defer_x);
 }
-
-// =============================================================================
-// The vector phase of a CG body as ONE launch (cg_vector_phase_k): alpha | x, r update + r.r | beta, loop
-// test | p update -- src/CGSolver.c:124-128 of body k and :107-116 of body k+1.  As separate launches these
-// are four dependent kernels (two of them single-workgroup scalar steps); a kernel boundary on this part
-// costs ~4 us (eight L2s to write back and invalidate), the four kernels move 134 MB, and r travels to memory
-// and back between them.  Here every thread keeps its elements of r, p, x, Ap in registers across the
-// two scalar steps; the steps themselves are taken by workgroup 0 while the others wait on a flag:
-//   A  all: load r, Ap, p, x.   WG 0: levels 1-2 of p.Ap (partials written by the SpMV), [all-reduce],
-//      alpha; publishes alpha.
-//   B  all: r -= alpha Ap, x += alpha p (stored), level-0 partials of r.r (stored), then count in.
-//   C  WG 0: once every workgroup has counted in: levels 1-2 of r.r, [all-reduce], beta and the loop test;
-//      publishes beta and the stop flag.
-//   D  all: p = r + beta p (unless the loop has ended).
-// The arithmetic per element and the dot order are those of the separate kernels: same bits.
-// What crosses workgroups inside the launch (partials, alpha, beta, the flags, the counter) travels by
-// agent-scope relaxed atomics -- on this part they bypass the XCD-private L2s -- ordered by "all my stores are
-// acknowledged" (s_waitcnt vmcnt(0)) in front of the flag / the count; no L2 write-back fence anywhere.
-// The grid is sized so that every workgroup is resident (the waits would otherwise never end); all waits
-// are bounded by a wall-clock timeout that raises VPhase::error (the host reports it at the end of the solve).
-// =============================================================================
-struct VPhase { // device control block, zeroed once
-  unsigned long long arrived;  // workgroups that have finished phase B, over all launches
-  unsigned long long launches; // finished launches (the next launch's sequence number - 1)
-  unsigned long long flagA, alphaBits;
-  unsigned long long flagB, betaBits, stopB;
-  int error;
-};
-
-#ifdef SB_LAB // the one-launch vector phase and the lead kernels: measured slower than the five launches; lab builds only
-
-__device__ __forceinline__ unsigned long long vp_load(const unsigned long long* p)
-{
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void vp_store(unsigned long long* p, unsigned long long v)
-{
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void vp_stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// thread 0 of the workgroup: wait until *flag >= want (bounded); false on timeout
-__device__ __forceinline__ bool vp_wait(const unsigned long long* flag, unsigned long long want, long long timeoutTicks)
-{
-  const long long t0 = wall_clock64();
-  while (vp_load(flag) < want) {
-    if (wall_clock64() - t0 > timeoutTicks) return false;
-    __builtin_amdgcn_s_sleep(2);
-  }
-  return true;
-}
-
-// reduce_final_1024 on partials written during THIS launch by other workgroups (agent-scope loads)
-__device__ __forceinline__ double reduce_final_1024_coherent(uint32_t m, const double* q, double* lds16)
-{
-  auto l1 = [&](uint32_t i) {
-    const unsigned long long* w = reinterpret_cast<const unsigned long long*>(q) + 4u * (size_t)i;
-    const double a = __longlong_as_double((long long)vp_load(w)), b = __longlong_as_double((long long)vp_load(w + 1));
-    const double c = __longlong_as_double((long long)vp_load(w + 2)), d = __longlong_as_double((long long)vp_load(w + 3));
-    return ((a + b) + c) + d;
-  };
-  double s   = 0.0;
-  uint32_t i = threadIdx.x;
-  for (; i + 3u * 1024u < m; i += 4u * 1024u) { // 16 loads in flight (the same sequence of additions as reduce_final_1024)
-    double a[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) a[u] = l1(i + (uint32_t)u * 1024u);
-#pragma unroll
-    for (int u = 0; u < 4; u++) s = s + a[u];
-  }
-  for (; i < m; i += 1024u) s = s + l1(i);
-  s = butterfly64(s);
-  if ((threadIdx.x & 63u) == 0) lds16[threadIdx.x >> 6] = s;
-  __syncthreads();
-  double total = lds16[0];
-#pragma unroll
-  for (int w = 1; w < 16; w++) total = total + lds16[w];
-  return total;
-}
-
-// SP: spans (128 consecutive elements, two per lane) a wave keeps in registers; the host picks the
-// instantiation and a grid of resident workgroups with nSpans <= 16 * gridDim.x * SP.
-template <int SP, bool P2P>
-__global__ __launch_bounds__(1024) void cg_vector_phase_k(uint32_t n, double* r, double* p, const double* __restrict__ Ap,
-    double* x, CgScalars* S, const double* __restrict__ pApPartials, double* rrPartials, uint32_t m,
-    double* __restrict__ rr_hist, double* __restrict__ pAp_hist, VPhase* V, long long timeoutTicks, const P2PView* pv,
-    unsigned long long p2pSeq, int pApL1)
-{
-  __shared__ double lds16[16];
-  __shared__ double shVal;
-  __shared__ int shFlag; // 0 go on, 1 loop ended, 2 error
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = blockIdx.x * 16u + (threadIdx.x >> 6), nWaves = gridDim.x * 16u;
-  const uint32_t nSpans = ((n + 255u) >> 8) * 2u;
-  double2 rv[SP], av[SP], pw[SP], xv[SP];
-#pragma unroll
-  for (int k = 0; k < SP; k++) {
-    const uint32_t e = (wave + (uint32_t)k * nWaves) * 128u + lane * 2u;
-    rv[k] = av[k] = pw[k] = xv[k] = double2{ 0.0, 0.0 };
-    if (e + 1 < n) {
-      rv[k] = *reinterpret_cast<const double2*>(r + e), av[k] = *reinterpret_cast<const double2*>(Ap + e);
-      pw[k] = *reinterpret_cast<const double2*>(p + e), xv[k] = *reinterpret_cast<const double2*>(x + e);
-    } else if (e < n) {
-      rv[k].x = r[e], av[k].x = Ap[e], pw[k].x = p[e], xv[k].x = x[e];
-    }
-  }
-  const int stopped            = S->stop;
-  const unsigned long long seq = V->launches + 1ull;
-  if (stopped) return; // every workgroup sees the same flag: it only changes in phase C, after all have read it
-  // ---- A: alpha -------------------------------------------------------------------------------------
-  if (blockIdx.x == 0) {
-    double total = reduce_final_1024(m, pApPartials, lds16, pApL1);
-    __syncthreads();
-    if (P2P) total = p2p_allreduce_sum(pv, total, p2pSeq, lds16, &S->p2p_error);
-    if (threadIdx.x == 0) {
-      cg_apply<2>(S, total, rr_hist, pAp_hist, 0);
-      vp_store(&V->alphaBits, (unsigned long long)__double_as_longlong(S->alpha));
-      vp_stores_done();
-      vp_store(&V->flagA, seq);
-    }
-  }
-  if (threadIdx.x == 0) {
-    const bool ok = vp_wait(&V->flagA, seq, timeoutTicks);
-    shVal  = __longlong_as_double((long long)vp_load(&V->alphaBits));
-    shFlag = ok ? 0 : 2;
-  }
-  __syncthreads();
-  if (shFlag == 2) { // (uniform per workgroup) a wait timed out: not every workgroup is running
-    if (threadIdx.x == 0) atomicExch(&V->error, 1), S->stop = 1; // (stop: the bodies already enqueued return at once)
-    return;
-  }
-  const double alpha = shVal, nalpha = -alpha;
-  // ---- B: x, r, level 0 of r.r ------------------------------------------------------------------------
-#pragma unroll
-  for (int k = 0; k < SP; k++) {
-    const uint32_t sp = wave + (uint32_t)k * nWaves, e = sp * 128u + lane * 2u;
-    double t = 0.0;
-    if (e + 1 < n) {
-      xv[k].x = xv[k].x + alpha * pw[k].x, xv[k].y = xv[k].y + alpha * pw[k].y;
-      rv[k].x = rv[k].x + nalpha * av[k].x, rv[k].y = rv[k].y + nalpha * av[k].y;
-      *reinterpret_cast<double2*>(x + e) = xv[k];
-      *reinterpret_cast<double2*>(r + e) = rv[k];
-      t = rv[k].x * rv[k].x + rv[k].y * rv[k].y;
-    } else if (e < n) {
-      xv[k].x = xv[k].x + alpha * pw[k].x;
-      rv[k].x = rv[k].x + nalpha * av[k].x;
-      x[e] = xv[k].x, r[e] = rv[k].x;
-      t    = rv[k].x * rv[k].x + 0.0;
-    }
-    t = butterfly32(t);
-    if (sp < nSpans && (lane & 31u) == 0)
-      vp_store(reinterpret_cast<unsigned long long*>(rrPartials) + sp * 2u + (lane >> 5), (unsigned long long)__double_as_longlong(t));
-  }
-  vp_stores_done();
-  __syncthreads(); // (also: nobody overwrites shVal / shFlag before everybody has read them)
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(&V->arrived, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  // ---- C: beta, loop test ------------------------------------------------------------------------------
-  if (blockIdx.x == 0) {
-    if (threadIdx.x == 0) shFlag = vp_wait(&V->arrived, (unsigned long long)gridDim.x * seq, timeoutTicks) ? 0 : 2;
-    __syncthreads();
-    if (shFlag != 2) {
-      double total = reduce_final_1024_coherent(m, rrPartials, lds16);
-      __syncthreads();
-      if (P2P) total = p2p_allreduce_sum(pv, total, p2pSeq + 1ull, lds16, &S->p2p_error);
-      if (threadIdx.x == 0) {
-        cg_apply<1>(S, total, rr_hist, pAp_hist, 0);
-        if (P2P && __hip_atomic_load(&S->p2p_error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) S->stop = 1;
-        vp_store(&V->betaBits, (unsigned long long)__double_as_longlong(S->beta));
-        vp_store(&V->stopB, (unsigned long long)S->stop);
-        vp_stores_done();
-        vp_store(&V->flagB, seq);
-        V->launches = seq;
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const bool ok = vp_wait(&V->flagB, seq, timeoutTicks);
-    shVal  = __longlong_as_double((long long)vp_load(&V->betaBits));
-    shFlag = !ok ? 2 : vp_load(&V->stopB) ? 1 : 0;
-  }
-  __syncthreads();
-  if (shFlag == 2) {
-    if (threadIdx.x == 0) atomicExch(&V->error, 1), S->stop = 1; // (stop: the bodies already enqueued return at once)
-    return;
-  }
-  if (shFlag == 1) return; // the loop has ended: p stays (the separate p update returns on the stop flag too)
-  // ---- D: p = r + beta p ---------------------------------------------------------------------------------
-  const double beta = shVal;
-#pragma unroll
-  for (int k = 0; k < SP; k++) {
-    const uint32_t e = (wave + (uint32_t)k * nWaves) * 128u + lane * 2u;
-    if (e + 1 < n) {
-      double2 o;
-      o.x = rv[k].x + beta * pw[k].x, o.y = rv[k].y + beta * pw[k].y;
-      *reinterpret_cast<double2*>(p + e) = o;
-    } else if (e < n) {
-      p[e] = rv[k].x + beta * pw[k].x;
-    }
-  }
-}
-
-#endif // SB_LAB (vector phase)
-
-// =============================================================================
-// Scalar steps inside their consumers ("lead" kernels): 5 -> 3 launches per CG body.
-// (One rank only: with several ranks the combination with the in-kernel all-reduce and the in-SpMV halo wait timed out
-// in the two-ranks-on-one-GPU test and, being slower anyway, was not pursued.)
-// The alpha step (levels 1-2 of p.Ap, alpha = rr / pAp) needs only the partials the SpMV has
-// written, and its only consumers are the kernel that updates r -- so workgroup 0 of THAT kernel takes the step
-// while the other workgroups already have their first loads in flight, then publishes alpha through a flag
-// (agent-scope relaxed atomics, vp_* above) on which the others wait.  The same for the beta step / loop test in
-// front of the p update.  Unlike cg_vector_phase_k nobody waits for ALL workgroups, only for workgroup 0, which is
-// dispatched first: no residency requirement (the launch counter moves when the LAST workgroup leaves, lead_leave), the
-// reads and writes of the kernel still overlap freely, and the
-// ~4 us of a dependent single-workgroup launch become the ~2 us the reduction itself takes.
-// 1024 threads per workgroup, so that workgroup 0 IS the reduction workgroup of the canonical dot.
-// =============================================================================
-struct Lead { // device control of one lead kernel, zeroed once
-  unsigned long long flag, valueBits, stop;
-  unsigned long long launches; // finished launches: the next one's sequence number - 1
-  unsigned long long done;     // workgroups of the running launch that have read `launches` and left (lead_leave)
-  int error;
-};
-
-#ifdef SB_LAB
-
-// Every workgroup reads Ld->launches when it starts, and a grid of more workgroups than the device holds starts in
-// rounds: the counter may therefore only move once EVERY workgroup of the launch has read it.  The last workgroup to
-// leave advances it (round 2 had workgroup 0 do so in the middle of the launch: a workgroup dispatched after that
-// read the new value, waited for a flag nobody would publish and ran into the time-out -- ADVICE r2).
-__device__ __forceinline__ void lead_leave(Lead* Ld, unsigned long long seq)
-{
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long prev = __hip_atomic_fetch_add(&Ld->done, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev == (unsigned long long)gridDim.x - 1ull) {
-      vp_store(&Ld->done, 0ull);
-      vp_store(&Ld->launches, seq);
-    }
-  }
-}
-
-// workgroup 0: total = the finished dot product.  Everybody returns the published (value, stop); false: timeout
-template <int MODE>
-__device__ __forceinline__ bool lead_step(CgScalars* S, const double* __restrict__ partials, uint32_t m,
-    double* __restrict__ rr_hist, double* __restrict__ pAp_hist, Lead* Ld, unsigned long long seq, long long timeoutTicks,
-    double* lds16, double* shVal, int* shFlag, double& value, int& stop, int l1 = 0)
-{
-  if (blockIdx.x == 0) {
-    const double total = reduce_final_1024(m, partials, lds16, l1);
-    if (threadIdx.x == 0) {
-      cg_apply<MODE>(S, total, rr_hist, pAp_hist, 1);
-      vp_store(&Ld->valueBits, (unsigned long long)__double_as_longlong(MODE == 2 ? S->alpha : S->beta));
-      vp_store(&Ld->stop, (unsigned long long)S->stop);
-      vp_stores_done();
-      vp_store(&Ld->flag, seq);
-    }
-  }
-  if (threadIdx.x == 0) {
-    const bool ok = vp_wait(&Ld->flag, seq, timeoutTicks);
-    *shVal  = __longlong_as_double((long long)vp_load(&Ld->valueBits));
-    *shFlag = !ok ? 2 : vp_load(&Ld->stop) ? 1 : 0;
-    if (!ok) atomicExch(&Ld->error, 1), S->stop = 1;
-  }
-  __syncthreads();
-  value = *shVal, stop = *shFlag;
-  return *shFlag != 2;
-}
-
-// alpha step + r -= alpha Ap + level-0 partials of r.r   (src/CGSolver.c:124-126, :128, :112)
-// = cg_scalar_k<2> followed by the r update (cg_update_r_k's arithmetic, level-0 partials), element for element
-__global__ __launch_bounds__(1024) void cg_lead_r_k(uint32_t n, const double* __restrict__ Ap, double* r, CgScalars* S,
-    const double* __restrict__ pApPartials, double* __restrict__ rrPartials, uint32_t m, double* __restrict__ rr_hist,
-    double* __restrict__ pAp_hist, Lead* Ld, long long timeoutTicks, int pApL1)
-{
-  __shared__ double lds16[16];
-  __shared__ double shVal;
-  __shared__ int shFlag;
-  const uint32_t lane   = threadIdx.x & 63u;
-  const uint32_t nSpans = ((n + 255u) >> 8) * 2u;
-  const uint32_t nWaves = gridDim.x * (blockDim.x >> 6);
-  uint32_t s            = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  // the first two spans' loads go in flight in front of the step
-  const bool pair0 = s + nWaves < nSpans && (s + nWaves) * 128u + 128u <= n; // wave-uniform
-  double2 r0 = { 0.0, 0.0 }, a0 = r0, r1 = r0, a1 = r0;
-  if (pair0) {
-    const uint32_t e0 = s * 128u + lane * 2u, e1 = (s + nWaves) * 128u + lane * 2u;
-    r0 = *reinterpret_cast<const double2*>(r + e0), a0 = *reinterpret_cast<const double2*>(Ap + e0);
-    r1 = *reinterpret_cast<const double2*>(r + e1), a1 = *reinterpret_cast<const double2*>(Ap + e1);
-  }
-  const int stopped            = S->stop;
-  const unsigned long long seq = vp_load(&Ld->launches) + 1ull;
-  if (stopped) return; // (the same decision in every workgroup: nobody counts, the counter stays)
-  double alpha;
-  int st;
-  if (!lead_step<2>(S, pApPartials, m, rr_hist, pAp_hist, Ld, seq, timeoutTicks, lds16, &shVal, &shFlag, alpha, st, pApL1)) return; // (fatal at the host)
-  const double nalpha = -alpha;
-  bool have = pair0;
-  while (have) {
-    const uint32_t e0 = s * 128u + lane * 2u, e1 = (s + nWaves) * 128u + lane * 2u;
-    r0.x = r0.x + nalpha * a0.x, r0.y = r0.y + nalpha * a0.y;
-    r1.x = r1.x + nalpha * a1.x, r1.y = r1.y + nalpha * a1.y;
-    *reinterpret_cast<double2*>(r + e0) = r0;
-    *reinterpret_cast<double2*>(r + e1) = r1;
-    const double t0 = butterfly32(r0.x * r0.x + r0.y * r0.y), t1 = butterfly32(r1.x * r1.x + r1.y * r1.y);
-    if ((lane & 31u) == 0) rrPartials[s * 2u + (lane >> 5)] = t0, rrPartials[(s + nWaves) * 2u + (lane >> 5)] = t1;
-    s += 2u * nWaves;
-    have = s + nWaves < nSpans && (s + nWaves) * 128u + 128u <= n;
-    if (have) {
-      const uint32_t f0 = s * 128u + lane * 2u, f1 = (s + nWaves) * 128u + lane * 2u;
-      r0 = *reinterpret_cast<const double2*>(r + f0), a0 = *reinterpret_cast<const double2*>(Ap + f0);
-      r1 = *reinterpret_cast<const double2*>(r + f1), a1 = *reinterpret_cast<const double2*>(Ap + f1);
-    }
-  }
-  for (; s < nSpans; s += nWaves) { // what the paired loop left over
-    const uint32_t e = s * 128u + lane * 2u;
-    double t         = 0.0;
-    if (e + 1 < n) {
-      double2 rv       = *reinterpret_cast<double2*>(r + e);
-      const double2 av = *reinterpret_cast<const double2*>(Ap + e);
-      rv.x = rv.x + nalpha * av.x;
-      rv.y = rv.y + nalpha * av.y;
-      *reinterpret_cast<double2*>(r + e) = rv;
-      t = rv.x * rv.x + rv.y * rv.y;
-    } else if (e < n) {
-      const double rn = r[e] + nalpha * Ap[e];
-      r[e]            = rn;
-      t               = rn * rn + 0.0;
-    }
-    t = butterfly32(t);
-    if ((lane & 31u) == 0) rrPartials[s * 2u + (lane >> 5)] = t;
-  }
-  lead_leave(Ld, seq);
-}
-
-// beta step / loop test + p = r + beta p + the x update the previous body owes   (:107-116, :127)
-// = cg_scalar_k<1> (defer_x) followed by cg_update_p(which = 0, x), element for element
-__global__ __launch_bounds__(1024) void cg_lead_p_k(uint32_t n, const double* __restrict__ r, double* p, double* x,
-    CgScalars* S, const double* __restrict__ rrPartials, uint32_t m, double* __restrict__ rr_hist,
-    double* __restrict__ pAp_hist, Lead* Ld, long long timeoutTicks)
-{
-  __shared__ double lds16[16];
-  __shared__ double shVal;
-  __shared__ int shFlag;
-  const uint32_t n2     = n >> 1;
-  const uint32_t stride = gridDim.x * blockDim.x;
-  const double2* r2     = reinterpret_cast<const double2*>(r);
-  double2* p2           = reinterpret_cast<double2*>(p);
-  double2* x2           = reinterpret_cast<double2*>(x);
-  uint32_t i            = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t last   = n2 ? n2 - 1u : 0u;
-  double2 a0 = { 0.0, 0.0 }, b0 = a0, x0 = a0, a1 = a0, b1 = a0, x1 = a0;
-  auto load = [&](uint32_t j, double2& a, double2& b, double2& xv) { a = r2[j], b = p2[j], xv = x2[j]; };
-  if (n2) load(min(i, last), a0, b0, x0), load(min(i + stride, last), a1, b1, x1);
-  const int stopped            = S->stop;
-  const double alpha           = S->alpha; // of the previous body: written by the kernel before this one
-  const unsigned long long seq = vp_load(&Ld->launches) + 1ull;
-  if (stopped) return;
-  double beta;
-  int st;
-  if (!lead_step<1>(S, rrPartials, m, rr_hist, pAp_hist, Ld, seq, timeoutTicks, lds16, &shVal, &shFlag, beta, st)) return;
-  if (st) { // the loop has ended: p stays, the x update stays owed (cg_x_finalize)
-    lead_leave(Ld, seq);
-    return;
-  }
-  auto finish = [&](uint32_t j, const double2& a, const double2& b, double2 xv) {
-    xv.x = xv.x + alpha * b.x;
-    xv.y = xv.y + alpha * b.y;
-    x2[j] = xv;
-    double2 o;
-    o.x = a.x + beta * b.x;
-    o.y = a.y + beta * b.y;
-    p2[j] = o;
-  };
-  for (; i < n2; i += 2u * stride) {
-    const bool second = i + stride < n2;
-    finish(i, a0, b0, x0);
-    if (second) finish(i + stride, a1, b1, x1);
-    const uint32_t nx = i + 2u * stride;
-    if (nx < n2) load(nx, a0, b0, x0), load(min(nx + stride, last), a1, b1, x1);
-  }
-  if ((n & 1u) && blockIdx.x == 0 && threadIdx.x == 0) {
-    const double bb = p[n - 1];
-    x[n - 1]        = x[n - 1] + alpha * bb;
-    p[n - 1]        = r[n - 1] + beta * bb;
-  }
-  lead_leave(Ld, seq);
-}
-
-#endif // SB_LAB (lead kernels)
 
 // =============================================================================
 // permutation / halo helpers

@@ -10,9 +10,12 @@
 //   2  values   if the matrix holds <= 256 distinct fp64 bit patterns (stencils, graph
 //               Laplacians, ...): one byte per element indexing a dictionary held in LDS;
 //   3  windows  per tile (4 chunks = one workgroup) the x entries its rows touch are staged in
-//               LDS; the 16-bit column becomes a slot in that window (spmv_scs64_lds);
+//               LDS; the 16-bit column becomes a slot in that window;
 //   4  patterns one byte per element names a (value, slot delta) pair of the tile's class;
-//   5  rows     a chunk = one shared dominant row pattern + its few odd lanes (spmv_scs64_pat).
+//   5  rows     a chunk = one shared dominant row pattern + its few odd lanes.
+//
+// The kernel that multiplies is level 6 (the masked row programs, spmv_scs64_pat with MASKED): levels 1-5 are built on
+// the way to it, and their own kernels, measured slower at every size, were removed after 658dd0b.
 //
 // Levels 1-2: elements are regrouped so that a lane fetches four consecutive columns of its row
 // with one load: 8 B (or 16 B wide) of indices + 4 B of codes per lane per group,
@@ -24,7 +27,7 @@
 // Reference semantics of padding (column 0, value 0.0, src/matrix-SCS.c:146-155) are
 // kept: a padded element is encoded as the marker 0xFFFF and decodes to `padCol`
 // (column 0, renumbered like any other column when sigma > 1).  (The CRS format's mirror
-// uses the SKIPPAD instantiation of the level 4-5 kernel instead: CRS has no padding terms.)
+// uses the SKIPPAD instantiation of the pattern kernel instead: CRS has no padding terms.)
 #pragma once
 #include "kernels.hip.h"
 
@@ -121,90 +124,6 @@ __global__ __launch_bounds__(256) void pack_write_k(const uint32_t* __restrict__
   }
 }
 
-// ---- SpMV on the packed stream --------------------------------------------------------
-// One wavefront per chunk, lane = row, exactly as spmv_scs64; per group of four columns
-// a lane issues one index load, one code load (DICT) and four x gathers.  Two groups
-// (eight columns) are kept in flight.  (Deeper batching / prefetching variants were
-// measured slower: they cost occupancy, and the limiter is the gather instruction rate
-// of the vector cache, not the length of the dependency chain.)
-#ifdef SB_LAB // levels 1-2 as a kernel of their own: lab builds only (the BUILD of these levels feeds level 6 and stays)
-template <bool DICT, bool DOT>
-__global__ __launch_bounds__(256) void spmv_scs64_packed(const PackMeta* __restrict__ meta,
-    const uint32_t* __restrict__ idx, const uint32_t* __restrict__ codes,
-    const double* __restrict__ dict, const uint32_t* __restrict__ chunkPtr,
-    const double* __restrict__ val, const double* __restrict__ x, double* __restrict__ y, uint32_t nr,
-    uint32_t nChunks, uint32_t blocksPerXcd, uint32_t padCol, double* __restrict__ dotPartials,
-    const int* __restrict__ stop)
-{
-  __shared__ double sdict[256];
-  const int stopped      = stop ? *stop : 0;
-  const uint32_t nBlocks = (nChunks + 3u) >> 2;
-  const uint32_t lb      = blocksPerXcd ? xcd_block(blockIdx.x, blocksPerXcd) : blockIdx.x;
-  if (lb >= nBlocks || stopped) return; // uniform per workgroup
-  if (DICT) {
-    sdict[threadIdx.x] = dict[threadIdx.x];
-    __syncthreads();
-  }
-  const uint32_t chunk = __builtin_amdgcn_readfirstlane(lb * 4u + (threadIdx.x >> 6));
-  const uint32_t lane  = threadIdx.x & 63u;
-  const bool active    = chunk < nChunks;
-  double acc           = 0.0;
-  if (active) {
-    const PackMeta m     = meta[chunk];
-    const uint32_t cpv   = DICT ? 0u : chunkPtr[chunk];
-    const uint32_t len   = m.info & 0x7FFFFFFFu;
-    const bool wide      = m.info >> 31;
-    const uint32_t ng    = (len + 3u) >> 2;
-    const uint32_t* cstream = codes + (size_t)m.grp * 64 + lane;
-    const double* vraw      = val + cpv + lane;
-    if (!wide) {
-      const u32x2* istream = reinterpret_cast<const u32x2*>(idx) + (size_t)m.idxOff * 64 + lane;
-      for (uint32_t g = 0; g < ng; g += 2) {
-        const bool two = g + 1 < ng; // wave-uniform
-        const u32x2 i0 = stream_load(istream + (size_t)g * 64);
-        u32x2 i1       = u32x2{ PACK_PAD | (PACK_PAD << 16), PACK_PAD | (PACK_PAD << 16) };
-        uint32_t cw0 = 0, cw1 = 0;
-        if (two) i1 = stream_load(istream + (size_t)(g + 1) * 64);
-        if (DICT) {
-          cw0 = stream_load(cstream + (size_t)g * 64);
-          if (two) cw1 = stream_load(cstream + (size_t)(g + 1) * 64);
-        }
-        const uint32_t d[8] = { i0.x & 0xFFFFu, i0.x >> 16, i0.y & 0xFFFFu, i0.y >> 16,
-                                i1.x & 0xFFFFu, i1.x >> 16, i1.y & 0xFFFFu, i1.y >> 16 };
-        double xv[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) xv[k] = x[d[k] == PACK_PAD ? padCol : m.base + d[k]];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-          const uint32_t j = g * 4u + (uint32_t)k;
-          if (j < len) { // wave-uniform: columns beyond the chunk's width are not accumulated
-            const uint32_t cw = k < 4 ? cw0 : cw1;
-            const double vv   = DICT ? sdict[(cw >> (8u * (k & 3))) & 255u] : stream_load(vraw + (size_t)j * 64);
-            acc               = acc + vv * xv[k];
-          }
-        }
-      }
-    } else {
-      const u32x4* istream = reinterpret_cast<const u32x4*>(idx + (size_t)m.idxOff * 128) + lane;
-      for (uint32_t g = 0; g < ng; g++) {
-        const u32x4 i0      = stream_load(istream + (size_t)g * 64);
-        const uint32_t cw0  = DICT ? stream_load(cstream + (size_t)g * 64) : 0u;
-        const uint32_t d[4] = { i0.x, i0.y, i0.z, i0.w };
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const uint32_t j = g * 4u + (uint32_t)k;
-          if (j < len) {
-            const double vv = DICT ? sdict[(cw0 >> (8u * k)) & 255u] : stream_load(vraw + (size_t)j * 64);
-            acc             = acc + vv * x[d[k]];
-          }
-        }
-      }
-    }
-  }
-  if (active) spmv_epilogue<DOT>(chunk, lane, acc, x, y, nr, dotPartials);
-}
-#endif // SB_LAB
-
 // ---- level 3: the x window of a tile staged in LDS -------------------------------------
 // With 3 bytes per element the kernel is no longer HBM-bound; PMC shows the vector
 // memory pipe busy with the gathers (27 per row, ~16 L1 requests per wave-instruction,
@@ -263,89 +182,6 @@ __global__ __launch_bounds__(256) void pack_slots_k(const uint32_t* __restrict__
     o[0] = sl[0] | (sl[1] << 16), o[1] = sl[2] | (sl[3] << 16);
   }
 }
-
-#ifdef SB_LAB // level 3 as a kernel of its own: lab builds only
-template <bool DICT, bool DOT>
-__global__ __launch_bounds__(256) void spmv_scs64_lds(const PackMeta* __restrict__ meta,
-    const uint32_t* __restrict__ slots, const uint32_t* __restrict__ codes,
-    const double* __restrict__ dict, const uint32_t* __restrict__ chunkPtr,
-    const double* __restrict__ val, const uint32_t* __restrict__ tileSegPtr,
-    const TileSeg* __restrict__ segs, const double* __restrict__ x, double* __restrict__ y, uint32_t nr,
-    uint32_t nChunks, uint32_t blocksPerXcd, uint32_t padCol, double* __restrict__ dotPartials,
-    const int* __restrict__ stop)
-{
-  extern __shared__ __attribute__((aligned(16))) double lds[]; // [256 dict][window]
-  double* sdict = lds;
-  double* sx    = lds + 256;
-  constexpr int PF = 8; // groups prefetched before the window is staged (a 32-column chunk)
-  const int stopped     = stop ? *stop : 0;
-  const uint32_t tile   = blocksPerXcd ? xcd_block(blockIdx.x, blocksPerXcd) : blockIdx.x;
-  const uint32_t nTiles = (nChunks + 3u) >> 2;
-  if (tile >= nTiles || stopped) return; // uniform per workgroup
-  const uint32_t chunk = __builtin_amdgcn_readfirstlane(tile * 4u + (threadIdx.x >> 6));
-  const uint32_t lane  = threadIdx.x & 63u;
-  const bool active    = chunk < nChunks; // wave-uniform; inactive waves still help staging
-  PackMeta m           = { 0u, 0u, 0u, 0u };
-  if (active) m = meta[chunk];
-  const uint32_t cpv = (DICT || !active) ? 0u : chunkPtr[chunk];
-  const uint32_t len = m.info & 0x7FFFFFFFu;
-  const uint32_t ng  = (len + 3u) >> 2;
-  const u32x2* sstream    = reinterpret_cast<const u32x2*>(slots) + (size_t)m.grp * 64 + lane;
-  const uint32_t* cstream = codes + (size_t)m.grp * 64 + lane;
-  const double* vraw      = val + cpv + lane;
-  // 1. the chunk's slot/code stream goes in flight first (HBM latency) ...
-  u32x2 iv[PF];
-  uint32_t cw[PF];
-#pragma unroll
-  for (int gi = 0; gi < PF; gi++) {
-    iv[gi] = u32x2{ 0u, 0u }, cw[gi] = 0u;
-    if ((uint32_t)gi < ng) {
-      iv[gi] = stream_load(sstream + (size_t)gi * 64);
-      if (DICT) cw[gi] = stream_load(cstream + (size_t)gi * 64);
-    }
-  }
-  // 2. ... while the workgroup stages its x window (mostly L2 hits)
-  if (DICT) sdict[threadIdx.x] = dict[threadIdx.x];
-  if (threadIdx.x == 0) sx[0] = x[padCol]; // slot 0: what padding multiplies (src/matrix-SCS.c:151-155)
-  const uint32_t s0 = tileSegPtr[tile], s1 = tileSegPtr[tile + 1];
-  for (uint32_t s = s0; s < s1; s++) {
-    const TileSeg sg = segs[s];
-    for (uint32_t i = threadIdx.x; i < sg.len; i += 256u) sx[sg.lds + i] = x[sg.col + i];
-  }
-  __syncthreads();
-  if (!active) return;
-  // 3. accumulate left to right: x from LDS, values from the dictionary or the fp64 stream
-  double acc = 0.0;
-#pragma unroll
-  for (int gi = 0; gi < PF; gi++) {
-    if ((uint32_t)gi < ng) {
-      const uint32_t d[4] = { iv[gi].x & 0xFFFFu, iv[gi].x >> 16, iv[gi].y & 0xFFFFu, iv[gi].y >> 16 };
-#pragma unroll
-      for (uint32_t k = 0; k < 4; k++) {
-        const uint32_t j = (uint32_t)gi * 4u + k;
-        if (j < len) {
-          const double vv = DICT ? sdict[(cw[gi] >> (8u * k)) & 255u] : stream_load(vraw + (size_t)j * 64);
-          acc             = acc + vv * sx[d[k]];
-        }
-      }
-    }
-  }
-  for (uint32_t g = PF; g < ng; g++) { // chunks wider than 32 columns
-    const u32x2 i0      = stream_load(sstream + (size_t)g * 64);
-    const uint32_t cw0  = DICT ? stream_load(cstream + (size_t)g * 64) : 0u;
-    const uint32_t d[4] = { i0.x & 0xFFFFu, i0.x >> 16, i0.y & 0xFFFFu, i0.y >> 16 };
-#pragma unroll
-    for (uint32_t k = 0; k < 4; k++) {
-      const uint32_t j = g * 4u + k;
-      if (j < len) {
-        const double vv = DICT ? sdict[(cw0 >> (8u * k)) & 255u] : stream_load(vraw + (size_t)j * 64);
-        acc             = acc + vv * sx[d[k]];
-      }
-    }
-  }
-  spmv_epilogue<DOT>(chunk, lane, acc, x, y, nr, dotPartials);
-}
-#endif // SB_LAB
 
 // ---- level 4: pattern dictionary ---------------------------------------------------------
 // In the LDS-window kernel an element costs 3 B (value code + 16-bit slot).  In a matrix
@@ -714,8 +550,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(72))) /* see sp
   constexpr int WB   = 3 * LONG + 3;     // window entries per thread in the first pass
   constexpr int EXL  = MASKED ? 0 : CPT / 2; // unconditional exception loads per thread (256 entries each)
   // A launch covers headers [firstHdr, firstHdr + nHdrs).  Headers are stored with the tiles
-  // that touch no halo column first, so that on several ranks the interior part of the
-  // product can run while the halo is still in flight (one launch for each part).
+  // that touch no halo column first, so that on several ranks the interior tiles can run
+  // while the halo is still in flight (HALO: the tiles stored last wait for it).
   if (HALO && blockIdx.x < hw.nPush) { // (uniform per workgroup) this workgroup carries the rank's halo push
     if (*stop) {
       if (blockIdx.x == 0 && threadIdx.x == 0 && halo_rank_failed(*hw.push)) halo_poison_flags(*hw.push); // this rank has failed

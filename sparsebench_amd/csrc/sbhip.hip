@@ -117,8 +117,6 @@ struct Ctx {
   bool init = false;
   int device = 0;
   hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr; // halo exchange while the interior tiles are multiplied
-  hipEvent_t evFork = nullptr, evJoin = nullptr;
   hipDeviceProp_t prop;
   char name[320];
   // scratch for stand-alone ddot / permuted sb_spmv
@@ -310,9 +308,7 @@ struct sb_cg {
   uint32_t nPartials;
   double *rr_hist, *pAp_hist;
   int hist_cap;
-  int fused, use_graph;
-  hipGraphExec_t iterGraph;
-  bool graphReady;
+  int fused;
   double region_ms[4];
   std::vector<hipEvent_t> ev;
   std::vector<int> evRegion;
@@ -332,15 +328,7 @@ struct sb_cg {
   int k_next;        // next loop body to enqueue
   bool started;
   CgScalars hostS;   // staging copy for the H2D of the control block
-  // fused >= 2: the vector phase of a body as one launch (kernels.hip.h: cg_vector_phase_k)
-  VPhase* vphase    = nullptr;
   double* partials2 = nullptr; // level-0 partials of r.r (the p.Ap ones stay in `partials` while it reads them)
-  int vSP = -1;                // spans per wave of the chosen instantiation; 0: not eligible; -1: not planned yet
-  uint32_t vGrid = 0;
-  // fused >= 1: the scalar steps inside their consumers (kernels.hip.h: cg_lead_r_k / cg_lead_p_k), 3 launches per body
-  Lead* lead     = nullptr; // [0] alpha step, [1] beta step
-  int leadPlan   = -1;      // 1 in use, 0 not, -1 not decided yet
-  bool betaOwed  = false;   // the last enqueued body's beta step / loop test has not been enqueued yet
 };
 
 // ===========================================================================
@@ -349,13 +337,8 @@ struct sb_cg {
 // Every sb_* function below is declared extern "C" by include/sbhip.h, which fixes
 // its linkage; the helpers in between stay C++.
 
-#ifdef SB_LAB
-const char* sb_version(void) { return "sparsebench_amd sbhip 0.5 (gfx950, LAB build)"; }
-int sb_lab_build(void) { return 1; }
-#else
 const char* sb_version(void) { return "sparsebench_amd sbhip 0.5 (gfx950)"; }
-int sb_lab_build(void) { return 0; }
-#endif
+int sb_lab_build(void) { return 0; } // (there is one build: DESIGN 4.6)
 
 int sb_device_count(void)
 {
@@ -379,9 +362,6 @@ void sb_init(int device)
   HIP_CHECK(hipGetDeviceProperties(&g.prop, device));
   snprintf(g.name, sizeof g.name, "%s (%s)", g.prop.name[0] ? g.prop.name : "AMD Instinct", g.prop.gcnArchName);
   HIP_CHECK(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-  HIP_CHECK(hipStreamCreateWithFlags(&g.stream2, hipStreamNonBlocking));
-  HIP_CHECK(hipEventCreateWithFlags(&g.evFork, hipEventDisableTiming));
-  HIP_CHECK(hipEventCreateWithFlags(&g.evJoin, hipEventDisableTiming));
   HIP_CHECK(hipMalloc(&g.scalar, 64));
   HIP_CHECK(hipMemset(g.scalar, 0, 64)); // [0] scratch double, [4] a permanent int 0 (zero_flag)
   g.device = device;
@@ -399,9 +379,6 @@ void sb_finalize(void)
     if (g.ws[i]) HIP_CHECK(hipFree(g.ws[i]));
   HIP_CHECK(hipFree(g.scalar));
   HIP_CHECK(hipStreamDestroy(g.stream));
-  HIP_CHECK(hipStreamDestroy(g.stream2));
-  HIP_CHECK(hipEventDestroy(g.evFork));
-  HIP_CHECK(hipEventDestroy(g.evJoin));
   g = Ctx();
 }
 

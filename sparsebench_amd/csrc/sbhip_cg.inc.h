@@ -103,16 +103,7 @@ sb_cg* sb_cg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, con
   s->rr_hist = s->pAp_hist = nullptr;
   s->partials2 = (double*)sb_malloc((4 * (size_t)s->nPartials + 4) * sizeof(double));
   HIP_CHECK(hipMemsetAsync(s->partials2, 0, (4 * (size_t)s->nPartials + 4) * sizeof(double), g.stream));
-#ifdef SB_LAB
-  s->lead = (Lead*)sb_malloc(2 * sizeof(Lead));
-  HIP_CHECK(hipMemsetAsync(s->lead, 0, 2 * sizeof(Lead), g.stream));
-  s->vphase = (VPhase*)sb_malloc(sizeof(VPhase));
-  HIP_CHECK(hipMemsetAsync(s->vphase, 0, sizeof(VPhase), g.stream));
-#endif
   s->fused      = 1;
-  s->use_graph  = 0;
-  s->graphReady = false;
-  s->iterGraph  = nullptr;
   s->timing     = false;
   s->evUsed     = 0;
   s->loop_ms    = 0.f;
@@ -142,7 +133,6 @@ void sb_cg_free(sb_cg* s)
     s->halo->push.p2pErr = nullptr;
     HIP_CHECK(hipMemcpy(s->halo->dPush, &s->halo->push, sizeof s->halo->push, hipMemcpyHostToDevice));
   }
-  if (s->iterGraph) HIP_CHECK(hipGraphExecDestroy(s->iterGraph));
   for (hipEvent_t e : s->ev) HIP_CHECK(hipEventDestroy(e));
   for (hipEvent_t e : s->spmvEv) HIP_CHECK(hipEventDestroy(e));
   for (hipEvent_t e : s->phEv) HIP_CHECK(hipEventDestroy(e));
@@ -150,22 +140,16 @@ void sb_cg_free(sb_cg* s)
   HIP_CHECK(hipEventDestroy(s->evLoop1));
   if (s->vecFromArena) const_cast<sb_matrix*>(s->A)->vecArenaBusy = false; // r, Ap, x, b, both p buffers, xexact: back to the matrix
   else sb_free(s->vecSlab);
-  sb_free(s->S), sb_free(s->partials), sb_free(s->rr_hist), sb_free(s->pAp_hist), sb_free(s->partials2), sb_free(s->vphase), sb_free(s->lead);
+  sb_free(s->S), sb_free(s->partials), sb_free(s->rr_hist), sb_free(s->pAp_hist), sb_free(s->partials2);
   delete s;
-}
-
-static void drop_graph(sb_cg* s)
-{
-  if (s->iterGraph) HIP_CHECK(hipGraphExecDestroy(s->iterGraph));
-  s->iterGraph = nullptr, s->graphReady = false;
 }
 
 // The dot order of the loop: tree (0, the fixed order of every fused kernel) or seq (1, the reference's sequential sum,
 // dot_seq_k).  seq runs the reference's op list (fused = 0) with each of its dots -- r.r of the prologue and of every body,
-// p.Ap -- as dot_seq_k; every fused dot, the fused p update, the folded scalar steps and the lab plans are bypassed because
-// fused is 0.  The caller's fused level is kept (fusedWant) and runs again when the order returns to tree.  Decided once per
-// solve, like the fused-p plan: sb_cg_start latches it, so the pieces of one solve never mix orders; a change in between
-// takes effect with the next sb_cg_start.
+// p.Ap -- as dot_seq_k; every fused dot, the fused p update and the folded scalar steps are bypassed because fused is 0.
+// The caller's fused level is kept (fusedWant) and runs again when the order returns to tree.  Decided once per solve,
+// like the fused-p plan: sb_cg_start latches it, so the pieces of one solve never mix orders; a change in between takes
+// effect with the next sb_cg_start.
 static bool cg_seq(const sb_cg* s)
 {
   if (s->seqLatched >= 0) return s->seqLatched > 0;
@@ -174,7 +158,7 @@ static bool cg_seq(const sb_cg* s)
 static void apply_dot_order(sb_cg* s)
 { // what runs: the caller's level, or the reference's op list under seq
   const int fused = cg_seq(s) ? 0 : s->fusedWant;
-  if (s->fused != fused) drop_graph(s), s->vSP = -1, s->leadPlan = -1, s->fusepPlan = -1;
+  if (s->fused != fused) s->fusepPlan = -1;
   s->fused = fused;
 }
 void sb_cg_set_dot_order(sb_cg* s, int order)
@@ -186,80 +170,19 @@ void sb_cg_set_dot_order(sb_cg* s, int order)
 int sb_cg_dot_order(const sb_cg* s) { return cg_seq(s) ? 1 : 0; }
 
 void sb_cg_set_fused(sb_cg* s, int fused)
-{ // 0: the reference's op list; 1 (default): dots fused into their producers (5 launches per body).  Lab builds (-DSB_LAB)
-  // additionally: 2: the vector phase of a body as one launch where that is possible (2 launches per body); 3: the two
-  // scalar steps taken by workgroup 0 of their consumers (3 launches per body) -- both measured SLOWER at 128^3, see
-  // below; the product treats every non-zero level as 1.
-#ifndef SB_LAB
-  fused = fused ? 1 : 0;
-#endif
-  s->fusedWant = fused;
+{ // 0: the reference's op list; 1 (default): dots fused into their producers (5 launches per body).  Every non-zero level is 1:
+  // levels 2 (the vector phase of a body as one launch) and 3 (the scalar steps taken by workgroup 0 of their consumers) were
+  // measured slower and removed (docs/LAB_NOTES.md; the code is in git history, 658dd0b)
+  s->fusedWant = fused ? 1 : 0;
   apply_dot_order(s);
 }
-
-#ifdef SB_LAB
-
-// Measured (MI355X, HPCG 128^3, Sell-64-256): 61.1 us per iteration against 51.5 us with the five launches.  The four
-// kernels it replaces overlap their reads and writes freely (134 MB in ~20 us, Infinity-Cache assisted) and pay ~8 us
-// for the two scalar launches; the one launch reads everything, THEN (after alpha) writes r and x, THEN (after beta)
-// writes p: the two grid-wide waits serialise the traffic, and one 1024-thread workgroup per CU is a thin streaming
-// configuration.  Kept selectable (sb_cg_set_fused(s, 2)) and tested, because the protocol -- workgroup 0 takes the
-// scalar step while the others hold their elements in registers -- is what a persistent CG kernel would build on.
-// The one-launch vector phase needs every workgroup of its grid resident at once (they wait for each other):
-// the grid is what the occupancy calculation says fits, and the instantiation the smallest whose registers hold
-// the rank's rows on that grid.  Not used when ranks share a GPU (SB_SHARED_GPU=1: rehearsal with several
-// processes per device -- two such grids would wait for each other's CUs), when the all-reduce is not the
-// in-kernel one, or with SB_VPHASE=0.
-template <int SP, bool P2P> static bool vphase_try(sb_cg* s, uint32_t nSpans)
-{
-  int perCU = 0;
-  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, cg_vector_phase_k<SP, P2P>, 1024, 0));
-  uint64_t grid = (uint64_t)perCU * (uint64_t)g.prop.multiProcessorCount;
-  // (tests with several ranks on ONE device cap the grid so that all ranks' grids are resident together)
-  if (const char* cap = getenv("SB_VPHASE_MAXGRID")) grid = std::min<uint64_t>(grid, (uint64_t)std::max(1, atoi(cap)));
-  if (grid == 0 || (uint64_t)nSpans > 16ull * grid * SP) return false;
-  s->vSP   = SP;
-  s->vGrid = (uint32_t)std::min<uint64_t>(grid, (nSpans + 16ull * SP - 1) / (16ull * SP));
-  return true;
-}
-static bool vphase_plan(sb_cg* s)
-{
-  if (s->vSP >= 0) return s->vSP > 0;
-  s->vSP = 0;
-  const bool off    = getenv("SB_VPHASE") && atoi(getenv("SB_VPHASE")) == 0;
-  const bool shared = getenv("SB_SHARED_GPU") && atoi(getenv("SB_SHARED_GPU")) != 0;
-  if (s->fused != 2 || off || s->nr == 0) return false;
-  if (multi_rank() && (!p2p_dots() || shared)) return false;
-  const uint32_t nSpans = ((s->nr + 255u) >> 8) * 2u;
-  if (multi_rank()) return vphase_try<1, true>(s, nSpans) || vphase_try<2, true>(s, nSpans) || vphase_try<4, true>(s, nSpans);
-  return vphase_try<1, false>(s, nSpans) || vphase_try<2, false>(s, nSpans) || vphase_try<4, false>(s, nSpans);
-}
-#else  // the product: five launches per body (or the reference's op list); DESIGN 4.4 has the measurements of the rest
-static bool vphase_plan(sb_cg*) { return false; }
-#endif // SB_LAB
-int sb_cg_vector_phase(sb_cg* s) { return vphase_plan(s) ? s->vSP : 0; }
+int sb_cg_vector_phase(sb_cg*) { return 0; } // (the one-launch vector phase: removed with fused level 2)
 
 template <int MODE> static void scalar_launch(sb_cg* s, int defer_x, const double* q, int l1 = 0);
 static int pAp_is_level1(const sb_cg* s);
 static int fusealpha_plan(sb_cg* s, int l1, uint32_t vb);
 static int fusebeta_plan(sb_cg* s, uint32_t vb);
 
-#ifdef SB_LAB
-
-// The scalar steps inside their consumers (sb_cg_set_fused(s, 3)): one rank only.
-// Measured (MI355X, HPCG 128^3, Sell-64-256, same box, back to back): 58.6 us per iteration against 51.7 us with the
-// five launches.  A dependent single-workgroup launch costs ~4 us here; waiting INSIDE a kernel for workgroup 0 --
-// its partial loads, the reduction, an agent-scope store, the pollers' round trips, 500 workgroups resuming -- costs
-// more (~7.5 us per step).  Not the default; kept selectable and tested (VERDICT r1 item 9 asked for 5 -> 3 launches).
-static bool lead_plan(sb_cg* s)
-{
-  if (s->leadPlan >= 0) return s->leadPlan > 0;
-  s->leadPlan = (s->fused == 3 && s->nr > 0 && !multi_rank()) ? 1 : 0;
-  return s->leadPlan > 0;
-}
-#else
-static bool lead_plan(sb_cg*) { return false; }
-#endif // SB_LAB
 static bool spmv_can_fuse_dot(const sb_cg* s);
 // The p update inside the SpMV (pack.hip.h: spmv_prog_fusep; 4 launches per body: SpMV | alpha | r update | beta): where the
 // matrix allows it (spmv_fusep_possible), in the default loop (fused = 1), on one rank or with the halo over peer-mapped
@@ -276,7 +199,7 @@ static bool fusep_plan(sb_cg* s)
     const char* env = getenv("SB_FUSE_P");
     s->fusepPlan    = (s->fusepWant >= 0 ? s->fusepWant != 0 : env ? atoi(env) != 0 : SB_FUSE_P_DEFAULT) ? 1 : 0;
   }
-  bool ok = s->fusepPlan > 0 && s->fused == 1 && s->nr > 0 && !s->use_graph && spmv_fusep_possible(s->A);
+  bool ok = s->fusepPlan > 0 && s->fused == 1 && s->nr > 0 && spmv_fusep_possible(s->A);
   if (ok && multi_rank()) ok = s->halo ? halo_p2p_active(s->halo) : true;
   return ok;
 }
@@ -288,7 +211,7 @@ static bool fusep_plan(sb_cg* s)
 int sb_cg_launches_per_body(sb_cg* s)
 {
   if (s->seqLatched < 0) apply_dot_order(s); // (the process default may have changed since the last call)
-  int base = vphase_plan(s) ? 2 : lead_plan(s) ? 3 : fusep_plan(s) ? 4 : s->fused ? 5 : 0;
+  int base = fusep_plan(s) ? 4 : s->fused ? 5 : 0;
   if (base >= 4 && fusealpha_plan(s, fusep_plan(s) ? 1 : pAp_is_level1(s), 1024u)) base -= 1; // (alpha step inside the r update)
   if (base >= 4 && fusebeta_plan(s, 1024u)) base -= 1;                                          // (beta step inside the p update)
   if (!multi_rank() || base == 0) return base;
@@ -310,69 +233,6 @@ int sb_cg_collectives_per_body(sb_cg* s)
   return (p2p_dots() ? 0 : 2) + (s->halo && !halo_p2p_active(s->halo) ? 1 : 0);
 }
 
-#ifdef SB_LAB
-
-static long long lead_timeout() { return 2000ll * P2P_TICKS_PER_MS; }
-template <typename K> static dim3 lead_grid(K kernel, uint32_t work, uint32_t perBlock)
-{ // one round of resident 1024-thread workgroups (what the occupancy calculation says fits: 1 per CU at ~96 VGPRs)
-  int perCU = 0;
-  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, 1024, 0));
-  const uint32_t cap = (uint32_t)g.prop.multiProcessorCount * (uint32_t)std::max(1, perCU);
-  return dim3(std::max(1u, std::min(cap, (work + perBlock - 1) / perBlock)));
-}
-// alpha step + r update + r.r partials (-> partials2)
-static void launch_lead_r(sb_cg* s)
-{
-  const uint32_t nSpans = ((s->nr + 255u) >> 8) * 2u;
-  hipLaunchKernelGGL(cg_lead_r_k, lead_grid(cg_lead_r_k, nSpans, 32) /* two spans per wave and step */, dim3(1024), 0, g.stream, s->nr, s->Ap,
-      s->r, s->S, s->partials, s->partials2, s->nPartials, s->rr_hist, s->pAp_hist, s->lead + 0, lead_timeout(), pAp_is_level1(s));
-  HIP_CHECK(hipGetLastError());
-  s->betaOwed = true;
-}
-// beta step / loop test + p update + owed x update
-static void launch_lead_p(sb_cg* s)
-{
-  hipLaunchKernelGGL(cg_lead_p_k, lead_grid(cg_lead_p_k, s->nr / 2 + 1, 2048) /* two element pairs per thread and step */, dim3(1024), 0,
-      g.stream, s->nr, s->r, s->p, s->x, s->S, s->partials2, s->nPartials, s->rr_hist, s->pAp_hist, s->lead + 1, lead_timeout());
-  HIP_CHECK(hipGetLastError());
-  s->betaOwed = false;
-}
-// the beta step / loop test of the last enqueued body as its own launch (nobody's p update follows yet)
-static void flush_beta(sb_cg* s)
-{
-  if (!s->betaOwed) return;
-  scalar_launch<1>(s, 1, s->partials2);
-  phase_mark(s, PH_BETA);
-  s->betaOwed = false;
-}
-
-static void launch_vphase(sb_cg* s)
-{
-  const long long ticks = 2000ll * P2P_TICKS_PER_MS + (multi_rank() ? g.p2pTimeoutTicks : 0ll);
-  unsigned long long seq = 0;
-  if (multi_rank()) seq = g.p2pSeq + 1ull, g.p2pSeq += 2ull; // two all-reduces per launch
-#define VP_LAUNCH(SPN, PP)                                                                                              \
-  hipLaunchKernelGGL((cg_vector_phase_k<SPN, PP>), dim3(s->vGrid), dim3(1024), 0, g.stream, s->nr, s->r, s->p, s->Ap, s->x, \
-      s->S, s->partials, s->partials2, s->nPartials, s->rr_hist, s->pAp_hist, s->vphase, ticks, (const P2PView*)g.p2pView, seq, pAp_is_level1(s))
-  if (multi_rank()) {
-    if (s->vSP == 1) VP_LAUNCH(1, true);
-    else if (s->vSP == 2) VP_LAUNCH(2, true);
-    else VP_LAUNCH(4, true);
-  } else {
-    if (s->vSP == 1) VP_LAUNCH(1, false);
-    else if (s->vSP == 2) VP_LAUNCH(2, false);
-    else VP_LAUNCH(4, false);
-  }
-#undef VP_LAUNCH
-  HIP_CHECK(hipGetLastError());
-}
-#else
-static void launch_lead_r(sb_cg*) {}
-static void launch_lead_p(sb_cg*) {}
-static void flush_beta(sb_cg*) {}
-static void launch_vphase(sb_cg*) {}
-#endif // SB_LAB
-// hipGraph replay of a loop body was measured slower (-7 % at 128^3, -13 ... -35 % at 64^3: DESIGN 4.4): lab builds only
 // 1 / 0: take / do not take the p update inside the SpMV where the matrix and the data plane allow it; -1: the default
 // (SB_FUSE_P, else the library's).  sb_cg_fuse_p: what the loop will do.
 void sb_cg_set_fuse_p(sb_cg* s, int on)
@@ -386,15 +246,9 @@ int sb_cg_fuse_p(sb_cg* s)
   return fusep_plan(s) ? 1 : 0;
 }
 
-void sb_cg_set_graph(sb_cg* s, int use_graph)
-{
-#ifdef SB_LAB
-  s->use_graph = use_graph;
-#else
-  (void)use_graph;
-  s->use_graph = 0;
-#endif
-}
+// hipGraph replay of a loop body was measured slower (-7 % at 128^3, -13 ... -35 % at 64^3: docs/LAB_NOTES.md) and removed;
+// the call stays for callers that still pass SB_GRAPH / --graph
+void sb_cg_set_graph(sb_cg*, int) {}
 
 void sb_cg_spmv_timing(sb_cg* s, int on)
 {
@@ -494,9 +348,9 @@ template <int MODE> static void scalar_launch(sb_cg* s, int defer_x, const doubl
   }
 }
 
-// 1: the SpMV's fused dot wrote LEVEL-1 values of p.Ap (one per 256 rows), 0: level-0 partials (dot pass, lab kernels)
-// (fused loop behind a kernel without a dot of its own: the dot pass is dot_l1_k)
-static int pAp_is_level1(const sb_cg* s) { return spmv_can_fuse_dot(s) ? (spmv_dot_kind(s->A) == 2 ? 1 : 0) : (s->fused && s->nr ? 1 : 0); }
+// 1: LEVEL-1 values of p.Ap (one per 256 rows) -- from the SpMV's fused dot, or (fused loop behind a kernel without a dot of
+// its own) from the dot pass dot_l1_k; 0: level-0 partials (the reference's op list)
+static int pAp_is_level1(const sb_cg* s) { return spmv_can_fuse_dot(s) || (s->fused && s->nr) ? 1 : 0; }
 
 // The scalar steps inside their consumers' launches (kernels.hip.h: cg_update_r_k<ALPHA>, cg_update_p<BETA>): EVERY workgroup of
 // the consumer takes the step itself -- nobody waits for anybody --, workgroup 0 records it.  Returns the mode: 0 the separate
@@ -507,7 +361,7 @@ static int pAp_is_level1(const sb_cg* s) { return spmv_can_fuse_dot(s) ? (spmv_d
 // SB_FUSE_BETA=0 / sb_cg_set_fuse_beta(s, 0): the separate launches.
 static int fold_mode(sb_cg* s, int l1, uint32_t vb)
 {
-  if (!s->fused || !l1 || vb != 1024u || vphase_plan(s) || lead_plan(s)) return 0;
+  if (!s->fused || !l1 || vb != 1024u) return 0;
   if (multi_rank()) return p2p_dots() ? 0 : 2;
   return 1;
 }
@@ -522,7 +376,7 @@ static int fusebeta_plan(sb_cg* s, uint32_t vb)
 {
   static const int env = getenv("SB_FUSE_BETA") ? atoi(getenv("SB_FUSE_BETA")) != 0 : -1;
   const bool want = s->fuseBetaWant >= 0 ? s->fuseBetaWant != 0 : env >= 0 ? env != 0 : true;
-  if (!want || fusep_plan(s) || s->use_graph) return 0;
+  if (!want || fusep_plan(s)) return 0;
   return fold_mode(s, 1, vb);
 }
 void sb_cg_set_fuse_alpha(sb_cg* s, int on) { s->fuseAlphaWant = on < 0 ? -1 : on != 0; }
@@ -731,11 +585,6 @@ static void loop_body(sb_cg* s, int k)
     if (n) hipLaunchKernelGGL(cg_update_p<0>, gridV, blockV, 0, g.stream, n, s->r, s->p, (double*)nullptr, s->S, 1, 0u, (const double*)nullptr, (double*)nullptr); // p = r (:109)
     mark(s, R_WAXPBY);
     phase_mark(s, PH_P_UPDATE);
-  } else if (vphase_plan(s)) {
-    // p = r + beta p (:114) was taken at the end of the previous body's vector phase
-  } else if (s->betaOwed) { // (lead kernels) the previous body's beta step / loop test rides in front of the p update
-    launch_lead_p(s);
-    phase_mark(s, PH_P_UPDATE);
   } else {
     if (!s->fused) { // rtrans = r.r ; beta (:111-113)
       cg_dot(s, s->r, s->r, stop);
@@ -758,35 +607,9 @@ static void loop_body(sb_cg* s, int k)
     phase_mark(s, PH_P_UPDATE);
   }
   HIP_CHECK(hipGetLastError());
-  // Off by default: a cross-stream event dependency costs ~12 us on this platform (measured with
-  // an x update moved beside the beta step: 63 -> 88 us per iteration for one fork + join), which
-  // is about what the overlap can hide.  SB_HALO_OVERLAP=1 enables it.
-#ifdef SB_LAB
-  static const bool overlapHalo = getenv("SB_HALO_OVERLAP") && atoi(getenv("SB_HALO_OVERLAP")) != 0;
-#else
-  const bool overlapHalo = false; // (measured: one cross-stream dependency costs what the overlap hides; lab builds only)
-#endif
-  if (overlapHalo && multi_rank() && s->halo && spmv_can_fuse_dot(s) && spmv_can_split(s->A)) {
-    // :122-126 with the halo exchange hidden behind the interior tiles: the exchange (pack,
-    // send/recv into the tail of p) AND the few halo-touching tiles that need it run on a
-    // second stream while the tiles that touch no halo column are multiplied on the main one;
-    // the scalar step waits for both.  RCCL calls on the one communicator stay ordered: the
-    // exchange is complete (event) before anything later on the main stream.
-    mark(s, R_COMM);
-    spmv_event(s);
-    // (a host-mediated transport blocks the host inside halo_exchange, so nothing overlaps
-    //  there, but the fork / join is the same code)
-    HIP_CHECK(hipEventRecord(g.evFork, g.stream));
-    HIP_CHECK(hipStreamWaitEvent(g.stream2, g.evFork, 0));
-    halo_exchange(s->halo, s->p, stop, g.stream2, true);
-    launch_spmv(s->A, s->p, s->Ap, s->partials, stop, 2, g.stream2);
-    HIP_CHECK(hipEventRecord(g.evJoin, g.stream2));
-    launch_spmv(s->A, s->p, s->Ap, s->partials, stop, 1);
-    HIP_CHECK(hipStreamWaitEvent(g.stream, g.evJoin, 0));
-    spmv_event(s);
-    mark(s, R_SPMVM);
-    phase_mark(s, PH_SPMV);
-  } else if (multi_rank() && halo_p2p_active(s->halo) && spmv_can_fuse_dot(s) && spmv_uses_patterns(s->A)) {
+  // (the exchange on a second stream behind the interior tiles was measured no faster -- one cross-stream dependency costs
+  // ~12 us here, about what it hides -- and removed: docs/LAB_NOTES.md)
+  if (multi_rank() && halo_p2p_active(s->halo) && spmv_can_fuse_dot(s) && spmv_uses_patterns(s->A)) {
     // :122-126 over peer-mapped memory with the pull inside the SpMV: the halo-touching tiles (stored
     // last) wait for the neighbours' pushes themselves and read the staging area; interior tiles hide it
     // SB_HALO_PUSH_INSIDE=1: the push rides in the SpMV launch too (its first 16 workgroups) instead of a launch of its
@@ -809,7 +632,7 @@ static void loop_body(sb_cg* s, int k)
     hw.src = h->dSrcRank, hw.nsrc = h->indegree, hw.seq = h->seq, hw.err = h->err;
     hw.stopw = &s->S->stop, hw.timeoutTicks = h->push.timeoutTicks;
     spmv_time_begin(s);
-    launch_spmv(s->A, s->p, s->Ap, s->partials, stop, 0, nullptr, &hw);
+    launch_spmv(s->A, s->p, s->Ap, s->partials, stop, &hw);
     spmv_time_end(s);
     mark(s, R_SPMVM);
     phase_mark(s, PH_SPMV);
@@ -818,16 +641,6 @@ static void loop_body(sb_cg* s, int k)
     mark(s, R_COMM);
     if (multi_rank() && s->halo) phase_mark(s, PH_HALO);
     spmv_and_pAp(s, stop);
-  }
-  if (vphase_plan(s)) { // alpha | x, r update + r.r | beta, loop test | the next body's p update: one launch
-    launch_vphase(s);
-    phase_mark(s, PH_R_UPDATE);
-    return;
-  }
-  if (lead_plan(s)) { // alpha step in front of the r update; the beta step waits for the next body's p update (or flush_beta)
-    launch_lead_r(s);
-    phase_mark(s, PH_R_UPDATE);
-    return;
   }
   if (s->fused) { // alpha; r -= alpha Ap (:128) + next r.r, beta, loop test; x += alpha p (:127) is owed
     // (level-1 values of r.r into partials2: `partials` keeps the layout the p.Ap producers write)
@@ -855,27 +668,6 @@ static void ensure_hist(sb_cg* s, int cap)
   s->hist_cap = cap;
   s->rr_hist  = (double*)sb_malloc((size_t)cap * sizeof(double));
   s->pAp_hist = (double*)sb_malloc((size_t)cap * sizeof(double));
-  drop_graph(s); // captured pointers are stale
-}
-
-static void run_body_maybe_graph(sb_cg* s, int k)
-{ // k >= 2 bodies are iteration-invariant (k lives in the device control block)
-  // (lead kernels: the captured body is the chained one, whose p update carries the previous body's beta step)
-  if (k < 2 || !s->use_graph || multi_rank() || s->timing || s->spmvTiming || s->phaseTiming || (lead_plan(s) && !vphase_plan(s) && !s->betaOwed)) {
-    loop_body(s, k);
-    return;
-  }
-  if (!s->graphReady) {
-    hipGraph_t graph;
-    HIP_CHECK(hipStreamBeginCapture(g.stream, hipStreamCaptureModeThreadLocal));
-    loop_body(s, 2);
-    HIP_CHECK(hipStreamEndCapture(g.stream, &graph));
-    // (captured with betaOwed set, and the body leaves it set: nothing to restore)
-    HIP_CHECK(hipGraphInstantiate(&s->iterGraph, graph, nullptr, nullptr, 0));
-    HIP_CHECK(hipGraphDestroy(graph));
-    s->graphReady = true;
-  }
-  HIP_CHECK(hipGraphLaunch(s->iterGraph, g.stream));
 }
 
 void sb_cg_start(sb_cg* s, int itermax, double eps)
@@ -927,7 +719,6 @@ void sb_cg_start(sb_cg* s, int itermax, double eps)
   mark(s, R_DDOT);
   s->k_next   = 1;
   s->started  = true;
-  s->betaOwed = false;
   s->betaFold = 0;
 }
 
@@ -936,9 +727,8 @@ void sb_cg_run_iters(sb_cg* s, int iters)
   need_init();
   if (!s->started) SB_FATAL("sb_cg_run_iters before sb_cg_start");
   phase_mark(s, -1);
-  for (int i = 0; i < iters; i++) run_body_maybe_graph(s, s->k_next++);
-  flush_beta(s); // every call leaves the loop state complete (counters, history, stop flag)
-  flush_beta_fold(s);
+  for (int i = 0; i < iters; i++) loop_body(s, s->k_next++);
+  flush_beta_fold(s); // every call leaves the loop state complete (counters, history, stop flag)
 }
 
 int sb_cg_finish(sb_cg* s)
@@ -955,20 +745,6 @@ int sb_cg_finish(sb_cg* s)
   HIP_CHECK(hipStreamSynchronize(g.stream));
   CgScalars h;
   HIP_CHECK(hipMemcpy(&h, s->S, sizeof h, hipMemcpyDeviceToHost));
-#ifdef SB_LAB
-  {
-    VPhase vp;
-    Lead ld[2];
-    HIP_CHECK(hipMemcpy(&vp, s->vphase, sizeof vp, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(ld, s->lead, sizeof ld, hipMemcpyDeviceToHost));
-    if (ld[0].error || ld[1].error)
-      SB_FATAL("rank %d: a lead kernel's workgroups timed out waiting for workgroup 0's scalar step (sb_cg_set_fused(s, 1) / "
-               "bench.py --fused 1 selects the separate launches)", g.rank);
-    if (vp.error)
-      SB_FATAL("rank %d: the one-launch vector phase timed out waiting for its own workgroups: the GPU is shared with other "
-               "work (set SB_SHARED_GPU=1 or SB_VPHASE=0 to use the separate launches)", g.rank);
-  }
-#endif
   // (a rank that fails poisons what it would have published, so the others leave their waits at once with code 2: the rank
   //  that saw the CAUSE -- code 1 or 3 -- is the one whose message matters)
   if (s->halo && s->halo->p2p) {

@@ -14,35 +14,26 @@ static hipEvent_t g_spmvEvA = nullptr, g_spmvEvB = nullptr;
     else hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);                                    \
   } while (0)
 
-static int g_scs_unroll = -1;
 static int g_scs_nt     = -1;
 static int g_scs_xcd    = 1;
 
 // dotPartials != NULL: fuse the level-0 partials of p.Ap into the SpMV (SCS C=64 only)
-// part: 0 the whole product; 1 / 2 its interior / halo-touching tiles (spmv_can_split only)
+// usePacked is 5 (the masked row programs) or 0 (the reference-layout stream): sb_matrix_use_packed, product_modes_only
 static bool spmv_uses_patterns(const sb_matrix* m)
 {
-  return (m->usePacked == 3 || m->usePacked == 5) && (m->fmt == 0 ? m->mirror != nullptr : m->C == 64);
+  return m->usePacked == 5 && (m->fmt == 0 ? m->mirror != nullptr : m->C == 64);
 }
-static bool spmv_can_split(const sb_matrix* m)
-{
-  const sb_matrix* pm = pat_of(m);
-  if (!spmv_uses_patterns(m)) return false;
-  if (m->usePacked == 5) return pm->mInterior > 0 && pm->mInterior < pm->mNTiles;
-  return pm->patInterior > 0 && pm->patInterior < pm->patNTiles;
-}
-static void launch_pat(const sb_matrix* pm, bool skipPad, bool masked, const double* x, double* y, double* dotPartials,
-    const int* stop, int part, hipStream_t stream, const HaloWait* halo);
+static void launch_pat(const sb_matrix* pm, bool skipPad, const double* x, double* y, double* dotPartials, const int* stop,
+    const HaloWait* halo);
 
 // halo != NULL (pattern kernel only): the halo-touching tiles wait for the neighbours' pushes themselves
-static void launch_spmv(const sb_matrix* m, const double* x, double* y, double* dotPartials,
-    const int* stop, int part = 0, hipStream_t stream = nullptr, const HaloWait* halo = nullptr)
+static void launch_spmv(const sb_matrix* m, const double* x, double* y, double* dotPartials, const int* stop,
+    const HaloWait* halo = nullptr)
 {
   const bool dot = dotPartials != nullptr;
   if (m->nr == 0) return;
-  if (part != 0 && !spmv_can_split(m)) SB_FATAL("this SpMV kernel cannot be launched in parts");
   if (m->fmt == 0 && spmv_uses_patterns(m)) {
-    launch_pat(m->mirror, true, m->usePacked == 5, x, y, dotPartials, stop, part, stream ? stream : g.stream, halo);
+    launch_pat(m->mirror, true, x, y, dotPartials, stop, halo);
   } else if (m->fmt == 0) {
     if (dot) SB_FATAL("the native CRS kernel has no fused dot (its row blocks are not aligned to the 64-row groups of "
                       "the canonical dot; a kernel that is was measured slower, kernels.hip.h): sbhip_cg adds a dot pass");
@@ -57,9 +48,7 @@ static void launch_spmv(const sb_matrix* m, const double* x, double* y, double* 
     SB_SPMV_LAUNCH(spmv_crs_stream, dim3(per * 8), dim3(CRS_THREADS), 0, g.stream, m->rowBlocks, m->rowPtr, m->colInd,
         m->val, x, y, m->nRowBlocks, per, stop);
   } else if (m->C == 64) {
-    if (g_scs_unroll < 0) {
-      const char* u = getenv("SB_SCS_UNROLL");
-      g_scs_unroll  = u ? atoi(u) : 4;
+    if (g_scs_nt < 0) {
       const char* n = getenv("SB_SCS_NT");
       g_scs_nt      = n ? atoi(n) : 1;
       const char* xc = getenv("SB_SCS_XCD");
@@ -68,36 +57,8 @@ static void launch_spmv(const sb_matrix* m, const double* x, double* y, double* 
     const uint32_t nBlocks = (m->nChunks + 3) / 4;
     const uint32_t per     = g_scs_xcd ? (nBlocks + 7) / 8 : 0;
     dim3 grid(g_scs_xcd ? per * 8 : nBlocks), block(256);
-    if (m->usePacked == 3 || m->usePacked == 5) {
-      launch_pat(m, false, m->usePacked == 5, x, y, dotPartials, stop, part, stream ? stream : g.stream, halo);
-#ifdef SB_LAB // levels 1-3 of the compressed mirror: measured slower than level 6 at every size; lab builds only
-    } else if (m->usePacked == 2) {
-      const size_t shmem = (256 + (size_t)m->ldsWindow) * sizeof(double);
-#define LDS_LAUNCH(DI, DO)                                                                                   \
-  SB_SPMV_LAUNCH((spmv_scs64_lds<DI, DO>), grid, block, shmem, g.stream, m->pmeta, m->pslots, m->pcodes, \
-      m->pdict, m->chunkPtr, m->val, m->tileSegPtr, m->tileSegs, x, y, m->nr, m->nChunks, per, m->padCol,    \
-      dotPartials, stop)
-      if (m->nDict > 0) {
-        if (dot) LDS_LAUNCH(true, true);
-        else LDS_LAUNCH(true, false);
-      } else {
-        if (dot) LDS_LAUNCH(false, true);
-        else LDS_LAUNCH(false, false);
-      }
-#undef LDS_LAUNCH
-    } else if (m->usePacked == 1) {
-#define PK_LAUNCH(DI, DO)                                                                                 \
-  SB_SPMV_LAUNCH((spmv_scs64_packed<DI, DO>), grid, block, 0, g.stream, m->pmeta, m->pidx, m->pcodes, \
-      m->pdict, m->chunkPtr, m->val, x, y, m->nr, m->nChunks, per, m->padCol, dotPartials, stop)
-      if (m->nDict > 0) {
-        if (dot) PK_LAUNCH(true, true);
-        else PK_LAUNCH(true, false);
-      } else {
-        if (dot) PK_LAUNCH(false, true);
-        else PK_LAUNCH(false, false);
-      }
-#undef PK_LAUNCH
-#endif // SB_LAB
+    if (m->usePacked == 5) {
+      launch_pat(m, false, x, y, dotPartials, stop, halo);
     } else {
 #define SCS_LAUNCH(U, D, N)                                                                      \
   SB_SPMV_LAUNCH((spmv_scs64<U, D, N>), grid, block, 0, g.stream, m->chunkPtr, m->chunkLens, \
@@ -107,17 +68,7 @@ static void launch_spmv(const sb_matrix* m, const double* x, double* y, double* 
     if (dot) { if (g_scs_nt) SCS_LAUNCH(U, true, true); else SCS_LAUNCH(U, true, false); }    \
     else { if (g_scs_nt) SCS_LAUNCH(U, false, true); else SCS_LAUNCH(U, false, false); }      \
   } while (0)
-#ifdef SB_LAB // unroll depths other than 4: measured equal or slower
-      switch (g_scs_unroll) {
-      case 1: SCS_PICK(1); break;
-      case 2: SCS_PICK(2); break;
-      case 8: SCS_PICK(8); break;
-      case 9: SCS_PICK(9); break;
-      default: SCS_PICK(4); break;
-      }
-#else
-      SCS_PICK(4);
-#endif
+      SCS_PICK(4); // (other unroll depths: measured equal or slower)
 #undef SCS_PICK
 #undef SCS_LAUNCH
     }
@@ -129,60 +80,41 @@ static void launch_spmv(const sb_matrix* m, const double* x, double* y, double* 
   HIP_CHECK(hipGetLastError());
 }
 
-// masked: the level-6 form of the same tiles (row programs, pack.hip.h)
-static void launch_pat(const sb_matrix* pm, bool skipPad, bool masked, const double* x, double* y, double* dotPartials,
-    const int* stop, int part, hipStream_t stream, const HaloWait* halo)
+// the level-6 form of the tiles (masked row programs, pack.hip.h: spmv_scs64_pat with MASKED)
+static void launch_pat(const sb_matrix* pm, bool skipPad, const double* x, double* y, double* dotPartials, const int* stop,
+    const HaloWait* halo)
 {
   HaloWait hw;
   memset(&hw, 0, sizeof hw);
   if (halo) hw = *halo;
-  if (masked && !pm->mHdrs) SB_FATAL("the matrix has no masked row programs");
+  if (!pm->mHdrs) SB_FATAL("the matrix has no masked row programs");
   const bool dot         = dotPartials != nullptr;
-  const uint32_t nBlocks = masked ? pm->mNTiles : pm->patNTiles, interior = masked ? pm->mInterior : pm->patInterior;
-  const uint32_t dictE = masked ? pm->mDict : pm->patDict, excE = masked ? 0u : pm->patExcLds;
-  const size_t shmem = ((size_t)dictE + excE + 8) * sizeof(PatEntry) + (size_t)(masked ? pm->mWindow : pm->patWindow) * sizeof(double);
+  const uint32_t nBlocks = pm->mNTiles, dictE = pm->mDict;
+  const size_t shmem     = ((size_t)dictE + 8) * sizeof(PatEntry) + (size_t)pm->mWindow * sizeof(double);
   if (!stop) stop = zero_flag();
-  const uint32_t first = part == 2 ? interior : 0u;
-  const uint32_t count = part == 1 ? interior : part == 2 ? nBlocks - interior : nBlocks;
-  const uint32_t pper  = g_scs_xcd ? (count + 7) / 8 : 0;
-  const dim3 pgrid((g_scs_xcd ? pper * 8 : count) + (halo ? hw.nPush : 0u)), block(256);
-  const uint32_t* hdrs   = masked ? pm->mHdrs : pm->tileHdrs;
-  const uint32_t* codes  = masked ? pm->mStream : pm->jcodes;
-  const uint16_t* rbase  = masked ? reinterpret_cast<const uint16_t*>(pm->mRowBase) : pm->rowBase;
-#define PAT_LAUNCH(CP, DO, SK, HA, MA)                                                                                     \
-  SB_SPMV_LAUNCH((spmv_scs64_pat<CP, DO, SK, HA, MA>), pgrid, block, shmem, stream, hdrs, codes, rbase,                \
-      masked ? pm->mClassDict : pm->classDict, pm->rowPats, pm->excRows, pm->mProgs, pm->mSlotMap, pm->mMapStride,           \
-      masked ? pm->mSegs : pm->patSegs, x, y, pm->nr, pm->nChunks, first, count, pper, pm->padCol, dictE, excE, dotPartials, \
-      stop, hw)
-#define PAT_PICK(CP, SK, HA, MA)                \
-  do {                                          \
-    if (dot) PAT_LAUNCH(CP, true, SK, HA, MA);  \
-    else PAT_LAUNCH(CP, false, SK, HA, MA);     \
+  const uint32_t pper = g_scs_xcd ? (nBlocks + 7) / 8 : 0;
+  const dim3 pgrid((g_scs_xcd ? pper * 8 : nBlocks) + (halo ? hw.nPush : 0u)), block(256);
+#define PAT_LAUNCH(CP, DO, SK, HA)                                                                                            \
+  SB_SPMV_LAUNCH((spmv_scs64_pat<CP, DO, SK, HA, true>), pgrid, block, shmem, g.stream, pm->mHdrs, pm->mStream,                \
+      reinterpret_cast<const uint16_t*>(pm->mRowBase), pm->mClassDict, pm->rowPats, pm->excRows, pm->mProgs, pm->mSlotMap,   \
+      pm->mMapStride, pm->mSegs, x, y, pm->nr, pm->nChunks, 0u, nBlocks, pper, pm->padCol, dictE, 0u, dotPartials, stop, hw)
+#define PAT_PICK(CP, SK, HA)                \
+  do {                                      \
+    if (dot) PAT_LAUNCH(CP, true, SK, HA);  \
+    else PAT_LAUNCH(CP, false, SK, HA);     \
   } while (0)
-#define PAT_PICK2(CP, MA)                       \
-  do {                                          \
-    if (skipPad) {                              \
-      if (halo) PAT_PICK(CP, true, true, MA);   \
-      else PAT_PICK(CP, true, false, MA);       \
-    } else {                                    \
-      if (halo) PAT_PICK(CP, false, true, MA);  \
-      else PAT_PICK(CP, false, false, MA);      \
-    }                                           \
+#define PAT_PICK2(CP)                       \
+  do {                                      \
+    if (skipPad) {                          \
+      if (halo) PAT_PICK(CP, true, true);   \
+      else PAT_PICK(CP, true, false);       \
+    } else {                                \
+      if (halo) PAT_PICK(CP, false, true);  \
+      else PAT_PICK(CP, false, false);      \
+    }                                       \
   } while (0)
-#ifndef SB_LAB // the product ships the masked row programs (level 6) only; levels 4-5 are lab builds
-  if (!masked) SB_FATAL("levels 4-5 of the compressed mirror are compiled into lab builds only (-DSB_LAB)");
-#endif
-  if ((masked ? pm->mCPT : pm->patCPT) == 8) {
-    if (masked) PAT_PICK2(8, true);
-#ifdef SB_LAB
-    else PAT_PICK2(8, false);
-#endif
-  } else {
-    if (masked) PAT_PICK2(4, true);
-#ifdef SB_LAB
-    else PAT_PICK2(4, false);
-#endif
-  }
+  if (pm->mCPT == 8) PAT_PICK2(8);
+  else PAT_PICK2(4);
 #undef PAT_PICK2
 #undef PAT_PICK
 #undef PAT_LAUNCH
@@ -193,7 +125,7 @@ static void launch_pat(const sb_matrix* pm, bool skipPad, bool masked, const dou
 // chunk is a row program (no per-lane code words) and every window is of the mapped or of the simple kind.
 static bool spmv_fusep_possible(const sb_matrix* m)
 {
-  if (m->usePacked != 5 || !spmv_uses_patterns(m)) return false;
+  if (!spmv_uses_patterns(m)) return false;
   const sb_matrix* pm = pat_of(m);
   return pm->mHdrs && pm->mDict == 0 && pm->nMaskedChunks == pm->nChunks && (pm->mSlotMap != nullptr || pm->mAllSimple);
 }
@@ -243,15 +175,9 @@ void sb_spmv_native(const sb_matrix* m, const double* x, double* y)
   launch_spmv(m, x, y, nullptr, nullptr);
 }
 
-// which values the fused dot of the selected SpMV kernel writes: 0 none (no fused dot), 1 level-0 partials (one per 64
-// rows), 2 LEVEL-1 values (one per 256 rows: the product's two wave-per-chunk kernels combine a block's / tile's four
-// chunks themselves; the lab-only kernels keep level 0)
-static int spmv_dot_kind(const sb_matrix* m)
-{
-  if (!(m->fmt == 1 ? m->C == 64 : spmv_uses_patterns(m))) return 0;
-  if (m->usePacked == 5 || (m->fmt == 1 && m->usePacked == 0)) return 2;
-  return 1;
-}
+// which values the fused dot of the selected SpMV kernel writes: 0 none (no fused dot), 2 LEVEL-1 values (one per 256
+// rows: the two wave-per-chunk kernels combine a block's / tile's four chunks themselves)
+static int spmv_dot_kind(const sb_matrix* m) { return (m->fmt == 1 ? m->C == 64 : spmv_uses_patterns(m)) ? 2 : 0; }
 
 int sb_spmv_native_dot(const sb_matrix* m, const double* x, double* y, double* partials_dev)
 { // the product with the fused partials of x . y, as the CG loop launches it for p . Ap

@@ -177,7 +177,7 @@ static void build_packed(sb_matrix* m, const double* hostVal, const uint32_t* ol
   // default kernel: the packed stream only where it really is smaller.  A matrix whose chunks span more than
   // 65535 columns (far couplings: the irregular stand-in) keeps 32-bit indices and fp64 values -- the same
   // bytes regrouped -- and the reference-layout kernel is the faster one there (260 vs 327 us at 94 M
-  // nonzeros).  sb_matrix_use_packed(m, 1) selects it regardless.
+  // nonzeros).  (The choices of levels 1-5 are interim: product_modes_only keeps 5 and turns the others into 0.)
   m->usePacked = m->packedBytes <= 0.9 * (12.0 * m->nElems) ? 1 : 0;
 }
 
@@ -1066,23 +1066,21 @@ static void build_patterns(sb_matrix* m, const uint32_t* chunkPtr, const uint32_
   // 6.4 us for level 3 and 7.7 us for level 5; 96^3 10.0 / 18.5 / 15.8; 128^3 18.6 / - / 27.5).  Otherwise the level-5
   // kernel once the matrix is more than one round of resident workgroups (8 per CU, 4 chunks each); below that
   // everything is one dependent-latency chain and the level-3 kernel's is shorter (64^3: 46.7k vs 43.2k CG it/s;
-  // 96^3: 22.8k vs 26.3k).  sb_matrix_use_packed(m, 3) selects it regardless.
+  // 96^3: 22.8k vs 26.3k).  (product_modes_only keeps 5 and turns the others into 0: their kernels were removed.)
   if (m->mHdrs) m->usePacked = 5;
   else if (level5) m->usePacked = (m->nChunks + 3) / 4 > (uint32_t)g.prop.multiProcessorCount * 8u ? 3 : 2;
 }
 
-#ifndef SB_LAB
-// The product ships two SpMV kernels per format: the reference-layout stream and the masked row programs (level 6).
+// The library ships two SpMV kernels per format: the reference-layout stream and the masked row programs (level 6).
 // Levels 1-5 are BUILT on the way to level 6 (value dictionary, window slots, pattern classes), but their kernels were
-// measured slower at every size and live in lab builds (-DSB_LAB) only: the streams that only those kernels
-// read are released here, and a matrix without row programs runs the reference-layout kernel.
+// measured slower at every size and have been removed: the streams that only those kernels read are
+// released here, and a matrix without row programs runs the reference-layout kernel.
 static void product_modes_only(sb_matrix* m)
 {
   if (m->usePacked != 5) m->usePacked = 0;
   sb_free(m->pidx), sb_free(m->pcodes), sb_free(m->pslots), sb_free(m->jcodes), sb_free(m->excRows);
   m->pidx = nullptr, m->pcodes = nullptr, m->pslots = nullptr, m->jcodes = nullptr, m->excRows = nullptr;
 }
-#endif
 
 void sb_set_external_ids(const uint32_t* global_ids, uint32_t n)
 {
@@ -1136,9 +1134,7 @@ sb_matrix* sb_scs_upload(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigma, u
   build_packed(m, val, oldToNewPerm);
   build_lds_windows(m, chunkPtr, chunkLens, colInd, val, oldToNewPerm);
   build_patterns(m, chunkPtr, chunkLens, colInd, val, oldToNewPerm);
-#ifndef SB_LAB
   product_modes_only(m);
-#endif
   tune_matrix_placement(m);
   return m;
 }
@@ -1193,12 +1189,7 @@ static void build_crs_mirror(sb_matrix* m, const uint32_t* rowPtr, const uint32_
   sb_matrix* mm   = sb_scs_upload(nr, m->nc, 64, 1, nChunks, (uint32_t)total, chunkPtr.data(), chunkLens.data(),
       scol.data(), sval.data(), nullptr, nullptr);
   g_tunePlacement = true;
-#ifdef SB_LAB
-  const bool useless = mm->nPatClasses == 0;
-#else
-  const bool useless = mm->mHdrs == nullptr; // (the product multiplies through the mirror's row programs only)
-#endif
-  if (useless) { // no repeating patterns: the native kernel it is
+  if (!mm->mHdrs) { // no row programs (the mirror multiplies through them only): the native kernel it is
     sb_matrix_free(mm);
     return;
   }
@@ -1306,20 +1297,10 @@ void sb_matrix_free(sb_matrix* m)
 
 int sb_matrix_pack_level(const sb_matrix* m) { return m->packLevel; }
 void sb_matrix_use_packed(sb_matrix* m, int mode)
-{ // 0 reference-layout stream, 1 packed stream + gathers through the cache, 2 packed + LDS window,
-  // 3 pattern codes + LDS window; a mode the matrix does not have falls to the next lower one
-  // (5: the pattern kernel on masked row programs, pack.hip.h level 6)
-#ifdef SB_LAB
-  if (m->fmt == 0) m->usePacked = mode >= 5 && m->mirror && m->mirror->mHdrs ? 5 : mode >= 3 && m->mirror ? 3 : 0;
-  else if (mode >= 5 && m->mHdrs) m->usePacked = 5;
-  else if (mode >= 3 && m->nPatClasses) m->usePacked = 3;
-  else if (mode >= 2 && m->ldsWindow) m->usePacked = 2;
-  else if (mode >= 1 && m->packLevel) m->usePacked = 1;
-  else m->usePacked = 0;
-#else // the product: masked row programs (5) where the matrix has them, or the reference-layout stream (0)
+{ // 5: the pattern kernel on masked row programs (pack.hip.h level 6) where the matrix has them; any other mode, or a matrix
+  // without them: the reference-layout stream (0)
   const sb_matrix* pm = m->fmt == 0 ? m->mirror : m;
   m->usePacked        = mode >= 5 && pm && pm->mHdrs ? 5 : 0;
-#endif
 }
 int sb_matrix_packed_mode(const sb_matrix* m) { return m->usePacked; }
 int sb_matrix_crs_kernel(const sb_matrix* m) { return m->fmt == 0 && m->tileRow ? 1 : 0; }

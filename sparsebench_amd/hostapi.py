@@ -202,7 +202,7 @@ class CG:
         self.ptr = self.L.sb_cg_create(problem.matrix, problem.halo, b.ctypes.data_as(vp),
                                        xe.ctypes.data_as(vp) if xe is not None else None)
         # fused: True = the default (1: dots fused into their producers), False = the reference's op list, or the
-        # level itself (0, 1, 2; 2 = additionally the vector phase as one launch where possible)
+        # level itself (0 or 1; any other non-zero level is 1)
         self.L.sb_cg_set_fused(self.ptr, int(fused))
         self.L.sb_cg_set_graph(self.ptr, int(graph))
         self.L.sb_cg_set_fuse_p(self.ptr, int(fuse_p))  # -1: default; 1 / 0: the p update inside the SpMV where possible / not
@@ -227,7 +227,7 @@ class CG:
         return "seq" if self.L.sb_cg_dot_order(self.ptr) else "tree"
 
     def vector_phase(self):
-        """spans per wave of the one-launch vector phase, 0 if the solver uses the separate launches"""
+        """always 0: the solver uses the separate launches (the one-launch vector phase was removed)"""
         return self.L.sb_cg_vector_phase(self.ptr)
 
     def launches_per_body(self):

@@ -44,20 +44,15 @@ def main():
     plans = po.Plans(locs)
     o = po.cg(locs, plans, itermax=itermax, fmt=fmt, Cc=Cc, sigma=sigma, dot="tree", rank_sum="tree", want_x=True)
     results = {}
-    # every kernel the matrix has: SCS C=64 levels 0..3; CRS native (0) and through its pattern mirror (3)
-    vphase_seen = 0
+    # every kernel the matrix has: SCS C=64 and CRS, the masked row programs (5, CRS: through its pattern mirror) and the
+    # reference layout / native CRS (0)
     # (every rank walks the SAME list: what a mode is clamped to may differ from rank to rank, the number of solves must not)
-    lab = bool(L.sb_lab_build())  # (the product: kernel modes 5 / 0 and fused 1 / 0; lab builds walk the alternatives too)
-    for mode in (((5, 3, 2, 1, 0) if lab else (5, 0)) if fmt == "scs" and Cc == 64 else ((5, 3, 0) if lab else (5, 0)) if fmt == "crs" else (0,)):
+    for mode in ((5, 0) if (fmt == "scs" and Cc == 64) or fmt == "crs" else (0,)):
         prob.use_packed(mode)  # clamped to what the matrix has
-        # 2: the vector phase as one launch (with the in-kernel all-reduce only; the test caps its grid so that the
-        # grids of all ranks on the one GPU are resident together), 1: five launches per body, 0: reference op list
-        # (3, scalar steps inside their consumers, is a one-rank mode -- DESIGN 4.4 says why -- and behaves as 1 here)
-        for fused in ((2, 1, 0) if lab else (1, 0)):
+        for fused in (1, 0):  # 1: five launches per body, 0: reference op list
             cg = hostapi.CG(prob, fused=fused)
-            vphase_seen += cg.vector_phase() > 0
             if os.environ.get("SB_TEST_VERBOSE"):
-                print("rank %d: mode %d fused %d vector phase %d" % (rank, mode, fused, cg.vector_phase()), flush=True)
+                print("rank %d: mode %d fused %d" % (rank, mode, fused), flush=True)
             k = cg.solve(itermax, 0.0)
             rr, pap = cg.history()
             x = cg.solution()
@@ -73,11 +68,10 @@ def main():
     golden = json.load(open(os.path.join(ROOT, "tests", "golden", "cg_hist_mpi.json")))
     if workload == "generate" and key in golden and golden[key]["itermax"] == itermax:
         ref = np.array([float(v) for v in golden[key]["rr"]])
-        rr = results[(0 if fmt == "crs" else 2 if (2, True) in results else 0, True)]
+        rr = results[(0, True)]
         live = ref / ref[0] >= 1e-20
         assert (np.abs(rr - ref) / ref)[live].max() <= 1e-12  # north_star tolerance vs the MPI reference
     dist.barrier()
-    print("VPHASE_RUNS %d" % vphase_seen, flush=True)
     mch = C.c_uint32(0)
     L.sb_matrix_row_programs(prob.matrix, C.byref(mch))
     nchunks = (prob.nr + 63) // 64

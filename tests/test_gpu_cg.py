@@ -15,7 +15,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import REFDATA, fused_levels, lab_build, modes_scs
+from conftest import REFDATA, fused_levels, modes_scs
 from oracle import pyoracle as po
 from sparsebench_amd import hostapi
 
@@ -26,14 +26,14 @@ def f(a):
     return np.array([float(v) for v in a])
 
 
-def run_gpu(filename, n, fmt, Cc, sigma, itermax, eps=0.0, fused=True, graph=False, pack_mode=None, pack_try=None, fuse_p=-1, fuse_alpha=-1, fuse_beta=-1):
+def run_gpu(filename, n, fmt, Cc, sigma, itermax, eps=0.0, fused=True, pack_mode=None, pack_try=None, fuse_p=-1, fuse_alpha=-1, fuse_beta=-1):
     nx, ny, nz = n if isinstance(n, tuple) else (n, n, n)
     p = hostapi.Problem(filename, nx, ny, nz, fmt=fmt, Cc=Cc, sigma=sigma)
     if pack_mode is not None:
         assert p.use_packed(pack_mode) == pack_mode
     if pack_try is not None:
         p.use_packed(pack_try)  # clamped to what the matrix has (CRS: its pattern mirror, if any)
-    cg = hostapi.CG(p, fused=fused, graph=graph, fuse_p=fuse_p, fuse_alpha=fuse_alpha, fuse_beta=fuse_beta)
+    cg = hostapi.CG(p, fused=fused, fuse_p=fuse_p, fuse_alpha=fuse_alpha, fuse_beta=fuse_beta)
     k = cg.solve(itermax, eps)
     rr, pap = cg.history()
     out = dict(k=k, rr=rr, pAp=pap, x=cg.solution(), err=cg.check_residual(), fuse_p=cg.fuse_p(), launches=cg.launches_per_body())
@@ -50,10 +50,9 @@ def test_history_bit_identical_to_oracle_same_dot_order(gpu, fmt, Cc, sigma, n):
     dims = n if isinstance(n, tuple) else (n, n, n)
     g = po.GMatrix.generate(*dims)
     o = po.cg(g, itermax=60, fmt=fmt, Cc=Cc, sigma=sigma, dot="tree", want_x=True)
-    # default kernel choice and the other pattern form the matrix may have (3: row patterns + exception lanes,
-    # 5: masked row programs); fused 1: five launches per body, 2: vector phase as one launch, 3: scalar steps inside their consumers, 0: reference op list
-    # (the product ships fused 1 / 0 and kernel modes 5 / 0; lab builds walk the measured-slower alternatives too)
-    combos = ((1, None), (2, None), (3, None), (0, None), (3, 3), (0, 3), (1, 5)) if lab_build() else ((1, None), (0, None), (1, 0), (0, 5))
+    # default kernel choice and the other one (5: masked row programs, 0: reference layout); fused 1: five launches per
+    # body, 0: reference op list
+    combos = ((1, None), (0, None), (1, 0), (0, 5))
     for fused, pack_try in combos:
         r = run_gpu("generate", n, fmt, Cc, sigma, 60, fused=fused, pack_try=pack_try)
         assert r["k"] == o["k"]
@@ -147,15 +146,14 @@ def test_scalar_steps_inside_their_consumers_same_bits(gpu, dims, fmt, sigma, mo
 
 
 def test_launches_per_body_variants(gpu):
-    """fused = 1 (default): five launches per body; 3: the two scalar steps ride in front of their consumers (3 launches);
-    2: the one-launch vector phase (2); 0: the reference's op list.  Same bits in all of them, also when the loop is
-    driven in pieces (every run_iters call flushes an owed beta step) and when it ends early (eps)."""
+    """fused = 1 (default): five launches per body; 0: the reference's op list; 2 and 3 (removed levels) behave as 1.
+    Same bits in all of them, also when the loop is driven in pieces (every run_iters call flushes an owed beta step) and
+    when it ends early (eps)."""
     g = po.GMatrix.generate(24, 20, 16)
     o = po.cg(g, itermax=70, fmt="scs", Cc=64, sigma=1, dot="tree", want_x=True)
     oe = po.cg(g, itermax=70, eps=1e-4, fmt="scs", Cc=64, sigma=1, dot="tree", want_x=True)
     assert oe["k"] < o["k"]
-    # (the product: 1 and 0; a request for the lab-only levels 2 / 3 behaves as 1 there)
-    for fused, want in (((1, 5), (3, 3), (2, 2), (0, 0)) if lab_build() else ((1, 5), (0, 0), (3, 5), (2, 5))):
+    for fused, want in ((1, 5), (0, 0), (3, 5), (2, 5)):
         p = hostapi.Problem("generate", 24, 20, 16, fmt="scs", Cc=64, sigma=1)
         cg = hostapi.CG(p, fused=fused, fuse_p=0, fuse_alpha=0, fuse_beta=0)  # (the p update inside the SpMV, the scalar steps inside their consumers: tests of their own)
         assert cg.launches_per_body() == want
@@ -182,14 +180,6 @@ def test_launches_per_body_variants(gpu):
         rr, pap = cg.history()
         assert np.array_equal(rr, oe["rr"]) and np.array_equal(pap, oe["pAp"]) and np.array_equal(cg.solution(), oe["x"][0])
         cg.free(), p.free()
-
-
-@pytest.mark.lab
-def test_graph_replay_gives_the_same_bits(gpu):
-    a = run_gpu("generate", 16, "scs", 64, 1, 50, graph=False)
-    b = run_gpu("generate", 16, "scs", 64, 1, 50, graph=True)
-    assert np.array_equal(a["rr"], b["rr"]) and np.array_equal(a["pAp"], b["pAp"])
-    assert np.array_equal(a["x"], b["x"])
 
 
 def test_band_klein_plumbing_case(gpu, golden_1rank):
@@ -300,8 +290,8 @@ def test_full_size_properties_128(gpu, golden_1rank):
     s = run_gpu("generate", n, "scs", 64, 256, 60)
     _assert_bits(s, "hpcg128_x1_scs_C64_sigma256")  # ... configs[2] itself, default kernel
     _assert_bits(c, "hpcg128_x1_crs")
-    # the benchmark configuration: every SpMV kernel the build has (the product: reference layout and the default masked
-    # row programs; lab builds: + compressed stream, LDS window, pattern dictionary + row patterns) gives the same bits
+    # the benchmark configuration: every SpMV kernel the library has (reference layout and the default masked row programs)
+    # gives the same bits
     for mode in [m for m in modes_scs() if m != 5]:
         q = run_gpu("generate", n, "scs", 64, 256, 25, pack_mode=mode)
         assert np.array_equal(q["rr"], s["rr"][:len(q["rr"])]) and np.array_equal(q["pAp"], s["pAp"][:len(q["pAp"])]), mode

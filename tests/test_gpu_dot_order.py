@@ -203,8 +203,8 @@ def test_switching_the_order_on_one_solver(gpu):
 
 
 def test_process_default_and_graph_request(seq_default):
-    """a solver without an order of its own follows the process default; a hipGraph request (lab builds replay the body as
-    a graph) gives the same bits"""
+    """a solver without an order of its own follows the process default; a hipGraph request (accepted and ignored: graph
+    replay was removed) gives the same bits"""
     g = po.GMatrix.generate(16, 16, 16)
     o = po.cg(g, itermax=50, fmt="scs", Cc=64, sigma=1, dot="seq")
     p = hostapi.Problem("generate", 16, 16, 16, fmt="scs", Cc=64, sigma=1)

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import REFDATA, lab_build, load_json, modes_scs
+from conftest import REFDATA, load_json, modes_scs
 from oracle import pyoracle as po
 from sparsebench_amd import capi, hostapi
 from sparsebench_amd.capi import DeviceVector
@@ -37,14 +37,13 @@ def gpu_spmv(L, m, x, nr):
     dx, dy = DeviceVector.from_host(x), DeviceVector(nr)
     L.sb_spmv(m, dx.ptr, dy.ptr)
     y = dy.get()
-    # every kernel the matrix has (0 reference stream / native CRS, 1 packed + cache gathers, 2 packed + LDS window,
-    # 3 pattern codes / row patterns + LDS window, 5 masked row programs; CRS: through its private mirror) must give
-    # the same bits.
+    # every kernel the matrix has (0 reference stream / native CRS, 5 masked row programs; CRS: through its private
+    # mirror) must give the same bits.
     # Where the result is NaN only the NaN-ness is compared (which NaN payload an add of two NaNs returns depends
     # on operand order, not on the algorithm)
     best = L.sb_matrix_packed_mode(m)
     tried = set()
-    for mode in (0, 1, 2, 3, 5):
+    for mode in (0, 5):
         L.sb_matrix_use_packed(m, mode)
         got = L.sb_matrix_packed_mode(m)
         if got in tried:
@@ -182,7 +181,7 @@ def test_packed_stream_levels_and_wide_chunks(gpu):
         assert L.sb_matrix_pack_level(m) == 2
         x = rng.standard_normal(g.nc)
         assert np.array_equal(gpu_spmv(L, m, x, g.nr), g.spmv(x))
-        if lab_build() or L.sb_matrix_packed_mode(m) == 5:  # (the product streams the mirror only through its row programs)
+        if L.sb_matrix_packed_mode(m) == 5:  # (the mirror is streamed only through its row programs)
             assert L.sb_matrix_stream_bytes(m) < 0.45 * L.sb_matrix_spmv_bytes(m)
         else:
             assert L.sb_matrix_packed_mode(m) == 0 and L.sb_matrix_stream_bytes(m) == L.sb_matrix_spmv_bytes(m)
@@ -231,12 +230,11 @@ def test_masked_row_programs_the_products_compressed_kernel(gpu):
         progs = L.sb_matrix_row_programs(m, C.byref(mch))
         if full:
             assert progs >= 1 and mch.value == s.nChunks, (dims, sg, progs, mch.value)
-        assert L.sb_matrix_packed_mode(m) == (5 if progs else (L.sb_matrix_packed_mode(m) if lab_build() else 0))
-        if not lab_build():
-            for want in (1, 2, 3, 4, 5, 7):
-                L.sb_matrix_use_packed(m, want)
-                assert L.sb_matrix_packed_mode(m) == (5 if progs and want >= 5 else 0), (dims, sg, want)
-            L.sb_matrix_use_packed(m, 5)
+        assert L.sb_matrix_packed_mode(m) == (5 if progs else 0)
+        for want in (1, 2, 3, 4, 5, 7):
+            L.sb_matrix_use_packed(m, want)
+            assert L.sb_matrix_packed_mode(m) == (5 if progs and want >= 5 else 0), (dims, sg, want)
+        L.sb_matrix_use_packed(m, 5)
         x = rng.standard_normal(g.nc)
         assert np.array_equal(gpu_spmv(L, m, x, g.nr), g.spmv(x))
         x[0], x[g.nc // 2] = np.inf, np.nan
@@ -245,99 +243,6 @@ def test_masked_row_programs_the_products_compressed_kernel(gpu):
         ok = ~np.isnan(exp)
         assert np.array_equal(got[ok].view(np.uint64), exp[ok].view(np.uint64))
         L.sb_matrix_free(m)
-
-
-@pytest.mark.lab
-def test_pattern_dictionary_mode(gpu, monkeypatch):
-    """mode 3 (one byte per element naming a (value, slot delta) pair): built for stencils
-    with and without the sigma permutation, refused when a tile has > 255 distinct pairs,
-    bit-identical to the oracle in every case (gpu_spmv compares all four kernels)"""
-    L = gpu
-    rng = np.random.default_rng(29)
-    # sigma > 1 on SMALL grids scatters a tile's rows over many lines: > 255 pairs per tile, the
-    # matrix then stays at mode 2 (allowed); with 128-row lines (the headline shape) mode 3 is built
-    cases = (((16, 16, 16), 1, True), ((16, 16, 16), 256, False), ((9, 8, 7), 64, False),
-             ((20, 5, 33), 4096, False), ((128, 128, 2), 256, True), ((70, 3, 5), 1, True))
-    for pack in (None, "4"):  # default: row patterns (level 5) where they pay; SB_PACK=4: per-lane codes only
-        if pack:
-            monkeypatch.setenv("SB_PACK", pack)
-        for dims, sg, must in cases:
-            g = po.GMatrix.generate(*dims)
-            s = g.to_scs(64, sg)
-            m = upload_scs(L, s)
-            assert L.sb_matrix_lds_window(m) > 0
-            uni = C.c_uint32(0)
-            pats = L.sb_matrix_row_patterns(m, C.byref(uni))
-            if must:
-                # default: the masked row programs where the matrix has them (faster at every size measured: 64^3 5.6 us
-                # against 6.4 us for level 3), else level 3 while the matrix is small
-                assert L.sb_matrix_pattern_classes(m) >= 1, (dims, sg)
-                assert L.sb_matrix_packed_mode(m) == (5 if L.sb_matrix_row_programs(m, None) else 2), (dims, sg)
-                L.sb_matrix_use_packed(m, 2)
-                lds_bytes = L.sb_matrix_stream_bytes(m)
-                L.sb_matrix_use_packed(m, 3)
-                assert L.sb_matrix_stream_bytes(m) < 0.62 * lds_bytes
-                if pack is None and dims[0] >= 64:
-                    # lines of >= 64 rows: most chunks are one shared row pattern + a few odd lanes
-                    # (short lines put many grid-boundary rows into a chunk: such tiles stay per-lane)
-                    # (70 x 3 x 5 mixes U and L chunks inside its tiles)
-                    assert pats >= 1 and uni.value >= (0.7 * s.nChunks if dims[0] >= 128 else 1), \
-                        (dims, sg, pats, uni.value, s.nChunks)
-                if pack is None and dims[0] >= 128:
-                    # ... and the odd lanes (rows next to the grid boundary, rows the sigma sort moved) are
-                    # sub-sequences of their tile's longer rows: every chunk becomes a masked row program
-                    mch = C.c_uint32(0)
-                    progs = L.sb_matrix_row_programs(m, C.byref(mch))
-                    assert progs >= 1 and mch.value == s.nChunks, (dims, sg, progs, mch.value, s.nChunks)
-                    L.sb_matrix_use_packed(m, 5)
-                    assert L.sb_matrix_packed_mode(m) == 5
-                    L.sb_matrix_use_packed(m, 2)
-            if pack:
-                assert pats == 0 and uni.value == 0 and L.sb_matrix_row_programs(m, None) == 0
-            x = rng.standard_normal(g.nc)
-            assert np.array_equal(gpu_spmv(L, m, x, g.nr), g.spmv(x))
-            # NaN / Inf in x reach exactly the rows the reference lets them reach (padding -> x[padCol])
-            x[0], x[g.nc // 2] = np.inf, np.nan
-            got, exp = gpu_spmv(L, m, x, g.nr), s.spmv(x)
-            assert np.isnan(exp).any() and np.array_equal(np.isnan(got), np.isnan(exp))
-            ok = ~np.isnan(exp)
-            assert np.array_equal(got[ok].view(np.uint64), exp[ok].view(np.uint64))
-            L.sb_matrix_free(m)
-        if pack:
-            monkeypatch.delenv("SB_PACK")
-    # banded matrix, 200 distinct values used round-robin: the LDS window is built (forced),
-    # but a tile holds far more than 255 (value, delta) pairs -> stays at mode 2
-    monkeypatch.setenv("SB_PACK_LDS", "1")
-    nr = 1024
-    rp = np.arange(0, 9 * nr + 1, 9, dtype=np.uint32)
-    col = (np.repeat(np.arange(nr), 9) + np.tile(np.arange(-4, 5), nr)).clip(0, nr - 1).astype(np.uint32)
-    val = (1.0 + (np.arange(9 * nr) * 7919 % 200)) * 0.125
-    gm = po.GMatrix.from_csr(rp, col, val, nc=nr)
-    s = gm.to_scs(64, 1)
-    m = upload_scs(L, s)
-    assert L.sb_matrix_lds_window(m) > 0 and L.sb_matrix_pattern_classes(m) == 0
-    assert L.sb_matrix_packed_mode(m) == 2
-    x = rng.standard_normal(nr)
-    assert np.array_equal(gpu_spmv(L, m, x, nr).view(np.uint64), gm.spmv(x).view(np.uint64))
-    L.sb_matrix_free(m)
-    # same band, 3 values by diagonal: patterns repeat -> mode 3; rows with duplicate columns
-    # (the clipped band ends) are separate elements and stay in order
-    val = np.tile(np.array([-1.0, -1.0, -0.5, -0.5, 8.0, -0.5, -0.5, -1.0, -1.0]), nr)
-    gm = po.GMatrix.from_csr(rp, col, val, nc=nr)
-    for sg in (1, 128):
-        s = gm.to_scs(64, sg)
-        m = upload_scs(L, s)
-        L.sb_matrix_use_packed(m, 3)
-        assert L.sb_matrix_pattern_classes(m) >= 1 and L.sb_matrix_packed_mode(m) == 3
-        assert np.array_equal(gpu_spmv(L, m, x, nr).view(np.uint64), gm.spmv(x).view(np.uint64))
-        L.sb_matrix_free(m)
-    monkeypatch.delenv("SB_PACK_LDS")
-    # SB_PACK=3 stops below the pattern level
-    monkeypatch.setenv("SB_PACK", "3")
-    g = po.GMatrix.generate(16, 16, 16)
-    m = upload_scs(L, g.to_scs(64, 1))
-    assert L.sb_matrix_pattern_classes(m) == 0 and L.sb_matrix_packed_mode(m) == 2
-    L.sb_matrix_free(m)
 
 
 def test_spmv_empty_matrix(gpu):
@@ -393,8 +298,8 @@ def test_waxpby_and_ddot_bit_exact(gpu, n):
 
 def test_fused_dot_partials_of_the_spmv(gpu):
     """the p . Ap partials the CG loop takes out of the SpMV launch: per 64 rows (device order) the butterfly of x_i * y_i,
-    combined per aligned 256 rows ((q0 + q1) + q2) + q3 -- by the kernel itself (the product's two kernels) or here (lab
-    kernels) -- equal to the oracle's level-1 partials of the same two vectors, for every kernel mode with a fused dot"""
+    combined per aligned 256 rows ((q0 + q1) + q2) + q3 by the kernel itself -- equal to the oracle's level-1 partials of
+    the same two vectors, for every kernel mode with a fused dot"""
     L = gpu
     rng = np.random.default_rng(41)
     for dims, sg in (((128, 128, 2), 256), ((32, 32, 32), 1), ((70, 3, 5), 1), ((20, 5, 33), 64)):
@@ -414,16 +319,12 @@ def test_fused_dot_partials_of_the_spmv(gpu):
             tried.add(got)
             dq = DeviceVector.from_host(np.zeros(nq))
             kind = L.sb_spmv_native_dot(m, dx.ptr, dy.ptr, dq.ptr)
-            assert kind == (2 if got in (0, 5) else 1)  # the product's kernels emit level-1 values, the lab-only ones level 0
-            if kind == 2:
-                y, lvl1 = dy.get(), dq.get()[:nq // 4]
-                assert not dq.get()[nq // 4:].any()  # nothing behind the last 256-group
-            else:
-                y, q = dy.get(), dq.get().reshape(-1, 4)
-                lvl1 = ((q[:, 0] + q[:, 1]) + q[:, 2]) + q[:, 3]
+            assert got in (0, 5) and kind == 2  # both kernels emit level-1 values
+            y, lvl1 = dy.get(), dq.get()[:nq // 4]
+            assert not dq.get()[nq // 4:].any()  # nothing behind the last 256-group
             assert np.array_equal(lvl1.view(np.uint64), po.ddot_partials(xp[:s.nr].copy(), y).view(np.uint64)), (dims, sg, got)
             dq.free()
-        assert len(tried) >= (3 if lab_build() else 2 if dims[0] >= 128 else 1)
+        assert len(tried) >= (2 if dims[0] >= 128 else 1)
         dx.free(), dy.free()
         L.sb_matrix_free(m)
 
@@ -506,8 +407,8 @@ def test_crs_through_its_pattern_mirror(gpu, monkeypatch):
     for dims in ((16, 16, 16), (128, 128, 2), (70, 3, 5), (9, 8, 7)):
         g = po.GMatrix.generate(*dims)
         m = upload_crs(L, g)
-        # (lab builds keep a mirror for its levels 4-5 too; the product only where it carries row programs)
-        assert L.sb_matrix_pattern_classes(m) >= 1 or (not lab_build() and not L.sb_matrix_row_programs(m, None)), dims
+        # (a mirror is kept only where it carries row programs)
+        assert L.sb_matrix_pattern_classes(m) >= 1 or not L.sb_matrix_row_programs(m, None), dims
         if dims[0] >= 128:
             assert L.sb_matrix_row_programs(m, None) >= 1
         # default: through the mirror's masked row programs where it has them, else (small matrix) the native kernel
@@ -536,7 +437,6 @@ def test_crs_through_its_pattern_mirror(gpu, monkeypatch):
                              np.concatenate(data), nc=nr)
     monkeypatch.setenv("SB_PACK_LDS", "1")
     m = upload_crs(L, gm)
-    assert L.sb_matrix_pattern_classes(m) >= 1 or not lab_build()
     x = rng.standard_normal(nr)
     x[5] = np.inf
     got, exp = gpu_spmv(L, m, x, nr), gm.spmv(x)

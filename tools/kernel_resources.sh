@@ -1,6 +1,6 @@
 #!/bin/bash
 # VGPRs / SGPRs / LDS / scratch / occupancy of every kernel in the library (device-only compile, -Rpass-analysis=kernel-resource-usage)
-# usage: tools/kernel_resources.sh [name-filter] [extra hipcc flags, e.g. -DSB_LAB=1]
+# usage: tools/kernel_resources.sh [name-filter] [extra hipcc flags]
 cd "$(dirname "$0")/.." || exit 1
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -Iinclude --cuda-device-only -c \
   -Rpass-analysis=kernel-resource-usage ${2} sparsebench_amd/csrc/sbhip.hip -o /dev/null 2>&1 |

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """pat_lab.py [n] [sigma] -- stand-alone timing of every SpMV kernel mode on the HPCG matrix
-(back-to-back launches, HIP events).  SBHIP_LIBRARY=<path> times a lab build of libsbhip.so
-(e.g. one compiled with -DSB_LAB=1 to knock out a phase of a kernel)."""
+(back-to-back launches, HIP events).  SBHIP_LIBRARY=<path> times another build of libsbhip.so
+(e.g. an instrumented copy from tools/make_prof_lab.py)."""
 import ctypes as C
 import os
 import sys

@@ -5,8 +5,8 @@ set -u
 cd "$(dirname "$0")/../sparsebench_amd/bin"
 N=${1:-128}
 for nt in 1 0; do
-  for u in 1 2 4 8 9; do
-    r=$(SB_SCS_UNROLL=$u SB_SCS_NT=$nt ./sparseBench-SCS-HIP -x $N -y $N -z $N -i 300 -t spmv -C 64 -s ${2:-1} | grep "spMVM:")
-    echo "n=$N sigma=${2:-1} unroll=$u nt=$nt $r"
+  for xcd in 1 0; do
+    r=$(SB_SCS_XCD=$xcd SB_SCS_NT=$nt ./sparseBench-SCS-HIP -x $N -y $N -z $N -i 300 -t spmv -C 64 -s ${2:-1} | grep "spMVM:")
+    echo "n=$N sigma=${2:-1} xcd=$xcd nt=$nt $r"
   done
 done
