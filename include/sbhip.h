@@ -188,6 +188,32 @@ void sb_reduce_final(uint32_t m, const double* partials_dev, double* result_dev)
 void sb_set_dot_order(int order);
 int sb_dot_order(void);
 
+/* ---- single precision: the reference's FLOAT_TYPE=SP build (src/util.h:47-51, -DPRECISION=1) ---------------- */
+/* CG_FLOAT = float everywhere: values, vectors and every operation; each product rounded to float before its add, sums
+ * accumulate in float, f32 subnormals kept.  An SP matrix streams the reference layout only (no compressed mirror, no masked
+ * row programs, no placement tuner).  One rank only (more is a fatal error).  Crossing precisions -- an fp64 entry point on an
+ * SP matrix or solver, or the other way round -- is a fatal error with file:line. */
+sb_matrix* sb_crs_upload_f32(uint32_t nr, uint32_t nc, const uint32_t* rowPtr, const uint32_t* colInd, const float* val);
+sb_matrix* sb_scs_upload_f32(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigma, uint32_t nChunks, uint32_t nElems,
+                             const uint32_t* chunkPtr, const uint32_t* chunkLens, const uint32_t* colInd, const float* val,
+                             const uint32_t* oldToNewPerm, const uint32_t* newToOldPerm);
+int sb_matrix_precision(const sb_matrix* m); /* 1 single, 2 double (the reference's PRECISION values) */
+void sb_spmv_f32(const sb_matrix* m, const float* x, float* y); /* as sb_spmv */
+/* as sb_spmv_native_dot: 2 = the LEVEL-1 values of x . y (Sell-64; ceil(nr / 256) floats), 0 = none (y only) */
+int sb_spmv_native_dot_f32(const sb_matrix* m, const float* x, float* y, float* l1_dev);
+void sb_permute_f32(const sb_matrix* m, const float* in_orig, float* out_perm);
+void sb_unpermute_f32(const sb_matrix* m, const float* in_perm, float* out_orig);
+void sb_waxpby_f32(uint32_t n, float alpha, const float* x, float beta, const float* y, float* w); /* src/solver.c:16-39 */
+/* ddot in float, in the process dot order (sb_dot_order): tree = the levels of sb_ddot_partials / sb_reduce_final, in float;
+ * seq = `CG_FLOAT sum = 0.0; sum += x[i] * y[i]` left to right.  Synchronises. */
+float sb_ddot_f32(uint32_t n, const float* x, const float* y);
+void sb_ddot_partials_f32(uint32_t n, const float* x, const float* y, float* partials_dev); /* level 0: 4*ceil(n/256) floats */
+void sb_reduce_final_f32(uint32_t m, const float* partials_dev, float* result_dev);          /* levels 1-2 over m groups */
+/* solveCG in single precision (src/CGSolver.c:62-141 of the SP build): b_host / xexact_host are nr floats.  Every other
+ * sb_cg_* call serves both precisions; sb_cg_history returns the float values exactly in its double arrays. */
+sb_cg* sb_cg_create_f32(const sb_matrix* m, sb_halo* halo, const float* b_host, const float* xexact_host);
+void sb_cg_solution_f32(const sb_cg* s, float* x_host);
+
 /* ---- multi-GPU (one rank per GPU, RCCL over xGMI) ---------------------------- */
 /* replaces MPI_Init / MPI_COMM_WORLD.  id = 128-byte ncclUniqueId made by rank 0
  * with sb_comm_unique_id() and handed to the other ranks by the launcher. */

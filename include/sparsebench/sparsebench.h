@@ -28,13 +28,25 @@ extern "C" {
 #endif
 
 /* ---- scalar types: src/util.h:35-53 (defaults of config.mk:7-8) --------------- */
+/* -DPRECISION=1 is the reference's FLOAT_TYPE=SP build (config.mk:7, 24-28): CG_FLOAT is float, the libraries are the _sp
+ * ones (libsparsebench_host_sp.so, libsparsebench_<fmt>_sp.so) and every call into the HIP layer goes to its _f32 entry point
+ * (SBH_FP).  Without it (or with -DPRECISION=2): double, as before. */
+#if PRECISION == 1
+#ifndef CG_FLOAT
+#define CG_FLOAT float
+#endif
+#define PRECISION_STRING "single"
+#define SBH_FP(name) name##_f32
+#else
 #ifndef CG_FLOAT
 #define CG_FLOAT double
+#endif
+#define PRECISION_STRING "double"
+#define SBH_FP(name) name
 #endif
 #ifndef CG_UINT
 #define CG_UINT unsigned int
 #endif
-#define PRECISION_STRING "double"
 #define UINT_STRING      "unsigned int"
 #ifndef ARRAY_ALIGNMENT
 #define ARRAY_ALIGNMENT 64 /* config.mk:11 */

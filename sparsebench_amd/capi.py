@@ -36,6 +36,9 @@ SYMBOLS = [
     "sb_malloc_host_visible", "sb_host_visible_reason", "sb_malloc_pinned_host", "sb_free_pinned_host", "sb_copy_counters",
     "sb_region_begin", "sb_region_end", "sb_region_seconds", "sb_region_reset",
     "sb_set_dot_order", "sb_dot_order", "sb_cg_set_dot_order", "sb_cg_dot_order",
+    "sb_crs_upload_f32", "sb_scs_upload_f32", "sb_matrix_precision", "sb_spmv_f32", "sb_spmv_native_dot_f32", "sb_permute_f32",
+    "sb_unpermute_f32", "sb_waxpby_f32", "sb_ddot_f32", "sb_ddot_partials_f32", "sb_reduce_final_f32", "sb_cg_create_f32",
+    "sb_cg_solution_f32",
     "sb_matrix_place", "sb_matrix_place_at", "sb_matrix_place_home", "sb_placement_arena_bytes", "sb_placement_probe", "sb_matrix_place_fresh", "sb_matrix_place_commit", "sb_matrix_placement", "sb_matrix_placement_report", "sb_matrix_debug_ptrs", "sb_cg_debug_ptrs",
 ]
 
@@ -178,6 +181,20 @@ def load():
         "sb_dot_order": (C.c_int, []),
         "sb_cg_set_dot_order": (None, [vp, C.c_int]),
         "sb_cg_dot_order": (C.c_int, [vp]),
+        # single precision
+        "sb_crs_upload_f32": (vp, [u32, u32, vp, vp, vp]),
+        "sb_scs_upload_f32": (vp, [u32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "sb_matrix_precision": (C.c_int, [vp]),
+        "sb_spmv_f32": (None, [vp, vp, vp]),
+        "sb_spmv_native_dot_f32": (C.c_int, [vp, vp, vp, vp]),
+        "sb_permute_f32": (None, [vp, vp, vp]),
+        "sb_unpermute_f32": (None, [vp, vp, vp]),
+        "sb_waxpby_f32": (None, [u32, C.c_float, vp, C.c_float, vp, vp]),
+        "sb_ddot_f32": (C.c_float, [u32, vp, vp]),
+        "sb_ddot_partials_f32": (None, [u32, vp, vp, vp]),
+        "sb_reduce_final_f32": (None, [u32, vp, vp]),
+        "sb_cg_create_f32": (vp, [vp, vp, vp, vp]),
+        "sb_cg_solution_f32": (None, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -218,34 +235,36 @@ def _hp(a):
 
 
 class DeviceVector:
-    """A vector of doubles in HBM owned through the C-ABI (sb_malloc / sb_free)."""
+    """A vector of doubles (or, dtype=np.float32, floats) in HBM owned through the C-ABI (sb_malloc / sb_free)."""
 
-    def __init__(self, n, host=None):
+    def __init__(self, n, host=None, dtype=np.float64):
         self.L = load()
         self.n = int(n)
-        self.ptr = self.L.sb_malloc(max(self.n, 1) * 8)
+        self.dtype = np.dtype(dtype)
+        self.isz = self.dtype.itemsize
+        self.ptr = self.L.sb_malloc(max(self.n, 1) * self.isz)
         if host is not None:
             self.set(host)
 
     @classmethod
-    def from_host(cls, a):
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        return cls(len(a), a)
+    def from_host(cls, a, dtype=np.float64):
+        a = np.ascontiguousarray(a, dtype=dtype)
+        return cls(len(a), a, dtype)
 
     def set(self, a):
-        a = np.ascontiguousarray(a, dtype=np.float64)
+        a = np.ascontiguousarray(a, dtype=self.dtype)
         assert len(a) == self.n
         if self.n:
-            self.L.sb_h2d(self.ptr, _hp(a), self.n * 8)
+            self.L.sb_h2d(self.ptr, _hp(a), self.n * self.isz)
 
     def get(self):
-        out = np.empty(self.n, dtype=np.float64)
+        out = np.empty(self.n, dtype=self.dtype)
         if self.n:
-            self.L.sb_d2h(_hp(out), self.ptr, self.n * 8)
+            self.L.sb_d2h(_hp(out), self.ptr, self.n * self.isz)
         return out
 
     def zero(self):
-        self.L.sb_memset(self.ptr, 0, self.n * 8)
+        self.L.sb_memset(self.ptr, 0, self.n * self.isz)
 
     def free(self):
         if self.ptr:

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "kernels.hip.h"
+#include "kernels_sp.hip.h"
 #include "pack.hip.h"
 
 #include <algorithm>
@@ -260,6 +261,10 @@ struct sb_matrix {
   uint32_t nRowPats = 0, nUniformChunks = 0;
   uint32_t nPatClasses  = 0;
   double patBytes       = 0.0;
+  // single precision (sb_crs_upload_f32 / sb_scs_upload_f32): prec = 1, the values in valf and val == NULL; it streams the
+  // reference layout only (no mirror, no placement tuner)
+  int prec    = 2; // the reference's PRECISION: 1 single, 2 double
+  float* valf = nullptr;
 };
 
 // global ids of the halo columns of the matrix about to be uploaded (sb_set_external_ids); consumed by the next upload
@@ -329,6 +334,11 @@ struct sb_cg {
   bool started;
   CgScalars hostS;   // staging copy for the H2D of the control block
   double* partials2 = nullptr; // level-0 partials of r.r (the p.Ap ones stay in `partials` while it reads them)
+  // single precision (sb_cg_create_f32; sbhip_sp.inc.h): prec = 1 and the loop's state below; the double members stay NULL
+  int prec = 2;
+  float *rf = nullptr, *pf = nullptr, *Apf = nullptr, *xf = nullptr, *bf = nullptr, *xexactf = nullptr;
+  CgScalarsF* SF = nullptr;
+  float *partialsF = nullptr, *partials2F = nullptr, *rrHistF = nullptr, *pApHistF = nullptr;
 };
 
 // ===========================================================================
@@ -637,3 +647,4 @@ void sb_event_destroy(void* ev) { HIP_CHECK(hipEventDestroy((hipEvent_t)ev)); }
 #include "sbhip_launch.inc.h"
 #include "sbhip_comm.inc.h"
 #include "sbhip_cg.inc.h"
+#include "sbhip_sp.inc.h"

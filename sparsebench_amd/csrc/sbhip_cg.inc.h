@@ -5,6 +5,16 @@
 // ===========================================================================
 enum { R_WAXPBY = 0, R_SPMVM = 1, R_DDOT = 2, R_COMM = 3 };
 
+// single precision (sbhip_sp.inc.h): the sb_cg_* calls below hand a solver made by sb_cg_create_f32 (prec 1) to these
+static void sp_cg_free_arrays(sb_cg* s);
+static int sp_launches_per_body(const sb_cg* s);
+static void sp_cg_start(sb_cg* s, int itermax, double eps);
+static void sp_cg_run_iters(sb_cg* s, int iters);
+static int sp_cg_finish(sb_cg* s);
+static int sp_cg_history(const sb_cg* s, double* rr_out, int rr_cap, double* pAp_out, int pAp_cap, int* n_pAp);
+static void sp_cg_counters(const sb_cg* s, int out[5]);
+static double sp_cg_check_residual(const sb_cg* s);
+
 // events that time kernels inside the loop: created without the system-scope fence a default event carries (SB_EVENT_FLAGS
 // overrides the creation flags; 0 = default events)
 static unsigned timing_event_flags()
@@ -67,6 +77,7 @@ static void apply_dot_order(sb_cg* s);
 sb_cg* sb_cg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host)
 {
   need_init();
+  SB_NEED_PREC(m, 2, "sb_cg_create");
   sb_cg* s = new sb_cg();
   s->A = m, s->halo = halo, s->nr = m->nr, s->nc = m->nc;
   if (halo && halo->nr != m->nr) SB_FATAL("halo plan and matrix disagree on nr");
@@ -141,6 +152,7 @@ void sb_cg_free(sb_cg* s)
   if (s->vecFromArena) const_cast<sb_matrix*>(s->A)->vecArenaBusy = false; // r, Ap, x, b, both p buffers, xexact: back to the matrix
   else sb_free(s->vecSlab);
   sb_free(s->S), sb_free(s->partials), sb_free(s->rr_hist), sb_free(s->pAp_hist), sb_free(s->partials2);
+  if (s->prec == 1) sp_cg_free_arrays(s);
   delete s;
 }
 
@@ -211,6 +223,7 @@ static bool fusep_plan(sb_cg* s)
 int sb_cg_launches_per_body(sb_cg* s)
 {
   if (s->seqLatched < 0) apply_dot_order(s); // (the process default may have changed since the last call)
+  if (s->prec == 1) return sp_launches_per_body(s);
   int base = fusep_plan(s) ? 4 : s->fused ? 5 : 0;
   if (base >= 4 && fusealpha_plan(s, fusep_plan(s) ? 1 : pAp_is_level1(s), 1024u)) base -= 1; // (alpha step inside the r update)
   if (base >= 4 && fusebeta_plan(s, 1024u)) base -= 1;                                          // (beta step inside the p update)
@@ -229,7 +242,7 @@ int sb_cg_launches_per_body(sb_cg* s)
 int sb_cg_collectives_per_body(sb_cg* s)
 {
   if (s->seqLatched < 0) apply_dot_order(s);
-  if (!multi_rank() || !s->fused) return 0;
+  if (!multi_rank() || !s->fused || s->prec == 1) return 0;
   return (p2p_dots() ? 0 : 2) + (s->halo && !halo_p2p_active(s->halo) ? 1 : 0);
 }
 
@@ -243,7 +256,7 @@ void sb_cg_set_fuse_p(sb_cg* s, int on)
 int sb_cg_fuse_p(sb_cg* s)
 {
   if (s->seqLatched < 0) apply_dot_order(s);
-  return fusep_plan(s) ? 1 : 0;
+  return s->prec == 2 && fusep_plan(s) ? 1 : 0;
 }
 
 // hipGraph replay of a loop body was measured slower (-7 % at 128^3, -13 ... -35 % at 64^3: docs/LAB_NOTES.md) and removed;
@@ -308,6 +321,7 @@ int sb_cg_phase_ms(sb_cg* s, double ms_out[8], int count_out[8])
 
 void sb_cg_counters(const sb_cg* s, int out[5])
 { // stop, stop_next, iters, n_rr, n_pAp of the device control block
+  if (s->prec == 1) return sp_cg_counters(s, out);
   HIP_CHECK(hipStreamSynchronize(g.stream));
   CgScalars h;
   HIP_CHECK(hipMemcpy(&h, s->S, sizeof h, hipMemcpyDeviceToHost));
@@ -673,6 +687,7 @@ static void ensure_hist(sb_cg* s, int cap)
 void sb_cg_start(sb_cg* s, int itermax, double eps)
 {
   need_init();
+  if (s->prec == 1) return sp_cg_start(s, itermax, eps);
   const uint32_t n = s->nr;
   s->started      = false;
   s->seqLatched   = -1;
@@ -726,6 +741,7 @@ void sb_cg_run_iters(sb_cg* s, int iters)
 {
   need_init();
   if (!s->started) SB_FATAL("sb_cg_run_iters before sb_cg_start");
+  if (s->prec == 1) return sp_cg_run_iters(s, iters);
   phase_mark(s, -1);
   for (int i = 0; i < iters; i++) loop_body(s, s->k_next++);
   flush_beta_fold(s); // every call leaves the loop state complete (counters, history, stop flag)
@@ -734,6 +750,7 @@ void sb_cg_run_iters(sb_cg* s, int iters)
 int sb_cg_finish(sb_cg* s)
 {
   need_init();
+  if (s->prec == 1) return sp_cg_finish(s);
   if (s->nr) { // the x update the last body left to "the next p update": nobody comes after it
     // (fused p update: body k left p_k in pbuf[k & 1]; which body ran last is on the device -- n_pAp -- not on the host)
     const bool fp = fusep_plan(s);
@@ -791,6 +808,7 @@ int sb_cg_solve(sb_cg* s, int itermax, double eps)
 int sb_cg_history(const sb_cg* s, double* rr_out, int rr_cap, double* pAp_out, int pAp_cap, int* n_pAp)
 {
   need_init();
+  if (s->prec == 1) return sp_cg_history(s, rr_out, rr_cap, pAp_out, pAp_cap, n_pAp);
   HIP_CHECK(hipStreamSynchronize(g.stream));
   CgScalars h;
   HIP_CHECK(hipMemcpy(&h, s->S, sizeof h, hipMemcpyDeviceToHost));
@@ -807,6 +825,7 @@ int sb_cg_history(const sb_cg* s, double* rr_out, int rr_cap, double* pAp_out, i
 void sb_cg_solution(const sb_cg* s, double* x_host)
 {
   need_init();
+  if (s->prec == 1) SB_FATAL("sb_cg_solution on a single-precision solver: use sb_cg_solution_f32");
   double* tmp = scratch_ws(1, s->nr);
   sb_unpermute(s->A, s->x, tmp);
   sb_d2h(x_host, tmp, (size_t)s->nr * sizeof(double));
@@ -815,6 +834,7 @@ void sb_cg_solution(const sb_cg* s, double* x_host)
 double sb_cg_check_residual(const sb_cg* s)
 {
   need_init();
+  if (s->prec == 1) return sp_cg_check_residual(s);
   if (!s->xexact || s->nr == 0) return 0.0;
   const uint32_t blocks = stream_grid(s->nr, 256);
   double* q             = scratch_partials(blocks);

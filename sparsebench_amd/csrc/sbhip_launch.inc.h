@@ -172,6 +172,7 @@ static void launch_spmv_fusep(const sb_matrix* m, const double* pold, const doub
 void sb_spmv_native(const sb_matrix* m, const double* x, double* y)
 {
   need_init();
+  SB_NEED_PREC(m, 2, "sb_spmv_native");
   launch_spmv(m, x, y, nullptr, nullptr);
 }
 
@@ -182,6 +183,7 @@ static int spmv_dot_kind(const sb_matrix* m) { return (m->fmt == 1 ? m->C == 64 
 int sb_spmv_native_dot(const sb_matrix* m, const double* x, double* y, double* partials_dev)
 { // the product with the fused partials of x . y, as the CG loop launches it for p . Ap
   need_init();
+  SB_NEED_PREC(m, 2, "sb_spmv_native_dot");
   const int kind = spmv_dot_kind(m);
   if (!kind) return 0;
   launch_spmv(m, x, y, partials_dev, nullptr);
@@ -191,6 +193,7 @@ int sb_spmv_native_dot(const sb_matrix* m, const double* x, double* y, double* p
 void sb_permute(const sb_matrix* m, const double* in_orig, double* out_perm)
 {
   need_init();
+  SB_NEED_PREC(m, 2, "sb_permute");
   if (!m->permuted) {
     if (in_orig != out_perm) sb_d2d(out_perm, in_orig, (size_t)m->nr * sizeof(double));
     return;
@@ -203,6 +206,7 @@ void sb_permute(const sb_matrix* m, const double* in_orig, double* out_perm)
 void sb_unpermute(const sb_matrix* m, const double* in_perm, double* out_orig)
 {
   need_init();
+  SB_NEED_PREC(m, 2, "sb_unpermute");
   if (!m->permuted) {
     if (in_perm != out_orig) sb_d2d(out_orig, in_perm, (size_t)m->nr * sizeof(double));
     return;
@@ -215,6 +219,7 @@ void sb_unpermute(const sb_matrix* m, const double* in_perm, double* out_orig)
 void sb_spmv(const sb_matrix* m, const double* x, double* y)
 {
   need_init();
+  SB_NEED_PREC(m, 2, "sb_spmv");
   if (!m->permuted) {
     launch_spmv(m, x, y, nullptr, nullptr);
     return;

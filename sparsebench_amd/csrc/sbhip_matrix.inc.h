@@ -16,11 +16,23 @@ static void build_crs_mirror(sb_matrix* m, const uint32_t* rowPtr, const uint32_
 static void tune_matrix_placement(sb_matrix* m); // (sbhip_launch.inc.h, behind launch_spmv)
 static bool g_tunePlacement = true;               // off while an upload builds a device-private mirror (its reference arrays are freed again)
 
-sb_matrix* sb_crs_upload(uint32_t nr, uint32_t nc, const uint32_t* rowPtr, const uint32_t* colInd,
-    const double* val)
+// crossing precisions is an error: an fp64 entry point on a single-precision matrix, or the other way round (file:line of the call)
+#define SB_NEED_PREC(m, p, fn)                                                                                            \
+  do {                                                                                                                    \
+    if ((m)->prec != (p))                                                                                                 \
+      SB_FATAL("%s: the matrix is %s precision (uploaded with %s); use the %s entry point", fn,                            \
+          (m)->prec == 1 ? "single" : "double", (m)->prec == 1 ? "an _f32 upload" : "sb_crs_upload / sb_scs_upload",     \
+          (m)->prec == 1 ? "_f32" : "fp64");                                                                               \
+  } while (0)
+
+// what the fp64 and the fp32 CRS uploads share: checks, the two kernels' row tables, rowPtr and colInd; the values (elemBytes
+// each, 64 zeroed elements of slack behind them) go to val (prec 2) or valf (prec 1)
+static sb_matrix* crs_upload_common(uint32_t nr, uint32_t nc, const uint32_t* rowPtr, const uint32_t* colInd, const void* val,
+    int prec)
 {
   need_init();
   sb_matrix* m = new sb_matrix();
+  m->prec = prec;
   m->fmt = 0, m->nr = nr, m->nc = nc, m->nnz = rowPtr[nr];
   for (uint32_t i = 0; i < nr; i++)
     if (rowPtr[i + 1] < rowPtr[i]) SB_FATAL("CRS rowPtr not monotone at row %u", i);
@@ -62,14 +74,25 @@ sb_matrix* sb_crs_upload(uint32_t nr, uint32_t nc, const uint32_t* rowPtr, const
   }
   m->rowPtr     = (uint32_t*)upload(rowPtr, ((size_t)nr + 1) * sizeof(uint32_t));
   // (64 zeroed elements of slack behind the arrays)
+  const size_t eb = prec == 1 ? sizeof(float) : sizeof(double);
+  char* v        = nullptr;
   HIP_CHECK(hipMalloc(&m->colInd, ((size_t)m->nnz + 64) * sizeof(uint32_t)));
-  HIP_CHECK(hipMalloc(&m->val, ((size_t)m->nnz + 64) * sizeof(double)));
+  HIP_CHECK(hipMalloc(&v, ((size_t)m->nnz + 64) * eb));
   HIP_CHECK(hipMemset(m->colInd + m->nnz, 0, 64 * sizeof(uint32_t)));
-  HIP_CHECK(hipMemset(m->val + m->nnz, 0, 64 * sizeof(double)));
+  HIP_CHECK(hipMemset(v + (size_t)m->nnz * eb, 0, 64 * eb));
   if (m->nnz) {
     HIP_CHECK(hipMemcpy(m->colInd, colInd, (size_t)m->nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(m->val, val, (size_t)m->nnz * sizeof(double), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(v, val, (size_t)m->nnz * eb, hipMemcpyHostToDevice));
   }
+  if (prec == 1) m->valf = reinterpret_cast<float*>(v);
+  else m->val = reinterpret_cast<double*>(v);
+  return m;
+}
+
+sb_matrix* sb_crs_upload(uint32_t nr, uint32_t nc, const uint32_t* rowPtr, const uint32_t* colInd,
+    const double* val)
+{
+  sb_matrix* m = crs_upload_common(nr, nc, rowPtr, colInd, val, 2);
   build_crs_mirror(m, rowPtr, colInd, val);
   tune_matrix_placement(m);
   return m;
@@ -1087,9 +1110,10 @@ void sb_set_external_ids(const uint32_t* global_ids, uint32_t n)
   g_externalIds.assign(global_ids, global_ids + (global_ids ? n : 0));
 }
 
-sb_matrix* sb_scs_upload(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigma, uint32_t nChunks,
+// what the fp64 and the fp32 Sell-C-sigma uploads share (see crs_upload_common)
+static sb_matrix* scs_upload_common(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigma, uint32_t nChunks,
     uint32_t nElems, const uint32_t* chunkPtr, const uint32_t* chunkLens, const uint32_t* colInd,
-    const double* val, const uint32_t* oldToNewPerm, const uint32_t* newToOldPerm)
+    const void* val, const uint32_t* oldToNewPerm, const uint32_t* newToOldPerm, int prec)
 {
   need_init();
   if (C == 0) SB_FATAL("SCS chunk height C must be >= 1");
@@ -1101,6 +1125,7 @@ sb_matrix* sb_scs_upload(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigma, u
   for (uint32_t k = 0; k < nElems; k++)
     if (colInd[k] >= nc) SB_FATAL("SCS colInd[%u]=%u out of range (nc=%u)", k, colInd[k], nc);
   sb_matrix* m = new sb_matrix();
+  m->prec = prec;
   m->fmt = 1, m->nr = nr, m->nc = nc, m->C = C, m->sigma = sigma, m->nChunks = nChunks;
   m->nElems = nElems, m->nrPadded = nChunks * C, m->nnz = nElems;
   int permuted = 0;
@@ -1115,14 +1140,18 @@ sb_matrix* sb_scs_upload(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigma, u
   m->chunkLens = (uint32_t*)upload(chunkLens, (size_t)nChunks * sizeof(uint32_t));
   // SCS_SLACK zeroed elements behind the data: the pipelined kernel prefetches up to
   // U-1 columns past a chunk's end
+  const size_t eb = prec == 1 ? sizeof(float) : sizeof(double);
+  char* v        = nullptr;
   HIP_CHECK(hipMalloc(&m->colInd, ((size_t)nElems + SCS_SLACK) * sizeof(uint32_t)));
-  HIP_CHECK(hipMalloc(&m->val, ((size_t)nElems + SCS_SLACK) * sizeof(double)));
+  HIP_CHECK(hipMalloc(&v, ((size_t)nElems + SCS_SLACK) * eb));
   HIP_CHECK(hipMemset(m->colInd + nElems, 0, SCS_SLACK * sizeof(uint32_t)));
-  HIP_CHECK(hipMemset(m->val + nElems, 0, SCS_SLACK * sizeof(double)));
+  HIP_CHECK(hipMemset(v + (size_t)nElems * eb, 0, SCS_SLACK * eb));
   if (nElems) {
     HIP_CHECK(hipMemcpy(m->colInd, colInd, (size_t)nElems * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(m->val, val, (size_t)nElems * sizeof(double), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(v, val, (size_t)nElems * eb, hipMemcpyHostToDevice));
   }
+  if (prec == 1) m->valf = reinterpret_cast<float*>(v);
+  else m->val = reinterpret_cast<double*>(v);
   if (permuted) {
     m->oldToNew = (uint32_t*)upload(oldToNewPerm, (size_t)nr * sizeof(uint32_t));
     m->newToOld = (uint32_t*)upload(newToOldPerm, (size_t)nr * sizeof(uint32_t));
@@ -1131,6 +1160,15 @@ sb_matrix* sb_scs_upload(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigma, u
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(g.stream));
   }
+  return m;
+}
+
+sb_matrix* sb_scs_upload(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigma, uint32_t nChunks,
+    uint32_t nElems, const uint32_t* chunkPtr, const uint32_t* chunkLens, const uint32_t* colInd,
+    const double* val, const uint32_t* oldToNewPerm, const uint32_t* newToOldPerm)
+{
+  sb_matrix* m = scs_upload_common(nr, nc, C, sigma, nChunks, nElems, chunkPtr, chunkLens, colInd, val, oldToNewPerm,
+      newToOldPerm, 2);
   build_packed(m, val, oldToNewPerm);
   build_lds_windows(m, chunkPtr, chunkLens, colInd, val, oldToNewPerm);
   build_patterns(m, chunkPtr, chunkLens, colInd, val, oldToNewPerm);
@@ -1284,7 +1322,7 @@ void sb_matrix_free(sb_matrix* m)
     m->colInd = nullptr, m->val = nullptr;
   }
   sb_free(m->rowPtr), sb_free(m->rowBlocks), sb_free(m->tileRow), sb_free(m->chunkPtr), sb_free(m->chunkLens);
-  sb_free(m->oldToNew), sb_free(m->newToOld), sb_free(m->colInd), sb_free(m->val);
+  sb_free(m->oldToNew), sb_free(m->newToOld), sb_free(m->colInd), sb_free(m->val), sb_free(m->valf);
   sb_free(m->pmeta), sb_free(m->pidx), sb_free(m->pcodes), sb_free(m->pdict);
   if (m->patSegs != m->tileSegs) sb_free(m->patSegs);
   sb_free(m->tileSegPtr), sb_free(m->tileSegs), sb_free(m->pslots);
@@ -1299,6 +1337,7 @@ int sb_matrix_pack_level(const sb_matrix* m) { return m->packLevel; }
 void sb_matrix_use_packed(sb_matrix* m, int mode)
 { // 5: the pattern kernel on masked row programs (pack.hip.h level 6) where the matrix has them; any other mode, or a matrix
   // without them: the reference-layout stream (0)
+  if (mode != 0) SB_NEED_PREC(m, 2, "sb_matrix_use_packed (a single-precision matrix streams its reference layout only)");
   const sb_matrix* pm = m->fmt == 0 ? m->mirror : m;
   m->usePacked        = mode >= 5 && pm && pm->mHdrs ? 5 : 0;
 }
@@ -1338,6 +1377,9 @@ uint32_t sb_matrix_nc(const sb_matrix* m) { return m->nc; }
 int sb_matrix_is_permuted(const sb_matrix* m) { return m->permuted; }
 double sb_matrix_spmv_bytes(const sb_matrix* m)
 {
+  if (m->prec == 1) // 4-byte values, x and y: CRS 8*nnz + 4*(nr+1) + 4*nr + 4*nc ; SCS 8*nElems + 8*nChunks + 4*nrPadded + 4*nc
+    return m->fmt == 0 ? 8.0 * m->nnz + 4.0 * ((double)m->nr + 1) + 4.0 * m->nr + 4.0 * m->nc
+                       : 8.0 * m->nElems + 8.0 * m->nChunks + 4.0 * m->nrPadded + 4.0 * m->nc;
   if (m->fmt == 0)
     return 12.0 * m->nnz + 4.0 * ((double)m->nr + 1) + 8.0 * m->nr + 8.0 * m->nc;
   return 12.0 * m->nElems + 8.0 * m->nChunks + 8.0 * m->nrPadded + 8.0 * m->nc;

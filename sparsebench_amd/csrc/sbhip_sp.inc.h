@@ -1,0 +1,438 @@
+// sbhip_sp.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context): single
+// precision, the reference's FLOAT_TYPE=SP build (src/util.h:47-51).  Matrices, the reference-shaped operations and the CG loop
+// on float data, over the kernels of kernels_sp.hip.h.  One rank only: the halo exchange and the all-reduce of the CG scalars
+// carry doubles.  An SP matrix always streams its reference layout: no compressed mirror, no masked row programs,
+// no p update inside the SpMV -- and no placement tuner: its proxy is an fp64 loop body.
+// ===========================================================================
+// single precision
+// ===========================================================================
+static void sp_single_rank(const char* fn)
+{
+  if (multi_rank() || sb_comm_size() > 1)
+    SB_FATAL("%s: single precision runs on one rank only (%d ranks here): the halo exchange and the in-kernel all-reduce of the "
+             "CG scalars carry doubles -- f32 halo push / pull and a float all-reduce are not built yet", fn, sb_comm_size());
+}
+
+sb_matrix* sb_crs_upload_f32(uint32_t nr, uint32_t nc, const uint32_t* rowPtr, const uint32_t* colInd, const float* val)
+{
+  need_init();
+  sp_single_rank("sb_crs_upload_f32");
+  return crs_upload_common(nr, nc, rowPtr, colInd, val, 1); // (no mirror, no placement tuner: see the head of this file)
+}
+
+sb_matrix* sb_scs_upload_f32(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigma, uint32_t nChunks, uint32_t nElems,
+    const uint32_t* chunkPtr, const uint32_t* chunkLens, const uint32_t* colInd, const float* val, const uint32_t* oldToNewPerm,
+    const uint32_t* newToOldPerm)
+{
+  need_init();
+  sp_single_rank("sb_scs_upload_f32");
+  return scs_upload_common(nr, nc, C, sigma, nChunks, nElems, chunkPtr, chunkLens, colInd, val, oldToNewPerm, newToOldPerm, 1);
+}
+
+int sb_matrix_precision(const sb_matrix* m) { return m->prec; }
+
+static float* sp_scratch(int which, size_t n) { return reinterpret_cast<float*>(scratch_ws(which, (n + 1) / 2)); }
+
+// y = A x in the matrix's device row order; dotL1 != NULL (Sell-64 only): the level-1 values of x . y as well
+static void launch_spmv_f32(const sb_matrix* m, const float* x, float* y, float* dotL1, const int* stop)
+{
+  if (m->nr == 0) return;
+  if (m->fmt == 0) {
+    if (dotL1) SB_FATAL("the single-precision CRS kernel has no fused dot: the CG loop adds a dot pass");
+    if (m->tileRow) {
+      const uint32_t per = (m->nCrsTiles + 7) / 8;
+      SB_SPMV_LAUNCH(spmv_crs_split_f32, dim3(per * 8), dim3(CRS_THREADS), 0, g.stream, m->tileRow, m->rowPtr, m->colInd, m->valf,
+          x, y, m->nCrsTiles, m->crsT, m->nnz, per, stop);
+    } else {
+      const uint32_t per = (m->nRowBlocks + 7) / 8;
+      SB_SPMV_LAUNCH(spmv_crs_stream_f32, dim3(per * 8), dim3(CRS_THREADS), 0, g.stream, m->rowBlocks, m->rowPtr, m->colInd,
+          m->valf, x, y, m->nRowBlocks, per, stop);
+    }
+  } else if (m->C == 64) {
+    const uint32_t nBlocks = (m->nChunks + 3) / 4, per = (nBlocks + 7) / 8;
+    if (dotL1)
+      SB_SPMV_LAUNCH(spmv_scs64_f32<true>, dim3(per * 8), dim3(256), 0, g.stream, m->chunkPtr, m->chunkLens, m->colInd, m->valf, x,
+          y, m->nr, m->nChunks, per, dotL1, stop);
+    else
+      SB_SPMV_LAUNCH(spmv_scs64_f32<false>, dim3(per * 8), dim3(256), 0, g.stream, m->chunkPtr, m->chunkLens, m->colInd, m->valf,
+          x, y, m->nr, m->nChunks, per, (float*)nullptr, stop);
+  } else {
+    if (dotL1) SB_FATAL("fused dot is a Sell-64 feature");
+    SB_SPMV_LAUNCH(spmv_scs_generic_f32, dim3((m->nrPadded + 255) / 256), dim3(256), 0, g.stream, m->chunkPtr, m->chunkLens,
+        m->colInd, m->valf, x, y, m->nr, m->nrPadded, m->C, stop);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+void sb_permute_f32(const sb_matrix* m, const float* in_orig, float* out_perm)
+{
+  need_init();
+  SB_NEED_PREC(m, 1, "sb_permute_f32");
+  if (!m->permuted) {
+    if (in_orig != out_perm) sb_d2d(out_perm, in_orig, (size_t)m->nr * sizeof(float));
+    return;
+  }
+  hipLaunchKernelGGL(gather_f32_k, dim3(stream_grid(m->nr, 256)), dim3(256), 0, g.stream, m->nr, m->newToOld, in_orig, out_perm);
+  HIP_CHECK(hipGetLastError());
+}
+
+void sb_unpermute_f32(const sb_matrix* m, const float* in_perm, float* out_orig)
+{
+  need_init();
+  SB_NEED_PREC(m, 1, "sb_unpermute_f32");
+  if (!m->permuted) {
+    if (in_perm != out_orig) sb_d2d(out_orig, in_perm, (size_t)m->nr * sizeof(float));
+    return;
+  }
+  hipLaunchKernelGGL(gather_f32_k, dim3(stream_grid(m->nr, 256)), dim3(256), 0, g.stream, m->nr, m->oldToNew, in_perm, out_orig);
+  HIP_CHECK(hipGetLastError());
+}
+
+void sb_spmv_f32(const sb_matrix* m, const float* x, float* y)
+{
+  need_init();
+  SB_NEED_PREC(m, 1, "sb_spmv_f32");
+  if (!m->permuted) {
+    launch_spmv_f32(m, x, y, nullptr, nullptr);
+    return;
+  }
+  float* xp = sp_scratch(0, m->nc);
+  float* yp = sp_scratch(1, m->nr);
+  sb_permute_f32(m, x, xp);
+  if (m->nc > m->nr) sb_d2d(xp + m->nr, x + m->nr, (size_t)(m->nc - m->nr) * sizeof(float));
+  launch_spmv_f32(m, xp, yp, nullptr, nullptr);
+  sb_unpermute_f32(m, yp, y);
+}
+
+int sb_spmv_native_dot_f32(const sb_matrix* m, const float* x, float* y, float* l1_dev)
+{
+  need_init();
+  SB_NEED_PREC(m, 1, "sb_spmv_native_dot_f32");
+  if (!(m->fmt == 1 && m->C == 64)) {
+    launch_spmv_f32(m, x, y, nullptr, nullptr);
+    return 0;
+  }
+  launch_spmv_f32(m, x, y, l1_dev, nullptr);
+  return 2;
+}
+
+void sb_waxpby_f32(uint32_t n, float alpha, const float* x, float beta, const float* y, float* w)
+{
+  need_init();
+  if (n == 0) return;
+  hipLaunchKernelGGL(waxpby_f32_k, dim3(stream_grid(n, 256)), dim3(256), 0, g.stream, n, alpha, x, beta, y, w, (const int*)nullptr);
+  HIP_CHECK(hipGetLastError());
+}
+
+static void launch_dot_l0_f32(uint32_t n, const float* a, const float* b, float* partials, const int* stop)
+{
+  if (n == 0) return;
+  const uint32_t nG = ((n + 255u) >> 8) * 4u;
+  hipLaunchKernelGGL(dot_l0_f32_k, dim3(stream_grid(nG, 4)), dim3(256), 0, g.stream, n, a, b, partials, stop);
+  HIP_CHECK(hipGetLastError());
+}
+static void launch_dot_seq_f32(uint32_t n, const float* a, const float* b, const uint32_t* perm, float* out, const int* stop)
+{
+  hipLaunchKernelGGL(dot_seq_f32_k, dim3(1), dim3(1024), 0, g.stream, n, a, b, perm, out, stop);
+  HIP_CHECK(hipGetLastError());
+}
+
+void sb_ddot_partials_f32(uint32_t n, const float* x, const float* y, float* partials_dev)
+{
+  need_init();
+  launch_dot_l0_f32(n, x, y, partials_dev, nullptr);
+}
+
+void sb_reduce_final_f32(uint32_t m, const float* partials_dev, float* result_dev)
+{
+  need_init();
+  hipLaunchKernelGGL(reduce_final_f32_k, dim3(1), dim3(1024), 0, g.stream, m, partials_dev, result_dev, 0);
+  HIP_CHECK(hipGetLastError());
+}
+
+float sb_ddot_f32(uint32_t n, const float* x, const float* y)
+{
+  need_init();
+  sp_single_rank("sb_ddot_f32");
+  float* res = reinterpret_cast<float*>(g.scalar);
+  if (sb_dot_order() == 1) {
+    launch_dot_seq_f32(n, x, y, nullptr, res, nullptr);
+  } else {
+    const uint32_t m = (n + 255u) / 256u;
+    float* q         = reinterpret_cast<float*>(scratch_partials(2 * (size_t)m + 1));
+    sb_ddot_partials_f32(n, x, y, q);
+    sb_reduce_final_f32(m, q, res);
+  }
+  float r = 0.f;
+  sb_d2h(&r, res, sizeof r);
+  return r;
+}
+
+// ---- CG in single precision (src/CGSolver.c:62-141 of the SP build) ------------------------------------------------------------
+// The same loop shapes as fp64, in float:
+//   fused (tree order, the default): p update with the beta step at its head and the owed x update | SpMV with the p.Ap level-1
+//     values (Sell-64; CRS and generic C: SpMV, then a level-1 dot pass) | r update with the alpha step and the r.r level-1
+//     values -- 3 launches per body on Sell-64, 4 otherwise;
+//   the reference's op list (fused = 0, and always under seq): waxpby, spMVM and ddot as separate launches, every dot either the
+//     tree order's level-0 partials or the sequential sum.
+// Both give the same bits under the tree order.
+sb_cg* sb_cg_create_f32(const sb_matrix* m, sb_halo* halo, const float* b_host, const float* xexact_host)
+{
+  need_init();
+  SB_NEED_PREC(m, 1, "sb_cg_create_f32");
+  sp_single_rank("sb_cg_create_f32");
+  sb_cg* s = new sb_cg();
+  s->prec = 1, s->A = m, s->halo = halo, s->nr = m->nr, s->nc = m->nc;
+  if (halo && halo->nr != m->nr) SB_FATAL("halo plan and matrix disagree on nr");
+  const size_t nb = (size_t)m->nr * sizeof(float);
+  s->rf = (float*)sb_malloc(nb), s->Apf = (float*)sb_malloc(nb), s->xf = (float*)sb_malloc(nb), s->bf = (float*)sb_malloc(nb);
+  s->pf = (float*)sb_malloc((size_t)m->nc * sizeof(float));
+  float* tmp = sp_scratch(0, m->nr);
+  sb_h2d(tmp, b_host, nb);
+  sb_permute_f32(m, tmp, s->bf);
+  if (xexact_host) {
+    s->xexactf = (float*)sb_malloc(nb);
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    sb_h2d(tmp, xexact_host, nb);
+    sb_permute_f32(m, tmp, s->xexactf);
+  }
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  s->SF = (CgScalarsF*)sb_malloc(sizeof(CgScalarsF));
+  HIP_CHECK(hipMemset(s->SF, 0, sizeof(CgScalarsF)));
+  s->nPartials  = (m->nr + 255) / 256;
+  const size_t np = (4 * (size_t)s->nPartials + 4) * sizeof(float);
+  s->partialsF = (float*)sb_malloc(np), s->partials2F = (float*)sb_malloc(np);
+  HIP_CHECK(hipMemset(s->partialsF, 0, np));
+  HIP_CHECK(hipMemset(s->partials2F, 0, np));
+  s->fused = 1, s->timing = false, s->evUsed = 0, s->loop_ms = 0.f, s->spmvTiming = false, s->spmvEvUsed = 0;
+  s->k_next = 1, s->started = false, s->hist_cap = 0;
+  HIP_CHECK(hipEventCreate(&s->evLoop0));
+  HIP_CHECK(hipEventCreate(&s->evLoop1));
+  for (double& v : s->region_ms) v = 0.0;
+  apply_dot_order(s);
+  return s;
+}
+
+static void sp_cg_free_arrays(sb_cg* s)
+{
+  sb_free(s->rf), sb_free(s->pf), sb_free(s->Apf), sb_free(s->xf), sb_free(s->bf), sb_free(s->xexactf);
+  sb_free(s->SF), sb_free(s->partialsF), sb_free(s->partials2F), sb_free(s->rrHistF), sb_free(s->pApHistF);
+}
+
+static bool sp_spmv_has_dot(const sb_cg* s) { return s->A->fmt == 1 && s->A->C == 64; }
+static int sp_launches_per_body(const sb_cg* s) { return s->fused ? (sp_spmv_has_dot(s) ? 3 : 4) : 0; }
+
+// one dot of the reference's op list into partialsF: tree level-0 partials, or (seq) the sequential sum in original row order
+static void sp_dot(sb_cg* s, const float* a, const float* b, const int* stop)
+{
+  if (s->seqLatched > 0) launch_dot_seq_f32(s->nr, a, b, s->A->permuted ? s->A->oldToNew : nullptr, s->partialsF, stop);
+  else launch_dot_l0_f32(s->nr, a, b, s->partialsF, stop);
+}
+// levels 1-2 of the dot in q + the scalar step (seq: q[0] is the whole sum)
+template <int MODE> static void sp_scalar(sb_cg* s, const float* q, int l1, int defer_x)
+{
+  uint32_t m = s->nPartials;
+  if (s->seqLatched > 0) m = 1, l1 = 1;
+  hipLaunchKernelGGL((cg_scalar_f32_k<MODE>), dim3(1), dim3(1024), 0, g.stream, m, q, s->SF, s->rrHistF, s->pApHistF, defer_x, l1);
+  HIP_CHECK(hipGetLastError());
+}
+static void sp_flush_beta(sb_cg* s)
+{
+  if (!s->betaFold) return;
+  sp_scalar<1>(s, s->partials2F, 1, 1);
+  mark(s, R_DDOT);
+  phase_mark(s, PH_BETA);
+  s->betaFold = 0;
+}
+
+static void sp_loop_body(sb_cg* s, int k)
+{
+  const uint32_t n = s->nr;
+  const int* stop  = &s->SF->stop;
+  const uint32_t vb = 1024u, capV = (uint32_t)g.prop.multiProcessorCount * 2u;
+  const dim3 gridV(std::max(1u, std::min(capV, (n / 4 + vb) / vb))), blockV(vb);
+  const dim3 gridW(stream_grid(n, 256)), blockW(256);
+  if (k == 1) { // p = r + 0.0 r (:109)
+    if (n) hipLaunchKernelGGL(cg_update_p_f32<0>, gridV, blockV, 0, g.stream, n, s->rf, s->pf, (float*)nullptr, s->SF, 1, 0u,
+        (const float*)nullptr, (float*)nullptr);
+  } else if (s->fused) { // beta step at the head, p = r + beta p, the owed x += alpha p (:111-116, :127)
+    if (s->betaFold) {
+      hipLaunchKernelGGL(cg_update_p_f32<1>, gridV, blockV, 0, g.stream, n, s->rf, s->pf, s->xf, s->SF, 0, s->nPartials,
+          (const float*)s->partials2F, s->rrHistF);
+      s->betaFold = 0;
+    } else if (n)
+      hipLaunchKernelGGL(cg_update_p_f32<0>, gridV, blockV, 0, g.stream, n, s->rf, s->pf, s->xf, s->SF, 0, 0u, (const float*)nullptr,
+          (float*)nullptr);
+  } else { // rtrans = r.r ; beta ; p = r + beta p (:111-114)
+    sp_dot(s, s->rf, s->rf, stop);
+    phase_mark(s, PH_DOT_PASS);
+    sp_scalar<1>(s, s->partialsF, 0, 0);
+    mark(s, R_DDOT);
+    phase_mark(s, PH_BETA);
+    if (n) hipLaunchKernelGGL(cg_update_p_f32<0>, gridV, blockV, 0, g.stream, n, s->rf, s->pf, (float*)nullptr, s->SF, 0, 0u,
+        (const float*)nullptr, (float*)nullptr);
+  }
+  HIP_CHECK(hipGetLastError());
+  mark(s, R_WAXPBY);
+  phase_mark(s, PH_P_UPDATE);
+  // Ap = A p (:123) and p.Ap (:124-125)
+  const bool fusedDot = s->fused && sp_spmv_has_dot(s);
+  spmv_time_begin(s);
+  launch_spmv_f32(s->A, s->pf, s->Apf, fusedDot ? s->partialsF : nullptr, stop);
+  spmv_time_end(s);
+  mark(s, R_SPMVM);
+  phase_mark(s, PH_SPMV);
+  if (s->fused) {
+    if (!fusedDot && n) {
+      const uint32_t nG = (n + 255u) >> 8;
+      hipLaunchKernelGGL(dot_l1_f32_k, dim3(std::max(1u, std::min(capV, (nG + 15u) / 16u))), dim3(1024), 0, g.stream, n,
+          (const float*)s->pf, (const float*)s->Apf, s->partialsF, stop);
+      HIP_CHECK(hipGetLastError());
+      phase_mark(s, PH_DOT_PASS);
+    }
+    // alpha (:126) inside the r update: r = r - alpha Ap (:128) + the level-1 values of the next r.r; x += alpha p is owed
+    const uint32_t nG = (n + 255u) >> 8;
+    const dim3 gridR(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount, (nG + 15u) / 16u)));
+    hipLaunchKernelGGL(cg_update_r_f32<1>, gridR, dim3(1024), 0, g.stream, n, (const float*)s->Apf, s->rf, s->SF, s->partials2F,
+        stop, s->nPartials, (const float*)s->partialsF, s->rrHistF, s->pApHistF);
+    HIP_CHECK(hipGetLastError());
+    mark(s, R_WAXPBY);
+    phase_mark(s, PH_R_UPDATE);
+    s->betaFold = 1; // the beta step / loop test rides at the head of the next p update (sp_flush_beta where none follows)
+    return;
+  }
+  sp_dot(s, s->pf, s->Apf, stop);
+  phase_mark(s, PH_DOT_PASS);
+  sp_scalar<2>(s, s->partialsF, 0, 0);
+  mark(s, R_DDOT);
+  phase_mark(s, PH_ALPHA);
+  if (n) { // x = x + alpha p ; r = r + (-alpha) Ap (:127-128)
+    hipLaunchKernelGGL(axpy_sdev_f32_k, gridW, blockW, 0, g.stream, n, (const float*)s->xf, (const float*)&s->SF->alpha,
+        (const float*)s->pf, s->xf, stop);
+    hipLaunchKernelGGL(axpy_sdev_f32_k, gridW, blockW, 0, g.stream, n, (const float*)s->rf, (const float*)&s->SF->neg_alpha,
+        (const float*)s->Apf, s->rf, stop);
+    HIP_CHECK(hipGetLastError());
+    mark(s, R_WAXPBY);
+    phase_mark(s, PH_R_UPDATE);
+  }
+}
+
+static void sp_cg_start(sb_cg* s, int itermax, double eps)
+{
+  const uint32_t n = s->nr;
+  s->started    = false;
+  s->seqLatched = -1;
+  s->seqLatched = cg_seq(s) ? 1 : 0;
+  apply_dot_order(s);
+  if (itermax + 2 > s->hist_cap) {
+    sb_free(s->rrHistF), sb_free(s->pApHistF);
+    s->hist_cap = itermax + 2;
+    s->rrHistF  = (float*)sb_malloc((size_t)s->hist_cap * sizeof(float));
+    s->pApHistF = (float*)sb_malloc((size_t)s->hist_cap * sizeof(float));
+  }
+  s->timing = !s->fused;
+  s->evUsed = 0;
+  CgScalarsF h;
+  memset(&h, 0, sizeof h);
+  h.itermax = itermax, h.eps = (float)eps, h.hist_cap = s->hist_cap; // CG_FLOAT eps = (CG_FLOAT)param->eps (:64)
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  HIP_CHECK(hipMemcpy(s->SF, &h, sizeof h, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemsetAsync(s->xf, 0, (size_t)n * sizeof(float), g.stream)); // x0 = 0 (:28)
+  HIP_CHECK(hipMemsetAsync(s->pf, 0, (size_t)s->nc * sizeof(float), g.stream));
+  mark(s, -1);
+  // prologue, src/CGSolver.c:94-100: p = x + 0.0 x ; Ap = A p ; r = b + (-1.0) Ap ; rtrans = r.r
+  const dim3 gridW(stream_grid(n, 256)), blockW(256);
+  if (n) hipLaunchKernelGGL(waxpby_f32_k, gridW, blockW, 0, g.stream, n, 1.0f, (const float*)s->xf, 0.0f, (const float*)s->xf, s->pf,
+      (const int*)nullptr);
+  mark(s, R_WAXPBY);
+  launch_spmv_f32(s->A, s->pf, s->Apf, nullptr, nullptr);
+  mark(s, R_SPMVM);
+  if (n) hipLaunchKernelGGL(waxpby_f32_k, gridW, blockW, 0, g.stream, n, 1.0f, (const float*)s->bf, -1.0f, (const float*)s->Apf,
+      s->rf, (const int*)nullptr);
+  HIP_CHECK(hipGetLastError());
+  mark(s, R_WAXPBY);
+  sp_dot(s, s->rf, s->rf, nullptr);
+  sp_scalar<0>(s, s->partialsF, 0, 0);
+  mark(s, R_DDOT);
+  s->k_next = 1, s->started = true, s->betaFold = 0;
+}
+
+static void sp_cg_run_iters(sb_cg* s, int iters)
+{
+  phase_mark(s, -1);
+  for (int i = 0; i < iters; i++) sp_loop_body(s, s->k_next++);
+  sp_flush_beta(s); // every call leaves the loop state complete
+}
+
+static int sp_cg_finish(sb_cg* s)
+{
+  if (s->nr) {
+    hipLaunchKernelGGL(cg_x_finalize_f32, dim3(stream_grid(s->nr, 256)), dim3(256), 0, g.stream, s->nr, s->xf, (const float*)s->pf,
+        (const CgScalarsF*)s->SF);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemsetAsync(&s->SF->x_pending, 0, sizeof(int), g.stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  CgScalarsF h;
+  HIP_CHECK(hipMemcpy(&h, s->SF, sizeof h, hipMemcpyDeviceToHost));
+  if (s->timing) {
+    for (double& v : s->region_ms) v = 0.0;
+    for (size_t i = 1; i < s->evUsed; i++) {
+      float ms = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&ms, s->ev[i - 1], s->ev[i]));
+      if (s->evRegion[i] >= 0) s->region_ms[s->evRegion[i]] += ms;
+    }
+  }
+  s->timing     = false;
+  s->seqLatched = -1;
+  apply_dot_order(s);
+  return h.iters + 1;
+}
+
+static int sp_cg_history(const sb_cg* s, double* rr_out, int rr_cap, double* pAp_out, int pAp_cap, int* n_pAp)
+{ // the float values, exactly, in the double arrays of sb_cg_history
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  CgScalarsF h;
+  HIP_CHECK(hipMemcpy(&h, s->SF, sizeof h, hipMemcpyDeviceToHost));
+  int nrr = std::min(std::min(h.n_rr, s->hist_cap), rr_cap), npa = std::min(std::min(h.n_pAp, s->hist_cap), pAp_cap);
+  std::vector<float> t((size_t)std::max(std::max(nrr, npa), 1));
+  if (nrr > 0) HIP_CHECK(hipMemcpy(t.data(), s->rrHistF, (size_t)nrr * sizeof(float), hipMemcpyDeviceToHost));
+  for (int i = 0; i < nrr; i++) rr_out[i] = (double)t[i];
+  if (npa > 0) HIP_CHECK(hipMemcpy(t.data(), s->pApHistF, (size_t)npa * sizeof(float), hipMemcpyDeviceToHost));
+  for (int i = 0; i < npa; i++) pAp_out[i] = (double)t[i];
+  if (n_pAp) *n_pAp = std::max(npa, 0);
+  return std::max(nrr, 0);
+}
+
+static void sp_cg_counters(const sb_cg* s, int out[5])
+{
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  CgScalarsF h;
+  HIP_CHECK(hipMemcpy(&h, s->SF, sizeof h, hipMemcpyDeviceToHost));
+  out[0] = h.stop, out[1] = h.stop_next, out[2] = h.iters, out[3] = h.n_rr, out[4] = h.n_pAp;
+}
+
+void sb_cg_solution_f32(const sb_cg* s, float* x_host)
+{
+  need_init();
+  if (s->prec != 1) SB_FATAL("sb_cg_solution_f32 on a double-precision solver: use sb_cg_solution");
+  float* tmp = sp_scratch(1, s->nr);
+  sb_unpermute_f32(s->A, s->xf, tmp);
+  sb_d2h(x_host, tmp, (size_t)s->nr * sizeof(float));
+}
+
+static double sp_cg_check_residual(const sb_cg* s)
+{
+  if (!s->xexactf || s->nr == 0) return 0.0;
+  const uint32_t blocks = stream_grid(s->nr, 256);
+  float* q              = reinterpret_cast<float*>(scratch_partials(blocks));
+  hipLaunchKernelGGL(max_abs_diff_f32_k, dim3(blocks), dim3(256), 0, g.stream, s->nr, (const float*)s->xf,
+      (const float*)s->xexactf, q);
+  HIP_CHECK(hipGetLastError());
+  std::vector<float> h(blocks);
+  sb_d2h(h.data(), q, blocks * sizeof(float));
+  float m = 0.0f;
+  for (float v : h)
+    if (v > m) m = v;
+  return (double)m;
+}

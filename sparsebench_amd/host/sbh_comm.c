@@ -486,17 +486,30 @@ void sbh_comm_attach_halo(Comm* c, CG_UINT nr, const CG_UINT* oldToNewPerm)
 void commExchange(Comm* c, CG_UINT numRows, CG_FLOAT* x)
 {
   if (c->size == 1) return;
+#if PRECISION == 1
+  (void)numRows, (void)x;
+  fprintf(stderr, "%s:%d: commExchange: the single-precision build runs on one rank only (%d here): the halo exchange "
+                  "carries doubles\n", __FILE__, __LINE__, c->size);
+  exit(EXIT_FAILURE);
+#else
   if (!c->dev) sbh_comm_attach_halo(c, numRows, NULL);
   if (!sb_is_device_ptr(x)) {
     fprintf(stderr, "commExchange: x must live in HBM (sb_malloc) when running on %d ranks\n", c->size);
     exit(EXIT_FAILURE);
   }
   sb_halo_exchange((sb_halo*)c->dev, x);
+#endif
 }
 
 void commReduction(CG_FLOAT* v, int op)
 {
   if (!sb_is_initialized() || sb_comm_size() == 1) return;
+#if PRECISION == 1
+  (void)v, (void)op;
+  fprintf(stderr, "%s:%d: commReduction: the single-precision build runs on one rank only (%d here): the all-reduce "
+                  "carries doubles\n", __FILE__, __LINE__, sb_comm_size());
+  exit(EXIT_FAILURE);
+#else
   if (sb_is_device_ptr(v)) {
     sb_comm_reduction(v, op);
     return;
@@ -506,4 +519,5 @@ void commReduction(CG_FLOAT* v, int op)
   sb_comm_reduction(d, op);
   sb_d2h(v, d, sizeof(double));
   sb_free(d);
+#endif
 }

@@ -41,7 +41,7 @@ void sbh_layout_crs(CRSMatrix* m, GMatrix* im)
 void sbh_convert_crs(CRSMatrix* m, GMatrix* im)
 {
   sbh_layout_crs(m, im);
-  m->dev = sb_crs_upload(m->nr, m->nc, m->rowPtr, m->colInd, m->val);
+  m->dev = SBH_FP(sb_crs_upload)(m->nr, m->nc, m->rowPtr, m->colInd, m->val);
 }
 
 /* Sell-C-sigma.
@@ -139,6 +139,6 @@ void sbh_layout_scs(SCSMatrix* m, GMatrix* im)
 void sbh_convert_scs(SCSMatrix* m, GMatrix* im)
 {
   sbh_layout_scs(m, im);
-  m->dev = sb_scs_upload(m->nr, m->nc, m->C, m->sigma, m->nChunks, m->nElems, m->chunkPtr,
+  m->dev = SBH_FP(sb_scs_upload)(m->nr, m->nc, m->C, m->sigma, m->nChunks, m->nElems, m->chunkPtr,
       m->chunkLens, m->colInd, m->val, m->oldToNewPerm, m->newToOldPerm);
 }

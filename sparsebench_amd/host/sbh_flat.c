@@ -149,7 +149,7 @@ unsigned sbh_gm_scalar(sbh_gm* g, int which)
   }
 }
 
-void sbh_gm_copy(sbh_gm* g, unsigned* rowPtr, unsigned* col, double* val)
+void sbh_gm_copy(sbh_gm* g, unsigned* rowPtr, unsigned* col, CG_FLOAT* val)
 {
   for (CG_UINT i = 0; i <= g->gm.nr; i++) rowPtr[i] = g->gm.rowPtr[i];
   for (CG_UINT i = 0; i < g->gm.nnz; i++) col[i] = g->gm.entries[i].col, val[i] = g->gm.entries[i].val;
@@ -161,19 +161,22 @@ void sbh_gm_free(sbh_gm* g)
   free(g->gm.rowPtr), free(g->gm.entries), free(g);
 }
 
-const double* sbh_problem_values(sbh_problem* p) { return p->fmt == 0 ? p->crs.val : p->scs.val; }
+const CG_FLOAT* sbh_problem_values(sbh_problem* p) { return p->fmt == 0 ? p->crs.val : p->scs.val; }
 
-void sbh_problem_gm_entries(sbh_problem* p, unsigned* col, double* val)
+void sbh_problem_gm_entries(sbh_problem* p, unsigned* col, CG_FLOAT* val)
 {
   for (CG_UINT i = 0; i < p->nnzTrue; i++) col[i] = p->gm.entries[i].col, val[i] = p->gm.entries[i].val;
 }
 
+/* CG_FLOAT = float in the SP library (-DPRECISION=1): values, b and xexact are float there */
+int sbh_problem_precision(void) { return sizeof(CG_FLOAT) == sizeof(float) ? 1 : 2; }
+
 /* b and xexact of initVectors (src/CGSolver.c:25-36); xexact may be NULL */
-int sbh_problem_rhs(sbh_problem* p, double* b, double* xexact)
+int sbh_problem_rhs(sbh_problem* p, CG_FLOAT* b, CG_FLOAT* xexact)
 {
   const CG_UINT* len = p->fmt == 0 ? p->crs.rowNnz : p->scs.rowNnz;
   for (CG_UINT i = 0; i < p->gm.nr; i++) {
-    b[i] = p->generated ? 27.0 - ((double)((int)len[i] - 1)) : 1.0;
+    b[i] = p->generated ? 27.0 - ((CG_FLOAT)((int)len[i] - 1)) : 1.0;
     if (xexact) xexact[i] = 1.0;
   }
   return p->generated;

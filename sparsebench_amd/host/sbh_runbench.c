@@ -31,12 +31,21 @@ static double time_region(void (*fn)(void*), void* ctx, int reps)
 typedef struct {
   Matrix* m;
   CG_UINT n;
-  double *x, *y, *w, *scalar;
+  CG_FLOAT *x, *y, *w, *scalar, *q;
 } ctx_t;
 
 static void run_spmv(void* p) { ctx_t* c = (ctx_t*)p; spMVM(c->m, c->x, c->y); }
 static void run_waxpby(void* p) { ctx_t* c = (ctx_t*)p; waxpby(c->n, 1.0, c->y, 0.5, c->w, c->w); }
+#if PRECISION == 1
+static void run_ddot(void* p)
+{ /* the tree order's two stages (sb_ddot_f32 itself waits for its result) */
+  ctx_t* c = (ctx_t*)p;
+  sb_ddot_partials_f32(c->n, c->y, c->w, c->q);
+  sb_reduce_final_f32((c->n + 255u) / 256u, c->q, c->scalar);
+}
+#else
 static void run_ddot(void* p) { ctx_t* c = (ctx_t*)p; sb_ddot_async(c->n, c->y, c->w, c->scalar); }
+#endif
 
 int main(int argc, char** argv)
 {
@@ -73,20 +82,22 @@ int main(int argc, char** argv)
 
   ctx_t c;
   c.m = &m, c.n = g.nr;
-  c.x      = (double*)sb_malloc((size_t)g.nc * sizeof(double));
-  c.y      = (double*)sb_malloc((size_t)g.nr * sizeof(double));
-  c.w      = (double*)sb_malloc((size_t)g.nr * sizeof(double));
-  c.scalar = (double*)sb_malloc(sizeof(double));
-  double* ones = (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)g.nc + 1) * sizeof(double));
+  const size_t fb = sizeof(CG_FLOAT);
+  c.x      = (CG_FLOAT*)sb_malloc((size_t)g.nc * fb);
+  c.y      = (CG_FLOAT*)sb_malloc((size_t)g.nr * fb);
+  c.w      = (CG_FLOAT*)sb_malloc((size_t)g.nr * fb);
+  c.scalar = (CG_FLOAT*)sb_malloc(fb);
+  c.q      = (CG_FLOAT*)sb_malloc((4 * (((size_t)g.nr + 255) / 256) + 4) * fb);
+  CG_FLOAT* ones = (CG_FLOAT*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)g.nc + 1) * fb);
   for (CG_UINT i = 0; i < g.nc; i++) ones[i] = 1.0;
-  sb_h2d(c.x, ones, (size_t)g.nc * sizeof(double));
-  sb_h2d(c.w, ones, (size_t)g.nr * sizeof(double));
+  sb_h2d(c.x, ones, (size_t)g.nc * fb);
+  sb_h2d(c.w, ones, (size_t)g.nr * fb);
 
   const double tS = time_region(run_spmv, &c, reps);
   const double tW = time_region(run_waxpby, &c, reps);
   const double tD = time_region(run_ddot, &c, reps);
   const double n  = (double)g.nr;
-  const double bytesSpmvRef = 12.0 * (double)g.nnz; /* the reference's convention */
+  const double bytesSpmvRef = (double)(fb + sizeof(CG_UINT)) * (double)g.nnz; /* the reference's convention */
   const double bytesSpmv    = sb_matrix_spmv_bytes((const sb_matrix*)m.dev);
   const double bytesStream  = sb_matrix_stream_bytes((const sb_matrix*)m.dev);
   if (commIsMaster(&comm)) {
@@ -95,9 +106,9 @@ int main(int argc, char** argv)
     printf("kernel     time(us)   GB/s(algorithmic)   GB/s(reference convention)   GFlop/s\n");
     printf("spMVM   %10.2f %12.1f %20.1f %22.1f\n", 1e6 * tS, 1e-9 * bytesSpmv / tS, 1e-9 * bytesSpmvRef / tS,
         1e-9 * 2.0 * nnzTrue / tS);
-    printf("waxpby  %10.2f %12.1f %20.1f %22.1f\n", 1e6 * tW, 1e-9 * 24.0 * n / tW, 1e-9 * 24.0 * n / tW,
+    printf("waxpby  %10.2f %12.1f %20.1f %22.1f\n", 1e6 * tW, 1e-9 * 3.0 * fb * n / tW, 1e-9 * 3.0 * fb * n / tW,
         1e-9 * 3.0 * n / tW);
-    printf("ddot    %10.2f %12.1f %20.1f %22.1f\n", 1e6 * tD, 1e-9 * 16.0 * n / tD, 1e-9 * 16.0 * n / tD,
+    printf("ddot    %10.2f %12.1f %20.1f %22.1f\n", 1e6 * tD, 1e-9 * 2.0 * fb * n / tD, 1e-9 * 2.0 * fb * n / tD,
         1e-9 * 2.0 * n / tD);
     printf(HLINE);
     printf("spMVM moves %.1f MB per launch (reference layout: %.1f MB; pack level %d)\n", 1e-6 * bytesStream,

@@ -36,24 +36,24 @@ void sbh_region_end(int tag)
 /* ---- staging helpers --------------------------------------------------------------- */
 typedef struct {
   const void* host;
-  double* dev;
+  CG_FLOAT* dev;
   int staged;
 } staged_vec;
 
-static staged_vec stage_in(const double* p, size_t n, int copy)
+static staged_vec stage_in(const CG_FLOAT* p, size_t n, int copy)
 {
-  staged_vec s = { p, (double*)p, 0 };
+  staged_vec s = { p, (CG_FLOAT*)p, 0 };
   if (n == 0 || sb_is_device_ptr(p)) return s;
-  s.dev    = (double*)sb_malloc(n * sizeof(double));
+  s.dev    = (CG_FLOAT*)sb_malloc(n * sizeof(CG_FLOAT));
   s.staged = 1;
-  if (copy) sb_h2d(s.dev, p, n * sizeof(double));
+  if (copy) sb_h2d(s.dev, p, n * sizeof(CG_FLOAT));
   return s;
 }
 
-static void stage_out(staged_vec* s, double* host, size_t n)
+static void stage_out(staged_vec* s, CG_FLOAT* host, size_t n)
 {
   if (!s->staged) return;
-  if (host) sb_d2h(host, s->dev, n * sizeof(double));
+  if (host) sb_d2h(host, s->dev, n * sizeof(CG_FLOAT));
   sb_free(s->dev);
 }
 
@@ -64,8 +64,8 @@ void waxpby(const CG_UINT n, const CG_FLOAT alpha, const CG_FLOAT* restrict x, c
   staged_vec sx = stage_in(x, n, 1);
   staged_vec sy = (y == x) ? sx : stage_in(y, n, 1);
   staged_vec sw = (w == x) ? sx : (w == y) ? sy : stage_in(w, n, 0);
-  sb_waxpby(n, alpha, sx.dev, beta, sy.dev, sw.dev);
-  if (sw.staged) sb_d2h(w, sw.dev, (size_t)n * sizeof(double));
+  SBH_FP(sb_waxpby)(n, alpha, sx.dev, beta, sy.dev, sw.dev);
+  if (sw.staged) sb_d2h(w, sw.dev, (size_t)n * sizeof(CG_FLOAT));
   if (sw.staged && w != x && w != y) sb_free(sw.dev);
   if (sy.staged && y != x) sb_free(sy.dev);
   if (sx.staged) sb_free(sx.dev);
@@ -76,7 +76,7 @@ void ddot(const CG_UINT n, const CG_FLOAT* restrict x, const CG_FLOAT* restrict 
 {
   staged_vec sx = stage_in(x, n, 1);
   staged_vec sy = (y == x) ? sx : stage_in(y, n, 1);
-  *result       = sb_ddot(n, sx.dev, sy.dev); /* process default dot order; includes the SUM all-reduce (src/solver.c:60) */
+  *result       = SBH_FP(sb_ddot)(n, sx.dev, sy.dev); /* process default dot order; includes the SUM all-reduce (src/solver.c:60) */
   if (sy.staged && y != x) sb_free(sy.dev);
   if (sx.staged) sb_free(sx.dev);
 }
@@ -85,7 +85,7 @@ void sbh_spmv(void* dev_matrix, CG_UINT nr, CG_UINT nc, const CG_FLOAT* x, CG_FL
 {
   staged_vec sx = stage_in(x, nc, 1);
   staged_vec sy = stage_in(y, nr, 0);
-  sb_spmv((const sb_matrix*)dev_matrix, sx.dev, sy.dev);
+  SBH_FP(sb_spmv)((const sb_matrix*)dev_matrix, sx.dev, sy.dev);
   stage_out(&sy, y, nr);
   stage_out(&sx, NULL, nc);
 }
@@ -99,12 +99,12 @@ static int sbh_solve(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
 {
   const int itermax    = param->itermax;
   const int generated  = strcmp(param->filename, "generate") == 0 || strcmp(param->filename, "generate7P") == 0;
-  double* b            = (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double));
-  double* xexact       = generated ? (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double)) : NULL;
+  CG_FLOAT* b          = (CG_FLOAT*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(CG_FLOAT));
+  CG_FLOAT* xexact     = generated ? (CG_FLOAT*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(CG_FLOAT)) : NULL;
   /* initVectors, src/CGSolver.c:25-36 */
   for (CG_UINT i = 0; i < nr; i++) {
     if (generated) {
-      b[i]      = 27.0 - ((double)((int)rowNnz[i] - 1));
+      b[i]      = 27.0 - ((CG_FLOAT)((int)rowNnz[i] - 1));
       xexact[i] = 1.0;
     } else {
       b[i] = 1.0;
@@ -113,7 +113,7 @@ static int sbh_solve(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
   sbh_comm_attach_halo(comm, nr, oldToNewPerm);
   /* the dot order is the process default (SB_DOT_ORDER / sb_set_dot_order): seq runs the reference's op list with its
    * sequential ddot, and the history -- the lines printed below -- is then the reference's bit for bit */
-  sb_cg* cg = sb_cg_create((const sb_matrix*)dev_matrix, (sb_halo*)comm->dev, b, xexact);
+  sb_cg* cg = SBH_FP(sb_cg_create)((const sb_matrix*)dev_matrix, (sb_halo*)comm->dev, b, xexact);
   const char* fused = getenv("SB_FUSED");
   const char* graph = getenv("SB_GRAPH");
   if (fused) sb_cg_set_fused(cg, atoi(fused));
@@ -130,12 +130,13 @@ static int sbh_solve(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
   if (printFreq > 50) printFreq = 50;
   if (printFreq < 1) printFreq = 1;
   if (commIsMaster(comm)) {
-    printf("Initial Residual = %E\n", nRr > 0 ? sqrt(rr[0]) : 0.0);
+    /* normr is a CG_FLOAT: sqrt in double, stored to CG_FLOAT (src/CGSolver.c:100,116) */
+    printf("Initial Residual = %E\n", nRr > 0 ? (CG_FLOAT)sqrt(rr[0]) : 0.0);
     /* iteration j's residual is sqrt of the r.r entering it: rr[0] for j = 1, rr[j-1] after */
     for (int j = 1; j < k; j++)
       if (j % printFreq == 0 || j + 1 == itermax) {
         const int idx = j == 1 ? 0 : j - 1;
-        if (idx < nRr) printf("Iteration = %d Residual = %E\n", j, sqrt(rr[idx]));
+        if (idx < nRr) printf("Iteration = %d Residual = %E\n", j, (CG_FLOAT)sqrt(rr[idx]));
       }
     printf("Solution performed %d iterations and took %.2fs\n", k, 1e-3 * sb_cg_loop_ms(cg));
   }

@@ -14,8 +14,10 @@ from . import capi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB = os.path.join(HERE, "lib", "libsparsebench_host.so")
+HOST_LIB_SP = os.path.join(HERE, "lib", "libsparsebench_host_sp.so")  # -DPRECISION=1: CG_FLOAT = float
 vp = C.c_void_p
 _host = None
+_host_sp = None
 
 # setup-exchange callbacks (include/sparsebench/sparsebench.h: sbh_exchange)
 ALLGATHER_FN = C.CFUNCTYPE(None, vp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int))
@@ -27,14 +29,21 @@ class ExchangeS(C.Structure):
     _fields_ = [("ctx", vp), ("allgather_ints", ALLGATHER_FN), ("alltoallv_ints", ALLTOALLV_FN)]
 
 
-def host():
-    global _host
-    if _host is not None:
+def host(precision="double"):
+    """the C host library: libsparsebench_host.so, or (precision="single") libsparsebench_host_sp.so -- both can be loaded in
+    one process (the SP core binds its own calls to itself)"""
+    global _host, _host_sp
+    if precision not in ("double", "single"):
+        raise ValueError("precision %r: expected 'double' or 'single'" % (precision,))
+    if precision == "single" and _host_sp is not None:
+        return _host_sp
+    if precision == "double" and _host is not None:
         return _host
     capi.load()  # same libsbhip.so instance the host library links against
-    if not os.path.exists(HOST_LIB):
-        raise RuntimeError("sparsebench_amd: %s is missing -- run `make host`" % HOST_LIB)
-    H = C.CDLL(HOST_LIB)
+    path = HOST_LIB_SP if precision == "single" else HOST_LIB
+    if not os.path.exists(path):
+        raise RuntimeError("sparsebench_amd: %s is missing -- run `make host`" % path)
+    H = C.CDLL(path)
     H.sbh_problem_create.restype = vp
     H.sbh_problem_create.argtypes = [C.c_char_p] + [C.c_int] * 9
     H.sbh_problem_matrix.restype = vp
@@ -59,7 +68,10 @@ def host():
     H.MMMatrixRead.argtypes = [vp, C.c_char_p]
     H.commDistributeMatrix.argtypes = [vp, vp, vp]
     H.sbh_exchange_rccl.restype = vp
-    _host = H
+    if precision == "single":
+        _host_sp = H
+    else:
+        _host = H
     return H
 
 
@@ -98,7 +110,7 @@ def read_bmx_slice(path, rank=0, size=1):
 def _view(ptr, n, dtype):
     if not ptr or n == 0:
         return np.zeros(0, dtype=dtype)
-    ct = {np.uint32: C.c_uint32, np.int32: C.c_int32, np.float64: C.c_double}[dtype]
+    ct = {np.uint32: C.c_uint32, np.int32: C.c_int32, np.float64: C.c_double, np.float32: C.c_float}[dtype]
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ct)), shape=(int(n),))
 
 
@@ -107,8 +119,11 @@ class Problem:
     and (upload=True) resident in HBM."""
 
     def __init__(self, filename="generate", nx=16, ny=16, nz=16, fmt="scs", Cc=64, sigma=1,
-                 rank=0, size=1, upload=True):
-        self.H = host()
+                 rank=0, size=1, upload=True, precision="double"):
+        # precision="single": the SP host library (CG_FLOAT = float, the _f32 entry points of the HIP layer)
+        self.H = host(precision)
+        self.precision = precision
+        self.fdtype = np.float32 if precision == "single" else np.float64
         self.fmt = fmt
         self.upload = upload
         self.ptr = self.H.sbh_problem_create(os.fsencode(filename), nx, ny, nz,
@@ -131,17 +146,17 @@ class Problem:
 
     def values(self):
         n = self.nnzTrue if self.fmt == "crs" else self.nElems
-        return _view(self.H.sbh_problem_values(self.ptr), n, np.float64)
+        return _view(self.H.sbh_problem_values(self.ptr), n, self.fdtype)
 
     def gm_entries(self):
         col = np.empty(self.nnzTrue, dtype=np.uint32)
-        val = np.empty(self.nnzTrue, dtype=np.float64)
+        val = np.empty(self.nnzTrue, dtype=self.fdtype)
         self.H.sbh_problem_gm_entries(self.ptr, col.ctypes.data_as(vp), val.ctypes.data_as(vp))
         return col, val
 
     def rhs(self):
-        b = np.empty(self.nr)
-        xe = np.empty(self.nr)
+        b = np.empty(self.nr, dtype=self.fdtype)
+        xe = np.empty(self.nr, dtype=self.fdtype)
         gen = self.H.sbh_problem_rhs(self.ptr, b.ctypes.data_as(vp), xe.ctypes.data_as(vp))
         return b, (xe if gen else None)
 
@@ -199,8 +214,11 @@ class CG:
         self.L = capi.load()
         self.problem = problem
         b, xe = problem.rhs()
-        self.ptr = self.L.sb_cg_create(problem.matrix, problem.halo, b.ctypes.data_as(vp),
-                                       xe.ctypes.data_as(vp) if xe is not None else None)
+        # the solver follows the matrix's precision (sb_matrix_precision: 1 single, 2 double)
+        self.single = self.L.sb_matrix_precision(problem.matrix) == 1
+        create = self.L.sb_cg_create_f32 if self.single else self.L.sb_cg_create
+        self.ptr = create(problem.matrix, problem.halo, b.ctypes.data_as(vp),
+                          xe.ctypes.data_as(vp) if xe is not None else None)
         # fused: True = the default (1: dots fused into their producers), False = the reference's op list, or the
         # level itself (0 or 1; any other non-zero level is 1)
         self.L.sb_cg_set_fused(self.ptr, int(fused))
@@ -265,6 +283,11 @@ class CG:
         return rr[:nrr].copy(), pap[:npap.value].copy()
 
     def solution(self):
+        """x in original row order: float64, or float32 for a single-precision solver"""
+        if self.single:
+            x = np.empty(self.problem.nr, dtype=np.float32)
+            self.L.sb_cg_solution_f32(self.ptr, x.ctypes.data_as(vp))
+            return x
         x = np.empty(self.problem.nr)
         self.L.sb_cg_solution(self.ptr, x.ctypes.data_as(vp))
         return x

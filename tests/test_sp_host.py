@@ -1,0 +1,124 @@
+"""Single precision (FLOAT_TYPE=SP, -DPRECISION=1) on the CPU: the header switch, the _sp libraries, the host layout of the SP
+build against the DP one, the committed reference histories, and tests/sp_ref.py against them."""
+import ctypes
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import sp_ref
+from sparsebench_amd import hostapi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "sparsebench_amd", "lib")
+BIN = os.path.join(ROOT, "sparsebench_amd", "bin")
+GOLD = os.path.join(ROOT, "tests", "golden", "cg_hist_sp_ref.json")
+BAND = os.path.join(ROOT, "tests", "golden", "ref", "matrix_band_klein.mtx")
+
+PROBE = r"""
+#include <stddef.h>
+#include <stdio.h>
+#include "sparsebench/sparsebench.h"
+int main(void)
+{
+  printf("%zu %s %zu %zu %zu\n", sizeof(CG_FLOAT), PRECISION_STRING, sizeof(Entry), offsetof(Entry, val), sizeof(CG_UINT));
+  return 0;
+}
+"""
+
+
+@pytest.mark.parametrize("defs,expect", [([], "8 double 16 8 4"), (["-DPRECISION=2"], "8 double 16 8 4"),
+                                         (["-DPRECISION=1"], "4 single 8 4 4")])
+def test_header_precision_switch(tmp_path, defs, expect):
+    src = tmp_path / "probe.c"
+    src.write_text(PROBE)
+    exe = tmp_path / "probe"
+    subprocess.check_call(["gcc", "-std=gnu11", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include")] + defs +
+                          [str(src), "-o", str(exe)])
+    assert subprocess.check_output([str(exe)], text=True).strip() == expect
+
+
+@pytest.mark.parametrize("fmt", ["crs", "scs"])
+def test_sp_dropin_exports_reference_symbols(fmt):
+    from sparsebench_amd import capi
+    capi.load()
+    hostapi.host("single")
+    d = ctypes.CDLL(os.path.join(LIB, "libsparsebench_%s_sp.so" % fmt))
+    for s in ("convertMatrix", "spMVM", "solveCG", "waxpby", "ddot", "commExchange", "commReduction", "commInit",
+              "profilerPrint", "allocate"):
+        getattr(d, s)
+    for exe in ("sparseBench-%s-HIP-SP", "runBenchmarks-%s-HIP-SP"):
+        assert os.access(os.path.join(BIN, exe % fmt.upper()), os.X_OK)
+
+
+@pytest.mark.parametrize("case", [("generate", 8, "crs", 64, 1), ("generate", 12, "scs", 64, 256), ("generate", 8, "scs", 8, 16),
+                                  (BAND, 1, "crs", 64, 1), (BAND, 1, "scs", 32, 4)])
+def test_sp_layout_is_dp_layout_cast(case):
+    """both host libraries in one process: every index array equal, values = the DP values cast to float"""
+    fn, n, fmt, Cc, sigma = case
+    dp = hostapi.Problem(fn, n, n, n, fmt=fmt, Cc=Cc, sigma=sigma, upload=False)
+    sp = hostapi.Problem(fn, n, n, n, fmt=fmt, Cc=Cc, sigma=sigma, upload=False, precision="single")
+    names = ["rowPtr", "rowNnz"] + (["crs_colInd"] if fmt == "crs" else ["chunkPtr", "chunkLens", "scs_colInd", "oldToNewPerm",
+                                                                         "newToOldPerm"])
+    for a in names:
+        assert np.array_equal(dp.array(a), sp.array(a)), a
+    assert sp.values().dtype == np.float32
+    assert np.array_equal(sp.values().view(np.uint32), dp.values().astype(np.float32).view(np.uint32))
+    bd, xd = dp.rhs()
+    bs, xs = sp.rhs()
+    assert bs.dtype == np.float32 and np.array_equal(bs, bd.astype(np.float32))
+    assert (xd is None) == (xs is None)
+    dp.free(), sp.free()
+
+
+def _golden():
+    return json.load(open(GOLD))
+
+
+def test_sp_golden_well_formed():
+    g = _golden()
+    assert set(g) == {"band_klein", "hpcg8", "hpcg16", "hpcg32", "hpcg64", "hpcg128"}
+    assert g["hpcg8"]["k"] == 44 and g["band_klein"]["k"] == 3 and g["hpcg128"]["itermax"] == 60
+    for name, c in g.items():
+        assert set(c) == {"itermax", "k", "rr", "pAp"}
+        assert len(c["rr"]) == c["k"] - 1 and len(c["pAp"]) == c["k"] - 1, name
+        for v in c["rr"] + c["pAp"]:
+            d = float(v)
+            assert np.isnan(d) or float(np.float32(d)) == d, (name, v)  # every value is a float32 value
+    rr16 = np.array([float(v) for v in g["hpcg16"]["rr"]], np.float32)
+    assert np.sum((rr16 != 0) & (np.abs(rr16) < np.finfo(np.float32).tiny)) > 50  # subnormal r.r values: no flush to zero
+    assert float(g["hpcg8"]["rr"][-1]) == 0.0  # the exact r.r = 0 exit
+
+
+def _crs(fn, n):
+    p = hostapi.Problem(fn, n, n, n, fmt="crs", upload=False, precision="single")
+    return p, p.array("rowPtr").copy(), p.array("crs_colInd").copy(), p.values().copy()
+
+
+@pytest.mark.parametrize("name", ["band_klein", "hpcg8", "hpcg16"])
+def test_sp_ref_seq_cg_reproduces_reference(name):
+    """the restatement in the seq order IS the reference's SP solveCG: the committed history bit for bit"""
+    g = _golden()[name]
+    p, rp, col, val = _crs(BAND, 1) if name == "band_klein" else _crs("generate", int(name[4:]))
+    b, _ = p.rhs()
+    k, rr, pap, _ = sp_ref.cg(lambda v: sp_ref.spmv_crs(rp, col, val, v), b, g["itermax"], dot=sp_ref.dot_seq)
+    assert k == g["k"]
+    assert np.array_equal(rr.view(np.uint32), np.array([float(v) for v in g["rr"]], np.float32).view(np.uint32))
+    gp = np.array([float(v) for v in g["pAp"]], np.float32)
+    assert np.array_equal(np.isnan(pap), np.isnan(gp))
+    assert np.array_equal(pap[~np.isnan(pap)].view(np.uint32), gp[~np.isnan(gp)].view(np.uint32))
+    p.free()
+
+
+def test_sp_ref_scs_equals_crs():
+    """Sell-C-sigma from the SP host layout (padding included) gives the CRS sums bit for bit"""
+    p, rp, col, val = _crs("generate", 8)
+    s = hostapi.Problem("generate", 8, 8, 8, fmt="scs", Cc=64, sigma=256, upload=False, precision="single")
+    x = np.random.default_rng(3).standard_normal(p.nc).astype(np.float32)
+    y1 = sp_ref.spmv_crs(rp, col, val, x)
+    y2 = sp_ref.spmv_scs(s.array("chunkPtr"), s.array("chunkLens"), s.array("scs_colInd"), s.values(), 64,
+                         s.array("oldToNewPerm"), s.nr, x)
+    assert np.array_equal(y1.view(np.uint32), y2.view(np.uint32))
+    p.free(), s.free()
