@@ -191,7 +191,8 @@ int sb_dot_order(void);
 /* ---- single precision: the reference's FLOAT_TYPE=SP build (src/util.h:47-51, -DPRECISION=1) ---------------- */
 /* CG_FLOAT = float everywhere: values, vectors and every operation; each product rounded to float before its add, sums
  * accumulate in float, f32 subnormals kept.  An SP matrix streams the reference layout only (no compressed mirror, no masked
- * row programs, no placement tuner).  One rank only (more is a fatal error).  Crossing precisions -- an fp64 entry point on an
+ * row programs, no placement tuner).  Any number of ranks: sb_halo_exchange_f32 / sb_comm_reduction_f32 and the CG loop's
+ * float halo and float all-reduce on both data planes.  Crossing precisions -- an fp64 entry point on an
  * SP matrix or solver, or the other way round -- is a fatal error with file:line. */
 sb_matrix* sb_crs_upload_f32(uint32_t nr, uint32_t nc, const uint32_t* rowPtr, const uint32_t* colInd, const float* val);
 sb_matrix* sb_scs_upload_f32(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigma, uint32_t nChunks, uint32_t nElems,
@@ -234,7 +235,9 @@ typedef struct {
                              const int* sendCounts, const int* sdispls, double* recv_dev, int indegree,
                              const int* sources, const int* recvCounts, const int* rdispls);
   /* optional (may be NULL): all_host[r * nbytes ..] = rank r's mine_host; lets the layer set up the
-   * exchange over peer-mapped memory (halo staging areas) on top of this transport */
+   * exchange over peer-mapped memory (halo staging areas) on top of this transport.  Single precision on
+   * several ranks needs it: the float all-reduce gathers the ranks' floats through it (sb_comm_reduction_f32);
+   * without it the SP uploads and sb_cg_create_f32 end the process with a message */
   void (*allgather_bytes)(void* ctx, const void* mine_host, int nbytes, void* all_host);
 } sb_transport;
 void sb_comm_init_transport(int rank, int size, const sb_transport* t);
@@ -272,6 +275,13 @@ int sb_comm_size(void);
 /* commReduction, src/comm.h:58 (op: 0 = MAX, 1 = SUM as enum op, src/comm.h:25);
  * in place on one device double; stream-ordered */
 void sb_comm_reduction(double* v_dev, int op);
+/* commReduction of the SP build (MPI_FLOAT): in place on one device float.  Every plane adds the ranks' floats pairwise in
+ * rank order, ((v0 + v1) + (v2 + v3)) + ..., in float -- MPICH's order -- so the bits do not depend on the plane or on P:
+ * RCCL all-gathers the values (stream-ordered) and one thread adds them; a host transport all-gathers them with its
+ * allgather_bytes (required) and the host adds them.  op 0 = MAX, 1 = SUM. */
+void sb_comm_reduction_f32(float* v_dev, int op);
+/* that rank reduction on the host: values[0 .. n) in rank order, op 0 = MAX, 1 = SUM (pairwise float tree) */
+float sb_rank_reduce_f32(const float* values, int n, int op);
 /* setup-time exchanges between ranks over the same communicator, host buffers in
  * and out (replace MPI_Allgather src/comm.c:496 and the Send/Irecv of wanted ids
  * src/comm.c:134-161) */
@@ -297,6 +307,9 @@ const char* sb_halo_p2p_reason(const sb_halo* h);
 /* commExchange, src/comm.h:57: pack x[elementsToSend] and deliver every
  * neighbour's slice into x[numRows ...]; stream-ordered */
 void sb_halo_exchange(sb_halo* h, double* x);
+/* the same for a float vector (commExchange of the SP build): one plan serves either precision.  RCCL sends float32;
+ * a host transport's neighbour_exchange carries the values widened to double, narrowed again into x[numRows ...] (exact) */
+void sb_halo_exchange_f32(sb_halo* h, float* x);
 
 /* ---- CG (solveCG, src/solver.h:11, src/CGSolver.c:62-141) --------------------- */
 /* b_host / xexact_host: nr doubles in original row order (xexact may be NULL). */
@@ -318,7 +331,10 @@ void sb_cg_set_dot_order(sb_cg* s, int order);
 int sb_cg_dot_order(const sb_cg* s);
 int sb_cg_vector_phase(sb_cg* s); /* always 0: the one-launch vector phase was removed */
 /* launches per loop body the loop will use: 5 (p update | SpMV | alpha | r update | beta), 4 with the p update inside the
- * SpMV, one fewer for each scalar step folded into its consumer; 0 for the reference's op list */
+ * SpMV, one fewer for each scalar step folded into its consumer; 0 for the reference's op list.  Single precision: 3 on
+ * Sell-64, 4 with the dot pass of CRS / generic C; on several ranks 7 / 8 on the peer-mapped plane (p update | push | pull |
+ * SpMV | (dot pass) | alpha | r update | beta) and, on the communicator's, 5 / 6 + the pack (+ the unpack of a host
+ * transport) + 2 */
 int sb_cg_launches_per_body(sb_cg* s);
 /* several ranks: the count above includes the halo kernels (peer-mapped push: +1, or +0 riding in the SpMV launch; pack
  * kernel in front of a send / recv group: +1) and, without the in-kernel all-reduce, one more kernel per dot (+2);

@@ -20,6 +20,7 @@
 
 #include "kernels.hip.h"
 #include "kernels_sp.hip.h"
+#include "kernels_sp_comm.hip.h"
 #include "pack.hip.h"
 
 #include <algorithm>
@@ -60,7 +61,7 @@ namespace {
 typedef struct ncclComm* ncclComm_t;
 typedef struct { char internal[128]; } ncclUniqueId;
 enum { ncclSuccess_ = 0 };
-enum { ncclInt8_ = 0, ncclInt32_ = 2, ncclFloat64_ = 8 }; // ncclDataType_t
+enum { ncclInt8_ = 0, ncclInt32_ = 2, ncclFloat32_ = 7, ncclFloat64_ = 8 }; // ncclDataType_t
 enum { ncclSum_ = 0, ncclMax_ = 2 }; // ncclRedOp_t
 
 struct Rccl {
@@ -141,6 +142,7 @@ struct Ctx {
   bool p2pUse = true;               // sb_comm_data_plane: 0 = run on the communicator's collectives although the mappings exist
   char p2pReason[256] = "not set up (one rank, or no communicator yet)"; // why the path is on / off
   long long p2pTimeoutTicks = 30000 * P2P_TICKS_PER_MS; // waits inside CG (SB_P2P_TIMEOUT_MS)
+  float* rankValsF = nullptr;       // sb_comm_reduction_f32 over RCCL: the all-gathered rank values (size floats)
 } g;
 
 inline bool multi_rank() { return g.comm != nullptr || g.hasXport; }
@@ -275,7 +277,8 @@ struct sb_halo {
   int outdegree, indegree, totalSend, externalCount;
   std::vector<int> destinations, sendCounts, sdispls, sources, recvCounts, rdispls;
   uint32_t* packIdx = nullptr; // device: row (in the vector's order) of each sent element
-  double* sendBuf = nullptr;   // device
+  double* sendBuf = nullptr;   // device (single precision: the packed floats, or widened to double for a host transport)
+  double* recvWide = nullptr;  // device, externalCount doubles: what a host transport delivers to a single-precision exchange
   // exchange over peer-mapped memory (kernels.hip.h: halo_push_k / halo_pull_k); p2p == false: RCCL / transport
   bool p2p = false;
   unsigned long long* stage = nullptr; // own fine-grained area: [2][externalCount] values, then [2][P2P_MAX] flags
@@ -339,6 +342,7 @@ struct sb_cg {
   float *rf = nullptr, *pf = nullptr, *Apf = nullptr, *xf = nullptr, *bf = nullptr, *xexactf = nullptr;
   CgScalarsF* SF = nullptr;
   float *partialsF = nullptr, *partials2F = nullptr, *rrHistF = nullptr, *pApHistF = nullptr;
+  CgCommF* XF = nullptr; // several ranks: the rank sum handed to the all-reduce, the peer-mapped plane's failure flag
 };
 
 // ===========================================================================

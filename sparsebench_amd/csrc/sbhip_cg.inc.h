@@ -242,7 +242,7 @@ int sb_cg_launches_per_body(sb_cg* s)
 int sb_cg_collectives_per_body(sb_cg* s)
 {
   if (s->seqLatched < 0) apply_dot_order(s);
-  if (!multi_rank() || !s->fused || s->prec == 1) return 0;
+  if (!multi_rank() || !s->fused) return 0;
   return (p2p_dots() ? 0 : 2) + (s->halo && !halo_p2p_active(s->halo) ? 1 : 0);
 }
 
@@ -747,6 +747,28 @@ void sb_cg_run_iters(sb_cg* s, int iters)
   flush_beta_fold(s); // every call leaves the loop state complete (counters, history, stop flag)
 }
 
+// a failed wait on the peer-mapped paths ends the process with the rank in the message (both precisions).  (A rank that fails
+// poisons what it would have published, so the others leave their waits at once with code 2: the rank that saw the CAUSE --
+// code 1 or 3 -- is the one whose message matters.)
+static void cg_comm_failures(const sb_cg* s, int p2pError)
+{
+  if (s->halo && s->halo->p2p) {
+    int e = 0;
+    HIP_CHECK(hipMemcpy(&e, s->halo->err, sizeof e, hipMemcpyDeviceToHost));
+    if (e == 1)
+      SB_FATAL("rank %d: a neighbour's halo block did not arrive within %lld ms (SB_P2P_TIMEOUT_MS raises the bound, "
+               "SB_P2P_HALO=0 selects RCCL)", g.rank, s->halo->push.timeoutTicks / P2P_TICKS_PER_MS);
+    if (e && p2pError != 1) p2pError = 2;
+  }
+  if (p2pError == 2)
+    SB_FATAL("rank %d: another rank reported a communication failure over the peer-mapped paths and ended the exchange "
+             "(its own message says which wait ran out); this rank stopped with it", g.rank);
+  if (p2pError)
+    SB_FATAL("rank %d: a peer's contribution to an in-kernel all-reduce did not arrive within %lld ms "
+             "(SB_P2P_TIMEOUT_MS raises the bound, SB_P2P=0 selects the RCCL all-reduce)", g.rank,
+        g.p2pTimeoutTicks / P2P_TICKS_PER_MS);
+}
+
 int sb_cg_finish(sb_cg* s)
 {
   need_init();
@@ -762,23 +784,7 @@ int sb_cg_finish(sb_cg* s)
   HIP_CHECK(hipStreamSynchronize(g.stream));
   CgScalars h;
   HIP_CHECK(hipMemcpy(&h, s->S, sizeof h, hipMemcpyDeviceToHost));
-  // (a rank that fails poisons what it would have published, so the others leave their waits at once with code 2: the rank
-  //  that saw the CAUSE -- code 1 or 3 -- is the one whose message matters)
-  if (s->halo && s->halo->p2p) {
-    int e = 0;
-    HIP_CHECK(hipMemcpy(&e, s->halo->err, sizeof e, hipMemcpyDeviceToHost));
-    if (e == 1)
-      SB_FATAL("rank %d: a neighbour's halo block did not arrive within %lld ms (SB_P2P_TIMEOUT_MS raises the bound, "
-               "SB_P2P_HALO=0 selects RCCL)", g.rank, s->halo->push.timeoutTicks / P2P_TICKS_PER_MS);
-    if (e && h.p2p_error != 1) h.p2p_error = 2;
-  }
-  if (h.p2p_error == 2)
-    SB_FATAL("rank %d: another rank reported a communication failure over the peer-mapped paths and ended the exchange "
-             "(its own message says which wait ran out); this rank stopped with it", g.rank);
-  if (h.p2p_error)
-    SB_FATAL("rank %d: a peer's contribution to an in-kernel all-reduce did not arrive within %lld ms "
-             "(SB_P2P_TIMEOUT_MS raises the bound, SB_P2P=0 selects the RCCL all-reduce)", g.rank,
-        g.p2pTimeoutTicks / P2P_TICKS_PER_MS);
+  cg_comm_failures(s, h.p2p_error);
   if (s->timing) {
     for (double& v : s->region_ms) v = 0.0;
     for (size_t i = 1; i < s->evUsed; i++) {

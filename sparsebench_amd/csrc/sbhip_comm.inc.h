@@ -262,6 +262,8 @@ void sb_comm_finalize(void)
     p2p_release();
   }
   g.hasXport = false;
+  if (g.rankValsF) HIP_CHECK(hipFree(g.rankValsF));
+  g.rankValsF = nullptr;
   if (g.comm) {
     HIP_CHECK(hipStreamSynchronize(g.stream));
     RCCL_CHECK(rccl.CommDestroy(g.comm));
@@ -284,6 +286,50 @@ void sb_comm_reduction(double* v_dev, int op)
   if (!g.comm) return;
   RCCL_CHECK(rccl.AllReduce(v_dev, v_dev, 1, ncclFloat64_, op == 0 ? ncclMax_ : ncclSum_, g.comm,
       g.stream));
+}
+
+// The float all-reduce (commReduction of the SP build: MPI_Allreduce with MPI_FLOAT, src/comm.c:655-662).  Every plane adds the
+// ranks' floats pairwise in rank order (rank_reduce_f32, MPICH's order) so that all of them give the same bits for any P: the host
+// transport all-gathers the P values (its allgather_bytes) and adds them here; RCCL all-gathers them on the stream and one thread
+// adds them (ncclAllReduce adds in RCCL's own order, which for P > 2 need not be that tree).  Widening to double and using the
+// double all-reduce would be wrong for P >= 3: it rounds once instead of after every add.
+float sb_rank_reduce_f32(const float* values, int n, int op)
+{
+  if (n < 1) return 0.0f;
+  std::vector<float> v(values, values + n);
+  return rank_reduce_f32(v.data(), n, op);
+}
+
+// a host transport without allgather_bytes cannot carry the float all-reduce: said at set-up (the SP uploads and
+// sb_cg_create_f32), before the first kernel of a single-precision run
+static void need_float_allreduce(const char* fn)
+{
+  if (g.hasXport && g.size > 1 && !g.xport.allgather_bytes)
+    SB_FATAL("%s: single precision on %d ranks over a host transport needs its allgather_bytes callback (sb_transport): the float "
+             "all-reduce gathers the ranks' values and adds them in float, pairwise in rank order -- the double allreduce callback "
+             "would round once instead of after every add", fn, g.size);
+}
+
+void sb_comm_reduction_f32(float* v_dev, int op)
+{
+  need_init();
+  if (g.hasXport) {
+    need_float_allreduce("sb_comm_reduction_f32");
+    if (g.size == 1) return;
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    float mine = 0.0f;
+    sb_d2h(&mine, v_dev, sizeof mine);
+    std::vector<float> all((size_t)g.size);
+    g.xport.allgather_bytes(g.xport.ctx, &mine, (int)sizeof mine, all.data());
+    const float r = rank_reduce_f32(all.data(), g.size, op);
+    sb_h2d(v_dev, &r, sizeof r);
+    return;
+  }
+  if (!g.comm) return;
+  if (!g.rankValsF) HIP_CHECK(hipMalloc(&g.rankValsF, ((size_t)g.size + 1) * sizeof(float)));
+  RCCL_CHECK(rccl.AllGather(v_dev, g.rankValsF, 1, ncclFloat32_, g.comm, g.stream));
+  hipLaunchKernelGGL(rank_reduce_f32_k, dim3(1), dim3(64), 0, g.stream, g.rankValsF, g.size, op, v_dev);
+  HIP_CHECK(hipGetLastError());
 }
 
 void sb_comm_allgather_bytes(const void* mine_host, int nbytes, void* all_host)
@@ -594,7 +640,7 @@ const char* sb_halo_p2p_reason(const sb_halo* h) { return h ? h->p2pReason : "no
 void sb_halo_free(sb_halo* h)
 {
   if (!h) return;
-  sb_free(h->packIdx), sb_free(h->sendBuf);
+  sb_free(h->packIdx), sb_free(h->sendBuf), sb_free(h->recvWide);
   halo_p2p_release(h);
   delete h;
 }
@@ -646,4 +692,59 @@ void sb_halo_exchange(sb_halo* h, double* x)
 {
   need_init();
   halo_exchange(h, x, nullptr);
+}
+
+// The halo exchange of a float vector (commExchange of the SP build, src/comm.c:627-649 with MPI_FLOAT).  One plan serves
+// either precision: it holds indices only.  Peer-mapped (inside CG): halo_push_f32_k stores each float into the low half of
+// the receiver's 64-bit staging slot, halo_pull_f32_k copies its sources' blocks into the float tail of x.  RCCL: the packed
+// floats, sent / received as float32 straight into the tail.  Host transport: its neighbour_exchange carries doubles, so the
+// pack widens and an unpack narrows into the tail (both exact).
+static void halo_exchange_f32(sb_halo* h, float* x, const int* stop, bool inCG)
+{
+  if (!h || g.size == 1) return;
+  if (halo_p2p_active(h) && inCG) {
+    const unsigned long long seq = ++h->seq;
+    if (h->totalSend)
+      hipLaunchKernelGGL(halo_push_f32_k, dim3(stream_grid(h->totalSend, 256)), dim3(256), 0, g.stream, h->push, (const float*)x, seq,
+          stop);
+    if (h->indegree)
+      hipLaunchKernelGGL(halo_pull_f32_k, dim3(h->indegree), dim3(256), 0, g.stream, h->dSrcRank, h->dRdispl, h->dRcount, h->stage,
+          h->stage + 2 * (size_t)h->externalCount, (uint32_t)h->externalCount, x + h->nr, seq, h->err, const_cast<int*>(stop),
+          h->push.timeoutTicks);
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  if (g.hasXport) {
+    if (h->totalSend)
+      hipLaunchKernelGGL(halo_pack_wide_f32_k, dim3(stream_grid(h->totalSend, 256)), dim3(256), 0, g.stream, (uint32_t)h->totalSend,
+          (const uint32_t*)h->packIdx, (const float*)x, h->sendBuf, stop);
+    HIP_CHECK(hipGetLastError());
+    if (!h->recvWide) h->recvWide = (double*)sb_malloc(((size_t)h->externalCount + 1) * sizeof(double));
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    g.xport.neighbour_exchange(g.xport.ctx, h->sendBuf, h->outdegree, h->destinations.data(), h->sendCounts.data(),
+        h->sdispls.data(), h->recvWide, h->indegree, h->sources.data(), h->recvCounts.data(), h->rdispls.data());
+    if (h->externalCount)
+      hipLaunchKernelGGL(halo_unpack_narrow_f32_k, dim3(stream_grid(h->externalCount, 256)), dim3(256), 0, g.stream,
+          (uint32_t)h->externalCount, (const double*)h->recvWide, x + h->nr);
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  float* sendF = reinterpret_cast<float*>(h->sendBuf);
+  if (h->totalSend) {
+    hipLaunchKernelGGL(gather_f32_k, dim3(stream_grid(h->totalSend, 256)), dim3(256), 0, g.stream, (uint32_t)h->totalSend,
+        (const uint32_t*)h->packIdx, (const float*)x, sendF);
+    HIP_CHECK(hipGetLastError());
+  }
+  RCCL_CHECK(rccl.GroupStart());
+  for (int i = 0; i < h->outdegree; i++)
+    RCCL_CHECK(rccl.Send(sendF + h->sdispls[i], (size_t)h->sendCounts[i], ncclFloat32_, h->destinations[i], g.comm, g.stream));
+  for (int i = 0; i < h->indegree; i++)
+    RCCL_CHECK(rccl.Recv(x + h->nr + h->rdispls[i], (size_t)h->recvCounts[i], ncclFloat32_, h->sources[i], g.comm, g.stream));
+  RCCL_CHECK(rccl.GroupEnd());
+}
+
+void sb_halo_exchange_f32(sb_halo* h, float* x)
+{
+  need_init();
+  halo_exchange_f32(h, x, nullptr, false);
 }

@@ -1,22 +1,15 @@
 // sbhip_sp.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context): single
 // precision, the reference's FLOAT_TYPE=SP build (src/util.h:47-51).  Matrices, the reference-shaped operations and the CG loop
-// on float data, over the kernels of kernels_sp.hip.h.  One rank only: the halo exchange and the all-reduce of the CG scalars
-// carry doubles.  An SP matrix always streams its reference layout: no compressed mirror, no masked row programs,
-// no p update inside the SpMV -- and no placement tuner: its proxy is an fp64 loop body.
+// on float data, over the kernels of kernels_sp.hip.h, on one rank or several (kernels_sp_comm.hip.h: float halo and float
+// all-reduce on both data planes).  An SP matrix always streams its reference layout: no compressed mirror, no masked
+// row programs, no p update inside the SpMV -- and no placement tuner: its proxy is an fp64 loop body.
 // ===========================================================================
 // single precision
 // ===========================================================================
-static void sp_single_rank(const char* fn)
-{
-  if (multi_rank() || sb_comm_size() > 1)
-    SB_FATAL("%s: single precision runs on one rank only (%d ranks here): the halo exchange and the in-kernel all-reduce of the "
-             "CG scalars carry doubles -- f32 halo push / pull and a float all-reduce are not built yet", fn, sb_comm_size());
-}
-
 sb_matrix* sb_crs_upload_f32(uint32_t nr, uint32_t nc, const uint32_t* rowPtr, const uint32_t* colInd, const float* val)
 {
   need_init();
-  sp_single_rank("sb_crs_upload_f32");
+  need_float_allreduce("sb_crs_upload_f32");
   return crs_upload_common(nr, nc, rowPtr, colInd, val, 1); // (no mirror, no placement tuner: see the head of this file)
 }
 
@@ -25,7 +18,7 @@ sb_matrix* sb_scs_upload_f32(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigm
     const uint32_t* newToOldPerm)
 {
   need_init();
-  sp_single_rank("sb_scs_upload_f32");
+  need_float_allreduce("sb_scs_upload_f32");
   return scs_upload_common(nr, nc, C, sigma, nChunks, nElems, chunkPtr, chunkLens, colInd, val, oldToNewPerm, newToOldPerm, 1);
 }
 
@@ -153,7 +146,6 @@ void sb_reduce_final_f32(uint32_t m, const float* partials_dev, float* result_de
 float sb_ddot_f32(uint32_t n, const float* x, const float* y)
 {
   need_init();
-  sp_single_rank("sb_ddot_f32");
   float* res = reinterpret_cast<float*>(g.scalar);
   if (sb_dot_order() == 1) {
     launch_dot_seq_f32(n, x, y, nullptr, res, nullptr);
@@ -163,6 +155,7 @@ float sb_ddot_f32(uint32_t n, const float* x, const float* y)
     sb_ddot_partials_f32(n, x, y, q);
     sb_reduce_final_f32(m, q, res);
   }
+  if (multi_rank()) sb_comm_reduction_f32(res, 1); // commReduction(&sum, SUM), src/solver.c:60
   float r = 0.f;
   sb_d2h(&r, res, sizeof r);
   return r;
@@ -176,14 +169,24 @@ float sb_ddot_f32(uint32_t n, const float* x, const float* y)
 //   the reference's op list (fused = 0, and always under seq): waxpby, spMVM and ddot as separate launches, every dot either the
 //     tree order's level-0 partials or the sequential sum.
 // Both give the same bits under the tree order.
+// Several ranks (src/CGSolver.c:122 commExchange, src/solver.c:60 commReduction): the halo exchange of p in front of the SpMV,
+// and every dot all-reduced before its scalar step -- so the steps cannot ride in their consumers (there is no
+// cg_update_p_f32<1> / cg_update_r_f32<1> here): the fused body is
+//   peer-mapped plane:    p update | push | pull | SpMV (+ p.Ap level 1) | alpha (cg_scalar_p2p_f32_k) | r update (+ r.r
+//                         level 1) | beta (cg_scalar_p2p_f32_k) -- 7 launches on Sell-64, 8 with the dot pass of CRS / generic C;
+//   communicator's plane: halo pack (+ the unpack of a host transport) in front of the send / recv, and each dot as local
+//                         reduce (cg_local_f32_k) | all-reduce (sb_comm_reduction_f32) | apply (cg_apply_local_f32_k).
+// The halo push stays a launch of its own: SP has no SpMV that waits for the flags or forms p itself (no pattern kernels, no
+// spmv_prog_fusep), so sb_comm_halo_push_inside has nothing to ride on here.
 sb_cg* sb_cg_create_f32(const sb_matrix* m, sb_halo* halo, const float* b_host, const float* xexact_host)
 {
   need_init();
   SB_NEED_PREC(m, 1, "sb_cg_create_f32");
-  sp_single_rank("sb_cg_create_f32");
+  need_float_allreduce("sb_cg_create_f32");
   sb_cg* s = new sb_cg();
   s->prec = 1, s->A = m, s->halo = halo, s->nr = m->nr, s->nc = m->nc;
   if (halo && halo->nr != m->nr) SB_FATAL("halo plan and matrix disagree on nr");
+  if (halo && m->nr + (uint32_t)halo->externalCount != m->nc) SB_FATAL("halo externalCount != nc-nr");
   const size_t nb = (size_t)m->nr * sizeof(float);
   s->rf = (float*)sb_malloc(nb), s->Apf = (float*)sb_malloc(nb), s->xf = (float*)sb_malloc(nb), s->bf = (float*)sb_malloc(nb);
   s->pf = (float*)sb_malloc((size_t)m->nc * sizeof(float));
@@ -199,6 +202,8 @@ sb_cg* sb_cg_create_f32(const sb_matrix* m, sb_halo* halo, const float* b_host, 
   HIP_CHECK(hipStreamSynchronize(g.stream));
   s->SF = (CgScalarsF*)sb_malloc(sizeof(CgScalarsF));
   HIP_CHECK(hipMemset(s->SF, 0, sizeof(CgScalarsF)));
+  s->XF = (CgCommF*)sb_malloc(sizeof(CgCommF));
+  HIP_CHECK(hipMemset(s->XF, 0, sizeof(CgCommF)));
   s->nPartials  = (m->nr + 255) / 256;
   const size_t np = (4 * (size_t)s->nPartials + 4) * sizeof(float);
   s->partialsF = (float*)sb_malloc(np), s->partials2F = (float*)sb_malloc(np);
@@ -215,12 +220,28 @@ sb_cg* sb_cg_create_f32(const sb_matrix* m, sb_halo* halo, const float* b_host, 
 
 static void sp_cg_free_arrays(sb_cg* s)
 {
+  if (s->halo && s->halo->p2p && s->halo->push.p2pErr == &s->XF->p2p_error) { // (sb_cg_free has synchronised the stream)
+    s->halo->push.p2pErr = nullptr;
+    HIP_CHECK(hipMemcpy(s->halo->dPush, &s->halo->push, sizeof s->halo->push, hipMemcpyHostToDevice));
+  }
+  sb_free(s->XF);
   sb_free(s->rf), sb_free(s->pf), sb_free(s->Apf), sb_free(s->xf), sb_free(s->bf), sb_free(s->xexactf);
   sb_free(s->SF), sb_free(s->partialsF), sb_free(s->partials2F), sb_free(s->rrHistF), sb_free(s->pApHistF);
 }
 
 static bool sp_spmv_has_dot(const sb_cg* s) { return s->A->fmt == 1 && s->A->C == 64; }
-static int sp_launches_per_body(const sb_cg* s) { return s->fused ? (sp_spmv_has_dot(s) ? 3 : 4) : 0; }
+static int sp_launches_per_body(const sb_cg* s)
+{
+  if (!s->fused) return 0;
+  if (!multi_rank()) return sp_spmv_has_dot(s) ? 3 : 4;
+  int n = sp_spmv_has_dot(s) ? 5 : 6; // p update | SpMV | (dot pass) | alpha | r update | beta
+  if (const sb_halo* h = s->halo) {
+    if (halo_p2p_active(h)) n += (h->totalSend ? 1 : 0) + (h->indegree ? 1 : 0); // push, pull
+    else n += (h->totalSend ? 1 : 0) + (g.hasXport && h->externalCount ? 1 : 0); // pack (+ the host transport's unpack)
+  }
+  if (!p2p_dots()) n += 2; // local reduce | all-reduce | apply: one launch more per dot
+  return n;
+}
 
 // one dot of the reference's op list into partialsF: tree level-0 partials, or (seq) the sequential sum in original row order
 static void sp_dot(sb_cg* s, const float* a, const float* b, const int* stop)
@@ -228,12 +249,30 @@ static void sp_dot(sb_cg* s, const float* a, const float* b, const int* stop)
   if (s->seqLatched > 0) launch_dot_seq_f32(s->nr, a, b, s->A->permuted ? s->A->oldToNew : nullptr, s->partialsF, stop);
   else launch_dot_l0_f32(s->nr, a, b, s->partialsF, stop);
 }
-// levels 1-2 of the dot in q + the scalar step (seq: q[0] is the whole sum)
+// levels 1-2 of the dot in q + the scalar step (seq: q[0] is the whole sum); several ranks: with the all-reduce of the rank sums
+// in between -- inside the step's launch (peer-mapped), or local reduce | sb_comm_reduction_f32 | apply (the communicator's)
 template <int MODE> static void sp_scalar(sb_cg* s, const float* q, int l1, int defer_x)
 {
   uint32_t m = s->nPartials;
   if (s->seqLatched > 0) m = 1, l1 = 1;
-  hipLaunchKernelGGL((cg_scalar_f32_k<MODE>), dim3(1), dim3(1024), 0, g.stream, m, q, s->SF, s->rrHistF, s->pApHistF, defer_x, l1);
+  if (!multi_rank()) {
+    hipLaunchKernelGGL((cg_scalar_f32_k<MODE>), dim3(1), dim3(1024), 0, g.stream, m, q, s->SF, s->rrHistF, s->pApHistF, defer_x, l1);
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  if (p2p_dots()) {
+    hipLaunchKernelGGL((cg_scalar_p2p_f32_k<MODE>), dim3(1), dim3(1024), 0, g.stream, m, q, s->SF, s->XF, s->rrHistF, s->pApHistF,
+        defer_x, (const P2PView*)g.p2pView, ++g.p2pSeq, l1, (const int*)(s->halo && s->halo->p2p ? s->halo->err : nullptr));
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  hipLaunchKernelGGL(cg_local_f32_k, dim3(1), dim3(1024), 0, g.stream, m, q, (const CgScalarsF*)s->SF, s->XF, l1);
+  HIP_CHECK(hipGetLastError());
+  mark(s, R_DDOT);
+  sb_comm_reduction_f32(&s->XF->local, 1);
+  mark(s, R_COMM);
+  hipLaunchKernelGGL((cg_apply_local_f32_k<MODE>), dim3(1), dim3(64), 0, g.stream, s->SF, (const CgCommF*)s->XF, s->rrHistF,
+      s->pApHistF, defer_x);
   HIP_CHECK(hipGetLastError());
 }
 static void sp_flush_beta(sb_cg* s)
@@ -275,6 +314,11 @@ static void sp_loop_body(sb_cg* s, int k)
   HIP_CHECK(hipGetLastError());
   mark(s, R_WAXPBY);
   phase_mark(s, PH_P_UPDATE);
+  if (multi_rank() && s->halo) { // commExchange(&comm, p) (:122)
+    halo_exchange_f32(s->halo, s->pf, stop, true);
+    mark(s, R_COMM);
+    phase_mark(s, PH_HALO);
+  }
   // Ap = A p (:123) and p.Ap (:124-125)
   const bool fusedDot = s->fused && sp_spmv_has_dot(s);
   spmv_time_begin(s);
@@ -293,6 +337,20 @@ static void sp_loop_body(sb_cg* s, int k)
     // alpha (:126) inside the r update: r = r - alpha Ap (:128) + the level-1 values of the next r.r; x += alpha p is owed
     const uint32_t nG = (n + 255u) >> 8;
     const dim3 gridR(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount, (nG + 15u) / 16u)));
+    if (multi_rank()) { // the all-reduced alpha step, r update, the all-reduced beta step / loop test (x += alpha p stays owed)
+      sp_scalar<2>(s, s->partialsF, 1, 0);
+      mark(s, R_DDOT);
+      phase_mark(s, PH_ALPHA);
+      hipLaunchKernelGGL(cg_update_r_f32<0>, gridR, dim3(1024), 0, g.stream, n, (const float*)s->Apf, s->rf, s->SF, s->partials2F,
+          stop, 0u, (const float*)nullptr, (float*)nullptr, (float*)nullptr);
+      HIP_CHECK(hipGetLastError());
+      mark(s, R_WAXPBY);
+      phase_mark(s, PH_R_UPDATE);
+      sp_scalar<1>(s, s->partials2F, 1, 1);
+      mark(s, R_DDOT);
+      phase_mark(s, PH_BETA);
+      return;
+    }
     hipLaunchKernelGGL(cg_update_r_f32<1>, gridR, dim3(1024), 0, g.stream, n, (const float*)s->Apf, s->rf, s->SF, s->partials2F,
         stop, s->nPartials, (const float*)s->partialsF, s->rrHistF, s->pApHistF);
     HIP_CHECK(hipGetLastError());
@@ -337,6 +395,12 @@ static void sp_cg_start(sb_cg* s, int itermax, double eps)
   h.itermax = itermax, h.eps = (float)eps, h.hist_cap = s->hist_cap; // CG_FLOAT eps = (CG_FLOAT)param->eps (:64)
   HIP_CHECK(hipStreamSynchronize(g.stream));
   HIP_CHECK(hipMemcpy(s->SF, &h, sizeof h, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemset(s->XF, 0, sizeof(CgCommF)));
+  if (s->halo && s->halo->p2p && s->halo->push.p2pErr != &s->XF->p2p_error) {
+    // the push kernels of THIS solve look at its failure flag (per solve: the plan may be shared, sb_cg_start)
+    s->halo->push.p2pErr = &s->XF->p2p_error;
+    HIP_CHECK(hipMemcpy(s->halo->dPush, &s->halo->push, sizeof s->halo->push, hipMemcpyHostToDevice));
+  }
   HIP_CHECK(hipMemsetAsync(s->xf, 0, (size_t)n * sizeof(float), g.stream)); // x0 = 0 (:28)
   HIP_CHECK(hipMemsetAsync(s->pf, 0, (size_t)s->nc * sizeof(float), g.stream));
   mark(s, -1);
@@ -345,6 +409,8 @@ static void sp_cg_start(sb_cg* s, int itermax, double eps)
   if (n) hipLaunchKernelGGL(waxpby_f32_k, gridW, blockW, 0, g.stream, n, 1.0f, (const float*)s->xf, 0.0f, (const float*)s->xf, s->pf,
       (const int*)nullptr);
   mark(s, R_WAXPBY);
+  halo_exchange_f32(s->halo, s->pf, nullptr, false); // (:96)
+  mark(s, R_COMM);
   launch_spmv_f32(s->A, s->pf, s->Apf, nullptr, nullptr);
   mark(s, R_SPMVM);
   if (n) hipLaunchKernelGGL(waxpby_f32_k, gridW, blockW, 0, g.stream, n, 1.0f, (const float*)s->bf, -1.0f, (const float*)s->Apf,
@@ -375,6 +441,9 @@ static int sp_cg_finish(sb_cg* s)
   HIP_CHECK(hipStreamSynchronize(g.stream));
   CgScalarsF h;
   HIP_CHECK(hipMemcpy(&h, s->SF, sizeof h, hipMemcpyDeviceToHost));
+  CgCommF x;
+  HIP_CHECK(hipMemcpy(&x, s->XF, sizeof x, hipMemcpyDeviceToHost));
+  cg_comm_failures(s, x.p2p_error);
   if (s->timing) {
     for (double& v : s->region_ms) v = 0.0;
     for (size_t i = 1; i < s->evUsed; i++) {
@@ -434,5 +503,11 @@ static double sp_cg_check_residual(const sb_cg* s)
   float m = 0.0f;
   for (float v : h)
     if (v > m) m = v;
+  if (multi_rank()) { // commReduction(&residual, MAX), src/CGSolver.c:55
+    float* d = reinterpret_cast<float*>(g.scalar);
+    sb_h2d(d, &m, sizeof m);
+    sb_comm_reduction_f32(d, 0);
+    sb_d2h(&m, d, sizeof m);
+  }
   return (double)m;
 }

@@ -18,9 +18,14 @@ from . import capi, hostapi
 vp = C.c_void_p
 
 
-def attach(L, H, dist, rank, size):
+def attach(L, H, dist, rank, size, allgather_bytes=True):
     """Install the setup exchange (H.commSetExchange) and the run-time transport
-    (L.sb_comm_init_transport).  Returns the ctypes objects that must stay alive."""
+    (L.sb_comm_init_transport).  Returns the ctypes objects that must stay alive.
+
+    H: the host library whose commPartition runs on these ranks -- hostapi.host("single") for single precision, whose
+    float all-reduce (sb_comm_reduction_f32) gathers the ranks' float32 values through allgather_bytes and adds them
+    pairwise in rank order inside the layer.  allgather_bytes=False leaves that optional callback out, as a launcher
+    without one would (the peer-mapped set-up, which needs it for the halo handles, is then skipped as well)."""
     import torch
 
     def allgather(ctx, mine, cnt, out):
@@ -93,15 +98,17 @@ def attach(L, H, dist, rank, size):
     cb1, cb2 = hostapi.ALLGATHER_FN(allgather), hostapi.ALLTOALLV_FN(alltoallv)
     xchg = hostapi.ExchangeS(None, cb1, cb2)
     H.commSetExchange(C.byref(xchg))
-    def allgather_bytes(ctx, mine, nbytes, out):
+    def allgather_bytes_cb(ctx, mine, nbytes, out):
         t = torch.tensor(list(C.string_at(mine, nbytes)), dtype=torch.uint8)
         outs = [torch.zeros(nbytes, dtype=torch.uint8) for _ in range(size)]
         dist.all_gather(outs, t)
         C.memmove(out, bytes(torch.cat(outs).tolist()), nbytes * size)
 
-    cb3, cb4, cb5 = capi.ALLREDUCE_FN(allreduce), capi.EXCHANGE_FN(exchange), capi.ALLGATHER_BYTES_FN(allgather_bytes)
-    tr = capi.TransportS(None, cb3, cb4, cb5)
+    cb3, cb4, cb5 = capi.ALLREDUCE_FN(allreduce), capi.EXCHANGE_FN(exchange), capi.ALLGATHER_BYTES_FN(allgather_bytes_cb)
+    tr = capi.TransportS(None, cb3, cb4, cb5) if allgather_bytes else capi.TransportS(None, cb3, cb4)  # (unset field: NULL)
     L.sb_comm_init_transport(rank, size, C.byref(tr))
+    if not allgather_bytes:
+        return (cb1, cb2, xchg, cb3, cb4, tr)
     # in-kernel all-reduce over peer-mapped memory (include/sbhip.h): gather the IPC handles, open, self-test
     mine = (C.c_ubyte * 64)()
     have = L.sb_comm_p2p_handle(mine)

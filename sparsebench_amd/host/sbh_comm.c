@@ -486,17 +486,14 @@ void sbh_comm_attach_halo(Comm* c, CG_UINT nr, const CG_UINT* oldToNewPerm)
 void commExchange(Comm* c, CG_UINT numRows, CG_FLOAT* x)
 {
   if (c->size == 1) return;
-#if PRECISION == 1
-  (void)numRows, (void)x;
-  fprintf(stderr, "%s:%d: commExchange: the single-precision build runs on one rank only (%d here): the halo exchange "
-                  "carries doubles\n", __FILE__, __LINE__, c->size);
-  exit(EXIT_FAILURE);
-#else
   if (!c->dev) sbh_comm_attach_halo(c, numRows, NULL);
   if (!sb_is_device_ptr(x)) {
     fprintf(stderr, "commExchange: x must live in HBM (sb_malloc) when running on %d ranks\n", c->size);
     exit(EXIT_FAILURE);
   }
+#if PRECISION == 1
+  sb_halo_exchange_f32((sb_halo*)c->dev, x);
+#else
   sb_halo_exchange((sb_halo*)c->dev, x);
 #endif
 }
@@ -504,11 +501,16 @@ void commExchange(Comm* c, CG_UINT numRows, CG_FLOAT* x)
 void commReduction(CG_FLOAT* v, int op)
 {
   if (!sb_is_initialized() || sb_comm_size() == 1) return;
-#if PRECISION == 1
-  (void)v, (void)op;
-  fprintf(stderr, "%s:%d: commReduction: the single-precision build runs on one rank only (%d here): the all-reduce "
-                  "carries doubles\n", __FILE__, __LINE__, sb_comm_size());
-  exit(EXIT_FAILURE);
+#if PRECISION == 1 /* MPI_FLOAT (src/util.h:47): the float all-reduce, host-resident v staged through one device float */
+  if (sb_is_device_ptr(v)) {
+    sb_comm_reduction_f32(v, op);
+    return;
+  }
+  float* d = (float*)sb_malloc(sizeof(float));
+  sb_h2d(d, v, sizeof(float));
+  sb_comm_reduction_f32(d, op);
+  sb_d2h(v, d, sizeof(float));
+  sb_free(d);
 #else
   if (sb_is_device_ptr(v)) {
     sb_comm_reduction(v, op);
