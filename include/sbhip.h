@@ -146,6 +146,10 @@ uint32_t sb_matrix_row_patterns(const sb_matrix* m, uint32_t* uniformChunks);
 uint32_t sb_matrix_row_programs(const sb_matrix* m, uint32_t* maskedChunks);
 /* bytes the selected SpMV kernel really moves per launch (stream + x + y) */
 double sb_matrix_stream_bytes(const sb_matrix* m);
+/* either precision: 1 when the matrix (CRS: its private mirror) has row programs for EVERY chunk, no class dictionary and
+ * only mapped or simple windows -- what the SpMV with the p update inside needs of a matrix, and the condition under which a
+ * single-precision upload keeps its mirror (sb_set_sp_mirror): for an SP matrix 1 exactly when the mirror was built and kept. */
+int sb_matrix_all_row_programs(const sb_matrix* m);
 
 /* ---- kernels ---------------------------------------------------------------- */
 /* spMVM, src/solver.h:13: y = A x, x has nc entries, y has nr entries, both in
@@ -190,17 +194,30 @@ int sb_dot_order(void);
 
 /* ---- single precision: the reference's FLOAT_TYPE=SP build (src/util.h:47-51, -DPRECISION=1) ---------------- */
 /* CG_FLOAT = float everywhere: values, vectors and every operation; each product rounded to float before its add, sums
- * accumulate in float, f32 subnormals kept.  An SP matrix streams the reference layout only (no compressed mirror, no masked
- * row programs, no placement tuner).  Any number of ranks: sb_halo_exchange_f32 / sb_comm_reduction_f32 and the CG loop's
+ * accumulate in float, f32 subnormals kept.  By default an SP matrix streams the reference layout only (no placement tuner
+ * either); sb_set_sp_mirror below opts into the compressed mirror with masked row programs in float.  Any number of ranks: sb_halo_exchange_f32 / sb_comm_reduction_f32 and the CG loop's
  * float halo and float all-reduce on both data planes.  Crossing precisions -- an fp64 entry point on an
  * SP matrix or solver, or the other way round -- is a fatal error with file:line. */
+/* The SP mirror switch (opt-in, off by default): while it is on, sb_crs_upload_f32 / sb_scs_upload_f32 also build the
+ * device-private mirror of the fp64 path (Sell-C-sigma with C = 64; CRS through its private Sell-64-1 mirror) with the
+ * program values and the x window in float, and keep it if EVERY chunk became a row program (sb_matrix_all_row_programs);
+ * otherwise the matrix is exactly what an upload with the switch off makes.  A matrix keeps what it was built with.  With a
+ * mirror the default kernel mode is 5 at every size, sb_matrix_use_packed(m, 0 / 5) selects, sb_spmv_native_dot_f32 returns
+ * level-1 values for CRS too, and the one-rank fused CG loop takes the p update inside the SpMV (3 launches per body;
+ * sb_cg_set_fuse_p / SB_FUSE_P=0 turn that off).  Same bits as the streaming kernels everywhere.
+ * SB_SP_MIRROR=0|1 sets the process default at the first call (any other value, or an argument other than 0 / 1, ends the
+ * process with a message); sb_sp_mirror works before sb_init.  SB_SP_MIRROR_REPORT=1: every SP upload prints one line to
+ * stderr: SP_MIRROR built=<0|1> fmt=<crs|scs> chunks=<n> programs=<n> window=<slots> reason=<text>. */
+void sb_set_sp_mirror(int on);
+int sb_sp_mirror(void);
 sb_matrix* sb_crs_upload_f32(uint32_t nr, uint32_t nc, const uint32_t* rowPtr, const uint32_t* colInd, const float* val);
 sb_matrix* sb_scs_upload_f32(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigma, uint32_t nChunks, uint32_t nElems,
                              const uint32_t* chunkPtr, const uint32_t* chunkLens, const uint32_t* colInd, const float* val,
                              const uint32_t* oldToNewPerm, const uint32_t* newToOldPerm);
 int sb_matrix_precision(const sb_matrix* m); /* 1 single, 2 double (the reference's PRECISION values) */
 void sb_spmv_f32(const sb_matrix* m, const float* x, float* y); /* as sb_spmv */
-/* as sb_spmv_native_dot: 2 = the LEVEL-1 values of x . y (Sell-64; ceil(nr / 256) floats), 0 = none (y only) */
+/* as sb_spmv_native_dot: 2 = the LEVEL-1 values of x . y (Sell-64, and CRS through a selected mirror; ceil(nr / 256) floats),
+ * 0 = none (y only) */
 int sb_spmv_native_dot_f32(const sb_matrix* m, const float* x, float* y, float* l1_dev);
 void sb_permute_f32(const sb_matrix* m, const float* in_orig, float* out_perm);
 void sb_unpermute_f32(const sb_matrix* m, const float* in_perm, float* out_orig);

@@ -39,6 +39,7 @@ SYMBOLS = [
     "sb_crs_upload_f32", "sb_scs_upload_f32", "sb_matrix_precision", "sb_spmv_f32", "sb_spmv_native_dot_f32", "sb_permute_f32",
     "sb_unpermute_f32", "sb_waxpby_f32", "sb_ddot_f32", "sb_ddot_partials_f32", "sb_reduce_final_f32", "sb_cg_create_f32",
     "sb_cg_solution_f32", "sb_comm_reduction_f32", "sb_rank_reduce_f32", "sb_halo_exchange_f32",
+    "sb_set_sp_mirror", "sb_sp_mirror", "sb_matrix_all_row_programs",
     "sb_matrix_place", "sb_matrix_place_at", "sb_matrix_place_home", "sb_placement_arena_bytes", "sb_placement_probe", "sb_matrix_place_fresh", "sb_matrix_place_commit", "sb_matrix_placement", "sb_matrix_placement_report", "sb_matrix_debug_ptrs", "sb_cg_debug_ptrs",
 ]
 
@@ -198,6 +199,9 @@ def load():
         "sb_comm_reduction_f32": (None, [vp, C.c_int]),
         "sb_rank_reduce_f32": (C.c_float, [vp, C.c_int, C.c_int]),
         "sb_halo_exchange_f32": (None, [vp, vp]),
+        "sb_set_sp_mirror": (None, [C.c_int]),
+        "sb_sp_mirror": (C.c_int, []),
+        "sb_matrix_all_row_programs": (C.c_int, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -22,6 +22,7 @@
 #include "kernels_sp.hip.h"
 #include "kernels_sp_comm.hip.h"
 #include "pack.hip.h"
+#include "pack_sp.hip.h"
 
 #include <algorithm>
 #include <iterator>
@@ -248,6 +249,8 @@ struct sb_matrix {
   int16_t* mRowBase  = nullptr; // per row: base slot that lines the row up with its chunk's program (may be < 0)
   ProgBlock* mProgs  = nullptr;
   uint32_t mDict = 0, nProgs = 0, nMaskedChunks = 0;
+  uint32_t nProgBlocks = 0;      // blocks of 8 entries behind mProgs
+  ProgBlockF* mProgsF = nullptr; // single precision with a mirror (sbhip_sp.inc.h): the programs narrowed to float; mProgs is then NULL
   PatEntry* mClassDict = nullptr; // its class tables, windows and segments: the level-5 form's, or its own
   TileSeg* mSegs       = nullptr; // (mOwnsTables) when the windows are laid out in original column order
   uint16_t* mSlotMap   = nullptr; // ... then: [tile][mMapStride] slot -> device column - the 256-slot block's base
@@ -264,7 +267,8 @@ struct sb_matrix {
   uint32_t nPatClasses  = 0;
   double patBytes       = 0.0;
   // single precision (sb_crs_upload_f32 / sb_scs_upload_f32): prec = 1, the values in valf and val == NULL; it streams the
-  // reference layout only (no mirror, no placement tuner)
+  // reference layout unless the upload built the opt-in float mirror (sb_set_sp_mirror: mProgsF here, or in `mirror` for CRS);
+  // no placement tuner
   int prec    = 2; // the reference's PRECISION: 1 single, 2 double
   float* valf = nullptr;
 };
@@ -339,6 +343,7 @@ struct sb_cg {
   double* partials2 = nullptr; // level-0 partials of r.r (the p.Ap ones stay in `partials` while it reads them)
   // single precision (sb_cg_create_f32; sbhip_sp.inc.h): prec = 1 and the loop's state below; the double members stay NULL
   int prec = 2;
+  float* pf2 = nullptr; // the second p buffer of the fused p update (spmv_prog_fusep_f32): body k reads buffer (k-1) & 1, writes k & 1; pf is buffer 0
   float *rf = nullptr, *pf = nullptr, *Apf = nullptr, *xf = nullptr, *bf = nullptr, *xexactf = nullptr;
   CgScalarsF* SF = nullptr;
   float *partialsF = nullptr, *partials2F = nullptr, *rrHistF = nullptr, *pApHistF = nullptr;

@@ -8,6 +8,7 @@ enum { R_WAXPBY = 0, R_SPMVM = 1, R_DDOT = 2, R_COMM = 3 };
 // single precision (sbhip_sp.inc.h): the sb_cg_* calls below hand a solver made by sb_cg_create_f32 (prec 1) to these
 static void sp_cg_free_arrays(sb_cg* s);
 static int sp_launches_per_body(const sb_cg* s);
+static bool sp_fusep_plan(sb_cg* s);
 static void sp_cg_start(sb_cg* s, int itermax, double eps);
 static void sp_cg_run_iters(sb_cg* s, int iters);
 static int sp_cg_finish(sb_cg* s);
@@ -256,7 +257,7 @@ void sb_cg_set_fuse_p(sb_cg* s, int on)
 int sb_cg_fuse_p(sb_cg* s)
 {
   if (s->seqLatched < 0) apply_dot_order(s);
-  return s->prec == 2 && fusep_plan(s) ? 1 : 0;
+  return (s->prec == 1 ? sp_fusep_plan(s) : fusep_plan(s)) ? 1 : 0;
 }
 
 // hipGraph replay of a loop body was measured slower (-7 % at 128^3, -13 ... -35 % at 64^3: docs/LAB_NOTES.md) and removed;

@@ -795,6 +795,7 @@ static bool build_masked(sb_matrix* m, const PatternPlan& P)
   HIP_CHECK(hipMemcpy(m->mRowBase, mBase.data(), mBase.size() * sizeof(int16_t), hipMemcpyHostToDevice));
   m->mProgs        = (ProgBlock*)upload(progs.data(), progs.size() * sizeof(ProgBlock));
   m->nProgs        = (uint32_t)progIndex.size();
+  m->nProgBlocks   = (uint32_t)progs.size();
   m->nMaskedChunks = nMasked;
   m->mDict         = Q.anyL ? 256u : 0u;
   m->mClassDict    = P.dClassDict; // (shared with the level-5 form unless the windows are the mapped ones)
@@ -1327,7 +1328,7 @@ void sb_matrix_free(sb_matrix* m)
   if (m->patSegs != m->tileSegs) sb_free(m->patSegs);
   sb_free(m->tileSegPtr), sb_free(m->tileSegs), sb_free(m->pslots);
   sb_free(m->rowBase), sb_free(m->tileClass), sb_free(m->jcodes), sb_free(m->classDict), sb_free(m->tileHdrs), sb_free(m->rowPats), sb_free(m->excRows);
-  sb_free(m->mHdrs), sb_free(m->mStream), sb_free(m->mRowBase), sb_free(m->mProgs), sb_free(m->mSlotMap);
+  sb_free(m->mHdrs), sb_free(m->mStream), sb_free(m->mRowBase), sb_free(m->mProgs), sb_free(m->mProgsF), sb_free(m->mSlotMap);
   if (m->mOwnsTables) sb_free(m->mClassDict), sb_free(m->mSegs);
   if (m->mirror) sb_matrix_free(m->mirror);
   delete m;
@@ -1336,9 +1337,11 @@ void sb_matrix_free(sb_matrix* m)
 int sb_matrix_pack_level(const sb_matrix* m) { return m->packLevel; }
 void sb_matrix_use_packed(sb_matrix* m, int mode)
 { // 5: the pattern kernel on masked row programs (pack.hip.h level 6) where the matrix has them; any other mode, or a matrix
-  // without them: the reference-layout stream (0)
-  if (mode != 0) SB_NEED_PREC(m, 2, "sb_matrix_use_packed (a single-precision matrix streams its reference layout only)");
+  // without them: the reference-layout stream (0).  A single-precision matrix has them only if its upload built the float
+  // mirror (sb_set_sp_mirror); without one any mode but 0 is refused
   const sb_matrix* pm = m->fmt == 0 ? m->mirror : m;
+  if (mode != 0 && !(m->prec == 1 && pm && pm->mProgsF))
+    SB_NEED_PREC(m, 2, "sb_matrix_use_packed (a single-precision matrix streams its reference layout only)");
   m->usePacked        = mode >= 5 && pm && pm->mHdrs ? 5 : 0;
 }
 int sb_matrix_packed_mode(const sb_matrix* m) { return m->usePacked; }
@@ -1364,6 +1367,7 @@ uint32_t sb_matrix_row_programs(const sb_matrix* m, uint32_t* maskedChunks)
 }
 double sb_matrix_stream_bytes(const sb_matrix* m)
 { // bytes the SELECTED SpMV kernel moves per launch (matrix stream + x once + y once)
+  if (m->prec == 1 && m->usePacked == 5) return pat_of(m)->mBytes + 4.0 * pat_of(m)->nrPadded + 4.0 * m->nc; // (mBytes: 128-byte program blocks)
   if (m->fmt == 0 && m->usePacked == 5) return m->mirror->mBytes + 8.0 * m->mirror->nrPadded + 8.0 * m->nc;
   if (m->fmt == 1 && m->usePacked == 5) return m->mBytes + 8.0 * m->nrPadded + 8.0 * m->nc;
   if (m->fmt == 0 && m->usePacked == 3) return m->mirror->patBytes + 8.0 * m->mirror->nrPadded + 8.0 * m->nc;

@@ -1,16 +1,124 @@
 // sbhip_sp.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context): single
 // precision, the reference's FLOAT_TYPE=SP build (src/util.h:47-51).  Matrices, the reference-shaped operations and the CG loop
 // on float data, over the kernels of kernels_sp.hip.h, on one rank or several (kernels_sp_comm.hip.h: float halo and float
-// all-reduce on both data planes).  An SP matrix always streams its reference layout: no compressed mirror, no masked
-// row programs, no p update inside the SpMV -- and no placement tuner: its proxy is an fp64 loop body.
+// all-reduce on both data planes).  By default an SP matrix streams its reference layout.  With the switch below on
+// (opt-in) an upload also builds the device-private mirror -- compressed tiles, masked row programs -- in float where EVERY
+// chunk becomes a row program, and the loop multiplies through pack_sp.hip.h: spmv_prog_f32, and on one rank
+// spmv_prog_fusep_f32 with the p update inside.  No placement tuner: its proxy is an fp64 loop body.
 // ===========================================================================
 // single precision
 // ===========================================================================
+// The process default of the SP mirror (include/sbhip.h: sb_sp_mirror): 0 off, 1 on.  SB_SP_MIRROR=0|1, read on first use --
+// before sb_init too; anything else ends the process.  Consulted by the two uploads; a matrix keeps what it was built with.
+static int g_spMirror = -1; // -1: not read yet
+int sb_sp_mirror(void)
+{
+  if (g_spMirror < 0) {
+    const char* e = getenv("SB_SP_MIRROR");
+    if (!e || !*e || strcmp(e, "0") == 0) g_spMirror = 0;
+    else if (strcmp(e, "1") == 0) g_spMirror = 1;
+    else SB_FATAL("SB_SP_MIRROR=%s: expected 0 or 1", e);
+  }
+  return g_spMirror;
+}
+void sb_set_sp_mirror(int on)
+{
+  if (on != 0 && on != 1) SB_FATAL("sb_set_sp_mirror(%d): expected 0 (off) or 1 (on)", on);
+  g_spMirror = on;
+}
+
+// the matrix-only part of spmv_fusep_possible: row programs for every chunk, no class dictionary, mapped or simple windows
+static bool all_row_programs(const sb_matrix* pm)
+{
+  return pm && pm->mHdrs && pm->mDict == 0 && pm->nMaskedChunks == pm->nChunks && (pm->mSlotMap != nullptr || pm->mAllSimple);
+}
+int sb_matrix_all_row_programs(const sb_matrix* m) { return all_row_programs(m->fmt == 0 ? m->mirror : m) ? 1 : 0; }
+static const char* why_not_all_row_programs(const sb_matrix* pm)
+{
+  if (!pm || !pm->mHdrs) return "no row programs (the pattern levels stop before level 6)";
+  if (pm->mDict != 0 || pm->nMaskedChunks != pm->nChunks) return "chunks with per-lane code words";
+  return "a window that is neither mapped nor simple";
+}
+
+// The builder of the mirror (sbhip_matrix.inc.h) never computes with matrix values, it only tells them apart -- by bit pattern:
+// the dictionary, the pad test (__double_as_longlong(v) == 0), the pair keys and the program fit (build_masked's Ent::v is the
+// 64-bit pattern) all work on the bits, and the host only copies the doubles.  So it runs unchanged on doubles whose element i
+// holds float i's 32 bits ZERO-EXTENDED into the 64-bit pattern.  Not a numeric conversion: +0.0f becomes all-zero bits, the
+// pad marker; -0.0f, subnormals, Inf and every NaN payload stay distinct and recoverable (a numeric widening would quiet
+// signalling NaNs).  Every embedded double is +0.0 or a positive subnormal: should any host code compare them as numbers, that
+// is bit equality as long as the host runs without denormals-are-zero -- the case for the Makefile's flags (-O3, no fast-math).
+static std::vector<double> sp_embed(const float* v, size_t n)
+{
+  std::vector<double> d(n);
+  for (size_t i = 0; i < n; i++) {
+    uint32_t b;
+    memcpy(&b, v + i, 4);
+    const uint64_t w = b;
+    memcpy(&d[i], &w, 8);
+  }
+  return d;
+}
+
+// ProgBlock -> ProgBlockF (pack_sp.hip.h: prog_narrow_k); the fp64 programs go
+static void sp_narrow_programs(sb_matrix* pm)
+{
+  const uint32_t nb = pm->nProgBlocks;
+  if (pm->mWindow > 256u * (pm->mCPT == 8 ? 15u : 12u) && pm->mSlotMap) SB_FATAL("mapped window of %u slots: more than a workgroup stages", pm->mWindow);
+  HIP_CHECK(hipMalloc(&pm->mProgsF, (size_t)std::max(nb, 1u) * sizeof(ProgBlockF)));
+  hipLaunchKernelGGL(prog_narrow_k, dim3((nb * 8u + 255u) / 256u + 1u), dim3(256), 0, g.stream, (const ProgBlock*)pm->mProgs, pm->mProgsF, nb);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  sb_free(pm->mProgs);
+  pm->mProgs = nullptr;
+  pm->mBytes -= (double)(sizeof(ProgBlock) - sizeof(ProgBlockF)) * nb;
+}
+
+// everything the chain built on an SCS matrix goes; what scs_upload_common made stays: an upload with the switch off
+static void sp_drop_mirror(sb_matrix* m)
+{
+  sb_free(m->pmeta), sb_free(m->pidx), sb_free(m->pcodes), sb_free(m->pdict);
+  if (m->patSegs != m->tileSegs) sb_free(m->patSegs);
+  sb_free(m->tileSegPtr), sb_free(m->tileSegs), sb_free(m->pslots);
+  sb_free(m->rowBase), sb_free(m->tileClass), sb_free(m->jcodes), sb_free(m->classDict), sb_free(m->tileHdrs), sb_free(m->rowPats), sb_free(m->excRows);
+  sb_free(m->mHdrs), sb_free(m->mStream), sb_free(m->mRowBase), sb_free(m->mProgs), sb_free(m->mProgsF), sb_free(m->mSlotMap);
+  if (m->mOwnsTables) sb_free(m->mClassDict), sb_free(m->mSegs);
+  sb_matrix b;
+  b.prec = m->prec, b.fmt = m->fmt, b.nr = m->nr, b.nc = m->nc, b.nnz = m->nnz, b.C = m->C, b.sigma = m->sigma, b.nChunks = m->nChunks;
+  b.nElems = m->nElems, b.nrPadded = m->nrPadded, b.permuted = m->permuted, b.chunkPtr = m->chunkPtr, b.chunkLens = m->chunkLens;
+  b.colInd = m->colInd, b.valf = m->valf, b.oldToNew = m->oldToNew, b.newToOld = m->newToOld;
+  *m = b;
+}
+
+static void sp_mirror_report(const sb_matrix* m, const char* reason)
+{
+  if (!(getenv("SB_SP_MIRROR_REPORT") && atoi(getenv("SB_SP_MIRROR_REPORT")) != 0)) return;
+  const sb_matrix* pm = m->fmt == 0 ? m->mirror : m;
+  const bool built    = pm && pm->mProgsF;
+  fprintf(stderr, "SP_MIRROR built=%d fmt=%s chunks=%u programs=%u window=%u reason=%s\n", built ? 1 : 0, m->fmt == 0 ? "crs" : "scs",
+      built ? pm->nChunks : (m->fmt == 1 ? m->nChunks : (m->nr + 63u) / 64u), built ? pm->nProgs : 0u, built ? pm->mWindow : 0u, reason);
+}
+
 sb_matrix* sb_crs_upload_f32(uint32_t nr, uint32_t nc, const uint32_t* rowPtr, const uint32_t* colInd, const float* val)
 {
   need_init();
   need_float_allreduce("sb_crs_upload_f32");
-  return crs_upload_common(nr, nc, rowPtr, colInd, val, 1); // (no mirror, no placement tuner: see the head of this file)
+  sb_matrix* m       = crs_upload_common(nr, nc, rowPtr, colInd, val, 1); // (no placement tuner: see the head of this file)
+  const char* reason = "SB_SP_MIRROR / sb_set_sp_mirror is off";
+  if (sb_sp_mirror()) { // the private Sell-64-1 mirror of build_crs_mirror, on the embedded values
+    const std::vector<double> emb = sp_embed(val, m->nnz);
+    build_crs_mirror(m, rowPtr, colInd, emb.data());
+    if (all_row_programs(m->mirror)) {
+      sp_narrow_programs(m->mirror);
+      m->usePacked = 5; // (at every size)
+      reason       = "every chunk is a row program";
+    } else {
+      reason = m->mirror ? why_not_all_row_programs(m->mirror) : "no pattern mirror (more than 255 distinct values, a stored +0.0 at column 0, or no row programs)";
+      if (m->mirror) sb_matrix_free(m->mirror);
+      m->mirror = nullptr, m->usePacked = 0;
+    }
+  }
+  sp_mirror_report(m, reason);
+  return m;
 }
 
 sb_matrix* sb_scs_upload_f32(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigma, uint32_t nChunks, uint32_t nElems,
@@ -19,7 +127,34 @@ sb_matrix* sb_scs_upload_f32(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigm
 {
   need_init();
   need_float_allreduce("sb_scs_upload_f32");
-  return scs_upload_common(nr, nc, C, sigma, nChunks, nElems, chunkPtr, chunkLens, colInd, val, oldToNewPerm, newToOldPerm, 1);
+  sb_matrix* m = scs_upload_common(nr, nc, C, sigma, nChunks, nElems, chunkPtr, chunkLens, colInd, val, oldToNewPerm, newToOldPerm, 1);
+  const char* reason = "SB_SP_MIRROR / sb_set_sp_mirror is off";
+  if (sb_sp_mirror()) {
+    if (C != 64) reason = "C != 64";
+    else if (nChunks == 0 || nElems == 0 || nr == 0) reason = "empty matrix";
+    else { // sb_scs_upload's chain, unchanged, on a temporary double copy of val that holds the floats' bit patterns
+      const std::vector<double> emb = sp_embed(val, nElems);
+      HIP_CHECK(hipMalloc(&m->val, ((size_t)nElems + SCS_SLACK) * sizeof(double)));
+      HIP_CHECK(hipMemset(m->val + nElems, 0, SCS_SLACK * sizeof(double)));
+      HIP_CHECK(hipMemcpy(m->val, emb.data(), (size_t)nElems * sizeof(double), hipMemcpyHostToDevice));
+      build_packed(m, emb.data(), oldToNewPerm);
+      build_lds_windows(m, chunkPtr, chunkLens, colInd, emb.data(), oldToNewPerm);
+      build_patterns(m, chunkPtr, chunkLens, colInd, emb.data(), oldToNewPerm);
+      product_modes_only(m);
+      HIP_CHECK(hipStreamSynchronize(g.stream));
+      sb_free(m->val);
+      m->val = nullptr;
+      if (all_row_programs(m)) {
+        sp_narrow_programs(m);
+        reason = "every chunk is a row program";
+      } else { // kept only whole: no class tables, exception entries or per-lane code words in the float kernels
+        reason = why_not_all_row_programs(m);
+        sp_drop_mirror(m);
+      }
+    }
+  }
+  sp_mirror_report(m, reason);
+  return m;
 }
 
 int sb_matrix_precision(const sb_matrix* m) { return m->prec; }
@@ -27,9 +162,80 @@ int sb_matrix_precision(const sb_matrix* m) { return m->prec; }
 static float* sp_scratch(int which, size_t n) { return reinterpret_cast<float*>(scratch_ws(which, (n + 1) / 2)); }
 
 // y = A x in the matrix's device row order; dotL1 != NULL (Sell-64 only): the level-1 values of x . y as well
+// the float mirror is there and selected (mode 5): SCS the matrix itself, CRS its private Sell-64-1 mirror
+static const sb_matrix* sp_mirror_selected(const sb_matrix* m)
+{
+  const sb_matrix* pm = m->fmt == 0 ? m->mirror : m;
+  return m->usePacked == 5 && pm && pm->mProgsF ? pm : nullptr;
+}
+// pack_sp.hip.h: y = A x over the row programs (+ the level-1 values of x . y)
+static void launch_prog_f32(const sb_matrix* pm, bool skipPad, const float* x, float* y, float* dotL1, const int* stop)
+{
+  const bool mapped = pm->mSlotMap != nullptr, dot = dotL1 != nullptr;
+  const uint32_t count = pm->mNTiles, pper = (count + 7) / 8;
+  const dim3 pgrid(pper * 8), block(256);
+  const size_t shmem = (16 + (size_t)pm->mWindow) * sizeof(float);
+  if (!stop) stop = zero_flag();
+#define PF_LAUNCH(CP, DO, SK, MP)                                                                                         \
+  SB_SPMV_LAUNCH((spmv_prog_f32<CP, DO, SK, MP>), pgrid, block, shmem, g.stream, pm->mHdrs, pm->mRowBase, pm->mProgsF,   \
+      pm->mSlotMap, pm->mMapStride, x, y, pm->nr, pm->nChunks, count, pper, pm->padCol, dotL1, stop)
+#define PF_PICK(CP, DO)                           \
+  do {                                            \
+    if (skipPad) {                                \
+      if (mapped) PF_LAUNCH(CP, DO, true, true);  \
+      else PF_LAUNCH(CP, DO, true, false);        \
+    } else {                                      \
+      if (mapped) PF_LAUNCH(CP, DO, false, true); \
+      else PF_LAUNCH(CP, DO, false, false);       \
+    }                                             \
+  } while (0)
+  if (pm->mCPT == 8) {
+    if (dot) PF_PICK(8, true);
+    else PF_PICK(8, false);
+  } else {
+    if (dot) PF_PICK(4, true);
+    else PF_PICK(4, false);
+  }
+#undef PF_PICK
+#undef PF_LAUNCH
+  HIP_CHECK(hipGetLastError());
+}
+// pack_sp.hip.h: Ap = A p_new with p_new = r + beta p_old formed on the way (which != 0: the first body), x += alpha p_old
+// where the previous body owes it, level-1 values of p_new . Ap into dotL1
+static void launch_prog_fusep_f32(const sb_matrix* pm, bool skipPad, const float* pold, const float* r, float* pnew, float* xsol,
+    float* y, const CgScalarsF* S, int which, float* dotL1)
+{
+  const bool mapped = pm->mSlotMap != nullptr;
+  const uint32_t count = pm->mNTiles, pper = (count + 7) / 8;
+  const dim3 pgrid(pper * 8), block(256);
+  const size_t shmem = (16 + (size_t)pm->mWindow) * sizeof(float);
+#define PFP_LAUNCH(CP, SK, MP)                                                                                                \
+  SB_SPMV_LAUNCH((spmv_prog_fusep_f32<CP, SK, MP>), pgrid, block, shmem, g.stream, pm->mHdrs, pm->mRowBase, pm->mProgsF,      \
+      pm->mSlotMap, pm->mMapStride, pold, r, pnew, xsol, y, S, which, pm->nr, pm->nChunks, count, pper, pm->padCol, dotL1)
+#define PFP_PICK(CP)                          \
+  do {                                        \
+    if (skipPad) {                            \
+      if (mapped) PFP_LAUNCH(CP, true, true); \
+      else PFP_LAUNCH(CP, true, false);       \
+    } else {                                  \
+      if (mapped) PFP_LAUNCH(CP, false, true); \
+      else PFP_LAUNCH(CP, false, false);      \
+    }                                         \
+  } while (0)
+  if (pm->mCPT == 8) PFP_PICK(8);
+  else PFP_PICK(4);
+#undef PFP_PICK
+#undef PFP_LAUNCH
+  HIP_CHECK(hipGetLastError());
+}
+
 static void launch_spmv_f32(const sb_matrix* m, const float* x, float* y, float* dotL1, const int* stop)
 {
   if (m->nr == 0) return;
+  if (const sb_matrix* pm = sp_mirror_selected(m)) {
+    launch_prog_f32(pm, m->fmt == 0, x, y, dotL1, stop);
+    return;
+  }
   if (m->fmt == 0) {
     if (dotL1) SB_FATAL("the single-precision CRS kernel has no fused dot: the CG loop adds a dot pass");
     if (m->tileRow) {
@@ -101,7 +307,7 @@ int sb_spmv_native_dot_f32(const sb_matrix* m, const float* x, float* y, float* 
 {
   need_init();
   SB_NEED_PREC(m, 1, "sb_spmv_native_dot_f32");
-  if (!(m->fmt == 1 && m->C == 64)) {
+  if (!(m->fmt == 1 && m->C == 64) && !sp_mirror_selected(m)) {
     launch_spmv_f32(m, x, y, nullptr, nullptr);
     return 0;
   }
@@ -225,15 +431,29 @@ static void sp_cg_free_arrays(sb_cg* s)
     HIP_CHECK(hipMemcpy(s->halo->dPush, &s->halo->push, sizeof s->halo->push, hipMemcpyHostToDevice));
   }
   sb_free(s->XF);
-  sb_free(s->rf), sb_free(s->pf), sb_free(s->Apf), sb_free(s->xf), sb_free(s->bf), sb_free(s->xexactf);
+  sb_free(s->rf), sb_free(s->pf), sb_free(s->pf2), sb_free(s->Apf), sb_free(s->xf), sb_free(s->bf), sb_free(s->xexactf);
   sb_free(s->SF), sb_free(s->partialsF), sb_free(s->partials2F), sb_free(s->rrHistF), sb_free(s->pApHistF);
 }
 
-static bool sp_spmv_has_dot(const sb_cg* s) { return s->A->fmt == 1 && s->A->C == 64; }
+static bool sp_spmv_has_dot(const sb_cg* s) { return (s->A->fmt == 1 && s->A->C == 64) || sp_mirror_selected(s->A); }
+// The p update inside the SpMV (pack_sp.hip.h: spmv_prog_fusep_f32; body = SpMV | r update with the alpha step | beta step): one
+// rank, the fused tree-order loop, the float mirror selected, and the wish (sb_cg_set_fuse_p, SB_FUSE_P, else the library's
+// default).  Inside a solve the answer is the one sp_cg_start latched, as fusep_plan does for fp64: the fused path keeps p
+// double-buffered, the in-place path does not, and the pieces of one solve must not mix them.
+static bool sp_fusep_plan(sb_cg* s)
+{
+  if (s->started && s->fusepLatched >= 0) return s->fusepLatched > 0;
+  if (s->fusepPlan < 0) {
+    const char* env = getenv("SB_FUSE_P");
+    s->fusepPlan    = (s->fusepWant >= 0 ? s->fusepWant != 0 : env ? atoi(env) != 0 : SB_FUSE_P_DEFAULT) ? 1 : 0;
+  }
+  // (nc == nr: the kernel forms p_new for every window column from r, which has nr entries)
+  return s->fusepPlan > 0 && s->fused == 1 && s->nr > 0 && s->nc == s->nr && !multi_rank() && sp_mirror_selected(s->A) != nullptr;
+}
 static int sp_launches_per_body(const sb_cg* s)
 {
   if (!s->fused) return 0;
-  if (!multi_rank()) return sp_spmv_has_dot(s) ? 3 : 4;
+  if (!multi_rank()) return sp_fusep_plan(const_cast<sb_cg*>(s)) || sp_spmv_has_dot(s) ? 3 : 4;
   int n = sp_spmv_has_dot(s) ? 5 : 6; // p update | SpMV | (dot pass) | alpha | r update | beta
   if (const sb_halo* h = s->halo) {
     if (halo_p2p_active(h)) n += (h->totalSend ? 1 : 0) + (h->indegree ? 1 : 0); // push, pull
@@ -291,6 +511,29 @@ static void sp_loop_body(sb_cg* s, int k)
   const uint32_t vb = 1024u, capV = (uint32_t)g.prop.multiProcessorCount * 2u;
   const dim3 gridV(std::max(1u, std::min(capV, (n / 4 + vb) / vb))), blockV(vb);
   const dim3 gridW(stream_grid(n, 256)), blockW(256);
+  if (sp_fusep_plan(s)) {
+    // p = r + beta p (:114; k = 1: p = r + 0.0 r, :109), the owed x update (:127) and Ap = A p with the p.Ap level-1 values
+    // (:123-125) in ONE launch: body k reads p_{k-1} in buffer (k - 1) & 1 and writes p_k into buffer k & 1
+    const int which = k == 1;
+    float* const pb[2] = { s->pf, s->pf2 };
+    const sb_matrix* pm = s->A->fmt == 0 ? s->A->mirror : s->A; // (the latched plan: whatever mode the matrix is in by now)
+    spmv_time_begin(s);
+    launch_prog_fusep_f32(pm, s->A->fmt == 0, which ? s->rf : pb[(k - 1) & 1], s->rf, pb[k & 1], s->xf, s->Apf, s->SF, which, s->partialsF);
+    spmv_time_end(s);
+    mark(s, R_SPMVM);
+    phase_mark(s, PH_SPMV);
+    const uint32_t nG = (n + 255u) >> 8;
+    const dim3 gridR(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount, (nG + 15u) / 16u)));
+    hipLaunchKernelGGL(cg_update_r_f32<1>, gridR, dim3(1024), 0, g.stream, n, (const float*)s->Apf, s->rf, s->SF, s->partials2F,
+        stop, s->nPartials, (const float*)s->partialsF, s->rrHistF, s->pApHistF);
+    HIP_CHECK(hipGetLastError());
+    mark(s, R_WAXPBY);
+    phase_mark(s, PH_R_UPDATE);
+    sp_scalar<1>(s, s->partials2F, 1, 1); // the beta step / loop test: a launch of its own (the next SpMV's tiles all need beta)
+    mark(s, R_DDOT);
+    phase_mark(s, PH_BETA);
+    return;
+  }
   if (k == 1) { // p = r + 0.0 r (:109)
     if (n) hipLaunchKernelGGL(cg_update_p_f32<0>, gridV, blockV, 0, g.stream, n, s->rf, s->pf, (float*)nullptr, s->SF, 1, 0u,
         (const float*)nullptr, (float*)nullptr);
@@ -382,6 +625,8 @@ static void sp_cg_start(sb_cg* s, int itermax, double eps)
   s->seqLatched = -1;
   s->seqLatched = cg_seq(s) ? 1 : 0;
   apply_dot_order(s);
+  s->fusepLatched = sp_fusep_plan(s) ? 1 : 0; // decided once per solve (sp_fusep_plan)
+  if (s->fusepLatched && !s->pf2) s->pf2 = (float*)sb_malloc((size_t)s->nc * sizeof(float));
   if (itermax + 2 > s->hist_cap) {
     sb_free(s->rrHistF), sb_free(s->pApHistF);
     s->hist_cap = itermax + 2;
@@ -403,6 +648,7 @@ static void sp_cg_start(sb_cg* s, int itermax, double eps)
   }
   HIP_CHECK(hipMemsetAsync(s->xf, 0, (size_t)n * sizeof(float), g.stream)); // x0 = 0 (:28)
   HIP_CHECK(hipMemsetAsync(s->pf, 0, (size_t)s->nc * sizeof(float), g.stream));
+  if (s->pf2) HIP_CHECK(hipMemsetAsync(s->pf2, 0, (size_t)s->nc * sizeof(float), g.stream));
   mark(s, -1);
   // prologue, src/CGSolver.c:94-100: p = x + 0.0 x ; Ap = A p ; r = b + (-1.0) Ap ; rtrans = r.r
   const dim3 gridW(stream_grid(n, 256)), blockW(256);
@@ -433,8 +679,13 @@ static void sp_cg_run_iters(sb_cg* s, int iters)
 static int sp_cg_finish(sb_cg* s)
 {
   if (s->nr) {
-    hipLaunchKernelGGL(cg_x_finalize_f32, dim3(stream_grid(s->nr, 256)), dim3(256), 0, g.stream, s->nr, s->xf, (const float*)s->pf,
-        (const CgScalarsF*)s->SF);
+    // (fused p update: body k left p_k in buffer k & 1; which body ran last is on the device -- n_pAp -- not on the host)
+    if (sp_fusep_plan(s))
+      hipLaunchKernelGGL(cg_x_finalize2_f32, dim3(stream_grid(s->nr, 256)), dim3(256), 0, g.stream, s->nr, s->xf, (const float*)s->pf,
+          (const float*)s->pf2, (const CgScalarsF*)s->SF);
+    else
+      hipLaunchKernelGGL(cg_x_finalize_f32, dim3(stream_grid(s->nr, 256)), dim3(256), 0, g.stream, s->nr, s->xf, (const float*)s->pf,
+          (const CgScalarsF*)s->SF);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemsetAsync(&s->SF->x_pending, 0, sizeof(int), g.stream));
   }
@@ -452,8 +703,9 @@ static int sp_cg_finish(sb_cg* s)
       if (s->evRegion[i] >= 0) s->region_ms[s->evRegion[i]] += ms;
     }
   }
-  s->timing     = false;
-  s->seqLatched = -1;
+  s->timing       = false;
+  s->fusepLatched = -1; // the solve is over: the next sp_cg_start decides anew
+  s->seqLatched   = -1;
   apply_dot_order(s);
   return h.iters + 1;
 }

@@ -119,16 +119,30 @@ class Problem:
     and (upload=True) resident in HBM."""
 
     def __init__(self, filename="generate", nx=16, ny=16, nz=16, fmt="scs", Cc=64, sigma=1,
-                 rank=0, size=1, upload=True, precision="double"):
+                 rank=0, size=1, upload=True, precision="double", mirror=None):
         # precision="single": the SP host library (CG_FLOAT = float, the _f32 entry points of the HIP layer)
+        # mirror (single precision only): None = the process default (sb_sp_mirror, SB_SP_MIRROR); True / False = the SP
+        # mirror switch set around the upload and put back afterwards
+        if mirror is not None and precision != "single":
+            if mirror:
+                raise ValueError("mirror=True is the single-precision mirror switch; a double-precision matrix builds its mirror anyway")
+            mirror = None
         self.H = host(precision)
         self.precision = precision
         self.fdtype = np.float32 if precision == "single" else np.float64
         self.fmt = fmt
         self.upload = upload
-        self.ptr = self.H.sbh_problem_create(os.fsencode(filename), nx, ny, nz,
-                                             0 if fmt == "crs" else 1, Cc, sigma, rank, size,
-                                             1 if upload else 0)
+        L = capi.load()
+        old = L.sb_sp_mirror() if mirror is not None else None
+        if mirror is not None:
+            L.sb_set_sp_mirror(1 if mirror else 0)
+        try:
+            self.ptr = self.H.sbh_problem_create(os.fsencode(filename), nx, ny, nz,
+                                                 0 if fmt == "crs" else 1, Cc, sigma, rank, size,
+                                                 1 if upload else 0)
+        finally:
+            if mirror is not None:
+                L.sb_set_sp_mirror(old)
         for i, name in enumerate(_SCALARS):
             setattr(self, name, int(self.H.sbh_problem_scalar(self.ptr, i)))
 
@@ -192,6 +206,10 @@ class Problem:
         n = capi.load().sb_matrix_placement_report(self.matrix, us)
         return {"probes_timed": n, "us_first_pair": round(us[0], 2), "us_kept": round(us[1], 2), "us_slowest": round(us[2], 2)} if n else None
 
+    def all_row_programs(self):
+        """1: every chunk is a row program with a mapped or simple window (sb_matrix_all_row_programs)"""
+        return capi.load().sb_matrix_all_row_programs(self.matrix)
+
     def pack_info(self):
         L = capi.load()
         uni = C.c_uint32(0)
@@ -252,7 +270,7 @@ class CG:
         return self.L.sb_cg_launches_per_body(self.ptr)
 
     def fuse_p(self):
-        """1: the loop takes the p update inside the SpMV launch (4 launches per body)"""
+        """1: the loop takes the p update inside the SpMV launch"""
         return self.L.sb_cg_fuse_p(self.ptr)
 
     def collectives_per_body(self):

@@ -6,6 +6,9 @@ the SpMV's microseconds between HIP events inside the loop (sb_cg_spmv_timing), 
 (sb_matrix_spmv_bytes: SP SCS 8 B/element + 8 B/chunk + 4 B/padded row + 4 B/column, SP CRS 8 B/nnz + 4 B/(row+1) +
 4 B/row + 4 B/column; DP 12 / 8 / 8 / 8) and the fraction of 8 TB/s those bytes reach.  The DP matrices get the
 upload's placement tuner (its report is included), the SP ones stream where hipMalloc put them.
+Two more rows per format run the structure-exploiting loops in the same process: `..._fp32_mirror` (the opt-in SP mirror,
+sb_set_sp_mirror: spmv_prog_fusep_f32, 3 launches per body) and `..._fp64_mirror` (the fp64 default: masked row programs,
+spmv_prog_fusep); every row carries `stream_bytes`, what its selected kernel really moves (sb_matrix_stream_bytes).
 
 usage: tools/sp_rate.py [--n 128] [--steps 40] [--warmup 5]
 """
@@ -21,9 +24,13 @@ from sparsebench_amd import capi, hostapi  # noqa: E402
 PEAK = 8.0e12
 
 
-def one(L, n, fmt, Cc, sigma, precision, steps, warmup):
-    p = hostapi.Problem("generate", n, n, n, fmt=fmt, Cc=Cc, sigma=sigma, precision=precision)
-    if precision == "double":
+def one(L, n, fmt, Cc, sigma, precision, steps, warmup, mirror=False):
+    p = hostapi.Problem("generate", n, n, n, fmt=fmt, Cc=Cc, sigma=sigma, precision=precision,
+                        mirror=mirror if precision == "single" else None)
+    if mirror:
+        if p.use_packed(5) != 5:
+            raise RuntimeError("%s %s: no row programs for this matrix" % (fmt, precision))
+    elif precision == "double":
         p.use_packed(0)  # the reference layout: the stream the SP matrix has too (the section-8d loop)
     cg = hostapi.CG(p, fused=True, dot_order="tree")
     itermax = warmup + 2 * steps + 10
@@ -44,7 +51,9 @@ def one(L, n, fmt, Cc, sigma, precision, steps, warmup):
     nbytes = p.spmv_bytes()
     out = {"ms_per_step": round(ms / steps, 4), "spmv_us": round(us, 2), "spmv_launches": launches,
            "spmv_bytes": int(nbytes), "frac_of_8TBs": round(nbytes / (us * 1e-6) / PEAK, 4), "k": k,
-           "launches_per_body": cg.launches_per_body()}
+           "launches_per_body": cg.launches_per_body(), "fuse_p": cg.fuse_p(), "mode": p.pack_info()["mode"],
+           "stream_bytes": int(p.stream_bytes())}
+    out["frac_of_8TBs_stream_bytes"] = round(out["stream_bytes"] / (us * 1e-6) / PEAK, 4)  # (moved bytes; not a roofline figure)
     if precision == "double":
         out["placement"] = p.placement_report()
     cg.free()
@@ -63,6 +72,8 @@ def main():
     for label, fmt, Cc, sigma in (("scs64_256", "scs", 64, 256), ("crs", "crs", 64, 1)):
         for precision, key in (("single", "fp32"), ("double", "fp64")):
             res["%s_%s" % (label, key)] = one(L, a.n, fmt, Cc, sigma, precision, a.steps, a.warmup)
+        for precision, key in (("single", "fp32_mirror"), ("double", "fp64_mirror")):
+            res["%s_%s" % (label, key)] = one(L, a.n, fmt, Cc, sigma, precision, a.steps, a.warmup, mirror=True)
     print(json.dumps(res))
 
 
