@@ -283,6 +283,16 @@ int sb_comm_data_plane_selected(void);
  * p[elementsToSend], src/comm.c:635-638) instead of a launch of its own; 0 = separate push kernel (default;
  * SB_HALO_PUSH_INSIDE=1 changes the default).  Same bits.  Collective, between solves. */
 void sb_comm_halo_push_inside(int on);
+/* The peer-mapped halo exchange folded into the STREAMING loop's own kernels (Sell-C-sigma, C = 64, the reference-layout
+ * kernel; double and single precision): 1 = the p update sends the boundary rows it has just written and the SpMV's blocks
+ * that hold a halo column, dispatched last, wait for the neighbours' flags and read the staging area themselves -- no push
+ * and no pull launch, 5 launches per body instead of 7; 0 = today's body (default; SB_HALO_FOLD=0|1 sets the process
+ * default at the first use, any other value ends the process).  Same bits.  Its per-step time on ranks with a GPU each
+ * is unmeasured.  sb_comm_halo_fold: collective, between solves, synchronises the layer's stream.
+ * sb_comm_halo_fold_selected answers before sb_init.  A solve that cannot fold (one rank, the communicator's plane, CRS,
+ * generic C, the row-program / mirror kernels, fused = 0, the seq dot order) silently keeps its body: sb_cg_halo_fold. */
+void sb_comm_halo_fold(int on);
+int sb_comm_halo_fold_selected(void);
 /* what the RCCL communicator itself reports (ncclCommCount / ncclCommUserRank / ncclCommCuDevice):
  * out = {ranks, this rank, HIP device}; returns 0 (out = -1) without an RCCL communicator */
 int sb_comm_rccl_info(int out[3]);
@@ -366,6 +376,9 @@ int sb_cg_collectives_per_body(sb_cg* s);
  * on = 1 / 0 selects / deselects it, -1 = default (SB_FUSE_P, else the library's choice).  sb_cg_fuse_p: what the loop will do. */
 void sb_cg_set_fuse_p(sb_cg* s, int on);
 int sb_cg_fuse_p(sb_cg* s);
+/* 1: the next solve of this solver runs the folded body of sb_comm_halo_fold (sb_cg_launches_per_body then counts 5),
+ * 0: today's body.  Decided once per solve (sb_cg_start), like the fused p update and the dot order. */
+int sb_cg_halo_fold(sb_cg* s);
 /* The alpha step (src/CGSolver.c:124-126) inside the r update's launch: every workgroup of the r update reduces the p.Ap
  * values itself in the canonical order (identical bits everywhere), workgroup 0 records the step -- one launch fewer per loop
  * body on one rank (sb_cg_launches_per_body tells).  on = 1 / 0, -1 = default (SB_FUSE_ALPHA, else on).  Same bits. */

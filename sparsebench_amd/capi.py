@@ -31,7 +31,7 @@ SYMBOLS = [
     "sb_matrix_packed_mode", "sb_matrix_crs_kernel", "sb_matrix_lds_window", "sb_matrix_pattern_classes", "sb_matrix_row_patterns", "sb_matrix_row_programs", "sb_comm_p2p_handle", "sb_comm_p2p_open", "sb_comm_p2p_enabled", "sb_halo_p2p_enabled", "sb_cg_start", "sb_cg_finish", "sb_cg_vector_phase", "sb_cg_launches_per_body",
     "sb_comm_init_transport", "sb_comm_p2p_reason", "sb_halo_p2p_reason",
     "sb_comm_data_plane", "sb_comm_data_plane_selected", "sb_comm_rccl_info", "sb_cg_phase_timing", "sb_cg_phase_ms",
-    "sb_comm_halo_push_inside", "sb_lab_build", "sb_cg_collectives_per_body",
+    "sb_comm_halo_push_inside", "sb_comm_halo_fold", "sb_comm_halo_fold_selected", "sb_cg_halo_fold", "sb_lab_build", "sb_cg_collectives_per_body",
     "sb_cg_set_fuse_p", "sb_cg_fuse_p", "sb_cg_set_fuse_alpha", "sb_cg_set_fuse_beta",
     "sb_malloc_host_visible", "sb_host_visible_reason", "sb_malloc_pinned_host", "sb_free_pinned_host", "sb_copy_counters",
     "sb_region_begin", "sb_region_end", "sb_region_seconds", "sb_region_reset",
@@ -149,6 +149,9 @@ def load():
         "sb_comm_data_plane": (None, [C.c_int]),
         "sb_comm_data_plane_selected": (C.c_int, []),
         "sb_comm_halo_push_inside": (None, [C.c_int]),
+        "sb_comm_halo_fold": (None, [C.c_int]),
+        "sb_comm_halo_fold_selected": (C.c_int, []),
+        "sb_cg_halo_fold": (C.c_int, [vp]),
         "sb_lab_build": (C.c_int, []),
         "sb_cg_collectives_per_body": (C.c_int, [vp]),
         "sb_cg_set_fuse_p": (None, [vp, C.c_int]),

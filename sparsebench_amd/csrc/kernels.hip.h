@@ -1111,6 +1111,264 @@ __global__ __launch_bounds__(256) void halo_pull_k(const int* __restrict__ srcRa
   for (int i = (int)threadIdx.x; i < rcount[j]; i += 256) dst[i] = __builtin_nontemporal_load(src + i);
 }
 
+// =============================================================================
+// The halo exchange folded into the streaming loop's own kernels (sb_comm_halo_fold; several ranks, peer-mapped plane,
+// Sell-64 in the reference layout).  Body: cg_update_p_push | spmv_scs64_halo | alpha | r update | beta -- no halo_push_k,
+// no halo_pull_k.
+//
+// cg_update_p_push = cg_update_p<0> + the rank's push.  p is updated IN PLACE, so extra workgroups that re-formed
+// r + beta p_old for the boundary rows would race with the rows' owners: every workgroup sends the rows it has written
+// itself.  The plan (HaloFold) holds the send list -- (row, dest, slot), a row once per destination -- sorted by the
+// workgroup of the update's fixed grid that writes the row, and each workgroup's start offset in it: no search.  Behind its
+// part of the update (and a barrier) a workgroup reads its boundary rows back -- the very bits it stored -- and stores
+// them where halo_push_block does (relaxed system-scope 64-bit stores into stage[d] + par ext[d] + slot); the workgroups
+// that own entries count themselves done and the last one raises the flags (halo_push_block's protocol).  The stop branch
+// poisons the flags of a rank that has failed, as halo_push_k does; dropSeq is honoured.
+// Why two staging areas still suffice: a neighbour reaches the push of exchange seq + 1 only behind the p.Ap all-reduce
+// of body seq, which needs this rank's contribution, which this rank makes after its SpMV of body seq has finished reading
+// parity seq & 1 -- the argument given above for halo_push_k / halo_pull_k, with the SpMV in halo_pull_k's place.
+// =============================================================================
+struct HaloFold {
+  const uint32_t* row;     // send entries sorted by owning workgroup (packIdx order inside one): row in the vector's order,
+  const uint32_t* slot;    // position in the receiver's staging area,
+  const uint8_t* dest;     // destination index (HaloPush::stage / flag / ext)
+  const uint32_t* wgStart; // [grid + 1]: workgroup b owns entries [wgStart[b], wgStart[b + 1])
+  uint32_t nPushWgs;       // workgroups that own at least one entry (the last-workgroup count)
+};
+// the tail of both precisions' push: this thread's stores are out -> the workgroup counts itself -> the last one announces
+__device__ __forceinline__ void halo_fold_announce(const HaloPush& hp, uint32_t nPushWgs, unsigned long long seq)
+{
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned prev = atomicAdd(hp.done, 1u);
+    if (prev == nPushWgs - 1u) { // every owning workgroup has pushed: tell the receivers
+      *hp.done = 0u;
+      __threadfence_system();
+      if (seq != hp.dropSeq) // (test hook, as halo_push_block)
+        for (int d = 0; d < hp.ndest; d++)
+          __hip_atomic_store(hp.flag[d] + (unsigned)(seq & 1ull) * P2P_MAX + hp.rank, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+__global__ __launch_bounds__(1024) void cg_update_p_push(HaloPush hp, HaloFold hf, unsigned long long seq, uint32_t n,
+    const double* __restrict__ r, double* p, double* x, CgScalars* S, int which)
+{
+  const uint32_t n2     = n >> 1;
+  const uint32_t stride = gridDim.x * blockDim.x;
+  const double2* r2     = reinterpret_cast<const double2*>(r);
+  double2* p2           = reinterpret_cast<double2*>(p);
+  double2* x2           = reinterpret_cast<double2*>(x);
+  uint32_t i            = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool useX       = x != nullptr && which == 0;
+  // (the update is cg_update_p<0>'s, statement for statement: same loads, same expressions, same stores)
+  const uint32_t last = n2 ? n2 - 1u : 0u;
+  double2 a0 = { 0.0, 0.0 }, b0 = a0, x0 = a0, a1 = a0, b1 = a0, x1 = a0;
+  auto load = [&](uint32_t j, double2& a, double2& b, double2& xv) {
+    a = r2[j];
+    b = which == 0 ? p2[j] : a;
+    if (useX) xv = x2[j];
+  };
+  if (n2) load(min(i, last), a0, b0, x0), load(min(i + stride, last), a1, b1, x1);
+  const int stopped  = S->stop;
+  const double beta  = which == 0 ? S->beta : 0.0;
+  const bool owed    = useX && S->x_pending;
+  const double alpha = S->alpha;
+  if (stopped) { // the same decision on every rank (the loop test is all-reduced) -- unless this rank has failed
+    if (blockIdx.x == 0 && threadIdx.x == 0 && halo_rank_failed(hp)) halo_poison_flags(hp);
+    return;
+  }
+  auto finish = [&](uint32_t j, const double2& a, const double2& b, double2 xv) {
+    if (owed) {
+      xv.x = xv.x + alpha * b.x;
+      xv.y = xv.y + alpha * b.y;
+      x2[j] = xv;
+    }
+    double2 o;
+    o.x = a.x + beta * b.x;
+    o.y = a.y + beta * b.y;
+    p2[j] = o;
+  };
+  for (; i < n2; i += 2u * stride) {
+    const bool second = i + stride < n2;
+    finish(i, a0, b0, x0);
+    if (second) finish(i + stride, a1, b1, x1);
+    const uint32_t nx = i + 2u * stride;
+    if (nx < n2) load(nx, a0, b0, x0), load(min(nx + stride, last), a1, b1, x1);
+  }
+  if ((n & 1u) && blockIdx.x == 0 && threadIdx.x == 0) { // (the plan gives row n - 1 of an odd n to workgroup 0)
+    const double bb = which == 0 ? p[n - 1] : r[n - 1];
+    if (owed) x[n - 1] = x[n - 1] + alpha * bb;
+    p[n - 1] = r[n - 1] + beta * bb;
+  }
+  // the push: this workgroup's boundary rows (uniform per workgroup: most own none and are done here)
+  const uint32_t e0 = hf.wgStart[blockIdx.x], e1 = hf.wgStart[blockIdx.x + 1u];
+  if (e0 == e1) return;
+  __syncthreads(); // the rows were written by threads of THIS workgroup: visible behind the barrier
+  const unsigned par = (unsigned)(seq & 1ull);
+  for (uint32_t e = e0 + threadIdx.x; e < e1; e += blockDim.x) {
+    const uint32_t d = hf.dest[e];
+    const double v   = p[hf.row[e]];
+    __hip_atomic_store(hp.stage[d] + (size_t)par * hp.ext[d] + hf.slot[e], (unsigned long long)__double_as_longlong(v),
+        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  halo_fold_announce(hp, hf.nPushWgs, seq);
+}
+
+// spmv_scs64<UNROLL, true, NT> whose boundary blocks wait for the neighbours' pushes and read the staging area themselves.
+// A block is the kernel's unit -- four chunks, one aligned 256-group of rows, one level-1 value of p.Ap -- so the plan
+// (ScsHalo) splits BLOCKS: those that hold no column >= nr (interior) and those that hold one (halo).  The first
+// 8 perXcdI workgroups take the interior blocks in the XCD-aware order of spmv_scs64 (order[] lists them ascending, so
+// an XCD still gets a contiguous slab of rows); the workgroups behind them, dispatched last, take the halo blocks.  The
+// remap changes who computes a block and when, never where its results go: y rows and the level-1 slot are those of the
+// block's own index lb.  Interior blocks run spmv_scs64's loop as it stands.  Halo blocks: thread j < nsrc waits for
+// source j's flag (p2p_wait, bounded; a failure goes through halo_wait_failed as in halo_pull_k), a barrier, then the same
+// loop with x[col] taken from p for col < nr and from the staging area of this exchange's parity for col >= nr (plain
+// loads behind the acquire and the barrier, as halo_pull_k / the HALO pattern kernel read it).  The order of a row's
+// products and adds is untouched; padding is still 0.0 * x[0].  The tail of p is never read.
+struct ScsHalo {
+  const uint32_t* order;           // [nBlocks]: interior blocks ascending, then the halo blocks ascending
+  uint32_t nInterior;              // how many of them are interior
+  const unsigned long long* flags; // own flags, [2][P2P_MAX]
+  const unsigned long long* ext;   // own staging area of this exchange's parity: column c >= nr is slot c - nr
+  const int* src;                  // source ranks
+  int nsrc;
+  unsigned long long seq;
+  int* err;
+  int* stopw;             // the loop's stop flag, raised together with err
+  long long timeoutTicks; // HaloPush::timeoutTicks
+};
+// plan time (once per matrix): touches[b] = 1 where one of block b's chunks holds a column >= nr (device colInd, i.e. after
+// the sigma renumbering; externals keep their numbers >= nr).  One wave per chunk; touches[] starts zeroed.
+__global__ __launch_bounds__(256) void scs_halo_blocks_k(const uint32_t* __restrict__ chunkPtr, const uint32_t* __restrict__ chunkLens,
+    const uint32_t* __restrict__ colInd, uint32_t nr, uint32_t nChunks, uint32_t* touches)
+{
+  const uint32_t chunk = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (chunk >= nChunks) return;
+  const uint32_t* c  = colInd + chunkPtr[chunk] + lane;
+  const uint32_t len = chunkLens[chunk];
+  bool any           = false;
+  for (uint32_t j = 0; j < len; j++) any |= c[(size_t)j * 64] >= nr;
+  if (any) atomicOr(touches + (chunk >> 2), 1u);
+}
+// which block this workgroup computes: false = none.  halo: it is one of the halo blocks.
+__device__ __forceinline__ bool scs_halo_block(const ScsHalo& hh, uint32_t nBlocks, uint32_t perXcdI, uint32_t& lb, bool& halo)
+{
+  const uint32_t gridI = perXcdI * 8u;
+  halo = blockIdx.x >= gridI;
+  uint32_t q;
+  if (!halo) {
+    q = xcd_block(blockIdx.x, perXcdI);
+    if (q >= hh.nInterior) return false;
+  } else {
+    q = hh.nInterior + (blockIdx.x - gridI);
+    if (q >= nBlocks) return false;
+  }
+  lb = hh.order[q];
+  return true;
+}
+// the wait of a halo block (every thread of the workgroup calls it): true = every source's block has arrived
+__device__ __forceinline__ bool scs_halo_wait(const ScsHalo& hh)
+{
+  __shared__ int failed;
+  if (threadIdx.x == 0) failed = 0;
+  __syncthreads();
+  if ((int)threadIdx.x < hh.nsrc) {
+    const unsigned long long* f = hh.flags + (unsigned)(hh.seq & 1ull) * P2P_MAX + hh.src[threadIdx.x];
+    const int how               = p2p_wait(f, hh.seq, hh.timeoutTicks);
+    if (how) {
+      halo_wait_failed(how, hh.err, hh.stopw);
+      failed = 1;
+    }
+  }
+  __syncthreads();
+  return !failed;
+}
+template <int UNROLL, bool NT>
+__global__ __launch_bounds__(256) void spmv_scs64_halo(const uint32_t* __restrict__ chunkPtr,
+    const uint32_t* __restrict__ chunkLens, const uint32_t* __restrict__ colInd,
+    const double* __restrict__ val, const double* __restrict__ x, double* __restrict__ y,
+    uint32_t nr, uint32_t nChunks, uint32_t perXcdI, double* __restrict__ dotPartials,
+    const int* __restrict__ stop, ScsHalo hh)
+{
+  const int stopped      = *stop;
+  const uint32_t nBlocks = (nChunks + 3u) >> 2;
+  uint32_t lb            = 0;
+  bool halo              = false;
+  if (!scs_halo_block(hh, nBlocks, perXcdI, lb, halo) || stopped) return; // uniform per workgroup
+  const uint32_t chunk = __builtin_amdgcn_readfirstlane(lb * 4u + (threadIdx.x >> 6));
+  const uint32_t lane  = threadIdx.x & 63u;
+  const bool active    = chunk < nChunks; // wave-uniform; an idle wave of the last block still joins the barriers below
+  double acc = 0.0;
+  if (!halo) {
+    if (active) { // spmv_scs64's loop
+      const uint32_t cp  = chunkPtr[chunk];
+      const uint32_t len = chunkLens[chunk];
+      const double* v    = val + cp + lane;
+      const uint32_t* c  = colInd + cp + lane;
+      uint32_t j         = 0;
+      for (; j + UNROLL <= len; j += UNROLL) {
+        double vv[UNROLL];
+        uint32_t cc[UNROLL];
+        double xx[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) {
+          vv[u] = NT ? stream_load(v + (size_t)(j + u) * 64) : v[(size_t)(j + u) * 64];
+          cc[u] = NT ? stream_load(c + (size_t)(j + u) * 64) : c[(size_t)(j + u) * 64];
+        }
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) xx[u] = x[cc[u]];
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) acc = acc + vv[u] * xx[u];
+      }
+      for (; j < len; j++) {
+        double vv   = NT ? stream_load(v + (size_t)j * 64) : v[(size_t)j * 64];
+        uint32_t cc = NT ? stream_load(c + (size_t)j * 64) : c[(size_t)j * 64];
+        acc         = acc + vv * x[cc];
+      }
+    }
+  } else {
+    const bool arrived = scs_halo_wait(hh); // (uniform per workgroup; a failed wait has raised err and the stop flag)
+    if (active && arrived) {
+      const double* ext  = reinterpret_cast<const double*>(hh.ext);
+      auto xcol          = [&](uint32_t col) -> double { return *(col >= nr ? ext + (col - nr) : x + col); };
+      const uint32_t cp  = chunkPtr[chunk];
+      const uint32_t len = chunkLens[chunk];
+      const double* v    = val + cp + lane;
+      const uint32_t* c  = colInd + cp + lane;
+      uint32_t j         = 0;
+      for (; j + UNROLL <= len; j += UNROLL) {
+        double vv[UNROLL];
+        uint32_t cc[UNROLL];
+        double xx[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) {
+          vv[u] = NT ? stream_load(v + (size_t)(j + u) * 64) : v[(size_t)(j + u) * 64];
+          cc[u] = NT ? stream_load(c + (size_t)(j + u) * 64) : c[(size_t)(j + u) * 64];
+        }
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) xx[u] = xcol(cc[u]);
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) acc = acc + vv[u] * xx[u];
+      }
+      for (; j < len; j++) {
+        double vv   = NT ? stream_load(v + (size_t)j * 64) : v[(size_t)j * 64];
+        uint32_t cc = NT ? stream_load(c + (size_t)j * 64) : c[(size_t)j * 64];
+        acc         = acc + vv * xcol(cc);
+      }
+    }
+  }
+  // y and the block's level-1 value of p.Ap, as spmv_scs64<.., DOT = true, ..> forms them, at the block's OWN index
+  const uint32_t row = chunk * 64u + lane;
+  if (active && row < nr) y[row] = acc;
+  __shared__ double sq[4];
+  double t = (active && row < nr) ? x[row] * acc : 0.0;
+  t        = butterfly64(t);
+  if (lane == 0) sq[threadIdx.x >> 6] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) dotPartials[lb] = ((sq[0] + sq[1]) + sq[2]) + sq[3];
+}
+
 // CG scalar step as its own launch: the reference-shaped (unfused) path, and after the
 // all-reduce on several ranks (REDUCE = false: the sum is already in S->local).
 template <int MODE, bool REDUCE>

@@ -162,6 +162,115 @@ __global__ __launch_bounds__(256) void halo_pull_f32_k(const int* __restrict__ s
   for (int i = (int)threadIdx.x; i < rcount[j]; i += 256) dst[i] = __uint_as_float((unsigned)__builtin_nontemporal_load(src + i));
 }
 
+// ---- the halo exchange folded into the loop's own kernels (sb_comm_halo_fold; kernels.hip.h: cg_update_p_push,
+// spmv_scs64_halo) in float.  One halo plan and one HaloFold / ScsHalo plan serve both precisions: they hold indices only,
+// and a float travels in the low half of its 64-bit staging slot, as halo_push_f32_k sends it.
+// cg_update_p_f32<0> + the push of the rows each workgroup has written (the plan's owner map follows THIS kernel's
+// four-elements-per-thread grid)
+__global__ __launch_bounds__(1024) void cg_update_p_push_f32(HaloPush hp, HaloFold hf, unsigned long long seq, uint32_t n,
+    const float* __restrict__ r, float* p, float* x, CgScalarsF* S, int which)
+{
+  const bool useX   = x != nullptr && which == 0;
+  const int stopped = S->stop;
+  const float beta  = which == 0 ? (float)S->beta : 0.0f;
+  const bool owed   = useX && S->x_pending;
+  const float alpha = S->alpha;
+  if (stopped) { // the same decision on every rank -- unless this rank has failed
+    if (blockIdx.x == 0 && threadIdx.x == 0 && halo_rank_failed(hp)) halo_poison_flags(hp);
+    return;
+  }
+  const uint32_t stride = gridDim.x * blockDim.x * 4u;
+  for (uint32_t e = (blockIdx.x * blockDim.x + threadIdx.x) * 4u; e < n; e += stride) { // (cg_update_p_f32<0>'s update)
+    const float4 a = load4_f(r, e, n);
+    const float4 b = which == 0 ? load4_f(p, e, n) : a;
+    if (owed) {
+      float4 xv = load4_f(x, e, n);
+      xv.x = xv.x + alpha * b.x, xv.y = xv.y + alpha * b.y, xv.z = xv.z + alpha * b.z, xv.w = xv.w + alpha * b.w;
+      store4_f(x, e, n, xv);
+    }
+    float4 o;
+    o.x = a.x + beta * b.x, o.y = a.y + beta * b.y, o.z = a.z + beta * b.z, o.w = a.w + beta * b.w;
+    store4_f(p, e, n, o);
+  }
+  const uint32_t e0 = hf.wgStart[blockIdx.x], e1 = hf.wgStart[blockIdx.x + 1u];
+  if (e0 == e1) return; // (uniform per workgroup)
+  __syncthreads();      // the rows were written by threads of THIS workgroup: visible behind the barrier
+  const unsigned par = (unsigned)(seq & 1ull);
+  for (uint32_t e = e0 + threadIdx.x; e < e1; e += blockDim.x) {
+    const uint32_t d = hf.dest[e];
+    __hip_atomic_store(hp.stage[d] + (size_t)par * hp.ext[d] + hf.slot[e], (unsigned long long)__float_as_uint(p[hf.row[e]]),
+        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  halo_fold_announce(hp, hf.nPushWgs, seq);
+}
+
+// spmv_scs64_f32<true> with spmv_scs64_halo's block order, wait and gather (a halo column's float is the low half of its slot)
+__global__ __launch_bounds__(256) void spmv_scs64_halo_f32(const uint32_t* __restrict__ chunkPtr,
+    const uint32_t* __restrict__ chunkLens, const uint32_t* __restrict__ colInd, const float* __restrict__ val,
+    const float* __restrict__ x, float* __restrict__ y, uint32_t nr, uint32_t nChunks, uint32_t perXcdI,
+    float* __restrict__ dotL1, const int* __restrict__ stop, ScsHalo hh)
+{
+  constexpr int U        = 4;
+  const int stopped      = *stop;
+  const uint32_t nBlocks = (nChunks + 3u) >> 2;
+  uint32_t lb            = 0;
+  bool halo              = false;
+  if (!scs_halo_block(hh, nBlocks, perXcdI, lb, halo) || stopped) return; // uniform per workgroup
+  const uint32_t chunk = __builtin_amdgcn_readfirstlane(lb * 4u + (threadIdx.x >> 6));
+  const uint32_t lane  = threadIdx.x & 63u;
+  const bool active    = chunk < nChunks;
+  float acc = 0.0f;
+  if (!halo) {
+    if (active) { // spmv_scs64_f32's loop
+      const uint32_t cp  = chunkPtr[chunk];
+      const uint32_t len = chunkLens[chunk];
+      const float* v     = val + cp + lane;
+      const uint32_t* c  = colInd + cp + lane;
+      uint32_t j         = 0;
+      for (; j + U <= len; j += U) {
+        float vv[U], xx[U];
+        uint32_t cc[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) vv[u] = stream_load(v + (size_t)(j + u) * 64), cc[u] = stream_load(c + (size_t)(j + u) * 64);
+#pragma unroll
+        for (int u = 0; u < U; u++) xx[u] = x[cc[u]];
+#pragma unroll
+        for (int u = 0; u < U; u++) acc = acc + vv[u] * xx[u];
+      }
+      for (; j < len; j++) acc = acc + stream_load(v + (size_t)j * 64) * x[stream_load(c + (size_t)j * 64)];
+    }
+  } else {
+    const bool arrived = scs_halo_wait(hh);
+    if (active && arrived) {
+      auto xcol = [&](uint32_t col) -> float { return col >= nr ? __uint_as_float((unsigned)hh.ext[col - nr]) : x[col]; };
+      const uint32_t cp  = chunkPtr[chunk];
+      const uint32_t len = chunkLens[chunk];
+      const float* v     = val + cp + lane;
+      const uint32_t* c  = colInd + cp + lane;
+      uint32_t j         = 0;
+      for (; j + U <= len; j += U) {
+        float vv[U], xx[U];
+        uint32_t cc[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) vv[u] = stream_load(v + (size_t)(j + u) * 64), cc[u] = stream_load(c + (size_t)(j + u) * 64);
+#pragma unroll
+        for (int u = 0; u < U; u++) xx[u] = xcol(cc[u]);
+#pragma unroll
+        for (int u = 0; u < U; u++) acc = acc + vv[u] * xx[u];
+      }
+      for (; j < len; j++) acc = acc + stream_load(v + (size_t)j * 64) * xcol(stream_load(c + (size_t)j * 64));
+    }
+  }
+  const uint32_t row = chunk * 64u + lane;
+  if (active && row < nr) y[row] = acc;
+  __shared__ float sq[4];
+  float t = (active && row < nr) ? x[row] * acc : 0.0f;
+  t       = xor_sum_f<64>(t);
+  if (lane == 0) sq[threadIdx.x >> 6] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) dotL1[lb] = ((sq[0] + sq[1]) + sq[2]) + sq[3];
+}
+
 // host transport (its neighbour_exchange carries doubles): pack widening out[i] = (double)in[idx[i]], unpack narrowing into the
 // float tail -- both exact
 __global__ __launch_bounds__(256) void halo_pack_wide_f32_k(uint32_t n, const uint32_t* __restrict__ idx, const float* __restrict__ in,

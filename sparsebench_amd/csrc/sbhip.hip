@@ -293,6 +293,19 @@ struct sb_halo {
   int *dSrcRank = nullptr, *dRdispl = nullptr, *dRcount = nullptr, *err = nullptr;
   unsigned long long seq = 0;
   char p2pReason[256] = "not set up";
+  // the exchange folded into the streaming loop's kernels (sb_comm_halo_fold; kernels.hip.h: cg_update_p_push, spmv_scs64_halo).
+  // Built by the first folded solve (sbhip_comm.inc.h: halo_fold_send_plan / halo_fold_block_plan), freed by halo_p2p_release.
+  std::vector<uint32_t> hPackIdx, hSlot; // host copies of packIdx / slot / dest as the push kernels use them
+  std::vector<uint8_t> hDest;
+  struct FoldSend {                      // the send list sorted by owning workgroup of the p update's grid, per precision
+    uint32_t grid = 0, vb = 0;           // the grid it was built for
+    HaloFold fold = {};
+    uint32_t *row = nullptr, *slot = nullptr, *wgStart = nullptr;
+    uint8_t* dest = nullptr;
+  } foldSend[2];                         // [0] fp64 (two rows per thread and step), [1] fp32 (four)
+  const sb_matrix* foldMatrix = nullptr; // the matrix the block split below was made for
+  uint32_t foldChunks = 0, foldInterior = 0;
+  uint32_t* foldOrder = nullptr;         // device: interior 4-chunk blocks ascending, then the halo blocks (ScsHalo::order)
 };
 
 struct sb_cg {
@@ -315,6 +328,7 @@ struct sb_cg {
   int fusedWant     = 1;  // sb_cg_set_fused: the caller's level; `fused` is what runs (0 while the dot order is seq)
   int dotOrderWant  = -1; // sb_cg_set_dot_order: 0 tree / 1 seq, -1: the process default (sb_dot_order)
   int seqLatched    = -1; // the dot order of the solve that is running (set by sb_cg_start, cleared by sb_cg_finish)
+  int foldLatched   = -1; // the halo-fold plan of the solve that is running (halo_fold_plan; same life)
   CgScalars* S;
   double* partials;
   uint32_t nPartials;

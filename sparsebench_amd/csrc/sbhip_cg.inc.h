@@ -15,6 +15,7 @@ static int sp_cg_finish(sb_cg* s);
 static int sp_cg_history(const sb_cg* s, double* rr_out, int rr_cap, double* pAp_out, int pAp_cap, int* n_pAp);
 static void sp_cg_counters(const sb_cg* s, int out[5]);
 static double sp_cg_check_residual(const sb_cg* s);
+static const sb_matrix* sp_mirror_selected(const sb_matrix* m);
 
 // events that time kernels inside the loop: created without the system-scope fence a default event carries (SB_EVENT_FLAGS
 // overrides the creation flags; 0 = default events)
@@ -216,14 +217,39 @@ static bool fusep_plan(sb_cg* s)
   if (ok && multi_rank()) ok = s->halo ? halo_p2p_active(s->halo) : true;
   return ok;
 }
+// The halo exchange folded into the streaming loop's own kernels (sb_comm_halo_fold; kernels.hip.h: cg_update_p_push |
+// spmv_scs64_halo | alpha | r update | beta -- 5 launches, both precisions).  Taken when ALL hold, today's body otherwise:
+// the switch is on; several ranks with a halo plan whose peer-mapped path is active; the fused loop under the tree order;
+// Sell-C-sigma with C = 64 and the reference-layout kernel selected (spmv_scs64 / spmv_scs64_f32: not the row programs, not
+// the SP mirror).  CRS, generic C, the mirror kernels, seq, fused = 0 and the communicator's plane keep their bodies.
+// Inside a solve the answer is the one sb_cg_start / sp_cg_start latched, like the fused-p plan and the dot order: the two
+// bodies use the staging area differently (the folded one never fills the tail of p), so the pieces of one solve must not
+// mix them; a change of the switch takes effect with the next start.
+static bool halo_fold_plan(sb_cg* s)
+{
+  if (s->started && s->foldLatched >= 0) return s->foldLatched > 0;
+  if (!sb_comm_halo_fold_selected()) return false;
+  const sb_matrix* A = s->A;
+  if (!multi_rank() || !s->halo || !halo_p2p_active(s->halo) || !p2p_dots() || s->fused != 1 || cg_seq(s) || s->nr == 0) return false;
+  if (A->fmt != 1 || A->C != 64) return false;
+  return s->prec == 1 ? sp_mirror_selected(A) == nullptr : !spmv_uses_patterns(A);
+}
+int sb_cg_halo_fold(sb_cg* s)
+{
+  if (s->seqLatched < 0) apply_dot_order(s);
+  return halo_fold_plan(s) ? 1 : 0;
+}
+
 // kernel launches per loop body.  One rank: 5 (p update | SpMV | alpha | r update | beta); 0 = the reference's op list.
 // Several ranks add the halo kernels (peer-mapped: the push, 0 with the push inside the SpMV launch, + a pull where the
 // SpMV is not the pattern kernel; otherwise the pack kernel in front of the send / recv group) and, without the in-kernel
 // all-reduce, one more kernel per dot (local reduce | all-reduce | scalar step) -- the all-reduce / send-recv calls
-// themselves are counted by sb_cg_collectives_per_body.
+// themselves are counted by sb_cg_collectives_per_body.  With the exchange folded into the streaming loop's own kernels
+// (halo_fold_plan above): 5, both precisions.
 int sb_cg_launches_per_body(sb_cg* s)
 {
   if (s->seqLatched < 0) apply_dot_order(s); // (the process default may have changed since the last call)
+  if (halo_fold_plan(s)) return 5; // p update + push | SpMV + pull | alpha | r update | beta (both precisions)
   if (s->prec == 1) return sp_launches_per_body(s);
   int base = fusep_plan(s) ? 4 : s->fused ? 5 : 0;
   if (base >= 4 && fusealpha_plan(s, fusep_plan(s) ? 1 : pAp_is_level1(s), 1024u)) base -= 1; // (alpha step inside the r update)
@@ -596,6 +622,30 @@ static void loop_body(sb_cg* s, int k)
     phase_mark(s, PH_BETA);
     return;
   }
+  if (halo_fold_plan(s)) {
+    // p = r + beta p (:114; k = 1: p = r + 0.0 r, :109) with the owed x update (:127) AND the push of the boundary rows
+    // (:122, send side) | Ap = A p with its p.Ap values (:123-125), the halo blocks waiting for the neighbours themselves
+    // (:122, receive side) | alpha | r update | beta
+    sb_halo* h       = s->halo;
+    const int which  = k == 1;
+    const HaloFold& hf = halo_fold_send_plan(h, 0, gridV.x, vb);
+    const unsigned long long seq = ++h->seq;
+    hipLaunchKernelGGL(cg_update_p_push, gridV, blockV, 0, g.stream, h->push, hf, seq, n, (const double*)s->r, s->p,
+        which ? (double*)nullptr : s->x, s->S, which);
+    HIP_CHECK(hipGetLastError());
+    mark(s, R_WAXPBY);
+    phase_mark(s, PH_P_UPDATE);
+    uint32_t perI = 0, gridS = 0;
+    const ScsHalo hh = halo_fold_spmv_arg(h, s->A, seq, &s->S->stop, &perI, &gridS);
+    spmv_time_begin(s);
+    launch_spmv_scs64_halo(s->A, s->p, s->Ap, s->partials, stop, hh, perI, gridS);
+    spmv_time_end(s);
+    mark(s, R_SPMVM);
+    phase_mark(s, PH_SPMV);
+    alpha_and_r_update(s, 1, capV, vb, stop);
+    beta_step_or_owe(s, vb);
+    return;
+  }
   if (k == 1) {
     if (n) hipLaunchKernelGGL(cg_update_p<0>, gridV, blockV, 0, g.stream, n, s->r, s->p, (double*)nullptr, s->S, 1, 0u, (const double*)nullptr, (double*)nullptr); // p = r (:109)
     mark(s, R_WAXPBY);
@@ -695,6 +745,8 @@ void sb_cg_start(sb_cg* s, int itermax, double eps)
   s->seqLatched   = cg_seq(s) ? 1 : 0; // the dot order, decided once per solve (cg_seq) ...
   apply_dot_order(s);                  // ... and the op list it runs
   s->fusepLatched = fusep_plan(s) ? 1 : 0; // decided once per solve (fusep_plan)
+  s->foldLatched  = -1;
+  s->foldLatched  = halo_fold_plan(s) ? 1 : 0; // ... and so is the folded halo exchange (halo_fold_plan)
   if (s->halo && s->halo->p2p && s->halo->push.p2pErr != &s->S->p2p_error) {
     // the push kernels of THIS solve also look at its control block's failure flag (poisoning: kernels.hip.h).  Set per solve,
     // not at create: the plan is shared, and a second sb_cg on the same halo must not redirect a running loop's pushes to a
@@ -797,6 +849,7 @@ int sb_cg_finish(sb_cg* s)
   s->timing       = false;
   s->fusepLatched = -1; // the solve is over: the next sb_cg_start decides anew
   s->seqLatched   = -1;
+  s->foldLatched  = -1;
   apply_dot_order(s); // (a dot order or fused level asked for during the solve)
   return h.iters + 1; // the value of k when the reference's for loop exits (:107,:140)
 }

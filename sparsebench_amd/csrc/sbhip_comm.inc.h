@@ -243,6 +243,32 @@ void sb_comm_halo_push_inside(int on)
   g.pushInside = on != 0;
 }
 
+// Peer-mapped halo exchange on the STREAMING loop (Sell-64 in the reference layout: spmv_scs64 / spmv_scs64_f32), variant:
+// 1 = the push rides in the p update (cg_update_p_push: every workgroup sends the boundary rows it has just written) and the
+// pull in the SpMV (spmv_scs64_halo: the blocks that hold a halo column, dispatched last, wait for the neighbours' flags and
+// read the staging area) -- 5 launches per body instead of 7, and the interior blocks no longer wait for the slowest
+// neighbour; 0 (default; SB_HALO_FOLD=1 changes the default) = halo_push_k and halo_pull_k as launches of their own.
+// Bit-identical either way.  Its per-step time on ranks with a GPU each is unmeasured (as sb_comm_halo_push_inside's).
+// SB_HALO_FOLD=0|1 is read on first use -- before sb_init too; anything else ends the process.  Where a solve cannot fold
+// (sbhip_cg.inc.h: halo_fold_plan) it silently keeps today's body; sb_cg_halo_fold tells.  Collective, between solves.
+static int g_haloFold = -1; // -1: not read yet
+int sb_comm_halo_fold_selected(void)
+{
+  if (g_haloFold < 0) {
+    const char* e = getenv("SB_HALO_FOLD");
+    if (!e || !*e || strcmp(e, "0") == 0) g_haloFold = 0;
+    else if (strcmp(e, "1") == 0) g_haloFold = 1;
+    else SB_FATAL("SB_HALO_FOLD=%s: expected 0 or 1", e);
+  }
+  return g_haloFold;
+}
+void sb_comm_halo_fold(int on)
+{
+  need_init();
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  g_haloFold = on != 0;
+}
+
 // what the RCCL communicator itself reports: out = {ranks in the communicator, this rank's id in it, HIP device it is
 // bound to}; returns 1, or 0 when there is no RCCL communicator (one rank, host transport) or the library lacks the queries
 int sb_comm_rccl_info(int out[3])
@@ -410,6 +436,12 @@ static void halo_p2p_release(sb_halo* h)
   sb_free(h->slot), sb_free(h->dest), sb_free(h->done), sb_free(h->dSrcRank), sb_free(h->dRdispl), sb_free(h->dRcount);
   sb_free(h->err), sb_free(h->dPush);
   h->dPush = nullptr;
+  for (sb_halo::FoldSend& f : h->foldSend) { // the folded exchange's plans (halo_fold_send_plan / halo_fold_block_plan)
+    sb_free(f.row), sb_free(f.slot), sb_free(f.wgStart), sb_free(f.dest);
+    f = sb_halo::FoldSend();
+  }
+  sb_free(h->foldOrder);
+  h->foldOrder = nullptr, h->foldMatrix = nullptr, h->foldChunks = h->foldInterior = 0;
   h->stage = nullptr, h->slot = nullptr, h->dest = nullptr, h->done = nullptr, h->dSrcRank = nullptr;
   h->dRdispl = nullptr, h->dRcount = nullptr, h->err = nullptr, h->p2p = false;
 }
@@ -516,6 +548,7 @@ static void halo_p2p_setup(sb_halo* h)
     }
     h->slot = (uint32_t*)upload(slot.data(), slot.size() * sizeof(uint32_t));
     h->dest = (uint8_t*)upload(dest.data(), dest.size());
+    h->hSlot = slot, h->hDest = dest; // (the folded exchange sorts them by workgroup: halo_fold_send_plan)
     h->done = (unsigned int*)sb_malloc(sizeof(unsigned int));
     h->err  = (int*)sb_malloc(sizeof(int));
     HIP_CHECK(hipMemset(h->done, 0, sizeof(unsigned int)));
@@ -627,6 +660,7 @@ sb_halo* sb_halo_create(uint32_t nr, int outdegree, const int* destinations, con
     }
   }
   h->packIdx = (uint32_t*)upload(idx.data(), idx.size() * sizeof(uint32_t));
+  h->hPackIdx = idx;
   HIP_CHECK(hipMalloc(&h->sendBuf, ((size_t)totalSendCount + 1) * sizeof(double)));
   halo_p2p_setup(h);
   return h;
@@ -636,6 +670,83 @@ int sb_halo_p2p_enabled(const sb_halo* h) { return h && h->p2p ? 1 : 0; }
 // set up AND selected (sb_comm_data_plane)
 static inline bool halo_p2p_active(const sb_halo* h) { return h && h->p2p && g.p2pUse; }
 const char* sb_halo_p2p_reason(const sb_halo* h) { return h ? h->p2pReason : "no halo plan (one rank)"; }
+
+// ---- the folded exchange's plans (sb_comm_halo_fold; kernels.hip.h: HaloFold, ScsHalo) -----------------------------------------
+// The send list in the order the p update's workgroups own it.  prec 0: cg_update_p_push (thread t of workgroup b writes the
+// row pairs b vb + t, + grid vb, ...; row n - 1 of an odd n belongs to workgroup 0); prec 1: cg_update_p_push_f32 (row
+// quadruples).  Inside a workgroup the entries keep packIdx order; a row sent to two destinations appears twice.  Rebuilt
+// when the grid changes (it does not between the bodies of a solve).
+static const HaloFold& halo_fold_send_plan(sb_halo* h, int prec, uint32_t grid, uint32_t vb)
+{
+  sb_halo::FoldSend& f = h->foldSend[prec];
+  if (f.grid == grid && f.vb == vb) return f.fold;
+  HIP_CHECK(hipStreamSynchronize(g.stream)); // (a launch that still reads the old plan)
+  sb_free(f.row), sb_free(f.slot), sb_free(f.wgStart), sb_free(f.dest);
+  const uint32_t n = h->nr, per = prec ? 4u : 2u, N = (uint32_t)h->totalSend;
+  const uint64_t stride = (uint64_t)grid * vb;
+  auto owner = [&](uint32_t row) -> uint32_t {
+    if (!prec && (n & 1u) && row == n - 1u) return 0u;
+    return (uint32_t)(((uint64_t)(row / per) % stride) / vb);
+  };
+  std::vector<uint32_t> start((size_t)grid + 1, 0u), row(N ? N : 1), slot(N ? N : 1);
+  std::vector<uint8_t> dest(N ? N : 1);
+  for (uint32_t i = 0; i < N; i++) start[owner(h->hPackIdx[i]) + 1]++;
+  uint32_t nPushWgs = 0;
+  for (uint32_t b = 0; b < grid; b++) nPushWgs += start[b + 1] ? 1u : 0u, start[b + 1] += start[b];
+  std::vector<uint32_t> at(start.begin(), start.end() - 1);
+  for (uint32_t i = 0; i < N; i++) { // (stable: packIdx order inside a workgroup)
+    const uint32_t e = at[owner(h->hPackIdx[i])]++;
+    row[e] = h->hPackIdx[i], slot[e] = h->hSlot[i], dest[e] = h->hDest[i];
+  }
+  f.row     = (uint32_t*)upload(row.data(), row.size() * sizeof(uint32_t));
+  f.slot    = (uint32_t*)upload(slot.data(), slot.size() * sizeof(uint32_t));
+  f.dest    = (uint8_t*)upload(dest.data(), dest.size());
+  f.wgStart = (uint32_t*)upload(start.data(), start.size() * sizeof(uint32_t));
+  f.fold.row = f.row, f.fold.slot = f.slot, f.fold.dest = f.dest, f.fold.wgStart = f.wgStart, f.fold.nPushWgs = nPushWgs;
+  f.grid = grid, f.vb = vb;
+  return f.fold;
+}
+// The 4-chunk blocks of a Sell-64 matrix, those without a halo column first (ScsHalo::order); returns how many those are.
+static uint32_t halo_fold_block_plan(sb_halo* h, const sb_matrix* m)
+{
+  if (h->foldMatrix == m && h->foldChunks == m->nChunks && h->foldOrder) return h->foldInterior;
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  sb_free(h->foldOrder);
+  const uint32_t nBlocks = (m->nChunks + 3u) / 4u;
+  uint32_t* touches      = (uint32_t*)sb_malloc((size_t)nBlocks * sizeof(uint32_t));
+  HIP_CHECK(hipMemsetAsync(touches, 0, (size_t)nBlocks * sizeof(uint32_t), g.stream));
+  hipLaunchKernelGGL(scs_halo_blocks_k, dim3(nBlocks), dim3(256), 0, g.stream, (const uint32_t*)m->chunkPtr, (const uint32_t*)m->chunkLens,
+      (const uint32_t*)m->colInd, m->nr, m->nChunks, touches);
+  HIP_CHECK(hipGetLastError());
+  std::vector<uint32_t> t(nBlocks), order;
+  sb_d2h(t.data(), touches, (size_t)nBlocks * sizeof(uint32_t));
+  sb_free(touches);
+  order.reserve(nBlocks);
+  for (uint32_t b = 0; b < nBlocks; b++)
+    if (!t[b]) order.push_back(b);
+  h->foldInterior = (uint32_t)order.size();
+  for (uint32_t b = 0; b < nBlocks; b++)
+    if (t[b]) order.push_back(b);
+  h->foldOrder  = (uint32_t*)upload(order.data(), order.size() * sizeof(uint32_t));
+  h->foldMatrix = m, h->foldChunks = m->nChunks;
+  return h->foldInterior;
+}
+// the SpMV's view of exchange `seq` (kernel argument) and its grid: 8 perXcdI workgroups for the interior blocks + the halo blocks
+static ScsHalo halo_fold_spmv_arg(sb_halo* h, const sb_matrix* m, unsigned long long seq, int* stopw, uint32_t* perXcdI, uint32_t* grid)
+{
+  ScsHalo hh;
+  memset(&hh, 0, sizeof hh);
+  hh.nInterior = halo_fold_block_plan(h, m);
+  hh.order     = h->foldOrder;
+  hh.flags     = h->stage + 2 * (size_t)h->externalCount;
+  hh.ext       = h->stage + (seq & 1ull) * (size_t)h->externalCount;
+  hh.src = h->dSrcRank, hh.nsrc = h->indegree, hh.seq = seq, hh.err = h->err, hh.stopw = stopw;
+  hh.timeoutTicks = h->push.timeoutTicks;
+  const uint32_t nBlocks = (m->nChunks + 3u) / 4u;
+  *perXcdI = (hh.nInterior + 7u) / 8u;
+  *grid    = *perXcdI * 8u + (nBlocks - hh.nInterior);
+  return hh;
+}
 
 void sb_halo_free(sb_halo* h)
 {

@@ -80,6 +80,26 @@ static void launch_spmv(const sb_matrix* m, const double* x, double* y, double* 
   HIP_CHECK(hipGetLastError());
 }
 
+// the streaming Sell-64 kernel whose halo blocks wait for the neighbours' pushes themselves (sb_comm_halo_fold; the CG loop's
+// folded body only: always with the p.Ap level-1 values).  perXcdI / grid: halo_fold_spmv_arg (sbhip_comm.inc.h)
+static void launch_spmv_scs64_halo(const sb_matrix* m, const double* x, double* y, double* dotL1, const int* stop, const ScsHalo& hh,
+    uint32_t perXcdI, uint32_t grid)
+{
+  if (g_scs_nt < 0) {
+    const char* n = getenv("SB_SCS_NT");
+    g_scs_nt      = n ? atoi(n) : 1;
+    const char* xc = getenv("SB_SCS_XCD");
+    g_scs_xcd     = xc ? atoi(xc) : 1;
+  }
+  if (g_scs_nt)
+    SB_SPMV_LAUNCH((spmv_scs64_halo<4, true>), dim3(grid), dim3(256), 0, g.stream, m->chunkPtr, m->chunkLens, m->colInd, m->val, x, y,
+        m->nr, m->nChunks, perXcdI, dotL1, stop, hh);
+  else
+    SB_SPMV_LAUNCH((spmv_scs64_halo<4, false>), dim3(grid), dim3(256), 0, g.stream, m->chunkPtr, m->chunkLens, m->colInd, m->val, x, y,
+        m->nr, m->nChunks, perXcdI, dotL1, stop, hh);
+  HIP_CHECK(hipGetLastError());
+}
+
 // the level-6 form of the tiles (masked row programs, pack.hip.h: spmv_scs64_pat with MASKED)
 static void launch_pat(const sb_matrix* pm, bool skipPad, const double* x, double* y, double* dotPartials, const int* stop,
     const HaloWait* halo)

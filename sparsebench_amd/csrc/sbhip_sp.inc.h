@@ -382,8 +382,10 @@ float sb_ddot_f32(uint32_t n, const float* x, const float* y)
 //                         level 1) | beta (cg_scalar_p2p_f32_k) -- 7 launches on Sell-64, 8 with the dot pass of CRS / generic C;
 //   communicator's plane: halo pack (+ the unpack of a host transport) in front of the send / recv, and each dot as local
 //                         reduce (cg_local_f32_k) | all-reduce (sb_comm_reduction_f32) | apply (cg_apply_local_f32_k).
-// The halo push stays a launch of its own: SP has no SpMV that waits for the flags or forms p itself (no pattern kernels, no
-// spmv_prog_fusep), so sb_comm_halo_push_inside has nothing to ride on here.
+// SP has no SpMV that forms p itself on several ranks (no spmv_prog_fusep there), so sb_comm_halo_push_inside has nothing to ride
+// on here.  With sb_comm_halo_fold(1) the Sell-64 body on the peer-mapped plane is cg_update_p_push_f32 | spmv_scs64_halo_f32 |
+// alpha | r update | beta -- 5 launches: the push in the p update, the pull in the SpMV's halo blocks (sbhip_cg.inc.h:
+// halo_fold_plan; kernels_sp_comm.hip.h).
 sb_cg* sb_cg_create_f32(const sb_matrix* m, sb_halo* halo, const float* b_host, const float* xexact_host)
 {
   need_init();
@@ -534,6 +536,43 @@ static void sp_loop_body(sb_cg* s, int k)
     phase_mark(s, PH_BETA);
     return;
   }
+  if (halo_fold_plan(s)) {
+    // the halo exchange inside the loop's own kernels (sbhip_cg.inc.h: halo_fold_plan): p update + push | SpMV whose halo blocks
+    // wait and read the staging area (+ p.Ap level 1) | alpha | r update (+ r.r level 1) | beta -- 5 launches
+    sb_halo* h         = s->halo;
+    const int which    = k == 1;
+    const HaloFold& hf = halo_fold_send_plan(h, 1, gridV.x, vb);
+    const unsigned long long seq = ++h->seq;
+    hipLaunchKernelGGL(cg_update_p_push_f32, gridV, blockV, 0, g.stream, h->push, hf, seq, n, (const float*)s->rf, s->pf,
+        which ? (float*)nullptr : s->xf, s->SF, which);
+    HIP_CHECK(hipGetLastError());
+    mark(s, R_WAXPBY);
+    phase_mark(s, PH_P_UPDATE);
+    uint32_t perI = 0, gridS = 0;
+    const ScsHalo hh = halo_fold_spmv_arg(h, s->A, seq, &s->SF->stop, &perI, &gridS);
+    const sb_matrix* m = s->A;
+    spmv_time_begin(s);
+    SB_SPMV_LAUNCH(spmv_scs64_halo_f32, dim3(gridS), dim3(256), 0, g.stream, m->chunkPtr, m->chunkLens, m->colInd, m->valf,
+        (const float*)s->pf, s->Apf, m->nr, m->nChunks, perI, s->partialsF, stop, hh);
+    HIP_CHECK(hipGetLastError());
+    spmv_time_end(s);
+    mark(s, R_SPMVM);
+    phase_mark(s, PH_SPMV);
+    const uint32_t nG = (n + 255u) >> 8;
+    const dim3 gridR(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount, (nG + 15u) / 16u)));
+    sp_scalar<2>(s, s->partialsF, 1, 0);
+    mark(s, R_DDOT);
+    phase_mark(s, PH_ALPHA);
+    hipLaunchKernelGGL(cg_update_r_f32<0>, gridR, dim3(1024), 0, g.stream, n, (const float*)s->Apf, s->rf, s->SF, s->partials2F,
+        stop, 0u, (const float*)nullptr, (float*)nullptr, (float*)nullptr);
+    HIP_CHECK(hipGetLastError());
+    mark(s, R_WAXPBY);
+    phase_mark(s, PH_R_UPDATE);
+    sp_scalar<1>(s, s->partials2F, 1, 1);
+    mark(s, R_DDOT);
+    phase_mark(s, PH_BETA);
+    return;
+  }
   if (k == 1) { // p = r + 0.0 r (:109)
     if (n) hipLaunchKernelGGL(cg_update_p_f32<0>, gridV, blockV, 0, g.stream, n, s->rf, s->pf, (float*)nullptr, s->SF, 1, 0u,
         (const float*)nullptr, (float*)nullptr);
@@ -626,6 +665,8 @@ static void sp_cg_start(sb_cg* s, int itermax, double eps)
   s->seqLatched = cg_seq(s) ? 1 : 0;
   apply_dot_order(s);
   s->fusepLatched = sp_fusep_plan(s) ? 1 : 0; // decided once per solve (sp_fusep_plan)
+  s->foldLatched  = -1;
+  s->foldLatched  = halo_fold_plan(s) ? 1 : 0; // ... and so is the folded halo exchange (sbhip_cg.inc.h: halo_fold_plan)
   if (s->fusepLatched && !s->pf2) s->pf2 = (float*)sb_malloc((size_t)s->nc * sizeof(float));
   if (itermax + 2 > s->hist_cap) {
     sb_free(s->rrHistF), sb_free(s->pApHistF);
@@ -706,6 +747,7 @@ static int sp_cg_finish(sb_cg* s)
   s->timing       = false;
   s->fusepLatched = -1; // the solve is over: the next sp_cg_start decides anew
   s->seqLatched   = -1;
+  s->foldLatched  = -1;
   apply_dot_order(s);
   return h.iters + 1;
 }

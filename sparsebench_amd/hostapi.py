@@ -273,6 +273,10 @@ class CG:
         """1: the loop takes the p update inside the SpMV launch"""
         return self.L.sb_cg_fuse_p(self.ptr)
 
+    def halo_fold(self):
+        """1: the next solve sends its halo from the p update and receives it in the SpMV (sb_comm_halo_fold), 0: today's body"""
+        return self.L.sb_cg_halo_fold(self.ptr)
+
     def collectives_per_body(self):
         return self.L.sb_cg_collectives_per_body(self.ptr)
 
