@@ -240,6 +240,54 @@ __device__ __forceinline__ void spmv_epilogue(uint32_t chunk, uint32_t lane, dou
 // =============================================================================
 constexpr uint32_t SCS_SLACK = 16 * 64; // zeroed elements behind val / colInd
 
+// One lane's row of a chunk: UNROLL val / colInd loads in flight, then the gathers, then the products added left to right.
+// xcol(col) is the x value of a column: x[col], or the staging-area lookup of the halo blocks (spmv_scs64_halo).
+template <int UNROLL, bool NT, typename T, typename XCol>
+__device__ __forceinline__ T scs64_row_sum(const uint32_t* __restrict__ chunkPtr, const uint32_t* __restrict__ chunkLens,
+    const uint32_t* __restrict__ colInd, const T* __restrict__ val, uint32_t chunk, uint32_t lane, XCol xcol)
+{
+  T acc              = 0;
+  const uint32_t cp  = chunkPtr[chunk];
+  const uint32_t len = chunkLens[chunk];
+  const T* v         = val + cp + lane;
+  const uint32_t* c  = colInd + cp + lane;
+  uint32_t j         = 0;
+  for (; j + UNROLL <= len; j += UNROLL) {
+    T vv[UNROLL];
+    uint32_t cc[UNROLL];
+    T xx[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++) {
+      vv[u] = NT ? stream_load(v + (size_t)(j + u) * 64) : v[(size_t)(j + u) * 64];
+      cc[u] = NT ? stream_load(c + (size_t)(j + u) * 64) : c[(size_t)(j + u) * 64];
+    }
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++) xx[u] = xcol(cc[u]);
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++) acc = acc + vv[u] * xx[u];
+  }
+  for (; j < len; j++) {
+    T vv        = NT ? stream_load(v + (size_t)j * 64) : v[(size_t)j * 64];
+    uint32_t cc = NT ? stream_load(c + (size_t)j * 64) : c[(size_t)j * 64];
+    acc         = acc + vv * xcol(cc);
+  }
+  return acc;
+}
+// The LEVEL-1 value of x . y for a block's four chunks (a block IS an aligned 256-group of the output vector): the four
+// waves' level-0 partials (wave_sum: the precision's 64-lane butterfly) meet in LDS and are added ((q0 + q1) + q2) + q3 --
+// the scalar step then reads n/256 values instead of n/64 through its one CU (which was 1.9 of its 4.3 us:
+// profiles/r03_scalar_anatomy.txt).  t: the lane's x[row] * y[row], 0 where it holds no row.  Every thread of the workgroup
+// calls it.
+template <typename T, typename WaveSum>
+__device__ __forceinline__ void scs64_block_dot(T t, uint32_t lane, T* __restrict__ dotL1, uint32_t lb, WaveSum wave_sum)
+{
+  __shared__ T sq[4];
+  t = wave_sum(t);
+  if (lane == 0) sq[threadIdx.x >> 6] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) dotL1[lb] = ((sq[0] + sq[1]) + sq[2]) + sq[3];
+}
+
 template <int UNROLL, bool DOT, bool NT>
 __global__ __launch_bounds__(256) void spmv_scs64(const uint32_t* __restrict__ chunkPtr,
     const uint32_t* __restrict__ chunkLens, const uint32_t* __restrict__ colInd,
@@ -256,45 +304,10 @@ __global__ __launch_bounds__(256) void spmv_scs64(const uint32_t* __restrict__ c
   const bool active    = chunk < nChunks; // wave-uniform; with DOT an idle wave of the last block still joins the combine below
   if (!DOT && !active) return;
   double acc = 0.0;
-  if (active) {
-    const uint32_t cp  = chunkPtr[chunk];
-    const uint32_t len = chunkLens[chunk];
-    const double* v    = val + cp + lane;
-    const uint32_t* c  = colInd + cp + lane;
-    uint32_t j         = 0;
-    for (; j + UNROLL <= len; j += UNROLL) {
-      double vv[UNROLL];
-      uint32_t cc[UNROLL];
-      double xx[UNROLL];
-#pragma unroll
-      for (int u = 0; u < UNROLL; u++) {
-        vv[u] = NT ? stream_load(v + (size_t)(j + u) * 64) : v[(size_t)(j + u) * 64];
-        cc[u] = NT ? stream_load(c + (size_t)(j + u) * 64) : c[(size_t)(j + u) * 64];
-      }
-#pragma unroll
-      for (int u = 0; u < UNROLL; u++) xx[u] = x[cc[u]];
-#pragma unroll
-      for (int u = 0; u < UNROLL; u++) acc = acc + vv[u] * xx[u];
-    }
-    for (; j < len; j++) {
-      double vv   = NT ? stream_load(v + (size_t)j * 64) : v[(size_t)j * 64];
-      uint32_t cc = NT ? stream_load(c + (size_t)j * 64) : c[(size_t)j * 64];
-      acc         = acc + vv * x[cc];
-    }
-  }
-  // y, and with DOT the LEVEL-1 value of the block's four chunks (a block IS an aligned 256-group of the output vector):
-  // the four waves' level-0 partials meet in LDS and are added ((q0 + q1) + q2) + q3 -- the scalar step then reads
-  // n/256 doubles instead of n/64 through its one CU (which was 1.9 of its 4.3 us: profiles/r03_scalar_anatomy.txt)
+  if (active) acc = scs64_row_sum<UNROLL, NT>(chunkPtr, chunkLens, colInd, val, chunk, lane, [&](uint32_t col) { return x[col]; });
   const uint32_t row = chunk * 64u + lane;
   if (active && row < nr) y[row] = acc;
-  if (DOT) {
-    __shared__ double sq[4];
-    double t = (active && row < nr) ? x[row] * acc : 0.0;
-    t        = butterfly64(t);
-    if (lane == 0) sq[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) dotPartials[lb] = ((sq[0] + sq[1]) + sq[2]) + sq[3];
-  }
+  if (DOT) scs64_block_dot((active && row < nr) ? x[row] * acc : 0.0, lane, dotPartials, lb, butterfly64);
 }
 
 // Any C (the reference's fixtures use C = 1, 2, 4): one thread per padded row.
@@ -948,25 +961,40 @@ __device__ __forceinline__ void halo_wait_failed(int how, int* err, int* stopw)
   if (stopw) atomicExch(stopw, 1); // the loop must not go on iterating on a stale halo
 }
 
-// every thread of the workgroup calls this with the same `mine`; returns the same sum in every thread
-__device__ __forceinline__ double p2p_allreduce_sum(const P2PView* pv, double mine, unsigned long long seq,
-    double* sh /* >= P2P_MAX doubles of LDS */, int* err)
+// A value travels as the 64 bits of a slot (all-reduce slots, halo staging areas): a double as its bits, a float in the low half.
+__device__ __forceinline__ unsigned long long slot_bits(double v) { return (unsigned long long)__double_as_longlong(v); }
+__device__ __forceinline__ unsigned long long slot_bits(float v) { return (unsigned long long)__float_as_uint(v); }
+__device__ __forceinline__ void slot_value(unsigned long long b, double& v) { v = __longlong_as_double((long long)b); }
+__device__ __forceinline__ void slot_value(unsigned long long b, float& v) { v = __uint_as_float((unsigned)b); }
+
+// the exchange of an in-kernel all-reduce, either precision: thread t < P stores `mine` and then seq into rank t's buffer and
+// waits for rank t's pair in the own buffer; behind it sh[0 .. P) holds the ranks' values (0 where a wait failed: *err).
+// Every thread of the workgroup calls it with the same `mine`.
+template <typename T>
+__device__ __forceinline__ void p2p_exchange(const P2PView* pv, T mine, unsigned long long seq, T* sh, int* err)
 {
   const int t = (int)threadIdx.x, P = pv->size;
   const unsigned par = (unsigned)(seq & 1ull);
   if (t < P) {
     P2PSlot* dst = pv->peer[t] + par * P2P_MAX + pv->rank;
-    __hip_atomic_store(&dst->bits, (unsigned long long)__double_as_longlong(mine), __ATOMIC_RELAXED,
-        __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&dst->bits, slot_bits(mine), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(&dst->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    P2PSlot* src       = pv->peer[pv->rank] + par * P2P_MAX + t;
+    P2PSlot* src  = pv->peer[pv->rank] + par * P2P_MAX + t;
     const int how = p2p_wait(&src->seq, seq, pv->timeoutTicks);
-    sh[t] = !how ? __longlong_as_double((long long)__hip_atomic_load(&src->bits, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM))
-                 : 0.0;
+    T got         = 0;
+    if (!how) slot_value(__hip_atomic_load(&src->bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), got);
+    sh[t] = got;
     if (how) atomicCAS(err, 0, how); // 1: timed out, 2: the peer has failed (the first cause stays)
   }
   __syncthreads();
+}
+
+// every thread of the workgroup calls this with the same `mine`; returns the same sum in every thread
+__device__ __forceinline__ double p2p_allreduce_sum(const P2PView* pv, double mine, unsigned long long seq,
+    double* sh /* >= P2P_MAX doubles of LDS */, int* err)
+{
+  const int P = pv->size;
+  p2p_exchange(pv, mine, seq, sh, err);
   // pairwise tree in rank order: ((v0+v1)+(v2+v3))+... (an odd tail moves up unchanged)
   double v[P2P_MAX];
 #pragma unroll
@@ -1034,31 +1062,36 @@ __device__ __forceinline__ void p2p_poison_allreduce(const P2PView* pv)
     for (int par = 0; par < 2; par++)
       __hip_atomic_store(&(pv->peer[t] + par * P2P_MAX + pv->rank)->seq, P2P_POISON, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-template <bool FUSEP = false>
-__device__ __forceinline__ void halo_push_block(const HaloPush& hp, const double* __restrict__ x, unsigned long long seq,
-    uint32_t block, uint32_t nBlocks, const double* __restrict__ r = nullptr, double beta = 0.0)
+// the tail of every push: this thread's stores are out -> its workgroup counts itself done -> the last of the nWgs pushing
+// workgroups raises the sequence flag at every destination
+__device__ __forceinline__ void halo_announce(const HaloPush& hp, uint32_t nWgs, unsigned long long seq)
+{
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned prev = atomicAdd(hp.done, 1u);
+    if (prev == nWgs - 1u) { // every workgroup has pushed: tell the receivers
+      *hp.done = 0u;
+      __threadfence_system();
+      if (seq != hp.dropSeq) // (test hook: this rank "forgets" to announce exchange dropSeq; 0 = never)
+        for (int d = 0; d < hp.ndest; d++)
+          __hip_atomic_store(hp.flag[d] + (unsigned)(seq & 1ull) * P2P_MAX + hp.rank, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+template <bool FUSEP = false, typename T>
+__device__ __forceinline__ void halo_push_block(const HaloPush& hp, const T* __restrict__ x, unsigned long long seq,
+    uint32_t block, uint32_t nBlocks, const T* __restrict__ r = nullptr, T beta = 0)
 {
   const unsigned par    = (unsigned)(seq & 1ull);
   const uint32_t stride = nBlocks * blockDim.x;
   for (uint32_t i = block * blockDim.x + threadIdx.x; i < hp.n; i += stride) {
     const uint32_t d = hp.dest[i];
     const uint32_t j = hp.packIdx[i];
-    const double v   = FUSEP ? r[j] + beta * x[j] : x[j];
-    __hip_atomic_store(hp.stage[d] + (size_t)par * hp.ext[d] + hp.slot[i],
-        (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    const T v        = FUSEP ? r[j] + beta * x[j] : x[j];
+    __hip_atomic_store(hp.stage[d] + (size_t)par * hp.ext[d] + hp.slot[i], slot_bits(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
-  __threadfence_system(); // this thread's stores are out before its workgroup counts itself done
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned prev = atomicAdd(hp.done, 1u);
-    if (prev == nBlocks - 1u) { // every workgroup has pushed: tell the receivers
-      *hp.done = 0u;
-      __threadfence_system();
-      if (seq != hp.dropSeq) // (test hook: this rank "forgets" to announce exchange dropSeq; 0 = never)
-        for (int d = 0; d < hp.ndest; d++)
-          __hip_atomic_store(hp.flag[d] + par * P2P_MAX + hp.rank, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  halo_announce(hp, nBlocks, seq);
 }
 // this rank has failed: the neighbours that wait for its halo block (either parity) leave at once.  One thread.
 __device__ __forceinline__ void halo_poison_flags(const HaloPush& hp)
@@ -1088,12 +1121,13 @@ __global__ __launch_bounds__(256) void halo_push_fusep_k(HaloPush hp, const doub
   halo_push_block<true>(hp, pold, seq, blockIdx.x, gridDim.x, r, which ? 0.0 : S->beta);
 }
 
-__global__ __launch_bounds__(256) void halo_pull_k(const int* __restrict__ srcRank, const int* __restrict__ rdispl,
-    const int* __restrict__ rcount, const unsigned long long* stage, const unsigned long long* flags,
-    uint32_t ext, double* __restrict__ xTail, unsigned long long seq, int* err, int* stop, long long timeoutTicks)
+// halo_pull_k of either precision: workgroup j waits for source j's flag and copies its block into the tail of x
+template <typename T>
+__device__ __forceinline__ void halo_pull_block(const int* __restrict__ srcRank, const int* __restrict__ rdispl,
+    const int* __restrict__ rcount, const unsigned long long* stage, const unsigned long long* flags, uint32_t ext,
+    T* __restrict__ xTail, unsigned long long seq, int* err, int* stop, long long timeoutTicks)
 {
   __shared__ int ok;
-  if (stop && *stop) return;
   const unsigned par = (unsigned)(seq & 1ull);
   const int j        = (int)blockIdx.x;
   if (threadIdx.x == 0) {
@@ -1106,9 +1140,16 @@ __global__ __launch_bounds__(256) void halo_pull_k(const int* __restrict__ srcRa
   if (!ok) return;
   // plain loads: thread 0's system-scope acquire + the barrier order them after the sender's
   // stores (one atomic load per element would serialise into one ~2 us round trip each)
-  const double* src = reinterpret_cast<const double*>(stage + (size_t)par * ext + rdispl[j]);
-  double* dst       = xTail + rdispl[j];
-  for (int i = (int)threadIdx.x; i < rcount[j]; i += 256) dst[i] = __builtin_nontemporal_load(src + i);
+  const unsigned long long* src = stage + (size_t)par * ext + rdispl[j];
+  T* dst                        = xTail + rdispl[j];
+  for (int i = (int)threadIdx.x; i < rcount[j]; i += 256) slot_value(__builtin_nontemporal_load(src + i), dst[i]);
+}
+__global__ __launch_bounds__(256) void halo_pull_k(const int* __restrict__ srcRank, const int* __restrict__ rdispl,
+    const int* __restrict__ rcount, const unsigned long long* stage, const unsigned long long* flags,
+    uint32_t ext, double* __restrict__ xTail, unsigned long long seq, int* err, int* stop, long long timeoutTicks)
+{
+  if (stop && *stop) return;
+  halo_pull_block(srcRank, rdispl, rcount, stage, flags, ext, xTail, seq, err, stop, timeoutTicks);
 }
 
 // =============================================================================
@@ -1121,8 +1162,8 @@ __global__ __launch_bounds__(256) void halo_pull_k(const int* __restrict__ srcRa
 // itself.  The plan (HaloFold) holds the send list -- (row, dest, slot), a row once per destination -- sorted by the
 // workgroup of the update's fixed grid that writes the row, and each workgroup's start offset in it: no search.  Behind its
 // part of the update (and a barrier) a workgroup reads its boundary rows back -- the very bits it stored -- and stores
-// them where halo_push_block does (relaxed system-scope 64-bit stores into stage[d] + par ext[d] + slot); the workgroups
-// that own entries count themselves done and the last one raises the flags (halo_push_block's protocol).  The stop branch
+// them where halo_push_block does (relaxed system-scope 64-bit stores into stage[d] + par ext[d] + slot); the workgroups that own entries count themselves done and the last
+// one raises the flags (halo_announce).  The stop branch
 // poisons the flags of a rank that has failed, as halo_push_k does; dropSeq is honoured.
 // Why two staging areas still suffice: a neighbour reaches the push of exchange seq + 1 only behind the p.Ap all-reduce
 // of body seq, which needs this rank's contribution, which this rank makes after its SpMV of body seq has finished reading
@@ -1135,21 +1176,21 @@ struct HaloFold {
   const uint32_t* wgStart; // [grid + 1]: workgroup b owns entries [wgStart[b], wgStart[b + 1])
   uint32_t nPushWgs;       // workgroups that own at least one entry (the last-workgroup count)
 };
-// the tail of both precisions' push: this thread's stores are out -> the workgroup counts itself -> the last one announces
-__device__ __forceinline__ void halo_fold_announce(const HaloPush& hp, uint32_t nPushWgs, unsigned long long seq)
+// the push of cg_update_p_push, either precision: behind its part of the update the workgroup sends the rows it has written,
+// entries [e0, e1) of the plan (the kernel has looked them up: most workgroups own none and have returned).  nThreads: blockDim.x,
+// read by the kernel.
+template <typename T>
+__device__ __forceinline__ void halo_fold_push(const HaloPush& hp, const HaloFold& hf, unsigned long long seq, const T* p,
+    uint32_t e0, uint32_t e1, uint32_t nThreads)
 {
-  __threadfence_system();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned prev = atomicAdd(hp.done, 1u);
-    if (prev == nPushWgs - 1u) { // every owning workgroup has pushed: tell the receivers
-      *hp.done = 0u;
-      __threadfence_system();
-      if (seq != hp.dropSeq) // (test hook, as halo_push_block)
-        for (int d = 0; d < hp.ndest; d++)
-          __hip_atomic_store(hp.flag[d] + (unsigned)(seq & 1ull) * P2P_MAX + hp.rank, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+  __syncthreads(); // the rows were written by threads of THIS workgroup: visible behind the barrier
+  const unsigned par = (unsigned)(seq & 1ull);
+  for (uint32_t e = e0 + threadIdx.x; e < e1; e += nThreads) {
+    const uint32_t d = hf.dest[e];
+    const T v        = p[hf.row[e]];
+    __hip_atomic_store(hp.stage[d] + (size_t)par * hp.ext[d] + hf.slot[e], slot_bits(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+  halo_announce(hp, hf.nPushWgs, seq);
 }
 __global__ __launch_bounds__(1024) void cg_update_p_push(HaloPush hp, HaloFold hf, unsigned long long seq, uint32_t n,
     const double* __restrict__ r, double* p, double* x, CgScalars* S, int which)
@@ -1161,7 +1202,8 @@ __global__ __launch_bounds__(1024) void cg_update_p_push(HaloPush hp, HaloFold h
   double2* x2           = reinterpret_cast<double2*>(x);
   uint32_t i            = blockIdx.x * blockDim.x + threadIdx.x;
   const bool useX       = x != nullptr && which == 0;
-  // (the update is cg_update_p<0>'s, statement for statement: same loads, same expressions, same stores)
+  // The update is a copy of cg_update_p<0>'s and must agree with it statement for statement (one shared body would not
+  // leave cg_update_p<BETA>'s code as it is: DESIGN 4.6).
   const uint32_t last = n2 ? n2 - 1u : 0u;
   double2 a0 = { 0.0, 0.0 }, b0 = a0, x0 = a0, a1 = a0, b1 = a0, x1 = a0;
   auto load = [&](uint32_t j, double2& a, double2& b, double2& xv) {
@@ -1201,18 +1243,9 @@ __global__ __launch_bounds__(1024) void cg_update_p_push(HaloPush hp, HaloFold h
     if (owed) x[n - 1] = x[n - 1] + alpha * bb;
     p[n - 1] = r[n - 1] + beta * bb;
   }
-  // the push: this workgroup's boundary rows (uniform per workgroup: most own none and are done here)
   const uint32_t e0 = hf.wgStart[blockIdx.x], e1 = hf.wgStart[blockIdx.x + 1u];
-  if (e0 == e1) return;
-  __syncthreads(); // the rows were written by threads of THIS workgroup: visible behind the barrier
-  const unsigned par = (unsigned)(seq & 1ull);
-  for (uint32_t e = e0 + threadIdx.x; e < e1; e += blockDim.x) {
-    const uint32_t d = hf.dest[e];
-    const double v   = p[hf.row[e]];
-    __hip_atomic_store(hp.stage[d] + (size_t)par * hp.ext[d] + hf.slot[e], (unsigned long long)__double_as_longlong(v),
-        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  halo_fold_announce(hp, hf.nPushWgs, seq);
+  if (e0 == e1) return; // (uniform per workgroup)
+  halo_fold_push(hp, hf, seq, p, e0, e1, blockDim.x);
 }
 
 // spmv_scs64<UNROLL, true, NT> whose boundary blocks wait for the neighbours' pushes and read the staging area themselves.
@@ -1221,7 +1254,7 @@ __global__ __launch_bounds__(1024) void cg_update_p_push(HaloPush hp, HaloFold h
 // 8 perXcdI workgroups take the interior blocks in the XCD-aware order of spmv_scs64 (order[] lists them ascending, so
 // an XCD still gets a contiguous slab of rows); the workgroups behind them, dispatched last, take the halo blocks.  The
 // remap changes who computes a block and when, never where its results go: y rows and the level-1 slot are those of the
-// block's own index lb.  Interior blocks run spmv_scs64's loop as it stands.  Halo blocks: thread j < nsrc waits for
+// block's own index lb.  Interior blocks run spmv_scs64's row loop.  Halo blocks: thread j < nsrc waits for
 // source j's flag (p2p_wait, bounded; a failure goes through halo_wait_failed as in halo_pull_k), a barrier, then the same
 // loop with x[col] taken from p for col < nr and from the staging area of this exchange's parity for col >= nr (plain
 // loads behind the acquire and the barrier, as halo_pull_k / the HALO pattern kernel read it).  The order of a row's
@@ -1284,12 +1317,13 @@ __device__ __forceinline__ bool scs_halo_wait(const ScsHalo& hh)
   __syncthreads();
   return !failed;
 }
-template <int UNROLL, bool NT>
-__global__ __launch_bounds__(256) void spmv_scs64_halo(const uint32_t* __restrict__ chunkPtr,
-    const uint32_t* __restrict__ chunkLens, const uint32_t* __restrict__ colInd,
-    const double* __restrict__ val, const double* __restrict__ x, double* __restrict__ y,
-    uint32_t nr, uint32_t nChunks, uint32_t perXcdI, double* __restrict__ dotPartials,
-    const int* __restrict__ stop, ScsHalo hh)
+// both precisions' spmv_scs64_halo.  xcol(col): x[col] for col < nr, the staging area's value for col >= nr -- called by the
+// halo blocks only, behind the wait.
+template <int UNROLL, bool NT, typename T, typename XCol, typename WaveSum>
+__device__ __forceinline__ void scs64_halo_spmv(const uint32_t* __restrict__ chunkPtr, const uint32_t* __restrict__ chunkLens,
+    const uint32_t* __restrict__ colInd, const T* __restrict__ val, const T* __restrict__ x, T* __restrict__ y, uint32_t nr,
+    uint32_t nChunks, uint32_t perXcdI, T* __restrict__ dotL1, const int* __restrict__ stop, const ScsHalo& hh, XCol xcol,
+    WaveSum wave_sum)
 {
   const int stopped      = *stop;
   const uint32_t nBlocks = (nChunks + 3u) >> 2;
@@ -1299,74 +1333,28 @@ __global__ __launch_bounds__(256) void spmv_scs64_halo(const uint32_t* __restric
   const uint32_t chunk = __builtin_amdgcn_readfirstlane(lb * 4u + (threadIdx.x >> 6));
   const uint32_t lane  = threadIdx.x & 63u;
   const bool active    = chunk < nChunks; // wave-uniform; an idle wave of the last block still joins the barriers below
-  double acc = 0.0;
+  T acc = 0;
   if (!halo) {
-    if (active) { // spmv_scs64's loop
-      const uint32_t cp  = chunkPtr[chunk];
-      const uint32_t len = chunkLens[chunk];
-      const double* v    = val + cp + lane;
-      const uint32_t* c  = colInd + cp + lane;
-      uint32_t j         = 0;
-      for (; j + UNROLL <= len; j += UNROLL) {
-        double vv[UNROLL];
-        uint32_t cc[UNROLL];
-        double xx[UNROLL];
-#pragma unroll
-        for (int u = 0; u < UNROLL; u++) {
-          vv[u] = NT ? stream_load(v + (size_t)(j + u) * 64) : v[(size_t)(j + u) * 64];
-          cc[u] = NT ? stream_load(c + (size_t)(j + u) * 64) : c[(size_t)(j + u) * 64];
-        }
-#pragma unroll
-        for (int u = 0; u < UNROLL; u++) xx[u] = x[cc[u]];
-#pragma unroll
-        for (int u = 0; u < UNROLL; u++) acc = acc + vv[u] * xx[u];
-      }
-      for (; j < len; j++) {
-        double vv   = NT ? stream_load(v + (size_t)j * 64) : v[(size_t)j * 64];
-        uint32_t cc = NT ? stream_load(c + (size_t)j * 64) : c[(size_t)j * 64];
-        acc         = acc + vv * x[cc];
-      }
-    }
+    if (active) acc = scs64_row_sum<UNROLL, NT>(chunkPtr, chunkLens, colInd, val, chunk, lane, [&](uint32_t col) { return x[col]; });
   } else {
     const bool arrived = scs_halo_wait(hh); // (uniform per workgroup; a failed wait has raised err and the stop flag)
-    if (active && arrived) {
-      const double* ext  = reinterpret_cast<const double*>(hh.ext);
-      auto xcol          = [&](uint32_t col) -> double { return *(col >= nr ? ext + (col - nr) : x + col); };
-      const uint32_t cp  = chunkPtr[chunk];
-      const uint32_t len = chunkLens[chunk];
-      const double* v    = val + cp + lane;
-      const uint32_t* c  = colInd + cp + lane;
-      uint32_t j         = 0;
-      for (; j + UNROLL <= len; j += UNROLL) {
-        double vv[UNROLL];
-        uint32_t cc[UNROLL];
-        double xx[UNROLL];
-#pragma unroll
-        for (int u = 0; u < UNROLL; u++) {
-          vv[u] = NT ? stream_load(v + (size_t)(j + u) * 64) : v[(size_t)(j + u) * 64];
-          cc[u] = NT ? stream_load(c + (size_t)(j + u) * 64) : c[(size_t)(j + u) * 64];
-        }
-#pragma unroll
-        for (int u = 0; u < UNROLL; u++) xx[u] = xcol(cc[u]);
-#pragma unroll
-        for (int u = 0; u < UNROLL; u++) acc = acc + vv[u] * xx[u];
-      }
-      for (; j < len; j++) {
-        double vv   = NT ? stream_load(v + (size_t)j * 64) : v[(size_t)j * 64];
-        uint32_t cc = NT ? stream_load(c + (size_t)j * 64) : c[(size_t)j * 64];
-        acc         = acc + vv * xcol(cc);
-      }
-    }
+    if (active && arrived) acc = scs64_row_sum<UNROLL, NT>(chunkPtr, chunkLens, colInd, val, chunk, lane, xcol);
   }
-  // y and the block's level-1 value of p.Ap, as spmv_scs64<.., DOT = true, ..> forms them, at the block's OWN index
+  // y and the block's level-1 value of p.Ap at the block's OWN index
   const uint32_t row = chunk * 64u + lane;
   if (active && row < nr) y[row] = acc;
-  __shared__ double sq[4];
-  double t = (active && row < nr) ? x[row] * acc : 0.0;
-  t        = butterfly64(t);
-  if (lane == 0) sq[threadIdx.x >> 6] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) dotPartials[lb] = ((sq[0] + sq[1]) + sq[2]) + sq[3];
+  scs64_block_dot((active && row < nr) ? x[row] * acc : 0, lane, dotL1, lb, wave_sum);
+}
+template <int UNROLL, bool NT>
+__global__ __launch_bounds__(256) void spmv_scs64_halo(const uint32_t* __restrict__ chunkPtr,
+    const uint32_t* __restrict__ chunkLens, const uint32_t* __restrict__ colInd,
+    const double* __restrict__ val, const double* __restrict__ x, double* __restrict__ y,
+    uint32_t nr, uint32_t nChunks, uint32_t perXcdI, double* __restrict__ dotPartials,
+    const int* __restrict__ stop, ScsHalo hh)
+{
+  const double* ext = reinterpret_cast<const double*>(hh.ext);
+  scs64_halo_spmv<UNROLL, NT>(chunkPtr, chunkLens, colInd, val, x, y, nr, nChunks, perXcdI, dotPartials, stop, hh,
+      [&](uint32_t col) -> double { return *(col >= nr ? ext + (col - nr) : x + col); }, butterfly64);
 }
 
 // CG scalar step as its own launch: the reference-shaped (unfused) path, and after the
@@ -1433,19 +1421,21 @@ __global__ __launch_bounds__(256) void gather_k(uint32_t n, const uint32_t* __re
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = in[idx[i]];
 }
 
-__global__ __launch_bounds__(256) void max_abs_diff_partials(uint32_t n,
-    const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out)
-{ // solverCheckResidual, src/CGSolver.c:50-53 (max is order-independent)
-  __shared__ double w[4];
-  double m              = 0.0;
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const double d = fabs(a[i] - b[i]);
+// solverCheckResidual, src/CGSolver.c:48-53, either precision: the workgroup's max of |a - b| (order-independent; it skips
+// NaN as `>` does) over the elements i, i + stride, ... of its threads
+template <typename T>
+__device__ __forceinline__ void max_abs_diff_block(uint32_t i, uint32_t stride, uint32_t n, const T* __restrict__ a,
+    const T* __restrict__ b, T* __restrict__ out)
+{
+  __shared__ T w[4];
+  T m = 0;
+  for (; i < n; i += stride) {
+    const T d = fabs(a[i] - b[i]);
     if (d > m) m = d;
   }
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) {
-    const double o = __shfl_xor(m, off, 64);
+    const T o = __shfl_xor(m, off, 64);
     if (o > m) m = o;
   }
   if ((threadIdx.x & 63u) == 0) w[threadIdx.x >> 6] = m;
@@ -1455,6 +1445,11 @@ __global__ __launch_bounds__(256) void max_abs_diff_partials(uint32_t n,
       if (w[i] > m) m = w[i];
     out[blockIdx.x] = m;
   }
+}
+__global__ __launch_bounds__(256) void max_abs_diff_partials(uint32_t n,
+    const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out)
+{
+  max_abs_diff_block(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, n, a, b, out);
 }
 
 // debug: pure streaming read (16 B per lane), result folded so nothing is elided

@@ -98,7 +98,6 @@ __global__ __launch_bounds__(256) void spmv_scs64_f32(const uint32_t* __restrict
     const float* __restrict__ x, float* __restrict__ y, uint32_t nr, uint32_t nChunks, uint32_t blocksPerXcd,
     float* __restrict__ dotL1, const int* __restrict__ stop)
 {
-  constexpr int U      = 4;
   const int stopped    = stop ? *stop : 0;
   const uint32_t nBlocks = (nChunks + 3u) >> 2;
   const uint32_t lb      = blocksPerXcd ? xcd_block(blockIdx.x, blocksPerXcd) : blockIdx.x;
@@ -108,34 +107,10 @@ __global__ __launch_bounds__(256) void spmv_scs64_f32(const uint32_t* __restrict
   const bool active    = chunk < nChunks;
   if (!DOT && !active) return;
   float acc = 0.0f;
-  if (active) {
-    const uint32_t cp  = chunkPtr[chunk];
-    const uint32_t len = chunkLens[chunk];
-    const float* v     = val + cp + lane;
-    const uint32_t* c  = colInd + cp + lane;
-    uint32_t j         = 0;
-    for (; j + U <= len; j += U) {
-      float vv[U], xx[U];
-      uint32_t cc[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) vv[u] = stream_load(v + (size_t)(j + u) * 64), cc[u] = stream_load(c + (size_t)(j + u) * 64);
-#pragma unroll
-      for (int u = 0; u < U; u++) xx[u] = x[cc[u]];
-#pragma unroll
-      for (int u = 0; u < U; u++) acc = acc + vv[u] * xx[u];
-    }
-    for (; j < len; j++) acc = acc + stream_load(v + (size_t)j * 64) * x[stream_load(c + (size_t)j * 64)];
-  }
+  if (active) acc = scs64_row_sum<4, true>(chunkPtr, chunkLens, colInd, val, chunk, lane, [&](uint32_t col) { return x[col]; });
   const uint32_t row = chunk * 64u + lane;
   if (active && row < nr) y[row] = acc;
-  if (DOT) {
-    __shared__ float sq[4];
-    float t = (active && row < nr) ? x[row] * acc : 0.0f;
-    t       = xor_sum_f<64>(t);
-    if (lane == 0) sq[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) dotL1[lb] = ((sq[0] + sq[1]) + sq[2]) + sq[3];
-  }
+  if (DOT) scs64_block_dot((active && row < nr) ? x[row] * acc : 0.0f, lane, dotL1, lb, xor_sum_f<64>);
 }
 
 // any C: one thread per padded row
@@ -507,29 +482,10 @@ __global__ __launch_bounds__(256) void gather_f32_k(uint32_t n, const uint32_t* 
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = in[idx[i]];
 }
 
-// solverCheckResidual, src/CGSolver.c:48-53 in SP: diff = fabs(x - xexact) of a float difference; the max skips NaN as `>` does
 __global__ __launch_bounds__(256) void max_abs_diff_f32_k(uint32_t n, const float* __restrict__ a, const float* __restrict__ b,
     float* __restrict__ out)
 {
-  __shared__ float w[4];
-  float m               = 0.0f;
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float d = fabsf(a[i] - b[i]);
-    if (d > m) m = d;
-  }
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const float o = __shfl_xor(m, off, 64);
-    if (o > m) m = o;
-  }
-  if ((threadIdx.x & 63u) == 0) w[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < 4; i++)
-      if (w[i] > m) m = w[i];
-    out[blockIdx.x] = m;
-  }
+  max_abs_diff_block(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, n, a, b, out);
 }
 
 } // namespace sbk

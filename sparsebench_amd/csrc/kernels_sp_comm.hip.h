@@ -41,17 +41,7 @@ __host__ __device__ inline float rank_reduce_f32(float* v, int P, int op)
 __device__ __forceinline__ float p2p_allreduce_sum_f32(const P2PView* pv, float mine, unsigned long long seq, float* sh, int* err)
 {
   const int t = (int)threadIdx.x, P = pv->size;
-  const unsigned par = (unsigned)(seq & 1ull);
-  if (t < P) {
-    P2PSlot* dst = pv->peer[t] + par * P2P_MAX + pv->rank;
-    __hip_atomic_store(&dst->bits, (unsigned long long)__float_as_uint(mine), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(&dst->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    P2PSlot* src  = pv->peer[pv->rank] + par * P2P_MAX + t;
-    const int how = p2p_wait(&src->seq, seq, pv->timeoutTicks);
-    sh[t] = !how ? __uint_as_float((unsigned)__hip_atomic_load(&src->bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) : 0.0f;
-    if (how) atomicCAS(err, 0, how); // 1: timed out, 2: the peer has failed (the first cause stays)
-  }
-  __syncthreads();
+  p2p_exchange(pv, mine, seq, sh, err);
   if (t == 0) sh[0] = rank_reduce_f32(sh, P, 1);
   __syncthreads();
   const float r = sh[0];
@@ -120,25 +110,7 @@ __global__ __launch_bounds__(256) void halo_push_f32_k(HaloPush hp, const float*
     if (blockIdx.x == 0 && threadIdx.x == 0 && halo_rank_failed(hp)) halo_poison_flags(hp);
     return;
   }
-  const unsigned par    = (unsigned)(seq & 1ull);
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < hp.n; i += stride) {
-    const uint32_t d = hp.dest[i];
-    __hip_atomic_store(hp.stage[d] + (size_t)par * hp.ext[d] + hp.slot[i], (unsigned long long)__float_as_uint(x[hp.packIdx[i]]),
-        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  __threadfence_system(); // this thread's stores are out before its workgroup counts itself done
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned prev = atomicAdd(hp.done, 1u);
-    if (prev == gridDim.x - 1u) { // every workgroup has pushed: tell the receivers
-      *hp.done = 0u;
-      __threadfence_system();
-      if (seq != hp.dropSeq)
-        for (int d = 0; d < hp.ndest; d++)
-          __hip_atomic_store(hp.flag[d] + par * P2P_MAX + hp.rank, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  halo_push_block(hp, x, seq, blockIdx.x, gridDim.x);
 }
 
 // halo_pull_k into the float tail of p: one workgroup per source, bounded wait on its flag, then the block
@@ -146,20 +118,8 @@ __global__ __launch_bounds__(256) void halo_pull_f32_k(const int* __restrict__ s
     const int* __restrict__ rcount, const unsigned long long* stage, const unsigned long long* flags, uint32_t ext,
     float* __restrict__ xTail, unsigned long long seq, int* err, int* stop, long long timeoutTicks)
 {
-  __shared__ int ok;
   if (stop && *stop) return;
-  const unsigned par = (unsigned)(seq & 1ull);
-  const int j        = (int)blockIdx.x;
-  if (threadIdx.x == 0) {
-    const int how = p2p_wait(flags + par * P2P_MAX + srcRank[j], seq, timeoutTicks);
-    if (how) halo_wait_failed(how, err, stop);
-    ok = !how;
-  }
-  __syncthreads();
-  if (!ok) return;
-  const unsigned long long* src = stage + (size_t)par * ext + rdispl[j];
-  float* dst                    = xTail + rdispl[j];
-  for (int i = (int)threadIdx.x; i < rcount[j]; i += 256) dst[i] = __uint_as_float((unsigned)__builtin_nontemporal_load(src + i));
+  halo_pull_block(srcRank, rdispl, rcount, stage, flags, ext, xTail, seq, err, stop, timeoutTicks);
 }
 
 // ---- the halo exchange folded into the loop's own kernels (sb_comm_halo_fold; kernels.hip.h: cg_update_p_push,
@@ -179,8 +139,10 @@ __global__ __launch_bounds__(1024) void cg_update_p_push_f32(HaloPush hp, HaloFo
     if (blockIdx.x == 0 && threadIdx.x == 0 && halo_rank_failed(hp)) halo_poison_flags(hp);
     return;
   }
+  // A copy of cg_update_p_f32's sweep, which it must agree with (as one shared function it changes this kernel's code:
+  // DESIGN 4.6).
   const uint32_t stride = gridDim.x * blockDim.x * 4u;
-  for (uint32_t e = (blockIdx.x * blockDim.x + threadIdx.x) * 4u; e < n; e += stride) { // (cg_update_p_f32<0>'s update)
+  for (uint32_t e = (blockIdx.x * blockDim.x + threadIdx.x) * 4u; e < n; e += stride) {
     const float4 a = load4_f(r, e, n);
     const float4 b = which == 0 ? load4_f(p, e, n) : a;
     if (owed) {
@@ -194,14 +156,7 @@ __global__ __launch_bounds__(1024) void cg_update_p_push_f32(HaloPush hp, HaloFo
   }
   const uint32_t e0 = hf.wgStart[blockIdx.x], e1 = hf.wgStart[blockIdx.x + 1u];
   if (e0 == e1) return; // (uniform per workgroup)
-  __syncthreads();      // the rows were written by threads of THIS workgroup: visible behind the barrier
-  const unsigned par = (unsigned)(seq & 1ull);
-  for (uint32_t e = e0 + threadIdx.x; e < e1; e += blockDim.x) {
-    const uint32_t d = hf.dest[e];
-    __hip_atomic_store(hp.stage[d] + (size_t)par * hp.ext[d] + hf.slot[e], (unsigned long long)__float_as_uint(p[hf.row[e]]),
-        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  halo_fold_announce(hp, hf.nPushWgs, seq);
+  halo_fold_push(hp, hf, seq, p, e0, e1, blockDim.x);
 }
 
 // spmv_scs64_f32<true> with spmv_scs64_halo's block order, wait and gather (a halo column's float is the low half of its slot)
@@ -210,65 +165,9 @@ __global__ __launch_bounds__(256) void spmv_scs64_halo_f32(const uint32_t* __res
     const float* __restrict__ x, float* __restrict__ y, uint32_t nr, uint32_t nChunks, uint32_t perXcdI,
     float* __restrict__ dotL1, const int* __restrict__ stop, ScsHalo hh)
 {
-  constexpr int U        = 4;
-  const int stopped      = *stop;
-  const uint32_t nBlocks = (nChunks + 3u) >> 2;
-  uint32_t lb            = 0;
-  bool halo              = false;
-  if (!scs_halo_block(hh, nBlocks, perXcdI, lb, halo) || stopped) return; // uniform per workgroup
-  const uint32_t chunk = __builtin_amdgcn_readfirstlane(lb * 4u + (threadIdx.x >> 6));
-  const uint32_t lane  = threadIdx.x & 63u;
-  const bool active    = chunk < nChunks;
-  float acc = 0.0f;
-  if (!halo) {
-    if (active) { // spmv_scs64_f32's loop
-      const uint32_t cp  = chunkPtr[chunk];
-      const uint32_t len = chunkLens[chunk];
-      const float* v     = val + cp + lane;
-      const uint32_t* c  = colInd + cp + lane;
-      uint32_t j         = 0;
-      for (; j + U <= len; j += U) {
-        float vv[U], xx[U];
-        uint32_t cc[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) vv[u] = stream_load(v + (size_t)(j + u) * 64), cc[u] = stream_load(c + (size_t)(j + u) * 64);
-#pragma unroll
-        for (int u = 0; u < U; u++) xx[u] = x[cc[u]];
-#pragma unroll
-        for (int u = 0; u < U; u++) acc = acc + vv[u] * xx[u];
-      }
-      for (; j < len; j++) acc = acc + stream_load(v + (size_t)j * 64) * x[stream_load(c + (size_t)j * 64)];
-    }
-  } else {
-    const bool arrived = scs_halo_wait(hh);
-    if (active && arrived) {
-      auto xcol = [&](uint32_t col) -> float { return col >= nr ? __uint_as_float((unsigned)hh.ext[col - nr]) : x[col]; };
-      const uint32_t cp  = chunkPtr[chunk];
-      const uint32_t len = chunkLens[chunk];
-      const float* v     = val + cp + lane;
-      const uint32_t* c  = colInd + cp + lane;
-      uint32_t j         = 0;
-      for (; j + U <= len; j += U) {
-        float vv[U], xx[U];
-        uint32_t cc[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) vv[u] = stream_load(v + (size_t)(j + u) * 64), cc[u] = stream_load(c + (size_t)(j + u) * 64);
-#pragma unroll
-        for (int u = 0; u < U; u++) xx[u] = xcol(cc[u]);
-#pragma unroll
-        for (int u = 0; u < U; u++) acc = acc + vv[u] * xx[u];
-      }
-      for (; j < len; j++) acc = acc + stream_load(v + (size_t)j * 64) * xcol(stream_load(c + (size_t)j * 64));
-    }
-  }
-  const uint32_t row = chunk * 64u + lane;
-  if (active && row < nr) y[row] = acc;
-  __shared__ float sq[4];
-  float t = (active && row < nr) ? x[row] * acc : 0.0f;
-  t       = xor_sum_f<64>(t);
-  if (lane == 0) sq[threadIdx.x >> 6] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) dotL1[lb] = ((sq[0] + sq[1]) + sq[2]) + sq[3];
+  scs64_halo_spmv<4, true>(chunkPtr, chunkLens, colInd, val, x, y, nr, nChunks, perXcdI, dotL1, stop, hh,
+      [&](uint32_t col) -> float { return col >= nr ? __uint_as_float((unsigned)hh.ext[col - nr]) : x[col]; },
+      xor_sum_f<64>);
 }
 
 // host transport (its neighbour_exchange carries doubles): pack widening out[i] = (double)in[idx[i]], unpack narrowing into the

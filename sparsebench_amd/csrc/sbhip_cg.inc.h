@@ -138,14 +138,23 @@ void sb_cg_debug_ptrs(const sb_cg* s, unsigned long long out[8])
   for (int i = 0; i < 8; i++) out[i] = (unsigned long long)v[i];
 }
 
+// The push kernels of a solve also look at ITS failure flag (the control block's; poisoning: kernels.hip.h).  on: sb_cg_start /
+// sp_cg_start point the plan at `flag` -- per solve, not at create: the plan is shared, and a second sb_cg on the same halo must
+// not redirect a running loop's pushes to a control block that is not in use.  !on: the flag's owner is being freed;
+// a plan that still points at it lets go.
+static void halo_push_watch(sb_halo* h, const int* flag, bool on)
+{
+  if (!h || !h->p2p || (h->push.p2pErr == flag) == on) return;
+  h->push.p2pErr = on ? flag : nullptr;
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  HIP_CHECK(hipMemcpy(h->dPush, &h->push, sizeof h->push, hipMemcpyHostToDevice));
+}
+
 void sb_cg_free(sb_cg* s)
 {
   if (!s) return;
   HIP_CHECK(hipStreamSynchronize(g.stream));
-  if (s->halo && s->halo->p2p && s->halo->push.p2pErr == &s->S->p2p_error) {
-    s->halo->push.p2pErr = nullptr;
-    HIP_CHECK(hipMemcpy(s->halo->dPush, &s->halo->push, sizeof s->halo->push, hipMemcpyHostToDevice));
-  }
+  halo_push_watch(s->halo, &s->S->p2p_error, false);
   for (hipEvent_t e : s->ev) HIP_CHECK(hipEventDestroy(e));
   for (hipEvent_t e : s->spmvEv) HIP_CHECK(hipEventDestroy(e));
   for (hipEvent_t e : s->phEv) HIP_CHECK(hipEventDestroy(e));
@@ -747,14 +756,7 @@ void sb_cg_start(sb_cg* s, int itermax, double eps)
   s->fusepLatched = fusep_plan(s) ? 1 : 0; // decided once per solve (fusep_plan)
   s->foldLatched  = -1;
   s->foldLatched  = halo_fold_plan(s) ? 1 : 0; // ... and so is the folded halo exchange (halo_fold_plan)
-  if (s->halo && s->halo->p2p && s->halo->push.p2pErr != &s->S->p2p_error) {
-    // the push kernels of THIS solve also look at its control block's failure flag (poisoning: kernels.hip.h).  Set per solve,
-    // not at create: the plan is shared, and a second sb_cg on the same halo must not redirect a running loop's pushes to a
-    // control block that is not in use
-    s->halo->push.p2pErr = &s->S->p2p_error;
-    HIP_CHECK(hipStreamSynchronize(g.stream));
-    HIP_CHECK(hipMemcpy(s->halo->dPush, &s->halo->push, sizeof s->halo->push, hipMemcpyHostToDevice));
-  }
+  halo_push_watch(s->halo, &s->S->p2p_error, true);
   ensure_hist(s, itermax + 2);
   s->timing  = !s->fused; // the reference-shaped op list is the one that gets the region table
   s->evUsed  = 0;
@@ -822,6 +824,24 @@ static void cg_comm_failures(const sb_cg* s, int p2pError)
         g.p2pTimeoutTicks / P2P_TICKS_PER_MS);
 }
 
+// the end of a solve, both precisions (the stream is idle): the region table of a timed solve, and the latches are released
+static void cg_solve_over(sb_cg* s)
+{
+  if (s->timing) {
+    for (double& v : s->region_ms) v = 0.0;
+    for (size_t i = 1; i < s->evUsed; i++) {
+      float ms = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&ms, s->ev[i - 1], s->ev[i]));
+      if (s->evRegion[i] >= 0) s->region_ms[s->evRegion[i]] += ms;
+    }
+  }
+  s->timing       = false;
+  s->fusepLatched = -1; // the next sb_cg_start / sp_cg_start decides anew
+  s->seqLatched   = -1;
+  s->foldLatched  = -1;
+  apply_dot_order(s); // (a dot order or fused level asked for during the solve)
+}
+
 int sb_cg_finish(sb_cg* s)
 {
   need_init();
@@ -838,19 +858,7 @@ int sb_cg_finish(sb_cg* s)
   CgScalars h;
   HIP_CHECK(hipMemcpy(&h, s->S, sizeof h, hipMemcpyDeviceToHost));
   cg_comm_failures(s, h.p2p_error);
-  if (s->timing) {
-    for (double& v : s->region_ms) v = 0.0;
-    for (size_t i = 1; i < s->evUsed; i++) {
-      float ms = 0.f;
-      HIP_CHECK(hipEventElapsedTime(&ms, s->ev[i - 1], s->ev[i]));
-      if (s->evRegion[i] >= 0) s->region_ms[s->evRegion[i]] += ms;
-    }
-  }
-  s->timing       = false;
-  s->fusepLatched = -1; // the solve is over: the next sb_cg_start decides anew
-  s->seqLatched   = -1;
-  s->foldLatched  = -1;
-  apply_dot_order(s); // (a dot order or fused level asked for during the solve)
+  cg_solve_over(s);
   return h.iters + 1; // the value of k when the reference's for loop exits (:107,:140)
 }
 

@@ -428,10 +428,7 @@ sb_cg* sb_cg_create_f32(const sb_matrix* m, sb_halo* halo, const float* b_host, 
 
 static void sp_cg_free_arrays(sb_cg* s)
 {
-  if (s->halo && s->halo->p2p && s->halo->push.p2pErr == &s->XF->p2p_error) { // (sb_cg_free has synchronised the stream)
-    s->halo->push.p2pErr = nullptr;
-    HIP_CHECK(hipMemcpy(s->halo->dPush, &s->halo->push, sizeof s->halo->push, hipMemcpyHostToDevice));
-  }
+  halo_push_watch(s->halo, &s->XF->p2p_error, false);
   sb_free(s->XF);
   sb_free(s->rf), sb_free(s->pf), sb_free(s->pf2), sb_free(s->Apf), sb_free(s->xf), sb_free(s->bf), sb_free(s->xexactf);
   sb_free(s->SF), sb_free(s->partialsF), sb_free(s->partials2F), sb_free(s->rrHistF), sb_free(s->pApHistF);
@@ -506,6 +503,25 @@ static void sp_flush_beta(sb_cg* s)
   s->betaFold = 0;
 }
 
+// several ranks: the all-reduced alpha step | r update (+ the level-1 values of r.r) | the all-reduced beta step / loop test
+// (x += alpha p stays owed)
+static void sp_alpha_r_beta(sb_cg* s, dim3 gridR)
+{
+  const uint32_t n = s->nr;
+  const int* stop  = &s->SF->stop;
+  sp_scalar<2>(s, s->partialsF, 1, 0);
+  mark(s, R_DDOT);
+  phase_mark(s, PH_ALPHA);
+  hipLaunchKernelGGL(cg_update_r_f32<0>, gridR, dim3(1024), 0, g.stream, n, (const float*)s->Apf, s->rf, s->SF, s->partials2F,
+      stop, 0u, (const float*)nullptr, (float*)nullptr, (float*)nullptr);
+  HIP_CHECK(hipGetLastError());
+  mark(s, R_WAXPBY);
+  phase_mark(s, PH_R_UPDATE);
+  sp_scalar<1>(s, s->partials2F, 1, 1);
+  mark(s, R_DDOT);
+  phase_mark(s, PH_BETA);
+}
+
 static void sp_loop_body(sb_cg* s, int k)
 {
   const uint32_t n = s->nr;
@@ -560,17 +576,7 @@ static void sp_loop_body(sb_cg* s, int k)
     phase_mark(s, PH_SPMV);
     const uint32_t nG = (n + 255u) >> 8;
     const dim3 gridR(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount, (nG + 15u) / 16u)));
-    sp_scalar<2>(s, s->partialsF, 1, 0);
-    mark(s, R_DDOT);
-    phase_mark(s, PH_ALPHA);
-    hipLaunchKernelGGL(cg_update_r_f32<0>, gridR, dim3(1024), 0, g.stream, n, (const float*)s->Apf, s->rf, s->SF, s->partials2F,
-        stop, 0u, (const float*)nullptr, (float*)nullptr, (float*)nullptr);
-    HIP_CHECK(hipGetLastError());
-    mark(s, R_WAXPBY);
-    phase_mark(s, PH_R_UPDATE);
-    sp_scalar<1>(s, s->partials2F, 1, 1);
-    mark(s, R_DDOT);
-    phase_mark(s, PH_BETA);
+    sp_alpha_r_beta(s, gridR);
     return;
   }
   if (k == 1) { // p = r + 0.0 r (:109)
@@ -620,17 +626,7 @@ static void sp_loop_body(sb_cg* s, int k)
     const uint32_t nG = (n + 255u) >> 8;
     const dim3 gridR(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount, (nG + 15u) / 16u)));
     if (multi_rank()) { // the all-reduced alpha step, r update, the all-reduced beta step / loop test (x += alpha p stays owed)
-      sp_scalar<2>(s, s->partialsF, 1, 0);
-      mark(s, R_DDOT);
-      phase_mark(s, PH_ALPHA);
-      hipLaunchKernelGGL(cg_update_r_f32<0>, gridR, dim3(1024), 0, g.stream, n, (const float*)s->Apf, s->rf, s->SF, s->partials2F,
-          stop, 0u, (const float*)nullptr, (float*)nullptr, (float*)nullptr);
-      HIP_CHECK(hipGetLastError());
-      mark(s, R_WAXPBY);
-      phase_mark(s, PH_R_UPDATE);
-      sp_scalar<1>(s, s->partials2F, 1, 1);
-      mark(s, R_DDOT);
-      phase_mark(s, PH_BETA);
+      sp_alpha_r_beta(s, gridR);
       return;
     }
     hipLaunchKernelGGL(cg_update_r_f32<1>, gridR, dim3(1024), 0, g.stream, n, (const float*)s->Apf, s->rf, s->SF, s->partials2F,
@@ -682,11 +678,7 @@ static void sp_cg_start(sb_cg* s, int itermax, double eps)
   HIP_CHECK(hipStreamSynchronize(g.stream));
   HIP_CHECK(hipMemcpy(s->SF, &h, sizeof h, hipMemcpyHostToDevice));
   HIP_CHECK(hipMemset(s->XF, 0, sizeof(CgCommF)));
-  if (s->halo && s->halo->p2p && s->halo->push.p2pErr != &s->XF->p2p_error) {
-    // the push kernels of THIS solve look at its failure flag (per solve: the plan may be shared, sb_cg_start)
-    s->halo->push.p2pErr = &s->XF->p2p_error;
-    HIP_CHECK(hipMemcpy(s->halo->dPush, &s->halo->push, sizeof s->halo->push, hipMemcpyHostToDevice));
-  }
+  halo_push_watch(s->halo, &s->XF->p2p_error, true);
   HIP_CHECK(hipMemsetAsync(s->xf, 0, (size_t)n * sizeof(float), g.stream)); // x0 = 0 (:28)
   HIP_CHECK(hipMemsetAsync(s->pf, 0, (size_t)s->nc * sizeof(float), g.stream));
   if (s->pf2) HIP_CHECK(hipMemsetAsync(s->pf2, 0, (size_t)s->nc * sizeof(float), g.stream));
@@ -736,19 +728,7 @@ static int sp_cg_finish(sb_cg* s)
   CgCommF x;
   HIP_CHECK(hipMemcpy(&x, s->XF, sizeof x, hipMemcpyDeviceToHost));
   cg_comm_failures(s, x.p2p_error);
-  if (s->timing) {
-    for (double& v : s->region_ms) v = 0.0;
-    for (size_t i = 1; i < s->evUsed; i++) {
-      float ms = 0.f;
-      HIP_CHECK(hipEventElapsedTime(&ms, s->ev[i - 1], s->ev[i]));
-      if (s->evRegion[i] >= 0) s->region_ms[s->evRegion[i]] += ms;
-    }
-  }
-  s->timing       = false;
-  s->fusepLatched = -1; // the solve is over: the next sp_cg_start decides anew
-  s->seqLatched   = -1;
-  s->foldLatched  = -1;
-  apply_dot_order(s);
+  cg_solve_over(s);
   return h.iters + 1;
 }
 
