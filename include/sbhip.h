@@ -32,6 +32,7 @@ extern "C" {
 typedef struct sb_matrix sb_matrix; /* device-resident sparse matrix (CRS or SCS) */
 typedef struct sb_halo sb_halo;     /* device-resident halo plan of this rank     */
 typedef struct sb_cg sb_cg;         /* CG solver state (vectors + scalars in HBM) */
+typedef struct sb_gmres sb_gmres;   /* restarted GMRES(m) state (Krylov basis + scalars in HBM) */
 
 /* ---- context ------------------------------------------------------------- */
 /* replaces: commInit's process setup, src/comm.c:863-878 (device instead of rank) */
@@ -430,6 +431,48 @@ int sb_cg_phase_ms(sb_cg* s, double ms_out[8], int count_out[8]);
 /* device control block: out = {stop, stop_next, iters, n_rr, n_pAp} (proof that the
  * timed iterations really ran) */
 void sb_cg_counters(const sb_cg* s, int out[5]);
+
+/* ---- restarted GMRES(m) (the solver the reference's driver names and leaves empty: src/main.c:31,217-222) ------ */
+/* For matrices that are not symmetric positive definite.  Double precision, ONE rank; a single-precision matrix, several
+ * ranks or restart < 1 are fatal errors with file:line.  The numerical contract is DESIGN 4.8: x0 = 0, b / xexact as
+ * sb_cg_create takes them, classical Gram-Schmidt with one reorthogonalisation (CGS2), every dot the tree order of sb_ddot
+ * over the device's row order, Givens rotations, the iteration counter and loop test of solveCG (src/CGSolver.c:105-107,140:
+ * k starts at 1, the loop runs while k < itermax && normr > eps on the residual ESTIMATE, k is returned).  The loop is
+ * device-resident like CG's: a control block in HBM, every kernel returns at once when its stop flag is set.
+ * b_host / xexact_host: nr doubles in original row order (xexact may be NULL); halo: NULL (one rank). */
+sb_gmres* sb_gmres_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int restart);
+void sb_gmres_free(sb_gmres* s);
+/* 1 (default): the fused kernels (multi-dot, multi-update); 0: the op list -- sb_spmv_native, one tree dot per h entry, one
+ * waxpby-shaped launch per projection (w = 1.0*w + (-h)*V[i] is bit-identical to w - h*V[i]), a divide-by-scalar.  Same bits
+ * in both.  Not between sb_gmres_start and sb_gmres_finish. */
+void sb_gmres_set_fused(sb_gmres* s, int fused);
+int sb_gmres_restart(const sb_gmres* s);
+/* launches of the Arnoldi step at cycle position j (0-based): 7, + 1 at j = 0 (the cycle's first basis vector), + 5 at
+ * j = restart - 1 (the cycle close); 0 for the op list */
+int sb_gmres_launches_per_step(sb_gmres* s, int j);
+int sb_gmres_solve(sb_gmres* s, int itermax, double eps); /* blocking; returns k */
+/* The same in three steps: sb_gmres_start x0 = 0, r = b - A x, r.r, the loop test for k = 1 (enqueues only);
+ * sb_gmres_run_steps enqueues the next `steps` Arnoldi steps (with the cycle closes between them), never touches the host,
+ * steps past the loop's exit are no-ops; sb_gmres_finish waits, closes the cycle the exit left open (x takes its columns,
+ * r.r of the final x is recorded) and returns k. */
+void sb_gmres_start(sb_gmres* s, int itermax, double eps);
+void sb_gmres_run_steps(sb_gmres* s, int steps);
+int sb_gmres_finish(sb_gmres* s);
+/* res_out[k]: the residual estimate after the step taken at counter k (res_out[0]: the initial norm); rr_out: the explicit
+ * r.r of the prologue and of every cycle close, the last one included.  Returns the number of estimates. */
+int sb_gmres_history(const sb_gmres* s, double* res_out, int res_cap, double* rr_out, int rr_cap, int* n_rr);
+void sb_gmres_solution(const sb_gmres* s, double* x_host); /* original row order */
+double sb_gmres_check_residual(const sb_gmres* s);         /* max|x - xexact| */
+double sb_gmres_loop_ms(const sb_gmres* s); /* GPU milliseconds between the end of sb_gmres_start and sb_gmres_finish */
+void sb_gmres_counters(const sb_gmres* s, int out[5]); /* {stop, steps run, cycles closed, n_res, n_rr} */
+/* the two vector kernels on their own, for parity tests and for callers that orthogonalise blocks themselves:
+ * V = nvec vectors of n doubles, vector i at V + i*ldv (ldv >= n, a multiple of 2; V and w 16-byte aligned).
+ * sb_multidot: h[i] = tree dot of V[i] and w, all from one read of w.  sb_multiaxpy_sub: w[e] = (..(w[e] - h[0]*V[0][e]) ..
+ * - h[nvec-1]*V[nvec-1][e]), ascending i, every product rounded before its subtraction.  Stream-ordered. */
+void sb_multidot(uint32_t n, int nvec, const double* V, size_t ldv, const double* w, double* h_dev);
+void sb_multiaxpy_sub(uint32_t n, int nvec, const double* V, size_t ldv, const double* h_dev, double* w);
+/* test entry: sqrt_dev[e] = sqrt(a[e]), div_dev[e] = a[e] / b[e] as the scalar steps compute them (IEEE correctly rounded) */
+void sb_debug_sqrt_div(uint32_t n, const double* a_dev, const double* b_dev, double* sqrt_dev, double* div_dev);
 
 /* debug/measurement: raw streaming-read rate of the device in GB/s (DESIGN.md uses it
  * as the measured ceiling next to the 8 TB/s spec) */

@@ -249,11 +249,18 @@ void sbh_convert_scs(SCSMatrix* m, GMatrix* im); /* honours m->C, m->sigma set b
 void sbh_spmv(void* dev_matrix, CG_UINT nr, CG_UINT nc, const CG_FLOAT* x, CG_FLOAT* y);
 int sbh_solve_cg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
                  const CG_UINT* rowNnz);
+/* restarted GMRES(restart) on the same matrix (sb_gmres_*, sbhip.h): prints what solveCG prints; double precision, one rank */
+int sbh_solve_gmres(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
+                    const CG_UINT* rowNnz, int restart);
 
 /* ---- the hot path: src/solver.h:11-25, src/matrix.h:57 -------------------------------- */
 #if defined(CRS) || defined(SCS)
 void convertMatrix(Matrix* m, GMatrix* im);
 int solveCG(Comm* comm, Parameter* param, Matrix* m);
+/* the solver the reference's driver names and leaves empty (src/main.c:31,217-222): restarted GMRES(restart) for matrices
+ * that are not symmetric positive definite; returns k as solveCG does.  The single-precision libraries export it too and
+ * end the process with "GMRES: double precision only". */
+int solveGMRES(Comm* comm, Parameter* param, Matrix* m, int restart);
 /* x (nc entries) and y (nr entries) may be device or host pointers; host pointers are
  * staged through HBM (correct, slow: use sb_malloc'ed vectors on the hot path) */
 void spMVM(Matrix* m, const CG_FLOAT* restrict x, CG_FLOAT* restrict y);

@@ -41,6 +41,9 @@ SYMBOLS = [
     "sb_cg_solution_f32", "sb_comm_reduction_f32", "sb_rank_reduce_f32", "sb_halo_exchange_f32",
     "sb_set_sp_mirror", "sb_sp_mirror", "sb_matrix_all_row_programs",
     "sb_matrix_place", "sb_matrix_place_at", "sb_matrix_place_home", "sb_placement_arena_bytes", "sb_placement_probe", "sb_matrix_place_fresh", "sb_matrix_place_commit", "sb_matrix_placement", "sb_matrix_placement_report", "sb_matrix_debug_ptrs", "sb_cg_debug_ptrs",
+    "sb_gmres_create", "sb_gmres_free", "sb_gmres_set_fused", "sb_gmres_restart", "sb_gmres_launches_per_step", "sb_gmres_solve",
+    "sb_gmres_start", "sb_gmres_run_steps", "sb_gmres_finish", "sb_gmres_history", "sb_gmres_solution", "sb_gmres_check_residual",
+    "sb_gmres_loop_ms", "sb_gmres_counters", "sb_multidot", "sb_multiaxpy_sub", "sb_debug_sqrt_div",
 ]
 
 _lib = None
@@ -205,6 +208,24 @@ def load():
         "sb_set_sp_mirror": (None, [C.c_int]),
         "sb_sp_mirror": (C.c_int, []),
         "sb_matrix_all_row_programs": (C.c_int, [vp]),
+        # restarted GMRES(m)
+        "sb_gmres_create": (vp, [vp, vp, vp, vp, C.c_int]),
+        "sb_gmres_free": (None, [vp]),
+        "sb_gmres_set_fused": (None, [vp, C.c_int]),
+        "sb_gmres_restart": (C.c_int, [vp]),
+        "sb_gmres_launches_per_step": (C.c_int, [vp, C.c_int]),
+        "sb_gmres_solve": (C.c_int, [vp, C.c_int, C.c_double]),
+        "sb_gmres_start": (None, [vp, C.c_int, C.c_double]),
+        "sb_gmres_run_steps": (None, [vp, C.c_int]),
+        "sb_gmres_finish": (C.c_int, [vp]),
+        "sb_gmres_history": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]),
+        "sb_gmres_solution": (None, [vp, vp]),
+        "sb_gmres_check_residual": (C.c_double, [vp]),
+        "sb_gmres_loop_ms": (C.c_double, [vp]),
+        "sb_gmres_counters": (None, [vp, vp]),
+        "sb_multidot": (None, [u32, C.c_int, vp, C.c_size_t, vp, vp]),
+        "sb_multiaxpy_sub": (None, [u32, C.c_int, vp, C.c_size_t, vp, vp]),
+        "sb_debug_sqrt_div": (None, [u32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

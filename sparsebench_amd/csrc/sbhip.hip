@@ -23,6 +23,7 @@
 #include "kernels_sp_comm.hip.h"
 #include "pack.hip.h"
 #include "pack_sp.hip.h"
+#include "gmres.hip.h"
 
 #include <algorithm>
 #include <iterator>
@@ -671,3 +672,4 @@ void sb_event_destroy(void* ev) { HIP_CHECK(hipEventDestroy((hipEvent_t)ev)); }
 #include "sbhip_comm.inc.h"
 #include "sbhip_cg.inc.h"
 #include "sbhip_sp.inc.h"
+#include "sbhip_gmres.inc.h"

@@ -50,6 +50,12 @@ int solveCG(Comm* comm, Parameter* param, Matrix* m)
 #error "compile with -DCRS or -DSCS"
 #endif
 
+/* restarted GMRES on this build's Matrix (the _sp libraries: ends the process with "GMRES: double precision only") */
+int solveGMRES(Comm* comm, Parameter* param, Matrix* m, int restart)
+{
+  return sbh_solve_gmres(comm, param, m->dev, m->nr, m->rowNnz, restart);
+}
+
 void sbh_print_banner(Comm* c, const char* fmt);
 void commPrintBanner(Comm* c) { sbh_print_banner(c, FMT); } /* src/comm.c:185-250: names the build's format */
 

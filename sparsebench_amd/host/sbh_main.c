@@ -26,7 +26,8 @@ static const char* kHelp =
     "  -f <parameter file>   Load options from a parameter file\n"
     "  -c <file name>   Convert MM matrix to binary matrix file (.bmx).\n"
     "  -m <matrix>   Load a matrix market (.mtx) or binary (.bmx) file\n"
-    "  -t <bench type>   Benchmark type, can be cg or spmv. Default cg.\n"
+    "  -t <bench type>   Benchmark type, can be cg, spmv, or gmres. Default cg.\n"
+    "  -r <int>   GMRES restart length. Default 30.\n"
     "  -x <int>   Size in x for generated matrix, ignored if MM file is loaded. Default 100.\n"
     "  -y <int>   Size in y for generated matrix, ignored if MM file is loaded. Default 100.\n"
     "  -z <int>   Size in z for generated matrix, ignored if MM file is loaded. Default 100.\n"
@@ -43,8 +44,9 @@ int main(int argc, char** argv)
   initParameter(&param);
   int type = CG, opt;
   unsigned scsC = 64, scsSigma = 1;
+  int restart = 30;
   opterr = 0;
-  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:")) != -1) switch (opt) {
+  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:")) != -1) switch (opt) {
     case 'h':
       if (commIsMaster(&comm)) printf("%s", kHelp);
       commAbort(&comm, "");
@@ -58,7 +60,14 @@ int main(int argc, char** argv)
     case 't':
       if (strcmp(optarg, "cg") == 0) type = CG;
       else if (strcmp(optarg, "spmv") == 0) type = SPMV;
-      else {
+      else if (strcmp(optarg, "gmres") == 0) {
+#if PRECISION == 1
+        fprintf(stderr, "GMRES: double precision only\n");
+        return 1;
+#else
+        type = GMRES;
+#endif
+      } else {
         printf("Unknown solver type %s\n", optarg);
         return 1;
       }
@@ -70,6 +79,7 @@ int main(int argc, char** argv)
     case 'e': param.eps = atof(optarg); break;
     case 'C': scsC = (unsigned)atoi(optarg); break;
     case 's': scsSigma = (unsigned)atoi(optarg); break;
+    case 'r': restart = atoi(optarg); break;
     default:
       if (isprint(optopt)) fprintf(stderr, "Unknown option `-%c'.\n", optopt);
       else fprintf(stderr, "Unknown option character `\\x%x'.\n", optopt);
@@ -107,6 +117,9 @@ int main(int argc, char** argv)
   if (type == CG) {
     if (commIsMaster(&comm)) printf("Test type: CG\n");
     k = solveCG(&comm, &param, &sm);
+  } else if (type == GMRES) {
+    if (commIsMaster(&comm)) printf("Test type: GMRES\n");
+    k = solveGMRES(&comm, &param, &sm, restart);
   } else {
     if (commIsMaster(&comm)) printf("Test type: SPMVM\n");
     /* exactly the reference's loop (src/main.c:205-215): vectors from the allocation hook, filled by host loops, spMVM under

@@ -171,6 +171,58 @@ int sbh_solve_cg_perm(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr
   return sbh_solve(comm, param, dev_matrix, nr, rowNnz, oldToNewPerm);
 }
 
+/* ---- solveGMRES -------------------------------------------------------------------------- */
+/* The solver src/main.c:31,217-222 names and leaves empty.  The loop runs in the HIP layer (sb_gmres_*); the lines solveCG
+ * prints while iterating are printed afterwards from the recorded history: iteration j shows the residual estimate after
+ * the step taken at counter j. */
+int sbh_solve_gmres(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int restart)
+{
+#if PRECISION == 1
+  (void)comm, (void)param, (void)dev_matrix, (void)nr, (void)rowNnz, (void)restart;
+  fprintf(stderr, "GMRES: double precision only\n");
+  exit(EXIT_FAILURE);
+#else
+  const int itermax   = param->itermax;
+  const int generated = strcmp(param->filename, "generate") == 0 || strcmp(param->filename, "generate7P") == 0;
+  double* b           = (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double));
+  double* xexact      = generated ? (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double)) : NULL;
+  for (CG_UINT i = 0; i < nr; i++) { /* initVectors, src/CGSolver.c:25-36 */
+    if (generated) {
+      b[i]      = 27.0 - ((double)((int)rowNnz[i] - 1));
+      xexact[i] = 1.0;
+    } else {
+      b[i] = 1.0;
+    }
+  }
+  sb_gmres* s       = sb_gmres_create((const sb_matrix*)dev_matrix, NULL, b, xexact, restart);
+  const char* fused = getenv("SB_FUSED");
+  if (fused) sb_gmres_set_fused(s, atoi(fused));
+  const int k   = sb_gmres_solve(s, itermax, param->eps);
+  const int cap = itermax + 2;
+  double* res   = (double*)malloc((size_t)cap * sizeof(double));
+  double* rr    = (double*)malloc((size_t)cap * sizeof(double));
+  int nRr       = 0;
+  const int nRes = sb_gmres_history(s, res, cap, rr, cap, &nRr);
+  int printFreq  = itermax / 10; /* src/CGSolver.c:85-91 */
+  if (printFreq > 50) printFreq = 50;
+  if (printFreq < 1) printFreq = 1;
+  if (commIsMaster(comm)) {
+    printf("Initial Residual = %E\n", nRes > 0 ? res[0] : 0.0);
+    for (int j = 1; j < k; j++)
+      if ((j % printFreq == 0 || j + 1 == itermax) && j < nRes) printf("Iteration = %d Residual = %E\n", j, res[j]);
+    printf("Solution performed %d iterations and took %.2fs\n", k, 1e-3 * sb_gmres_loop_ms(s));
+  }
+  if (xexact) {
+    const double diff = sb_gmres_check_residual(s);
+    if (commIsMaster(comm)) printf("Difference between computed and exact  = %f\n", diff);
+  }
+  _t[SPMVM] += 1e-3 * sb_gmres_loop_ms(s); /* the loop's kernels overlap regions: the table's SpMV row carries the loop */
+  sb_gmres_free(s);
+  free(res), free(rr), free(b), free(xexact);
+  return k;
+#endif
+}
+
 /* ---- profiler table: src/profiler.c:11-141 ----------------------------------------------- */
 static const char* const kLabel[NUMREGIONS] = { "waxpby:  ", "spMVM:   ", "ddot:    ", "comm:    " };
 static double g_words[NUMREGIONS], g_flops[NUMREGIONS];

@@ -353,3 +353,73 @@ class CG:
         if self.ptr:
             self.L.sb_cg_free(self.ptr)
             self.ptr = None
+
+
+class GMRES:
+    """restarted GMRES(m) on the GPU (sb_gmres_*): for matrices that are not symmetric positive definite.  Krylov basis and
+    scalars in HBM, loop without host round trips; double precision, one rank."""
+
+    def __init__(self, problem, restart=30, fused=True):
+        if getattr(problem, "precision", "double") != "double":
+            raise ValueError("GMRES: double precision only (the problem was built with precision=%r)" % (problem.precision,))
+        self.L = capi.load()
+        self.problem = problem
+        b, xe = problem.rhs()
+        self.ptr = self.L.sb_gmres_create(problem.matrix, problem.halo, b.ctypes.data_as(vp),
+                                          xe.ctypes.data_as(vp) if xe is not None else None, int(restart))
+        # fused: True = the multi-dot / multi-update kernels, False = the op list (one tree dot per h entry, one waxpby-shaped
+        # launch per projection); same bits
+        self.L.sb_gmres_set_fused(self.ptr, int(bool(fused)))
+        self.itermax = 0
+
+    def restart(self):
+        return self.L.sb_gmres_restart(self.ptr)
+
+    def launches_per_step(self, j):
+        return self.L.sb_gmres_launches_per_step(self.ptr, int(j))
+
+    def solve(self, itermax=150, eps=0.0):
+        self.itermax = itermax
+        return self.L.sb_gmres_solve(self.ptr, itermax, eps)
+
+    def start(self, itermax, eps=0.0):
+        """prologue only; follow with run_steps() and finish()"""
+        self.itermax = itermax
+        self.L.sb_gmres_start(self.ptr, itermax, eps)
+
+    def run_steps(self, steps):
+        self.L.sb_gmres_run_steps(self.ptr, int(steps))
+
+    def finish(self):
+        return self.L.sb_gmres_finish(self.ptr)
+
+    def history(self):
+        """(res_hist, rr_hist): the residual estimates (index 0: the initial norm) and every explicit r.r"""
+        cap = self.itermax + 2
+        res = np.zeros(cap)
+        rr = np.zeros(cap)
+        nrr = C.c_int(0)
+        nres = self.L.sb_gmres_history(self.ptr, res.ctypes.data_as(vp), cap, rr.ctypes.data_as(vp), cap, C.byref(nrr))
+        return res[:nres].copy(), rr[:nrr.value].copy()
+
+    def solution(self):
+        """x in original row order"""
+        x = np.empty(self.problem.nr)
+        self.L.sb_gmres_solution(self.ptr, x.ctypes.data_as(vp))
+        return x
+
+    def check_residual(self):
+        return self.L.sb_gmres_check_residual(self.ptr)
+
+    def counters(self):
+        out = (C.c_int * 5)()
+        self.L.sb_gmres_counters(self.ptr, out)
+        return dict(zip(["stop", "steps", "cycles", "n_res", "n_rr"], list(out)))
+
+    def loop_ms(self):
+        return self.L.sb_gmres_loop_ms(self.ptr)
+
+    def free(self):
+        if self.ptr:
+            self.L.sb_gmres_free(self.ptr)
+            self.ptr = None
