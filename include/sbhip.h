@@ -474,6 +474,51 @@ void sb_multiaxpy_sub(uint32_t n, int nvec, const double* V, size_t ldv, const d
 /* test entry: sqrt_dev[e] = sqrt(a[e]), div_dev[e] = a[e] / b[e] as the scalar steps compute them (IEEE correctly rounded) */
 void sb_debug_sqrt_div(uint32_t n, const double* a_dev, const double* b_dev, double* sqrt_dev, double* div_dev);
 
+/* ---- batched CG: nrhs right-hand sides on one pass over the matrix ----------------------------------- */
+/* nrhs INDEPENDENT CG solves (not block CG: every column has its own alpha, beta, residual, loop test and iteration count)
+ * whose loop bodies share one stream of the matrix.  The contract is exact: column c is bit for bit sb_cg_create(..., b_c, ...)
+ * solved alone in the tree dot order -- k_c, every r.r, every p.Ap, x_c.  Double precision, ONE rank, tree order, nrhs in
+ * {2, 4, 8}; anything else (another width, a halo with more than one rank, a single-precision matrix, the seq order) is a
+ * fatal error with file:line.  The batched path streams the reference layout whatever sb_matrix_use_packed selected: the
+ * compressed mirror and the row programs take one vector.  Only Sell-C-sigma with C = 64 is tuned; CRS and other C run a
+ * one-thread-per-row correctness kernel.
+ * A BLOCK VECTOR is interleaved, element (row, c) at X[row * nrhs + c], rows in the device's row order (the permuted order
+ * for sigma > 1), 16-byte aligned. */
+typedef struct sb_cgb sb_cgb;
+/* Y = A X on block vectors (device pointers; X has nc rows, Y nr). */
+void sb_spmmv_native(const sb_matrix* m, int nrhs, const double* X_dev, double* Y_dev);
+/* ... with the fused level-1 values of X_c . Y_c, column c at l1_dev + c * ceil(nr/256): what the batched loop launches for
+ * p . Ap.  Returns 2 (level-1 values, as sb_spmv_native_dot does), or 0 without having run where the block kernel has no
+ * fused dot (CRS, C != 64). */
+int sb_spmmv_native_dot(const sb_matrix* m, int nrhs, const double* X_dev, double* Y_dev, double* l1_dev);
+/* nrhs plain vectors of nr doubles in ORIGINAL row order (vector c at cols_dev + c * nr) -> one block vector of nr rows, and
+ * back; both permute for sigma > 1.  Device pointers, stream-ordered. */
+void sb_block_interleave(const sb_matrix* m, int nrhs, const double* cols_dev, double* X_dev);
+void sb_block_deinterleave(const sb_matrix* m, int nrhs, const double* X_dev, double* cols_dev);
+/* algorithmic bytes of one SpMMV: the matrix part of sb_matrix_spmv_bytes once + nrhs times its vector part */
+double sb_matrix_spmmv_bytes(const sb_matrix* m, int nrhs);
+/* B_host: nrhs vectors of nr doubles in original row order, vector c at B_host + c * nr.  xexact0_host: the exact solution of
+ * column 0 (nr doubles) or NULL -- the other columns have none.  halo: NULL or a one-rank plan. */
+sb_cgb* sb_cgb_create(const sb_matrix* m, sb_halo* halo, int nrhs, const double* B_host, const double* xexact0_host);
+void sb_cgb_free(sb_cgb* s);
+int sb_cgb_nrhs(const sb_cgb* s);
+/* 5 on Sell-64 (p update | SpMMV with the p.Ap values | alpha steps | r update with the r.r values | beta steps; a scalar
+ * step is one launch of nrhs workgroups); 6 where the block kernel has no fused dot (+ the dot pass) */
+int sb_cgb_launches_per_body(const sb_cgb* s);
+int sb_cgb_solve(sb_cgb* s, int itermax, double eps); /* blocking; returns the largest k_c */
+/* The same in three steps, as sb_cg_start / _run_iters / _finish: bodies enqueued past every column's exit are no-ops, a
+ * column that has stopped no longer changes (the SpMMV still computes it), nothing is read back between bodies. */
+void sb_cgb_start(sb_cgb* s, int itermax, double eps);
+void sb_cgb_run_iters(sb_cgb* s, int iters);
+int sb_cgb_finish(sb_cgb* s);
+int sb_cgb_iterations(const sb_cgb* s, int c); /* k_c */
+int sb_cgb_history(const sb_cgb* s, int c, double* rr_out, int rr_cap, double* pAp_out, int pAp_cap, int* n_pAp);
+void sb_cgb_solution(const sb_cgb* s, int c, double* x_host); /* x_c, original row order */
+double sb_cgb_check_residual(const sb_cgb* s, int c);         /* max|x_0 - xexact_0| for c = 0 with an exact solution, else 0.0 */
+double sb_cgb_loop_ms(const sb_cgb* s); /* GPU milliseconds between the end of sb_cgb_start and sb_cgb_finish */
+/* c >= 0: {stop, stop_next, iters, n_rr, n_pAp} of column c; c = -1: {all stopped, columns stopped, bodies enqueued, 0, 0} */
+void sb_cgb_counters(const sb_cgb* s, int c, int out[5]);
+
 /* debug/measurement: raw streaming-read rate of the device in GB/s (DESIGN.md uses it
  * as the measured ceiling next to the 8 TB/s spec) */
 double sb_debug_stream_read_gbs(size_t bytes, int reps);

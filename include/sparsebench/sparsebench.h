@@ -252,6 +252,10 @@ int sbh_solve_cg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
 /* restarted GMRES(restart) on the same matrix (sb_gmres_*, sbhip.h): prints what solveCG prints; double precision, one rank */
 int sbh_solve_gmres(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
                     const CG_UINT* rowNnz, int restart);
+/* batched CG (sb_cgb_*, sbhip.h): nrhs independent CG solves on one pass over the matrix per body; startRow: the global index
+ * of local row 0 (the right-hand sides of columns >= 1 are a function of the global row index); double precision, one rank */
+int sbh_solve_cg_batch(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, CG_UINT startRow,
+                       int nrhs);
 
 /* ---- the hot path: src/solver.h:11-25, src/matrix.h:57 -------------------------------- */
 #if defined(CRS) || defined(SCS)
@@ -261,6 +265,13 @@ int solveCG(Comm* comm, Parameter* param, Matrix* m);
  * that are not symmetric positive definite; returns k as solveCG does.  The single-precision libraries export it too and
  * end the process with "GMRES: double precision only". */
 int solveGMRES(Comm* comm, Parameter* param, Matrix* m, int restart);
+/* nrhs (2, 4 or 8) independent CG solves on ONE stream of the matrix per loop body.  Column 0's right-hand side
+ * is initVectors' b (and xexact); for c >= 1, b_c[i] = b_0[i] + c * ((g(i) mod 5) - 2) with g the global row index, without
+ * an exact solution.  Prints solveCG's lines per column, each prefixed "RHS c: ", then the usual "Solution performed %d
+ * iterations and took %.2fs" with the largest k_c and the residual check of column 0; returns the largest k_c.  Column c's
+ * numbers are bit for bit those of solveCG on b_c alone.  One rank, tree dot order; the single-precision libraries export it
+ * too and end the process with "batched CG: double precision only". */
+int solveCGBatch(Comm* comm, Parameter* param, Matrix* m, int nrhs);
 /* x (nc entries) and y (nr entries) may be device or host pointers; host pointers are
  * staged through HBM (correct, slow: use sb_malloc'ed vectors on the hot path) */
 void spMVM(Matrix* m, const CG_FLOAT* restrict x, CG_FLOAT* restrict y);

@@ -44,6 +44,10 @@ SYMBOLS = [
     "sb_gmres_create", "sb_gmres_free", "sb_gmres_set_fused", "sb_gmres_restart", "sb_gmres_launches_per_step", "sb_gmres_solve",
     "sb_gmres_start", "sb_gmres_run_steps", "sb_gmres_finish", "sb_gmres_history", "sb_gmres_solution", "sb_gmres_check_residual",
     "sb_gmres_loop_ms", "sb_gmres_counters", "sb_multidot", "sb_multiaxpy_sub", "sb_debug_sqrt_div",
+    "sb_spmmv_native", "sb_spmmv_native_dot", "sb_block_interleave", "sb_block_deinterleave", "sb_matrix_spmmv_bytes",
+    "sb_cgb_create", "sb_cgb_free", "sb_cgb_nrhs", "sb_cgb_launches_per_body", "sb_cgb_solve", "sb_cgb_start", "sb_cgb_run_iters",
+    "sb_cgb_finish", "sb_cgb_iterations", "sb_cgb_history", "sb_cgb_solution", "sb_cgb_check_residual", "sb_cgb_loop_ms",
+    "sb_cgb_counters",
 ]
 
 _lib = None
@@ -226,6 +230,26 @@ def load():
         "sb_multidot": (None, [u32, C.c_int, vp, C.c_size_t, vp, vp]),
         "sb_multiaxpy_sub": (None, [u32, C.c_int, vp, C.c_size_t, vp, vp]),
         "sb_debug_sqrt_div": (None, [u32, vp, vp, vp, vp]),
+        # batched CG
+        "sb_spmmv_native": (None, [vp, C.c_int, vp, vp]),
+        "sb_spmmv_native_dot": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+        "sb_block_interleave": (None, [vp, C.c_int, vp, vp]),
+        "sb_block_deinterleave": (None, [vp, C.c_int, vp, vp]),
+        "sb_matrix_spmmv_bytes": (C.c_double, [vp, C.c_int]),
+        "sb_cgb_create": (vp, [vp, vp, C.c_int, vp, vp]),
+        "sb_cgb_free": (None, [vp]),
+        "sb_cgb_nrhs": (C.c_int, [vp]),
+        "sb_cgb_launches_per_body": (C.c_int, [vp]),
+        "sb_cgb_solve": (C.c_int, [vp, C.c_int, C.c_double]),
+        "sb_cgb_start": (None, [vp, C.c_int, C.c_double]),
+        "sb_cgb_run_iters": (None, [vp, C.c_int]),
+        "sb_cgb_finish": (C.c_int, [vp]),
+        "sb_cgb_iterations": (C.c_int, [vp, C.c_int]),
+        "sb_cgb_history": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]),
+        "sb_cgb_solution": (None, [vp, C.c_int, vp]),
+        "sb_cgb_check_residual": (C.c_double, [vp, C.c_int]),
+        "sb_cgb_loop_ms": (C.c_double, [vp]),
+        "sb_cgb_counters": (None, [vp, C.c_int, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -24,6 +24,7 @@
 #include "pack.hip.h"
 #include "pack_sp.hip.h"
 #include "gmres.hip.h"
+#include "batch.hip.h"
 
 #include <algorithm>
 #include <iterator>
@@ -673,3 +674,4 @@ void sb_event_destroy(void* ev) { HIP_CHECK(hipEventDestroy((hipEvent_t)ev)); }
 #include "sbhip_cg.inc.h"
 #include "sbhip_sp.inc.h"
 #include "sbhip_gmres.inc.h"
+#include "sbhip_cgb.inc.h"

@@ -56,6 +56,12 @@ int solveGMRES(Comm* comm, Parameter* param, Matrix* m, int restart)
   return sbh_solve_gmres(comm, param, m->dev, m->nr, m->rowNnz, restart);
 }
 
+/* nrhs CG solves on one pass over this build's Matrix per body (the _sp libraries: "batched CG: double precision only") */
+int solveCGBatch(Comm* comm, Parameter* param, Matrix* m, int nrhs)
+{
+  return sbh_solve_cg_batch(comm, param, m->dev, m->nr, m->rowNnz, m->startRow, nrhs);
+}
+
 void sbh_print_banner(Comm* c, const char* fmt);
 void commPrintBanner(Comm* c) { sbh_print_banner(c, FMT); } /* src/comm.c:185-250: names the build's format */
 

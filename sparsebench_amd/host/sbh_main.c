@@ -28,6 +28,7 @@ static const char* kHelp =
     "  -m <matrix>   Load a matrix market (.mtx) or binary (.bmx) file\n"
     "  -t <bench type>   Benchmark type, can be cg, spmv, or gmres. Default cg.\n"
     "  -r <int>   GMRES restart length. Default 30.\n"
+    "  -n <int>   Number of right-hand sides for -t cg. Default 1.\n"
     "  -x <int>   Size in x for generated matrix, ignored if MM file is loaded. Default 100.\n"
     "  -y <int>   Size in y for generated matrix, ignored if MM file is loaded. Default 100.\n"
     "  -z <int>   Size in z for generated matrix, ignored if MM file is loaded. Default 100.\n"
@@ -44,9 +45,9 @@ int main(int argc, char** argv)
   initParameter(&param);
   int type = CG, opt;
   unsigned scsC = 64, scsSigma = 1;
-  int restart = 30;
+  int restart = 30, nrhs = 1;
   opterr = 0;
-  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:")) != -1) switch (opt) {
+  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:")) != -1) switch (opt) {
     case 'h':
       if (commIsMaster(&comm)) printf("%s", kHelp);
       commAbort(&comm, "");
@@ -80,12 +81,17 @@ int main(int argc, char** argv)
     case 'C': scsC = (unsigned)atoi(optarg); break;
     case 's': scsSigma = (unsigned)atoi(optarg); break;
     case 'r': restart = atoi(optarg); break;
+    case 'n': nrhs = atoi(optarg); break;
     default:
       if (isprint(optopt)) fprintf(stderr, "Unknown option `-%c'.\n", optopt);
       else fprintf(stderr, "Unknown option character `\\x%x'.\n", optopt);
       return 1;
     }
   for (int i = optind; i < argc; i++) printf("Non-option argument %s\n", argv[i]);
+  if (nrhs != 1 && type != CG) {
+    fprintf(stderr, "-n <int> (several right-hand sides) goes with -t cg only\n");
+    return 1;
+  }
 
   commPrintBanner(&comm);
 
@@ -116,7 +122,7 @@ int main(int argc, char** argv)
   int k = 0;
   if (type == CG) {
     if (commIsMaster(&comm)) printf("Test type: CG\n");
-    k = solveCG(&comm, &param, &sm);
+    k = nrhs == 1 ? solveCG(&comm, &param, &sm) : solveCGBatch(&comm, &param, &sm, nrhs);
   } else if (type == GMRES) {
     if (commIsMaster(&comm)) printf("Test type: GMRES\n");
     k = solveGMRES(&comm, &param, &sm, restart);

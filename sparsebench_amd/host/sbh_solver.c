@@ -223,6 +223,66 @@ int sbh_solve_gmres(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, 
 #endif
 }
 
+/* ---- solveCGBatch ------------------------------------------------------------------------ */
+/* nrhs independent CG solves whose loop bodies share one stream of the matrix (sb_cgb_*).  Column 0 is solveCG's
+ * system; column c >= 1 has b_c[i] = b_0[i] + c * ((g(i) mod 5) - 2), g = startRow + i (small integers: exact).  The lines
+ * solveCG prints come per column, prefixed "RHS c: ", from the recorded histories. */
+int sbh_solve_cg_batch(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, CG_UINT startRow, int nrhs)
+{
+#if PRECISION == 1
+  (void)comm, (void)param, (void)dev_matrix, (void)nr, (void)rowNnz, (void)startRow, (void)nrhs;
+  fprintf(stderr, "batched CG: double precision only\n");
+  exit(EXIT_FAILURE);
+#else
+  const int itermax   = param->itermax;
+  const int generated = strcmp(param->filename, "generate") == 0 || strcmp(param->filename, "generate7P") == 0;
+  const int nv        = nrhs > 0 ? nrhs : 1; /* (a width the layer does not have is refused by sb_cgb_create, with its message) */
+  double* B           = (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr * nv + 1) * sizeof(double));
+  double* xexact      = generated ? (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double)) : NULL;
+  for (CG_UINT i = 0; i < nr; i++) { /* initVectors, src/CGSolver.c:25-36 */
+    if (generated) {
+      B[i]      = 27.0 - ((double)((int)rowNnz[i] - 1));
+      xexact[i] = 1.0;
+    } else {
+      B[i] = 1.0;
+    }
+  }
+  for (int c = 1; c < nv; c++)
+    for (CG_UINT i = 0; i < nr; i++) B[(size_t)c * nr + i] = B[i] + (double)c * (double)((int)(((size_t)startRow + i) % 5) - 2);
+  sb_cgb* s   = sb_cgb_create((const sb_matrix*)dev_matrix, NULL, nrhs, B, xexact);
+  const int k = sb_cgb_solve(s, itermax, param->eps);
+  const int cap = itermax + 2;
+  double* rr    = (double*)malloc((size_t)cap * sizeof(double));
+  double* pAp   = (double*)malloc((size_t)cap * sizeof(double));
+  int printFreq = itermax / 10; /* :85-91 */
+  if (printFreq > 50) printFreq = 50;
+  if (printFreq < 1) printFreq = 1;
+  if (commIsMaster(comm)) {
+    for (int c = 0; c < nv; c++) {
+      int nPAp      = 0;
+      const int nRr = sb_cgb_history(s, c, rr, cap, pAp, cap, &nPAp);
+      const int kc  = sb_cgb_iterations(s, c);
+      printf("RHS %d: Initial Residual = %E\n", c, nRr > 0 ? sqrt(rr[0]) : 0.0);
+      for (int j = 1; j < kc; j++)
+        if (j % printFreq == 0 || j + 1 == itermax) {
+          const int idx = j == 1 ? 0 : j - 1;
+          if (idx < nRr) printf("RHS %d: Iteration = %d Residual = %E\n", c, j, sqrt(rr[idx]));
+        }
+      printf("RHS %d: Solution performed %d iterations\n", c, kc);
+    }
+    printf("Solution performed %d iterations and took %.2fs\n", k, 1e-3 * sb_cgb_loop_ms(s));
+  }
+  if (xexact) { /* solverCheckResidual, :40-60, for the column that has an exact solution */
+    const double diff = sb_cgb_check_residual(s, 0);
+    if (commIsMaster(comm)) printf("Difference between computed and exact  = %f\n", diff);
+  }
+  _t[SPMVM] += 1e-3 * sb_cgb_loop_ms(s); /* the loop's kernels overlap regions: the table's SpMV row carries the loop */
+  sb_cgb_free(s);
+  free(rr), free(pAp), free(B), free(xexact);
+  return k;
+#endif
+}
+
 /* ---- profiler table: src/profiler.c:11-141 ----------------------------------------------- */
 static const char* const kLabel[NUMREGIONS] = { "waxpby:  ", "spMVM:   ", "ddot:    ", "comm:    " };
 static double g_words[NUMREGIONS], g_flops[NUMREGIONS];

@@ -423,3 +423,93 @@ class GMRES:
         if self.ptr:
             self.L.sb_gmres_free(self.ptr)
             self.ptr = None
+
+
+def batch_rhs(b0, nrhs, start_row=0):
+    """the right-hand sides of solveCGBatch: row 0 is b0; for c >= 1, b_c[i] = b0[i] + c * ((g(i) mod 5) - 2) with g the
+    global row index (small integers: exact)"""
+    b0 = np.asarray(b0, dtype=np.float64)
+    g = (np.arange(len(b0), dtype=np.int64) + int(start_row)) % 5 - 2
+    return np.stack([b0 + float(c) * g for c in range(int(nrhs))])
+
+
+class BatchCG:
+    """nrhs independent CG solves on one pass over the matrix per loop body (sb_cgb_*): column c is bit for bit
+    `CG` on b_c alone in the tree dot order.  B: an (nrhs, nr) array in original row order; None: `batch_rhs` of the problem's
+    own right-hand side.  Double precision, one rank, nrhs in {2, 4, 8}."""
+
+    def __init__(self, problem, B=None, nrhs=4):
+        if getattr(problem, "precision", "double") != "double":
+            raise ValueError("batched CG: double precision only (the problem was built with precision=%r)" % (problem.precision,))
+        self.L = capi.load()
+        self.problem = problem
+        b0, xe = problem.rhs()
+        if B is None:
+            B = batch_rhs(b0, nrhs, problem.startRow)
+        else:
+            B = np.ascontiguousarray(B, dtype=np.float64)
+            if B.ndim != 2 or B.shape[1] != problem.nr:
+                raise ValueError("B must be an (nrhs, nr) array, got shape %r" % (B.shape,))
+            nrhs = B.shape[0]
+            if xe is not None and not np.array_equal(B[0], b0):
+                xe = None  # the exact solution belongs to the problem's own right-hand side
+        self.nrhs = int(nrhs)
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        self.ptr = self.L.sb_cgb_create(problem.matrix, problem.halo, self.nrhs, B.ctypes.data_as(vp),
+                                        xe.ctypes.data_as(vp) if xe is not None else None)
+        self.itermax = 0
+
+    def launches_per_body(self):
+        return self.L.sb_cgb_launches_per_body(self.ptr)
+
+    def solve(self, itermax=150, eps=0.0):
+        """returns the largest k_c"""
+        self.itermax = itermax
+        return self.L.sb_cgb_solve(self.ptr, itermax, eps)
+
+    def start(self, itermax, eps=0.0):
+        """prologue only; follow with run_iters() and finish()"""
+        self.itermax = itermax
+        self.L.sb_cgb_start(self.ptr, itermax, eps)
+
+    def run_iters(self, iters):
+        self.L.sb_cgb_run_iters(self.ptr, int(iters))
+
+    def finish(self):
+        return self.L.sb_cgb_finish(self.ptr)
+
+    def iterations(self, c):
+        return self.L.sb_cgb_iterations(self.ptr, int(c))
+
+    def history(self, c):
+        cap = self.itermax + 2
+        rr = np.zeros(cap)
+        pap = np.zeros(cap)
+        npap = C.c_int(0)
+        nrr = self.L.sb_cgb_history(self.ptr, int(c), rr.ctypes.data_as(vp), cap, pap.ctypes.data_as(vp), cap, C.byref(npap))
+        return rr[:nrr].copy(), pap[:npap.value].copy()
+
+    def solution(self, c):
+        """x_c in original row order"""
+        x = np.empty(self.problem.nr)
+        self.L.sb_cgb_solution(self.ptr, int(c), x.ctypes.data_as(vp))
+        return x
+
+    def check_residual(self, c=0):
+        return self.L.sb_cgb_check_residual(self.ptr, int(c))
+
+    def counters(self, c=-1):
+        """column c: stop, stop_next, iters, n_rr, n_pAp; c = -1: all_stopped, columns_stopped, bodies_enqueued"""
+        out = (C.c_int * 5)()
+        self.L.sb_cgb_counters(self.ptr, int(c), out)
+        if c < 0:
+            return dict(zip(["all_stopped", "columns_stopped", "bodies_enqueued"], list(out)[:3]))
+        return dict(zip(["stop", "stop_next", "iters", "n_rr", "n_pAp"], list(out)))
+
+    def loop_ms(self):
+        return self.L.sb_cgb_loop_ms(self.ptr)
+
+    def free(self):
+        if self.ptr:
+            self.L.sb_cgb_free(self.ptr)
+            self.ptr = None

@@ -1,0 +1,61 @@
+"""The batched-CG surface without a GPU: the new entry points are declared in include/sbhip.h, exported by libsbhip.so and
+listed in capi.SYMBOLS; the four drop-in libraries export solveCGBatch; hostapi.BatchCG refuses a single-precision problem
+before it touches the library; loading initialises no device."""
+import ctypes
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "sparsebench_amd", "lib")
+
+NEW = ["sb_spmmv_native", "sb_spmmv_native_dot", "sb_block_interleave", "sb_block_deinterleave", "sb_matrix_spmmv_bytes",
+       "sb_cgb_create", "sb_cgb_free", "sb_cgb_nrhs", "sb_cgb_launches_per_body", "sb_cgb_solve", "sb_cgb_start", "sb_cgb_run_iters",
+       "sb_cgb_finish", "sb_cgb_iterations", "sb_cgb_history", "sb_cgb_solution", "sb_cgb_check_residual", "sb_cgb_loop_ms",
+       "sb_cgb_counters"]
+
+
+def test_batch_symbols_declared_exported_and_listed():
+    from sparsebench_amd import capi
+    L = capi.load()
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sbhip.h")).read(), flags=re.S)
+    for n in NEW:
+        assert re.search(r"\b%s\s*\(" % n, header), "include/sbhip.h does not declare %s" % n
+        assert hasattr(L, n), "libsbhip.so does not export %s" % n
+        assert n in capi.SYMBOLS
+        assert getattr(L, n).argtypes is not None, "capi.load() gives %s no prototype" % n
+    assert L.sb_is_initialized() == 0  # loading touched no device
+
+
+@pytest.mark.parametrize("lib", ["libsparsebench_crs.so", "libsparsebench_scs.so", "libsparsebench_crs_sp.so", "libsparsebench_scs_sp.so"])
+def test_dropin_libraries_export_solveCGBatch(lib):
+    from sparsebench_amd import hostapi
+    hostapi.host()
+    hostapi.host("single")
+    d = ctypes.CDLL(os.path.join(LIB, lib))
+    assert hasattr(d, "solveCGBatch")
+    hdr = open(os.path.join(ROOT, "include", "sparsebench", "sparsebench.h")).read()
+    assert re.search(r"\bint\s+solveCGBatch\s*\(\s*Comm\s*\*[^)]*Parameter\s*\*[^)]*Matrix\s*\*[^)]*int\s+nrhs\s*\)", hdr)
+
+
+def test_hostapi_batchcg_refuses_single_precision():
+    from sparsebench_amd import hostapi
+
+    class FakeSP:  # never touched: the refusal comes first
+        precision = "single"
+
+        def rhs(self):
+            raise AssertionError("the library was touched")
+
+    with pytest.raises(ValueError, match="double precision only"):
+        hostapi.BatchCG(FakeSP())
+    for name in ("solve", "start", "run_iters", "finish", "iterations", "history", "solution", "check_residual",
+                 "launches_per_body", "loop_ms", "counters", "free"):
+        assert callable(getattr(hostapi.BatchCG, name)), name
+
+
+def test_driver_help_names_the_option():
+    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
+    assert "-n <int>   Number of right-hand sides for -t cg. Default 1." in src
+    assert re.search(r'getopt\(argc, argv, "[^"]*n:[^"]*"\)', src)

@@ -54,6 +54,8 @@ def functions(elf):
         if m:
             cur = out.setdefault(m.group(1), [])
         elif cur is not None and line.startswith("\t"):
+            if line.strip() == "...":  # llvm-objdump's mark for a run of zero bytes: alignment padding behind the last instruction
+                continue
             cur.append(" ".join(line.split("//")[0].split()))
     return out
 
