@@ -519,6 +519,46 @@ double sb_cgb_loop_ms(const sb_cgb* s); /* GPU milliseconds between the end of s
 /* c >= 0: {stop, stop_next, iters, n_rr, n_pAp} of column c; c = -1: {all stopped, columns stopped, bodies enqueued, 0, 0} */
 void sb_cgb_counters(const sb_cgb* s, int c, int out[5]);
 
+/* ---- CG with a diagonal preconditioner ---------------------------------------------------------------- */
+/* solveCG's loop with z = r o dinv put back (HPCG's CG with its preconditioner): alpha = r.z / p.Ap, beta = r.z / (r.z)_old,
+ * p = z + beta p; the loop test stays on sqrt(r.r) with solveCG's one-body lag, so dinv = 1.0 everywhere is sb_cg in the tree
+ * order bit for bit (k, every r.r, every p.Ap, x; r.z == r.r).  Double precision, ONE rank, tree dot order; a halo with more
+ * than one rank, a single-precision matrix, the seq order, a matrix row without a finite positive diagonal (Jacobi) and a
+ * caller's dinv entry that is not finite and positive are fatal errors with file:line.  The SpMV is the one the matrix's
+ * kernel mode selects (sb_matrix_use_packed), as sb_spmv_native_dot launches it. */
+typedef struct sb_pcg sb_pcg;
+/* d_dev[i] = the sum, in storage order from +0.0, of row i's stored entries whose column is i; device pointer, nr doubles,
+ * the device's row order (the permuted order for sigma > 1); stream-ordered */
+void sb_matrix_diagonal(const sb_matrix* m, double* d_dev);
+/* b_host, xexact_host (or NULL) as for sb_cg_create.  dinv_host NULL: Jacobi, dinv_i = 1.0 / d_i; else nr finite positive
+ * doubles in ORIGINAL row order.  halo: NULL or a one-rank plan. */
+sb_pcg* sb_pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const double* dinv_host);
+void sb_pcg_free(sb_pcg* s);
+int sb_pcg_solve(sb_pcg* s, int itermax, double eps); /* blocking; returns k as solveCG does */
+/* The same in three steps, as sb_cg_start / _run_iters / _finish: bodies enqueued past the exit are no-ops, nothing is read
+ * back between bodies; a handle can be solved again. */
+void sb_pcg_start(sb_pcg* s, int itermax, double eps);
+void sb_pcg_run_iters(sb_pcg* s, int iters);
+int sb_pcg_finish(sb_pcg* s);
+/* rr[0], rz[0]: the prologue's; then one rr, one rz (both under rr_cap / rz_cap, the smaller counts) and one pAp per body, as
+ * sb_cg_history indexes its own.  Returns the number of rr (= rz) entries. */
+int sb_pcg_history(const sb_pcg* s, double* rr_out, int rr_cap, double* rz_out, int rz_cap, double* pAp_out, int pAp_cap, int* n_pAp);
+void sb_pcg_solution(const sb_pcg* s, double* x_host);   /* original row order */
+double sb_pcg_check_residual(const sb_pcg* s);           /* max|x - xexact|, 0.0 without an exact solution */
+void sb_pcg_dinv(const sb_pcg* s, double* dinv_host);    /* the preconditioner in use, original row order */
+/* 5 (p update | SpMV with the p.Ap values | alpha | r update with z and the r.z, r.r values | beta); 6 where the selected SpMV
+ * kernel has no fused dot (native CRS, C != 64: + the dot pass) */
+int sb_pcg_launches_per_body(const sb_pcg* s);
+double sb_pcg_loop_ms(const sb_pcg* s); /* GPU milliseconds between the end of sb_pcg_start and sb_pcg_finish */
+void sb_pcg_counters(const sb_pcg* s, int out[5]); /* stop, stop_next, iters, n_rr, n_pAp of the device control block */
+/* test entry for the fused kernel: r = r + nalpha * Ap, z = r o dinv and the ceil(n/256) level-1 values of r.z and of r.r;
+ * r, Ap, dinv, z device vectors of n doubles (16-byte aligned), nalpha a host scalar; blocking */
+void sb_pcg_update_r_native(uint32_t n, double nalpha, const double* Ap_dev, double* r_dev, const double* dinv_dev, double* z_dev,
+                            double* l1_rz_dev, double* l1_rr_dev);
+/* its launch over n rows: {workgroups, threads per workgroup, compute units of the device}; a wave owns whole 256-row groups
+ * and strides over them by the number of waves in the grid */
+void sb_pcg_update_r_launch(uint32_t n, uint32_t out[3]);
+
 /* debug/measurement: raw streaming-read rate of the device in GB/s (DESIGN.md uses it
  * as the measured ceiling next to the 8 TB/s spec) */
 double sb_debug_stream_read_gbs(size_t bytes, int reps);

@@ -256,6 +256,8 @@ int sbh_solve_gmres(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
  * of local row 0 (the right-hand sides of columns >= 1 are a function of the global row index); double precision, one rank */
 int sbh_solve_cg_batch(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, CG_UINT startRow,
                        int nrhs);
+/* CG with the Jacobi preconditioner dinv = 1 / diag(A) (sb_pcg_*, sbhip.h): prints what solveCG prints; double precision, one rank */
+int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz);
 
 /* ---- the hot path: src/solver.h:11-25, src/matrix.h:57 -------------------------------- */
 #if defined(CRS) || defined(SCS)
@@ -272,6 +274,11 @@ int solveGMRES(Comm* comm, Parameter* param, Matrix* m, int restart);
  * numbers are bit for bit those of solveCG on b_c alone.  One rank, tree dot order; the single-precision libraries export it
  * too and end the process with "batched CG: double precision only". */
 int solveCGBatch(Comm* comm, Parameter* param, Matrix* m, int nrhs);
+/* solveCG with the Jacobi preconditioner put back: z = r o (1 / diag(A)), alpha = r.z / p.Ap, beta = r.z / (r.z)_old,
+ * the loop test on sqrt(r.r) as in solveCG.  Prints solveCG's lines from the recorded history and returns k as solveCG does.
+ * A matrix row without a finite positive diagonal entry ends the process with a message.  One rank, tree dot order; the
+ * single-precision libraries export it too and end the process with "PCG: double precision only". */
+int solvePCG(Comm* comm, Parameter* param, Matrix* m);
 /* x (nc entries) and y (nr entries) may be device or host pointers; host pointers are
  * staged through HBM (correct, slow: use sb_malloc'ed vectors on the hot path) */
 void spMVM(Matrix* m, const CG_FLOAT* restrict x, CG_FLOAT* restrict y);

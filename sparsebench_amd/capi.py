@@ -48,6 +48,9 @@ SYMBOLS = [
     "sb_cgb_create", "sb_cgb_free", "sb_cgb_nrhs", "sb_cgb_launches_per_body", "sb_cgb_solve", "sb_cgb_start", "sb_cgb_run_iters",
     "sb_cgb_finish", "sb_cgb_iterations", "sb_cgb_history", "sb_cgb_solution", "sb_cgb_check_residual", "sb_cgb_loop_ms",
     "sb_cgb_counters",
+    "sb_matrix_diagonal", "sb_pcg_create", "sb_pcg_free", "sb_pcg_solve", "sb_pcg_start", "sb_pcg_run_iters", "sb_pcg_finish",
+    "sb_pcg_history", "sb_pcg_solution", "sb_pcg_check_residual", "sb_pcg_dinv", "sb_pcg_launches_per_body", "sb_pcg_loop_ms",
+    "sb_pcg_counters", "sb_pcg_update_r_native", "sb_pcg_update_r_launch",
 ]
 
 _lib = None
@@ -250,6 +253,23 @@ def load():
         "sb_cgb_check_residual": (C.c_double, [vp, C.c_int]),
         "sb_cgb_loop_ms": (C.c_double, [vp]),
         "sb_cgb_counters": (None, [vp, C.c_int, vp]),
+        # CG with a diagonal preconditioner
+        "sb_matrix_diagonal": (None, [vp, vp]),
+        "sb_pcg_create": (vp, [vp, vp, vp, vp, vp]),
+        "sb_pcg_free": (None, [vp]),
+        "sb_pcg_solve": (C.c_int, [vp, C.c_int, C.c_double]),
+        "sb_pcg_start": (None, [vp, C.c_int, C.c_double]),
+        "sb_pcg_run_iters": (None, [vp, C.c_int]),
+        "sb_pcg_finish": (C.c_int, [vp]),
+        "sb_pcg_history": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]),
+        "sb_pcg_solution": (None, [vp, vp]),
+        "sb_pcg_check_residual": (C.c_double, [vp]),
+        "sb_pcg_dinv": (None, [vp, vp]),
+        "sb_pcg_launches_per_body": (C.c_int, [vp]),
+        "sb_pcg_loop_ms": (C.c_double, [vp]),
+        "sb_pcg_counters": (None, [vp, vp]),
+        "sb_pcg_update_r_native": (None, [u32, C.c_double, vp, vp, vp, vp, vp, vp]),
+        "sb_pcg_update_r_launch": (None, [u32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -25,6 +25,7 @@
 #include "pack_sp.hip.h"
 #include "gmres.hip.h"
 #include "batch.hip.h"
+#include "pcg.hip.h"
 
 #include <algorithm>
 #include <iterator>
@@ -675,3 +676,4 @@ void sb_event_destroy(void* ev) { HIP_CHECK(hipEventDestroy((hipEvent_t)ev)); }
 #include "sbhip_sp.inc.h"
 #include "sbhip_gmres.inc.h"
 #include "sbhip_cgb.inc.h"
+#include "sbhip_pcg.inc.h"

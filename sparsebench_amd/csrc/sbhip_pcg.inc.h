@@ -1,0 +1,324 @@
+// sbhip_pcg.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context): CG with a
+// diagonal preconditioner (kernels: pcg.hip.h).  Double precision, one rank, tree dot order.  The SpMV is the
+// one the matrix's kernel mode selects (launch_spmv: the reference-layout stream or the masked row programs, with their
+// fused p.Ap values; native CRS and generic C are followed by dot_l1_k).  The loop's vectors are allocations of the handle's
+// own: the matrix's tuned arena (sb_matrix::vecArena) is laid out for sb_cg's vectors and stays with sb_cg.
+// ===========================================================================
+// preconditioned CG
+// ===========================================================================
+struct sb_pcg {
+  const sb_matrix* A = nullptr;
+  uint32_t nr = 0, nc = 0, nGroups = 0;
+  double *r = nullptr, *z = nullptr, *p = nullptr, *Ap = nullptr, *x = nullptr, *b = nullptr, *dinv = nullptr; // device row order
+  double* xexact = nullptr;
+  PcgScalars* S = nullptr;
+  double *l1pAp = nullptr, *l1rz = nullptr, *l1rr = nullptr;
+  double *rr_hist = nullptr, *rz_hist = nullptr, *pAp_hist = nullptr;
+  int hist_cap = 0;
+  int k_next = 1;
+  bool started = false;
+  float loop_ms = 0.f;
+  hipEvent_t evLoop0 = nullptr, evLoop1 = nullptr;
+};
+
+// the diagonal in the device's row order; bad_dev: NULL, or two uint32 (rows without a finite positive diagonal, the first of
+// them) preset to {0, 0xFFFFFFFF}
+static void launch_diagonal(const sb_matrix* m, double* d_dev, uint32_t* bad_dev)
+{
+  if (m->nr == 0) return;
+  uint32_t* bad = bad_dev ? bad_dev : reinterpret_cast<uint32_t*>(scratch_partials(2));
+  const dim3 grid((m->nr + 255) / 256), block(256);
+  if (m->fmt == 0) hipLaunchKernelGGL(diag_crs_k, grid, block, 0, g.stream, m->nr, m->rowPtr, m->colInd, m->val, d_dev, bad);
+  else
+    hipLaunchKernelGGL(diag_scs_k, grid, block, 0, g.stream, m->nr, m->C, m->chunkPtr, m->chunkLens, m->colInd, m->val, d_dev, bad);
+  HIP_CHECK(hipGetLastError());
+}
+
+void sb_matrix_diagonal(const sb_matrix* m, double* d_dev)
+{
+  need_init();
+  SB_NEED_PREC(m, 2, "sb_matrix_diagonal");
+  launch_diagonal(m, d_dev, nullptr);
+}
+
+// grid of pcg_update_r_k over n rows (cg_update_r_k<0>'s: 1024 threads, a wave per 256-row group, two workgroups per CU at most)
+static uint32_t pcg_update_r_grid(uint32_t n)
+{
+  const uint32_t nGroups = (n + 255u) >> 8;
+  return std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * 2u, (nGroups + 15u) / 16u));
+}
+void sb_pcg_update_r_launch(uint32_t n, uint32_t out[3])
+{
+  need_init();
+  out[0] = pcg_update_r_grid(n), out[1] = 1024u, out[2] = (uint32_t)g.prop.multiProcessorCount;
+}
+
+static void pcg_need_aligned(const void* a, const void* b, const void* c, const void* d, const char* fn)
+{
+  if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15u) SB_FATAL("%s: vectors must be 16-byte aligned", fn);
+}
+
+void sb_pcg_update_r_native(uint32_t n, double nalpha, const double* Ap_dev, double* r_dev, const double* dinv_dev, double* z_dev,
+    double* l1_rz_dev, double* l1_rr_dev)
+{
+  need_init();
+  if (n == 0) return;
+  pcg_need_aligned(Ap_dev, r_dev, dinv_dev, z_dev, "sb_pcg_update_r_native");
+  PcgScalars h;
+  memset(&h, 0, sizeof h);
+  h.neg_alpha   = nalpha;
+  PcgScalars* S = (PcgScalars*)sb_malloc(sizeof h);
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  HIP_CHECK(hipMemcpy(S, &h, sizeof h, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(pcg_update_r_k<0>, dim3(pcg_update_r_grid(n)), dim3(1024), 0, g.stream, n, Ap_dev, (const double*)r_dev, r_dev,
+      dinv_dev, z_dev, (const PcgScalars*)S, l1_rz_dev, l1_rr_dev);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  sb_free(S);
+}
+
+static void pcg_need_tree(const char* fn)
+{
+  if (sb_dot_order() == 1)
+    SB_FATAL("%s: PCG runs in the tree dot order only (the process is in the seq order: SB_DOT_ORDER=seq / sb_set_dot_order(1), "
+             "the validation mode of sb_cg)", fn);
+}
+
+sb_pcg* sb_pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const double* dinv_host)
+{
+  need_init();
+  if (m->prec != 2) SB_FATAL("sb_pcg_create: PCG: double precision only (the matrix was uploaded in single precision)");
+  if (multi_rank() || sb_comm_size() > 1 || m->nc != m->nr || (halo && halo->externalCount > 0))
+    SB_FATAL("sb_pcg_create: PCG runs on one rank (this process is rank %d of %d, the matrix has %u halo columns)", g.rank, g.size,
+        m->nc - m->nr);
+  pcg_need_tree("sb_pcg_create");
+  if (dinv_host)
+    for (uint32_t i = 0; i < m->nr; i++)
+      if (!(dinv_host[i] > 0.0 && dinv_host[i] < INFINITY))
+        SB_FATAL("sb_pcg_create: dinv[%u] = %g: the preconditioner's entries must be finite and positive", i, dinv_host[i]);
+  sb_pcg* s       = new sb_pcg();
+  s->A = m, s->nr = m->nr, s->nc = m->nc;
+  s->nGroups      = (m->nr + 255u) >> 8;
+  const size_t nb = (size_t)m->nr * sizeof(double);
+  double** vecs[] = { &s->r, &s->z, &s->Ap, &s->x, &s->b, &s->dinv, &s->p };
+  for (double** v : vecs) *v = (double*)sb_malloc((size_t)m->nc * sizeof(double) + 4096);
+  double* tmp = scratch_ws(0, (size_t)m->nr + 2);
+  if (dinv_host) {
+    if (m->nr) sb_h2d(tmp, dinv_host, nb);
+    sb_permute(m, tmp, s->dinv);
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+  } else if (m->nr) { // Jacobi: dinv = 1 / diag(A)
+    uint32_t bad[2] = { 0u, 0xFFFFFFFFu };
+    uint32_t* dbad  = (uint32_t*)sb_malloc(sizeof bad);
+    sb_h2d(dbad, bad, sizeof bad);
+    launch_diagonal(m, tmp, dbad);
+    sb_d2h(bad, dbad, sizeof bad);
+    sb_free(dbad);
+    if (bad[0])
+      SB_FATAL("sb_pcg_create: %u of %u matrix rows have no finite positive diagonal entry (the first: device row %u): the Jacobi "
+               "preconditioner needs one in every row; pass dinv_host for another diagonal preconditioner", bad[0], m->nr, bad[1]);
+    hipLaunchKernelGGL(pcg_reciprocal_k, dim3(stream_grid(m->nr, 256)), dim3(256), 0, g.stream, m->nr, (const double*)tmp, s->dinv);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+  }
+  if (m->nr) sb_h2d(tmp, b_host, nb);
+  sb_permute(m, tmp, s->b);
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  if (xexact_host) {
+    s->xexact = (double*)sb_malloc(nb + 4096);
+    if (m->nr) sb_h2d(tmp, xexact_host, nb);
+    sb_permute(m, tmp, s->xexact);
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+  }
+  s->S = (PcgScalars*)sb_malloc(sizeof(PcgScalars));
+  HIP_CHECK(hipMemset(s->S, 0, sizeof(PcgScalars)));
+  // p.Ap: sized as sb_cg sizes the array its SpMV kernels write (4 per 256 rows, tail +0.0)
+  const size_t lb = (4 * (size_t)s->nGroups + 4) * sizeof(double);
+  double** l1s[]  = { &s->l1pAp, &s->l1rz, &s->l1rr };
+  for (double** v : l1s) {
+    *v = (double*)sb_malloc(lb);
+    HIP_CHECK(hipMemsetAsync(*v, 0, lb, g.stream));
+  }
+  HIP_CHECK(hipEventCreate(&s->evLoop0));
+  HIP_CHECK(hipEventCreate(&s->evLoop1));
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  return s;
+}
+
+void sb_pcg_free(sb_pcg* s)
+{
+  if (!s) return;
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  HIP_CHECK(hipEventDestroy(s->evLoop0));
+  HIP_CHECK(hipEventDestroy(s->evLoop1));
+  sb_free(s->r), sb_free(s->z), sb_free(s->p), sb_free(s->Ap), sb_free(s->x), sb_free(s->b), sb_free(s->dinv), sb_free(s->xexact);
+  sb_free(s->S), sb_free(s->l1pAp), sb_free(s->l1rz), sb_free(s->l1rr), sb_free(s->rr_hist), sb_free(s->rz_hist), sb_free(s->pAp_hist);
+  delete s;
+}
+
+// launches per loop body: p update | SpMV (+ p.Ap values) | alpha | r update (+ z, r.z and r.r values) | beta = 5 where the
+// selected SpMV kernel has a fused dot; native CRS and generic C add the dot pass: 6
+int sb_pcg_launches_per_body(const sb_pcg* s) { return spmv_dot_kind(s->A) ? 5 : 6; }
+
+template <int MODE> static void pcg_scalar_launch(sb_pcg* s)
+{
+  hipLaunchKernelGGL((pcg_scalar_k<MODE>), dim3(1), dim3(1024), 0, g.stream, s->nGroups, (const double*)(MODE == 2 ? s->l1pAp : s->l1rz),
+      (const double*)s->l1rr, s->S, s->rr_hist, s->rz_hist, s->pAp_hist);
+  HIP_CHECK(hipGetLastError());
+}
+
+// one loop body
+static void pcg_body(sb_pcg* s, int k)
+{
+  const uint32_t n = s->nr;
+  const int* stop  = &s->S->stop;
+  if (n) {
+    const dim3 gridV(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * 2u, (n / 2 + 1 + 1023u) / 1024u)));
+    hipLaunchKernelGGL(pcg_update_p_k, gridV, dim3(1024), 0, g.stream, n, (const double*)s->z, s->p, s->x, (const PcgScalars*)s->S,
+        k == 1 ? 1 : 0);
+    HIP_CHECK(hipGetLastError());
+  }
+  if (spmv_dot_kind(s->A)) {
+    launch_spmv(s->A, s->p, s->Ap, s->l1pAp, stop);
+  } else {
+    launch_spmv(s->A, s->p, s->Ap, nullptr, stop);
+    if (n) {
+      hipLaunchKernelGGL(dot_l1_k, dim3(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * 2u, (s->nGroups + 15u) / 16u))),
+          dim3(1024), 0, g.stream, n, (const double*)s->p, (const double*)s->Ap, s->l1pAp, stop);
+      HIP_CHECK(hipGetLastError());
+    }
+  }
+  pcg_scalar_launch<2>(s);
+  if (n) {
+    hipLaunchKernelGGL(pcg_update_r_k<0>, dim3(pcg_update_r_grid(n)), dim3(1024), 0, g.stream, n, (const double*)s->Ap,
+        (const double*)s->r, s->r, (const double*)s->dinv, s->z, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
+    HIP_CHECK(hipGetLastError());
+  }
+  pcg_scalar_launch<1>(s);
+}
+
+void sb_pcg_start(sb_pcg* s, int itermax, double eps)
+{
+  need_init();
+  pcg_need_tree("sb_pcg_start");
+  if (itermax + 2 > s->hist_cap) {
+    sb_free(s->rr_hist), sb_free(s->rz_hist), sb_free(s->pAp_hist);
+    s->hist_cap = itermax + 2;
+    const size_t hb = (size_t)s->hist_cap * sizeof(double);
+    s->rr_hist = (double*)sb_malloc(hb), s->rz_hist = (double*)sb_malloc(hb), s->pAp_hist = (double*)sb_malloc(hb);
+  }
+  PcgScalars h;
+  memset(&h, 0, sizeof h);
+  h.itermax = itermax, h.eps = eps, h.hist_cap = s->hist_cap;
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  HIP_CHECK(hipMemcpy(s->S, &h, sizeof h, hipMemcpyHostToDevice));
+  // prologue: x0 = 0, p = 1.0 x + 0.0 x = 0, Ap = A p, r = 1.0 b + (-1.0) Ap, z = r o dinv, r.r, r.z, the loop test for k = 1
+  HIP_CHECK(hipMemsetAsync(s->x, 0, (size_t)s->nr * sizeof(double), g.stream));
+  HIP_CHECK(hipMemsetAsync(s->p, 0, (size_t)s->nc * sizeof(double), g.stream));
+  launch_spmv(s->A, s->p, s->Ap, nullptr, nullptr);
+  if (s->nr) {
+    hipLaunchKernelGGL(pcg_update_r_k<1>, dim3(pcg_update_r_grid(s->nr)), dim3(1024), 0, g.stream, s->nr, (const double*)s->Ap,
+        (const double*)s->b, s->r, (const double*)s->dinv, s->z, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
+    HIP_CHECK(hipGetLastError());
+  }
+  pcg_scalar_launch<0>(s);
+  s->k_next = 1, s->started = true, s->loop_ms = 0.f;
+  HIP_CHECK(hipEventRecord(s->evLoop0, g.stream));
+}
+
+void sb_pcg_run_iters(sb_pcg* s, int iters)
+{
+  need_init();
+  if (!s->started) SB_FATAL("sb_pcg_run_iters before sb_pcg_start");
+  for (int i = 0; i < iters; i++) pcg_body(s, s->k_next++);
+}
+
+static PcgScalars pcg_control(const sb_pcg* s)
+{
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  PcgScalars h;
+  HIP_CHECK(hipMemcpy(&h, s->S, sizeof h, hipMemcpyDeviceToHost));
+  return h;
+}
+
+int sb_pcg_finish(sb_pcg* s)
+{
+  need_init();
+  if (!s->started) SB_FATAL("sb_pcg_finish before sb_pcg_start");
+  HIP_CHECK(hipEventRecord(s->evLoop1, g.stream));
+  if (s->nr) { // the x update the last body left to "the next p update": nobody comes after it
+    hipLaunchKernelGGL(pcg_x_finalize, dim3(stream_grid(s->nr, 256)), dim3(256), 0, g.stream, s->nr, s->x, (const double*)s->p,
+        (const PcgScalars*)s->S);
+    hipLaunchKernelGGL(pcg_clear_pending, dim3(1), dim3(1), 0, g.stream, s->S);
+    HIP_CHECK(hipGetLastError());
+  }
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  HIP_CHECK(hipEventElapsedTime(&s->loop_ms, s->evLoop0, s->evLoop1));
+  s->started = false;
+  return pcg_control(s).iters + 1; // the value of k when the for loop exits
+}
+
+int sb_pcg_solve(sb_pcg* s, int itermax, double eps)
+{
+  sb_pcg_start(s, itermax, eps);
+  sb_pcg_run_iters(s, itermax > 1 ? itermax - 1 : 0);
+  return sb_pcg_finish(s);
+}
+
+int sb_pcg_history(const sb_pcg* s, double* rr_out, int rr_cap, double* rz_out, int rz_cap, double* pAp_out, int pAp_cap, int* n_pAp)
+{
+  need_init();
+  const PcgScalars h = pcg_control(s);
+  int nrr = std::min(std::min(h.n_rr, s->hist_cap), std::min(rr_cap, rz_cap)), npa = std::min(std::min(h.n_pAp, s->hist_cap), pAp_cap);
+  if (nrr > 0) {
+    HIP_CHECK(hipMemcpy(rr_out, s->rr_hist, (size_t)nrr * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(rz_out, s->rz_hist, (size_t)nrr * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  if (npa > 0) HIP_CHECK(hipMemcpy(pAp_out, s->pAp_hist, (size_t)npa * sizeof(double), hipMemcpyDeviceToHost));
+  if (n_pAp) *n_pAp = npa > 0 ? npa : 0;
+  return nrr > 0 ? nrr : 0;
+}
+
+static void pcg_to_host_orig(const sb_pcg* s, const double* v_dev, double* v_host)
+{
+  if (s->nr == 0) return;
+  double* tmp = scratch_ws(1, s->nr);
+  sb_unpermute(s->A, v_dev, tmp);
+  sb_d2h(v_host, tmp, (size_t)s->nr * sizeof(double));
+}
+void sb_pcg_solution(const sb_pcg* s, double* x_host)
+{
+  need_init();
+  pcg_to_host_orig(s, s->x, x_host);
+}
+void sb_pcg_dinv(const sb_pcg* s, double* dinv_host)
+{
+  need_init();
+  pcg_to_host_orig(s, s->dinv, dinv_host);
+}
+
+// max|x - xexact| (solverCheckResidual, src/CGSolver.c:40-60); 0.0 without an exact solution
+double sb_pcg_check_residual(const sb_pcg* s)
+{
+  need_init();
+  if (!s->xexact || s->nr == 0) return 0.0;
+  const uint32_t blocks = stream_grid(s->nr, 256);
+  double* q             = scratch_partials(blocks);
+  hipLaunchKernelGGL(max_abs_diff_partials, dim3(blocks), dim3(256), 0, g.stream, s->nr, (const double*)s->x, (const double*)s->xexact, q);
+  HIP_CHECK(hipGetLastError());
+  std::vector<double> h(blocks);
+  sb_d2h(h.data(), q, blocks * sizeof(double));
+  double mx = 0.0;
+  for (double v : h)
+    if (v > mx) mx = v;
+  return mx;
+}
+
+double sb_pcg_loop_ms(const sb_pcg* s) { return (double)s->loop_ms; }
+
+// stop, stop_next, iters, n_rr (= entries of rz too), n_pAp of the device control block
+void sb_pcg_counters(const sb_pcg* s, int out[5])
+{
+  const PcgScalars h = pcg_control(s);
+  out[0] = h.stop, out[1] = h.stop_next, out[2] = h.iters, out[3] = h.n_rr, out[4] = h.n_pAp;
+}

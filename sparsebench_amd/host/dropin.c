@@ -62,6 +62,9 @@ int solveCGBatch(Comm* comm, Parameter* param, Matrix* m, int nrhs)
   return sbh_solve_cg_batch(comm, param, m->dev, m->nr, m->rowNnz, m->startRow, nrhs);
 }
 
+/* Jacobi-preconditioned CG on this build's Matrix (the _sp libraries: "PCG: double precision only") */
+int solvePCG(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_pcg(comm, param, m->dev, m->nr, m->rowNnz); }
+
 void sbh_print_banner(Comm* c, const char* fmt);
 void commPrintBanner(Comm* c) { sbh_print_banner(c, FMT); } /* src/comm.c:185-250: names the build's format */
 

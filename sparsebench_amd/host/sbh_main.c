@@ -17,7 +17,7 @@
 #include "sbhip.h"
 #include "sparsebench/sparsebench.h"
 
-typedef enum { CG = 0, SPMV, GMRES, CHEBFD } bench_type;
+typedef enum { CG = 0, SPMV, GMRES, CHEBFD, PCG } bench_type;
 
 static const char* kHelp =
     "Usage: sparseBench [options]\n\n"
@@ -26,7 +26,7 @@ static const char* kHelp =
     "  -f <parameter file>   Load options from a parameter file\n"
     "  -c <file name>   Convert MM matrix to binary matrix file (.bmx).\n"
     "  -m <matrix>   Load a matrix market (.mtx) or binary (.bmx) file\n"
-    "  -t <bench type>   Benchmark type, can be cg, spmv, or gmres. Default cg.\n"
+    "  -t <bench type>   Benchmark type, can be cg, spmv, gmres, or pcg (CG with the Jacobi preconditioner). Default cg.\n"
     "  -r <int>   GMRES restart length. Default 30.\n"
     "  -n <int>   Number of right-hand sides for -t cg. Default 1.\n"
     "  -x <int>   Size in x for generated matrix, ignored if MM file is loaded. Default 100.\n"
@@ -67,6 +67,13 @@ int main(int argc, char** argv)
         return 1;
 #else
         type = GMRES;
+#endif
+      } else if (strcmp(optarg, "pcg") == 0) {
+#if PRECISION == 1
+        fprintf(stderr, "PCG: double precision only\n");
+        return 1;
+#else
+        type = PCG;
 #endif
       } else {
         printf("Unknown solver type %s\n", optarg);
@@ -126,6 +133,9 @@ int main(int argc, char** argv)
   } else if (type == GMRES) {
     if (commIsMaster(&comm)) printf("Test type: GMRES\n");
     k = solveGMRES(&comm, &param, &sm, restart);
+  } else if (type == PCG) {
+    if (commIsMaster(&comm)) printf("Test type: PCG\n");
+    k = solvePCG(&comm, &param, &sm);
   } else {
     if (commIsMaster(&comm)) printf("Test type: SPMVM\n");
     /* exactly the reference's loop (src/main.c:205-215): vectors from the allocation hook, filled by host loops, spMVM under

@@ -283,6 +283,59 @@ int sbh_solve_cg_batch(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT n
 #endif
 }
 
+/* ---- solvePCG ---------------------------------------------------------------------------- */
+/* solveCG with the Jacobi preconditioner (sb_pcg_*).  The lines solveCG prints while iterating are printed
+ * afterwards from the recorded r.r history, indexed as solveCG's own. */
+int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
+{
+#if PRECISION == 1
+  (void)comm, (void)param, (void)dev_matrix, (void)nr, (void)rowNnz;
+  fprintf(stderr, "PCG: double precision only\n");
+  exit(EXIT_FAILURE);
+#else
+  const int itermax   = param->itermax;
+  const int generated = strcmp(param->filename, "generate") == 0 || strcmp(param->filename, "generate7P") == 0;
+  double* b           = (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double));
+  double* xexact      = generated ? (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double)) : NULL;
+  for (CG_UINT i = 0; i < nr; i++) { /* initVectors, src/CGSolver.c:25-36 */
+    if (generated) {
+      b[i]      = 27.0 - ((double)((int)rowNnz[i] - 1));
+      xexact[i] = 1.0;
+    } else {
+      b[i] = 1.0;
+    }
+  }
+  sb_pcg* s     = sb_pcg_create((const sb_matrix*)dev_matrix, NULL, b, xexact, NULL);
+  const int k   = sb_pcg_solve(s, itermax, param->eps);
+  const int cap = itermax + 2;
+  double* rr    = (double*)malloc((size_t)cap * sizeof(double));
+  double* rz    = (double*)malloc((size_t)cap * sizeof(double));
+  double* pAp   = (double*)malloc((size_t)cap * sizeof(double));
+  int nPAp      = 0;
+  const int nRr = sb_pcg_history(s, rr, cap, rz, cap, pAp, cap, &nPAp);
+  int printFreq = itermax / 10; /* :85-91 */
+  if (printFreq > 50) printFreq = 50;
+  if (printFreq < 1) printFreq = 1;
+  if (commIsMaster(comm)) {
+    printf("Initial Residual = %E\n", nRr > 0 ? sqrt(rr[0]) : 0.0);
+    for (int j = 1; j < k; j++)
+      if (j % printFreq == 0 || j + 1 == itermax) {
+        const int idx = j == 1 ? 0 : j - 1;
+        if (idx < nRr) printf("Iteration = %d Residual = %E\n", j, sqrt(rr[idx]));
+      }
+    printf("Solution performed %d iterations and took %.2fs\n", k, 1e-3 * sb_pcg_loop_ms(s));
+  }
+  if (xexact) { /* solverCheckResidual, :40-60 */
+    const double diff = sb_pcg_check_residual(s);
+    if (commIsMaster(comm)) printf("Difference between computed and exact  = %f\n", diff);
+  }
+  _t[SPMVM] += 1e-3 * sb_pcg_loop_ms(s); /* the loop's kernels overlap regions: the table's SpMV row carries the loop */
+  sb_pcg_free(s);
+  free(rr), free(rz), free(pAp), free(b), free(xexact);
+  return k;
+#endif
+}
+
 /* ---- profiler table: src/profiler.c:11-141 ----------------------------------------------- */
 static const char* const kLabel[NUMREGIONS] = { "waxpby:  ", "spMVM:   ", "ddot:    ", "comm:    " };
 static double g_words[NUMREGIONS], g_flops[NUMREGIONS];

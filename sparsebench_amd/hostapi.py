@@ -513,3 +513,79 @@ class BatchCG:
         if self.ptr:
             self.L.sb_cgb_free(self.ptr)
             self.ptr = None
+
+
+class PCG:
+    """solveCG with a diagonal preconditioner put back (sb_pcg_*): z = r * dinv, alpha = r.z / p.Ap,
+    beta = r.z / (r.z)_old, the loop test on sqrt(r.r).  dinv None: Jacobi, 1 / diag(A); else nr finite positive doubles in
+    original row order (all 1.0: `CG` in the tree order bit for bit).  Double precision, one rank, tree dot order."""
+
+    def __init__(self, problem, dinv=None):
+        if getattr(problem, "precision", "double") != "double":
+            raise ValueError("PCG: double precision only (the problem was built with precision=%r)" % (problem.precision,))
+        self.L = capi.load()
+        self.problem = problem
+        b, xe = problem.rhs()
+        if dinv is not None:
+            dinv = np.ascontiguousarray(dinv, dtype=np.float64)
+            if dinv.shape != (problem.nr,):
+                raise ValueError("dinv must hold nr = %d doubles, got shape %r" % (problem.nr, dinv.shape))
+        self.ptr = self.L.sb_pcg_create(problem.matrix, problem.halo, b.ctypes.data_as(vp),
+                                        xe.ctypes.data_as(vp) if xe is not None else None,
+                                        dinv.ctypes.data_as(vp) if dinv is not None else None)
+        self.itermax = 0
+
+    def launches_per_body(self):
+        return self.L.sb_pcg_launches_per_body(self.ptr)
+
+    def solve(self, itermax=150, eps=0.0):
+        self.itermax = itermax
+        return self.L.sb_pcg_solve(self.ptr, itermax, eps)
+
+    def start(self, itermax, eps=0.0):
+        """prologue only; follow with run_iters() and finish()"""
+        self.itermax = itermax
+        self.L.sb_pcg_start(self.ptr, itermax, eps)
+
+    def run_iters(self, iters):
+        self.L.sb_pcg_run_iters(self.ptr, int(iters))
+
+    def finish(self):
+        return self.L.sb_pcg_finish(self.ptr)
+
+    def history(self):
+        """rr, rz, pAp"""
+        cap = self.itermax + 2
+        rr, rz, pap = np.zeros(cap), np.zeros(cap), np.zeros(cap)
+        npap = C.c_int(0)
+        nrr = self.L.sb_pcg_history(self.ptr, rr.ctypes.data_as(vp), cap, rz.ctypes.data_as(vp), cap, pap.ctypes.data_as(vp), cap,
+                                    C.byref(npap))
+        return rr[:nrr].copy(), rz[:nrr].copy(), pap[:npap.value].copy()
+
+    def solution(self):
+        """x in original row order"""
+        x = np.empty(self.problem.nr)
+        self.L.sb_pcg_solution(self.ptr, x.ctypes.data_as(vp))
+        return x
+
+    def check_residual(self):
+        return self.L.sb_pcg_check_residual(self.ptr)
+
+    def dinv(self):
+        """the preconditioner in use, original row order"""
+        d = np.empty(self.problem.nr)
+        self.L.sb_pcg_dinv(self.ptr, d.ctypes.data_as(vp))
+        return d
+
+    def counters(self):
+        out = (C.c_int * 5)()
+        self.L.sb_pcg_counters(self.ptr, out)
+        return dict(zip(["stop", "stop_next", "iters", "n_rr", "n_pAp"], list(out)))
+
+    def loop_ms(self):
+        return self.L.sb_pcg_loop_ms(self.ptr)
+
+    def free(self):
+        if self.ptr:
+            self.L.sb_pcg_free(self.ptr)
+            self.ptr = None

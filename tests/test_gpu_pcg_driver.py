@@ -1,0 +1,96 @@
+"""`-t pcg` from the benchmark drivers and solvePCG from both drop-in libraries (a C caller written against
+include/sparsebench/sparsebench.h only), against the CPU restatement of the PCG contract (tests/pcg_ref.py): on the scaled
+stencil from a Matrix Market file, where Jacobi decides the iteration count, and on the generated 16^3 stencil."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import pcg_ref as ref
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "sparsebench_amd", "lib")
+BIN = os.path.join(ROOT, "sparsebench_amd", "bin")
+ITERMAX = 150
+EPS = 1e-9
+
+
+@pytest.fixture(scope="module")
+def wants(tmp_path_factory):
+    """restatement runs in the drivers' formats: CRS and Sell-64-1 (the same order: sigma = 1)"""
+    tmp = tmp_path_factory.mktemp("pcg_driver")
+    out = {"path": ref.scaled_path(16, tmp)}
+    for key, matrix in (("scaled", ("scaled", 16)), ("hpcg", ("hpcg", 16))):
+        g = ref.gmatrix(matrix, tmp)
+        out[key] = ref.solve(ref.operator(g), g.rhs(), ref.jacobi(g), ITERMAX, EPS)
+        assert 1 < out[key]["k"] < ITERMAX
+        g.free()
+    return out
+
+
+def run(cmd):
+    return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+
+
+def check_lines(txt, w, itermax):
+    freq = max(1, min(50, itermax // 10))
+    assert "Initial Residual = %E" % np.sqrt(w["rr"][0]) in txt
+    shown = 0
+    for j in range(1, w["k"]):
+        if j % freq == 0 or j + 1 == itermax:
+            assert "Iteration = %d Residual = %E" % (j, np.sqrt(w["rr"][0 if j == 1 else j - 1])) in txt, j
+            shown += 1
+    assert shown >= 1 and len(re.findall(r"^Iteration = ", txt, re.M)) == shown
+    assert re.search(r"^Solution performed %d iterations and took \d+\.\d\ds$" % w["k"], txt, re.M)
+
+
+@pytest.mark.parametrize("exe", ["sparseBench-CRS-HIP", "sparseBench-SCS-HIP"])
+def test_driver_runs_pcg(gpu, exe, wants):
+    for key, args in (("scaled", ["-m", wants["path"]]), ("hpcg", ["-x", "16", "-y", "16", "-z", "16"])):
+        out = run([os.path.join(BIN, exe), "-t", "pcg", "-i", str(ITERMAX), "-e", repr(EPS)] + args)
+        assert out.returncode == 0, out.stderr.decode()[-2000:]
+        txt = out.stdout.decode()
+        assert "Test type: PCG" in txt
+        check_lines(txt, wants[key], ITERMAX)
+        assert ("Difference between computed and exact  = " in txt) == (key == "hpcg")
+        assert "Function   Rate(MB/s)  Rate(MFlop/s)  Walltime(s)" in txt
+
+
+def test_driver_help_and_refusals(gpu):
+    crs = os.path.join(BIN, "sparseBench-CRS-HIP")
+    assert re.search(r"-t <bench type>.*\bpcg\b", run([crs, "-h"]).stdout.decode())
+    size = ["-x", "8", "-y", "8", "-z", "8", "-i", "10"]
+    for exe in ("sparseBench-CRS-HIP-SP", "sparseBench-SCS-HIP-SP"):
+        out = run([os.path.join(BIN, exe), "-t", "pcg"] + size)
+        assert out.returncode == 1 and "PCG: double precision only" in out.stderr.decode()
+    out = run([crs, "-t", "cheb"] + size)
+    assert out.returncode == 1 and "Unknown solver type cheb" in out.stdout.decode()
+    out = run([crs, "-t", "pcg", "-n", "2"] + size)
+    assert out.returncode == 1 and "-t cg only" in out.stderr.decode()
+
+
+@pytest.mark.parametrize("fmt", ["CRS", "SCS"])
+def test_c_caller_of_solvePCG(gpu, fmt, wants, tmp_path):
+    exe = os.path.join(str(tmp_path), "pcg_driver_%s" % fmt)
+    subprocess.check_call(["gcc", "-std=gnu11", "-O1", "-Wall", "-D" + fmt, "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "c", "pcg_driver.c"), "-o", exe, "-L" + LIB,
+                           "-lsparsebench_%s" % fmt.lower(), "-lsparsebench_host", "-lsbhip", "-Wl,-rpath," + LIB, "-lm"])
+    for key, arg in (("scaled", wants["path"]), ("hpcg", "16")):
+        out = run([exe, arg, str(ITERMAX), repr(EPS)])
+        assert out.returncode == 0, out.stderr.decode()[-2000:]
+        txt = out.stdout.decode()
+        assert int(re.search(r"^k (\d+)$", txt, re.M).group(1)) == wants[key]["k"]
+        check_lines(txt, wants[key], ITERMAX)
+
+
+@pytest.mark.parametrize("fmt", ["CRS", "SCS"])
+def test_sp_library_refuses_solvePCG(gpu, fmt, tmp_path):
+    exe = os.path.join(str(tmp_path), "pcg_driver_%s_sp" % fmt)
+    subprocess.check_call(["gcc", "-std=gnu11", "-O1", "-Wall", "-DPRECISION=1", "-D" + fmt, "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "c", "pcg_driver.c"), "-o", exe, "-L" + LIB,
+                           "-lsparsebench_%s_sp" % fmt.lower(), "-lsparsebench_host_sp", "-lsbhip", "-Wl,-rpath," + LIB, "-lm"])
+    out = run([exe, "8", "10", "0.0"])
+    assert out.returncode == 1 and "PCG: double precision only" in out.stderr.decode()
