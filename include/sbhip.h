@@ -559,6 +559,56 @@ void sb_pcg_update_r_native(uint32_t n, double nalpha, const double* Ap_dev, dou
  * and strides over them by the number of waves in the grid */
 void sb_pcg_update_r_launch(uint32_t n, uint32_t out[3]);
 
+/* ---- BiCGStab with a diagonal preconditioner ----------------------------------------------------------- */
+/* Right-preconditioned BiCGStab for matrices that need not be symmetric: two SpMVs per body, about ten vectors whatever the
+ * iteration count, no restart.  x0 = 0, rhat = b; the loop test is on sqrt(r.r) alone (no exit on ||s||); rho = 0, rhat.v = 0
+ * or t.t = 0 is NOT detected: the quotients become Inf or NaN and the loop runs on to itermax, as CG's does on a matrix it
+ * cannot solve.  Double precision, ONE rank, tree dot order; a halo with more than one rank, a single-precision matrix, the
+ * seq order, a Jacobi row whose diagonal is zero or not finite and a caller's dinv entry that is zero or not finite are fatal
+ * errors with file:line.  The SpMV is the one the matrix's kernel mode selects (sb_matrix_use_packed), without a fused dot. */
+typedef struct sb_bicgstab sb_bicgstab;
+/* b_host, xexact_host (or NULL) as for sb_cg_create.  precond 0: none (dinv = 1.0 everywhere, dinv_host ignored); 1: Jacobi,
+ * dinv_i = 1.0 / d_i with d by sb_matrix_diagonal's rule (dinv_host ignored); 2: dinv_host, nr finite non-zero doubles (either
+ * sign) in ORIGINAL row order.  halo: NULL or a one-rank plan. */
+sb_bicgstab* sb_bicgstab_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int precond,
+                                const double* dinv_host);
+void sb_bicgstab_free(sb_bicgstab* s);
+int sb_bicgstab_solve(sb_bicgstab* s, int itermax, double eps); /* blocking; returns k of "for (k = 1; k < itermax && normr > eps; k++)" */
+/* The same in three steps: bodies enqueued past the exit are no-ops, nothing is read back between bodies; a handle can be
+ * solved again. */
+void sb_bicgstab_start(sb_bicgstab* s, int itermax, double eps);
+void sb_bicgstab_run_iters(sb_bicgstab* s, int iters);
+int sb_bicgstab_finish(sb_bicgstab* s);
+/* which 0: r.r, 1: rho = rhat.r (entry 0 of both is the prologue's, then one per body); 2: rhat.v, 3: t.s, 4: t.t (one per
+ * body).  Copies at most cap entries to out and returns their number. */
+int sb_bicgstab_history(const sb_bicgstab* s, int which, double* out, int cap);
+void sb_bicgstab_solution(const sb_bicgstab* s, double* x_host);   /* original row order */
+double sb_bicgstab_check_residual(const sb_bicgstab* s);           /* max|x - xexact|, 0.0 without an exact solution */
+void sb_bicgstab_dinv(const sb_bicgstab* s, double* dinv_host);    /* the preconditioner in use, original row order */
+/* 10 for every format: p update | SpMV | rhat.v | alpha | s update | SpMV | t.s, t.t | omega | x, r update | beta */
+int sb_bicgstab_launches_per_body(const sb_bicgstab* s);
+double sb_bicgstab_loop_ms(const sb_bicgstab* s); /* GPU milliseconds between the end of sb_bicgstab_start and sb_bicgstab_finish */
+void sb_bicgstab_counters(const sb_bicgstab* s, int out[5]); /* stop, iters, n_rr (= n_rho), n_rv, n_ts (= n_tt) of the control block */
+/* Test entries for the fused kernels on caller-supplied device vectors of n doubles (16-byte aligned), scalars from the host;
+ * blocking.  l1 arrays: ceil(n/256) level-1 values.
+ *   update_p:  p = r + beta * (p - omega * v), ph = p o dinv
+ *   update_s:  s = r - alpha * v, sh = s o dinv (s_dev may be r_dev)
+ *   dot2:      pair != 0: level-1 values of a.b and of a.a; pair == 0: of a.b alone (l1_aa_dev untouched)
+ *   update_xr: x = (x + alpha * ph) + omega * sh, r = s - omega * t (r_dev may be s_dev), level-1 values of rhat.r and r.r
+ *   reduce:    the scalar step's totals of m level-1 values each: out[0] of l1_a_dev, out[1] of l1_b_dev */
+void sb_bicgstab_update_p_native(uint32_t n, double beta, double omega, const double* r_dev, double* p_dev, const double* v_dev,
+                                 const double* dinv_dev, double* ph_dev);
+void sb_bicgstab_update_s_native(uint32_t n, double alpha, const double* r_dev, const double* v_dev, const double* dinv_dev,
+                                 double* s_dev, double* sh_dev);
+void sb_bicgstab_dot2_native(uint32_t n, int pair, const double* a_dev, const double* b_dev, double* l1_ab_dev, double* l1_aa_dev);
+void sb_bicgstab_update_xr_native(uint32_t n, double alpha, double omega, double* x_dev, const double* ph_dev, const double* sh_dev,
+                                  const double* s_dev, const double* t_dev, const double* rhat_dev, double* r_dev,
+                                  double* l1_rho_dev, double* l1_rr_dev);
+void sb_bicgstab_reduce_native(uint32_t m, const double* l1_a_dev, const double* l1_b_dev, double out[2]);
+/* the launch of the four streaming kernels over n rows: {workgroups, threads per workgroup, compute units of the device}; a
+ * wave owns whole 256-row groups and strides over them by the number of waves in the grid */
+void sb_bicgstab_launch(uint32_t n, uint32_t out[3]);
+
 /* debug/measurement: raw streaming-read rate of the device in GB/s (DESIGN.md uses it
  * as the measured ceiling next to the 8 TB/s spec) */
 double sb_debug_stream_read_gbs(size_t bytes, int reps);

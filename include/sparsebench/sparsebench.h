@@ -258,6 +258,9 @@ int sbh_solve_cg_batch(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT n
                        int nrhs);
 /* CG with the Jacobi preconditioner dinv = 1 / diag(A) (sb_pcg_*, sbhip.h): prints what solveCG prints; double precision, one rank */
 int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz);
+/* BiCGStab with the Jacobi right preconditioner (sb_bicgstab_*, sbhip.h) for matrices that need not be symmetric: prints what
+ * solveCG prints; double precision, one rank */
+int sbh_solve_bicgstab(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz);
 
 /* ---- the hot path: src/solver.h:11-25, src/matrix.h:57 -------------------------------- */
 #if defined(CRS) || defined(SCS)
@@ -279,6 +282,9 @@ int solveCGBatch(Comm* comm, Parameter* param, Matrix* m, int nrhs);
  * A matrix row without a finite positive diagonal entry ends the process with a message.  One rank, tree dot order; the
  * single-precision libraries export it too and end the process with "PCG: double precision only". */
 int solvePCG(Comm* comm, Parameter* param, Matrix* m);
+/* Jacobi-preconditioned BiCGStab: the short-recurrence solver for matrices that are not symmetric; returns k as
+ * solveCG does.  The single-precision libraries export it too and end the process with "BiCGStab: double precision only". */
+int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m);
 /* x (nc entries) and y (nr entries) may be device or host pointers; host pointers are
  * staged through HBM (correct, slow: use sb_malloc'ed vectors on the hot path) */
 void spMVM(Matrix* m, const CG_FLOAT* restrict x, CG_FLOAT* restrict y);

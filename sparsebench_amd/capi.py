@@ -51,6 +51,10 @@ SYMBOLS = [
     "sb_matrix_diagonal", "sb_pcg_create", "sb_pcg_free", "sb_pcg_solve", "sb_pcg_start", "sb_pcg_run_iters", "sb_pcg_finish",
     "sb_pcg_history", "sb_pcg_solution", "sb_pcg_check_residual", "sb_pcg_dinv", "sb_pcg_launches_per_body", "sb_pcg_loop_ms",
     "sb_pcg_counters", "sb_pcg_update_r_native", "sb_pcg_update_r_launch",
+    "sb_bicgstab_create", "sb_bicgstab_free", "sb_bicgstab_solve", "sb_bicgstab_start", "sb_bicgstab_run_iters", "sb_bicgstab_finish",
+    "sb_bicgstab_history", "sb_bicgstab_solution", "sb_bicgstab_check_residual", "sb_bicgstab_dinv", "sb_bicgstab_launches_per_body",
+    "sb_bicgstab_loop_ms", "sb_bicgstab_counters", "sb_bicgstab_update_p_native", "sb_bicgstab_update_s_native",
+    "sb_bicgstab_dot2_native", "sb_bicgstab_update_xr_native", "sb_bicgstab_reduce_native", "sb_bicgstab_launch",
 ]
 
 _lib = None
@@ -270,6 +274,26 @@ def load():
         "sb_pcg_counters": (None, [vp, vp]),
         "sb_pcg_update_r_native": (None, [u32, C.c_double, vp, vp, vp, vp, vp, vp]),
         "sb_pcg_update_r_launch": (None, [u32, vp]),
+        # BiCGStab with a diagonal preconditioner
+        "sb_bicgstab_create": (vp, [vp, vp, vp, vp, C.c_int, vp]),
+        "sb_bicgstab_free": (None, [vp]),
+        "sb_bicgstab_solve": (C.c_int, [vp, C.c_int, C.c_double]),
+        "sb_bicgstab_start": (None, [vp, C.c_int, C.c_double]),
+        "sb_bicgstab_run_iters": (None, [vp, C.c_int]),
+        "sb_bicgstab_finish": (C.c_int, [vp]),
+        "sb_bicgstab_history": (C.c_int, [vp, C.c_int, vp, C.c_int]),
+        "sb_bicgstab_solution": (None, [vp, vp]),
+        "sb_bicgstab_check_residual": (C.c_double, [vp]),
+        "sb_bicgstab_dinv": (None, [vp, vp]),
+        "sb_bicgstab_launches_per_body": (C.c_int, [vp]),
+        "sb_bicgstab_loop_ms": (C.c_double, [vp]),
+        "sb_bicgstab_counters": (None, [vp, vp]),
+        "sb_bicgstab_update_p_native": (None, [u32, C.c_double, C.c_double, vp, vp, vp, vp, vp]),
+        "sb_bicgstab_update_s_native": (None, [u32, C.c_double, vp, vp, vp, vp, vp]),
+        "sb_bicgstab_dot2_native": (None, [u32, C.c_int, vp, vp, vp, vp]),
+        "sb_bicgstab_update_xr_native": (None, [u32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sb_bicgstab_reduce_native": (None, [u32, vp, vp, vp]),
+        "sb_bicgstab_launch": (None, [u32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -26,6 +26,7 @@
 #include "gmres.hip.h"
 #include "batch.hip.h"
 #include "pcg.hip.h"
+#include "bicgstab.hip.h"
 
 #include <algorithm>
 #include <iterator>
@@ -677,3 +678,4 @@ void sb_event_destroy(void* ev) { HIP_CHECK(hipEventDestroy((hipEvent_t)ev)); }
 #include "sbhip_gmres.inc.h"
 #include "sbhip_cgb.inc.h"
 #include "sbhip_pcg.inc.h"
+#include "sbhip_bicgstab.inc.h"

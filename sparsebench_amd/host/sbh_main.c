@@ -17,7 +17,7 @@
 #include "sbhip.h"
 #include "sparsebench/sparsebench.h"
 
-typedef enum { CG = 0, SPMV, GMRES, CHEBFD, PCG } bench_type;
+typedef enum { CG = 0, SPMV, GMRES, CHEBFD, PCG, BICGSTAB } bench_type;
 
 static const char* kHelp =
     "Usage: sparseBench [options]\n\n"
@@ -26,7 +26,8 @@ static const char* kHelp =
     "  -f <parameter file>   Load options from a parameter file\n"
     "  -c <file name>   Convert MM matrix to binary matrix file (.bmx).\n"
     "  -m <matrix>   Load a matrix market (.mtx) or binary (.bmx) file\n"
-    "  -t <bench type>   Benchmark type, can be cg, spmv, gmres, or pcg (CG with the Jacobi preconditioner). Default cg.\n"
+    "  -t <bench type>   Benchmark type, can be cg, spmv, gmres, pcg (CG with the Jacobi preconditioner),\n"
+    "                    or bicgstab (BiCGStab with the Jacobi preconditioner: non-symmetric matrices). Default cg.\n"
     "  -r <int>   GMRES restart length. Default 30.\n"
     "  -n <int>   Number of right-hand sides for -t cg. Default 1.\n"
     "  -x <int>   Size in x for generated matrix, ignored if MM file is loaded. Default 100.\n"
@@ -74,6 +75,13 @@ int main(int argc, char** argv)
         return 1;
 #else
         type = PCG;
+#endif
+      } else if (strcmp(optarg, "bicgstab") == 0) {
+#if PRECISION == 1
+        fprintf(stderr, "BiCGStab: double precision only\n");
+        return 1;
+#else
+        type = BICGSTAB;
 #endif
       } else {
         printf("Unknown solver type %s\n", optarg);
@@ -136,6 +144,9 @@ int main(int argc, char** argv)
   } else if (type == PCG) {
     if (commIsMaster(&comm)) printf("Test type: PCG\n");
     k = solvePCG(&comm, &param, &sm);
+  } else if (type == BICGSTAB) {
+    if (commIsMaster(&comm)) printf("Test type: BiCGStab\n");
+    k = solveBiCGStab(&comm, &param, &sm);
   } else {
     if (commIsMaster(&comm)) printf("Test type: SPMVM\n");
     /* exactly the reference's loop (src/main.c:205-215): vectors from the allocation hook, filled by host loops, spMVM under

@@ -336,6 +336,56 @@ int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, co
 #endif
 }
 
+/* ---- solveBiCGStab ----------------------------------------------------------------------- */
+/* BiCGStab with the Jacobi right preconditioner (sb_bicgstab_*) for matrices that need not be symmetric.  The
+ * lines solveCG prints while iterating are printed afterwards from the recorded r.r history: "Iteration = j" shows the
+ * residual iteration j starts from, sqrt(rr[j - 1]), as solveCG and solvePCG do. */
+int sbh_solve_bicgstab(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
+{
+#if PRECISION == 1
+  (void)comm, (void)param, (void)dev_matrix, (void)nr, (void)rowNnz;
+  fprintf(stderr, "BiCGStab: double precision only\n");
+  exit(EXIT_FAILURE);
+#else
+  const int itermax   = param->itermax;
+  const int generated = strcmp(param->filename, "generate") == 0 || strcmp(param->filename, "generate7P") == 0;
+  double* b           = (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double));
+  double* xexact      = generated ? (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double)) : NULL;
+  for (CG_UINT i = 0; i < nr; i++) { /* initVectors, src/CGSolver.c:25-36 */
+    if (generated) {
+      b[i]      = 27.0 - ((double)((int)rowNnz[i] - 1));
+      xexact[i] = 1.0;
+    } else {
+      b[i] = 1.0;
+    }
+  }
+  sb_bicgstab* s = sb_bicgstab_create((const sb_matrix*)dev_matrix, NULL, b, xexact, 1, NULL);
+  const int k    = sb_bicgstab_solve(s, itermax, param->eps);
+  const int cap  = itermax + 2;
+  double* rr     = (double*)malloc((size_t)cap * sizeof(double));
+  const int nRr  = sb_bicgstab_history(s, 0, rr, cap);
+  int printFreq  = itermax / 10; /* :85-91 */
+  if (printFreq > 50) printFreq = 50;
+  if (printFreq < 1) printFreq = 1;
+  if (commIsMaster(comm)) {
+    printf("Initial Residual = %E\n", nRr > 0 ? sqrt(rr[0]) : 0.0);
+    for (int j = 1; j < k; j++)
+      if (j % printFreq == 0 || j + 1 == itermax) {
+        if (j - 1 < nRr) printf("Iteration = %d Residual = %E\n", j, sqrt(rr[j - 1]));
+      }
+    printf("Solution performed %d iterations and took %.2fs\n", k, 1e-3 * sb_bicgstab_loop_ms(s));
+  }
+  if (xexact) { /* solverCheckResidual, :40-60 */
+    const double diff = sb_bicgstab_check_residual(s);
+    if (commIsMaster(comm)) printf("Difference between computed and exact  = %f\n", diff);
+  }
+  _t[SPMVM] += 1e-3 * sb_bicgstab_loop_ms(s); /* the loop's kernels overlap regions: the table's SpMV row carries the loop */
+  sb_bicgstab_free(s);
+  free(rr), free(b), free(xexact);
+  return k;
+#endif
+}
+
 /* ---- profiler table: src/profiler.c:11-141 ----------------------------------------------- */
 static const char* const kLabel[NUMREGIONS] = { "waxpby:  ", "spMVM:   ", "ddot:    ", "comm:    " };
 static double g_words[NUMREGIONS], g_flops[NUMREGIONS];

@@ -589,3 +589,87 @@ class PCG:
         if self.ptr:
             self.L.sb_pcg_free(self.ptr)
             self.ptr = None
+
+
+class BiCGStab:
+    """Right-preconditioned BiCGStab with a diagonal preconditioner (sb_bicgstab_*) for matrices that need not be
+    symmetric.  precond "none": dinv = 1.0 everywhere; "jacobi": 1 / diag(A); a `dinv` of nr finite non-zero doubles in original
+    row order selects the caller's (precond is then "caller").  Double precision, one rank, tree dot order."""
+
+    HISTORIES = ("rr", "rho", "rv", "ts", "tt")
+
+    def __init__(self, problem, precond="none", dinv=None):
+        if getattr(problem, "precision", "double") != "double":
+            raise ValueError("BiCGStab: double precision only (the problem was built with precision=%r)" % (problem.precision,))
+        if dinv is not None:
+            precond = "caller"
+        kinds = {"none": 0, "jacobi": 1, "caller": 2}
+        if precond not in kinds or (precond == "caller" and dinv is None):
+            raise ValueError("precond must be 'none' or 'jacobi', or pass dinv; got %r" % (precond,))
+        self.L = capi.load()
+        self.problem = problem
+        b, xe = problem.rhs()
+        if dinv is not None:
+            dinv = np.ascontiguousarray(dinv, dtype=np.float64)
+            if dinv.shape != (problem.nr,):
+                raise ValueError("dinv must hold nr = %d doubles, got shape %r" % (problem.nr, dinv.shape))
+        self.ptr = self.L.sb_bicgstab_create(problem.matrix, problem.halo, b.ctypes.data_as(vp),
+                                             xe.ctypes.data_as(vp) if xe is not None else None, kinds[precond],
+                                             dinv.ctypes.data_as(vp) if dinv is not None else None)
+        self.itermax = 0
+
+    def launches_per_body(self):
+        return self.L.sb_bicgstab_launches_per_body(self.ptr)
+
+    def solve(self, itermax=150, eps=0.0):
+        self.itermax = itermax
+        return self.L.sb_bicgstab_solve(self.ptr, itermax, eps)
+
+    def start(self, itermax, eps=0.0):
+        """prologue only; follow with run_iters() and finish()"""
+        self.itermax = itermax
+        self.L.sb_bicgstab_start(self.ptr, itermax, eps)
+
+    def run_iters(self, iters):
+        self.L.sb_bicgstab_run_iters(self.ptr, int(iters))
+
+    def finish(self):
+        return self.L.sb_bicgstab_finish(self.ptr)
+
+    def history(self):
+        """dict of rr, rho (entry 0: the prologue's, then one per body) and rv, ts, tt (one per body)"""
+        cap = max(self.itermax, 0) + 2
+        out = {}
+        for which, name in enumerate(self.HISTORIES):
+            a = np.zeros(cap)
+            cnt = self.L.sb_bicgstab_history(self.ptr, which, a.ctypes.data_as(vp), cap)
+            out[name] = a[:cnt].copy()
+        return out
+
+    def solution(self):
+        """x in original row order"""
+        x = np.empty(self.problem.nr)
+        self.L.sb_bicgstab_solution(self.ptr, x.ctypes.data_as(vp))
+        return x
+
+    def check_residual(self):
+        return self.L.sb_bicgstab_check_residual(self.ptr)
+
+    def dinv(self):
+        """the preconditioner in use, original row order"""
+        d = np.empty(self.problem.nr)
+        self.L.sb_bicgstab_dinv(self.ptr, d.ctypes.data_as(vp))
+        return d
+
+    def counters(self):
+        out = (C.c_int * 5)()
+        self.L.sb_bicgstab_counters(self.ptr, out)
+        return dict(zip(["stop", "iters", "n_rr", "n_rv", "n_ts"], list(out)))
+
+    def loop_ms(self):
+        return self.L.sb_bicgstab_loop_ms(self.ptr)
+
+    def free(self):
+        if self.ptr:
+            self.L.sb_bicgstab_free(self.ptr)
+            self.ptr = None
