@@ -673,6 +673,7 @@ void sb_event_destroy(void* ev) { HIP_CHECK(hipEventDestroy((hipEvent_t)ev)); }
 #include "sbhip_matrix.inc.h"
 #include "sbhip_launch.inc.h"
 #include "sbhip_comm.inc.h"
+#include "sbhip_solver.inc.h"
 #include "sbhip_cg.inc.h"
 #include "sbhip_sp.inc.h"
 #include "sbhip_gmres.inc.h"

@@ -18,46 +18,22 @@ struct sb_bicgstab {
   double* hist = nullptr; // 5 x hist_cap: rr, rho, rv, ts, tt
   int hist_cap = 0;
   int k_next = 1;
-  bool started = false;
-  float loop_ms = 0.f;
-  hipEvent_t evLoop0 = nullptr, evLoop1 = nullptr;
+  LoopClock clock;
 };
 
-// grid of the four streaming kernels over n rows: 1024 threads, a wave per 256-row group, two workgroups per CU at most
-static uint32_t bicg_grid(uint32_t n)
-{
-  const uint32_t nGroups = (n + 255u) >> 8;
-  return std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * 2u, (nGroups + 15u) / 16u));
-}
+// grid of the four streaming kernels over n rows: vec_stream_grid
 void sb_bicgstab_launch(uint32_t n, uint32_t out[3])
 {
   need_init();
-  out[0] = bicg_grid(n), out[1] = 1024u, out[2] = (uint32_t)g.prop.multiProcessorCount;
+  out[0] = vec_stream_grid(n), out[1] = 1024u, out[2] = (uint32_t)g.prop.multiProcessorCount;
 }
 
-static void bicg_need_aligned(std::initializer_list<const void*> ptrs, const char* fn)
+// the control block of a blocking test entry: its three coefficients, everything else zero
+static BicgScalars* bicg_coeffs(double alpha, double omega, double beta)
 {
-  uintptr_t bits = 0;
-  for (const void* q : ptrs) bits |= (uintptr_t)q;
-  if (bits & 15u) SB_FATAL("%s: vectors must be 16-byte aligned", fn);
-}
-
-// a control block for the blocking test entries
-static BicgScalars* bicg_test_block(double alpha, double omega, double beta)
-{
-  BicgScalars h;
-  memset(&h, 0, sizeof h);
+  BicgScalars h = zeroed<BicgScalars>();
   h.alpha = alpha, h.omega = omega, h.beta = beta;
-  BicgScalars* S = (BicgScalars*)sb_malloc(sizeof h);
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  HIP_CHECK(hipMemcpy(S, &h, sizeof h, hipMemcpyHostToDevice));
-  return S;
-}
-static void bicg_test_done(BicgScalars* S)
-{
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  sb_free(S);
+  return test_block(h);
 }
 
 void sb_bicgstab_update_p_native(uint32_t n, double beta, double omega, const double* r_dev, double* p_dev, const double* v_dev,
@@ -65,11 +41,11 @@ void sb_bicgstab_update_p_native(uint32_t n, double beta, double omega, const do
 {
   need_init();
   if (n == 0) return;
-  bicg_need_aligned({ r_dev, p_dev, v_dev, dinv_dev, ph_dev }, "sb_bicgstab_update_p_native");
-  BicgScalars* S = bicg_test_block(0.0, omega, beta);
-  hipLaunchKernelGGL(bicg_update_p_k, dim3(bicg_grid(n)), dim3(1024), 0, g.stream, n, r_dev, p_dev, v_dev, dinv_dev, ph_dev,
+  need_aligned16({ r_dev, p_dev, v_dev, dinv_dev, ph_dev }, "sb_bicgstab_update_p_native", "vectors");
+  BicgScalars* S = bicg_coeffs(0.0, omega, beta);
+  hipLaunchKernelGGL(bicg_update_p_k, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, r_dev, p_dev, v_dev, dinv_dev, ph_dev,
       (const BicgScalars*)S);
-  bicg_test_done(S);
+  test_block_done(S);
 }
 
 void sb_bicgstab_update_s_native(uint32_t n, double alpha, const double* r_dev, const double* v_dev, const double* dinv_dev, double* s_dev,
@@ -77,22 +53,22 @@ void sb_bicgstab_update_s_native(uint32_t n, double alpha, const double* r_dev, 
 {
   need_init();
   if (n == 0) return;
-  bicg_need_aligned({ r_dev, v_dev, dinv_dev, s_dev, sh_dev }, "sb_bicgstab_update_s_native");
-  BicgScalars* S = bicg_test_block(alpha, 0.0, 0.0);
-  hipLaunchKernelGGL(bicg_update_s_k, dim3(bicg_grid(n)), dim3(1024), 0, g.stream, n, r_dev, v_dev, dinv_dev, s_dev, sh_dev,
+  need_aligned16({ r_dev, v_dev, dinv_dev, s_dev, sh_dev }, "sb_bicgstab_update_s_native", "vectors");
+  BicgScalars* S = bicg_coeffs(alpha, 0.0, 0.0);
+  hipLaunchKernelGGL(bicg_update_s_k, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, r_dev, v_dev, dinv_dev, s_dev, sh_dev,
       (const BicgScalars*)S);
-  bicg_test_done(S);
+  test_block_done(S);
 }
 
 void sb_bicgstab_dot2_native(uint32_t n, int pair, const double* a_dev, const double* b_dev, double* l1_ab_dev, double* l1_aa_dev)
 {
   need_init();
   if (n == 0) return;
-  bicg_need_aligned({ a_dev, b_dev }, "sb_bicgstab_dot2_native");
+  need_aligned16({ a_dev, b_dev }, "sb_bicgstab_dot2_native", "vectors");
   if (pair)
-    hipLaunchKernelGGL(bicg_dot2_k, dim3(bicg_grid(n)), dim3(1024), 0, g.stream, n, a_dev, b_dev, l1_ab_dev, l1_aa_dev, (const int*)nullptr);
+    hipLaunchKernelGGL(bicg_dot2_k, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, a_dev, b_dev, l1_ab_dev, l1_aa_dev, (const int*)nullptr);
   else
-    hipLaunchKernelGGL(dot_l1_k, dim3(bicg_grid(n)), dim3(1024), 0, g.stream, n, a_dev, b_dev, l1_ab_dev, (const int*)nullptr);
+    hipLaunchKernelGGL(dot_l1_k, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, a_dev, b_dev, l1_ab_dev, (const int*)nullptr);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(g.stream));
 }
@@ -102,43 +78,32 @@ void sb_bicgstab_update_xr_native(uint32_t n, double alpha, double omega, double
 {
   need_init();
   if (n == 0) return;
-  bicg_need_aligned({ x_dev, ph_dev, sh_dev, s_dev, t_dev, rhat_dev, r_dev }, "sb_bicgstab_update_xr_native");
-  BicgScalars* S = bicg_test_block(alpha, omega, 0.0);
-  hipLaunchKernelGGL(bicg_update_xr_k, dim3(bicg_grid(n)), dim3(1024), 0, g.stream, n, x_dev, ph_dev, sh_dev, s_dev, t_dev, rhat_dev, r_dev,
+  need_aligned16({ x_dev, ph_dev, sh_dev, s_dev, t_dev, rhat_dev, r_dev }, "sb_bicgstab_update_xr_native", "vectors");
+  BicgScalars* S = bicg_coeffs(alpha, omega, 0.0);
+  hipLaunchKernelGGL(bicg_update_xr_k, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, x_dev, ph_dev, sh_dev, s_dev, t_dev, rhat_dev, r_dev,
       (const BicgScalars*)S, l1_rho_dev, l1_rr_dev);
-  bicg_test_done(S);
+  test_block_done(S);
 }
 
 // the scalar step's reduction alone: the totals of two arrays of m level-1 values, as the prologue step forms them
 void sb_bicgstab_reduce_native(uint32_t m, const double* l1_a_dev, const double* l1_b_dev, double out[2])
 {
   need_init();
-  BicgScalars* S = bicg_test_block(0.0, 0.0, 0.0); // itermax = 0, hist_cap = 0: nothing is recorded
+  BicgScalars* S = bicg_coeffs(0.0, 0.0, 0.0); // itermax = 0, hist_cap = 0: nothing is recorded
   hipLaunchKernelGGL((bicg_scalar_k<0>), dim3(1), dim3(1024), 0, g.stream, m, l1_a_dev, l1_b_dev, S, (double*)nullptr);
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  BicgScalars h;
-  HIP_CHECK(hipMemcpy(&h, S, sizeof h, hipMemcpyDeviceToHost));
+  const BicgScalars h = read_block(S);
   sb_free(S);
   out[0] = h.rho, out[1] = h.rr;
-}
-
-static void bicg_need_tree(const char* fn)
-{
-  if (sb_dot_order() == 1)
-    SB_FATAL("%s: BiCGStab runs in the tree dot order only (the process is in the seq order: SB_DOT_ORDER=seq / "
-             "sb_set_dot_order(1), the validation mode of sb_cg)", fn);
 }
 
 sb_bicgstab* sb_bicgstab_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int precond,
     const double* dinv_host)
 {
   need_init();
-  if (m->prec != 2) SB_FATAL("sb_bicgstab_create: BiCGStab: double precision only (the matrix was uploaded in single precision)");
-  if (multi_rank() || sb_comm_size() > 1 || m->nc != m->nr || (halo && halo->externalCount > 0))
-    SB_FATAL("sb_bicgstab_create: BiCGStab runs on one rank (this process is rank %d of %d, the matrix has %u halo columns)", g.rank,
-        g.size, m->nc - m->nr);
-  bicg_need_tree("sb_bicgstab_create");
+  need_dp(m, "sb_bicgstab_create", "BiCGStab");
+  need_one_rank(m, halo, "sb_bicgstab_create", "BiCGStab");
+  need_tree("sb_bicgstab_create", "BiCGStab", "sb_cg");
   if (precond < 0 || precond > 2) SB_FATAL("sb_bicgstab_create: precond = %d (0: none, 1: Jacobi, 2: the caller's dinv_host)", precond);
   if (precond == 2) {
     if (!dinv_host) SB_FATAL("sb_bicgstab_create: precond = 2 needs dinv_host");
@@ -149,7 +114,8 @@ sb_bicgstab* sb_bicgstab_create(const sb_matrix* m, sb_halo* halo, const double*
   const size_t nb = (size_t)m->nr * sizeof(double);
   std::vector<double> hd; // the preconditioner on the host: original order (none, the caller's) or device order (Jacobi)
   double* tmp = scratch_ws(0, (size_t)m->nr + 2);
-  if (precond == 1 && m->nr) { // Jacobi: dinv = 1 / diag(A), d by sb_matrix_diagonal's rule; checked on the host
+  if (precond == 1 && m->nr) { // Jacobi: dinv = 1 / diag(A), d by sb_matrix_diagonal's rule.  Checked on the host, for finite and
+                               // NON-ZERO (PCG's check is for finite and positive, inside diag_*_k: the two stay apart)
     hd.resize(m->nr);
     launch_diagonal(m, tmp, nullptr);
     sb_d2h(hd.data(), tmp, nb);
@@ -168,25 +134,18 @@ sb_bicgstab* sb_bicgstab_create(const sb_matrix* m, sb_halo* halo, const double*
   s->nGroups      = (m->nr + 255u) >> 8;
   double** vecs[] = { &s->r, &s->rhat, &s->p, &s->ph, &s->v, &s->sh, &s->t, &s->x, &s->b, &s->dinv };
   for (double** vv : vecs) *vv = (double*)sb_malloc((size_t)m->nc * sizeof(double) + 4096);
-  if (m->nr) {
-    if (precond == 1) {
-      hipLaunchKernelGGL(pcg_reciprocal_k, dim3(stream_grid(m->nr, 256)), dim3(256), 0, g.stream, m->nr, (const double*)tmp, s->dinv);
-      HIP_CHECK(hipGetLastError());
-    } else {
-      if (precond == 0) hd.assign(m->nr, 1.0);
-      sb_h2d(tmp, precond == 0 ? hd.data() : dinv_host, nb);
-      sb_permute(m, tmp, s->dinv);
-    }
+  if (precond != 1) {
+    if (precond == 0) hd.assign(m->nr, 1.0);
+    upload_permuted(m, precond == 0 ? hd.data() : dinv_host, s->dinv);
+  } else if (m->nr) {
+    hipLaunchKernelGGL(pcg_reciprocal_k, dim3(stream_grid(m->nr, 256)), dim3(256), 0, g.stream, m->nr, (const double*)tmp, s->dinv);
+    HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(g.stream));
-    sb_h2d(tmp, b_host, nb);
   }
-  sb_permute(m, tmp, s->b);
-  HIP_CHECK(hipStreamSynchronize(g.stream));
+  upload_permuted(m, b_host, s->b);
   if (xexact_host) {
     s->xexact = (double*)sb_malloc(nb + 4096);
-    if (m->nr) sb_h2d(tmp, xexact_host, nb);
-    sb_permute(m, tmp, s->xexact);
-    HIP_CHECK(hipStreamSynchronize(g.stream));
+    upload_permuted(m, xexact_host, s->xexact);
   }
   s->S = (BicgScalars*)sb_malloc(sizeof(BicgScalars));
   HIP_CHECK(hipMemset(s->S, 0, sizeof(BicgScalars)));
@@ -196,8 +155,7 @@ sb_bicgstab* sb_bicgstab_create(const sb_matrix* m, sb_halo* halo, const double*
     *vv = (double*)sb_malloc(lb);
     HIP_CHECK(hipMemsetAsync(*vv, 0, lb, g.stream));
   }
-  HIP_CHECK(hipEventCreate(&s->evLoop0));
-  HIP_CHECK(hipEventCreate(&s->evLoop1));
+  s->clock.create();
   HIP_CHECK(hipStreamSynchronize(g.stream));
   return s;
 }
@@ -206,8 +164,7 @@ void sb_bicgstab_free(sb_bicgstab* s)
 {
   if (!s) return;
   HIP_CHECK(hipStreamSynchronize(g.stream));
-  HIP_CHECK(hipEventDestroy(s->evLoop0));
-  HIP_CHECK(hipEventDestroy(s->evLoop1));
+  s->clock.destroy();
   sb_free(s->r), sb_free(s->rhat), sb_free(s->p), sb_free(s->ph), sb_free(s->v), sb_free(s->sh), sb_free(s->t), sb_free(s->x);
   sb_free(s->b), sb_free(s->dinv), sb_free(s->xexact), sb_free(s->S), sb_free(s->l1a), sb_free(s->l1b), sb_free(s->hist);
   delete s;
@@ -233,7 +190,7 @@ static void bicg_body(sb_bicgstab* s)
 {
   const uint32_t n = s->nr;
   const int* stop  = &s->S->stop;
-  const dim3 grid(bicg_grid(n)), block(1024);
+  const dim3 grid(vec_stream_grid(n)), block(1024);
   const BicgScalars* S = s->S;
   if (n) {
     hipLaunchKernelGGL(bicg_update_p_k, grid, block, 0, g.stream, n, (const double*)s->r, s->p, (const double*)s->v, (const double*)s->dinv,
@@ -268,17 +225,13 @@ static void bicg_body(sb_bicgstab* s)
 void sb_bicgstab_start(sb_bicgstab* s, int itermax, double eps)
 {
   need_init();
-  bicg_need_tree("sb_bicgstab_start");
-  if (itermax + 2 > s->hist_cap) {
-    sb_free(s->hist);
-    s->hist_cap = itermax + 2;
-    s->hist     = (double*)sb_malloc(5 * (size_t)s->hist_cap * sizeof(double));
-  }
-  BicgScalars h;
-  memset(&h, 0, sizeof h); // beta = omega = +0.0: the first body's p update is the general one
+  need_tree("sb_bicgstab_start", "BiCGStab", "sb_cg");
+  const int want = std::max(s->hist_cap, itermax + 2);
+  grow(s->hist, s->hist_cap, want, 5);
+  s->hist_cap   = want;
+  BicgScalars h = zeroed<BicgScalars>(); // beta = omega = +0.0: the first body's p update is the general one
   h.itermax = itermax, h.eps = eps, h.hist_cap = s->hist_cap;
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  HIP_CHECK(hipMemcpy(s->S, &h, sizeof h, hipMemcpyHostToDevice));
+  write_block(s->S, &h);
   // prologue: x = 0, r = b, rhat = b, p = 0, v = 0, rho = rhat.r, rr = r.r, the loop test for k = 1
   const size_t nb = (size_t)s->nr * sizeof(double);
   HIP_CHECK(hipMemsetAsync(s->x, 0, nb, g.stream));
@@ -287,45 +240,36 @@ void sb_bicgstab_start(sb_bicgstab* s, int itermax, double eps)
   if (s->nr) {
     HIP_CHECK(hipMemcpyAsync(s->r, s->b, nb, hipMemcpyDeviceToDevice, g.stream));
     HIP_CHECK(hipMemcpyAsync(s->rhat, s->b, nb, hipMemcpyDeviceToDevice, g.stream));
-    hipLaunchKernelGGL(bicg_dot2_k, dim3(bicg_grid(s->nr)), dim3(1024), 0, g.stream, s->nr, (const double*)s->r, (const double*)s->rhat,
+    hipLaunchKernelGGL(bicg_dot2_k, dim3(vec_stream_grid(s->nr)), dim3(1024), 0, g.stream, s->nr, (const double*)s->r, (const double*)s->rhat,
         s->l1a, s->l1b, (const int*)nullptr);
     HIP_CHECK(hipGetLastError());
   }
   bicg_scalar_launch<0>(s);
-  s->k_next = 1, s->started = true, s->loop_ms = 0.f;
-  HIP_CHECK(hipEventRecord(s->evLoop0, g.stream));
+  s->k_next = 1;
+  s->clock.begin();
 }
 
 void sb_bicgstab_run_iters(sb_bicgstab* s, int iters)
 {
   need_init();
-  if (!s->started) SB_FATAL("sb_bicgstab_run_iters before sb_bicgstab_start");
+  s->clock.need_open("sb_bicgstab_run_iters", "sb_bicgstab_start");
   for (int i = 0; i < iters; i++) bicg_body(s), s->k_next++;
-}
-
-static BicgScalars bicg_control(const sb_bicgstab* s)
-{
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  BicgScalars h;
-  HIP_CHECK(hipMemcpy(&h, s->S, sizeof h, hipMemcpyDeviceToHost));
-  return h;
 }
 
 int sb_bicgstab_finish(sb_bicgstab* s)
 {
   need_init();
-  if (!s->started) SB_FATAL("sb_bicgstab_finish before sb_bicgstab_start");
-  HIP_CHECK(hipEventRecord(s->evLoop1, g.stream));
+  s->clock.need_open("sb_bicgstab_finish", "sb_bicgstab_start");
+  s->clock.end();
   HIP_CHECK(hipStreamSynchronize(g.stream));
-  HIP_CHECK(hipEventElapsedTime(&s->loop_ms, s->evLoop0, s->evLoop1));
-  s->started = false;
-  return bicg_control(s).iters + 1; // the value of k when the for loop exits
+  s->clock.read();
+  return read_block(s->S).iters + 1; // the value of k when the for loop exits
 }
 
 int sb_bicgstab_solve(sb_bicgstab* s, int itermax, double eps)
 {
   sb_bicgstab_start(s, itermax, eps);
-  sb_bicgstab_run_iters(s, itermax > 1 ? itermax - 1 : 0);
+  sb_bicgstab_run_iters(s, loop_bodies(itermax));
   return sb_bicgstab_finish(s);
 }
 
@@ -334,54 +278,34 @@ int sb_bicgstab_history(const sb_bicgstab* s, int which, double* out, int cap)
 {
   need_init();
   if (which < 0 || which > 4) SB_FATAL("sb_bicgstab_history: which = %d (0 rr, 1 rho, 2 rv, 3 ts, 4 tt)", which);
-  const BicgScalars h = bicg_control(s);
+  const BicgScalars h = read_block(s->S);
   const int have      = which < 2 ? h.n_rr : which == 2 ? h.n_rv : h.n_ts;
-  const int cnt       = std::min(std::min(have, s->hist_cap), cap);
-  if (cnt <= 0) return 0;
-  HIP_CHECK(hipMemcpy(out, s->hist + (size_t)which * s->hist_cap, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost));
-  return cnt;
+  return copy_history(s->hist + (size_t)which * s->hist_cap, have, s->hist_cap, out, cap);
 }
 
-static void bicg_to_host_orig(const sb_bicgstab* s, const double* v_dev, double* v_host)
-{
-  if (s->nr == 0) return;
-  double* tmp = scratch_ws(1, s->nr);
-  sb_unpermute(s->A, v_dev, tmp);
-  sb_d2h(v_host, tmp, (size_t)s->nr * sizeof(double));
-}
 void sb_bicgstab_solution(const sb_bicgstab* s, double* x_host)
 {
   need_init();
-  bicg_to_host_orig(s, s->x, x_host);
+  download_original(s->A, s->x, x_host);
 }
 void sb_bicgstab_dinv(const sb_bicgstab* s, double* dinv_host)
 {
   need_init();
-  bicg_to_host_orig(s, s->dinv, dinv_host);
+  download_original(s->A, s->dinv, dinv_host);
 }
 
 // max|x - xexact| (solverCheckResidual, src/CGSolver.c:40-60); 0.0 without an exact solution
 double sb_bicgstab_check_residual(const sb_bicgstab* s)
 {
   need_init();
-  if (!s->xexact || s->nr == 0) return 0.0;
-  const uint32_t blocks = stream_grid(s->nr, 256);
-  double* q             = scratch_partials(blocks);
-  hipLaunchKernelGGL(max_abs_diff_partials, dim3(blocks), dim3(256), 0, g.stream, s->nr, (const double*)s->x, (const double*)s->xexact, q);
-  HIP_CHECK(hipGetLastError());
-  std::vector<double> h(blocks);
-  sb_d2h(h.data(), q, blocks * sizeof(double));
-  double mx = 0.0;
-  for (double vv : h)
-    if (vv > mx) mx = vv;
-  return mx;
+  return max_abs_diff_host(s->nr, s->x, s->xexact);
 }
 
-double sb_bicgstab_loop_ms(const sb_bicgstab* s) { return (double)s->loop_ms; }
+double sb_bicgstab_loop_ms(const sb_bicgstab* s) { return (double)s->clock.ms; }
 
 // stop, iters, n_rr (= entries of rho too), n_rv, n_ts (= entries of tt too) of the device control block
 void sb_bicgstab_counters(const sb_bicgstab* s, int out[5])
 {
-  const BicgScalars h = bicg_control(s);
+  const BicgScalars h = read_block(s->S);
   out[0] = h.stop, out[1] = h.iters, out[2] = h.n_rr, out[3] = h.n_rv, out[4] = h.n_ts;
 }

@@ -574,9 +574,8 @@ static void spmv_and_pAp(sb_cg* s, const int* stop)
     mark(s, R_SPMVM);
     phase_mark(s, PH_SPMV);
     if (s->fused && n) { // level-1 values straight away (pAp_is_level1): a quarter of the bytes for the step, which can then ride in the r update
-      const uint32_t nGroups = (n + 255u) >> 8;
-      hipLaunchKernelGGL(dot_l1_k, dim3(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * 2u, (nGroups + 15u) / 16u))), dim3(1024), 0,
-          g.stream, n, (const double*)s->p, (const double*)s->Ap, s->partials, stop);
+      hipLaunchKernelGGL(dot_l1_k, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, (const double*)s->p, (const double*)s->Ap,
+          s->partials, stop);
       HIP_CHECK(hipGetLastError());
     } else cg_dot(s, s->p, s->Ap, stop);
     phase_mark(s, PH_DOT_PASS);
@@ -894,9 +893,7 @@ void sb_cg_solution(const sb_cg* s, double* x_host)
 {
   need_init();
   if (s->prec == 1) SB_FATAL("sb_cg_solution on a single-precision solver: use sb_cg_solution_f32");
-  double* tmp = scratch_ws(1, s->nr);
-  sb_unpermute(s->A, s->x, tmp);
-  sb_d2h(x_host, tmp, (size_t)s->nr * sizeof(double));
+  download_original(s->A, s->x, x_host);
 }
 
 double sb_cg_check_residual(const sb_cg* s)
@@ -904,15 +901,7 @@ double sb_cg_check_residual(const sb_cg* s)
   need_init();
   if (s->prec == 1) return sp_cg_check_residual(s);
   if (!s->xexact || s->nr == 0) return 0.0;
-  const uint32_t blocks = stream_grid(s->nr, 256);
-  double* q             = scratch_partials(blocks);
-  hipLaunchKernelGGL(max_abs_diff_partials, dim3(blocks), dim3(256), 0, g.stream, s->nr, s->x, s->xexact, q);
-  HIP_CHECK(hipGetLastError());
-  std::vector<double> h(blocks);
-  sb_d2h(h.data(), q, blocks * sizeof(double));
-  double m = 0.0;
-  for (double v : h)
-    if (v > m) m = v;
+  double m = max_abs_diff_host(s->nr, s->x, s->xexact);
   if (multi_rank()) { // commReduction(&residual, MAX), src/CGSolver.c:55
     sb_h2d(g.scalar, &m, sizeof m);
     sb_comm_reduction(g.scalar, 0);

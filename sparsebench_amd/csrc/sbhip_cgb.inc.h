@@ -17,9 +17,7 @@ struct sb_cgb {
   double *rr_hist = nullptr, *pAp_hist = nullptr; // nv * hist_cap: column c at + c * hist_cap
   int hist_cap = 0;
   int k_next = 1;
-  bool started = false;
-  float loop_ms = 0.f;
-  hipEvent_t evLoop0 = nullptr, evLoop1 = nullptr;
+  LoopClock clock;
 };
 
 #define CGB_WIDTHS "2, 4 or 8"
@@ -38,10 +36,6 @@ static void cgb_need_width(int nrhs, const char* fn)
 {
   if (nrhs != 2 && nrhs != 4 && nrhs != 8)
     SB_FATAL("%s: nrhs = %d: the block kernels are built for " CGB_WIDTHS " right-hand sides (one right-hand side: sb_cg_create / sb_spmv_native)", fn, nrhs);
-}
-static void cgb_need_aligned(const void* a, const void* b, const char* fn)
-{
-  if (((uintptr_t)a | (uintptr_t)b) & 15u) SB_FATAL("%s: block vectors must be 16-byte aligned", fn);
 }
 static bool spmmv_has_dot(const sb_matrix* m) { return m->fmt == 1 && m->C == 64; }
 
@@ -103,7 +97,7 @@ void sb_spmmv_native(const sb_matrix* m, int nrhs, const double* X_dev, double* 
   need_init();
   SB_NEED_PREC(m, 2, "sb_spmmv_native");
   cgb_need_width(nrhs, "sb_spmmv_native");
-  cgb_need_aligned(X_dev, Y_dev, "sb_spmmv_native");
+  need_aligned16({ X_dev, Y_dev }, "sb_spmmv_native", "block vectors");
   launch_spmmv(m, nrhs, X_dev, Y_dev, nullptr, nullptr);
 }
 
@@ -112,7 +106,7 @@ int sb_spmmv_native_dot(const sb_matrix* m, int nrhs, const double* X_dev, doubl
   need_init();
   SB_NEED_PREC(m, 2, "sb_spmmv_native_dot");
   cgb_need_width(nrhs, "sb_spmmv_native_dot");
-  cgb_need_aligned(X_dev, Y_dev, "sb_spmmv_native_dot");
+  need_aligned16({ X_dev, Y_dev }, "sb_spmmv_native_dot", "block vectors");
   if (!spmmv_has_dot(m)) return 0;
   launch_spmmv(m, nrhs, X_dev, Y_dev, l1_dev, nullptr);
   return 2;
@@ -147,22 +141,13 @@ double sb_matrix_spmmv_bytes(const sb_matrix* m, int nrhs)
   return (sb_matrix_spmv_bytes(m) - vec) + (double)nrhs * vec;
 }
 
-static void cgb_need_tree(const char* fn)
-{
-  if (sb_dot_order() == 1)
-    SB_FATAL("%s: batched CG runs in the tree dot order only (the process is in the seq order: SB_DOT_ORDER=seq / sb_set_dot_order(1), "
-             "the validation mode of the single right-hand-side solver)", fn);
-}
-
 sb_cgb* sb_cgb_create(const sb_matrix* m, sb_halo* halo, int nrhs, const double* B_host, const double* xexact0_host)
 {
   need_init();
   cgb_need_width(nrhs, "sb_cgb_create");
-  if (m->prec != 2) SB_FATAL("sb_cgb_create: batched CG: double precision only (the matrix was uploaded in single precision)");
-  if (multi_rank() || sb_comm_size() > 1 || m->nc != m->nr)
-    SB_FATAL("sb_cgb_create: batched CG runs on one rank (this process is rank %d of %d, the matrix has %u halo columns)", g.rank, g.size,
-        m->nc - m->nr);
-  cgb_need_tree("sb_cgb_create");
+  need_dp(m, "sb_cgb_create", "batched CG");
+  need_one_rank(m, nullptr, "sb_cgb_create", "batched CG");
+  need_tree("sb_cgb_create", "batched CG", "the single right-hand-side solver");
   (void)halo;
   sb_cgb* s = new sb_cgb();
   s->A = m, s->nv = nrhs, s->nr = m->nr, s->nc = m->nc;
@@ -171,11 +156,11 @@ sb_cgb* sb_cgb_create(const sb_matrix* m, sb_halo* halo, int nrhs, const double*
   double** vecs[] = { &s->r, &s->Ap, &s->x, &s->b };
   for (double** v : vecs) *v = (double*)sb_malloc(vb + 4096);
   s->p = (double*)sb_malloc(vbc + 4096);
-  double* tmp = (double*)sb_malloc(vb + 64); // the caller's plain vectors, original row order
+  // the caller's plain vectors, original row order, interleaved on the device: another layout than upload_permuted's
+  double* tmp = scratch_ws(0, (size_t)m->nr * nrhs);
   if (m->nr) sb_h2d(tmp, B_host, vb);
   sb_block_interleave(m, nrhs, tmp, s->b);
   HIP_CHECK(hipStreamSynchronize(g.stream));
-  sb_free(tmp);
   if (xexact0_host) {
     s->xexact = (double*)sb_malloc((size_t)m->nr * sizeof(double) + 64);
     if (m->nr) sb_h2d(s->xexact, xexact0_host, (size_t)m->nr * sizeof(double));
@@ -188,8 +173,7 @@ sb_cgb* sb_cgb_create(const sb_matrix* m, sb_halo* halo, int nrhs, const double*
   s->l1pAp = (double*)sb_malloc(lb), s->l1rr = (double*)sb_malloc(lb);
   HIP_CHECK(hipMemsetAsync(s->l1pAp, 0, lb, g.stream));
   HIP_CHECK(hipMemsetAsync(s->l1rr, 0, lb, g.stream));
-  HIP_CHECK(hipEventCreate(&s->evLoop0));
-  HIP_CHECK(hipEventCreate(&s->evLoop1));
+  s->clock.create();
   return s;
 }
 
@@ -197,8 +181,7 @@ void sb_cgb_free(sb_cgb* s)
 {
   if (!s) return;
   HIP_CHECK(hipStreamSynchronize(g.stream));
-  HIP_CHECK(hipEventDestroy(s->evLoop0));
-  HIP_CHECK(hipEventDestroy(s->evLoop1));
+  s->clock.destroy();
   sb_free(s->r), sb_free(s->p), sb_free(s->Ap), sb_free(s->x), sb_free(s->b), sb_free(s->xexact);
   sb_free(s->S), sb_free(s->ctl), sb_free(s->l1pAp), sb_free(s->l1rr), sb_free(s->rr_hist), sb_free(s->pAp_hist);
   delete s;
@@ -246,19 +229,14 @@ static void cgb_body(sb_cgb* s, int k)
 void sb_cgb_start(sb_cgb* s, int itermax, double eps)
 {
   need_init();
-  cgb_need_tree("sb_cgb_start");
-  const int nv = s->nv;
-  if (itermax + 2 > s->hist_cap) {
-    sb_free(s->rr_hist), sb_free(s->pAp_hist);
-    s->hist_cap = itermax + 2;
-    s->rr_hist  = (double*)sb_malloc((size_t)nv * s->hist_cap * sizeof(double));
-    s->pAp_hist = (double*)sb_malloc((size_t)nv * s->hist_cap * sizeof(double));
-  }
-  std::vector<CgScalars> h(nv);
-  memset(h.data(), 0, sizeof(CgScalars) * nv);
+  need_tree("sb_cgb_start", "batched CG", "the single right-hand-side solver");
+  const int nv = s->nv, want = std::max(s->hist_cap, itermax + 2);
+  grow(s->rr_hist, s->hist_cap, want, nv);
+  grow(s->pAp_hist, s->hist_cap, want, nv);
+  s->hist_cap = want;
+  std::vector<CgScalars> h(nv, zeroed<CgScalars>());
   for (CgScalars& c : h) c.itermax = itermax, c.eps = eps, c.hist_cap = s->hist_cap;
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  HIP_CHECK(hipMemcpy(s->S, h.data(), sizeof(CgScalars) * nv, hipMemcpyHostToDevice));
+  write_block(s->S, h.data(), nv);
   HIP_CHECK(hipMemsetAsync(s->ctl, 0, sizeof(CgbControl), g.stream));
   // prologue, src/CGSolver.c:94-100: x0 = 0 (:28), p = 1.0 x + 0.0 x = 0, Ap = A p, r = 1.0 b + (-1.0) Ap, r.r, the loop test for k = 1
   HIP_CHECK(hipMemsetAsync(s->x, 0, (size_t)s->nr * nv * sizeof(double), g.stream));
@@ -266,22 +244,22 @@ void sb_cgb_start(sb_cgb* s, int itermax, double eps)
   launch_spmmv(s->A, nv, s->p, s->Ap, nullptr, nullptr);
   launch_block_vec(2, nv, s->nr, s->b, s->Ap, s->r, nullptr, s->l1rr, nullptr);
   cgb_scalar_launch<0>(s, s->l1rr, 0);
-  s->k_next = 1, s->started = true, s->loop_ms = 0.f;
-  HIP_CHECK(hipEventRecord(s->evLoop0, g.stream));
+  s->k_next = 1;
+  s->clock.begin();
 }
 
 void sb_cgb_run_iters(sb_cgb* s, int iters)
 {
   need_init();
-  if (!s->started) SB_FATAL("sb_cgb_run_iters before sb_cgb_start");
+  s->clock.need_open("sb_cgb_run_iters", "sb_cgb_start");
   for (int i = 0; i < iters; i++) cgb_body(s, s->k_next++);
 }
 
 int sb_cgb_finish(sb_cgb* s)
 {
   need_init();
-  if (!s->started) SB_FATAL("sb_cgb_finish before sb_cgb_start");
-  HIP_CHECK(hipEventRecord(s->evLoop1, g.stream));
+  s->clock.need_open("sb_cgb_finish", "sb_cgb_start");
+  s->clock.end();
   if (s->nr) { // the x update every column's last body left to "the next p update": nobody comes after it
     CGB_DISPATCH(s->nv, hipLaunchKernelGGL(cgb_x_finalize<NV>, dim3(stream_grid(s->nr, 256)), dim3(256), 0, g.stream, s->nr, s->x,
                             (const double*)s->p, (const CgScalars*)s->S));
@@ -289,8 +267,7 @@ int sb_cgb_finish(sb_cgb* s)
     HIP_CHECK(hipGetLastError());
   }
   HIP_CHECK(hipStreamSynchronize(g.stream));
-  HIP_CHECK(hipEventElapsedTime(&s->loop_ms, s->evLoop0, s->evLoop1));
-  s->started = false;
+  s->clock.read();
   int k = 0;
   for (int c = 0; c < s->nv; c++) k = std::max(k, sb_cgb_iterations(s, c));
   return k; // the largest k_c
@@ -299,7 +276,7 @@ int sb_cgb_finish(sb_cgb* s)
 int sb_cgb_solve(sb_cgb* s, int itermax, double eps)
 {
   sb_cgb_start(s, itermax, eps);
-  sb_cgb_run_iters(s, itermax > 1 ? itermax - 1 : 0);
+  sb_cgb_run_iters(s, loop_bodies(itermax));
   return sb_cgb_finish(s);
 }
 
@@ -307,10 +284,7 @@ static CgScalars cgb_column(const sb_cgb* s, int c, const char* fn)
 {
   need_init();
   if (c < 0 || c >= s->nv) SB_FATAL("%s: column %d outside 0 .. %d", fn, c, s->nv - 1);
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  CgScalars h;
-  HIP_CHECK(hipMemcpy(&h, s->S + c, sizeof h, hipMemcpyDeviceToHost));
-  return h;
+  return read_block(s->S + c);
 }
 
 // k_c: the value of k when column c's for loop exits (src/CGSolver.c:107,:140)
@@ -319,11 +293,9 @@ int sb_cgb_iterations(const sb_cgb* s, int c) { return cgb_column(s, c, "sb_cgb_
 int sb_cgb_history(const sb_cgb* s, int c, double* rr_out, int rr_cap, double* pAp_out, int pAp_cap, int* n_pAp)
 {
   const CgScalars h = cgb_column(s, c, "sb_cgb_history");
-  int nrr = std::min(std::min(h.n_rr, s->hist_cap), rr_cap), npa = std::min(std::min(h.n_pAp, s->hist_cap), pAp_cap);
-  if (nrr > 0) HIP_CHECK(hipMemcpy(rr_out, s->rr_hist + (size_t)c * s->hist_cap, (size_t)nrr * sizeof(double), hipMemcpyDeviceToHost));
-  if (npa > 0) HIP_CHECK(hipMemcpy(pAp_out, s->pAp_hist + (size_t)c * s->hist_cap, (size_t)npa * sizeof(double), hipMemcpyDeviceToHost));
-  if (n_pAp) *n_pAp = npa > 0 ? npa : 0;
-  return nrr > 0 ? nrr : 0;
+  const int npa     = copy_history(s->pAp_hist + (size_t)c * s->hist_cap, h.n_pAp, s->hist_cap, pAp_out, pAp_cap);
+  if (n_pAp) *n_pAp = npa;
+  return copy_history(s->rr_hist + (size_t)c * s->hist_cap, h.n_rr, s->hist_cap, rr_out, rr_cap);
 }
 
 void sb_cgb_solution(const sb_cgb* s, int c, double* x_host)
@@ -343,20 +315,11 @@ double sb_cgb_check_residual(const sb_cgb* s, int c)
   if (c < 0 || c >= s->nv) SB_FATAL("sb_cgb_check_residual: column %d outside 0 .. %d", c, s->nv - 1);
   if (c != 0 || !s->xexact || s->nr == 0) return 0.0;
   double* tmp = scratch_ws(1, (size_t)s->nr * s->nv);
-  sb_block_deinterleave(s->A, s->nv, s->x, tmp);
-  const uint32_t blocks = stream_grid(s->nr, 256);
-  double* q             = scratch_partials(blocks);
-  hipLaunchKernelGGL(max_abs_diff_partials, dim3(blocks), dim3(256), 0, g.stream, s->nr, (const double*)tmp, (const double*)s->xexact, q);
-  HIP_CHECK(hipGetLastError());
-  std::vector<double> h(blocks);
-  sb_d2h(h.data(), q, blocks * sizeof(double));
-  double mx = 0.0;
-  for (double v : h)
-    if (v > mx) mx = v;
-  return mx;
+  sb_block_deinterleave(s->A, s->nv, s->x, tmp); // column 0 leads the de-interleaved columns, in xexact's original row order
+  return max_abs_diff_host(s->nr, tmp, s->xexact);
 }
 
-double sb_cgb_loop_ms(const sb_cgb* s) { return (double)s->loop_ms; }
+double sb_cgb_loop_ms(const sb_cgb* s) { return (double)s->clock.ms; }
 
 // c >= 0: {stop, stop_next, iters, n_rr, n_pAp} of column c's control block; c = -1: {global stop, columns stopped, bodies
 // enqueued since sb_cgb_start, 0, 0}
@@ -367,8 +330,6 @@ void sb_cgb_counters(const sb_cgb* s, int c, int out[5])
     out[0] = h.stop, out[1] = h.stop_next, out[2] = h.iters, out[3] = h.n_rr, out[4] = h.n_pAp;
     return;
   }
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  CgbControl h;
-  HIP_CHECK(hipMemcpy(&h, s->ctl, sizeof h, hipMemcpyDeviceToHost));
+  const CgbControl h = read_block(s->ctl);
   out[0] = h.stop, out[1] = h.nStopped, out[2] = s->k_next - 1, out[3] = 0, out[4] = 0;
 }

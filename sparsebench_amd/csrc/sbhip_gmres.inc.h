@@ -16,9 +16,7 @@ struct sb_gmres {
   int hist_cap = 0;
   int fused = 1;
   int pos = 0; // cycle position of the next step (host side: only the stop flag can end a cycle early)
-  bool started = false;
-  float loop_ms = 0.f;
-  hipEvent_t evLoop0 = nullptr, evLoop1 = nullptr;
+  LoopClock clock;
 };
 
 static void gm_need_vectors(const void* a, const void* b, size_t ldv, const char* fn)
@@ -30,7 +28,8 @@ static dim3 gm_group_grid(uint32_t nGroups) { return dim3(stream_grid(nGroups, 4
 sb_gmres* sb_gmres_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int restart)
 {
   need_init();
-  if (m->prec != 2) SB_FATAL("sb_gmres_create: GMRES: double precision only (the matrix was uploaded in single precision)");
+  need_dp(m, "sb_gmres_create", "GMRES");
+  // the one-rank refusal in this solver's own two messages (need_one_rank has the other three's single one)
   if (multi_rank() || sb_comm_size() > 1) SB_FATAL("sb_gmres_create: GMRES runs on one rank (this process is rank %d of %d)", g.rank, g.size);
   if (restart < 1) SB_FATAL("sb_gmres_create: restart = %d, expected a restart length >= 1", restart);
   if (m->nc != m->nr) SB_FATAL("sb_gmres_create: GMRES runs on one rank: the matrix has %u halo columns", m->nc - m->nr);
@@ -40,19 +39,14 @@ sb_gmres* sb_gmres_create(const sb_matrix* m, sb_halo* halo, const double* b_hos
   s->nGroups = (s->n + 255u) >> 8;
   s->ldv     = ((size_t)s->n + 511u) & ~(size_t)511u;
   if (s->ldv == 0) s->ldv = 512;
-  const size_t nb = (size_t)s->n * sizeof(double), vb = s->ldv * sizeof(double);
+  const size_t vb = s->ldv * sizeof(double);
   s->V = (double*)sb_malloc((size_t)(restart + 1) * vb + 4096); // (the slack the CG loop's vector slab ends with: vec_layout)
   double** vecs[] = { &s->w, &s->r, &s->x, &s->b, &s->Ap };
   for (double** v : vecs) *v = (double*)sb_malloc(vb + 4096);
-  double* tmp = scratch_ws(0, s->n);
-  sb_h2d(tmp, b_host, nb);
-  sb_permute(m, tmp, s->b);
-  HIP_CHECK(hipStreamSynchronize(g.stream));
+  upload_permuted(m, b_host, s->b);
   if (xexact_host) {
     s->xexact = (double*)sb_malloc(vb + 4096);
-    sb_h2d(tmp, xexact_host, nb);
-    sb_permute(m, tmp, s->xexact);
-    HIP_CHECK(hipStreamSynchronize(g.stream));
+    upload_permuted(m, xexact_host, s->xexact);
   }
   s->l1       = (double*)sb_malloc(((size_t)(restart + 1) * s->nGroups + 4) * sizeof(double));
   s->partials = (double*)sb_malloc((4 * (size_t)s->nGroups + 4) * sizeof(double));
@@ -75,8 +69,7 @@ sb_gmres* sb_gmres_create(const sb_matrix* m, sb_halo* halo, const double* b_hos
   gv.nh2 = d, d += M + 1;
   gv.hcol = d, d += M + 1;
   gv.res_hist = gv.rr_hist = nullptr;
-  HIP_CHECK(hipEventCreate(&s->evLoop0));
-  HIP_CHECK(hipEventCreate(&s->evLoop1));
+  s->clock.create();
   return s;
 }
 
@@ -84,8 +77,7 @@ void sb_gmres_free(sb_gmres* s)
 {
   if (!s) return;
   HIP_CHECK(hipStreamSynchronize(g.stream));
-  HIP_CHECK(hipEventDestroy(s->evLoop0));
-  HIP_CHECK(hipEventDestroy(s->evLoop1));
+  s->clock.destroy();
   sb_free(s->V), sb_free(s->w), sb_free(s->r), sb_free(s->x), sb_free(s->b), sb_free(s->Ap), sb_free(s->xexact);
   sb_free(s->l1), sb_free(s->partials), sb_free(s->state), sb_free(s->gv.res_hist), sb_free(s->gv.rr_hist);
   delete s;
@@ -93,7 +85,7 @@ void sb_gmres_free(sb_gmres* s)
 
 void sb_gmres_set_fused(sb_gmres* s, int fused)
 {
-  if (s->started) SB_FATAL("sb_gmres_set_fused between sb_gmres_start and sb_gmres_finish");
+  if (s->clock.open) SB_FATAL("sb_gmres_set_fused between sb_gmres_start and sb_gmres_finish");
   s->fused = fused ? 1 : 0;
 }
 int sb_gmres_restart(const sb_gmres* s) { return s->m; }
@@ -206,29 +198,25 @@ static void gm_step(sb_gmres* s, int j)
 void sb_gmres_start(sb_gmres* s, int itermax, double eps)
 {
   need_init();
-  if (itermax + 2 > s->hist_cap) {
-    sb_free(s->gv.res_hist), sb_free(s->gv.rr_hist);
-    s->hist_cap    = itermax + 2;
-    s->gv.res_hist = (double*)sb_malloc((size_t)s->hist_cap * sizeof(double));
-    s->gv.rr_hist  = (double*)sb_malloc((size_t)s->hist_cap * sizeof(double));
-  }
-  GmScalars h;
-  memset(&h, 0, sizeof h);
+  const int want = std::max(s->hist_cap, itermax + 2);
+  grow(s->gv.res_hist, s->hist_cap, want, 1);
+  grow(s->gv.rr_hist, s->hist_cap, want, 1);
+  s->hist_cap = want;
+  GmScalars h = zeroed<GmScalars>();
   h.eps = eps, h.itermax = itermax, h.hist_cap = s->hist_cap;
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  HIP_CHECK(hipMemcpy(s->gv.S, &h, sizeof h, hipMemcpyHostToDevice));
+  write_block(s->gv.S, &h);
   HIP_CHECK(hipMemsetAsync(s->x, 0, s->ldv * sizeof(double), g.stream)); // x0 = 0
   gm_true_residual(s, nullptr);
   hipLaunchKernelGGL((gm_rr_k<0>), dim3(1), dim3(1024), 0, g.stream, s->nGroups, (const double*)s->partials, 0, s->gv, (const int*)nullptr);
   HIP_CHECK(hipGetLastError());
-  s->pos = 0, s->started = true, s->loop_ms = 0.f;
-  HIP_CHECK(hipEventRecord(s->evLoop0, g.stream));
+  s->pos = 0;
+  s->clock.begin();
 }
 
 void sb_gmres_run_steps(sb_gmres* s, int steps)
 {
   need_init();
-  if (!s->started) SB_FATAL("sb_gmres_run_steps before sb_gmres_start");
+  s->clock.need_open("sb_gmres_run_steps", "sb_gmres_start");
   for (int i = 0; i < steps; i++) {
     gm_step(s, s->pos);
     s->pos = s->pos + 1 == s->m ? 0 : s->pos + 1;
@@ -238,71 +226,50 @@ void sb_gmres_run_steps(sb_gmres* s, int steps)
 int sb_gmres_finish(sb_gmres* s)
 {
   need_init();
-  if (!s->started) SB_FATAL("sb_gmres_finish before sb_gmres_start");
-  HIP_CHECK(hipEventRecord(s->evLoop1, g.stream));
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  GmScalars h;
-  HIP_CHECK(hipMemcpy(&h, s->gv.S, sizeof h, hipMemcpyDeviceToHost));
+  s->clock.need_open("sb_gmres_finish", "sb_gmres_start");
+  s->clock.end();
+  const GmScalars h = read_block(s->gv.S);
   if (h.j > 0) { // the cycle the stop flag (or the caller) left open: x takes its columns, r.r of the final x is recorded
     gm_close<2>(s, h.j, nullptr);
     HIP_CHECK(hipStreamSynchronize(g.stream));
   }
-  HIP_CHECK(hipEventElapsedTime(&s->loop_ms, s->evLoop0, s->evLoop1));
-  s->started = false;
+  s->clock.read();
   return h.k;
 }
 
 int sb_gmres_solve(sb_gmres* s, int itermax, double eps)
 {
   sb_gmres_start(s, itermax, eps);
-  sb_gmres_run_steps(s, itermax > 1 ? itermax - 1 : 0);
+  sb_gmres_run_steps(s, loop_bodies(itermax));
   return sb_gmres_finish(s);
 }
 
 int sb_gmres_history(const sb_gmres* s, double* res_out, int res_cap, double* rr_out, int rr_cap, int* n_rr)
 {
   need_init();
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  GmScalars h;
-  HIP_CHECK(hipMemcpy(&h, s->gv.S, sizeof h, hipMemcpyDeviceToHost));
-  int nres = std::min(std::min(h.n_res, s->hist_cap), res_cap), nrr = std::min(std::min(h.n_rr, s->hist_cap), rr_cap);
-  if (nres > 0) HIP_CHECK(hipMemcpy(res_out, s->gv.res_hist, (size_t)nres * sizeof(double), hipMemcpyDeviceToHost));
-  if (nrr > 0) HIP_CHECK(hipMemcpy(rr_out, s->gv.rr_hist, (size_t)nrr * sizeof(double), hipMemcpyDeviceToHost));
-  if (n_rr) *n_rr = nrr > 0 ? nrr : 0;
-  return nres > 0 ? nres : 0;
+  const GmScalars h = read_block(s->gv.S);
+  const int nrr     = copy_history(s->gv.rr_hist, h.n_rr, s->hist_cap, rr_out, rr_cap);
+  if (n_rr) *n_rr = nrr;
+  return copy_history(s->gv.res_hist, h.n_res, s->hist_cap, res_out, res_cap);
 }
 
 void sb_gmres_solution(const sb_gmres* s, double* x_host)
 {
   need_init();
-  double* tmp = scratch_ws(1, s->n);
-  sb_unpermute(s->A, s->x, tmp);
-  sb_d2h(x_host, tmp, (size_t)s->n * sizeof(double));
+  download_original(s->A, s->x, x_host);
 }
 
 double sb_gmres_check_residual(const sb_gmres* s)
 {
   need_init();
-  if (!s->xexact || s->n == 0) return 0.0;
-  const uint32_t blocks = stream_grid(s->n, 256);
-  double* q             = scratch_partials(blocks);
-  hipLaunchKernelGGL(max_abs_diff_partials, dim3(blocks), dim3(256), 0, g.stream, s->n, (const double*)s->x, (const double*)s->xexact, q);
-  HIP_CHECK(hipGetLastError());
-  std::vector<double> h(blocks);
-  sb_d2h(h.data(), q, blocks * sizeof(double));
-  double mx = 0.0;
-  for (double v : h)
-    if (v > mx) mx = v;
-  return mx;
+  return max_abs_diff_host(s->n, s->x, s->xexact);
 }
 
-double sb_gmres_loop_ms(const sb_gmres* s) { return (double)s->loop_ms; }
+double sb_gmres_loop_ms(const sb_gmres* s) { return (double)s->clock.ms; }
 
 void sb_gmres_counters(const sb_gmres* s, int out[5])
 {
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  GmScalars h;
-  HIP_CHECK(hipMemcpy(&h, s->gv.S, sizeof h, hipMemcpyDeviceToHost));
+  const GmScalars h = read_block(s->gv.S);
   out[0] = h.stop, out[1] = h.steps, out[2] = h.cycles, out[3] = h.n_res, out[4] = h.n_rr;
 }
 

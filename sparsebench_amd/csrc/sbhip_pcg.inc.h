@@ -16,9 +16,7 @@ struct sb_pcg {
   double *rr_hist = nullptr, *rz_hist = nullptr, *pAp_hist = nullptr;
   int hist_cap = 0;
   int k_next = 1;
-  bool started = false;
-  float loop_ms = 0.f;
-  hipEvent_t evLoop0 = nullptr, evLoop1 = nullptr;
+  LoopClock clock;
 };
 
 // the diagonal in the device's row order; bad_dev: NULL, or two uint32 (rows without a finite positive diagonal, the first of
@@ -41,21 +39,11 @@ void sb_matrix_diagonal(const sb_matrix* m, double* d_dev)
   launch_diagonal(m, d_dev, nullptr);
 }
 
-// grid of pcg_update_r_k over n rows (cg_update_r_k<0>'s: 1024 threads, a wave per 256-row group, two workgroups per CU at most)
-static uint32_t pcg_update_r_grid(uint32_t n)
-{
-  const uint32_t nGroups = (n + 255u) >> 8;
-  return std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * 2u, (nGroups + 15u) / 16u));
-}
+// grid of pcg_update_r_k over n rows: vec_stream_grid
 void sb_pcg_update_r_launch(uint32_t n, uint32_t out[3])
 {
   need_init();
-  out[0] = pcg_update_r_grid(n), out[1] = 1024u, out[2] = (uint32_t)g.prop.multiProcessorCount;
-}
-
-static void pcg_need_aligned(const void* a, const void* b, const void* c, const void* d, const char* fn)
-{
-  if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15u) SB_FATAL("%s: vectors must be 16-byte aligned", fn);
+  out[0] = vec_stream_grid(n), out[1] = 1024u, out[2] = (uint32_t)g.prop.multiProcessorCount;
 }
 
 void sb_pcg_update_r_native(uint32_t n, double nalpha, const double* Ap_dev, double* r_dev, const double* dinv_dev, double* z_dev,
@@ -63,35 +51,21 @@ void sb_pcg_update_r_native(uint32_t n, double nalpha, const double* Ap_dev, dou
 {
   need_init();
   if (n == 0) return;
-  pcg_need_aligned(Ap_dev, r_dev, dinv_dev, z_dev, "sb_pcg_update_r_native");
-  PcgScalars h;
-  memset(&h, 0, sizeof h);
+  need_aligned16({ Ap_dev, r_dev, dinv_dev, z_dev }, "sb_pcg_update_r_native", "vectors");
+  PcgScalars h  = zeroed<PcgScalars>();
   h.neg_alpha   = nalpha;
-  PcgScalars* S = (PcgScalars*)sb_malloc(sizeof h);
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  HIP_CHECK(hipMemcpy(S, &h, sizeof h, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(pcg_update_r_k<0>, dim3(pcg_update_r_grid(n)), dim3(1024), 0, g.stream, n, Ap_dev, (const double*)r_dev, r_dev,
+  PcgScalars* S = test_block(h);
+  hipLaunchKernelGGL(pcg_update_r_k<0>, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, Ap_dev, (const double*)r_dev, r_dev,
       dinv_dev, z_dev, (const PcgScalars*)S, l1_rz_dev, l1_rr_dev);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  sb_free(S);
-}
-
-static void pcg_need_tree(const char* fn)
-{
-  if (sb_dot_order() == 1)
-    SB_FATAL("%s: PCG runs in the tree dot order only (the process is in the seq order: SB_DOT_ORDER=seq / sb_set_dot_order(1), "
-             "the validation mode of sb_cg)", fn);
+  test_block_done(S);
 }
 
 sb_pcg* sb_pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const double* dinv_host)
 {
   need_init();
-  if (m->prec != 2) SB_FATAL("sb_pcg_create: PCG: double precision only (the matrix was uploaded in single precision)");
-  if (multi_rank() || sb_comm_size() > 1 || m->nc != m->nr || (halo && halo->externalCount > 0))
-    SB_FATAL("sb_pcg_create: PCG runs on one rank (this process is rank %d of %d, the matrix has %u halo columns)", g.rank, g.size,
-        m->nc - m->nr);
-  pcg_need_tree("sb_pcg_create");
+  need_dp(m, "sb_pcg_create", "PCG");
+  need_one_rank(m, halo, "sb_pcg_create", "PCG");
+  need_tree("sb_pcg_create", "PCG", "sb_cg");
   if (dinv_host)
     for (uint32_t i = 0; i < m->nr; i++)
       if (!(dinv_host[i] > 0.0 && dinv_host[i] < INFINITY))
@@ -102,12 +76,11 @@ sb_pcg* sb_pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, c
   const size_t nb = (size_t)m->nr * sizeof(double);
   double** vecs[] = { &s->r, &s->z, &s->Ap, &s->x, &s->b, &s->dinv, &s->p };
   for (double** v : vecs) *v = (double*)sb_malloc((size_t)m->nc * sizeof(double) + 4096);
-  double* tmp = scratch_ws(0, (size_t)m->nr + 2);
   if (dinv_host) {
-    if (m->nr) sb_h2d(tmp, dinv_host, nb);
-    sb_permute(m, tmp, s->dinv);
-    HIP_CHECK(hipStreamSynchronize(g.stream));
-  } else if (m->nr) { // Jacobi: dinv = 1 / diag(A)
+    upload_permuted(m, dinv_host, s->dinv);
+  } else if (m->nr) { // Jacobi: dinv = 1 / diag(A).  Rows without a finite positive diagonal are counted on the device, by
+                      // diag_*_k's own predicate (BiCGStab's is another one, taken on the host: the two checks stay apart)
+    double* tmp     = scratch_ws(0, m->nr);
     uint32_t bad[2] = { 0u, 0xFFFFFFFFu };
     uint32_t* dbad  = (uint32_t*)sb_malloc(sizeof bad);
     sb_h2d(dbad, bad, sizeof bad);
@@ -121,14 +94,10 @@ sb_pcg* sb_pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, c
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(g.stream));
   }
-  if (m->nr) sb_h2d(tmp, b_host, nb);
-  sb_permute(m, tmp, s->b);
-  HIP_CHECK(hipStreamSynchronize(g.stream));
+  upload_permuted(m, b_host, s->b);
   if (xexact_host) {
     s->xexact = (double*)sb_malloc(nb + 4096);
-    if (m->nr) sb_h2d(tmp, xexact_host, nb);
-    sb_permute(m, tmp, s->xexact);
-    HIP_CHECK(hipStreamSynchronize(g.stream));
+    upload_permuted(m, xexact_host, s->xexact);
   }
   s->S = (PcgScalars*)sb_malloc(sizeof(PcgScalars));
   HIP_CHECK(hipMemset(s->S, 0, sizeof(PcgScalars)));
@@ -139,8 +108,7 @@ sb_pcg* sb_pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, c
     *v = (double*)sb_malloc(lb);
     HIP_CHECK(hipMemsetAsync(*v, 0, lb, g.stream));
   }
-  HIP_CHECK(hipEventCreate(&s->evLoop0));
-  HIP_CHECK(hipEventCreate(&s->evLoop1));
+  s->clock.create();
   HIP_CHECK(hipStreamSynchronize(g.stream));
   return s;
 }
@@ -149,8 +117,7 @@ void sb_pcg_free(sb_pcg* s)
 {
   if (!s) return;
   HIP_CHECK(hipStreamSynchronize(g.stream));
-  HIP_CHECK(hipEventDestroy(s->evLoop0));
-  HIP_CHECK(hipEventDestroy(s->evLoop1));
+  s->clock.destroy();
   sb_free(s->r), sb_free(s->z), sb_free(s->p), sb_free(s->Ap), sb_free(s->x), sb_free(s->b), sb_free(s->dinv), sb_free(s->xexact);
   sb_free(s->S), sb_free(s->l1pAp), sb_free(s->l1rz), sb_free(s->l1rr), sb_free(s->rr_hist), sb_free(s->rz_hist), sb_free(s->pAp_hist);
   delete s;
@@ -183,14 +150,14 @@ static void pcg_body(sb_pcg* s, int k)
   } else {
     launch_spmv(s->A, s->p, s->Ap, nullptr, stop);
     if (n) {
-      hipLaunchKernelGGL(dot_l1_k, dim3(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * 2u, (s->nGroups + 15u) / 16u))),
-          dim3(1024), 0, g.stream, n, (const double*)s->p, (const double*)s->Ap, s->l1pAp, stop);
+      hipLaunchKernelGGL(dot_l1_k, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, (const double*)s->p, (const double*)s->Ap,
+          s->l1pAp, stop);
       HIP_CHECK(hipGetLastError());
     }
   }
   pcg_scalar_launch<2>(s);
   if (n) {
-    hipLaunchKernelGGL(pcg_update_r_k<0>, dim3(pcg_update_r_grid(n)), dim3(1024), 0, g.stream, n, (const double*)s->Ap,
+    hipLaunchKernelGGL(pcg_update_r_k<0>, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, (const double*)s->Ap,
         (const double*)s->r, s->r, (const double*)s->dinv, s->z, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
     HIP_CHECK(hipGetLastError());
   }
@@ -200,52 +167,39 @@ static void pcg_body(sb_pcg* s, int k)
 void sb_pcg_start(sb_pcg* s, int itermax, double eps)
 {
   need_init();
-  pcg_need_tree("sb_pcg_start");
-  if (itermax + 2 > s->hist_cap) {
-    sb_free(s->rr_hist), sb_free(s->rz_hist), sb_free(s->pAp_hist);
-    s->hist_cap = itermax + 2;
-    const size_t hb = (size_t)s->hist_cap * sizeof(double);
-    s->rr_hist = (double*)sb_malloc(hb), s->rz_hist = (double*)sb_malloc(hb), s->pAp_hist = (double*)sb_malloc(hb);
-  }
-  PcgScalars h;
-  memset(&h, 0, sizeof h);
+  need_tree("sb_pcg_start", "PCG", "sb_cg");
+  const int want = std::max(s->hist_cap, itermax + 2);
+  for (double** hist : { &s->rr_hist, &s->rz_hist, &s->pAp_hist }) grow(*hist, s->hist_cap, want, 1);
+  s->hist_cap  = want;
+  PcgScalars h = zeroed<PcgScalars>();
   h.itermax = itermax, h.eps = eps, h.hist_cap = s->hist_cap;
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  HIP_CHECK(hipMemcpy(s->S, &h, sizeof h, hipMemcpyHostToDevice));
+  write_block(s->S, &h);
   // prologue: x0 = 0, p = 1.0 x + 0.0 x = 0, Ap = A p, r = 1.0 b + (-1.0) Ap, z = r o dinv, r.r, r.z, the loop test for k = 1
   HIP_CHECK(hipMemsetAsync(s->x, 0, (size_t)s->nr * sizeof(double), g.stream));
   HIP_CHECK(hipMemsetAsync(s->p, 0, (size_t)s->nc * sizeof(double), g.stream));
   launch_spmv(s->A, s->p, s->Ap, nullptr, nullptr);
   if (s->nr) {
-    hipLaunchKernelGGL(pcg_update_r_k<1>, dim3(pcg_update_r_grid(s->nr)), dim3(1024), 0, g.stream, s->nr, (const double*)s->Ap,
+    hipLaunchKernelGGL(pcg_update_r_k<1>, dim3(vec_stream_grid(s->nr)), dim3(1024), 0, g.stream, s->nr, (const double*)s->Ap,
         (const double*)s->b, s->r, (const double*)s->dinv, s->z, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
     HIP_CHECK(hipGetLastError());
   }
   pcg_scalar_launch<0>(s);
-  s->k_next = 1, s->started = true, s->loop_ms = 0.f;
-  HIP_CHECK(hipEventRecord(s->evLoop0, g.stream));
+  s->k_next = 1;
+  s->clock.begin();
 }
 
 void sb_pcg_run_iters(sb_pcg* s, int iters)
 {
   need_init();
-  if (!s->started) SB_FATAL("sb_pcg_run_iters before sb_pcg_start");
+  s->clock.need_open("sb_pcg_run_iters", "sb_pcg_start");
   for (int i = 0; i < iters; i++) pcg_body(s, s->k_next++);
-}
-
-static PcgScalars pcg_control(const sb_pcg* s)
-{
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  PcgScalars h;
-  HIP_CHECK(hipMemcpy(&h, s->S, sizeof h, hipMemcpyDeviceToHost));
-  return h;
 }
 
 int sb_pcg_finish(sb_pcg* s)
 {
   need_init();
-  if (!s->started) SB_FATAL("sb_pcg_finish before sb_pcg_start");
-  HIP_CHECK(hipEventRecord(s->evLoop1, g.stream));
+  s->clock.need_open("sb_pcg_finish", "sb_pcg_start");
+  s->clock.end();
   if (s->nr) { // the x update the last body left to "the next p update": nobody comes after it
     hipLaunchKernelGGL(pcg_x_finalize, dim3(stream_grid(s->nr, 256)), dim3(256), 0, g.stream, s->nr, s->x, (const double*)s->p,
         (const PcgScalars*)s->S);
@@ -253,72 +207,52 @@ int sb_pcg_finish(sb_pcg* s)
     HIP_CHECK(hipGetLastError());
   }
   HIP_CHECK(hipStreamSynchronize(g.stream));
-  HIP_CHECK(hipEventElapsedTime(&s->loop_ms, s->evLoop0, s->evLoop1));
-  s->started = false;
-  return pcg_control(s).iters + 1; // the value of k when the for loop exits
+  s->clock.read();
+  return read_block(s->S).iters + 1; // the value of k when the for loop exits
 }
 
 int sb_pcg_solve(sb_pcg* s, int itermax, double eps)
 {
   sb_pcg_start(s, itermax, eps);
-  sb_pcg_run_iters(s, itermax > 1 ? itermax - 1 : 0);
+  sb_pcg_run_iters(s, loop_bodies(itermax));
   return sb_pcg_finish(s);
 }
 
 int sb_pcg_history(const sb_pcg* s, double* rr_out, int rr_cap, double* rz_out, int rz_cap, double* pAp_out, int pAp_cap, int* n_pAp)
 {
   need_init();
-  const PcgScalars h = pcg_control(s);
-  int nrr = std::min(std::min(h.n_rr, s->hist_cap), std::min(rr_cap, rz_cap)), npa = std::min(std::min(h.n_pAp, s->hist_cap), pAp_cap);
-  if (nrr > 0) {
-    HIP_CHECK(hipMemcpy(rr_out, s->rr_hist, (size_t)nrr * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(rz_out, s->rz_hist, (size_t)nrr * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  if (npa > 0) HIP_CHECK(hipMemcpy(pAp_out, s->pAp_hist, (size_t)npa * sizeof(double), hipMemcpyDeviceToHost));
-  if (n_pAp) *n_pAp = npa > 0 ? npa : 0;
-  return nrr > 0 ? nrr : 0;
+  const PcgScalars h = read_block(s->S);
+  const int cap = std::min(rr_cap, rz_cap); // rr and rz come in pairs
+  const int nrr = copy_history(s->rr_hist, h.n_rr, s->hist_cap, rr_out, cap);
+  copy_history(s->rz_hist, h.n_rr, s->hist_cap, rz_out, cap);
+  const int npa = copy_history(s->pAp_hist, h.n_pAp, s->hist_cap, pAp_out, pAp_cap);
+  if (n_pAp) *n_pAp = npa;
+  return nrr;
 }
 
-static void pcg_to_host_orig(const sb_pcg* s, const double* v_dev, double* v_host)
-{
-  if (s->nr == 0) return;
-  double* tmp = scratch_ws(1, s->nr);
-  sb_unpermute(s->A, v_dev, tmp);
-  sb_d2h(v_host, tmp, (size_t)s->nr * sizeof(double));
-}
 void sb_pcg_solution(const sb_pcg* s, double* x_host)
 {
   need_init();
-  pcg_to_host_orig(s, s->x, x_host);
+  download_original(s->A, s->x, x_host);
 }
 void sb_pcg_dinv(const sb_pcg* s, double* dinv_host)
 {
   need_init();
-  pcg_to_host_orig(s, s->dinv, dinv_host);
+  download_original(s->A, s->dinv, dinv_host);
 }
 
 // max|x - xexact| (solverCheckResidual, src/CGSolver.c:40-60); 0.0 without an exact solution
 double sb_pcg_check_residual(const sb_pcg* s)
 {
   need_init();
-  if (!s->xexact || s->nr == 0) return 0.0;
-  const uint32_t blocks = stream_grid(s->nr, 256);
-  double* q             = scratch_partials(blocks);
-  hipLaunchKernelGGL(max_abs_diff_partials, dim3(blocks), dim3(256), 0, g.stream, s->nr, (const double*)s->x, (const double*)s->xexact, q);
-  HIP_CHECK(hipGetLastError());
-  std::vector<double> h(blocks);
-  sb_d2h(h.data(), q, blocks * sizeof(double));
-  double mx = 0.0;
-  for (double v : h)
-    if (v > mx) mx = v;
-  return mx;
+  return max_abs_diff_host(s->nr, s->x, s->xexact);
 }
 
-double sb_pcg_loop_ms(const sb_pcg* s) { return (double)s->loop_ms; }
+double sb_pcg_loop_ms(const sb_pcg* s) { return (double)s->clock.ms; }
 
 // stop, stop_next, iters, n_rr (= entries of rz too), n_pAp of the device control block
 void sb_pcg_counters(const sb_pcg* s, int out[5])
 {
-  const PcgScalars h = pcg_control(s);
+  const PcgScalars h = read_block(s->S);
   out[0] = h.stop, out[1] = h.stop_next, out[2] = h.iters, out[3] = h.n_rr, out[4] = h.n_pAp;
 }

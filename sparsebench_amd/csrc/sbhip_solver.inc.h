@@ -1,0 +1,163 @@
+// sbhip_solver.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context): the host
+// plumbing every solver handle repeats around its own kernels ("One definition per solver plumbing step").  Plain
+// functions; what a solver does between them (its prologue, body and epilogue) stays in its own file.
+// ===========================================================================
+// solver plumbing
+// ===========================================================================
+
+// --- refusals at create / start -------------------------------------------------------------------------------------------
+static void need_dp(const sb_matrix* m, const char* fn, const char* who)
+{
+  if (m->prec != 2) SB_FATAL("%s: %s: double precision only (the matrix was uploaded in single precision)", fn, who);
+}
+// halo: NULL where the entry point ignores its halo plan
+static void need_one_rank(const sb_matrix* m, const sb_halo* halo, const char* fn, const char* who)
+{
+  if (multi_rank() || sb_comm_size() > 1 || m->nc != m->nr || (halo && halo->externalCount > 0))
+    SB_FATAL("%s: %s runs on one rank (this process is rank %d of %d, the matrix has %u halo columns)", fn, who, g.rank, g.size,
+        m->nc - m->nr);
+}
+// seq_owner: whose validation mode the sequential order is, as the message names it
+static void need_tree(const char* fn, const char* who, const char* seq_owner)
+{
+  if (sb_dot_order() == 1)
+    SB_FATAL("%s: %s runs in the tree dot order only (the process is in the seq order: SB_DOT_ORDER=seq / sb_set_dot_order(1), "
+             "the validation mode of %s)", fn, who, seq_owner);
+}
+// what: "vectors" or "block vectors"
+static void need_aligned16(std::initializer_list<const void*> ptrs, const char* fn, const char* what)
+{
+  uintptr_t bits = 0;
+  for (const void* q : ptrs) bits |= (uintptr_t)q;
+  if (bits & 15u) SB_FATAL("%s: %s must be 16-byte aligned", fn, what);
+}
+
+// --- vectors between the caller's row order and the device's ----------------------------------------------------------------
+static void upload_permuted(const sb_matrix* m, const double* host, double* dev)
+{
+  if (m->nr == 0) return;
+  double* tmp = scratch_ws(0, m->nr);
+  sb_h2d(tmp, host, (size_t)m->nr * sizeof(double));
+  sb_permute(m, tmp, dev);
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+}
+static void download_original(const sb_matrix* m, const double* dev, double* host)
+{
+  if (m->nr == 0) return;
+  double* tmp = scratch_ws(1, m->nr);
+  sb_unpermute(m, dev, tmp);
+  sb_d2h(host, tmp, (size_t)m->nr * sizeof(double));
+}
+
+// --- device control blocks ------------------------------------------------------------------------------------------------
+template <class S> static S zeroed()
+{
+  S h;
+  memset(&h, 0, sizeof h);
+  return h;
+}
+// both wait for the stream first: the block is read and written by the kernels in flight
+template <class S> static S read_block(const S* dev)
+{
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  S h;
+  HIP_CHECK(hipMemcpy(&h, dev, sizeof h, hipMemcpyDeviceToHost));
+  return h;
+}
+template <class S> static void write_block(S* dev, const S* h, size_t count = 1)
+{
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  HIP_CHECK(hipMemcpy(dev, h, sizeof(S) * count, hipMemcpyHostToDevice));
+}
+// a throw-away control block for a blocking test entry: test_block | the kernel launch | test_block_done
+template <class S> static S* test_block(const S& h)
+{
+  S* dev = (S*)sb_malloc(sizeof h);
+  write_block(dev, &h);
+  return dev;
+}
+template <class S> static void test_block_done(S* dev)
+{
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  sb_free(dev);
+}
+
+// --- the loop between *_start and *_finish ----------------------------------------------------------------------------------
+// start ends with begin(); finish records end(), enqueues and waits for its epilogue, then read()s
+namespace {
+struct LoopClock {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  float ms      = 0.f;
+  bool open     = false; // between begin() and read()
+  void create()
+  {
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+  }
+  void destroy()
+  {
+    HIP_CHECK(hipEventDestroy(e0));
+    HIP_CHECK(hipEventDestroy(e1));
+  }
+  void begin()
+  {
+    ms = 0.f, open = true;
+    HIP_CHECK(hipEventRecord(e0, g.stream));
+  }
+  void end() { HIP_CHECK(hipEventRecord(e1, g.stream)); }
+  void read() // after the stream has been waited for
+  {
+    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    open = false;
+  }
+  void need_open(const char* fn, const char* start_fn) const
+  {
+    if (!open) SB_FATAL("%s before %s", fn, start_fn);
+  }
+};
+} // namespace
+
+// bodies of a whole solve: the reference's loop runs k = 1 .. itermax - 1 (src/CGSolver.c:107)
+static int loop_bodies(int itermax) { return itermax > 1 ? itermax - 1 : 0; }
+
+// --- histories --------------------------------------------------------------------------------------------------------------
+// room for `per` histories of `want` entries each where `have` entries are not enough (the contents are not kept)
+static void grow(double*& buf, int have, int want, size_t per)
+{
+  if (want <= have) return;
+  sb_free(buf);
+  buf = (double*)sb_malloc(per * (size_t)want * sizeof(double));
+}
+// the first min(have, hist_cap, cap) entries; returns the entries copied
+static int copy_history(const double* dev, int have, int hist_cap, double* out, int cap)
+{
+  const int cnt = std::min(std::min(have, hist_cap), cap);
+  if (cnt <= 0) return 0;
+  HIP_CHECK(hipMemcpy(out, dev, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost));
+  return cnt;
+}
+
+// --- max|x - xexact| on this rank (solverCheckResidual, src/CGSolver.c:40-60); 0.0 without an exact solution ----------------
+static double max_abs_diff_host(uint32_t n, const double* x, const double* xexact)
+{
+  if (!xexact || n == 0) return 0.0;
+  const uint32_t blocks = stream_grid(n, 256);
+  double* q             = scratch_partials(blocks);
+  hipLaunchKernelGGL(max_abs_diff_partials, dim3(blocks), dim3(256), 0, g.stream, n, x, xexact, q);
+  HIP_CHECK(hipGetLastError());
+  std::vector<double> h(blocks);
+  sb_d2h(h.data(), q, blocks * sizeof(double));
+  double mx = 0.0;
+  for (double v : h)
+    if (v > mx) mx = v;
+  return mx;
+}
+
+// --- grid of the 1024-thread streaming kernels over n rows (cg_update_r_k<0>'s, dot_l1_k's): a wave per 256-row group, two
+// workgroups per CU at most ------------------------------------------------------------------------------------------------
+static uint32_t vec_stream_grid(uint32_t n)
+{
+  const uint32_t nGroups = (n + 255u) >> 8;
+  return std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * 2u, (nGroups + 15u) / 16u));
+}

@@ -38,6 +38,17 @@ static const char* kHelp =
     "  -C <int>   Sell-C-sigma chunk height (SCS build). Default 64.\n"
     "  -s <int>   Sell-C-sigma sorting scope (SCS build). Default 1.\n";
 
+/* a solver the single-precision driver does not have: its message, exit status 1 */
+static void dp_only(const char* msg)
+{
+#if PRECISION == 1
+  fputs(msg, stderr);
+  exit(1);
+#else
+  (void)msg;
+#endif
+}
+
 int main(int argc, char** argv)
 {
   Parameter param;
@@ -63,26 +74,14 @@ int main(int argc, char** argv)
       if (strcmp(optarg, "cg") == 0) type = CG;
       else if (strcmp(optarg, "spmv") == 0) type = SPMV;
       else if (strcmp(optarg, "gmres") == 0) {
-#if PRECISION == 1
-        fprintf(stderr, "GMRES: double precision only\n");
-        return 1;
-#else
+        dp_only("GMRES: double precision only\n");
         type = GMRES;
-#endif
       } else if (strcmp(optarg, "pcg") == 0) {
-#if PRECISION == 1
-        fprintf(stderr, "PCG: double precision only\n");
-        return 1;
-#else
+        dp_only("PCG: double precision only\n");
         type = PCG;
-#endif
       } else if (strcmp(optarg, "bicgstab") == 0) {
-#if PRECISION == 1
-        fprintf(stderr, "BiCGStab: double precision only\n");
-        return 1;
-#else
+        dp_only("BiCGStab: double precision only\n");
         type = BICGSTAB;
-#endif
       } else {
         printf("Unknown solver type %s\n", optarg);
         return 1;

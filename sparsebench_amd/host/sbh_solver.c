@@ -90,6 +90,67 @@ void sbh_spmv(void* dev_matrix, CG_UINT nr, CG_UINT nc, const CG_FLOAT* x, CG_FL
   stage_out(&sx, NULL, nc);
 }
 
+/* ---- what the solvers below share around their sb_*_solve -------------------------------- */
+/* All but solveCG exist in the double-precision libraries only: the single-precision build refuses at the call. */
+static void dp_only(const char* msg)
+{
+#if PRECISION == 1
+  fputs(msg, stderr);
+  exit(EXIT_FAILURE);
+#else
+  (void)msg;
+#endif
+}
+
+/* initVectors, src/CGSolver.c:25-36, into fresh host arrays: *b has room for ncols right-hand sides of nr rows (the first one
+ * is filled), *xexact is NULL for a matrix that was read from a file */
+static void init_vectors_dp(const Parameter* param, CG_UINT nr, const CG_UINT* rowNnz, int ncols, double** b, double** xexact)
+{
+  const int generated = strcmp(param->filename, "generate") == 0 || strcmp(param->filename, "generate7P") == 0;
+  *b                  = (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr * ncols + 1) * sizeof(double));
+  *xexact             = generated ? (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double)) : NULL;
+  for (CG_UINT i = 0; i < nr; i++) {
+    if (generated) {
+      (*b)[i]      = 27.0 - ((double)((int)rowNnz[i] - 1));
+      (*xexact)[i] = 1.0;
+    } else {
+      (*b)[i] = 1.0;
+    }
+  }
+}
+
+static int print_freq(int itermax) /* src/CGSolver.c:85-91 */
+{
+  const int f = itermax / 10;
+  return f > 50 ? 50 : f < 1 ? 1 : f;
+}
+
+/* The lines solveCG prints while iterating (src/CGSolver.c:100,:116-118) for a solve that left its loop at k, from a recorded
+ * history v of n entries.  rr != 0: v holds r.r, iteration j shows the residual it starts from, sqrt(v[j - 1]).  rr == 0: v
+ * holds GMRES's residual estimates, iteration j shows the one after its step, v[j]. */
+static void print_history(Comm* comm, const char* prefix, int k, int itermax, const double* v, int n, int rr)
+{
+  if (!commIsMaster(comm)) return;
+  const int printFreq = print_freq(itermax);
+  printf("%sInitial Residual = %E\n", prefix, n > 0 ? (rr ? sqrt(v[0]) : v[0]) : 0.0);
+  for (int j = 1; j < k; j++)
+    if (j % printFreq == 0 || j + 1 == itermax) {
+      const int idx = rr ? j - 1 : j;
+      if (idx < n) printf("%sIteration = %d Residual = %E\n", prefix, j, rr ? sqrt(v[idx]) : v[idx]);
+    }
+}
+
+/* solveCG's closing line and solverCheckResidual's (:40-60); the loop's kernels overlap regions, so the profiler table's SpMV
+ * row carries the loop */
+static void print_tail(Comm* comm, int k, double loop_ms, int have_exact, double diff)
+{
+  if (commIsMaster(comm)) {
+    printf("Solution performed %d iterations and took %.2fs\n", k, 1e-3 * loop_ms);
+    if (have_exact) printf("Difference between computed and exact  = %f\n", diff);
+  }
+  _t[SPMVM] += 1e-3 * loop_ms;
+}
+
 /* ---- solveCG --------------------------------------------------------------------------- */
 /* src/CGSolver.c:62-141.  The whole loop runs in the HIP layer without host round
  * trips; the lines the reference prints while iterating are printed afterwards from
@@ -126,9 +187,7 @@ static int sbh_solve(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
   double* pAp   = (double*)malloc((size_t)cap * sizeof(double));
   int nPAp      = 0;
   const int nRr = sb_cg_history(cg, rr, cap, pAp, cap, &nPAp);
-  int printFreq = itermax / 10; /* :85-91 */
-  if (printFreq > 50) printFreq = 50;
-  if (printFreq < 1) printFreq = 1;
+  const int printFreq = print_freq(itermax);
   if (commIsMaster(comm)) {
     /* normr is a CG_FLOAT: sqrt in double, stored to CG_FLOAT (src/CGSolver.c:100,116) */
     printf("Initial Residual = %E\n", nRr > 0 ? (CG_FLOAT)sqrt(rr[0]) : 0.0);
@@ -177,50 +236,23 @@ int sbh_solve_cg_perm(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr
  * the step taken at counter j. */
 int sbh_solve_gmres(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int restart)
 {
-#if PRECISION == 1
-  (void)comm, (void)param, (void)dev_matrix, (void)nr, (void)rowNnz, (void)restart;
-  fprintf(stderr, "GMRES: double precision only\n");
-  exit(EXIT_FAILURE);
-#else
-  const int itermax   = param->itermax;
-  const int generated = strcmp(param->filename, "generate") == 0 || strcmp(param->filename, "generate7P") == 0;
-  double* b           = (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double));
-  double* xexact      = generated ? (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double)) : NULL;
-  for (CG_UINT i = 0; i < nr; i++) { /* initVectors, src/CGSolver.c:25-36 */
-    if (generated) {
-      b[i]      = 27.0 - ((double)((int)rowNnz[i] - 1));
-      xexact[i] = 1.0;
-    } else {
-      b[i] = 1.0;
-    }
-  }
+  dp_only("GMRES: double precision only\n");
+  const int itermax = param->itermax, cap = itermax + 2;
+  double *b, *xexact;
+  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
   sb_gmres* s       = sb_gmres_create((const sb_matrix*)dev_matrix, NULL, b, xexact, restart);
   const char* fused = getenv("SB_FUSED");
   if (fused) sb_gmres_set_fused(s, atoi(fused));
-  const int k   = sb_gmres_solve(s, itermax, param->eps);
-  const int cap = itermax + 2;
-  double* res   = (double*)malloc((size_t)cap * sizeof(double));
-  double* rr    = (double*)malloc((size_t)cap * sizeof(double));
-  int nRr       = 0;
+  const int k    = sb_gmres_solve(s, itermax, param->eps);
+  double* res    = (double*)malloc((size_t)cap * sizeof(double));
+  double* rr     = (double*)malloc((size_t)cap * sizeof(double));
+  int nRr        = 0;
   const int nRes = sb_gmres_history(s, res, cap, rr, cap, &nRr);
-  int printFreq  = itermax / 10; /* src/CGSolver.c:85-91 */
-  if (printFreq > 50) printFreq = 50;
-  if (printFreq < 1) printFreq = 1;
-  if (commIsMaster(comm)) {
-    printf("Initial Residual = %E\n", nRes > 0 ? res[0] : 0.0);
-    for (int j = 1; j < k; j++)
-      if ((j % printFreq == 0 || j + 1 == itermax) && j < nRes) printf("Iteration = %d Residual = %E\n", j, res[j]);
-    printf("Solution performed %d iterations and took %.2fs\n", k, 1e-3 * sb_gmres_loop_ms(s));
-  }
-  if (xexact) {
-    const double diff = sb_gmres_check_residual(s);
-    if (commIsMaster(comm)) printf("Difference between computed and exact  = %f\n", diff);
-  }
-  _t[SPMVM] += 1e-3 * sb_gmres_loop_ms(s); /* the loop's kernels overlap regions: the table's SpMV row carries the loop */
+  print_history(comm, "", k, itermax, res, nRes, 0);
+  print_tail(comm, k, sb_gmres_loop_ms(s), xexact != NULL, sb_gmres_check_residual(s));
   sb_gmres_free(s);
   free(res), free(rr), free(b), free(xexact);
   return k;
-#endif
 }
 
 /* ---- solveCGBatch ------------------------------------------------------------------------ */
@@ -229,58 +261,33 @@ int sbh_solve_gmres(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, 
  * solveCG prints come per column, prefixed "RHS c: ", from the recorded histories. */
 int sbh_solve_cg_batch(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, CG_UINT startRow, int nrhs)
 {
-#if PRECISION == 1
-  (void)comm, (void)param, (void)dev_matrix, (void)nr, (void)rowNnz, (void)startRow, (void)nrhs;
-  fprintf(stderr, "batched CG: double precision only\n");
-  exit(EXIT_FAILURE);
-#else
-  const int itermax   = param->itermax;
-  const int generated = strcmp(param->filename, "generate") == 0 || strcmp(param->filename, "generate7P") == 0;
-  const int nv        = nrhs > 0 ? nrhs : 1; /* (a width the layer does not have is refused by sb_cgb_create, with its message) */
-  double* B           = (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr * nv + 1) * sizeof(double));
-  double* xexact      = generated ? (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double)) : NULL;
-  for (CG_UINT i = 0; i < nr; i++) { /* initVectors, src/CGSolver.c:25-36 */
-    if (generated) {
-      B[i]      = 27.0 - ((double)((int)rowNnz[i] - 1));
-      xexact[i] = 1.0;
-    } else {
-      B[i] = 1.0;
-    }
-  }
+  dp_only("batched CG: double precision only\n");
+  const int itermax = param->itermax, cap = itermax + 2;
+  const int nv      = nrhs > 0 ? nrhs : 1; /* (a width the layer does not have is refused by sb_cgb_create, with its message) */
+  double *B, *xexact;
+  init_vectors_dp(param, nr, rowNnz, nv, &B, &xexact);
   for (int c = 1; c < nv; c++)
     for (CG_UINT i = 0; i < nr; i++) B[(size_t)c * nr + i] = B[i] + (double)c * (double)((int)(((size_t)startRow + i) % 5) - 2);
   sb_cgb* s   = sb_cgb_create((const sb_matrix*)dev_matrix, NULL, nrhs, B, xexact);
   const int k = sb_cgb_solve(s, itermax, param->eps);
-  const int cap = itermax + 2;
-  double* rr    = (double*)malloc((size_t)cap * sizeof(double));
-  double* pAp   = (double*)malloc((size_t)cap * sizeof(double));
-  int printFreq = itermax / 10; /* :85-91 */
-  if (printFreq > 50) printFreq = 50;
-  if (printFreq < 1) printFreq = 1;
+  double* rr  = (double*)malloc((size_t)cap * sizeof(double));
+  double* pAp = (double*)malloc((size_t)cap * sizeof(double));
   if (commIsMaster(comm)) {
     for (int c = 0; c < nv; c++) {
+      char prefix[32];
+      snprintf(prefix, sizeof prefix, "RHS %d: ", c);
       int nPAp      = 0;
       const int nRr = sb_cgb_history(s, c, rr, cap, pAp, cap, &nPAp);
       const int kc  = sb_cgb_iterations(s, c);
-      printf("RHS %d: Initial Residual = %E\n", c, nRr > 0 ? sqrt(rr[0]) : 0.0);
-      for (int j = 1; j < kc; j++)
-        if (j % printFreq == 0 || j + 1 == itermax) {
-          const int idx = j == 1 ? 0 : j - 1;
-          if (idx < nRr) printf("RHS %d: Iteration = %d Residual = %E\n", c, j, sqrt(rr[idx]));
-        }
+      print_history(comm, prefix, kc, itermax, rr, nRr, 1);
       printf("RHS %d: Solution performed %d iterations\n", c, kc);
     }
-    printf("Solution performed %d iterations and took %.2fs\n", k, 1e-3 * sb_cgb_loop_ms(s));
   }
-  if (xexact) { /* solverCheckResidual, :40-60, for the column that has an exact solution */
-    const double diff = sb_cgb_check_residual(s, 0);
-    if (commIsMaster(comm)) printf("Difference between computed and exact  = %f\n", diff);
-  }
-  _t[SPMVM] += 1e-3 * sb_cgb_loop_ms(s); /* the loop's kernels overlap regions: the table's SpMV row carries the loop */
+  /* (the difference is for column 0, the one that has an exact solution) */
+  print_tail(comm, k, sb_cgb_loop_ms(s), xexact != NULL, sb_cgb_check_residual(s, 0));
   sb_cgb_free(s);
   free(rr), free(pAp), free(B), free(xexact);
   return k;
-#endif
 }
 
 /* ---- solvePCG ---------------------------------------------------------------------------- */
@@ -288,52 +295,22 @@ int sbh_solve_cg_batch(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT n
  * afterwards from the recorded r.r history, indexed as solveCG's own. */
 int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
 {
-#if PRECISION == 1
-  (void)comm, (void)param, (void)dev_matrix, (void)nr, (void)rowNnz;
-  fprintf(stderr, "PCG: double precision only\n");
-  exit(EXIT_FAILURE);
-#else
-  const int itermax   = param->itermax;
-  const int generated = strcmp(param->filename, "generate") == 0 || strcmp(param->filename, "generate7P") == 0;
-  double* b           = (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double));
-  double* xexact      = generated ? (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double)) : NULL;
-  for (CG_UINT i = 0; i < nr; i++) { /* initVectors, src/CGSolver.c:25-36 */
-    if (generated) {
-      b[i]      = 27.0 - ((double)((int)rowNnz[i] - 1));
-      xexact[i] = 1.0;
-    } else {
-      b[i] = 1.0;
-    }
-  }
+  dp_only("PCG: double precision only\n");
+  const int itermax = param->itermax, cap = itermax + 2;
+  double *b, *xexact;
+  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
   sb_pcg* s     = sb_pcg_create((const sb_matrix*)dev_matrix, NULL, b, xexact, NULL);
   const int k   = sb_pcg_solve(s, itermax, param->eps);
-  const int cap = itermax + 2;
   double* rr    = (double*)malloc((size_t)cap * sizeof(double));
   double* rz    = (double*)malloc((size_t)cap * sizeof(double));
   double* pAp   = (double*)malloc((size_t)cap * sizeof(double));
   int nPAp      = 0;
   const int nRr = sb_pcg_history(s, rr, cap, rz, cap, pAp, cap, &nPAp);
-  int printFreq = itermax / 10; /* :85-91 */
-  if (printFreq > 50) printFreq = 50;
-  if (printFreq < 1) printFreq = 1;
-  if (commIsMaster(comm)) {
-    printf("Initial Residual = %E\n", nRr > 0 ? sqrt(rr[0]) : 0.0);
-    for (int j = 1; j < k; j++)
-      if (j % printFreq == 0 || j + 1 == itermax) {
-        const int idx = j == 1 ? 0 : j - 1;
-        if (idx < nRr) printf("Iteration = %d Residual = %E\n", j, sqrt(rr[idx]));
-      }
-    printf("Solution performed %d iterations and took %.2fs\n", k, 1e-3 * sb_pcg_loop_ms(s));
-  }
-  if (xexact) { /* solverCheckResidual, :40-60 */
-    const double diff = sb_pcg_check_residual(s);
-    if (commIsMaster(comm)) printf("Difference between computed and exact  = %f\n", diff);
-  }
-  _t[SPMVM] += 1e-3 * sb_pcg_loop_ms(s); /* the loop's kernels overlap regions: the table's SpMV row carries the loop */
+  print_history(comm, "", k, itermax, rr, nRr, 1);
+  print_tail(comm, k, sb_pcg_loop_ms(s), xexact != NULL, sb_pcg_check_residual(s));
   sb_pcg_free(s);
   free(rr), free(rz), free(pAp), free(b), free(xexact);
   return k;
-#endif
 }
 
 /* ---- solveBiCGStab ----------------------------------------------------------------------- */
@@ -342,48 +319,19 @@ int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, co
  * residual iteration j starts from, sqrt(rr[j - 1]), as solveCG and solvePCG do. */
 int sbh_solve_bicgstab(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
 {
-#if PRECISION == 1
-  (void)comm, (void)param, (void)dev_matrix, (void)nr, (void)rowNnz;
-  fprintf(stderr, "BiCGStab: double precision only\n");
-  exit(EXIT_FAILURE);
-#else
-  const int itermax   = param->itermax;
-  const int generated = strcmp(param->filename, "generate") == 0 || strcmp(param->filename, "generate7P") == 0;
-  double* b           = (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double));
-  double* xexact      = generated ? (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double)) : NULL;
-  for (CG_UINT i = 0; i < nr; i++) { /* initVectors, src/CGSolver.c:25-36 */
-    if (generated) {
-      b[i]      = 27.0 - ((double)((int)rowNnz[i] - 1));
-      xexact[i] = 1.0;
-    } else {
-      b[i] = 1.0;
-    }
-  }
+  dp_only("BiCGStab: double precision only\n");
+  const int itermax = param->itermax, cap = itermax + 2;
+  double *b, *xexact;
+  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
   sb_bicgstab* s = sb_bicgstab_create((const sb_matrix*)dev_matrix, NULL, b, xexact, 1, NULL);
   const int k    = sb_bicgstab_solve(s, itermax, param->eps);
-  const int cap  = itermax + 2;
   double* rr     = (double*)malloc((size_t)cap * sizeof(double));
   const int nRr  = sb_bicgstab_history(s, 0, rr, cap);
-  int printFreq  = itermax / 10; /* :85-91 */
-  if (printFreq > 50) printFreq = 50;
-  if (printFreq < 1) printFreq = 1;
-  if (commIsMaster(comm)) {
-    printf("Initial Residual = %E\n", nRr > 0 ? sqrt(rr[0]) : 0.0);
-    for (int j = 1; j < k; j++)
-      if (j % printFreq == 0 || j + 1 == itermax) {
-        if (j - 1 < nRr) printf("Iteration = %d Residual = %E\n", j, sqrt(rr[j - 1]));
-      }
-    printf("Solution performed %d iterations and took %.2fs\n", k, 1e-3 * sb_bicgstab_loop_ms(s));
-  }
-  if (xexact) { /* solverCheckResidual, :40-60 */
-    const double diff = sb_bicgstab_check_residual(s);
-    if (commIsMaster(comm)) printf("Difference between computed and exact  = %f\n", diff);
-  }
-  _t[SPMVM] += 1e-3 * sb_bicgstab_loop_ms(s); /* the loop's kernels overlap regions: the table's SpMV row carries the loop */
+  print_history(comm, "", k, itermax, rr, nRr, 1);
+  print_tail(comm, k, sb_bicgstab_loop_ms(s), xexact != NULL, sb_bicgstab_check_residual(s));
   sb_bicgstab_free(s);
   free(rr), free(b), free(xexact);
   return k;
-#endif
 }
 
 /* ---- profiler table: src/profiler.c:11-141 ----------------------------------------------- */

@@ -355,22 +355,100 @@ class CG:
             self.ptr = None
 
 
-class GMRES:
+def _ptr(a):
+    return a.ctypes.data_as(vp) if a is not None else None
+
+
+class _Solver:
+    """What GMRES, BatchCG, PCG and BiCGStab share: a handle of the C family PREFIX (sb_pcg_*, ...), refused for a
+    single-precision problem before the library or the problem is touched.  A subclass's __init__ creates `ptr`."""
+
+    PREFIX = NAME = None
+    COUNTERS = ()
+
+    def _need_double(self, problem):
+        if getattr(problem, "precision", "double") != "double":
+            raise ValueError("%s: double precision only (the problem was built with precision=%r)" % (self.NAME, problem.precision))
+
+    def _open(self, problem):
+        """the refusal, the library, and the problem's (b, xexact)"""
+        self._need_double(problem)
+        self.L = capi.load()
+        self.problem = problem
+        self.itermax = 0
+        return problem.rhs()
+
+    def _c(self, name):
+        return getattr(self.L, "%s_%s" % (self.PREFIX, name))
+
+    def _dinv_arg(self, dinv):
+        if dinv is not None:
+            dinv = np.ascontiguousarray(dinv, dtype=np.float64)
+            if dinv.shape != (self.problem.nr,):
+                raise ValueError("dinv must hold nr = %d doubles, got shape %r" % (self.problem.nr, dinv.shape))
+        return dinv
+
+    def _vector(self, name, *args):
+        x = np.empty(self.problem.nr)
+        self._c(name)(self.ptr, *args, x.ctypes.data_as(vp))
+        return x
+
+    def solve(self, itermax=150, eps=0.0):
+        self.itermax = itermax
+        return self._c("solve")(self.ptr, itermax, eps)
+
+    def start(self, itermax, eps=0.0):
+        """prologue only; follow with run_iters() and finish()"""
+        self.itermax = itermax
+        self._c("start")(self.ptr, itermax, eps)
+
+    def finish(self):
+        return self._c("finish")(self.ptr)
+
+    def solution(self):
+        """x in original row order"""
+        return self._vector("solution")
+
+    def check_residual(self):
+        return self._c("check_residual")(self.ptr)
+
+    def counters(self):
+        out = (C.c_int * 5)()
+        self._c("counters")(self.ptr, out)
+        return dict(zip(self.COUNTERS, list(out)))
+
+    def loop_ms(self):
+        return self._c("loop_ms")(self.ptr)
+
+    def free(self):
+        if self.ptr:
+            self._c("free")(self.ptr)
+            self.ptr = None
+
+
+class _BodySolver(_Solver):
+    """the three whose loop is made of bodies (GMRES has steps: launches_per_step(j), run_steps())"""
+
+    def launches_per_body(self):
+        return self._c("launches_per_body")(self.ptr)
+
+    def run_iters(self, iters):
+        self._c("run_iters")(self.ptr, int(iters))
+
+
+class GMRES(_Solver):
     """restarted GMRES(m) on the GPU (sb_gmres_*): for matrices that are not symmetric positive definite.  Krylov basis and
     scalars in HBM, loop without host round trips; double precision, one rank."""
 
+    PREFIX, NAME = "sb_gmres", "GMRES"
+    COUNTERS = ("stop", "steps", "cycles", "n_res", "n_rr")
+
     def __init__(self, problem, restart=30, fused=True):
-        if getattr(problem, "precision", "double") != "double":
-            raise ValueError("GMRES: double precision only (the problem was built with precision=%r)" % (problem.precision,))
-        self.L = capi.load()
-        self.problem = problem
-        b, xe = problem.rhs()
-        self.ptr = self.L.sb_gmres_create(problem.matrix, problem.halo, b.ctypes.data_as(vp),
-                                          xe.ctypes.data_as(vp) if xe is not None else None, int(restart))
+        b, xe = self._open(problem)
+        self.ptr = self.L.sb_gmres_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), int(restart))
         # fused: True = the multi-dot / multi-update kernels, False = the op list (one tree dot per h entry, one waxpby-shaped
         # launch per projection); same bits
         self.L.sb_gmres_set_fused(self.ptr, int(bool(fused)))
-        self.itermax = 0
 
     def restart(self):
         return self.L.sb_gmres_restart(self.ptr)
@@ -378,20 +456,12 @@ class GMRES:
     def launches_per_step(self, j):
         return self.L.sb_gmres_launches_per_step(self.ptr, int(j))
 
-    def solve(self, itermax=150, eps=0.0):
-        self.itermax = itermax
-        return self.L.sb_gmres_solve(self.ptr, itermax, eps)
-
     def start(self, itermax, eps=0.0):
         """prologue only; follow with run_steps() and finish()"""
-        self.itermax = itermax
-        self.L.sb_gmres_start(self.ptr, itermax, eps)
+        _Solver.start(self, itermax, eps)
 
     def run_steps(self, steps):
         self.L.sb_gmres_run_steps(self.ptr, int(steps))
-
-    def finish(self):
-        return self.L.sb_gmres_finish(self.ptr)
 
     def history(self):
         """(res_hist, rr_hist): the residual estimates (index 0: the initial norm) and every explicit r.r"""
@@ -402,28 +472,6 @@ class GMRES:
         nres = self.L.sb_gmres_history(self.ptr, res.ctypes.data_as(vp), cap, rr.ctypes.data_as(vp), cap, C.byref(nrr))
         return res[:nres].copy(), rr[:nrr.value].copy()
 
-    def solution(self):
-        """x in original row order"""
-        x = np.empty(self.problem.nr)
-        self.L.sb_gmres_solution(self.ptr, x.ctypes.data_as(vp))
-        return x
-
-    def check_residual(self):
-        return self.L.sb_gmres_check_residual(self.ptr)
-
-    def counters(self):
-        out = (C.c_int * 5)()
-        self.L.sb_gmres_counters(self.ptr, out)
-        return dict(zip(["stop", "steps", "cycles", "n_res", "n_rr"], list(out)))
-
-    def loop_ms(self):
-        return self.L.sb_gmres_loop_ms(self.ptr)
-
-    def free(self):
-        if self.ptr:
-            self.L.sb_gmres_free(self.ptr)
-            self.ptr = None
-
 
 def batch_rhs(b0, nrhs, start_row=0):
     """the right-hand sides of solveCGBatch: row 0 is b0; for c >= 1, b_c[i] = b0[i] + c * ((g(i) mod 5) - 2) with g the
@@ -433,17 +481,16 @@ def batch_rhs(b0, nrhs, start_row=0):
     return np.stack([b0 + float(c) * g for c in range(int(nrhs))])
 
 
-class BatchCG:
+class BatchCG(_BodySolver):
     """nrhs independent CG solves on one pass over the matrix per loop body (sb_cgb_*): column c is bit for bit
     `CG` on b_c alone in the tree dot order.  B: an (nrhs, nr) array in original row order; None: `batch_rhs` of the problem's
     own right-hand side.  Double precision, one rank, nrhs in {2, 4, 8}."""
 
+    PREFIX, NAME = "sb_cgb", "batched CG"
+    COUNTERS = ("stop", "stop_next", "iters", "n_rr", "n_pAp")
+
     def __init__(self, problem, B=None, nrhs=4):
-        if getattr(problem, "precision", "double") != "double":
-            raise ValueError("batched CG: double precision only (the problem was built with precision=%r)" % (problem.precision,))
-        self.L = capi.load()
-        self.problem = problem
-        b0, xe = problem.rhs()
+        b0, xe = self._open(problem)
         if B is None:
             B = batch_rhs(b0, nrhs, problem.startRow)
         else:
@@ -455,28 +502,11 @@ class BatchCG:
                 xe = None  # the exact solution belongs to the problem's own right-hand side
         self.nrhs = int(nrhs)
         B = np.ascontiguousarray(B, dtype=np.float64)
-        self.ptr = self.L.sb_cgb_create(problem.matrix, problem.halo, self.nrhs, B.ctypes.data_as(vp),
-                                        xe.ctypes.data_as(vp) if xe is not None else None)
-        self.itermax = 0
-
-    def launches_per_body(self):
-        return self.L.sb_cgb_launches_per_body(self.ptr)
+        self.ptr = self.L.sb_cgb_create(problem.matrix, problem.halo, self.nrhs, _ptr(B), _ptr(xe))
 
     def solve(self, itermax=150, eps=0.0):
         """returns the largest k_c"""
-        self.itermax = itermax
-        return self.L.sb_cgb_solve(self.ptr, itermax, eps)
-
-    def start(self, itermax, eps=0.0):
-        """prologue only; follow with run_iters() and finish()"""
-        self.itermax = itermax
-        self.L.sb_cgb_start(self.ptr, itermax, eps)
-
-    def run_iters(self, iters):
-        self.L.sb_cgb_run_iters(self.ptr, int(iters))
-
-    def finish(self):
-        return self.L.sb_cgb_finish(self.ptr)
+        return _Solver.solve(self, itermax, eps)
 
     def iterations(self, c):
         return self.L.sb_cgb_iterations(self.ptr, int(c))
@@ -491,9 +521,7 @@ class BatchCG:
 
     def solution(self, c):
         """x_c in original row order"""
-        x = np.empty(self.problem.nr)
-        self.L.sb_cgb_solution(self.ptr, int(c), x.ctypes.data_as(vp))
-        return x
+        return self._vector("solution", int(c))
 
     def check_residual(self, c=0):
         return self.L.sb_cgb_check_residual(self.ptr, int(c))
@@ -504,54 +532,20 @@ class BatchCG:
         self.L.sb_cgb_counters(self.ptr, int(c), out)
         if c < 0:
             return dict(zip(["all_stopped", "columns_stopped", "bodies_enqueued"], list(out)[:3]))
-        return dict(zip(["stop", "stop_next", "iters", "n_rr", "n_pAp"], list(out)))
-
-    def loop_ms(self):
-        return self.L.sb_cgb_loop_ms(self.ptr)
-
-    def free(self):
-        if self.ptr:
-            self.L.sb_cgb_free(self.ptr)
-            self.ptr = None
+        return dict(zip(self.COUNTERS, list(out)))
 
 
-class PCG:
+class PCG(_BodySolver):
     """solveCG with a diagonal preconditioner put back (sb_pcg_*): z = r * dinv, alpha = r.z / p.Ap,
     beta = r.z / (r.z)_old, the loop test on sqrt(r.r).  dinv None: Jacobi, 1 / diag(A); else nr finite positive doubles in
     original row order (all 1.0: `CG` in the tree order bit for bit).  Double precision, one rank, tree dot order."""
 
+    PREFIX, NAME = "sb_pcg", "PCG"
+    COUNTERS = ("stop", "stop_next", "iters", "n_rr", "n_pAp")
+
     def __init__(self, problem, dinv=None):
-        if getattr(problem, "precision", "double") != "double":
-            raise ValueError("PCG: double precision only (the problem was built with precision=%r)" % (problem.precision,))
-        self.L = capi.load()
-        self.problem = problem
-        b, xe = problem.rhs()
-        if dinv is not None:
-            dinv = np.ascontiguousarray(dinv, dtype=np.float64)
-            if dinv.shape != (problem.nr,):
-                raise ValueError("dinv must hold nr = %d doubles, got shape %r" % (problem.nr, dinv.shape))
-        self.ptr = self.L.sb_pcg_create(problem.matrix, problem.halo, b.ctypes.data_as(vp),
-                                        xe.ctypes.data_as(vp) if xe is not None else None,
-                                        dinv.ctypes.data_as(vp) if dinv is not None else None)
-        self.itermax = 0
-
-    def launches_per_body(self):
-        return self.L.sb_pcg_launches_per_body(self.ptr)
-
-    def solve(self, itermax=150, eps=0.0):
-        self.itermax = itermax
-        return self.L.sb_pcg_solve(self.ptr, itermax, eps)
-
-    def start(self, itermax, eps=0.0):
-        """prologue only; follow with run_iters() and finish()"""
-        self.itermax = itermax
-        self.L.sb_pcg_start(self.ptr, itermax, eps)
-
-    def run_iters(self, iters):
-        self.L.sb_pcg_run_iters(self.ptr, int(iters))
-
-    def finish(self):
-        return self.L.sb_pcg_finish(self.ptr)
+        b, xe = self._open(problem)
+        self.ptr = self.L.sb_pcg_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), _ptr(self._dinv_arg(dinv)))
 
     def history(self):
         """rr, rz, pAp"""
@@ -562,79 +556,30 @@ class PCG:
                                     C.byref(npap))
         return rr[:nrr].copy(), rz[:nrr].copy(), pap[:npap.value].copy()
 
-    def solution(self):
-        """x in original row order"""
-        x = np.empty(self.problem.nr)
-        self.L.sb_pcg_solution(self.ptr, x.ctypes.data_as(vp))
-        return x
-
-    def check_residual(self):
-        return self.L.sb_pcg_check_residual(self.ptr)
-
     def dinv(self):
         """the preconditioner in use, original row order"""
-        d = np.empty(self.problem.nr)
-        self.L.sb_pcg_dinv(self.ptr, d.ctypes.data_as(vp))
-        return d
-
-    def counters(self):
-        out = (C.c_int * 5)()
-        self.L.sb_pcg_counters(self.ptr, out)
-        return dict(zip(["stop", "stop_next", "iters", "n_rr", "n_pAp"], list(out)))
-
-    def loop_ms(self):
-        return self.L.sb_pcg_loop_ms(self.ptr)
-
-    def free(self):
-        if self.ptr:
-            self.L.sb_pcg_free(self.ptr)
-            self.ptr = None
+        return self._vector("dinv")
 
 
-class BiCGStab:
+class BiCGStab(_BodySolver):
     """Right-preconditioned BiCGStab with a diagonal preconditioner (sb_bicgstab_*) for matrices that need not be
     symmetric.  precond "none": dinv = 1.0 everywhere; "jacobi": 1 / diag(A); a `dinv` of nr finite non-zero doubles in original
     row order selects the caller's (precond is then "caller").  Double precision, one rank, tree dot order."""
 
+    PREFIX, NAME = "sb_bicgstab", "BiCGStab"
+    COUNTERS = ("stop", "iters", "n_rr", "n_rv", "n_ts")
     HISTORIES = ("rr", "rho", "rv", "ts", "tt")
 
     def __init__(self, problem, precond="none", dinv=None):
-        if getattr(problem, "precision", "double") != "double":
-            raise ValueError("BiCGStab: double precision only (the problem was built with precision=%r)" % (problem.precision,))
+        self._need_double(problem)
         if dinv is not None:
             precond = "caller"
         kinds = {"none": 0, "jacobi": 1, "caller": 2}
         if precond not in kinds or (precond == "caller" and dinv is None):
             raise ValueError("precond must be 'none' or 'jacobi', or pass dinv; got %r" % (precond,))
-        self.L = capi.load()
-        self.problem = problem
-        b, xe = problem.rhs()
-        if dinv is not None:
-            dinv = np.ascontiguousarray(dinv, dtype=np.float64)
-            if dinv.shape != (problem.nr,):
-                raise ValueError("dinv must hold nr = %d doubles, got shape %r" % (problem.nr, dinv.shape))
-        self.ptr = self.L.sb_bicgstab_create(problem.matrix, problem.halo, b.ctypes.data_as(vp),
-                                             xe.ctypes.data_as(vp) if xe is not None else None, kinds[precond],
-                                             dinv.ctypes.data_as(vp) if dinv is not None else None)
-        self.itermax = 0
-
-    def launches_per_body(self):
-        return self.L.sb_bicgstab_launches_per_body(self.ptr)
-
-    def solve(self, itermax=150, eps=0.0):
-        self.itermax = itermax
-        return self.L.sb_bicgstab_solve(self.ptr, itermax, eps)
-
-    def start(self, itermax, eps=0.0):
-        """prologue only; follow with run_iters() and finish()"""
-        self.itermax = itermax
-        self.L.sb_bicgstab_start(self.ptr, itermax, eps)
-
-    def run_iters(self, iters):
-        self.L.sb_bicgstab_run_iters(self.ptr, int(iters))
-
-    def finish(self):
-        return self.L.sb_bicgstab_finish(self.ptr)
+        b, xe = self._open(problem)
+        self.ptr = self.L.sb_bicgstab_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), kinds[precond],
+                                             _ptr(self._dinv_arg(dinv)))
 
     def history(self):
         """dict of rr, rho (entry 0: the prologue's, then one per body) and rv, ts, tt (one per body)"""
@@ -646,30 +591,6 @@ class BiCGStab:
             out[name] = a[:cnt].copy()
         return out
 
-    def solution(self):
-        """x in original row order"""
-        x = np.empty(self.problem.nr)
-        self.L.sb_bicgstab_solution(self.ptr, x.ctypes.data_as(vp))
-        return x
-
-    def check_residual(self):
-        return self.L.sb_bicgstab_check_residual(self.ptr)
-
     def dinv(self):
         """the preconditioner in use, original row order"""
-        d = np.empty(self.problem.nr)
-        self.L.sb_bicgstab_dinv(self.ptr, d.ctypes.data_as(vp))
-        return d
-
-    def counters(self):
-        out = (C.c_int * 5)()
-        self.L.sb_bicgstab_counters(self.ptr, out)
-        return dict(zip(["stop", "iters", "n_rr", "n_rv", "n_ts"], list(out)))
-
-    def loop_ms(self):
-        return self.L.sb_bicgstab_loop_ms(self.ptr)
-
-    def free(self):
-        if self.ptr:
-            self.L.sb_bicgstab_free(self.ptr)
-            self.ptr = None
+        return self._vector("dinv")

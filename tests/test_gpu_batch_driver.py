@@ -82,7 +82,7 @@ def test_driver_refusals(gpu):
 def test_c_caller_of_solveCGBatch(gpu, fmt, want16, tmp_path):
     exe = os.path.join(str(tmp_path), "batch_driver_%s" % fmt)
     subprocess.check_call(["gcc", "-std=gnu11", "-O1", "-Wall", "-D" + fmt, "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "c", "batch_driver.c"), "-o", exe, "-L" + LIB,
+                           "-DSOLVER_BATCH", os.path.join(ROOT, "tests", "c", "solver_driver.c"), "-o", exe, "-L" + LIB,
                            "-lsparsebench_%s" % fmt.lower(), "-lsparsebench_host", "-lsbhip", "-Wl,-rpath," + LIB, "-lm"])
     out = run([exe, "16", str(ITERMAX), "0.0", "4"])
     assert out.returncode == 0, out.stderr.decode()[-2000:]

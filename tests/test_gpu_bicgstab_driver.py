@@ -77,7 +77,7 @@ def build(fmt, tmp_path, sp):
     exe = os.path.join(str(tmp_path), "bicgstab_driver_%s%s" % (fmt, "_sp" if sp else ""))
     suffix = "_sp" if sp else ""
     subprocess.check_call(["gcc", "-std=gnu11", "-O1", "-Wall"] + (["-DPRECISION=1"] if sp else []) +
-                          ["-D" + fmt, "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "c", "bicgstab_driver.c"), "-o", exe,
+                          ["-D" + fmt, "-I" + os.path.join(ROOT, "include"), "-DSOLVER_BICGSTAB", os.path.join(ROOT, "tests", "c", "solver_driver.c"), "-o", exe,
                            "-L" + LIB, "-lsparsebench_%s%s" % (fmt.lower(), suffix), "-lsparsebench_host%s" % suffix, "-lsbhip",
                            "-Wl,-rpath," + LIB, "-lm"])
     return exe

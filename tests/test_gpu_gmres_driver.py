@@ -60,7 +60,7 @@ def test_c_caller_of_solveGMRES(gpu, fmt, cd16, tmp_path):
     mtx, want = cd16
     exe = os.path.join(str(tmp_path), "gmres_driver_%s" % fmt)
     subprocess.check_call(["gcc", "-std=gnu11", "-O1", "-Wall", "-D" + fmt, "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "c", "gmres_driver.c"), "-o", exe, "-L" + LIB,
+                           "-DSOLVER_GMRES", os.path.join(ROOT, "tests", "c", "solver_driver.c"), "-o", exe, "-L" + LIB,
                            "-lsparsebench_%s" % fmt.lower(), "-lsparsebench_host", "-lsbhip", "-Wl,-rpath," + LIB, "-lm"])
     out = run([exe, mtx, "150", repr(want["eps"]), "30"])
     assert out.returncode == 0, out.stderr.decode()[-2000:]

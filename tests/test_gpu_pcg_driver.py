@@ -76,7 +76,7 @@ def test_driver_help_and_refusals(gpu):
 def test_c_caller_of_solvePCG(gpu, fmt, wants, tmp_path):
     exe = os.path.join(str(tmp_path), "pcg_driver_%s" % fmt)
     subprocess.check_call(["gcc", "-std=gnu11", "-O1", "-Wall", "-D" + fmt, "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "c", "pcg_driver.c"), "-o", exe, "-L" + LIB,
+                           "-DSOLVER_PCG", os.path.join(ROOT, "tests", "c", "solver_driver.c"), "-o", exe, "-L" + LIB,
                            "-lsparsebench_%s" % fmt.lower(), "-lsparsebench_host", "-lsbhip", "-Wl,-rpath," + LIB, "-lm"])
     for key, arg in (("scaled", wants["path"]), ("hpcg", "16")):
         out = run([exe, arg, str(ITERMAX), repr(EPS)])
@@ -90,7 +90,7 @@ def test_c_caller_of_solvePCG(gpu, fmt, wants, tmp_path):
 def test_sp_library_refuses_solvePCG(gpu, fmt, tmp_path):
     exe = os.path.join(str(tmp_path), "pcg_driver_%s_sp" % fmt)
     subprocess.check_call(["gcc", "-std=gnu11", "-O1", "-Wall", "-DPRECISION=1", "-D" + fmt, "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "c", "pcg_driver.c"), "-o", exe, "-L" + LIB,
+                           "-DSOLVER_PCG", os.path.join(ROOT, "tests", "c", "solver_driver.c"), "-o", exe, "-L" + LIB,
                            "-lsparsebench_%s_sp" % fmt.lower(), "-lsparsebench_host_sp", "-lsbhip", "-Wl,-rpath," + LIB, "-lm"])
     out = run([exe, "8", "10", "0.0"])
     assert out.returncode == 1 and "PCG: double precision only" in out.stderr.decode()
