@@ -61,6 +61,8 @@ void* sb_malloc_host_visible(size_t bytes);
 const char* sb_host_visible_reason(void);
 void* sb_malloc_pinned_host(size_t bytes); /* fallback: pinned host memory (staged by spMVM / waxpby / ddot); NULL on failure */
 void sb_free_pinned_host(void* p);
+int sb_is_pinned_host_ptr(const void* p); /* 1: memory from hipHostMalloc (sb_malloc_pinned_host) */
+size_t sb_mem_free_bytes(void);           /* free device memory (hipMemGetInfo) */
 /* host <-> device copies made through sb_h2d / sb_d2h so far: {h2d calls, h2d bytes, d2h calls, d2h bytes} */
 void sb_copy_counters(uint64_t out[4]);
 

@@ -235,11 +235,16 @@ void sbh_write_bin_matrix(Comm* c, char* mtxFilename);
 /* src/allocate.h:9 -- the allocation hook.  With a device up, requests >= 64 KiB come back as memory that lives in HBM, that
  * host loops can store to and that spMVM / waxpby / ddot use in place (src/main.c:205-215 then times the kernel, not staging);
  * see host/sbh_base.c.  sbh_allocate_kind(): what the last request got -- 0 plain host, 1 device-resident and host-visible,
- * 2 pinned host.  sbh_alloc_host(): always plain host memory (what the library's own host-side arrays use). */
+ * 2 pinned host.  sbh_alloc_host(): always plain host memory (what the library's own host-side arrays use).
+ * spMVM and waxpby on a kind-1 vector are stream-ordered, NOT synchronous as the reference's are: call sbh_profile_sync()
+ * before the host reads their output or refills one of their inputs (ddot returns its value and has waited).  Host reads cross
+ * the PCIe BAR uncached: slow.  Memory from allocate() is released with sbh_allocate_free(), never with free(): kind 1 and 2
+ * are not libc's. */
 void* allocate(size_t alignment, size_t bytesize);
 void* sbh_alloc_host(size_t alignment, size_t bytesize);
 int sbh_allocate_kind(void);
 void sbh_allocate_free(void* p);
+size_t sbh_device_free_bytes(void); /* free device memory, bytes */
 double getTimeStamp(void);                          /* src/timing.h:8 */
 double getTimeResolution(void);                     /* src/timing.h:9 */
 

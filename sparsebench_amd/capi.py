@@ -35,6 +35,7 @@ SYMBOLS = [
     "sb_cg_set_fuse_p", "sb_cg_fuse_p", "sb_cg_set_fuse_alpha", "sb_cg_set_fuse_beta",
     "sb_malloc_host_visible", "sb_host_visible_reason", "sb_malloc_pinned_host", "sb_free_pinned_host", "sb_copy_counters",
     "sb_region_begin", "sb_region_end", "sb_region_seconds", "sb_region_reset",
+    "sb_is_pinned_host_ptr", "sb_mem_free_bytes",
     "sb_set_dot_order", "sb_dot_order", "sb_cg_set_dot_order", "sb_cg_dot_order",
     "sb_crs_upload_f32", "sb_scs_upload_f32", "sb_matrix_precision", "sb_spmv_f32", "sb_spmv_native_dot_f32", "sb_permute_f32",
     "sb_unpermute_f32", "sb_waxpby_f32", "sb_ddot_f32", "sb_ddot_partials_f32", "sb_reduce_final_f32", "sb_cg_create_f32",
@@ -184,6 +185,8 @@ def load():
         "sb_region_end": (None, [C.c_int]),
         "sb_region_seconds": (C.c_double, [C.c_int, C.POINTER(C.c_uint64)]),
         "sb_region_reset": (None, []),
+        "sb_is_pinned_host_ptr": (C.c_int, [vp]),
+        "sb_mem_free_bytes": (C.c_size_t, []),
         "sb_matrix_place": (None, [vp, C.c_int, C.c_int]),
         "sb_matrix_place_commit": (None, [vp]),
         "sb_matrix_place_fresh": (None, [vp]),

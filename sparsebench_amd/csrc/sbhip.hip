@@ -568,6 +568,22 @@ void sb_free_pinned_host(void* p)
 {
   if (p) HIP_CHECK(hipHostFree(p));
 }
+int sb_is_pinned_host_ptr(const void* p)
+{
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return a.type == hipMemoryTypeHost ? 1 : 0;
+}
+size_t sb_mem_free_bytes(void)
+{
+  need_init();
+  size_t freeB = 0, totalB = 0;
+  HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
+  return freeB;
+}
 
 // ---- device-timed profile regions (PROFILE macro, src/profiler.h:18-21) ---------------------------------------------------
 // The reference's PROFILE reads the host clock around a synchronous CPU call.  Here the call is a stream-ordered launch: a

@@ -36,12 +36,14 @@ void* sbh_alloc_host(size_t alignment, size_t bytesize)
  * (sb_host_visible_reason), or with SPARSEBENCH_ALLOCATE=host, the request falls back to pinned host memory, then to plain host
  * memory, both staged through HBM by the kernels' wrappers as before.  Host READS of the device-resident kind cross the BAR
  * uncached (slow): a caller that post-processes results on the CPU should copy them out with sb_d2h or use SPARSEBENCH_ALLOCATE=host.
- * sbh_allocate_kind() reports what the last request got; memory from here is never freed by the reference (sbh_allocate_free
- * returns any kind). */
+ * sbh_allocate_kind() reports what the last request got.  Every block that is not plain host memory is kept in a table that
+ * grows with the requests, and sbh_allocate_free() -- the one way to release such memory; the reference never frees what
+ * allocate() gave it -- returns each kind to where it came from.  spMVM / waxpby on such vectors are stream-ordered like any
+ * other device vector: the caller waits (sbh_profile_sync) before it reads an output or refills an input. */
 #define SBH_ALLOCATE_DEVICE_MIN ((size_t)64 << 10)
 static int g_alloc_kind; /* 0 host, 1 device-resident host-visible, 2 pinned host */
-static struct { void* p; int kind; } g_allocs[256];
-static int g_nallocs;
+static struct sbh_alloc { void* p; int kind; }* g_allocs;
+static size_t g_nallocs, g_capallocs;
 
 void* allocate(size_t alignment, size_t bytesize)
 {
@@ -52,8 +54,17 @@ void* allocate(size_t alignment, size_t bytesize)
     const char* mode = getenv("SPARSEBENCH_ALLOCATE");
     if (!p && !(mode && strcmp(mode, "host") == 0)) p = sb_malloc_pinned_host(bytesize), kind = 2;
     if (p) {
-      g_alloc_kind = kind;
-      if (g_nallocs < 256) g_allocs[g_nallocs].p = p, g_allocs[g_nallocs++].kind = kind;
+      if (g_nallocs == g_capallocs) {
+        const size_t cap      = g_capallocs ? 2 * g_capallocs : 256;
+        struct sbh_alloc* tab = (struct sbh_alloc*)realloc(g_allocs, cap * sizeof *tab);
+        if (!tab) {
+          fprintf(stderr, "Error: Insufficient memory to fulfill the request\n");
+          exit(EXIT_FAILURE);
+        }
+        g_allocs = tab, g_capallocs = cap;
+      }
+      g_allocs[g_nallocs++] = (struct sbh_alloc){ p, kind };
+      g_alloc_kind          = kind;
       return p;
     }
   }
@@ -64,15 +75,18 @@ int sbh_allocate_kind(void) { return g_alloc_kind; }
 
 void sbh_allocate_free(void* p)
 {
-  for (int i = 0; i < g_nallocs; i++)
-    if (g_allocs[i].p == p) {
-      if (g_allocs[i].kind == 1) sb_free(p);
-      else sb_free_pinned_host(p);
-      g_allocs[i] = g_allocs[--g_nallocs];
-      return;
-    }
-  free(p);
+  int kind = 0;
+  for (size_t i = 0; i < g_nallocs && !kind; i++)
+    if (g_allocs[i].p == p) kind = g_allocs[i].kind, g_allocs[i] = g_allocs[--g_nallocs];
+  /* libc's free() never sees memory of the HIP runtime's, listed or not */
+  if (!kind && p && sb_is_initialized()) kind = sb_is_device_ptr(p) ? 1 : sb_is_pinned_host_ptr(p) ? 2 : 0;
+  if (kind == 1) sb_free(p);
+  else if (kind == 2) sb_free_pinned_host(p);
+  else free(p);
 }
+
+/* free device memory in bytes (what a caller of the hook can watch its requests and releases with); 0 before a device is up */
+size_t sbh_device_free_bytes(void) { return sb_is_initialized() ? sb_mem_free_bytes() : 0; }
 
 /* src/timing.c:8-13: CLOCK_MONOTONIC seconds */
 double getTimeStamp(void)
