@@ -8,7 +8,7 @@ transport (sparsebench_amd/gloo_transport.py) and, where its set-up succeeds, th
   ops CASE...  sb_halo_exchange_f32 puts the exact float of the owning rank's row in every tail slot (device row order, sigma > 1
                included); sb_comm_reduction_f32 SUM / MAX equal the pairwise float tree
   noallgather  a transport without allgather_bytes: the SP upload must end the process with its message
-CASE = fmt C sigma name itermax (name: hpcgN or band_klein)."""
+CASE = fmt C sigma name itermax (name: hpcgN, hpcgXxYxZ or band_klein)."""
 import ctypes as C
 import json
 import os
@@ -37,8 +37,8 @@ def bits(a):
 def problem(fmt, Cc, sigma, name, rank, size):
     if name == "band_klein":
         return hostapi.Problem(BAND, 1, 1, 1, fmt=fmt, Cc=Cc, sigma=sigma, rank=rank, size=size, precision="single")
-    n = int(name[4:])
-    return hostapi.Problem("generate", n, n, n, fmt=fmt, Cc=Cc, sigma=sigma, rank=rank, size=size, precision="single")
+    nx, ny, nz = sp_mpi_ref.hpcg_dims(name)
+    return hostapi.Problem("generate", nx, ny, nz, fmt=fmt, Cc=Cc, sigma=sigma, rank=rank, size=size, precision="single")
 
 
 def run_cg(L, prob, fmt, Cc, sigma, name, itermax, rank, size):

@@ -34,11 +34,18 @@ def rank_max(values):
     return m
 
 
+def hpcg_dims(name):
+    """"hpcgN" -> (N, N, N), "hpcgXxYxZ" -> (X, Y, Z)"""
+    d = [int(v) for v in name[4:].split("x")]
+    assert len(d) in (1, 3), name
+    return tuple(d * 3) if len(d) == 1 else tuple(d)
+
+
 def locals_and_plans(po, name, size):
-    """the P local matrices (oracle-owned) and their halo plans: name = "hpcgN" or a .mtx path"""
+    """the P local matrices (oracle-owned) and their halo plans: name = "hpcgN", "hpcgXxYxZ" or a .mtx path"""
     if name.startswith("hpcg"):
-        n = int(name[4:])
-        locs = [po.GMatrix.generate(n, n, n, r, size) for r in range(size)]
+        nx, ny, nz = hpcg_dims(name)
+        locs = [po.GMatrix.generate(nx, ny, nz, r, size) for r in range(size)]
     else:
         locs = [po.GMatrix.from_mtx(name, r, size) for r in range(size)]
     plans = po.Plans(locs)

@@ -39,6 +39,7 @@ CASES = [
     ("scs", 64, 1, "hpcg48", 3, 150, 600),       # many exchanges: staging-area parity and flags
     ("scs", 64, 1, "band_klein", 2, 150, 300),
     ("crs", 64, 1, "hpcg8", 8, 60, 600),         # the reference's 8-rank history
+    ("scs", 64, 1, "hpcg7x7x9", 3, 40, 300),     # a 7 x 7 x 9 brick per rank, 441 rows (n % 4 = 1): float halo push / pull and p update over a partial float4
 ]
 GOLDEN = {("hpcg16", 2): "hpcg16_x2", ("hpcg16", 4): "hpcg16_x4", ("hpcg8", 8): "hpcg8_x8", ("band_klein", 2): "band_klein_x2"}
 

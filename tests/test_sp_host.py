@@ -15,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "sparsebench_amd", "lib")
 BIN = os.path.join(ROOT, "sparsebench_amd", "bin")
 GOLD = os.path.join(ROOT, "tests", "golden", "cg_hist_sp_ref.json")
+GOLD_ODD = os.path.join(ROOT, "tests", "golden", "cg_hist_sp_ref_odd.json")
 BAND = os.path.join(ROOT, "tests", "golden", "ref", "matrix_band_klein.mtx")
 
 PROBE = r"""
@@ -109,6 +110,37 @@ def test_sp_ref_seq_cg_reproduces_reference(name):
     gp = np.array([float(v) for v in g["pAp"]], np.float32)
     assert np.array_equal(np.isnan(pap), np.isnan(gp))
     assert np.array_equal(pap[~np.isnan(pap)].view(np.uint32), gp[~np.isnan(gp)].view(np.uint32))
+    p.free()
+
+
+def test_sp_golden_odd_well_formed():
+    g = json.load(open(GOLD_ODD))
+    assert set(g) == {"hpcg33x7x5", "hpcg19x21x23"}
+    assert (g["hpcg33x7x5"]["itermax"], g["hpcg33x7x5"]["k"]) == (60, 60)
+    assert (g["hpcg19x21x23"]["itermax"], g["hpcg19x21x23"]["k"]) == (40, 40)
+    for name, c in g.items():
+        assert set(c) == {"itermax", "k", "rr", "pAp"}
+        assert len(c["rr"]) == c["k"] - 1 and len(c["pAp"]) == c["k"] - 1, name
+        for v in c["rr"] + c["pAp"]:
+            d = float(v)
+            assert float(np.float32(d)) == d, (name, v)  # every value is a float32 value, none a NaN
+    rr = np.array([float(v) for v in g["hpcg33x7x5"]["rr"]], np.float32)
+    assert np.sum((rr != 0) & (np.abs(rr) < np.finfo(np.float32).tiny)) >= 2  # ends among subnormal r.r values
+
+
+@pytest.mark.parametrize("dims", [(33, 7, 5), (19, 21, 23)])
+def test_sp_ref_seq_cg_reproduces_reference_at_odd_shapes(dims):
+    """row counts off the 4 / 64 / 256 grids (1155 and 9177 rows): the restatement in the seq order is the reference's SP solveCG
+    there too, bit for bit (oracle/build_ref_sp.sh, tests/golden/make_golden_sp_odd.py)"""
+    g = json.load(open(GOLD_ODD))["hpcg%dx%dx%d" % dims]
+    p = hostapi.Problem("generate", dims[0], dims[1], dims[2], fmt="crs", upload=False, precision="single")
+    assert p.nr % 4 != 0
+    rp, col, val = p.array("rowPtr").copy(), p.array("crs_colInd").copy(), p.values().copy()
+    b, _ = p.rhs()
+    k, rr, pap, _ = sp_ref.cg(lambda v: sp_ref.spmv_crs(rp, col, val, v), b, g["itermax"], dot=sp_ref.dot_seq)
+    assert k == g["k"]
+    assert np.array_equal(rr.view(np.uint32), np.array([float(v) for v in g["rr"]], np.float32).view(np.uint32))
+    assert np.array_equal(pap.view(np.uint32), np.array([float(v) for v in g["pAp"]], np.float32).view(np.uint32))
     p.free()
 
 

@@ -115,3 +115,12 @@ def test_c_probe_links_sp_entry_points(tmp_path):
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, out.stderr
     assert out.stdout.split() == ["0", "7"], out.stdout
+
+
+def test_problem_names_of_the_multirank_cases():
+    """"hpcgN" is an N^3 brick per rank, "hpcgXxYxZ" an X x Y x Z one (tests/gpu_sp_multirank_worker.py)"""
+    assert sp_mpi_ref.hpcg_dims("hpcg16") == (16, 16, 16) and sp_mpi_ref.hpcg_dims("hpcg7x7x9") == (7, 7, 9)
+    locs, plans, keep = sp_mpi_ref.locals_and_plans(po, "hpcg7x7x9", 3)
+    assert [g.nr for g in locs] == [441, 441, 441] and [pl["externalCount"] for pl in plans] == [49, 98, 49]
+    for g in locs:
+        g.free()
