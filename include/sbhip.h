@@ -149,6 +149,15 @@ uint32_t sb_matrix_row_patterns(const sb_matrix* m, uint32_t* uniformChunks);
 uint32_t sb_matrix_row_programs(const sb_matrix* m, uint32_t* maskedChunks);
 /* bytes the selected SpMV kernel really moves per launch (stream + x + y) */
 double sb_matrix_stream_bytes(const sb_matrix* m);
+/* Sell-64, double precision, reference-layout kernel (mode 0): k sixteenths of the stream's 4-chunk blocks, evenly
+ * interleaved, are read with plain loads and so stay in the 256 MiB Infinity Cache from one SpMV to the next; the rest is read
+ * non-temporally.  The upload sets k from the stream's bytes, the loop's vector bytes (4 vectors of nc doubles) and the
+ * cache size; it is 0 where ranks share a device and where the vectors alone exceed the cache.  k = -1 selects that rule
+ * again, 0 ... 16 forces a share (tests, A/B measurements); the share in force is returned (0 for any other matrix).  Every
+ * share gives the same bits. */
+int sb_matrix_resident_share(sb_matrix* m, int k);
+/* the rule itself (host arithmetic only): the share for a stream of streamBytes and vectors of nc doubles */
+int sb_resident_share_rule(double streamBytes, uint32_t nc, int sharedDevice);
 /* either precision: 1 when the matrix (CRS: its private mirror) has row programs for EVERY chunk, no class dictionary and
  * only mapped or simple windows -- what the SpMV with the p update inside needs of a matrix, and the condition under which a
  * single-precision upload keeps its mirror (sb_set_sp_mirror): for an SP matrix 1 exactly when the mirror was built and kept. */

@@ -56,6 +56,7 @@ SYMBOLS = [
     "sb_bicgstab_history", "sb_bicgstab_solution", "sb_bicgstab_check_residual", "sb_bicgstab_dinv", "sb_bicgstab_launches_per_body",
     "sb_bicgstab_loop_ms", "sb_bicgstab_counters", "sb_bicgstab_update_p_native", "sb_bicgstab_update_s_native",
     "sb_bicgstab_dot2_native", "sb_bicgstab_update_xr_native", "sb_bicgstab_reduce_native", "sb_bicgstab_launch",
+    "sb_matrix_resident_share", "sb_resident_share_rule",
 ]
 
 _lib = None
@@ -141,6 +142,8 @@ def load():
         "sb_debug_stream_read_gbs": (C.c_double, [C.c_size_t, C.c_int]),
         "sb_matrix_pack_level": (C.c_int, [vp]),
         "sb_matrix_use_packed": (None, [vp, C.c_int]),
+        "sb_matrix_resident_share": (C.c_int, [vp, C.c_int]),
+        "sb_resident_share_rule": (C.c_int, [C.c_double, C.c_uint32, C.c_int]),
         "sb_set_external_ids": (None, [vp, C.c_uint32]),
         "sb_spmv_native_dot": (C.c_int, [vp, vp, vp, vp]),
         "sb_matrix_stream_bytes": (C.c_double, [vp]),

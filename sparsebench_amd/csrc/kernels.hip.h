@@ -242,6 +242,8 @@ constexpr uint32_t SCS_SLACK = 16 * 64; // zeroed elements behind val / colInd
 
 // One lane's row of a chunk: UNROLL val / colInd loads in flight, then the gathers, then the products added left to right.
 // xcol(col) is the x value of a column: x[col], or the staging-area lookup of the halo blocks (spmv_scs64_halo).
+// NT: val / colInd with non-temporal loads (they pass through the Infinity Cache without displacing what plain loads left
+// there) or with plain ones (they stay in it).
 template <int UNROLL, bool NT, typename T, typename XCol>
 __device__ __forceinline__ T scs64_row_sum(const uint32_t* __restrict__ chunkPtr, const uint32_t* __restrict__ chunkLens,
     const uint32_t* __restrict__ colInd, const T* __restrict__ val, uint32_t chunk, uint32_t lane, XCol xcol)
@@ -273,6 +275,21 @@ __device__ __forceinline__ T scs64_row_sum(const uint32_t* __restrict__ chunkPtr
   }
   return acc;
 }
+// The same row with the kind of load chosen at run time.  resident (wave-uniform): the chunk belongs to the share of the
+// stream that is kept in the Infinity Cache from one SpMV to the next (scs64_block_resident) and is read with plain loads;
+// the rest is read non-temporally.  Two copies of one loop behind a scalar branch: same products, same order, same bits.
+template <int UNROLL, typename T, typename XCol>
+__device__ __forceinline__ T scs64_row_sum(const uint32_t* __restrict__ chunkPtr, const uint32_t* __restrict__ chunkLens,
+    const uint32_t* __restrict__ colInd, const T* __restrict__ val, uint32_t chunk, uint32_t lane, bool resident, XCol xcol)
+{
+  if (resident) return scs64_row_sum<UNROLL, false>(chunkPtr, chunkLens, colInd, val, chunk, lane, xcol);
+  return scs64_row_sum<UNROLL, true>(chunkPtr, chunkLens, colInd, val, chunk, lane, xcol);
+}
+// Which blocks (4 chunks, ~83 KB of stream at 27 elements per row) make up a resident share of k sixteenths: a pure function
+// of the block's position j in its XCD's range (blockIdx.x >> 3 under the XCD mapping: the order in which an XCD is handed
+// its workgroups), so the set is the same in every launch, every 16 consecutive j hold exactly k resident blocks, evenly
+// spaced, and every XCD has the same mix of cache-served and HBM-served blocks in flight at any moment of the launch.
+__device__ __forceinline__ bool scs64_block_resident(uint32_t j, uint32_t k) { return ((j * k) & 15u) < k; }
 // The LEVEL-1 value of x . y for a block's four chunks (a block IS an aligned 256-group of the output vector): the four
 // waves' level-0 partials (wave_sum: the precision's 64-lane butterfly) meet in LDS and are added ((q0 + q1) + q2) + q3 --
 // the scalar step then reads n/256 values instead of n/64 through its one CU (which was 1.9 of its 4.3 us:
@@ -288,12 +305,13 @@ __device__ __forceinline__ void scs64_block_dot(T t, uint32_t lane, T* __restric
   if (threadIdx.x == 0) dotL1[lb] = ((sq[0] + sq[1]) + sq[2]) + sq[3];
 }
 
-template <int UNROLL, bool DOT, bool NT>
+// residentK: the resident share of the stream in sixteenths, 0 (all non-temporal) ... 16 (all plain)
+template <int UNROLL, bool DOT>
 __global__ __launch_bounds__(256) void spmv_scs64(const uint32_t* __restrict__ chunkPtr,
     const uint32_t* __restrict__ chunkLens, const uint32_t* __restrict__ colInd,
     const double* __restrict__ val, const double* __restrict__ x, double* __restrict__ y,
     uint32_t nr, uint32_t nChunks, uint32_t blocksPerXcd, double* __restrict__ dotPartials,
-    const int* __restrict__ stop)
+    const int* __restrict__ stop, uint32_t residentK)
 {
   const int stopped      = stop ? *stop : 0; // one wait covers this and the loads below
   const uint32_t nBlocks = (nChunks + 3u) >> 2;
@@ -303,8 +321,9 @@ __global__ __launch_bounds__(256) void spmv_scs64(const uint32_t* __restrict__ c
   const uint32_t lane  = threadIdx.x & 63u;
   const bool active    = chunk < nChunks; // wave-uniform; with DOT an idle wave of the last block still joins the combine below
   if (!DOT && !active) return;
+  const bool resident = scs64_block_resident(blocksPerXcd ? blockIdx.x >> 3 : blockIdx.x, residentK);
   double acc = 0.0;
-  if (active) acc = scs64_row_sum<UNROLL, NT>(chunkPtr, chunkLens, colInd, val, chunk, lane, [&](uint32_t col) { return x[col]; });
+  if (active) acc = scs64_row_sum<UNROLL>(chunkPtr, chunkLens, colInd, val, chunk, lane, resident, [&](uint32_t col) { return x[col]; });
   const uint32_t row = chunk * 64u + lane;
   if (active && row < nr) y[row] = acc;
   if (DOT) scs64_block_dot((active && row < nr) ? x[row] * acc : 0.0, lane, dotPartials, lb, butterfly64);
@@ -1248,7 +1267,7 @@ __global__ __launch_bounds__(1024) void cg_update_p_push(HaloPush hp, HaloFold h
   halo_fold_push(hp, hf, seq, p, e0, e1, blockDim.x);
 }
 
-// spmv_scs64<UNROLL, true, NT> whose boundary blocks wait for the neighbours' pushes and read the staging area themselves.
+// spmv_scs64<UNROLL, true> whose boundary blocks wait for the neighbours' pushes and read the staging area themselves.
 // A block is the kernel's unit -- four chunks, one aligned 256-group of rows, one level-1 value of p.Ap -- so the plan
 // (ScsHalo) splits BLOCKS: those that hold no column >= nr (interior) and those that hold one (halo).  The first
 // 8 perXcdI workgroups take the interior blocks in the XCD-aware order of spmv_scs64 (order[] lists them ascending, so
@@ -1318,12 +1337,14 @@ __device__ __forceinline__ bool scs_halo_wait(const ScsHalo& hh)
   return !failed;
 }
 // both precisions' spmv_scs64_halo.  xcol(col): x[col] for col < nr, the staging area's value for col >= nr -- called by the
-// halo blocks only, behind the wait.
-template <int UNROLL, bool NT, typename T, typename XCol, typename WaveSum>
+// halo blocks only, behind the wait.  LOADS: 1 the stream non-temporal (single precision), 0 plain, SCS_SHARE: residentK
+// sixteenths plain as in spmv_scs64, with j the workgroup's place in its XCD's dispatch order (interior and halo alike).
+constexpr int SCS_SHARE = 2;
+template <int UNROLL, int LOADS, typename T, typename XCol, typename WaveSum>
 __device__ __forceinline__ void scs64_halo_spmv(const uint32_t* __restrict__ chunkPtr, const uint32_t* __restrict__ chunkLens,
     const uint32_t* __restrict__ colInd, const T* __restrict__ val, const T* __restrict__ x, T* __restrict__ y, uint32_t nr,
     uint32_t nChunks, uint32_t perXcdI, T* __restrict__ dotL1, const int* __restrict__ stop, const ScsHalo& hh, XCol xcol,
-    WaveSum wave_sum)
+    WaveSum wave_sum, uint32_t residentK = 0)
 {
   const int stopped      = *stop;
   const uint32_t nBlocks = (nChunks + 3u) >> 2;
@@ -1333,28 +1354,34 @@ __device__ __forceinline__ void scs64_halo_spmv(const uint32_t* __restrict__ chu
   const uint32_t chunk = __builtin_amdgcn_readfirstlane(lb * 4u + (threadIdx.x >> 6));
   const uint32_t lane  = threadIdx.x & 63u;
   const bool active    = chunk < nChunks; // wave-uniform; an idle wave of the last block still joins the barriers below
+  auto row_sum = [&](auto xc) {
+    if constexpr (LOADS == SCS_SHARE)
+      return scs64_row_sum<UNROLL>(chunkPtr, chunkLens, colInd, val, chunk, lane, scs64_block_resident(blockIdx.x >> 3, residentK), xc);
+    else
+      return scs64_row_sum<UNROLL, LOADS == 1>(chunkPtr, chunkLens, colInd, val, chunk, lane, xc);
+  };
   T acc = 0;
   if (!halo) {
-    if (active) acc = scs64_row_sum<UNROLL, NT>(chunkPtr, chunkLens, colInd, val, chunk, lane, [&](uint32_t col) { return x[col]; });
+    if (active) acc = row_sum([&](uint32_t col) { return x[col]; });
   } else {
     const bool arrived = scs_halo_wait(hh); // (uniform per workgroup; a failed wait has raised err and the stop flag)
-    if (active && arrived) acc = scs64_row_sum<UNROLL, NT>(chunkPtr, chunkLens, colInd, val, chunk, lane, xcol);
+    if (active && arrived) acc = row_sum(xcol);
   }
   // y and the block's level-1 value of p.Ap at the block's OWN index
   const uint32_t row = chunk * 64u + lane;
   if (active && row < nr) y[row] = acc;
   scs64_block_dot((active && row < nr) ? x[row] * acc : 0, lane, dotL1, lb, wave_sum);
 }
-template <int UNROLL, bool NT>
+template <int UNROLL>
 __global__ __launch_bounds__(256) void spmv_scs64_halo(const uint32_t* __restrict__ chunkPtr,
     const uint32_t* __restrict__ chunkLens, const uint32_t* __restrict__ colInd,
     const double* __restrict__ val, const double* __restrict__ x, double* __restrict__ y,
     uint32_t nr, uint32_t nChunks, uint32_t perXcdI, double* __restrict__ dotPartials,
-    const int* __restrict__ stop, ScsHalo hh)
+    const int* __restrict__ stop, ScsHalo hh, uint32_t residentK)
 {
   const double* ext = reinterpret_cast<const double*>(hh.ext);
-  scs64_halo_spmv<UNROLL, NT>(chunkPtr, chunkLens, colInd, val, x, y, nr, nChunks, perXcdI, dotPartials, stop, hh,
-      [&](uint32_t col) -> double { return *(col >= nr ? ext + (col - nr) : x + col); }, butterfly64);
+  scs64_halo_spmv<UNROLL, SCS_SHARE>(chunkPtr, chunkLens, colInd, val, x, y, nr, nChunks, perXcdI, dotPartials, stop, hh,
+      [&](uint32_t col) -> double { return *(col >= nr ? ext + (col - nr) : x + col); }, butterfly64, residentK);
 }
 
 // CG scalar step as its own launch: the reference-shaped (unfused) path, and after the

@@ -225,6 +225,9 @@ struct sb_matrix {
   double* pdict = nullptr;
   int packLevel = 0; // 0 none, 1 16-bit columns, 2 + value dictionary
   int usePacked = 0;
+  // spmv_scs64 / spmv_scs64_halo: sixteenths of the reference-layout stream read with plain loads, i.e. kept in the Infinity
+  // Cache from one SpMV to the next (sbhip_launch.inc.h: "resident share"); residentRule is what the upload's rule gave
+  int residentK = 0, residentRule = 0;
   uint32_t padCol = 0;
   double packedBytes = 0.0; // matrix-stream bytes of the packed form
   uint32_t nWideChunks = 0;

@@ -48,15 +48,14 @@ static void launch_spmmv(const sb_matrix* m, int nv, const double* X, double* Y,
 {
   if (m->nr == 0) return;
   if (m->fmt == 1 && m->C == 64) {
+    static int g_scs_nt = -1; // the batched kernel's own switch (SB_SCS_NT=0: plain loads; lab)
     if (g_scs_nt < 0) {
       const char* n = getenv("SB_SCS_NT");
       g_scs_nt      = n ? atoi(n) : 1;
-      const char* xc = getenv("SB_SCS_XCD");
-      g_scs_xcd     = xc ? atoi(xc) : 1;
     }
     const uint32_t nBlocks = (m->nChunks + 3) / 4;
-    const uint32_t per     = g_scs_xcd ? (nBlocks + 7) / 8 : 0;
-    const dim3 grid(g_scs_xcd ? per * 8 : nBlocks), block(256);
+    const uint32_t per     = scs_xcd() ? (nBlocks + 7) / 8 : 0;
+    const dim3 grid(scs_xcd() ? per * 8 : nBlocks), block(256);
 #define SPMMV_LAUNCH(D, N)                                                                                                       \
   hipLaunchKernelGGL((spmmv_scs64<NV, SpmmvUnroll<NV>::value, D, N>), grid, block, 0, g.stream, m->chunkPtr, m->chunkLens, m->colInd, \
       m->val, X, Y, m->nr, m->nChunks, per, l1, stop)

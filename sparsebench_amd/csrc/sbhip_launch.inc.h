@@ -14,8 +14,15 @@ static hipEvent_t g_spmvEvA = nullptr, g_spmvEvB = nullptr;
     else hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);                                    \
   } while (0)
 
-static int g_scs_nt     = -1;
-static int g_scs_xcd    = 1;
+static int g_scs_xcd = -1; // SB_SCS_XCD=0: blocks in plain order (lab); read on first use
+static int scs_xcd()
+{
+  if (g_scs_xcd < 0) {
+    const char* xc = getenv("SB_SCS_XCD");
+    g_scs_xcd      = xc ? atoi(xc) != 0 : 1;
+  }
+  return g_scs_xcd;
+}
 
 // dotPartials != NULL: fuse the level-0 partials of p.Ap into the SpMV (SCS C=64 only)
 // usePacked is 5 (the masked row programs) or 0 (the reference-layout stream): sb_matrix_use_packed, product_modes_only
@@ -48,28 +55,17 @@ static void launch_spmv(const sb_matrix* m, const double* x, double* y, double* 
     SB_SPMV_LAUNCH(spmv_crs_stream, dim3(per * 8), dim3(CRS_THREADS), 0, g.stream, m->rowBlocks, m->rowPtr, m->colInd,
         m->val, x, y, m->nRowBlocks, per, stop);
   } else if (m->C == 64) {
-    if (g_scs_nt < 0) {
-      const char* n = getenv("SB_SCS_NT");
-      g_scs_nt      = n ? atoi(n) : 1;
-      const char* xc = getenv("SB_SCS_XCD");
-      g_scs_xcd     = xc ? atoi(xc) : 1;
-    }
     const uint32_t nBlocks = (m->nChunks + 3) / 4;
-    const uint32_t per     = g_scs_xcd ? (nBlocks + 7) / 8 : 0;
-    dim3 grid(g_scs_xcd ? per * 8 : nBlocks), block(256);
+    const uint32_t per     = scs_xcd() ? (nBlocks + 7) / 8 : 0;
+    dim3 grid(scs_xcd() ? per * 8 : nBlocks), block(256);
     if (m->usePacked == 5) {
       launch_pat(m, false, x, y, dotPartials, stop, halo);
     } else {
-#define SCS_LAUNCH(U, D, N)                                                                      \
-  SB_SPMV_LAUNCH((spmv_scs64<U, D, N>), grid, block, 0, g.stream, m->chunkPtr, m->chunkLens, \
-      m->colInd, m->val, x, y, m->nr, m->nChunks, per, dotPartials, stop)
-#define SCS_PICK(U)                                                                           \
-  do {                                                                                        \
-    if (dot) { if (g_scs_nt) SCS_LAUNCH(U, true, true); else SCS_LAUNCH(U, true, false); }    \
-    else { if (g_scs_nt) SCS_LAUNCH(U, false, true); else SCS_LAUNCH(U, false, false); }      \
-  } while (0)
-      SCS_PICK(4); // (other unroll depths: measured equal or slower)
-#undef SCS_PICK
+#define SCS_LAUNCH(U, D)                                                                  \
+  SB_SPMV_LAUNCH((spmv_scs64<U, D>), grid, block, 0, g.stream, m->chunkPtr, m->chunkLens, \
+      m->colInd, m->val, x, y, m->nr, m->nChunks, per, dotPartials, stop, (uint32_t)m->residentK)
+      if (dot) SCS_LAUNCH(4, true); // (other unroll depths: measured equal or slower)
+      else SCS_LAUNCH(4, false);
 #undef SCS_LAUNCH
     }
   } else {
@@ -85,18 +81,8 @@ static void launch_spmv(const sb_matrix* m, const double* x, double* y, double* 
 static void launch_spmv_scs64_halo(const sb_matrix* m, const double* x, double* y, double* dotL1, const int* stop, const ScsHalo& hh,
     uint32_t perXcdI, uint32_t grid)
 {
-  if (g_scs_nt < 0) {
-    const char* n = getenv("SB_SCS_NT");
-    g_scs_nt      = n ? atoi(n) : 1;
-    const char* xc = getenv("SB_SCS_XCD");
-    g_scs_xcd     = xc ? atoi(xc) : 1;
-  }
-  if (g_scs_nt)
-    SB_SPMV_LAUNCH((spmv_scs64_halo<4, true>), dim3(grid), dim3(256), 0, g.stream, m->chunkPtr, m->chunkLens, m->colInd, m->val, x, y,
-        m->nr, m->nChunks, perXcdI, dotL1, stop, hh);
-  else
-    SB_SPMV_LAUNCH((spmv_scs64_halo<4, false>), dim3(grid), dim3(256), 0, g.stream, m->chunkPtr, m->chunkLens, m->colInd, m->val, x, y,
-        m->nr, m->nChunks, perXcdI, dotL1, stop, hh);
+  SB_SPMV_LAUNCH((spmv_scs64_halo<4>), dim3(grid), dim3(256), 0, g.stream, m->chunkPtr, m->chunkLens, m->colInd, m->val, x, y,
+      m->nr, m->nChunks, perXcdI, dotL1, stop, hh, (uint32_t)m->residentK);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -112,8 +98,8 @@ static void launch_pat(const sb_matrix* pm, bool skipPad, const double* x, doubl
   const uint32_t nBlocks = pm->mNTiles, dictE = pm->mDict;
   const size_t shmem     = ((size_t)dictE + 8) * sizeof(PatEntry) + (size_t)pm->mWindow * sizeof(double);
   if (!stop) stop = zero_flag();
-  const uint32_t pper = g_scs_xcd ? (nBlocks + 7) / 8 : 0;
-  const dim3 pgrid((g_scs_xcd ? pper * 8 : nBlocks) + (halo ? hw.nPush : 0u)), block(256);
+  const uint32_t pper = scs_xcd() ? (nBlocks + 7) / 8 : 0;
+  const dim3 pgrid((scs_xcd() ? pper * 8 : nBlocks) + (halo ? hw.nPush : 0u)), block(256);
 #define PAT_LAUNCH(CP, DO, SK, HA)                                                                                            \
   SB_SPMV_LAUNCH((spmv_scs64_pat<CP, DO, SK, HA, true>), pgrid, block, shmem, g.stream, pm->mHdrs, pm->mStream,                \
       reinterpret_cast<const uint16_t*>(pm->mRowBase), pm->mClassDict, pm->rowPats, pm->excRows, pm->mProgs, pm->mSlotMap,   \
@@ -160,8 +146,8 @@ static void launch_spmv_fusep(const sb_matrix* m, const double* pold, const doub
   memset(&hw, 0, sizeof hw);
   if (halo) hw = *halo;
   const uint32_t count = pm->mNTiles;
-  const uint32_t pper  = g_scs_xcd ? (count + 7) / 8 : 0;
-  const dim3 pgrid((g_scs_xcd ? pper * 8 : count) + (halo ? hw.nPush : 0u)), block(256);
+  const uint32_t pper  = scs_xcd() ? (count + 7) / 8 : 0;
+  const dim3 pgrid((scs_xcd() ? pper * 8 : count) + (halo ? hw.nPush : 0u)), block(256);
   const size_t shmem = (16 + (size_t)pm->mWindow) * sizeof(double);
 #define FP_LAUNCH(CP, SK, HA, MP)                                                                                          \
   SB_SPMV_LAUNCH((spmv_prog_fusep<CP, SK, HA, MP>), pgrid, block, shmem, g.stream, pm->mHdrs, pm->mRowBase, pm->mProgs,  \
@@ -415,11 +401,14 @@ static float placement_probe(sb_matrix* m, char* arena, const VecLayout& L, hipE
   }
   return best;
 }
+// ranks share this GPU (a rehearsal; set by the drivers when there are more ranks than devices): timings mean nothing, memory
+// and the Infinity Cache are shared
+static bool ranks_share_device() { return getenv("SB_SHARED_GPU") && atoi(getenv("SB_SHARED_GPU")) != 0; }
 static void tune_matrix_placement(sb_matrix* m)
 {
   const char* off = getenv("SB_PLACE");
   if ((off && atoi(off) == 0) || !g_tunePlacement) return;
-  if (getenv("SB_SHARED_GPU") && atoi(getenv("SB_SHARED_GPU")) != 0) return; // ranks share this GPU (a rehearsal): timings mean nothing, memory is shared
+  if (ranks_share_device()) return;
   if (!m || !m->colInd || !m->val || m->nr == 0) return;
   if (m->fmt == 1 && m->C != 64) return;
   const size_t ne = place_elems(m), colBytes = ne * sizeof(uint32_t), valBytes = ne * sizeof(double);
@@ -591,11 +580,53 @@ float sb_placement_probe(sb_matrix* m, void* arena)
   hipEvent_t ea, eb;
   HIP_CHECK(hipEventCreate(&ea));
   HIP_CHECK(hipEventCreate(&eb));
-  const int mode = m->usePacked;
-  m->usePacked   = 0;
+  const int mode = m->usePacked, share = m->residentK;
+  m->usePacked = 0, m->residentK = 0; // as the upload's tuner probes
   const float t  = placement_probe(m, (char*)arena, L, ea, eb);
-  m->usePacked   = mode;
+  m->usePacked = mode, m->residentK = share;
   HIP_CHECK(hipEventDestroy(ea));
   HIP_CHECK(hipEventDestroy(eb));
   return t;
+}
+
+// ===========================================================================
+// resident share of the Sell-64 stream (kernels.hip.h: scs64_block_resident)
+// ===========================================================================
+// The matrix does not change between the SpMVs of a solve, and the 256 MiB Infinity Cache keeps what plain loads read while
+// non-temporal loads pass through it (profiles/r03_mall_lab.txt, profiles/resident_share_mall_lab.txt).  Between two SpMVs the
+// section-8d loop touches r, p, x and Ap; the rest of the cache holds nothing the loop uses.  So k sixteenths of the stream's
+// blocks, evenly interleaved in every XCD's range, are read with plain loads and come from the cache in every SpMV after the
+// first; the other blocks stay non-temporal so that they displace neither that share nor the vectors.
+//   share bytes = RESIDENT_FILL x (cache - 4 vectors of nc doubles), floored at 0, capped at the stream, rounded DOWN to
+//   sixteenths of the stream;
+//   k = 0 (today's all-non-temporal kernel) when ranks share the device, and whenever the vectors alone exceed the cache.
+// There is no query for the cache's size: it is a constant of the architecture this library is built for (gfx950: 256 MiB).
+static constexpr double INFINITY_CACHE_BYTES = 256.0 * 1048576.0;
+// RESIDENT_FILL: in the lab case a table of 192 MiB (with the vectors: the whole cache) is still read back at its cache-hot rate;
+// in the product the sweep of k at HPCG 128^3 is fastest at k = 4 (168 MB + 67 MB of vectors = 0.88 of the cache), k = 5 (210 MB:
+// more than the cache with the vectors) is slower again and k >= 6 is slower than k = 0.  0.85 of the room the
+// vectors leave gives k = 4 there and stays below the knee.
+static constexpr double RESIDENT_FILL        = 0.85;
+int sb_resident_share_rule(double streamBytes, uint32_t nc, int sharedDevice)
+{
+  if (sharedDevice || !(streamBytes > 0.0)) return 0;
+  const double room = INFINITY_CACHE_BYTES - 4.0 * 8.0 * (double)nc;
+  if (room <= 0.0) return 0;
+  const double share = std::min(RESIDENT_FILL * room, streamBytes);
+  return (int)std::min(16.0, std::floor(16.0 * share / streamBytes));
+}
+static double resident_stream_bytes(const sb_matrix* m) { return 12.0 * (double)m->nElems; }
+static void set_resident_share(sb_matrix* m)
+{
+  m->residentRule = (m->fmt == 1 && m->C == 64 && m->prec == 2) ? sb_resident_share_rule(resident_stream_bytes(m), m->nc, ranks_share_device()) : 0;
+  m->residentK    = m->residentRule;
+}
+// k = -1: the rule's share (the default); 0 ... 16: that many sixteenths.  Returns the share in force (always 0 for a matrix
+// that spmv_scs64 does not serve).  Any share gives the same bits.
+int sb_matrix_resident_share(sb_matrix* m, int k)
+{
+  if (k < -1 || k > 16) SB_FATAL("sb_matrix_resident_share(%d): expected -1 (the rule) or 0 ... 16 sixteenths", k);
+  if (!(m->fmt == 1 && m->C == 64 && m->prec == 2)) return 0;
+  m->residentK = k < 0 ? m->residentRule : k;
+  return m->residentK;
 }

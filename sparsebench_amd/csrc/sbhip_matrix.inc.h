@@ -14,6 +14,7 @@ static void* upload(const void* host, size_t bytes)
 static void build_crs_mirror(sb_matrix* m, const uint32_t* rowPtr, const uint32_t* colInd, const double* val);
 
 static void tune_matrix_placement(sb_matrix* m); // (sbhip_launch.inc.h, behind launch_spmv)
+static void set_resident_share(sb_matrix* m);    // (sbhip_launch.inc.h, behind the tuner: it probes with share 0)
 static bool g_tunePlacement = true;               // off while an upload builds a device-private mirror (its reference arrays are freed again)
 
 // crossing precisions is an error: an fp64 entry point on a single-precision matrix, or the other way round (file:line of the call)
@@ -1175,6 +1176,7 @@ sb_matrix* sb_scs_upload(uint32_t nr, uint32_t nc, uint32_t C, uint32_t sigma, u
   build_patterns(m, chunkPtr, chunkLens, colInd, val, oldToNewPerm);
   product_modes_only(m);
   tune_matrix_placement(m);
+  set_resident_share(m);
   return m;
 }
 

@@ -198,6 +198,11 @@ class Problem:
         capi.load().sb_matrix_use_packed(self.matrix, int(mode))
         return capi.load().sb_matrix_packed_mode(self.matrix)
 
+    def resident_share(self, k=-1):
+        """sixteenths of the Sell-64 stream that the reference-layout kernel keeps in the Infinity Cache across SpMVs
+        (sb_matrix_resident_share): -1 = the upload's rule, 0 ... 16 = forced.  Returns the share in force."""
+        return capi.load().sb_matrix_resident_share(self.matrix, int(k))
+
     def placement_report(self):
         """what the upload's placement tuner saw (us of a proxy loop body: p update | SpMV on the reference-layout stream | r update):
         with the first vectors' arena tried and the stream where hipMalloc put it, at the pair kept, at the slowest pair; None if

@@ -7,6 +7,10 @@
 // For each policy:   write V (84 MB, dirty) | stream M (704 MB) | read V   -- times of all three, read V compared with
 //   "hot" (read V right after write V) and "cold" (after 704 MB of plain stores to another buffer).
 // Also: stream M after V was only READ (clean lines) vs after V was WRITTEN (dirty lines): the write-back share.
+// Resident-table case (`mall_lab resident` runs it alone): a table of T MB is read once per round with plain loads; between two
+// reads of it lie 540 MB of nt stream reads and 67 MB of plain vector traffic (what the rest of a CG iteration does when T MB of
+// the matrix stream are to be served from the cache).  The table's read-back rate for T = 32 ... 192 MB, next to the same read
+// right after itself (hot) and after 704 MB of plain stores (cold).
 // build: hipcc --offload-arch=gfx950 -O3 -o bin/mall_lab mall_lab.hip
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -59,8 +63,55 @@ template <typename F> static float timed(F f)
   return ms * 1e3f;
 }
 
-int main()
+// the resident-table case (see the head of the file)
+static void resident_table_case()
 {
+  const size_t TMAX = 192ull << 20, SB = 540ull << 20, JB = 704ull << 20;
+  const size_t vb = (size_t)128 * 128 * 128 * 8; // one CG vector at 128^3: 16.8 MB
+  f64x2 *T, *S, *Junk, *r, *p, *x;
+  double* out;
+  CK(hipMalloc(&T, TMAX)); CK(hipMalloc(&S, SB)); CK(hipMalloc(&Junk, JB)); CK(hipMalloc(&r, vb)); CK(hipMalloc(&p, vb)); CK(hipMalloc(&x, vb));
+  CK(hipMalloc(&out, 64));
+  CK(hipMemset(T, 1, TMAX)); CK(hipMemset(S, 1, SB)); CK(hipMemset(Junk, 0, JB)); CK(hipMemset(r, 0, vb)); CK(hipMemset(p, 0, vb)); CK(hipMemset(x, 0, vb));
+  const dim3 grid(256 * 8), block(256);
+  const size_t s2 = SB / 16, j2 = JB / 16, h2 = vb / 16;
+  printf("resident table: T MB read with plain loads once per round; between two reads 540 MB of nt reads + 67 MB of plain vector traffic "
+         "(axpy: 2 reads + 1 write of 16.8 MB, one more 16.8 MB read); times in us, rates in TB/s, median of 5 rounds [min .. max]\n");
+  for (size_t tmb = 32; tmb <= 192; tmb += 32) {
+    const size_t t2 = (tmb << 20) / 16;
+    auto rdT    = [&]() { hipLaunchKernelGGL(read_k<false>, grid, block, 0, 0, T, t2, out); };
+    auto between = [&]() {
+      hipLaunchKernelGGL(read_k<true>, grid, block, 0, 0, S, s2, out);
+      hipLaunchKernelGGL(axpy_k<false>, grid, block, 0, 0, r, p, h2, 0.5);
+      hipLaunchKernelGGL(read_k<false>, grid, block, 0, 0, x, h2, out);
+    };
+    hipLaunchKernelGGL(write_k<false>, grid, block, 0, 0, Junk, j2, 2.0);
+    rdT();
+    const float hot = timed(rdT);
+    hipLaunchKernelGGL(write_k<false>, grid, block, 0, 0, Junk, j2, 2.0);
+    const float cold = timed(rdT);
+    float t[5], tb[5];
+    for (int w = 0; w < 2; w++) { between(); rdT(); }
+    for (int i = 0; i < 5; i++) { tb[i] = timed(between); t[i] = timed(rdT); }
+    for (int i = 0; i < 5; i++)
+      for (int j = i + 1; j < 5; j++) {
+        if (t[j] < t[i]) { float q = t[i]; t[i] = t[j]; t[j] = q; }
+        if (tb[j] < tb[i]) { float q = tb[i]; tb[i] = tb[j]; tb[j] = q; }
+      }
+    const double B = (double)(tmb << 20);
+    printf("T = %3zu MB: hot %.1f us (%.2f)  cold %.1f us (%.2f)  in the loop %.1f us (%.2f) [%.1f .. %.1f]   the 607 MB between: %.1f us [%.1f .. %.1f]\n",
+        tmb, hot, B / hot * 1e-6, cold, B / cold * 1e-6, t[2], B / t[2] * 1e-6, t[0], t[4], tb[2], tb[0], tb[4]);
+  }
+  CK(hipFree(T)); CK(hipFree(S)); CK(hipFree(Junk)); CK(hipFree(r)); CK(hipFree(p)); CK(hipFree(x)); CK(hipFree(out));
+}
+
+int main(int argc, char** argv)
+{
+  if (argc > 1 && argv[1][0] == 'r') {
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    resident_table_case();
+    return 0;
+  }
   const size_t VB = 84ull << 20, MB = 704ull << 20;
   f64x2 *V, *W, *M, *Mu, *Junk;
   double* out;
@@ -123,5 +174,6 @@ int main()
       printf("axpy 3 x 16.8 MB, %s stores: cold %.1f us (%.2f TB/s)  hot %.1f us (%.2f)\n", nt ? "nt" : "plain", cold, 3.0 * h2 * 16 / cold * 1e-6, hot, 3.0 * h2 * 16 / hot * 1e-6);
     }
   }
+  resident_table_case();
   return 0;
 }
