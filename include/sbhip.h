@@ -570,6 +570,25 @@ void sb_pcg_update_r_native(uint32_t n, double nalpha, const double* Ap_dev, dou
  * and strides over them by the number of waves in the grid */
 void sb_pcg_update_r_launch(uint32_t n, uint32_t out[3]);
 
+/* ---- symmetric Gauss-Seidel preconditioning by multicolouring ----
+ * z = M^-1 r with M = (D + L) D^-1 (D + U) in a colour order: rows are adjacent when a_ij or a_ji is stored, off the diagonal
+ * and non-zero; rows 0, 1, ... of the device's order each take the smallest colour no adjacent, already coloured row has.  A
+ * colour is one launch: nC forward, nC - 1 backward per apply.  The handle is an sb_pcg: every other sb_pcg_* call works on it,
+ * sb_pcg_dinv gives 1 / diag(A).  Square matrix, double precision, one rank, tree dot order; a row without a finite positive
+ * diagonal is a fatal error.  The set-up downloads the matrix once and builds the sweep structure on the host. */
+sb_pcg* sb_pcg_create_sgs(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host);
+int sb_pcg_precond(const sb_pcg* s); /* 0 diagonal, 1 SGS */
+int sb_pcg_colours(const sb_pcg* s); /* nC; 0 for a diagonal handle */
+void sb_pcg_colouring(const sb_pcg* s, uint32_t* colour_host); /* nr colours, original row order; SGS handles only */
+/* z = M^-1 r once, with the handle's preconditioner (either kind), on host vectors of nr doubles in original row order;
+ * blocking, on scratch vectors of its own; a fatal error between sb_pcg_start and sb_pcg_finish */
+void sb_pcg_apply_precond(sb_pcg* s, const double* r_host, double* z_host);
+/* GPU milliseconds per apply, the mean of `reps` back-to-back applies (after one untimed) on scratch vectors holding b; blocking;
+ * not between sb_pcg_start and sb_pcg_finish */
+double sb_pcg_apply_precond_ms(sb_pcg* s, int reps);
+/* bytes one apply reads and writes: the sweep structure and the vector traffic (diagonal: 24 per row) */
+double sb_pcg_precond_bytes(const sb_pcg* s);
+
 /* ---- BiCGStab with a diagonal preconditioner ----------------------------------------------------------- */
 /* Right-preconditioned BiCGStab for matrices that need not be symmetric: two SpMVs per body, about ten vectors whatever the
  * iteration count, no restart.  x0 = 0, rhat = b; the loop test is on sqrt(r.r) alone (no exit on ||s||); rho = 0, rhat.v = 0

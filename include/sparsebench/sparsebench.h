@@ -263,6 +263,9 @@ int sbh_solve_cg_batch(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT n
                        int nrhs);
 /* CG with the Jacobi preconditioner dinv = 1 / diag(A) (sb_pcg_*, sbhip.h): prints what solveCG prints; double precision, one rank */
 int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz);
+/* the same with symmetric Gauss-Seidel by multicolouring in the diagonal's place (sb_pcg_create_sgs, sbhip.h); first prints
+ * "Preconditioner: SGS ..., nC = <colours>" */
+int sbh_solve_pcg_sgs(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz);
 /* BiCGStab with the Jacobi right preconditioner (sb_bicgstab_*, sbhip.h) for matrices that need not be symmetric: prints what
  * solveCG prints; double precision, one rank */
 int sbh_solve_bicgstab(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz);
@@ -287,6 +290,12 @@ int solveCGBatch(Comm* comm, Parameter* param, Matrix* m, int nrhs);
  * A matrix row without a finite positive diagonal entry ends the process with a message.  One rank, tree dot order; the
  * single-precision libraries export it too and end the process with "PCG: double precision only". */
 int solvePCG(Comm* comm, Parameter* param, Matrix* m);
+/* solvePCG with HPCG's own preconditioner, symmetric Gauss-Seidel, applied by multicolouring: z = M^-1 r with
+ * M = (D + L) D^-1 (D + U) in a greedy colour order of the rows, one launch per colour and sweep.  Prints the preconditioner and
+ * its colour count, then solvePCG's lines; returns k as solveCG does.  Square matrix, one rank, tree dot order; a row without a
+ * finite positive diagonal entry ends the process with a message; the single-precision libraries export it too and end the
+ * process with "PCG: double precision only". */
+int solvePCGSGS(Comm* comm, Parameter* param, Matrix* m);
 /* Jacobi-preconditioned BiCGStab: the short-recurrence solver for matrices that are not symmetric; returns k as
  * solveCG does.  The single-precision libraries export it too and end the process with "BiCGStab: double precision only". */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m);

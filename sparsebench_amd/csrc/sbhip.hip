@@ -26,6 +26,7 @@
 #include "gmres.hip.h"
 #include "batch.hip.h"
 #include "pcg.hip.h"
+#include "sgs.hip.h"
 #include "bicgstab.hip.h"
 
 #include <algorithm>
@@ -698,4 +699,5 @@ void sb_event_destroy(void* ev) { HIP_CHECK(hipEventDestroy((hipEvent_t)ev)); }
 #include "sbhip_gmres.inc.h"
 #include "sbhip_cgb.inc.h"
 #include "sbhip_pcg.inc.h"
+#include "sbhip_sgs.inc.h"
 #include "sbhip_bicgstab.inc.h"

@@ -17,7 +17,11 @@ struct sb_pcg {
   int hist_cap = 0;
   int k_next = 1;
   LoopClock clock;
+  struct SgsPlan* sgs = nullptr; // symmetric Gauss-Seidel in place of the diagonal (sbhip_sgs.inc.h); dinv is 1 / diag(A)
 };
+// (sbhip_sgs.inc.h) the r update, the sweeps and the r.z values of an SGS handle; its plan's release
+static void sgs_residual_and_z(sb_pcg* s, bool prologue);
+static void sgs_release(sb_pcg* s);
 
 // the diagonal in the device's row order; bad_dev: NULL, or two uint32 (rows without a finite positive diagonal, the first of
 // them) preset to {0, 0xFFFFFFFF}
@@ -60,16 +64,19 @@ void sb_pcg_update_r_native(uint32_t n, double nalpha, const double* Ap_dev, dou
   test_block_done(S);
 }
 
-sb_pcg* sb_pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const double* dinv_host)
+// fn: the entry point as messages name it; precond: "Jacobi", or "SGS" (which has no caller's diagonal to fall back on)
+static bool dinv_host_allowed(const char* precond) { return precond[0] == 'J'; }
+static sb_pcg* pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const double* dinv_host,
+    const char* fn, const char* precond)
 {
   need_init();
-  need_dp(m, "sb_pcg_create", "PCG");
-  need_one_rank(m, halo, "sb_pcg_create", "PCG");
-  need_tree("sb_pcg_create", "PCG", "sb_cg");
+  need_dp(m, fn, "PCG");
+  need_one_rank(m, halo, fn, "PCG");
+  need_tree(fn, "PCG", "sb_cg");
   if (dinv_host)
     for (uint32_t i = 0; i < m->nr; i++)
       if (!(dinv_host[i] > 0.0 && dinv_host[i] < INFINITY))
-        SB_FATAL("sb_pcg_create: dinv[%u] = %g: the preconditioner's entries must be finite and positive", i, dinv_host[i]);
+        SB_FATAL("%s: dinv[%u] = %g: the preconditioner's entries must be finite and positive", fn, i, dinv_host[i]);
   sb_pcg* s       = new sb_pcg();
   s->A = m, s->nr = m->nr, s->nc = m->nc;
   s->nGroups      = (m->nr + 255u) >> 8;
@@ -88,8 +95,9 @@ sb_pcg* sb_pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, c
     sb_d2h(bad, dbad, sizeof bad);
     sb_free(dbad);
     if (bad[0])
-      SB_FATAL("sb_pcg_create: %u of %u matrix rows have no finite positive diagonal entry (the first: device row %u): the Jacobi "
-               "preconditioner needs one in every row; pass dinv_host for another diagonal preconditioner", bad[0], m->nr, bad[1]);
+      SB_FATAL("%s: %u of %u matrix rows have no finite positive diagonal entry (the first: device row %u): the %s "
+               "preconditioner needs one in every row%s", fn, bad[0], m->nr, bad[1], precond,
+          dinv_host_allowed(precond) ? "; pass dinv_host for another diagonal preconditioner" : "");
     hipLaunchKernelGGL(pcg_reciprocal_k, dim3(stream_grid(m->nr, 256)), dim3(256), 0, g.stream, m->nr, (const double*)tmp, s->dinv);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(g.stream));
@@ -113,19 +121,26 @@ sb_pcg* sb_pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, c
   return s;
 }
 
+sb_pcg* sb_pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const double* dinv_host)
+{
+  return pcg_create(m, halo, b_host, xexact_host, dinv_host, "sb_pcg_create", "Jacobi");
+}
+
 void sb_pcg_free(sb_pcg* s)
 {
   if (!s) return;
   HIP_CHECK(hipStreamSynchronize(g.stream));
   s->clock.destroy();
+  sgs_release(s);
   sb_free(s->r), sb_free(s->z), sb_free(s->p), sb_free(s->Ap), sb_free(s->x), sb_free(s->b), sb_free(s->dinv), sb_free(s->xexact);
   sb_free(s->S), sb_free(s->l1pAp), sb_free(s->l1rz), sb_free(s->l1rr), sb_free(s->rr_hist), sb_free(s->rz_hist), sb_free(s->pAp_hist);
   delete s;
 }
 
 // launches per loop body: p update | SpMV (+ p.Ap values) | alpha | r update (+ z, r.z and r.r values) | beta = 5 where the
-// selected SpMV kernel has a fused dot; native CRS and generic C add the dot pass: 6
-int sb_pcg_launches_per_body(const sb_pcg* s) { return spmv_dot_kind(s->A) ? 5 : 6; }
+// selected SpMV kernel has a fused dot; native CRS and generic C add the dot pass: 6.  An SGS handle: the r update makes no z;
+// nC forward and nC - 1 backward launches and the r.z pass stand in between it and beta: 2 nC + 5 (+ 1)
+int sb_pcg_launches_per_body(const sb_pcg* s) { return (spmv_dot_kind(s->A) ? 5 : 6) + (s->sgs ? 2 * sb_pcg_colours(s) : 0); }
 
 template <int MODE> static void pcg_scalar_launch(sb_pcg* s)
 {
@@ -156,7 +171,9 @@ static void pcg_body(sb_pcg* s, int k)
     }
   }
   pcg_scalar_launch<2>(s);
-  if (n) {
+  if (s->sgs) {
+    sgs_residual_and_z(s, false);
+  } else if (n) {
     hipLaunchKernelGGL(pcg_update_r_k<0>, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, (const double*)s->Ap,
         (const double*)s->r, s->r, (const double*)s->dinv, s->z, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
     HIP_CHECK(hipGetLastError());
@@ -178,7 +195,9 @@ void sb_pcg_start(sb_pcg* s, int itermax, double eps)
   HIP_CHECK(hipMemsetAsync(s->x, 0, (size_t)s->nr * sizeof(double), g.stream));
   HIP_CHECK(hipMemsetAsync(s->p, 0, (size_t)s->nc * sizeof(double), g.stream));
   launch_spmv(s->A, s->p, s->Ap, nullptr, nullptr);
-  if (s->nr) {
+  if (s->sgs) {
+    sgs_residual_and_z(s, true);
+  } else if (s->nr) {
     hipLaunchKernelGGL(pcg_update_r_k<1>, dim3(vec_stream_grid(s->nr)), dim3(1024), 0, g.stream, s->nr, (const double*)s->Ap,
         (const double*)s->b, s->r, (const double*)s->dinv, s->z, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
     HIP_CHECK(hipGetLastError());

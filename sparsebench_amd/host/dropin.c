@@ -64,6 +64,8 @@ int solveCGBatch(Comm* comm, Parameter* param, Matrix* m, int nrhs)
 
 /* Jacobi-preconditioned CG on this build's Matrix (the _sp libraries: "PCG: double precision only") */
 int solvePCG(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_pcg(comm, param, m->dev, m->nr, m->rowNnz); }
+/* the same with multicolour symmetric Gauss-Seidel in the diagonal's place */
+int solvePCGSGS(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_pcg_sgs(comm, param, m->dev, m->nr, m->rowNnz); }
 /* Jacobi-preconditioned BiCGStab on this build's Matrix (the _sp libraries: "BiCGStab: double precision only") */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_bicgstab(comm, param, m->dev, m->nr, m->rowNnz); }
 

@@ -28,6 +28,7 @@ static const char* kHelp =
     "  -m <matrix>   Load a matrix market (.mtx) or binary (.bmx) file\n"
     "  -t <bench type>   Benchmark type, can be cg, spmv, gmres, pcg (CG with the Jacobi preconditioner),\n"
     "                    or bicgstab (BiCGStab with the Jacobi preconditioner: non-symmetric matrices). Default cg.\n"
+    "  -p <jacobi|sgs>   Preconditioner of -t pcg, sgs is multicolour symmetric Gauss-Seidel. Default jacobi.\n"
     "  -r <int>   GMRES restart length. Default 30.\n"
     "  -n <int>   Number of right-hand sides for -t cg. Default 1.\n"
     "  -x <int>   Size in x for generated matrix, ignored if MM file is loaded. Default 100.\n"
@@ -58,8 +59,9 @@ int main(int argc, char** argv)
   int type = CG, opt;
   unsigned scsC = 64, scsSigma = 1;
   int restart = 30, nrhs = 1;
+  int precond = -1; /* -p: 0 jacobi, 1 sgs; -1 not given */
   opterr = 0;
-  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:")) != -1) switch (opt) {
+  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:p:")) != -1) switch (opt) {
     case 'h':
       if (commIsMaster(&comm)) printf("%s", kHelp);
       commAbort(&comm, "");
@@ -96,6 +98,14 @@ int main(int argc, char** argv)
     case 's': scsSigma = (unsigned)atoi(optarg); break;
     case 'r': restart = atoi(optarg); break;
     case 'n': nrhs = atoi(optarg); break;
+    case 'p':
+      if (strcmp(optarg, "jacobi") == 0) precond = 0;
+      else if (strcmp(optarg, "sgs") == 0) precond = 1;
+      else {
+        fprintf(stderr, "Unknown preconditioner %s (-p <jacobi|sgs>)\n", optarg);
+        return 1;
+      }
+      break;
     default:
       if (isprint(optopt)) fprintf(stderr, "Unknown option `-%c'.\n", optopt);
       else fprintf(stderr, "Unknown option character `\\x%x'.\n", optopt);
@@ -104,6 +114,10 @@ int main(int argc, char** argv)
   for (int i = optind; i < argc; i++) printf("Non-option argument %s\n", argv[i]);
   if (nrhs != 1 && type != CG) {
     fprintf(stderr, "-n <int> (several right-hand sides) goes with -t cg only\n");
+    return 1;
+  }
+  if (precond != -1 && type != PCG) {
+    fprintf(stderr, "-p <jacobi|sgs> (the preconditioner) goes with -t pcg only\n");
     return 1;
   }
 
@@ -142,7 +156,12 @@ int main(int argc, char** argv)
     k = solveGMRES(&comm, &param, &sm, restart);
   } else if (type == PCG) {
     if (commIsMaster(&comm)) printf("Test type: PCG\n");
-    k = solvePCG(&comm, &param, &sm);
+    if (precond == 1) {
+      k = solvePCGSGS(&comm, &param, &sm); /* (prints "Preconditioner: SGS ..., nC = <colours>" itself: it knows them) */
+    } else {
+      if (commIsMaster(&comm)) printf("Preconditioner: Jacobi (diagonal), nC = 0\n");
+      k = solvePCG(&comm, &param, &sm);
+    }
   } else if (type == BICGSTAB) {
     if (commIsMaster(&comm)) printf("Test type: BiCGStab\n");
     k = solveBiCGStab(&comm, &param, &sm);

@@ -290,16 +290,19 @@ int sbh_solve_cg_batch(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT n
   return k;
 }
 
-/* ---- solvePCG ---------------------------------------------------------------------------- */
-/* solveCG with the Jacobi preconditioner (sb_pcg_*).  The lines solveCG prints while iterating are printed
- * afterwards from the recorded r.r history, indexed as solveCG's own. */
-int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
+/* ---- solvePCG, solvePCGSGS --------------------------------------------------------------- */
+/* solveCG with the Jacobi preconditioner (sb_pcg_*), or with symmetric Gauss-Seidel by multicolouring in its place
+ * (sgs).  The lines solveCG prints while iterating are printed afterwards from the recorded r.r history, indexed as
+ * solveCG's own; the SGS solve names its preconditioner and colour count first. */
+static int solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int sgs)
 {
   dp_only("PCG: double precision only\n");
   const int itermax = param->itermax, cap = itermax + 2;
   double *b, *xexact;
   init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
-  sb_pcg* s     = sb_pcg_create((const sb_matrix*)dev_matrix, NULL, b, xexact, NULL);
+  sb_pcg* s = sgs ? sb_pcg_create_sgs((const sb_matrix*)dev_matrix, NULL, b, xexact)
+                  : sb_pcg_create((const sb_matrix*)dev_matrix, NULL, b, xexact, NULL);
+  if (sgs && commIsMaster(comm)) printf("Preconditioner: SGS (multicolour symmetric Gauss-Seidel), nC = %d\n", sb_pcg_colours(s));
   const int k   = sb_pcg_solve(s, itermax, param->eps);
   double* rr    = (double*)malloc((size_t)cap * sizeof(double));
   double* rz    = (double*)malloc((size_t)cap * sizeof(double));
@@ -311,6 +314,14 @@ int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, co
   sb_pcg_free(s);
   free(rr), free(rz), free(pAp), free(b), free(xexact);
   return k;
+}
+int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
+{
+  return solve_pcg(comm, param, dev_matrix, nr, rowNnz, 0);
+}
+int sbh_solve_pcg_sgs(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
+{
+  return solve_pcg(comm, param, dev_matrix, nr, rowNnz, 1);
 }
 
 /* ---- solveBiCGStab ----------------------------------------------------------------------- */

@@ -543,14 +543,52 @@ class BatchCG(_BodySolver):
 class PCG(_BodySolver):
     """solveCG with a diagonal preconditioner put back (sb_pcg_*): z = r * dinv, alpha = r.z / p.Ap,
     beta = r.z / (r.z)_old, the loop test on sqrt(r.r).  dinv None: Jacobi, 1 / diag(A); else nr finite positive doubles in
-    original row order (all 1.0: `CG` in the tree order bit for bit).  Double precision, one rank, tree dot order."""
+    original row order (all 1.0: `CG` in the tree order bit for bit).  precond "sgs": symmetric Gauss-Seidel by multicolouring
+    in place of the diagonal (takes no dinv).  Double precision, one rank, tree dot order."""
 
     PREFIX, NAME = "sb_pcg", "PCG"
     COUNTERS = ("stop", "stop_next", "iters", "n_rr", "n_pAp")
 
-    def __init__(self, problem, dinv=None):
+    def __init__(self, problem, dinv=None, precond="jacobi"):
+        self._need_double(problem)
+        if precond not in ("jacobi", "sgs"):
+            raise ValueError("precond must be 'jacobi' or 'sgs', got %r" % (precond,))
+        if precond == "sgs" and dinv is not None:
+            raise ValueError("precond='sgs' takes no dinv: its diagonal is the matrix's own")
         b, xe = self._open(problem)
-        self.ptr = self.L.sb_pcg_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), _ptr(self._dinv_arg(dinv)))
+        if precond == "sgs":
+            self.ptr = self.L.sb_pcg_create_sgs(problem.matrix, problem.halo, _ptr(b), _ptr(xe))
+        else:
+            self.ptr = self.L.sb_pcg_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), _ptr(self._dinv_arg(dinv)))
+
+    def precond(self):
+        """"jacobi" (any diagonal) or "sgs" """
+        return ("jacobi", "sgs")[self.L.sb_pcg_precond(self.ptr)]
+
+    def colours(self):
+        """nC of an SGS handle; 0 for a diagonal one"""
+        return self.L.sb_pcg_colours(self.ptr)
+
+    def colouring(self):
+        """the colour of every row, original row order (SGS handles)"""
+        out = np.zeros(self.problem.nr, dtype=np.uint32)
+        self.L.sb_pcg_colouring(self.ptr, out.ctypes.data_as(vp))
+        return out
+
+    def apply(self, r):
+        """z = M^-1 r with the handle's preconditioner, once; r and z in original row order.  Not between start and finish."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if r.shape != (self.problem.nr,):
+            raise ValueError("r must hold nr = %d doubles, got shape %r" % (self.problem.nr, r.shape))
+        return self._vector("apply_precond", r.ctypes.data_as(vp))
+
+    def apply_ms(self, reps=10):
+        """GPU milliseconds per apply, the mean of `reps` back-to-back applies on scratch vectors"""
+        return self.L.sb_pcg_apply_precond_ms(self.ptr, int(reps))
+
+    def precond_bytes(self):
+        """bytes one apply reads and writes (the byte model's input)"""
+        return self.L.sb_pcg_precond_bytes(self.ptr)
 
     def history(self):
         """rr, rz, pAp"""

@@ -1,0 +1,70 @@
+"""`-t pcg -p sgs` from the benchmark drivers: the iteration count, the residual lines and the colour count of the
+CPU restatement at 16^3; the switch's refusals."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import pcg_ref
+import sgs_ref as ref
+from conftest import load_json
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "sparsebench_amd", "bin")
+ITERMAX = 60
+SIZE = ["-x", "16", "-y", "16", "-z", "16"]
+
+
+def run(cmd):
+    return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+
+
+@pytest.fixture(scope="module")
+def want():
+    """CRS and Sell-64-1 walk the same order (sigma = 1); itermax 60, eps 0: the golden case's histories in the natural order"""
+    g = ref.gmatrix(("hpcg", 16))
+    op = ref.operator(g)
+    out = ref.solve(op, ref.Plan(g, op), g.rhs(), pcg_ref.jacobi(g), ITERMAX, 0.0)
+    g.free()
+    return out
+
+
+@pytest.mark.parametrize("exe", ["sparseBench-CRS-HIP", "sparseBench-SCS-HIP"])
+def test_driver_runs_sgs_pcg(gpu, exe, want):
+    e = load_json("sgs_hist.json")["cases"]["hpcg16_sell_64_256"]
+    assert want["k"] == e["k"] == ITERMAX
+    out = run([os.path.join(BIN, exe), "-t", "pcg", "-p", "sgs", "-i", str(ITERMAX), "-e", "0.0"] + SIZE)
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    txt = out.stdout.decode()
+    assert re.search(r"^Test type: PCG\nPreconditioner: SGS .*nC = %d$" % e["nC"], txt, re.M)
+    assert "Initial Residual = %E" % np.sqrt(want["rr"][0]) in txt
+    freq = max(1, min(50, ITERMAX // 10))
+    for j in range(1, want["k"]):
+        if j % freq == 0 or j + 1 == ITERMAX:
+            assert "Iteration = %d Residual = %E" % (j, np.sqrt(want["rr"][0 if j == 1 else j - 1])) in txt, j
+    assert re.search(r"^Solution performed %d iterations and took \d+\.\d\ds$" % e["k"], txt, re.M)
+    assert "Difference between computed and exact  = " in txt
+    # the default and -p jacobi are the Jacobi solve
+    for extra in ([], ["-p", "jacobi"]):
+        txt = run([os.path.join(BIN, exe), "-t", "pcg", "-i", "20"] + extra + SIZE).stdout.decode()
+        assert re.search(r"^Test type: PCG\nPreconditioner: Jacobi .*nC = 0$", txt, re.M)
+        assert re.search(r"^Solution performed 20 iterations", txt, re.M)
+
+
+def test_switch_refusals(gpu):
+    crs = os.path.join(BIN, "sparseBench-CRS-HIP")
+    small = ["-x", "8", "-y", "8", "-z", "8", "-i", "10"]
+    assert re.search(r"-p <jacobi\|sgs>", run([crs, "-h"]).stdout.decode())
+    for t in ("cg", "gmres", "spmv", "bicgstab"):
+        out = run([crs, "-t", t, "-p", "sgs"] + small)
+        assert out.returncode == 1 and "goes with -t pcg only" in out.stderr.decode(), t
+    out = run([crs, "-p", "sgs"] + small)  # the default type is cg
+    assert out.returncode == 1 and "goes with -t pcg only" in out.stderr.decode()
+    out = run([crs, "-t", "pcg", "-p", "ilu"] + small)
+    assert out.returncode == 1 and "Unknown preconditioner ilu" in out.stderr.decode()
+    for exe in ("sparseBench-CRS-HIP-SP", "sparseBench-SCS-HIP-SP"):
+        out = run([os.path.join(BIN, exe), "-t", "pcg", "-p", "sgs"] + small)
+        assert out.returncode == 1 and "PCG: double precision only" in out.stderr.decode()

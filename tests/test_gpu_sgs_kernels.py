@@ -1,0 +1,87 @@
+"""The SGS preconditioner on the GPU without a solve: the colouring the set-up makes, and one apply through
+sb_pcg_apply_precond, == the CPU restatement (tests/sgs_ref.py, pinned by tests/test_sgs_host.py) BIT FOR BIT, NaN equal to NaN:
+colours with fewer than 64 rows, full plus partial chunks, varying row lengths, every format, hand-made matrices (1 x 1,
+diagonal, arrow, stored zeros), right-hand sides with +0.0, -0.0, a denormal, an inf and a NaN."""
+import numpy as np
+import pytest
+
+import pcg_ref
+import sgs_cases
+import sgs_ref as ref
+from sparsebench_amd import hostapi
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def tmp(tmp_path_factory):
+    return tmp_path_factory.mktemp("sgs_kernels")
+
+
+def same(got, want, what):
+    a, b = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(want, dtype=np.float64)
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    na, nb = np.isnan(a), np.isnan(b)
+    assert np.array_equal(na, nb), (what, "NaN positions differ", np.nonzero(na != nb)[0][:5])
+    bad = np.nonzero((a.view(np.uint64) != b.view(np.uint64)) & ~na)[0]
+    assert bad.size == 0, (what, "first difference at", int(bad[0]), a[bad[0]], b[bad[0]], "of", bad.size)
+
+
+def check(matrix, fmt, C, sigma, tmp, nC=None):
+    g = ref.gmatrix(matrix, tmp)
+    op = ref.operator(g, fmt, C, sigma)
+    plan = ref.Plan(g, op)
+    dinv = pcg_ref.jacobi(g)
+    p = hostapi.Problem(*ref.problem_args(matrix, tmp), fmt=fmt, Cc=C, sigma=sigma)
+    if sigma > 1:  # the restatement walks the device's own permutation
+        assert np.array_equal(p.array("oldToNewPerm"), op.o2n if op.o2n is not None else np.arange(p.nr))
+    s = hostapi.PCG(p, precond="sgs")
+    what = (matrix, fmt, C, sigma)
+    assert s.precond() == "sgs" and s.colours() == plan.nC, (what, s.colours(), plan.nC)
+    if nC is not None:
+        assert plan.nC == nC
+    assert np.array_equal(s.colouring(), op.to_orig(plan.colour)), what
+    same(s.dinv(), dinv, what + ("dinv",))
+    for seed, special in ((1, False), (2, True)):
+        r = ref.probe_vector(g.nr, seed, special)
+        want = op.to_orig(plan.apply(op.to_dev(r), op.to_dev(dinv))[0])
+        same(s.apply(r), want, what + ("special" if special else "finite",))
+        if g.nr > 5:
+            assert np.isnan(want).any() == special
+    assert s.precond_bytes() > 40.0 * g.nr and s.apply_ms(2) > 0.0
+    # the diagonal handle's apply on the same problem: one multiply per row
+    j = hostapi.PCG(p)
+    assert j.precond() == "jacobi" and j.colours() == 0 and j.precond_bytes() == 24.0 * g.nr
+    r = ref.probe_vector(g.nr, 3, True)
+    with np.errstate(all="ignore"):
+        same(j.apply(r), r * dinv, what + ("jacobi",))
+    j.free(), s.free(), p.free(), g.free()
+    return plan
+
+
+@pytest.mark.parametrize("fmt,C,sigma", sgs_cases.KERNEL_FORMATS)
+@pytest.mark.parametrize("matrix", sgs_cases.KERNEL_SHAPES, ids=lambda m: "_".join(str(v).split("/")[-1] for v in m))
+def test_colouring_and_apply_equal_the_restatement(gpu, matrix, fmt, C, sigma, tmp):
+    plan = check(matrix, fmt, C, sigma, tmp)
+    sizes = [len(r) for r in plan.rows]
+    if matrix == ("dims", 5, 5, 5):
+        assert plan.nC == 8 and max(sizes) < 64
+        if sigma == 1:
+            assert sizes == [27, 18, 18, 12, 18, 12, 12, 8]
+    if matrix == ("dims", 17, 17, 17) and sigma == 1:
+        # several full chunks in every colour; a partial last chunk (729 = 11 * 64 + 25, 648 = 10 * 64 + 8) and none (576, 512)
+        assert sorted(sizes) == [512, 576, 576, 576, 648, 648, 648, 729]
+    if matrix == ("irregular", 12):
+        assert plan.nC > 8
+
+
+def test_sell_4_8(gpu, tmp):
+    check(("scaled", 8), "scs", 4, 8, tmp, nC=8)
+
+
+@pytest.mark.parametrize("kind,nC", [("one", 1), ("diagonal", 1), ("arrow", 2), ("zeros", 2)])
+@pytest.mark.parametrize("fmt", ["crs", "scs"])
+def test_hand_made_matrices(gpu, kind, nC, fmt, tmp):
+    plan = check(("file", sgs_cases.hand_made(kind, tmp)), fmt, 64, 1, tmp, nC=nC)
+    if kind == "arrow":
+        assert len(plan.upper(0)[0]) == 299 and len(plan.rows[0]) == 1 and len(plan.rows[1]) == 299
