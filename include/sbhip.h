@@ -577,7 +577,7 @@ void sb_pcg_update_r_launch(uint32_t n, uint32_t out[3]);
  * sb_pcg_dinv gives 1 / diag(A).  Square matrix, double precision, one rank, tree dot order; a row without a finite positive
  * diagonal is a fatal error.  The set-up downloads the matrix once and builds the sweep structure on the host. */
 sb_pcg* sb_pcg_create_sgs(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host);
-int sb_pcg_precond(const sb_pcg* s); /* 0 diagonal, 1 SGS */
+int sb_pcg_precond(const sb_pcg* s); /* 0 diagonal, 1 SGS, 2 MG (below) */
 int sb_pcg_colours(const sb_pcg* s); /* nC; 0 for a diagonal handle */
 void sb_pcg_colouring(const sb_pcg* s, uint32_t* colour_host); /* nr colours, original row order; SGS handles only */
 /* z = M^-1 r once, with the handle's preconditioner (either kind), on host vectors of nr doubles in original row order;
@@ -588,6 +588,20 @@ void sb_pcg_apply_precond(sb_pcg* s, const double* r_host, double* z_host);
 double sb_pcg_apply_precond_ms(sb_pcg* s, int reps);
 /* bytes one apply reads and writes: the sweep structure and the vector traffic (diagonal: 24 per row) */
 double sb_pcg_precond_bytes(const sb_pcg* s);
+
+/* ---- multigrid V-cycle preconditioning, HPCG's own ----
+ * z = V(0, r) on levels 0 .. nCoarse (level 0 is m): pre-smooth from zero with the SGS apply above, the residual at the coarse
+ * points only, the cycle on the next level, the correction added at the coarse points, post-smooth from that guess (forward over
+ * all colours, backward over all but the last).  Injection: f2c_host[l] holds the coarse[l]->nr distinct rows of level l that are
+ * level l + 1's points, both sides in original row numbering.  Every level: square, double precision, fewer rows than the one
+ * above, a finite positive diagonal in every row; any format, its own permutation.  The caller keeps the coarse matrices alive
+ * as it does m.  nCoarse = 0 is sb_pcg_create_sgs bit for bit.  One rank, tree dot order.  On the handle sb_pcg_colours and
+ * sb_pcg_colouring report level 0, sb_pcg_launches_per_body counts the cycle, sb_pcg_precond_bytes sums the levels. */
+sb_pcg* sb_pcg_create_mg(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int nCoarse,
+    const sb_matrix* const* coarse, const uint32_t* const* f2c_host);
+int sb_pcg_levels(const sb_pcg* s);                  /* L of an MG handle; 1 SGS; 0 diagonal */
+uint32_t sb_pcg_level_rows(const sb_pcg* s, int l);  /* n_l */
+int sb_pcg_level_colours(const sb_pcg* s, int l);    /* nC_l */
 
 /* ---- BiCGStab with a diagonal preconditioner ----------------------------------------------------------- */
 /* Right-preconditioned BiCGStab for matrices that need not be symmetric: two SpMVs per body, about ten vectors whatever the

@@ -266,6 +266,24 @@ int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, co
 /* the same with symmetric Gauss-Seidel by multicolouring in the diagonal's place (sb_pcg_create_sgs, sbhip.h); first prints
  * "Preconditioner: SGS ..., nC = <colours>" */
 int sbh_solve_pcg_sgs(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz);
+/* the same with a multigrid V-cycle around that smoother (sb_pcg_create_mg, sbhip.h) on the geometric hierarchy of
+ * a generated matrix: level l + 1 is the same generator on half the grid in every direction, in the fine matrix's format (fmt: 0
+ * CRS, 1 Sell-C-sigma with C and sigma).  levels: L, or 0 for the deepest L <= 4 the grid allows.  First prints "Preconditioner:
+ * MG ..., levels = L, nC = <colours of level 0>".  A matrix from a file, or a grid that does not allow L levels, ends the
+ * process with a message. */
+int sbh_solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+                     CG_UINT sigma, int levels);
+/* the geometric hierarchy's rule: L levels need every dimension divisible by 2^(L-1) and every coarse dimension >= 2.  want: L, or
+ * 0 for the deepest L <= 4.  Returns L, or 0 with the reason in why (cap bytes) */
+int sbh_mg_levels(int nx, int ny, int nz, int want, char* why, size_t cap);
+/* the injection map of an nx x ny x nz grid (all even): coarse point (x, y, z) of the (nx/2) x (ny/2) x (nz/2) grid is fine
+ * point (2x, 2y, 2z), both in the generator's lexicographic numbering (x fastest); f2c holds (nx/2)(ny/2)(nz/2) entries */
+void sbh_mg_f2c(int nx, int ny, int nz, CG_UINT* f2c);
+/* the L - 1 coarse levels of param's grid in the fine matrix's format, generated, converted and uploaded as the driver does the
+ * fine one: mats[l - 1] (an sb_matrix*) and maps[l - 1] are level l's device matrix and the injection map into it, l = 1 .. L - 1.
+ * Returns what sbh_mg_hierarchy_free releases (after the solver handle that uses the levels) */
+void* sbh_mg_hierarchy_build(const Parameter* param, int fmt, CG_UINT C, CG_UINT sigma, int L, const void** mats, const CG_UINT** maps);
+void sbh_mg_hierarchy_free(void* hierarchy, int fmt, int L);
 /* BiCGStab with the Jacobi right preconditioner (sb_bicgstab_*, sbhip.h) for matrices that need not be symmetric: prints what
  * solveCG prints; double precision, one rank */
 int sbh_solve_bicgstab(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz);
@@ -296,6 +314,12 @@ int solvePCG(Comm* comm, Parameter* param, Matrix* m);
  * finite positive diagonal entry ends the process with a message; the single-precision libraries export it too and end the
  * process with "PCG: double precision only". */
 int solvePCGSGS(Comm* comm, Parameter* param, Matrix* m);
+/* solvePCG with HPCG's whole preconditioner: a geometric multigrid V-cycle with that symmetric Gauss-Seidel smoother, injection
+ * and the same stencil regenerated on each coarser grid, at the deepest of up to 4 levels the grid allows.  For
+ * matrices made by "generate" or "generate7P" with param's nx, ny, nz: a matrix from a file ends the process with "needs the
+ * grid".  Prints the preconditioner, its levels and level 0's colour count, then solvePCG's lines; returns k as solveCG does.
+ * One rank, tree dot order; the single-precision libraries export it too and end the process with "PCG: double precision only". */
+int solvePCGMG(Comm* comm, Parameter* param, Matrix* m);
 /* Jacobi-preconditioned BiCGStab: the short-recurrence solver for matrices that are not symmetric; returns k as
  * solveCG does.  The single-precision libraries export it too and end the process with "BiCGStab: double precision only". */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m);

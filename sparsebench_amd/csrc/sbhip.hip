@@ -28,6 +28,7 @@
 #include "pcg.hip.h"
 #include "sgs.hip.h"
 #include "bicgstab.hip.h"
+#include "mg.hip.h"
 
 #include <algorithm>
 #include <iterator>
@@ -700,4 +701,5 @@ void sb_event_destroy(void* ev) { HIP_CHECK(hipEventDestroy((hipEvent_t)ev)); }
 #include "sbhip_cgb.inc.h"
 #include "sbhip_pcg.inc.h"
 #include "sbhip_sgs.inc.h"
+#include "sbhip_mg.inc.h"
 #include "sbhip_bicgstab.inc.h"

@@ -1,0 +1,226 @@
+// sbhip_mg.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context): HPCG's
+// preconditioner, a geometric multigrid V-cycle with the multicolour symmetric Gauss-Seidel smoother of sbhip_sgs.inc.h
+// (kernels: mg.hip.h).  The handle is an sb_pcg whose `mg` plan is set and whose `sgs` plan is level 0's smoother:
+// the loop and every other sb_pcg_* call are sbhip_pcg.inc.h's and sbhip_sgs.inc.h's; what differs is how z is made.
+// ===========================================================================
+// multigrid V-cycle
+// ===========================================================================
+struct MgLevel {
+  const sb_matrix* A = nullptr;
+  uint32_t n = 0;
+  SgsPlan* P = nullptr;   // level 0: the handle's own `sgs`
+  double* dinv = nullptr; // level 0: the handle's own
+  double *r = nullptr, *z = nullptr; // levels 1 ..: the restricted residual and the correction (level 0: the caller's)
+  // the restriction to the next level (absent on the last): Sell-64 over its rows in its device order
+  uint32_t nCoarse = 0, nRChunks = 0;
+  MgRestrict R = {};      // device arrays; R.fineRow is also the translated f2c the prolongation uses
+  double restrictBytes = 0.0;
+};
+struct MgPlan {
+  std::vector<MgLevel> lev;
+};
+
+namespace {
+// old row -> device row of a matrix (identity unless Sell-C-sigma permuted)
+std::vector<uint32_t> mg_old_to_new(const sb_matrix* m)
+{
+  std::vector<uint32_t> o2n(m->nr);
+  if (m->fmt == 1 && m->permuted) {
+    if (m->nr) sb_d2h(o2n.data(), m->oldToNew, (size_t)m->nr * sizeof(uint32_t));
+  } else {
+    for (uint32_t i = 0; i < m->nr; i++) o2n[i] = i;
+  }
+  return o2n;
+}
+
+// the restriction structure of level l from its downloaded rows h and the injection map in original numbering
+void mg_build_restrict(MgLevel& F, const sb_matrix* coarse, const HostRows& h, const uint32_t* f2c, int l)
+{
+  const uint32_t nf = F.n, ncs = coarse->nr;
+  std::vector<uint32_t> seen(nf, 0);
+  for (uint32_t c = 0; c < ncs; c++) {
+    if (f2c[c] >= nf) SB_FATAL("sb_pcg_create_mg: f2c[%d][%u] = %u is outside the %u rows of level %d", l, c, f2c[c], nf, l);
+    if (seen[f2c[c]]) SB_FATAL("sb_pcg_create_mg: f2c[%d][%u] = %u repeats entry %u: the coarse points must be distinct", l, c, f2c[c], seen[f2c[c]] - 1);
+    seen[f2c[c]] = c + 1;
+  }
+  const std::vector<uint32_t> fo2n = mg_old_to_new(F.A), co2n = mg_old_to_new(coarse);
+  F.nCoarse  = ncs;
+  F.nRChunks = (ncs + 63u) / 64u;
+  const size_t slots = (size_t)F.nRChunks * 64u;
+  std::vector<uint32_t> fineRow(slots, 0xFFFFFFFFu), rowLen(slots, 0), chunkLen(F.nRChunks, 0);
+  for (uint32_t c = 0; c < ncs; c++) fineRow[co2n[c]] = fo2n[f2c[c]];
+  auto stored = [&](size_t q) { return h.val[q] != 0.0; }; // (Sell padding is a stored +0.0 and drops out, as in sgs_build)
+  for (size_t sl = 0; sl < slots; sl++) {
+    const uint32_t f = fineRow[sl];
+    if (f == 0xFFFFFFFFu) continue;
+    uint32_t len = 0;
+    for (size_t q = h.ptr[f]; q < h.ptr[f + 1]; q++)
+      if (stored(q)) {
+        if (h.col[q] >= nf) SB_FATAL("sb_pcg_create_mg: level %d: device row %u has column %u outside the %u rows", l, f, h.col[q], nf);
+        len++;
+      }
+    rowLen[sl]         = len;
+    chunkLen[sl / 64u] = std::max(chunkLen[sl / 64u], len);
+  }
+  std::vector<unsigned long long> chunkPtr((size_t)F.nRChunks + 1, 0);
+  for (uint32_t c = 0; c < F.nRChunks; c++) chunkPtr[c + 1] = chunkPtr[c] + (unsigned long long)chunkLen[c] * 64u;
+  std::vector<uint32_t> col(chunkPtr[F.nRChunks], 0);
+  std::vector<double> val(chunkPtr[F.nRChunks], 0.0);
+  for (size_t sl = 0; sl < slots; sl++) {
+    const uint32_t f = fineRow[sl];
+    if (f == 0xFFFFFFFFu) continue;
+    size_t o = chunkPtr[sl / 64u] + (sl & 63u);
+    for (size_t q = h.ptr[f]; q < h.ptr[f + 1]; q++)
+      if (stored(q)) col[o] = h.col[q], val[o] = h.val[q], o += 64;
+  }
+  F.R.chunkPtr = sgs_to_device(chunkPtr), F.R.chunkLen = sgs_to_device(chunkLen), F.R.fineRow = sgs_to_device(fineRow);
+  F.R.rowLen = sgs_to_device(rowLen), F.R.col = sgs_to_device(col), F.R.val = sgs_to_device(val);
+  // val + col | fineRow, rowLen per slot; chunkPtr, chunkLen per chunk | per coarse row r and one gathered z in, rc out
+  F.restrictBytes = (double)chunkPtr[F.nRChunks] * 12.0 + (double)F.nRChunks * (64.0 * 8.0 + 12.0) + 24.0 * (double)ncs;
+}
+} // namespace
+
+static void mg_release(sb_pcg* s)
+{
+  MgPlan* M = s->mg;
+  if (!M) return;
+  for (size_t l = 0; l < M->lev.size(); l++) {
+    MgLevel& V = M->lev[l];
+    sb_free((void*)V.R.chunkPtr), sb_free((void*)V.R.chunkLen), sb_free((void*)V.R.fineRow), sb_free((void*)V.R.rowLen);
+    sb_free((void*)V.R.col), sb_free((void*)V.R.val);
+    if (l == 0) continue; // level 0's smoother, dinv, r and z are the handle's
+    sgs_free_plan(V.P);
+    sb_free(V.dinv), sb_free(V.r), sb_free(V.z);
+  }
+  delete M;
+  s->mg = nullptr;
+}
+
+// the forward sweep from the guess in z (both halves of the plan, t kept), then the smoother's own backward sweep
+static void mg_post_smooth(const SgsPlan* P, const double* dinv, const double* r, double* t, double* z, const int* stop)
+{
+  for (uint32_t c = 0; c < P->nC; c++)
+    hipLaunchKernelGGL(mg_sweep_guess_k, sgs_grid(P, c), dim3(256), 0, g.stream, P->chunk0[c], P->chunk0[c + 1] - P->chunk0[c],
+        (const uint32_t*)P->rowIdx, P->half[0], P->half[1], r, dinv, t, z, stop);
+  sgs_backward(P, dinv, t, z, stop);
+}
+
+// z = V(0, r): r, t and z are level 0's vectors (the solve's, or sb_pcg_apply_precond's scratch)
+static void mg_apply(const sb_pcg* s, const double* r, double* t, double* z, const int* stop)
+{
+  const MgPlan* M = s->mg;
+  const size_t L  = M->lev.size();
+  // down: pre-smooth from zero, the residual at the coarse points
+  for (size_t l = 0; l < L; l++) {
+    const MgLevel& V   = M->lev[l];
+    const double* rl   = l ? V.r : r;
+    double *tl = l ? V.P->t : t, *zl = l ? V.z : z;
+    sgs_apply(V.P, (const double*)V.dinv, rl, tl, zl, stop);
+    if (l + 1 < L && V.nRChunks)
+      hipLaunchKernelGGL(mg_restrict_residual_k, dim3((V.nRChunks + 3u) / 4u), dim3(256), 0, g.stream, V.nRChunks, V.R, rl,
+          (const double*)zl, M->lev[l + 1].r, stop);
+  }
+  // up: prolong, post-smooth from the guess
+  for (size_t l = L - 1; l-- > 0;) {
+    const MgLevel& V = M->lev[l];
+    const double* rl = l ? V.r : r;
+    double *tl = l ? V.P->t : t, *zl = l ? V.z : z;
+    if (V.nCoarse)
+      hipLaunchKernelGGL(mg_prolong_add_k, dim3(stream_grid(V.nCoarse, 256)), dim3(256), 0, g.stream, V.nCoarse, V.R.fineRow,
+          (const double*)M->lev[l + 1].z, zl, stop);
+    mg_post_smooth(V.P, (const double*)V.dinv, rl, tl, zl, stop);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// launches of one V-cycle: per level but the last two smoothing applies (2 nC - 1 each), the restriction, the prolongation; the
+// last level one apply
+static int mg_apply_launches(const sb_pcg* s)
+{
+  int n = 0;
+  const size_t L = s->mg->lev.size();
+  for (size_t l = 0; l < L; l++) {
+    const int a = 2 * (int)s->mg->lev[l].P->nC - 1;
+    n += l + 1 < L ? 2 * a + 2 : a;
+  }
+  return n;
+}
+
+// bytes one V-cycle reads and writes: per level the pre-smoothing apply as sgs_bytes counts it; per level but the
+// last the restriction structure with r and one gathered z in and rc out per coarse row, the prolongation (f2c, zc, z in, z out:
+// 28 per coarse row), and the post-smoothing: forward both halves of the sweep structure with r, dinv, one gathered z in and t, z
+// out per row, backward as the apply's
+static double mg_bytes(const sb_pcg* s)
+{
+  double b = 0.0;
+  const size_t L = s->mg->lev.size();
+  for (size_t l = 0; l < L; l++) {
+    const MgLevel& V = s->mg->lev[l];
+    b += sgs_bytes(V.P, V.n);
+    if (l + 1 == L) break;
+    b += V.restrictBytes + 28.0 * (double)V.nCoarse;
+    b += V.P->halfBytes[0] + V.P->halfBytes[1] + 40.0 * (double)V.n;                    // forward from the guess
+    b += V.P->structBytes - V.P->halfBytes[0] + 32.0 * (double)V.P->rowsBackward;       // backward
+  }
+  return b;
+}
+
+sb_pcg* sb_pcg_create_mg(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int nCoarse,
+    const sb_matrix* const* coarse, const uint32_t* const* f2c_host)
+{
+  need_init();
+  if (nCoarse < 0) SB_FATAL("sb_pcg_create_mg: nCoarse = %d: the number of coarse levels cannot be negative", nCoarse);
+  if (nCoarse > 0 && (!coarse || !f2c_host)) SB_FATAL("sb_pcg_create_mg: %d coarse levels need their matrices and injection maps", nCoarse);
+  // every level is looked at before anything is built (level 0 here for its shape alone: pcg_create would take its extra
+  // columns for another rank's and say so)
+  if (m->nr != m->nc) SB_FATAL("sb_pcg_create_mg: the matrix of level 0 is not square (%u rows, %u columns)", m->nr, m->nc);
+  for (int l = 1; l <= nCoarse; l++) {
+    const sb_matrix* c    = coarse[l - 1];
+    const sb_matrix* fine = l == 1 ? m : coarse[l - 2];
+    if (!c || !f2c_host[l - 1]) SB_FATAL("sb_pcg_create_mg: level %d has no matrix or no injection map", l);
+    if (c->prec != 2) SB_FATAL("sb_pcg_create_mg: MG: double precision only (the matrix of level %d was uploaded in single precision)", l);
+    if (c->nr != c->nc) SB_FATAL("sb_pcg_create_mg: the matrix of level %d is not square (%u rows, %u columns)", l, c->nr, c->nc);
+    if (c->nr >= fine->nr)
+      SB_FATAL("sb_pcg_create_mg: level %d has %u rows, level %d has %u: every level must be smaller than the one above it", l, c->nr,
+          l - 1, fine->nr);
+  }
+  char who[32];
+  snprintf(who, sizeof who, "MG (level %d)", 0);
+  sb_pcg* s = pcg_create(m, halo, b_host, xexact_host, nullptr, "sb_pcg_create_mg", who);
+  MgPlan* M = new MgPlan();
+  M->lev.resize((size_t)nCoarse + 1);
+  s->mg = M;
+  for (int l = 0; l <= nCoarse; l++) {
+    MgLevel& V = M->lev[l];
+    V.A = l ? coarse[l - 1] : m;
+    V.n = V.A->nr;
+    if (l) {
+      const size_t nb = (size_t)V.n * sizeof(double) + 4096;
+      V.dinv = (double*)sb_malloc(nb), V.r = (double*)sb_malloc(nb), V.z = (double*)sb_malloc(nb);
+      snprintf(who, sizeof who, "MG (level %d)", l);
+      jacobi_dinv(V.A, V.dinv, "sb_pcg_create_mg", who);
+    } else {
+      V.dinv = s->dinv;
+    }
+    HostRows h = sgs_download(V.A); // once: the restriction reads the rows whole, the smoother's plan compacts them
+    if (l < nCoarse) mg_build_restrict(V, coarse[l], h, f2c_host[l], l);
+    snprintf(who, sizeof who, "sb_pcg_create_mg: level %d", l);
+    V.P = sgs_build(V.A, std::move(h), who);
+    if (!l) s->sgs = V.P;
+  }
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  return s;
+}
+
+int sb_pcg_levels(const sb_pcg* s) { return s->mg ? (int)s->mg->lev.size() : s->sgs ? 1 : 0; }
+static const SgsPlan* mg_level_plan(const sb_pcg* s, int l, const char* fn)
+{
+  if (l < 0 || l >= sb_pcg_levels(s)) SB_FATAL("%s: level %d of a handle with %d levels", fn, l, sb_pcg_levels(s));
+  return s->mg ? s->mg->lev[l].P : s->sgs;
+}
+uint32_t sb_pcg_level_rows(const sb_pcg* s, int l)
+{
+  mg_level_plan(s, l, "sb_pcg_level_rows");
+  return s->mg ? s->mg->lev[l].n : s->nr;
+}
+int sb_pcg_level_colours(const sb_pcg* s, int l) { return (int)mg_level_plan(s, l, "sb_pcg_level_colours")->nC; }

@@ -18,10 +18,15 @@ struct sb_pcg {
   int k_next = 1;
   LoopClock clock;
   struct SgsPlan* sgs = nullptr; // symmetric Gauss-Seidel in place of the diagonal (sbhip_sgs.inc.h); dinv is 1 / diag(A)
+  struct MgPlan* mg = nullptr;   // a multigrid V-cycle around it (sbhip_mg.inc.h); `sgs` is then level 0's smoother
 };
 // (sbhip_sgs.inc.h) the r update, the sweeps and the r.z values of an SGS handle; its plan's release
 static void sgs_residual_and_z(sb_pcg* s, bool prologue);
 static void sgs_release(sb_pcg* s);
+// (sbhip_mg.inc.h) the V-cycle z = V(0, r) of an MG handle, its launches, its plan's release
+static void mg_apply(const sb_pcg* s, const double* r, double* t, double* z, const int* stop);
+static int mg_apply_launches(const sb_pcg* s);
+static void mg_release(sb_pcg* s);
 
 // the diagonal in the device's row order; bad_dev: NULL, or two uint32 (rows without a finite positive diagonal, the first of
 // them) preset to {0, 0xFFFFFFFF}
@@ -64,6 +69,28 @@ void sb_pcg_update_r_native(uint32_t n, double nalpha, const double* Ap_dev, dou
   test_block_done(S);
 }
 
+// dinv = 1 / diag(A) in the device's row order.  Rows without a finite positive diagonal are counted on the device, by
+// diag_*_k's own predicate (BiCGStab's is another one, taken on the host: the two checks stay apart), and refused
+static bool dinv_host_allowed(const char* precond);
+static void jacobi_dinv(const sb_matrix* m, double* dinv_dev, const char* fn, const char* precond)
+{
+  if (!m->nr) return;
+  double* tmp     = scratch_ws(0, m->nr);
+  uint32_t bad[2] = { 0u, 0xFFFFFFFFu };
+  uint32_t* dbad  = (uint32_t*)sb_malloc(sizeof bad);
+  sb_h2d(dbad, bad, sizeof bad);
+  launch_diagonal(m, tmp, dbad);
+  sb_d2h(bad, dbad, sizeof bad);
+  sb_free(dbad);
+  if (bad[0])
+    SB_FATAL("%s: %u of %u matrix rows have no finite positive diagonal entry (the first: device row %u): the %s "
+             "preconditioner needs one in every row%s", fn, bad[0], m->nr, bad[1], precond,
+        dinv_host_allowed(precond) ? "; pass dinv_host for another diagonal preconditioner" : "");
+  hipLaunchKernelGGL(pcg_reciprocal_k, dim3(stream_grid(m->nr, 256)), dim3(256), 0, g.stream, m->nr, (const double*)tmp, dinv_dev);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+}
+
 // fn: the entry point as messages name it; precond: "Jacobi", or "SGS" (which has no caller's diagonal to fall back on)
 static bool dinv_host_allowed(const char* precond) { return precond[0] == 'J'; }
 static sb_pcg* pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const double* dinv_host,
@@ -85,22 +112,8 @@ static sb_pcg* pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_hos
   for (double** v : vecs) *v = (double*)sb_malloc((size_t)m->nc * sizeof(double) + 4096);
   if (dinv_host) {
     upload_permuted(m, dinv_host, s->dinv);
-  } else if (m->nr) { // Jacobi: dinv = 1 / diag(A).  Rows without a finite positive diagonal are counted on the device, by
-                      // diag_*_k's own predicate (BiCGStab's is another one, taken on the host: the two checks stay apart)
-    double* tmp     = scratch_ws(0, m->nr);
-    uint32_t bad[2] = { 0u, 0xFFFFFFFFu };
-    uint32_t* dbad  = (uint32_t*)sb_malloc(sizeof bad);
-    sb_h2d(dbad, bad, sizeof bad);
-    launch_diagonal(m, tmp, dbad);
-    sb_d2h(bad, dbad, sizeof bad);
-    sb_free(dbad);
-    if (bad[0])
-      SB_FATAL("%s: %u of %u matrix rows have no finite positive diagonal entry (the first: device row %u): the %s "
-               "preconditioner needs one in every row%s", fn, bad[0], m->nr, bad[1], precond,
-          dinv_host_allowed(precond) ? "; pass dinv_host for another diagonal preconditioner" : "");
-    hipLaunchKernelGGL(pcg_reciprocal_k, dim3(stream_grid(m->nr, 256)), dim3(256), 0, g.stream, m->nr, (const double*)tmp, s->dinv);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(g.stream));
+  } else {
+    jacobi_dinv(m, s->dinv, fn, precond);
   }
   upload_permuted(m, b_host, s->b);
   if (xexact_host) {
@@ -131,6 +144,7 @@ void sb_pcg_free(sb_pcg* s)
   if (!s) return;
   HIP_CHECK(hipStreamSynchronize(g.stream));
   s->clock.destroy();
+  mg_release(s);
   sgs_release(s);
   sb_free(s->r), sb_free(s->z), sb_free(s->p), sb_free(s->Ap), sb_free(s->x), sb_free(s->b), sb_free(s->dinv), sb_free(s->xexact);
   sb_free(s->S), sb_free(s->l1pAp), sb_free(s->l1rz), sb_free(s->l1rr), sb_free(s->rr_hist), sb_free(s->rz_hist), sb_free(s->pAp_hist);
@@ -139,8 +153,13 @@ void sb_pcg_free(sb_pcg* s)
 
 // launches per loop body: p update | SpMV (+ p.Ap values) | alpha | r update (+ z, r.z and r.r values) | beta = 5 where the
 // selected SpMV kernel has a fused dot; native CRS and generic C add the dot pass: 6.  An SGS handle: the r update makes no z;
-// nC forward and nC - 1 backward launches and the r.z pass stand in between it and beta: 2 nC + 5 (+ 1)
-int sb_pcg_launches_per_body(const sb_pcg* s) { return (spmv_dot_kind(s->A) ? 5 : 6) + (s->sgs ? 2 * sb_pcg_colours(s) : 0); }
+// nC forward and nC - 1 backward launches and the r.z pass stand in between it and beta: 2 nC + 5 (+ 1).  An MG handle: the
+// V-cycle's launches in the sweeps' place: 6 (+ 1) + mg_apply_launches
+int sb_pcg_launches_per_body(const sb_pcg* s)
+{
+  if (s->mg) return (spmv_dot_kind(s->A) ? 6 : 7) + mg_apply_launches(s);
+  return (spmv_dot_kind(s->A) ? 5 : 6) + (s->sgs ? 2 * sb_pcg_colours(s) : 0);
+}
 
 template <int MODE> static void pcg_scalar_launch(sb_pcg* s)
 {

@@ -14,6 +14,7 @@ struct SgsPlan {
   double* t = nullptr;           // the forward sums
   double *ar = nullptr, *at = nullptr, *az = nullptr; // sb_pcg_apply_precond's scratch vectors (first call)
   double structBytes = 0.0;      // the sweep structure as one apply reads it
+  double halfBytes[2] = { 0.0, 0.0 }; // each half over all its chunks (a sweep from a guess reads both: sbhip_mg.inc.h)
   uint32_t rowsBackward = 0;     // rows of the colours 0 .. nC - 2
 };
 
@@ -64,12 +65,13 @@ template <class T> T* sgs_to_device(const std::vector<T>& v)
 }
 } // namespace
 
-// kept lists, symmetrised adjacency, greedy colouring in device row order, the two halves as Sell-64 per colour
-static SgsPlan* sgs_build(const sb_matrix* m)
+// kept lists, symmetrised adjacency, greedy colouring in device row order, the two halves as Sell-64 per colour; h: the
+// matrix's rows as sgs_download gives them (a caller that has downloaded them for its own use passes them on); who: the entry
+// point, and the level where there are several, as messages name them
+static SgsPlan* sgs_build(const sb_matrix* m, HostRows h, const char* who)
 {
   SgsPlan* P        = new SgsPlan();
   const uint32_t nr = m->nr;
-  HostRows h        = sgs_download(m);
   // kept entries: col != row and val != 0.0 (Sell padding is a stored +0.0 and drops out by the same rule); compacted in place
   {
     size_t o = 0;
@@ -78,7 +80,7 @@ static SgsPlan* sgs_build(const sb_matrix* m)
       h.ptr[i]       = o;
       for (size_t q = b; q < e; q++)
         if (h.col[q] != i && h.val[q] != 0.0) {
-          if (h.col[q] >= nr) SB_FATAL("sb_pcg_create_sgs: device row %u has column %u outside the %u rows", i, h.col[q], nr);
+          if (h.col[q] >= nr) SB_FATAL("%s: device row %u has column %u outside the %u rows", who, i, h.col[q], nr);
           h.col[o] = h.col[q], h.val[o] = h.val[q], o++;
         }
     }
@@ -132,7 +134,7 @@ static SgsPlan* sgs_build(const sb_matrix* m)
   for (int up = 0; up < 2; up++) {
     auto in_half = [&](uint32_t i, size_t q) {
       const uint32_t ci = P->colour[i], cj = P->colour[h.col[q]];
-      if (ci == cj) SB_FATAL("sb_pcg_create_sgs: device rows %u and %u are adjacent and share colour %u", i, h.col[q], ci);
+      if (ci == cj) SB_FATAL("%s: device rows %u and %u are adjacent and share colour %u", who, i, h.col[q], ci);
       return up ? cj > ci : cj < ci;
     };
     std::vector<uint32_t> rowLen(rowIdx.size(), 0), chunkLen(P->nChunks, 0);
@@ -161,34 +163,49 @@ static SgsPlan* sgs_build(const sb_matrix* m)
     // what one apply reads of it: the backward sweep leaves the last colour's chunks alone
     const uint32_t chunksRead = up ? (nC ? P->chunk0[nC - 1] : 0) : P->nChunks;
     P->structBytes += (double)chunkPtr[chunksRead] * 12.0 + (double)chunksRead * (64.0 * 8.0 + 12.0); // val + col | rowIdx, rowLen, chunkPtr, chunkLen
+    P->halfBytes[up] = (double)chunkPtr[P->nChunks] * 12.0 + (double)P->nChunks * (64.0 * 8.0 + 12.0);
   }
   P->t = (double*)sb_malloc((size_t)nr * sizeof(double) + 4096);
   return P;
 }
+static SgsPlan* sgs_build(const sb_matrix* m) { return sgs_build(m, sgs_download(m), "sb_pcg_create_sgs"); }
 
-static void sgs_release(sb_pcg* s)
+static void sgs_free_plan(SgsPlan* P)
 {
-  SgsPlan* P = s->sgs;
   if (!P) return;
   sb_free(P->rowIdx), sb_free(P->t), sb_free(P->ar), sb_free(P->at), sb_free(P->az);
   for (SgsHalf& H : P->half)
     sb_free((void*)H.chunkPtr), sb_free((void*)H.chunkLen), sb_free((void*)H.rowLen), sb_free((void*)H.col), sb_free((void*)H.val);
   delete P;
+}
+static void sgs_release(sb_pcg* s)
+{
+  sgs_free_plan(s->sgs);
   s->sgs = nullptr;
 }
 
 // z = M^-1 r: forward over the colours 0 .. nC-1, backward over nC-2 .. 0; one launch per colour (a wave per chunk)
+static dim3 sgs_grid(const SgsPlan* P, uint32_t c) { return dim3((P->chunk0[c + 1] - P->chunk0[c] + 3u) / 4u); }
+// the backward sweep alone: from the forward sums in t
+static void sgs_backward(const SgsPlan* P, const double* dinv, double* t, double* z, const int* stop)
+{
+  for (uint32_t c = P->nC > 1 ? P->nC - 1 : 0; c-- > 0;)
+    hipLaunchKernelGGL(sgs_sweep_k<1>, sgs_grid(P, c), dim3(256), 0, g.stream, P->chunk0[c], P->chunk0[c + 1] - P->chunk0[c],
+        (const uint32_t*)P->rowIdx, P->half[1], (const double*)t, dinv, t, z, stop);
+}
+static void sgs_apply(const SgsPlan* P, const double* dinv, const double* r, double* t, double* z, const int* stop)
+{
+  for (uint32_t c = 0; c < P->nC; c++)
+    hipLaunchKernelGGL(sgs_sweep_k<0>, sgs_grid(P, c), dim3(256), 0, g.stream, P->chunk0[c], P->chunk0[c + 1] - P->chunk0[c],
+        (const uint32_t*)P->rowIdx, P->half[0], r, dinv, t, z, stop);
+  sgs_backward(P, dinv, t, z, stop);
+  HIP_CHECK(hipGetLastError());
+}
+// the handle's preconditioner: the sweeps of its matrix, or the V-cycle around them
 static void sgs_apply(const sb_pcg* s, const double* r, double* t, double* z, const int* stop)
 {
-  const SgsPlan* P = s->sgs;
-  auto grid        = [&](uint32_t c) { return dim3((P->chunk0[c + 1] - P->chunk0[c] + 3u) / 4u); };
-  for (uint32_t c = 0; c < P->nC; c++)
-    hipLaunchKernelGGL(sgs_sweep_k<0>, grid(c), dim3(256), 0, g.stream, P->chunk0[c], P->chunk0[c + 1] - P->chunk0[c],
-        (const uint32_t*)P->rowIdx, P->half[0], r, (const double*)s->dinv, t, z, stop);
-  for (uint32_t c = P->nC > 1 ? P->nC - 1 : 0; c-- > 0;)
-    hipLaunchKernelGGL(sgs_sweep_k<1>, grid(c), dim3(256), 0, g.stream, P->chunk0[c], P->chunk0[c + 1] - P->chunk0[c],
-        (const uint32_t*)P->rowIdx, P->half[1], (const double*)t, (const double*)s->dinv, t, z, stop);
-  HIP_CHECK(hipGetLastError());
+  if (s->mg) mg_apply(s, r, t, z, stop);
+  else sgs_apply(s->sgs, (const double*)s->dinv, r, t, z, stop);
 }
 
 // the r update (PRO 1: the prologue's b - Ap) with the r.r values, the apply, the r.z values
@@ -214,7 +231,7 @@ sb_pcg* sb_pcg_create_sgs(const sb_matrix* m, sb_halo* halo, const double* b_hos
   return s;
 }
 
-int sb_pcg_precond(const sb_pcg* s) { return s->sgs ? 1 : 0; }
+int sb_pcg_precond(const sb_pcg* s) { return s->mg ? 2 : s->sgs ? 1 : 0; }
 int sb_pcg_colours(const sb_pcg* s) { return s->sgs ? (int)s->sgs->nC : 0; }
 
 void sb_pcg_colouring(const sb_pcg* s, uint32_t* colour_host)
@@ -284,9 +301,11 @@ double sb_pcg_apply_precond_ms(sb_pcg* s, int reps)
 }
 
 // bytes one apply reads and writes.  Diagonal: r, dinv in, z out.  SGS: the sweep structure, and per row forward r, dinv, one
-// gathered z in, t, z out; backward (the rows of every colour but the last) t, dinv, one gathered z in, z out
+// gathered z in, t, z out; backward (the rows of every colour but the last) t, dinv, one gathered z in, z out.  MG: mg_bytes
+static double sgs_bytes(const SgsPlan* P, uint32_t nr) { return P->structBytes + 40.0 * (double)nr + 32.0 * (double)P->rowsBackward; }
+static double mg_bytes(const sb_pcg* s);
 double sb_pcg_precond_bytes(const sb_pcg* s)
 {
   if (!s->sgs) return 24.0 * (double)s->nr;
-  return s->sgs->structBytes + 40.0 * (double)s->nr + 32.0 * (double)s->sgs->rowsBackward;
+  return s->mg ? mg_bytes(s) : sgs_bytes(s->sgs, s->nr);
 }

@@ -66,6 +66,15 @@ int solveCGBatch(Comm* comm, Parameter* param, Matrix* m, int nrhs)
 int solvePCG(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_pcg(comm, param, m->dev, m->nr, m->rowNnz); }
 /* the same with multicolour symmetric Gauss-Seidel in the diagonal's place */
 int solvePCGSGS(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_pcg_sgs(comm, param, m->dev, m->nr, m->rowNnz); }
+/* the same with the multigrid V-cycle around it, on the generated grid's own hierarchy at auto depth */
+int solvePCGMG(Comm* comm, Parameter* param, Matrix* m)
+{
+#if defined(CRS)
+  return sbh_solve_pcg_mg(comm, param, m->dev, m->nr, m->rowNnz, 0, 0, 0, 0);
+#else
+  return sbh_solve_pcg_mg(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, 0);
+#endif
+}
 /* Jacobi-preconditioned BiCGStab on this build's Matrix (the _sp libraries: "BiCGStab: double precision only") */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_bicgstab(comm, param, m->dev, m->nr, m->rowNnz); }
 

@@ -29,6 +29,8 @@ static const char* kHelp =
     "  -t <bench type>   Benchmark type, can be cg, spmv, gmres, pcg (CG with the Jacobi preconditioner),\n"
     "                    or bicgstab (BiCGStab with the Jacobi preconditioner: non-symmetric matrices). Default cg.\n"
     "  -p <jacobi|sgs>   Preconditioner of -t pcg, sgs is multicolour symmetric Gauss-Seidel. Default jacobi.\n"
+    "  -p mg      Multigrid V-cycle with the sgs smoother as the preconditioner of -t pcg (generated matrices).\n"
+    "  -l <int>   Levels of -p mg. Default the deepest of up to 4 that the grid allows.\n"
     "  -r <int>   GMRES restart length. Default 30.\n"
     "  -n <int>   Number of right-hand sides for -t cg. Default 1.\n"
     "  -x <int>   Size in x for generated matrix, ignored if MM file is loaded. Default 100.\n"
@@ -59,9 +61,10 @@ int main(int argc, char** argv)
   int type = CG, opt;
   unsigned scsC = 64, scsSigma = 1;
   int restart = 30, nrhs = 1;
-  int precond = -1; /* -p: 0 jacobi, 1 sgs; -1 not given */
+  int precond = -1; /* -p: 0 jacobi, 1 sgs, 2 mg; -1 not given */
+  int levels  = 0;  /* -l: levels of -p mg; 0 not given (the deepest of up to 4) */
   opterr = 0;
-  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:p:")) != -1) switch (opt) {
+  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:p:l:")) != -1) switch (opt) {
     case 'h':
       if (commIsMaster(&comm)) printf("%s", kHelp);
       commAbort(&comm, "");
@@ -101,8 +104,16 @@ int main(int argc, char** argv)
     case 'p':
       if (strcmp(optarg, "jacobi") == 0) precond = 0;
       else if (strcmp(optarg, "sgs") == 0) precond = 1;
+      else if (strcmp(optarg, "mg") == 0) precond = 2;
       else {
         fprintf(stderr, "Unknown preconditioner %s (-p <jacobi|sgs>)\n", optarg);
+        return 1;
+      }
+      break;
+    case 'l':
+      levels = atoi(optarg);
+      if (levels < 1) {
+        fprintf(stderr, "-l <int> (the levels of -p mg) must be 1 or more, got %s\n", optarg);
         return 1;
       }
       break;
@@ -119,6 +130,21 @@ int main(int argc, char** argv)
   if (precond != -1 && type != PCG) {
     fprintf(stderr, "-p <jacobi|sgs> (the preconditioner) goes with -t pcg only\n");
     return 1;
+  }
+  if (levels != 0 && precond != 2) {
+    fprintf(stderr, "-l <int> (the levels) goes with -p mg only\n");
+    return 1;
+  }
+  if (precond == 2) { /* refused before the set-up: a file has no grid, a grid may not allow the levels */
+    char why[256];
+    if (strcmp(param.filename, "generate") != 0 && strcmp(param.filename, "generate7P") != 0) {
+      fprintf(stderr, "-p mg needs the grid: its hierarchy is the generated matrix's on coarser grids, not -m %s\n", param.filename);
+      return 1;
+    }
+    if (!sbh_mg_levels(param.nx, param.ny, param.nz, levels, why, sizeof why)) {
+      fprintf(stderr, "%s\n", why);
+      return 1;
+    }
   }
 
   commPrintBanner(&comm);
@@ -158,6 +184,14 @@ int main(int argc, char** argv)
     if (commIsMaster(&comm)) printf("Test type: PCG\n");
     if (precond == 1) {
       k = solvePCGSGS(&comm, &param, &sm); /* (prints "Preconditioner: SGS ..., nC = <colours>" itself: it knows them) */
+    } else if (precond == 2 && levels == 0) {
+      k = solvePCGMG(&comm, &param, &sm); /* (prints "Preconditioner: MG ..., levels = L, nC = <colours>" itself) */
+    } else if (precond == 2) {
+#ifdef SCS
+      k = sbh_solve_pcg_mg(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, levels);
+#else
+      k = sbh_solve_pcg_mg(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels);
+#endif
     } else {
       if (commIsMaster(&comm)) printf("Preconditioner: Jacobi (diagonal), nC = 0\n");
       k = solvePCG(&comm, &param, &sm);

@@ -1,0 +1,107 @@
+/* sbh_mg.c -- the geometric hierarchy of a generated matrix for the multigrid preconditioner of PCG: how deep the
+ * grid lets it go, the injection maps, and the coarse levels themselves: the stencil regenerated on each coarser grid through
+ * the same calls the driver makes for the fine one (generate -> commPartition -> convert).  solvePCGMG's body (sbh_solver.c)
+ * hands them to sb_pcg_create_mg.  Nothing is computed here.
+ */
+#define _GNU_SOURCE
+#include <stdlib.h>
+
+#include "sbhip.h"
+#include "sparsebench/sparsebench.h"
+
+#define MG_AUTO_DEPTH 4 /* HPCG's */
+
+static int divisible(int n, int by) { return n > 0 && n % by == 0; }
+
+int sbh_mg_levels(int nx, int ny, int nz, int want, char* why, size_t cap)
+{
+  if (why && cap) why[0] = '\0';
+  if (want < 0) {
+    if (why) snprintf(why, cap, "MG: %d levels asked for (1 or more, or 0 for the deepest of up to %d)", want, MG_AUTO_DEPTH);
+    return 0;
+  }
+  if (nx < 1 || ny < 1 || nz < 1) {
+    if (why) snprintf(why, cap, "MG: the grid %d x %d x %d has an empty dimension", nx, ny, nz);
+    return 0;
+  }
+  const int top = want ? want : MG_AUTO_DEPTH;
+  for (int L = top; L >= 1; L--) {
+    const int f = L < 31 ? 1 << (L - 1) : 0;
+    const int div = f && divisible(nx, f) && divisible(ny, f) && divisible(nz, f);
+    const int big = L == 1 || (div && nx / f >= 2 && ny / f >= 2 && nz / f >= 2);
+    if (div && big) return L;
+    if (want) {
+      if (!why) return 0;
+      if (!f) snprintf(why, cap, "MG: %d levels are more than any grid allows", L);
+      else if (!div) snprintf(why, cap, "MG: %d levels need every dimension divisible by %d (the grid is %d x %d x %d)", L, f, nx, ny, nz);
+      else
+        snprintf(why, cap, "MG: %d levels would give a coarse dimension smaller than 2 (the grid is %d x %d x %d, the coarsest %d x %d x %d)",
+            L, nx, ny, nz, nx / f, ny / f, nz / f);
+      return 0;
+    }
+  }
+  return 1;
+}
+
+void sbh_mg_f2c(int nx, int ny, int nz, CG_UINT* f2c)
+{
+  const int cx = nx / 2, cy = ny / 2, cz = nz / 2;
+  for (int z = 0; z < cz; z++)
+    for (int y = 0; y < cy; y++)
+      for (int x = 0; x < cx; x++)
+        f2c[((size_t)z * cy + y) * cx + x] = (CG_UINT)(((size_t)(2 * z) * ny + 2 * y) * nx + 2 * x);
+}
+
+/* one coarse level: the generator's matrix on its grid, converted and uploaded as the fine one was */
+typedef struct {
+  GMatrix gm;
+  CRSMatrix crs;
+  SCSMatrix scs;
+  void* dev;
+  CG_UINT* f2c; /* from the level above */
+} mg_level;
+
+static void level_free(mg_level* v, int fmt)
+{
+  if (v->dev) sb_matrix_free((sb_matrix*)v->dev);
+  free(v->gm.rowPtr), free(v->gm.entries), free(v->f2c);
+  if (fmt == 0) free(v->crs.rowPtr), free(v->crs.colInd), free(v->crs.val), free(v->crs.rowNnz);
+  else
+    free(v->scs.chunkPtr), free(v->scs.chunkLens), free(v->scs.colInd), free(v->scs.val), free(v->scs.oldToNewPerm),
+        free(v->scs.newToOldPerm), free(v->scs.rowNnz);
+}
+
+/* the coarse levels (sparsebench.h) */
+void* sbh_mg_hierarchy_build(const Parameter* param, int fmt, CG_UINT C, CG_UINT sigma, int L, const void** mats, const CG_UINT** maps)
+{
+  mg_level* lev = (mg_level*)calloc((size_t)L + 1, sizeof *lev);
+  Parameter pc  = *param;
+  for (int l = 1; l < L; l++) {
+    mg_level* v = &lev[l];
+    v->f2c      = (CG_UINT*)malloc(((size_t)(pc.nx / 2) * (pc.ny / 2) * (pc.nz / 2) + 1) * sizeof(CG_UINT));
+    sbh_mg_f2c(pc.nx, pc.ny, pc.nz, v->f2c);
+    pc.nx /= 2, pc.ny /= 2, pc.nz /= 2;
+    Comm cc;
+    memset(&cc, 0, sizeof cc);
+    cc.size = 1;
+    sbh_init_matrix(&cc, &pc, &v->gm);
+    commPartition(&cc, &v->gm);
+    if (fmt == 0) {
+      sbh_convert_crs(&v->crs, &v->gm);
+      v->dev = v->crs.dev;
+    } else {
+      v->scs.C = C, v->scs.sigma = sigma;
+      sbh_convert_scs(&v->scs, &v->gm);
+      v->dev = v->scs.dev;
+    }
+    mats[l - 1] = v->dev, maps[l - 1] = v->f2c;
+  }
+  return lev;
+}
+
+void sbh_mg_hierarchy_free(void* hierarchy, int fmt, int L)
+{
+  mg_level* lev = (mg_level*)hierarchy;
+  for (int l = 1; l < L; l++) level_free(&lev[l], fmt);
+  free(lev);
+}

@@ -294,15 +294,10 @@ int sbh_solve_cg_batch(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT n
 /* solveCG with the Jacobi preconditioner (sb_pcg_*), or with symmetric Gauss-Seidel by multicolouring in its place
  * (sgs).  The lines solveCG prints while iterating are printed afterwards from the recorded r.r history, indexed as
  * solveCG's own; the SGS solve names its preconditioner and colour count first. */
-static int solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int sgs)
+/* solves with the handle, prints, releases it and the vectors */
+static int run_pcg(Comm* comm, Parameter* param, sb_pcg* s, double* b, double* xexact)
 {
-  dp_only("PCG: double precision only\n");
   const int itermax = param->itermax, cap = itermax + 2;
-  double *b, *xexact;
-  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
-  sb_pcg* s = sgs ? sb_pcg_create_sgs((const sb_matrix*)dev_matrix, NULL, b, xexact)
-                  : sb_pcg_create((const sb_matrix*)dev_matrix, NULL, b, xexact, NULL);
-  if (sgs && commIsMaster(comm)) printf("Preconditioner: SGS (multicolour symmetric Gauss-Seidel), nC = %d\n", sb_pcg_colours(s));
   const int k   = sb_pcg_solve(s, itermax, param->eps);
   double* rr    = (double*)malloc((size_t)cap * sizeof(double));
   double* rz    = (double*)malloc((size_t)cap * sizeof(double));
@@ -315,6 +310,16 @@ static int solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
   free(rr), free(rz), free(pAp), free(b), free(xexact);
   return k;
 }
+static int solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int sgs)
+{
+  dp_only("PCG: double precision only\n");
+  double *b, *xexact;
+  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
+  sb_pcg* s = sgs ? sb_pcg_create_sgs((const sb_matrix*)dev_matrix, NULL, b, xexact)
+                  : sb_pcg_create((const sb_matrix*)dev_matrix, NULL, b, xexact, NULL);
+  if (sgs && commIsMaster(comm)) printf("Preconditioner: SGS (multicolour symmetric Gauss-Seidel), nC = %d\n", sb_pcg_colours(s));
+  return run_pcg(comm, param, s, b, xexact);
+}
 int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
 {
   return solve_pcg(comm, param, dev_matrix, nr, rowNnz, 0);
@@ -322,6 +327,40 @@ int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, co
 int sbh_solve_pcg_sgs(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
 {
   return solve_pcg(comm, param, dev_matrix, nr, rowNnz, 1);
+}
+
+/* ---- solvePCGMG --------------------------------------------------------------------------- */
+/* solvePCGSGS with the multigrid V-cycle around the smoother on the generated grid's own hierarchy (sbh_mg.c).
+ * levels: L, or 0 for the deepest of up to 4 the grid allows. */
+static void mg_refuse(const char* msg)
+{
+  fprintf(stderr, "%s\n", msg);
+  exit(EXIT_FAILURE);
+}
+
+int sbh_solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int levels)
+{
+  dp_only("PCG: double precision only\n");
+  if (strcmp(param->filename, "generate") != 0 && strcmp(param->filename, "generate7P") != 0)
+    mg_refuse("MG: needs the grid: the hierarchy is the generator's on coarser grids, and the matrix was read from a file "
+              "(sb_pcg_create_mg takes a caller's own hierarchy)");
+  if (comm->size > 1) mg_refuse("MG: runs on one rank");
+  char why[256];
+  const int L = sbh_mg_levels(param->nx, param->ny, param->nz, levels, why, sizeof why);
+  if (!L) mg_refuse(why);
+  const void** mats    = (const void**)calloc((size_t)L, sizeof *mats);
+  const CG_UINT** maps = (const CG_UINT**)calloc((size_t)L, sizeof *maps);
+  void* hierarchy      = sbh_mg_hierarchy_build(param, fmt, C, sigma, L, mats, maps);
+  double *b, *xexact;
+  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
+  sb_pcg* s = sb_pcg_create_mg((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats, maps);
+  if (commIsMaster(comm))
+    printf("Preconditioner: MG (V-cycle, multicolour SGS smoother), levels = %d, nC = %d\n", sb_pcg_levels(s), sb_pcg_colours(s));
+  const int k = run_pcg(comm, param, s, b, xexact);
+  sbh_mg_hierarchy_free(hierarchy, fmt, L);
+  free(mats), free(maps);
+  return k;
 }
 
 /* ---- solveBiCGStab ----------------------------------------------------------------------- */

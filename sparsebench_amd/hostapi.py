@@ -68,6 +68,10 @@ def host(precision="double"):
     H.MMMatrixRead.argtypes = [vp, C.c_char_p]
     H.commDistributeMatrix.argtypes = [vp, vp, vp]
     H.sbh_exchange_rccl.restype = vp
+    H.sbh_mg_levels.restype = C.c_int
+    H.sbh_mg_levels.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+    H.sbh_mg_f2c.restype = None
+    H.sbh_mg_f2c.argtypes = [C.c_int, C.c_int, C.c_int, vp]
     if precision == "single":
         _host_sp = H
     else:
@@ -82,6 +86,28 @@ _ARRAYS = {"rowPtr": 0, "rowNnz": 1, "crs_colInd": 2, "chunkPtr": 3, "chunkLens"
            "scs_colInd": 5, "oldToNewPerm": 6, "newToOldPerm": 7, "elementsToSend": 8,
            "sources": 9, "recvCounts": 10, "rdispls": 11, "destinations": 12, "sendCounts": 13,
            "sdispls": 14, "externalGlobal": 15}
+
+
+def mg_levels(nx, ny, nz, levels=None):
+    """L of the geometric hierarchy of an nx x ny x nz grid (sbh_mg_levels): `levels`, or None for the deepest of up to 4 the
+    grid allows.  L levels need every dimension divisible by 2^(L-1) and every coarse dimension >= 2: ValueError otherwise."""
+    why = C.create_string_buffer(256)
+    L = host().sbh_mg_levels(int(nx), int(ny), int(nz), 0 if levels is None else int(levels), why, 256)
+    if levels is not None and int(levels) < 1:
+        raise ValueError("MG: levels must be 1 or more, got %r" % (levels,))
+    if not L:
+        raise ValueError(why.value.decode())
+    return L
+
+
+def mg_f2c(nx, ny, nz):
+    """the injection map of an nx x ny x nz grid (all even) onto the grid of half the size in every direction (sbh_mg_f2c):
+    coarse point (x, y, z) is fine point (2x, 2y, 2z), both in the generator's numbering"""
+    if nx % 2 or ny % 2 or nz % 2:
+        raise ValueError("MG: the grid %d x %d x %d has an odd dimension" % (nx, ny, nz))
+    out = np.empty((nx // 2) * (ny // 2) * (nz // 2), dtype=np.uint32)
+    host().sbh_mg_f2c(int(nx), int(ny), int(nz), out.ctypes.data_as(vp))
+    return out
 
 
 def convert_mtx_to_bmx(path):
@@ -132,6 +158,8 @@ class Problem:
         self.fdtype = np.float32 if precision == "single" else np.float64
         self.fmt = fmt
         self.upload = upload
+        # what a geometric hierarchy is regenerated from (PCG(precond="mg", levels=...))
+        self.filename, self.dims, self.Cc, self.sigma_arg = os.fsdecode(filename), (int(nx), int(ny), int(nz)), Cc, sigma
         L = capi.load()
         old = L.sb_sp_mirror() if mirror is not None else None
         if mirror is not None:
@@ -544,26 +572,92 @@ class PCG(_BodySolver):
     """solveCG with a diagonal preconditioner put back (sb_pcg_*): z = r * dinv, alpha = r.z / p.Ap,
     beta = r.z / (r.z)_old, the loop test on sqrt(r.r).  dinv None: Jacobi, 1 / diag(A); else nr finite positive doubles in
     original row order (all 1.0: `CG` in the tree order bit for bit).  precond "sgs": symmetric Gauss-Seidel by multicolouring
-    in place of the diagonal (takes no dinv).  Double precision, one rank, tree dot order."""
+    in place of the diagonal (takes no dinv).  precond "mg": a multigrid V-cycle with that smoother:
+    `levels` for a generated problem's own geometric hierarchy (None: the deepest of up to 4 the grid allows), or
+    `coarse=[(Problem, f2c), ...]` for the caller's.  Double precision, one rank, tree dot order."""
 
     PREFIX, NAME = "sb_pcg", "PCG"
     COUNTERS = ("stop", "stop_next", "iters", "n_rr", "n_pAp")
 
-    def __init__(self, problem, dinv=None, precond="jacobi"):
+    def __init__(self, problem, dinv=None, precond="jacobi", levels=None, coarse=None):
         self._need_double(problem)
-        if precond not in ("jacobi", "sgs"):
-            raise ValueError("precond must be 'jacobi' or 'sgs', got %r" % (precond,))
-        if precond == "sgs" and dinv is not None:
-            raise ValueError("precond='sgs' takes no dinv: its diagonal is the matrix's own")
+        if precond not in ("jacobi", "sgs", "mg"):
+            raise ValueError("precond must be 'jacobi' or 'sgs' or 'mg', got %r" % (precond,))
+        if precond in ("sgs", "mg") and dinv is not None:
+            raise ValueError("precond=%r takes no dinv: its diagonal is the matrix's own" % (precond,))
+        if precond != "mg" and (levels is not None or coarse is not None):
+            raise ValueError("levels and coarse go with precond='mg' only")
+        if levels is not None and coarse is not None:
+            raise ValueError("precond='mg' takes levels (a generated problem's own hierarchy) or coarse (the caller's), not both")
+        self._owned = []  # the coarse problems this handle generated itself
+        self._keep = None
+        if precond == "mg":
+            try:
+                self._create_mg(problem, levels, coarse)
+            except Exception:
+                self._free_owned()  # the coarse problems generated so far
+                raise
+            return
         b, xe = self._open(problem)
         if precond == "sgs":
             self.ptr = self.L.sb_pcg_create_sgs(problem.matrix, problem.halo, _ptr(b), _ptr(xe))
         else:
             self.ptr = self.L.sb_pcg_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), _ptr(self._dinv_arg(dinv)))
 
+    def _create_mg(self, problem, levels, coarse):
+        """coarse: [(Problem, f2c), ...], level l + 1's problem and the rows of level l that are its points (original numbering);
+        else the geometric hierarchy of a generated problem at `levels` (None: the deepest of up to 4)"""
+        if coarse is None:
+            name = getattr(problem, "filename", None)
+            if name not in ("generate", "generate7P"):
+                raise ValueError("precond='mg' needs the grid: %r is not a generated problem (pass coarse=[(Problem, f2c), ...])" % (name,))
+            if problem.nr != problem.totalNr:
+                raise ValueError("precond='mg' runs on one rank")
+            dims = problem.dims
+            nlev = mg_levels(*dims, levels=levels)
+            coarse = []
+            for _ in range(nlev - 1):
+                f2c = mg_f2c(*dims)
+                dims = tuple(d // 2 for d in dims)
+                q = Problem(name, *dims, fmt=problem.fmt, Cc=problem.Cc, sigma=problem.sigma_arg)
+                self._owned.append(q)
+                coarse.append((q, f2c))
+        maps = []
+        for q, f2c in coarse:
+            self._need_double(q)
+            f2c = np.ascontiguousarray(f2c, dtype=np.uint32)
+            if f2c.shape != (q.nr,):
+                raise ValueError("f2c must hold the coarse problem's nr = %d rows, got shape %r" % (q.nr, f2c.shape))
+            maps.append(f2c)
+        b, xe = self._open(problem)
+        n = len(coarse)
+        mats = (vp * max(n, 1))(*[q.matrix for q, _ in coarse])
+        ptrs = (vp * max(n, 1))(*[m.ctypes.data for m in maps])
+        self._keep = (coarse, maps)  # the caller's coarse problems must outlive the handle, as the fine one must
+        self.ptr = self.L.sb_pcg_create_mg(problem.matrix, problem.halo, _ptr(b), _ptr(xe), n, mats, ptrs)
+
+    def _free_owned(self):
+        for q in self._owned:
+            q.free()
+        self._owned = []
+
+    def free(self):
+        _BodySolver.free(self)
+        self._free_owned()
+
     def precond(self):
-        """"jacobi" (any diagonal) or "sgs" """
-        return ("jacobi", "sgs")[self.L.sb_pcg_precond(self.ptr)]
+        """"jacobi" (any diagonal), "sgs" or "mg" """
+        return ("jacobi", "sgs", "mg")[self.L.sb_pcg_precond(self.ptr)]
+
+    def levels(self):
+        """L of an MG handle; 1 for SGS, 0 for a diagonal one"""
+        return self.L.sb_pcg_levels(self.ptr)
+
+    def level_rows(self, l):
+        return self.L.sb_pcg_level_rows(self.ptr, int(l))
+
+    def level_colours(self, l):
+        return self.L.sb_pcg_level_colours(self.ptr, int(l))
 
     def colours(self):
         """nC of an SGS handle; 0 for a diagonal one"""

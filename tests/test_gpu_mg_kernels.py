@@ -1,0 +1,113 @@
+"""The MG preconditioner on the GPU without a solve: one V-cycle through sb_pcg_apply_precond == the CPU
+restatement (tests/mg_ref.py, pinned by tests/test_mg_host.py) BIT FOR BIT, NaN equal to NaN: a coarse level of 8 rows (one
+partial chunk of the restriction), three and four levels, coarse grids with odd dimensions, colours that end in partial chunks,
+every format, a caller's hierarchy on hand-made files (65 coarse rows: a full chunk plus one lane), right-hand sides with +0.0,
+-0.0, a denormal, an inf and a NaN.  One level is the SGS handle's apply; the levels' rows, colours and the launches per body are
+the restatement's."""
+import numpy as np
+import pytest
+
+import mg_cases
+import mg_ref as ref
+from sparsebench_amd import hostapi
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def tmp(tmp_path_factory):
+    return tmp_path_factory.mktemp("mg_kernels")
+
+
+def same(got, want, what):
+    a, b = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(want, dtype=np.float64)
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    na, nb = np.isnan(a), np.isnan(b)
+    assert np.array_equal(na, nb), (what, "NaN positions differ", np.nonzero(na != nb)[0][:5])
+    bad = np.nonzero((a.view(np.uint64) != b.view(np.uint64)) & ~na)[0]
+    assert bad.size == 0, (what, "first difference at", int(bad[0]), a[bad[0]], b[bad[0]], "of", bad.size)
+
+
+def fused_dot(p, fmt, C):
+    return (fmt == "scs" and C == 64) or p.use_packed(5) == 5
+
+
+def check_handle(s, p, hier, fmt, C, what):
+    """levels, rows, colours, launches and two applies of the handle against the restatement"""
+    op = hier.lev[0].op
+    assert s.precond() == "mg" and s.levels() == hier.L, (what, s.levels(), hier.L)
+    assert [s.level_rows(l) for l in range(hier.L)] == [V.n for V in hier.lev], what
+    assert [s.level_colours(l) for l in range(hier.L)] == [V.plan.nC for V in hier.lev], what
+    assert s.colours() == hier.nC and np.array_equal(s.colouring(), op.to_orig(hier.lev[0].plan.colour)), what
+    apply_launches = sum(2 * (2 * V.plan.nC - 1) + 2 for V in hier.lev[:-1]) + 2 * hier.lev[-1].plan.nC - 1
+    assert hier.launches() == apply_launches
+    assert s.launches_per_body() == 6 + apply_launches + (0 if fused_dot(p, fmt, C) else 1), what
+    for seed, special in ((1, False), (2, True)):
+        r = ref.probe_vector(hier.n, seed, special)
+        want = op.to_orig(hier.apply(op.to_dev(r))[0])
+        same(s.apply(r), want, what + ("special" if special else "finite",))
+        if hier.n > 5:
+            assert np.isnan(want).any() == special
+    assert s.precond_bytes() > 2 * 40.0 * hier.n and s.apply_ms(2) > 0.0
+
+
+def check(matrix, levels, fmt, C, sigma, tmp):
+    c = dict(matrix=matrix, fmt=fmt, C=C, sigma=sigma, levels=levels)
+    hier, f2cs = ref.build_hierarchy(c, tmp)
+    assert hier.L == levels
+    p = hostapi.Problem(*ref.problem_args(matrix, tmp), fmt=fmt, Cc=C, sigma=sigma)
+    if sigma > 1:  # the restatement walks the device's own permutation
+        op = hier.lev[0].op
+        assert np.array_equal(p.array("oldToNewPerm"), op.o2n if op.o2n is not None else np.arange(p.nr))
+    s = hostapi.PCG(p, precond="mg", levels=levels)
+    check_handle(s, p, hier, fmt, C, (matrix, levels, fmt, C, sigma))
+    s.free(), p.free(), hier.free()
+    return hier
+
+
+@pytest.mark.parametrize("fmt,C,sigma", mg_cases.KERNEL_FORMATS)
+@pytest.mark.parametrize("matrix,levels", mg_cases.KERNEL_SHAPES, ids=lambda m: "_".join(str(v) for v in m) if isinstance(m, tuple) else "L%d" % m)
+def test_one_cycle_equals_the_restatement(gpu, matrix, levels, fmt, C, sigma, tmp):
+    hier = check(matrix, levels, fmt, C, sigma, tmp)
+    rows = [V.n for V in hier.lev]
+    if matrix == ("dims", 4, 4, 4):
+        assert rows == [64, 8]
+    if matrix == ("dims", 16, 16, 16):
+        assert rows == [4096, 512, 64, 8]
+    if matrix == ("dims", 12, 8, 20) and sigma == 1:
+        assert rows == [1920, 240, 30]
+    if matrix == ("dims", 34, 6, 10) and sigma == 1:
+        assert all(len(r) % 64 for r in hier.lev[0].plan.rows)  # every colour ends in a partial chunk
+
+
+def test_sell_4_8(gpu, tmp):
+    matrix, levels = mg_cases.SELL_4_8_SHAPE
+    check(matrix, levels, "scs", 4, 8, tmp)
+
+
+@pytest.mark.parametrize("fmt,sigma", [("crs", 1), ("scs", 1), ("scs", 256)])
+def test_a_callers_hierarchy_on_hand_made_files(gpu, fmt, sigma, tmp):
+    fine, coarse, f2c = mg_cases.hand_made(tmp)
+    c = dict(matrix=("file", fine), fmt=fmt, C=64, sigma=sigma, coarse=[(("file", coarse), f2c)])
+    hier, f2cs = ref.build_hierarchy(c, tmp)
+    assert [V.n for V in hier.lev] == [130, 65]
+    p = hostapi.Problem(fine, 1, 1, 1, fmt=fmt, Cc=64, sigma=sigma)
+    q = hostapi.Problem(coarse, 1, 1, 1, fmt=fmt, Cc=64, sigma=sigma)
+    s = hostapi.PCG(p, precond="mg", coarse=[(q, f2c)])
+    check_handle(s, p, hier, fmt, 64, ("hand made", fmt, sigma))
+    s.free(), q.free(), p.free(), hier.free()
+
+
+@pytest.mark.parametrize("fmt,C,sigma", mg_cases.KERNEL_FORMATS)
+def test_one_level_is_the_sgs_handle(gpu, fmt, C, sigma):
+    p = hostapi.Problem("generate", 10, 11, 13, fmt=fmt, Cc=C, sigma=sigma)
+    s, m, j = hostapi.PCG(p, precond="sgs"), hostapi.PCG(p, precond="mg", levels=1), hostapi.PCG(p)
+    assert m.precond() == "mg" and m.levels() == 1 and s.levels() == 1 and j.levels() == 0
+    assert m.level_rows(0) == p.nr and m.level_colours(0) == s.colours() == m.colours()
+    assert m.launches_per_body() == s.launches_per_body() and m.precond_bytes() == s.precond_bytes()
+    assert np.array_equal(m.colouring(), s.colouring())
+    for seed, special in ((1, False), (2, True)):
+        r = ref.probe_vector(p.nr, seed, special)
+        same(m.apply(r), s.apply(r), (fmt, C, sigma, special))
+    same(m.dinv(), s.dinv(), "dinv")
+    m.free(), s.free(), j.free(), p.free()

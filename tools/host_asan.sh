@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."
 mkdir -p /tmp/sb_asan
 ( cd sparsebench_amd/host && gcc -O1 -g -std=gnu11 -fPIC -Wall -Wextra -Wno-unused-parameter -fopenmp -fsanitize=address,undefined \
     -fno-omit-frame-pointer -I../../include -shared -o /tmp/sb_asan/libsparsebench_host.so sbh_base.c sbh_setup.c sbh_comm.c \
-    sbh_convert.c sbh_solver.c sbh_flat.c sbh_binfile.c sbh_irregular.c -L../lib -lsbhip -Wl,-rpath,"$PWD/../lib" -lm )
+    sbh_convert.c sbh_solver.c sbh_flat.c sbh_binfile.c sbh_irregular.c sbh_mg.c -L../lib -lsbhip -Wl,-rpath,"$PWD/../lib" -lm )
 cp sparsebench_amd/lib/libsparsebench_host.so /tmp/sb_asan/host_orig.so
 trap 'cp /tmp/sb_asan/host_orig.so sparsebench_amd/lib/libsparsebench_host.so' EXIT
 cp /tmp/sb_asan/libsparsebench_host.so sparsebench_amd/lib/libsparsebench_host.so
