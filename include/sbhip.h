@@ -577,7 +577,7 @@ void sb_pcg_update_r_launch(uint32_t n, uint32_t out[3]);
  * sb_pcg_dinv gives 1 / diag(A).  Square matrix, double precision, one rank, tree dot order; a row without a finite positive
  * diagonal is a fatal error.  The set-up downloads the matrix once and builds the sweep structure on the host. */
 sb_pcg* sb_pcg_create_sgs(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host);
-int sb_pcg_precond(const sb_pcg* s); /* 0 diagonal, 1 SGS, 2 MG (below) */
+int sb_pcg_precond(const sb_pcg* s); /* 0 diagonal, 1 SGS, 2 MG, 3 MG with full-weighting transfers (below) */
 int sb_pcg_colours(const sb_pcg* s); /* nC; 0 for a diagonal handle */
 void sb_pcg_colouring(const sb_pcg* s, uint32_t* colour_host); /* nr colours, original row order; SGS handles only */
 /* z = M^-1 r once, with the handle's preconditioner (either kind), on host vectors of nr doubles in original row order;
@@ -602,6 +602,24 @@ sb_pcg* sb_pcg_create_mg(const sb_matrix* m, sb_halo* halo, const double* b_host
 int sb_pcg_levels(const sb_pcg* s);                  /* L of an MG handle; 1 SGS; 0 diagonal */
 uint32_t sb_pcg_level_rows(const sb_pcg* s, int l);  /* n_l */
 int sb_pcg_level_colours(const sb_pcg* s, int l);    /* nC_l */
+
+/* ---- the V-cycle with full-weighting transfers ----
+ * sb_pcg_create_mg with a prolongation per level in the injection map's place: P_l = (p_ptr[l], p_col[l], p_val[l]) is CSR with
+ * n_l rows and columns < n_{l+1}, original row numbering on both sides, 64-bit row pointers.  Between the two smoothings of level
+ * l the cycle takes the FULL residual d = r - A z (one launch over all colours), restricts rc = omega[l] * (P_l^T d) -- a coarse
+ * row's terms in ascending original fine row number -- and prolongs z = z + P_l zc, a row's terms in storage order; rows of P
+ * without an entry are left alone and a stored weight of 0.0 is dropped.  Refused before anything is built, each naming the
+ * level: what sb_pcg_create_mg refuses, a column out of range, a row pointer that falls, a weight that is not finite, an omega
+ * that is not finite and positive.  nCoarse = 0 is sb_pcg_create_sgs bit for bit.  sb_pcg_precond gives 3; the level queries,
+ * sb_pcg_launches_per_body (one more launch per level but the last) and sb_pcg_precond_bytes count this cycle. */
+sb_pcg* sb_pcg_create_mg_p(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int nCoarse,
+    const sb_matrix* const* coarse, const uint64_t* const* p_ptr, const uint32_t* const* p_col, const double* const* p_val,
+    const double* omega);
+/* test entry, blocking, on scratch vectors; refused between sb_pcg_start and sb_pcg_finish.  The transfers of level l alone
+ * (l + 1 < levels): d_out = r - A_l z and rc_out = omega_l P_l^T d_out from (r, z), z_out = z + P_l zc.  r, z, d_out, z_out: n_l
+ * doubles in level l's original row order; zc, rc_out: n_{l+1} doubles in level l + 1's */
+void sb_pcg_mg_fw_probe(sb_pcg* s, int l, const double* r_host, const double* z_host, const double* zc_host, double* d_out,
+    double* rc_out, double* z_out);
 
 /* ---- BiCGStab with a diagonal preconditioner ----------------------------------------------------------- */
 /* Right-preconditioned BiCGStab for matrices that need not be symmetric: two SpMVs per body, about ten vectors whatever the

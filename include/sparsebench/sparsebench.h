@@ -20,6 +20,7 @@
 #define SPARSEBENCH_H
 #include <stdbool.h>
 #include <stddef.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -273,12 +274,23 @@ int sbh_solve_pcg_sgs(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr
  * process with a message. */
 int sbh_solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
                      CG_UINT sigma, int levels);
+/* sbh_solve_pcg_mg with full-weighting transfers in the injection's place (sb_pcg_create_mg_p, sbhip.h): the
+ * trilinear prolongation of sbh_mg_trilinear and omega = 0.5 between every two levels; the same depth rules and refusals.  First
+ * prints "Preconditioner: MG (V-cycle, full-weighting transfers, multicolour SGS smoother), levels = L, nC = <colours>" */
+int sbh_solve_pcg_mgfw(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+                       CG_UINT sigma, int levels);
 /* the geometric hierarchy's rule: L levels need every dimension divisible by 2^(L-1) and every coarse dimension >= 2.  want: L, or
  * 0 for the deepest L <= 4.  Returns L, or 0 with the reason in why (cap bytes) */
 int sbh_mg_levels(int nx, int ny, int nz, int want, char* why, size_t cap);
 /* the injection map of an nx x ny x nz grid (all even): coarse point (x, y, z) of the (nx/2) x (ny/2) x (nz/2) grid is fine
  * point (2x, 2y, 2z), both in the generator's lexicographic numbering (x fastest); f2c holds (nx/2)(ny/2)(nz/2) entries */
 void sbh_mg_f2c(int nx, int ny, int nz, CG_UINT* f2c);
+/* the trilinear prolongation of an nx x ny x nz grid (all even) from the grid of half the size in every direction, as CSR over the
+ * nx ny nz fine points, both sides in the generator's numbering (x fastest): per dimension an even index i takes coarse i / 2 with
+ * weight 1, an odd one (i - 1) / 2 and (i + 1) / 2 with 1/2 each, the second dropped (not renormalised) where it would be the
+ * coarse dimension itself; a row's weights are the products 1, 1/2, 1/4, 1/8, its entries in ascending coarse number.  ptr holds
+ * nx ny nz + 1 entries; col and val room for 8 per row.  With it goes omega = 0.5 */
+void sbh_mg_trilinear(int nx, int ny, int nz, uint64_t* ptr, CG_UINT* col, double* val);
 /* the L - 1 coarse levels of param's grid in the fine matrix's format, generated, converted and uploaded as the driver does the
  * fine one: mats[l - 1] (an sb_matrix*) and maps[l - 1] are level l's device matrix and the injection map into it, l = 1 .. L - 1.
  * Returns what sbh_mg_hierarchy_free releases (after the solver handle that uses the levels) */
@@ -320,6 +332,10 @@ int solvePCGSGS(Comm* comm, Parameter* param, Matrix* m);
  * grid".  Prints the preconditioner, its levels and level 0's colour count, then solvePCG's lines; returns k as solveCG does.
  * One rank, tree dot order; the single-precision libraries export it too and end the process with "PCG: double precision only". */
 int solvePCGMG(Comm* comm, Parameter* param, Matrix* m);
+/* solvePCGMG with trilinear interpolation and its scaled transpose applied to the full residual between the levels:
+ * the transfers with which the coarse levels count in every row order.  The same matrices, refusals, printed lines (the
+ * preconditioner line says "full-weighting transfers") and return value. */
+int solvePCGMGFW(Comm* comm, Parameter* param, Matrix* m);
 /* Jacobi-preconditioned BiCGStab: the short-recurrence solver for matrices that are not symmetric; returns k as
  * solveCG does.  The single-precision libraries export it too and end the process with "BiCGStab: double precision only". */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m);

@@ -55,6 +55,7 @@ SYMBOLS = [
     "sb_pcg_create_sgs", "sb_pcg_precond", "sb_pcg_colours", "sb_pcg_colouring", "sb_pcg_apply_precond", "sb_pcg_precond_bytes",
     "sb_pcg_apply_precond_ms",
     "sb_pcg_create_mg", "sb_pcg_levels", "sb_pcg_level_rows", "sb_pcg_level_colours",
+    "sb_pcg_create_mg_p", "sb_pcg_mg_fw_probe",
     "sb_bicgstab_create", "sb_bicgstab_free", "sb_bicgstab_solve", "sb_bicgstab_start", "sb_bicgstab_run_iters", "sb_bicgstab_finish",
     "sb_bicgstab_history", "sb_bicgstab_solution", "sb_bicgstab_check_residual", "sb_bicgstab_dinv", "sb_bicgstab_launches_per_body",
     "sb_bicgstab_loop_ms", "sb_bicgstab_counters", "sb_bicgstab_update_p_native", "sb_bicgstab_update_s_native",
@@ -294,6 +295,8 @@ def load():
         "sb_pcg_levels": (C.c_int, [vp]),
         "sb_pcg_level_rows": (u32, [vp, C.c_int]),
         "sb_pcg_level_colours": (C.c_int, [vp, C.c_int]),
+        "sb_pcg_create_mg_p": (vp, [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
+        "sb_pcg_mg_fw_probe": (None, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),
         # BiCGStab with a diagonal preconditioner
         "sb_bicgstab_create": (vp, [vp, vp, vp, vp, C.c_int, vp]),
         "sb_bicgstab_free": (None, [vp]),

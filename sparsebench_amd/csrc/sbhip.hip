@@ -29,6 +29,7 @@
 #include "sgs.hip.h"
 #include "bicgstab.hip.h"
 #include "mg.hip.h"
+#include "mg_fw.hip.h"
 
 #include <algorithm>
 #include <iterator>
@@ -702,4 +703,5 @@ void sb_event_destroy(void* ev) { HIP_CHECK(hipEventDestroy((hipEvent_t)ev)); }
 #include "sbhip_pcg.inc.h"
 #include "sbhip_sgs.inc.h"
 #include "sbhip_mg.inc.h"
+#include "sbhip_mg_fw.inc.h"
 #include "sbhip_bicgstab.inc.h"

@@ -15,10 +15,30 @@ struct MgLevel {
   uint32_t nCoarse = 0, nRChunks = 0;
   MgRestrict R = {};      // device arrays; R.fineRow is also the translated f2c the prolongation uses
   double restrictBytes = 0.0;
+  // the full-weighting transfers to the next level (sbhip_mg_fw.inc.h) in the injection's place
+  double *diag = nullptr, *d = nullptr; // the diagonal whose reciprocal is dinv; the full residual
+  MgTransfer PT = {}, Pm = {};          // omega P^T over the next level's rows, P over this level's; device arrays
+  uint32_t nPTChunks = 0, nPChunks = 0;
+  double omega = 0.0;
+  double transferBytes = 0.0;           // both structures as one cycle reads them
 };
 struct MgPlan {
   std::vector<MgLevel> lev;
+  bool fw = false; // full-weighting transfers (sb_pcg_create_mg_p) in place of injection
 };
+// (sbhip_mg_fw.inc.h) a caller's prolongations: their checks, the structures of one level, the transfers' launches and bytes
+struct MgFwArgs {
+  const uint64_t* const* ptr;
+  const uint32_t* const* col;
+  const double* const* val;
+  const double* omega;
+};
+static void mg_fw_check(const char* fn, const MgFwArgs& a, int l, uint32_t nFine, uint32_t nCoarseRows);
+static void mg_fw_build(MgLevel& F, const sb_matrix* coarse, const MgFwArgs& a, int l);
+static void mg_fw_free(MgLevel& V);
+static void mg_fw_restrict(const MgLevel& V, const double* r, const double* z, double* rc, const int* stop);
+static void mg_fw_prolong(const MgLevel& V, const double* zc, double* z, const int* stop);
+static double mg_fw_bytes(const MgLevel& V);
 
 namespace {
 // old row -> device row of a matrix (identity unless Sell-C-sigma permuted)
@@ -88,6 +108,7 @@ static void mg_release(sb_pcg* s)
     MgLevel& V = M->lev[l];
     sb_free((void*)V.R.chunkPtr), sb_free((void*)V.R.chunkLen), sb_free((void*)V.R.fineRow), sb_free((void*)V.R.rowLen);
     sb_free((void*)V.R.col), sb_free((void*)V.R.val);
+    mg_fw_free(V);
     if (l == 0) continue; // level 0's smoother, dinv, r and z are the handle's
     sgs_free_plan(V.P);
     sb_free(V.dinv), sb_free(V.r), sb_free(V.z);
@@ -116,7 +137,8 @@ static void mg_apply(const sb_pcg* s, const double* r, double* t, double* z, con
     const double* rl   = l ? V.r : r;
     double *tl = l ? V.P->t : t, *zl = l ? V.z : z;
     sgs_apply(V.P, (const double*)V.dinv, rl, tl, zl, stop);
-    if (l + 1 < L && V.nRChunks)
+    if (l + 1 < L && M->fw) mg_fw_restrict(V, rl, zl, M->lev[l + 1].r, stop);
+    else if (l + 1 < L && V.nRChunks)
       hipLaunchKernelGGL(mg_restrict_residual_k, dim3((V.nRChunks + 3u) / 4u), dim3(256), 0, g.stream, V.nRChunks, V.R, rl,
           (const double*)zl, M->lev[l + 1].r, stop);
   }
@@ -125,7 +147,8 @@ static void mg_apply(const sb_pcg* s, const double* r, double* t, double* z, con
     const MgLevel& V = M->lev[l];
     const double* rl = l ? V.r : r;
     double *tl = l ? V.P->t : t, *zl = l ? V.z : z;
-    if (V.nCoarse)
+    if (M->fw) mg_fw_prolong(V, M->lev[l + 1].z, zl, stop);
+    else if (V.nCoarse)
       hipLaunchKernelGGL(mg_prolong_add_k, dim3(stream_grid(V.nCoarse, 256)), dim3(256), 0, g.stream, V.nCoarse, V.R.fineRow,
           (const double*)M->lev[l + 1].z, zl, stop);
     mg_post_smooth(V.P, (const double*)V.dinv, rl, tl, zl, stop);
@@ -133,15 +156,15 @@ static void mg_apply(const sb_pcg* s, const double* r, double* t, double* z, con
   HIP_CHECK(hipGetLastError());
 }
 
-// launches of one V-cycle: per level but the last two smoothing applies (2 nC - 1 each), the restriction, the prolongation; the
-// last level one apply
+// launches of one V-cycle: per level but the last two smoothing applies (2 nC - 1 each), the restriction (full weighting: the
+// residual and the restriction), the prolongation; the last level one apply
 static int mg_apply_launches(const sb_pcg* s)
 {
   int n = 0;
   const size_t L = s->mg->lev.size();
   for (size_t l = 0; l < L; l++) {
     const int a = 2 * (int)s->mg->lev[l].P->nC - 1;
-    n += l + 1 < L ? 2 * a + 2 : a;
+    n += l + 1 < L ? 2 * a + (s->mg->fw ? 3 : 2) : a;
   }
   return n;
 }
@@ -158,37 +181,43 @@ static double mg_bytes(const sb_pcg* s)
     const MgLevel& V = s->mg->lev[l];
     b += sgs_bytes(V.P, V.n);
     if (l + 1 == L) break;
-    b += V.restrictBytes + 28.0 * (double)V.nCoarse;
+    b += s->mg->fw ? mg_fw_bytes(V) : V.restrictBytes + 28.0 * (double)V.nCoarse;
     b += V.P->halfBytes[0] + V.P->halfBytes[1] + 40.0 * (double)V.n;                    // forward from the guess
     b += V.P->structBytes - V.P->halfBytes[0] + 32.0 * (double)V.P->rowsBackward;       // backward
   }
   return b;
 }
 
-sb_pcg* sb_pcg_create_mg(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int nCoarse,
-    const sb_matrix* const* coarse, const uint32_t* const* f2c_host)
+// fn: the entry point as messages name it.  fw NULL: injection by f2c_host; else its prolongations (f2c_host NULL)
+static sb_pcg* mg_create(const char* fn, const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int nCoarse,
+    const sb_matrix* const* coarse, const uint32_t* const* f2c_host, const MgFwArgs* fw)
 {
   need_init();
-  if (nCoarse < 0) SB_FATAL("sb_pcg_create_mg: nCoarse = %d: the number of coarse levels cannot be negative", nCoarse);
-  if (nCoarse > 0 && (!coarse || !f2c_host)) SB_FATAL("sb_pcg_create_mg: %d coarse levels need their matrices and injection maps", nCoarse);
+  if (nCoarse < 0) SB_FATAL("%s: nCoarse = %d: the number of coarse levels cannot be negative", fn, nCoarse);
+  if (nCoarse > 0 && (!coarse || (fw ? !fw->ptr || !fw->col || !fw->val || !fw->omega : !f2c_host)))
+    SB_FATAL("%s: %d coarse levels need their matrices and %s", fn, nCoarse, fw ? "prolongations" : "injection maps");
   // every level is looked at before anything is built (level 0 here for its shape alone: pcg_create would take its extra
   // columns for another rank's and say so)
-  if (m->nr != m->nc) SB_FATAL("sb_pcg_create_mg: the matrix of level 0 is not square (%u rows, %u columns)", m->nr, m->nc);
+  if (m->nr != m->nc) SB_FATAL("%s: the matrix of level 0 is not square (%u rows, %u columns)", fn, m->nr, m->nc);
   for (int l = 1; l <= nCoarse; l++) {
     const sb_matrix* c    = coarse[l - 1];
     const sb_matrix* fine = l == 1 ? m : coarse[l - 2];
-    if (!c || !f2c_host[l - 1]) SB_FATAL("sb_pcg_create_mg: level %d has no matrix or no injection map", l);
-    if (c->prec != 2) SB_FATAL("sb_pcg_create_mg: MG: double precision only (the matrix of level %d was uploaded in single precision)", l);
-    if (c->nr != c->nc) SB_FATAL("sb_pcg_create_mg: the matrix of level %d is not square (%u rows, %u columns)", l, c->nr, c->nc);
+    if (!c || (fw ? !fw->ptr[l - 1] || !fw->col[l - 1] || !fw->val[l - 1] : !f2c_host[l - 1]))
+      SB_FATAL("%s: level %d has no matrix or no %s", fn, l, fw ? "prolongation from it" : "injection map");
+    if (c->prec != 2) SB_FATAL("%s: MG: double precision only (the matrix of level %d was uploaded in single precision)", fn, l);
+    if (c->nr != c->nc) SB_FATAL("%s: the matrix of level %d is not square (%u rows, %u columns)", fn, l, c->nr, c->nc);
     if (c->nr >= fine->nr)
-      SB_FATAL("sb_pcg_create_mg: level %d has %u rows, level %d has %u: every level must be smaller than the one above it", l, c->nr,
-          l - 1, fine->nr);
+      SB_FATAL("%s: level %d has %u rows, level %d has %u: every level must be smaller than the one above it", fn, l, c->nr, l - 1,
+          fine->nr);
   }
-  char who[32];
+  if (fw)
+    for (int l = 0; l < nCoarse; l++) mg_fw_check(fn, *fw, l, l ? coarse[l - 1]->nr : m->nr, coarse[l]->nr);
+  char who[64];
   snprintf(who, sizeof who, "MG (level %d)", 0);
-  sb_pcg* s = pcg_create(m, halo, b_host, xexact_host, nullptr, "sb_pcg_create_mg", who);
+  sb_pcg* s = pcg_create(m, halo, b_host, xexact_host, nullptr, fn, who);
   MgPlan* M = new MgPlan();
   M->lev.resize((size_t)nCoarse + 1);
+  M->fw = fw != nullptr;
   s->mg = M;
   for (int l = 0; l <= nCoarse; l++) {
     MgLevel& V = M->lev[l];
@@ -198,13 +227,14 @@ sb_pcg* sb_pcg_create_mg(const sb_matrix* m, sb_halo* halo, const double* b_host
       const size_t nb = (size_t)V.n * sizeof(double) + 4096;
       V.dinv = (double*)sb_malloc(nb), V.r = (double*)sb_malloc(nb), V.z = (double*)sb_malloc(nb);
       snprintf(who, sizeof who, "MG (level %d)", l);
-      jacobi_dinv(V.A, V.dinv, "sb_pcg_create_mg", who);
+      jacobi_dinv(V.A, V.dinv, fn, who);
     } else {
       V.dinv = s->dinv;
     }
     HostRows h = sgs_download(V.A); // once: the restriction reads the rows whole, the smoother's plan compacts them
-    if (l < nCoarse) mg_build_restrict(V, coarse[l], h, f2c_host[l], l);
-    snprintf(who, sizeof who, "sb_pcg_create_mg: level %d", l);
+    if (l < nCoarse && fw) mg_fw_build(V, coarse[l], *fw, l);
+    else if (l < nCoarse) mg_build_restrict(V, coarse[l], h, f2c_host[l], l);
+    snprintf(who, sizeof who, "%s: level %d", fn, l);
     V.P = sgs_build(V.A, std::move(h), who);
     if (!l) s->sgs = V.P;
   }
@@ -212,6 +242,13 @@ sb_pcg* sb_pcg_create_mg(const sb_matrix* m, sb_halo* halo, const double* b_host
   return s;
 }
 
+sb_pcg* sb_pcg_create_mg(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int nCoarse,
+    const sb_matrix* const* coarse, const uint32_t* const* f2c_host)
+{
+  return mg_create("sb_pcg_create_mg", m, halo, b_host, xexact_host, nCoarse, coarse, f2c_host, nullptr);
+}
+
+static bool mg_is_fw(const sb_pcg* s) { return s->mg->fw; }
 int sb_pcg_levels(const sb_pcg* s) { return s->mg ? (int)s->mg->lev.size() : s->sgs ? 1 : 0; }
 static const SgsPlan* mg_level_plan(const sb_pcg* s, int l, const char* fn)
 {

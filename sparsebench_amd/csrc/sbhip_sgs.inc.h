@@ -231,7 +231,8 @@ sb_pcg* sb_pcg_create_sgs(const sb_matrix* m, sb_halo* halo, const double* b_hos
   return s;
 }
 
-int sb_pcg_precond(const sb_pcg* s) { return s->mg ? 2 : s->sgs ? 1 : 0; }
+static bool mg_is_fw(const sb_pcg* s); // (sbhip_mg.inc.h)
+int sb_pcg_precond(const sb_pcg* s) { return s->mg ? (mg_is_fw(s) ? 3 : 2) : s->sgs ? 1 : 0; }
 int sb_pcg_colours(const sb_pcg* s) { return s->sgs ? (int)s->sgs->nC : 0; }
 
 void sb_pcg_colouring(const sb_pcg* s, uint32_t* colour_host)

@@ -75,6 +75,15 @@ int solvePCGMG(Comm* comm, Parameter* param, Matrix* m)
   return sbh_solve_pcg_mg(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, 0);
 #endif
 }
+/* the same with full-weighting transfers between the levels */
+int solvePCGMGFW(Comm* comm, Parameter* param, Matrix* m)
+{
+#if defined(CRS)
+  return sbh_solve_pcg_mgfw(comm, param, m->dev, m->nr, m->rowNnz, 0, 0, 0, 0);
+#else
+  return sbh_solve_pcg_mgfw(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, 0);
+#endif
+}
 /* Jacobi-preconditioned BiCGStab on this build's Matrix (the _sp libraries: "BiCGStab: double precision only") */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_bicgstab(comm, param, m->dev, m->nr, m->rowNnz); }
 

@@ -30,7 +30,8 @@ static const char* kHelp =
     "                    or bicgstab (BiCGStab with the Jacobi preconditioner: non-symmetric matrices). Default cg.\n"
     "  -p <jacobi|sgs>   Preconditioner of -t pcg, sgs is multicolour symmetric Gauss-Seidel. Default jacobi.\n"
     "  -p mg      Multigrid V-cycle with the sgs smoother as the preconditioner of -t pcg (generated matrices).\n"
-    "  -l <int>   Levels of -p mg. Default the deepest of up to 4 that the grid allows.\n"
+    "  -p mgfw    The same with full-weighting transfers: trilinear interpolation and its scaled transpose.\n"
+    "  -l <int>   Levels of -p mg and -p mgfw. Default the deepest of up to 4 that the grid allows.\n"
     "  -r <int>   GMRES restart length. Default 30.\n"
     "  -n <int>   Number of right-hand sides for -t cg. Default 1.\n"
     "  -x <int>   Size in x for generated matrix, ignored if MM file is loaded. Default 100.\n"
@@ -61,7 +62,7 @@ int main(int argc, char** argv)
   int type = CG, opt;
   unsigned scsC = 64, scsSigma = 1;
   int restart = 30, nrhs = 1;
-  int precond = -1; /* -p: 0 jacobi, 1 sgs, 2 mg; -1 not given */
+  int precond = -1; /* -p: 0 jacobi, 1 sgs, 2 mg, 3 mgfw; -1 not given */
   int levels  = 0;  /* -l: levels of -p mg; 0 not given (the deepest of up to 4) */
   opterr = 0;
   while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:p:l:")) != -1) switch (opt) {
@@ -105,6 +106,7 @@ int main(int argc, char** argv)
       if (strcmp(optarg, "jacobi") == 0) precond = 0;
       else if (strcmp(optarg, "sgs") == 0) precond = 1;
       else if (strcmp(optarg, "mg") == 0) precond = 2;
+      else if (strcmp(optarg, "mgfw") == 0) precond = 3;
       else {
         fprintf(stderr, "Unknown preconditioner %s (-p <jacobi|sgs>)\n", optarg);
         return 1;
@@ -131,14 +133,15 @@ int main(int argc, char** argv)
     fprintf(stderr, "-p <jacobi|sgs> (the preconditioner) goes with -t pcg only\n");
     return 1;
   }
-  if (levels != 0 && precond != 2) {
+  if (levels != 0 && precond != 2 && precond != 3) {
     fprintf(stderr, "-l <int> (the levels) goes with -p mg only\n");
     return 1;
   }
-  if (precond == 2) { /* refused before the set-up: a file has no grid, a grid may not allow the levels */
+  if (precond == 2 || precond == 3) { /* refused before the set-up: a file has no grid, a grid may not allow the levels */
     char why[256];
     if (strcmp(param.filename, "generate") != 0 && strcmp(param.filename, "generate7P") != 0) {
-      fprintf(stderr, "-p mg needs the grid: its hierarchy is the generated matrix's on coarser grids, not -m %s\n", param.filename);
+      fprintf(stderr, "-p %s needs the grid: its hierarchy is the generated matrix's on coarser grids, not -m %s\n",
+          precond == 3 ? "mgfw" : "mg", param.filename);
       return 1;
     }
     if (!sbh_mg_levels(param.nx, param.ny, param.nz, levels, why, sizeof why)) {
@@ -191,6 +194,14 @@ int main(int argc, char** argv)
       k = sbh_solve_pcg_mg(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, levels);
 #else
       k = sbh_solve_pcg_mg(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels);
+#endif
+    } else if (precond == 3 && levels == 0) {
+      k = solvePCGMGFW(&comm, &param, &sm); /* (prints "Preconditioner: MG (V-cycle, full-weighting transfers, ..." itself) */
+    } else if (precond == 3) {
+#ifdef SCS
+      k = sbh_solve_pcg_mgfw(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, levels);
+#else
+      k = sbh_solve_pcg_mgfw(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels);
 #endif
     } else {
       if (commIsMaster(&comm)) printf("Preconditioner: Jacobi (diagonal), nC = 0\n");

@@ -1,9 +1,11 @@
 /* sbh_mg.c -- the geometric hierarchy of a generated matrix for the multigrid preconditioner of PCG: how deep the
  * grid lets it go, the injection maps, and the coarse levels themselves: the stencil regenerated on each coarser grid through
  * the same calls the driver makes for the fine one (generate -> commPartition -> convert).  solvePCGMG's body (sbh_solver.c)
- * hands them to sb_pcg_create_mg.  Nothing is computed here.
+ * hands them to sb_pcg_create_mg -- or, with the trilinear prolongations below in the injection maps' place, to
+ * sb_pcg_create_mg_p.  Nothing is computed here but those weights, products of 1 and 1/2.
  */
 #define _GNU_SOURCE
+#include <stdint.h>
 #include <stdlib.h>
 
 #include "sbhip.h"
@@ -50,6 +52,43 @@ void sbh_mg_f2c(int nx, int ny, int nz, CG_UINT* f2c)
     for (int y = 0; y < cy; y++)
       for (int x = 0; x < cx; x++)
         f2c[((size_t)z * cy + y) * cx + x] = (CG_UINT)(((size_t)(2 * z) * ny + 2 * y) * nx + 2 * x);
+}
+
+/* the trilinear prolongation (sparsebench.h): per dimension an even fine index i takes coarse i / 2 with weight 1, an odd one
+ * (i - 1) / 2 and (i + 1) / 2 with 1/2 each, the second dropped where it is past the coarse grid; a row's weights are the
+ * products, its entries in ascending coarse number */
+static int line_weights(int i, int nc, int idx[2], double w[2])
+{
+  if (i % 2 == 0) {
+    idx[0] = i / 2, w[0] = 1.0;
+    return 1;
+  }
+  idx[0] = (i - 1) / 2, w[0] = 0.5;
+  idx[1] = (i + 1) / 2, w[1] = 0.5;
+  return idx[1] < nc ? 2 : 1;
+}
+
+void sbh_mg_trilinear(int nx, int ny, int nz, uint64_t* ptr, CG_UINT* col, double* val)
+{
+  const int cx = nx / 2, cy = ny / 2, cz = nz / 2;
+  uint64_t o = 0;
+  size_t row = 0;
+  ptr[0]     = 0;
+  for (int z = 0; z < nz; z++)
+    for (int y = 0; y < ny; y++)
+      for (int x = 0; x < nx; x++) {
+        int ix[2], iy[2], iz[2];
+        double wx[2], wy[2], wz[2];
+        const int kx = line_weights(x, cx, ix, wx), ky = line_weights(y, cy, iy, wy), kz = line_weights(z, cz, iz, wz);
+        for (int c = 0; c < kz; c++)
+          for (int b = 0; b < ky; b++)
+            for (int a = 0; a < kx; a++) {
+              col[o] = (CG_UINT)(((size_t)iz[c] * cy + iy[b]) * cx + ix[a]);
+              val[o] = wz[c] * wy[b] * wx[a];
+              o++;
+            }
+        ptr[++row] = o;
+      }
 }
 
 /* one coarse level: the generator's matrix on its grid, converted and uploaded as the fine one was */

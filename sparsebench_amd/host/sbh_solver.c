@@ -338,8 +338,9 @@ static void mg_refuse(const char* msg)
   exit(EXIT_FAILURE);
 }
 
-int sbh_solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
-    CG_UINT sigma, int levels)
+/* fw: the trilinear prolongations and omega = 0.5 in the injection maps' place */
+static int solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int levels, int fw)
 {
   dp_only("PCG: double precision only\n");
   if (strcmp(param->filename, "generate") != 0 && strcmp(param->filename, "generate7P") != 0)
@@ -354,13 +355,43 @@ int sbh_solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
   void* hierarchy      = sbh_mg_hierarchy_build(param, fmt, C, sigma, L, mats, maps);
   double *b, *xexact;
   init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
-  sb_pcg* s = sb_pcg_create_mg((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats, maps);
+  sb_pcg* s;
+  if (fw) {
+    uint64_t** ptr  = (uint64_t**)calloc((size_t)L, sizeof *ptr);
+    CG_UINT** col   = (CG_UINT**)calloc((size_t)L, sizeof *col);
+    double** val    = (double**)calloc((size_t)L, sizeof *val);
+    double* omega   = (double*)calloc((size_t)L, sizeof *omega);
+    int nx = param->nx, ny = param->ny, nz = param->nz;
+    for (int l = 0; l + 1 < L; l++, nx /= 2, ny /= 2, nz /= 2) {
+      const size_t n = (size_t)nx * ny * nz;
+      ptr[l] = (uint64_t*)malloc((n + 1) * sizeof(uint64_t)), col[l] = (CG_UINT*)malloc(8 * n * sizeof(CG_UINT));
+      val[l] = (double*)malloc(8 * n * sizeof(double)), omega[l] = 0.5;
+      sbh_mg_trilinear(nx, ny, nz, ptr[l], col[l], val[l]);
+    }
+    s = sb_pcg_create_mg_p((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats, (const uint64_t* const*)ptr,
+        (const uint32_t* const*)col, (const double* const*)val, omega);
+    for (int l = 0; l + 1 < L; l++) free(ptr[l]), free(col[l]), free(val[l]);
+    free(ptr), free(col), free(val), free(omega);
+  } else {
+    s = sb_pcg_create_mg((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats, maps);
+  }
   if (commIsMaster(comm))
-    printf("Preconditioner: MG (V-cycle, multicolour SGS smoother), levels = %d, nC = %d\n", sb_pcg_levels(s), sb_pcg_colours(s));
+    printf("Preconditioner: MG (V-cycle, %smulticolour SGS smoother), levels = %d, nC = %d\n", fw ? "full-weighting transfers, " : "",
+        sb_pcg_levels(s), sb_pcg_colours(s));
   const int k = run_pcg(comm, param, s, b, xexact);
   sbh_mg_hierarchy_free(hierarchy, fmt, L);
   free(mats), free(maps);
   return k;
+}
+int sbh_solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int levels)
+{
+  return solve_pcg_mg(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, levels, 0);
+}
+int sbh_solve_pcg_mgfw(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int levels)
+{
+  return solve_pcg_mg(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, levels, 1);
 }
 
 /* ---- solveBiCGStab ----------------------------------------------------------------------- */

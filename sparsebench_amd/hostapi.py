@@ -72,6 +72,8 @@ def host(precision="double"):
     H.sbh_mg_levels.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     H.sbh_mg_f2c.restype = None
     H.sbh_mg_f2c.argtypes = [C.c_int, C.c_int, C.c_int, vp]
+    H.sbh_mg_trilinear.restype = None
+    H.sbh_mg_trilinear.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp]
     if precision == "single":
         _host_sp = H
     else:
@@ -108,6 +110,48 @@ def mg_f2c(nx, ny, nz):
     out = np.empty((nx // 2) * (ny // 2) * (nz // 2), dtype=np.uint32)
     host().sbh_mg_f2c(int(nx), int(ny), int(nz), out.ctypes.data_as(vp))
     return out
+
+
+def mg_trilinear(nx, ny, nz):
+    """the trilinear prolongation of an nx x ny x nz grid (all even) from the grid of half the size in every direction
+    (sbh_mg_trilinear) as a CSR triple (ptr uint64, col uint32, val float64) over the fine points, generator's numbering on both
+    sides: weights 1, 1/2, 1/4, 1/8, the upper faces' missing neighbours dropped.  omega = 0.5 goes with it"""
+    if nx % 2 or ny % 2 or nz % 2 or min(nx, ny, nz) < 2:
+        raise ValueError("MG: the grid %d x %d x %d has an odd or empty dimension" % (nx, ny, nz))
+    n = nx * ny * nz
+    ptr, col, val = np.empty(n + 1, dtype=np.uint64), np.empty(8 * n, dtype=np.uint32), np.empty(8 * n, dtype=np.float64)
+    host().sbh_mg_trilinear(int(nx), int(ny), int(nz), ptr.ctypes.data_as(vp), col.ctypes.data_as(vp), val.ctypes.data_as(vp))
+    nnz = int(ptr[n])
+    return ptr, col[:nnz].copy(), val[:nnz].copy()
+
+
+def _omega(omega, l):
+    if not (isinstance(omega, (int, float)) and np.isfinite(omega) and omega > 0.0):
+        raise ValueError("omega of level %d must be finite and positive, got %r" % (l, omega))
+    return float(omega)
+
+
+def _p_triple(P, n_fine, n_coarse, l):
+    """a prolongation as contiguous (ptr uint64, col uint32, val float64): a scipy.sparse matrix (its CSR form, entries as
+    stored) or a (ptr, col, val) triple; the shape is checked here, the contents by the library"""
+    if hasattr(P, "tocsr"):
+        if P.shape != (n_fine, n_coarse):
+            raise ValueError("P of level %d must be %d x %d, got %r" % (l, n_fine, n_coarse, P.shape))
+        P = P.tocsr()
+        P = (P.indptr, P.indices, P.data)
+    try:
+        ptr, col, val = P
+    except (TypeError, ValueError):
+        raise ValueError("P of level %d must be a scipy.sparse matrix or a (ptr, col, val) triple" % l)
+    if np.any(np.asarray(ptr) < 0) or np.any(np.asarray(col) < 0):
+        raise ValueError("P of level %d has a negative pointer or column" % l)
+    ptr, col = np.ascontiguousarray(ptr, dtype=np.uint64), np.ascontiguousarray(col, dtype=np.uint32)
+    val = np.ascontiguousarray(val, dtype=np.float64)
+    if ptr.shape != (n_fine + 1,):
+        raise ValueError("P of level %d must have %d row pointers (level %d has %d rows), got %r" % (l, n_fine + 1, l, n_fine, ptr.shape))
+    if col.ndim != 1 or col.shape != val.shape or int(ptr.max()) > len(col):
+        raise ValueError("P of level %d: %d columns, %d weights, row pointers up to %d" % (l, col.size, val.size, int(ptr.max())))
+    return ptr, col, val
 
 
 def convert_mtx_to_bmx(path):
@@ -574,26 +618,28 @@ class PCG(_BodySolver):
     original row order (all 1.0: `CG` in the tree order bit for bit).  precond "sgs": symmetric Gauss-Seidel by multicolouring
     in place of the diagonal (takes no dinv).  precond "mg": a multigrid V-cycle with that smoother:
     `levels` for a generated problem's own geometric hierarchy (None: the deepest of up to 4 the grid allows), or
-    `coarse=[(Problem, f2c), ...]` for the caller's.  Double precision, one rank, tree dot order."""
+    `coarse=[(Problem, f2c), ...]` for the caller's.  precond "mgfw": that cycle with full-weighting transfers:
+    `levels` for the generated hierarchy with the trilinear P and omega = 0.5, or `coarse=[(Problem, P, omega), ...]` with P a
+    scipy.sparse matrix or a (ptr, col, val) CSR triple of n_l x n_{l+1}.  Double precision, one rank, tree dot order."""
 
     PREFIX, NAME = "sb_pcg", "PCG"
     COUNTERS = ("stop", "stop_next", "iters", "n_rr", "n_pAp")
 
     def __init__(self, problem, dinv=None, precond="jacobi", levels=None, coarse=None):
         self._need_double(problem)
-        if precond not in ("jacobi", "sgs", "mg"):
-            raise ValueError("precond must be 'jacobi' or 'sgs' or 'mg', got %r" % (precond,))
-        if precond in ("sgs", "mg") and dinv is not None:
+        if precond not in ("jacobi", "sgs", "mg", "mgfw"):
+            raise ValueError("precond must be 'jacobi' or 'sgs' or 'mg' or 'mgfw', got %r" % (precond,))
+        if precond in ("sgs", "mg", "mgfw") and dinv is not None:
             raise ValueError("precond=%r takes no dinv: its diagonal is the matrix's own" % (precond,))
-        if precond != "mg" and (levels is not None or coarse is not None):
-            raise ValueError("levels and coarse go with precond='mg' only")
+        if precond not in ("mg", "mgfw") and (levels is not None or coarse is not None):
+            raise ValueError("levels and coarse go with precond='mg' only, or with 'mgfw'")
         if levels is not None and coarse is not None:
             raise ValueError("precond='mg' takes levels (a generated problem's own hierarchy) or coarse (the caller's), not both")
         self._owned = []  # the coarse problems this handle generated itself
         self._keep = None
-        if precond == "mg":
+        if precond in ("mg", "mgfw"):
             try:
-                self._create_mg(problem, levels, coarse)
+                self._create_mg(problem, levels, coarse, precond == "mgfw")
             except Exception:
                 self._free_owned()  # the coarse problems generated so far
                 raise
@@ -604,24 +650,28 @@ class PCG(_BodySolver):
         else:
             self.ptr = self.L.sb_pcg_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), _ptr(self._dinv_arg(dinv)))
 
-    def _create_mg(self, problem, levels, coarse):
+    def _create_mg(self, problem, levels, coarse, fw=False):
         """coarse: [(Problem, f2c), ...], level l + 1's problem and the rows of level l that are its points (original numbering);
-        else the geometric hierarchy of a generated problem at `levels` (None: the deepest of up to 4)"""
+        else the geometric hierarchy of a generated problem at `levels` (None: the deepest of up to 4).  fw: (Problem, P, omega)
+        triples and the trilinear P with omega = 0.5 in their place"""
         if coarse is None:
             name = getattr(problem, "filename", None)
             if name not in ("generate", "generate7P"):
-                raise ValueError("precond='mg' needs the grid: %r is not a generated problem (pass coarse=[(Problem, f2c), ...])" % (name,))
+                raise ValueError("precond=%r needs the grid: %r is not a generated problem (pass coarse=[(Problem, %s), ...])"
+                                 % ("mgfw" if fw else "mg", name, "P, omega" if fw else "f2c"))
             if problem.nr != problem.totalNr:
                 raise ValueError("precond='mg' runs on one rank")
             dims = problem.dims
             nlev = mg_levels(*dims, levels=levels)
             coarse = []
             for _ in range(nlev - 1):
-                f2c = mg_f2c(*dims)
+                transfer = (mg_trilinear(*dims), 0.5) if fw else (mg_f2c(*dims),)
                 dims = tuple(d // 2 for d in dims)
                 q = Problem(name, *dims, fmt=problem.fmt, Cc=problem.Cc, sigma=problem.sigma_arg)
                 self._owned.append(q)
-                coarse.append((q, f2c))
+                coarse.append((q,) + transfer)
+        if fw:
+            return self._create_mg_p(problem, coarse)
         maps = []
         for q, f2c in coarse:
             self._need_double(q)
@@ -636,6 +686,35 @@ class PCG(_BodySolver):
         self._keep = (coarse, maps)  # the caller's coarse problems must outlive the handle, as the fine one must
         self.ptr = self.L.sb_pcg_create_mg(problem.matrix, problem.halo, _ptr(b), _ptr(xe), n, mats, ptrs)
 
+    def _create_mg_p(self, problem, coarse):
+        ps, omegas, n_fine = [], [], problem.nr
+        for l, item in enumerate(coarse):
+            if not isinstance(item, (tuple, list)) or len(item) != 3:
+                raise ValueError("precond='mgfw' takes coarse=[(Problem, P, omega), ...]: entry %d is not such a triple" % l)
+            q, P, omega = item
+            self._need_double(q)
+            omegas.append(_omega(omega, l))
+            ps.append(_p_triple(P, n_fine, q.nr, l))
+            n_fine = q.nr
+        b, xe = self._open(problem)
+        n = len(coarse)
+        mats = (vp * max(n, 1))(*[item[0].matrix for item in coarse])
+        arrs = [(vp * max(n, 1))(*[t[i].ctypes.data for t in ps]) for i in range(3)]
+        om = np.array(omegas + [0.0], dtype=np.float64)
+        self._keep = (coarse, ps)  # the caller's coarse problems must outlive the handle, as the fine one must
+        self.ptr = self.L.sb_pcg_create_mg_p(problem.matrix, problem.halo, _ptr(b), _ptr(xe), n, mats, arrs[0], arrs[1], arrs[2], _ptr(om))
+
+    def mg_fw_probe(self, l, r, z, zc):
+        """(d, rc, z_out) of the transfers of level l alone (sb_pcg_mg_fw_probe): d = r - A_l z, rc = omega_l P_l^T d,
+        z_out = z + P_l zc; r, z in level l's original row order, zc in level l + 1's"""
+        nf, nc = self.level_rows(l), self.level_rows(l + 1)
+        r, z, zc = (np.ascontiguousarray(v, dtype=np.float64) for v in (r, z, zc))
+        if r.shape != (nf,) or z.shape != (nf,) or zc.shape != (nc,):
+            raise ValueError("r and z must hold %d doubles, zc %d" % (nf, nc))
+        d, rc, zo = np.empty(nf), np.empty(nc), np.empty(nf)
+        self.L.sb_pcg_mg_fw_probe(self.ptr, int(l), _ptr(r), _ptr(z), _ptr(zc), _ptr(d), _ptr(rc), _ptr(zo))
+        return d, rc, zo
+
     def _free_owned(self):
         for q in self._owned:
             q.free()
@@ -646,8 +725,8 @@ class PCG(_BodySolver):
         self._free_owned()
 
     def precond(self):
-        """"jacobi" (any diagonal), "sgs" or "mg" """
-        return ("jacobi", "sgs", "mg")[self.L.sb_pcg_precond(self.ptr)]
+        """"jacobi" (any diagonal), "sgs", "mg" or "mgfw" """
+        return ("jacobi", "sgs", "mg", "mgfw")[self.L.sb_pcg_precond(self.ptr)]
 
     def levels(self):
         """L of an MG handle; 1 for SGS, 0 for a diagonal one"""
