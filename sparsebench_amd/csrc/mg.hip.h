@@ -8,45 +8,12 @@
 
 namespace sbk {
 
-// s = s - a * z[col] over the lane's row of chunk c of a Sell-64 structure (chunkPtr, chunkLen per chunk; rowLen per slot; col,
-// val column-major per chunk), with sgs_sweep_k's batching: MG_BATCH loads, then their gathers, in flight before their updates
-// in storage order; past the chunk's end the index is clamped to its last element and the update is skipped by the lane's own
-// length
-constexpr uint32_t MG_BATCH = 16;
-__device__ __forceinline__ double mg_row(const unsigned long long* chunkPtr, const uint32_t* chunkLen, const uint32_t* rowLen,
-    const uint32_t* col, const double* val, uint32_t c, uint32_t lane, size_t slot, const double* z, double s)
-{
-  const uint32_t len = rowLen[slot];
-  const uint32_t n   = chunkLen[c]; // wave-uniform
-  const double* v    = val + chunkPtr[c] + lane;
-  const uint32_t* ci = col + chunkPtr[c] + lane;
-  for (uint32_t j = 0; j < n; j += MG_BATCH) {
-    double a[MG_BATCH], zz[MG_BATCH];
-    uint32_t cc[MG_BATCH];
-#pragma unroll
-    for (uint32_t u = 0; u < MG_BATCH; u++) {
-      const size_t e = (size_t)min(j + u, n - 1u) * 64u;
-      a[u] = stream_load(v + e), cc[u] = stream_load(ci + e);
-    }
-#pragma unroll
-    for (uint32_t u = 0; u < MG_BATCH; u++) zz[u] = z[cc[u]];
-#pragma unroll
-    for (uint32_t u = 0; u < MG_BATCH; u++)
-      if (j + u < len) s = s - a[u] * zz[u];
-  }
-  return s;
-}
-__device__ __forceinline__ double mg_half_row(const SgsHalf& H, uint32_t c, uint32_t lane, size_t slot, const double* z, double s)
-{
-  return mg_row(H.chunkPtr, H.chunkLen, H.rowLen, H.col, H.val, c, lane, slot, z, s);
-}
-
 // The forward sweep of the post-smoother, one colour: chunks [chunk0, chunk0 + nChunks) of the sweep structure, a wave per
 // chunk, a lane per row.  z holds a guess:
 //   s = r_i - sum lower ;  t_i = s ;  s = s - sum upper ;  z_i = s * dinv_i
 // Both halves share slots and rowIdx.  The rows gathered have another colour than the rows written, as in sgs_sweep_k.
 __global__ __launch_bounds__(256) void mg_sweep_guess_k(uint32_t chunk0, uint32_t nChunks, const uint32_t* __restrict__ rowIdx,
-    SgsHalf Lo, SgsHalf Up, const double* __restrict__ r, const double* __restrict__ dinv, double* t, double* z,
+    SellRows Lo, SellRows Up, const double* __restrict__ r, const double* __restrict__ dinv, double* t, double* z,
     const int* __restrict__ stop)
 {
   const uint32_t lane = threadIdx.x & 63u;
@@ -59,9 +26,9 @@ __global__ __launch_bounds__(256) void mg_sweep_guess_k(uint32_t chunk0, uint32_
   const bool live    = row != 0xFFFFFFFFu;
   double s           = live ? r[row] : 0.0;
   const double dv    = live ? dinv[row] : 0.0;
-  s                  = mg_half_row(Lo, c, lane, slot, z, s);
+  s                  = sell_row<16, false>(Lo, c, lane, Lo.rowLen[slot], z, s);
   if (live) t[row] = s;
-  s = mg_half_row(Up, c, lane, slot, z, s);
+  s = sell_row<16, false>(Up, c, lane, Up.rowLen[slot], z, s);
   if (live) z[row] = s * dv;
 }
 
@@ -89,7 +56,9 @@ __global__ __launch_bounds__(256) void mg_restrict_residual_k(uint32_t nChunks, 
   const size_t slot = (size_t)c * 64u + lane;
   const uint32_t f  = R.fineRow[slot];
   const bool live   = f != 0xFFFFFFFFu;
-  const double s    = mg_row(R.chunkPtr, R.chunkLen, R.rowLen, R.col, R.val, c, lane, slot, z, live ? r[f] : 0.0);
+  const double rf   = live ? r[f] : 0.0;
+  const SellRows A  = { R.chunkPtr, R.chunkLen, R.rowLen, R.col, R.val };
+  const double s    = sell_row<16, false>(A, c, lane, R.rowLen[slot], z, rf);
   if (live) rc[slot] = s; // (a live slot is a coarse row: slot < the coarse level's rows)
 }
 

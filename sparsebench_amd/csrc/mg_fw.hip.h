@@ -10,9 +10,9 @@
 namespace sbk {
 
 // d_i = r_i - sum lower - sum upper - diag_i * z_i over every row of the level: all chunks of all colours of the sweep structure
-// in ONE launch (a residual has no colour dependence), a wave per chunk, a lane per row.  Both halves are read with mg_half_row's
+// in ONE launch (a residual has no colour dependence), a wave per chunk, a lane per row.  Both halves are read with sell_row's
 // batching and skip-by-own-length rule.  z is only read here, d only written: no lane reads what another writes.
-__global__ __launch_bounds__(256) void mg_residual_k(uint32_t nChunks, const uint32_t* __restrict__ rowIdx, SgsHalf Lo, SgsHalf Up,
+__global__ __launch_bounds__(256) void mg_residual_k(uint32_t nChunks, const uint32_t* __restrict__ rowIdx, SellRows Lo, SellRows Up,
     const double* __restrict__ r, const double* __restrict__ z, const double* __restrict__ diag, double* __restrict__ d,
     const int* __restrict__ stop)
 {
@@ -26,52 +26,18 @@ __global__ __launch_bounds__(256) void mg_residual_k(uint32_t nChunks, const uin
   double s           = live ? r[row] : 0.0;
   const double dg    = live ? diag[row] : 0.0;
   const double zi    = live ? z[row] : 0.0;
-  s                  = mg_half_row(Lo, c, lane, slot, z, s);
-  s                  = mg_half_row(Up, c, lane, slot, z, s);
+  s                  = sell_row<16, false>(Lo, c, lane, Lo.rowLen[slot], z, s);
+  s                  = sell_row<16, false>(Up, c, lane, Up.rowLen[slot], z, s);
   if (live) d[row] = s - dg * zi;
 }
 
-// A transfer operator (built on the host, sbhip_mg_fw.inc.h): Sell-64 over the rows written, in their level's device order
+// A transfer operator (built on the host, sbhip_mg_fw.inc.h) is a SellRows over the rows written, in their level's device order
 // (slot == device row), the columns the device rows of the level gathered from; rowLen per slot is the row's kept (non-zero)
-// entries, 0 for a row without any and for a slot past the last row; col / val column-major per chunk.
-struct MgTransfer {
-  const unsigned long long* chunkPtr;
-  const uint32_t* chunkLen;
-  const uint32_t* rowLen;
-  const uint32_t* col;
-  const double* val;
-};
-
-// s = +0.0 ; s = s + w * v[col] over the lane's row of chunk c, mg_row's batching with BATCH entries in flight: past the chunk's
-// end the index is clamped to its last element and the update is skipped by the lane's own length (padding is skipped, not
-// multiplied: 0.0 * inf would be a NaN the contract does not have)
-template <uint32_t BATCH>
-__device__ __forceinline__ double mg_transfer_row(const MgTransfer& T, uint32_t c, uint32_t lane, uint32_t len, const double* v)
-{
-  const uint32_t n   = T.chunkLen[c]; // wave-uniform
-  const double* w    = T.val + T.chunkPtr[c] + lane;
-  const uint32_t* ci = T.col + T.chunkPtr[c] + lane;
-  double s           = 0.0;
-  for (uint32_t j = 0; j < n; j += BATCH) {
-    double a[BATCH], vv[BATCH];
-    uint32_t cc[BATCH];
-#pragma unroll
-    for (uint32_t u = 0; u < BATCH; u++) {
-      const size_t e = (size_t)min(j + u, n - 1u) * 64u;
-      a[u] = stream_load(w + e), cc[u] = stream_load(ci + e);
-    }
-#pragma unroll
-    for (uint32_t u = 0; u < BATCH; u++) vv[u] = v[cc[u]];
-#pragma unroll
-    for (uint32_t u = 0; u < BATCH; u++)
-      if (j + u < len) s = s + a[u] * vv[u];
-  }
-  return s;
-}
+// entries, 0 for a row without any and for a slot past the last row.  Its sums start from +0.0 and add: sell_row<BATCH, true>
 
 // rc_c = omega * sum over the kept entries of row c of P^T of w * d[fine row], in ascending original fine row number (the
 // host's order): a wave per chunk, a lane per coarse row.  The trilinear P has up to 27 entries per row: two batches of 16.
-__global__ __launch_bounds__(256) void mg_restrict_pt_k(uint32_t nChunks, uint32_t nCoarse, MgTransfer T, double omega,
+__global__ __launch_bounds__(256) void mg_restrict_pt_k(uint32_t nChunks, uint32_t nCoarse, SellRows T, double omega,
     const double* __restrict__ d, double* __restrict__ rc, const int* __restrict__ stop)
 {
   const uint32_t lane = threadIdx.x & 63u;
@@ -79,13 +45,13 @@ __global__ __launch_bounds__(256) void mg_restrict_pt_k(uint32_t nChunks, uint32
   if (*stop) return;
   if (c >= nChunks) return;
   const size_t slot = (size_t)c * 64u + lane;
-  const double s    = mg_transfer_row<16>(T, c, lane, T.rowLen[slot], d);
+  const double s    = sell_row<16, true>(T, c, lane, T.rowLen[slot], d, 0.0);
   if (slot < nCoarse) rc[slot] = omega * s;
 }
 
 // z_i = z_i + sum over the kept entries of row i of P of w * zc[coarse row], in the caller's storage order; a row without a kept
 // entry writes nothing.  A wave per chunk, a lane per fine row; up to 8 entries per row for the trilinear P: one batch.
-__global__ __launch_bounds__(256) void mg_prolong_p_k(uint32_t nChunks, MgTransfer T, const double* __restrict__ zc, double* z,
+__global__ __launch_bounds__(256) void mg_prolong_p_k(uint32_t nChunks, SellRows T, const double* __restrict__ zc, double* z,
     const int* __restrict__ stop)
 {
   const uint32_t lane = threadIdx.x & 63u;
@@ -94,7 +60,7 @@ __global__ __launch_bounds__(256) void mg_prolong_p_k(uint32_t nChunks, MgTransf
   if (c >= nChunks) return;
   const size_t slot  = (size_t)c * 64u + lane;
   const uint32_t len = T.rowLen[slot];
-  const double s     = mg_transfer_row<8>(T, c, lane, len, zc);
+  const double s     = sell_row<8, true>(T, c, lane, len, zc, 0.0);
   if (len) z[slot] = z[slot] + s; // (len > 0 only for slot < the level's rows)
 }
 

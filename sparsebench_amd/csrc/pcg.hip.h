@@ -47,6 +47,8 @@ __device__ __forceinline__ PcgScalars pcg_fetch(const PcgScalars* S)
 // elements 2l, 2l + 1 of each), the first group's loads go in flight beside the control block, the group's level-1 values
 // are formed in registers.  Six streams per row instead of three (r, Ap, dinv in; r, z out), two butterfly reductions per
 // span.  The partial last group and an odd n take the guarded loop behind.
+// sgs_update_r_k (sgs.hip.h) is this kernel without the dinv loads, the z stores and the r.z values: its twin, to be changed
+// with it (as one body with a compile-time switch neither kernel keeps its code: DESIGN 4.6).
 // =============================================================================
 template <int PRO>
 __global__ __launch_bounds__(1024) void pcg_update_r_k(uint32_t n, const double* __restrict__ Ap, const double* src, double* r,

@@ -704,4 +704,5 @@ void sb_event_destroy(void* ev) { HIP_CHECK(hipEventDestroy((hipEvent_t)ev)); }
 #include "sbhip_sgs.inc.h"
 #include "sbhip_mg.inc.h"
 #include "sbhip_mg_fw.inc.h"
+#include "sbhip_pcg_loop.inc.h"
 #include "sbhip_bicgstab.inc.h"

@@ -13,11 +13,12 @@ struct MgLevel {
   double *r = nullptr, *z = nullptr; // levels 1 ..: the restricted residual and the correction (level 0: the caller's)
   // the restriction to the next level (absent on the last): Sell-64 over its rows in its device order
   uint32_t nCoarse = 0, nRChunks = 0;
-  MgRestrict R = {};      // device arrays; R.fineRow is also the translated f2c the prolongation uses
+  SellRows R = {};             // device arrays: the stored non-zero entries of the fine rows that are coarse points
+  uint32_t* fineRow = nullptr; // per slot of R its fine device row: also the translated f2c the prolongation uses
   double restrictBytes = 0.0;
   // the full-weighting transfers to the next level (sbhip_mg_fw.inc.h) in the injection's place
   double *diag = nullptr, *d = nullptr; // the diagonal whose reciprocal is dinv; the full residual
-  MgTransfer PT = {}, Pm = {};          // omega P^T over the next level's rows, P over this level's; device arrays
+  SellRows PT = {}, Pm = {};            // omega P^T over the next level's rows, P over this level's; device arrays
   uint32_t nPTChunks = 0, nPChunks = 0;
   double omega = 0.0;
   double transferBytes = 0.0;           // both structures as one cycle reads them
@@ -41,18 +42,6 @@ static void mg_fw_prolong(const MgLevel& V, const double* zc, double* z, const i
 static double mg_fw_bytes(const MgLevel& V);
 
 namespace {
-// old row -> device row of a matrix (identity unless Sell-C-sigma permuted)
-std::vector<uint32_t> mg_old_to_new(const sb_matrix* m)
-{
-  std::vector<uint32_t> o2n(m->nr);
-  if (m->fmt == 1 && m->permuted) {
-    if (m->nr) sb_d2h(o2n.data(), m->oldToNew, (size_t)m->nr * sizeof(uint32_t));
-  } else {
-    for (uint32_t i = 0; i < m->nr; i++) o2n[i] = i;
-  }
-  return o2n;
-}
-
 // the restriction structure of level l from its downloaded rows h and the injection map in original numbering
 void mg_build_restrict(MgLevel& F, const sb_matrix* coarse, const HostRows& h, const uint32_t* f2c, int l)
 {
@@ -63,40 +52,22 @@ void mg_build_restrict(MgLevel& F, const sb_matrix* coarse, const HostRows& h, c
     if (seen[f2c[c]]) SB_FATAL("sb_pcg_create_mg: f2c[%d][%u] = %u repeats entry %u: the coarse points must be distinct", l, c, f2c[c], seen[f2c[c]] - 1);
     seen[f2c[c]] = c + 1;
   }
-  const std::vector<uint32_t> fo2n = mg_old_to_new(F.A), co2n = mg_old_to_new(coarse);
+  const std::vector<uint32_t> fo2n = old_to_device_rows(F.A), co2n = old_to_device_rows(coarse);
   F.nCoarse  = ncs;
   F.nRChunks = (ncs + 63u) / 64u;
-  const size_t slots = (size_t)F.nRChunks * 64u;
-  std::vector<uint32_t> fineRow(slots, 0xFFFFFFFFu), rowLen(slots, 0), chunkLen(F.nRChunks, 0);
+  std::vector<uint32_t> fineRow((size_t)F.nRChunks * 64u, 0xFFFFFFFFu);
   for (uint32_t c = 0; c < ncs; c++) fineRow[co2n[c]] = fo2n[f2c[c]];
-  auto stored = [&](size_t q) { return h.val[q] != 0.0; }; // (Sell padding is a stored +0.0 and drops out, as in sgs_build)
-  for (size_t sl = 0; sl < slots; sl++) {
-    const uint32_t f = fineRow[sl];
-    if (f == 0xFFFFFFFFu) continue;
-    uint32_t len = 0;
-    for (size_t q = h.ptr[f]; q < h.ptr[f + 1]; q++)
-      if (stored(q)) {
-        if (h.col[q] >= nf) SB_FATAL("sb_pcg_create_mg: level %d: device row %u has column %u outside the %u rows", l, f, h.col[q], nf);
-        len++;
-      }
-    rowLen[sl]         = len;
-    chunkLen[sl / 64u] = std::max(chunkLen[sl / 64u], len);
-  }
-  std::vector<unsigned long long> chunkPtr((size_t)F.nRChunks + 1, 0);
-  for (uint32_t c = 0; c < F.nRChunks; c++) chunkPtr[c + 1] = chunkPtr[c] + (unsigned long long)chunkLen[c] * 64u;
-  std::vector<uint32_t> col(chunkPtr[F.nRChunks], 0);
-  std::vector<double> val(chunkPtr[F.nRChunks], 0.0);
-  for (size_t sl = 0; sl < slots; sl++) {
-    const uint32_t f = fineRow[sl];
-    if (f == 0xFFFFFFFFu) continue;
-    size_t o = chunkPtr[sl / 64u] + (sl & 63u);
-    for (size_t q = h.ptr[f]; q < h.ptr[f + 1]; q++)
-      if (stored(q)) col[o] = h.col[q], val[o] = h.val[q], o += 64;
-  }
-  F.R.chunkPtr = sgs_to_device(chunkPtr), F.R.chunkLen = sgs_to_device(chunkLen), F.R.fineRow = sgs_to_device(fineRow);
-  F.R.rowLen = sgs_to_device(rowLen), F.R.col = sgs_to_device(col), F.R.val = sgs_to_device(val);
-  // val + col | fineRow, rowLen per slot; chunkPtr, chunkLen per chunk | per coarse row r and one gathered z in, rc out
-  F.restrictBytes = (double)chunkPtr[F.nRChunks] * 12.0 + (double)F.nRChunks * (64.0 * 8.0 + 12.0) + 24.0 * (double)ncs;
+  // (Sell padding is a stored +0.0 and drops out, as in sgs_build)
+  auto stored = [&](uint32_t f, size_t q) {
+    if (h.val[q] == 0.0) return false;
+    if (h.col[q] >= nf) SB_FATAL("sb_pcg_create_mg: level %d: device row %u has column %u outside the %u rows", l, f, h.col[q], nf);
+    return true;
+  };
+  std::vector<unsigned long long> chunkPtr;
+  F.R       = sell64_pack(h, fineRow, stored, chunkPtr);
+  F.fineRow = sgs_to_device(fineRow);
+  // the structure with fineRow beside rowLen | per coarse row r and one gathered z in, rc out
+  F.restrictBytes = sell64_bytes(chunkPtr[F.nRChunks], F.nRChunks, 8) + 24.0 * (double)ncs;
 }
 } // namespace
 
@@ -106,8 +77,7 @@ static void mg_release(sb_pcg* s)
   if (!M) return;
   for (size_t l = 0; l < M->lev.size(); l++) {
     MgLevel& V = M->lev[l];
-    sb_free((void*)V.R.chunkPtr), sb_free((void*)V.R.chunkLen), sb_free((void*)V.R.fineRow), sb_free((void*)V.R.rowLen);
-    sb_free((void*)V.R.col), sb_free((void*)V.R.val);
+    sell64_free(V.R), sb_free(V.fineRow);
     mg_fw_free(V);
     if (l == 0) continue; // level 0's smoother, dinv, r and z are the handle's
     sgs_free_plan(V.P);
@@ -139,8 +109,8 @@ static void mg_apply(const sb_pcg* s, const double* r, double* t, double* z, con
     sgs_apply(V.P, (const double*)V.dinv, rl, tl, zl, stop);
     if (l + 1 < L && M->fw) mg_fw_restrict(V, rl, zl, M->lev[l + 1].r, stop);
     else if (l + 1 < L && V.nRChunks)
-      hipLaunchKernelGGL(mg_restrict_residual_k, dim3((V.nRChunks + 3u) / 4u), dim3(256), 0, g.stream, V.nRChunks, V.R, rl,
-          (const double*)zl, M->lev[l + 1].r, stop);
+      hipLaunchKernelGGL(mg_restrict_residual_k, dim3((V.nRChunks + 3u) / 4u), dim3(256), 0, g.stream, V.nRChunks,
+          MgRestrict{ V.R.chunkPtr, V.R.chunkLen, V.fineRow, V.R.rowLen, V.R.col, V.R.val }, rl, (const double*)zl, M->lev[l + 1].r, stop);
   }
   // up: prolong, post-smooth from the guess
   for (size_t l = L - 1; l-- > 0;) {
@@ -149,7 +119,7 @@ static void mg_apply(const sb_pcg* s, const double* r, double* t, double* z, con
     double *tl = l ? V.P->t : t, *zl = l ? V.z : z;
     if (M->fw) mg_fw_prolong(V, M->lev[l + 1].z, zl, stop);
     else if (V.nCoarse)
-      hipLaunchKernelGGL(mg_prolong_add_k, dim3(stream_grid(V.nCoarse, 256)), dim3(256), 0, g.stream, V.nCoarse, V.R.fineRow,
+      hipLaunchKernelGGL(mg_prolong_add_k, dim3(stream_grid(V.nCoarse, 256)), dim3(256), 0, g.stream, V.nCoarse, (const uint32_t*)V.fineRow,
           (const double*)M->lev[l + 1].z, zl, stop);
     mg_post_smooth(V.P, (const double*)V.dinv, rl, tl, zl, stop);
   }
@@ -248,7 +218,6 @@ sb_pcg* sb_pcg_create_mg(const sb_matrix* m, sb_halo* halo, const double* b_host
   return mg_create("sb_pcg_create_mg", m, halo, b_host, xexact_host, nCoarse, coarse, f2c_host, nullptr);
 }
 
-static bool mg_is_fw(const sb_pcg* s) { return s->mg->fw; }
 int sb_pcg_levels(const sb_pcg* s) { return s->mg ? (int)s->mg->lev.size() : s->sgs ? 1 : 0; }
 static const SgsPlan* mg_level_plan(const sb_pcg* s, int l, const char* fn)
 {

@@ -27,41 +27,18 @@ static void mg_fw_check(const char* fn, const MgFwArgs& a, int l, uint32_t nFine
 }
 
 namespace {
-// a transfer's kept entries as CSR over its device rows, a row's entries in the order the contract sums them
-struct MgFwRows {
-  std::vector<size_t> ptr;
-  std::vector<uint32_t> col;
-  std::vector<double> val;
-};
-// -> Sell-64, slot == device row
-MgTransfer mg_fw_sell(const MgFwRows& R, uint32_t* nChunksOut, double* bytes)
+// a transfer's kept entries (HostRows over its device rows, a row's entries in the order the contract sums them) -> Sell-64,
+// slot == device row
+SellRows mg_fw_sell(const HostRows& R, uint32_t* nChunksOut, double* bytes)
 {
   const uint32_t n = (uint32_t)R.ptr.size() - 1u, nChunks = (n + 63u) / 64u;
-  const size_t slots = (size_t)nChunks * 64u;
-  std::vector<uint32_t> rowLen(slots, 0), chunkLen(nChunks, 0);
-  for (uint32_t d = 0; d < n; d++) {
-    rowLen[d]         = (uint32_t)(R.ptr[d + 1] - R.ptr[d]);
-    chunkLen[d / 64u] = std::max(chunkLen[d / 64u], rowLen[d]);
-  }
-  std::vector<unsigned long long> chunkPtr((size_t)nChunks + 1, 0);
-  for (uint32_t c = 0; c < nChunks; c++) chunkPtr[c + 1] = chunkPtr[c] + (unsigned long long)chunkLen[c] * 64u;
-  std::vector<uint32_t> col(chunkPtr[nChunks], 0); // padding: (+0.0, column 0), never used (the lane's own length stops it)
-  std::vector<double> val(chunkPtr[nChunks], 0.0);
-  for (uint32_t d = 0; d < n; d++) {
-    size_t o = chunkPtr[d / 64u] + (d & 63u);
-    for (size_t q = R.ptr[d]; q < R.ptr[d + 1]; q++) col[o] = R.col[q], val[o] = R.val[q], o += 64;
-  }
-  MgTransfer T;
-  T.chunkPtr = sgs_to_device(chunkPtr), T.chunkLen = sgs_to_device(chunkLen), T.rowLen = sgs_to_device(rowLen);
-  T.col = sgs_to_device(col), T.val = sgs_to_device(val);
+  std::vector<uint32_t> slotRow((size_t)nChunks * 64u, 0xFFFFFFFFu);
+  for (uint32_t d = 0; d < n; d++) slotRow[d] = d;
+  std::vector<unsigned long long> chunkPtr;
+  const SellRows T = sell64_pack(R, slotRow, [](uint32_t, size_t) { return true; }, chunkPtr);
   *nChunksOut = nChunks;
-  *bytes += (double)chunkPtr[nChunks] * 12.0 + (double)nChunks * (64.0 * 4.0 + 12.0); // val + col | rowLen per slot; chunkPtr, chunkLen
+  *bytes += sell64_bytes(chunkPtr[nChunks], nChunks, 4);
   return T;
-}
-void mg_fw_free_transfer(MgTransfer& T)
-{
-  sb_free((void*)T.chunkPtr), sb_free((void*)T.chunkLen), sb_free((void*)T.rowLen), sb_free((void*)T.col), sb_free((void*)T.val);
-  T = {};
 }
 } // namespace
 
@@ -71,8 +48,8 @@ void mg_fw_free_transfer(MgTransfer& T)
 static void mg_fw_build(MgLevel& F, const sb_matrix* coarse, const MgFwArgs& a, int l)
 {
   const uint32_t nf = F.n, ncs = coarse->nr;
-  const std::vector<uint32_t> fo2n = mg_old_to_new(F.A), co2n = mg_old_to_new(coarse);
-  MgFwRows p, pt;
+  const std::vector<uint32_t> fo2n = old_to_device_rows(F.A), co2n = old_to_device_rows(coarse);
+  HostRows p, pt;
   p.ptr.assign((size_t)nf + 1, 0), pt.ptr.assign((size_t)ncs + 1, 0);
   for (uint32_t i = 0; i < nf; i++)
     for (uint64_t q = a.ptr[l][i]; q < a.ptr[l][i + 1]; q++)
@@ -106,7 +83,7 @@ static void mg_fw_build(MgLevel& F, const sb_matrix* coarse, const MgFwArgs& a, 
 
 static void mg_fw_free(MgLevel& V)
 {
-  mg_fw_free_transfer(V.PT), mg_fw_free_transfer(V.Pm);
+  sell64_free(V.PT), sell64_free(V.Pm);
   sb_free(V.diag), sb_free(V.d);
   V.diag = V.d = nullptr;
 }

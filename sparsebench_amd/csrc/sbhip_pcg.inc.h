@@ -3,6 +3,8 @@
 // one the matrix's kernel mode selects (launch_spmv: the reference-layout stream or the masked row programs, with their
 // fused p.Ap values; native CRS and generic C are followed by dot_l1_k).  The loop's vectors are allocations of the handle's
 // own: the matrix's tuned arena (sb_matrix::vecArena) is laid out for sb_cg's vectors and stays with sb_cg.
+// This file holds the handle and what does not ask how z is made; the loop, which does, is sbhip_pcg_loop.inc.h, included behind
+// the preconditioners' files.
 // ===========================================================================
 // preconditioned CG
 // ===========================================================================
@@ -20,14 +22,6 @@ struct sb_pcg {
   struct SgsPlan* sgs = nullptr; // symmetric Gauss-Seidel in place of the diagonal (sbhip_sgs.inc.h); dinv is 1 / diag(A)
   struct MgPlan* mg = nullptr;   // a multigrid V-cycle around it (sbhip_mg.inc.h); `sgs` is then level 0's smoother
 };
-// (sbhip_sgs.inc.h) the r update, the sweeps and the r.z values of an SGS handle; its plan's release
-static void sgs_residual_and_z(sb_pcg* s, bool prologue);
-static void sgs_release(sb_pcg* s);
-// (sbhip_mg.inc.h) the V-cycle z = V(0, r) of an MG handle, its launches, its plan's release
-static void mg_apply(const sb_pcg* s, const double* r, double* t, double* z, const int* stop);
-static int mg_apply_launches(const sb_pcg* s);
-static void mg_release(sb_pcg* s);
-
 // the diagonal in the device's row order; bad_dev: NULL, or two uint32 (rows without a finite positive diagonal, the first of
 // them) preset to {0, 0xFFFFFFFF}
 static void launch_diagonal(const sb_matrix* m, double* d_dev, uint32_t* bad_dev)
@@ -69,9 +63,10 @@ void sb_pcg_update_r_native(uint32_t n, double nalpha, const double* Ap_dev, dou
   test_block_done(S);
 }
 
+// precond: "Jacobi", or "SGS" / "MG (level l)", which have no caller's diagonal to fall back on
+static bool dinv_host_allowed(const char* precond) { return precond[0] == 'J'; }
 // dinv = 1 / diag(A) in the device's row order.  Rows without a finite positive diagonal are counted on the device, by
 // diag_*_k's own predicate (BiCGStab's is another one, taken on the host: the two checks stay apart), and refused
-static bool dinv_host_allowed(const char* precond);
 static void jacobi_dinv(const sb_matrix* m, double* dinv_dev, const char* fn, const char* precond)
 {
   if (!m->nr) return;
@@ -91,8 +86,7 @@ static void jacobi_dinv(const sb_matrix* m, double* dinv_dev, const char* fn, co
   HIP_CHECK(hipStreamSynchronize(g.stream));
 }
 
-// fn: the entry point as messages name it; precond: "Jacobi", or "SGS" (which has no caller's diagonal to fall back on)
-static bool dinv_host_allowed(const char* precond) { return precond[0] == 'J'; }
+// fn: the entry point as messages name it; precond: as jacobi_dinv takes it
 static sb_pcg* pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const double* dinv_host,
     const char* fn, const char* precond)
 {
@@ -137,123 +131,6 @@ static sb_pcg* pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_hos
 sb_pcg* sb_pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const double* dinv_host)
 {
   return pcg_create(m, halo, b_host, xexact_host, dinv_host, "sb_pcg_create", "Jacobi");
-}
-
-void sb_pcg_free(sb_pcg* s)
-{
-  if (!s) return;
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  s->clock.destroy();
-  mg_release(s);
-  sgs_release(s);
-  sb_free(s->r), sb_free(s->z), sb_free(s->p), sb_free(s->Ap), sb_free(s->x), sb_free(s->b), sb_free(s->dinv), sb_free(s->xexact);
-  sb_free(s->S), sb_free(s->l1pAp), sb_free(s->l1rz), sb_free(s->l1rr), sb_free(s->rr_hist), sb_free(s->rz_hist), sb_free(s->pAp_hist);
-  delete s;
-}
-
-// launches per loop body: p update | SpMV (+ p.Ap values) | alpha | r update (+ z, r.z and r.r values) | beta = 5 where the
-// selected SpMV kernel has a fused dot; native CRS and generic C add the dot pass: 6.  An SGS handle: the r update makes no z;
-// nC forward and nC - 1 backward launches and the r.z pass stand in between it and beta: 2 nC + 5 (+ 1).  An MG handle: the
-// V-cycle's launches in the sweeps' place: 6 (+ 1) + mg_apply_launches
-int sb_pcg_launches_per_body(const sb_pcg* s)
-{
-  if (s->mg) return (spmv_dot_kind(s->A) ? 6 : 7) + mg_apply_launches(s);
-  return (spmv_dot_kind(s->A) ? 5 : 6) + (s->sgs ? 2 * sb_pcg_colours(s) : 0);
-}
-
-template <int MODE> static void pcg_scalar_launch(sb_pcg* s)
-{
-  hipLaunchKernelGGL((pcg_scalar_k<MODE>), dim3(1), dim3(1024), 0, g.stream, s->nGroups, (const double*)(MODE == 2 ? s->l1pAp : s->l1rz),
-      (const double*)s->l1rr, s->S, s->rr_hist, s->rz_hist, s->pAp_hist);
-  HIP_CHECK(hipGetLastError());
-}
-
-// one loop body
-static void pcg_body(sb_pcg* s, int k)
-{
-  const uint32_t n = s->nr;
-  const int* stop  = &s->S->stop;
-  if (n) {
-    const dim3 gridV(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * 2u, (n / 2 + 1 + 1023u) / 1024u)));
-    hipLaunchKernelGGL(pcg_update_p_k, gridV, dim3(1024), 0, g.stream, n, (const double*)s->z, s->p, s->x, (const PcgScalars*)s->S,
-        k == 1 ? 1 : 0);
-    HIP_CHECK(hipGetLastError());
-  }
-  if (spmv_dot_kind(s->A)) {
-    launch_spmv(s->A, s->p, s->Ap, s->l1pAp, stop);
-  } else {
-    launch_spmv(s->A, s->p, s->Ap, nullptr, stop);
-    if (n) {
-      hipLaunchKernelGGL(dot_l1_k, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, (const double*)s->p, (const double*)s->Ap,
-          s->l1pAp, stop);
-      HIP_CHECK(hipGetLastError());
-    }
-  }
-  pcg_scalar_launch<2>(s);
-  if (s->sgs) {
-    sgs_residual_and_z(s, false);
-  } else if (n) {
-    hipLaunchKernelGGL(pcg_update_r_k<0>, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, (const double*)s->Ap,
-        (const double*)s->r, s->r, (const double*)s->dinv, s->z, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
-    HIP_CHECK(hipGetLastError());
-  }
-  pcg_scalar_launch<1>(s);
-}
-
-void sb_pcg_start(sb_pcg* s, int itermax, double eps)
-{
-  need_init();
-  need_tree("sb_pcg_start", "PCG", "sb_cg");
-  const int want = std::max(s->hist_cap, itermax + 2);
-  for (double** hist : { &s->rr_hist, &s->rz_hist, &s->pAp_hist }) grow(*hist, s->hist_cap, want, 1);
-  s->hist_cap  = want;
-  PcgScalars h = zeroed<PcgScalars>();
-  h.itermax = itermax, h.eps = eps, h.hist_cap = s->hist_cap;
-  write_block(s->S, &h);
-  // prologue: x0 = 0, p = 1.0 x + 0.0 x = 0, Ap = A p, r = 1.0 b + (-1.0) Ap, z = r o dinv, r.r, r.z, the loop test for k = 1
-  HIP_CHECK(hipMemsetAsync(s->x, 0, (size_t)s->nr * sizeof(double), g.stream));
-  HIP_CHECK(hipMemsetAsync(s->p, 0, (size_t)s->nc * sizeof(double), g.stream));
-  launch_spmv(s->A, s->p, s->Ap, nullptr, nullptr);
-  if (s->sgs) {
-    sgs_residual_and_z(s, true);
-  } else if (s->nr) {
-    hipLaunchKernelGGL(pcg_update_r_k<1>, dim3(vec_stream_grid(s->nr)), dim3(1024), 0, g.stream, s->nr, (const double*)s->Ap,
-        (const double*)s->b, s->r, (const double*)s->dinv, s->z, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
-    HIP_CHECK(hipGetLastError());
-  }
-  pcg_scalar_launch<0>(s);
-  s->k_next = 1;
-  s->clock.begin();
-}
-
-void sb_pcg_run_iters(sb_pcg* s, int iters)
-{
-  need_init();
-  s->clock.need_open("sb_pcg_run_iters", "sb_pcg_start");
-  for (int i = 0; i < iters; i++) pcg_body(s, s->k_next++);
-}
-
-int sb_pcg_finish(sb_pcg* s)
-{
-  need_init();
-  s->clock.need_open("sb_pcg_finish", "sb_pcg_start");
-  s->clock.end();
-  if (s->nr) { // the x update the last body left to "the next p update": nobody comes after it
-    hipLaunchKernelGGL(pcg_x_finalize, dim3(stream_grid(s->nr, 256)), dim3(256), 0, g.stream, s->nr, s->x, (const double*)s->p,
-        (const PcgScalars*)s->S);
-    hipLaunchKernelGGL(pcg_clear_pending, dim3(1), dim3(1), 0, g.stream, s->S);
-    HIP_CHECK(hipGetLastError());
-  }
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  s->clock.read();
-  return read_block(s->S).iters + 1; // the value of k when the for loop exits
-}
-
-int sb_pcg_solve(sb_pcg* s, int itermax, double eps)
-{
-  sb_pcg_start(s, itermax, eps);
-  sb_pcg_run_iters(s, loop_bodies(itermax));
-  return sb_pcg_finish(s);
 }
 
 int sb_pcg_history(const sb_pcg* s, double* rr_out, int rr_cap, double* rz_out, int rz_cap, double* pAp_out, int pAp_cap, int* n_pAp)

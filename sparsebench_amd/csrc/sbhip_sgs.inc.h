@@ -1,7 +1,8 @@
 // sbhip_sgs.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context): the symmetric
 // Gauss-Seidel preconditioner of PCG by multicolouring (kernels: sgs.hip.h).  The handle is an sb_pcg whose `sgs`
 // plan is set: the loop, its control block, histories and every other sb_pcg_* call are sbhip_pcg.inc.h's; what differs is how
-// z is made (the r update without z, nC forward launches, nC - 1 backward launches, r.z by dot_l1_k).
+// z is made (the r update without z, nC forward launches, nC - 1 backward launches, r.z by dot_l1_k: sbhip_pcg_loop.inc.h).
+// The host's one packer of Sell-64 gather structures (sell64_pack) lives here with its first user.
 // ===========================================================================
 // multicolour symmetric Gauss-Seidel
 // ===========================================================================
@@ -10,16 +11,16 @@ struct SgsPlan {
   std::vector<uint32_t> chunk0;  // nC + 1: first chunk of every colour
   std::vector<uint32_t> colour;  // device row order
   uint32_t* rowIdx = nullptr;    // device, nChunks * 64
-  SgsHalf half[2];               // [0] lower / forward, [1] upper / backward; device arrays
+  SellRows half[2];              // [0] lower / forward, [1] upper / backward; device arrays
   double* t = nullptr;           // the forward sums
-  double *ar = nullptr, *at = nullptr, *az = nullptr; // sb_pcg_apply_precond's scratch vectors (first call)
   double structBytes = 0.0;      // the sweep structure as one apply reads it
   double halfBytes[2] = { 0.0, 0.0 }; // each half over all its chunks (a sweep from a guess reads both: sbhip_mg.inc.h)
   uint32_t rowsBackward = 0;     // rows of the colours 0 .. nC - 2
 };
 
 namespace {
-// the matrix in device numbering as rows of (col, val) in storage order, entry for entry as stored (padding included)
+// CSR over device rows, a row's entries in the order they are summed: the matrix in device numbering entry for entry as stored
+// (sgs_download; padding included), or a transfer operator's kept entries (sbhip_mg_fw.inc.h)
 struct HostRows {
   std::vector<size_t> ptr;
   std::vector<uint32_t> col;
@@ -62,6 +63,62 @@ template <class T> T* sgs_to_device(const std::vector<T>& v)
   T* d = (T*)sb_malloc(v.size() * sizeof(T));
   if (!v.empty()) sb_h2d(d, v.data(), v.size() * sizeof(T));
   return d;
+}
+// old row -> device row of a matrix (identity unless Sell-C-sigma permuted)
+std::vector<uint32_t> old_to_device_rows(const sb_matrix* m)
+{
+  std::vector<uint32_t> o2n(m->nr);
+  if (m->fmt == 1 && m->permuted) {
+    if (m->nr) sb_d2h(o2n.data(), m->oldToNew, (size_t)m->nr * sizeof(uint32_t));
+  } else {
+    for (uint32_t i = 0; i < m->nr; i++) o2n[i] = i;
+  }
+  return o2n;
+}
+
+// The one packer of the preconditioners' Sell-64 gather structures (SellRows, sgs.hip.h).  slotRow: per slot (a multiple of 64
+// of them) the row of R it holds, 0xFFFFFFFF for none; keep(i, q): whether entry q of row i goes in.  Per slot the kept
+// entries' count, per chunk their maximum, chunkPtr its prefix sum (handed back: the byte models read it), col / val
+// column-major per chunk in R's order; padding is (+0.0, column 0) and is never used (the lane's own length stops it)
+template <class Keep>
+SellRows sell64_pack(const HostRows& R, const std::vector<uint32_t>& slotRow, Keep keep, std::vector<unsigned long long>& chunkPtr)
+{
+  const size_t slots = slotRow.size(), nChunks = slots / 64u;
+  std::vector<uint32_t> rowLen(slots, 0), chunkLen(nChunks, 0);
+  for (size_t sl = 0; sl < slots; sl++) {
+    const uint32_t i = slotRow[sl];
+    if (i == 0xFFFFFFFFu) continue;
+    uint32_t len = 0;
+    for (size_t q = R.ptr[i]; q < R.ptr[i + 1]; q++) len += keep(i, q) ? 1u : 0u;
+    rowLen[sl]         = len;
+    chunkLen[sl / 64u] = std::max(chunkLen[sl / 64u], len);
+  }
+  chunkPtr.assign(nChunks + 1, 0);
+  for (size_t c = 0; c < nChunks; c++) chunkPtr[c + 1] = chunkPtr[c] + (unsigned long long)chunkLen[c] * 64u;
+  std::vector<uint32_t> col(chunkPtr[nChunks], 0);
+  std::vector<double> val(chunkPtr[nChunks], 0.0);
+  for (size_t sl = 0; sl < slots; sl++) {
+    const uint32_t i = slotRow[sl];
+    if (i == 0xFFFFFFFFu) continue;
+    size_t o = chunkPtr[sl / 64u] + (sl & 63u);
+    for (size_t q = R.ptr[i]; q < R.ptr[i + 1]; q++)
+      if (keep(i, q)) col[o] = R.col[q], val[o] = R.val[q], o += 64;
+  }
+  SellRows S;
+  S.chunkPtr = sgs_to_device(chunkPtr), S.chunkLen = sgs_to_device(chunkLen), S.rowLen = sgs_to_device(rowLen);
+  S.col = sgs_to_device(col), S.val = sgs_to_device(val);
+  return S;
+}
+void sell64_free(SellRows& S)
+{
+  sb_free((void*)S.chunkPtr), sb_free((void*)S.chunkLen), sb_free((void*)S.rowLen), sb_free((void*)S.col), sb_free((void*)S.val);
+  S = {};
+}
+// bytes a kernel reads of `chunks` chunks that hold `elements` elements: val + col per element; chunkPtr, chunkLen per chunk;
+// per slot rowLen alone (4: slot == row) or rowLen and a row index beside it (8)
+double sell64_bytes(unsigned long long elements, size_t chunks, int slotBytes)
+{
+  return (double)elements * 12.0 + (double)chunks * (64.0 * slotBytes + 12.0);
 }
 } // namespace
 
@@ -130,40 +187,19 @@ static SgsPlan* sgs_build(const sb_matrix* m, HostRows h, const char* who)
   }
   P->rowIdx = sgs_to_device(rowIdx);
   // the halves: lower(i) the kept entries whose column's colour is less than colour(i), upper(i) those with a greater one, each
-  // in storage order, column-major per chunk; padding is (+0.0, column 0) and is never used (the lane's own length stops it)
+  // in storage order
   for (int up = 0; up < 2; up++) {
     auto in_half = [&](uint32_t i, size_t q) {
       const uint32_t ci = P->colour[i], cj = P->colour[h.col[q]];
       if (ci == cj) SB_FATAL("%s: device rows %u and %u are adjacent and share colour %u", who, i, h.col[q], ci);
       return up ? cj > ci : cj < ci;
     };
-    std::vector<uint32_t> rowLen(rowIdx.size(), 0), chunkLen(P->nChunks, 0);
-    std::vector<unsigned long long> chunkPtr((size_t)P->nChunks + 1, 0);
-    for (size_t sl = 0; sl < rowIdx.size(); sl++) {
-      const uint32_t i = rowIdx[sl];
-      if (i == 0xFFFFFFFFu) continue;
-      uint32_t len = 0;
-      for (size_t q = h.ptr[i]; q < h.ptr[i + 1]; q++) len += in_half(i, q) ? 1u : 0u;
-      rowLen[sl]       = len;
-      chunkLen[sl / 64] = std::max(chunkLen[sl / 64], len);
-    }
-    for (uint32_t c = 0; c < P->nChunks; c++) chunkPtr[c + 1] = chunkPtr[c] + (unsigned long long)chunkLen[c] * 64u;
-    std::vector<uint32_t> col(chunkPtr[P->nChunks], 0);
-    std::vector<double> val(chunkPtr[P->nChunks], 0.0);
-    for (size_t sl = 0; sl < rowIdx.size(); sl++) {
-      const uint32_t i = rowIdx[sl];
-      if (i == 0xFFFFFFFFu) continue;
-      size_t o = chunkPtr[sl / 64] + (sl & 63u);
-      for (size_t q = h.ptr[i]; q < h.ptr[i + 1]; q++)
-        if (in_half(i, q)) col[o] = h.col[q], val[o] = h.val[q], o += 64;
-    }
-    SgsHalf& H = P->half[up];
-    H.chunkPtr = sgs_to_device(chunkPtr), H.chunkLen = sgs_to_device(chunkLen), H.rowLen = sgs_to_device(rowLen);
-    H.col = sgs_to_device(col), H.val = sgs_to_device(val);
+    std::vector<unsigned long long> chunkPtr;
+    P->half[up] = sell64_pack(h, rowIdx, in_half, chunkPtr);
     // what one apply reads of it: the backward sweep leaves the last colour's chunks alone
     const uint32_t chunksRead = up ? (nC ? P->chunk0[nC - 1] : 0) : P->nChunks;
-    P->structBytes += (double)chunkPtr[chunksRead] * 12.0 + (double)chunksRead * (64.0 * 8.0 + 12.0); // val + col | rowIdx, rowLen, chunkPtr, chunkLen
-    P->halfBytes[up] = (double)chunkPtr[P->nChunks] * 12.0 + (double)P->nChunks * (64.0 * 8.0 + 12.0);
+    P->structBytes += sell64_bytes(chunkPtr[chunksRead], chunksRead, 8);
+    P->halfBytes[up] = sell64_bytes(chunkPtr[P->nChunks], P->nChunks, 8);
   }
   P->t = (double*)sb_malloc((size_t)nr * sizeof(double) + 4096);
   return P;
@@ -173,9 +209,8 @@ static SgsPlan* sgs_build(const sb_matrix* m) { return sgs_build(m, sgs_download
 static void sgs_free_plan(SgsPlan* P)
 {
   if (!P) return;
-  sb_free(P->rowIdx), sb_free(P->t), sb_free(P->ar), sb_free(P->at), sb_free(P->az);
-  for (SgsHalf& H : P->half)
-    sb_free((void*)H.chunkPtr), sb_free((void*)H.chunkLen), sb_free((void*)H.rowLen), sb_free((void*)H.col), sb_free((void*)H.val);
+  sb_free(P->rowIdx), sb_free(P->t);
+  for (SellRows& H : P->half) sell64_free(H);
   delete P;
 }
 static void sgs_release(sb_pcg* s)
@@ -201,27 +236,6 @@ static void sgs_apply(const SgsPlan* P, const double* dinv, const double* r, dou
   sgs_backward(P, dinv, t, z, stop);
   HIP_CHECK(hipGetLastError());
 }
-// the handle's preconditioner: the sweeps of its matrix, or the V-cycle around them
-static void sgs_apply(const sb_pcg* s, const double* r, double* t, double* z, const int* stop)
-{
-  if (s->mg) mg_apply(s, r, t, z, stop);
-  else sgs_apply(s->sgs, (const double*)s->dinv, r, t, z, stop);
-}
-
-// the r update (PRO 1: the prologue's b - Ap) with the r.r values, the apply, the r.z values
-template <int PRO> static void sgs_residual_and_z(sb_pcg* s)
-{
-  const uint32_t n = s->nr;
-  if (!n) return;
-  const int* stop = &s->S->stop; // (0 throughout the prologue: sb_pcg_start has just written the block)
-  hipLaunchKernelGGL(sgs_update_r_k<PRO>, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, (const double*)s->Ap,
-      (const double*)(PRO ? s->b : s->r), s->r, (const PcgScalars*)s->S, s->l1rr);
-  sgs_apply(s, s->r, s->sgs->t, s->z, stop);
-  hipLaunchKernelGGL(dot_l1_k, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, (const double*)s->r, (const double*)s->z, s->l1rz,
-      stop);
-  HIP_CHECK(hipGetLastError());
-}
-static void sgs_residual_and_z(sb_pcg* s, bool prologue) { prologue ? sgs_residual_and_z<1>(s) : sgs_residual_and_z<0>(s); }
 
 sb_pcg* sb_pcg_create_sgs(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host)
 {
@@ -231,82 +245,16 @@ sb_pcg* sb_pcg_create_sgs(const sb_matrix* m, sb_halo* halo, const double* b_hos
   return s;
 }
 
-static bool mg_is_fw(const sb_pcg* s); // (sbhip_mg.inc.h)
-int sb_pcg_precond(const sb_pcg* s) { return s->mg ? (mg_is_fw(s) ? 3 : 2) : s->sgs ? 1 : 0; }
 int sb_pcg_colours(const sb_pcg* s) { return s->sgs ? (int)s->sgs->nC : 0; }
 
 void sb_pcg_colouring(const sb_pcg* s, uint32_t* colour_host)
 {
   need_init();
   if (!s->sgs) SB_FATAL("sb_pcg_colouring: the handle has a diagonal preconditioner (sb_pcg_create_sgs makes the coloured one)");
-  const sb_matrix* m = s->A;
-  if (m->fmt == 1 && m->permuted) {
-    std::vector<uint32_t> o2n(m->nr);
-    if (m->nr) sb_d2h(o2n.data(), m->oldToNew, (size_t)m->nr * sizeof(uint32_t));
-    for (uint32_t i = 0; i < m->nr; i++) colour_host[i] = s->sgs->colour[o2n[i]];
-  } else {
-    std::copy(s->sgs->colour.begin(), s->sgs->colour.end(), colour_host);
-  }
+  const std::vector<uint32_t> o2n = old_to_device_rows(s->A);
+  for (uint32_t i = 0; i < s->A->nr; i++) colour_host[i] = s->sgs->colour[o2n[i]];
 }
 
-void sb_pcg_apply_precond(sb_pcg* s, const double* r_host, double* z_host)
-{
-  need_init();
-  if (s->clock.open) SB_FATAL("sb_pcg_apply_precond between sb_pcg_start and sb_pcg_finish: the solve's vectors are in flight");
-  const uint32_t n = s->nr;
-  if (!n) return;
-  const size_t nb = (size_t)n * sizeof(double) + 4096;
-  if (s->sgs) {
-    SgsPlan* P = s->sgs;
-    if (!P->ar) P->ar = (double*)sb_malloc(nb), P->at = (double*)sb_malloc(nb), P->az = (double*)sb_malloc(nb);
-    upload_permuted(s->A, r_host, P->ar);
-    sgs_apply(s, P->ar, P->at, P->az, zero_flag());
-    HIP_CHECK(hipStreamSynchronize(g.stream));
-    download_original(s->A, P->az, z_host);
-  } else {
-    double *ar = (double*)sb_malloc(nb), *az = (double*)sb_malloc(nb);
-    upload_permuted(s->A, r_host, ar);
-    hipLaunchKernelGGL(precond_diag_k, dim3(stream_grid(n, 256)), dim3(256), 0, g.stream, n, (const double*)ar, (const double*)s->dinv, az);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(g.stream));
-    download_original(s->A, az, z_host);
-    sb_free(ar), sb_free(az);
-  }
-}
-
-// GPU milliseconds of one apply, the mean over `reps` back-to-back applies on the scratch vectors (r = b); for the rate tool
-double sb_pcg_apply_precond_ms(sb_pcg* s, int reps)
-{
-  need_init();
-  if (s->clock.open) SB_FATAL("sb_pcg_apply_precond_ms between sb_pcg_start and sb_pcg_finish: the solve's vectors are in flight");
-  const uint32_t n = s->nr;
-  if (!n || reps < 1) return 0.0;
-  const size_t nb = (size_t)n * sizeof(double) + 4096;
-  double *ar = (double*)sb_malloc(nb), *at = (double*)sb_malloc(nb), *az = (double*)sb_malloc(nb);
-  sb_d2d(ar, s->b, (size_t)n * sizeof(double));
-  LoopClock c;
-  c.create();
-  for (int i = -1; i < reps; i++) { // (i = -1: an untimed first apply)
-    if (i == 0) c.begin();
-    if (s->sgs) sgs_apply(s, ar, at, az, zero_flag());
-    else
-      hipLaunchKernelGGL(precond_diag_k, dim3(stream_grid(n, 256)), dim3(256), 0, g.stream, n, (const double*)ar, (const double*)s->dinv, az);
-  }
-  c.end();
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  c.read();
-  c.destroy();
-  sb_free(ar), sb_free(at), sb_free(az);
-  return (double)c.ms / reps;
-}
-
-// bytes one apply reads and writes.  Diagonal: r, dinv in, z out.  SGS: the sweep structure, and per row forward r, dinv, one
-// gathered z in, t, z out; backward (the rows of every colour but the last) t, dinv, one gathered z in, z out.  MG: mg_bytes
+// bytes one apply reads and writes: the sweep structure, and per row forward r, dinv, one gathered z in, t, z out; backward (the
+// rows of every colour but the last) t, dinv, one gathered z in, z out
 static double sgs_bytes(const SgsPlan* P, uint32_t nr) { return P->structBytes + 40.0 * (double)nr + 32.0 * (double)P->rowsBackward; }
-static double mg_bytes(const sb_pcg* s);
-double sb_pcg_precond_bytes(const sb_pcg* s)
-{
-  if (!s->sgs) return 24.0 * (double)s->nr;
-  return s->mg ? mg_bytes(s) : sgs_bytes(s->sgs, s->nr);
-}

@@ -15,14 +15,49 @@
 
 namespace sbk {
 
-// One half of the sweep structure: lower (forward) or upper (backward) entries of every row, chunk by chunk
-struct SgsHalf {
+// A Sell-64 gather structure: rows in chunks of 64 slots, a wave per chunk, a lane per slot.  The sweeps have two (the lower and
+// the upper entries of every row, chunk by chunk), the V-cycle's transfers one each (mg.hip.h, mg_fw.hip.h); the host's one
+// packer is sell64_pack (sbhip_sgs.inc.h)
+struct SellRows {
   const unsigned long long* chunkPtr; // first element of the chunk in val / col
   const uint32_t* chunkLen;           // longest row of the chunk
-  const uint32_t* rowLen;             // per lane: the row's entries in this half (0 for a lane without a row)
+  const uint32_t* rowLen;             // per slot: the row's own entries (0 for a slot without a row)
   const uint32_t* col;
   const double* val;
 };
+
+// The row loop of every kernel that reads such a structure: s = s - a * z[col] (ADD: s = s + a * z[col]) over a row of `len`
+// entries in storage order; v / ci: the lane's first element of val / col, n: the chunk's length (wave-uniform).  BATCH
+// elements' loads, then their gathers, in flight before their updates: a stencil's half row (13 entries) is one batch of 16, two
+// dependent memory latencies per launch instead of two per entry.  Past the chunk's end the index is clamped to its last element
+// (a line already on its way) and the update is skipped by the lane's own length: padding is skipped, not multiplied (0.0 * inf
+// would be a NaN the contract does not have).  blockDim / gridDim and the early returns stay in the kernels ("One
+// definition per device loop", which also says why sgs_sweep_k below keeps a copy of this loop).
+template <uint32_t BATCH, bool ADD>
+__device__ __forceinline__ double sell_row(uint32_t n, const double* v, const uint32_t* ci, uint32_t len, const double* z, double s)
+{
+  for (uint32_t j = 0; j < n; j += BATCH) {
+    double a[BATCH], zz[BATCH];
+    uint32_t cc[BATCH];
+#pragma unroll
+    for (uint32_t u = 0; u < BATCH; u++) {
+      const size_t e = (size_t)min(j + u, n - 1u) * 64u;
+      a[u] = stream_load(v + e), cc[u] = stream_load(ci + e);
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < BATCH; u++) zz[u] = z[cc[u]];
+#pragma unroll
+    for (uint32_t u = 0; u < BATCH; u++)
+      if (j + u < len) s = ADD ? s + a[u] * zz[u] : s - a[u] * zz[u];
+  }
+  return s;
+}
+// ... over the row in lane `lane` of chunk c of R
+template <uint32_t BATCH, bool ADD>
+__device__ __forceinline__ double sell_row(const SellRows& R, uint32_t c, uint32_t lane, uint32_t len, const double* z, double s)
+{
+  return sell_row<BATCH, ADD>(R.chunkLen[c], R.val + R.chunkPtr[c] + lane, R.col + R.chunkPtr[c] + lane, len, z, s);
+}
 
 // One colour: chunks [chunk0, chunk0 + nChunks) of the structure, a wave per chunk, a lane per row.
 //   BACKWARD 0   s = r_i - sum lower ;  t_i = s ;  z_i = s * dinv_i
@@ -31,7 +66,7 @@ struct SgsHalf {
 // (a padded element gathers z[0] and drops it).  The matrix stream is read once and does not stay in the caches; t, z, dinv do.
 template <int BACKWARD>
 __global__ __launch_bounds__(256) void sgs_sweep_k(uint32_t chunk0, uint32_t nChunks, const uint32_t* __restrict__ rowIdx,
-    SgsHalf H, const double* src, const double* __restrict__ dinv, double* t, double* z, const int* __restrict__ stop)
+    SellRows H, const double* src, const double* __restrict__ dinv, double* t, double* z, const int* __restrict__ stop)
 {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t ch   = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -47,22 +82,21 @@ __global__ __launch_bounds__(256) void sgs_sweep_k(uint32_t chunk0, uint32_t nCh
   const uint32_t* ci  = H.col + H.chunkPtr[c] + lane;
   double s            = live ? src[row] : 0.0;
   const double dv     = live ? dinv[row] : 0.0;
-  // SGS_BATCH elements' loads, then their gathers, in flight before their updates in storage order: a stencil's half row
-  // (13 entries) is one batch, two dependent memory latencies per launch instead of two per entry.  Past the chunk's end the
-  // index is clamped to its last element (a line already on its way) and the update is skipped by the lane's own length.
-  constexpr uint32_t SGS_BATCH = 16;
-  for (uint32_t j = 0; j < n; j += SGS_BATCH) {
-    double a[SGS_BATCH], zz[SGS_BATCH];
-    uint32_t cc[SGS_BATCH];
+  // sell_row<16, false>(n, v, ci, len, z, s), written out: the twin of that loop, to be changed with it.  Called as a function
+  // the loop is compiled ahead of this kernel, its first update stays a branch that the element's loads sink into, and the
+  // kernel takes 86 registers for 78
+  for (uint32_t j = 0; j < n; j += 16u) {
+    double a[16], zz[16];
+    uint32_t cc[16];
 #pragma unroll
-    for (uint32_t u = 0; u < SGS_BATCH; u++) {
+    for (uint32_t u = 0; u < 16u; u++) {
       const size_t e = (size_t)min(j + u, n - 1u) * 64u;
       a[u] = stream_load(v + e), cc[u] = stream_load(ci + e);
     }
 #pragma unroll
-    for (uint32_t u = 0; u < SGS_BATCH; u++) zz[u] = z[cc[u]];
+    for (uint32_t u = 0; u < 16u; u++) zz[u] = z[cc[u]];
 #pragma unroll
-    for (uint32_t u = 0; u < SGS_BATCH; u++)
+    for (uint32_t u = 0; u < 16u; u++)
       if (j + u < len) s = s - a[u] * zz[u];
   }
   if (live) {
@@ -84,6 +118,8 @@ __global__ __launch_bounds__(256) void precond_diag_k(uint32_t n, const double* 
 //   PRO 0   r = r + (-alpha) Ap ;  level-1 values of r.r        (src = r, coefficient S->neg_alpha)
 //   PRO 1   r = b + (-1.0) Ap   ;  the same array: the prologue  (src = b)
 // A wave owns whole aligned 256-row groups, as there; three streams per row (r, Ap in; r out).
+// The twin of pcg_update_r_k (pcg.hip.h), statement for statement less those lines, to be changed with it: as one body with a
+// compile-time switch neither kernel keeps its code.
 // =============================================================================
 template <int PRO>
 __global__ __launch_bounds__(1024) void sgs_update_r_k(uint32_t n, const double* __restrict__ Ap, const double* src, double* r,

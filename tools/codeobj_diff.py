@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of two builds, kernel by kernel.  No GPU needed, nothing is started on one.
 
-  tools/codeobj_diff.py OLD NEW [-v]
+  tools/codeobj_diff.py OLD NEW [-v] [--rename FROM=TO ...]
 
 OLD / NEW: a source tree (its sparsebench_amd/csrc/sbhip.hip is compiled device-only with the Makefile's flags) or a device
 object made that way (hipcc ... --cuda-device-only -c).  Each is unbundled, disassembled and its metadata notes are read;
@@ -13,6 +13,11 @@ then every symbol is classed as
   different     anything else
 Exit status 1 if a symbol is missing on either side or different.  -v prints a unified diff of each symbol that is
 not identical.  DESIGN.md 4.6 says which symbols may be vector-equal.
+
+--rename FROM=TO (repeatable): a type was renamed between OLD and NEW, and kernel symbols carry their parameter types.  FROM is
+replaced by TO in OLD's mangled symbol names and in its notes before the two sides are matched, so a renamed kernel is compared
+with its parent instead of being reported missing twice.  Give the mangled component with its length, e.g. 7SgsHalf=8SellRows
+(the substitution indices S_, S0_, ... behind it do not move: the number of components does not change).
 """
 import collections
 import difflib
@@ -91,14 +96,35 @@ def demangle(names):
     return {n: n for n in names}
 
 
+def renamed(table, renames):
+    """the keys and, where they are text, the values of OLD's table with every FROM replaced by TO"""
+    def sub(t):
+        for old, new in renames:
+            t = t.replace(old, new)
+        return t
+    return {sub(k): sub(v) if isinstance(v, str) else v for k, v in table.items()}
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "-v"]
-    verbose = "-v" in sys.argv[1:]
+    args, renames, verbose = [], [], False
+    argv = sys.argv[1:]
+    while argv:
+        a = argv.pop(0)
+        if a == "-v":
+            verbose = True
+        elif a == "--rename" or a.startswith("--rename="):
+            pair = a[len("--rename="):] if "=" in a else (argv.pop(0) if argv else "")
+            if pair.count("=") != 1 or not all(pair.split("=")):
+                sys.exit("--rename takes FROM=TO, got %r" % pair)
+            renames.append(tuple(pair.split("=")))
+        else:
+            args.append(a)
     if len(args) != 2:
         sys.exit(__doc__)
     with tempfile.TemporaryDirectory() as tmp:
         elfs = [device_elf(p, tmp, t) for p, t in zip(args, ("old", "new"))]
         (fa, fb), (na, nb) = [functions(e) for e in elfs], [notes(e) for e in elfs]
+    fa, na = renamed(fa, renames), renamed(na, renames)
     pretty = demangle(sorted(set(fa) | set(fb)))
     count = collections.Counter()
     for s in sorted(set(fa) | set(fb), key=lambda s: pretty[s]):
