@@ -577,7 +577,7 @@ void sb_pcg_update_r_launch(uint32_t n, uint32_t out[3]);
  * sb_pcg_dinv gives 1 / diag(A).  Square matrix, double precision, one rank, tree dot order; a row without a finite positive
  * diagonal is a fatal error.  The set-up downloads the matrix once and builds the sweep structure on the host. */
 sb_pcg* sb_pcg_create_sgs(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host);
-int sb_pcg_precond(const sb_pcg* s); /* 0 diagonal, 1 SGS, 2 MG, 3 MG with full-weighting transfers (below) */
+int sb_pcg_precond(const sb_pcg* s); /* 0 diagonal, 1 SGS, 2 MG, 3 MG with full-weighting transfers (below), 4 Chebyshev polynomial */
 int sb_pcg_colours(const sb_pcg* s); /* nC; 0 for a diagonal handle */
 void sb_pcg_colouring(const sb_pcg* s, uint32_t* colour_host); /* nr colours, original row order; SGS handles only */
 /* z = M^-1 r once, with the handle's preconditioner (either kind), on host vectors of nr doubles in original row order;
@@ -620,6 +620,35 @@ sb_pcg* sb_pcg_create_mg_p(const sb_matrix* m, sb_halo* halo, const double* b_ho
  * doubles in level l's original row order; zc, rc_out: n_{l+1} doubles in level l + 1's */
 void sb_pcg_mg_fw_probe(sb_pcg* s, int l, const double* r_host, const double* z_host, const double* zc_host, double* d_out,
     double* rc_out, double* z_out);
+
+/* ---- Chebyshev polynomial preconditioning ----
+ * z = q(D^-1 A) D^-1 r, `steps` terms of the Chebyshev recurrence for D^-1 A on [lmin, lmax], lmin = lmax / ratio.  Step 1:
+ * d = z = (r o dinv) * c1.  Step j >= 2: w = A z by the matrix's selected SpMV (any kernel mode), then per row u = r - w,
+ * u = u * dinv, d = (a_j * d) + (b_j * u), z = z + d.  Host doubles, in this order: theta = (lmax + lmin) * 0.5,
+ * delta = (lmax - lmin) * 0.5, sigma = theta / delta, c1 = 1.0 / theta, rho_1 = 1.0 / sigma, rho_j = 1.0 / (2.0 * sigma - rho_{j-1}),
+ * a_j = rho_j * rho_{j-1}, b_j = (2.0 * rho_j) / delta.  No colouring, no structure, no matrix download.
+ * steps: 1 .. 16.  lmax <= 0.0: the bound max_i g_i, g_i the sum in storage order from +0.0 over row i's stored entries of
+ * (|a_e| * sd_i) * sd[col_e], sd = sqrt(dinv): an absolute row sum of D^-1/2 A D^-1/2, computed on the device.  ratio == 0.0: 16.
+ * Fatal errors: steps out of range, a ratio that is not finite and > 1, an lmax that is not finite, a bound that is not finite
+ * and positive, and what sb_pcg_create refuses (a row without a finite positive diagonal names this preconditioner).  The handle
+ * is an sb_pcg: every other sb_pcg_* call works on it, sb_pcg_dinv gives 1 / diag(A), sb_pcg_launches_per_body gives
+ * 5 + 2 (steps - 1) (+ 1 without a fused dot), sb_pcg_precond_bytes (steps - 1) * (sb_matrix_spmv_bytes + 56 per row) + 24 per row. */
+sb_pcg* sb_pcg_create_poly(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int steps, double lmax,
+    double ratio);
+int sb_pcg_poly_steps(const sb_pcg* s);                     /* 0 for a handle of another kind */
+void sb_pcg_poly_interval(const sb_pcg* s, double out[2]);  /* lmin, lmax */
+void sb_pcg_poly_coeffs(const sb_pcg* s, double* out);      /* 2 steps - 1 doubles: c1, then a_j, b_j for j = 2 .. steps */
+void sb_pcg_poly_rowbound(const sb_pcg* s, double* g_host); /* g, nr doubles, original row order */
+/* test entries for the two streaming kernels, blocking; device vectors of n doubles (16-byte aligned), host scalars.
+ * update_r: r = r + nalpha * Ap (pro: r = r + (-1.0) * Ap, the prologue's form), d = z = (r o dinv) * c1, the ceil(n/256) level-1
+ * values of r.r and, with last, of r.z (l1_rz_dev is not touched otherwise).  step: one step j >= 2 from (r, w, dinv, d, z) with
+ * coefficients a, b; with last the level-1 values of r.z */
+void sb_pcg_poly_update_r_native(uint32_t n, int pro, int last, double nalpha, double c1, const double* Ap_dev, double* r_dev,
+    const double* dinv_dev, double* d_dev, double* z_dev, double* l1_rz_dev, double* l1_rr_dev);
+void sb_pcg_poly_step_native(uint32_t n, int last, double a, double b, const double* r_dev, const double* w_dev, const double* dinv_dev,
+    double* d_dev, double* z_dev, double* l1_rz_dev);
+/* their launch over n rows, as sb_pcg_update_r_launch reports its own */
+void sb_pcg_poly_step_launch(uint32_t n, uint32_t out[3]);
 
 /* ---- BiCGStab with a diagonal preconditioner ----------------------------------------------------------- */
 /* Right-preconditioned BiCGStab for matrices that need not be symmetric: two SpMVs per body, about ten vectors whatever the

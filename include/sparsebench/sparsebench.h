@@ -279,6 +279,10 @@ int sbh_solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
  * prints "Preconditioner: MG (V-cycle, full-weighting transfers, multicolour SGS smoother), levels = L, nC = <colours>" */
 int sbh_solve_pcg_mgfw(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
                        CG_UINT sigma, int levels);
+/* sbh_solve_pcg with a Chebyshev polynomial in D^-1 A in the diagonal's place (sb_pcg_create_poly, sbhip.h): steps
+ * terms (1 .. 16; 0: the default 3) on [lmax / 16, lmax], lmax by the row-sum bound of D^-1/2 A D^-1/2.  First prints
+ * "Preconditioner: Chebyshev polynomial, steps = <steps>, lambda in [<lmin>, <lmax>]" */
+int sbh_solve_pcg_poly(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int steps);
 /* the geometric hierarchy's rule: L levels need every dimension divisible by 2^(L-1) and every coarse dimension >= 2.  want: L, or
  * 0 for the deepest L <= 4.  Returns L, or 0 with the reason in why (cap bytes) */
 int sbh_mg_levels(int nx, int ny, int nz, int want, char* why, size_t cap);
@@ -336,6 +340,12 @@ int solvePCGMG(Comm* comm, Parameter* param, Matrix* m);
  * the transfers with which the coarse levels count in every row order.  The same matrices, refusals, printed lines (the
  * preconditioner line says "full-weighting transfers") and return value. */
 int solvePCGMGFW(Comm* comm, Parameter* param, Matrix* m);
+/* solvePCG with a Chebyshev polynomial preconditioner: z = q(D^-1 A) D^-1 r, three terms of the Chebyshev recurrence
+ * on [lmax / 16, lmax], each term behind the first one SpMV of the matrix's own and a streaming kernel; no colouring, no set-up
+ * beyond a row-sum bound for lmax.  Prints the preconditioner, its steps and interval, then solvePCG's lines; returns k as solveCG
+ * does.  Square matrix, one rank, tree dot order; a row without a finite positive diagonal entry ends the process with a message;
+ * the single-precision libraries export it too and end the process with "PCG: double precision only". */
+int solvePCGPoly(Comm* comm, Parameter* param, Matrix* m);
 /* Jacobi-preconditioned BiCGStab: the short-recurrence solver for matrices that are not symmetric; returns k as
  * solveCG does.  The single-precision libraries export it too and end the process with "BiCGStab: double precision only". */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m);

@@ -1,16 +1,18 @@
 // sbhip_pcg_loop.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context): the loop
 // of preconditioned CG and the one place that asks how the handle's z is made: the diagonal (riding in the r
-// update), the sweeps (sbhip_sgs.inc.h) or the V-cycle (sbhip_mg.inc.h, sbhip_mg_fw.inc.h).
+// update), the sweeps (sbhip_sgs.inc.h), the V-cycle (sbhip_mg.inc.h, sbhip_mg_fw.inc.h) or the
+// Chebyshev polynomial (sbhip_poly.inc.h).
 // Included behind those files, so nothing here is declared ahead of its definition; the handle is sbhip_pcg.inc.h's.
 // ===========================================================================
 // preconditioned CG: z and the loop
 // ===========================================================================
-int sb_pcg_precond(const sb_pcg* s) { return s->mg ? (s->mg->fw ? 3 : 2) : s->sgs ? 1 : 0; }
+int sb_pcg_precond(const sb_pcg* s) { return s->poly ? 4 : s->mg ? (s->mg->fw ? 3 : 2) : s->sgs ? 1 : 0; }
 
 // z = M^-1 r with the handle's preconditioner: r o dinv, the sweeps of its matrix, or the V-cycle around them (t: the forward
-// sums of level 0; the diagonal does not touch it)
+// sums of level 0; the diagonal does not touch it), or the polynomial on the handle's own d and w
 static void precond_apply(const sb_pcg* s, const double* r, double* t, double* z, const int* stop)
 {
+  if (s->poly) return poly_apply(s->A, (const double*)s->dinv, s->poly->c, r, z, s->poly->d, s->poly->w, stop);
   if (s->mg) return mg_apply(s, r, t, z, stop);
   if (s->sgs) return sgs_apply(s->sgs, (const double*)s->dinv, r, t, z, stop);
   if (!s->nr) return;
@@ -19,7 +21,8 @@ static void precond_apply(const sb_pcg* s, const double* r, double* t, double* z
 }
 
 // the r update (PRO 1: the prologue's b - Ap) with the r.r values, z and the r.z values.  The diagonal: all of it in
-// pcg_update_r_k.  Sweeps and V-cycle: the r update without z, the apply, r.z by dot_l1_k
+// pcg_update_r_k.  Sweeps and V-cycle: the r update without z, the apply, r.z by dot_l1_k.  The polynomial: step 1 in
+// poly_update_r_k, the steps behind it by poly_steps, the last of them with the r.z values
 template <int PRO> static void pcg_residual_and_z(sb_pcg* s)
 {
   const uint32_t n = s->nr;
@@ -27,7 +30,16 @@ template <int PRO> static void pcg_residual_and_z(sb_pcg* s)
   const int* stop   = &s->S->stop; // (0 throughout the prologue: sb_pcg_start has just written the block)
   const double* src = PRO ? s->b : s->r;
   const dim3 grid(vec_stream_grid(n)), block(1024);
-  if (!s->sgs) {
+  if (s->poly) {
+    const PolyPlan* P = s->poly;
+    if (P->c.steps == 1)
+      hipLaunchKernelGGL((poly_update_r_k<PRO, 1>), grid, block, 0, g.stream, n, (const double*)s->Ap, src, s->r, (const double*)s->dinv,
+          P->d, s->z, P->c.c1, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
+    else
+      hipLaunchKernelGGL((poly_update_r_k<PRO, 0>), grid, block, 0, g.stream, n, (const double*)s->Ap, src, s->r, (const double*)s->dinv,
+          P->d, s->z, P->c.c1, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
+    poly_steps(s->A, (const double*)s->dinv, P->c, s->r, s->z, P->d, P->w, stop, s->l1rz);
+  } else if (!s->sgs) {
     hipLaunchKernelGGL(pcg_update_r_k<PRO>, grid, block, 0, g.stream, n, (const double*)s->Ap, src, s->r, (const double*)s->dinv, s->z,
         (const PcgScalars*)s->S, s->l1rz, s->l1rr);
   } else {
@@ -39,9 +51,10 @@ template <int PRO> static void pcg_residual_and_z(sb_pcg* s)
   HIP_CHECK(hipGetLastError());
 }
 
-// bytes one apply reads and writes.  Diagonal: r, dinv in, z out.  SGS: sgs_bytes.  MG: mg_bytes
+// bytes one apply reads and writes.  Diagonal: r, dinv in, z out.  SGS: sgs_bytes.  MG: mg_bytes.  Polynomial: poly_bytes
 double sb_pcg_precond_bytes(const sb_pcg* s)
 {
+  if (s->poly) return poly_bytes(s);
   if (!s->sgs) return 24.0 * (double)s->nr;
   return s->mg ? mg_bytes(s) : sgs_bytes(s->sgs, s->nr);
 }
@@ -90,6 +103,7 @@ void sb_pcg_free(sb_pcg* s)
   if (!s) return;
   HIP_CHECK(hipStreamSynchronize(g.stream));
   s->clock.destroy();
+  poly_release(s);
   mg_release(s);
   sgs_release(s);
   sb_free(s->r), sb_free(s->z), sb_free(s->p), sb_free(s->Ap), sb_free(s->x), sb_free(s->b), sb_free(s->dinv), sb_free(s->xexact);
@@ -100,9 +114,11 @@ void sb_pcg_free(sb_pcg* s)
 // launches per loop body: p update | SpMV (+ p.Ap values) | alpha | r update (+ z, r.z and r.r values) | beta = 5 where the
 // selected SpMV kernel has a fused dot; native CRS and generic C add the dot pass: 6.  An SGS handle: the r update makes no z;
 // nC forward and nC - 1 backward launches and the r.z pass stand in between it and beta: 2 nC + 5 (+ 1).  An MG handle: the
-// V-cycle's launches in the sweeps' place: 6 (+ 1) + mg_apply_launches
+// V-cycle's launches in the sweeps' place: 6 (+ 1) + mg_apply_launches.  A polynomial handle: step 1 rides in the r update, the
+// last step makes the r.z values; an SpMV and a step kernel per step behind the first: 5 (+ 1) + 2 (steps - 1)
 int sb_pcg_launches_per_body(const sb_pcg* s)
 {
+  if (s->poly) return (spmv_dot_kind(s->A) ? 5 : 6) + 2 * (s->poly->c.steps - 1);
   if (s->mg) return (spmv_dot_kind(s->A) ? 6 : 7) + mg_apply_launches(s);
   return (spmv_dot_kind(s->A) ? 5 : 6) + (s->sgs ? 2 * sb_pcg_colours(s) : 0);
 }

@@ -84,6 +84,8 @@ int solvePCGMGFW(Comm* comm, Parameter* param, Matrix* m)
   return sbh_solve_pcg_mgfw(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, 0);
 #endif
 }
+/* solvePCG with the Chebyshev polynomial preconditioner at its default steps */
+int solvePCGPoly(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_pcg_poly(comm, param, m->dev, m->nr, m->rowNnz, 0); }
 /* Jacobi-preconditioned BiCGStab on this build's Matrix (the _sp libraries: "BiCGStab: double precision only") */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_bicgstab(comm, param, m->dev, m->nr, m->rowNnz); }
 

@@ -32,6 +32,8 @@ static const char* kHelp =
     "  -p mg      Multigrid V-cycle with the sgs smoother as the preconditioner of -t pcg (generated matrices).\n"
     "  -p mgfw    The same with full-weighting transfers: trilinear interpolation and its scaled transpose.\n"
     "  -l <int>   Levels of -p mg and -p mgfw. Default the deepest of up to 4 that the grid allows.\n"
+    "  -p poly    Chebyshev polynomial in D^-1 A as the preconditioner of -t pcg: one SpMV per step behind the first.\n"
+    "  -d <int>   Steps of -p poly, 1 to 16. Default 3.\n"
     "  -r <int>   GMRES restart length. Default 30.\n"
     "  -n <int>   Number of right-hand sides for -t cg. Default 1.\n"
     "  -x <int>   Size in x for generated matrix, ignored if MM file is loaded. Default 100.\n"
@@ -62,10 +64,11 @@ int main(int argc, char** argv)
   int type = CG, opt;
   unsigned scsC = 64, scsSigma = 1;
   int restart = 30, nrhs = 1;
-  int precond = -1; /* -p: 0 jacobi, 1 sgs, 2 mg, 3 mgfw; -1 not given */
+  int precond = -1; /* -p: 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly; -1 not given */
   int levels  = 0;  /* -l: levels of -p mg; 0 not given (the deepest of up to 4) */
+  int steps   = 0;  /* -d: steps of -p poly; 0 not given (3) */
   opterr = 0;
-  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:p:l:")) != -1) switch (opt) {
+  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:p:l:d:")) != -1) switch (opt) {
     case 'h':
       if (commIsMaster(&comm)) printf("%s", kHelp);
       commAbort(&comm, "");
@@ -107,6 +110,7 @@ int main(int argc, char** argv)
       else if (strcmp(optarg, "sgs") == 0) precond = 1;
       else if (strcmp(optarg, "mg") == 0) precond = 2;
       else if (strcmp(optarg, "mgfw") == 0) precond = 3;
+      else if (strcmp(optarg, "poly") == 0) precond = 4;
       else {
         fprintf(stderr, "Unknown preconditioner %s (-p <jacobi|sgs>)\n", optarg);
         return 1;
@@ -116,6 +120,13 @@ int main(int argc, char** argv)
       levels = atoi(optarg);
       if (levels < 1) {
         fprintf(stderr, "-l <int> (the levels of -p mg) must be 1 or more, got %s\n", optarg);
+        return 1;
+      }
+      break;
+    case 'd':
+      steps = atoi(optarg);
+      if (steps < 1 || steps > 16) {
+        fprintf(stderr, "-d <int> (the steps of -p poly) must be 1 to 16, got %s\n", optarg);
         return 1;
       }
       break;
@@ -135,6 +146,10 @@ int main(int argc, char** argv)
   }
   if (levels != 0 && precond != 2 && precond != 3) {
     fprintf(stderr, "-l <int> (the levels) goes with -p mg only\n");
+    return 1;
+  }
+  if (steps != 0 && precond != 4) {
+    fprintf(stderr, "-d <int> (the steps) goes with -p poly only\n");
     return 1;
   }
   if (precond == 2 || precond == 3) { /* refused before the set-up: a file has no grid, a grid may not allow the levels */
@@ -203,6 +218,8 @@ int main(int argc, char** argv)
 #else
       k = sbh_solve_pcg_mgfw(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels);
 #endif
+    } else if (precond == 4) { /* (prints "Preconditioner: Chebyshev polynomial, steps = ..., lambda in [...]" itself) */
+      k = steps == 0 ? solvePCGPoly(&comm, &param, &sm) : sbh_solve_pcg_poly(&comm, &param, sm.dev, sm.nr, sm.rowNnz, steps);
     } else {
       if (commIsMaster(&comm)) printf("Preconditioner: Jacobi (diagonal), nC = 0\n");
       k = solvePCG(&comm, &param, &sm);

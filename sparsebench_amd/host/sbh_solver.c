@@ -328,6 +328,19 @@ int sbh_solve_pcg_sgs(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr
 {
   return solve_pcg(comm, param, dev_matrix, nr, rowNnz, 1);
 }
+/* ... or with the Chebyshev polynomial in D^-1 A; steps 0: the default.  Names its steps and interval first */
+int sbh_solve_pcg_poly(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int steps)
+{
+  dp_only("PCG: double precision only\n");
+  double *b, *xexact;
+  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
+  sb_pcg* s = sb_pcg_create_poly((const sb_matrix*)dev_matrix, NULL, b, xexact, steps ? steps : 3, 0.0, 0.0);
+  double iv[2];
+  sb_pcg_poly_interval(s, iv);
+  if (commIsMaster(comm))
+    printf("Preconditioner: Chebyshev polynomial, steps = %d, lambda in [%.6g, %.6g]\n", sb_pcg_poly_steps(s), iv[0], iv[1]);
+  return run_pcg(comm, param, s, b, xexact);
+}
 
 /* ---- solvePCGMG --------------------------------------------------------------------------- */
 /* solvePCGSGS with the multigrid V-cycle around the smoother on the generated grid's own hierarchy (sbh_mg.c).

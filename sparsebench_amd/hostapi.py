@@ -6,6 +6,7 @@ commPartition -> convertMatrix -- through the flat surface in host/sbh_flat.c, a
 Python, and nothing here falls back to the CPU.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -620,16 +621,22 @@ class PCG(_BodySolver):
     `levels` for a generated problem's own geometric hierarchy (None: the deepest of up to 4 the grid allows), or
     `coarse=[(Problem, f2c), ...]` for the caller's.  precond "mgfw": that cycle with full-weighting transfers:
     `levels` for the generated hierarchy with the trilinear P and omega = 0.5, or `coarse=[(Problem, P, omega), ...]` with P a
-    scipy.sparse matrix or a (ptr, col, val) CSR triple of n_l x n_{l+1}.  Double precision, one rank, tree dot order."""
+    scipy.sparse matrix or a (ptr, col, val) CSR triple of n_l x n_{l+1}.  precond "poly": a Chebyshev polynomial in D^-1 A
+    (DESIGN 4.15): `steps` terms (1 .. 16, default 3) on [lmax / ratio, lmax]; lmax None: the row-sum bound of D^-1/2 A D^-1/2,
+    ratio default 16.0; takes no dinv.  Double precision, one rank, tree dot order."""
 
     PREFIX, NAME = "sb_pcg", "PCG"
     COUNTERS = ("stop", "stop_next", "iters", "n_rr", "n_pAp")
 
-    def __init__(self, problem, dinv=None, precond="jacobi", levels=None, coarse=None):
+    def __init__(self, problem, dinv=None, precond="jacobi", levels=None, coarse=None, steps=None, lmax=None, ratio=None):
         self._need_double(problem)
-        if precond not in ("jacobi", "sgs", "mg", "mgfw"):
-            raise ValueError("precond must be 'jacobi' or 'sgs' or 'mg' or 'mgfw', got %r" % (precond,))
-        if precond in ("sgs", "mg", "mgfw") and dinv is not None:
+        if precond not in ("jacobi", "sgs", "mg", "mgfw", "poly"):
+            raise ValueError("precond must be 'jacobi' or 'sgs' or 'mg' or 'mgfw' or 'poly', got %r" % (precond,))
+        if precond != "poly" and (steps is not None or lmax is not None or ratio is not None):
+            raise ValueError("steps, lmax and ratio go with precond='poly' only")
+        if precond == "poly":
+            steps, lmax, ratio = self._poly_args(steps, lmax, ratio)
+        if precond in ("sgs", "mg", "mgfw", "poly") and dinv is not None:
             raise ValueError("precond=%r takes no dinv: its diagonal is the matrix's own" % (precond,))
         if precond not in ("mg", "mgfw") and (levels is not None or coarse is not None):
             raise ValueError("levels and coarse go with precond='mg' only, or with 'mgfw'")
@@ -647,8 +654,23 @@ class PCG(_BodySolver):
         b, xe = self._open(problem)
         if precond == "sgs":
             self.ptr = self.L.sb_pcg_create_sgs(problem.matrix, problem.halo, _ptr(b), _ptr(xe))
+        elif precond == "poly":
+            self.ptr = self.L.sb_pcg_create_poly(problem.matrix, problem.halo, _ptr(b), _ptr(xe), steps, lmax, ratio)
         else:
             self.ptr = self.L.sb_pcg_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), _ptr(self._dinv_arg(dinv)))
+
+    @staticmethod
+    def _poly_args(steps, lmax, ratio):
+        """(steps, lmax, ratio) as sb_pcg_create_poly takes them (lmax 0.0: the bound), refused here where it would refuse them"""
+        steps = 3 if steps is None else steps
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= 16:
+            raise ValueError("steps must be an integer from 1 to 16, got %r" % (steps,))
+        ratio = 16.0 if ratio is None else float(ratio)
+        if not (1.0 < ratio < math.inf):
+            raise ValueError("ratio (lmax / lmin) must be finite and greater than 1, got %r" % (ratio,))
+        if lmax is not None and not (0.0 < float(lmax) < math.inf):
+            raise ValueError("lmax must be finite and positive (None: the row-sum bound), got %r" % (lmax,))
+        return int(steps), 0.0 if lmax is None else float(lmax), ratio
 
     def _create_mg(self, problem, levels, coarse, fw=False):
         """coarse: [(Problem, f2c), ...], level l + 1's problem and the rows of level l that are its points (original numbering);
@@ -725,8 +747,35 @@ class PCG(_BodySolver):
         self._free_owned()
 
     def precond(self):
-        """"jacobi" (any diagonal), "sgs", "mg" or "mgfw" """
-        return ("jacobi", "sgs", "mg", "mgfw")[self.L.sb_pcg_precond(self.ptr)]
+        """"jacobi" (any diagonal), "sgs", "mg", "mgfw" or "poly" """
+        return ("jacobi", "sgs", "mg", "mgfw", "poly")[self.L.sb_pcg_precond(self.ptr)]
+
+    def steps(self):
+        """steps of a polynomial handle; 0 for the other kinds"""
+        return self.L.sb_pcg_poly_steps(self.ptr)
+
+    def _need_poly(self, what):
+        if self.steps() == 0:
+            raise ValueError("%s: the handle's preconditioner is %r, not 'poly'" % (what, self.precond()))
+
+    def interval(self):
+        """(lmin, lmax) of a polynomial handle"""
+        self._need_poly("interval")
+        out = np.zeros(2)
+        self.L.sb_pcg_poly_interval(self.ptr, out.ctypes.data_as(vp))
+        return float(out[0]), float(out[1])
+
+    def coeffs(self):
+        """c1, then a_j, b_j for j = 2 .. steps: 2 steps - 1 doubles"""
+        self._need_poly("coeffs")
+        out = np.zeros(2 * self.steps() - 1)
+        self.L.sb_pcg_poly_coeffs(self.ptr, out.ctypes.data_as(vp))
+        return out
+
+    def rowbound(self):
+        """g of the bound on lmax, original row order: the absolute row sums of D^-1/2 A D^-1/2"""
+        self._need_poly("rowbound")
+        return self._vector("poly_rowbound")
 
     def levels(self):
         """L of an MG handle; 1 for SGS, 0 for a diagonal one"""
