@@ -577,7 +577,8 @@ void sb_pcg_update_r_launch(uint32_t n, uint32_t out[3]);
  * sb_pcg_dinv gives 1 / diag(A).  Square matrix, double precision, one rank, tree dot order; a row without a finite positive
  * diagonal is a fatal error.  The set-up downloads the matrix once and builds the sweep structure on the host. */
 sb_pcg* sb_pcg_create_sgs(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host);
-int sb_pcg_precond(const sb_pcg* s); /* 0 diagonal, 1 SGS, 2 MG, 3 MG with full-weighting transfers (below), 4 Chebyshev polynomial */
+int sb_pcg_precond(const sb_pcg* s); /* 0 diagonal, 1 SGS, 2 MG, 3 MG with full-weighting transfers (below), 4 Chebyshev polynomial,
+                                        5 Chebyshev-smoothed MG */
 int sb_pcg_colours(const sb_pcg* s); /* nC; 0 for a diagonal handle */
 void sb_pcg_colouring(const sb_pcg* s, uint32_t* colour_host); /* nr colours, original row order; SGS handles only */
 /* z = M^-1 r once, with the handle's preconditioner (either kind), on host vectors of nr doubles in original row order;
@@ -649,6 +650,36 @@ void sb_pcg_poly_step_native(uint32_t n, int last, double a, double b, const dou
     double* d_dev, double* z_dev, double* l1_rz_dev);
 /* their launch over n rows, as sb_pcg_update_r_launch reports its own */
 void sb_pcg_poly_step_launch(uint32_t n, uint32_t out[3]);
+
+/* ---- the V-cycle with the Chebyshev polynomial as its smoother ----
+ * z = V(0, r) on levels 0 .. nCoarse with the hierarchy arguments of sb_pcg_create_mg_p.  V(l, r): z = the polynomial apply above
+ * on level l from zero (`steps` steps; the last level `coarse_steps`, 0: as many as steps) and, unless l is the last level:
+ * w = A_l z by the level's selected SpMV; rc_c = omega_l * s with s = +0.0 and s = s + w_e * (r[row_e] - w[row_e]) over row c of
+ * P_l^T in ascending original fine row number (no residual vector is written); zc = V(l + 1, rc); z = z + P_l zc as
+ * sb_pcg_create_mg_p prolongs; then `steps` steps from that guess: w = A_l z, per row u = r - w, u = u * dinv, d = u * c1,
+ * z = z + d, and steps j >= 2 exactly as the polynomial's.  Per level dinv = 1 / diag, the interval [lmax_l / ratio, lmax_l] with
+ * lmax_l the row-sum bound of that level's matrix (lmax <= 0.0) or the caller's lmax on every level, and the coefficients by the
+ * formulas above.  ratio == 0.0: 4.  No colouring, no matrix download: sb_pcg_colours gives 0.  Fatal errors, by name and level:
+ * what sb_pcg_create_mg_p and sb_pcg_create_poly refuse.  nCoarse = 0 is sb_pcg_create_poly with coarse_steps steps bit for bit.
+ * sb_pcg_precond gives 5, sb_pcg_poly_steps `steps`; the level queries work; sb_pcg_launches_per_body gives
+ * 4 + nCoarse * (4 steps + 2) + 2 coarse_steps - 1 (+ 1 without a fused dot); sb_pcg_precond_bytes per level but the last
+ * 2 steps * sb_matrix_spmv_bytes + (2 (steps - 1) * 56 + 48 + 24) per row + both transfer structures + 32 per row + 16 per coarse
+ * row, the last level as the polynomial's. */
+sb_pcg* sb_pcg_create_mg_poly(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int nCoarse,
+    const sb_matrix* const* coarse, const uint64_t* const* p_ptr, const uint32_t* const* p_col, const double* const* p_val,
+    const double* omega, int steps, int coarse_steps, double lmax, double ratio);
+int sb_pcg_mg_poly_level_steps(const sb_pcg* s, int l);               /* steps; on the last level coarse_steps */
+void sb_pcg_mg_poly_interval(const sb_pcg* s, int l, double out[2]);  /* lmin, lmax of level l */
+void sb_pcg_mg_poly_coeffs(const sb_pcg* s, int l, double* out);      /* level l's c1, then a_j, b_j: 2 (its steps) - 1 doubles */
+/* test entries, blocking, on scratch vectors; the probe is refused between sb_pcg_start and sb_pcg_finish.  probe: the transfers
+ * of level l alone (l + 1 < levels): rc_out = omega_l P_l^T (r - w) and z_out = z + P_l zc.  r, w, z, z_out: n_l doubles in level
+ * l's original row order; zc, rc_out: n_{l+1} doubles in level l + 1's.  first: step 1 of the post-smoothing on device vectors of
+ * n doubles (16-byte aligned): d = ((r - w) * dinv) * c1, z = z + d and, with last, the ceil(n/256) level-1 values of r.z */
+void sb_pcg_mg_poly_probe(sb_pcg* s, int l, const double* r_host, const double* w_host, const double* z_host, const double* zc_host,
+    double* rc_out, double* z_out);
+void sb_pcg_mg_poly_first_native(uint32_t n, int last, double c1, const double* r_dev, const double* w_dev, const double* dinv_dev,
+    double* d_dev, double* z_dev, double* l1_rz_dev);
+void sb_pcg_mg_poly_first_launch(uint32_t n, uint32_t out[3]);
 
 /* ---- BiCGStab with a diagonal preconditioner ----------------------------------------------------------- */
 /* Right-preconditioned BiCGStab for matrices that need not be symmetric: two SpMVs per body, about ten vectors whatever the

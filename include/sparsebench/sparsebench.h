@@ -279,6 +279,12 @@ int sbh_solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
  * prints "Preconditioner: MG (V-cycle, full-weighting transfers, multicolour SGS smoother), levels = L, nC = <colours>" */
 int sbh_solve_pcg_mgfw(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
                        CG_UINT sigma, int levels);
+/* sbh_solve_pcg_mgfw with the Chebyshev polynomial as the smoother of every level (sb_pcg_create_mg_poly, sbhip.h):
+ * the regenerated hierarchy, the trilinear prolongation with omega = 0.25, steps per smoothing (1 .. 16; 0: the default 2) on
+ * [lmax_l / 4, lmax_l] per level; the same depth rules and refusals.  First prints "Preconditioner: MG (V-cycle, full-weighting
+ * transfers, Chebyshev polynomial smoother), levels = L, steps = <steps>, lambda in [<lmin>, <lmax> of level 0]" */
+int sbh_solve_pcg_mgpoly(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+                         CG_UINT sigma, int levels, int steps);
 /* sbh_solve_pcg with a Chebyshev polynomial in D^-1 A in the diagonal's place (sb_pcg_create_poly, sbhip.h): steps
  * terms (1 .. 16; 0: the default 3) on [lmax / 16, lmax], lmax by the row-sum bound of D^-1/2 A D^-1/2.  First prints
  * "Preconditioner: Chebyshev polynomial, steps = <steps>, lambda in [<lmin>, <lmax>]" */
@@ -346,6 +352,10 @@ int solvePCGMGFW(Comm* comm, Parameter* param, Matrix* m);
  * does.  Square matrix, one rank, tree dot order; a row without a finite positive diagonal entry ends the process with a message;
  * the single-precision libraries export it too and end the process with "PCG: double precision only". */
 int solvePCGPoly(Comm* comm, Parameter* param, Matrix* m);
+/* solvePCGMGFW with that polynomial as the smoother of every level in the Gauss-Seidel sweeps' place: two steps
+ * before and after on every level, omega = 0.25, every SpMV of the cycle the level's own; no colouring.  The same matrices and
+ * refusals; the preconditioner line names the smoother, its steps and level 0's interval. */
+int solvePCGMGPoly(Comm* comm, Parameter* param, Matrix* m);
 /* Jacobi-preconditioned BiCGStab: the short-recurrence solver for matrices that are not symmetric; returns k as
  * solveCG does.  The single-precision libraries export it too and end the process with "BiCGStab: double precision only". */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m);

@@ -58,6 +58,8 @@ SYMBOLS = [
     "sb_pcg_create_mg_p", "sb_pcg_mg_fw_probe",
     "sb_pcg_create_poly", "sb_pcg_poly_steps", "sb_pcg_poly_interval", "sb_pcg_poly_coeffs", "sb_pcg_poly_rowbound",
     "sb_pcg_poly_update_r_native", "sb_pcg_poly_step_native", "sb_pcg_poly_step_launch",
+    "sb_pcg_create_mg_poly", "sb_pcg_mg_poly_level_steps", "sb_pcg_mg_poly_interval", "sb_pcg_mg_poly_coeffs", "sb_pcg_mg_poly_probe",
+    "sb_pcg_mg_poly_first_native", "sb_pcg_mg_poly_first_launch",
     "sb_bicgstab_create", "sb_bicgstab_free", "sb_bicgstab_solve", "sb_bicgstab_start", "sb_bicgstab_run_iters", "sb_bicgstab_finish",
     "sb_bicgstab_history", "sb_bicgstab_solution", "sb_bicgstab_check_residual", "sb_bicgstab_dinv", "sb_bicgstab_launches_per_body",
     "sb_bicgstab_loop_ms", "sb_bicgstab_counters", "sb_bicgstab_update_p_native", "sb_bicgstab_update_s_native",
@@ -307,6 +309,13 @@ def load():
         "sb_pcg_poly_update_r_native": (None, [u32, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp]),
         "sb_pcg_poly_step_native": (None, [u32, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]),
         "sb_pcg_poly_step_launch": (None, [u32, vp]),
+        "sb_pcg_create_mg_poly": (vp, [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double]),
+        "sb_pcg_mg_poly_level_steps": (C.c_int, [vp, C.c_int]),
+        "sb_pcg_mg_poly_interval": (None, [vp, C.c_int, vp]),
+        "sb_pcg_mg_poly_coeffs": (None, [vp, C.c_int, vp]),
+        "sb_pcg_mg_poly_probe": (None, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),
+        "sb_pcg_mg_poly_first_native": (None, [u32, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp]),
+        "sb_pcg_mg_poly_first_launch": (None, [u32, vp]),
         # BiCGStab with a diagonal preconditioner
         "sb_bicgstab_create": (vp, [vp, vp, vp, vp, C.c_int, vp]),
         "sb_bicgstab_free": (None, [vp]),

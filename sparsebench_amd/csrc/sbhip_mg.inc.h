@@ -35,6 +35,7 @@ struct MgFwArgs {
   const double* omega;
 };
 static void mg_fw_check(const char* fn, const MgFwArgs& a, int l, uint32_t nFine, uint32_t nCoarseRows);
+static void mg_fw_transfers(MgLevel& F, const sb_matrix* coarse, const MgFwArgs& a, int l);
 static void mg_fw_build(MgLevel& F, const sb_matrix* coarse, const MgFwArgs& a, int l);
 static void mg_fw_free(MgLevel& V);
 static void mg_fw_restrict(const MgLevel& V, const double* r, const double* z, double* rc, const int* stop);
@@ -158,11 +159,11 @@ static double mg_bytes(const sb_pcg* s)
   return b;
 }
 
-// fn: the entry point as messages name it.  fw NULL: injection by f2c_host; else its prolongations (f2c_host NULL)
-static sb_pcg* mg_create(const char* fn, const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int nCoarse,
-    const sb_matrix* const* coarse, const uint32_t* const* f2c_host, const MgFwArgs* fw)
+// every refusal of a caller's hierarchy, before anything is built.  fn: the entry point as messages name it.  fw NULL: injection
+// by f2c_host; else its prolongations (f2c_host NULL)
+static void mg_check_hierarchy(const char* fn, const sb_matrix* m, int nCoarse, const sb_matrix* const* coarse,
+    const uint32_t* const* f2c_host, const MgFwArgs* fw)
 {
-  need_init();
   if (nCoarse < 0) SB_FATAL("%s: nCoarse = %d: the number of coarse levels cannot be negative", fn, nCoarse);
   if (nCoarse > 0 && (!coarse || (fw ? !fw->ptr || !fw->col || !fw->val || !fw->omega : !f2c_host)))
     SB_FATAL("%s: %d coarse levels need their matrices and %s", fn, nCoarse, fw ? "prolongations" : "injection maps");
@@ -182,6 +183,14 @@ static sb_pcg* mg_create(const char* fn, const sb_matrix* m, sb_halo* halo, cons
   }
   if (fw)
     for (int l = 0; l < nCoarse; l++) mg_fw_check(fn, *fw, l, l ? coarse[l - 1]->nr : m->nr, coarse[l]->nr);
+}
+
+// fn, f2c_host, fw: as mg_check_hierarchy takes them
+static sb_pcg* mg_create(const char* fn, const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int nCoarse,
+    const sb_matrix* const* coarse, const uint32_t* const* f2c_host, const MgFwArgs* fw)
+{
+  need_init();
+  mg_check_hierarchy(fn, m, nCoarse, coarse, f2c_host, fw);
   char who[64];
   snprintf(who, sizeof who, "MG (level %d)", 0);
   sb_pcg* s = pcg_create(m, halo, b_host, xexact_host, nullptr, fn, who);
@@ -218,7 +227,11 @@ sb_pcg* sb_pcg_create_mg(const sb_matrix* m, sb_halo* halo, const double* b_host
   return mg_create("sb_pcg_create_mg", m, halo, b_host, xexact_host, nCoarse, coarse, f2c_host, nullptr);
 }
 
-int sb_pcg_levels(const sb_pcg* s) { return s->mg ? (int)s->mg->lev.size() : s->sgs ? 1 : 0; }
+// (sbhip_mg_poly.inc.h) the levels of a Chebyshev-smoothed cycle, which has no SgsPlan: no colours
+static int mgp_levels(const sb_pcg* s);
+static uint32_t mgp_level_rows(const sb_pcg* s, int l);
+
+int sb_pcg_levels(const sb_pcg* s) { return s->mgp ? mgp_levels(s) : s->mg ? (int)s->mg->lev.size() : s->sgs ? 1 : 0; }
 static const SgsPlan* mg_level_plan(const sb_pcg* s, int l, const char* fn)
 {
   if (l < 0 || l >= sb_pcg_levels(s)) SB_FATAL("%s: level %d of a handle with %d levels", fn, l, sb_pcg_levels(s));
@@ -227,6 +240,10 @@ static const SgsPlan* mg_level_plan(const sb_pcg* s, int l, const char* fn)
 uint32_t sb_pcg_level_rows(const sb_pcg* s, int l)
 {
   mg_level_plan(s, l, "sb_pcg_level_rows");
-  return s->mg ? s->mg->lev[l].n : s->nr;
+  return s->mgp ? mgp_level_rows(s, l) : s->mg ? s->mg->lev[l].n : s->nr;
 }
-int sb_pcg_level_colours(const sb_pcg* s, int l) { return (int)mg_level_plan(s, l, "sb_pcg_level_colours")->nC; }
+int sb_pcg_level_colours(const sb_pcg* s, int l)
+{
+  const SgsPlan* P = mg_level_plan(s, l, "sb_pcg_level_colours");
+  return P ? (int)P->nC : 0;
+}

@@ -44,8 +44,8 @@ SellRows mg_fw_sell(const HostRows& R, uint32_t* nChunksOut, double* bytes)
 
 // level l's two structures from its (checked) prolongation: P in this level's device order with the next level's device rows
 // as columns, entries in the caller's storage order; P^T the other way round, a coarse row's entries in ascending ORIGINAL fine
-// row number (equal rows: storage order).  A stored weight of 0.0 is dropped from both.  Also the level's diagonal and d
-static void mg_fw_build(MgLevel& F, const sb_matrix* coarse, const MgFwArgs& a, int l)
+// row number (equal rows: storage order).  A stored weight of 0.0 is dropped from both
+static void mg_fw_transfers(MgLevel& F, const sb_matrix* coarse, const MgFwArgs& a, int l)
 {
   const uint32_t nf = F.n, ncs = coarse->nr;
   const std::vector<uint32_t> fo2n = old_to_device_rows(F.A), co2n = old_to_device_rows(coarse);
@@ -75,7 +75,12 @@ static void mg_fw_build(MgLevel& F, const sb_matrix* coarse, const MgFwArgs& a, 
   F.omega   = a.omega[l];
   F.PT      = mg_fw_sell(pt, &F.nPTChunks, &F.transferBytes);
   F.Pm      = mg_fw_sell(p, &F.nPChunks, &F.transferBytes);
-  const size_t nb = (size_t)nf * sizeof(double) + 4096;
+}
+// ... and the level's diagonal and d, which the full residual needs
+static void mg_fw_build(MgLevel& F, const sb_matrix* coarse, const MgFwArgs& a, int l)
+{
+  mg_fw_transfers(F, coarse, a, l);
+  const size_t nb = (size_t)F.n * sizeof(double) + 4096;
   F.diag = (double*)sb_malloc(nb), F.d = (double*)sb_malloc(nb);
   launch_diagonal(F.A, F.diag, nullptr);
   HIP_CHECK(hipStreamSynchronize(g.stream));

@@ -1,17 +1,18 @@
 // sbhip_pcg_loop.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context): the loop
 // of preconditioned CG and the one place that asks how the handle's z is made: the diagonal (riding in the r
 // update), the sweeps (sbhip_sgs.inc.h), the V-cycle (sbhip_mg.inc.h, sbhip_mg_fw.inc.h) or the
-// Chebyshev polynomial (sbhip_poly.inc.h).
+// Chebyshev polynomial (sbhip_poly.inc.h), alone or as the smoother of a V-cycle (sbhip_mg_poly.inc.h).
 // Included behind those files, so nothing here is declared ahead of its definition; the handle is sbhip_pcg.inc.h's.
 // ===========================================================================
 // preconditioned CG: z and the loop
 // ===========================================================================
-int sb_pcg_precond(const sb_pcg* s) { return s->poly ? 4 : s->mg ? (s->mg->fw ? 3 : 2) : s->sgs ? 1 : 0; }
+int sb_pcg_precond(const sb_pcg* s) { return s->mgp ? 5 : s->poly ? 4 : s->mg ? (s->mg->fw ? 3 : 2) : s->sgs ? 1 : 0; }
 
 // z = M^-1 r with the handle's preconditioner: r o dinv, the sweeps of its matrix, or the V-cycle around them (t: the forward
 // sums of level 0; the diagonal does not touch it), or the polynomial on the handle's own d and w
 static void precond_apply(const sb_pcg* s, const double* r, double* t, double* z, const int* stop)
 {
+  if (s->mgp) return mgp_apply(s, r, z, stop, false, nullptr);
   if (s->poly) return poly_apply(s->A, (const double*)s->dinv, s->poly->c, r, z, s->poly->d, s->poly->w, stop);
   if (s->mg) return mg_apply(s, r, t, z, stop);
   if (s->sgs) return sgs_apply(s->sgs, (const double*)s->dinv, r, t, z, stop);
@@ -22,7 +23,8 @@ static void precond_apply(const sb_pcg* s, const double* r, double* t, double* z
 
 // the r update (PRO 1: the prologue's b - Ap) with the r.r values, z and the r.z values.  The diagonal: all of it in
 // pcg_update_r_k.  Sweeps and V-cycle: the r update without z, the apply, r.z by dot_l1_k.  The polynomial: step 1 in
-// poly_update_r_k, the steps behind it by poly_steps, the last of them with the r.z values
+// poly_update_r_k, the steps behind it by poly_steps, the last of them with the r.z values.  The Chebyshev-smoothed cycle: level
+// 0's step 1 in poly_update_r_k, the rest by mgp_apply, whose last kernel on level 0 makes the r.z values
 template <int PRO> static void pcg_residual_and_z(sb_pcg* s)
 {
   const uint32_t n = s->nr;
@@ -30,7 +32,16 @@ template <int PRO> static void pcg_residual_and_z(sb_pcg* s)
   const int* stop   = &s->S->stop; // (0 throughout the prologue: sb_pcg_start has just written the block)
   const double* src = PRO ? s->b : s->r;
   const dim3 grid(vec_stream_grid(n)), block(1024);
-  if (s->poly) {
+  if (s->mgp) {
+    const MgPolyLevel& V = s->mgp->lev[0];
+    if (s->mgp->lev.size() == 1 && V.c.steps == 1)
+      hipLaunchKernelGGL((poly_update_r_k<PRO, 1>), grid, block, 0, g.stream, n, (const double*)s->Ap, src, s->r, (const double*)s->dinv,
+          V.d, s->z, V.c.c1, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
+    else
+      hipLaunchKernelGGL((poly_update_r_k<PRO, 0>), grid, block, 0, g.stream, n, (const double*)s->Ap, src, s->r, (const double*)s->dinv,
+          V.d, s->z, V.c.c1, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
+    mgp_apply(s, s->r, s->z, stop, true, s->l1rz);
+  } else if (s->poly) {
     const PolyPlan* P = s->poly;
     if (P->c.steps == 1)
       hipLaunchKernelGGL((poly_update_r_k<PRO, 1>), grid, block, 0, g.stream, n, (const double*)s->Ap, src, s->r, (const double*)s->dinv,
@@ -51,9 +62,11 @@ template <int PRO> static void pcg_residual_and_z(sb_pcg* s)
   HIP_CHECK(hipGetLastError());
 }
 
-// bytes one apply reads and writes.  Diagonal: r, dinv in, z out.  SGS: sgs_bytes.  MG: mg_bytes.  Polynomial: poly_bytes
+// bytes one apply reads and writes.  Diagonal: r, dinv in, z out.  SGS: sgs_bytes.  MG: mg_bytes.  Polynomial: poly_bytes.
+// Chebyshev-smoothed cycle: mgp_bytes
 double sb_pcg_precond_bytes(const sb_pcg* s)
 {
+  if (s->mgp) return mgp_bytes(s);
   if (s->poly) return poly_bytes(s);
   if (!s->sgs) return 24.0 * (double)s->nr;
   return s->mg ? mg_bytes(s) : sgs_bytes(s->sgs, s->nr);
@@ -103,6 +116,7 @@ void sb_pcg_free(sb_pcg* s)
   if (!s) return;
   HIP_CHECK(hipStreamSynchronize(g.stream));
   s->clock.destroy();
+  mgp_release(s);
   poly_release(s);
   mg_release(s);
   sgs_release(s);
@@ -115,9 +129,11 @@ void sb_pcg_free(sb_pcg* s)
 // selected SpMV kernel has a fused dot; native CRS and generic C add the dot pass: 6.  An SGS handle: the r update makes no z;
 // nC forward and nC - 1 backward launches and the r.z pass stand in between it and beta: 2 nC + 5 (+ 1).  An MG handle: the
 // V-cycle's launches in the sweeps' place: 6 (+ 1) + mg_apply_launches.  A polynomial handle: step 1 rides in the r update, the
-// last step makes the r.z values; an SpMV and a step kernel per step behind the first: 5 (+ 1) + 2 (steps - 1)
+// last step makes the r.z values; an SpMV and a step kernel per step behind the first: 5 (+ 1) + 2 (steps - 1).  A
+// Chebyshev-smoothed cycle: the r update counts among the cycle's launches and no r.z pass follows: 4 (+ 1) + mgp_apply_launches
 int sb_pcg_launches_per_body(const sb_pcg* s)
 {
+  if (s->mgp) return (spmv_dot_kind(s->A) ? 4 : 5) + mgp_apply_launches(s);
   if (s->poly) return (spmv_dot_kind(s->A) ? 5 : 6) + 2 * (s->poly->c.steps - 1);
   if (s->mg) return (spmv_dot_kind(s->A) ? 6 : 7) + mg_apply_launches(s);
   return (spmv_dot_kind(s->A) ? 5 : 6) + (s->sgs ? 2 * sb_pcg_colours(s) : 0);

@@ -131,7 +131,8 @@ static const PolyPlan* need_poly(const sb_pcg* s, const char* fn)
   if (!s->poly) SB_FATAL("%s: the handle has another preconditioner (sb_pcg_create_poly makes the polynomial one)", fn);
   return s->poly;
 }
-int sb_pcg_poly_steps(const sb_pcg* s) { return s->poly ? s->poly->c.steps : 0; }
+static int mgp_steps(const sb_pcg* s); // (sbhip_mg_poly.inc.h)
+int sb_pcg_poly_steps(const sb_pcg* s) { return s->poly ? s->poly->c.steps : s->mgp ? mgp_steps(s) : 0; }
 void sb_pcg_poly_interval(const sb_pcg* s, double out[2])
 {
   const PolyPlan* P = need_poly(s, "sb_pcg_poly_interval");

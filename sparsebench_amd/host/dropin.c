@@ -86,6 +86,15 @@ int solvePCGMGFW(Comm* comm, Parameter* param, Matrix* m)
 }
 /* solvePCG with the Chebyshev polynomial preconditioner at its default steps */
 int solvePCGPoly(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_pcg_poly(comm, param, m->dev, m->nr, m->rowNnz, 0); }
+/* solvePCGMGFW with the polynomial as the smoother of every level, at its default steps */
+int solvePCGMGPoly(Comm* comm, Parameter* param, Matrix* m)
+{
+#if defined(CRS)
+  return sbh_solve_pcg_mgpoly(comm, param, m->dev, m->nr, m->rowNnz, 0, 0, 0, 0, 0);
+#else
+  return sbh_solve_pcg_mgpoly(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, 0, 0);
+#endif
+}
 /* Jacobi-preconditioned BiCGStab on this build's Matrix (the _sp libraries: "BiCGStab: double precision only") */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_bicgstab(comm, param, m->dev, m->nr, m->rowNnz); }
 

@@ -34,6 +34,8 @@ static const char* kHelp =
     "  -l <int>   Levels of -p mg and -p mgfw. Default the deepest of up to 4 that the grid allows.\n"
     "  -p poly    Chebyshev polynomial in D^-1 A as the preconditioner of -t pcg: one SpMV per step behind the first.\n"
     "  -d <int>   Steps of -p poly, 1 to 16. Default 3.\n"
+    "  -p mgpoly  The V-cycle of -p mgfw with that polynomial as the smoother of every level: no colouring.\n"
+    "             Takes -l as -p mg does, and -d for the steps of each smoothing. Default 2.\n"
     "  -r <int>   GMRES restart length. Default 30.\n"
     "  -n <int>   Number of right-hand sides for -t cg. Default 1.\n"
     "  -x <int>   Size in x for generated matrix, ignored if MM file is loaded. Default 100.\n"
@@ -64,9 +66,9 @@ int main(int argc, char** argv)
   int type = CG, opt;
   unsigned scsC = 64, scsSigma = 1;
   int restart = 30, nrhs = 1;
-  int precond = -1; /* -p: 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly; -1 not given */
+  int precond = -1; /* -p: 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly; -1 not given */
   int levels  = 0;  /* -l: levels of -p mg; 0 not given (the deepest of up to 4) */
-  int steps   = 0;  /* -d: steps of -p poly; 0 not given (3) */
+  int steps   = 0;  /* -d: steps of -p poly or -p mgpoly; 0 not given (3, 2) */
   opterr = 0;
   while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:p:l:d:")) != -1) switch (opt) {
     case 'h':
@@ -111,6 +113,7 @@ int main(int argc, char** argv)
       else if (strcmp(optarg, "mg") == 0) precond = 2;
       else if (strcmp(optarg, "mgfw") == 0) precond = 3;
       else if (strcmp(optarg, "poly") == 0) precond = 4;
+      else if (strcmp(optarg, "mgpoly") == 0) precond = 5;
       else {
         fprintf(stderr, "Unknown preconditioner %s (-p <jacobi|sgs>)\n", optarg);
         return 1;
@@ -119,14 +122,14 @@ int main(int argc, char** argv)
     case 'l':
       levels = atoi(optarg);
       if (levels < 1) {
-        fprintf(stderr, "-l <int> (the levels of -p mg) must be 1 or more, got %s\n", optarg);
+        fprintf(stderr, "-l <int> (the levels of -p mg, -p mgfw or -p mgpoly) must be 1 or more, got %s\n", optarg);
         return 1;
       }
       break;
     case 'd':
       steps = atoi(optarg);
       if (steps < 1 || steps > 16) {
-        fprintf(stderr, "-d <int> (the steps of -p poly) must be 1 to 16, got %s\n", optarg);
+        fprintf(stderr, "-d <int> (the steps of -p poly or -p mgpoly) must be 1 to 16, got %s\n", optarg);
         return 1;
       }
       break;
@@ -144,19 +147,19 @@ int main(int argc, char** argv)
     fprintf(stderr, "-p <jacobi|sgs> (the preconditioner) goes with -t pcg only\n");
     return 1;
   }
-  if (levels != 0 && precond != 2 && precond != 3) {
-    fprintf(stderr, "-l <int> (the levels) goes with -p mg only\n");
+  if (levels != 0 && precond != 2 && precond != 3 && precond != 5) {
+    fprintf(stderr, "-l <int> (the levels) goes with -p mg only, or with -p mgfw or -p mgpoly\n");
     return 1;
   }
-  if (steps != 0 && precond != 4) {
-    fprintf(stderr, "-d <int> (the steps) goes with -p poly only\n");
+  if (steps != 0 && precond != 4 && precond != 5) {
+    fprintf(stderr, "-d <int> (the steps) goes with -p poly only, or with -p mgpoly\n");
     return 1;
   }
-  if (precond == 2 || precond == 3) { /* refused before the set-up: a file has no grid, a grid may not allow the levels */
+  if (precond == 2 || precond == 3 || precond == 5) { /* refused before the set-up: a file has no grid, a grid may not allow the levels */
     char why[256];
     if (strcmp(param.filename, "generate") != 0 && strcmp(param.filename, "generate7P") != 0) {
       fprintf(stderr, "-p %s needs the grid: its hierarchy is the generated matrix's on coarser grids, not -m %s\n",
-          precond == 3 ? "mgfw" : "mg", param.filename);
+          precond == 5 ? "mgpoly" : precond == 3 ? "mgfw" : "mg", param.filename);
       return 1;
     }
     if (!sbh_mg_levels(param.nx, param.ny, param.nz, levels, why, sizeof why)) {
@@ -217,6 +220,14 @@ int main(int argc, char** argv)
       k = sbh_solve_pcg_mgfw(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, levels);
 #else
       k = sbh_solve_pcg_mgfw(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels);
+#endif
+    } else if (precond == 5 && levels == 0 && steps == 0) {
+      k = solvePCGMGPoly(&comm, &param, &sm); /* (prints "Preconditioner: MG (V-cycle, ..., Chebyshev polynomial smoother), ..." itself) */
+    } else if (precond == 5) {
+#ifdef SCS
+      k = sbh_solve_pcg_mgpoly(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, levels, steps);
+#else
+      k = sbh_solve_pcg_mgpoly(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels, steps);
 #endif
     } else if (precond == 4) { /* (prints "Preconditioner: Chebyshev polynomial, steps = ..., lambda in [...]" itself) */
       k = steps == 0 ? solvePCGPoly(&comm, &param, &sm) : sbh_solve_pcg_poly(&comm, &param, sm.dev, sm.nr, sm.rowNnz, steps);

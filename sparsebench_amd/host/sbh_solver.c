@@ -351,9 +351,10 @@ static void mg_refuse(const char* msg)
   exit(EXIT_FAILURE);
 }
 
-/* fw: the trilinear prolongations and omega = 0.5 in the injection maps' place */
+/* fw 1: the trilinear prolongations and omega = 0.5 in the injection maps' place; fw 2: those prolongations with
+ * omega = 0.25 and the Chebyshev polynomial (steps per smoothing; 0: the default 2; ratio 4) as the smoother */
 static int solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
-    CG_UINT sigma, int levels, int fw)
+    CG_UINT sigma, int levels, int fw, int steps)
 {
   dp_only("PCG: double precision only\n");
   if (strcmp(param->filename, "generate") != 0 && strcmp(param->filename, "generate7P") != 0)
@@ -378,17 +379,26 @@ static int solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT 
     for (int l = 0; l + 1 < L; l++, nx /= 2, ny /= 2, nz /= 2) {
       const size_t n = (size_t)nx * ny * nz;
       ptr[l] = (uint64_t*)malloc((n + 1) * sizeof(uint64_t)), col[l] = (CG_UINT*)malloc(8 * n * sizeof(CG_UINT));
-      val[l] = (double*)malloc(8 * n * sizeof(double)), omega[l] = 0.5;
+      val[l] = (double*)malloc(8 * n * sizeof(double)), omega[l] = fw == 2 ? 0.25 : 0.5;
       sbh_mg_trilinear(nx, ny, nz, ptr[l], col[l], val[l]);
     }
-    s = sb_pcg_create_mg_p((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats, (const uint64_t* const*)ptr,
-        (const uint32_t* const*)col, (const double* const*)val, omega);
+    if (fw == 2)
+      s = sb_pcg_create_mg_poly((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats,
+          (const uint64_t* const*)ptr, (const uint32_t* const*)col, (const double* const*)val, omega, steps ? steps : 2, 0, 0.0, 0.0);
+    else
+      s = sb_pcg_create_mg_p((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats,
+          (const uint64_t* const*)ptr, (const uint32_t* const*)col, (const double* const*)val, omega);
     for (int l = 0; l + 1 < L; l++) free(ptr[l]), free(col[l]), free(val[l]);
     free(ptr), free(col), free(val), free(omega);
   } else {
     s = sb_pcg_create_mg((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats, maps);
   }
-  if (commIsMaster(comm))
+  if (fw == 2 && commIsMaster(comm)) {
+    double iv[2];
+    sb_pcg_mg_poly_interval(s, 0, iv);
+    printf("Preconditioner: MG (V-cycle, full-weighting transfers, Chebyshev polynomial smoother), levels = %d, steps = %d, "
+           "lambda in [%.6g, %.6g]\n", sb_pcg_levels(s), sb_pcg_poly_steps(s), iv[0], iv[1]);
+  } else if (commIsMaster(comm))
     printf("Preconditioner: MG (V-cycle, %smulticolour SGS smoother), levels = %d, nC = %d\n", fw ? "full-weighting transfers, " : "",
         sb_pcg_levels(s), sb_pcg_colours(s));
   const int k = run_pcg(comm, param, s, b, xexact);
@@ -399,12 +409,17 @@ static int solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT 
 int sbh_solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
     CG_UINT sigma, int levels)
 {
-  return solve_pcg_mg(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, levels, 0);
+  return solve_pcg_mg(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, levels, 0, 0);
 }
 int sbh_solve_pcg_mgfw(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
     CG_UINT sigma, int levels)
 {
-  return solve_pcg_mg(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, levels, 1);
+  return solve_pcg_mg(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, levels, 1, 0);
+}
+int sbh_solve_pcg_mgpoly(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int levels, int steps)
+{
+  return solve_pcg_mg(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, levels, 2, steps);
 }
 
 /* ---- solveBiCGStab ----------------------------------------------------------------------- */

@@ -8,6 +8,8 @@ Python, and nothing here falls back to the CPU.
 import ctypes as C
 import math
 import os
+import shutil
+import tempfile
 
 import numpy as np
 
@@ -124,6 +126,61 @@ def mg_trilinear(nx, ny, nz):
     host().sbh_mg_trilinear(int(nx), int(ny), int(nz), ptr.ctypes.data_as(vp), col.ctypes.data_as(vp), val.ctypes.data_as(vp))
     nnz = int(ptr[n])
     return ptr, col[:nnz].copy(), val[:nnz].copy()
+
+
+def _write_mtx(path, A):
+    """a scipy CSR matrix as a general real Matrix Market file, entries in storage order, 17 significant digits: every double
+    comes back bit for bit through Problem(path)"""
+    with open(path, "w") as f:
+        f.write("%%%%MatrixMarket matrix coordinate real general\n%d %d %d\n" % (A.shape[0], A.shape[1], A.nnz))
+        rows = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
+        step = 1 << 20
+        for a in range(0, A.nnz, step):
+            f.write("".join("%d %d %.17g\n" % t for t in zip((rows[a:a + step] + 1).tolist(), (A.indices[a:a + step] + 1).tolist(),
+                                                              A.data[a:a + step].tolist())))
+
+
+def mg_galerkin(problem, levels=None, directory=None, _owned=None):
+    """the Galerkin hierarchy of a generated problem for PCG(precond="mgpoly", coarse=...): [(Problem, P, 1.0), ...] with the
+    trilinear P per level and A_{l+1} = P_l^T A_l P_l, formed by scipy.sparse in CSR with sorted columns and exact zeros dropped,
+    written with 17 significant digits as level<l>.mtx into `directory` (None: a new temporary one) and opened as Problems of the
+    fine problem's format, C and sigma.  omega is 1.0: scaling A_c and the restriction together cancels in the cycle.  The caller
+    frees the problems and removes the files (PCG(galerkin=True) does both with the handle).  ImportError without scipy."""
+    try:
+        import scipy.sparse as sp
+    except ImportError:
+        raise ImportError("mg_galerkin forms P^T A P with scipy.sparse, and scipy is not installed")
+    name = getattr(problem, "filename", None)
+    if name not in ("generate", "generate7P"):
+        raise ValueError("mg_galerkin needs the grid: %r is not a generated problem" % (name,))
+    if problem.nr != problem.totalNr:
+        raise ValueError("mg_galerkin runs on one rank")
+    if getattr(problem, "precision", "double") != "double":
+        raise ValueError("mg_galerkin: double precision only (the problem was built with precision=%r)" % (problem.precision,))
+    dims = problem.dims
+    nlev = mg_levels(*dims, levels=levels)
+    if directory is None:
+        directory = tempfile.mkdtemp(prefix="sb_galerkin_")
+    col, val = problem.gm_entries()
+    A = sp.csr_matrix((val.astype(np.float64), col.astype(np.int64), problem.array("rowPtr").astype(np.int64)),
+                      shape=(problem.nr, problem.nr))
+    out = []
+    for l in range(nlev - 1):
+        triple = mg_trilinear(*dims)
+        nf = dims[0] * dims[1] * dims[2]
+        dims = tuple(d // 2 for d in dims)
+        P = sp.csr_matrix((triple[2], triple[1].astype(np.int64), triple[0].astype(np.int64)), shape=(nf, nf // 8))
+        A = (P.T.tocsr() @ A @ P).tocsr()
+        A.sum_duplicates()
+        A.eliminate_zeros()
+        A.sort_indices()
+        path = os.path.join(os.fspath(directory), "level%d.mtx" % (l + 1))
+        _write_mtx(path, A)
+        q = Problem(path, fmt=problem.fmt, Cc=problem.Cc, sigma=problem.sigma_arg, upload=problem.upload)
+        if _owned is not None:
+            _owned.append(q)
+        out.append((q, triple, 1.0))
+    return out
 
 
 def _omega(omega, l):
@@ -623,30 +680,50 @@ class PCG(_BodySolver):
     `levels` for the generated hierarchy with the trilinear P and omega = 0.5, or `coarse=[(Problem, P, omega), ...]` with P a
     scipy.sparse matrix or a (ptr, col, val) CSR triple of n_l x n_{l+1}.  precond "poly": a Chebyshev polynomial in D^-1 A
     (DESIGN 4.15): `steps` terms (1 .. 16, default 3) on [lmax / ratio, lmax]; lmax None: the row-sum bound of D^-1/2 A D^-1/2,
-    ratio default 16.0; takes no dinv.  Double precision, one rank, tree dot order."""
+    ratio default 16.0; takes no dinv.  precond "mgpoly": a V-cycle with that polynomial as the smoother of every level and mgfw's
+    transfers: `steps` per smoothing (default 2), `coarse_steps` on the last level (default: steps), ratio default
+    4.0, lmax None: every level's own bound; `levels` for the generated hierarchy with the trilinear P and omega = 0.25,
+    `galerkin=True` for mg_galerkin's coarse operators in the regenerated ones' place, or `coarse` as "mgfw" takes it.  Double
+    precision, one rank, tree dot order."""
 
     PREFIX, NAME = "sb_pcg", "PCG"
     COUNTERS = ("stop", "stop_next", "iters", "n_rr", "n_pAp")
 
-    def __init__(self, problem, dinv=None, precond="jacobi", levels=None, coarse=None, steps=None, lmax=None, ratio=None):
+    def __init__(self, problem, dinv=None, precond="jacobi", levels=None, coarse=None, steps=None, lmax=None, ratio=None,
+                 coarse_steps=None, galerkin=False):
         self._need_double(problem)
-        if precond not in ("jacobi", "sgs", "mg", "mgfw", "poly"):
-            raise ValueError("precond must be 'jacobi' or 'sgs' or 'mg' or 'mgfw' or 'poly', got %r" % (precond,))
-        if precond != "poly" and (steps is not None or lmax is not None or ratio is not None):
-            raise ValueError("steps, lmax and ratio go with precond='poly' only")
+        if precond not in ("jacobi", "sgs", "mg", "mgfw", "poly", "mgpoly"):
+            raise ValueError("precond must be 'jacobi' or 'sgs' or 'mg' or 'mgfw' or 'poly' or 'mgpoly', got %r" % (precond,))
+        if precond not in ("poly", "mgpoly") and (steps is not None or lmax is not None or ratio is not None):
+            raise ValueError("steps, lmax and ratio go with precond='poly' only, or with 'mgpoly'")
+        if precond != "mgpoly" and (coarse_steps is not None or galerkin):
+            raise ValueError("coarse_steps and galerkin go with precond='mgpoly' only")
         if precond == "poly":
             steps, lmax, ratio = self._poly_args(steps, lmax, ratio)
-        if precond in ("sgs", "mg", "mgfw", "poly") and dinv is not None:
+        poly = None
+        if precond == "mgpoly":
+            steps, lmax, ratio = self._poly_args(2 if steps is None else steps, lmax, 4.0 if ratio is None else ratio)
+            cs = self._poly_args(steps if coarse_steps is None else coarse_steps, None, None, "coarse_steps")[0]
+            poly = (steps, cs, lmax, ratio)
+            if not isinstance(galerkin, (bool, np.bool_)):
+                raise ValueError("galerkin must be True or False, got %r" % (galerkin,))
+            if galerkin and coarse is not None:
+                raise ValueError("galerkin=True builds the coarse operators itself: it takes levels, not coarse")
+        if precond in ("sgs", "mg", "mgfw", "poly", "mgpoly") and dinv is not None:
             raise ValueError("precond=%r takes no dinv: its diagonal is the matrix's own" % (precond,))
-        if precond not in ("mg", "mgfw") and (levels is not None or coarse is not None):
-            raise ValueError("levels and coarse go with precond='mg' only, or with 'mgfw'")
+        if precond not in ("mg", "mgfw", "mgpoly") and (levels is not None or coarse is not None):
+            raise ValueError("levels and coarse go with precond='mg' only, or with 'mgfw' or 'mgpoly'")
         if levels is not None and coarse is not None:
             raise ValueError("precond='mg' takes levels (a generated problem's own hierarchy) or coarse (the caller's), not both")
         self._owned = []  # the coarse problems this handle generated itself
+        self._owned_dir = None  # ... and the directory of the Galerkin operators' files
         self._keep = None
-        if precond in ("mg", "mgfw"):
+        if precond in ("mg", "mgfw", "mgpoly"):
             try:
-                self._create_mg(problem, levels, coarse, precond == "mgfw")
+                if galerkin:
+                    self._create_galerkin(problem, levels, poly)
+                else:
+                    self._create_mg(problem, levels, coarse, precond != "mg", precond, poly)
             except Exception:
                 self._free_owned()  # the coarse problems generated so far
                 raise
@@ -660,11 +737,11 @@ class PCG(_BodySolver):
             self.ptr = self.L.sb_pcg_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), _ptr(self._dinv_arg(dinv)))
 
     @staticmethod
-    def _poly_args(steps, lmax, ratio):
+    def _poly_args(steps, lmax, ratio, what="steps"):
         """(steps, lmax, ratio) as sb_pcg_create_poly takes them (lmax 0.0: the bound), refused here where it would refuse them"""
         steps = 3 if steps is None else steps
         if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= 16:
-            raise ValueError("steps must be an integer from 1 to 16, got %r" % (steps,))
+            raise ValueError("%s must be an integer from 1 to 16, got %r" % (what, steps))
         ratio = 16.0 if ratio is None else float(ratio)
         if not (1.0 < ratio < math.inf):
             raise ValueError("ratio (lmax / lmin) must be finite and greater than 1, got %r" % (ratio,))
@@ -672,28 +749,29 @@ class PCG(_BodySolver):
             raise ValueError("lmax must be finite and positive (None: the row-sum bound), got %r" % (lmax,))
         return int(steps), 0.0 if lmax is None else float(lmax), ratio
 
-    def _create_mg(self, problem, levels, coarse, fw=False):
+    def _create_mg(self, problem, levels, coarse, fw=False, precond="mg", poly=None):
         """coarse: [(Problem, f2c), ...], level l + 1's problem and the rows of level l that are its points (original numbering);
         else the geometric hierarchy of a generated problem at `levels` (None: the deepest of up to 4).  fw: (Problem, P, omega)
-        triples and the trilinear P with omega = 0.5 in their place"""
+        triples and the trilinear P with omega = 0.5 in their place; poly (steps, coarse_steps, lmax, ratio): the
+        Chebyshev-smoothed cycle on them, omega = 0.25"""
         if coarse is None:
             name = getattr(problem, "filename", None)
             if name not in ("generate", "generate7P"):
                 raise ValueError("precond=%r needs the grid: %r is not a generated problem (pass coarse=[(Problem, %s), ...])"
-                                 % ("mgfw" if fw else "mg", name, "P, omega" if fw else "f2c"))
+                                 % (precond if fw else "mg", name, "P, omega" if fw else "f2c"))
             if problem.nr != problem.totalNr:
                 raise ValueError("precond='mg' runs on one rank")
             dims = problem.dims
             nlev = mg_levels(*dims, levels=levels)
             coarse = []
             for _ in range(nlev - 1):
-                transfer = (mg_trilinear(*dims), 0.5) if fw else (mg_f2c(*dims),)
+                transfer = (mg_trilinear(*dims), 0.25 if poly else 0.5) if fw else (mg_f2c(*dims),)
                 dims = tuple(d // 2 for d in dims)
                 q = Problem(name, *dims, fmt=problem.fmt, Cc=problem.Cc, sigma=problem.sigma_arg)
                 self._owned.append(q)
                 coarse.append((q,) + transfer)
         if fw:
-            return self._create_mg_p(problem, coarse)
+            return self._create_mg_p(problem, coarse, precond, poly)
         maps = []
         for q, f2c in coarse:
             self._need_double(q)
@@ -708,11 +786,17 @@ class PCG(_BodySolver):
         self._keep = (coarse, maps)  # the caller's coarse problems must outlive the handle, as the fine one must
         self.ptr = self.L.sb_pcg_create_mg(problem.matrix, problem.halo, _ptr(b), _ptr(xe), n, mats, ptrs)
 
-    def _create_mg_p(self, problem, coarse):
+    def _create_galerkin(self, problem, levels, poly):
+        """mg_galerkin's hierarchy in a temporary directory that goes with the handle"""
+        self._owned_dir = tempfile.mkdtemp(prefix="sb_galerkin_")
+        coarse = mg_galerkin(problem, levels, self._owned_dir, _owned=self._owned)
+        self._create_mg_p(problem, coarse, "mgpoly", poly)
+
+    def _create_mg_p(self, problem, coarse, precond="mgfw", poly=None):
         ps, omegas, n_fine = [], [], problem.nr
         for l, item in enumerate(coarse):
             if not isinstance(item, (tuple, list)) or len(item) != 3:
-                raise ValueError("precond='mgfw' takes coarse=[(Problem, P, omega), ...]: entry %d is not such a triple" % l)
+                raise ValueError("precond=%r takes coarse=[(Problem, P, omega), ...]: entry %d is not such a triple" % (precond, l))
             q, P, omega = item
             self._need_double(q)
             omegas.append(_omega(omega, l))
@@ -724,7 +808,24 @@ class PCG(_BodySolver):
         arrs = [(vp * max(n, 1))(*[t[i].ctypes.data for t in ps]) for i in range(3)]
         om = np.array(omegas + [0.0], dtype=np.float64)
         self._keep = (coarse, ps)  # the caller's coarse problems must outlive the handle, as the fine one must
+        if poly:
+            self.ptr = self.L.sb_pcg_create_mg_poly(problem.matrix, problem.halo, _ptr(b), _ptr(xe), n, mats, arrs[0], arrs[1], arrs[2],
+                                                    _ptr(om), *poly)
+            return
         self.ptr = self.L.sb_pcg_create_mg_p(problem.matrix, problem.halo, _ptr(b), _ptr(xe), n, mats, arrs[0], arrs[1], arrs[2], _ptr(om))
+
+    def mg_poly_probe(self, l, r, w, z, zc):
+        """(rc, z_out) of the transfers of level l alone (sb_pcg_mg_poly_probe): rc = omega_l P_l^T (r - w), z_out = z + P_l zc;
+        r, w, z in level l's original row order, zc in level l + 1's"""
+        if self.precond() != "mgpoly" or not 0 <= int(l) < self.levels() - 1:
+            raise ValueError("mg_poly_probe: level %r of a %r handle with %d levels has no transfers" % (l, self.precond(), self.levels()))
+        nf, nc = self.level_rows(l), self.level_rows(l + 1)
+        r, w, z, zc = (np.ascontiguousarray(v, dtype=np.float64) for v in (r, w, z, zc))
+        if r.shape != (nf,) or w.shape != (nf,) or z.shape != (nf,) or zc.shape != (nc,):
+            raise ValueError("r, w and z must hold %d doubles, zc %d" % (nf, nc))
+        rc, zo = np.empty(nc), np.empty(nf)
+        self.L.sb_pcg_mg_poly_probe(self.ptr, int(l), _ptr(r), _ptr(w), _ptr(z), _ptr(zc), _ptr(rc), _ptr(zo))
+        return rc, zo
 
     def mg_fw_probe(self, l, r, z, zc):
         """(d, rc, z_out) of the transfers of level l alone (sb_pcg_mg_fw_probe): d = r - A_l z, rc = omega_l P_l^T d,
@@ -741,33 +842,53 @@ class PCG(_BodySolver):
         for q in self._owned:
             q.free()
         self._owned = []
+        if getattr(self, "_owned_dir", None):
+            shutil.rmtree(self._owned_dir, ignore_errors=True)
+            self._owned_dir = None
 
     def free(self):
         _BodySolver.free(self)
         self._free_owned()
 
     def precond(self):
-        """"jacobi" (any diagonal), "sgs", "mg", "mgfw" or "poly" """
-        return ("jacobi", "sgs", "mg", "mgfw", "poly")[self.L.sb_pcg_precond(self.ptr)]
+        """"jacobi" (any diagonal), "sgs", "mg", "mgfw", "poly" or "mgpoly" """
+        return ("jacobi", "sgs", "mg", "mgfw", "poly", "mgpoly")[self.L.sb_pcg_precond(self.ptr)]
 
     def steps(self):
-        """steps of a polynomial handle; 0 for the other kinds"""
+        """steps of a polynomial handle or of a Chebyshev-smoothed cycle; 0 for the other kinds"""
         return self.L.sb_pcg_poly_steps(self.ptr)
 
-    def _need_poly(self, what):
-        if self.steps() == 0:
+    def _need_poly(self, what, l=None):
+        """True on an "mgpoly" handle, whose queries take a level (default 0); a "poly" handle takes none"""
+        mgp = self.precond() == "mgpoly"
+        if self.steps() == 0 or (what == "rowbound" and mgp):
             raise ValueError("%s: the handle's preconditioner is %r, not 'poly'" % (what, self.precond()))
+        if l is not None and not mgp:
+            raise ValueError("%s: a level goes with precond='mgpoly' only" % what)
+        if mgp and not 0 <= (0 if l is None else int(l)) < self.levels():
+            raise ValueError("%s: level %r of a handle with %d levels" % (what, l, self.levels()))
+        return mgp
 
-    def interval(self):
-        """(lmin, lmax) of a polynomial handle"""
-        self._need_poly("interval")
+    def level_steps(self, l):
+        """steps of level l of an "mgpoly" handle: steps, on the last level coarse_steps"""
+        self._need_poly("level_steps", l)
+        return self.L.sb_pcg_mg_poly_level_steps(self.ptr, int(l))
+
+    def interval(self, l=None):
+        """(lmin, lmax) of a polynomial handle, or of level l of an "mgpoly" handle"""
         out = np.zeros(2)
-        self.L.sb_pcg_poly_interval(self.ptr, out.ctypes.data_as(vp))
+        if self._need_poly("interval", l):
+            self.L.sb_pcg_mg_poly_interval(self.ptr, int(l or 0), out.ctypes.data_as(vp))
+        else:
+            self.L.sb_pcg_poly_interval(self.ptr, out.ctypes.data_as(vp))
         return float(out[0]), float(out[1])
 
-    def coeffs(self):
-        """c1, then a_j, b_j for j = 2 .. steps: 2 steps - 1 doubles"""
-        self._need_poly("coeffs")
+    def coeffs(self, l=None):
+        """c1, then a_j, b_j for j = 2 .. steps: 2 steps - 1 doubles; of level l on an "mgpoly" handle"""
+        if self._need_poly("coeffs", l):
+            out = np.zeros(2 * self.level_steps(int(l or 0)) - 1)
+            self.L.sb_pcg_mg_poly_coeffs(self.ptr, int(l or 0), out.ctypes.data_as(vp))
+            return out
         out = np.zeros(2 * self.steps() - 1)
         self.L.sb_pcg_poly_coeffs(self.ptr, out.ctypes.data_as(vp))
         return out
