@@ -681,6 +681,32 @@ void sb_pcg_mg_poly_first_native(uint32_t n, int last, double c1, const double* 
     double* d_dev, double* z_dev, double* l1_rz_dev);
 void sb_pcg_mg_poly_first_launch(uint32_t n, uint32_t out[3]);
 
+/* ---- Galerkin coarse operators formed on the device ------------------------------------------------------- */
+/* A_c = P^T A P for a square double-precision one-rank matrix A (n x n, any format, any permutation), read in place from its
+ * upload, and a prolongation P (n x nCoarse) as a CSR triple in original numbering on both sides, as sb_pcg_create_mg_p takes it.
+ * Set-up work in two row-wise products, T = A P and A_c = P^T T, every operation rounded on its own:
+ *   T[i, J]   = the sum, from +0.0, of a_e * p_q over the entries e of row i of A in the order the device matrix stores the row
+ *               (the order the SpMV sums it) whose stored value does not compare equal to 0.0 (Sell padding, explicit zeros) and,
+ *               inside each, over the entries q of row col_e of P in storage order whose weight is not 0.0 and whose column is
+ *               J; T has the entry where at least one such term exists, and nothing is dropped from it;
+ *   A_c[I, J] = the sum, from +0.0, of w * T[i, J] over the entries (i, w) of row I of P^T with w != 0.0 in ascending original
+ *               fine row i (equal rows: storage order) for which T[i, J] exists; an entry whose sum compares equal to 0.0 is
+ *               dropped, NaN is kept.
+ * The result is in the coarse level's original numbering on both sides, columns ascending, row pointers 64-bit, and the same
+ * bits for A in CRS and in every Sell-C-sigma; it lives on the host.  Ends the process with a message for a single-precision
+ * matrix, nr != nc (halo columns, several ranks), a P that sb_pcg_create_mg_p would refuse, intermediate storage beyond
+ * sb_mem_free_bytes(), and a row of T or of P^T T with more than 1024 distinct columns (naming stage, row and the count reached:
+ * never truncated). */
+typedef struct sb_csr sb_csr;
+sb_csr* sb_matrix_galerkin(const sb_matrix* A, uint32_t nCoarse, const uint64_t* p_ptr, const uint32_t* p_col, const double* p_val);
+uint32_t sb_csr_rows(const sb_csr* c);
+uint64_t sb_csr_nnz(const sb_csr* c);
+void sb_csr_copy(const sb_csr* c, uint64_t* ptr, uint32_t* col, double* val); /* rows + 1, nnz, nnz entries */
+/* device ms of stage 1, of stage 2 (both launches each); entries of T; entries dropped as 0.0; the largest number of distinct
+ * columns of a row of T, of a row of P^T T before the drop */
+void sb_csr_stats(const sb_csr* c, double out[6]);
+void sb_csr_free(sb_csr* c);
+
 /* ---- BiCGStab with a diagonal preconditioner ----------------------------------------------------------- */
 /* Right-preconditioned BiCGStab for matrices that need not be symmetric: two SpMVs per body, about ten vectors whatever the
  * iteration count, no restart.  x0 = 0, rhat = b; the loop test is on sqrt(r.r) alone (no exit on ||s||); rho = 0, rhat.v = 0

@@ -285,6 +285,11 @@ int sbh_solve_pcg_mgfw(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT n
  * transfers, Chebyshev polynomial smoother), levels = L, steps = <steps>, lambda in [<lmin>, <lmax> of level 0]" */
 int sbh_solve_pcg_mgpoly(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
                          CG_UINT sigma, int levels, int steps);
+/* sbh_solve_pcg_mgpoly on Galerkin coarse operators in the regenerated ones' place: A_{l+1} = P_l^T A_l P_l formed
+ * on the device (sbh_mg_hierarchy_build_galerkin), omega = 1.0; the same depth rules, refusals and default steps.  The
+ * preconditioner line says "Galerkin coarse operators"; a second line gives the products' device milliseconds per level */
+int sbh_solve_pcg_mgpoly_galerkin(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt,
+                                  CG_UINT C, CG_UINT sigma, int levels, int steps);
 /* sbh_solve_pcg with a Chebyshev polynomial in D^-1 A in the diagonal's place (sb_pcg_create_poly, sbhip.h): steps
  * terms (1 .. 16; 0: the default 3) on [lmax / 16, lmax], lmax by the row-sum bound of D^-1/2 A D^-1/2.  First prints
  * "Preconditioner: Chebyshev polynomial, steps = <steps>, lambda in [<lmin>, <lmax>]" */
@@ -306,6 +311,17 @@ void sbh_mg_trilinear(int nx, int ny, int nz, uint64_t* ptr, CG_UINT* col, doubl
  * Returns what sbh_mg_hierarchy_free releases (after the solver handle that uses the levels) */
 void* sbh_mg_hierarchy_build(const Parameter* param, int fmt, CG_UINT C, CG_UINT sigma, int L, const void** mats, const CG_UINT** maps);
 void sbh_mg_hierarchy_free(void* hierarchy, int fmt, int L);
+/* the Galerkin mode of the builder: level l + 1 is P_l^T A_l P_l with the trilinear P_l of level l's grid, formed on
+ * the device from level l's UPLOADED matrix (sb_matrix_galerkin, sbhip.h; fine_dev is level 0's), put into a GMatrix and taken
+ * through the same commPartition -> convert (the fine level's C and sigma) -> upload as a regenerated level.  mats[l - 1] is level
+ * l's device matrix, p_ptr / p_col / p_val[l - 1] the prolongation INTO level l - 1 from it (owned by the hierarchy: they live
+ * until sbh_mg_hierarchy_free), stage_ms[2 (l - 1)] and [2 (l - 1) + 1] the device milliseconds of the product's two stages
+ * (NULL: not wanted).  omega = 1.0 goes with it.  Double precision, one rank. */
+void* sbh_mg_hierarchy_build_galerkin(const Parameter* param, const void* fine_dev, int fmt, CG_UINT C, CG_UINT sigma, int L,
+    const void** mats, const uint64_t** p_ptr, const CG_UINT** p_col, const double** p_val, double* stage_ms);
+/* a one-rank GMatrix of n rows from CSR in memory (64-bit row pointers): a row's entries end up in ascending column, storage order
+ * kept among equal columns -- what reading the same entries from a .mtx file gives */
+void sbh_gmatrix_from_csr(GMatrix* m, CG_UINT n, const uint64_t* ptr, const CG_UINT* col, const double* val);
 /* BiCGStab with the Jacobi right preconditioner (sb_bicgstab_*, sbhip.h) for matrices that need not be symmetric: prints what
  * solveCG prints; double precision, one rank */
 int sbh_solve_bicgstab(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz);
@@ -356,6 +372,10 @@ int solvePCGPoly(Comm* comm, Parameter* param, Matrix* m);
  * before and after on every level, omega = 0.25, every SpMV of the cycle the level's own; no colouring.  The same matrices and
  * refusals; the preconditioner line names the smoother, its steps and level 0's interval. */
 int solvePCGMGPoly(Comm* comm, Parameter* param, Matrix* m);
+/* solvePCGMGPoly on Galerkin coarse operators P^T A P, formed on the device from the uploaded matrices, in the regenerated
+ * stencils' place; omega = 1.0.  The same matrices and refusals; the preconditioner line says "Galerkin coarse
+ * operators" and a second line gives the products' device time per level. */
+int solvePCGMGPolyGalerkin(Comm* comm, Parameter* param, Matrix* m);
 /* Jacobi-preconditioned BiCGStab: the short-recurrence solver for matrices that are not symmetric; returns k as
  * solveCG does.  The single-precision libraries export it too and end the process with "BiCGStab: double precision only". */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m);

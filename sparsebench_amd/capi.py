@@ -65,6 +65,7 @@ SYMBOLS = [
     "sb_bicgstab_loop_ms", "sb_bicgstab_counters", "sb_bicgstab_update_p_native", "sb_bicgstab_update_s_native",
     "sb_bicgstab_dot2_native", "sb_bicgstab_update_xr_native", "sb_bicgstab_reduce_native", "sb_bicgstab_launch",
     "sb_matrix_resident_share", "sb_resident_share_rule",
+    "sb_matrix_galerkin", "sb_csr_rows", "sb_csr_nnz", "sb_csr_copy", "sb_csr_stats", "sb_csr_free",
 ]
 
 _lib = None
@@ -336,6 +337,13 @@ def load():
         "sb_bicgstab_update_xr_native": (None, [u32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "sb_bicgstab_reduce_native": (None, [u32, vp, vp, vp]),
         "sb_bicgstab_launch": (None, [u32, vp]),
+        # Galerkin coarse operators on the device
+        "sb_matrix_galerkin": (vp, [vp, u32, vp, vp, vp]),
+        "sb_csr_rows": (u32, [vp]),
+        "sb_csr_nnz": (C.c_uint64, [vp]),
+        "sb_csr_copy": (None, [vp, vp, vp, vp]),
+        "sb_csr_stats": (None, [vp, vp]),
+        "sb_csr_free": (None, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

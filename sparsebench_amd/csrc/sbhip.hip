@@ -32,6 +32,7 @@
 #include "mg_fw.hip.h"
 #include "poly.hip.h"
 #include "mg_poly.hip.h"
+#include "galerkin.hip.h"
 
 #include <algorithm>
 #include <iterator>
@@ -708,5 +709,6 @@ void sb_event_destroy(void* ev) { HIP_CHECK(hipEventDestroy((hipEvent_t)ev)); }
 #include "sbhip_mg_fw.inc.h"
 #include "sbhip_poly.inc.h"
 #include "sbhip_mg_poly.inc.h"
+#include "sbhip_galerkin.inc.h"
 #include "sbhip_pcg_loop.inc.h"
 #include "sbhip_bicgstab.inc.h"

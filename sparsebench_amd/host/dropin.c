@@ -95,6 +95,15 @@ int solvePCGMGPoly(Comm* comm, Parameter* param, Matrix* m)
   return sbh_solve_pcg_mgpoly(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, 0, 0);
 #endif
 }
+/* solvePCGMGPoly on Galerkin coarse operators formed on the device, omega = 1.0 */
+int solvePCGMGPolyGalerkin(Comm* comm, Parameter* param, Matrix* m)
+{
+#if defined(CRS)
+  return sbh_solve_pcg_mgpoly_galerkin(comm, param, m->dev, m->nr, m->rowNnz, 0, 0, 0, 0, 0);
+#else
+  return sbh_solve_pcg_mgpoly_galerkin(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, 0, 0);
+#endif
+}
 /* Jacobi-preconditioned BiCGStab on this build's Matrix (the _sp libraries: "BiCGStab: double precision only") */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_bicgstab(comm, param, m->dev, m->nr, m->rowNnz); }
 

@@ -52,6 +52,34 @@ sbh_problem* sbh_problem_create(const char* filename, int nx, int ny, int nz, in
   return p;
 }
 
+/* a Problem from CSR in memory (one rank; filename "memory"): the entries as reading them from a .mtx file would leave them
+ * (sbh_gmatrix_from_csr), then the same commPartition -> convert as above.  upload = 0: the host layout only, no GPU */
+sbh_problem* sbh_problem_create_csr(unsigned nr, const uint64_t* rowPtr, const unsigned* col, const double* val, int fmt, int C,
+    int sigma, int upload)
+{
+  sbh_problem* p = (sbh_problem*)calloc(1, sizeof *p);
+  double t0      = getTimeStamp();
+  p->fmt         = fmt;
+  initParameter(&p->par);
+  p->par.filename = strdup("memory");
+  p->par.nx = p->par.ny = p->par.nz = 1;
+  p->comm.rank = 0, p->comm.size = 1;
+  sbh_gmatrix_from_csr(&p->gm, nr, rowPtr, col, val);
+  p->nnzTrue = p->gm.rowPtr[p->gm.nr];
+  commPartition(&p->comm, &p->gm);
+  if (fmt == 0) {
+    if (upload) sbh_convert_crs(&p->crs, &p->gm);
+    else sbh_layout_crs(&p->crs, &p->gm);
+  } else {
+    p->scs.C = (CG_UINT)C, p->scs.sigma = (CG_UINT)sigma;
+    if (upload) sbh_convert_scs(&p->scs, &p->gm);
+    else sbh_layout_scs(&p->scs, &p->gm);
+  }
+  if (upload) sbh_comm_attach_halo(&p->comm, p->gm.nr, fmt == 1 ? p->scs.oldToNewPerm : NULL);
+  p->setup_s = getTimeStamp() - t0;
+  return p;
+}
+
 void* sbh_problem_matrix(sbh_problem* p) { return p->fmt == 0 ? p->crs.dev : p->scs.dev; }
 void* sbh_problem_halo(sbh_problem* p) { return p->comm.dev; }
 double sbh_problem_setup_seconds(sbh_problem* p) { return p->setup_s; }

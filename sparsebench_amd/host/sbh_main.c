@@ -36,6 +36,7 @@ static const char* kHelp =
     "  -d <int>   Steps of -p poly, 1 to 16. Default 3.\n"
     "  -p mgpoly  The V-cycle of -p mgfw with that polynomial as the smoother of every level: no colouring.\n"
     "             Takes -l as -p mg does, and -d for the steps of each smoothing. Default 2.\n"
+    "  -g         Galerkin coarse operators P^T A P, formed on the device, for -p mgpoly in the regenerated stencils' place.\n"
     "  -r <int>   GMRES restart length. Default 30.\n"
     "  -n <int>   Number of right-hand sides for -t cg. Default 1.\n"
     "  -x <int>   Size in x for generated matrix, ignored if MM file is loaded. Default 100.\n"
@@ -69,8 +70,9 @@ int main(int argc, char** argv)
   int precond = -1; /* -p: 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly; -1 not given */
   int levels  = 0;  /* -l: levels of -p mg; 0 not given (the deepest of up to 4) */
   int steps   = 0;  /* -d: steps of -p poly or -p mgpoly; 0 not given (3, 2) */
+  int galerkin = 0; /* -g: the coarse operators of -p mgpoly are P^T A P */
   opterr = 0;
-  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:p:l:d:")) != -1) switch (opt) {
+  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:p:l:d:g")) != -1) switch (opt) {
     case 'h':
       if (commIsMaster(&comm)) printf("%s", kHelp);
       commAbort(&comm, "");
@@ -126,6 +128,7 @@ int main(int argc, char** argv)
         return 1;
       }
       break;
+    case 'g': galerkin = 1; break;
     case 'd':
       steps = atoi(optarg);
       if (steps < 1 || steps > 16) {
@@ -153,6 +156,10 @@ int main(int argc, char** argv)
   }
   if (steps != 0 && precond != 4 && precond != 5) {
     fprintf(stderr, "-d <int> (the steps) goes with -p poly only, or with -p mgpoly\n");
+    return 1;
+  }
+  if (galerkin && precond != 5) {
+    fprintf(stderr, "-g (Galerkin coarse operators) goes with -p mgpoly only\n");
     return 1;
   }
   if (precond == 2 || precond == 3 || precond == 5) { /* refused before the set-up: a file has no grid, a grid may not allow the levels */
@@ -220,6 +227,14 @@ int main(int argc, char** argv)
       k = sbh_solve_pcg_mgfw(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, levels);
 #else
       k = sbh_solve_pcg_mgfw(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels);
+#endif
+    } else if (precond == 5 && galerkin && levels == 0 && steps == 0) {
+      k = solvePCGMGPolyGalerkin(&comm, &param, &sm); /* (prints "Preconditioner: MG (V-cycle, ..., Galerkin coarse operators), ..." itself) */
+    } else if (precond == 5 && galerkin) {
+#ifdef SCS
+      k = sbh_solve_pcg_mgpoly_galerkin(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, levels, steps);
+#else
+      k = sbh_solve_pcg_mgpoly_galerkin(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels, steps);
 #endif
     } else if (precond == 5 && levels == 0 && steps == 0) {
       k = solvePCGMGPoly(&comm, &param, &sm); /* (prints "Preconditioner: MG (V-cycle, ..., Chebyshev polynomial smoother), ..." itself) */

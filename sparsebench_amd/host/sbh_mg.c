@@ -98,12 +98,17 @@ typedef struct {
   SCSMatrix scs;
   void* dev;
   CG_UINT* f2c; /* from the level above */
+  /* Galerkin mode: the prolongation from this level (owned here, handed to the solver handle's constructor) */
+  uint64_t* pptr;
+  CG_UINT* pcol;
+  double* pval;
 } mg_level;
 
 static void level_free(mg_level* v, int fmt)
 {
   if (v->dev) sb_matrix_free((sb_matrix*)v->dev);
   free(v->gm.rowPtr), free(v->gm.entries), free(v->f2c);
+  free(v->pptr), free(v->pcol), free(v->pval);
   if (fmt == 0) free(v->crs.rowPtr), free(v->crs.colInd), free(v->crs.val), free(v->crs.rowNnz);
   else
     free(v->scs.chunkPtr), free(v->scs.chunkLens), free(v->scs.colInd), free(v->scs.val), free(v->scs.oldToNewPerm),
@@ -136,6 +141,90 @@ void* sbh_mg_hierarchy_build(const Parameter* param, int fmt, CG_UINT C, CG_UINT
     mats[l - 1] = v->dev, maps[l - 1] = v->f2c;
   }
   return lev;
+}
+
+/* a one-rank GMatrix from CSR in memory (sparsebench.h): what MMMatrixRead -> matrixConvertfromMM make of the same entries in a
+ * file -- a row's entries in ascending column, storage order kept among equal columns */
+void sbh_gmatrix_from_csr(GMatrix* m, CG_UINT n, const uint64_t* ptr, const CG_UINT* col, const double* val)
+{
+  const uint64_t nnz = ptr[n];
+  if (ptr[0] != 0 || nnz > 0xFFFFFFFEull) {
+    fprintf(stderr, "sbh_gmatrix_from_csr: row pointers from %llu to %llu: must start at 0 and fit the 32-bit row pointer\n",
+        (unsigned long long)ptr[0], (unsigned long long)nnz);
+    exit(EXIT_FAILURE);
+  }
+  memset(m, 0, sizeof *m);
+  m->nr = m->nc = m->totalNr = n;
+  m->nnz = m->totalNnz = (CG_UINT)nnz;
+  m->startRow = 0, m->stopRow = n ? n - 1 : 0;
+  m->entries  = (Entry*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nnz + 1) * sizeof(Entry));
+  m->rowPtr   = (CG_UINT*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)n + 1) * sizeof(CG_UINT));
+  m->rowPtr[0] = 0;
+  for (CG_UINT i = 0; i < n; i++) {
+    if (ptr[i + 1] < ptr[i]) {
+      fprintf(stderr, "sbh_gmatrix_from_csr: the row pointer falls at row %u\n", i);
+      exit(EXIT_FAILURE);
+    }
+    m->rowPtr[i + 1] = (CG_UINT)ptr[i + 1];
+    for (uint64_t q = ptr[i]; q < ptr[i + 1]; q++) {
+      if (col[q] >= n) {
+        fprintf(stderr, "sbh_gmatrix_from_csr: row %u has column %u outside the %u rows\n", i, col[q], n);
+        exit(EXIT_FAILURE);
+      }
+      uint64_t o = q; /* stable insertion by column: rows are short and usually sorted already */
+      for (; o > ptr[i] && m->entries[o - 1].col > col[q]; o--) m->entries[o] = m->entries[o - 1];
+      m->entries[o].col = col[q], m->entries[o].val = (CG_FLOAT)val[q];
+    }
+  }
+}
+
+/* the coarse levels as Galerkin products formed on the device (sparsebench.h) */
+void* sbh_mg_hierarchy_build_galerkin(const Parameter* param, const void* fine_dev, int fmt, CG_UINT C, CG_UINT sigma, int L,
+    const void** mats, const uint64_t** p_ptr, const CG_UINT** p_col, const double** p_val, double* stage_ms)
+{
+#if PRECISION == 1
+  (void)param, (void)fine_dev, (void)fmt, (void)C, (void)sigma, (void)L, (void)mats, (void)p_ptr, (void)p_col, (void)p_val, (void)stage_ms;
+  fprintf(stderr, "MG: the Galerkin hierarchy is double precision only\n");
+  exit(EXIT_FAILURE);
+#else
+  mg_level* lev = (mg_level*)calloc((size_t)L + 1, sizeof *lev);
+  int nx = param->nx, ny = param->ny, nz = param->nz;
+  const void* fine = fine_dev;
+  for (int l = 1; l < L; l++) {
+    mg_level* v    = &lev[l];
+    const size_t n = (size_t)nx * ny * nz;
+    v->pptr = (uint64_t*)malloc((n + 1) * sizeof(uint64_t)), v->pcol = (CG_UINT*)malloc(8 * n * sizeof(CG_UINT));
+    v->pval = (double*)malloc(8 * n * sizeof(double));
+    sbh_mg_trilinear(nx, ny, nz, v->pptr, v->pcol, v->pval);
+    nx /= 2, ny /= 2, nz /= 2;
+    const CG_UINT nc = (CG_UINT)((size_t)nx * ny * nz);
+    sb_csr* ac       = sb_matrix_galerkin((const sb_matrix*)fine, nc, v->pptr, v->pcol, v->pval);
+    const uint64_t nnz = sb_csr_nnz(ac);
+    uint64_t* ptr    = (uint64_t*)malloc(((size_t)nc + 1) * sizeof(uint64_t));
+    CG_UINT* col     = (CG_UINT*)malloc((nnz + 1) * sizeof(CG_UINT));
+    double* val      = (double*)malloc((nnz + 1) * sizeof(double));
+    double st[6];
+    sb_csr_copy(ac, ptr, col, val), sb_csr_stats(ac, st), sb_csr_free(ac);
+    if (stage_ms) stage_ms[2 * (l - 1)] = st[0], stage_ms[2 * (l - 1) + 1] = st[1];
+    sbh_gmatrix_from_csr(&v->gm, nc, ptr, col, val);
+    free(ptr), free(col), free(val);
+    Comm cc;
+    memset(&cc, 0, sizeof cc);
+    cc.size = 1;
+    commPartition(&cc, &v->gm);
+    if (fmt == 0) {
+      sbh_convert_crs(&v->crs, &v->gm);
+      v->dev = v->crs.dev;
+    } else {
+      v->scs.C = C, v->scs.sigma = sigma;
+      sbh_convert_scs(&v->scs, &v->gm);
+      v->dev = v->scs.dev;
+    }
+    mats[l - 1] = v->dev, p_ptr[l - 1] = v->pptr, p_col[l - 1] = v->pcol, p_val[l - 1] = v->pval;
+    fine = v->dev;
+  }
+  return lev;
+#endif
 }
 
 void sbh_mg_hierarchy_free(void* hierarchy, int fmt, int L)

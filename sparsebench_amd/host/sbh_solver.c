@@ -352,7 +352,8 @@ static void mg_refuse(const char* msg)
 }
 
 /* fw 1: the trilinear prolongations and omega = 0.5 in the injection maps' place; fw 2: those prolongations with
- * omega = 0.25 and the Chebyshev polynomial (steps per smoothing; 0: the default 2; ratio 4) as the smoother */
+ * omega = 0.25 and the Chebyshev polynomial (steps per smoothing; 0: the default 2; ratio 4) as the smoother;
+ * fw 3: fw 2 on Galerkin coarse operators formed on the device, omega = 1.0 */
 static int solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
     CG_UINT sigma, int levels, int fw, int steps)
 {
@@ -366,11 +367,22 @@ static int solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT 
   if (!L) mg_refuse(why);
   const void** mats    = (const void**)calloc((size_t)L, sizeof *mats);
   const CG_UINT** maps = (const CG_UINT**)calloc((size_t)L, sizeof *maps);
-  void* hierarchy      = sbh_mg_hierarchy_build(param, fmt, C, sigma, L, mats, maps);
+  const uint64_t** gptr = (const uint64_t**)calloc((size_t)L, sizeof *gptr);
+  const CG_UINT** gcol  = (const CG_UINT**)calloc((size_t)L, sizeof *gcol);
+  const double** gval   = (const double**)calloc((size_t)L, sizeof *gval);
+  double* gms           = (double*)calloc(2 * (size_t)L, sizeof *gms);
+  void* hierarchy = fw == 3 ? sbh_mg_hierarchy_build_galerkin(param, dev_matrix, fmt, C, sigma, L, mats, gptr, gcol, gval, gms)
+                            : sbh_mg_hierarchy_build(param, fmt, C, sigma, L, mats, maps);
   double *b, *xexact;
   init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
   sb_pcg* s;
-  if (fw) {
+  if (fw == 3) {
+    double* omega = (double*)calloc((size_t)L, sizeof *omega);
+    for (int l = 0; l + 1 < L; l++) omega[l] = 1.0;
+    s = sb_pcg_create_mg_poly((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats,
+        (const uint64_t* const*)gptr, (const uint32_t* const*)gcol, (const double* const*)gval, omega, steps ? steps : 2, 0, 0.0, 0.0);
+    free(omega);
+  } else if (fw) {
     uint64_t** ptr  = (uint64_t**)calloc((size_t)L, sizeof *ptr);
     CG_UINT** col   = (CG_UINT**)calloc((size_t)L, sizeof *col);
     double** val    = (double**)calloc((size_t)L, sizeof *val);
@@ -393,17 +405,22 @@ static int solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT 
   } else {
     s = sb_pcg_create_mg((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats, maps);
   }
-  if (fw == 2 && commIsMaster(comm)) {
+  if (fw >= 2 && commIsMaster(comm)) {
     double iv[2];
     sb_pcg_mg_poly_interval(s, 0, iv);
-    printf("Preconditioner: MG (V-cycle, full-weighting transfers, Chebyshev polynomial smoother), levels = %d, steps = %d, "
-           "lambda in [%.6g, %.6g]\n", sb_pcg_levels(s), sb_pcg_poly_steps(s), iv[0], iv[1]);
+    printf("Preconditioner: MG (V-cycle, full-weighting transfers, Chebyshev polynomial smoother%s), levels = %d, steps = %d, "
+           "lambda in [%.6g, %.6g]\n", fw == 3 ? ", Galerkin coarse operators" : "", sb_pcg_levels(s), sb_pcg_poly_steps(s), iv[0], iv[1]);
+    if (fw == 3) {
+      printf("Galerkin products P^T A P on the device, ms (A P + P^T (A P)):");
+      for (int l = 1; l < L; l++) printf(" level %d: %.3f + %.3f%s", l, gms[2 * (l - 1)], gms[2 * (l - 1) + 1], l + 1 < L ? "," : "");
+      printf("\n");
+    }
   } else if (commIsMaster(comm))
     printf("Preconditioner: MG (V-cycle, %smulticolour SGS smoother), levels = %d, nC = %d\n", fw ? "full-weighting transfers, " : "",
         sb_pcg_levels(s), sb_pcg_colours(s));
   const int k = run_pcg(comm, param, s, b, xexact);
   sbh_mg_hierarchy_free(hierarchy, fmt, L);
-  free(mats), free(maps);
+  free(mats), free(maps), free(gptr), free(gcol), free(gval), free(gms);
   return k;
 }
 int sbh_solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
@@ -420,6 +437,12 @@ int sbh_solve_pcg_mgpoly(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT
     CG_UINT sigma, int levels, int steps)
 {
   return solve_pcg_mg(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, levels, 2, steps);
+}
+
+int sbh_solve_pcg_mgpoly_galerkin(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt,
+    CG_UINT C, CG_UINT sigma, int levels, int steps)
+{
+  return solve_pcg_mg(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, levels, 3, steps);
 }
 
 /* ---- solveBiCGStab ----------------------------------------------------------------------- */

@@ -67,6 +67,8 @@ def host(precision="double"):
     H.sbh_problem_rhs.restype = C.c_int
     H.sbh_problem_rhs.argtypes = [vp, vp, vp]
     H.sbh_problem_free.argtypes = [vp]
+    H.sbh_problem_create_csr.restype = vp
+    H.sbh_problem_create_csr.argtypes = [C.c_uint, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
     H.commSetExchange.argtypes = [vp]
     H.MMMatrixRead.argtypes = [vp, C.c_char_p]
     H.commDistributeMatrix.argtypes = [vp, vp, vp]
@@ -140,12 +142,60 @@ def _write_mtx(path, A):
                                                               A.data[a:a + step].tolist())))
 
 
-def mg_galerkin(problem, levels=None, directory=None, _owned=None):
+def galerkin_product(problem, P, n_coarse=None):
+    """A_c = P^T A P of an uploaded double-precision one-rank problem, formed on the device (sb_matrix_galerkin): P a
+    scipy.sparse matrix or a (ptr, col, val) CSR triple of nr x n_c, original numbering on both sides (n_coarse: n_c of a triple
+    whose last coarse columns no row touches; None: its largest column + 1).  Returns ((ptr uint64, col
+    uint32, val float64) in the coarse level's original numbering, columns ascending, exact zeros dropped, and the stats dict)"""
+    if getattr(problem, "precision", "double") != "double":
+        raise ValueError("galerkin_product: double precision only (the problem was built with precision=%r)" % (problem.precision,))
+    if problem.nr != problem.totalNr:
+        raise ValueError("galerkin_product runs on one rank")
+    if not problem.upload:
+        raise ValueError("galerkin_product reads the uploaded matrix: the problem was built with upload=False")
+    if n_coarse is not None:
+        nc = int(n_coarse)
+    elif hasattr(P, "tocsr"):
+        nc = P.shape[1]
+    else:
+        try:
+            nc = int(np.max(P[1])) + 1 if len(P[1]) else 1
+        except (TypeError, ValueError, IndexError):
+            raise ValueError("P of level 0 must be a scipy.sparse matrix or a (ptr, col, val) triple")
+    return _galerkin_product(problem, P, nc)
+
+
+def _galerkin_product(problem, P, nc):
+    ptr, col, val = _p_triple(P, problem.nr, int(nc), 0)
+    L = capi.load()
+    h = L.sb_matrix_galerkin(problem.matrix, int(nc), ptr.ctypes.data_as(vp), col.ctypes.data_as(vp), val.ctypes.data_as(vp))
+    try:
+        n, nnz = L.sb_csr_rows(h), L.sb_csr_nnz(h)
+        out = (np.empty(n + 1, dtype=np.uint64), np.empty(nnz, dtype=np.uint32), np.empty(nnz, dtype=np.float64))
+        st = np.zeros(6)
+        L.sb_csr_copy(h, *[a.ctypes.data_as(vp) for a in out])
+        L.sb_csr_stats(h, st.ctypes.data_as(vp))
+    finally:
+        L.sb_csr_free(h)
+    return out, {"stage1_ms": float(st[0]), "stage2_ms": float(st[1]), "t_entries": int(st[2]), "dropped": int(st[3]),
+                 "max_row_t": int(st[4]), "max_row_ac": int(st[5])}
+
+
+def mg_galerkin(problem, levels=None, directory=None, _owned=None, product="scipy"):
     """the Galerkin hierarchy of a generated problem for PCG(precond="mgpoly", coarse=...): [(Problem, P, 1.0), ...] with the
     trilinear P per level and A_{l+1} = P_l^T A_l P_l, formed by scipy.sparse in CSR with sorted columns and exact zeros dropped,
     written with 17 significant digits as level<l>.mtx into `directory` (None: a new temporary one) and opened as Problems of the
     fine problem's format, C and sigma.  omega is 1.0: scaling A_c and the restriction together cancels in the cycle.  The caller
-    frees the problems and removes the files (PCG(galerkin=True) does both with the handle).  ImportError without scipy."""
+    frees the problems and removes the files (PCG(galerkin=True) does both with the handle).  ImportError without scipy.
+    product="device": the same list with every A_{l+1} formed on the device from level l's uploaded matrix (galerkin_product,
+    DESIGN 4.17) and opened with Problem.from_csr -- no scipy, no files, no directory; each Problem carries the product's stats as
+    `galerkin_stats` (PCG(galerkin="device") frees the problems with the handle)."""
+    if product not in ("scipy", "device"):
+        raise ValueError("product must be 'scipy' or 'device', got %r" % (product,))
+    if product == "device":
+        if directory is not None:
+            raise ValueError("product='device' writes no files: it takes no directory")
+        return _mg_galerkin_device(problem, levels, _owned)
     try:
         import scipy.sparse as sp
     except ImportError:
@@ -180,6 +230,32 @@ def mg_galerkin(problem, levels=None, directory=None, _owned=None):
         if _owned is not None:
             _owned.append(q)
         out.append((q, triple, 1.0))
+    return out
+
+
+def _mg_galerkin_device(problem, levels, _owned):
+    name = getattr(problem, "filename", None)
+    if name not in ("generate", "generate7P"):
+        raise ValueError("mg_galerkin needs the grid: %r is not a generated problem" % (name,))
+    if problem.nr != problem.totalNr:
+        raise ValueError("mg_galerkin runs on one rank")
+    if getattr(problem, "precision", "double") != "double":
+        raise ValueError("mg_galerkin: double precision only (the problem was built with precision=%r)" % (problem.precision,))
+    if not problem.upload:
+        raise ValueError("mg_galerkin(product='device') reads the uploaded matrices: the problem was built with upload=False")
+    dims = problem.dims
+    nlev = mg_levels(*dims, levels=levels)
+    out, fine = [], problem
+    for _ in range(nlev - 1):
+        triple = mg_trilinear(*dims)
+        dims = tuple(d // 2 for d in dims)
+        (ptr, col, val), stats = _galerkin_product(fine, triple, dims[0] * dims[1] * dims[2])
+        q = Problem.from_csr(ptr, col, val, fmt=problem.fmt, Cc=problem.Cc, sigma=problem.sigma_arg)
+        q.galerkin_stats = stats
+        if _owned is not None:
+            _owned.append(q)
+        out.append((q, triple, 1.0))
+        fine = q
     return out
 
 
@@ -275,6 +351,28 @@ class Problem:
                 L.sb_set_sp_mirror(old)
         for i, name in enumerate(_SCALARS):
             setattr(self, name, int(self.H.sbh_problem_scalar(self.ptr, i)))
+
+    @classmethod
+    def from_csr(cls, ptr, col, val, fmt="scs", Cc=64, sigma=1, upload=True):
+        """a one-rank double-precision Problem from CSR in memory (sbh_problem_create_csr): the layout, array for array, that
+        Problem(file.mtx) gives for the same entries; filename "memory".  upload=False: the host layout only, no GPU"""
+        ptr = np.ascontiguousarray(ptr, dtype=np.uint64)
+        col = np.ascontiguousarray(col, dtype=np.uint32)
+        val = np.ascontiguousarray(val, dtype=np.float64)
+        if ptr.ndim != 1 or len(ptr) < 1 or col.shape != val.shape or col.ndim != 1 or int(ptr[-1]) != len(col) or int(ptr[0]) != 0:
+            raise ValueError("from_csr: %d row pointers from %r to %r, %d columns, %d values"
+                             % (len(ptr), ptr[:1].tolist(), ptr[-1:].tolist(), col.size, val.size))
+        if len(col) and int(col.max()) >= len(ptr) - 1:
+            raise ValueError("from_csr: column %d is outside the %d rows" % (int(col.max()), len(ptr) - 1))
+        self = cls.__new__(cls)
+        self.H = host("double")
+        self.precision, self.fdtype, self.fmt, self.upload = "double", np.float64, fmt, upload
+        self.filename, self.dims, self.Cc, self.sigma_arg = "memory", (1, 1, 1), Cc, sigma
+        self.ptr = self.H.sbh_problem_create_csr(len(ptr) - 1, ptr.ctypes.data_as(vp), col.ctypes.data_as(vp), val.ctypes.data_as(vp),
+                                                 0 if fmt == "crs" else 1, Cc, sigma, 1 if upload else 0)
+        for i, name in enumerate(_SCALARS):
+            setattr(self, name, int(self.H.sbh_problem_scalar(self.ptr, i)))
+        return self
 
     def array(self, name):
         n = {"rowPtr": self.nr + 1, "rowNnz": self.nr, "crs_colInd": self.nnzTrue,
@@ -683,7 +781,8 @@ class PCG(_BodySolver):
     ratio default 16.0; takes no dinv.  precond "mgpoly": a V-cycle with that polynomial as the smoother of every level and mgfw's
     transfers: `steps` per smoothing (default 2), `coarse_steps` on the last level (default: steps), ratio default
     4.0, lmax None: every level's own bound; `levels` for the generated hierarchy with the trilinear P and omega = 0.25,
-    `galerkin=True` for mg_galerkin's coarse operators in the regenerated ones' place, or `coarse` as "mgfw" takes it.  Double
+    `galerkin=True` for mg_galerkin's coarse operators in the regenerated ones' place (`galerkin="device"`: the same operators formed on
+    the device, DESIGN 4.17: no scipy, no files), or `coarse` as "mgfw" takes it.  Double
     precision, one rank, tree dot order."""
 
     PREFIX, NAME = "sb_pcg", "PCG"
@@ -705,10 +804,11 @@ class PCG(_BodySolver):
             steps, lmax, ratio = self._poly_args(2 if steps is None else steps, lmax, 4.0 if ratio is None else ratio)
             cs = self._poly_args(steps if coarse_steps is None else coarse_steps, None, None, "coarse_steps")[0]
             poly = (steps, cs, lmax, ratio)
-            if not isinstance(galerkin, (bool, np.bool_)):
-                raise ValueError("galerkin must be True or False, got %r" % (galerkin,))
+            if not isinstance(galerkin, (bool, np.bool_)) and not (isinstance(galerkin, str) and galerkin == "device"):
+                raise ValueError("galerkin must be True or False, or 'device', got %r" % (galerkin,))
             if galerkin and coarse is not None:
-                raise ValueError("galerkin=True builds the coarse operators itself: it takes levels, not coarse")
+                raise ValueError("galerkin=%r builds the coarse operators itself: it takes levels, not coarse"
+                                 % (galerkin if isinstance(galerkin, str) else True,))
         if precond in ("sgs", "mg", "mgfw", "poly", "mgpoly") and dinv is not None:
             raise ValueError("precond=%r takes no dinv: its diagonal is the matrix's own" % (precond,))
         if precond not in ("mg", "mgfw", "mgpoly") and (levels is not None or coarse is not None):
@@ -721,7 +821,7 @@ class PCG(_BodySolver):
         if precond in ("mg", "mgfw", "mgpoly"):
             try:
                 if galerkin:
-                    self._create_galerkin(problem, levels, poly)
+                    self._create_galerkin(problem, levels, poly, device=isinstance(galerkin, str))
                 else:
                     self._create_mg(problem, levels, coarse, precond != "mg", precond, poly)
             except Exception:
@@ -786,10 +886,13 @@ class PCG(_BodySolver):
         self._keep = (coarse, maps)  # the caller's coarse problems must outlive the handle, as the fine one must
         self.ptr = self.L.sb_pcg_create_mg(problem.matrix, problem.halo, _ptr(b), _ptr(xe), n, mats, ptrs)
 
-    def _create_galerkin(self, problem, levels, poly):
-        """mg_galerkin's hierarchy in a temporary directory that goes with the handle"""
-        self._owned_dir = tempfile.mkdtemp(prefix="sb_galerkin_")
-        coarse = mg_galerkin(problem, levels, self._owned_dir, _owned=self._owned)
+    def _create_galerkin(self, problem, levels, poly, device=False):
+        """mg_galerkin's hierarchy in a temporary directory that goes with the handle; device: formed on the device, no directory"""
+        if device:
+            coarse = mg_galerkin(problem, levels, _owned=self._owned, product="device")
+        else:
+            self._owned_dir = tempfile.mkdtemp(prefix="sb_galerkin_")
+            coarse = mg_galerkin(problem, levels, self._owned_dir, _owned=self._owned)
         self._create_mg_p(problem, coarse, "mgpoly", poly)
 
     def _create_mg_p(self, problem, coarse, precond="mgfw", poly=None):
