@@ -705,10 +705,10 @@ void sb_event_destroy(void* ev) { HIP_CHECK(hipEventDestroy((hipEvent_t)ev)); }
 #include "sbhip_cgb.inc.h"
 #include "sbhip_pcg.inc.h"
 #include "sbhip_sgs.inc.h"
+#include "sbhip_poly.inc.h"
 #include "sbhip_mg.inc.h"
 #include "sbhip_mg_fw.inc.h"
-#include "sbhip_poly.inc.h"
-#include "sbhip_mg_poly.inc.h"
+#include "sbhip_precond.inc.h"
 #include "sbhip_galerkin.inc.h"
 #include "sbhip_pcg_loop.inc.h"
 #include "sbhip_bicgstab.inc.h"

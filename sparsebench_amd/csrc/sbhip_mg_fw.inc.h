@@ -1,10 +1,17 @@
-// sbhip_mg_fw.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context): the second
-// transfer mode of the multigrid V-cycle of sbhip_mg.inc.h (kernels: mg_fw.hip.h).  Per level but the last a
-// prolongation P_l (n_l x n_{l+1}, the caller's CSR in original numbering on both sides) and the restriction omega_l P_l^T of the
-// FULL residual stand in for the injection.  The levels, the smoother, the handle and the loop are sbhip_mg.inc.h's.
+// sbhip_mg_fw.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context): the
+// full-weighting transfers between the levels of a preconditioner plan (sbhip_mg.inc.h) as a caller gives them (DESIGN 4.14;
+// kernels: mg_fw.hip.h): per level but the last a prolongation P_l (n_l x n_{l+1}, the caller's CSR in original numbering on both
+// sides) and the restriction omega_l P_l^T of the FULL residual.  Here: their checks, the structures built from them, and the
+// probes that run one level's transfers alone.  Their launches are the cycle's, in sbhip_mg.inc.h.
 // ===========================================================================
 // full-weighting transfers
 // ===========================================================================
+struct MgFwArgs {
+  const uint64_t* const* ptr;
+  const uint32_t* const* col;
+  const double* const* val;
+  const double* omega;
+};
 
 // every refusal of level l's prolongation, before anything is built
 static void mg_fw_check(const char* fn, const MgFwArgs& a, int l, uint32_t nFine, uint32_t nCoarseRows)
@@ -45,7 +52,7 @@ SellRows mg_fw_sell(const HostRows& R, uint32_t* nChunksOut, double* bytes)
 // level l's two structures from its (checked) prolongation: P in this level's device order with the next level's device rows
 // as columns, entries in the caller's storage order; P^T the other way round, a coarse row's entries in ascending ORIGINAL fine
 // row number (equal rows: storage order).  A stored weight of 0.0 is dropped from both
-static void mg_fw_transfers(MgLevel& F, const sb_matrix* coarse, const MgFwArgs& a, int l)
+static void mg_fw_transfers(PrecondLevel& F, const sb_matrix* coarse, const MgFwArgs& a, int l)
 {
   const uint32_t nf = F.n, ncs = coarse->nr;
   const std::vector<uint32_t> fo2n = old_to_device_rows(F.A), co2n = old_to_device_rows(coarse);
@@ -71,84 +78,90 @@ static void mg_fw_transfers(MgLevel& F, const sb_matrix* coarse, const MgFwArgs&
       }
     }
   }
-  F.nCoarse = ncs;
-  F.omega   = a.omega[l];
-  F.PT      = mg_fw_sell(pt, &F.nPTChunks, &F.transferBytes);
-  F.Pm      = mg_fw_sell(p, &F.nPChunks, &F.transferBytes);
+  F.nCoarse  = ncs;
+  F.fw.omega = a.omega[l];
+  F.fw.PT    = mg_fw_sell(pt, &F.fw.nPTChunks, &F.fw.transferBytes);
+  F.fw.Pm    = mg_fw_sell(p, &F.fw.nPChunks, &F.fw.transferBytes);
 }
-// ... and the level's diagonal and d, which the full residual needs
-static void mg_fw_build(MgLevel& F, const sb_matrix* coarse, const MgFwArgs& a, int l)
+// ... and under the sweeps the level's diagonal and d, which the full residual needs
+static void mg_fw_build(PrecondLevel& F, const sb_matrix* coarse, const MgFwArgs& a, int l)
 {
   mg_fw_transfers(F, coarse, a, l);
   const size_t nb = (size_t)F.n * sizeof(double) + 4096;
-  F.diag = (double*)sb_malloc(nb), F.d = (double*)sb_malloc(nb);
-  launch_diagonal(F.A, F.diag, nullptr);
+  F.fw.diag = (double*)sb_malloc(nb), F.fw.d = (double*)sb_malloc(nb);
+  launch_diagonal(F.A, F.fw.diag, nullptr);
   HIP_CHECK(hipStreamSynchronize(g.stream));
 }
 
-static void mg_fw_free(MgLevel& V)
+namespace {
+// The two probes run the transfers of level l alone on scratch vectors of their own: three of level l's rows, two of level
+// l + 1's, in the levels' original row order on the host.  A NULL host vector is neither uploaded nor downloaded
+struct ProbeVecs {
+  const sb_matrix *F, *C;
+  double *f[3], *c[2];
+};
+ProbeVecs probe_upload(const PrecondLevel& V, const PrecondLevel& C, const double* const (&f_host)[3], const double* const (&c_host)[2])
 {
-  sell64_free(V.PT), sell64_free(V.Pm);
-  sb_free(V.diag), sb_free(V.d);
-  V.diag = V.d = nullptr;
+  ProbeVecs p = { V.A, C.A, {}, {} };
+  for (int i = 0; i < 3; i++) {
+    p.f[i] = (double*)sb_malloc((size_t)V.n * sizeof(double) + 4096);
+    if (f_host[i]) upload_permuted(p.F, f_host[i], p.f[i]);
+  }
+  for (int i = 0; i < 2; i++) {
+    p.c[i] = (double*)sb_malloc((size_t)C.n * sizeof(double) + 4096);
+    if (c_host[i]) upload_permuted(p.C, c_host[i], p.c[i]);
+  }
+  return p;
 }
+void probe_download(ProbeVecs& p, double* const (&f_out)[3], double* const (&c_out)[2])
+{
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  for (int i = 0; i < 3; i++) {
+    if (f_out[i]) download_original(p.F, p.f[i], f_out[i]);
+    sb_free(p.f[i]);
+  }
+  for (int i = 0; i < 2; i++) {
+    if (c_out[i]) download_original(p.C, p.c[i], c_out[i]);
+    sb_free(p.c[i]);
+  }
+}
+} // namespace
 
-// steps 3 and 4: d = r - A z over every row in one launch, rc = omega P^T d
-static void mg_fw_restrict(const MgLevel& V, const double* r, const double* z, double* rc, const int* stop)
-{
-  const SgsPlan* P = V.P;
-  if (P->nChunks)
-    hipLaunchKernelGGL(mg_residual_k, dim3((P->nChunks + 3u) / 4u), dim3(256), 0, g.stream, P->nChunks, (const uint32_t*)P->rowIdx,
-        P->half[0], P->half[1], r, z, (const double*)V.diag, V.d, stop);
-  if (V.nPTChunks)
-    hipLaunchKernelGGL(mg_restrict_pt_k, dim3((V.nPTChunks + 3u) / 4u), dim3(256), 0, g.stream, V.nPTChunks, V.nCoarse, V.PT, V.omega,
-        (const double*)V.d, rc, stop);
-}
-// step 6: z = z + P zc
-static void mg_fw_prolong(const MgLevel& V, const double* zc, double* z, const int* stop)
-{
-  if (V.nPChunks)
-    hipLaunchKernelGGL(mg_prolong_p_k, dim3((V.nPChunks + 3u) / 4u), dim3(256), 0, g.stream, V.nPChunks, V.Pm, zc, z, stop);
-}
-
-// bytes the transfers of one level read and write: the residual reads both halves of the sweep structure and r, z, diag per
-// row and writes d; the restriction reads its structure and d and writes rc; the prolongation its structure and zc, z in and out
-static double mg_fw_bytes(const MgLevel& V)
-{
-  return V.P->halfBytes[0] + V.P->halfBytes[1] + 32.0 * (double)V.n // the residual
-         + V.transferBytes + 8.0 * (double)V.n + 8.0 * (double)V.nCoarse // P^T, d in, rc out
-         + 8.0 * (double)V.nCoarse + 16.0 * (double)V.n;                // P (counted above), zc in, z in and out
-}
-
-sb_pcg* sb_pcg_create_mg_p(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int nCoarse,
-    const sb_matrix* const* coarse, const uint64_t* const* p_ptr, const uint32_t* const* p_col, const double* const* p_val,
-    const double* omega)
-{
-  const MgFwArgs a = { p_ptr, p_col, p_val, omega };
-  return mg_create("sb_pcg_create_mg_p", m, halo, b_host, xexact_host, nCoarse, coarse, nullptr, &a);
-}
-
-// steps 3, 4 and 6 on level l alone, on scratch vectors: d and rc from (r, z), z_out = z after prolonging zc.  r, z, d_out and
-// z_out in level l's original row order, zc and rc_out in level l + 1's
+// steps 3, 4 and 6 on level l alone: d and rc from (r, z), z_out = z after prolonging zc.  r, z, d_out and z_out in level l's
+// original row order, zc and rc_out in level l + 1's
 void sb_pcg_mg_fw_probe(sb_pcg* s, int l, const double* r_host, const double* z_host, const double* zc_host, double* d_out,
     double* rc_out, double* z_out)
 {
   need_init();
-  if (!s->mg || !s->mg->fw) SB_FATAL("sb_pcg_mg_fw_probe: the handle has no full-weighting transfers (sb_pcg_create_mg_p makes them)");
+  if (!s->pre || s->pre->kind != 3)
+    SB_FATAL("sb_pcg_mg_fw_probe: the handle has no full-weighting transfers (sb_pcg_create_mg_p makes them)");
   if (s->clock.open) SB_FATAL("sb_pcg_mg_fw_probe between sb_pcg_start and sb_pcg_finish: the solve's vectors are in flight");
-  const int L = (int)s->mg->lev.size();
+  const int L = (int)s->pre->lev.size();
   if (l < 0 || l + 1 >= L) SB_FATAL("sb_pcg_mg_fw_probe: level %d of a handle with %d levels has no transfers", l, L);
-  MgLevel V        = s->mg->lev[l]; // a copy: its d is the probe's own
-  const MgLevel& C = s->mg->lev[l + 1];
-  const size_t nf = (size_t)V.n * sizeof(double) + 4096, nc = (size_t)C.n * sizeof(double) + 4096;
-  double *r = (double*)sb_malloc(nf), *z = (double*)sb_malloc(nf), *d = (double*)sb_malloc(nf);
-  double *zc = (double*)sb_malloc(nc), *rc = (double*)sb_malloc(nc);
-  upload_permuted(V.A, r_host, r), upload_permuted(V.A, z_host, z), upload_permuted(C.A, zc_host, zc);
-  V.d = d;
-  mg_fw_restrict(V, r, z, rc, zero_flag());
-  mg_fw_prolong(V, zc, z, zero_flag());
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  download_original(V.A, d, d_out), download_original(C.A, rc, rc_out), download_original(V.A, z, z_out);
-  sb_free(r), sb_free(z), sb_free(d), sb_free(zc), sb_free(rc);
+  PrecondLevel V = s->pre->lev[l]; // a copy: its d is the probe's own
+  ProbeVecs p    = probe_upload(V, s->pre->lev[l + 1], { r_host, z_host, nullptr }, { zc_host, nullptr });
+  V.fw.d         = p.f[2];
+  mg_fw_restrict(V, p.f[0], p.f[1], p.c[1], zero_flag());
+  mg_fw_prolong(V, p.c[0], p.f[1], zero_flag());
+  probe_download(p, { nullptr, z_out, d_out }, { nullptr, rc_out });
+}
+
+// steps 4 and 6 of the Chebyshev-smoothed cycle on level l alone: rc = omega P^T (r - w), z_out = z after prolonging zc.  r, w,
+// z and z_out in level l's original row order, zc and rc_out in level l + 1's
+void sb_pcg_mg_poly_probe(sb_pcg* s, int l, const double* r_host, const double* w_host, const double* z_host, const double* zc_host,
+    double* rc_out, double* z_out)
+{
+  need_init();
+  const char* fn = "sb_pcg_mg_poly_probe";
+  if (!s->pre || s->pre->kind != 5)
+    SB_FATAL("%s: the handle has another preconditioner (sb_pcg_create_mg_poly makes the Chebyshev-smoothed cycle)", fn);
+  if (s->clock.open) SB_FATAL("%s between sb_pcg_start and sb_pcg_finish: the solve's vectors are in flight", fn);
+  const int L = (int)s->pre->lev.size();
+  if (l < 0 || l + 1 >= L) SB_FATAL("%s: level %d of a handle with %d levels has no transfers", fn, l, L);
+  const PrecondLevel& V = s->pre->lev[l];
+  ProbeVecs p           = probe_upload(V, s->pre->lev[l + 1], { r_host, w_host, z_host }, { zc_host, nullptr });
+  mgp_restrict(V, p.f[0], p.f[1], p.c[1], zero_flag());
+  mg_fw_prolong(V, p.c[0], p.f[2], zero_flag());
+  probe_download(p, { nullptr, nullptr, z_out }, { nullptr, rc_out });
 }

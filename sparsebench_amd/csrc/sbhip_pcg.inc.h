@@ -19,10 +19,9 @@ struct sb_pcg {
   int hist_cap = 0;
   int k_next = 1;
   LoopClock clock;
-  struct SgsPlan* sgs = nullptr; // symmetric Gauss-Seidel in place of the diagonal (sbhip_sgs.inc.h); dinv is 1 / diag(A)
-  struct MgPlan* mg = nullptr;   // a multigrid V-cycle around it (sbhip_mg.inc.h); `sgs` is then level 0's smoother
-  struct PolyPlan* poly = nullptr; // a Chebyshev polynomial in D^-1 A in the diagonal's place (sbhip_poly.inc.h)
-  struct MgPolyPlan* mgp = nullptr; // a V-cycle with that polynomial as the smoother of every level (sbhip_mg_poly.inc.h)
+  // owned; NULL: the diagonal, which rides in pcg_update_r_k.  Else the sweeps, the polynomial or a V-cycle of either in its
+  // place (sbhip_mg.inc.h); dinv is then 1 / diag(A) and level 0's
+  struct PrecondPlan* pre = nullptr;
 };
 // the diagonal in the device's row order; bad_dev: NULL, or two uint32 (rows without a finite positive diagonal, the first of
 // them) preset to {0, 0xFFFFFFFF}

@@ -1,76 +1,57 @@
 // sbhip_pcg_loop.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context): the loop
-// of preconditioned CG and the one place that asks how the handle's z is made: the diagonal (riding in the r
-// update), the sweeps (sbhip_sgs.inc.h), the V-cycle (sbhip_mg.inc.h, sbhip_mg_fw.inc.h) or the
-// Chebyshev polynomial (sbhip_poly.inc.h), alone or as the smoother of a V-cycle (sbhip_mg_poly.inc.h).
-// Included behind those files, so nothing here is declared ahead of its definition; the handle is sbhip_pcg.inc.h's.
+// of preconditioned CG and the one place that asks how the handle's z is made: by the diagonal (riding in the r
+// update), or by the V-cycle of the handle's plan (sbhip_mg.inc.h), smoothed by the sweeps or by the
+// Chebyshev polynomial.  Included behind the plan's files, so nothing here is declared ahead of its definition; the handle is
+// sbhip_pcg.inc.h's.
 // ===========================================================================
 // preconditioned CG: z and the loop
 // ===========================================================================
-int sb_pcg_precond(const sb_pcg* s) { return s->mgp ? 5 : s->poly ? 4 : s->mg ? (s->mg->fw ? 3 : 2) : s->sgs ? 1 : 0; }
 
-// z = M^-1 r with the handle's preconditioner: r o dinv, the sweeps of its matrix, or the V-cycle around them (t: the forward
-// sums of level 0; the diagonal does not touch it), or the polynomial on the handle's own d and w
+// z = M^-1 r with the handle's preconditioner: r o dinv, or the cycle of its plan (t: the sweeps' forward sums of level 0; the
+// diagonal and the polynomial do not touch it)
 static void precond_apply(const sb_pcg* s, const double* r, double* t, double* z, const int* stop)
 {
-  if (s->mgp) return mgp_apply(s, r, z, stop, false, nullptr);
-  if (s->poly) return poly_apply(s->A, (const double*)s->dinv, s->poly->c, r, z, s->poly->d, s->poly->w, stop);
-  if (s->mg) return mg_apply(s, r, t, z, stop);
-  if (s->sgs) return sgs_apply(s->sgs, (const double*)s->dinv, r, t, z, stop);
+  if (s->pre) return precond_cycle(s->pre, r, t, z, stop, false, nullptr);
   if (!s->nr) return;
   hipLaunchKernelGGL(precond_diag_k, dim3(stream_grid(s->nr, 256)), dim3(256), 0, g.stream, s->nr, r, (const double*)s->dinv, z);
   HIP_CHECK(hipGetLastError());
 }
 
 // the r update (PRO 1: the prologue's b - Ap) with the r.r values, z and the r.z values.  The diagonal: all of it in
-// pcg_update_r_k.  Sweeps and V-cycle: the r update without z, the apply, r.z by dot_l1_k.  The polynomial: step 1 in
-// poly_update_r_k, the steps behind it by poly_steps, the last of them with the r.z values.  The Chebyshev-smoothed cycle: level
-// 0's step 1 in poly_update_r_k, the rest by mgp_apply, whose last kernel on level 0 makes the r.z values
+// pcg_update_r_k.  The polynomial, alone or in a cycle: level 0's step 1 in poly_update_r_k, the rest by the cycle, whose last
+// kernel on level 0 makes the r.z values (one level of one step: poly_update_r_k itself).  The sweeps, alone or in a cycle: the r
+// update without z, the cycle, r.z by dot_l1_k
 template <int PRO> static void pcg_residual_and_z(sb_pcg* s)
 {
   const uint32_t n = s->nr;
   if (!n) return;
-  const int* stop   = &s->S->stop; // (0 throughout the prologue: sb_pcg_start has just written the block)
-  const double* src = PRO ? s->b : s->r;
+  const int* stop      = &s->S->stop; // (0 throughout the prologue: sb_pcg_start has just written the block)
+  const double* src    = PRO ? s->b : s->r;
+  const PrecondPlan* M = s->pre;
   const dim3 grid(vec_stream_grid(n)), block(1024);
-  if (s->mgp) {
-    const MgPolyLevel& V = s->mgp->lev[0];
-    if (s->mgp->lev.size() == 1 && V.c.steps == 1)
-      hipLaunchKernelGGL((poly_update_r_k<PRO, 1>), grid, block, 0, g.stream, n, (const double*)s->Ap, src, s->r, (const double*)s->dinv,
-          V.d, s->z, V.c.c1, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
-    else
-      hipLaunchKernelGGL((poly_update_r_k<PRO, 0>), grid, block, 0, g.stream, n, (const double*)s->Ap, src, s->r, (const double*)s->dinv,
-          V.d, s->z, V.c.c1, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
-    mgp_apply(s, s->r, s->z, stop, true, s->l1rz);
-  } else if (s->poly) {
-    const PolyPlan* P = s->poly;
-    if (P->c.steps == 1)
-      hipLaunchKernelGGL((poly_update_r_k<PRO, 1>), grid, block, 0, g.stream, n, (const double*)s->Ap, src, s->r, (const double*)s->dinv,
-          P->d, s->z, P->c.c1, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
-    else
-      hipLaunchKernelGGL((poly_update_r_k<PRO, 0>), grid, block, 0, g.stream, n, (const double*)s->Ap, src, s->r, (const double*)s->dinv,
-          P->d, s->z, P->c.c1, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
-    poly_steps(s->A, (const double*)s->dinv, P->c, s->r, s->z, P->d, P->w, stop, s->l1rz);
-  } else if (!s->sgs) {
+  if (!M) {
     hipLaunchKernelGGL(pcg_update_r_k<PRO>, grid, block, 0, g.stream, n, (const double*)s->Ap, src, s->r, (const double*)s->dinv, s->z,
         (const PcgScalars*)s->S, s->l1rz, s->l1rr);
+  } else if (M->smoother == SMOOTH_CHEB) {
+    const PrecondLevel& V = M->lev[0];
+    if (M->lev.size() == 1 && V.cheb.c.steps == 1)
+      hipLaunchKernelGGL((poly_update_r_k<PRO, 1>), grid, block, 0, g.stream, n, (const double*)s->Ap, src, s->r, (const double*)s->dinv,
+          V.cheb.d, s->z, V.cheb.c.c1, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
+    else
+      hipLaunchKernelGGL((poly_update_r_k<PRO, 0>), grid, block, 0, g.stream, n, (const double*)s->Ap, src, s->r, (const double*)s->dinv,
+          V.cheb.d, s->z, V.cheb.c.c1, (const PcgScalars*)s->S, s->l1rz, s->l1rr);
+    precond_cycle(M, s->r, nullptr, s->z, stop, true, s->l1rz);
   } else {
     hipLaunchKernelGGL(sgs_update_r_k<PRO>, grid, block, 0, g.stream, n, (const double*)s->Ap, src, s->r, (const PcgScalars*)s->S,
         s->l1rr);
-    precond_apply(s, s->r, s->sgs->t, s->z, stop);
+    precond_cycle(M, s->r, M->lev[0].sgs->t, s->z, stop, false, nullptr);
     hipLaunchKernelGGL(dot_l1_k, grid, block, 0, g.stream, n, (const double*)s->r, (const double*)s->z, s->l1rz, stop);
   }
   HIP_CHECK(hipGetLastError());
 }
 
-// bytes one apply reads and writes.  Diagonal: r, dinv in, z out.  SGS: sgs_bytes.  MG: mg_bytes.  Polynomial: poly_bytes.
-// Chebyshev-smoothed cycle: mgp_bytes
-double sb_pcg_precond_bytes(const sb_pcg* s)
-{
-  if (s->mgp) return mgp_bytes(s);
-  if (s->poly) return poly_bytes(s);
-  if (!s->sgs) return 24.0 * (double)s->nr;
-  return s->mg ? mg_bytes(s) : sgs_bytes(s->sgs, s->nr);
-}
+// bytes one apply reads and writes.  The diagonal: r, dinv in, z out
+double sb_pcg_precond_bytes(const sb_pcg* s) { return s->pre ? precond_cycle_bytes(s->pre) : 24.0 * (double)s->nr; }
 
 // The two probes run applies outside a solve on scratch vectors of their own, allocated and freed by the call (t: the forward
 // sums, which the diagonal leaves alone)
@@ -116,27 +97,22 @@ void sb_pcg_free(sb_pcg* s)
   if (!s) return;
   HIP_CHECK(hipStreamSynchronize(g.stream));
   s->clock.destroy();
-  mgp_release(s);
-  poly_release(s);
-  mg_release(s);
-  sgs_release(s);
+  precond_release(s);
   sb_free(s->r), sb_free(s->z), sb_free(s->p), sb_free(s->Ap), sb_free(s->x), sb_free(s->b), sb_free(s->dinv), sb_free(s->xexact);
   sb_free(s->S), sb_free(s->l1pAp), sb_free(s->l1rz), sb_free(s->l1rr), sb_free(s->rr_hist), sb_free(s->rz_hist), sb_free(s->pAp_hist);
   delete s;
 }
 
 // launches per loop body: p update | SpMV (+ p.Ap values) | alpha | r update (+ z, r.z and r.r values) | beta = 5 where the
-// selected SpMV kernel has a fused dot; native CRS and generic C add the dot pass: 6.  An SGS handle: the r update makes no z;
-// nC forward and nC - 1 backward launches and the r.z pass stand in between it and beta: 2 nC + 5 (+ 1).  An MG handle: the
-// V-cycle's launches in the sweeps' place: 6 (+ 1) + mg_apply_launches.  A polynomial handle: step 1 rides in the r update, the
-// last step makes the r.z values; an SpMV and a step kernel per step behind the first: 5 (+ 1) + 2 (steps - 1).  A
-// Chebyshev-smoothed cycle: the r update counts among the cycle's launches and no r.z pass follows: 4 (+ 1) + mgp_apply_launches
+// selected SpMV kernel has a fused dot; native CRS and generic C add the dot pass: 6.  The polynomial's plan: the r update counts
+// among the cycle's launches, as level 0's step 1, and the cycle's last kernel makes the r.z values: 4 (+ 1) +
+// precond_cycle_launches.  The sweeps' plan: the r update makes no z, and the r.z pass follows the cycle: 6 (+ 1) +
+// precond_cycle_launches
 int sb_pcg_launches_per_body(const sb_pcg* s)
 {
-  if (s->mgp) return (spmv_dot_kind(s->A) ? 4 : 5) + mgp_apply_launches(s);
-  if (s->poly) return (spmv_dot_kind(s->A) ? 5 : 6) + 2 * (s->poly->c.steps - 1);
-  if (s->mg) return (spmv_dot_kind(s->A) ? 6 : 7) + mg_apply_launches(s);
-  return (spmv_dot_kind(s->A) ? 5 : 6) + (s->sgs ? 2 * sb_pcg_colours(s) : 0);
+  const int base = spmv_dot_kind(s->A) ? 5 : 6;
+  if (!s->pre) return base;
+  return base + (s->pre->smoother == SMOOTH_CHEB ? -1 : 1) + precond_cycle_launches(s->pre);
 }
 
 template <int MODE> static void pcg_scalar_launch(sb_pcg* s)

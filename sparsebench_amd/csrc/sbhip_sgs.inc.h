@@ -1,7 +1,6 @@
 // sbhip_sgs.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context): the symmetric
-// Gauss-Seidel preconditioner of PCG by multicolouring (kernels: sgs.hip.h).  The handle is an sb_pcg whose `sgs`
-// plan is set: the loop, its control block, histories and every other sb_pcg_* call are sbhip_pcg.inc.h's; what differs is how
-// z is made (the r update without z, nC forward launches, nC - 1 backward launches, r.z by dot_l1_k: sbhip_pcg_loop.inc.h).
+// Gauss-Seidel smoother of PCG's preconditioners by multicolouring (kernels: sgs.hip.h, mg.hip.h): its plan for one
+// matrix, and its sweeps from zero and from a guess.  Which handle runs them, on which levels, is sbhip_mg.inc.h's.
 // The host's one packer of Sell-64 gather structures (sell64_pack) lives here with its first user.
 // ===========================================================================
 // multicolour symmetric Gauss-Seidel
@@ -14,7 +13,7 @@ struct SgsPlan {
   SellRows half[2];              // [0] lower / forward, [1] upper / backward; device arrays
   double* t = nullptr;           // the forward sums
   double structBytes = 0.0;      // the sweep structure as one apply reads it
-  double halfBytes[2] = { 0.0, 0.0 }; // each half over all its chunks (a sweep from a guess reads both: sbhip_mg.inc.h)
+  double halfBytes[2] = { 0.0, 0.0 }; // each half over all its chunks (a sweep from a guess reads both: sgs_apply_guess)
   uint32_t rowsBackward = 0;     // rows of the colours 0 .. nC - 2
 };
 
@@ -204,7 +203,6 @@ static SgsPlan* sgs_build(const sb_matrix* m, HostRows h, const char* who)
   P->t = (double*)sb_malloc((size_t)nr * sizeof(double) + 4096);
   return P;
 }
-static SgsPlan* sgs_build(const sb_matrix* m) { return sgs_build(m, sgs_download(m), "sb_pcg_create_sgs"); }
 
 static void sgs_free_plan(SgsPlan* P)
 {
@@ -212,11 +210,6 @@ static void sgs_free_plan(SgsPlan* P)
   sb_free(P->rowIdx), sb_free(P->t);
   for (SellRows& H : P->half) sell64_free(H);
   delete P;
-}
-static void sgs_release(sb_pcg* s)
-{
-  sgs_free_plan(s->sgs);
-  s->sgs = nullptr;
 }
 
 // z = M^-1 r: forward over the colours 0 .. nC-1, backward over nC-2 .. 0; one launch per colour (a wave per chunk)
@@ -234,25 +227,15 @@ static void sgs_apply(const SgsPlan* P, const double* dinv, const double* r, dou
     hipLaunchKernelGGL(sgs_sweep_k<0>, sgs_grid(P, c), dim3(256), 0, g.stream, P->chunk0[c], P->chunk0[c + 1] - P->chunk0[c],
         (const uint32_t*)P->rowIdx, P->half[0], r, dinv, t, z, stop);
   sgs_backward(P, dinv, t, z, stop);
-  HIP_CHECK(hipGetLastError());
 }
 
-sb_pcg* sb_pcg_create_sgs(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host)
+// the forward sweep from the guess in z (both halves of the plan, t kept), then the backward sweep as the apply's
+static void sgs_apply_guess(const SgsPlan* P, const double* dinv, const double* r, double* t, double* z, const int* stop)
 {
-  sb_pcg* s = pcg_create(m, halo, b_host, xexact_host, nullptr, "sb_pcg_create_sgs", "SGS");
-  s->sgs    = sgs_build(m);
-  HIP_CHECK(hipStreamSynchronize(g.stream));
-  return s;
-}
-
-int sb_pcg_colours(const sb_pcg* s) { return s->sgs ? (int)s->sgs->nC : 0; }
-
-void sb_pcg_colouring(const sb_pcg* s, uint32_t* colour_host)
-{
-  need_init();
-  if (!s->sgs) SB_FATAL("sb_pcg_colouring: the handle has a diagonal preconditioner (sb_pcg_create_sgs makes the coloured one)");
-  const std::vector<uint32_t> o2n = old_to_device_rows(s->A);
-  for (uint32_t i = 0; i < s->A->nr; i++) colour_host[i] = s->sgs->colour[o2n[i]];
+  for (uint32_t c = 0; c < P->nC; c++)
+    hipLaunchKernelGGL(mg_sweep_guess_k, sgs_grid(P, c), dim3(256), 0, g.stream, P->chunk0[c], P->chunk0[c + 1] - P->chunk0[c],
+        (const uint32_t*)P->rowIdx, P->half[0], P->half[1], r, dinv, t, z, stop);
+  sgs_backward(P, dinv, t, z, stop);
 }
 
 // bytes one apply reads and writes: the sweep structure, and per row forward r, dinv, one gathered z in, t, z out; backward (the
