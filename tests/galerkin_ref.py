@@ -129,17 +129,18 @@ def underflowing():
 
 def scaled_case(fmt=("crs", 64, 1), steps=2):
     """the two-level solve on the scaled 8^3 matrix with the trilinear P, omega = 1.0 and THIS file's coarse operator:
-    (mg_poly_ref.Hierarchy, operator of level 0, b, eps, (A, P, A_c)); b = 1, eps = 1e-10 ||b||"""
+    (precond_ref.Hierarchy, operator of level 0, b, eps, (A, P, A_c)); b = 1, eps = 1e-10 ||b||"""
     import math
 
     from oracle import pyoracle as po
 
-    import mg_poly_ref as mp
+    import pcg_ref
+    import precond_ref as mp
     A, P = scaled_hpcg8(), mp.trilinear((8, 8, 8))
     Ac = product(A, P, 64)[0]
     gs = [po.GMatrix.from_csr(M[0].astype(np.uint32), M[1], M[2]) for M in (A, Ac)]
-    levels = [(g, mp.operator(g, *fmt)) for g in gs]
-    hier = mp.Hierarchy(levels, [P], [1.0], steps=steps, fmt=fmt)
+    levels = [(g, pcg_ref.operator(g, *fmt)) for g in gs]
+    hier = mp.Hierarchy(mp.MGPOLY, levels, [(P, 1.0)], steps=steps, fmt=fmt)
     op, b = levels[0][1], gs[0].rhs()
     eps = 1e-10 * math.sqrt(po.ddot_tree(op.to_dev(b), op.to_dev(b)))
     return hier, op, b, eps, (A, P, Ac)

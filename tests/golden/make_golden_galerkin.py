@@ -2,7 +2,7 @@
 """Writes tests/golden/galerkin_hist.json from the CPU restatement of the Galerkin product (tests/galerkin_ref.py) alone: per
 hierarchy of galerkin_ref.GOLDEN_PRODUCTS and for the scaled 8^3 matrix, the cancelling and the underflowing case every A_c as
 its nnz and a SHA-256 over the bytes of ptr / col / val, the entries dropped and the row maxima; and of the two-level solve on the
-scaled matrix (mg_poly_ref.Hierarchy over galerkin_ref's operator) at 1 and 2 steps, CRS order and Sell-64-256 order: k, the r.r /
+scaled matrix (precond_ref.Hierarchy over galerkin_ref's operator) at 1 and 2 steps, CRS order and Sell-64-256 order: k, the r.r /
 r.z / p.Ap histories as exact hex doubles and a SHA-256 of x.  Run from the repository root:
   python tests/golden/make_golden_galerkin.py"""
 import json
@@ -13,7 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.dirname(os.path.dirname(HERE)), os.path.dirname(HERE)]
 
 import galerkin_ref as gr  # noqa: E402
-import mg_poly_ref as mp  # noqa: E402
+import pcg_ref  # noqa: E402
+import precond_ref as mp  # noqa: E402
 
 
 def products():
@@ -33,16 +34,16 @@ def solves():
     for fname, fmt in (("crs", ("crs", 64, 1)), ("sell_64_256", ("scs", 64, 256))):
         for steps in (1, 2):
             hier, op, b, eps = gr.scaled_case(fmt, steps)[:4]
-            run = mp.solve(op, hier, b, 150, eps)
+            run = mp.solve(op, hier, b, op.to_orig(hier.dinv), 150, eps)
             run["eps"] = eps
-            out["scaled8_%s_steps%d" % (fname, steps)] = mp.record(run)
+            out["scaled8_%s_steps%d" % (fname, steps)] = pcg_ref.record(run)
             hier.free()
     return out
 
 
 if __name__ == "__main__":
     rec = {"_comment": "Galerkin coarse operators and the two-level solve on them as the CPU restatement (tests/galerkin_ref.py, "
-                       "tests/mg_poly_ref.py) gives them; made by tests/golden/make_golden_galerkin.py",
+                       "tests/precond_ref.py) gives them; made by tests/golden/make_golden_galerkin.py",
            "products": products(), "solves": solves()}
     with open(os.path.join(HERE, "galerkin_hist.json"), "w") as f:
         json.dump(rec, f, indent=1)

@@ -2,7 +2,7 @@
 bit at HPCG 16^3; PCG(galerkin="device") == PCG(galerkin=True) in k, r.r, r.z, p.Ap, x, per-level intervals and coefficients,
 launches per body and precond_bytes for the committed Galerkin cases of tests/golden/mg_poly_hist.json (and therefore equal to that
 golden) at 1 and 2 steps; on the scaled 8^3 matrix, whose products are not exact, the two-level solve on the device's operator is
-the CPU restatement (mg_poly_ref.Hierarchy over galerkin_ref's operator) and tests/golden/galerkin_hist.json bit for bit; the
+the CPU restatement (precond_ref.Hierarchy over galerkin_ref's operator) and tests/golden/galerkin_hist.json bit for bit; the
 other kinds of handle give their own goldens before and after; freeing the handle frees the coarse problems and no directory is
 made; the library's refusals end a child process with their message."""
 import os
@@ -16,9 +16,10 @@ import pytest
 import galerkin_ref as gr
 import mg_fw_cases
 import mg_poly_cases as cases
-import mg_poly_ref as ref
 import pcg_cases
+import pcg_ref
 import poly_cases
+import precond_ref as ref
 from conftest import load_json
 from sparsebench_amd import hostapi
 from test_gpu_mg import collect, same, same_as_golden
@@ -57,14 +58,14 @@ def test_pcg_on_the_device_hierarchy_is_pcg_on_the_scipy_one(gpu, name, steps):
     assert c["galerkin"] and c["levels"] == 3 and c.get("steps") is None
     e = load_json("mg_poly_hist.json")["cases"][name]
     eps = float.fromhex(e["eps"])
-    p = hostapi.Problem(*ref.problem_args(c["matrix"]), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+    p = hostapi.Problem(*pcg_ref.problem_args(c["matrix"]), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
     d = hostapi.PCG(p, precond="mgpoly", levels=3, galerkin="device", steps=steps)
     h = hostapi.PCG(p, precond="mgpoly", levels=3, galerkin=True, steps=steps)
     assert d.levels() == h.levels() == 3 and d._owned_dir is None and len(d._owned) == 2
     for l in range(3):
         assert d.level_rows(l) == h.level_rows(l)
         assert [float(v).hex() for v in d.interval(l)] == [float(v).hex() for v in h.interval(l)], (name, l)
-        assert ref.same_bits(d.coeffs(l), h.coeffs(l)), (name, l)
+        assert pcg_ref.same_bits(d.coeffs(l), h.coeffs(l)), (name, l)
     assert d.launches_per_body() == h.launches_per_body() and d.precond_bytes() == h.precond_bytes()
     got, want = collect(d, d.solve(c["itermax"], eps)), collect(h, h.solve(c["itermax"], eps))
     same(got, want, (name, steps))
@@ -82,8 +83,9 @@ def test_pcg_on_the_device_hierarchy_is_pcg_on_the_scipy_one(gpu, name, steps):
 @pytest.mark.parametrize("fname,fmt", [("crs", ("crs", 64, 1)), ("sell_64_256", ("scs", 64, 256))])
 def test_inexact_operator_solve_equals_the_restatement_and_the_golden(gpu, fname, fmt, steps):
     hier, op, b, eps, (A, P, Ac) = gr.scaled_case(fmt, steps)
-    want = ref.solve(op, hier, b, 150, eps)
-    want["dinv"] = op.to_orig(hier.dinv)
+    dinv = op.to_orig(hier.dinv)
+    want = ref.solve(op, hier, b, dinv, 150, eps)
+    want["dinv"] = dinv
     e = load_json("galerkin_hist.json")["solves"]["scaled8_%s_steps%d" % (fname, steps)]
     assert eps == float.fromhex(e["eps"])
     p = hostapi.Problem.from_csr(*A, fmt=fmt[0], Cc=fmt[1], sigma=fmt[2])

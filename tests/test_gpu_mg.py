@@ -1,4 +1,4 @@
-"""MG-preconditioned CG on the GPU == the CPU restatement of its contract (tests/mg_ref.py, pinned by
+"""MG-preconditioned CG on the GPU == the CPU restatement of its contract (tests/precond_ref.py, pinned by
 tests/test_mg_host.py) and tests/golden/mg_hist.json BIT FOR BIT: k, every r.r, every r.z, every p.Ap, x and dinv, in both kernel
 modes of the fine matrix's SpMV.  With one level the solver is hostapi.PCG(precond="sgs") bit for bit; a second solve on one
 handle repeats the first; every refusal of sb_pcg_create_mg ends the process with its message.  (NaN compares equal to NaN.)"""
@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 import mg_cases
-import mg_ref as ref
+import pcg_ref
+import precond_ref as ref
 import sgs_cases
 from conftest import load_json
 from sparsebench_amd import hostapi
@@ -55,18 +56,18 @@ def same(got, want, what, keys=("rr", "rz", "pAp", "x", "dinv")):
 def same_as_golden(got, e, what):
     assert got["k"] == e["k"], (what, got["k"], e["k"])
     for key in ("rr", "rz", "pAp"):
-        assert ref.same_bits(got[key], ref.unhex(e[key])), (what, key)
+        assert pcg_ref.same_bits(got[key], pcg_ref.unhex(e[key])), (what, key)
     assert hashlib.sha256(np.ascontiguousarray(got["x"]).tobytes()).hexdigest() == e["x_sha256"], what
 
 
 def handle(c, tmp):
     """(problem, the coarse problems the caller owns, a constructor of MG handles) of a case"""
-    p = hostapi.Problem(*ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+    p = hostapi.Problem(*pcg_ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
     if c.get("coarse") is None:
         return p, [], lambda: hostapi.PCG(p, precond="mg", levels=c.get("levels"))
     coarse = []
     for matrix, f2c in c["coarse"]:
-        q = hostapi.Problem(*ref.problem_args(matrix, tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+        q = hostapi.Problem(*pcg_ref.problem_args(matrix, tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
         coarse.append((q, ref.geometric_f2c(f2c[1:]) if isinstance(f2c, tuple) else np.asarray(f2c)))
     return p, [q for q, _ in coarse], lambda: hostapi.PCG(p, precond="mg", coarse=coarse)
 
@@ -79,7 +80,7 @@ def modes(p):
 @pytest.mark.parametrize("name", mg_cases.SMALL)
 def test_gpu_equals_the_restatement_and_the_golden(gpu, name, tmp, golden):
     c = mg_cases.CASES[name]
-    hier, f2cs, op, b, dinv, eps = ref.build_case(c, tmp)
+    hier, f2cs, op, b, dinv, eps = ref.build_case(ref.MG, c, tmp)
     want = ref.solve(op, hier, b, dinv, c["itermax"], eps)
     want["dinv"] = dinv
     e = golden["cases"][name]
@@ -108,7 +109,7 @@ def test_gpu_equals_the_restatement_and_the_golden(gpu, name, tmp, golden):
 
 def test_one_level_is_sgs_pcg_and_a_second_solve_repeats_the_first(gpu, tmp):
     c = sgs_cases.CASES["scaled16_sell_64_256"]
-    p = hostapi.Problem(*ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+    p = hostapi.Problem(*pcg_ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
     b = p.rhs()[0]
     eps = 1e-10 * float(np.sqrt(b @ b))
     s = hostapi.PCG(p, precond="sgs")
@@ -128,7 +129,7 @@ def test_one_level_is_sgs_pcg_and_a_second_solve_repeats_the_first(gpu, tmp):
     short = collect(two, two.solve(7, 0.0))
     assert short["k"] == 7
     for key in ("rr", "rz", "pAp"):
-        assert ref.same_bits(short[key][:6], first[key][:6]), key
+        assert pcg_ref.same_bits(short[key][:6], first[key][:6]), key
     z = two.apply(b)
     same(collect(two, two.solve(150, eps)), first, "after another solve and an apply")
     assert np.isfinite(z).all() and two.loop_ms() > 0.0
@@ -230,7 +231,7 @@ def test_big_case_against_the_committed_golden(gpu, name, golden):
     """HPCG 64^3 at HPCG's depth, 60 iterations: tests/golden/mg_hist.json, made by the CPU restatement"""
     c = mg_cases.CASES[name]
     e = golden["cases"][name]
-    p = hostapi.Problem(*ref.problem_args(c["matrix"]), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+    p = hostapi.Problem(*pcg_ref.problem_args(c["matrix"]), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
     for mode in modes(p):
         p.use_packed(mode)
         s = hostapi.PCG(p, precond="mg", levels=c["levels"])

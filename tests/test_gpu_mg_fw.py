@@ -1,4 +1,4 @@
-"""PCG with the full-weighting V-cycle on the GPU == the CPU restatement of its contract (tests/mg_fw_ref.py,
+"""PCG with the full-weighting V-cycle on the GPU == the CPU restatement of its contract (tests/precond_ref.py,
 pinned by tests/test_mg_fw_host.py) and tests/golden/mg_fw_hist.json BIT FOR BIT: k, every r.r, every r.z, every p.Ap, x and dinv,
 in both kernel modes of the fine matrix's SpMV.  Without coarse levels the solver is hostapi.PCG(precond="sgs") bit for bit; a
 second solve on one handle repeats the first; every refusal of sb_pcg_create_mg_p ends the process with its message.  (NaN
@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 import mg_fw_cases as cases
-import mg_fw_ref as ref
+import pcg_ref
+import precond_ref as ref
 import sgs_cases
 from conftest import load_json
 from sparsebench_amd import hostapi
@@ -33,12 +34,12 @@ def golden():
 
 def handle(c, tmp):
     """(problem, the coarse problems the caller owns, a constructor of handles) of a case"""
-    p = hostapi.Problem(*ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+    p = hostapi.Problem(*pcg_ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
     if c.get("coarse") is None:
         return p, [], lambda: hostapi.PCG(p, precond="mgfw", levels=c.get("levels"))
     coarse = []
-    for (matrix, _, _), (P, omega) in zip(c["coarse"], ref.case_transfers(c)):
-        q = hostapi.Problem(*ref.problem_args(matrix, tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+    for (matrix, _, _), (P, omega) in zip(c["coarse"], ref.case_transfers(ref.MGFW, c)):
+        q = hostapi.Problem(*pcg_ref.problem_args(matrix, tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
         coarse.append((q, P, omega))
     return p, [q for q, _, _ in coarse], lambda: hostapi.PCG(p, precond="mgfw", coarse=coarse)
 
@@ -46,7 +47,7 @@ def handle(c, tmp):
 @pytest.mark.parametrize("name", cases.SMALL)
 def test_gpu_equals_the_restatement_and_the_golden(gpu, name, tmp, golden):
     c = cases.CASES[name]
-    hier, transfers, op, b, dinv, eps = ref.build_case(c, tmp)
+    hier, transfers, op, b, dinv, eps = ref.build_case(ref.MGFW, c, tmp)
     want = ref.solve(op, hier, b, dinv, c["itermax"], eps)
     want["dinv"] = dinv
     e = golden["cases"][name]
@@ -76,7 +77,7 @@ def test_gpu_equals_the_restatement_and_the_golden(gpu, name, tmp, golden):
 
 def test_no_coarse_level_is_sgs_pcg_and_solves_repeat(gpu, tmp):
     c = sgs_cases.CASES["scaled16_sell_64_256"]
-    p = hostapi.Problem(*ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+    p = hostapi.Problem(*pcg_ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
     b = p.rhs()[0]
     eps = 1e-10 * float(np.sqrt(b @ b))
     s = hostapi.PCG(p, precond="sgs")
@@ -96,7 +97,7 @@ def test_no_coarse_level_is_sgs_pcg_and_solves_repeat(gpu, tmp):
     short = collect(two, two.solve(7, 0.0))
     assert short["k"] == 7
     for key in ("rr", "rz", "pAp"):
-        assert ref.same_bits(short[key][:6], first[key][:6]), key
+        assert pcg_ref.same_bits(short[key][:6], first[key][:6]), key
     z = two.apply(b)
     two.mg_fw_probe(0, b, z, np.ones(512))
     same(collect(two, two.solve(150, eps)), first, "after another solve, an apply and a probe")
@@ -195,7 +196,7 @@ def test_big_case_against_the_committed_golden(gpu, name, golden):
     """HPCG 32^3 at HPCG's depth: tests/golden/mg_fw_hist.json, made by the CPU restatement"""
     c = cases.CASES[name]
     e = golden["cases"][name]
-    p = hostapi.Problem(*ref.problem_args(c["matrix"]), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+    p = hostapi.Problem(*pcg_ref.problem_args(c["matrix"]), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
     for mode in modes(p):
         p.use_packed(mode)
         s = hostapi.PCG(p, precond="mgfw", levels=c["levels"])

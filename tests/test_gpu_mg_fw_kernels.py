@@ -1,6 +1,6 @@
 """The full-weighting transfers on the GPU without a solve: the three kernels each on its own through
 sb_pcg_mg_fw_probe -- d = r - A z, rc = omega P^T d, z + P zc -- and one whole V-cycle through sb_pcg_apply_precond == the CPU
-restatement (tests/mg_fw_ref.py, pinned by tests/test_mg_fw_host.py) BIT FOR BIT, NaN equal to NaN, on vectors with +0.0, -0.0,
+restatement (tests/precond_ref.py, pinned by tests/test_mg_fw_host.py) BIT FOR BIT, NaN equal to NaN, on vectors with +0.0, -0.0,
 a denormal, an inf and a NaN in r, z and zc.  The shapes are mg_cases': 4^3 (8 coarse rows: one partial chunk of P^T),
 34 x 6 x 10 (every colour ends in a partial chunk, so the one-launch residual crosses colour boundaries at partial chunks),
 12 x 8 x 20 (odd coarse dimensions: dropped boundary weights where the coarse colouring is not the parity one), three and four
@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 import mg_fw_cases as cases
-import mg_fw_ref as ref
+import pcg_ref
+import precond_ref as ref
 from sparsebench_amd import hostapi
 
 pytestmark = pytest.mark.gpu
@@ -38,9 +39,9 @@ def check_handle(s, p, hier, fmt, C, what):
     op = hier.lev[0].op
     assert s.precond() == "mgfw" and s.levels() == hier.L, (what, s.precond(), s.levels(), hier.L)
     assert [s.level_rows(l) for l in range(hier.L)] == [V.n for V in hier.lev], what
-    assert [s.level_colours(l) for l in range(hier.L)] == [V.plan.nC for V in hier.lev], what
-    assert s.colours() == hier.nC and np.array_equal(s.colouring(), op.to_orig(hier.lev[0].plan.colour)), what
-    apply_launches = sum(2 * (2 * V.plan.nC - 1) + 3 for V in hier.lev[:-1]) + 2 * hier.lev[-1].plan.nC - 1
+    assert [s.level_colours(l) for l in range(hier.L)] == [V.smoother.nC for V in hier.lev], what
+    assert s.colours() == hier.lev[0].smoother.nC and np.array_equal(s.colouring(), op.to_orig(hier.lev[0].smoother.colour)), what
+    apply_launches = sum(2 * (2 * V.smoother.nC - 1) + 3 for V in hier.lev[:-1]) + 2 * hier.lev[-1].smoother.nC - 1
     assert hier.launches() == apply_launches
     assert s.launches_per_body() == 6 + apply_launches + (0 if fused_dot(p, fmt, C) else 1), what
     for l in range(hier.L - 1):
@@ -64,9 +65,9 @@ def check_handle(s, p, hier, fmt, C, what):
 
 def check(matrix, levels, fmt, C, sigma, tmp):
     c = dict(matrix=matrix, fmt=fmt, C=C, sigma=sigma, levels=levels)
-    hier, transfers = ref.build_hierarchy(c, tmp)
+    hier, transfers = ref.build_hierarchy(ref.MGFW, c, tmp)
     assert hier.L == levels
-    p = hostapi.Problem(*ref.problem_args(matrix, tmp), fmt=fmt, Cc=C, sigma=sigma)
+    p = hostapi.Problem(*pcg_ref.problem_args(matrix, tmp), fmt=fmt, Cc=C, sigma=sigma)
     if sigma > 1:  # the restatement walks the device's own permutation
         op = hier.lev[0].op
         assert np.array_equal(p.array("oldToNewPerm"), op.o2n if op.o2n is not None else np.arange(p.nr))
@@ -82,14 +83,15 @@ def test_transfers_and_one_cycle_equal_the_restatement(gpu, matrix, levels, fmt,
     hier = check(matrix, levels, fmt, C, sigma, tmp)
     rows = [V.n for V in hier.lev]
     if matrix == ("dims", 4, 4, 4):
-        assert rows == [64, 8] and int(hier.lev[0].PT[0].max()) == 27  # one partial chunk of P^T; the corner-free row has 27 entries
+        # one partial chunk of P^T; the corner-free row has 27 entries
+        assert rows == [64, 8] and int(hier.lev[0].transfer.PT[0].max()) == 27
     if matrix == ("dims", 16, 16, 16):
         assert rows == [4096, 512, 64, 8]
     if matrix == ("dims", 12, 8, 20) and sigma == 1:
         assert rows == [1920, 240, 30]
     if matrix == ("dims", 34, 6, 10) and sigma == 1:
-        assert all(len(r) % 64 for r in hier.lev[0].plan.rows)  # every colour ends in a partial chunk
-    ln = hier.lev[0].P[0]
+        assert all(len(r) % 64 for r in hier.lev[0].smoother.rows)  # every colour ends in a partial chunk
+    ln = hier.lev[0].transfer.P[0]
     assert ln.min() >= 1 and ln.max() == 8  # chunk lengths of P vary between 1 and 8
 
 
@@ -102,9 +104,9 @@ def test_sell_4_8(gpu, tmp):
 def test_a_callers_hierarchy_with_an_empty_row_and_a_zero_weight(gpu, fmt, sigma, tmp):
     fine, coarse, P, omega = cases.hand_made(tmp)
     c = cases.hand_made_case(tmp, fmt, sigma)
-    hier, transfers = ref.build_hierarchy(c, tmp)
+    hier, transfers = ref.build_hierarchy(ref.MGFW, c, tmp)
     assert [V.n for V in hier.lev] == [130, 65] and omega == 0.5 and 0.0 in P[2].tolist()
-    assert (hier.lev[0].P[0] == 0).sum() == 1  # the empty row
+    assert (hier.lev[0].transfer.P[0] == 0).sum() == 1  # the empty row
     p = hostapi.Problem(fine, 1, 1, 1, fmt=fmt, Cc=64, sigma=sigma)
     q = hostapi.Problem(coarse, 1, 1, 1, fmt=fmt, Cc=64, sigma=sigma)
     if fmt == "crs":  # as a scipy.sparse matrix, the stored 0.0 kept

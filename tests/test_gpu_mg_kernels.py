@@ -1,5 +1,5 @@
 """The MG preconditioner on the GPU without a solve: one V-cycle through sb_pcg_apply_precond == the CPU
-restatement (tests/mg_ref.py, pinned by tests/test_mg_host.py) BIT FOR BIT, NaN equal to NaN: a coarse level of 8 rows (one
+restatement (tests/precond_ref.py, pinned by tests/test_mg_host.py) BIT FOR BIT, NaN equal to NaN: a coarse level of 8 rows (one
 partial chunk of the restriction), three and four levels, coarse grids with odd dimensions, colours that end in partial chunks,
 every format, a caller's hierarchy on hand-made files (65 coarse rows: a full chunk plus one lane), right-hand sides with +0.0,
 -0.0, a denormal, an inf and a NaN.  One level is the SGS handle's apply; the levels' rows, colours and the launches per body are
@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 import mg_cases
-import mg_ref as ref
+import pcg_ref
+import precond_ref as ref
 from sparsebench_amd import hostapi
 
 pytestmark = pytest.mark.gpu
@@ -37,9 +38,9 @@ def check_handle(s, p, hier, fmt, C, what):
     op = hier.lev[0].op
     assert s.precond() == "mg" and s.levels() == hier.L, (what, s.levels(), hier.L)
     assert [s.level_rows(l) for l in range(hier.L)] == [V.n for V in hier.lev], what
-    assert [s.level_colours(l) for l in range(hier.L)] == [V.plan.nC for V in hier.lev], what
-    assert s.colours() == hier.nC and np.array_equal(s.colouring(), op.to_orig(hier.lev[0].plan.colour)), what
-    apply_launches = sum(2 * (2 * V.plan.nC - 1) + 2 for V in hier.lev[:-1]) + 2 * hier.lev[-1].plan.nC - 1
+    assert [s.level_colours(l) for l in range(hier.L)] == [V.smoother.nC for V in hier.lev], what
+    assert s.colours() == hier.lev[0].smoother.nC and np.array_equal(s.colouring(), op.to_orig(hier.lev[0].smoother.colour)), what
+    apply_launches = sum(2 * (2 * V.smoother.nC - 1) + 2 for V in hier.lev[:-1]) + 2 * hier.lev[-1].smoother.nC - 1
     assert hier.launches() == apply_launches
     assert s.launches_per_body() == 6 + apply_launches + (0 if fused_dot(p, fmt, C) else 1), what
     for seed, special in ((1, False), (2, True)):
@@ -53,9 +54,9 @@ def check_handle(s, p, hier, fmt, C, what):
 
 def check(matrix, levels, fmt, C, sigma, tmp):
     c = dict(matrix=matrix, fmt=fmt, C=C, sigma=sigma, levels=levels)
-    hier, f2cs = ref.build_hierarchy(c, tmp)
+    hier, f2cs = ref.build_hierarchy(ref.MG, c, tmp)
     assert hier.L == levels
-    p = hostapi.Problem(*ref.problem_args(matrix, tmp), fmt=fmt, Cc=C, sigma=sigma)
+    p = hostapi.Problem(*pcg_ref.problem_args(matrix, tmp), fmt=fmt, Cc=C, sigma=sigma)
     if sigma > 1:  # the restatement walks the device's own permutation
         op = hier.lev[0].op
         assert np.array_equal(p.array("oldToNewPerm"), op.o2n if op.o2n is not None else np.arange(p.nr))
@@ -77,7 +78,7 @@ def test_one_cycle_equals_the_restatement(gpu, matrix, levels, fmt, C, sigma, tm
     if matrix == ("dims", 12, 8, 20) and sigma == 1:
         assert rows == [1920, 240, 30]
     if matrix == ("dims", 34, 6, 10) and sigma == 1:
-        assert all(len(r) % 64 for r in hier.lev[0].plan.rows)  # every colour ends in a partial chunk
+        assert all(len(r) % 64 for r in hier.lev[0].smoother.rows)  # every colour ends in a partial chunk
 
 
 def test_sell_4_8(gpu, tmp):
@@ -89,7 +90,7 @@ def test_sell_4_8(gpu, tmp):
 def test_a_callers_hierarchy_on_hand_made_files(gpu, fmt, sigma, tmp):
     fine, coarse, f2c = mg_cases.hand_made(tmp)
     c = dict(matrix=("file", fine), fmt=fmt, C=64, sigma=sigma, coarse=[(("file", coarse), f2c)])
-    hier, f2cs = ref.build_hierarchy(c, tmp)
+    hier, f2cs = ref.build_hierarchy(ref.MG, c, tmp)
     assert [V.n for V in hier.lev] == [130, 65]
     p = hostapi.Problem(fine, 1, 1, 1, fmt=fmt, Cc=64, sigma=sigma)
     q = hostapi.Problem(coarse, 1, 1, 1, fmt=fmt, Cc=64, sigma=sigma)

@@ -1,4 +1,4 @@
-"""PCG with the Chebyshev-smoothed V-cycle on the GPU == the CPU restatement of its contract (tests/mg_poly_ref.py,
+"""PCG with the Chebyshev-smoothed V-cycle on the GPU == the CPU restatement of its contract (tests/precond_ref.py,
 pinned by tests/test_mg_poly_host.py) and tests/golden/mg_poly_hist.json BIT FOR BIT: k, every r.r, every r.z, every p.Ap, x and
 dinv, in both kernel modes of the SpMV, on the regenerated hierarchy, on a caller's and on the Galerkin one.  Without coarse
 levels the solver is hostapi.PCG(precond="poly") bit for bit; a solve in pieces and a second solve repeat the first; the other
@@ -13,9 +13,10 @@ import pytest
 
 import mg_fw_cases
 import mg_poly_cases as cases
-import mg_poly_ref as ref
 import pcg_cases
+import pcg_ref
 import poly_cases
+import precond_ref as ref
 from conftest import load_json
 from sparsebench_amd import hostapi
 from test_gpu_mg import collect, check_counters, same, same_as_golden, modes, files
@@ -40,12 +41,12 @@ def steps_of(c):
 
 def handle(c, tmp):
     """(problem, the coarse problems the caller owns, a constructor of handles) of a case"""
-    p = hostapi.Problem(*ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+    p = hostapi.Problem(*pcg_ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
     if c.get("coarse") is None:
         return p, [], lambda: hostapi.PCG(p, precond="mgpoly", levels=c.get("levels"), galerkin=bool(c.get("galerkin")), **steps_of(c))
     coarse = []
-    for (matrix, _, _), (P, omega) in zip(c["coarse"], ref.case_transfers(c)):
-        q = hostapi.Problem(*ref.problem_args(matrix, tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+    for (matrix, _, _), (P, omega) in zip(c["coarse"], ref.case_transfers(ref.MGPOLY, c)):
+        q = hostapi.Problem(*pcg_ref.problem_args(matrix, tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
         coarse.append((q, P, omega))
     return p, [q for q, _, _ in coarse], lambda: hostapi.PCG(p, precond="mgpoly", coarse=coarse, **steps_of(c))
 
@@ -53,8 +54,8 @@ def handle(c, tmp):
 @pytest.mark.parametrize("name", cases.SMALL)
 def test_gpu_equals_the_restatement_and_the_golden(gpu, name, tmp, golden):
     c = cases.CASES[name]
-    hier, transfers, op, b, eps = ref.build_case(c, tmp)
-    want = ref.solve(op, hier, b, c["itermax"], eps)
+    hier, transfers, op, b, dinv, eps = ref.build_case(ref.MGPOLY, c, tmp)
+    want = ref.solve(op, hier, b, dinv, c["itermax"], eps)
     want["dinv"] = op.to_orig(hier.dinv)
     e = golden["cases"][name]
     assert eps == float.fromhex(e["eps"]) and e["L"] == hier.L
@@ -115,7 +116,7 @@ def test_galerkin_coarse_operators_through_the_callers_door(gpu, tmp):
 
 def test_no_coarse_level_is_poly_pcg_solves_repeat_and_other_kinds_are_untouched(gpu, tmp):
     c = poly_cases.CASES["scaled16_sell_64_256_eps"]
-    p = hostapi.Problem(*ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+    p = hostapi.Problem(*pcg_ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
     b = p.rhs()[0]
     eps = 1e-10 * float(np.sqrt(b @ b))
     # the other kinds of handle on this problem, before anything of the new kind exists
@@ -133,7 +134,7 @@ def test_no_coarse_level_is_poly_pcg_solves_repeat_and_other_kinds_are_untouched
         assert one.launches_per_body() == q.launches_per_body() and one.precond_bytes() == q.precond_bytes()
         same(collect(one, one.solve(150, eps)), want, "no coarse level == the polynomial handle")
         r = ref.probe_vector(p.nr, 3, True)
-        assert ref.same_bits(one.apply(r), q.apply(r))
+        assert pcg_ref.same_bits(one.apply(r), q.apply(r))
         one.free(), q.free()
     # two levels: in uneven pieces, then another itermax, an apply and a probe in between, then the first again
     coarse = hostapi.Problem("generate", 8, 8, 8, fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
@@ -147,7 +148,7 @@ def test_no_coarse_level_is_poly_pcg_solves_repeat_and_other_kinds_are_untouched
     short = collect(two, two.solve(7, 0.0))
     assert short["k"] == 7
     for key in ("rr", "rz", "pAp"):
-        assert ref.same_bits(short[key][:6], first[key][:6]), key
+        assert pcg_ref.same_bits(short[key][:6], first[key][:6]), key
     z = two.apply(b)
     two.mg_poly_probe(0, b, z, z, np.ones(512))
     same(collect(two, two.solve(150, eps)), first, "after another solve, an apply and a probe")
@@ -269,7 +270,7 @@ def test_big_case_against_the_committed_golden(gpu, name, golden):
     """HPCG 32^3 at HPCG's depth: tests/golden/mg_poly_hist.json, made by the CPU restatement"""
     c = cases.CASES[name]
     e = golden["cases"][name]
-    p = hostapi.Problem(*ref.problem_args(c["matrix"]), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+    p = hostapi.Problem(*pcg_ref.problem_args(c["matrix"]), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
     for mode in modes(p):
         p.use_packed(mode)
         s = hostapi.PCG(p, precond="mgpoly", levels=c["levels"])

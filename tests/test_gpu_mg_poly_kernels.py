@@ -1,4 +1,4 @@
-"""The kernels of the Chebyshev-smoothed V-cycle alone, BIT FOR BIT against the CPU restatement (tests/mg_poly_ref.py,
+"""The kernels of the Chebyshev-smoothed V-cycle alone, BIT FOR BIT against the CPU restatement (tests/precond_ref.py,
 pinned by tests/test_mg_poly_host.py), NaN equal to NaN: mgp_first_k through its native entry at the sizes where its paths change
 -- fewer rows than one wave's span, the partial last group, an odd n, every wave on a second trip of its group loop -- with +0.0,
 -0.0, denormals, an inf and a NaN in every vector, a stale inf and NaN in d, and guard doubles behind them; mgp_restrict_k and the
@@ -11,8 +11,8 @@ import pytest
 from oracle import pyoracle as po
 
 import mg_poly_cases as cases
-import mg_poly_ref as ref
-import poly_ref
+import pcg_ref
+import precond_ref as ref
 from sparsebench_amd import hostapi
 from sparsebench_amd.capi import DeviceVector
 from test_gpu_poly_kernels import same, vectors, guarded, check_guarded, modes, GUARD
@@ -106,9 +106,9 @@ def check_handle(s, p, hier, fmt, C, what, cycles=True):
     assert [s.level_rows(l) for l in range(hier.L)] == [V.n for V in hier.lev], what
     assert [s.level_colours(l) for l in range(hier.L)] == [0] * hier.L and s.steps() == hier.steps
     for l, V in enumerate(hier.lev):
-        assert s.level_steps(l) == V.steps == (hier.coarse_steps if l == hier.L - 1 else hier.steps)
-        assert s.interval(l) == (V.plan.c["lmin"], V.plan.c["lmax"]), (what, l)
-        same(s.coeffs(l), poly_ref.coeff_array(V.plan.c), what + (l, "coeffs"))
+        assert s.level_steps(l) == V.smoother.steps == (hier.coarse_steps if l == hier.L - 1 else hier.steps)
+        assert s.interval(l) == (V.smoother.c["lmin"], V.smoother.c["lmax"]), (what, l)
+        same(s.coeffs(l), ref.coeff_array(V.smoother.c), what + (l, "coeffs"))
     assert s.interval() == s.interval(0)
     same(s.dinv(), op.to_orig(hier.dinv), what + ("dinv",))
     assert s.launches_per_body() == hier.launches_per_body(fused_dot(p, fmt, C)), what
@@ -120,7 +120,7 @@ def check_handle(s, p, hier, fmt, C, what, cycles=True):
                            ref.probe_vector(V.n, seed + 10, special), ref.probe_vector(W.n, seed + 20, special))
             if special and V.n > 8:  # an inf in w beside rows that do not touch it, a NaN in zc
                 w[5], zc[W.n // 2] = -np.inf, np.nan
-            want = hier.probe(l, V.op.to_dev(r), V.op.to_dev(w), V.op.to_dev(z), W.op.to_dev(zc))
+            want = hier.probe_w(l, V.op.to_dev(r), V.op.to_dev(w), V.op.to_dev(z), W.op.to_dev(zc))
             got = s.mg_poly_probe(l, r, w, z, zc)
             for name, g, wv, o in zip(("rc", "z_out"), got, want, (W.op, V.op)):
                 same(g, o.to_orig(wv), what + (l, name, "special" if special else "finite"))
@@ -136,9 +136,9 @@ def check_handle(s, p, hier, fmt, C, what, cycles=True):
 
 def check(matrix, levels, fmt, C, sigma, tmp, **kw):
     c = dict(matrix=matrix, fmt=fmt, C=C, sigma=sigma, levels=levels, **kw)
-    hier, transfers = ref.build_hierarchy(c, tmp)
+    hier, transfers = ref.build_hierarchy(ref.MGPOLY, c, tmp)
     assert hier.L == levels
-    p = hostapi.Problem(*ref.problem_args(matrix, tmp), fmt=fmt, Cc=C, sigma=sigma)
+    p = hostapi.Problem(*pcg_ref.problem_args(matrix, tmp), fmt=fmt, Cc=C, sigma=sigma)
     if sigma > 1:  # the restatement walks the device's own permutation
         op = hier.lev[0].op
         assert np.array_equal(p.array("oldToNewPerm"), op.o2n if op.o2n is not None else np.arange(p.nr))
@@ -154,10 +154,11 @@ def test_transfers_levels_and_one_cycle_equal_the_restatement(gpu, matrix, level
     hier = check(matrix, levels, fmt, C, sigma, tmp)
     rows = [V.n for V in hier.lev]
     if matrix == ("dims", 4, 4, 4):
-        assert rows == [64, 8] and int(hier.lev[0].PT[0].max()) == 27  # one partial chunk of P^T; two batches of 16 in a row
+        assert rows == [64, 8] and int(hier.lev[0].transfer.PT[0].max()) == 27  # one partial chunk of P^T; two batches of 16 in a row
     if matrix == ("dims", 16, 16, 16):
         assert rows == [4096, 512, 64, 8]
-    assert hier.lev[0].omega == 0.25 and hier.steps == hier.coarse_steps == 2 and hier.lev[0].plan.c["lmax"] / hier.lev[0].plan.c["lmin"] == 4.0
+    c0 = hier.lev[0].smoother.c
+    assert hier.lev[0].transfer.omega == 0.25 and hier.steps == hier.coarse_steps == 2 and c0["lmax"] / c0["lmin"] == 4.0
 
 
 def test_sell_4_8(gpu, tmp):
@@ -169,7 +170,7 @@ def test_sell_4_8(gpu, tmp):
 def test_one_cycle_per_step_count_in_both_kernel_modes(gpu, steps, coarse_steps, tmp):
     """16^3 at four levels in Sell-64-256: the row programs (mode 5) and the reference-layout stream (mode 0) on every level"""
     c = dict(matrix=("hpcg", 16), fmt="scs", C=64, sigma=256, levels=4, steps=steps, coarse_steps=coarse_steps)
-    hier, transfers = ref.build_hierarchy(c, tmp)
+    hier, transfers = ref.build_hierarchy(ref.MGPOLY, c, tmp)
     op = hier.lev[0].op
     p = hostapi.Problem("generate", 16, 16, 16, fmt="scs", Cc=64, sigma=256)
     seen = modes(p)
@@ -188,7 +189,7 @@ def test_one_cycle_per_step_count_in_both_kernel_modes(gpu, steps, coarse_steps,
 def test_a_callers_lmax_and_ratio_hold_on_every_level(gpu, tmp):
     kw = dict(steps=2, coarse_steps=3, lmax=1.75, ratio=8.0)
     hier = check(("dims", 8, 8, 8), 3, "scs", 64, 256, tmp, **kw)
-    assert all(V.plan.c["lmax"] == 1.75 and V.plan.c["lmin"] == 1.75 / 8.0 for V in hier.lev)
+    assert all(V.smoother.c["lmax"] == 1.75 and V.smoother.c["lmin"] == 1.75 / 8.0 for V in hier.lev)
 
 
 @pytest.mark.parametrize("fmt,sigma", [("crs", 1), ("scs", 1), ("scs", 256)])
@@ -197,10 +198,10 @@ def test_a_callers_hierarchy_with_an_empty_row_and_a_zero_weight(gpu, fmt, sigma
     outs = []
     for store_zero in (True, False):
         c = cases.hand_made_case(tmp, fmt, sigma, store_zero)
-        hier, transfers = ref.build_hierarchy(c, tmp)
+        hier, transfers = ref.build_hierarchy(ref.MGPOLY, c, tmp)
         P = transfers[0][0]
         assert [V.n for V in hier.lev] == [130, 65] and omega == 0.5 and (0.0 in P[2].tolist()) == store_zero
-        assert (hier.lev[0].P[0] == 0).sum() == 1  # the empty row
+        assert (hier.lev[0].transfer.P[0] == 0).sum() == 1  # the empty row
         p = hostapi.Problem(fine, 1, 1, 1, fmt=fmt, Cc=64, sigma=sigma)
         q = hostapi.Problem(coarse, 1, 1, 1, fmt=fmt, Cc=64, sigma=sigma)
         s = hostapi.PCG(p, precond="mgpoly", coarse=[(q, P, omega)])

@@ -1,5 +1,5 @@
 """PCG with the Chebyshev polynomial preconditioner on the GPU == the CPU restatement of its contract
-(tests/poly_ref.py, pinned by tests/test_poly_host.py) and tests/golden/poly_hist.json BIT FOR BIT: k, every r.r, every r.z,
+(tests/precond_ref.py, pinned by tests/test_poly_host.py) and tests/golden/poly_hist.json BIT FOR BIT: k, every r.r, every r.z,
 every p.Ap, x and dinv, every format, both kernel modes of the SpMV.  With steps = 1 and c1 = 1.0 the solver is Jacobi
 hostapi.PCG bit for bit, and Jacobi and SGS handles made before and after a polynomial handle still give the histories of their
 own goldens.  (NaN compares equal to NaN.)"""
@@ -12,8 +12,9 @@ import numpy as np
 import pytest
 
 import pcg_cases
+import pcg_ref
 import poly_cases
-import poly_ref as ref
+import precond_ref as ref
 import sgs_cases
 from conftest import load_json
 from sparsebench_amd import hostapi
@@ -65,12 +66,12 @@ def same(got, want, what, keys=("rr", "rz", "pAp", "x", "dinv")):
 def same_as_golden(got, e, what):
     assert got["k"] == e["k"], (what, got["k"], e["k"])
     for key in ("rr", "rz", "pAp"):
-        assert ref.same_bits(got[key], ref.unhex(e[key])), (what, key)
+        assert pcg_ref.same_bits(got[key], pcg_ref.unhex(e[key])), (what, key)
     assert hashlib.sha256(np.ascontiguousarray(got["x"]).tobytes()).hexdigest() == e["x_sha256"], what
 
 
 def problem(c, tmp):
-    return hostapi.Problem(*ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+    return hostapi.Problem(*pcg_ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
 
 
 def modes(p):
@@ -82,7 +83,8 @@ def modes(p):
 def test_gpu_equals_the_restatement_and_the_golden(gpu, name, tmp, golden):
     """both solves of the matrix: to eps = 1e-10 ||b||, and 60 fixed iterations with eps = 0"""
     c_eps, c_60 = poly_cases.CASES[name + "_eps"], poly_cases.CASES[name + "_60"]
-    g, op, plan, b, eps = ref.build_case(c_eps, tmp)
+    plan, _, op, b, dinv, eps = ref.build_case(ref.POLY, c_eps, tmp)
+    g = plan.lev[0].g
     p = problem(c_eps, tmp)
     assert np.array_equal(p.rhs()[0], b)
     if c_eps["sigma"] > 1:
@@ -91,7 +93,7 @@ def test_gpu_equals_the_restatement_and_the_golden(gpu, name, tmp, golden):
     if name.startswith("hpcg"):
         assert seen == [5, 0], seen
     for c, tag, e in ((c_eps, "_eps", eps), (c_60, "_60", 0.0)):
-        want = ref.solve(op, plan, b, c["itermax"], e)
+        want = ref.solve(op, plan, b, dinv, c["itermax"], e)
         want["dinv"] = op.to_orig(plan.dinv)
         rec = golden["cases"][name + tag]
         assert float.fromhex(rec["eps"]) == e
@@ -124,7 +126,8 @@ def test_pieces_second_solve_and_the_other_kinds_around_it(gpu, tmp):
     cj, cs = pcg_cases.CASES[name], sgs_cases.CASES[name]
     ej, es = load_json("pcg_hist.json")["cases"][name], load_json("sgs_hist.json")["cases"][name]
     c = poly_cases.CASES[name + "_eps"]
-    g, op, plan, b, eps = ref.build_case(c, tmp)
+    plan, _, op, b, dinv, eps = ref.build_case(ref.POLY, c, tmp)
+    g = plan.lev[0].g
     assert float.fromhex(ej["eps"]) == float.fromhex(es["eps"]) == eps
     p = problem(c, tmp)
 
@@ -136,13 +139,13 @@ def test_pieces_second_solve_and_the_other_kinds_around_it(gpu, tmp):
 
     others("before")
     p.use_packed(5)
-    full = ref.solve(op, plan, b, 150, eps)
+    full = ref.solve(op, plan, b, dinv, 150, eps)
     full["dinv"] = op.to_orig(plan.dinv)
     assert 1 < full["k"] < 150
     # itermax = 1 and 0: the prologue only (one apply, r.r and r.z recorded)
     for im in (1, 0):
         got = solve_gpu(p, im, eps, precond="poly")
-        want = ref.solve(op, plan, b, im, eps)
+        want = ref.solve(op, plan, b, dinv, im, eps)
         want["dinv"] = full["dinv"]
         same(got, want, ("itermax", im))
         assert got["k"] == 1 and len(got["rr"]) == len(got["rz"]) == 1 and len(got["pAp"]) == 0 and not got["x"].any()
@@ -154,7 +157,7 @@ def test_pieces_second_solve_and_the_other_kinds_around_it(gpu, tmp):
     same(out, full, "pieces")
     check_counters(s, out)
     assert s.loop_ms() > 0.0
-    short = ref.solve(op, plan, b, 9, 0.0)
+    short = ref.solve(op, plan, b, dinv, 9, 0.0)
     short["dinv"] = full["dinv"]
     same(collect(s, s.solve(9, 0.0)), short, "second solve")
     same(collect(s, s.solve(150, eps)), out, "third solve == first")
@@ -170,7 +173,7 @@ def test_pieces_second_solve_and_the_other_kinds_around_it(gpu, tmp):
 
 @pytest.mark.parametrize("fmt,C,sigma", [("crs", 64, 1), ("scs", 64, 256), ("scs", 4, 8)])
 def test_one_step_with_c1_one_gives_the_bits_of_jacobi(gpu, fmt, C, sigma, tmp):
-    p = hostapi.Problem(*ref.problem_args(("scaled", 8), tmp), fmt=fmt, Cc=C, sigma=sigma)
+    p = hostapi.Problem(*pcg_ref.problem_args(("scaled", 8), tmp), fmt=fmt, Cc=C, sigma=sigma)
     s, j = hostapi.PCG(p, precond="poly", steps=1, lmax=1.6, ratio=4.0), hostapi.PCG(p)
     assert s.coeffs().tolist() == [1.0] and s.interval() == (1.6 / 4.0, 1.6)  # c1 is exactly 1.0: verified, not assumed
     assert s.launches_per_body() == j.launches_per_body()
@@ -270,7 +273,7 @@ def test_big_case_against_the_committed_golden(gpu, name, golden):
     for mode in modes(p):
         p.use_packed(mode)
         s = hostapi.PCG(p, precond="poly")
-        assert ref.same_bits(s.coeffs(), ref.unhex(e["coeffs"]))
+        assert pcg_ref.same_bits(s.coeffs(), pcg_ref.unhex(e["coeffs"]))
         got = collect(s, s.solve(c["itermax"], float.fromhex(e["eps"])))
         s.free()
         same_as_golden(got, e, (name, mode))

@@ -5,9 +5,10 @@ import re
 import subprocess
 
 import numpy as np
+import pcg_ref
+import precond_ref as ref
 import pytest
 
-import poly_ref as ref
 from sparsebench_amd import hostapi
 
 pytestmark = pytest.mark.gpu
@@ -31,16 +32,17 @@ def tmp(tmp_path_factory):
 def test_driver_runs_polynomial_pcg(gpu, exe, fmt, where, tmp):
     """CRS and Sell-64-1 walk the same order (sigma = 1).  itermax 150; eps absolute, 1e-10 ||b||, as the driver takes it"""
     matrix = ("hpcg", 16) if where == "generated" else ("scaled", 8)
-    g = ref.gmatrix(matrix, tmp)
-    op = ref.operator(g)
+    g = pcg_ref.gmatrix(matrix, tmp)
+    op = pcg_ref.operator(g)
     b = g.rhs()
     eps = 1e-10 * float(np.sqrt(b @ b))
-    args = ref.problem_args(matrix, tmp)
+    args = pcg_ref.problem_args(matrix, tmp)
     source = SIZE if where == "generated" else ["-m", args[0]]
     p = hostapi.Problem(*args, fmt=fmt, Cc=64, sigma=1)
     for steps, extra in ((3, []), (2, ["-d", "2"])):
-        plan = ref.Plan(g, op, steps=steps)
-        want = ref.solve(op, plan, b, 150, eps)
+        plan = ref.poly(g, op, steps=steps)
+        ch = plan.lev[0].smoother
+        want = ref.solve(op, plan, b, pcg_ref.jacobi(g), 150, eps)
         s = hostapi.PCG(p, precond="poly", steps=steps)
         k = s.solve(150, eps)
         s.free()
@@ -48,7 +50,7 @@ def test_driver_runs_polynomial_pcg(gpu, exe, fmt, where, tmp):
         out = run([os.path.join(BIN, exe), "-t", "pcg", "-p", "poly", "-i", "150", "-e", repr(eps)] + extra + source)
         assert out.returncode == 0, out.stderr.decode()[-2000:]
         txt = out.stdout.decode()
-        assert re.search(LINE % (steps, re.escape("%.6g" % plan.c["lmin"]), re.escape("%.6g" % plan.c["lmax"])), txt, re.M), txt[-1500:]
+        assert re.search(LINE % (steps, re.escape("%.6g" % ch.c["lmin"]), re.escape("%.6g" % ch.c["lmax"])), txt, re.M), txt[-1500:]
         assert "Initial Residual = %E" % np.sqrt(want["rr"][0]) in txt
         assert re.search(r"^Solution performed %d iterations and took \d+\.\d\ds$" % k, txt, re.M), txt[-1500:]
     p.free(), g.free()

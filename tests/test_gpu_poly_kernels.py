@@ -1,5 +1,5 @@
 """The kernels of the Chebyshev polynomial preconditioner alone, BIT FOR BIT against the CPU restatement
-(tests/poly_ref.py, pinned by tests/test_poly_host.py), NaN equal to NaN: the r update with step 1 and the step kernel through
+(tests/precond_ref.py, pinned by tests/test_poly_host.py), NaN equal to NaN: the r update with step 1 and the step kernel through
 their native entries at the sizes where their paths change -- fewer rows than one wave's span, the partial last group, an odd n,
 every wave on a second trip of its group loop -- with +0.0, -0.0, denormals, an inf and a NaN in every vector and guard doubles
 behind them; the bound's row values, the coefficients and the interval in every format; and one apply through
@@ -9,8 +9,9 @@ import pytest
 
 from oracle import pyoracle as po
 
+import pcg_ref
 import poly_cases
-import poly_ref as ref
+import precond_ref as ref
 from sparsebench_amd import hostapi
 from sparsebench_amd.capi import DeviceVector
 
@@ -33,7 +34,7 @@ def same(got, want, what):
 
 
 def vectors(n, seed, count):
-    """`count` vectors of sgs_ref.probe_vector(special=True), each rolled by its own offset so that the special values of
+    """`count` vectors of precond_ref.probe_vector(special=True), each rolled by its own offset so that the special values of
     different vectors meet ordinary ones; dinv-like vectors are used as they come (the kernels do not ask for positive ones)"""
     return [np.roll(ref.probe_vector(n, seed + 31 * w, special=True), 5 * w) for w in range(count)]
 
@@ -145,9 +146,9 @@ def modes(p):
 @pytest.mark.parametrize("fmt,C,sigma", poly_cases.APPLY_FORMATS)
 @pytest.mark.parametrize("matrix", poly_cases.APPLY_MATRICES, ids=lambda m: "_".join(str(v) for v in m))
 def test_rowbound_coefficients_and_apply_equal_the_restatement(gpu, matrix, fmt, C, sigma, tmp):
-    g = ref.gmatrix(matrix, tmp)
-    op = ref.operator(g, fmt, C, sigma)
-    p = hostapi.Problem(*ref.problem_args(matrix, tmp), fmt=fmt, Cc=C, sigma=sigma)
+    g = pcg_ref.gmatrix(matrix, tmp)
+    op = pcg_ref.operator(g, fmt, C, sigma)
+    p = hostapi.Problem(*pcg_ref.problem_args(matrix, tmp), fmt=fmt, Cc=C, sigma=sigma)
     if sigma > 1:  # the restatement walks the device's own permutation
         assert np.array_equal(p.array("oldToNewPerm"), op.o2n if op.o2n is not None else np.arange(p.nr))
     what = (matrix, fmt, C, sigma)
@@ -156,13 +157,14 @@ def test_rowbound_coefficients_and_apply_equal_the_restatement(gpu, matrix, fmt,
         assert seen[0] == 5 or C != 64, seen
     probes = [ref.probe_vector(g.nr, 1, False), ref.probe_vector(g.nr, 2, True)]
     for steps in (1, 2, 3, 4):
-        plan = ref.Plan(g, op, steps=steps)
+        plan = ref.poly(g, op, steps=steps)
+        ch = plan.lev[0].smoother
         s = hostapi.PCG(p, precond="poly", steps=steps)
         assert s.precond() == "poly" and s.steps() == steps and s.colours() == 0 and s.levels() == 0
         same(s.dinv(), op.to_orig(plan.dinv), what + ("dinv",))
-        same(s.rowbound(), op.to_orig(plan.g), what + ("rowbound",))
-        assert s.interval() == (plan.c["lmin"], plan.c["lmax"]) and plan.c["lmax"] == np.max(plan.g)
-        same(s.coeffs(), ref.coeff_array(plan.c), what + ("coeffs", steps))
+        same(s.rowbound(), op.to_orig(ch.g), what + ("rowbound",))
+        assert s.interval() == (ch.c["lmin"], ch.c["lmax"]) and ch.c["lmax"] == np.max(ch.g)
+        same(s.coeffs(), ref.coeff_array(ch.c), what + ("coeffs", steps))
         for mode in seen:
             assert p.use_packed(mode) == mode
             for r, special in zip(probes, (False, True)):
@@ -178,17 +180,18 @@ def test_rowbound_coefficients_and_apply_equal_the_restatement(gpu, matrix, fmt,
 @pytest.mark.parametrize("steps,lmax,ratio", [(16, None, None), (1, 1.6, 4.0), (4, 1.37, 30.0), (3, 2.5, 8.0), (2, None, 4.0)])
 def test_coefficients_and_interval_for_a_callers_arguments(gpu, steps, lmax, ratio, tmp):
     matrix = ("scaled", 8)
-    g = ref.gmatrix(matrix, tmp)
-    op = ref.operator(g, "scs", 64, 256)
-    p = hostapi.Problem(*ref.problem_args(matrix, tmp), fmt="scs", Cc=64, sigma=256)
-    plan = ref.Plan(g, op, steps=steps, lmax=lmax, ratio=ref.RATIO if ratio is None else ratio)
+    g = pcg_ref.gmatrix(matrix, tmp)
+    op = pcg_ref.operator(g, "scs", 64, 256)
+    p = hostapi.Problem(*pcg_ref.problem_args(matrix, tmp), fmt="scs", Cc=64, sigma=256)
+    plan = ref.poly(g, op, steps=steps, lmax=lmax, ratio=ref.RATIO[ref.POLY] if ratio is None else ratio)
+    ch = plan.lev[0].smoother
     s = hostapi.PCG(p, precond="poly", steps=steps, lmax=lmax, ratio=ratio)
-    assert s.steps() == steps and s.interval() == (plan.c["lmin"], plan.c["lmax"])
+    assert s.steps() == steps and s.interval() == (ch.c["lmin"], ch.c["lmax"])
     if lmax is not None:
         assert s.interval()[1] == lmax
-    same(s.coeffs(), ref.coeff_array(plan.c), (steps, lmax, ratio))
+    same(s.coeffs(), ref.coeff_array(ch.c), (steps, lmax, ratio))
     assert len(s.coeffs()) == 2 * steps - 1
-    same(s.rowbound(), op.to_orig(plan.g), "rowbound")  # computed whoever supplies lmax
+    same(s.rowbound(), op.to_orig(ch.g), "rowbound")  # computed whoever supplies lmax
     r = ref.probe_vector(g.nr, 4, False)
     same(s.apply(r), op.to_orig(plan.apply(op.to_dev(r))[0]), ("apply", steps, lmax, ratio))
     s.free(), p.free(), g.free()

@@ -7,7 +7,7 @@ tests/test_gpu_mg_fw.py's (histories).  Also pinned here: how many levels each k
 import numpy as np
 import pytest
 
-import sgs_ref
+import precond_ref
 from sparsebench_amd import hostapi
 
 pytestmark = pytest.mark.gpu
@@ -34,7 +34,7 @@ def test_the_polynomial_is_the_one_level_chebyshev_cycle(problem, steps):
     assert poly.precond() == "poly" and one.precond() == "mgpoly" and poly.steps() == one.steps() == one.level_steps(0) == steps
     assert one.launches_per_body() == poly.launches_per_body()
     assert one.precond_bytes() == poly.precond_bytes()
-    r = sgs_ref.probe_vector(problem.nr, 7)
+    r = precond_ref.probe_vector(problem.nr, 7)
     assert same_bits(one.apply(r), poly.apply(r))
     assert one.solve(12, 0.0) == poly.solve(12, 0.0) == 12
     for a, b, what in zip(one.history(), poly.history(), ("rr", "rz", "pAp")):

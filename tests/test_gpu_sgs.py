@@ -1,4 +1,4 @@
-"""SGS-preconditioned CG on the GPU == the CPU restatement of its contract (tests/sgs_ref.py, pinned by
+"""SGS-preconditioned CG on the GPU == the CPU restatement of its contract (tests/precond_ref.py, pinned by
 tests/test_sgs_host.py) BIT FOR BIT: k, every r.r, every r.z, every p.Ap, x and dinv, every format, both kernel modes of the
 SpMV.  With one colour the solver is Jacobi hostapi.PCG bit for bit, and a Jacobi handle made after an SGS handle still
 reproduces pcg_ref.  (NaN compares equal to NaN.)"""
@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 
 import pcg_ref
+import precond_ref as ref
 import sgs_cases
-import sgs_ref as ref
 from conftest import load_json
 from sparsebench_amd import hostapi
 
@@ -56,7 +56,7 @@ def same(got, want, what, keys=("rr", "rz", "pAp", "x", "dinv")):
 
 
 def problem(c, tmp):
-    return hostapi.Problem(*ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
+    return hostapi.Problem(*pcg_ref.problem_args(c["matrix"], tmp), fmt=c["fmt"], Cc=c["C"], sigma=c["sigma"])
 
 
 def modes(p):
@@ -67,7 +67,8 @@ def modes(p):
 @pytest.mark.parametrize("name", sgs_cases.SMALL)
 def test_gpu_equals_the_restatement(gpu, name, tmp):
     c = sgs_cases.CASES[name]
-    g, op, plan, b, dinv, eps = ref.build_case(c, tmp)
+    plan, _, op, b, dinv, eps = ref.build_case(ref.SGS, c, tmp)
+    g, nC = plan.lev[0].g, plan.lev[0].smoother.nC
     want = ref.solve(op, plan, b, dinv, c["itermax"], eps)
     want["dinv"] = dinv
     p = problem(c, tmp)
@@ -84,17 +85,18 @@ def test_gpu_equals_the_restatement(gpu, name, tmp):
     if c["eps_rel"] > 0.0:
         assert 1 < want["k"] < c["itermax"]  # eps was reached in the middle
     s = hostapi.PCG(p, precond="sgs")
-    assert s.colours() == plan.nC
+    assert s.colours() == nC
     fused_dot = (c["fmt"] == "scs" and c["C"] == 64) or p.use_packed(5) == 5
-    assert s.launches_per_body() == 2 * plan.nC + 5 + (0 if fused_dot else 1)
+    assert s.launches_per_body() == 2 * nC + 5 + (0 if fused_dot else 1)
     p.use_packed(0)
-    assert s.launches_per_body() == 2 * plan.nC + 5 + (0 if (c["fmt"] == "scs" and c["C"] == 64) else 1)
+    assert s.launches_per_body() == 2 * nC + 5 + (0 if (c["fmt"] == "scs" and c["C"] == 64) else 1)
     s.free(), p.free(), g.free()
 
 
 def test_pieces_second_solve_and_a_jacobi_handle_afterwards(gpu, tmp):
     c = sgs_cases.CASES["scaled16_sell_64_256"]
-    g, op, plan, b, dinv, eps = ref.build_case(c, tmp)
+    plan, _, op, b, dinv, eps = ref.build_case(ref.SGS, c, tmp)
+    g = plan.lev[0].g
     p = problem(c, tmp)
     full = ref.solve(op, plan, b, dinv, 150, eps)
     full["dinv"] = dinv
@@ -229,6 +231,6 @@ def test_big_case_against_the_committed_golden(gpu, name):
         s.free()
         assert got["k"] == e["k"], (mode, got["k"])
         for key in ("rr", "rz", "pAp"):
-            assert ref.same_bits(got[key], ref.unhex(e[key])), (name, mode, key)
+            assert pcg_ref.same_bits(got[key], pcg_ref.unhex(e[key])), (name, mode, key)
         assert hashlib.sha256(np.ascontiguousarray(got["x"]).tobytes()).hexdigest() == e["x_sha256"], (name, mode)
     p.free()

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import pcg_ref
-import sgs_ref as ref
+import precond_ref as ref
 from conftest import load_json
 
 pytestmark = pytest.mark.gpu
@@ -25,9 +25,9 @@ def run(cmd):
 @pytest.fixture(scope="module")
 def want():
     """CRS and Sell-64-1 walk the same order (sigma = 1); itermax 60, eps 0: the golden case's histories in the natural order"""
-    g = ref.gmatrix(("hpcg", 16))
-    op = ref.operator(g)
-    out = ref.solve(op, ref.Plan(g, op), g.rhs(), pcg_ref.jacobi(g), ITERMAX, 0.0)
+    g = pcg_ref.gmatrix(("hpcg", 16))
+    op = pcg_ref.operator(g)
+    out = ref.solve(op, ref.sgs(g, op), g.rhs(), pcg_ref.jacobi(g), ITERMAX, 0.0)
     g.free()
     return out
 

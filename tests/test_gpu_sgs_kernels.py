@@ -1,13 +1,13 @@
 """The SGS preconditioner on the GPU without a solve: the colouring the set-up makes, and one apply through
-sb_pcg_apply_precond, == the CPU restatement (tests/sgs_ref.py, pinned by tests/test_sgs_host.py) BIT FOR BIT, NaN equal to NaN:
+sb_pcg_apply_precond, == the CPU restatement (tests/precond_ref.py, pinned by tests/test_sgs_host.py) BIT FOR BIT, NaN equal to NaN:
 colours with fewer than 64 rows, full plus partial chunks, varying row lengths, every format, hand-made matrices (1 x 1,
 diagonal, arrow, stored zeros), right-hand sides with +0.0, -0.0, a denormal, an inf and a NaN."""
 import numpy as np
 import pytest
 
 import pcg_ref
+import precond_ref as ref
 import sgs_cases
-import sgs_ref as ref
 from sparsebench_amd import hostapi
 
 pytestmark = pytest.mark.gpu
@@ -28,11 +28,12 @@ def same(got, want, what):
 
 
 def check(matrix, fmt, C, sigma, tmp, nC=None):
-    g = ref.gmatrix(matrix, tmp)
-    op = ref.operator(g, fmt, C, sigma)
-    plan = ref.Plan(g, op)
+    g = pcg_ref.gmatrix(matrix, tmp)
+    op = pcg_ref.operator(g, fmt, C, sigma)
+    hier = ref.sgs(g, op)
+    plan = hier.lev[0].smoother
     dinv = pcg_ref.jacobi(g)
-    p = hostapi.Problem(*ref.problem_args(matrix, tmp), fmt=fmt, Cc=C, sigma=sigma)
+    p = hostapi.Problem(*pcg_ref.problem_args(matrix, tmp), fmt=fmt, Cc=C, sigma=sigma)
     if sigma > 1:  # the restatement walks the device's own permutation
         assert np.array_equal(p.array("oldToNewPerm"), op.o2n if op.o2n is not None else np.arange(p.nr))
     s = hostapi.PCG(p, precond="sgs")
@@ -44,7 +45,7 @@ def check(matrix, fmt, C, sigma, tmp, nC=None):
     same(s.dinv(), dinv, what + ("dinv",))
     for seed, special in ((1, False), (2, True)):
         r = ref.probe_vector(g.nr, seed, special)
-        want = op.to_orig(plan.apply(op.to_dev(r), op.to_dev(dinv))[0])
+        want = op.to_orig(hier.apply(op.to_dev(r), op.to_dev(dinv))[0])
         same(s.apply(r), want, what + ("special" if special else "finite",))
         if g.nr > 5:
             assert np.isnan(want).any() == special

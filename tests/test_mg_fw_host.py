@@ -1,5 +1,5 @@
-"""The CPU restatement of the V-cycle with full-weighting transfers (tests/mg_fw_ref.py) pinned before the GPU is
-compared with it: the trilinear P is the host library's and scipy's kron of the 1-D operators; one level is sgs_ref bit for bit;
+"""The CPU restatement of the V-cycle with full-weighting transfers (tests/precond_ref.py) pinned before the GPU is
+compared with it: the trilinear P is the host library's and scipy's kron of the 1-D operators; one level is the SGS plan bit for bit;
 the vectorised cycle is the entry-by-entry cycle; one V-cycle is the textbook one (triangular solves, A @ z, P.T @ d, P @ zc) to
 rounding and a symmetric operator; the solve is PCG under that operator (against scipy); a stored weight of 0.0 changes nothing;
 the hierarchy counts in the natural row order, where injection's is idle: the depth changes the cycle and the iteration count
@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 import mg_fw_cases as cases
-import mg_fw_ref as ref
-import sgs_ref
+import pcg_ref
+import precond_ref as ref
 from conftest import load_json
 
 EPS = np.finfo(float).eps
@@ -86,13 +86,13 @@ def n_coarse(dims):
 @pytest.mark.parametrize("matrix,fmt,sigma", [(("hpcg", 8), "crs", 1), (("dims", 7, 7, 6), "scs", 256), (("irregular", 12), "crs", 1)])
 def test_one_level_is_sgs_bit_for_bit(matrix, fmt, sigma):
     c = dict(matrix=matrix, fmt=fmt, C=64, sigma=sigma, itermax=40, eps_rel=1e-10, coarse=[])
-    hier, transfers, op, b, dinv, eps = ref.build_case(c)
-    assert hier.L == 1 and transfers == [] and hier.launches() == 2 * hier.nC - 1
-    plan = sgs_ref.Plan(hier.lev[0].g, op)
+    hier, transfers, op, b, dinv, eps = ref.build_case(ref.MGFW, c)
+    assert hier.L == 1 and transfers == [] and hier.launches() == 2 * hier.lev[0].smoother.nC - 1
+    plan = ref.sgs(hier.lev[0].g, op)
     for special in (False, True):
         r = ref.probe_vector(hier.n, 5, special)
         assert bits_equal(hier.apply(r)[0], plan.apply(r, op.to_dev(dinv))[0])
-    got, want = ref.solve(op, hier, b, dinv, 40, eps), sgs_ref.solve(op, plan, b, dinv, 40, eps)
+    got, want = ref.solve(op, hier, b, dinv, 40, eps), ref.solve(op, plan, b, dinv, 40, eps)
     assert got["k"] == want["k"] > 5
     for key in ("rr", "rz", "pAp", "x"):
         assert bits_equal(got[key], want[key]), key
@@ -102,8 +102,8 @@ def test_one_level_is_sgs_bit_for_bit(matrix, fmt, sigma):
 def cycle_scalar(hier, transfers, l, r):
     """V(l, r) entry by entry, as the contract words it, from the transfers in original numbering"""
     V = hier.lev[l]
-    p, n = V.plan, V.n
-    z = sgs_ref.apply_scalar(p, r, V.dinv)
+    p, n = V.smoother, V.n
+    z = ref.apply_scalar(p, r, V.dinv)
     if l == hier.L - 1:
         return z
     d = np.zeros(n)
@@ -155,7 +155,7 @@ def test_vectorised_cycle_is_the_entry_by_entry_cycle(which, tmp):
     c = {"dims_4_4_4_L2": dict(matrix=("dims", 4, 4, 4), fmt="crs", C=64, sigma=1, levels=2),
          "dims_8_4_6_L2_permuted": dict(matrix=("dims", 8, 4, 6), fmt="scs", C=64, sigma=256, levels=2),
          "hand_made": cases.hand_made_case(tmp), "hand_made_permuted": cases.hand_made_case(tmp, "scs", 256)}[which]
-    hier, transfers = ref.build_hierarchy(c, tmp)
+    hier, transfers = ref.build_hierarchy(ref.MGFW, c, tmp)
     assert hier.L == 2
     for special in (False, True):
         r = ref.probe_vector(hier.n, 7, special)
@@ -173,10 +173,10 @@ def textbook(hier, transfers):
     import scipy.sparse.linalg as sl
     lev = []
     for l, V in enumerate(hier.lev):
-        A = ref.csr(V.g).tocsr()
+        A = pcg_ref.csr(V.g).tocsr()
         if V.op.o2n is not None:
             A = A[V.op.n2o][:, V.op.n2o].tocsr()
-        perm = np.argsort(V.plan.colour, kind="stable")
+        perm = np.argsort(V.smoother.colour, kind="stable")
         B = A[perm][:, perm].tocsr()
         e = dict(A=A, perm=perm, d=B.diagonal(), DL=sp.tril(B, 0).tocsr(), DU=sp.triu(B, 0).tocsr(), Lo=sp.tril(B, -1).tocsr(),
                  Up=sp.triu(B, 1).tocsr())
@@ -214,7 +214,7 @@ def test_cycle_is_the_textbook_cycle_and_symmetric(name, tmp):
     residual (a row of up to 27 terms: 27 eps), a restriction (up to 27 terms of weight <= 1, scaled: 28 eps) and a
     prolongation (up to 8 terms: 8 eps): 63 eps, taken as one more 64 eps each"""
     pytest.importorskip("scipy")
-    hier, transfers, op, b, dinv, eps = ref.build_case(cases.SCIPY_CASES[name], tmp)
+    hier, transfers, op, b, dinv, eps = ref.build_case(ref.MGFW, cases.SCIPY_CASES[name], tmp)
     bound = 64 * EPS * (2 * hier.L - 1 + hier.L - 1)
     want_of = textbook(hier, transfers)
     rng = np.random.RandomState(3)
@@ -233,11 +233,11 @@ def test_cycle_is_the_textbook_cycle_and_symmetric(name, tmp):
 def scipy_gap(c, tmp):
     """as test_mg_host.scipy_gap, with M the restated full-weighting cycle as a LinearOperator"""
     import scipy.sparse.linalg as sl
-    hier, transfers, op, b, dinv, eps = ref.build_case(c, tmp)
+    hier, transfers, op, b, dinv, eps = ref.build_case(ref.MGFW, c, tmp)
     assert op.o2n is None
     ours = ref.solve(op, hier, b, dinv, c["itermax"], eps, keep_x=True)
     xs = ours["xs"]
-    A = ref.csr(hier.lev[0].g)
+    A = pcg_ref.csr(hier.lev[0].g)
     M = sl.LinearOperator(A.shape, matvec=lambda r: hier.apply(np.asarray(r, dtype=np.float64).ravel())[0], dtype=np.float64)
     theirs = []
     sl.cg(A, b, x0=np.zeros(len(b)), rtol=0.0, atol=0.0, maxiter=len(xs), M=M, callback=lambda xk: theirs.append(xk.copy()))
@@ -270,7 +270,7 @@ def test_a_stored_weight_of_zero_changes_nothing(tmp):
         outs = []
         for store_zero in (True, False):
             c = cases.hand_made_case(tmp, fmt, sigma, store_zero)
-            hier, transfers, op, b, dinv, eps = ref.build_case(c, tmp)
+            hier, transfers, op, b, dinv, eps = ref.build_case(ref.MGFW, c, tmp)
             P = transfers[0][0]
             assert P[0][cases.EMPTY_ROW + 1] == P[0][cases.EMPTY_ROW]
             assert (0.0 in P[2].tolist()) == store_zero
@@ -282,7 +282,7 @@ def test_a_stored_weight_of_zero_changes_nothing(tmp):
             assert bits_equal(a, w)
         assert outs[0][-1]["k"] == outs[1][-1]["k"] and bits_equal(outs[0][-1]["x"], outs[1][-1]["x"])
     # the empty row keeps its z through the prolongation, the sign of a zero included (z + (+0.0) would lose it)
-    hier, transfers = ref.build_hierarchy(cases.hand_made_case(tmp), tmp)
+    hier, transfers = ref.build_hierarchy(ref.MGFW, cases.hand_made_case(tmp), tmp)
     z = np.ones(130)
     z[cases.EMPTY_ROW] = z[8] = -0.0
     zo = hier.probe(0, np.zeros(130), z, np.zeros(65))[2]
@@ -295,12 +295,12 @@ def test_in_the_natural_order_the_depth_changes_the_cycle(tmp):
     cycle is not the two sweeps, and the cycles of three and of four levels differ"""
     zs = {}
     for L in (3, 4):
-        hier, transfers = ref.build_hierarchy(dict(matrix=("hpcg", 16), fmt="crs", C=64, sigma=1, levels=L), tmp)
+        hier, transfers = ref.build_hierarchy(ref.MGFW, dict(matrix=("hpcg", 16), fmt="crs", C=64, sigma=1, levels=L), tmp)
         r = np.random.RandomState(1).standard_normal(hier.n)
         zs[L] = hier.apply(r)[0]
         two = ref.TwoSweeps(hier.lev[0]).apply(r)[0]
         V = hier.lev[0]
-        rc = V.restrict(V.residual(r, V.plan.apply(r, V.dinv)[0]))
+        rc = V.transfer.restrict(V, r, V.smoother.pre(r)[0])
         print("L", L, "||rc|| / ||r||", np.linalg.norm(rc) / np.linalg.norm(r), "||V(r) - two sweeps|| / ||V(r)||",
               np.linalg.norm(zs[L] - two) / np.linalg.norm(zs[L]))
         assert np.linalg.norm(rc) > 1e-3 * np.linalg.norm(r) and np.linalg.norm(zs[L] - two) > 1e-4 * np.linalg.norm(zs[L])
@@ -309,7 +309,7 @@ def test_in_the_natural_order_the_depth_changes_the_cycle(tmp):
 
 
 def count(c, tmp):
-    hier, transfers, op, b, dinv, eps = ref.build_case(c, tmp)
+    hier, transfers, op, b, dinv, eps = ref.build_case(ref.MGFW, c, tmp)
     k = ref.solve(op, hier, b, dinv, c["itermax"], eps)["k"]
     L = hier.L
     hier.free()
@@ -332,12 +332,12 @@ def test_iteration_count_falls_below_the_two_sweeps(name, tmp, golden, mg_golden
 
 
 def golden_record(out):
-    rec = ref.record(out)
+    rec = pcg_ref.record(out)
     rec["nC"], rec["L"], rec["rows"] = [int(v) for v in out["nC"]], int(out["L"]), [int(v) for v in out["rows"]]
     return rec
 
 
 @pytest.mark.parametrize("name", cases.SMALL)
 def test_the_committed_golden_is_what_the_restatement_gives(name, tmp, golden):
-    assert golden_record(ref.run_case(cases.CASES[name], tmp)) == golden["cases"][name]
+    assert golden_record(ref.run_case(ref.MGFW, cases.CASES[name], tmp)) == golden["cases"][name]
     assert set(golden["cases"]) == set(cases.CASES)

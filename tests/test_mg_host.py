@@ -1,5 +1,5 @@
-"""The CPU restatement of MG-preconditioned CG (tests/mg_ref.py) pinned before the GPU is compared with it: one
-level is sgs_ref bit for bit; the vectorised cycle is the entry-by-entry cycle; one V-cycle is the textbook one (triangular
+"""The CPU restatement of MG-preconditioned CG (tests/precond_ref.py) pinned before the GPU is compared with it: one
+level is the SGS plan bit for bit; the vectorised cycle is the entry-by-entry cycle; one V-cycle is the textbook one (triangular
 solves in colour order, a sparse A z, fancy-indexed injection) to rounding; the cycle is a symmetric operator; the solve is PCG
 under that operator (against scipy); the geometric hierarchy's rule and injection map are the host library's; the iteration
 count drops against SGS and Jacobi -- by as much as the two sweeps of level 0 alone give; in the natural row order the coarse
@@ -8,9 +8,8 @@ import numpy as np
 import pytest
 
 import mg_cases
-import mg_ref as ref
 import pcg_ref
-import sgs_ref
+import precond_ref as ref
 from conftest import load_json
 
 EPS = np.finfo(float).eps
@@ -34,13 +33,13 @@ def bits_equal(a, w):
 @pytest.mark.parametrize("matrix,fmt,sigma", [(("hpcg", 8), "crs", 1), (("dims", 7, 7, 6), "scs", 256), (("irregular", 12), "crs", 1)])
 def test_one_level_is_sgs_bit_for_bit(matrix, fmt, sigma):
     c = dict(matrix=matrix, fmt=fmt, C=64, sigma=sigma, itermax=40, eps_rel=1e-10, coarse=[])
-    hier, f2cs, op, b, dinv, eps = ref.build_case(c)
-    assert hier.L == 1 and f2cs == [] and hier.launches() == 2 * hier.nC - 1
-    plan = sgs_ref.Plan(hier.lev[0].g, op)
+    hier, f2cs, op, b, dinv, eps = ref.build_case(ref.MG, c)
+    assert hier.L == 1 and f2cs == [] and hier.launches() == 2 * hier.lev[0].smoother.nC - 1
+    plan = ref.sgs(hier.lev[0].g, op)
     for special in (False, True):
         r = ref.probe_vector(hier.n, 5, special)
         assert bits_equal(hier.apply(r)[0], plan.apply(r, op.to_dev(dinv))[0])
-    got, want = ref.solve(op, hier, b, dinv, 40, eps), sgs_ref.solve(op, plan, b, dinv, 40, eps)
+    got, want = ref.solve(op, hier, b, dinv, 40, eps), ref.solve(op, plan, b, dinv, 40, eps)
     assert got["k"] == want["k"] > 5
     for key in ("rr", "rz", "pAp", "x"):
         assert bits_equal(got[key], want[key]), key
@@ -50,20 +49,20 @@ def test_one_level_is_sgs_bit_for_bit(matrix, fmt, sigma):
 def cycle_scalar(hier, l, r):
     """V(l, r) entry by entry, as the contract words it"""
     V = hier.lev[l]
-    p, n = V.plan, V.n
-    ptr, col, val = sgs_ref.device_rows(V.g, V.op)
-    z = sgs_ref.apply_scalar(p, r, V.dinv)
+    p, n, fine = V.smoother, V.n, V.transfer and V.transfer.fine
+    ptr, col, val = ref.device_rows(V.g, V.op)
+    z = ref.apply_scalar(p, r, V.dinv)
     if l == hier.L - 1:
         return z
-    rc = np.zeros(len(V.fine))
-    for c, f in enumerate(V.fine):
+    rc = np.zeros(len(fine))
+    for c, f in enumerate(fine):
         s = np.float64(r[f])
         for e in range(ptr[f], ptr[f + 1]):
             if val[e] != 0.0:
                 s = s - val[e] * z[col[e]]
         rc[c] = s
     zc = cycle_scalar(hier, l + 1, rc)
-    for c, f in enumerate(V.fine):
+    for c, f in enumerate(fine):
         z[f] = z[f] + zc[c]
     t = np.zeros(n)
     for c in range(p.nC):
@@ -94,7 +93,7 @@ def test_vectorised_cycle_is_the_entry_by_entry_cycle(which, tmp):
     c = {"dims_4_4_4_L2": dict(matrix=("dims", 4, 4, 4), fmt="crs", C=64, sigma=1, levels=2),
          "dims_8_4_6_L2_permuted": dict(matrix=("dims", 8, 4, 6), fmt="scs", C=64, sigma=256, levels=2),
          "hand_made": hand_made_case(tmp), "hand_made_permuted": hand_made_case(tmp, "scs", 256)}[which]
-    hier, f2cs = ref.build_hierarchy(c, tmp)
+    hier, f2cs = ref.build_hierarchy(ref.MG, c, tmp)
     assert hier.L == 2
     for special in (False, True):
         r = ref.probe_vector(hier.n, 7, special)
@@ -112,13 +111,13 @@ def textbook(hier):
     import scipy.sparse.linalg as sl
     lev = []
     for V in hier.lev:
-        A = ref.csr(V.g).tocsr()
+        A = pcg_ref.csr(V.g).tocsr()
         if V.op.o2n is not None:
             A = A[V.op.n2o][:, V.op.n2o].tocsr()
-        perm = np.argsort(V.plan.colour, kind="stable")
+        perm = np.argsort(V.smoother.colour, kind="stable")
         B = A[perm][:, perm].tocsr()
         lev.append(dict(A=A, perm=perm, d=B.diagonal(), DL=sp.tril(B, 0).tocsr(), DU=sp.triu(B, 0).tocsr(), Lo=sp.tril(B, -1).tocsr(),
-                        Up=sp.triu(B, 1).tocsr(), fine=V.fine))
+                        Up=sp.triu(B, 1).tocsr(), fine=V.transfer and V.transfer.fine))
 
     def cycle(l, r):
         v = lev[l]
@@ -137,7 +136,7 @@ def textbook(hier):
 
 
 def scipy_case(name, tmp):
-    return ref.build_case(mg_cases.SCIPY_CASES[name], tmp)
+    return ref.build_case(ref.MG, mg_cases.SCIPY_CASES[name], tmp)
 
 
 @pytest.mark.parametrize("name", list(mg_cases.SCIPY_CASES))
@@ -164,11 +163,11 @@ def test_cycle_is_the_textbook_cycle_and_symmetric(name, tmp):
 def scipy_gap(c, tmp):
     """as test_sgs_host.scipy_gap, with M the restated cycle as a LinearOperator"""
     import scipy.sparse.linalg as sl
-    hier, f2cs, op, b, dinv, eps = ref.build_case(c, tmp)
+    hier, f2cs, op, b, dinv, eps = ref.build_case(ref.MG, c, tmp)
     assert op.o2n is None
     ours = ref.solve(op, hier, b, dinv, c["itermax"], eps, keep_x=True)
     xs = ours["xs"]
-    A = ref.csr(hier.lev[0].g)
+    A = pcg_ref.csr(hier.lev[0].g)
     M = sl.LinearOperator(A.shape, matvec=lambda r: hier.apply(np.asarray(r, dtype=np.float64).ravel())[0], dtype=np.float64)
     theirs = []
     sl.cg(A, b, x0=np.zeros(len(b)), rtol=0.0, atol=0.0, maxiter=len(xs), M=M, callback=lambda xk: theirs.append(xk.copy()))
@@ -221,10 +220,10 @@ def test_geometric_rule_and_injection_map_are_the_host_librarys():
 
 
 def counts(c, tmp):
-    hier, f2cs, op, b, dinv, eps = ref.build_case(c, tmp)
+    hier, f2cs, op, b, dinv, eps = ref.build_case(ref.MG, c, tmp)
     out = dict(k_jacobi=pcg_ref.solve(op, b, dinv, c["itermax"], eps)["k"],
-               k_sgs=sgs_ref.solve(op, hier.lev[0].plan, b, dinv, c["itermax"], eps)["k"],
-               k_two_sweeps=sgs_ref.solve(op, ref.TwoSweeps(hier.lev[0]), b, dinv, c["itermax"], eps)["k"],
+               k_sgs=ref.solve(op, ref.sgs(hier.lev[0].g, op), b, dinv, c["itermax"], eps)["k"],
+               k_two_sweeps=ref.solve(op, ref.TwoSweeps(hier.lev[0]), b, dinv, c["itermax"], eps)["k"],
                k_mg=ref.solve(op, hier, b, dinv, c["itermax"], eps)["k"], L=hier.L)
     hier.free()
     return out
@@ -245,8 +244,8 @@ def hierarchy_effect(hier, seed=1):
     """||rc|| / ||r|| on level 0 after the pre-smoothing, and V(0, r) against the two sweeps without coarse levels"""
     r = np.random.RandomState(seed).standard_normal(hier.n)
     V = hier.lev[0]
-    z0 = V.plan.apply(r, V.dinv)[0]
-    rc = V.restrict_residual(r, z0)
+    z0 = V.smoother.pre(r)[0]
+    rc = V.transfer.restrict(V, r, z0)
     z, two = hier.apply(r)[0], ref.TwoSweeps(V).apply(r)[0]
     return float(np.linalg.norm(rc) / np.linalg.norm(r)), z, two
 
@@ -260,9 +259,10 @@ def test_in_the_natural_order_the_coarse_levels_are_idle(which, tmp):
     prolongation added is overwritten.  The cycle is then the two sweeps of level 0 BIT FOR BIT, whatever the coarse levels hold."""
     c = {"hpcg16_crs_L4": dict(matrix=("hpcg", 16), fmt="crs", C=64, sigma=1, levels=4),
          "hpcg16_sell_64_1_L4": dict(matrix=("hpcg", 16), fmt="scs", C=64, sigma=1, levels=4), "hand_made_crs": hand_made_case(tmp)}[which]
-    hier, f2cs = ref.build_hierarchy(c, tmp)
+    hier, f2cs = ref.build_hierarchy(ref.MG, c, tmp)
     V = hier.lev[0]
-    assert set(V.plan.colour[V.fine].tolist()) == {0} and len(V.fine) == len(V.plan.rows[0])  # coarse points == colour 0
+    fine = V.transfer.fine
+    assert set(V.smoother.colour[fine].tolist()) == {0} and len(fine) == len(V.smoother.rows[0])  # coarse points == colour 0
     rel, z, two = hierarchy_effect(hier)
     print(which, "||rc|| / ||r||", rel)
     assert rel <= 64 * EPS
@@ -277,9 +277,9 @@ def test_in_a_permuted_order_the_coarse_levels_change_the_cycle(which, tmp):
     two sweeps (the tests that compare the GPU's restriction and prolongation with the restatement stand on these orders)"""
     c = {"hpcg16_sell_64_256_L4": dict(matrix=("hpcg", 16), fmt="scs", C=64, sigma=256, levels=4),
          "hand_made_permuted": hand_made_case(tmp, "scs", 256)}[which]
-    hier, f2cs = ref.build_hierarchy(c, tmp)
+    hier, f2cs = ref.build_hierarchy(ref.MG, c, tmp)
     V = hier.lev[0]
-    assert 0 not in set(V.plan.colour[V.fine].tolist())
+    assert 0 not in set(V.smoother.colour[V.transfer.fine].tolist())
     rel, z, two = hierarchy_effect(hier)
     diff = float(np.linalg.norm(z - two) / np.linalg.norm(z))
     print(which, "||rc|| / ||r||", rel, "||V(r) - two sweeps|| / ||V(r)||", diff)
@@ -288,12 +288,12 @@ def test_in_a_permuted_order_the_coarse_levels_change_the_cycle(which, tmp):
 
 
 def golden_record(out):
-    rec = ref.record(out)
+    rec = pcg_ref.record(out)
     rec["nC"], rec["L"], rec["rows"] = [int(v) for v in out["nC"]], int(out["L"]), [int(v) for v in out["rows"]]
     return rec
 
 
 @pytest.mark.parametrize("name", mg_cases.SMALL)
 def test_the_committed_golden_is_what_the_restatement_gives(name, tmp, golden):
-    assert golden_record(ref.run_case(mg_cases.CASES[name], tmp)) == golden["cases"][name]
+    assert golden_record(ref.run_case(ref.MG, mg_cases.CASES[name], tmp)) == golden["cases"][name]
     assert set(golden["cases"]) == set(mg_cases.CASES)

@@ -1,14 +1,14 @@
-"""The CPU restatement of the Chebyshev-smoothed V-cycle (tests/mg_poly_ref.py) pinned before the GPU is compared with
+"""The CPU restatement of the Chebyshev-smoothed V-cycle (tests/precond_ref.py) pinned before the GPU is compared with
 it: one V-cycle is the textbook one from scipy's pieces (A @ z, P.T @, P @) to rounding; the solve is PCG under that operator
-(against scipy); one level is poly_ref bit for bit; the cycle's matrix is symmetric and positive definite; the launch count and
+(against scipy); one level is the polynomial plan bit for bit; the cycle's matrix is symmetric and positive definite; the launch count and
 the byte model are the formulas of the contract; hostapi.mg_galerkin's matrices are P^T A P and survive their files bit for bit;
 the iteration count does not grow from 16^3 to 32^3; tests/golden/mg_poly_hist.json holds what the restatement gives."""
 import numpy as np
 import pytest
 
 import mg_poly_cases as cases
-import mg_poly_ref as ref
-import poly_ref
+import pcg_ref
+import precond_ref as ref
 from conftest import load_json
 
 EPS = np.finfo(float).eps
@@ -40,10 +40,10 @@ def textbook(hier, transfers):
     import scipy.sparse as sp
     lev = []
     for l, V in enumerate(hier.lev):
-        A = ref.csr(V.g).tocsr()
+        A = pcg_ref.csr(V.g).tocsr()
         if V.op.o2n is not None:
             A = A[V.op.n2o][:, V.op.n2o].tocsr()
-        e = dict(A=A, dinv=1.0 / A.diagonal(), c=V.plan.c, steps=V.steps)
+        e = dict(A=A, dinv=1.0 / A.diagonal(), c=V.smoother.c, steps=V.smoother.steps)
         if l + 1 < hier.L:
             (ptr, col, val), e["omega"] = transfers[l]
             P = sp.csr_matrix((val, col, ptr), shape=(V.n, hier.lev[l + 1].n))
@@ -84,7 +84,7 @@ def test_cycle_is_the_textbook_cycle_and_symmetric(name, steps, tmp):
     (32 eps), so two steps stand for one of those applies: 32 eps * steps * (2 L - 1) for the smoothings, 64 eps * (L - 1) for
     the transfers and the residual's SpMV"""
     pytest.importorskip("scipy")
-    hier, transfers, op, b, eps = ref.build_case(dict(cases.SCIPY_CASES[name], steps=steps), tmp)
+    hier, transfers, op, b, dinv, eps = ref.build_case(ref.MGPOLY, dict(cases.SCIPY_CASES[name], steps=steps), tmp)
     bound = EPS * (32 * steps * (2 * hier.L - 1) + 64 * (hier.L - 1))
     want_of = textbook(hier, transfers)
     rng = np.random.RandomState(3)
@@ -103,11 +103,11 @@ def test_cycle_is_the_textbook_cycle_and_symmetric(name, steps, tmp):
 def scipy_gap(c, tmp):
     """as test_mg_fw_host.scipy_gap, with M the restated Chebyshev-smoothed cycle as a LinearOperator"""
     import scipy.sparse.linalg as sl
-    hier, transfers, op, b, eps = ref.build_case(c, tmp)
+    hier, transfers, op, b, dinv, eps = ref.build_case(ref.MGPOLY, c, tmp)
     assert op.o2n is None
-    ours = ref.solve(op, hier, b, c["itermax"], eps, keep_x=True)
+    ours = ref.solve(op, hier, b, dinv, c["itermax"], eps, keep_x=True)
     xs = ours["xs"]
-    A = ref.csr(hier.lev[0].g)
+    A = pcg_ref.csr(hier.lev[0].g)
     M = sl.LinearOperator(A.shape, matvec=lambda r: hier.apply(np.asarray(r, dtype=np.float64).ravel())[0], dtype=np.float64)
     theirs = []
     sl.cg(A, b, x0=np.zeros(len(b)), rtol=0.0, atol=0.0, maxiter=len(xs), M=M, callback=lambda xk: theirs.append(xk.copy()))
@@ -139,16 +139,16 @@ def test_one_level_is_poly_ref_bit_for_bit(matrix, fmt, sigma, coarse_steps):
     """steps := coarse_steps: the only level is the last one"""
     c = dict(matrix=matrix, fmt=fmt, C=64, sigma=sigma, itermax=40, eps_rel=1e-10, coarse=[], steps=5, coarse_steps=coarse_steps,
              ratio=16.0)
-    hier, transfers, op, b, eps = ref.build_case(c)
+    hier, transfers, op, b, dinv, eps = ref.build_case(ref.MGPOLY, c)
     assert hier.L == 1 and transfers == [] and hier.launches_per_body() == 5 + 2 * (coarse_steps - 1)
-    plan = poly_ref.Plan(hier.lev[0].g, op, steps=coarse_steps)
-    assert hier.lev[0].plan.c == plan.c
+    plan = ref.poly(hier.lev[0].g, op, steps=coarse_steps)
+    assert hier.lev[0].smoother.c == plan.lev[0].smoother.c
     assert hier.bytes() == (coarse_steps - 1) * (hier.lev[0].spmv_bytes() + 56.0 * hier.n) + 24.0 * hier.n
     for special in (False, True):
         r = ref.probe_vector(hier.n, 5, special)
         with np.errstate(all="ignore"):
             assert bits_equal(hier.apply(r)[0], plan.apply(r)[0])
-    got, want = ref.solve(op, hier, b, 40, eps), poly_ref.solve(op, plan, b, 40, eps)
+    got, want = ref.solve(op, hier, b, dinv, 40, eps), ref.solve(op, plan, b, dinv, 40, eps)
     assert got["k"] == want["k"] > 5
     for key in ("rr", "rz", "pAp", "x"):
         assert bits_equal(got[key], want[key]), key
@@ -162,8 +162,8 @@ def test_cycle_matrix_is_symmetric_and_positive_definite(steps, galerkin, tmp):
     rounding, and positive definite since every level's spectrum of D^-1 A lies in (0, lmax_l]"""
     pytest.importorskip("scipy")
     c = dict(matrix=("hpcg", 8), fmt="crs", C=64, sigma=1, levels=2, steps=steps, galerkin=galerkin)
-    hier, transfers = ref.build_hierarchy(c, tmp)
-    assert hier.L == 2 and hier.lev[0].omega == (1.0 if galerkin else 0.25)
+    hier, transfers = ref.build_hierarchy(ref.MGPOLY, c, tmp)
+    assert hier.L == 2 and hier.lev[0].transfer.omega == (1.0 if galerkin else 0.25)
     M = ref.dense_apply(hier)
     asym = np.abs(M - M.T).max() / np.abs(M).max()
     w = np.linalg.eigvalsh((M + M.T) * 0.5)
@@ -171,10 +171,10 @@ def test_cycle_matrix_is_symmetric_and_positive_definite(steps, galerkin, tmp):
     assert asym <= 64 * EPS * (3 * steps + 1)
     assert w[0] > 0.0
     for V in hier.lev:  # the premise: lambda(D^-1 A) in (0, lmax]
-        A = ref.csr(V.g).toarray()
+        A = pcg_ref.csr(V.g).toarray()
         sd = np.sqrt(1.0 / np.diag(A))
         lam = np.linalg.eigvalsh(sd[:, None] * A * sd[None, :])
-        assert 0.0 < lam[0] and lam[-1] <= V.plan.c["lmax"]
+        assert 0.0 < lam[0] and lam[-1] <= V.smoother.c["lmax"]
     hier.free()
 
 
@@ -183,7 +183,7 @@ def test_launch_count_is_the_contracts(L, steps, coarse_steps, want, tmp):
     """4 + (L - 1) (4 steps + 2) + 2 coarse_steps - 1, plus 1 where the SpMV has no fused dot: 23 at steps = 1, L = 4 and 37 at the
     defaults, where the full-weighting cycle with Gauss-Seidel sweeps has 120"""
     c = dict(matrix=("hpcg", 16), fmt="crs", C=64, sigma=1, levels=L, steps=steps, coarse_steps=coarse_steps)
-    hier, transfers = ref.build_hierarchy(c, tmp)
+    hier, transfers = ref.build_hierarchy(ref.MGPOLY, c, tmp)
     cs = steps if coarse_steps is None else coarse_steps
     assert hier.L == L and hier.launches_per_body() == 4 + (L - 1) * (4 * steps + 2) + 2 * cs - 1 == want
     assert hier.launches_per_body(fused_dot=False) == want + 1
@@ -195,17 +195,19 @@ def test_byte_model_is_the_contracts_formula(fmt, C, sigma, tmp):
     """counted operation by operation in the restatement == the closed formula of DESIGN 4.16 and sbhip.h; integers in doubles"""
     for steps, cs in ((1, 1), (2, 2), (3, 1), (2, 5)):
         c = dict(matrix=("dims", 12, 8, 20), fmt=fmt, C=C, sigma=sigma, levels=3, steps=steps, coarse_steps=cs)
-        hier, transfers = ref.build_hierarchy(c, tmp)
+        hier, transfers = ref.build_hierarchy(ref.MGPOLY, c, tmp)
         want = 0.0
         for V in hier.lev[:-1]:
-            want += 2 * steps * V.spmv_bytes() + (2 * (steps - 1) * 56.0 + 48.0 + 24.0) * V.n + V.transfer_bytes() + 32.0 * V.n + 16.0 * V.nc
+            want += 2 * steps * V.spmv_bytes() + (2 * (steps - 1) * 56.0 + 48.0 + 24.0) * V.n
+            want += V.transfer.bytes() + 32.0 * V.n + 16.0 * V.transfer.nc
         last = hier.lev[-1]
         want += (cs - 1) * (last.spmv_bytes() + 56.0 * last.n) + 24.0 * last.n
         assert hier.bytes() == want and want == int(want)
         hier.free()
     # the structures: 12 B per padded element, 64 row lengths and 12 B per chunk; P^T of 12 x 8 x 20 has 240 rows, 27 entries at most
-    V = ref.build_hierarchy(dict(matrix=("dims", 12, 8, 20), fmt="crs", C=64, sigma=1, levels=2), tmp)[0].lev[0]
-    assert V.nc == 240 and int(V.PT[0].max()) == 27 and int(V.P[0].max()) == 8
+    V = ref.build_hierarchy(ref.MGPOLY, dict(matrix=("dims", 12, 8, 20), fmt="crs", C=64, sigma=1, levels=2), tmp)[0].lev[0]
+    T = V.transfer
+    assert T.nc == 240 and int(T.PT[0].max()) == 27 and int(T.P[0].max()) == 8
     assert V.spmv_bytes() == 12.0 * int(V.g.rowPtr[V.g.nr]) + 4.0 * 1921 + 16.0 * 1920
 
 
@@ -236,8 +238,8 @@ def test_mg_galerkin_is_pt_a_p_and_survives_its_files(tmp):
         assert q.fmt == "crs" and q.filename.endswith(".mtx")
         dims = tuple(v // 2 for v in dims)
     # 17 significant digits bring every double back: a matrix whose values are not short decimals, through mg_galerkin's writer
-    g = ref.gmatrix(("scaled", 8), tmp)
-    S = ref.csr(g)
+    g = pcg_ref.gmatrix(("scaled", 8), tmp)
+    S = pcg_ref.csr(g)
     Pt = ref.trilinear((8, 8, 8))
     gc, Ac = ref.galerkin_gmatrix(S, sp.csr_matrix((Pt[2], Pt[1], Pt[0]), shape=(512, 64)))
     path = str(d / "scaled.mtx")
@@ -255,8 +257,8 @@ def test_mg_galerkin_is_pt_a_p_and_survives_its_files(tmp):
 
 
 def count(c, tmp):
-    hier, transfers, op, b, eps = ref.build_case(c, tmp)
-    k = ref.solve(op, hier, b, c["itermax"], eps)["k"]
+    hier, transfers, op, b, dinv, eps = ref.build_case(ref.MGPOLY, c, tmp)
+    k = ref.solve(op, hier, b, dinv, c["itermax"], eps)["k"]
     L = hier.L
     hier.free()
     return k, L
@@ -278,7 +280,7 @@ def test_iteration_count_does_not_grow_with_the_grid(tmp, golden):
 @pytest.mark.parametrize("n", [16, 32])
 def test_the_count_table_of_the_design_document(n, tmp, golden):
     """DESIGN 4.16's table (Jacobi, the polynomial, the regenerated hierarchy at omega = 1/2 and 1/4, the Galerkin one, steps 1 / 2 / 3)
-    is mg_poly_ref.count_table's, recorded by the golden's maker; 16^3 and 32^3 are recomputed here, 64^3 (minutes) only by the maker"""
+    is precond_ref.count_table's, recorded by the golden's maker; 16^3 and 32^3 are recomputed here, 64^3 (minutes) only by the maker"""
     pytest.importorskip("scipy")
     assert ref.count_table(n) == golden["table"][str(n)]
     assert set(golden["table"]) == {"16", "32", "64"}
@@ -287,7 +289,7 @@ def test_the_count_table_of_the_design_document(n, tmp, golden):
 
 
 def golden_record(out):
-    rec = ref.record(out)
+    rec = pcg_ref.record(out)
     rec["L"], rec["rows"] = int(out["L"]), [int(v) for v in out["rows"]]
     rec["coeffs"] = [[float(v).hex() for v in level] for level in out["coeffs"]]
     rec["intervals"] = [[float(v).hex() for v in level] for level in out["intervals"]]
@@ -298,5 +300,5 @@ def golden_record(out):
 @pytest.mark.parametrize("name", cases.SMALL)
 def test_the_committed_golden_is_what_the_restatement_gives(name, tmp, golden):
     pytest.importorskip("scipy")
-    assert golden_record(ref.run_case(cases.CASES[name], tmp)) == golden["cases"][name]
+    assert golden_record(ref.run_case(ref.MGPOLY, cases.CASES[name], tmp)) == golden["cases"][name]
     assert set(golden["cases"]) == set(cases.CASES)

@@ -1,4 +1,4 @@
-"""The CPU restatement of PCG with the Chebyshev polynomial preconditioner (tests/poly_ref.py) pinned before the
+"""The CPU restatement of PCG with the Chebyshev polynomial preconditioner (tests/precond_ref.py) pinned before the
 GPU is compared with it: the apply is q(D^-1 A) D^-1 r by the three-term recurrence (against scipy's A @ z) and the residual
 polynomial is the scaled Chebyshev polynomial; its matrix is symmetric and positive definite; the symmetric row-sum bound is 53/27
 on the stencil, scaled or not, where the naive one is useless; the solve is PCG under that operator (against scipy); the
@@ -10,7 +10,7 @@ import pytest
 import pcg_cases
 import pcg_ref
 import poly_cases
-import poly_ref as ref
+import precond_ref as ref
 from conftest import load_json
 
 EPS = np.finfo(float).eps
@@ -27,13 +27,15 @@ def tmp(tmp_path_factory):
 
 
 def plan_of(matrix, fmt="crs", C=64, sigma=1, tmp=None, **kw):
-    g = ref.gmatrix(matrix, tmp)
-    op = ref.operator(g, fmt, C, sigma)
-    return g, op, ref.Plan(g, op, **kw)
+    """(g, operator, the one-level hierarchy, its Cheb)"""
+    g = pcg_ref.gmatrix(matrix, tmp)
+    op = pcg_ref.operator(g, fmt, C, sigma)
+    plan = ref.poly(g, op, **kw)
+    return g, op, plan, plan.lev[0].smoother
 
 
 def dev_matrix(g, op):
-    A = ref.csr(g).tocsr()
+    A = pcg_ref.csr(g).tocsr()
     if op.o2n is None:
         return A
     return A[op.n2o][:, op.n2o].tocsr()
@@ -63,10 +65,10 @@ def test_apply_is_the_three_term_recurrence(matrix, fmt, sigma, steps, tmp):
     operations per step, each relative to quantities no larger than ||z|| in norm (|D^-1 A| has row sums <= 2 on these
     matrices, a_j < 1, b_j < 2): bound steps * (L + 8) eps ||z||"""
     pytest.importorskip("scipy")
-    g, op, plan = plan_of(matrix, fmt, 64, sigma, tmp, steps=steps)
+    g, op, plan, ch = plan_of(matrix, fmt, 64, sigma, tmp, steps=steps)
     A = dev_matrix(g, op)
     L = int(np.diff(A.indptr).max())
-    c = plan.c
+    c = ch.c
     theta, delta = (c["lmax"] + c["lmin"]) / 2, (c["lmax"] - c["lmin"]) / 2
     rng = np.random.RandomState(3)
     r = rng.standard_normal(g.nr)
@@ -92,7 +94,7 @@ def test_apply_is_symmetric_positive_definite_and_chebyshev(steps):
     apply of O(steps * 35) roundings at entries <= 1: bound 1e-13 absolute), positive definite, and its residual polynomial is
     the scaled Chebyshev polynomial: I - M A = T_s((theta - D^-1 A) / delta) / T_s(sigma), taken densely by T's own recurrence
     (entries of T_k grow to T_s(sigma) < 10 before the division, n = 512 terms per product: bound 1e-11 absolute)."""
-    g, op, plan = plan_of(("hpcg", 8), steps=steps)
+    g, op, plan, ch = plan_of(("hpcg", 8), steps=steps)
     n = g.nr
     M = ref.dense_apply(plan)
     asym = float(np.max(np.abs(M - M.T)))
@@ -105,7 +107,7 @@ def test_apply_is_symmetric_positive_definite_and_chebyshev(steps):
         e = np.zeros(n)
         e[i] = 1.0
         A[:, i] = op.spmv(e)
-    c = plan.c
+    c = ch.c
     theta, delta = (c["lmax"] + c["lmin"]) / 2, (c["lmax"] - c["lmin"]) / 2
     X = (theta * np.eye(n) - plan.dinv[:, None] * A) / delta
     sigma = theta / delta
@@ -126,14 +128,14 @@ def test_symmetric_bound_is_two_where_the_naive_bound_is_useless(tmp):
     sum of D^-1 A is not"""
     seen = []
     for matrix in (("hpcg", 16), ("scaled", 16)):
-        g, op, plan = plan_of(matrix, tmp=tmp)
+        g, op, plan, ch = plan_of(matrix, tmp=tmp)
         assert set(pcg_ref.diagonal(g) / (pcg_cases.scale(np.arange(g.nr)) ** 2 if matrix[0] == "scaled" else 1.0)) == {27.0}
-        lmax = float(np.max(plan.g))
+        lmax = float(np.max(ch.g))
         naive = ref.naive_bound(g)
         print(matrix, "bound", repr(lmax), "in ulps of 2.0 from 53/27:", (lmax - 53.0 / 27.0) / np.spacing(2.0), "naive", naive)
         assert abs(lmax - 53.0 / 27.0) <= 2 * np.spacing(2.0)
         assert lmax <= 2.0
-        assert plan.c["lmax"] == lmax and plan.c["lmin"] == lmax / 16.0
+        assert ch.c["lmax"] == lmax and ch.c["lmin"] == lmax / 16.0
         if matrix[0] == "scaled":
             assert naive > 10.0 * lmax
         else:
@@ -145,22 +147,23 @@ def test_symmetric_bound_is_two_where_the_naive_bound_is_useless(tmp):
 
 def test_rowbound_is_the_same_in_every_row_order(tmp):
     """the bound's row values do not depend on the format: a row's entries keep their storage order under the permutation"""
-    g, op, plan = plan_of(("irregular", 12))
+    g, op, plan, ch = plan_of(("irregular", 12))
     for fmt, C, sigma in (("scs", 64, 256), ("scs", 4, 8)):
-        op2 = ref.operator(g, fmt, C, sigma)
-        plan2 = ref.Plan(g, op2)
-        assert ref.same_bits(op2.to_orig(plan2.g), op.to_orig(plan.g))
+        op2 = pcg_ref.operator(g, fmt, C, sigma)
+        ch2 = ref.poly(g, op2).lev[0].smoother
+        assert pcg_ref.same_bits(op2.to_orig(ch2.g), op.to_orig(ch.g))
     g.free()
 
 
 def scipy_gap(c, tmp):
     """as test_pcg_host.scipy_gap, with M the restatement's own apply as a LinearOperator"""
     import scipy.sparse.linalg as sl
-    g, op, plan, b, eps = ref.build_case(c, tmp)
+    plan, _, op, b, dinv, eps = ref.build_case(ref.POLY, c, tmp)
+    g = plan.lev[0].g
     assert op.o2n is None
-    ours = ref.solve(op, plan, b, c["itermax"], eps, keep_x=True)
+    ours = ref.solve(op, plan, b, dinv, c["itermax"], eps, keep_x=True)
     xs = ours["xs"]
-    A = ref.csr(g)
+    A = pcg_ref.csr(g)
     M = sl.LinearOperator(A.shape, matvec=lambda r: plan.apply(np.asarray(r, dtype=np.float64).ravel())[0], dtype=np.float64)
     theirs = []
     sl.cg(A, b, x0=np.zeros(len(b)), rtol=0.0, atol=0.0, maxiter=len(xs), M=M, callback=lambda xk: theirs.append(xk.copy()))
@@ -188,9 +191,10 @@ def test_restatement_is_pcg_against_scipy(name, tmp, golden):
 @pytest.mark.parametrize("name", list(poly_cases.COUNT_CASES))
 def test_iteration_count_drops_against_jacobi(name, tmp, golden):
     c = poly_cases.COUNT_CASES[name]
-    g, op, plan, b, eps = ref.build_case(c, tmp)
-    k_poly = ref.solve(op, plan, b, c["itermax"], eps)["k"]
-    k_jacobi = pcg_ref.solve(op, b, pcg_ref.jacobi(g), c["itermax"], eps)["k"]
+    plan, _, op, b, dinv, eps = ref.build_case(ref.POLY, c, tmp)
+    g = plan.lev[0].g
+    k_poly = ref.solve(op, plan, b, dinv, c["itermax"], eps)["k"]
+    k_jacobi = pcg_ref.solve(op, b, dinv, c["itermax"], eps)["k"]
     print(name, "k_jacobi", k_jacobi, "k_poly", k_poly)
     assert k_poly < k_jacobi < c["itermax"]
     assert golden["counts"][name] == dict(k_jacobi=k_jacobi, k_poly=k_poly)
@@ -198,37 +202,37 @@ def test_iteration_count_drops_against_jacobi(name, tmp, golden):
 
 
 def test_one_step_with_c1_one_is_jacobi_pcg_bit_for_bit(tmp):
-    g, op, plan = plan_of(("scaled", 8), "scs", 4, 8, tmp, steps=1, lmax=1.6, ratio=4.0)
-    assert plan.c["c1"] == 1.0
+    g, op, plan, ch = plan_of(("scaled", 8), "scs", 4, 8, tmp, steps=1, lmax=1.6, ratio=4.0)
+    assert ch.c["c1"] == 1.0
     b = g.rhs()
-    got, want = ref.solve(op, plan, b, 40, 0.0), pcg_ref.solve(op, b, pcg_ref.jacobi(g), 40, 0.0)
+    got, want = ref.solve(op, plan, b, pcg_ref.jacobi(g), 40, 0.0), pcg_ref.solve(op, b, pcg_ref.jacobi(g), 40, 0.0)
     assert got["k"] == want["k"]
     for key in ("rr", "rz", "pAp", "x"):
-        assert ref.same_bits(got[key], want[key]), key
+        assert pcg_ref.same_bits(got[key], want[key]), key
     g.free()
 
 
 def test_kernel_lines_are_the_apply(tmp):
-    """update_r's z and step_l1's (d, z) chained are Plan.apply; their level-1 values reduce to the tree dot"""
+    """update_r's z and step_l1's (d, z) chained are the plan's apply; their level-1 values reduce to the tree dot"""
     from oracle import pyoracle as po
-    g, op, plan = plan_of(("dims", 7, 7, 6), "scs", 64, 256, tmp, steps=3)
+    g, op, plan, ch = plan_of(("dims", 7, 7, 6), "scs", 64, 256, tmp, steps=3)
     rng = np.random.RandomState(5)
     r0, Ap = rng.standard_normal(g.nr), rng.standard_normal(g.nr)
-    r, z, l1rz, l1rr = ref.update_r(r0, Ap, plan.dinv, -0.25, plan.c["c1"])
+    r, z, l1rz, l1rr = ref.update_r(r0, Ap, plan.dinv, -0.25, ch.c["c1"])
     assert po.reduce_final(l1rr) == po.ddot_tree(r, r) and po.reduce_final(l1rz) == po.ddot_tree(r, z)
     d = z.copy()
     for j in (2, 3):
-        d, z, l1 = ref.step_l1(r, op.spmv(z), plan.dinv, d, z, plan.c["a"][j], plan.c["b"][j])
+        d, z, l1 = ref.step_l1(r, op.spmv(z), plan.dinv, d, z, ch.c["a"][j], ch.c["b"][j])
     want = plan.apply(r)
-    assert ref.same_bits(z, want[0]) and ref.same_bits(d, want[1])
+    assert pcg_ref.same_bits(z, want[0]) and pcg_ref.same_bits(d, want[1])
     assert po.reduce_final(l1) == po.ddot_tree(r, z)
     g.free()
 
 
 @pytest.mark.parametrize("name", poly_cases.SMALL)
 def test_the_committed_golden_is_what_the_restatement_gives(name, tmp, golden):
-    out = ref.run_case(poly_cases.CASES[name], tmp)
-    rec = ref.record(out)
+    out = ref.run_case(ref.POLY, poly_cases.CASES[name], tmp)
+    rec = pcg_ref.record(out)
     rec["coeffs"] = [float(v).hex() for v in out["coeffs"]]
     assert rec == golden["cases"][name]
     assert set(golden["cases"]) == set(poly_cases.CASES)

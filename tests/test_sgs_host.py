@@ -1,4 +1,4 @@
-"""The CPU restatement of SGS-preconditioned CG (tests/sgs_ref.py) pinned before the GPU is compared with it:
+"""The CPU restatement of SGS-preconditioned CG (tests/precond_ref.py) pinned before the GPU is compared with it:
 the colouring is proper and greedy-minimal, the apply is the two triangular solves of the colour-permuted matrix with D in
 between, M is symmetric, the solve is PCG under that operator (against scipy), a diagonal matrix gives Jacobi PCG bit for bit,
 the iteration count drops against Jacobi, and tests/golden/sgs_hist.json holds what the restatement gives."""
@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 
 import pcg_ref
+import precond_ref as ref
 import sgs_cases
-import sgs_ref as ref
 from conftest import load_json
 
 
@@ -22,9 +22,11 @@ def tmp(tmp_path_factory):
 
 
 def plan_of(matrix, fmt="crs", C=64, sigma=1, tmp=None):
-    g = ref.gmatrix(matrix, tmp)
-    op = ref.operator(g, fmt, C, sigma)
-    return g, op, ref.Plan(g, op)
+    """(g, operator, the one-level hierarchy, its Sweeps)"""
+    g = pcg_ref.gmatrix(matrix, tmp)
+    op = pcg_ref.operator(g, fmt, C, sigma)
+    plan = ref.sgs(g, op)
+    return g, op, plan, plan.lev[0].smoother
 
 
 COLOURED = [(("dims", 5, 5, 5), "crs", 1), (("hpcg", 16), "crs", 1), (("dims", 7, 7, 6), "scs", 256), (("irregular", 12), "crs", 1),
@@ -33,11 +35,11 @@ COLOURED = [(("dims", 5, 5, 5), "crs", 1), (("hpcg", 16), "crs", 1), (("dims", 7
 
 @pytest.mark.parametrize("matrix,fmt,sigma", COLOURED)
 def test_colouring_is_proper_and_greedy_minimal(matrix, fmt, sigma):
-    g, op, plan = plan_of(matrix, fmt, 64, sigma)
-    n, colour = plan.n, plan.colour
+    g, op, plan, sw = plan_of(matrix, fmt, 64, sigma)
+    n, colour = sw.n, sw.colour
     adj = [set() for _ in range(n)]
-    row = np.repeat(np.arange(n), np.diff(plan.kptr))
-    for i, j in zip(row.tolist(), plan.kcol.tolist()):
+    row = np.repeat(np.arange(n), np.diff(sw.kptr))
+    for i, j in zip(row.tolist(), sw.kcol.tolist()):
         adj[i].add(j), adj[j].add(i)
     for i in range(n):
         assert i not in adj[i]
@@ -45,34 +47,34 @@ def test_colouring_is_proper_and_greedy_minimal(matrix, fmt, sigma):
         assert int(colour[i]) not in around  # proper
         before = {int(colour[j]) for j in adj[i] if j < i}
         assert set(range(int(colour[i]))) <= before  # every smaller colour was taken by an earlier neighbour
-    assert plan.nC == int(colour.max()) + 1
+    assert sw.nC == int(colour.max()) + 1
     if matrix in (("dims", 5, 5, 5), ("hpcg", 16)):
-        assert plan.nC == 8
+        assert sw.nC == 8
     if matrix == ("dims", 5, 5, 5):
-        assert [len(r) for r in plan.rows] == [27, 18, 18, 12, 18, 12, 12, 8]
+        assert [len(r) for r in sw.rows] == [27, 18, 18, 12, 18, 12, 12, 8]
     g.free()
 
 
 def test_hand_made_matrices_colour_as_designed(tmp):
     for kind, nC in (("one", 1), ("diagonal", 1), ("arrow", 2), ("zeros", 2)):
-        g, op, plan = plan_of(("file", sgs_cases.hand_made(kind, tmp)))
-        assert plan.nC == nC, kind
+        g, op, plan, sw = plan_of(("file", sgs_cases.hand_made(kind, tmp)))
+        assert sw.nC == nC, kind
         if kind == "arrow":
-            assert len(plan.upper(0)[0]) == 299 and all(len(plan.lower(i)[0]) == 1 for i in range(1, 300))
+            assert len(sw.upper(0)[0]) == 299 and all(len(sw.lower(i)[0]) == 1 for i in range(1, 300))
         if kind == "zeros":
-            assert len(g.val) > len(plan.kval) + g.nr  # explicit zeros are stored and were dropped
-            assert max(len(plan.lower(i)[0]) + len(plan.upper(i)[0]) for i in range(g.nr)) == 2
+            assert len(g.val) > len(sw.kval) + g.nr  # explicit zeros are stored and were dropped
+            assert max(len(sw.lower(i)[0]) + len(sw.upper(i)[0]) for i in range(g.nr)) == 2
         g.free()
 
 
 @pytest.mark.parametrize("matrix,fmt,sigma", [(("dims", 5, 5, 5), "crs", 1), (("dims", 7, 7, 6), "scs", 256), (("irregular", 12), "scs", 256)])
 def test_vectorised_apply_is_the_entry_by_entry_apply(matrix, fmt, sigma):
-    g, op, plan = plan_of(matrix, fmt, 64, sigma)
+    g, op, plan, sw = plan_of(matrix, fmt, 64, sigma)
     dinv = op.to_dev(pcg_ref.jacobi(g))
     for special in (False, True):
         r = ref.probe_vector(g.nr, 7, special)
         z = plan.apply(r, dinv)[0]
-        want = ref.apply_scalar(plan, r, dinv)
+        want = ref.apply_scalar(sw, r, dinv)
         na = np.isnan(z)
         assert np.array_equal(na, np.isnan(want)) and np.array_equal(z.view(np.uint64)[~na], want.view(np.uint64)[~na])
         assert na.any() == special
@@ -80,7 +82,7 @@ def test_vectorised_apply_is_the_entry_by_entry_apply(matrix, fmt, sigma):
 
 
 def dev_matrix(g, op):
-    A = ref.csr(g).tocsr()
+    A = pcg_ref.csr(g).tocsr()
     if op.o2n is None:
         return A
     return A[op.n2o][:, op.n2o].tocsr()
@@ -94,9 +96,9 @@ def test_apply_is_two_triangular_solves_and_symmetric(matrix, fmt, sigma, tmp):
     pytest.importorskip("scipy")
     import scipy.sparse as sp
     import scipy.sparse.linalg as sl
-    g, op, plan = plan_of(matrix, fmt, 64, sigma, tmp)
+    g, op, plan, sw = plan_of(matrix, fmt, 64, sigma, tmp)
     A = dev_matrix(g, op)
-    perm = np.argsort(plan.colour, kind="stable")  # colour order, rows ascending within a colour
+    perm = np.argsort(sw.colour, kind="stable")  # colour order, rows ascending within a colour
     B = A[perm][:, perm].tocsr()
     d = B.diagonal()
     assert np.array_equal(d, op.to_dev(pcg_ref.diagonal(g))[perm])
@@ -118,11 +120,12 @@ def test_apply_is_two_triangular_solves_and_symmetric(matrix, fmt, sigma, tmp):
 def scipy_gap(c, tmp):
     """as test_pcg_host.scipy_gap, with M the restatement's own apply as a LinearOperator"""
     import scipy.sparse.linalg as sl
-    g, op, plan, b, dinv, eps = ref.build_case(c, tmp)
+    plan, _, op, b, dinv, eps = ref.build_case(ref.SGS, c, tmp)
+    g = plan.lev[0].g
     assert op.o2n is None
     ours = ref.solve(op, plan, b, dinv, c["itermax"], eps, keep_x=True)
     xs = ours["xs"]
-    A = ref.csr(g)
+    A = pcg_ref.csr(g)
     M = sl.LinearOperator(A.shape, matvec=lambda r: plan.apply(np.asarray(r, dtype=np.float64).ravel(), dinv)[0], dtype=np.float64)
     theirs = []
     sl.cg(A, b, x0=np.zeros(len(b)), rtol=0.0, atol=0.0, maxiter=len(xs), M=M, callback=lambda xk: theirs.append(xk.copy()))
@@ -148,8 +151,8 @@ def test_restatement_is_pcg_against_scipy(name, tmp, golden):
 
 
 def test_diagonal_matrix_is_jacobi_pcg_bit_for_bit(tmp):
-    g, op, plan = plan_of(("file", sgs_cases.hand_made("diagonal", tmp)))
-    assert plan.nC == 1
+    g, op, plan, sw = plan_of(("file", sgs_cases.hand_made("diagonal", tmp)))
+    assert sw.nC == 1
     b = np.arange(1.0, g.nr + 1.0) * (-1.0) ** np.arange(g.nr)
     dinv = pcg_ref.jacobi(g)
     got, want = ref.solve(op, plan, b, dinv, 10, 0.0), pcg_ref.solve(op, b, dinv, 10, 0.0)
@@ -164,19 +167,20 @@ def test_diagonal_matrix_is_jacobi_pcg_bit_for_bit(tmp):
 @pytest.mark.parametrize("name", list(sgs_cases.COUNT_CASES))
 def test_iteration_count_drops_against_jacobi(name, tmp, golden):
     c = sgs_cases.COUNT_CASES[name]
-    g, op, plan, b, dinv, eps = ref.build_case(c, tmp)
+    plan, _, op, b, dinv, eps = ref.build_case(ref.SGS, c, tmp)
+    g = plan.lev[0].g
     k_sgs = ref.solve(op, plan, b, dinv, c["itermax"], eps)["k"]
     k_jacobi = pcg_ref.solve(op, b, dinv, c["itermax"], eps)["k"]
     print(name, "k_jacobi", k_jacobi, "k_sgs", k_sgs)
     assert k_sgs < k_jacobi < c["itermax"]
-    assert golden["counts"][name] == dict(k_jacobi=k_jacobi, k_sgs=k_sgs, nC=plan.nC)
+    assert golden["counts"][name] == dict(k_jacobi=k_jacobi, k_sgs=k_sgs, nC=plan.lev[0].smoother.nC)
     g.free()
 
 
 @pytest.mark.parametrize("name", sgs_cases.SMALL)
 def test_the_committed_golden_is_what_the_restatement_gives(name, tmp, golden):
-    out = ref.run_case(sgs_cases.CASES[name], tmp)
-    rec = ref.record(out)
+    out = ref.run_case(ref.SGS, sgs_cases.CASES[name], tmp)
+    rec = pcg_ref.record(out)
     rec["nC"] = out["nC"]
     assert rec == golden["cases"][name]
     assert set(golden["cases"]) == set(sgs_cases.CASES)
