@@ -732,9 +732,19 @@ int sb_bicgstab_finish(sb_bicgstab* s);
 int sb_bicgstab_history(const sb_bicgstab* s, int which, double* out, int cap);
 void sb_bicgstab_solution(const sb_bicgstab* s, double* x_host);   /* original row order */
 double sb_bicgstab_check_residual(const sb_bicgstab* s);           /* max|x - xexact|, 0.0 without an exact solution */
-void sb_bicgstab_dinv(const sb_bicgstab* s, double* dinv_host);    /* the preconditioner in use, original row order */
-/* 10 for every format: p update | SpMV | rhat.v | alpha | s update | SpMV | t.s, t.t | omega | x, r update | beta */
+void sb_bicgstab_dinv(const sb_bicgstab* s, double* dinv_host);    /* the diagonal in use (a plan handle: level 0's dinv), original row order */
+/* 10 for every format: p update | SpMV | rhat.v | alpha | s update | SpMV | t.s, t.t | omega | x, r update | beta.  On a plan
+ * handle (sb_bicgstab_create_pre) with C launches per cycle: 10 + 2 C under the sweeps, 8 + 2 C under the polynomial, whose step 1
+ * on level 0 rides in the two updates */
 int sb_bicgstab_launches_per_body(const sb_bicgstab* s);
+/* BiCGStab preconditioned by the plan of a PCG handle: ph = V(0, p) and sh = V(0, s) are the V-cycle of M's plan --
+ * the sweeps, the polynomial or a cycle of either, whatever sb_pcg_create_* made.  M is BORROWED: it must outlive the handle, it
+ * must have been made over m, and it must not be between sb_pcg_start and sb_pcg_finish here or at any sb_bicgstab_start (the
+ * plan's level vectors are the cycle's scratch: handles that share M, and M's own solves, take turns); each of these, and what
+ * sb_bicgstab_create refuses, is a fatal error with file:line.  A diagonal M without a plan: its dinv is copied, the handle is a
+ * diagonal one and does not refer to M afterwards. */
+sb_bicgstab* sb_bicgstab_create_pre(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const sb_pcg* M);
+int sb_bicgstab_precond(const sb_bicgstab* s); /* 0: a diagonal; else the plan's kind as sb_pcg_precond reports it */
 double sb_bicgstab_loop_ms(const sb_bicgstab* s); /* GPU milliseconds between the end of sb_bicgstab_start and sb_bicgstab_finish */
 void sb_bicgstab_counters(const sb_bicgstab* s, int out[5]); /* stop, iters, n_rr (= n_rho), n_rv, n_ts (= n_tt) of the control block */
 /* Test entries for the fused kernels on caller-supplied device vectors of n doubles (16-byte aligned), scalars from the host;
@@ -748,6 +758,12 @@ void sb_bicgstab_update_p_native(uint32_t n, double beta, double omega, const do
                                  const double* dinv_dev, double* ph_dev);
 void sb_bicgstab_update_s_native(uint32_t n, double alpha, const double* r_dev, const double* v_dev, const double* dinv_dev,
                                  double* s_dev, double* sh_dev);
+/* the two updates of a plan handle.  cheb 0: p (s) alone, dinv_dev, d_dev, ph_dev (sh_dev) unused and may be NULL; cheb 1: also
+ * d = (p o dinv) * c1 and ph = d (the s twin: of s, into sh): level 0's first Chebyshev step */
+void sb_bicgstab_plan_update_p_native(uint32_t n, int cheb, double c1, double beta, double omega, const double* r_dev, double* p_dev,
+                                      const double* v_dev, const double* dinv_dev, double* d_dev, double* ph_dev);
+void sb_bicgstab_plan_update_s_native(uint32_t n, int cheb, double c1, double alpha, const double* r_dev, const double* v_dev,
+                                      const double* dinv_dev, double* s_dev, double* d_dev, double* sh_dev);
 void sb_bicgstab_dot2_native(uint32_t n, int pair, const double* a_dev, const double* b_dev, double* l1_ab_dev, double* l1_aa_dev);
 void sb_bicgstab_update_xr_native(uint32_t n, double alpha, double omega, double* x_dev, const double* ph_dev, const double* sh_dev,
                                   const double* s_dev, const double* t_dev, const double* rhat_dev, double* r_dev,

@@ -325,6 +325,13 @@ void sbh_gmatrix_from_csr(GMatrix* m, CG_UINT n, const uint64_t* ptr, const CG_U
 /* BiCGStab with the Jacobi right preconditioner (sb_bicgstab_*, sbhip.h) for matrices that need not be symmetric: prints what
  * solveCG prints; double precision, one rank */
 int sbh_solve_bicgstab(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz);
+/* BiCGStab with a preconditioner plan of PCG's in the diagonal's place (sb_bicgstab_create_pre, sbhip.h): precond 1
+ * sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly (galerkin != 0: on Galerkin coarse operators formed on the device); levels, steps 0: the
+ * defaults; fmt, C, sigma as sbh_solve_pcg_mg takes them (used by the V-cycles only).  The PCG handle is built as the
+ * sbh_solve_pcg_* entries build theirs and the same "Preconditioner: ..." line is printed first; the same refusals.  Double
+ * precision, one rank */
+int sbh_solve_bicgstab_precond(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+                               CG_UINT sigma, int precond, int levels, int steps, int galerkin);
 
 /* ---- the hot path: src/solver.h:11-25, src/matrix.h:57 -------------------------------- */
 #if defined(CRS) || defined(SCS)
@@ -379,6 +386,11 @@ int solvePCGMGPolyGalerkin(Comm* comm, Parameter* param, Matrix* m);
 /* Jacobi-preconditioned BiCGStab: the short-recurrence solver for matrices that are not symmetric; returns k as
  * solveCG does.  The single-precision libraries export it too and end the process with "BiCGStab: double precision only". */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m);
+/* solveBiCGStab with one of PCG's preconditioners in the diagonal's place: precond 1 sgs, 2 mg, 3 mgfw, 4 poly,
+ * 5 mgpoly, each at its defaults and built as the solvePCG* entry of that name builds it (the V-cycles: generated matrices only).
+ * Prints that entry's preconditioner line, then solveBiCGStab's lines; returns k as solveCG does.  One rank; the single-precision
+ * libraries export it too and end the process with "BiCGStab: double precision only". */
+int solveBiCGStabPrecond(Comm* comm, Parameter* param, Matrix* m, int precond);
 /* x (nc entries) and y (nr entries) may be device or host pointers; host pointers are
  * staged through HBM (correct, slow: use sb_malloc'ed vectors on the hot path) */
 void spMVM(Matrix* m, const CG_FLOAT* restrict x, CG_FLOAT* restrict y);

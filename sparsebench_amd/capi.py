@@ -64,6 +64,7 @@ SYMBOLS = [
     "sb_bicgstab_history", "sb_bicgstab_solution", "sb_bicgstab_check_residual", "sb_bicgstab_dinv", "sb_bicgstab_launches_per_body",
     "sb_bicgstab_loop_ms", "sb_bicgstab_counters", "sb_bicgstab_update_p_native", "sb_bicgstab_update_s_native",
     "sb_bicgstab_dot2_native", "sb_bicgstab_update_xr_native", "sb_bicgstab_reduce_native", "sb_bicgstab_launch",
+    "sb_bicgstab_create_pre", "sb_bicgstab_precond", "sb_bicgstab_plan_update_p_native", "sb_bicgstab_plan_update_s_native",
     "sb_matrix_resident_share", "sb_resident_share_rule",
     "sb_matrix_galerkin", "sb_csr_rows", "sb_csr_nnz", "sb_csr_copy", "sb_csr_stats", "sb_csr_free",
 ]
@@ -337,6 +338,11 @@ def load():
         "sb_bicgstab_update_xr_native": (None, [u32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "sb_bicgstab_reduce_native": (None, [u32, vp, vp, vp]),
         "sb_bicgstab_launch": (None, [u32, vp]),
+        # ... with the preconditioner plan of a borrowed sb_pcg handle
+        "sb_bicgstab_create_pre": (vp, [vp, vp, vp, vp, vp]),
+        "sb_bicgstab_precond": (C.c_int, [vp]),
+        "sb_bicgstab_plan_update_p_native": (None, [u32, C.c_int, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]),
+        "sb_bicgstab_plan_update_s_native": (None, [u32, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]),
         # Galerkin coarse operators on the device
         "sb_matrix_galerkin": (vp, [vp, u32, vp, vp, vp]),
         "sb_csr_rows": (u32, [vp]),

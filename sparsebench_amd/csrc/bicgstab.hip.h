@@ -1,4 +1,5 @@
-// bicgstab.hip.h -- kernels of right-preconditioned BiCGStab with a diagonal preconditioner.  wave64, fp64.
+// bicgstab.hip.h -- kernels of right-preconditioned BiCGStab with a diagonal preconditioner, and the two updates it
+// runs under a preconditioner plan of PCG's in the diagonal's place.  wave64, fp64.
 //
 // Every operation is rounded on its own (the TU is compiled with -ffp-contract=off): alpha * v is one multiply, r - (alpha * v)
 // one subtraction, and so on, in the order DESIGN 4.11 writes them.  Every dot is the canonical dot of kernels.hip.h (level 0
@@ -183,6 +184,77 @@ __global__ __launch_bounds__(1024) void bicg_update_s_k(uint32_t n, const double
         const double t1 = alpha * w[1];
         o[0]            = w[0] - t1;
         o[1]            = o[0] * w[2];
+      },
+      [&](uint32_t, double, double) {});
+}
+
+// The two updates under a preconditioner plan: ph = V(0, p) and sh = V(0, s) are the plan's cycle, not a product
+// with dinv.
+//   CHEB 0  the sweeps: p (s) alone; the cycle makes ph (sh) from zero.  Three (two) streams in, one out.
+//   CHEB 1  the polynomial: level 0's step 1 rides here, as it rides in poly_update_r_k for PCG: d = (p o dinv) * c1 and
+//           ph = d, poly_first_k's arithmetic.  Four (three) streams in, three out; d is level 0's cheb.d.
+// p = r + beta * (p - omega * v), the first body literally on p = v = 0, beta = omega = 0.0
+template <int CHEB>
+__global__ __launch_bounds__(1024) void bicg_plan_update_p_k(uint32_t n, const double* __restrict__ r, double* p, const double* __restrict__ v,
+    const double* __restrict__ dinv, double* __restrict__ d, double* __restrict__ ph, double c1, const BicgScalars* S)
+{
+  constexpr int NIN = CHEB ? 4 : 3, NOUT = CHEB ? 3 : 1;
+  const double* in[NIN];
+  double* out[NOUT];
+  in[0] = r, in[1] = p, in[2] = v, out[0] = p;
+  if constexpr (CHEB) in[3] = dinv, out[1] = d, out[2] = ph;
+  const double* const(&cin)[NIN] = in;
+  double* const(&cout)[NOUT]     = out;
+  double beta = 0.0, omega = 0.0;
+  bicg_stream<NIN, NOUT, 0>(
+      n, cin, cout,
+      [&] {
+        if (S->stop) return false;
+        beta = S->beta, omega = S->omega;
+        return true;
+      },
+      [&](const double(&w)[NIN], double(&o)[NOUT], double&, double&) {
+        const double t1 = omega * w[2];
+        const double t2 = w[1] - t1;
+        const double t3 = beta * t2;
+        o[0]            = w[0] + t3;
+        if constexpr (CHEB) {
+          const double u = o[0] * w[NIN - 1];
+          o[NOUT - 2]    = u * c1;
+          o[NOUT - 1]    = o[NOUT - 2];
+        }
+      },
+      [&](uint32_t, double, double) {});
+}
+
+// s = r - alpha * v, s may be r's storage (the loop's is); CHEB 1: d = (s o dinv) * c1 and sh = d
+template <int CHEB>
+__global__ __launch_bounds__(1024) void bicg_plan_update_s_k(uint32_t n, const double* r, const double* __restrict__ v,
+    const double* __restrict__ dinv, double* s, double* __restrict__ d, double* __restrict__ sh, double c1, const BicgScalars* S)
+{
+  constexpr int NIN = CHEB ? 3 : 2, NOUT = CHEB ? 3 : 1;
+  const double* in[NIN];
+  double* out[NOUT];
+  in[0] = r, in[1] = v, out[0] = s;
+  if constexpr (CHEB) in[2] = dinv, out[1] = d, out[2] = sh;
+  const double* const(&cin)[NIN] = in;
+  double* const(&cout)[NOUT]     = out;
+  double alpha = 0.0;
+  bicg_stream<NIN, NOUT, 0>(
+      n, cin, cout,
+      [&] {
+        if (S->stop) return false;
+        alpha = S->alpha;
+        return true;
+      },
+      [&](const double(&w)[NIN], double(&o)[NOUT], double&, double&) {
+        const double t1 = alpha * w[1];
+        o[0]            = w[0] - t1;
+        if constexpr (CHEB) {
+          const double u = o[0] * w[NIN - 1];
+          o[NOUT - 2]    = u * c1;
+          o[NOUT - 1]    = o[NOUT - 2];
+        }
       },
       [&](uint32_t, double, double) {});
 }

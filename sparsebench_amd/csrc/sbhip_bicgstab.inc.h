@@ -1,5 +1,6 @@
 // sbhip_bicgstab.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context):
-// right-preconditioned BiCGStab with a diagonal preconditioner (kernels: bicgstab.hip.h).  Double precision, one
+// right-preconditioned BiCGStab with a diagonal preconditioner (kernels: bicgstab.hip.h), or with the preconditioner
+// plan of a borrowed sb_pcg handle (ph = V(0, p), sh = V(0, s) by precond_cycle).  Double precision, one
 // rank, tree dot order.  The SpMV is the one the matrix's kernel mode selects (launch_spmv: the reference-layout stream or the
 // masked row programs), WITHOUT a fused dot: neither rhat.v nor t.s is x.y of its SpMV.  The loop's vectors are allocations of
 // the handle's own: the matrix's tuned arena (sb_matrix::vecArena) is laid out for sb_cg's vectors and stays with sb_cg.
@@ -19,6 +20,10 @@ struct sb_bicgstab {
   int hist_cap = 0;
   int k_next = 1;
   LoopClock clock;
+  // sb_bicgstab_create_pre: the borrowed handle and its plan (NULL: a diagonal, the handle's own dinv).  The plan's level
+  // vectors are the cycle's scratch, so every handle on M and M's own solves take turns
+  const sb_pcg* M = nullptr;
+  const PrecondPlan* pre = nullptr;
 };
 
 // grid of the four streaming kernels over n rows: vec_stream_grid
@@ -60,6 +65,45 @@ void sb_bicgstab_update_s_native(uint32_t n, double alpha, const double* r_dev, 
   test_block_done(S);
 }
 
+// cheb 0: p alone (dinv, d, ph unused, may be NULL); cheb 1: with d = (p o dinv) * c1 and ph = d
+void sb_bicgstab_plan_update_p_native(uint32_t n, int cheb, double c1, double beta, double omega, const double* r_dev, double* p_dev,
+    const double* v_dev, const double* dinv_dev, double* d_dev, double* ph_dev)
+{
+  need_init();
+  if (n == 0) return;
+  need_aligned16({ r_dev, p_dev, v_dev }, "sb_bicgstab_plan_update_p_native", "vectors");
+  if (cheb) need_aligned16({ dinv_dev, d_dev, ph_dev }, "sb_bicgstab_plan_update_p_native", "vectors");
+  if (cheb && (!dinv_dev || !d_dev || !ph_dev)) SB_FATAL("sb_bicgstab_plan_update_p_native: cheb = 1 needs dinv_dev, d_dev and ph_dev");
+  BicgScalars* S = bicg_coeffs(0.0, omega, beta);
+  const dim3 grid(vec_stream_grid(n)), block(1024);
+  if (cheb)
+    hipLaunchKernelGGL(bicg_plan_update_p_k<1>, grid, block, 0, g.stream, n, r_dev, p_dev, v_dev, dinv_dev, d_dev, ph_dev, c1,
+        (const BicgScalars*)S);
+  else
+    hipLaunchKernelGGL(bicg_plan_update_p_k<0>, grid, block, 0, g.stream, n, r_dev, p_dev, v_dev, (const double*)nullptr, (double*)nullptr,
+        (double*)nullptr, c1, (const BicgScalars*)S);
+  test_block_done(S);
+}
+
+void sb_bicgstab_plan_update_s_native(uint32_t n, int cheb, double c1, double alpha, const double* r_dev, const double* v_dev,
+    const double* dinv_dev, double* s_dev, double* d_dev, double* sh_dev)
+{
+  need_init();
+  if (n == 0) return;
+  need_aligned16({ r_dev, v_dev, s_dev }, "sb_bicgstab_plan_update_s_native", "vectors");
+  if (cheb) need_aligned16({ dinv_dev, d_dev, sh_dev }, "sb_bicgstab_plan_update_s_native", "vectors");
+  if (cheb && (!dinv_dev || !d_dev || !sh_dev)) SB_FATAL("sb_bicgstab_plan_update_s_native: cheb = 1 needs dinv_dev, d_dev and sh_dev");
+  BicgScalars* S = bicg_coeffs(alpha, 0.0, 0.0);
+  const dim3 grid(vec_stream_grid(n)), block(1024);
+  if (cheb)
+    hipLaunchKernelGGL(bicg_plan_update_s_k<1>, grid, block, 0, g.stream, n, r_dev, v_dev, dinv_dev, s_dev, d_dev, sh_dev, c1,
+        (const BicgScalars*)S);
+  else
+    hipLaunchKernelGGL(bicg_plan_update_s_k<0>, grid, block, 0, g.stream, n, r_dev, v_dev, (const double*)nullptr, s_dev, (double*)nullptr,
+        (double*)nullptr, c1, (const BicgScalars*)S);
+  test_block_done(S);
+}
+
 void sb_bicgstab_dot2_native(uint32_t n, int pair, const double* a_dev, const double* b_dev, double* l1_ab_dev, double* l1_aa_dev)
 {
   need_init();
@@ -97,6 +141,43 @@ void sb_bicgstab_reduce_native(uint32_t m, const double* l1_a_dev, const double*
   out[0] = h.rho, out[1] = h.rr;
 }
 
+// the handle and its loop vectors; dinv: the handle keeps a diagonal of its own
+static sb_bicgstab* bicg_alloc(const sb_matrix* m, bool dinv)
+{
+  sb_bicgstab* s  = new sb_bicgstab();
+  s->A = m, s->nr = m->nr, s->nc = m->nc;
+  s->nGroups      = (m->nr + 255u) >> 8;
+  double** vecs[] = { &s->r, &s->rhat, &s->p, &s->ph, &s->v, &s->sh, &s->t, &s->x, &s->b, &s->dinv };
+  for (double** vv : vecs)
+    if (dinv || vv != &s->dinv) *vv = (double*)sb_malloc((size_t)m->nc * sizeof(double) + 4096);
+  return s;
+}
+// b, the exact solution, the control block and the level-1 arrays
+static void bicg_finish_create(sb_bicgstab* s, const double* b_host, const double* xexact_host)
+{
+  const sb_matrix* m = s->A;
+  upload_permuted(m, b_host, s->b);
+  if (xexact_host) {
+    s->xexact = (double*)sb_malloc((size_t)m->nr * sizeof(double) + 4096);
+    upload_permuted(m, xexact_host, s->xexact);
+  }
+  s->S = (BicgScalars*)sb_malloc(sizeof(BicgScalars));
+  HIP_CHECK(hipMemset(s->S, 0, sizeof(BicgScalars)));
+  const size_t lb = ((size_t)s->nGroups + 4) * sizeof(double);
+  double** l1s[]  = { &s->l1a, &s->l1b };
+  for (double** vv : l1s) {
+    *vv = (double*)sb_malloc(lb);
+    HIP_CHECK(hipMemsetAsync(*vv, 0, lb, g.stream));
+  }
+  s->clock.create();
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+}
+// the borrowed handle's plan vectors are the cycle's scratch: not while its own solve has them in flight
+static void bicg_need_closed(const sb_pcg* M, const char* fn)
+{
+  if (M->clock.open) SB_FATAL("%s between sb_pcg_start and sb_pcg_finish of the borrowed PCG handle: the plan's vectors are in flight", fn);
+}
+
 sb_bicgstab* sb_bicgstab_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int precond,
     const double* dinv_host)
 {
@@ -129,11 +210,7 @@ sb_bicgstab* sb_bicgstab_create(const sb_matrix* m, sb_halo* halo, const double*
       SB_FATAL("sb_bicgstab_create: %u of %u matrix rows have no finite non-zero diagonal entry (the first: device row %u): the "
                "Jacobi preconditioner needs one in every row; pass precond 0 or a dinv_host of your own", bad, m->nr, first);
   }
-  sb_bicgstab* s  = new sb_bicgstab();
-  s->A = m, s->nr = m->nr, s->nc = m->nc;
-  s->nGroups      = (m->nr + 255u) >> 8;
-  double** vecs[] = { &s->r, &s->rhat, &s->p, &s->ph, &s->v, &s->sh, &s->t, &s->x, &s->b, &s->dinv };
-  for (double** vv : vecs) *vv = (double*)sb_malloc((size_t)m->nc * sizeof(double) + 4096);
+  sb_bicgstab* s = bicg_alloc(m, true);
   if (precond != 1) {
     if (precond == 0) hd.assign(m->nr, 1.0);
     upload_permuted(m, precond == 0 ? hd.data() : dinv_host, s->dinv);
@@ -142,23 +219,30 @@ sb_bicgstab* sb_bicgstab_create(const sb_matrix* m, sb_halo* halo, const double*
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(g.stream));
   }
-  upload_permuted(m, b_host, s->b);
-  if (xexact_host) {
-    s->xexact = (double*)sb_malloc(nb + 4096);
-    upload_permuted(m, xexact_host, s->xexact);
-  }
-  s->S = (BicgScalars*)sb_malloc(sizeof(BicgScalars));
-  HIP_CHECK(hipMemset(s->S, 0, sizeof(BicgScalars)));
-  const size_t lb = ((size_t)s->nGroups + 4) * sizeof(double);
-  double** l1s[]  = { &s->l1a, &s->l1b };
-  for (double** vv : l1s) {
-    *vv = (double*)sb_malloc(lb);
-    HIP_CHECK(hipMemsetAsync(*vv, 0, lb, g.stream));
-  }
-  s->clock.create();
-  HIP_CHECK(hipStreamSynchronize(g.stream));
+  bicg_finish_create(s, b_host, xexact_host);
   return s;
 }
+
+// M's preconditioner in the diagonal's place.  M is borrowed: it must outlive the handle, be made over the same matrix, and have
+// no solve open here or at any sb_bicgstab_start.  A diagonal M without a plan: its dinv is copied and the handle is a diagonal one
+sb_bicgstab* sb_bicgstab_create_pre(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const sb_pcg* M)
+{
+  need_init();
+  need_dp(m, "sb_bicgstab_create_pre", "BiCGStab");
+  need_one_rank(m, halo, "sb_bicgstab_create_pre", "BiCGStab");
+  need_tree("sb_bicgstab_create_pre", "BiCGStab", "sb_cg");
+  if (!M) SB_FATAL("sb_bicgstab_create_pre: no PCG handle to take the preconditioner from");
+  if (M->A != m) SB_FATAL("sb_bicgstab_create_pre: the PCG handle was made over another matrix: its preconditioner is that matrix's");
+  bicg_need_closed(M, "sb_bicgstab_create_pre");
+  sb_bicgstab* s = bicg_alloc(m, !M->pre);
+  if (M->pre) s->M = M, s->pre = M->pre;
+  else if (m->nr) sb_d2d(s->dinv, M->dinv, (size_t)m->nr * sizeof(double));
+  bicg_finish_create(s, b_host, xexact_host);
+  return s;
+}
+
+// 0: a diagonal; else the plan's kind as sb_pcg_precond reports it
+int sb_bicgstab_precond(const sb_bicgstab* s) { return s->pre ? s->pre->kind : 0; }
 
 void sb_bicgstab_free(sb_bicgstab* s)
 {
@@ -171,11 +255,13 @@ void sb_bicgstab_free(sb_bicgstab* s)
 }
 
 // launches per loop body: p update | SpMV | rhat.v | alpha | s update | SpMV | t.s, t.t | omega | x, r update | beta = 10, the
-// same for every format and kernel mode (no SpMV kernel's fused dot is used)
+// same for every format and kernel mode (no SpMV kernel's fused dot is used).  Under a plan each of the two products with dinv
+// becomes a cycle of C = precond_cycle_launches: 10 + 2 C under the sweeps; under the polynomial level 0's step 1 counts among C
+// and rides in the two updates: 8 + 2 C
 int sb_bicgstab_launches_per_body(const sb_bicgstab* s)
 {
-  (void)s;
-  return 10;
+  if (!s->pre) return 10;
+  return (s->pre->smoother == SMOOTH_CHEB ? 8 : 10) + 2 * precond_cycle_launches(s->pre);
 }
 
 template <int MODE> static void bicg_scalar_launch(sb_bicgstab* s)
@@ -185,29 +271,50 @@ template <int MODE> static void bicg_scalar_launch(sb_bicgstab* s)
   HIP_CHECK(hipGetLastError());
 }
 
-// one loop body (DESIGN 4.11)
+// p and ph = M^-1 p (SECOND 0), s (in r's storage) and sh = M^-1 s (SECOND 1): the diagonal's one kernel, or the plan's update
+// and its cycle
+template <int SECOND> static void bicg_update_and_precond(sb_bicgstab* s)
+{
+  const uint32_t n = s->nr;
+  if (!n) return;
+  const dim3 grid(vec_stream_grid(n)), block(1024);
+  const BicgScalars* S = s->S;
+  const double *r = s->r, *v = s->v;
+  double* zh = SECOND ? s->sh : s->ph;
+  const PrecondPlan* M = s->pre;
+  if (!M) {
+    if (SECOND) hipLaunchKernelGGL(bicg_update_s_k, grid, block, 0, g.stream, n, r, v, (const double*)s->dinv, s->r, zh, S);
+    else hipLaunchKernelGGL(bicg_update_p_k, grid, block, 0, g.stream, n, r, s->p, v, (const double*)s->dinv, zh, S);
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  const PrecondLevel& V = M->lev[0];
+  const bool cheb       = M->smoother == SMOOTH_CHEB;
+  const double* dinv    = V.dinv;
+  const double c1       = V.cheb.c.c1;
+  if (SECOND && cheb) hipLaunchKernelGGL(bicg_plan_update_s_k<1>, grid, block, 0, g.stream, n, r, v, dinv, s->r, V.cheb.d, zh, c1, S);
+  else if (SECOND) hipLaunchKernelGGL(bicg_plan_update_s_k<0>, grid, block, 0, g.stream, n, r, v, dinv, s->r, (double*)nullptr, (double*)nullptr, c1, S);
+  else if (cheb) hipLaunchKernelGGL(bicg_plan_update_p_k<1>, grid, block, 0, g.stream, n, r, s->p, v, dinv, V.cheb.d, zh, c1, S);
+  else hipLaunchKernelGGL(bicg_plan_update_p_k<0>, grid, block, 0, g.stream, n, r, s->p, v, dinv, (double*)nullptr, (double*)nullptr, c1, S);
+  HIP_CHECK(hipGetLastError());
+  precond_cycle(M, SECOND ? s->r : s->p, cheb ? nullptr : V.sgs->t, zh, &s->S->stop, cheb, nullptr);
+}
+
+// one loop body (DESIGN 4.11, 4.18)
 static void bicg_body(sb_bicgstab* s)
 {
   const uint32_t n = s->nr;
   const int* stop  = &s->S->stop;
   const dim3 grid(vec_stream_grid(n)), block(1024);
   const BicgScalars* S = s->S;
-  if (n) {
-    hipLaunchKernelGGL(bicg_update_p_k, grid, block, 0, g.stream, n, (const double*)s->r, s->p, (const double*)s->v, (const double*)s->dinv,
-        s->ph, S);
-    HIP_CHECK(hipGetLastError());
-  }
+  bicg_update_and_precond<0>(s);
   launch_spmv(s->A, s->ph, s->v, nullptr, stop);
   if (n) {
     hipLaunchKernelGGL(dot_l1_k, grid, block, 0, g.stream, n, (const double*)s->rhat, (const double*)s->v, s->l1a, stop);
     HIP_CHECK(hipGetLastError());
   }
   bicg_scalar_launch<1>(s);
-  if (n) {
-    hipLaunchKernelGGL(bicg_update_s_k, grid, block, 0, g.stream, n, (const double*)s->r, (const double*)s->v, (const double*)s->dinv, s->r,
-        s->sh, S);
-    HIP_CHECK(hipGetLastError());
-  }
+  bicg_update_and_precond<1>(s);
   launch_spmv(s->A, s->sh, s->t, nullptr, stop);
   if (n) {
     hipLaunchKernelGGL(bicg_dot2_k, grid, block, 0, g.stream, n, (const double*)s->t, (const double*)s->r, s->l1a, s->l1b, stop);
@@ -226,6 +333,7 @@ void sb_bicgstab_start(sb_bicgstab* s, int itermax, double eps)
 {
   need_init();
   need_tree("sb_bicgstab_start", "BiCGStab", "sb_cg");
+  if (s->M) bicg_need_closed(s->M, "sb_bicgstab_start");
   const int want = std::max(s->hist_cap, itermax + 2);
   grow(s->hist, s->hist_cap, want, 5);
   s->hist_cap   = want;
@@ -291,7 +399,7 @@ void sb_bicgstab_solution(const sb_bicgstab* s, double* x_host)
 void sb_bicgstab_dinv(const sb_bicgstab* s, double* dinv_host)
 {
   need_init();
-  download_original(s->A, s->dinv, dinv_host);
+  download_original(s->A, s->pre ? s->pre->lev[0].dinv : s->dinv, dinv_host); // a plan's: level 0's, the borrowed handle's
 }
 
 // max|x - xexact| (solverCheckResidual, src/CGSolver.c:40-60); 0.0 without an exact solution

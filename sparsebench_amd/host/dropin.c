@@ -106,6 +106,15 @@ int solvePCGMGPolyGalerkin(Comm* comm, Parameter* param, Matrix* m)
 }
 /* Jacobi-preconditioned BiCGStab on this build's Matrix (the _sp libraries: "BiCGStab: double precision only") */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_bicgstab(comm, param, m->dev, m->nr, m->rowNnz); }
+/* ... with one of PCG's preconditioners at its defaults: 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly */
+int solveBiCGStabPrecond(Comm* comm, Parameter* param, Matrix* m, int precond)
+{
+#if defined(CRS)
+  return sbh_solve_bicgstab_precond(comm, param, m->dev, m->nr, m->rowNnz, 0, 0, 0, precond, 0, 0, 0);
+#else
+  return sbh_solve_bicgstab_precond(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, precond, 0, 0, 0);
+#endif
+}
 
 void sbh_print_banner(Comm* c, const char* fmt);
 void commPrintBanner(Comm* c) { sbh_print_banner(c, FMT); } /* src/comm.c:185-250: names the build's format */

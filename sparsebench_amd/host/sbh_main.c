@@ -37,6 +37,7 @@ static const char* kHelp =
     "  -p mgpoly  The V-cycle of -p mgfw with that polynomial as the smoother of every level: no colouring.\n"
     "             Takes -l as -p mg does, and -d for the steps of each smoothing. Default 2.\n"
     "  -g         Galerkin coarse operators P^T A P, formed on the device, for -p mgpoly in the regenerated stencils' place.\n"
+    "  -P <sgs|mg|mgfw|poly|mgpoly>   One of those preconditioners for -t bicgstab in its diagonal's place, with -l, -d, -g as for -p.\n"
     "  -r <int>   GMRES restart length. Default 30.\n"
     "  -n <int>   Number of right-hand sides for -t cg. Default 1.\n"
     "  -x <int>   Size in x for generated matrix, ignored if MM file is loaded. Default 100.\n"
@@ -71,8 +72,9 @@ int main(int argc, char** argv)
   int levels  = 0;  /* -l: levels of -p mg; 0 not given (the deepest of up to 4) */
   int steps   = 0;  /* -d: steps of -p poly or -p mgpoly; 0 not given (3, 2) */
   int galerkin = 0; /* -g: the coarse operators of -p mgpoly are P^T A P */
+  int bprecond = -1; /* -P: the plan preconditioner of -t bicgstab, numbered as -p; -1 not given */
   opterr = 0;
-  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:p:l:d:g")) != -1) switch (opt) {
+  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:p:P:l:d:g")) != -1) switch (opt) {
     case 'h':
       if (commIsMaster(&comm)) printf("%s", kHelp);
       commAbort(&comm, "");
@@ -121,6 +123,17 @@ int main(int argc, char** argv)
         return 1;
       }
       break;
+    case 'P':
+      if (strcmp(optarg, "sgs") == 0) bprecond = 1;
+      else if (strcmp(optarg, "mg") == 0) bprecond = 2;
+      else if (strcmp(optarg, "mgfw") == 0) bprecond = 3;
+      else if (strcmp(optarg, "poly") == 0) bprecond = 4;
+      else if (strcmp(optarg, "mgpoly") == 0) bprecond = 5;
+      else {
+        fprintf(stderr, "Unknown preconditioner %s (-P <sgs|mg|mgfw|poly|mgpoly>)\n", optarg);
+        return 1;
+      }
+      break;
     case 'l':
       levels = atoi(optarg);
       if (levels < 1) {
@@ -150,6 +163,12 @@ int main(int argc, char** argv)
     fprintf(stderr, "-p <jacobi|sgs> (the preconditioner) goes with -t pcg only\n");
     return 1;
   }
+  if (bprecond != -1 && type != BICGSTAB) {
+    fprintf(stderr, "-P <sgs|mg|mgfw|poly|mgpoly> (the preconditioner of BiCGStab) goes with -t bicgstab only\n");
+    return 1;
+  }
+  const int bicg = bprecond != -1; /* -l, -d, -g and the grid's refusals below take -P where they take -p */
+  if (bicg) precond = bprecond;
   if (levels != 0 && precond != 2 && precond != 3 && precond != 5) {
     fprintf(stderr, "-l <int> (the levels) goes with -p mg only, or with -p mgfw or -p mgpoly\n");
     return 1;
@@ -165,7 +184,7 @@ int main(int argc, char** argv)
   if (precond == 2 || precond == 3 || precond == 5) { /* refused before the set-up: a file has no grid, a grid may not allow the levels */
     char why[256];
     if (strcmp(param.filename, "generate") != 0 && strcmp(param.filename, "generate7P") != 0) {
-      fprintf(stderr, "-p %s needs the grid: its hierarchy is the generated matrix's on coarser grids, not -m %s\n",
+      fprintf(stderr, "-%c %s needs the grid: its hierarchy is the generated matrix's on coarser grids, not -m %s\n", bicg ? 'P' : 'p',
           precond == 5 ? "mgpoly" : precond == 3 ? "mgfw" : "mg", param.filename);
       return 1;
     }
@@ -252,7 +271,14 @@ int main(int argc, char** argv)
     }
   } else if (type == BICGSTAB) {
     if (commIsMaster(&comm)) printf("Test type: BiCGStab\n");
-    k = solveBiCGStab(&comm, &param, &sm);
+    if (!bicg) k = solveBiCGStab(&comm, &param, &sm);
+    else if (levels == 0 && steps == 0 && !galerkin) k = solveBiCGStabPrecond(&comm, &param, &sm, precond); /* (prints "Preconditioner: ..." itself) */
+    else
+#ifdef SCS
+      k = sbh_solve_bicgstab_precond(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, precond, levels, steps, galerkin);
+#else
+      k = sbh_solve_bicgstab_precond(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, precond, levels, steps, galerkin);
+#endif
   } else {
     if (commIsMaster(&comm)) printf("Test type: SPMVM\n");
     /* exactly the reference's loop (src/main.c:205-215): vectors from the allocation hook, filled by host loops, spMVM under

@@ -310,54 +310,39 @@ static int run_pcg(Comm* comm, Parameter* param, sb_pcg* s, double* b, double* x
   free(rr), free(rz), free(pAp), free(b), free(xexact);
   return k;
 }
-static int solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int sgs)
+/* the coarse levels of a V-cycle handle and the arrays they were built through: released after the handle (all NULL for the
+ * one-level preconditioners) */
+typedef struct {
+  void* hierarchy;
+  int fmt, L;
+  const void** mats;
+  const CG_UINT** maps;
+  const uint64_t** gptr;
+  const CG_UINT** gcol;
+  const double** gval;
+  double* gms;
+} pcg_levels;
+static void pcg_levels_free(pcg_levels* H)
 {
-  dp_only("PCG: double precision only\n");
-  double *b, *xexact;
-  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
-  sb_pcg* s = sgs ? sb_pcg_create_sgs((const sb_matrix*)dev_matrix, NULL, b, xexact)
-                  : sb_pcg_create((const sb_matrix*)dev_matrix, NULL, b, xexact, NULL);
-  if (sgs && commIsMaster(comm)) printf("Preconditioner: SGS (multicolour symmetric Gauss-Seidel), nC = %d\n", sb_pcg_colours(s));
-  return run_pcg(comm, param, s, b, xexact);
-}
-int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
-{
-  return solve_pcg(comm, param, dev_matrix, nr, rowNnz, 0);
-}
-int sbh_solve_pcg_sgs(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
-{
-  return solve_pcg(comm, param, dev_matrix, nr, rowNnz, 1);
-}
-/* ... or with the Chebyshev polynomial in D^-1 A (DESIGN 4.15); steps 0: the default.  Names its steps and interval first */
-int sbh_solve_pcg_poly(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int steps)
-{
-  dp_only("PCG: double precision only\n");
-  double *b, *xexact;
-  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
-  sb_pcg* s = sb_pcg_create_poly((const sb_matrix*)dev_matrix, NULL, b, xexact, steps ? steps : 3, 0.0, 0.0);
-  double iv[2];
-  sb_pcg_poly_interval(s, iv);
-  if (commIsMaster(comm))
-    printf("Preconditioner: Chebyshev polynomial, steps = %d, lambda in [%.6g, %.6g]\n", sb_pcg_poly_steps(s), iv[0], iv[1]);
-  return run_pcg(comm, param, s, b, xexact);
+  if (H->hierarchy) sbh_mg_hierarchy_free(H->hierarchy, H->fmt, H->L);
+  free(H->mats), free(H->maps), free(H->gptr), free(H->gcol), free(H->gval), free(H->gms);
+  memset(H, 0, sizeof *H);
 }
 
-/* ---- solvePCGMG --------------------------------------------------------------------------- */
-/* solvePCGSGS with the multigrid V-cycle around the smoother on the generated grid's own hierarchy (sbh_mg.c).
- * levels: L, or 0 for the deepest of up to 4 the grid allows. */
 static void mg_refuse(const char* msg)
 {
   fprintf(stderr, "%s\n", msg);
   exit(EXIT_FAILURE);
 }
 
-/* fw 1: the trilinear prolongations and omega = 0.5 in the injection maps' place; fw 2: those prolongations with
- * omega = 0.25 and the Chebyshev polynomial (steps per smoothing; 0: the default 2; ratio 4) as the smoother;
- * fw 3: fw 2 on Galerkin coarse operators formed on the device, omega = 1.0 */
-static int solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
-    CG_UINT sigma, int levels, int fw, int steps)
+/* The V-cycle handles on the generated grid's own hierarchy (sbh_mg.c), with their "Preconditioner: ..." line.
+ * levels: L, or 0 for the deepest of up to 4 the grid allows.  fw 0: injection; fw 1: the trilinear prolongations and omega = 0.5
+ *  in the injection maps' place; fw 2: those prolongations with omega = 0.25 and the Chebyshev polynomial (steps per
+ * smoothing; 0: the default 2; ratio 4) as the smoother; fw 3: fw 2 on Galerkin coarse operators formed on the
+ * device, omega = 1.0 */
+static sb_pcg* build_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, const double* b, const double* xexact, int fmt, CG_UINT C,
+    CG_UINT sigma, int levels, int fw, int steps, pcg_levels* H)
 {
-  dp_only("PCG: double precision only\n");
   if (strcmp(param->filename, "generate") != 0 && strcmp(param->filename, "generate7P") != 0)
     mg_refuse("MG: needs the grid: the hierarchy is the generator's on coarser grids, and the matrix was read from a file "
               "(sb_pcg_create_mg takes a caller's own hierarchy)");
@@ -373,8 +358,8 @@ static int solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT 
   double* gms           = (double*)calloc(2 * (size_t)L, sizeof *gms);
   void* hierarchy = fw == 3 ? sbh_mg_hierarchy_build_galerkin(param, dev_matrix, fmt, C, sigma, L, mats, gptr, gcol, gval, gms)
                             : sbh_mg_hierarchy_build(param, fmt, C, sigma, L, mats, maps);
-  double *b, *xexact;
-  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
+  const pcg_levels built = { hierarchy, fmt, L, mats, maps, gptr, gcol, gval, gms };
+  *H                     = built;
   sb_pcg* s;
   if (fw == 3) {
     double* omega = (double*)calloc((size_t)L, sizeof *omega);
@@ -418,44 +403,98 @@ static int solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT 
   } else if (commIsMaster(comm))
     printf("Preconditioner: MG (V-cycle, %smulticolour SGS smoother), levels = %d, nC = %d\n", fw ? "full-weighting transfers, " : "",
         sb_pcg_levels(s), sb_pcg_colours(s));
+  return s;
+}
+
+/* The one place that makes a PCG handle for the solvers below and names its preconditioner: precond 0 Jacobi (no line: the
+ * driver prints it), 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly (galerkin: on device-formed P^T A P), as -p numbers them; levels and
+ * steps 0: the defaults.  H: what pcg_levels_free releases after the handle */
+static sb_pcg* build_pcg(Comm* comm, Parameter* param, void* dev_matrix, const double* b, const double* xexact, int fmt, CG_UINT C,
+    CG_UINT sigma, int precond, int levels, int steps, int galerkin, pcg_levels* H)
+{
+  memset(H, 0, sizeof *H);
+  const sb_matrix* m = (const sb_matrix*)dev_matrix;
+  sb_pcg* s;
+  switch (precond) {
+  case 0: return sb_pcg_create(m, NULL, b, xexact, NULL);
+  case 1:
+    s = sb_pcg_create_sgs(m, NULL, b, xexact);
+    if (commIsMaster(comm)) printf("Preconditioner: SGS (multicolour symmetric Gauss-Seidel), nC = %d\n", sb_pcg_colours(s));
+    return s;
+  case 4: {
+    s = sb_pcg_create_poly(m, NULL, b, xexact, steps ? steps : 3, 0.0, 0.0);
+    double iv[2];
+    sb_pcg_poly_interval(s, iv);
+    if (commIsMaster(comm))
+      printf("Preconditioner: Chebyshev polynomial, steps = %d, lambda in [%.6g, %.6g]\n", sb_pcg_poly_steps(s), iv[0], iv[1]);
+    return s;
+  }
+  case 2: return build_pcg_mg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, levels, 0, 0, H);
+  case 3: return build_pcg_mg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, levels, 1, 0, H);
+  case 5: return build_pcg_mg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, levels, galerkin ? 3 : 2, steps, H);
+  }
+  fprintf(stderr, "preconditioner %d: 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly\n", precond);
+  exit(EXIT_FAILURE);
+}
+
+static int solve_pcg_with(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int precond, int levels, int steps, int galerkin)
+{
+  dp_only("PCG: double precision only\n");
+  double *b, *xexact;
+  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
+  pcg_levels H;
+  sb_pcg* s   = build_pcg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, precond, levels, steps, galerkin, &H);
   const int k = run_pcg(comm, param, s, b, xexact);
-  sbh_mg_hierarchy_free(hierarchy, fmt, L);
-  free(mats), free(maps), free(gptr), free(gcol), free(gval), free(gms);
+  pcg_levels_free(&H);
   return k;
 }
+int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
+{
+  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, 0, 0, 0, 0, 0, 0, 0);
+}
+int sbh_solve_pcg_sgs(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
+{
+  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, 0, 0, 0, 1, 0, 0, 0);
+}
+/* ... or with the Chebyshev polynomial in D^-1 A (DESIGN 4.15); steps 0: the default.  Names its steps and interval first */
+int sbh_solve_pcg_poly(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int steps)
+{
+  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, 0, 0, 0, 4, 0, steps, 0);
+}
+
+/* ---- solvePCGMG --------------------------------------------------------------------------- */
+/* solvePCGSGS with the multigrid V-cycle around the smoother (build_pcg_mg) */
 int sbh_solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
     CG_UINT sigma, int levels)
 {
-  return solve_pcg_mg(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, levels, 0, 0);
+  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 2, levels, 0, 0);
 }
 int sbh_solve_pcg_mgfw(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
     CG_UINT sigma, int levels)
 {
-  return solve_pcg_mg(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, levels, 1, 0);
+  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 3, levels, 0, 0);
 }
 int sbh_solve_pcg_mgpoly(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
     CG_UINT sigma, int levels, int steps)
 {
-  return solve_pcg_mg(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, levels, 2, steps);
+  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 5, levels, steps, 0);
 }
 
 int sbh_solve_pcg_mgpoly_galerkin(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt,
     CG_UINT C, CG_UINT sigma, int levels, int steps)
 {
-  return solve_pcg_mg(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, levels, 3, steps);
+  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 5, levels, steps, 1);
 }
 
-/* ---- solveBiCGStab ----------------------------------------------------------------------- */
+/* ---- solveBiCGStab, solveBiCGStabPrecond ------------------------------------------------- */
 /* BiCGStab with the Jacobi right preconditioner (sb_bicgstab_*) for matrices that need not be symmetric.  The
  * lines solveCG prints while iterating are printed afterwards from the recorded r.r history: "Iteration = j" shows the
  * residual iteration j starts from, sqrt(rr[j - 1]), as solveCG and solvePCG do. */
-int sbh_solve_bicgstab(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
+/* solves with the handle, prints, releases it and the vectors */
+static int run_bicgstab(Comm* comm, Parameter* param, sb_bicgstab* s, double* b, double* xexact)
 {
-  dp_only("BiCGStab: double precision only\n");
   const int itermax = param->itermax, cap = itermax + 2;
-  double *b, *xexact;
-  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
-  sb_bicgstab* s = sb_bicgstab_create((const sb_matrix*)dev_matrix, NULL, b, xexact, 1, NULL);
   const int k    = sb_bicgstab_solve(s, itermax, param->eps);
   double* rr     = (double*)malloc((size_t)cap * sizeof(double));
   const int nRr  = sb_bicgstab_history(s, 0, rr, cap);
@@ -463,6 +502,30 @@ int sbh_solve_bicgstab(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT n
   print_tail(comm, k, sb_bicgstab_loop_ms(s), xexact != NULL, sb_bicgstab_check_residual(s));
   sb_bicgstab_free(s);
   free(rr), free(b), free(xexact);
+  return k;
+}
+int sbh_solve_bicgstab(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
+{
+  dp_only("BiCGStab: double precision only\n");
+  double *b, *xexact;
+  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
+  return run_bicgstab(comm, param, sb_bicgstab_create((const sb_matrix*)dev_matrix, NULL, b, xexact, 1, NULL), b, xexact);
+}
+/* ... with the preconditioner plan of a PCG handle in the diagonal's place (sb_bicgstab_create_pre): the handle is
+ * build_pcg's, as the sbh_solve_pcg_* entries make theirs, with the same "Preconditioner: ..." line */
+int sbh_solve_bicgstab_precond(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int precond, int levels, int steps, int galerkin)
+{
+  dp_only("BiCGStab: double precision only\n");
+  if (comm->size > 1) mg_refuse("BiCGStab: runs on one rank");
+  if (precond < 1 || precond > 5) mg_refuse("BiCGStab: the plan preconditioners are 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly");
+  double *b, *xexact;
+  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
+  pcg_levels H;
+  sb_pcg* M   = build_pcg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, precond, levels, steps, galerkin, &H);
+  const int k = run_bicgstab(comm, param, sb_bicgstab_create_pre((const sb_matrix*)dev_matrix, NULL, b, xexact, M), b, xexact);
+  sb_pcg_free(M);
+  pcg_levels_free(&H);
   return k;
 }
 

@@ -1051,24 +1051,64 @@ class PCG(_BodySolver):
 
 
 class BiCGStab(_BodySolver):
-    """Right-preconditioned BiCGStab with a diagonal preconditioner (sb_bicgstab_*) for matrices that need not be
-    symmetric.  precond "none": dinv = 1.0 everywhere; "jacobi": 1 / diag(A); a `dinv` of nr finite non-zero doubles in original
-    row order selects the caller's (precond is then "caller").  Double precision, one rank, tree dot order."""
+    """Right-preconditioned BiCGStab (sb_bicgstab_*) for matrices that need not be symmetric.  precond "none":
+    dinv = 1.0 everywhere; "jacobi": 1 / diag(A); a `dinv` of nr finite non-zero doubles in original row order selects the
+    caller's (precond is then "caller").  precond a `PCG` instance: that handle's preconditioner plan makes ph and sh (DESIGN
+    4.18) -- the sweeps, the polynomial or a V-cycle of either; the PCG is BORROWED: it must be over the same problem, outlive this
+    handle and have no solve open when this one is made or started (a diagonal PCG without a plan: its dinv is copied).  precond
+    "sgs", "mg", "mgfw", "poly" or "mgpoly" with PCG's own keyword arguments (levels, coarse, steps, lmax, ratio, coarse_steps,
+    galerkin): the handle builds such a PCG of its own and frees it with itself.  Neither takes a dinv.  Double precision, one
+    rank, tree dot order."""
 
     PREFIX, NAME = "sb_bicgstab", "BiCGStab"
     COUNTERS = ("stop", "iters", "n_rr", "n_rv", "n_ts")
     HISTORIES = ("rr", "rho", "rv", "ts", "tt")
+    PLANS = ("sgs", "mg", "mgfw", "poly", "mgpoly")
 
-    def __init__(self, problem, precond="none", dinv=None):
+    def __init__(self, problem, precond="none", dinv=None, **plan_args):
         self._need_double(problem)
+        self.pcg, self._owns_pcg = None, False
+        if isinstance(precond, PCG) or (isinstance(precond, str) and precond in self.PLANS):
+            if dinv is not None:
+                raise ValueError("precond=%s takes no dinv: the preconditioner is the plan's"
+                                 % ("a PCG handle" if isinstance(precond, PCG) else repr(precond)))
+            if isinstance(precond, PCG):
+                if plan_args:
+                    raise ValueError("%s go with a precond given by name: a PCG handle brings its own" % ", ".join(sorted(plan_args)))
+                if precond.ptr is None:
+                    raise ValueError("the PCG handle has been freed")
+                if precond.problem is not problem:
+                    raise ValueError("the PCG handle was made over another problem: its preconditioner is that matrix's")
+                self.pcg = precond
+            else:
+                self.pcg, self._owns_pcg = PCG(problem, precond=precond, **plan_args), True
+            b, xe = self._open(problem)
+            self._kind = None
+            self.ptr = self.L.sb_bicgstab_create_pre(problem.matrix, problem.halo, _ptr(b), _ptr(xe), self.pcg.ptr)
+            return
+        if plan_args:
+            raise TypeError("BiCGStab: %s go with precond 'sgs', 'mg', 'mgfw', 'poly' or 'mgpoly' only" % ", ".join(sorted(plan_args)))
         if dinv is not None:
             precond = "caller"
         kinds = {"none": 0, "jacobi": 1, "caller": 2}
         if precond not in kinds or (precond == "caller" and dinv is None):
             raise ValueError("precond must be 'none' or 'jacobi', or pass dinv; got %r" % (precond,))
         b, xe = self._open(problem)
+        self._kind = precond
         self.ptr = self.L.sb_bicgstab_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), kinds[precond],
                                              _ptr(self._dinv_arg(dinv)))
+
+    def precond(self):
+        """the kind's name: "none", "jacobi" or "caller" as the handle was made; under a plan "sgs", "mg", "mgfw", "poly" or
+        "mgpoly" as the library reports it ("jacobi" for a borrowed diagonal PCG, whose dinv was copied)"""
+        kind = self.L.sb_bicgstab_precond(self.ptr)
+        return self.PLANS[kind - 1] if kind else (self._kind or "jacobi")
+
+    def free(self):
+        _BodySolver.free(self)
+        if self._owns_pcg and self.pcg is not None:
+            self.pcg.free()
+        self.pcg = None
 
     def history(self):
         """dict of rr, rho (entry 0: the prologue's, then one per body) and rv, ts, tt (one per body)"""
