@@ -707,6 +707,35 @@ void sb_csr_copy(const sb_csr* c, uint64_t* ptr, uint32_t* col, double* val); /*
 void sb_csr_stats(const sb_csr* c, double out[6]);
 void sb_csr_free(sb_csr* c);
 
+/* ---- smoothed-aggregation prolongation from the matrix alone ---------------------------------------------- */
+/* A prolongation for sb_pcg_create_mg_poly and sb_matrix_galerkin made on the device from a square double-precision one-rank
+ * matrix in any format or permutation, read in place (no download), everything stated in ORIGINAL numbering, every
+ * floating-point operation rounded on its own.  d_i is sb_matrix_diagonal's.
+ *   Strong entries: a stored entry (i, j, a) with j != i, a not comparing equal to 0.0 and a*a > (theta*theta) * (fabs(d_i) *
+ *     fabs(d_j)) -- no square root, a comparison with NaN is false, theta = 0 keeps every non-zero off-diagonal entry.  The graph
+ *     is the directed one as stored.  A row without a strong entry is isolated: never a root, joins nothing, agg = -1.
+ *   Keys, uint32 arithmetic: h = fmix32((i + 1) * 0x9E3779B1), fmix32 murmur3's (h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13;
+ *     h *= 0xC2B2AE35; h ^= h >> 16); key_i = (uint64(h >> 2) << 32) | i with the state in bits 62-63: in 2, undecided 1; an out
+ *     or isolated row's whole key is 0.
+ *   Rounds, synchronous: m1_i = max(key_i, key_j over the strong j of row i); m2_i = max(m1_i, m1_j over the same j); an
+ *     undecided row with m2_i == key_i becomes in, one whose m2_i carries the state in becomes out (the states of the round's
+ *     start); until no row is undecided.  *rounds counts them up to the last one that decided a row.
+ *   Aggregates: the in rows are the roots, numbered in ascending row.  Pass 1: a row that is no root and has roots among its strong
+ *     entries joins the one with the largest row.  Pass 2: any other row that is not isolated joins the largest aggregate number
+ *     among the pass-1 aggregates of its strong entries.
+ * sb_matrix_aggregate: agg_out (nr int32, or NULL), *n_agg, *rounds; returns 0.
+ * sb_matrix_sa_prolongation: T[i, agg_i] = 1.0; W = A T by sb_matrix_galerkin's first product, unchanged; P has W's pattern
+ * (columns ascending, nothing dropped) and P[i, J] = t - (W[i, J] * dinv_i) * s with t = 1.0 for J == agg_i and +0.0 otherwise,
+ * dinv_i = 1.0 / d_i, s = omega_s / lmax in host doubles; lmax <= 0.0: the row-sum bound of sb_pcg_create_poly.  omega_s == 0.0
+ * gives T itself.  The result is read with sb_csr_copy; sb_csr_stats gives {aggregation ms, A T ms, smoothing ms, rounds, strong
+ * entries, the longest row of P}.
+ * Both end the process with a message, before any launch, for a single-precision matrix, nr != nc, a theta that is negative or
+ * not finite, and storage beyond sb_mem_free_bytes(); behind the diagonal's launch for a diagonal entry that is zero or not
+ * finite.  sb_matrix_sa_prolongation also refuses an omega_s that is negative or not finite, an lmax that is not finite, a matrix
+ * without a root (every row isolated) and what the first product refuses (a row of W above 1024 columns: never truncated). */
+int sb_matrix_aggregate(const sb_matrix* A, double theta, int32_t* agg_out, uint32_t* n_agg, uint32_t* rounds);
+sb_csr* sb_matrix_sa_prolongation(const sb_matrix* A, double theta, double omega_s, double lmax, uint32_t* n_agg);
+
 /* ---- BiCGStab with a diagonal preconditioner ----------------------------------------------------------- */
 /* Right-preconditioned BiCGStab for matrices that need not be symmetric: two SpMVs per body, about ten vectors whatever the
  * iteration count, no restart.  x0 = 0, rhat = b; the loop test is on sqrt(r.r) alone (no exit on ||s||); rho = 0, rhat.v = 0

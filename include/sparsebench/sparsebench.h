@@ -319,6 +319,24 @@ void sbh_mg_hierarchy_free(void* hierarchy, int fmt, int L);
  * (NULL: not wanted).  omega = 1.0 goes with it.  Double precision, one rank. */
 void* sbh_mg_hierarchy_build_galerkin(const Parameter* param, const void* fine_dev, int fmt, CG_UINT C, CG_UINT sigma, int L,
     const void** mats, const uint64_t** p_ptr, const CG_UINT** p_col, const double** p_val, double* stage_ms);
+/* the aggregation mode of the builder, for ANY square one-rank double-precision matrix: no grid.  Level l + 1 is
+ * P_l^T A_l P_l with P_l = sb_matrix_sa_prolongation(level l's uploaded matrix, theta, omega_s, its own row-sum bound), both formed
+ * on the device, then GMatrix -> commPartition -> convert -> upload as sbh_mg_hierarchy_build_galerkin does.  Stops at maxL levels
+ * or at the first level of at most SBH_MG_SA_COARSEST rows; *L_out is the depth reached (free with it).  mats, p_ptr, p_col, p_val
+ * as there (room for maxL entries each); rows[l] level l's rows (maxL entries), rounds[l] the rounds of level l's aggregation,
+ * ms[3 l], [3 l + 1], [3 l + 2] the device milliseconds of level l's aggregation, of A T with the smoothing, and of the Galerkin
+ * product (NULL: not wanted).  A level that coarsens by less than 2 ends the process with a message naming it; a level without a
+ * root is the library's refusal.  omega = 1.0 goes with it. */
+#define SBH_MG_SA_COARSEST 64
+#define SBH_MG_SA_DEPTH 4
+void* sbh_mg_hierarchy_build_sa(const void* fine_dev, CG_UINT fine_nr, int fmt, CG_UINT C, CG_UINT sigma, int maxL, double theta,
+    double omega_s, int* L_out, const void** mats, const uint64_t** p_ptr, const CG_UINT** p_col, const double** p_val, CG_UINT* rows,
+    CG_UINT* rounds, double* ms);
+/* sbh_solve_pcg_mgpoly on that hierarchy (theta = 0, omega_s = 4/3; levels 0: up to SBH_MG_SA_DEPTH), on generated matrices and
+ * files alike.  The preconditioner line says "smoothed-aggregation coarsening"; a second line gives every level's rows and the
+ * rounds of every aggregation, a third the set-up's device milliseconds per level */
+int sbh_solve_pcg_mgpoly_sa(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+                            CG_UINT sigma, int levels, int steps);
 /* a one-rank GMatrix of n rows from CSR in memory (64-bit row pointers): a row's entries end up in ascending column, storage order
  * kept among equal columns -- what reading the same entries from a .mtx file gives */
 void sbh_gmatrix_from_csr(GMatrix* m, CG_UINT n, const uint64_t* ptr, const CG_UINT* col, const double* val);
@@ -326,7 +344,7 @@ void sbh_gmatrix_from_csr(GMatrix* m, CG_UINT n, const uint64_t* ptr, const CG_U
  * solveCG prints; double precision, one rank */
 int sbh_solve_bicgstab(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz);
 /* BiCGStab with a preconditioner plan of PCG's in the diagonal's place (sb_bicgstab_create_pre, sbhip.h): precond 1
- * sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly (galerkin != 0: on Galerkin coarse operators formed on the device); levels, steps 0: the
+ * sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly (galerkin 1: on Galerkin coarse operators formed on the device; 2: on the aggregation hierarchy); levels, steps 0: the
  * defaults; fmt, C, sigma as sbh_solve_pcg_mg takes them (used by the V-cycles only).  The PCG handle is built as the
  * sbh_solve_pcg_* entries build theirs and the same "Preconditioner: ..." line is printed first; the same refusals.  Double
  * precision, one rank */
@@ -383,6 +401,10 @@ int solvePCGMGPoly(Comm* comm, Parameter* param, Matrix* m);
  * stencils' place; omega = 1.0.  The same matrices and refusals; the preconditioner line says "Galerkin coarse
  * operators" and a second line gives the products' device time per level. */
 int solvePCGMGPolyGalerkin(Comm* comm, Parameter* param, Matrix* m);
+/* solvePCGMGPoly on the smoothed-aggregation hierarchy made from the matrix alone: any square matrix, generated or
+ * read from a file; theta = 0, omega_s = 4/3, up to 4 levels, omega = 1.0.  The preconditioner line says "smoothed-aggregation
+ * coarsening"; two more lines give the level sizes with the rounds, and the set-up's device time per level. */
+int solvePCGMGPolySA(Comm* comm, Parameter* param, Matrix* m);
 /* Jacobi-preconditioned BiCGStab: the short-recurrence solver for matrices that are not symmetric; returns k as
  * solveCG does.  The single-precision libraries export it too and end the process with "BiCGStab: double precision only". */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m);

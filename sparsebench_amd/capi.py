@@ -67,6 +67,7 @@ SYMBOLS = [
     "sb_bicgstab_create_pre", "sb_bicgstab_precond", "sb_bicgstab_plan_update_p_native", "sb_bicgstab_plan_update_s_native",
     "sb_matrix_resident_share", "sb_resident_share_rule",
     "sb_matrix_galerkin", "sb_csr_rows", "sb_csr_nnz", "sb_csr_copy", "sb_csr_stats", "sb_csr_free",
+    "sb_matrix_aggregate", "sb_matrix_sa_prolongation",
 ]
 
 _lib = None
@@ -350,6 +351,9 @@ def load():
         "sb_csr_copy": (None, [vp, vp, vp, vp]),
         "sb_csr_stats": (None, [vp, vp]),
         "sb_csr_free": (None, [vp]),
+        # smoothed-aggregation prolongation from the matrix alone
+        "sb_matrix_aggregate": (C.c_int, [vp, C.c_double, vp, vp, vp]),
+        "sb_matrix_sa_prolongation": (vp, [vp, C.c_double, C.c_double, C.c_double, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

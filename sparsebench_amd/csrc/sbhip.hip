@@ -33,6 +33,7 @@
 #include "poly.hip.h"
 #include "mg_poly.hip.h"
 #include "galerkin.hip.h"
+#include "aggregation.hip.h"
 
 #include <algorithm>
 #include <iterator>
@@ -710,5 +711,6 @@ void sb_event_destroy(void* ev) { HIP_CHECK(hipEventDestroy((hipEvent_t)ev)); }
 #include "sbhip_mg_fw.inc.h"
 #include "sbhip_precond.inc.h"
 #include "sbhip_galerkin.inc.h"
+#include "sbhip_aggregation.inc.h"
 #include "sbhip_pcg_loop.inc.h"
 #include "sbhip_bicgstab.inc.h"

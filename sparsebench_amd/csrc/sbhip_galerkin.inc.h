@@ -25,15 +25,15 @@ struct GalOut {
 };
 void gal_free(GalOut& o) { sb_free(o.ptr), sb_free(o.col), sb_free(o.val), o = GalOut(); }
 
-void gal_need_bytes(int stage, const char* what, double bytes)
+void gal_need_bytes(const char* gal_fn, int stage, const char* what, double bytes)
 {
   const double have = (double)sb_mem_free_bytes();
   if (bytes > have)
-    SB_FATAL("sb_matrix_galerkin: stage %d: %s needs %.0f bytes of device memory, %.0f are free", stage, what, bytes, have);
+    SB_FATAL("%s: stage %d: %s needs %.0f bytes of device memory, %.0f are free", gal_fn, stage, what, bytes, have);
 }
 
-// C = X Y, stage 1 (SKIPY: a stored weight of 0.0 in Y has no term) or 2
-template <class X, bool SKIPY> GalOut gal_product(int stage, uint32_t nRows, const X& x, const GalMap& map, const GalY& y)
+// C = X Y, stage 1 (SKIPY: a stored weight of 0.0 in Y has no term) or 2; gal_fn: the entry point the messages name
+template <class X, bool SKIPY> GalOut gal_product(const char* gal_fn, int stage, uint32_t nRows, const X& x, const GalMap& map, const GalY& y)
 {
   GalOut o;
   std::vector<uint64_t> ptr((size_t)nRows + 1, 0);
@@ -41,7 +41,7 @@ template <class X, bool SKIPY> GalOut gal_product(int stage, uint32_t nRows, con
     o.ptr = sgs_to_device(ptr);
     return o;
   }
-  gal_need_bytes(stage, "the row counts and pointers", 12.0 * (double)nRows + 64.0);
+  gal_need_bytes(gal_fn, stage, "the row counts and pointers", 12.0 * (double)nRows + 64.0);
   uint32_t* count = (uint32_t*)sb_malloc((size_t)nRows * sizeof(uint32_t));
   unsigned long long* flags = (unsigned long long*)sb_malloc(16); // [0] the first row above the capacity, [1] bad columns
   const unsigned long long init[2] = { ~0ull, 0ull };
@@ -59,13 +59,13 @@ template <class X, bool SKIPY> GalOut gal_product(int stage, uint32_t nRows, con
   sb_d2h(got, flags, sizeof got);
   sb_free(count);
   if (got[1] & 1ull)
-    SB_FATAL("sb_matrix_galerkin: stage %d: an entry of the left factor has a column outside the %u rows of the right one", stage, y.nY);
+    SB_FATAL("%s: stage %d: an entry of the left factor has a column outside the %u rows of the right one", gal_fn, stage, y.nY);
   if (got[0] != ~0ull)
-    SB_FATAL("sb_matrix_galerkin: stage %d (%s): row %u has at least %u distinct columns, the capacity of a row is %u: refused, not "
-             "truncated", stage, stage == 1 ? "A P" : "P^T (A P)", (uint32_t)(got[0] >> 32), (uint32_t)(got[0] & 0xFFFFFFFFull), GAL_CAP);
+    SB_FATAL("%s: stage %d (%s): row %u has at least %u distinct columns, the capacity of a row is %u: refused, not "
+             "truncated", gal_fn, stage, stage == 1 ? "A P" : "P^T (A P)", (uint32_t)(got[0] >> 32), (uint32_t)(got[0] & 0xFFFFFFFFull), GAL_CAP);
   for (uint32_t i = 0; i < nRows; i++) ptr[i + 1] = ptr[i] + cnt[i], o.maxRow = std::max(o.maxRow, cnt[i]);
   o.nnz = ptr[nRows];
-  gal_need_bytes(stage, "the product", 12.0 * (double)o.nnz + 8.0 * (double)nRows + 64.0);
+  gal_need_bytes(gal_fn, stage, "the product", 12.0 * (double)o.nnz + 8.0 * (double)nRows + 64.0);
   o.ptr = sgs_to_device(ptr);
   o.col = (uint32_t*)sb_malloc((size_t)o.nnz * sizeof(uint32_t)), o.val = (double*)sb_malloc((size_t)o.nnz * sizeof(double));
   HIP_CHECK(hipEventRecord(ev[2], g.stream));
@@ -74,13 +74,22 @@ template <class X, bool SKIPY> GalOut gal_product(int stage, uint32_t nRows, con
   HIP_CHECK(hipEventRecord(ev[3], g.stream));
   sb_d2h(got, flags, sizeof got);
   sb_free(flags);
-  if (got[1]) SB_FATAL("sb_matrix_galerkin: stage %d: the second pass found other rows than the first (flags %llu)", stage, got[1]);
+  if (got[1]) SB_FATAL("%s: stage %d: the second pass found other rows than the first (flags %llu)", gal_fn, stage, got[1]);
   float a = 0.f, b = 0.f;
   HIP_CHECK(hipEventElapsedTime(&a, ev[0], ev[1]));
   HIP_CHECK(hipEventElapsedTime(&b, ev[2], ev[3]));
   for (hipEvent_t& e : ev) HIP_CHECK(hipEventDestroy(e));
   o.ms = (double)a + (double)b;
   return o;
+}
+
+// stage 1 alone: T = A Y with A read in place in its device order, T in the original numbering of both sides; Y has A's rows
+GalOut gal_stage1(const char* fn, const sb_matrix* A, const GalY& y)
+{
+  const bool perm   = A->fmt == 1 && A->permuted;
+  const GalMap mapA = { perm ? A->oldToNew : nullptr, perm ? A->newToOld : nullptr };
+  return A->fmt == 0 ? gal_product<GalCrs, true>(fn, 1, A->nr, GalCrs{ A->rowPtr, A->colInd, A->val }, mapA, y)
+                     : gal_product<GalSell, true>(fn, 1, A->nr, GalSell{ A->chunkPtr, A->chunkLens, A->C, A->colInd, A->val }, mapA, y);
 }
 } // namespace
 
@@ -116,7 +125,7 @@ sb_csr* sb_matrix_galerkin(const sb_matrix* A, uint32_t nCoarse, const uint64_t*
       for (uint64_t q = p_ptr[i]; q < p_ptr[i + 1]; q++)
         if (p_val[q] != 0.0) tcol[next[p_col[q]]] = i, tval[next[p_col[q]]] = p_val[q], next[p_col[q]]++;
   }
-  gal_need_bytes(1, "the prolongation and its transpose", 24.0 * (double)nnzP + 8.0 * ((double)n + (double)nCoarse) + 4096.0);
+  gal_need_bytes(fn, 1, "the prolongation and its transpose", 24.0 * (double)nnzP + 8.0 * ((double)n + (double)nCoarse) + 4096.0);
 
   // stage 1: T = A P, A in place in its device order, T in the original numbering of both sides
   uint64_t* dPptr = (uint64_t*)sb_malloc(((size_t)n + 1) * sizeof(uint64_t));
@@ -124,11 +133,8 @@ sb_csr* sb_matrix_galerkin(const sb_matrix* A, uint32_t nCoarse, const uint64_t*
   double* dPval   = (double*)sb_malloc((size_t)nnzP * sizeof(double));
   sb_h2d(dPptr, p_ptr, ((size_t)n + 1) * sizeof(uint64_t));
   if (nnzP) sb_h2d(dPcol, p_col, (size_t)nnzP * sizeof(uint32_t)), sb_h2d(dPval, p_val, (size_t)nnzP * sizeof(double));
-  const GalY yP       = { dPptr, dPcol, dPval, n };
-  const bool perm     = A->fmt == 1 && A->permuted;
-  const GalMap mapA   = { perm ? A->oldToNew : nullptr, perm ? A->newToOld : nullptr };
-  GalOut T = A->fmt == 0 ? gal_product<GalCrs, true>(1, n, GalCrs{ A->rowPtr, A->colInd, A->val }, mapA, yP)
-                         : gal_product<GalSell, true>(1, n, GalSell{ A->chunkPtr, A->chunkLens, A->C, A->colInd, A->val }, mapA, yP);
+  const GalY yP = { dPptr, dPcol, dPval, n };
+  GalOut T      = gal_stage1(fn, A, yP);
   sb_free(dPptr), sb_free(dPcol), sb_free(dPval);
 
   // stage 2: A_c = P^T T
@@ -136,7 +142,7 @@ sb_csr* sb_matrix_galerkin(const sb_matrix* A, uint32_t nCoarse, const uint64_t*
   uint32_t* dTcol = sgs_to_device(tcol);
   double* dTval   = sgs_to_device(tval);
   const GalY yT   = { T.ptr, T.col, T.val, n };
-  GalOut R        = gal_product<GalCsr64, false>(2, nCoarse, GalCsr64{ dTptr, dTcol, dTval }, GalMap{ nullptr, nullptr }, yT);
+  GalOut R        = gal_product<GalCsr64, false>(fn, 2, nCoarse, GalCsr64{ dTptr, dTcol, dTval }, GalMap{ nullptr, nullptr }, yT);
   sb_free(dTptr), sb_free(dTcol), sb_free(dTval);
 
   // download; an entry whose sum compares equal to 0.0 is dropped (NaN is kept)

@@ -104,6 +104,15 @@ int solvePCGMGPolyGalerkin(Comm* comm, Parameter* param, Matrix* m)
   return sbh_solve_pcg_mgpoly_galerkin(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, 0, 0);
 #endif
 }
+/* solvePCGMGPoly on the smoothed-aggregation hierarchy made from the matrix alone */
+int solvePCGMGPolySA(Comm* comm, Parameter* param, Matrix* m)
+{
+#if defined(CRS)
+  return sbh_solve_pcg_mgpoly_sa(comm, param, m->dev, m->nr, m->rowNnz, 0, 0, 0, 0, 0);
+#else
+  return sbh_solve_pcg_mgpoly_sa(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, 0, 0);
+#endif
+}
 /* Jacobi-preconditioned BiCGStab on this build's Matrix (the _sp libraries: "BiCGStab: double precision only") */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_bicgstab(comm, param, m->dev, m->nr, m->rowNnz); }
 /* ... with one of PCG's preconditioners at its defaults: 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly */

@@ -37,7 +37,9 @@ static const char* kHelp =
     "  -p mgpoly  The V-cycle of -p mgfw with that polynomial as the smoother of every level: no colouring.\n"
     "             Takes -l as -p mg does, and -d for the steps of each smoothing. Default 2.\n"
     "  -g         Galerkin coarse operators P^T A P, formed on the device, for -p mgpoly in the regenerated stencils' place.\n"
-    "  -P <sgs|mg|mgfw|poly|mgpoly>   One of those preconditioners for -t bicgstab in its diagonal's place, with -l, -d, -g as for -p.\n"
+    "  -a         Smoothed-aggregation coarsening for -p mgpoly, made on the device from the matrix alone: any matrix (-m file,\n"
+    "             -m irregular, generated). Forms its own Galerkin products (not with -g). Takes -l (default up to 4) and -d.\n"
+    "  -P <sgs|mg|mgfw|poly|mgpoly>   One of those preconditioners for -t bicgstab in its diagonal's place, with -l, -d, -g, -a as for -p.\n"
     "  -r <int>   GMRES restart length. Default 30.\n"
     "  -n <int>   Number of right-hand sides for -t cg. Default 1.\n"
     "  -x <int>   Size in x for generated matrix, ignored if MM file is loaded. Default 100.\n"
@@ -72,9 +74,10 @@ int main(int argc, char** argv)
   int levels  = 0;  /* -l: levels of -p mg; 0 not given (the deepest of up to 4) */
   int steps   = 0;  /* -d: steps of -p poly or -p mgpoly; 0 not given (3, 2) */
   int galerkin = 0; /* -g: the coarse operators of -p mgpoly are P^T A P */
+  int aggregation = 0; /* -a: the hierarchy of -p mgpoly is made from the matrix alone by smoothed aggregation */
   int bprecond = -1; /* -P: the plan preconditioner of -t bicgstab, numbered as -p; -1 not given */
   opterr = 0;
-  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:p:P:l:d:g")) != -1) switch (opt) {
+  while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:p:P:l:ad:g")) != -1) switch (opt) {
     case 'h':
       if (commIsMaster(&comm)) printf("%s", kHelp);
       commAbort(&comm, "");
@@ -142,6 +145,7 @@ int main(int argc, char** argv)
       }
       break;
     case 'g': galerkin = 1; break;
+    case 'a': aggregation = 1; break;
     case 'd':
       steps = atoi(optarg);
       if (steps < 1 || steps > 16) {
@@ -181,7 +185,16 @@ int main(int argc, char** argv)
     fprintf(stderr, "-g (Galerkin coarse operators) goes with -p mgpoly only\n");
     return 1;
   }
-  if (precond == 2 || precond == 3 || precond == 5) { /* refused before the set-up: a file has no grid, a grid may not allow the levels */
+  if (aggregation && precond != 5) {
+    fprintf(stderr, "-a (smoothed-aggregation coarsening) goes with -p mgpoly only\n");
+    return 1;
+  }
+  if (aggregation && galerkin) {
+    fprintf(stderr, "-a (smoothed-aggregation coarsening) forms its own Galerkin products P^T A P on the device: it does not go with -g, "
+                    "which is the trilinear hierarchy's\n");
+    return 1;
+  }
+  if ((precond == 2 || precond == 3 || precond == 5) && !aggregation) { /* refused before the set-up: a file has no grid, a grid may not allow the levels */
     char why[256];
     if (strcmp(param.filename, "generate") != 0 && strcmp(param.filename, "generate7P") != 0) {
       fprintf(stderr, "-%c %s needs the grid: its hierarchy is the generated matrix's on coarser grids, not -m %s\n", bicg ? 'P' : 'p',
@@ -247,6 +260,14 @@ int main(int argc, char** argv)
 #else
       k = sbh_solve_pcg_mgfw(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels);
 #endif
+    } else if (precond == 5 && aggregation && levels == 0 && steps == 0) {
+      k = solvePCGMGPolySA(&comm, &param, &sm); /* (prints "Preconditioner: MG (V-cycle, ..., smoothed-aggregation coarsening), ..." itself) */
+    } else if (precond == 5 && aggregation) {
+#ifdef SCS
+      k = sbh_solve_pcg_mgpoly_sa(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, levels, steps);
+#else
+      k = sbh_solve_pcg_mgpoly_sa(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels, steps);
+#endif
     } else if (precond == 5 && galerkin && levels == 0 && steps == 0) {
       k = solvePCGMGPolyGalerkin(&comm, &param, &sm); /* (prints "Preconditioner: MG (V-cycle, ..., Galerkin coarse operators), ..." itself) */
     } else if (precond == 5 && galerkin) {
@@ -272,12 +293,12 @@ int main(int argc, char** argv)
   } else if (type == BICGSTAB) {
     if (commIsMaster(&comm)) printf("Test type: BiCGStab\n");
     if (!bicg) k = solveBiCGStab(&comm, &param, &sm);
-    else if (levels == 0 && steps == 0 && !galerkin) k = solveBiCGStabPrecond(&comm, &param, &sm, precond); /* (prints "Preconditioner: ..." itself) */
+    else if (levels == 0 && steps == 0 && !galerkin && !aggregation) k = solveBiCGStabPrecond(&comm, &param, &sm, precond); /* (prints "Preconditioner: ..." itself) */
     else
 #ifdef SCS
-      k = sbh_solve_bicgstab_precond(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, precond, levels, steps, galerkin);
+      k = sbh_solve_bicgstab_precond(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, precond, levels, steps, aggregation ? 2 : galerkin);
 #else
-      k = sbh_solve_bicgstab_precond(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, precond, levels, steps, galerkin);
+      k = sbh_solve_bicgstab_precond(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, precond, levels, steps, aggregation ? 2 : galerkin);
 #endif
   } else {
     if (commIsMaster(&comm)) printf("Test type: SPMVM\n");

@@ -227,6 +227,68 @@ void* sbh_mg_hierarchy_build_galerkin(const Parameter* param, const void* fine_d
 #endif
 }
 
+/* the coarse levels by smoothed aggregation from the matrix alone (sparsebench.h) */
+void* sbh_mg_hierarchy_build_sa(const void* fine_dev, CG_UINT fine_nr, int fmt, CG_UINT C, CG_UINT sigma, int maxL, double theta,
+    double omega_s, int* L_out, const void** mats, const uint64_t** p_ptr, const CG_UINT** p_col, const double** p_val, CG_UINT* rows,
+    CG_UINT* rounds, double* ms)
+{
+#if PRECISION == 1
+  (void)fine_dev, (void)fine_nr, (void)fmt, (void)C, (void)sigma, (void)maxL, (void)theta, (void)omega_s, (void)L_out, (void)mats;
+  (void)p_ptr, (void)p_col, (void)p_val, (void)rows, (void)rounds, (void)ms;
+  fprintf(stderr, "MG: the aggregation hierarchy is double precision only\n");
+  exit(EXIT_FAILURE);
+#else
+  mg_level* lev    = (mg_level*)calloc((size_t)maxL + 1, sizeof *lev);
+  const void* fine = fine_dev;
+  CG_UINT n        = fine_nr;
+  int L            = 1;
+  rows[0]          = n;
+  for (int l = 1; l < maxL && n > SBH_MG_SA_COARSEST; l++, L++) {
+    mg_level* v  = &lev[l];
+    uint32_t nc  = 0;
+    sb_csr* p    = sb_matrix_sa_prolongation((const sb_matrix*)fine, theta, omega_s, 0.0, &nc);
+    double st[6];
+    sb_csr_stats(p, st);
+    if (2 * (uint64_t)nc > (uint64_t)n) {
+      fprintf(stderr, "MG: aggregation: level %d: %u aggregates of %u rows: the level coarsens by less than 2 (theta = %g)\n", l - 1, nc, n,
+          theta);
+      exit(EXIT_FAILURE);
+    }
+    const uint64_t pnnz = sb_csr_nnz(p);
+    v->pptr = (uint64_t*)malloc(((size_t)n + 1) * sizeof(uint64_t)), v->pcol = (CG_UINT*)malloc((pnnz + 1) * sizeof(CG_UINT));
+    v->pval = (double*)malloc((pnnz + 1) * sizeof(double));
+    sb_csr_copy(p, v->pptr, v->pcol, v->pval), sb_csr_free(p);
+    sb_csr* ac         = sb_matrix_galerkin((const sb_matrix*)fine, nc, v->pptr, v->pcol, v->pval);
+    const uint64_t nnz = sb_csr_nnz(ac);
+    uint64_t* ptr      = (uint64_t*)malloc(((size_t)nc + 1) * sizeof(uint64_t));
+    CG_UINT* col       = (CG_UINT*)malloc((nnz + 1) * sizeof(CG_UINT));
+    double* val        = (double*)malloc((nnz + 1) * sizeof(double));
+    double gst[6];
+    sb_csr_copy(ac, ptr, col, val), sb_csr_stats(ac, gst), sb_csr_free(ac);
+    if (ms) ms[3 * (l - 1)] = st[0], ms[3 * (l - 1) + 1] = st[1] + st[2], ms[3 * (l - 1) + 2] = gst[0] + gst[1];
+    rounds[l - 1] = (CG_UINT)st[3], rows[l] = nc;
+    sbh_gmatrix_from_csr(&v->gm, nc, ptr, col, val);
+    free(ptr), free(col), free(val);
+    Comm cc;
+    memset(&cc, 0, sizeof cc);
+    cc.size = 1;
+    commPartition(&cc, &v->gm);
+    if (fmt == 0) {
+      sbh_convert_crs(&v->crs, &v->gm);
+      v->dev = v->crs.dev;
+    } else {
+      v->scs.C = C, v->scs.sigma = sigma;
+      sbh_convert_scs(&v->scs, &v->gm);
+      v->dev = v->scs.dev;
+    }
+    mats[l - 1] = v->dev, p_ptr[l - 1] = v->pptr, p_col[l - 1] = v->pcol, p_val[l - 1] = v->pval;
+    fine = v->dev, n = nc;
+  }
+  *L_out = L;
+  return lev;
+#endif
+}
+
 void sbh_mg_hierarchy_free(void* hierarchy, int fmt, int L)
 {
   mg_level* lev = (mg_level*)hierarchy;

@@ -406,8 +406,50 @@ static sb_pcg* build_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, cons
   return s;
 }
 
+/* The Chebyshev-smoothed V-cycle on the smoothed-aggregation hierarchy made from the matrix alone: any square
+ * matrix, theta = 0, omega_s = 4/3, omega = 1.0; levels 0: up to SBH_MG_SA_DEPTH */
+static sb_pcg* build_pcg_sa(Comm* comm, void* dev_matrix, CG_UINT nr, const double* b, const double* xexact, int fmt, CG_UINT C,
+    CG_UINT sigma, int levels, int steps, pcg_levels* H)
+{
+  if (comm->size > 1) mg_refuse("MG: runs on one rank");
+  const int maxL        = levels ? levels : SBH_MG_SA_DEPTH;
+  const void** mats     = (const void**)calloc((size_t)maxL, sizeof *mats);
+  const uint64_t** gptr = (const uint64_t**)calloc((size_t)maxL, sizeof *gptr);
+  const CG_UINT** gcol  = (const CG_UINT**)calloc((size_t)maxL, sizeof *gcol);
+  const double** gval   = (const double**)calloc((size_t)maxL, sizeof *gval);
+  double* gms           = (double*)calloc(3 * (size_t)maxL, sizeof *gms);
+  CG_UINT* rows         = (CG_UINT*)calloc((size_t)maxL, sizeof *rows);
+  CG_UINT* rounds       = (CG_UINT*)calloc((size_t)maxL, sizeof *rounds);
+  int L                 = 1;
+  void* hierarchy = sbh_mg_hierarchy_build_sa(dev_matrix, nr, fmt, C, sigma, maxL, 0.0, 4.0 / 3.0, &L, mats, gptr, gcol, gval, rows, rounds, gms);
+  const pcg_levels built = { hierarchy, fmt, L, mats, NULL, gptr, gcol, gval, gms };
+  *H                     = built;
+  double* omega          = (double*)calloc((size_t)L, sizeof *omega);
+  for (int l = 0; l + 1 < L; l++) omega[l] = 1.0;
+  sb_pcg* s = sb_pcg_create_mg_poly((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats,
+      (const uint64_t* const*)gptr, (const uint32_t* const*)gcol, (const double* const*)gval, omega, steps ? steps : 2, 0, 0.0, 0.0);
+  free(omega);
+  if (commIsMaster(comm)) {
+    double iv[2];
+    sb_pcg_mg_poly_interval(s, 0, iv);
+    printf("Preconditioner: MG (V-cycle, full-weighting transfers, Chebyshev polynomial smoother, smoothed-aggregation coarsening), "
+           "levels = %d, steps = %d, lambda in [%.6g, %.6g]\n", sb_pcg_levels(s), sb_pcg_poly_steps(s), iv[0], iv[1]);
+    printf("Aggregation on the device, rows:");
+    for (int l = 0; l < L; l++) printf(" %u", rows[l]);
+    printf("; rounds:");
+    for (int l = 0; l + 1 < L; l++) printf(" %u", rounds[l]);
+    printf("\n");
+    printf("Aggregation set-up on the device, ms (aggregates + A T and smoothing + P^T A P):");
+    for (int l = 0; l + 1 < L; l++)
+      printf(" level %d: %.3f + %.3f + %.3f%s", l, gms[3 * l], gms[3 * l + 1], gms[3 * l + 2], l + 2 < L ? "," : "");
+    printf("\n");
+  }
+  free(rows), free(rounds);
+  return s;
+}
+
 /* The one place that makes a PCG handle for the solvers below and names its preconditioner: precond 0 Jacobi (no line: the
- * driver prints it), 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly (galerkin: on device-formed P^T A P), as -p numbers them; levels and
+ * driver prints it), 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly (galerkin 1: on device-formed P^T A P; 2: on the aggregation hierarchy), as -p numbers them; levels and
  * steps 0: the defaults.  H: what pcg_levels_free releases after the handle */
 static sb_pcg* build_pcg(Comm* comm, Parameter* param, void* dev_matrix, const double* b, const double* xexact, int fmt, CG_UINT C,
     CG_UINT sigma, int precond, int levels, int steps, int galerkin, pcg_levels* H)
@@ -431,7 +473,9 @@ static sb_pcg* build_pcg(Comm* comm, Parameter* param, void* dev_matrix, const d
   }
   case 2: return build_pcg_mg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, levels, 0, 0, H);
   case 3: return build_pcg_mg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, levels, 1, 0, H);
-  case 5: return build_pcg_mg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, levels, galerkin ? 3 : 2, steps, H);
+  case 5:
+    if (galerkin == 2) return build_pcg_sa(comm, dev_matrix, sb_matrix_nr(m), b, xexact, fmt, C, sigma, levels, steps, H);
+    return build_pcg_mg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, levels, galerkin ? 3 : 2, steps, H);
   }
   fprintf(stderr, "preconditioner %d: 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly\n", precond);
   exit(EXIT_FAILURE);
@@ -485,6 +529,12 @@ int sbh_solve_pcg_mgpoly_galerkin(Comm* comm, Parameter* param, void* dev_matrix
     CG_UINT C, CG_UINT sigma, int levels, int steps)
 {
   return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 5, levels, steps, 1);
+}
+
+int sbh_solve_pcg_mgpoly_sa(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int levels, int steps)
+{
+  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 5, levels, steps, 2);
 }
 
 /* ---- solveBiCGStab, solveBiCGStabPrecond ------------------------------------------------- */

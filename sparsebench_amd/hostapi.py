@@ -259,6 +259,97 @@ def _mg_galerkin_device(problem, levels, _owned):
     return out
 
 
+def _need_device_matrix(problem, who):
+    if getattr(problem, "precision", "double") != "double":
+        raise ValueError("%s: double precision only (the problem was built with precision=%r)" % (who, problem.precision))
+    if problem.nr != problem.totalNr:
+        raise ValueError("%s runs on one rank" % who)
+    if not problem.upload:
+        raise ValueError("%s reads the uploaded matrix: the problem was built with upload=False" % who)
+
+
+def _theta(theta, who):
+    if isinstance(theta, bool) or not isinstance(theta, (int, float, np.integer, np.floating)) or not 0.0 <= float(theta) < math.inf:
+        raise ValueError("%s: theta must be finite and not negative, got %r" % (who, theta))
+    return float(theta)
+
+
+def _omega_s(omega_s, who):
+    if isinstance(omega_s, bool) or not isinstance(omega_s, (int, float, np.integer, np.floating)) or not 0.0 <= float(omega_s) < math.inf:
+        raise ValueError("%s: omega_s must be finite and not negative, got %r" % (who, omega_s))
+    return float(omega_s)
+
+
+def aggregate(problem, theta=0.0):
+    """the aggregates of an uploaded double-precision one-rank problem, made on the device from the matrix alone
+    (sb_matrix_aggregate): (agg int32 per row in original numbering, -1 for a row without a strong entry; the number
+    of aggregates; the rounds the independent set took)"""
+    _need_device_matrix(problem, "aggregate")
+    theta = _theta(theta, "aggregate")
+    agg, n_agg, rounds = np.empty(problem.nr, dtype=np.int32), C.c_uint32(0), C.c_uint32(0)
+    capi.load().sb_matrix_aggregate(problem.matrix, theta, agg.ctypes.data_as(vp), C.byref(n_agg), C.byref(rounds))
+    return agg, int(n_agg.value), int(rounds.value)
+
+
+def sa_prolongation(problem, theta=0.0, omega_s=4.0 / 3.0, lmax=None, stats=False):
+    """the smoothed-aggregation prolongation P = T - (omega_s / lmax) D^-1 A T of such a problem (sb_matrix_sa_prolongation, DESIGN
+    4.19): ((ptr uint64, col uint32, val float64) of nr x n_agg in original numbering, columns ascending; n_agg).  lmax None: the
+    row-sum bound of D^-1/2 A D^-1/2; omega_s = 0: the tentative 0/1 prolongator.  stats=True adds the dict of device times and
+    counts"""
+    _need_device_matrix(problem, "sa_prolongation")
+    theta, omega_s = _theta(theta, "sa_prolongation"), _omega_s(omega_s, "sa_prolongation")
+    if lmax is not None and not (0.0 < float(lmax) < math.inf):
+        raise ValueError("lmax must be finite and positive (None: the row-sum bound), got %r" % (lmax,))
+    L = capi.load()
+    n_agg = C.c_uint32(0)
+    h = L.sb_matrix_sa_prolongation(problem.matrix, theta, omega_s, 0.0 if lmax is None else float(lmax), C.byref(n_agg))
+    try:
+        n, nnz = L.sb_csr_rows(h), L.sb_csr_nnz(h)
+        out = (np.empty(n + 1, dtype=np.uint64), np.empty(nnz, dtype=np.uint32), np.empty(nnz, dtype=np.float64))
+        st = np.zeros(6)
+        L.sb_csr_copy(h, *[a.ctypes.data_as(vp) for a in out])
+        L.sb_csr_stats(h, st.ctypes.data_as(vp))
+    finally:
+        L.sb_csr_free(h)
+    if stats:
+        return out, int(n_agg.value), {"aggregate_ms": float(st[0]), "product_ms": float(st[1]), "smooth_ms": float(st[2]),
+                                       "rounds": int(st[3]), "strong_entries": int(st[4]), "max_row_p": int(st[5])}
+    return out, int(n_agg.value)
+
+
+MG_AGGREGATION_DEPTH = 4    # levels at most, the fine one included
+MG_AGGREGATION_COARSEST = 64  # a level of at most this many rows is the last
+
+
+def mg_aggregation(problem, levels=None, theta=0.0, omega_s=4.0 / 3.0, _owned=None):
+    """the smoothed-aggregation hierarchy of ANY uploaded double-precision one-rank problem for PCG(precond="mgpoly", coarse=...):
+    [(Problem, P, 1.0), ...] with P_l = sa_prolongation(level l) and A_{l+1} = P_l^T A_l P_l formed on the device
+    (galerkin_product), opened with Problem.from_csr in the fine problem's format, C and sigma.  Stops at `levels`
+    levels (None: 4) or at the first level of at most 64 rows.  A level that coarsens by less than 2 is refused by name (a level
+    without a root by the library).  Each Problem carries `aggregation_stats` (the level above's rounds and times) and
+    `galerkin_stats`; the caller frees the problems (PCG(coarsening="aggregation") does with the handle)."""
+    _need_device_matrix(problem, "mg_aggregation")
+    if levels is not None and (isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or levels < 1):
+        raise ValueError("MG: levels must be 1 or more, got %r" % (levels,))
+    theta, omega_s = _theta(theta, "mg_aggregation"), _omega_s(omega_s, "mg_aggregation")
+    depth = MG_AGGREGATION_DEPTH if levels is None else int(levels)
+    out, fine = [], problem
+    while len(out) + 1 < depth and fine.nr > MG_AGGREGATION_COARSEST:
+        l = len(out)
+        P, n_agg, st = sa_prolongation(fine, theta, omega_s, stats=True)
+        if 2 * n_agg > fine.nr:
+            raise ValueError("mg_aggregation: level %d: %d aggregates of %d rows: the level coarsens by less than 2 (theta = %r)"
+                             % (l, n_agg, fine.nr, theta))
+        (ptr, col, val), gst = _galerkin_product(fine, P, n_agg)
+        q = Problem.from_csr(ptr, col, val, fmt=problem.fmt, Cc=problem.Cc, sigma=problem.sigma_arg)
+        q.aggregation_stats, q.galerkin_stats = st, gst
+        if _owned is not None:
+            _owned.append(q)
+        out.append((q, P, 1.0))
+        fine = q
+    return out
+
+
 def _omega(omega, l):
     if not (isinstance(omega, (int, float)) and np.isfinite(omega) and omega > 0.0):
         raise ValueError("omega of level %d must be finite and positive, got %r" % (l, omega))
@@ -782,15 +873,25 @@ class PCG(_BodySolver):
     transfers: `steps` per smoothing (default 2), `coarse_steps` on the last level (default: steps), ratio default
     4.0, lmax None: every level's own bound; `levels` for the generated hierarchy with the trilinear P and omega = 0.25,
     `galerkin=True` for mg_galerkin's coarse operators in the regenerated ones' place (`galerkin="device"`: the same operators formed on
-    the device, DESIGN 4.17: no scipy, no files), or `coarse` as "mgfw" takes it.  Double
+    the device, DESIGN 4.17: no scipy, no files), or `coarse` as "mgfw" takes it; `coarsening="aggregation"` (with `theta`, `omega_s`
+    and `levels`) for mg_aggregation's hierarchy made from the matrix alone, on any problem.  Double
     precision, one rank, tree dot order."""
 
     PREFIX, NAME = "sb_pcg", "PCG"
     COUNTERS = ("stop", "stop_next", "iters", "n_rr", "n_pAp")
 
     def __init__(self, problem, dinv=None, precond="jacobi", levels=None, coarse=None, steps=None, lmax=None, ratio=None,
-                 coarse_steps=None, galerkin=False):
+                 coarse_steps=None, galerkin=False, coarsening="geometric", theta=None, omega_s=None):
         self._need_double(problem)
+        if coarsening not in ("geometric", "aggregation"):
+            raise ValueError("coarsening must be 'geometric' or 'aggregation', got %r" % (coarsening,))
+        if coarsening == "aggregation":
+            if precond != "mgpoly":
+                raise ValueError("coarsening='aggregation' goes with precond='mgpoly' only")
+            if galerkin or coarse is not None:
+                raise ValueError("coarsening='aggregation' builds the hierarchy itself: it takes levels, not coarse or galerkin")
+        elif theta is not None or omega_s is not None:
+            raise ValueError("theta and omega_s go with coarsening='aggregation' only")
         if precond not in ("jacobi", "sgs", "mg", "mgfw", "poly", "mgpoly"):
             raise ValueError("precond must be 'jacobi' or 'sgs' or 'mg' or 'mgfw' or 'poly' or 'mgpoly', got %r" % (precond,))
         if precond not in ("poly", "mgpoly") and (steps is not None or lmax is not None or ratio is not None):
@@ -820,7 +921,11 @@ class PCG(_BodySolver):
         self._keep = None
         if precond in ("mg", "mgfw", "mgpoly"):
             try:
-                if galerkin:
+                if coarsening == "aggregation":
+                    found = mg_aggregation(problem, levels, 0.0 if theta is None else theta, 4.0 / 3.0 if omega_s is None else omega_s,
+                                           _owned=self._owned)
+                    self._create_mg_p(problem, found, "mgpoly", poly)
+                elif galerkin:
                     self._create_galerkin(problem, levels, poly, device=isinstance(galerkin, str))
                 else:
                     self._create_mg(problem, levels, coarse, precond != "mg", precond, poly)
@@ -1057,7 +1162,7 @@ class BiCGStab(_BodySolver):
     4.18) -- the sweeps, the polynomial or a V-cycle of either; the PCG is BORROWED: it must be over the same problem, outlive this
     handle and have no solve open when this one is made or started (a diagonal PCG without a plan: its dinv is copied).  precond
     "sgs", "mg", "mgfw", "poly" or "mgpoly" with PCG's own keyword arguments (levels, coarse, steps, lmax, ratio, coarse_steps,
-    galerkin): the handle builds such a PCG of its own and frees it with itself.  Neither takes a dinv.  Double precision, one
+    galerkin, coarsening, theta, omega_s): the handle builds such a PCG of its own and frees it with itself.  Neither takes a dinv.  Double precision, one
     rank, tree dot order."""
 
     PREFIX, NAME = "sb_bicgstab", "BiCGStab"
