@@ -802,6 +802,46 @@ void sb_bicgstab_reduce_native(uint32_t m, const double* l1_a_dev, const double*
  * wave owns whole 256-row groups and strides over them by the number of waves in the grid */
 void sb_bicgstab_launch(uint32_t n, uint32_t out[3]);
 
+/* ---- right-preconditioned GMRES(m) ------------------------------------------------------------------------ */
+/* GMRES(m) on A M^-1 by a change of variable: the loop of sb_gmres_create runs unchanged on u, with w = A (M^-1 V[j]) in the
+ * step and r = b - A xs, xs = M^-1 u, in the prologue and at every cycle close; sb_gmres_solution and sb_gmres_check_residual
+ * give xs (the xs of the last close; 0 when no step was taken).  rr_hist is the explicit r.r of b - A xs.  M^-1 is the
+ * preconditioner of the PCG handle M: its plan's V(0, .) -- the sweeps, the polynomial or a cycle of either, bit for bit
+ * what sb_pcg_apply_precond gives -- or, for a handle without a plan, its diagonal.  A cycle of j steps costs j + 1 applies.
+ * M is BORROWED, by sb_bicgstab_create_pre's rule: it must outlive the handle, it must have been made over m, and it must not
+ * be between sb_pcg_start and sb_pcg_finish here or at any sb_gmres_start (the plan's level vectors are the cycle's scratch:
+ * handles that share M -- GMRES and BiCGStab alike -- and M's own solves take turns); each of these, and what sb_gmres_create
+ * refuses, is a fatal error with file:line.  A diagonal M without a plan: its dinv is copied (entries of either sign) and the
+ * handle does not refer to M afterwards.  Tree dot order only.
+ * sb_gmres_set_fused(s, 1) (default): the kernel that makes V[0], V[j+1] or x also writes the diagonal's product or level 0's
+ * first Chebyshev step; 0: the op list, with M^-1 made wholly by the plan's own apply.  Same bits in both.
+ * sb_gmres_launches_per_step: 7 + A, + 1 at j = 0, + 5 + A at j = restart - 1, with A the launches of an apply beyond what
+ * rides: the cycle's under the sweeps, one fewer under the polynomial, 0 for a diagonal.  Handles that share M take turns
+ * between sb_gmres_run_steps calls as well as between solves: under the polynomial the first step of a call that resumes inside
+ * a cycle (j > 0) makes level 0's first step again from V[j] (one launch more than the count, the same bits), because the plan's
+ * vectors may have served another handle since the step that made V[j]. */
+sb_gmres* sb_gmres_create_pre(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int restart,
+                              const sb_pcg* M);
+/* the caller's diagonal in M^-1's place: dinv_host holds nr finite NON-ZERO doubles of either sign in original row order (a
+ * PCG handle takes positive entries only); everything else as sb_gmres_create_pre with a plan-less handle */
+sb_gmres* sb_gmres_create_dinv(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int restart,
+                               const double* dinv_host);
+int sb_gmres_precond(const sb_gmres* s); /* -1: none (sb_gmres_create); 0: a diagonal; else the plan's kind as sb_pcg_precond reports it */
+void sb_gmres_dinv(const sb_gmres* s, double* dinv_host); /* the diagonal in use (a plan: level 0's dinv), original row order */
+/* Test entries for the three riding kernels on caller-supplied device vectors (16-byte aligned); blocking.  mode -1: the
+ * unfused twin (dinv_dev, d_dev, z_dev unused); 0: z = out o dinv; 1: d = z = (out o dinv) * c1.
+ * scale: out = a / *scalar_dev, *g0_dev = *scalar_dev.  multiupdate: w += c[i] * V[i], ascending i, as sb_multiaxpy_sub lays V
+ * out.  step: the step-and-normalise kernel at cycle position j on a throw-away state whose earlier rotations are zero:
+ * hcol_host the j + 1 entries of H's column, gj = g[j], l1_dev the (n + 255) / 256 level-1 values of w . w, vnext = w / hn;
+ * out_host: H's column (j + 1), cs[j], sn[j], g[j], g[j+1], the estimate, hn. */
+void sb_gmres_pre_scale_native(uint32_t n, int mode, double c1, const double* a_dev, const double* scalar_dev, double* out_dev,
+                               double* g0_dev, const double* dinv_dev, double* d_dev, double* z_dev);
+void sb_gmres_pre_multiupdate_native(uint32_t n, int mode, double c1, int nvec, const double* V_dev, size_t ldv, const double* c_dev,
+                                     double* w_dev, const double* dinv_dev, double* d_dev, double* z_dev);
+void sb_gmres_pre_step_native(uint32_t n, int mode, double c1, int j, const double* hcol_host, double gj, const double* l1_dev,
+                              const double* w_dev, double* vnext_dev, const double* dinv_dev, double* d_dev, double* z_dev,
+                              double* out_host);
+
 /* debug/measurement: raw streaming-read rate of the device in GB/s (DESIGN.md uses it
  * as the measured ceiling next to the 8 TB/s spec) */
 double sb_debug_stream_read_gbs(size_t bytes, int reps);

@@ -352,6 +352,13 @@ int sbh_solve_bicgstab_precond(Comm* comm, Parameter* param, void* dev_matrix, C
                                CG_UINT sigma, int precond, int levels, int steps, int galerkin);
 
 /* ---- the hot path: src/solver.h:11-25, src/matrix.h:57 -------------------------------- */
+/* GMRES(restart) right-preconditioned by one of PCG's preconditioners (sb_gmres_create_pre, sbhip.h): GMRES on
+ * A M^-1, the solution x = M^-1 u.  precond 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly (galerkin 1: on Galerkin coarse
+ * operators formed on the device; 2: on the aggregation hierarchy); levels, steps 0: the defaults; fmt, C, sigma as
+ * sbh_solve_pcg_mg takes them (used by the V-cycles only).  The PCG handle is built as the sbh_solve_pcg_* entries build theirs
+ * and freed after the solver; the same "Preconditioner: ..." line is printed first; the same refusals.  Double precision, one rank */
+int sbh_solve_gmres_precond(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int restart, int precond, int levels, int steps, int galerkin);
 #if defined(CRS) || defined(SCS)
 void convertMatrix(Matrix* m, GMatrix* im);
 int solveCG(Comm* comm, Parameter* param, Matrix* m);
@@ -413,6 +420,11 @@ int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m);
  * Prints that entry's preconditioner line, then solveBiCGStab's lines; returns k as solveCG does.  One rank; the single-precision
  * libraries export it too and end the process with "BiCGStab: double precision only". */
 int solveBiCGStabPrecond(Comm* comm, Parameter* param, Matrix* m, int precond);
+/* solveGMRES right-preconditioned by one of PCG's preconditioners: precond 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly,
+ * 5 mgpoly, each at its defaults and built as the solvePCG* entry of that name builds it (the V-cycles: generated matrices only).
+ * Prints that entry's preconditioner line, then solveGMRES's lines; returns k as solveCG does.  One rank; the single-precision
+ * libraries export it too and end the process with "GMRES: double precision only". */
+int solveGMRESPrecond(Comm* comm, Parameter* param, Matrix* m, int restart, int precond);
 /* x (nc entries) and y (nr entries) may be device or host pointers; host pointers are
  * staged through HBM (correct, slow: use sb_malloc'ed vectors on the hot path) */
 void spMVM(Matrix* m, const CG_FLOAT* restrict x, CG_FLOAT* restrict y);

@@ -68,6 +68,8 @@ SYMBOLS = [
     "sb_matrix_resident_share", "sb_resident_share_rule",
     "sb_matrix_galerkin", "sb_csr_rows", "sb_csr_nnz", "sb_csr_copy", "sb_csr_stats", "sb_csr_free",
     "sb_matrix_aggregate", "sb_matrix_sa_prolongation",
+    "sb_gmres_create_pre", "sb_gmres_create_dinv", "sb_gmres_precond", "sb_gmres_dinv", "sb_gmres_pre_scale_native", "sb_gmres_pre_multiupdate_native",
+    "sb_gmres_pre_step_native",
 ]
 
 _lib = None
@@ -341,6 +343,13 @@ def load():
         "sb_bicgstab_launch": (None, [u32, vp]),
         # ... with the preconditioner plan of a borrowed sb_pcg handle
         "sb_bicgstab_create_pre": (vp, [vp, vp, vp, vp, vp]),
+        "sb_gmres_create_pre": (vp, [vp, vp, vp, vp, C.c_int, vp]),
+        "sb_gmres_create_dinv": (vp, [vp, vp, vp, vp, C.c_int, vp]),
+        "sb_gmres_precond": (C.c_int, [vp]),
+        "sb_gmres_dinv": (None, [vp, vp]),
+        "sb_gmres_pre_scale_native": (None, [u32, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp]),
+        "sb_gmres_pre_multiupdate_native": (None, [u32, C.c_int, C.c_double, C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp]),
+        "sb_gmres_pre_step_native": (None, [u32, C.c_int, C.c_double, C.c_int, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp]),
         "sb_bicgstab_precond": (C.c_int, [vp]),
         "sb_bicgstab_plan_update_p_native": (None, [u32, C.c_int, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]),
         "sb_bicgstab_plan_update_s_native": (None, [u32, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]),

@@ -294,6 +294,108 @@ __global__ __launch_bounds__(64) void gm_backsolve_k(GmView gv, int nvec, const 
   }
 }
 
+// =============================================================================
+// Right-preconditioned GMRES: the three kernels that PRODUCE a vector the preconditioner is applied to next also
+// write the first part of M^-1 of it, as bicg_plan_update_p_k<1> does for BiCGStab and poly_update_r_k for PCG.
+//   MODE 0  a diagonal:              z = v o dinv                       (all of M^-1; d is not touched)
+//   MODE 1  a Chebyshev-smoothed plan: d = z = (v o dinv) * c1          (poly_first_k's arithmetic; d is level 0's cheb.d, and
+//                                                                        precond_cycle then runs with firstDone = true)
+// Each is the twin of the kernel it stands in for, statement for statement plus those lines, to be changed with it: V, x, H, g
+// and the estimate are the twin's bits.  The twins themselves are not templated on this (their code objects stay as they are).
+// =============================================================================
+template <int MODE> __device__ __forceinline__ double gm_pre_first(double v, double di, double c1)
+{
+  const double t = v * di;
+  return MODE ? t * c1 : t;
+}
+
+// gm_scale_k's twin: out = a / (*d0), g0, and the first part of M^-1 out
+template <int MODE>
+__global__ __launch_bounds__(256) void gm_pre_scale_k(uint32_t n, const double* __restrict__ a, const double* __restrict__ d0,
+    double* __restrict__ out, double* __restrict__ g0, const double* __restrict__ dinv, double* __restrict__ d, double* __restrict__ z,
+    double c1, const int* __restrict__ stop)
+{
+  if (stop && *stop) return;
+  const double dv       = *d0;
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
+    const double v = a[e] / dv;
+    out[e]         = v;
+    const double f = gm_pre_first<MODE>(v, dinv[e], c1);
+    if (MODE) d[e] = f;
+    z[e] = f;
+  }
+  if (g0 && blockIdx.x == 0 && threadIdx.x == 0) *g0 = dv;
+}
+
+// gm_step_k<true>'s twin: the scalar step, V[j+1] = w / hn, and the first part of M^-1 V[j+1]
+template <int MODE>
+__global__ __launch_bounds__(1024) void gm_pre_step_k(uint32_t n, uint32_t nGroups, const double* __restrict__ q, int l1, GmView gv, int j,
+    const double* __restrict__ w, double* __restrict__ vnext, const double* __restrict__ dinv, double* __restrict__ d,
+    double* __restrict__ z, double c1)
+{
+  __shared__ double lds16[16];
+  const bool recorder = blockIdx.x == 0 && threadIdx.x == 0;
+  GmScalars in;
+  if (recorder) in = *gv.S;
+  const int stopped = gv.S->stop;
+  const double ww   = reduce_final_1024(nGroups, q, lds16, l1);
+  if (stopped) return;
+  const double hn = sqrt(ww);
+  if (recorder) gm_scalar_step(gv, in, j, hn);
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
+    const double v = w[e] / hn;
+    vnext[e]       = v;
+    const double f = gm_pre_first<MODE>(v, dinv[e], c1);
+    if (MODE) d[e] = f;
+    z[e] = f;
+  }
+}
+
+// gm_multiupdate_k<true, 0>'s twin (the x update of a cycle close): w += c[i] * V[i], ascending i, and the first part of M^-1 w
+template <int MODE>
+__global__ __launch_bounds__(256) void gm_pre_multiupdate_k(uint32_t n, int nvec, const double* __restrict__ V, size_t ldv,
+    const double* __restrict__ c, double* w, const double* __restrict__ dinv, double* __restrict__ d, double* __restrict__ z, double c1,
+    const int* __restrict__ stop)
+{
+  const uint32_t lane    = threadIdx.x & 63u;
+  const uint32_t nGroups = (n + 255u) >> 8;
+  const uint32_t nWaves  = gridDim.x * (blockDim.x >> 6);
+  if (stop && *stop) return;
+  for (uint32_t gI = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); gI < nGroups; gI += nWaves) {
+    const uint32_t e0 = gI * 256u + lane * 2u, e1 = e0 + 128u;
+    double2 w0 = gm_load2(w, e0, n), w1 = gm_load2(w, e1, n);
+    const double2 i0 = gm_load2(dinv, e0, n), i1 = gm_load2(dinv, e1, n);
+    auto apply = [&](double ci, const double2& a, const double2& b) {
+      w0.x = w0.x + ci * a.x, w0.y = w0.y + ci * a.y;
+      w1.x = w1.x + ci * b.x, w1.y = w1.y + ci * b.y;
+    };
+    int i = 0;
+    for (; i + MD_UNROLL <= nvec; i += MD_UNROLL) {
+      double2 a[MD_UNROLL], b[MD_UNROLL];
+      double ci[MD_UNROLL];
+#pragma unroll
+      for (int u = 0; u < MD_UNROLL; u++) {
+        const double* v = V + (size_t)(i + u) * ldv;
+        a[u] = gm_load2(v, e0, n), b[u] = gm_load2(v, e1, n), ci[u] = c[i + u];
+      }
+#pragma unroll
+      for (int u = 0; u < MD_UNROLL; u++) apply(ci[u], a[u], b[u]);
+    }
+    for (; i < nvec; i++) {
+      const double* v = V + (size_t)i * ldv;
+      apply(c[i], gm_load2(v, e0, n), gm_load2(v, e1, n));
+    }
+    gm_store2(w, e0, n, w0), gm_store2(w, e1, n, w1);
+    double2 f0, f1;
+    f0.x = gm_pre_first<MODE>(w0.x, i0.x, c1), f0.y = gm_pre_first<MODE>(w0.y, i0.y, c1);
+    f1.x = gm_pre_first<MODE>(w1.x, i1.x, c1), f1.y = gm_pre_first<MODE>(w1.y, i1.y, c1);
+    if (MODE) gm_store2(d, e0, n, f0), gm_store2(d, e1, n, f1);
+    gm_store2(z, e0, n, f0), gm_store2(z, e1, n, f1);
+  }
+}
+
 // test entry (sb_debug_sqrt_div): the device's sqrt and / on caller-supplied operands
 __global__ __launch_bounds__(256) void gm_sqrt_div_k(uint32_t n, const double* __restrict__ a, const double* __restrict__ b,
     double* __restrict__ sq, double* __restrict__ dv)

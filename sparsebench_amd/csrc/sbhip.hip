@@ -714,3 +714,4 @@ void sb_event_destroy(void* ev) { HIP_CHECK(hipEventDestroy((hipEvent_t)ev)); }
 #include "sbhip_aggregation.inc.h"
 #include "sbhip_pcg_loop.inc.h"
 #include "sbhip_bicgstab.inc.h"
+#include "sbhip_gmres_precond.inc.h"

@@ -1,0 +1,201 @@
+// sbhip_gmres_precond.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context):
+// right-preconditioned GMRES(m).  The loop is sbhip_gmres.inc.h's, run on A M^-1 by a change of variable: the
+// handle's x is u, xs = M^-1 u is the solution, and zh = M^-1 V[j] is what the step's SpMV reads.  M^-1 is a diagonal (the
+// handle's own copy of a plan-less sb_pcg handle's dinv) or precond_cycle on the plan of a borrowed sb_pcg handle: V(0, .), bit
+// for bit what sb_pcg_apply_precond and BiCGStab get.  Included behind the plan's files and sbhip_bicgstab.inc.h, whose
+// borrowed-handle rule this one repeats.  Double precision, one rank, tree dot order.
+// ===========================================================================
+// GMRES on A M^-1
+// ===========================================================================
+static int gm_pre_rides(const sb_gmres* s) { return !s->plan ? 1 : s->plan->smoother == SMOOTH_CHEB ? 2 : 0; }
+
+static GmPreFirst gm_pre_operands(const sb_gmres* s)
+{
+  if (!s->plan) return GmPreFirst{ s->dinv, nullptr, 0.0 };
+  const PrecondLevel& V = s->plan->lev[0];
+  return GmPreFirst{ V.dinv, V.cheb.d, V.cheb.c.c1 };
+}
+
+// launches of an apply beyond what rides in the fused loop: none for a diagonal, the cycle less level 0's step 1 under the
+// polynomial, the whole cycle under the sweeps
+static int gm_pre_apply_launches(const sb_gmres* s)
+{
+  if (!s->plan) return 0;
+  return precond_cycle_launches(s->plan) - (s->plan->smoother == SMOOTH_CHEB ? 1 : 0);
+}
+
+// dst = M^-1 src.  rode: the kernel that made src has written the diagonal's product or level 0's step 1 (the fused loop);
+// otherwise everything is made here by what the plan's own apply runs (the op list, and the sweeps always)
+static void gm_pre_apply(sb_gmres* s, const double* src, double* dst, const int* stop, bool rode)
+{
+  if (!s->n) return;
+  const PrecondPlan* M = s->plan;
+  if (!M) {
+    if (rode) return;
+    hipLaunchKernelGGL(precond_diag_k, dim3(stream_grid(s->n, 256)), dim3(256), 0, g.stream, s->n, src, (const double*)s->dinv, dst);
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  if (!stop) stop = zero_flag(); // (sb_gmres_finish's close: the plan's kernels read their flag unconditionally)
+  const bool cheb = M->smoother == SMOOTH_CHEB;
+  precond_cycle(M, src, cheb ? nullptr : M->lev[0].sgs->t, dst, stop, cheb && rode, nullptr);
+}
+
+static void gm_pre_need_start(const sb_gmres* s)
+{
+  need_tree("sb_gmres_start", "preconditioned GMRES", "sb_cg");
+  if (s->M) bicg_need_closed(s->M, "sb_gmres_start");
+}
+
+// M's preconditioner on the right of A.  M is borrowed: it must outlive the handle, be made over the same matrix, and have no
+// solve open here or at any sb_gmres_start.  A diagonal M without a plan: its dinv is copied and M is not referred to afterwards
+sb_gmres* sb_gmres_create_pre(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int restart,
+    const sb_pcg* M)
+{
+  need_init();
+  need_dp(m, "sb_gmres_create_pre", "GMRES");
+  need_tree("sb_gmres_create_pre", "preconditioned GMRES", "sb_cg");
+  if (!M) SB_FATAL("sb_gmres_create_pre: no PCG handle to take the preconditioner from");
+  if (M->A != m) SB_FATAL("sb_gmres_create_pre: the PCG handle was made over another matrix: its preconditioner is that matrix's");
+  bicg_need_closed(M, "sb_gmres_create_pre");
+  (void)halo;
+  sb_gmres* s     = gm_create(m, b_host, xexact_host, restart, "sb_gmres_create_pre");
+  const size_t vb = s->ldv * sizeof(double) + 4096;
+  s->pre = 1;
+  s->zh = (double*)sb_malloc(vb), s->xs = (double*)sb_malloc(vb);
+  HIP_CHECK(hipMemsetAsync(s->zh, 0, vb, g.stream));
+  HIP_CHECK(hipMemsetAsync(s->xs, 0, vb, g.stream));
+  if (M->pre) s->M = M, s->plan = M->pre;
+  else {
+    s->dinv = (double*)sb_malloc(vb);
+    if (m->nr) sb_d2d(s->dinv, M->dinv, (size_t)m->nr * sizeof(double));
+  }
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  return s;
+}
+
+// the caller's diagonal on the right of A: nr finite non-zero doubles of either sign in original row order (a PCG handle takes
+// positive ones only, so this diagonal has an entry point of its own)
+sb_gmres* sb_gmres_create_dinv(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int restart,
+    const double* dinv_host)
+{
+  need_init();
+  need_dp(m, "sb_gmres_create_dinv", "GMRES");
+  need_tree("sb_gmres_create_dinv", "preconditioned GMRES", "sb_cg");
+  if (!dinv_host) SB_FATAL("sb_gmres_create_dinv: no dinv_host");
+  for (uint32_t i = 0; i < m->nr; i++)
+    if (!(dinv_host[i] != 0.0 && fabs(dinv_host[i]) < INFINITY))
+      SB_FATAL("sb_gmres_create_dinv: dinv[%u] = %g: the preconditioner's entries must be finite and non-zero", i, dinv_host[i]);
+  (void)halo;
+  sb_gmres* s     = gm_create(m, b_host, xexact_host, restart, "sb_gmres_create_dinv");
+  const size_t vb = s->ldv * sizeof(double) + 4096;
+  s->pre = 1;
+  double** vecs[] = { &s->zh, &s->xs, &s->dinv };
+  for (double** v : vecs) {
+    *v = (double*)sb_malloc(vb);
+    HIP_CHECK(hipMemsetAsync(*v, 0, vb, g.stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  upload_permuted(m, dinv_host, s->dinv);
+  return s;
+}
+
+// -1: no preconditioner (sb_gmres_create); 0: a diagonal; else the plan's kind as sb_pcg_precond reports it
+int sb_gmres_precond(const sb_gmres* s) { return !s->pre ? -1 : s->plan ? s->plan->kind : 0; }
+
+void sb_gmres_dinv(const sb_gmres* s, double* dinv_host)
+{
+  need_init();
+  if (!s->pre) SB_FATAL("sb_gmres_dinv: the handle has no preconditioner (sb_gmres_create)");
+  download_original(s->A, s->plan ? s->plan->lev[0].dinv : s->dinv, dinv_host); // a plan's: level 0's, the borrowed handle's
+}
+
+// --- the three riding kernels on a caller's vectors (blocking; tests) -------------------------------------------------------
+// mode -1: the unfused twin (dinv, d, z unused); 0: z = out o dinv; 1: d = z = (out o dinv) * c1
+static void gm_pre_native_args(int mode, const double* dinv, const double* d, const double* z, const char* fn)
+{
+  if (mode < -1 || mode > 1) SB_FATAL("%s: mode = %d (-1: the twin, 0: a diagonal, 1: Chebyshev)", fn, mode);
+  if (mode >= 0 && (!dinv || !z || (mode == 1 && !d))) SB_FATAL("%s: mode %d needs dinv_dev, z_dev%s", fn, mode, mode ? " and d_dev" : "");
+}
+
+// out = a / *scalar_dev, *g0_dev = *scalar_dev
+void sb_gmres_pre_scale_native(uint32_t n, int mode, double c1, const double* a_dev, const double* scalar_dev, double* out_dev,
+    double* g0_dev, const double* dinv_dev, double* d_dev, double* z_dev)
+{
+  need_init();
+  gm_pre_native_args(mode, dinv_dev, d_dev, z_dev, "sb_gmres_pre_scale_native");
+  if (n == 0) return;
+  const dim3 grid(stream_grid(n, 256)), block(256);
+  const int* stop = nullptr;
+  if (mode == 1) hipLaunchKernelGGL(gm_pre_scale_k<1>, grid, block, 0, g.stream, n, a_dev, scalar_dev, out_dev, g0_dev, dinv_dev, d_dev, z_dev, c1, stop);
+  else if (mode == 0) hipLaunchKernelGGL(gm_pre_scale_k<0>, grid, block, 0, g.stream, n, a_dev, scalar_dev, out_dev, g0_dev, dinv_dev, d_dev, z_dev, c1, stop);
+  else hipLaunchKernelGGL(gm_scale_k, grid, block, 0, g.stream, n, a_dev, scalar_dev, out_dev, g0_dev, stop);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+}
+
+// w += c[i] * V[i], ascending i (the x update of a close)
+void sb_gmres_pre_multiupdate_native(uint32_t n, int mode, double c1, int nvec, const double* V_dev, size_t ldv, const double* c_dev,
+    double* w_dev, const double* dinv_dev, double* d_dev, double* z_dev)
+{
+  need_init();
+  gm_pre_native_args(mode, dinv_dev, d_dev, z_dev, "sb_gmres_pre_multiupdate_native");
+  if (nvec < 1 || ldv < n) SB_FATAL("sb_gmres_pre_multiupdate_native: nvec = %d, ldv = %zu, n = %u", nvec, ldv, n);
+  gm_need_vectors(V_dev, w_dev, ldv, "sb_gmres_pre_multiupdate_native");
+  if (mode >= 0) need_aligned16({ dinv_dev, d_dev, z_dev }, "sb_gmres_pre_multiupdate_native", "vectors");
+  if (n == 0) return;
+  const dim3 grid = gm_group_grid((n + 255u) >> 8), block(256);
+  const int* stop = nullptr;
+  if (mode == 1) hipLaunchKernelGGL(gm_pre_multiupdate_k<1>, grid, block, 0, g.stream, n, nvec, V_dev, ldv, c_dev, w_dev, dinv_dev, d_dev, z_dev, c1, stop);
+  else if (mode == 0) hipLaunchKernelGGL(gm_pre_multiupdate_k<0>, grid, block, 0, g.stream, n, nvec, V_dev, ldv, c_dev, w_dev, dinv_dev, d_dev, z_dev, c1, stop);
+  else hipLaunchKernelGGL((gm_multiupdate_k<true, 0>), grid, block, 0, g.stream, n, nvec, V_dev, ldv, c_dev, w_dev, (double*)nullptr, stop);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+}
+
+// The step-and-normalise kernel at cycle position j on a throw-away state of restart length j + 1 whose rotations are zero:
+// hcol_host holds the j + 1 entries of H's column before the rotations, gj is g[j], l1_dev the level-1 values of w . w over
+// the (n + 255) / 256 groups.  vnext = w / hn.  out_host takes H's column (j + 1 entries), then cs[j], sn[j], g[j], g[j+1],
+// the estimate and hn
+void sb_gmres_pre_step_native(uint32_t n, int mode, double c1, int j, const double* hcol_host, double gj, const double* l1_dev,
+    const double* w_dev, double* vnext_dev, const double* dinv_dev, double* d_dev, double* z_dev, double* out_host)
+{
+  need_init();
+  gm_pre_native_args(mode, dinv_dev, d_dev, z_dev, "sb_gmres_pre_step_native");
+  if (j < 0 || j > 1023) SB_FATAL("sb_gmres_pre_step_native: cycle position %d outside 0 .. 1023", j);
+  const size_t M = (size_t)j + 1, head = (sizeof(GmScalars) + 15u) & ~(size_t)15u;
+  const size_t doubles = M * (M + 1) + 3 * M + 2 * (M + 1);
+  std::vector<char> h(head + doubles * sizeof(double), 0);
+  GmScalars* S = reinterpret_cast<GmScalars*>(h.data());
+  S->itermax = 1 << 30, S->k = 1; // (hist_cap = 0: nothing is recorded)
+  double* d = reinterpret_cast<double*>(h.data() + head);
+  char* dev = (char*)sb_malloc(h.size());
+  double* dd = reinterpret_cast<double*>(dev + head);
+  GmView gv;
+  memset(&gv, 0, sizeof gv);
+  gv.S = reinterpret_cast<GmScalars*>(dev), gv.m = (int)M;
+  size_t o = 0;
+  gv.H = dd + o, o += M * (M + 1);
+  gv.cs = dd + o, o += M;
+  gv.sn = dd + o, o += M;
+  gv.y = dd + o, o += M;
+  gv.g = dd + o, d[o + j] = gj, o += M + 1;
+  gv.hcol = dd + o;
+  for (size_t i = 0; i < M; i++) d[o + i] = hcol_host[i];
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  HIP_CHECK(hipMemcpy(dev, h.data(), h.size(), hipMemcpyHostToDevice));
+  const uint32_t nG = (n + 255u) >> 8;
+  const dim3 grid(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount, (n + 4095u) / 4096u))), block(1024);
+  if (mode == 1) hipLaunchKernelGGL(gm_pre_step_k<1>, grid, block, 0, g.stream, n, nG, l1_dev, 1, gv, j, w_dev, vnext_dev, dinv_dev, d_dev, z_dev, c1);
+  else if (mode == 0) hipLaunchKernelGGL(gm_pre_step_k<0>, grid, block, 0, g.stream, n, nG, l1_dev, 1, gv, j, w_dev, vnext_dev, dinv_dev, d_dev, z_dev, c1);
+  else hipLaunchKernelGGL((gm_step_k<true>), grid, block, 0, g.stream, n, nG, l1_dev, 1, gv, j, w_dev, vnext_dev);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(g.stream));
+  HIP_CHECK(hipMemcpy(h.data(), dev, h.size(), hipMemcpyDeviceToHost));
+  sb_free(dev);
+  const double* Hj = d + (size_t)j * (M + 1);
+  for (size_t i = 0; i < M; i++) out_host[i] = Hj[i];
+  const double* gg = d + M * (M + 1) + 3 * M;
+  out_host[M] = d[M * (M + 1) + j], out_host[M + 1] = d[M * (M + 1) + M + j];
+  out_host[M + 2] = gg[j], out_host[M + 3] = gg[j + 1], out_host[M + 4] = S->normr, out_host[M + 5] = S->hn;
+}

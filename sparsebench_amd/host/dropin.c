@@ -124,6 +124,16 @@ int solveBiCGStabPrecond(Comm* comm, Parameter* param, Matrix* m, int precond)
   return sbh_solve_bicgstab_precond(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, precond, 0, 0, 0);
 #endif
 }
+/* restarted GMRES right-preconditioned by one of PCG's preconditioners at its defaults: 0 jacobi, 1 sgs, 2 mg,
+ * 3 mgfw, 4 poly, 5 mgpoly (the _sp libraries: "GMRES: double precision only") */
+int solveGMRESPrecond(Comm* comm, Parameter* param, Matrix* m, int restart, int precond)
+{
+#if defined(CRS)
+  return sbh_solve_gmres_precond(comm, param, m->dev, m->nr, m->rowNnz, 0, 0, 0, restart, precond, 0, 0, 0);
+#else
+  return sbh_solve_gmres_precond(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, restart, precond, 0, 0, 0);
+#endif
+}
 
 void sbh_print_banner(Comm* c, const char* fmt);
 void commPrintBanner(Comm* c) { sbh_print_banner(c, FMT); } /* src/comm.c:185-250: names the build's format */

@@ -40,6 +40,7 @@ static const char* kHelp =
     "  -a         Smoothed-aggregation coarsening for -p mgpoly, made on the device from the matrix alone: any matrix (-m file,\n"
     "             -m irregular, generated). Forms its own Galerkin products (not with -g). Takes -l (default up to 4) and -d.\n"
     "  -P <sgs|mg|mgfw|poly|mgpoly>   One of those preconditioners for -t bicgstab in its diagonal's place, with -l, -d, -g, -a as for -p.\n"
+    "             With -t gmres it is the right preconditioner of GMRES(m), and -P jacobi (the diagonal) is one more.\n"
     "  -r <int>   GMRES restart length. Default 30.\n"
     "  -n <int>   Number of right-hand sides for -t cg. Default 1.\n"
     "  -x <int>   Size in x for generated matrix, ignored if MM file is loaded. Default 100.\n"
@@ -75,7 +76,7 @@ int main(int argc, char** argv)
   int steps   = 0;  /* -d: steps of -p poly or -p mgpoly; 0 not given (3, 2) */
   int galerkin = 0; /* -g: the coarse operators of -p mgpoly are P^T A P */
   int aggregation = 0; /* -a: the hierarchy of -p mgpoly is made from the matrix alone by smoothed aggregation */
-  int bprecond = -1; /* -P: the plan preconditioner of -t bicgstab, numbered as -p; -1 not given */
+  int bprecond = -1; /* -P: the plan preconditioner of -t bicgstab or -t gmres, numbered as -p (0 with -t gmres only); -1 not given */
   opterr = 0;
   while ((opt = getopt(argc, argv, "hc:t:f:m:x:y:z:i:e:C:s:r:n:p:P:l:ad:g")) != -1) switch (opt) {
     case 'h':
@@ -127,7 +128,8 @@ int main(int argc, char** argv)
       }
       break;
     case 'P':
-      if (strcmp(optarg, "sgs") == 0) bprecond = 1;
+      if (strcmp(optarg, "jacobi") == 0) bprecond = 0; /* (with -t gmres only: refused below, where the type is known) */
+      else if (strcmp(optarg, "sgs") == 0) bprecond = 1;
       else if (strcmp(optarg, "mg") == 0) bprecond = 2;
       else if (strcmp(optarg, "mgfw") == 0) bprecond = 3;
       else if (strcmp(optarg, "poly") == 0) bprecond = 4;
@@ -167,8 +169,13 @@ int main(int argc, char** argv)
     fprintf(stderr, "-p <jacobi|sgs> (the preconditioner) goes with -t pcg only\n");
     return 1;
   }
-  if (bprecond != -1 && type != BICGSTAB) {
-    fprintf(stderr, "-P <sgs|mg|mgfw|poly|mgpoly> (the preconditioner of BiCGStab) goes with -t bicgstab only\n");
+  if (bprecond == 0 && type != GMRES) { /* BiCGStab's diagonal is its default: -P names the plans there */
+    fprintf(stderr, "Unknown preconditioner jacobi (-P <sgs|mg|mgfw|poly|mgpoly>)\n");
+    return 1;
+  }
+  if (bprecond != -1 && type != BICGSTAB && type != GMRES) {
+    fprintf(stderr, "-P <sgs|mg|mgfw|poly|mgpoly> (the preconditioner of BiCGStab) goes with -t bicgstab only, or as "
+                    "-P <jacobi|sgs|mg|mgfw|poly|mgpoly> with -t gmres\n");
     return 1;
   }
   const int bicg = bprecond != -1; /* -l, -d, -g and the grid's refusals below take -P where they take -p */
@@ -239,7 +246,14 @@ int main(int argc, char** argv)
     k = nrhs == 1 ? solveCG(&comm, &param, &sm) : solveCGBatch(&comm, &param, &sm, nrhs);
   } else if (type == GMRES) {
     if (commIsMaster(&comm)) printf("Test type: GMRES\n");
-    k = solveGMRES(&comm, &param, &sm, restart);
+    if (!bicg) k = solveGMRES(&comm, &param, &sm, restart);
+    else if (levels == 0 && steps == 0 && !galerkin && !aggregation) k = solveGMRESPrecond(&comm, &param, &sm, restart, precond); /* (prints "Preconditioner: ..." itself) */
+    else
+#ifdef SCS
+      k = sbh_solve_gmres_precond(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, restart, precond, levels, steps, aggregation ? 2 : galerkin);
+#else
+      k = sbh_solve_gmres_precond(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, restart, precond, levels, steps, aggregation ? 2 : galerkin);
+#endif
   } else if (type == PCG) {
     if (commIsMaster(&comm)) printf("Test type: PCG\n");
     if (precond == 1) {

@@ -234,13 +234,10 @@ int sbh_solve_cg_perm(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr
 /* The solver src/main.c:31,217-222 names and leaves empty.  The loop runs in the HIP layer (sb_gmres_*); the lines solveCG
  * prints while iterating are printed afterwards from the recorded history: iteration j shows the residual estimate after
  * the step taken at counter j. */
-int sbh_solve_gmres(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int restart)
+/* solves with the handle, prints, releases it and the vectors */
+static int run_gmres(Comm* comm, Parameter* param, sb_gmres* s, double* b, double* xexact)
 {
-  dp_only("GMRES: double precision only\n");
   const int itermax = param->itermax, cap = itermax + 2;
-  double *b, *xexact;
-  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
-  sb_gmres* s       = sb_gmres_create((const sb_matrix*)dev_matrix, NULL, b, xexact, restart);
   const char* fused = getenv("SB_FUSED");
   if (fused) sb_gmres_set_fused(s, atoi(fused));
   const int k    = sb_gmres_solve(s, itermax, param->eps);
@@ -253,6 +250,13 @@ int sbh_solve_gmres(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, 
   sb_gmres_free(s);
   free(res), free(rr), free(b), free(xexact);
   return k;
+}
+int sbh_solve_gmres(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int restart)
+{
+  dp_only("GMRES: double precision only\n");
+  double *b, *xexact;
+  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
+  return run_gmres(comm, param, sb_gmres_create((const sb_matrix*)dev_matrix, NULL, b, xexact, restart), b, xexact);
 }
 
 /* ---- solveCGBatch ------------------------------------------------------------------------ */
@@ -574,6 +578,27 @@ int sbh_solve_bicgstab_precond(Comm* comm, Parameter* param, void* dev_matrix, C
   pcg_levels H;
   sb_pcg* M   = build_pcg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, precond, levels, steps, galerkin, &H);
   const int k = run_bicgstab(comm, param, sb_bicgstab_create_pre((const sb_matrix*)dev_matrix, NULL, b, xexact, M), b, xexact);
+  sb_pcg_free(M);
+  pcg_levels_free(&H);
+  return k;
+}
+
+/* ---- solveGMRESPrecond --------------------------------------------------------------------- */
+/* GMRES(m) right-preconditioned by a PCG handle's preconditioner (sb_gmres_create_pre): the handle is build_pcg's,
+ * with the same "Preconditioner: ..." line; precond 0 is Jacobi, whose line is printed here.  The printed residuals are the
+ * estimates of the preconditioned operator's loop, which are those of b - A x with x = M^-1 u */
+int sbh_solve_gmres_precond(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int restart, int precond, int levels, int steps, int galerkin)
+{
+  dp_only("GMRES: double precision only\n");
+  if (comm->size > 1) mg_refuse("GMRES: runs on one rank");
+  if (precond < 0 || precond > 5) mg_refuse("GMRES: the preconditioners are 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly");
+  double *b, *xexact;
+  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
+  pcg_levels H;
+  sb_pcg* M = build_pcg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, precond, levels, steps, galerkin, &H);
+  if (precond == 0 && commIsMaster(comm)) printf("Preconditioner: Jacobi (diagonal), nC = 0\n");
+  const int k = run_gmres(comm, param, sb_gmres_create_pre((const sb_matrix*)dev_matrix, NULL, b, xexact, restart, M), b, xexact);
   sb_pcg_free(M);
   pcg_levels_free(&H);
   return k;

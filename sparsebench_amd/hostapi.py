@@ -762,17 +762,95 @@ class _BodySolver(_Solver):
 
 class GMRES(_Solver):
     """restarted GMRES(m) on the GPU (sb_gmres_*): for matrices that are not symmetric positive definite.  Krylov basis and
-    scalars in HBM, loop without host round trips; double precision, one rank."""
+    scalars in HBM, loop without host round trips; double precision, one rank.
+
+    precond "none": no preconditioner (sb_gmres_create).  Anything else is RIGHT preconditioning, GMRES on A M^-1:
+    "jacobi", or a `dinv` of nr finite non-zero doubles in original row order (precond is then "caller"), builds a diagonal PCG
+    handle whose dinv is copied; a `PCG` instance is BORROWED -- over the same problem, outliving this handle, with no solve open
+    when this one is made or started; "sgs", "mg", "mgfw", "poly" or "mgpoly" with PCG's own keyword arguments (levels, coarse,
+    steps, lmax, ratio, coarse_steps, galerkin, coarsening, theta, omega_s) builds such a PCG of its own and frees it with
+    itself.  A plan takes no dinv.  solution() is M^-1 u of the last cycle close; history() is unchanged in shape, its rr the
+    explicit r.r of b - A M^-1 u."""
 
     PREFIX, NAME = "sb_gmres", "GMRES"
     COUNTERS = ("stop", "steps", "cycles", "n_res", "n_rr")
+    PLANS = ("sgs", "mg", "mgfw", "poly", "mgpoly")
 
-    def __init__(self, problem, restart=30, fused=True):
-        b, xe = self._open(problem)
-        self.ptr = self.L.sb_gmres_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), int(restart))
+    def __init__(self, problem, restart=30, fused=True, precond="none", dinv=None, **plan_args):
+        self._need_double(problem)
+        self.pcg, self._owns_pcg, self._kind = None, False, None
+        plan = isinstance(precond, PCG) or (isinstance(precond, str) and precond in self.PLANS)
+        if plan and dinv is not None:
+            raise ValueError("precond=%s takes no dinv: the preconditioner is the plan's"
+                             % ("a PCG handle" if isinstance(precond, PCG) else repr(precond)))
+        if isinstance(precond, PCG):
+            if plan_args:
+                raise ValueError("%s go with a precond given by name: a PCG handle brings its own" % ", ".join(sorted(plan_args)))
+            if precond.ptr is None:
+                raise ValueError("the PCG handle has been freed")
+            if precond.problem is not problem:
+                raise ValueError("the PCG handle was made over another problem: its preconditioner is that matrix's")
+        elif not plan:
+            if plan_args:
+                raise TypeError("GMRES: %s go with precond 'sgs', 'mg', 'mgfw', 'poly' or 'mgpoly' only" % ", ".join(sorted(plan_args)))
+            if dinv is not None:
+                if precond not in ("none", "caller"):
+                    raise ValueError("dinv is the caller's diagonal: it goes with no other precond, got %r" % (precond,))
+                precond = "caller"
+            if precond not in ("none", "jacobi", "caller") or (precond == "caller" and dinv is None):
+                raise ValueError("precond must be 'none', 'jacobi', 'sgs', 'mg', 'mgfw', 'poly', 'mgpoly' or a PCG handle, or pass "
+                                 "dinv; got %r" % (precond,))
+            dinv = self._dinv_arg_of(problem, dinv)
+        if precond == "none":
+            b, xe = self._open(problem)
+            self._kind = "none"
+            self.ptr = self.L.sb_gmres_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), int(restart))
+        else:
+            if isinstance(precond, PCG):
+                self.pcg = precond
+            elif plan:
+                self.pcg, self._owns_pcg = PCG(problem, precond=precond, **plan_args), True
+            elif precond == "jacobi":  # a diagonal PCG handle: its dinv is copied, so the handle goes at once
+                self._kind = precond
+                self.pcg, self._owns_pcg = PCG(problem), True
+            b, xe = self._open(problem)
+            if precond == "caller":  # entries of either sign: an entry point of its own
+                self._kind = precond
+                self.ptr = self.L.sb_gmres_create_dinv(problem.matrix, problem.halo, _ptr(b), _ptr(xe), int(restart), _ptr(dinv))
+            else:
+                self.ptr = self.L.sb_gmres_create_pre(problem.matrix, problem.halo, _ptr(b), _ptr(xe), int(restart), self.pcg.ptr)
+            if self._kind == "jacobi":
+                self.pcg.free()
+                self.pcg, self._owns_pcg = None, False
         # fused: True = the multi-dot / multi-update kernels, False = the op list (one tree dot per h entry, one waxpby-shaped
         # launch per projection); same bits
         self.L.sb_gmres_set_fused(self.ptr, int(bool(fused)))
+
+    @staticmethod
+    def _dinv_arg_of(problem, dinv):
+        if dinv is not None:
+            dinv = np.ascontiguousarray(dinv, dtype=np.float64)
+            if dinv.shape != (problem.nr,):
+                raise ValueError("dinv must hold nr = %d doubles, got shape %r" % (problem.nr, dinv.shape))
+            if not np.all(np.isfinite(dinv) & (dinv != 0.0)):
+                raise ValueError("dinv: the preconditioner's entries must be finite and non-zero")
+        return dinv
+
+    def precond(self):
+        """the kind's name: "none", "jacobi" or "caller" as the handle was made; under a plan "sgs", "mg", "mgfw", "poly" or
+        "mgpoly" as the library reports it ("jacobi" for a borrowed diagonal PCG, whose dinv was copied)"""
+        kind = self.L.sb_gmres_precond(self.ptr)
+        return self.PLANS[kind - 1] if kind > 0 else (self._kind or "jacobi")
+
+    def dinv(self):
+        """the diagonal in use (a plan: level 0's), original row order"""
+        return self._vector("dinv")
+
+    def free(self):
+        _Solver.free(self)
+        if self._owns_pcg and self.pcg is not None:
+            self.pcg.free()
+        self.pcg = None
 
     def restart(self):
         return self.L.sb_gmres_restart(self.ptr)
