@@ -141,122 +141,100 @@ __device__ __forceinline__ void bicg_stream(uint32_t n, const double* const (&in
   }
 }
 
-// p = r + beta * (p - omega * v) ;  ph = p o dinv.  Four streams in (r, p, v, dinv), two out.  The first body runs it
-// literally on p = v = 0, beta = omega = 0.0.
-__global__ __launch_bounds__(1024) void bicg_update_p_k(uint32_t n, const double* __restrict__ r, double* p, const double* __restrict__ v,
-    const double* __restrict__ dinv, double* __restrict__ ph, const BicgScalars* S)
+// The two updates that make a vector M^-1 is applied to next, each written once for the three things M^-1 can be:
+//   MODE -1  the sweeps of a plan: p (s) alone; the plan's cycle makes ph (sh) from zero.  dinv, d, ph unused
+//   MODE 0   a diagonal: ph = p o dinv, all of M^-1
+//   MODE 1   a Chebyshev-smoothed plan: level 0's step 1 rides here, as it rides in poly_update_r_k for PCG: d = (p o dinv) * c1
+//            and ph = d (pre_first, kernels.hip.h); d is level 0's cheb.d
+// p = r + beta * (p - omega * v).  Three streams in (r, p, v) and with a MODE a fourth (dinv); one out, and ph, and d.  The first
+// body runs it literally on p = v = 0, beta = omega = 0.0.
+template <int MODE>
+__device__ __forceinline__ void bicg_update_p_rows(uint32_t n, const double* __restrict__ r, double* p, const double* __restrict__ v,
+    const double* __restrict__ dinv, double* __restrict__ d, double* __restrict__ ph, double c1, const BicgScalars* S)
 {
-  const double* const in[4] = { r, p, v, dinv };
-  double* const out[2]      = { p, ph };
+  constexpr int NIN = MODE < 0 ? 3 : 4, NOUT = MODE < 0 ? 1 : 2 + MODE;
+  const double* in[NIN];
+  double* out[NOUT];
+  in[0] = r, in[1] = p, in[2] = v, out[0] = p;
+  if constexpr (MODE >= 0) in[3] = dinv, out[NOUT - 1] = ph;
+  if constexpr (MODE > 0) out[1] = d;
+  const double* const(&cin)[NIN] = in;
+  double* const(&cout)[NOUT]     = out;
   double beta = 0.0, omega = 0.0;
-  bicg_stream<4, 2, 0>(
-      n, in, out,
+  bicg_stream<NIN, NOUT, 0>(
+      n, cin, cout,
       [&] {
         if (S->stop) return false;
         beta = S->beta, omega = S->omega;
         return true;
       },
-      [&](const double(&w)[4], double(&o)[2], double&, double&) {
+      [&](const double(&w)[NIN], double(&o)[NOUT], double&, double&) {
         const double t1 = omega * w[2];
         const double t2 = w[1] - t1;
         const double t3 = beta * t2;
         o[0]            = w[0] + t3;
-        o[1]            = o[0] * w[3];
+        if constexpr (MODE >= 0) {
+          o[NOUT - 1] = pre_first<(MODE > 0)>(o[0], w[NIN - 1], c1);
+          if constexpr (MODE > 0) o[1] = o[NOUT - 1];
+        }
       },
       [&](uint32_t, double, double) {});
 }
-
-// s = r - alpha * v ;  sh = s o dinv.  Three streams in (r, v, dinv), two out; s may be r's storage (the loop's is).
-__global__ __launch_bounds__(1024) void bicg_update_s_k(uint32_t n, const double* r, const double* __restrict__ v,
-    const double* __restrict__ dinv, double* s, double* __restrict__ sh, const BicgScalars* S)
+// s = r - alpha * v; s may be r's storage (the loop's is).  Two streams in (r, v) and with a MODE a third (dinv)
+template <int MODE>
+__device__ __forceinline__ void bicg_update_s_rows(uint32_t n, const double* r, const double* __restrict__ v, const double* __restrict__ dinv,
+    double* s, double* __restrict__ d, double* __restrict__ sh, double c1, const BicgScalars* S)
 {
-  const double* const in[3] = { r, v, dinv };
-  double* const out[2]      = { s, sh };
+  constexpr int NIN = MODE < 0 ? 2 : 3, NOUT = MODE < 0 ? 1 : 2 + MODE;
+  const double* in[NIN];
+  double* out[NOUT];
+  in[0] = r, in[1] = v, out[0] = s;
+  if constexpr (MODE >= 0) in[2] = dinv, out[NOUT - 1] = sh;
+  if constexpr (MODE > 0) out[1] = d;
+  const double* const(&cin)[NIN] = in;
+  double* const(&cout)[NOUT]     = out;
   double alpha = 0.0;
-  bicg_stream<3, 2, 0>(
-      n, in, out,
+  bicg_stream<NIN, NOUT, 0>(
+      n, cin, cout,
       [&] {
         if (S->stop) return false;
         alpha = S->alpha;
         return true;
       },
-      [&](const double(&w)[3], double(&o)[2], double&, double&) {
+      [&](const double(&w)[NIN], double(&o)[NOUT], double&, double&) {
         const double t1 = alpha * w[1];
         o[0]            = w[0] - t1;
-        o[1]            = o[0] * w[2];
+        if constexpr (MODE >= 0) {
+          o[NOUT - 1] = pre_first<(MODE > 0)>(o[0], w[NIN - 1], c1);
+          if constexpr (MODE > 0) o[1] = o[NOUT - 1];
+        }
       },
       [&](uint32_t, double, double) {});
 }
 
-// The two updates under a preconditioner plan: ph = V(0, p) and sh = V(0, s) are the plan's cycle, not a product
-// with dinv.
-//   CHEB 0  the sweeps: p (s) alone; the cycle makes ph (sh) from zero.  Three (two) streams in, one out.
-//   CHEB 1  the polynomial: level 0's step 1 rides here, as it rides in poly_update_r_k for PCG: d = (p o dinv) * c1 and
-//           ph = d, poly_first_k's arithmetic.  Four (three) streams in, three out; d is level 0's cheb.d.
-// p = r + beta * (p - omega * v), the first body literally on p = v = 0, beta = omega = 0.0
+// the diagonal's two kernels
+__global__ __launch_bounds__(1024) void bicg_update_p_k(uint32_t n, const double* __restrict__ r, double* p, const double* __restrict__ v,
+    const double* __restrict__ dinv, double* __restrict__ ph, const BicgScalars* S)
+{
+  bicg_update_p_rows<0>(n, r, p, v, dinv, nullptr, ph, 0.0, S);
+}
+__global__ __launch_bounds__(1024) void bicg_update_s_k(uint32_t n, const double* r, const double* __restrict__ v,
+    const double* __restrict__ dinv, double* s, double* __restrict__ sh, const BicgScalars* S)
+{
+  bicg_update_s_rows<0>(n, r, v, dinv, s, nullptr, sh, 0.0, S);
+}
+// a plan's two: CHEB 0 the sweeps, CHEB 1 the polynomial
 template <int CHEB>
 __global__ __launch_bounds__(1024) void bicg_plan_update_p_k(uint32_t n, const double* __restrict__ r, double* p, const double* __restrict__ v,
     const double* __restrict__ dinv, double* __restrict__ d, double* __restrict__ ph, double c1, const BicgScalars* S)
 {
-  constexpr int NIN = CHEB ? 4 : 3, NOUT = CHEB ? 3 : 1;
-  const double* in[NIN];
-  double* out[NOUT];
-  in[0] = r, in[1] = p, in[2] = v, out[0] = p;
-  if constexpr (CHEB) in[3] = dinv, out[1] = d, out[2] = ph;
-  const double* const(&cin)[NIN] = in;
-  double* const(&cout)[NOUT]     = out;
-  double beta = 0.0, omega = 0.0;
-  bicg_stream<NIN, NOUT, 0>(
-      n, cin, cout,
-      [&] {
-        if (S->stop) return false;
-        beta = S->beta, omega = S->omega;
-        return true;
-      },
-      [&](const double(&w)[NIN], double(&o)[NOUT], double&, double&) {
-        const double t1 = omega * w[2];
-        const double t2 = w[1] - t1;
-        const double t3 = beta * t2;
-        o[0]            = w[0] + t3;
-        if constexpr (CHEB) {
-          const double u = o[0] * w[NIN - 1];
-          o[NOUT - 2]    = u * c1;
-          o[NOUT - 1]    = o[NOUT - 2];
-        }
-      },
-      [&](uint32_t, double, double) {});
+  bicg_update_p_rows<CHEB ? 1 : -1>(n, r, p, v, dinv, d, ph, c1, S);
 }
-
-// s = r - alpha * v, s may be r's storage (the loop's is); CHEB 1: d = (s o dinv) * c1 and sh = d
 template <int CHEB>
 __global__ __launch_bounds__(1024) void bicg_plan_update_s_k(uint32_t n, const double* r, const double* __restrict__ v,
     const double* __restrict__ dinv, double* s, double* __restrict__ d, double* __restrict__ sh, double c1, const BicgScalars* S)
 {
-  constexpr int NIN = CHEB ? 3 : 2, NOUT = CHEB ? 3 : 1;
-  const double* in[NIN];
-  double* out[NOUT];
-  in[0] = r, in[1] = v, out[0] = s;
-  if constexpr (CHEB) in[2] = dinv, out[1] = d, out[2] = sh;
-  const double* const(&cin)[NIN] = in;
-  double* const(&cout)[NOUT]     = out;
-  double alpha = 0.0;
-  bicg_stream<NIN, NOUT, 0>(
-      n, cin, cout,
-      [&] {
-        if (S->stop) return false;
-        alpha = S->alpha;
-        return true;
-      },
-      [&](const double(&w)[NIN], double(&o)[NOUT], double&, double&) {
-        const double t1 = alpha * w[1];
-        o[0]            = w[0] - t1;
-        if constexpr (CHEB) {
-          const double u = o[0] * w[NIN - 1];
-          o[NOUT - 2]    = u * c1;
-          o[NOUT - 1]    = o[NOUT - 2];
-        }
-      },
-      [&](uint32_t, double, double) {});
+  bicg_update_s_rows<CHEB ? 1 : -1>(n, r, v, dinv, s, d, sh, c1, S);
 }
 
 // the level-1 values of a.b and of a.a from one pass over a and b: t.s and t.t, and in the prologue r.rhat and r.r.  (The

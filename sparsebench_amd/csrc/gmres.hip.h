@@ -180,15 +180,35 @@ __global__ __launch_bounds__(256) void gm_multiupdate_k(uint32_t n, int nvec, co
   }
 }
 
+// The divide loop of the six scale / step kernels: out = a / dv over the caller's rows first, first + stride, ..., and on the way
+// out the first part of M^-1 out (pre_first, kernels.hip.h) for the vector the preconditioner is applied to next:
+//   MODE -1  nothing rides (dinv, d, z unused)
+//   MODE 0   a diagonal:                z = out o dinv            (all of M^-1; d is not touched)
+//   MODE 1   a Chebyshev-smoothed plan: d = z = (out o dinv) * c1 (d is level 0's cheb.d; precond_cycle then runs with firstDone)
+// blockDim / gridDim are read and every early return is taken in the kernel.
+template <int MODE>
+__device__ __forceinline__ void gm_divide_rows(uint32_t first, uint32_t stride, uint32_t n, const double* __restrict__ a, double dv,
+    double* __restrict__ out, const double* __restrict__ dinv, double* __restrict__ d, double* __restrict__ z, double c1)
+{
+  for (uint32_t e = first; e < n; e += stride) {
+    const double v = a[e] / dv;
+    out[e]         = v;
+    if (MODE >= 0) {
+      const double f = pre_first<(MODE > 0)>(v, dinv[e], c1);
+      if (MODE > 0) d[e] = f;
+      z[e] = f;
+    }
+  }
+}
+
 // out = a / (*d): the normalisation of a basis vector; g0 != NULL: block 0 also records *g0 = *d (the start of a cycle:
 // V[0] = r / normr, g[0] = normr)
 __global__ __launch_bounds__(256) void gm_scale_k(uint32_t n, const double* __restrict__ a, const double* __restrict__ d,
     double* __restrict__ out, double* __restrict__ g0, const int* __restrict__ stop)
 {
   if (stop && *stop) return;
-  const double dv       = *d;
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) out[e] = a[e] / dv;
+  const double dv = *d;
+  gm_divide_rows<-1>(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, n, a, dv, out, nullptr, nullptr, nullptr, 0.0);
   if (g0 && blockIdx.x == 0 && threadIdx.x == 0) *g0 = dv;
 }
 
@@ -274,10 +294,7 @@ __global__ __launch_bounds__(1024) void gm_step_k(uint32_t n, uint32_t nGroups, 
   if (stopped) return;
   const double hn = sqrt(ww);
   if (recorder) gm_scalar_step(gv, in, j, hn);
-  if (SCALE) {
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) vnext[e] = w[e] / hn;
-  }
+  if (SCALE) gm_divide_rows<-1>(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, n, w, hn, vnext, nullptr, nullptr, nullptr, 0.0);
 }
 
 // back substitution of a cycle close over its nvec columns (one thread):
@@ -296,39 +313,23 @@ __global__ __launch_bounds__(64) void gm_backsolve_k(GmView gv, int nvec, const 
 
 // =============================================================================
 // Right-preconditioned GMRES: the three kernels that PRODUCE a vector the preconditioner is applied to next also
-// write the first part of M^-1 of it, as bicg_plan_update_p_k<1> does for BiCGStab and poly_update_r_k for PCG.
-//   MODE 0  a diagonal:              z = v o dinv                       (all of M^-1; d is not touched)
-//   MODE 1  a Chebyshev-smoothed plan: d = z = (v o dinv) * c1          (poly_first_k's arithmetic; d is level 0's cheb.d, and
-//                                                                        precond_cycle then runs with firstDone = true)
-// Each is the twin of the kernel it stands in for, statement for statement plus those lines, to be changed with it: V, x, H, g
-// and the estimate are the twin's bits.  The twins themselves are not templated on this (their code objects stay as they are).
+// write the first part of M^-1 of it (pre_first<MODE>, kernels.hip.h), as bicg_plan_update_p_k<1> does for BiCGStab and
+// poly_update_r_k for PCG.  Each stands in for an unpreconditioned kernel, whose bits V, x, H, g and the estimate are.  The scale
+// and step kernels share their loop with it (gm_divide_rows); the multi-update is a twin, below.
 // =============================================================================
-template <int MODE> __device__ __forceinline__ double gm_pre_first(double v, double di, double c1)
-{
-  const double t = v * di;
-  return MODE ? t * c1 : t;
-}
-
-// gm_scale_k's twin: out = a / (*d0), g0, and the first part of M^-1 out
+// gm_scale_k with the first part of M^-1 out: out = a / (*d0), g0
 template <int MODE>
 __global__ __launch_bounds__(256) void gm_pre_scale_k(uint32_t n, const double* __restrict__ a, const double* __restrict__ d0,
     double* __restrict__ out, double* __restrict__ g0, const double* __restrict__ dinv, double* __restrict__ d, double* __restrict__ z,
     double c1, const int* __restrict__ stop)
 {
   if (stop && *stop) return;
-  const double dv       = *d0;
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
-    const double v = a[e] / dv;
-    out[e]         = v;
-    const double f = gm_pre_first<MODE>(v, dinv[e], c1);
-    if (MODE) d[e] = f;
-    z[e] = f;
-  }
+  const double dv = *d0;
+  gm_divide_rows<MODE>(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, n, a, dv, out, dinv, d, z, c1);
   if (g0 && blockIdx.x == 0 && threadIdx.x == 0) *g0 = dv;
 }
 
-// gm_step_k<true>'s twin: the scalar step, V[j+1] = w / hn, and the first part of M^-1 V[j+1]
+// gm_step_k<true> with the first part of M^-1 V[j+1]: the scalar step, V[j+1] = w / hn
 template <int MODE>
 __global__ __launch_bounds__(1024) void gm_pre_step_k(uint32_t n, uint32_t nGroups, const double* __restrict__ q, int l1, GmView gv, int j,
     const double* __restrict__ w, double* __restrict__ vnext, const double* __restrict__ dinv, double* __restrict__ d,
@@ -343,17 +344,16 @@ __global__ __launch_bounds__(1024) void gm_pre_step_k(uint32_t n, uint32_t nGrou
   if (stopped) return;
   const double hn = sqrt(ww);
   if (recorder) gm_scalar_step(gv, in, j, hn);
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
-    const double v = w[e] / hn;
-    vnext[e]       = v;
-    const double f = gm_pre_first<MODE>(v, dinv[e], c1);
-    if (MODE) d[e] = f;
-    z[e] = f;
-  }
+  gm_divide_rows<MODE>(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, n, w, hn, vnext, dinv, d, z, c1);
 }
 
-// gm_multiupdate_k<true, 0>'s twin (the x update of a cycle close): w += c[i] * V[i], ascending i, and the first part of M^-1 w
+// gm_multiupdate_k<true, 0>'s twin (the x update of a cycle close): w += c[i] * V[i], ascending i, and the first part of M^-1 w.
+// Its group loop (from `int i = 0` to the tail loop) is the twin's statement for statement, to be changed with it.  Tried as one
+// __forceinline__ template -- the loop over (V, ldv, nvec, c, n, e0, e1) with w0 / w1 by reference, with and without __restrict__
+// on V and c, and with the apply lambda left in the kernel and handed in as a functor -- every wording gave the same result:
+// gm_multiupdate_k<false, 0>, <false, 1>, <true, 0> and both gm_pre_multiupdate_k lose two scalar instructions (the address
+// arithmetic of the unrolled loads is scheduled differently: vector-equal only), and gm_multiupdate_k<false, 2> goes from 71 to 69
+// SGPRs and from 55 to 56 VGPRs.  DESIGN 4.6 keeps a sharing only where every symbol stays identical.
 template <int MODE>
 __global__ __launch_bounds__(256) void gm_pre_multiupdate_k(uint32_t n, int nvec, const double* __restrict__ V, size_t ldv,
     const double* __restrict__ c, double* w, const double* __restrict__ dinv, double* __restrict__ d, double* __restrict__ z, double c1,
@@ -389,8 +389,8 @@ __global__ __launch_bounds__(256) void gm_pre_multiupdate_k(uint32_t n, int nvec
     }
     gm_store2(w, e0, n, w0), gm_store2(w, e1, n, w1);
     double2 f0, f1;
-    f0.x = gm_pre_first<MODE>(w0.x, i0.x, c1), f0.y = gm_pre_first<MODE>(w0.y, i0.y, c1);
-    f1.x = gm_pre_first<MODE>(w1.x, i1.x, c1), f1.y = gm_pre_first<MODE>(w1.y, i1.y, c1);
+    f0.x = pre_first<MODE>(w0.x, i0.x, c1), f0.y = pre_first<MODE>(w0.y, i0.y, c1);
+    f1.x = pre_first<MODE>(w1.x, i1.x, c1), f1.y = pre_first<MODE>(w1.y, i1.y, c1);
     if (MODE) gm_store2(d, e0, n, f0), gm_store2(d, e1, n, f1);
     gm_store2(z, e0, n, f0), gm_store2(z, e1, n, f1);
   }

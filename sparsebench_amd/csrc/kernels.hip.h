@@ -1479,6 +1479,16 @@ __global__ __launch_bounds__(256) void max_abs_diff_partials(uint32_t n,
   max_abs_diff_block(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, n, a, b, out);
 }
 
+// The first part of M^-1 v that the kernel producing v writes on the way out, for the solvers that borrow a
+// preconditioner of PCG's:
+//   MODE 0  a diagonal:                z = v o dinv              (all of M^-1)
+//   MODE 1  a Chebyshev-smoothed plan: d = z = (v o dinv) * c1   (poly_first_k's arithmetic: level 0's step 1)
+template <int MODE> __device__ __forceinline__ double pre_first(double v, double di, double c1)
+{
+  const double t = v * di;
+  return MODE ? t * c1 : t;
+}
+
 // debug: pure streaming read (16 B per lane), result folded so nothing is elided
 __global__ __launch_bounds__(256) void stream_read_k(const double2* __restrict__ in, size_t n2,
     double* __restrict__ out)

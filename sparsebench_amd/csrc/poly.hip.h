@@ -58,8 +58,8 @@ __global__ __launch_bounds__(1024) void poly_update_r_k(uint32_t n, const double
     r0.x = r0.x + c * a0.x, r0.y = r0.y + c * a0.y;
     r1.x = r1.x + c * a1.x, r1.y = r1.y + c * a1.y;
     double2 z0, z1;
-    z0.x = (r0.x * d0.x) * c1, z0.y = (r0.y * d0.y) * c1;
-    z1.x = (r1.x * d1.x) * c1, z1.y = (r1.y * d1.y) * c1;
+    z0.x = pre_first<1>(r0.x, d0.x, c1), z0.y = pre_first<1>(r0.y, d0.y, c1);
+    z1.x = pre_first<1>(r1.x, d1.x, c1), z1.y = pre_first<1>(r1.y, d1.y, c1);
     *reinterpret_cast<double2*>(r + e0) = r0;
     *reinterpret_cast<double2*>(r + e1) = r1;
     *reinterpret_cast<double2*>(d + e0) = z0;
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(1024) void poly_update_r_k(uint32_t n, const double
         rv.x = rv.x + c * av.x;
         rv.y = rv.y + c * av.y;
         double2 zv;
-        zv.x = (rv.x * dv.x) * c1, zv.y = (rv.y * dv.y) * c1;
+        zv.x = pre_first<1>(rv.x, dv.x, c1), zv.y = pre_first<1>(rv.y, dv.y, c1);
         *reinterpret_cast<double2*>(r + e) = rv;
         *reinterpret_cast<double2*>(d + e) = zv;
         *reinterpret_cast<double2*>(z + e) = zv;
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(1024) void poly_update_r_k(uint32_t n, const double
         sr = rv.x * rv.x + rv.y * rv.y;
       } else if (e < n) {
         const double rn = src[e] + c * Ap[e];
-        const double zn = (rn * dinv[e]) * c1;
+        const double zn = pre_first<1>(rn, dinv[e], c1);
         r[e] = rn, d[e] = zn, z[e] = zn;
         sz = rn * zn + 0.0;
         sr = rn * rn + 0.0;
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void poly_first_k(uint32_t n, const double* __
   if (*stop) return;
   const uint32_t stride = gridDim.x * blockDim.x;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const double v = (r[i] * dinv[i]) * c1;
+    const double v = pre_first<1>(r[i], dinv[i], c1);
     d[i] = v, z[i] = v;
   }
 }

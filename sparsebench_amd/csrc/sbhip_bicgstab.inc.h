@@ -11,8 +11,7 @@ struct sb_bicgstab {
   const sb_matrix* A = nullptr;
   uint32_t nr = 0, nc = 0, nGroups = 0;
   // device row order; s lives in r's storage
-  double *r = nullptr, *rhat = nullptr, *p = nullptr, *ph = nullptr, *v = nullptr, *sh = nullptr, *t = nullptr, *x = nullptr, *b = nullptr,
-         *dinv = nullptr;
+  double *r = nullptr, *rhat = nullptr, *p = nullptr, *ph = nullptr, *v = nullptr, *sh = nullptr, *t = nullptr, *x = nullptr, *b = nullptr;
   double* xexact = nullptr;
   BicgScalars* S = nullptr;
   double *l1a = nullptr, *l1b = nullptr;
@@ -20,10 +19,7 @@ struct sb_bicgstab {
   int hist_cap = 0;
   int k_next = 1;
   LoopClock clock;
-  // sb_bicgstab_create_pre: the borrowed handle and its plan (NULL: a diagonal, the handle's own dinv).  The plan's level
-  // vectors are the cycle's scratch, so every handle on M and M's own solves take turns
-  const sb_pcg* M = nullptr;
-  const PrecondPlan* pre = nullptr;
+  RightPrecond pre; // the handle's own diagonal, or (sb_bicgstab_create_pre) the plan of a borrowed PCG handle
 };
 
 // grid of the four streaming kernels over n rows: vec_stream_grid
@@ -41,6 +37,25 @@ static BicgScalars* bicg_coeffs(double alpha, double omega, double beta)
   return test_block(h);
 }
 
+// the p update (the s update below) whose kernel f.mode picks: -1 bicg_plan_update_p_k<0>, 0 bicg_update_p_k, 1
+// bicg_plan_update_p_k<1>
+static void bicg_launch_update_p(uint32_t n, const double* r, double* p, const double* v, const PrecondRide& f, double* ph,
+    const BicgScalars* S)
+{
+  const dim3 grid(vec_stream_grid(n)), block(1024);
+  if (f.mode == 1) hipLaunchKernelGGL(bicg_plan_update_p_k<1>, grid, block, 0, g.stream, n, r, p, v, f.dinv, f.d, ph, f.c1, S);
+  else if (f.mode == 0) hipLaunchKernelGGL(bicg_update_p_k, grid, block, 0, g.stream, n, r, p, v, f.dinv, ph, S);
+  else hipLaunchKernelGGL(bicg_plan_update_p_k<0>, grid, block, 0, g.stream, n, r, p, v, f.dinv, f.d, (double*)nullptr, f.c1, S);
+}
+static void bicg_launch_update_s(uint32_t n, const double* r, const double* v, double* s, const PrecondRide& f, double* sh,
+    const BicgScalars* S)
+{
+  const dim3 grid(vec_stream_grid(n)), block(1024);
+  if (f.mode == 1) hipLaunchKernelGGL(bicg_plan_update_s_k<1>, grid, block, 0, g.stream, n, r, v, f.dinv, s, f.d, sh, f.c1, S);
+  else if (f.mode == 0) hipLaunchKernelGGL(bicg_update_s_k, grid, block, 0, g.stream, n, r, v, f.dinv, s, sh, S);
+  else hipLaunchKernelGGL(bicg_plan_update_s_k<0>, grid, block, 0, g.stream, n, r, v, f.dinv, s, f.d, (double*)nullptr, f.c1, S);
+}
+
 void sb_bicgstab_update_p_native(uint32_t n, double beta, double omega, const double* r_dev, double* p_dev, const double* v_dev,
     const double* dinv_dev, double* ph_dev)
 {
@@ -48,8 +63,7 @@ void sb_bicgstab_update_p_native(uint32_t n, double beta, double omega, const do
   if (n == 0) return;
   need_aligned16({ r_dev, p_dev, v_dev, dinv_dev, ph_dev }, "sb_bicgstab_update_p_native", "vectors");
   BicgScalars* S = bicg_coeffs(0.0, omega, beta);
-  hipLaunchKernelGGL(bicg_update_p_k, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, r_dev, p_dev, v_dev, dinv_dev, ph_dev,
-      (const BicgScalars*)S);
+  bicg_launch_update_p(n, r_dev, p_dev, v_dev, PrecondRide{ 0, dinv_dev }, ph_dev, S);
   test_block_done(S);
 }
 
@@ -60,8 +74,7 @@ void sb_bicgstab_update_s_native(uint32_t n, double alpha, const double* r_dev, 
   if (n == 0) return;
   need_aligned16({ r_dev, v_dev, dinv_dev, s_dev, sh_dev }, "sb_bicgstab_update_s_native", "vectors");
   BicgScalars* S = bicg_coeffs(alpha, 0.0, 0.0);
-  hipLaunchKernelGGL(bicg_update_s_k, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, r_dev, v_dev, dinv_dev, s_dev, sh_dev,
-      (const BicgScalars*)S);
+  bicg_launch_update_s(n, r_dev, v_dev, s_dev, PrecondRide{ 0, dinv_dev }, sh_dev, S);
   test_block_done(S);
 }
 
@@ -75,13 +88,7 @@ void sb_bicgstab_plan_update_p_native(uint32_t n, int cheb, double c1, double be
   if (cheb) need_aligned16({ dinv_dev, d_dev, ph_dev }, "sb_bicgstab_plan_update_p_native", "vectors");
   if (cheb && (!dinv_dev || !d_dev || !ph_dev)) SB_FATAL("sb_bicgstab_plan_update_p_native: cheb = 1 needs dinv_dev, d_dev and ph_dev");
   BicgScalars* S = bicg_coeffs(0.0, omega, beta);
-  const dim3 grid(vec_stream_grid(n)), block(1024);
-  if (cheb)
-    hipLaunchKernelGGL(bicg_plan_update_p_k<1>, grid, block, 0, g.stream, n, r_dev, p_dev, v_dev, dinv_dev, d_dev, ph_dev, c1,
-        (const BicgScalars*)S);
-  else
-    hipLaunchKernelGGL(bicg_plan_update_p_k<0>, grid, block, 0, g.stream, n, r_dev, p_dev, v_dev, (const double*)nullptr, (double*)nullptr,
-        (double*)nullptr, c1, (const BicgScalars*)S);
+  bicg_launch_update_p(n, r_dev, p_dev, v_dev, cheb ? PrecondRide{ 1, dinv_dev, d_dev, c1 } : PrecondRide{}, ph_dev, S);
   test_block_done(S);
 }
 
@@ -94,13 +101,7 @@ void sb_bicgstab_plan_update_s_native(uint32_t n, int cheb, double c1, double al
   if (cheb) need_aligned16({ dinv_dev, d_dev, sh_dev }, "sb_bicgstab_plan_update_s_native", "vectors");
   if (cheb && (!dinv_dev || !d_dev || !sh_dev)) SB_FATAL("sb_bicgstab_plan_update_s_native: cheb = 1 needs dinv_dev, d_dev and sh_dev");
   BicgScalars* S = bicg_coeffs(alpha, 0.0, 0.0);
-  const dim3 grid(vec_stream_grid(n)), block(1024);
-  if (cheb)
-    hipLaunchKernelGGL(bicg_plan_update_s_k<1>, grid, block, 0, g.stream, n, r_dev, v_dev, dinv_dev, s_dev, d_dev, sh_dev, c1,
-        (const BicgScalars*)S);
-  else
-    hipLaunchKernelGGL(bicg_plan_update_s_k<0>, grid, block, 0, g.stream, n, r_dev, v_dev, (const double*)nullptr, s_dev, (double*)nullptr,
-        (double*)nullptr, c1, (const BicgScalars*)S);
+  bicg_launch_update_s(n, r_dev, v_dev, s_dev, cheb ? PrecondRide{ 1, dinv_dev, d_dev, c1 } : PrecondRide{}, sh_dev, S);
   test_block_done(S);
 }
 
@@ -141,15 +142,15 @@ void sb_bicgstab_reduce_native(uint32_t m, const double* l1_a_dev, const double*
   out[0] = h.rho, out[1] = h.rr;
 }
 
-// the handle and its loop vectors; dinv: the handle keeps a diagonal of its own
-static sb_bicgstab* bicg_alloc(const sb_matrix* m, bool dinv)
+// the handle and its loop vectors
+static size_t bicg_vector_bytes(const sb_matrix* m) { return (size_t)m->nc * sizeof(double) + 4096; }
+static sb_bicgstab* bicg_alloc(const sb_matrix* m)
 {
   sb_bicgstab* s  = new sb_bicgstab();
   s->A = m, s->nr = m->nr, s->nc = m->nc;
   s->nGroups      = (m->nr + 255u) >> 8;
-  double** vecs[] = { &s->r, &s->rhat, &s->p, &s->ph, &s->v, &s->sh, &s->t, &s->x, &s->b, &s->dinv };
-  for (double** vv : vecs)
-    if (dinv || vv != &s->dinv) *vv = (double*)sb_malloc((size_t)m->nc * sizeof(double) + 4096);
+  double** vecs[] = { &s->r, &s->rhat, &s->p, &s->ph, &s->v, &s->sh, &s->t, &s->x, &s->b };
+  for (double** vv : vecs) *vv = (double*)sb_malloc(bicg_vector_bytes(m));
   return s;
 }
 // b, the exact solution, the control block and the level-1 arrays
@@ -171,11 +172,6 @@ static void bicg_finish_create(sb_bicgstab* s, const double* b_host, const doubl
   }
   s->clock.create();
   HIP_CHECK(hipStreamSynchronize(g.stream));
-}
-// the borrowed handle's plan vectors are the cycle's scratch: not while its own solve has them in flight
-static void bicg_need_closed(const sb_pcg* M, const char* fn)
-{
-  if (M->clock.open) SB_FATAL("%s between sb_pcg_start and sb_pcg_finish of the borrowed PCG handle: the plan's vectors are in flight", fn);
 }
 
 sb_bicgstab* sb_bicgstab_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int precond,
@@ -210,12 +206,13 @@ sb_bicgstab* sb_bicgstab_create(const sb_matrix* m, sb_halo* halo, const double*
       SB_FATAL("sb_bicgstab_create: %u of %u matrix rows have no finite non-zero diagonal entry (the first: device row %u): the "
                "Jacobi preconditioner needs one in every row; pass precond 0 or a dinv_host of your own", bad, m->nr, first);
   }
-  sb_bicgstab* s = bicg_alloc(m, true);
+  sb_bicgstab* s = bicg_alloc(m);
+  s->pre.dinv    = (double*)sb_malloc(bicg_vector_bytes(m));
   if (precond != 1) {
     if (precond == 0) hd.assign(m->nr, 1.0);
-    upload_permuted(m, precond == 0 ? hd.data() : dinv_host, s->dinv);
+    upload_permuted(m, precond == 0 ? hd.data() : dinv_host, s->pre.dinv);
   } else if (m->nr) {
-    hipLaunchKernelGGL(pcg_reciprocal_k, dim3(stream_grid(m->nr, 256)), dim3(256), 0, g.stream, m->nr, (const double*)tmp, s->dinv);
+    hipLaunchKernelGGL(pcg_reciprocal_k, dim3(stream_grid(m->nr, 256)), dim3(256), 0, g.stream, m->nr, (const double*)tmp, s->pre.dinv);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(g.stream));
   }
@@ -223,26 +220,23 @@ sb_bicgstab* sb_bicgstab_create(const sb_matrix* m, sb_halo* halo, const double*
   return s;
 }
 
-// M's preconditioner in the diagonal's place.  M is borrowed: it must outlive the handle, be made over the same matrix, and have
-// no solve open here or at any sb_bicgstab_start.  A diagonal M without a plan: its dinv is copied and the handle is a diagonal one
+// M's preconditioner in the diagonal's place.  M is borrowed (RightPrecond): it must outlive the handle, be made over the same
+// matrix, and have no solve open here or at any sb_bicgstab_start.  A plan-less M: its dinv is copied, the handle is a diagonal one
 sb_bicgstab* sb_bicgstab_create_pre(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const sb_pcg* M)
 {
   need_init();
   need_dp(m, "sb_bicgstab_create_pre", "BiCGStab");
   need_one_rank(m, halo, "sb_bicgstab_create_pre", "BiCGStab");
   need_tree("sb_bicgstab_create_pre", "BiCGStab", "sb_cg");
-  if (!M) SB_FATAL("sb_bicgstab_create_pre: no PCG handle to take the preconditioner from");
-  if (M->A != m) SB_FATAL("sb_bicgstab_create_pre: the PCG handle was made over another matrix: its preconditioner is that matrix's");
-  bicg_need_closed(M, "sb_bicgstab_create_pre");
-  sb_bicgstab* s = bicg_alloc(m, !M->pre);
-  if (M->pre) s->M = M, s->pre = M->pre;
-  else if (m->nr) sb_d2d(s->dinv, M->dinv, (size_t)m->nr * sizeof(double));
+  RightPrecond::need_borrowable(m, M, "sb_bicgstab_create_pre");
+  sb_bicgstab* s = bicg_alloc(m);
+  s->pre.borrow(M, bicg_vector_bytes(m));
   bicg_finish_create(s, b_host, xexact_host);
   return s;
 }
 
 // 0: a diagonal; else the plan's kind as sb_pcg_precond reports it
-int sb_bicgstab_precond(const sb_bicgstab* s) { return s->pre ? s->pre->kind : 0; }
+int sb_bicgstab_precond(const sb_bicgstab* s) { return s->pre.kind(); }
 
 void sb_bicgstab_free(sb_bicgstab* s)
 {
@@ -250,19 +244,15 @@ void sb_bicgstab_free(sb_bicgstab* s)
   HIP_CHECK(hipStreamSynchronize(g.stream));
   s->clock.destroy();
   sb_free(s->r), sb_free(s->rhat), sb_free(s->p), sb_free(s->ph), sb_free(s->v), sb_free(s->sh), sb_free(s->t), sb_free(s->x);
-  sb_free(s->b), sb_free(s->dinv), sb_free(s->xexact), sb_free(s->S), sb_free(s->l1a), sb_free(s->l1b), sb_free(s->hist);
+  sb_free(s->b), sb_free(s->pre.dinv), sb_free(s->xexact), sb_free(s->S), sb_free(s->l1a), sb_free(s->l1b), sb_free(s->hist);
   delete s;
 }
 
 // launches per loop body: p update | SpMV | rhat.v | alpha | s update | SpMV | t.s, t.t | omega | x, r update | beta = 10, the
 // same for every format and kernel mode (no SpMV kernel's fused dot is used).  Under a plan each of the two products with dinv
 // becomes a cycle of C = precond_cycle_launches: 10 + 2 C under the sweeps; under the polynomial level 0's step 1 counts among C
-// and rides in the two updates: 8 + 2 C
-int sb_bicgstab_launches_per_body(const sb_bicgstab* s)
-{
-  if (!s->pre) return 10;
-  return (s->pre->smoother == SMOOTH_CHEB ? 8 : 10) + 2 * precond_cycle_launches(s->pre);
-}
+// and rides in the two updates: 8 + 2 C (RightPrecond::apply_launches)
+int sb_bicgstab_launches_per_body(const sb_bicgstab* s) { return 10 + 2 * s->pre.apply_launches(); }
 
 template <int MODE> static void bicg_scalar_launch(sb_bicgstab* s)
 {
@@ -271,33 +261,17 @@ template <int MODE> static void bicg_scalar_launch(sb_bicgstab* s)
   HIP_CHECK(hipGetLastError());
 }
 
-// p and ph = M^-1 p (SECOND 0), s (in r's storage) and sh = M^-1 s (SECOND 1): the diagonal's one kernel, or the plan's update
-// and its cycle
+// p and ph = M^-1 p (SECOND 0), s (in r's storage) and sh = M^-1 s (SECOND 1): the update with what rides in it, then what is
+// left of the apply (a diagonal: nothing)
 template <int SECOND> static void bicg_update_and_precond(sb_bicgstab* s)
 {
   const uint32_t n = s->nr;
   if (!n) return;
-  const dim3 grid(vec_stream_grid(n)), block(1024);
-  const BicgScalars* S = s->S;
-  const double *r = s->r, *v = s->v;
   double* zh = SECOND ? s->sh : s->ph;
-  const PrecondPlan* M = s->pre;
-  if (!M) {
-    if (SECOND) hipLaunchKernelGGL(bicg_update_s_k, grid, block, 0, g.stream, n, r, v, (const double*)s->dinv, s->r, zh, S);
-    else hipLaunchKernelGGL(bicg_update_p_k, grid, block, 0, g.stream, n, r, s->p, v, (const double*)s->dinv, zh, S);
-    HIP_CHECK(hipGetLastError());
-    return;
-  }
-  const PrecondLevel& V = M->lev[0];
-  const bool cheb       = M->smoother == SMOOTH_CHEB;
-  const double* dinv    = V.dinv;
-  const double c1       = V.cheb.c.c1;
-  if (SECOND && cheb) hipLaunchKernelGGL(bicg_plan_update_s_k<1>, grid, block, 0, g.stream, n, r, v, dinv, s->r, V.cheb.d, zh, c1, S);
-  else if (SECOND) hipLaunchKernelGGL(bicg_plan_update_s_k<0>, grid, block, 0, g.stream, n, r, v, dinv, s->r, (double*)nullptr, (double*)nullptr, c1, S);
-  else if (cheb) hipLaunchKernelGGL(bicg_plan_update_p_k<1>, grid, block, 0, g.stream, n, r, s->p, v, dinv, V.cheb.d, zh, c1, S);
-  else hipLaunchKernelGGL(bicg_plan_update_p_k<0>, grid, block, 0, g.stream, n, r, s->p, v, dinv, (double*)nullptr, (double*)nullptr, c1, S);
+  if (SECOND) bicg_launch_update_s(n, s->r, s->v, s->r, s->pre.ride(), zh, s->S);
+  else bicg_launch_update_p(n, s->r, s->p, s->v, s->pre.ride(), zh, s->S);
   HIP_CHECK(hipGetLastError());
-  precond_cycle(M, SECOND ? s->r : s->p, cheb ? nullptr : V.sgs->t, zh, &s->S->stop, cheb, nullptr);
+  s->pre.apply(n, SECOND ? s->r : s->p, zh, &s->S->stop, true);
 }
 
 // one loop body
@@ -333,7 +307,7 @@ void sb_bicgstab_start(sb_bicgstab* s, int itermax, double eps)
 {
   need_init();
   need_tree("sb_bicgstab_start", "BiCGStab", "sb_cg");
-  if (s->M) bicg_need_closed(s->M, "sb_bicgstab_start");
+  s->pre.need_closed("sb_bicgstab_start");
   const int want = std::max(s->hist_cap, itermax + 2);
   grow(s->hist, s->hist_cap, want, 5);
   s->hist_cap   = want;
@@ -399,7 +373,7 @@ void sb_bicgstab_solution(const sb_bicgstab* s, double* x_host)
 void sb_bicgstab_dinv(const sb_bicgstab* s, double* dinv_host)
 {
   need_init();
-  download_original(s->A, s->pre ? s->pre->lev[0].dinv : s->dinv, dinv_host); // a plan's: level 0's, the borrowed handle's
+  download_original(s->A, s->pre.diagonal(), dinv_host); // a plan's: level 0's, the borrowed handle's
 }
 
 // max|x - xexact| (solverCheckResidual, src/CGSolver.c:40-60); 0.0 without an exact solution

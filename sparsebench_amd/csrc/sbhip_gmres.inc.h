@@ -17,32 +17,52 @@ struct sb_gmres {
   int fused = 1;
   int pos = 0; // cycle position of the next step (host side: only the stop flag can end a cycle early)
   LoopClock clock;
-  // sb_gmres_create_pre: GMRES on A M^-1.  x is then u, xs = M^-1 u the solution, zh = M^-1 V[j].  M^-1 is the plan
-  // of the borrowed handle M, or (no plan) the handle's own copy of M's diagonal
-  int pre = 0; // 1: right-preconditioned
+  // sb_gmres_create_pre / _dinv: GMRES on A M^-1.  x is then u, xs = M^-1 u the solution, zh = M^-1 V[j]
+  RightPrecond pre; // set(): right-preconditioned
   // The polynomial's first step for V[j] is written by the step that made V[j], into the BORROWED plan's level-0 d.  Handles
   // that share the plan take turns between sb_gmres_run_steps calls, so the first step of a call at j > 0 cannot rely on d: it
   // makes that first step again from V[j] (poly_first_k: the same bits, one launch more)
   bool resumed = false;
-  double *zh = nullptr, *xs = nullptr, *dinv = nullptr;
-  const struct sb_pcg* M = nullptr;
-  const struct PrecondPlan* plan = nullptr;
+  double *zh = nullptr, *xs = nullptr;
 };
-
-// sbhip_gmres_precond.inc.h (behind the plan's files): does the fused loop's producer of a vector write the first part of M^-1 of
-// it (0: no, the sweeps; else the kernels' MODE + 1), and dst = M^-1 src (rode: that first part is in place)
-static int gm_pre_rides(const sb_gmres* s);
-static void gm_pre_apply(sb_gmres* s, const double* src, double* dst, const int* stop, bool rode);
-static int gm_pre_apply_launches(const sb_gmres* s);
-struct GmPreFirst { const double* dinv; double* d; double c1; }; // the operands of gm_pre_first beside the vector
-static GmPreFirst gm_pre_operands(const sb_gmres* s);
-static void gm_pre_need_start(const sb_gmres* s); // the refusals of sb_gmres_start on a preconditioned handle
 
 static void gm_need_vectors(const void* a, const void* b, size_t ldv, const char* fn)
 {
   if ((((uintptr_t)a | (uintptr_t)b) & 15u) || (ldv & 1u)) SB_FATAL("%s: vectors must be 16-byte aligned and ldv a multiple of 2", fn);
 }
 static dim3 gm_group_grid(uint32_t nGroups) { return dim3(stream_grid(nGroups, 4)); }
+
+// The three kernels that produce a vector M^-1 is applied to next, each launched as the twin f.mode picks (-1: the
+// unpreconditioned kernel; 0, 1: gm_pre_*_k<mode>, which also writes pre_first<mode> of the vector to z, and d).  The loop and the
+// sb_gmres_pre_*_native test entries launch them from here.
+// out = a / *scalar, *g0 = *scalar
+static void gm_launch_scale(uint32_t n, const double* a, const double* scalar, double* out, double* g0, const PrecondRide& f, double* z,
+    const int* stop)
+{
+  const dim3 grid(stream_grid(n, 256)), block(256);
+  if (f.mode == 1) hipLaunchKernelGGL(gm_pre_scale_k<1>, grid, block, 0, g.stream, n, a, scalar, out, g0, f.dinv, f.d, z, f.c1, stop);
+  else if (f.mode == 0) hipLaunchKernelGGL(gm_pre_scale_k<0>, grid, block, 0, g.stream, n, a, scalar, out, g0, f.dinv, f.d, z, f.c1, stop);
+  else hipLaunchKernelGGL(gm_scale_k, grid, block, 0, g.stream, n, a, scalar, out, g0, stop);
+}
+// w += c[i] * V[i], ascending i (the x update of a close)
+static void gm_launch_multiadd(uint32_t n, int nvec, const double* V, size_t ldv, const double* c, double* w, const PrecondRide& f,
+    double* z, const int* stop)
+{
+  const dim3 grid = gm_group_grid((n + 255u) >> 8), block(256);
+  if (f.mode == 1) hipLaunchKernelGGL(gm_pre_multiupdate_k<1>, grid, block, 0, g.stream, n, nvec, V, ldv, c, w, f.dinv, f.d, z, f.c1, stop);
+  else if (f.mode == 0) hipLaunchKernelGGL(gm_pre_multiupdate_k<0>, grid, block, 0, g.stream, n, nvec, V, ldv, c, w, f.dinv, f.d, z, f.c1, stop);
+  else hipLaunchKernelGGL((gm_multiupdate_k<true, 0>), grid, block, 0, g.stream, n, nvec, V, ldv, c, w, (double*)nullptr, stop);
+}
+// the scalar step at cycle position j from the level-1 values of w . w, and vnext = w / hn
+static void gm_launch_step(uint32_t n, const double* l1, const GmView& gv, int j, const double* w, double* vnext, const PrecondRide& f,
+    double* z)
+{
+  const uint32_t nG = (n + 255u) >> 8;
+  const dim3 grid(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount, (n + 4095u) / 4096u))), block(1024);
+  if (f.mode == 1) hipLaunchKernelGGL(gm_pre_step_k<1>, grid, block, 0, g.stream, n, nG, l1, 1, gv, j, w, vnext, f.dinv, f.d, z, f.c1);
+  else if (f.mode == 0) hipLaunchKernelGGL(gm_pre_step_k<0>, grid, block, 0, g.stream, n, nG, l1, 1, gv, j, w, vnext, f.dinv, f.d, z, f.c1);
+  else hipLaunchKernelGGL((gm_step_k<true>), grid, block, 0, g.stream, n, nG, l1, 1, gv, j, w, vnext);
+}
 
 // the handle behind its entry point's refusals (fn: the entry point's name in their messages)
 static sb_gmres* gm_create(const sb_matrix* m, const double* b_host, const double* xexact_host, int restart, const char* fn)
@@ -105,7 +125,7 @@ void sb_gmres_free(sb_gmres* s)
   s->clock.destroy();
   sb_free(s->V), sb_free(s->w), sb_free(s->r), sb_free(s->x), sb_free(s->b), sb_free(s->Ap), sb_free(s->xexact);
   sb_free(s->l1), sb_free(s->partials), sb_free(s->state), sb_free(s->gv.res_hist), sb_free(s->gv.rr_hist);
-  sb_free(s->zh), sb_free(s->xs), sb_free(s->dinv);
+  sb_free(s->zh), sb_free(s->xs), sb_free(s->pre.dinv);
   delete s;
 }
 
@@ -124,14 +144,14 @@ int sb_gmres_launches_per_step(sb_gmres* s, int j)
 {
   if (!s->fused) return 0;
   if (j < 0 || j >= s->m) SB_FATAL("sb_gmres_launches_per_step: cycle position %d outside 0 .. %d", j, s->m - 1);
-  const int A = s->pre ? gm_pre_apply_launches(s) : 0;
+  const int A = s->pre.apply_launches();
   return 7 + A + (j == 0 ? 1 : 0) + (j == s->m - 1 ? 5 + A : 0);
 }
 
 // r = 1.0 * b + (-1.0) * (A x) and the level-0 partials of r.r (solveCG's prologue ops, src/CGSolver.c:94-98)
 static void gm_true_residual(sb_gmres* s, const int* stop)
 {
-  launch_spmv(s->A, s->pre ? s->xs : s->x, s->Ap, nullptr, stop); // (preconditioned: x is u and xs = M^-1 u the solution)
+  launch_spmv(s->A, s->pre.set() ? s->xs : s->x, s->Ap, nullptr, stop); // (preconditioned: x is u and xs = M^-1 u the solution)
   if (s->fused) {
     launch_dot_spans(2, s->n, s->b, s->Ap, nullptr, s->r, nullptr, s->partials, stop);
   } else {
@@ -156,27 +176,17 @@ template <int MODE> static void gm_close(sb_gmres* s, int nvec, const int* stop)
   const uint32_t n = s->n;
   hipLaunchKernelGGL(gm_backsolve_k, dim3(1), dim3(64), 0, g.stream, s->gv, nvec, stop);
   HIP_CHECK(hipGetLastError());
-  const int ride = s->pre && s->fused ? gm_pre_rides(s) : 0;
+  const PrecondRide f = s->fused ? s->pre.ride() : PrecondRide{}; // (no preconditioner: nothing rides)
   if (n) {
-    if (ride) {
-      const GmPreFirst f = gm_pre_operands(s);
-      if (ride == 2)
-        hipLaunchKernelGGL(gm_pre_multiupdate_k<1>, gm_group_grid(s->nGroups), dim3(256), 0, g.stream, n, nvec, (const double*)s->V, s->ldv,
-            (const double*)s->gv.y, s->x, f.dinv, f.d, s->xs, f.c1, stop);
-      else
-        hipLaunchKernelGGL(gm_pre_multiupdate_k<0>, gm_group_grid(s->nGroups), dim3(256), 0, g.stream, n, nvec, (const double*)s->V, s->ldv,
-            (const double*)s->gv.y, s->x, f.dinv, f.d, s->xs, f.c1, stop);
-    } else if (s->fused) {
-      hipLaunchKernelGGL((gm_multiupdate_k<true, 0>), gm_group_grid(s->nGroups), dim3(256), 0, g.stream, n, nvec, (const double*)s->V,
-          s->ldv, (const double*)s->gv.y, s->x, (double*)nullptr, stop);
-    } else {
+    if (s->fused) gm_launch_multiadd(n, nvec, s->V, s->ldv, s->gv.y, s->x, f, s->xs, stop);
+    else {
       const dim3 gridW(stream_grid(n / 2 + 1, 256)), blockW(256);
       for (int i = 0; i < nvec; i++)
         hipLaunchKernelGGL(waxpby_sdev_k, gridW, blockW, 0, g.stream, n, (const double*)s->x, (const double*)(s->gv.y + i),
             (const double*)(s->V + (size_t)i * s->ldv), s->x, stop);
     }
     HIP_CHECK(hipGetLastError());
-    if (s->pre) gm_pre_apply(s, s->x, s->xs, stop, ride != 0);
+    if (s->pre.set()) s->pre.apply(n, s->x, s->xs, stop, f.mode >= 0);
   }
   gm_true_residual(s, stop);
   hipLaunchKernelGGL((gm_rr_k<MODE>), dim3(1), dim3(1024), 0, g.stream, s->nGroups, (const double*)s->partials, 0, s->gv, stop);
@@ -192,21 +202,13 @@ static void gm_step(sb_gmres* s, int j)
   const GmView& gv = s->gv;
   double* Vj       = s->V + (size_t)j * s->ldv;
   double* Vn       = s->V + (size_t)(j + 1) * s->ldv;
-  const dim3 gridS(stream_grid(n, 256));
-  const int ride     = s->pre && s->fused && n ? gm_pre_rides(s) : 0;
-  const GmPreFirst f = ride ? gm_pre_operands(s) : GmPreFirst{ nullptr, nullptr, 0.0 };
+  const PrecondRide f = s->fused && n ? s->pre.ride() : PrecondRide{}; // (no preconditioner: nothing rides)
   if (j == 0) { // V[0] = r / normr, g[0] = normr
-    if (ride == 2)
-      hipLaunchKernelGGL(gm_pre_scale_k<1>, gridS, dim3(256), 0, g.stream, n, (const double*)s->r, (const double*)&gv.S->normr, s->V, gv.g,
-          f.dinv, f.d, s->zh, f.c1, stop);
-    else if (ride)
-      hipLaunchKernelGGL(gm_pre_scale_k<0>, gridS, dim3(256), 0, g.stream, n, (const double*)s->r, (const double*)&gv.S->normr, s->V, gv.g,
-          f.dinv, f.d, s->zh, f.c1, stop);
-    else hipLaunchKernelGGL(gm_scale_k, gridS, dim3(256), 0, g.stream, n, (const double*)s->r, (const double*)&gv.S->normr, s->V, gv.g, stop);
+    gm_launch_scale(n, s->r, &gv.S->normr, s->V, gv.g, f, s->zh, stop);
     HIP_CHECK(hipGetLastError());
   }
-  if (s->pre) { // w = A (M^-1 V[j])
-    if (n) gm_pre_apply(s, Vj, s->zh, stop, ride != 0 && !(ride == 2 && s->resumed && j > 0));
+  if (s->pre.set()) { // w = A (M^-1 V[j])
+    s->pre.apply(n, Vj, s->zh, stop, f.mode >= 0 && !(f.mode == 1 && s->resumed && j > 0));
     s->resumed = false;
     launch_spmv(s->A, s->zh, s->w, nullptr, stop);
   } else launch_spmv(s->A, Vj, s->w, nullptr, stop); // w = A V[j]
@@ -221,15 +223,8 @@ static void gm_step(sb_gmres* s, int j)
         (const double*)gv.h1, gv.hcol, stop);
     hipLaunchKernelGGL((gm_multiupdate_k<false, 1>), gridG, dim3(256), 0, g.stream, n, nvec, (const double*)s->V, s->ldv,
         (const double*)gv.h2, s->w, s->l1, stop);
-    const dim3 gridN(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount, (n + 4095u) / 4096u)));
     // (V[m] starts no step: at the cycle's last position nothing rides)
-    if (ride == 2 && j + 1 < s->m)
-      hipLaunchKernelGGL(gm_pre_step_k<1>, gridN, dim3(1024), 0, g.stream, n, nG, (const double*)s->l1, 1, gv, j, (const double*)s->w, Vn,
-          f.dinv, f.d, s->zh, f.c1);
-    else if (ride && j + 1 < s->m)
-      hipLaunchKernelGGL(gm_pre_step_k<0>, gridN, dim3(1024), 0, g.stream, n, nG, (const double*)s->l1, 1, gv, j, (const double*)s->w, Vn,
-          f.dinv, f.d, s->zh, f.c1);
-    else hipLaunchKernelGGL((gm_step_k<true>), gridN, dim3(1024), 0, g.stream, n, nG, (const double*)s->l1, 1, gv, j, (const double*)s->w, Vn);
+    gm_launch_step(n, s->l1, gv, j, s->w, Vn, j + 1 < s->m ? f : PrecondRide{}, s->zh);
     HIP_CHECK(hipGetLastError());
   } else {
     // the op list: one tree dot per h entry, one waxpby-shaped launch per projection (w = w + (-h) * V[i])
@@ -246,7 +241,7 @@ static void gm_step(sb_gmres* s, int j)
     launch_dot_spans(0, n, s->w, s->w, nullptr, nullptr, nullptr, s->partials, stop);
     hipLaunchKernelGGL((gm_step_k<false>), dim3(1), dim3(1024), 0, g.stream, n, nG, (const double*)s->partials, 0, gv, j,
         (const double*)nullptr, (double*)nullptr);
-    hipLaunchKernelGGL(gm_scale_k, gridS, dim3(256), 0, g.stream, n, (const double*)s->w, (const double*)&gv.S->hn, Vn, (double*)nullptr, stop);
+    gm_launch_scale(n, s->w, &gv.S->hn, Vn, nullptr, PrecondRide{}, nullptr, stop);
     HIP_CHECK(hipGetLastError());
   }
   if (j + 1 == s->m) gm_close<1>(s, s->m, stop); // a full cycle: restart from the true residual
@@ -255,7 +250,8 @@ static void gm_step(sb_gmres* s, int j)
 void sb_gmres_start(sb_gmres* s, int itermax, double eps)
 {
   need_init();
-  if (s->pre) gm_pre_need_start(s);
+  if (s->pre.set()) need_tree("sb_gmres_start", "preconditioned GMRES", "sb_cg");
+  s->pre.need_closed("sb_gmres_start");
   const int want = std::max(s->hist_cap, itermax + 2);
   grow(s->gv.res_hist, s->hist_cap, want, 1);
   grow(s->gv.rr_hist, s->hist_cap, want, 1);
@@ -264,7 +260,7 @@ void sb_gmres_start(sb_gmres* s, int itermax, double eps)
   h.eps = eps, h.itermax = itermax, h.hist_cap = s->hist_cap;
   write_block(s->gv.S, &h);
   HIP_CHECK(hipMemsetAsync(s->x, 0, s->ldv * sizeof(double), g.stream)); // x0 = 0
-  if (s->pre) HIP_CHECK(hipMemsetAsync(s->xs, 0, s->ldv * sizeof(double), g.stream)); // M^-1 0 = 0: the prologue needs no apply
+  if (s->pre.set()) HIP_CHECK(hipMemsetAsync(s->xs, 0, s->ldv * sizeof(double), g.stream)); // M^-1 0 = 0: the prologue needs no apply
   gm_true_residual(s, nullptr);
   hipLaunchKernelGGL((gm_rr_k<0>), dim3(1), dim3(1024), 0, g.stream, s->nGroups, (const double*)s->partials, 0, s->gv, (const int*)nullptr);
   HIP_CHECK(hipGetLastError());
@@ -316,13 +312,13 @@ int sb_gmres_history(const sb_gmres* s, double* res_out, int res_cap, double* rr
 void sb_gmres_solution(const sb_gmres* s, double* x_host)
 {
   need_init();
-  download_original(s->A, s->pre ? s->xs : s->x, x_host);
+  download_original(s->A, s->pre.set() ? s->xs : s->x, x_host);
 }
 
 double sb_gmres_check_residual(const sb_gmres* s)
 {
   need_init();
-  return max_abs_diff_host(s->n, s->pre ? s->xs : s->x, s->xexact);
+  return max_abs_diff_host(s->n, s->pre.set() ? s->xs : s->x, s->xexact);
 }
 
 double sb_gmres_loop_ms(const sb_gmres* s) { return (double)s->clock.ms; }

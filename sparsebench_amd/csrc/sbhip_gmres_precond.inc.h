@@ -1,52 +1,11 @@
 // sbhip_gmres_precond.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context):
 // right-preconditioned GMRES(m).  The loop is sbhip_gmres.inc.h's, run on A M^-1 by a change of variable: the
 // handle's x is u, xs = M^-1 u is the solution, and zh = M^-1 V[j] is what the step's SpMV reads.  M^-1 is a diagonal (the
-// handle's own copy of a plan-less sb_pcg handle's dinv) or precond_cycle on the plan of a borrowed sb_pcg handle: V(0, .), bit
-// for bit what sb_pcg_apply_precond and BiCGStab get.  Included behind the plan's files and sbhip_bicgstab.inc.h, whose
-// borrowed-handle rule this one repeats.  Double precision, one rank, tree dot order.
+// handle's own copy of a plan-less sb_pcg handle's dinv, or the caller's) or the plan of a borrowed sb_pcg handle: the handle's
+// RightPrecond (sbhip_solver.inc.h, sbhip_mg.inc.h), which BiCGStab holds too.  Double precision, one rank, tree dot order.
 // ===========================================================================
 // GMRES on A M^-1
 // ===========================================================================
-static int gm_pre_rides(const sb_gmres* s) { return !s->plan ? 1 : s->plan->smoother == SMOOTH_CHEB ? 2 : 0; }
-
-static GmPreFirst gm_pre_operands(const sb_gmres* s)
-{
-  if (!s->plan) return GmPreFirst{ s->dinv, nullptr, 0.0 };
-  const PrecondLevel& V = s->plan->lev[0];
-  return GmPreFirst{ V.dinv, V.cheb.d, V.cheb.c.c1 };
-}
-
-// launches of an apply beyond what rides in the fused loop: none for a diagonal, the cycle less level 0's step 1 under the
-// polynomial, the whole cycle under the sweeps
-static int gm_pre_apply_launches(const sb_gmres* s)
-{
-  if (!s->plan) return 0;
-  return precond_cycle_launches(s->plan) - (s->plan->smoother == SMOOTH_CHEB ? 1 : 0);
-}
-
-// dst = M^-1 src.  rode: the kernel that made src has written the diagonal's product or level 0's step 1 (the fused loop);
-// otherwise everything is made here by what the plan's own apply runs (the op list, and the sweeps always)
-static void gm_pre_apply(sb_gmres* s, const double* src, double* dst, const int* stop, bool rode)
-{
-  if (!s->n) return;
-  const PrecondPlan* M = s->plan;
-  if (!M) {
-    if (rode) return;
-    hipLaunchKernelGGL(precond_diag_k, dim3(stream_grid(s->n, 256)), dim3(256), 0, g.stream, s->n, src, (const double*)s->dinv, dst);
-    HIP_CHECK(hipGetLastError());
-    return;
-  }
-  if (!stop) stop = zero_flag(); // (sb_gmres_finish's close: the plan's kernels read their flag unconditionally)
-  const bool cheb = M->smoother == SMOOTH_CHEB;
-  precond_cycle(M, src, cheb ? nullptr : M->lev[0].sgs->t, dst, stop, cheb && rode, nullptr);
-}
-
-static void gm_pre_need_start(const sb_gmres* s)
-{
-  need_tree("sb_gmres_start", "preconditioned GMRES", "sb_cg");
-  if (s->M) bicg_need_closed(s->M, "sb_gmres_start");
-}
-
 // M's preconditioner on the right of A.  M is borrowed: it must outlive the handle, be made over the same matrix, and have no
 // solve open here or at any sb_gmres_start.  A diagonal M without a plan: its dinv is copied and M is not referred to afterwards
 sb_gmres* sb_gmres_create_pre(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int restart,
@@ -55,21 +14,14 @@ sb_gmres* sb_gmres_create_pre(const sb_matrix* m, sb_halo* halo, const double* b
   need_init();
   need_dp(m, "sb_gmres_create_pre", "GMRES");
   need_tree("sb_gmres_create_pre", "preconditioned GMRES", "sb_cg");
-  if (!M) SB_FATAL("sb_gmres_create_pre: no PCG handle to take the preconditioner from");
-  if (M->A != m) SB_FATAL("sb_gmres_create_pre: the PCG handle was made over another matrix: its preconditioner is that matrix's");
-  bicg_need_closed(M, "sb_gmres_create_pre");
+  RightPrecond::need_borrowable(m, M, "sb_gmres_create_pre");
   (void)halo;
   sb_gmres* s     = gm_create(m, b_host, xexact_host, restart, "sb_gmres_create_pre");
   const size_t vb = s->ldv * sizeof(double) + 4096;
-  s->pre = 1;
   s->zh = (double*)sb_malloc(vb), s->xs = (double*)sb_malloc(vb);
   HIP_CHECK(hipMemsetAsync(s->zh, 0, vb, g.stream));
   HIP_CHECK(hipMemsetAsync(s->xs, 0, vb, g.stream));
-  if (M->pre) s->M = M, s->plan = M->pre;
-  else {
-    s->dinv = (double*)sb_malloc(vb);
-    if (m->nr) sb_d2d(s->dinv, M->dinv, (size_t)m->nr * sizeof(double));
-  }
+  s->pre.borrow(M, vb);
   HIP_CHECK(hipStreamSynchronize(g.stream));
   return s;
 }
@@ -89,29 +41,28 @@ sb_gmres* sb_gmres_create_dinv(const sb_matrix* m, sb_halo* halo, const double* 
   (void)halo;
   sb_gmres* s     = gm_create(m, b_host, xexact_host, restart, "sb_gmres_create_dinv");
   const size_t vb = s->ldv * sizeof(double) + 4096;
-  s->pre = 1;
-  double** vecs[] = { &s->zh, &s->xs, &s->dinv };
+  double** vecs[] = { &s->zh, &s->xs, &s->pre.dinv };
   for (double** v : vecs) {
     *v = (double*)sb_malloc(vb);
     HIP_CHECK(hipMemsetAsync(*v, 0, vb, g.stream));
   }
   HIP_CHECK(hipStreamSynchronize(g.stream));
-  upload_permuted(m, dinv_host, s->dinv);
+  upload_permuted(m, dinv_host, s->pre.dinv);
   return s;
 }
 
 // -1: no preconditioner (sb_gmres_create); 0: a diagonal; else the plan's kind as sb_pcg_precond reports it
-int sb_gmres_precond(const sb_gmres* s) { return !s->pre ? -1 : s->plan ? s->plan->kind : 0; }
+int sb_gmres_precond(const sb_gmres* s) { return s->pre.set() ? s->pre.kind() : -1; }
 
 void sb_gmres_dinv(const sb_gmres* s, double* dinv_host)
 {
   need_init();
-  if (!s->pre) SB_FATAL("sb_gmres_dinv: the handle has no preconditioner (sb_gmres_create)");
-  download_original(s->A, s->plan ? s->plan->lev[0].dinv : s->dinv, dinv_host); // a plan's: level 0's, the borrowed handle's
+  if (!s->pre.set()) SB_FATAL("sb_gmres_dinv: the handle has no preconditioner (sb_gmres_create)");
+  download_original(s->A, s->pre.diagonal(), dinv_host); // a plan's: level 0's, the borrowed handle's
 }
 
-// --- the three riding kernels on a caller's vectors (blocking; tests) -------------------------------------------------------
-// mode -1: the unfused twin (dinv, d, z unused); 0: z = out o dinv; 1: d = z = (out o dinv) * c1
+// --- the three riding kernels on a caller's vectors (blocking; tests), through the loop's gm_launch_* -------------------------
+// mode -1: the unpreconditioned kernel (dinv, d, z unused); 0: z = out o dinv; 1: d = z = (out o dinv) * c1
 static void gm_pre_native_args(int mode, const double* dinv, const double* d, const double* z, const char* fn)
 {
   if (mode < -1 || mode > 1) SB_FATAL("%s: mode = %d (-1: the twin, 0: a diagonal, 1: Chebyshev)", fn, mode);
@@ -125,11 +76,7 @@ void sb_gmres_pre_scale_native(uint32_t n, int mode, double c1, const double* a_
   need_init();
   gm_pre_native_args(mode, dinv_dev, d_dev, z_dev, "sb_gmres_pre_scale_native");
   if (n == 0) return;
-  const dim3 grid(stream_grid(n, 256)), block(256);
-  const int* stop = nullptr;
-  if (mode == 1) hipLaunchKernelGGL(gm_pre_scale_k<1>, grid, block, 0, g.stream, n, a_dev, scalar_dev, out_dev, g0_dev, dinv_dev, d_dev, z_dev, c1, stop);
-  else if (mode == 0) hipLaunchKernelGGL(gm_pre_scale_k<0>, grid, block, 0, g.stream, n, a_dev, scalar_dev, out_dev, g0_dev, dinv_dev, d_dev, z_dev, c1, stop);
-  else hipLaunchKernelGGL(gm_scale_k, grid, block, 0, g.stream, n, a_dev, scalar_dev, out_dev, g0_dev, stop);
+  gm_launch_scale(n, a_dev, scalar_dev, out_dev, g0_dev, PrecondRide{ mode, dinv_dev, d_dev, c1 }, z_dev, nullptr);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(g.stream));
 }
@@ -144,11 +91,7 @@ void sb_gmres_pre_multiupdate_native(uint32_t n, int mode, double c1, int nvec, 
   gm_need_vectors(V_dev, w_dev, ldv, "sb_gmres_pre_multiupdate_native");
   if (mode >= 0) need_aligned16({ dinv_dev, d_dev, z_dev }, "sb_gmres_pre_multiupdate_native", "vectors");
   if (n == 0) return;
-  const dim3 grid = gm_group_grid((n + 255u) >> 8), block(256);
-  const int* stop = nullptr;
-  if (mode == 1) hipLaunchKernelGGL(gm_pre_multiupdate_k<1>, grid, block, 0, g.stream, n, nvec, V_dev, ldv, c_dev, w_dev, dinv_dev, d_dev, z_dev, c1, stop);
-  else if (mode == 0) hipLaunchKernelGGL(gm_pre_multiupdate_k<0>, grid, block, 0, g.stream, n, nvec, V_dev, ldv, c_dev, w_dev, dinv_dev, d_dev, z_dev, c1, stop);
-  else hipLaunchKernelGGL((gm_multiupdate_k<true, 0>), grid, block, 0, g.stream, n, nvec, V_dev, ldv, c_dev, w_dev, (double*)nullptr, stop);
+  gm_launch_multiadd(n, nvec, V_dev, ldv, c_dev, w_dev, PrecondRide{ mode, dinv_dev, d_dev, c1 }, z_dev, nullptr);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(g.stream));
 }
@@ -184,11 +127,7 @@ void sb_gmres_pre_step_native(uint32_t n, int mode, double c1, int j, const doub
   for (size_t i = 0; i < M; i++) d[o + i] = hcol_host[i];
   HIP_CHECK(hipStreamSynchronize(g.stream));
   HIP_CHECK(hipMemcpy(dev, h.data(), h.size(), hipMemcpyHostToDevice));
-  const uint32_t nG = (n + 255u) >> 8;
-  const dim3 grid(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount, (n + 4095u) / 4096u))), block(1024);
-  if (mode == 1) hipLaunchKernelGGL(gm_pre_step_k<1>, grid, block, 0, g.stream, n, nG, l1_dev, 1, gv, j, w_dev, vnext_dev, dinv_dev, d_dev, z_dev, c1);
-  else if (mode == 0) hipLaunchKernelGGL(gm_pre_step_k<0>, grid, block, 0, g.stream, n, nG, l1_dev, 1, gv, j, w_dev, vnext_dev, dinv_dev, d_dev, z_dev, c1);
-  else hipLaunchKernelGGL((gm_step_k<true>), grid, block, 0, g.stream, n, nG, l1_dev, 1, gv, j, w_dev, vnext_dev);
+  gm_launch_step(n, l1_dev, gv, j, w_dev, vnext_dev, PrecondRide{ mode, dinv_dev, d_dev, c1 }, z_dev);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(g.stream));
   HIP_CHECK(hipMemcpy(h.data(), dev, h.size(), hipMemcpyDeviceToHost));

@@ -179,6 +179,55 @@ static int precond_cycle_launches(const PrecondPlan* M)
   return n;
 }
 
+// --- RightPrecond (sbhip_solver.inc.h): the cycle for the solvers that borrow it ------------------------------------------------
+void RightPrecond::need_borrowable(const sb_matrix* m, const sb_pcg* M, const char* fn)
+{
+  if (!M) SB_FATAL("%s: no PCG handle to take the preconditioner from", fn);
+  if (M->A != m) SB_FATAL("%s: the PCG handle was made over another matrix: its preconditioner is that matrix's", fn);
+  RightPrecond{ M }.need_closed(fn);
+}
+void RightPrecond::borrow(const sb_pcg* from, size_t bytes)
+{
+  if (from->pre) {
+    M = from, plan = from->pre;
+    return;
+  }
+  dinv = (double*)sb_malloc(bytes);
+  if (from->nr) sb_d2d(dinv, from->dinv, (size_t)from->nr * sizeof(double));
+}
+void RightPrecond::need_closed(const char* fn) const
+{
+  if (M && M->clock.open)
+    SB_FATAL("%s between sb_pcg_start and sb_pcg_finish of the borrowed PCG handle: the plan's vectors are in flight", fn);
+}
+int RightPrecond::kind() const { return plan ? plan->kind : 0; }
+const double* RightPrecond::diagonal() const { return plan ? plan->lev[0].dinv : dinv; }
+PrecondRide RightPrecond::ride() const
+{
+  if (!plan) return dinv ? PrecondRide{ 0, dinv, nullptr, 0.0 } : PrecondRide{};
+  const PrecondLevel& V = plan->lev[0];
+  return plan->smoother == SMOOTH_CHEB ? PrecondRide{ 1, V.dinv, V.cheb.d, V.cheb.c.c1 } : PrecondRide{};
+}
+void RightPrecond::apply(uint32_t n, const double* src, double* dst, const int* stop, bool rode) const
+{
+  if (!n) return;
+  if (!plan) {
+    if (rode) return;
+    hipLaunchKernelGGL(precond_diag_k, dim3(stream_grid(n, 256)), dim3(256), 0, g.stream, n, src, (const double*)dinv, dst);
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  if (!stop) stop = zero_flag(); // (the plan's kernels read their flag unconditionally)
+  const bool cheb = plan->smoother == SMOOTH_CHEB;
+  precond_cycle(plan, src, cheb ? nullptr : plan->lev[0].sgs->t, dst, stop, cheb && rode, nullptr);
+}
+// none for a diagonal, the cycle less level 0's step 1 under the polynomial, the whole cycle under the sweeps
+int RightPrecond::apply_launches() const
+{
+  if (!plan) return 0;
+  return precond_cycle_launches(plan) - (plan->smoother == SMOOTH_CHEB ? 1 : 0);
+}
+
 // bytes the full-weighting transfers of one level read and write beside their structures: P^T's gathered fine vectors in (d;
 // r and w under the polynomial) and rc out; P's zc in, z in and out
 static double mg_fw_vector_bytes(const PrecondLevel& V, int fineIn)

@@ -154,6 +154,41 @@ static double max_abs_diff_host(uint32_t n, const double* x, const double* xexac
   return mx;
 }
 
+// --- M^-1 for a solver that borrows a PCG handle's preconditioner --------------------------------------------
+// BiCGStab and GMRES each hold one.  M^-1 is a diagonal (dinv, the holder's own allocation: a copy of a plan-less PCG handle's,
+// or the caller's) or precond_cycle on the plan of the borrowed handle M: V(0, .), bit for bit sb_pcg_apply_precond's.  A plan's
+// level vectors are the cycle's scratch, so every handle on M and M's own solves take turns.  The members are defined beside
+// precond_cycle (sbhip_mg.inc.h).
+struct sb_pcg;
+struct PrecondPlan;
+namespace {
+// what the kernel that PRODUCES a vector writes of M^-1 of it on the way out (pre_first<mode>, kernels.hip.h): -1 nothing (the
+// sweeps; no preconditioner), 0 a diagonal's product with dinv, 1 the polynomial's step 1 into level 0's d and the destination
+struct PrecondRide {
+  int mode           = -1;
+  const double* dinv = nullptr;
+  double* d          = nullptr;
+  double c1          = 0.0;
+};
+struct RightPrecond {
+  const sb_pcg* M         = nullptr; // borrowed with its plan; NULL for a diagonal
+  const PrecondPlan* plan = nullptr;
+  double* dinv            = nullptr; // a diagonal's entries, device row order (the holder frees them)
+  // the refusals of a *_create_pre entry point fn (no handle, another matrix, a solve open); nothing is taken yet
+  static void need_borrowable(const sb_matrix* m, const sb_pcg* M, const char* fn);
+  // M's plan, or (a plan-less M) a copy of its dinv in `bytes` of the holder's own, after which M is not referred to again
+  void borrow(const sb_pcg* M, size_t bytes);
+  void need_closed(const char* fn) const; // at every *_start: not while M's own solve has the plan's vectors in flight
+  bool set() const { return plan || dinv; }
+  int kind() const;                 // 0: a diagonal; else the plan's kind as sb_pcg_precond reports it
+  const double* diagonal() const;   // dinv, or level 0's of the plan
+  PrecondRide ride() const;
+  // dst = M^-1 src over n rows.  rode: src's producer has written ride()'s part; else everything is made here
+  void apply(uint32_t n, const double* src, double* dst, const int* stop, bool rode) const;
+  int apply_launches() const; // of an apply behind a producer that rode
+};
+} // namespace
+
 // --- grid of the 1024-thread streaming kernels over n rows (cg_update_r_k<0>'s, dot_l1_k's): a wave per 256-row group, two
 // workgroups per CU at most ------------------------------------------------------------------------------------------------
 static uint32_t vec_stream_grid(uint32_t n)

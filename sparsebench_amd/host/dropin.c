@@ -50,6 +50,13 @@ int solveCG(Comm* comm, Parameter* param, Matrix* m)
 #error "compile with -DCRS or -DSCS"
 #endif
 
+/* the fmt, C, sigma arguments of the sbh_solve_* entries that rebuild the matrix on coarser grids, for this build's Matrix */
+#if defined(CRS)
+#define SBH_FMT_ARGS(m) 0, 0, 0
+#else
+#define SBH_FMT_ARGS(m) 1, (m)->C, (m)->sigma
+#endif
+
 /* restarted GMRES on this build's Matrix (the _sp libraries: ends the process with "GMRES: double precision only") */
 int solveGMRES(Comm* comm, Parameter* param, Matrix* m, int restart)
 {
@@ -69,70 +76,42 @@ int solvePCGSGS(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_pcg_
 /* the same with the multigrid V-cycle around it, on the generated grid's own hierarchy at auto depth */
 int solvePCGMG(Comm* comm, Parameter* param, Matrix* m)
 {
-#if defined(CRS)
-  return sbh_solve_pcg_mg(comm, param, m->dev, m->nr, m->rowNnz, 0, 0, 0, 0);
-#else
-  return sbh_solve_pcg_mg(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, 0);
-#endif
+  return sbh_solve_pcg_mg(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), 0);
 }
 /* the same with full-weighting transfers between the levels */
 int solvePCGMGFW(Comm* comm, Parameter* param, Matrix* m)
 {
-#if defined(CRS)
-  return sbh_solve_pcg_mgfw(comm, param, m->dev, m->nr, m->rowNnz, 0, 0, 0, 0);
-#else
-  return sbh_solve_pcg_mgfw(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, 0);
-#endif
+  return sbh_solve_pcg_mgfw(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), 0);
 }
 /* solvePCG with the Chebyshev polynomial preconditioner at its default steps */
 int solvePCGPoly(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_pcg_poly(comm, param, m->dev, m->nr, m->rowNnz, 0); }
 /* solvePCGMGFW with the polynomial as the smoother of every level, at its default steps */
 int solvePCGMGPoly(Comm* comm, Parameter* param, Matrix* m)
 {
-#if defined(CRS)
-  return sbh_solve_pcg_mgpoly(comm, param, m->dev, m->nr, m->rowNnz, 0, 0, 0, 0, 0);
-#else
-  return sbh_solve_pcg_mgpoly(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, 0, 0);
-#endif
+  return sbh_solve_pcg_mgpoly(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), 0, 0);
 }
 /* solvePCGMGPoly on Galerkin coarse operators formed on the device, omega = 1.0 */
 int solvePCGMGPolyGalerkin(Comm* comm, Parameter* param, Matrix* m)
 {
-#if defined(CRS)
-  return sbh_solve_pcg_mgpoly_galerkin(comm, param, m->dev, m->nr, m->rowNnz, 0, 0, 0, 0, 0);
-#else
-  return sbh_solve_pcg_mgpoly_galerkin(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, 0, 0);
-#endif
+  return sbh_solve_pcg_mgpoly_galerkin(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), 0, 0);
 }
 /* solvePCGMGPoly on the smoothed-aggregation hierarchy made from the matrix alone */
 int solvePCGMGPolySA(Comm* comm, Parameter* param, Matrix* m)
 {
-#if defined(CRS)
-  return sbh_solve_pcg_mgpoly_sa(comm, param, m->dev, m->nr, m->rowNnz, 0, 0, 0, 0, 0);
-#else
-  return sbh_solve_pcg_mgpoly_sa(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, 0, 0);
-#endif
+  return sbh_solve_pcg_mgpoly_sa(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), 0, 0);
 }
 /* Jacobi-preconditioned BiCGStab on this build's Matrix (the _sp libraries: "BiCGStab: double precision only") */
 int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_bicgstab(comm, param, m->dev, m->nr, m->rowNnz); }
 /* ... with one of PCG's preconditioners at its defaults: 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly */
 int solveBiCGStabPrecond(Comm* comm, Parameter* param, Matrix* m, int precond)
 {
-#if defined(CRS)
-  return sbh_solve_bicgstab_precond(comm, param, m->dev, m->nr, m->rowNnz, 0, 0, 0, precond, 0, 0, 0);
-#else
-  return sbh_solve_bicgstab_precond(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, precond, 0, 0, 0);
-#endif
+  return sbh_solve_bicgstab_precond(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), precond, 0, 0, 0);
 }
 /* restarted GMRES right-preconditioned by one of PCG's preconditioners at its defaults: 0 jacobi, 1 sgs, 2 mg,
  * 3 mgfw, 4 poly, 5 mgpoly (the _sp libraries: "GMRES: double precision only") */
 int solveGMRESPrecond(Comm* comm, Parameter* param, Matrix* m, int restart, int precond)
 {
-#if defined(CRS)
-  return sbh_solve_gmres_precond(comm, param, m->dev, m->nr, m->rowNnz, 0, 0, 0, restart, precond, 0, 0, 0);
-#else
-  return sbh_solve_gmres_precond(comm, param, m->dev, m->nr, m->rowNnz, 1, m->C, m->sigma, restart, precond, 0, 0, 0);
-#endif
+  return sbh_solve_gmres_precond(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), restart, precond, 0, 0, 0);
 }
 
 void sbh_print_banner(Comm* c, const char* fmt);

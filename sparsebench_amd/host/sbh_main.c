@@ -51,6 +51,25 @@ static const char* kHelp =
     "  -C <int>   Sell-C-sigma chunk height (SCS build). Default 64.\n"
     "  -s <int>   Sell-C-sigma sorting scope (SCS build). Default 1.\n";
 
+/* the fmt, C, sigma arguments of the sbh_solve_* entries that rebuild the matrix on coarser grids, for this build's Matrix */
+#ifdef SCS
+#define SBH_FMT_ARGS(m) 1, (m)->C, (m)->sigma
+#else
+#define SBH_FMT_ARGS(m) 0, 0, 0
+#endif
+
+/* -p and -P number the preconditioners alike: optarg's number, -1 for a name that is none */
+static int precond_number(void)
+{
+  if (strcmp(optarg, "jacobi") == 0) return 0;
+  if (strcmp(optarg, "sgs") == 0) return 1;
+  if (strcmp(optarg, "mg") == 0) return 2;
+  if (strcmp(optarg, "mgfw") == 0) return 3;
+  if (strcmp(optarg, "poly") == 0) return 4;
+  if (strcmp(optarg, "mgpoly") == 0) return 5;
+  return -1;
+}
+
 /* a solver the single-precision driver does not have: its message, exit status 1 */
 static void dp_only(const char* msg)
 {
@@ -116,25 +135,13 @@ int main(int argc, char** argv)
     case 'r': restart = atoi(optarg); break;
     case 'n': nrhs = atoi(optarg); break;
     case 'p':
-      if (strcmp(optarg, "jacobi") == 0) precond = 0;
-      else if (strcmp(optarg, "sgs") == 0) precond = 1;
-      else if (strcmp(optarg, "mg") == 0) precond = 2;
-      else if (strcmp(optarg, "mgfw") == 0) precond = 3;
-      else if (strcmp(optarg, "poly") == 0) precond = 4;
-      else if (strcmp(optarg, "mgpoly") == 0) precond = 5;
-      else {
+      if ((precond = precond_number()) < 0) {
         fprintf(stderr, "Unknown preconditioner %s (-p <jacobi|sgs>)\n", optarg);
         return 1;
       }
       break;
-    case 'P':
-      if (strcmp(optarg, "jacobi") == 0) bprecond = 0; /* (with -t gmres only: refused below, where the type is known) */
-      else if (strcmp(optarg, "sgs") == 0) bprecond = 1;
-      else if (strcmp(optarg, "mg") == 0) bprecond = 2;
-      else if (strcmp(optarg, "mgfw") == 0) bprecond = 3;
-      else if (strcmp(optarg, "poly") == 0) bprecond = 4;
-      else if (strcmp(optarg, "mgpoly") == 0) bprecond = 5;
-      else {
+    case 'P': /* (jacobi with -t gmres only: refused below, where the type is known) */
+      if ((bprecond = precond_number()) < 0) {
         fprintf(stderr, "Unknown preconditioner %s (-P <sgs|mg|mgfw|poly|mgpoly>)\n", optarg);
         return 1;
       }
@@ -249,11 +256,7 @@ int main(int argc, char** argv)
     if (!bicg) k = solveGMRES(&comm, &param, &sm, restart);
     else if (levels == 0 && steps == 0 && !galerkin && !aggregation) k = solveGMRESPrecond(&comm, &param, &sm, restart, precond); /* (prints "Preconditioner: ..." itself) */
     else
-#ifdef SCS
-      k = sbh_solve_gmres_precond(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, restart, precond, levels, steps, aggregation ? 2 : galerkin);
-#else
-      k = sbh_solve_gmres_precond(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, restart, precond, levels, steps, aggregation ? 2 : galerkin);
-#endif
+      k = sbh_solve_gmres_precond(&comm, &param, sm.dev, sm.nr, sm.rowNnz, SBH_FMT_ARGS(&sm), restart, precond, levels, steps, aggregation ? 2 : galerkin);
   } else if (type == PCG) {
     if (commIsMaster(&comm)) printf("Test type: PCG\n");
     if (precond == 1) {
@@ -261,43 +264,23 @@ int main(int argc, char** argv)
     } else if (precond == 2 && levels == 0) {
       k = solvePCGMG(&comm, &param, &sm); /* (prints "Preconditioner: MG ..., levels = L, nC = <colours>" itself) */
     } else if (precond == 2) {
-#ifdef SCS
-      k = sbh_solve_pcg_mg(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, levels);
-#else
-      k = sbh_solve_pcg_mg(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels);
-#endif
+      k = sbh_solve_pcg_mg(&comm, &param, sm.dev, sm.nr, sm.rowNnz, SBH_FMT_ARGS(&sm), levels);
     } else if (precond == 3 && levels == 0) {
       k = solvePCGMGFW(&comm, &param, &sm); /* (prints "Preconditioner: MG (V-cycle, full-weighting transfers, ..." itself) */
     } else if (precond == 3) {
-#ifdef SCS
-      k = sbh_solve_pcg_mgfw(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, levels);
-#else
-      k = sbh_solve_pcg_mgfw(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels);
-#endif
+      k = sbh_solve_pcg_mgfw(&comm, &param, sm.dev, sm.nr, sm.rowNnz, SBH_FMT_ARGS(&sm), levels);
     } else if (precond == 5 && aggregation && levels == 0 && steps == 0) {
       k = solvePCGMGPolySA(&comm, &param, &sm); /* (prints "Preconditioner: MG (V-cycle, ..., smoothed-aggregation coarsening), ..." itself) */
     } else if (precond == 5 && aggregation) {
-#ifdef SCS
-      k = sbh_solve_pcg_mgpoly_sa(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, levels, steps);
-#else
-      k = sbh_solve_pcg_mgpoly_sa(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels, steps);
-#endif
+      k = sbh_solve_pcg_mgpoly_sa(&comm, &param, sm.dev, sm.nr, sm.rowNnz, SBH_FMT_ARGS(&sm), levels, steps);
     } else if (precond == 5 && galerkin && levels == 0 && steps == 0) {
       k = solvePCGMGPolyGalerkin(&comm, &param, &sm); /* (prints "Preconditioner: MG (V-cycle, ..., Galerkin coarse operators), ..." itself) */
     } else if (precond == 5 && galerkin) {
-#ifdef SCS
-      k = sbh_solve_pcg_mgpoly_galerkin(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, levels, steps);
-#else
-      k = sbh_solve_pcg_mgpoly_galerkin(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels, steps);
-#endif
+      k = sbh_solve_pcg_mgpoly_galerkin(&comm, &param, sm.dev, sm.nr, sm.rowNnz, SBH_FMT_ARGS(&sm), levels, steps);
     } else if (precond == 5 && levels == 0 && steps == 0) {
       k = solvePCGMGPoly(&comm, &param, &sm); /* (prints "Preconditioner: MG (V-cycle, ..., Chebyshev polynomial smoother), ..." itself) */
     } else if (precond == 5) {
-#ifdef SCS
-      k = sbh_solve_pcg_mgpoly(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, levels, steps);
-#else
-      k = sbh_solve_pcg_mgpoly(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, levels, steps);
-#endif
+      k = sbh_solve_pcg_mgpoly(&comm, &param, sm.dev, sm.nr, sm.rowNnz, SBH_FMT_ARGS(&sm), levels, steps);
     } else if (precond == 4) { /* (prints "Preconditioner: Chebyshev polynomial, steps = ..., lambda in [...]" itself) */
       k = steps == 0 ? solvePCGPoly(&comm, &param, &sm) : sbh_solve_pcg_poly(&comm, &param, sm.dev, sm.nr, sm.rowNnz, steps);
     } else {
@@ -309,11 +292,7 @@ int main(int argc, char** argv)
     if (!bicg) k = solveBiCGStab(&comm, &param, &sm);
     else if (levels == 0 && steps == 0 && !galerkin && !aggregation) k = solveBiCGStabPrecond(&comm, &param, &sm, precond); /* (prints "Preconditioner: ..." itself) */
     else
-#ifdef SCS
-      k = sbh_solve_bicgstab_precond(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 1, sm.C, sm.sigma, precond, levels, steps, aggregation ? 2 : galerkin);
-#else
-      k = sbh_solve_bicgstab_precond(&comm, &param, sm.dev, sm.nr, sm.rowNnz, 0, 0, 0, precond, levels, steps, aggregation ? 2 : galerkin);
-#endif
+      k = sbh_solve_bicgstab_precond(&comm, &param, sm.dev, sm.nr, sm.rowNnz, SBH_FMT_ARGS(&sm), precond, levels, steps, aggregation ? 2 : galerkin);
   } else {
     if (commIsMaster(&comm)) printf("Test type: SPMVM\n");
     /* exactly the reference's loop (src/main.c:205-215): vectors from the allocation hook, filled by host loops, spMVM under

@@ -541,7 +541,7 @@ int sbh_solve_pcg_mgpoly_sa(Comm* comm, Parameter* param, void* dev_matrix, CG_U
   return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 5, levels, steps, 2);
 }
 
-/* ---- solveBiCGStab, solveBiCGStabPrecond ------------------------------------------------- */
+/* ---- solveBiCGStab ----------------------------------------------------------------------- */
 /* BiCGStab with the Jacobi right preconditioner (sb_bicgstab_*) for matrices that need not be symmetric.  The
  * lines solveCG prints while iterating are printed afterwards from the recorded r.r history: "Iteration = j" shows the
  * residual iteration j starts from, sqrt(rr[j - 1]), as solveCG and solvePCG do. */
@@ -565,43 +565,41 @@ int sbh_solve_bicgstab(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT n
   init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
   return run_bicgstab(comm, param, sb_bicgstab_create((const sb_matrix*)dev_matrix, NULL, b, xexact, 1, NULL), b, xexact);
 }
-/* ... with the preconditioner plan of a PCG handle in the diagonal's place (sb_bicgstab_create_pre): the handle is
- * build_pcg's, as the sbh_solve_pcg_* entries make theirs, with the same "Preconditioner: ..." line */
-int sbh_solve_bicgstab_precond(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
-    CG_UINT sigma, int precond, int levels, int steps, int galerkin)
-{
-  dp_only("BiCGStab: double precision only\n");
-  if (comm->size > 1) mg_refuse("BiCGStab: runs on one rank");
-  if (precond < 1 || precond > 5) mg_refuse("BiCGStab: the plan preconditioners are 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly");
-  double *b, *xexact;
-  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
-  pcg_levels H;
-  sb_pcg* M   = build_pcg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, precond, levels, steps, galerkin, &H);
-  const int k = run_bicgstab(comm, param, sb_bicgstab_create_pre((const sb_matrix*)dev_matrix, NULL, b, xexact, M), b, xexact);
-  sb_pcg_free(M);
-  pcg_levels_free(&H);
-  return k;
-}
-
-/* ---- solveGMRESPrecond --------------------------------------------------------------------- */
-/* GMRES(m) right-preconditioned by a PCG handle's preconditioner (sb_gmres_create_pre): the handle is build_pcg's,
- * with the same "Preconditioner: ..." line; precond 0 is Jacobi, whose line is printed here.  The printed residuals are the
+/* ---- solveBiCGStabPrecond, solveGMRESPrecond ------------------------------------------------ */
+/* BiCGStab with the preconditioner plan of a PCG handle in the diagonal's place (sb_bicgstab_create_pre), or (gmres)
+ * GMRES(restart) right-preconditioned by it (sb_gmres_create_pre).  The handle is build_pcg's, as the
+ * sbh_solve_pcg_* entries make theirs, with the same "Preconditioner: ..." line; precond 0 is Jacobi, which GMRES alone takes
+ * here (BiCGStab's own diagonal is sbh_solve_bicgstab) and whose line is printed here.  GMRES's printed residuals are the
  * estimates of the preconditioned operator's loop, which are those of b - A x with x = M^-1 u */
-int sbh_solve_gmres_precond(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
-    CG_UINT sigma, int restart, int precond, int levels, int steps, int galerkin)
+static int solve_borrowing(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int gmres, int restart, int precond, int levels, int steps, int galerkin)
 {
-  dp_only("GMRES: double precision only\n");
-  if (comm->size > 1) mg_refuse("GMRES: runs on one rank");
-  if (precond < 0 || precond > 5) mg_refuse("GMRES: the preconditioners are 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly");
+  dp_only(gmres ? "GMRES: double precision only\n" : "BiCGStab: double precision only\n");
+  if (comm->size > 1) mg_refuse(gmres ? "GMRES: runs on one rank" : "BiCGStab: runs on one rank");
+  if (precond < (gmres ? 0 : 1) || precond > 5)
+    mg_refuse(gmres ? "GMRES: the preconditioners are 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly"
+                    : "BiCGStab: the plan preconditioners are 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly");
   double *b, *xexact;
   init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
   pcg_levels H;
   sb_pcg* M = build_pcg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, precond, levels, steps, galerkin, &H);
   if (precond == 0 && commIsMaster(comm)) printf("Preconditioner: Jacobi (diagonal), nC = 0\n");
-  const int k = run_gmres(comm, param, sb_gmres_create_pre((const sb_matrix*)dev_matrix, NULL, b, xexact, restart, M), b, xexact);
+  const sb_matrix* m = (const sb_matrix*)dev_matrix;
+  const int k = gmres ? run_gmres(comm, param, sb_gmres_create_pre(m, NULL, b, xexact, restart, M), b, xexact)
+                      : run_bicgstab(comm, param, sb_bicgstab_create_pre(m, NULL, b, xexact, M), b, xexact);
   sb_pcg_free(M);
   pcg_levels_free(&H);
   return k;
+}
+int sbh_solve_bicgstab_precond(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int precond, int levels, int steps, int galerkin)
+{
+  return solve_borrowing(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 0, 0, precond, levels, steps, galerkin);
+}
+int sbh_solve_gmres_precond(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int restart, int precond, int levels, int steps, int galerkin)
+{
+  return solve_borrowing(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 1, restart, precond, levels, steps, galerkin);
 }
 
 /* ---- profiler table: src/profiler.c:11-141 ----------------------------------------------- */

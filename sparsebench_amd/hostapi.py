@@ -760,23 +760,14 @@ class _BodySolver(_Solver):
         self._c("run_iters")(self.ptr, int(iters))
 
 
-class GMRES(_Solver):
-    """restarted GMRES(m) on the GPU (sb_gmres_*): for matrices that are not symmetric positive definite.  Krylov basis and
-    scalars in HBM, loop without host round trips; double precision, one rank (DESIGN 4.8).
+class _PlanBorrower:
+    """What GMRES and BiCGStab share beside _Solver: a preconditioner taken from a `PCG` -- the caller's instance, BORROWED, or
+    one built by name with PCG's own keyword arguments and freed with the handle."""
 
-    precond "none": no preconditioner (sb_gmres_create).  Anything else is RIGHT preconditioning, GMRES on A M^-1 (DESIGN 4.20):
-    "jacobi", or a `dinv` of nr finite non-zero doubles in original row order (precond is then "caller"), builds a diagonal PCG
-    handle whose dinv is copied; a `PCG` instance is BORROWED -- over the same problem, outliving this handle, with no solve open
-    when this one is made or started; "sgs", "mg", "mgfw", "poly" or "mgpoly" with PCG's own keyword arguments (levels, coarse,
-    steps, lmax, ratio, coarse_steps, galerkin, coarsening, theta, omega_s) builds such a PCG of its own and frees it with
-    itself.  A plan takes no dinv.  solution() is M^-1 u of the last cycle close; history() is unchanged in shape, its rr the
-    explicit r.r of b - A M^-1 u."""
-
-    PREFIX, NAME = "sb_gmres", "GMRES"
-    COUNTERS = ("stop", "steps", "cycles", "n_res", "n_rr")
     PLANS = ("sgs", "mg", "mgfw", "poly", "mgpoly")
 
-    def __init__(self, problem, restart=30, fused=True, precond="none", dinv=None, **plan_args):
+    def _check_precond(self, problem, precond, dinv, plan_args):
+        """the refusals that need no library; True where precond is a PCG instance or a plan's name"""
         self._need_double(problem)
         self.pcg, self._owns_pcg, self._kind = None, False, None
         plan = isinstance(precond, PCG) or (isinstance(precond, str) and precond in self.PLANS)
@@ -790,9 +781,55 @@ class GMRES(_Solver):
                 raise ValueError("the PCG handle has been freed")
             if precond.problem is not problem:
                 raise ValueError("the PCG handle was made over another problem: its preconditioner is that matrix's")
-        elif not plan:
-            if plan_args:
-                raise TypeError("GMRES: %s go with precond 'sgs', 'mg', 'mgfw', 'poly' or 'mgpoly' only" % ", ".join(sorted(plan_args)))
+        elif not plan and plan_args:
+            raise TypeError("%s: %s go with precond 'sgs', 'mg', 'mgfw', 'poly' or 'mgpoly' only" % (self.NAME, ", ".join(sorted(plan_args))))
+        return plan
+
+    def _take_pcg(self, problem, precond, plan_args):
+        """the caller's PCG, or one of this handle's own by the name PCG knows it by"""
+        if isinstance(precond, PCG):
+            self.pcg = precond
+        else:
+            self.pcg, self._owns_pcg = PCG(problem, precond=precond, **plan_args), True
+
+    def _drop_pcg(self):
+        if self._owns_pcg and self.pcg is not None:
+            self.pcg.free()
+        self.pcg, self._owns_pcg = None, False
+
+    def precond(self):
+        """the kind's name: "none", "jacobi" or "caller" as the handle was made; under a plan "sgs", "mg", "mgfw", "poly" or
+        "mgpoly" as the library reports it ("jacobi" for a borrowed diagonal PCG, whose dinv was copied)"""
+        kind = self._c("precond")(self.ptr)
+        return self.PLANS[kind - 1] if kind > 0 else (self._kind or "jacobi")
+
+    def dinv(self):
+        """the diagonal in use (a plan: level 0's), original row order"""
+        return self._vector("dinv")
+
+    def free(self):
+        super().free()
+        self._drop_pcg()
+
+
+class GMRES(_PlanBorrower, _Solver):
+    """restarted GMRES(m) on the GPU (sb_gmres_*): for matrices that are not symmetric positive definite.  Krylov basis and
+    scalars in HBM, loop without host round trips; double precision, one rank (DESIGN 4.8).
+
+    precond "none": no preconditioner (sb_gmres_create).  Anything else is RIGHT preconditioning, GMRES on A M^-1 (DESIGN 4.20):
+    "jacobi", or a `dinv` of nr finite non-zero doubles in original row order (precond is then "caller"), builds a diagonal PCG
+    handle whose dinv is copied; a `PCG` instance is BORROWED -- over the same problem, outliving this handle, with no solve open
+    when this one is made or started; "sgs", "mg", "mgfw", "poly" or "mgpoly" with PCG's own keyword arguments (levels, coarse,
+    steps, lmax, ratio, coarse_steps, galerkin, coarsening, theta, omega_s) builds such a PCG of its own and frees it with
+    itself.  A plan takes no dinv.  solution() is M^-1 u of the last cycle close; history() is unchanged in shape, its rr the
+    explicit r.r of b - A M^-1 u."""
+
+    PREFIX, NAME = "sb_gmres", "GMRES"
+    COUNTERS = ("stop", "steps", "cycles", "n_res", "n_rr")
+
+    def __init__(self, problem, restart=30, fused=True, precond="none", dinv=None, **plan_args):
+        plan = self._check_precond(problem, precond, dinv, plan_args)
+        if not plan:
             if dinv is not None:
                 if precond not in ("none", "caller"):
                     raise ValueError("dinv is the caller's diagonal: it goes with no other precond, got %r" % (precond,))
@@ -801,27 +838,19 @@ class GMRES(_Solver):
                 raise ValueError("precond must be 'none', 'jacobi', 'sgs', 'mg', 'mgfw', 'poly', 'mgpoly' or a PCG handle, or pass "
                                  "dinv; got %r" % (precond,))
             dinv = self._dinv_arg_of(problem, dinv)
+            self._kind = precond
+        if plan or precond == "jacobi":
+            self._take_pcg(problem, precond, plan_args)
+        b, xe = self._open(problem)
+        args = (problem.matrix, problem.halo, _ptr(b), _ptr(xe), int(restart))
         if precond == "none":
-            b, xe = self._open(problem)
-            self._kind = "none"
-            self.ptr = self.L.sb_gmres_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), int(restart))
+            self.ptr = self.L.sb_gmres_create(*args)
+        elif precond == "caller":  # entries of either sign: an entry point of its own
+            self.ptr = self.L.sb_gmres_create_dinv(*args, _ptr(dinv))
         else:
-            if isinstance(precond, PCG):
-                self.pcg = precond
-            elif plan:
-                self.pcg, self._owns_pcg = PCG(problem, precond=precond, **plan_args), True
-            elif precond == "jacobi":  # a diagonal PCG handle: its dinv is copied, so the handle goes at once
-                self._kind = precond
-                self.pcg, self._owns_pcg = PCG(problem), True
-            b, xe = self._open(problem)
-            if precond == "caller":  # entries of either sign: an entry point of its own
-                self._kind = precond
-                self.ptr = self.L.sb_gmres_create_dinv(problem.matrix, problem.halo, _ptr(b), _ptr(xe), int(restart), _ptr(dinv))
-            else:
-                self.ptr = self.L.sb_gmres_create_pre(problem.matrix, problem.halo, _ptr(b), _ptr(xe), int(restart), self.pcg.ptr)
-            if self._kind == "jacobi":
-                self.pcg.free()
-                self.pcg, self._owns_pcg = None, False
+            self.ptr = self.L.sb_gmres_create_pre(*args, self.pcg.ptr)
+        if precond == "jacobi":  # a diagonal PCG handle: its dinv has been copied, so the handle goes at once
+            self._drop_pcg()
         # fused: True = the multi-dot / multi-update kernels, False = the op list (one tree dot per h entry, one waxpby-shaped
         # launch per projection); same bits
         self.L.sb_gmres_set_fused(self.ptr, int(bool(fused)))
@@ -835,22 +864,6 @@ class GMRES(_Solver):
             if not np.all(np.isfinite(dinv) & (dinv != 0.0)):
                 raise ValueError("dinv: the preconditioner's entries must be finite and non-zero")
         return dinv
-
-    def precond(self):
-        """the kind's name: "none", "jacobi" or "caller" as the handle was made; under a plan "sgs", "mg", "mgfw", "poly" or
-        "mgpoly" as the library reports it ("jacobi" for a borrowed diagonal PCG, whose dinv was copied)"""
-        kind = self.L.sb_gmres_precond(self.ptr)
-        return self.PLANS[kind - 1] if kind > 0 else (self._kind or "jacobi")
-
-    def dinv(self):
-        """the diagonal in use (a plan: level 0's), original row order"""
-        return self._vector("dinv")
-
-    def free(self):
-        _Solver.free(self)
-        if self._owns_pcg and self.pcg is not None:
-            self.pcg.free()
-        self.pcg = None
 
     def restart(self):
         return self.L.sb_gmres_restart(self.ptr)
@@ -1233,7 +1246,7 @@ class PCG(_BodySolver):
         return self._vector("dinv")
 
 
-class BiCGStab(_BodySolver):
+class BiCGStab(_PlanBorrower, _BodySolver):
     """Right-preconditioned BiCGStab (sb_bicgstab_*) for matrices that need not be symmetric.  precond "none":
     dinv = 1.0 everywhere; "jacobi": 1 / diag(A); a `dinv` of nr finite non-zero doubles in original row order selects the
     caller's (precond is then "caller").  precond a `PCG` instance: that handle's preconditioner plan makes ph and sh (DESIGN
@@ -1246,31 +1259,13 @@ class BiCGStab(_BodySolver):
     PREFIX, NAME = "sb_bicgstab", "BiCGStab"
     COUNTERS = ("stop", "iters", "n_rr", "n_rv", "n_ts")
     HISTORIES = ("rr", "rho", "rv", "ts", "tt")
-    PLANS = ("sgs", "mg", "mgfw", "poly", "mgpoly")
 
     def __init__(self, problem, precond="none", dinv=None, **plan_args):
-        self._need_double(problem)
-        self.pcg, self._owns_pcg = None, False
-        if isinstance(precond, PCG) or (isinstance(precond, str) and precond in self.PLANS):
-            if dinv is not None:
-                raise ValueError("precond=%s takes no dinv: the preconditioner is the plan's"
-                                 % ("a PCG handle" if isinstance(precond, PCG) else repr(precond)))
-            if isinstance(precond, PCG):
-                if plan_args:
-                    raise ValueError("%s go with a precond given by name: a PCG handle brings its own" % ", ".join(sorted(plan_args)))
-                if precond.ptr is None:
-                    raise ValueError("the PCG handle has been freed")
-                if precond.problem is not problem:
-                    raise ValueError("the PCG handle was made over another problem: its preconditioner is that matrix's")
-                self.pcg = precond
-            else:
-                self.pcg, self._owns_pcg = PCG(problem, precond=precond, **plan_args), True
+        if self._check_precond(problem, precond, dinv, plan_args):
+            self._take_pcg(problem, precond, plan_args)
             b, xe = self._open(problem)
-            self._kind = None
             self.ptr = self.L.sb_bicgstab_create_pre(problem.matrix, problem.halo, _ptr(b), _ptr(xe), self.pcg.ptr)
             return
-        if plan_args:
-            raise TypeError("BiCGStab: %s go with precond 'sgs', 'mg', 'mgfw', 'poly' or 'mgpoly' only" % ", ".join(sorted(plan_args)))
         if dinv is not None:
             precond = "caller"
         kinds = {"none": 0, "jacobi": 1, "caller": 2}
@@ -1281,18 +1276,6 @@ class BiCGStab(_BodySolver):
         self.ptr = self.L.sb_bicgstab_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), kinds[precond],
                                              _ptr(self._dinv_arg(dinv)))
 
-    def precond(self):
-        """the kind's name: "none", "jacobi" or "caller" as the handle was made; under a plan "sgs", "mg", "mgfw", "poly" or
-        "mgpoly" as the library reports it ("jacobi" for a borrowed diagonal PCG, whose dinv was copied)"""
-        kind = self.L.sb_bicgstab_precond(self.ptr)
-        return self.PLANS[kind - 1] if kind else (self._kind or "jacobi")
-
-    def free(self):
-        _BodySolver.free(self)
-        if self._owns_pcg and self.pcg is not None:
-            self.pcg.free()
-        self.pcg = None
-
     def history(self):
         """dict of rr, rho (entry 0: the prologue's, then one per body) and rv, ts, tt (one per body)"""
         cap = max(self.itermax, 0) + 2
@@ -1302,7 +1285,3 @@ class BiCGStab(_BodySolver):
             cnt = self.L.sb_bicgstab_history(self.ptr, which, a.ctypes.data_as(vp), cap)
             out[name] = a[:cnt].copy()
         return out
-
-    def dinv(self):
-        """the preconditioner in use, original row order"""
-        return self._vector("dinv")

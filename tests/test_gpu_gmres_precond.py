@@ -241,6 +241,33 @@ def test_in_pieces_equals_solve(gpu, name, fused, tmp, golden):
     a.free(), p.free()
 
 
+@pytest.mark.parametrize("kw", [dict(precond="poly", steps=3, ratio=16.0), dict(precond="sgs")], ids=["poly_3_16", "sgs"])
+def test_gmres_and_bicgstab_take_turns_on_one_borrowed_plan(gpu, kw, tmp):
+    """The two SOLVERS on one PCG handle's plan, both solves open at once and advanced alternately with the PCG handle's own apply
+    between the turns: level 0's d (the polynomial) or the forward sums t (the sweeps) are overwritten at every turn, and each
+    solver's histories, k and solution are its own uninterrupted run's bit for bit"""
+    p = hostapi.Problem(*bicgstab_ref.problem_args(cases.CD16, tmp), fmt="crs")
+    eps = 1e-10 * np.sqrt(p.nr)
+    M = hostapi.PCG(p, **kw)
+    a, bi = hostapi.GMRES(p, restart=7, precond=M), hostapi.BiCGStab(p, precond=M)
+    want_a = collect(a, a.solve(40, eps))
+    want_k, want_h, want_x = bi.solve(40, eps), bi.history(), bi.solution()
+    assert 1 < want_a["k"] <= 40 and 1 < want_k <= 40 and want_a["x"].any() and want_x.any()
+    r = np.linspace(-1.0, 2.0, p.nr)
+    a.start(40, eps), bi.start(40, eps)
+    for _ in range(20):  # 39 steps in fives, 39 bodies in twos: turns past a solver's exit are no-ops
+        a.run_steps(5)
+        M.apply(r)
+        bi.run_iters(2)
+        M.apply(r)
+    same(collect(a, a.finish()), want_a, (kw, "GMRES in turns"))
+    assert bi.finish() == want_k and np.array_equal(bi.solution(), want_x), (kw, "BiCGStab in turns")
+    got_h = bi.history()
+    assert all(np.array_equal(got_h[key], want_h[key]) for key in want_h), (kw, "BiCGStab's histories")
+    for h in (a, bi, M, p):
+        h.free()
+
+
 def test_python_refusals(gpu, tmp):
     c = cases.CASES["cd16_crs_poly_3_16_m30"]
     p, q = problem(c, tmp), hostapi.Problem("generate", 8, 8, 8, fmt="crs")
