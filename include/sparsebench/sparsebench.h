@@ -359,7 +359,56 @@ int sbh_solve_bicgstab_precond(Comm* comm, Parameter* param, void* dev_matrix, C
  * and freed after the solver; the same "Preconditioner: ..." line is printed first; the same refusals.  Double precision, one rank */
 int sbh_solve_gmres_precond(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
     CG_UINT sigma, int restart, int precond, int levels, int steps, int galerkin);
+
+/* ---- one spec and one entry behind the add-on solvers above, and the driver's options ------------------ */
+/* the preconditioner kinds, with the numbers -p, -P, solveBiCGStabPrecond and solveGMRESPrecond give them; NONE: none was named */
+enum { SBH_PRECOND_NONE = -1, SBH_PRECOND_JACOBI = 0, SBH_PRECOND_SGS, SBH_PRECOND_MG, SBH_PRECOND_MGFW, SBH_PRECOND_POLY, SBH_PRECOND_MGPOLY };
+/* the coarse operators of SBH_PRECOND_MGPOLY: the stencil regenerated on every coarser grid, P^T A P formed on the device with
+ * the trilinear P, or the smoothed-aggregation hierarchy made from the matrix alone */
+enum { SBH_COARSE_REGENERATED = 0, SBH_COARSE_GALERKIN, SBH_COARSE_AGGREGATION };
+enum { SBH_SOLVER_PCG = 0, SBH_SOLVER_BICGSTAB, SBH_SOLVER_GMRES };
+/* a preconditioner as every entry above names it: levels (the V-cycles) and steps (poly, mgpoly) 0: the default */
+typedef struct {
+  int kind, levels, steps, coarse;
+} sbh_precond_spec;
+/* What every sbh_solve_pcg*, sbh_solve_bicgstab* and sbh_solve_gmres* entry above is a one-line call of (they remain): solver
+ * SBH_SOLVER_* with the preconditioner of spec, restart for GMRES only; fmt, C, sigma as sbh_solve_pcg_mg takes them (used by
+ * the V-cycles only).  spec NULL: PCG's Jacobi, and BiCGStab or GMRES alone (sbh_solve_bicgstab, sbh_solve_gmres); with a spec
+ * those two borrow PCG's plan (one rank; BiCGStab's own diagonal is not a kind of its).  Prints the "Preconditioner: ..." line
+ * of the kind first (PCG's Jacobi: none, the driver prints it).  Double precision */
+int sbh_solve_precond(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int solver, int restart, const sbh_precond_spec* spec);
+static inline int sbh_is_generated(const Parameter* param)
+{
+  return strcmp(param->filename, "generate") == 0 || strcmp(param->filename, "generate7P") == 0;
+}
+
+/* The benchmark driver's command line, parsed without a device (host/sbh_options.c): no Comm, no sb_* call, no exit, no output */
+enum { SBH_BENCH_CG = 0, SBH_BENCH_SPMV, SBH_BENCH_GMRES, SBH_BENCH_PCG, SBH_BENCH_BICGSTAB };
+enum { SBH_ACT_RUN = 0, SBH_ACT_HELP, SBH_ACT_CONVERT }; /* what the caller does next: set up and run, print the help, write <file> as .bmx */
+typedef struct {
+  int type;                 /* -t: SBH_BENCH_* */
+  int restart, nrhs;        /* -r, -n */
+  unsigned scsC, scsSigma;  /* -C, -s */
+  int byP;                  /* the preconditioner came by -P (BiCGStab's, GMRES's), not by -p */
+  sbh_precond_spec precond; /* -p or -P with -l, -d and -g or -a */
+  int optind;               /* the first non-option argument (argc: none, or the parse ended inside the options) */
+  int action;               /* SBH_ACT_* */
+  char* convert;            /* SBH_ACT_CONVERT: -c's <file> */
+  int toStdout;             /* of a refusal: its message goes to stdout (the unknown -t), not to stderr */
+} sbh_options;
+/* Parses argv into param and o as the driver always has, checks in the same order.  Returns 0, or 1 for a refusal with its
+ * message (the newline included) in msg.  -h and -c end the parse where they stand: what came before them is applied, what
+ * follows is not looked at.  Resets getopt's state, so it can be called again; param->filename may point into argv */
+int sbh_parse_options(int argc, char** argv, Parameter* param, sbh_options* o, char* msg, size_t cap);
+const char* sbh_help_text(void);
 #if defined(CRS) || defined(SCS)
+/* the fmt, C, sigma arguments of the entries above that rebuild the matrix on coarser grids, for this build's Matrix */
+#ifdef SCS
+#define SBH_FMT_ARGS(m) 1, (m)->C, (m)->sigma
+#else
+#define SBH_FMT_ARGS(m) 0, 0, 0
+#endif
 void convertMatrix(Matrix* m, GMatrix* im);
 int solveCG(Comm* comm, Parameter* param, Matrix* m);
 /* the solver the reference's driver names and leaves empty (src/main.c:31,217-222): restarted GMRES(restart) for matrices

@@ -50,69 +50,53 @@ int solveCG(Comm* comm, Parameter* param, Matrix* m)
 #error "compile with -DCRS or -DSCS"
 #endif
 
-/* the fmt, C, sigma arguments of the sbh_solve_* entries that rebuild the matrix on coarser grids, for this build's Matrix */
-#if defined(CRS)
-#define SBH_FMT_ARGS(m) 0, 0, 0
-#else
-#define SBH_FMT_ARGS(m) 1, (m)->C, (m)->sigma
-#endif
-
-/* restarted GMRES on this build's Matrix (the _sp libraries: ends the process with "GMRES: double precision only") */
-int solveGMRES(Comm* comm, Parameter* param, Matrix* m, int restart)
-{
-  return sbh_solve_gmres(comm, param, m->dev, m->nr, m->rowNnz, restart);
-}
-
 /* nrhs CG solves on one pass over this build's Matrix per body (the _sp libraries: "batched CG: double precision only") */
 int solveCGBatch(Comm* comm, Parameter* param, Matrix* m, int nrhs)
 {
   return sbh_solve_cg_batch(comm, param, m->dev, m->nr, m->rowNnz, m->startRow, nrhs);
 }
 
-/* Jacobi-preconditioned CG on this build's Matrix (the _sp libraries: "PCG: double precision only") */
-int solvePCG(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_pcg(comm, param, m->dev, m->nr, m->rowNnz); }
-/* the same with multicolour symmetric Gauss-Seidel in the diagonal's place */
-int solvePCGSGS(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_pcg_sgs(comm, param, m->dev, m->nr, m->rowNnz); }
-/* the same with the multigrid V-cycle around it, on the generated grid's own hierarchy at auto depth */
-int solvePCGMG(Comm* comm, Parameter* param, Matrix* m)
+/* the add-on solvers on this build's Matrix, each preconditioner at its defaults (the _sp libraries: "<solver>: double precision
+ * only"); spec NULL: the solver's own default */
+static int solve(Comm* comm, Parameter* param, Matrix* m, int solver, int restart, const sbh_precond_spec* spec)
 {
-  return sbh_solve_pcg_mg(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), 0);
+  return sbh_solve_precond(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), solver, restart, spec);
 }
-/* the same with full-weighting transfers between the levels */
-int solvePCGMGFW(Comm* comm, Parameter* param, Matrix* m)
-{
-  return sbh_solve_pcg_mgfw(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), 0);
-}
-/* solvePCG with the Chebyshev polynomial preconditioner at its default steps */
-int solvePCGPoly(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_pcg_poly(comm, param, m->dev, m->nr, m->rowNnz, 0); }
-/* solvePCGMGFW with the polynomial as the smoother of every level, at its default steps */
+#define SPEC(kind, coarse) &(const sbh_precond_spec){ kind, 0, 0, coarse }
+/* Jacobi-preconditioned CG; with multicolour symmetric Gauss-Seidel in the diagonal's place; with the multigrid V-cycle
+ * around it on the generated grid's own hierarchy at auto depth (4.13); with full-weighting transfers between the levels (4.14) */
+int solvePCG(Comm* comm, Parameter* param, Matrix* m) { return solve(comm, param, m, SBH_SOLVER_PCG, 0, NULL); }
+int solvePCGSGS(Comm* comm, Parameter* param, Matrix* m) { return solve(comm, param, m, SBH_SOLVER_PCG, 0, SPEC(SBH_PRECOND_SGS, 0)); }
+int solvePCGMG(Comm* comm, Parameter* param, Matrix* m) { return solve(comm, param, m, SBH_SOLVER_PCG, 0, SPEC(SBH_PRECOND_MG, 0)); }
+int solvePCGMGFW(Comm* comm, Parameter* param, Matrix* m) { return solve(comm, param, m, SBH_SOLVER_PCG, 0, SPEC(SBH_PRECOND_MGFW, 0)); }
+/* with the Chebyshev polynomial preconditioner (4.15); solvePCGMGFW with the polynomial as the smoother of every level (4.16); that on
+ * Galerkin coarse operators formed on the device (4.17); that on the smoothed-aggregation hierarchy made from the matrix alone (4.19) */
+int solvePCGPoly(Comm* comm, Parameter* param, Matrix* m) { return solve(comm, param, m, SBH_SOLVER_PCG, 0, SPEC(SBH_PRECOND_POLY, 0)); }
 int solvePCGMGPoly(Comm* comm, Parameter* param, Matrix* m)
 {
-  return sbh_solve_pcg_mgpoly(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), 0, 0);
+  return solve(comm, param, m, SBH_SOLVER_PCG, 0, SPEC(SBH_PRECOND_MGPOLY, SBH_COARSE_REGENERATED));
 }
-/* solvePCGMGPoly on Galerkin coarse operators formed on the device, omega = 1.0 */
 int solvePCGMGPolyGalerkin(Comm* comm, Parameter* param, Matrix* m)
 {
-  return sbh_solve_pcg_mgpoly_galerkin(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), 0, 0);
+  return solve(comm, param, m, SBH_SOLVER_PCG, 0, SPEC(SBH_PRECOND_MGPOLY, SBH_COARSE_GALERKIN));
 }
-/* solvePCGMGPoly on the smoothed-aggregation hierarchy made from the matrix alone */
 int solvePCGMGPolySA(Comm* comm, Parameter* param, Matrix* m)
 {
-  return sbh_solve_pcg_mgpoly_sa(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), 0, 0);
+  return solve(comm, param, m, SBH_SOLVER_PCG, 0, SPEC(SBH_PRECOND_MGPOLY, SBH_COARSE_AGGREGATION));
 }
-/* Jacobi-preconditioned BiCGStab on this build's Matrix (the _sp libraries: "BiCGStab: double precision only") */
-int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m) { return sbh_solve_bicgstab(comm, param, m->dev, m->nr, m->rowNnz); }
-/* ... with one of PCG's preconditioners at its defaults: 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly */
+/* Jacobi-preconditioned BiCGStab, or with one of PCG's preconditioners (4.18): 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly */
+int solveBiCGStab(Comm* comm, Parameter* param, Matrix* m) { return solve(comm, param, m, SBH_SOLVER_BICGSTAB, 0, NULL); }
 int solveBiCGStabPrecond(Comm* comm, Parameter* param, Matrix* m, int precond)
 {
-  return sbh_solve_bicgstab_precond(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), precond, 0, 0, 0);
+  return solve(comm, param, m, SBH_SOLVER_BICGSTAB, 0, SPEC(precond, 0));
 }
-/* restarted GMRES right-preconditioned by one of PCG's preconditioners at its defaults: 0 jacobi, 1 sgs, 2 mg,
- * 3 mgfw, 4 poly, 5 mgpoly (the _sp libraries: "GMRES: double precision only") */
+/* restarted GMRES, or right-preconditioned by one of PCG's preconditioners (4.20): 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly */
+int solveGMRES(Comm* comm, Parameter* param, Matrix* m, int restart) { return solve(comm, param, m, SBH_SOLVER_GMRES, restart, NULL); }
 int solveGMRESPrecond(Comm* comm, Parameter* param, Matrix* m, int restart, int precond)
 {
-  return sbh_solve_gmres_precond(comm, param, m->dev, m->nr, m->rowNnz, SBH_FMT_ARGS(m), restart, precond, 0, 0, 0);
+  return solve(comm, param, m, SBH_SOLVER_GMRES, restart, SPEC(precond, 0));
 }
+#undef SPEC
 
 void sbh_print_banner(Comm* c, const char* fmt);
 void commPrintBanner(Comm* c) { sbh_print_banner(c, FMT); } /* src/comm.c:185-250: names the build's format */

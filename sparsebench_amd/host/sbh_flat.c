@@ -35,7 +35,7 @@ sbh_problem* sbh_problem_create(const char* filename, int nx, int ny, int nz, in
   p->par.filename = strdup(filename);
   p->par.nx = nx, p->par.ny = ny, p->par.nz = nz;
   p->comm.rank = rank, p->comm.size = size;
-  p->generated = strcmp(filename, "generate") == 0 || strcmp(filename, "generate7P") == 0;
+  p->generated = sbh_is_generated(&p->par);
   sbh_init_matrix(&p->comm, &p->par, &p->gm);
   p->nnzTrue = p->gm.rowPtr[p->gm.nr];
   commPartition(&p->comm, &p->gm);

@@ -106,7 +106,7 @@ static void dp_only(const char* msg)
  * is filled), *xexact is NULL for a matrix that was read from a file */
 static void init_vectors_dp(const Parameter* param, CG_UINT nr, const CG_UINT* rowNnz, int ncols, double** b, double** xexact)
 {
-  const int generated = strcmp(param->filename, "generate") == 0 || strcmp(param->filename, "generate7P") == 0;
+  const int generated = sbh_is_generated(param);
   *b                  = (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr * ncols + 1) * sizeof(double));
   *xexact             = generated ? (double*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(double)) : NULL;
   for (CG_UINT i = 0; i < nr; i++) {
@@ -159,7 +159,7 @@ static int sbh_solve(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr,
     const CG_UINT* oldToNewPerm)
 {
   const int itermax    = param->itermax;
-  const int generated  = strcmp(param->filename, "generate") == 0 || strcmp(param->filename, "generate7P") == 0;
+  const int generated  = sbh_is_generated(param);
   CG_FLOAT* b          = (CG_FLOAT*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(CG_FLOAT));
   CG_FLOAT* xexact     = generated ? (CG_FLOAT*)sbh_alloc_host(ARRAY_ALIGNMENT, ((size_t)nr + 1) * sizeof(CG_FLOAT)) : NULL;
   /* initVectors, src/CGSolver.c:25-36 */
@@ -251,13 +251,6 @@ static int run_gmres(Comm* comm, Parameter* param, sb_gmres* s, double* b, doubl
   free(res), free(rr), free(b), free(xexact);
   return k;
 }
-int sbh_solve_gmres(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int restart)
-{
-  dp_only("GMRES: double precision only\n");
-  double *b, *xexact;
-  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
-  return run_gmres(comm, param, sb_gmres_create((const sb_matrix*)dev_matrix, NULL, b, xexact, restart), b, xexact);
-}
 
 /* ---- solveCGBatch ------------------------------------------------------------------------ */
 /* nrhs independent CG solves whose loop bodies share one stream of the matrix (sb_cgb_*).  Column 0 is solveCG's
@@ -294,11 +287,9 @@ int sbh_solve_cg_batch(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT n
   return k;
 }
 
-/* ---- solvePCG, solvePCGSGS --------------------------------------------------------------- */
-/* solveCG with the Jacobi preconditioner (sb_pcg_*), or with symmetric Gauss-Seidel by multicolouring in its place
- * (sgs).  The lines solveCG prints while iterating are printed afterwards from the recorded r.r history, indexed as
- * solveCG's own; the SGS solve names its preconditioner and colour count first. */
-/* solves with the handle, prints, releases it and the vectors */
+/* ---- solvePCG and its preconditioners -------------------------------------------------------- */
+/* solveCG with a preconditioner (sb_pcg_*): solves with the handle, prints solveCG's lines afterwards from the
+ * recorded r.r history, indexed as solveCG's own, releases the handle and the vectors */
 static int run_pcg(Comm* comm, Parameter* param, sb_pcg* s, double* b, double* xexact)
 {
   const int itermax = param->itermax, cap = itermax + 2;
@@ -326,6 +317,18 @@ typedef struct {
   const double** gval;
   double* gms;
 } pcg_levels;
+/* room for a hierarchy of up to maxL levels, ms_per_level stage times each; L is set once it is built */
+static void pcg_levels_alloc(pcg_levels* H, int fmt, int maxL, int ms_per_level)
+{
+  memset(H, 0, sizeof *H);
+  H->fmt  = fmt;
+  H->mats = (const void**)calloc((size_t)maxL, sizeof *H->mats);
+  H->maps = (const CG_UINT**)calloc((size_t)maxL, sizeof *H->maps);
+  H->gptr = (const uint64_t**)calloc((size_t)maxL, sizeof *H->gptr);
+  H->gcol = (const CG_UINT**)calloc((size_t)maxL, sizeof *H->gcol);
+  H->gval = (const double**)calloc((size_t)maxL, sizeof *H->gval);
+  H->gms  = (double*)calloc((size_t)ms_per_level * (size_t)maxL, sizeof *H->gms);
+}
 static void pcg_levels_free(pcg_levels* H)
 {
   if (H->hierarchy) sbh_mg_hierarchy_free(H->hierarchy, H->fmt, H->L);
@@ -338,40 +341,45 @@ static void mg_refuse(const char* msg)
   fprintf(stderr, "%s\n", msg);
   exit(EXIT_FAILURE);
 }
+/* the Chebyshev-smoothed V-cycle over the L levels of H with the prolongations ptr, col, val and the restriction's scale omega
+ * between every two levels; steps per smoothing, 0: the default 2 (ratio 4) */
+static sb_pcg* create_mg_poly(const sb_matrix* m, const double* b, const double* xexact, const pcg_levels* H, const uint64_t* const* ptr,
+    const CG_UINT* const* col, const double* const* val, double omega, int steps)
+{
+  double* om = (double*)calloc((size_t)H->L, sizeof *om);
+  for (int l = 0; l + 1 < H->L; l++) om[l] = omega;
+  sb_pcg* s = sb_pcg_create_mg_poly(m, NULL, b, xexact, H->L - 1, (const sb_matrix* const*)H->mats, ptr, (const uint32_t* const*)col, val, om,
+      steps ? steps : 2, 0, 0.0, 0.0);
+  free(om);
+  return s;
+}
 
 /* The V-cycle handles on the generated grid's own hierarchy (sbh_mg.c), with their "Preconditioner: ..." line.
- * levels: L, or 0 for the deepest of up to 4 the grid allows.  fw 0: injection; fw 1: the trilinear prolongations and omega = 0.5
- *  in the injection maps' place; fw 2: those prolongations with omega = 0.25 and the Chebyshev polynomial (steps per
- * smoothing; 0: the default 2; ratio 4) as the smoother; fw 3: fw 2 on Galerkin coarse operators formed on the
- * device, omega = 1.0 */
+ * spec->levels: L, or 0 for the deepest of up to 4 the grid allows.  mg: injection.  mgfw: the trilinear prolongations and omega =
+ * 0.5 in the injection maps' place.  mgpoly: those prolongations with omega = 0.25 and the Chebyshev polynomial as the
+ * smoother, or (SBH_COARSE_GALERKIN) the same on Galerkin coarse operators formed on the device, omega = 1.0
+ *  */
 static sb_pcg* build_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, const double* b, const double* xexact, int fmt, CG_UINT C,
-    CG_UINT sigma, int levels, int fw, int steps, pcg_levels* H)
+    CG_UINT sigma, const sbh_precond_spec* spec, pcg_levels* H)
 {
-  if (strcmp(param->filename, "generate") != 0 && strcmp(param->filename, "generate7P") != 0)
+  if (!sbh_is_generated(param))
     mg_refuse("MG: needs the grid: the hierarchy is the generator's on coarser grids, and the matrix was read from a file "
               "(sb_pcg_create_mg takes a caller's own hierarchy)");
   if (comm->size > 1) mg_refuse("MG: runs on one rank");
   char why[256];
-  const int L = sbh_mg_levels(param->nx, param->ny, param->nz, levels, why, sizeof why);
+  const int L = sbh_mg_levels(param->nx, param->ny, param->nz, spec->levels, why, sizeof why);
   if (!L) mg_refuse(why);
-  const void** mats    = (const void**)calloc((size_t)L, sizeof *mats);
-  const CG_UINT** maps = (const CG_UINT**)calloc((size_t)L, sizeof *maps);
-  const uint64_t** gptr = (const uint64_t**)calloc((size_t)L, sizeof *gptr);
-  const CG_UINT** gcol  = (const CG_UINT**)calloc((size_t)L, sizeof *gcol);
-  const double** gval   = (const double**)calloc((size_t)L, sizeof *gval);
-  double* gms           = (double*)calloc(2 * (size_t)L, sizeof *gms);
-  void* hierarchy = fw == 3 ? sbh_mg_hierarchy_build_galerkin(param, dev_matrix, fmt, C, sigma, L, mats, gptr, gcol, gval, gms)
-                            : sbh_mg_hierarchy_build(param, fmt, C, sigma, L, mats, maps);
-  const pcg_levels built = { hierarchy, fmt, L, mats, maps, gptr, gcol, gval, gms };
-  *H                     = built;
+  const sb_matrix* m = (const sb_matrix*)dev_matrix;
+  const int poly     = spec->kind == SBH_PRECOND_MGPOLY;
+  const int galerkin = poly && spec->coarse == SBH_COARSE_GALERKIN;
+  pcg_levels_alloc(H, fmt, L, 2);
+  H->hierarchy = galerkin ? sbh_mg_hierarchy_build_galerkin(param, dev_matrix, fmt, C, sigma, L, H->mats, H->gptr, H->gcol, H->gval, H->gms)
+                          : sbh_mg_hierarchy_build(param, fmt, C, sigma, L, H->mats, H->maps);
+  H->L = L;
   sb_pcg* s;
-  if (fw == 3) {
-    double* omega = (double*)calloc((size_t)L, sizeof *omega);
-    for (int l = 0; l + 1 < L; l++) omega[l] = 1.0;
-    s = sb_pcg_create_mg_poly((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats,
-        (const uint64_t* const*)gptr, (const uint32_t* const*)gcol, (const double* const*)gval, omega, steps ? steps : 2, 0, 0.0, 0.0);
-    free(omega);
-  } else if (fw) {
+  if (galerkin) {
+    s = create_mg_poly(m, b, xexact, H, H->gptr, H->gcol, H->gval, 1.0, spec->steps);
+  } else if (spec->kind != SBH_PRECOND_MG) {
     uint64_t** ptr  = (uint64_t**)calloc((size_t)L, sizeof *ptr);
     CG_UINT** col   = (CG_UINT**)calloc((size_t)L, sizeof *col);
     double** val    = (double**)calloc((size_t)L, sizeof *val);
@@ -380,59 +388,50 @@ static sb_pcg* build_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, cons
     for (int l = 0; l + 1 < L; l++, nx /= 2, ny /= 2, nz /= 2) {
       const size_t n = (size_t)nx * ny * nz;
       ptr[l] = (uint64_t*)malloc((n + 1) * sizeof(uint64_t)), col[l] = (CG_UINT*)malloc(8 * n * sizeof(CG_UINT));
-      val[l] = (double*)malloc(8 * n * sizeof(double)), omega[l] = fw == 2 ? 0.25 : 0.5;
+      val[l] = (double*)malloc(8 * n * sizeof(double)), omega[l] = 0.5;
       sbh_mg_trilinear(nx, ny, nz, ptr[l], col[l], val[l]);
     }
-    if (fw == 2)
-      s = sb_pcg_create_mg_poly((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats,
-          (const uint64_t* const*)ptr, (const uint32_t* const*)col, (const double* const*)val, omega, steps ? steps : 2, 0, 0.0, 0.0);
+    if (poly)
+      s = create_mg_poly(m, b, xexact, H, (const uint64_t* const*)ptr, (const CG_UINT* const*)col, (const double* const*)val, 0.25, spec->steps);
     else
-      s = sb_pcg_create_mg_p((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats,
-          (const uint64_t* const*)ptr, (const uint32_t* const*)col, (const double* const*)val, omega);
+      s = sb_pcg_create_mg_p(m, NULL, b, xexact, L - 1, (const sb_matrix* const*)H->mats, (const uint64_t* const*)ptr,
+          (const uint32_t* const*)col, (const double* const*)val, omega);
     for (int l = 0; l + 1 < L; l++) free(ptr[l]), free(col[l]), free(val[l]);
     free(ptr), free(col), free(val), free(omega);
   } else {
-    s = sb_pcg_create_mg((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats, maps);
+    s = sb_pcg_create_mg(m, NULL, b, xexact, L - 1, (const sb_matrix* const*)H->mats, H->maps);
   }
-  if (fw >= 2 && commIsMaster(comm)) {
+  if (poly && commIsMaster(comm)) {
     double iv[2];
     sb_pcg_mg_poly_interval(s, 0, iv);
     printf("Preconditioner: MG (V-cycle, full-weighting transfers, Chebyshev polynomial smoother%s), levels = %d, steps = %d, "
-           "lambda in [%.6g, %.6g]\n", fw == 3 ? ", Galerkin coarse operators" : "", sb_pcg_levels(s), sb_pcg_poly_steps(s), iv[0], iv[1]);
-    if (fw == 3) {
+           "lambda in [%.6g, %.6g]\n", galerkin ? ", Galerkin coarse operators" : "", sb_pcg_levels(s), sb_pcg_poly_steps(s), iv[0], iv[1]);
+    if (galerkin) {
       printf("Galerkin products P^T A P on the device, ms (A P + P^T (A P)):");
-      for (int l = 1; l < L; l++) printf(" level %d: %.3f + %.3f%s", l, gms[2 * (l - 1)], gms[2 * (l - 1) + 1], l + 1 < L ? "," : "");
+      for (int l = 1; l < L; l++) printf(" level %d: %.3f + %.3f%s", l, H->gms[2 * (l - 1)], H->gms[2 * (l - 1) + 1], l + 1 < L ? "," : "");
       printf("\n");
     }
   } else if (commIsMaster(comm))
-    printf("Preconditioner: MG (V-cycle, %smulticolour SGS smoother), levels = %d, nC = %d\n", fw ? "full-weighting transfers, " : "",
-        sb_pcg_levels(s), sb_pcg_colours(s));
+    printf("Preconditioner: MG (V-cycle, %smulticolour SGS smoother), levels = %d, nC = %d\n",
+        spec->kind == SBH_PRECOND_MGFW ? "full-weighting transfers, " : "", sb_pcg_levels(s), sb_pcg_colours(s));
   return s;
 }
 
 /* The Chebyshev-smoothed V-cycle on the smoothed-aggregation hierarchy made from the matrix alone: any square
- * matrix, theta = 0, omega_s = 4/3, omega = 1.0; levels 0: up to SBH_MG_SA_DEPTH */
+ * matrix, theta = 0, omega_s = 4/3, omega = 1.0; spec->levels 0: up to SBH_MG_SA_DEPTH */
 static sb_pcg* build_pcg_sa(Comm* comm, void* dev_matrix, CG_UINT nr, const double* b, const double* xexact, int fmt, CG_UINT C,
-    CG_UINT sigma, int levels, int steps, pcg_levels* H)
+    CG_UINT sigma, const sbh_precond_spec* spec, pcg_levels* H)
 {
   if (comm->size > 1) mg_refuse("MG: runs on one rank");
-  const int maxL        = levels ? levels : SBH_MG_SA_DEPTH;
-  const void** mats     = (const void**)calloc((size_t)maxL, sizeof *mats);
-  const uint64_t** gptr = (const uint64_t**)calloc((size_t)maxL, sizeof *gptr);
-  const CG_UINT** gcol  = (const CG_UINT**)calloc((size_t)maxL, sizeof *gcol);
-  const double** gval   = (const double**)calloc((size_t)maxL, sizeof *gval);
-  double* gms           = (double*)calloc(3 * (size_t)maxL, sizeof *gms);
-  CG_UINT* rows         = (CG_UINT*)calloc((size_t)maxL, sizeof *rows);
-  CG_UINT* rounds       = (CG_UINT*)calloc((size_t)maxL, sizeof *rounds);
-  int L                 = 1;
-  void* hierarchy = sbh_mg_hierarchy_build_sa(dev_matrix, nr, fmt, C, sigma, maxL, 0.0, 4.0 / 3.0, &L, mats, gptr, gcol, gval, rows, rounds, gms);
-  const pcg_levels built = { hierarchy, fmt, L, mats, NULL, gptr, gcol, gval, gms };
-  *H                     = built;
-  double* omega          = (double*)calloc((size_t)L, sizeof *omega);
-  for (int l = 0; l + 1 < L; l++) omega[l] = 1.0;
-  sb_pcg* s = sb_pcg_create_mg_poly((const sb_matrix*)dev_matrix, NULL, b, xexact, L - 1, (const sb_matrix* const*)mats,
-      (const uint64_t* const*)gptr, (const uint32_t* const*)gcol, (const double* const*)gval, omega, steps ? steps : 2, 0, 0.0, 0.0);
-  free(omega);
+  const int maxL  = spec->levels ? spec->levels : SBH_MG_SA_DEPTH;
+  CG_UINT* rows   = (CG_UINT*)calloc((size_t)maxL, sizeof *rows);
+  CG_UINT* rounds = (CG_UINT*)calloc((size_t)maxL, sizeof *rounds);
+  int L           = 1;
+  pcg_levels_alloc(H, fmt, maxL, 3);
+  H->hierarchy = sbh_mg_hierarchy_build_sa(dev_matrix, nr, fmt, C, sigma, maxL, 0.0, 4.0 / 3.0, &L, H->mats, H->gptr, H->gcol, H->gval, rows,
+      rounds, H->gms);
+  H->L      = L;
+  sb_pcg* s = create_mg_poly((const sb_matrix*)dev_matrix, b, xexact, H, H->gptr, H->gcol, H->gval, 1.0, spec->steps);
   if (commIsMaster(comm)) {
     double iv[2];
     sb_pcg_mg_poly_interval(s, 0, iv);
@@ -445,100 +444,43 @@ static sb_pcg* build_pcg_sa(Comm* comm, void* dev_matrix, CG_UINT nr, const doub
     printf("\n");
     printf("Aggregation set-up on the device, ms (aggregates + A T and smoothing + P^T A P):");
     for (int l = 0; l + 1 < L; l++)
-      printf(" level %d: %.3f + %.3f + %.3f%s", l, gms[3 * l], gms[3 * l + 1], gms[3 * l + 2], l + 2 < L ? "," : "");
+      printf(" level %d: %.3f + %.3f + %.3f%s", l, H->gms[3 * l], H->gms[3 * l + 1], H->gms[3 * l + 2], l + 2 < L ? "," : "");
     printf("\n");
   }
   free(rows), free(rounds);
   return s;
 }
 
-/* The one place that makes a PCG handle for the solvers below and names its preconditioner: precond 0 Jacobi (no line: the
- * driver prints it), 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly (galerkin 1: on device-formed P^T A P; 2: on the aggregation hierarchy), as -p numbers them; levels and
- * steps 0: the defaults.  H: what pcg_levels_free releases after the handle */
+/* The one place that makes a PCG handle for the solvers below and names its preconditioner (Jacobi: no line, the driver's or
+ * sbh_solve_precond's own).  H: what pcg_levels_free releases after the handle */
 static sb_pcg* build_pcg(Comm* comm, Parameter* param, void* dev_matrix, const double* b, const double* xexact, int fmt, CG_UINT C,
-    CG_UINT sigma, int precond, int levels, int steps, int galerkin, pcg_levels* H)
+    CG_UINT sigma, const sbh_precond_spec* spec, pcg_levels* H)
 {
   memset(H, 0, sizeof *H);
   const sb_matrix* m = (const sb_matrix*)dev_matrix;
   sb_pcg* s;
-  switch (precond) {
-  case 0: return sb_pcg_create(m, NULL, b, xexact, NULL);
-  case 1:
+  switch (spec->kind) {
+  case SBH_PRECOND_JACOBI: return sb_pcg_create(m, NULL, b, xexact, NULL);
+  case SBH_PRECOND_SGS:
     s = sb_pcg_create_sgs(m, NULL, b, xexact);
     if (commIsMaster(comm)) printf("Preconditioner: SGS (multicolour symmetric Gauss-Seidel), nC = %d\n", sb_pcg_colours(s));
     return s;
-  case 4: {
-    s = sb_pcg_create_poly(m, NULL, b, xexact, steps ? steps : 3, 0.0, 0.0);
+  case SBH_PRECOND_POLY: {
+    s = sb_pcg_create_poly(m, NULL, b, xexact, spec->steps ? spec->steps : 3, 0.0, 0.0);
     double iv[2];
     sb_pcg_poly_interval(s, iv);
     if (commIsMaster(comm))
       printf("Preconditioner: Chebyshev polynomial, steps = %d, lambda in [%.6g, %.6g]\n", sb_pcg_poly_steps(s), iv[0], iv[1]);
     return s;
   }
-  case 2: return build_pcg_mg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, levels, 0, 0, H);
-  case 3: return build_pcg_mg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, levels, 1, 0, H);
-  case 5:
-    if (galerkin == 2) return build_pcg_sa(comm, dev_matrix, sb_matrix_nr(m), b, xexact, fmt, C, sigma, levels, steps, H);
-    return build_pcg_mg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, levels, galerkin ? 3 : 2, steps, H);
+  case SBH_PRECOND_MGPOLY:
+    if (spec->coarse == SBH_COARSE_AGGREGATION) return build_pcg_sa(comm, dev_matrix, sb_matrix_nr(m), b, xexact, fmt, C, sigma, spec, H);
+    /* fall through */
+  case SBH_PRECOND_MG:
+  case SBH_PRECOND_MGFW: return build_pcg_mg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, spec, H);
   }
-  fprintf(stderr, "preconditioner %d: 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly\n", precond);
+  fprintf(stderr, "preconditioner %d: 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly\n", spec->kind);
   exit(EXIT_FAILURE);
-}
-
-static int solve_pcg_with(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
-    CG_UINT sigma, int precond, int levels, int steps, int galerkin)
-{
-  dp_only("PCG: double precision only\n");
-  double *b, *xexact;
-  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
-  pcg_levels H;
-  sb_pcg* s   = build_pcg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, precond, levels, steps, galerkin, &H);
-  const int k = run_pcg(comm, param, s, b, xexact);
-  pcg_levels_free(&H);
-  return k;
-}
-int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
-{
-  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, 0, 0, 0, 0, 0, 0, 0);
-}
-int sbh_solve_pcg_sgs(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
-{
-  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, 0, 0, 0, 1, 0, 0, 0);
-}
-/* ... or with the Chebyshev polynomial in D^-1 A; steps 0: the default.  Names its steps and interval first */
-int sbh_solve_pcg_poly(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int steps)
-{
-  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, 0, 0, 0, 4, 0, steps, 0);
-}
-
-/* ---- solvePCGMG --------------------------------------------------------------------------- */
-/* solvePCGSGS with the multigrid V-cycle around the smoother (build_pcg_mg) */
-int sbh_solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
-    CG_UINT sigma, int levels)
-{
-  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 2, levels, 0, 0);
-}
-int sbh_solve_pcg_mgfw(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
-    CG_UINT sigma, int levels)
-{
-  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 3, levels, 0, 0);
-}
-int sbh_solve_pcg_mgpoly(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
-    CG_UINT sigma, int levels, int steps)
-{
-  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 5, levels, steps, 0);
-}
-
-int sbh_solve_pcg_mgpoly_galerkin(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt,
-    CG_UINT C, CG_UINT sigma, int levels, int steps)
-{
-  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 5, levels, steps, 1);
-}
-
-int sbh_solve_pcg_mgpoly_sa(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
-    CG_UINT sigma, int levels, int steps)
-{
-  return solve_pcg_with(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 5, levels, steps, 2);
 }
 
 /* ---- solveBiCGStab ----------------------------------------------------------------------- */
@@ -558,49 +500,104 @@ static int run_bicgstab(Comm* comm, Parameter* param, sb_bicgstab* s, double* b,
   free(rr), free(b), free(xexact);
   return k;
 }
-int sbh_solve_bicgstab(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
-{
-  dp_only("BiCGStab: double precision only\n");
-  double *b, *xexact;
-  init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
-  return run_bicgstab(comm, param, sb_bicgstab_create((const sb_matrix*)dev_matrix, NULL, b, xexact, 1, NULL), b, xexact);
-}
-/* ---- solveBiCGStabPrecond, solveGMRESPrecond ------------------------------------------------ */
-/* BiCGStab with the preconditioner plan of a PCG handle in the diagonal's place (sb_bicgstab_create_pre), or (gmres)
- * GMRES(restart) right-preconditioned by it (sb_gmres_create_pre).  The handle is build_pcg's, as the
- * sbh_solve_pcg_* entries make theirs, with the same "Preconditioner: ..." line; precond 0 is Jacobi, which GMRES alone takes
- * here (BiCGStab's own diagonal is sbh_solve_bicgstab) and whose line is printed here.  GMRES's printed residuals are the
+
+/* ---- the one add-on solve: every sbh_solve_pcg*, sbh_solve_bicgstab* and sbh_solve_gmres* entry ------------------ */
+/* PCG makes its handle with build_pcg and runs it (no spec: Jacobi).  BiCGStab and GMRES(restart) without a spec are the solvers
+ * alone; with one they borrow the preconditioner plan of a PCG handle (sb_bicgstab_create_pre; sb_gmres_create_pre,
+ * DESIGN 4.20), built by the same build_pcg with the same "Preconditioner: ..." line and freed after the solver.  Jacobi is a kind
+ * for GMRES alone (BiCGStab's own diagonal is its default) and its line is printed here.  GMRES's printed residuals are the
  * estimates of the preconditioned operator's loop, which are those of b - A x with x = M^-1 u */
-static int solve_borrowing(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
-    CG_UINT sigma, int gmres, int restart, int precond, int levels, int steps, int galerkin)
+int sbh_solve_precond(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int solver, int restart, const sbh_precond_spec* spec)
 {
-  dp_only(gmres ? "GMRES: double precision only\n" : "BiCGStab: double precision only\n");
-  if (comm->size > 1) mg_refuse(gmres ? "GMRES: runs on one rank" : "BiCGStab: runs on one rank");
-  if (precond < (gmres ? 0 : 1) || precond > 5)
-    mg_refuse(gmres ? "GMRES: the preconditioners are 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly"
-                    : "BiCGStab: the plan preconditioners are 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly");
+  static const sbh_precond_spec jacobi = { SBH_PRECOND_JACOBI, 0, 0, SBH_COARSE_REGENERATED };
+  const int gmres = solver == SBH_SOLVER_GMRES, pcg = solver == SBH_SOLVER_PCG;
+  const sb_matrix* m = (const sb_matrix*)dev_matrix;
+  if (pcg && !spec) spec = &jacobi;
+  dp_only(pcg ? "PCG: double precision only\n" : gmres ? "GMRES: double precision only\n" : "BiCGStab: double precision only\n");
+  if (!pcg && spec) {
+    if (comm->size > 1) mg_refuse(gmres ? "GMRES: runs on one rank" : "BiCGStab: runs on one rank");
+    if (spec->kind < (gmres ? SBH_PRECOND_JACOBI : SBH_PRECOND_SGS) || spec->kind > SBH_PRECOND_MGPOLY)
+      mg_refuse(gmres ? "GMRES: the preconditioners are 0 jacobi, 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly"
+                      : "BiCGStab: the plan preconditioners are 1 sgs, 2 mg, 3 mgfw, 4 poly, 5 mgpoly");
+  }
   double *b, *xexact;
   init_vectors_dp(param, nr, rowNnz, 1, &b, &xexact);
+  if (!spec)
+    return gmres ? run_gmres(comm, param, sb_gmres_create(m, NULL, b, xexact, restart), b, xexact)
+                 : run_bicgstab(comm, param, sb_bicgstab_create(m, NULL, b, xexact, 1, NULL), b, xexact);
   pcg_levels H;
-  sb_pcg* M = build_pcg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, precond, levels, steps, galerkin, &H);
-  if (precond == 0 && commIsMaster(comm)) printf("Preconditioner: Jacobi (diagonal), nC = 0\n");
-  const sb_matrix* m = (const sb_matrix*)dev_matrix;
-  const int k = gmres ? run_gmres(comm, param, sb_gmres_create_pre(m, NULL, b, xexact, restart, M), b, xexact)
+  sb_pcg* M = build_pcg(comm, param, dev_matrix, b, xexact, fmt, C, sigma, spec, &H);
+  if (!pcg && spec->kind == SBH_PRECOND_JACOBI && commIsMaster(comm)) printf("Preconditioner: Jacobi (diagonal), nC = 0\n");
+  const int k = pcg ? run_pcg(comm, param, M, b, xexact) /* (releases M) */
+              : gmres ? run_gmres(comm, param, sb_gmres_create_pre(m, NULL, b, xexact, restart, M), b, xexact)
                       : run_bicgstab(comm, param, sb_bicgstab_create_pre(m, NULL, b, xexact, M), b, xexact);
-  sb_pcg_free(M);
+  if (!pcg) sb_pcg_free(M);
   pcg_levels_free(&H);
   return k;
+}
+
+/* the entries of before: each names its solver and spec (the one-level preconditioners rebuild no matrix: no fmt, C, sigma) */
+#define SPEC(...) &(const sbh_precond_spec){ __VA_ARGS__ }
+int sbh_solve_pcg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
+{
+  return sbh_solve_precond(comm, param, dev_matrix, nr, rowNnz, 0, 0, 0, SBH_SOLVER_PCG, 0, NULL);
+}
+int sbh_solve_pcg_sgs(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
+{
+  return sbh_solve_precond(comm, param, dev_matrix, nr, rowNnz, 0, 0, 0, SBH_SOLVER_PCG, 0, SPEC(SBH_PRECOND_SGS, 0, 0, 0));
+}
+int sbh_solve_pcg_poly(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int steps)
+{
+  return sbh_solve_precond(comm, param, dev_matrix, nr, rowNnz, 0, 0, 0, SBH_SOLVER_PCG, 0, SPEC(SBH_PRECOND_POLY, 0, steps, 0));
+}
+int sbh_solve_pcg_mg(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int levels)
+{
+  return sbh_solve_precond(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, SBH_SOLVER_PCG, 0, SPEC(SBH_PRECOND_MG, levels, 0, 0));
+}
+int sbh_solve_pcg_mgfw(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int levels)
+{
+  return sbh_solve_precond(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, SBH_SOLVER_PCG, 0, SPEC(SBH_PRECOND_MGFW, levels, 0, 0));
+}
+int sbh_solve_pcg_mgpoly(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int levels, int steps)
+{
+  return sbh_solve_precond(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, SBH_SOLVER_PCG, 0,
+      SPEC(SBH_PRECOND_MGPOLY, levels, steps, SBH_COARSE_REGENERATED));
+}
+int sbh_solve_pcg_mgpoly_galerkin(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt,
+    CG_UINT C, CG_UINT sigma, int levels, int steps)
+{
+  return sbh_solve_precond(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, SBH_SOLVER_PCG, 0,
+      SPEC(SBH_PRECOND_MGPOLY, levels, steps, SBH_COARSE_GALERKIN));
+}
+int sbh_solve_pcg_mgpoly_sa(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
+    CG_UINT sigma, int levels, int steps)
+{
+  return sbh_solve_precond(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, SBH_SOLVER_PCG, 0,
+      SPEC(SBH_PRECOND_MGPOLY, levels, steps, SBH_COARSE_AGGREGATION));
+}
+int sbh_solve_bicgstab(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz)
+{
+  return sbh_solve_precond(comm, param, dev_matrix, nr, rowNnz, 0, 0, 0, SBH_SOLVER_BICGSTAB, 0, NULL);
 }
 int sbh_solve_bicgstab_precond(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
     CG_UINT sigma, int precond, int levels, int steps, int galerkin)
 {
-  return solve_borrowing(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 0, 0, precond, levels, steps, galerkin);
+  return sbh_solve_precond(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, SBH_SOLVER_BICGSTAB, 0, SPEC(precond, levels, steps, galerkin));
+}
+int sbh_solve_gmres(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int restart)
+{
+  return sbh_solve_precond(comm, param, dev_matrix, nr, rowNnz, 0, 0, 0, SBH_SOLVER_GMRES, restart, NULL);
 }
 int sbh_solve_gmres_precond(Comm* comm, Parameter* param, void* dev_matrix, CG_UINT nr, const CG_UINT* rowNnz, int fmt, CG_UINT C,
     CG_UINT sigma, int restart, int precond, int levels, int steps, int galerkin)
 {
-  return solve_borrowing(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, 1, restart, precond, levels, steps, galerkin);
+  return sbh_solve_precond(comm, param, dev_matrix, nr, rowNnz, fmt, C, sigma, SBH_SOLVER_GMRES, restart, SPEC(precond, levels, steps, galerkin));
 }
+#undef SPEC
 
 /* ---- profiler table: src/profiler.c:11-141 ----------------------------------------------- */
 static const char* const kLabel[NUMREGIONS] = { "waxpby:  ", "spMVM:   ", "ddot:    ", "comm:    " };

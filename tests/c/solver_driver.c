@@ -5,6 +5,9 @@
  *   -DSOLVER_BATCH     solveCGBatch   (nrhs CG solves on one pass over the matrix per loop body)
  *   -DSOLVER_PCG       solvePCG       (CG with the Jacobi preconditioner)
  *   -DSOLVER_BICGSTAB  solveBiCGStab  (BiCGStab with the Jacobi preconditioner)
+ *   -DSOLVER_PCG_SGS, _MG, _MGFW, _POLY, _MGPOLY, _MGPOLY_GALERKIN, _MGPOLY_SA
+ *                      solvePCGSGS, solvePCGMG, solvePCGMGFW, solvePCGPoly, solvePCGMGPoly, solvePCGMGPolyGalerkin, solvePCGMGPolySA
+ *                      (CG with that preconditioner at its defaults)
  * Usage: solver_driver <n | file.mtx> <itermax> <eps> [<restart> | <nrhs>]: a first argument that starts with a digit generates
  * the n^3 grid, any other is read as a Matrix Market file; the fourth argument goes with GMRES (restart) and the batch (nrhs).
  * Built twice per solver: -DCRS and -DSCS.
@@ -31,7 +34,26 @@
 #define EXTRA 0
 #define SOLVE(comm, param, sm, extra) solveBiCGStab(comm, param, sm)
 #else
-#error "define one of SOLVER_GMRES, SOLVER_BATCH, SOLVER_PCG, SOLVER_BICGSTAB"
+#if defined(SOLVER_PCG_SGS)
+#define PCG_ENTRY solvePCGSGS
+#elif defined(SOLVER_PCG_MG)
+#define PCG_ENTRY solvePCGMG
+#elif defined(SOLVER_PCG_MGFW)
+#define PCG_ENTRY solvePCGMGFW
+#elif defined(SOLVER_PCG_POLY)
+#define PCG_ENTRY solvePCGPoly
+#elif defined(SOLVER_PCG_MGPOLY)
+#define PCG_ENTRY solvePCGMGPoly
+#elif defined(SOLVER_PCG_MGPOLY_GALERKIN)
+#define PCG_ENTRY solvePCGMGPolyGalerkin
+#elif defined(SOLVER_PCG_MGPOLY_SA)
+#define PCG_ENTRY solvePCGMGPolySA
+#else
+#error "define one of SOLVER_GMRES, SOLVER_BATCH, SOLVER_PCG, SOLVER_BICGSTAB, SOLVER_PCG_<preconditioner>"
+#endif
+#define USAGE "<n | file.mtx> <itermax> <eps>"
+#define EXTRA 0
+#define SOLVE(comm, param, sm, extra) PCG_ENTRY(comm, param, sm)
 #endif
 
 int main(int argc, char** argv)

@@ -113,14 +113,35 @@ def test_hostapi_keywords_and_refusals():
 
 
 def test_driver_help_and_messages_name_a():
-    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-    help_text = "".join(re.findall(r'^\s+"(.*)"\s*;?\s*$', src.split("kHelp =")[1].split(";")[0], flags=re.M))
+    import driver_options as opts
+    help_text = opts.help_text()
     assert re.search(r"-a\b.*Smoothed-aggregation coarsening.*-p mgpoly.*any matrix", help_text)
     assert re.search(r"-g\b.*Galerkin coarse operators.*-p mgpoly", help_text) and "-C <int>" in help_text  # the help text is still whole
-    assert re.search(r'getopt\(argc, argv, "[^"]*l:a[^"]*"\)', src)
-    both = src.index("it does not go with -g")
-    alone = src.index("-a (smoothed-aggregation coarsening) goes with -p mgpoly only")
-    assert max(both, alone) < src.index("commPrintBanner(&comm);") < src.index("sbh_init_matrix(&comm, &param, &m);")  # before the set-up
-    assert re.search(r"\(precond == 2 \|\| precond == 3 \|\| precond == 5\) && !aggregation", src)  # a file has no grid, and -a asks for none
-    assert "solvePCGMGPolySA(&comm, &param, &sm)" in src and "sbh_solve_pcg_mgpoly_sa(" in src
-    assert "solvePCGMGPolyGalerkin(&comm, &param, &sm)" in src and "solvePCGMGPoly(&comm, &param, &sm)" in src  # the existing paths
+    size, MGPOLY, A = opts.SIZE, opts.KIND["mgpoly"], opts.COARSE["aggregation"]
+    # -a is a switch of its own, takes no argument, and lands in the spec's coarse operators: at the defaults (solvePCGMGPolySA's
+    # spec; the symbol itself runs in test_gpu_aggregation_driver.py) and beside -l and -d, by -p and by -P
+    for head, byP in ((["-t", "pcg", "-p"], 0), (["-t", "bicgstab", "-P"], 1), (["-t", "gmres", "-P"], 1)):
+        for extra, levels, steps in (([], 0, 0), (["-l", "3"], 3, 0), (["-d", "1"], 0, 1), (["-l", "2", "-d", "4"], 2, 4)):
+            p = opts.accepted(head + ["mgpoly", "-a"] + extra + size)
+            assert p.spec == (MGPOLY, levels, steps, A) and p.byP == byP and p.type == opts.TYPE[head[1]]
+    # the existing paths
+    assert opts.accepted(["-t", "pcg", "-p", "mgpoly", "-g"] + size).spec == (MGPOLY, 0, 0, opts.COARSE["galerkin"])
+    assert opts.accepted(["-t", "pcg", "-p", "mgpoly"] + size).spec == (MGPOLY, 0, 0, opts.COARSE["regenerated"])
+    for args, msg in ((["-t", "pcg", "-p", "mgpoly", "-a", "-g"], "it does not go with -g"),
+                      (["-t", "bicgstab", "-P", "mgpoly", "-g", "-a"], "it does not go with -g"),
+                      (["-t", "pcg", "-p", "mgfw", "-a"], "-a (smoothed-aggregation coarsening) goes with -p mgpoly only"),
+                      (["-t", "pcg", "-a"], "-a (smoothed-aggregation coarsening) goes with -p mgpoly only"),
+                      (["-a"], "-a (smoothed-aggregation coarsening) goes with -p mgpoly only")):
+        opts.refused(args + ["-i", "10"] + size, msg)
+    # a file has no grid, and -a asks for none: any matrix, and levels that no grid rule bounds
+    for head in (["-t", "pcg", "-p"], ["-t", "bicgstab", "-P"], ["-t", "gmres", "-P"]):
+        opts.refused(head + ["mgpoly", "-m", "a.mtx"], "-%s mgpoly needs the grid: its hierarchy is the generated matrix's on coarser grids, not -m a.mtx\n"
+                     % head[2][1])
+        p = opts.accepted(head + ["mgpoly", "-a", "-m", "a.mtx"])
+        assert p.spec == (MGPOLY, 0, 0, A) and p.filename == "a.mtx"
+    for kind in ("mg", "mgfw"):
+        opts.refused(["-t", "pcg", "-p", kind, "-m", "a.mtx"], "-p %s needs the grid" % kind)
+    opts.refused(["-t", "pcg", "-p", "mgpoly", "-l", "6"] + size, "6 levels")
+    assert opts.accepted(["-t", "pcg", "-p", "mgpoly", "-a", "-l", "6"] + size).spec == (MGPOLY, 6, 0, A)
+    opts.refused(["-t", "pcg", "-p", "mgpoly", "-a", "-i", "10"] + size, "PCG: double precision only", precision="single")
+    assert opts.no_device_was_touched()  # before the set-up: the parser has no way to a device

@@ -62,10 +62,15 @@ def test_hostapi_bicgstab_refuses_single_precision_and_has_its_methods():
 
 
 def test_driver_help_names_bicgstab_and_the_sp_drivers_refuse_it():
-    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-    help_text = "".join(re.findall(r'^\s+"(.*)"\s*;?\s*$', src.split("kHelp =")[1].split(";")[0], flags=re.M))
-    assert re.search(r"-t <bench type>.*\bbicgstab\b", help_text) and re.search(r"-t <bench type>.*\bpcg\b", help_text)
-    assert 'strcmp(optarg, "bicgstab") == 0' in src and "BiCGStab: double precision only" in src and "Test type: BiCGStab" in src
-    assert 'strcmp(optarg, "cheb")' not in src  # still an unknown type
+    import driver_options as opts
+    help_text = opts.help_text()
+    assert re.search(r"-t <bench type>.*\bbicgstab\b", help_text, re.S) and re.search(r"-t <bench type>.*\bpcg\b", help_text)  # (its two lines)
+    size = ["-x", "8", "-y", "8", "-z", "8", "-i", "10"]
+    p = opts.accepted(["-t", "bicgstab"] + size)
+    assert p.type == opts.TYPE["bicgstab"] and p.spec == (opts.KIND[None], 0, 0, 0) and not p.byP  # no -P: solveBiCGStab's own diagonal
+    opts.refused(["-t", "bicgstab"] + size, "BiCGStab: double precision only\n", precision="single")
+    opts.refused(["-t", "cheb"] + size, "Unknown solver type cheb\n", stream="stdout")  # still an unknown type
+    opts.refused(["-t", "bicgstab", "-n", "2"] + size, "-t cg only")
+    assert opts.no_device_was_touched()
     solver = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_solver.c")).read()
     assert "sbh_solve_bicgstab" in solver and "BiCGStab: double precision only" in solver

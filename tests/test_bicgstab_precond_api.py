@@ -76,15 +76,37 @@ def test_hostapi_refusals_before_the_library_and_methods():
 
 
 def test_driver_help_names_P_and_the_refusals_are_in_place():
-    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-    help_text = "".join(re.findall(r'^\s+"(.*)"\s*;?\s*$', src.split("kHelp =")[1].split(";")[0], flags=re.M))
+    import driver_options as opts
+    help_text = opts.help_text()
     assert re.search(r"-P <sgs\|mg\|mgfw\|poly\|mgpoly>.*-t bicgstab", help_text)
     for whole in (r"-p <jacobi\|sgs>.*Default jacobi", r"-g\b.*Galerkin coarse operators.*-p mgpoly", r"-d <int>   Steps of -p poly",
                   r"-l <int>   Levels of -p mg", r"-C <int>", r"-s <int>"):
         assert re.search(whole, help_text), whole  # the help text is otherwise whole
-    assert "goes with -t bicgstab only" in src and "goes with -t pcg only" in src
-    assert src.index("goes with -t bicgstab only") < src.index("commPrintBanner(&comm);")  # before the set-up
-    assert "solveBiCGStabPrecond(&comm, &param, &sm, precond)" in src and "sbh_solve_bicgstab_precond(" in src
+    size, K, C = ["-x", "8", "-y", "8", "-z", "8", "-i", "10"], opts.KIND, opts.COARSE
+    # every plan at its defaults is solveBiCGStabPrecond's spec (the symbol itself runs in test_gpu_bicgstab_precond_driver.py);
+    # -l, -d, -g and -a are the other path
+    for name in ("sgs", "mg", "mgfw", "poly", "mgpoly"):
+        p = opts.accepted(["-t", "bicgstab", "-P", name] + size)
+        assert p.type == opts.TYPE["bicgstab"] and p.byP == 1 and p.spec == (K[name], 0, 0, 0)
+    for extra, spec in ((["-P", "mg", "-l", "2"], (K["mg"], 2, 0, 0)), (["-P", "mgfw", "-l", "3"], (K["mgfw"], 3, 0, 0)),
+                        (["-P", "poly", "-d", "3"], (K["poly"], 0, 3, 0)), (["-P", "mgpoly", "-l", "2", "-d", "1"], (K["mgpoly"], 2, 1, 0)),
+                        (["-P", "mgpoly", "-g", "-d", "1"], (K["mgpoly"], 0, 1, C["galerkin"])),
+                        (["-P", "mgpoly", "-a", "-d", "2"], (K["mgpoly"], 0, 2, C["aggregation"]))):
+        p = opts.accepted(["-t", "bicgstab"] + extra + size)
+        assert p.byP == 1 and p.spec == spec, extra
+    for args, msg in ((["-t", "bicgstab", "-p", "sgs"], "goes with -t pcg only"),
+                      (["-t", "pcg", "-P", "sgs"], "goes with -t bicgstab only"),
+                      (["-P", "poly"], "goes with -t bicgstab only"),
+                      (["-t", "bicgstab", "-P", "jacobi"], "Unknown preconditioner jacobi (-P <sgs|mg|mgfw|poly|mgpoly>)"),
+                      (["-t", "bicgstab", "-P", "sgs", "-d", "3"], "-d <int> (the steps) goes with -p poly only"),
+                      (["-t", "bicgstab", "-P", "poly", "-l", "2"], "-l <int> (the levels) goes with -p mg only"),
+                      (["-t", "bicgstab", "-P", "poly", "-g"], "-g (Galerkin coarse operators) goes with -p mgpoly only"),
+                      (["-t", "bicgstab", "-l", "2"], "-l <int> (the levels) goes with -p mg only"),
+                      (["-t", "bicgstab", "-P", "mg", "-l", "5"], "levels"),
+                      (["-t", "bicgstab", "-P", "mgpoly", "-m", "some.mtx"], "-P mgpoly needs the grid")):
+        opts.refused(args + size, msg)
+    opts.refused(["-t", "bicgstab", "-P", "poly"] + size, "BiCGStab: double precision only", precision="single")
+    assert opts.no_device_was_touched()  # before the set-up: the parser has no way to a device
     solver = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_solver.c")).read()
     assert solver.count("sb_pcg_create_sgs(") == solver.count("sb_pcg_create_poly(") == solver.count("sb_pcg_create_mg(") == 1  # one builder
     assert "sb_bicgstab_create_pre(" in solver

@@ -56,6 +56,13 @@ def test_hostapi_batchcg_refuses_single_precision():
 
 
 def test_driver_help_names_the_option():
-    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-    assert "-n <int>   Number of right-hand sides for -t cg. Default 1." in src
-    assert re.search(r'getopt\(argc, argv, "[^"]*n:[^"]*"\)', src)
+    import driver_options as opts
+    assert "-n <int>   Number of right-hand sides for -t cg. Default 1." in opts.help_text()
+    size = ["-x", "8", "-y", "8", "-z", "8", "-i", "10"]
+    for args, nrhs in ((["-t", "cg", "-n", "4"], 4), (["-n", "4"], 4), (["-t", "cg", "-n", "3"], 3), (["-t", "cg"], 1), ([], 1)):
+        p = opts.accepted(args + size)  # -n takes an argument and lands in nrhs (a width the layer does not have is its own refusal)
+        assert p.type == opts.TYPE["cg"] and p.nrhs == nrhs
+    assert opts.accepted(["-t", "cg", "-n", "4"] + size, precision="single").nrhs == 4  # (refused by the solver, not by the options)
+    for t in ("spmv", "gmres"):
+        opts.refused(["-n", "2", "-t", t] + size, "-n <int> (several right-hand sides) goes with -t cg only\n")
+    assert opts.no_device_was_touched()

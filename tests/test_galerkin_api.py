@@ -119,13 +119,19 @@ def test_hostapi_keywords_and_refusals():
 
 
 def test_driver_help_and_messages_name_g():
-    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-    help_text = "".join(re.findall(r'^\s+"(.*)"\s*;?\s*$', src.split("kHelp =")[1].split(";")[0], flags=re.M))
+    import driver_options as opts
+    help_text = opts.help_text()
     assert re.search(r"-g\b.*Galerkin coarse operators.*-p mgpoly", help_text)
     assert re.search(r"-p <jacobi\|sgs>.*Default jacobi", help_text) and "-C <int>" in help_text  # the help text is still whole
-    assert re.search(r'getopt\(argc, argv, "[^"]*d:g"\)', src)
-    refusal = src.index("-g (Galerkin coarse operators) goes with -p mgpoly only")
-    assert re.search(r"if \(galerkin && precond != 5\) \{\s*fprintf\(stderr, \"-g \(Galerkin[^;]*;\s*return 1;", src)
-    assert refusal < src.index("commPrintBanner(&comm);") < src.index("sbh_init_matrix(&comm, &param, &m);")  # before the set-up
-    assert "solvePCGMGPolyGalerkin(&comm, &param, &sm)" in src and "sbh_solve_pcg_mgpoly_galerkin(" in src
-    assert "solvePCGMGPoly(&comm, &param, &sm)" in src and "sbh_solve_pcg_mgpoly(" in src  # the existing path is still there
+    SIZE, MGPOLY, G = opts.SIZE + ["-i", "10"], opts.KIND["mgpoly"], opts.COARSE["galerkin"]
+    # -g is a switch of its own, takes no argument, and lands in the spec's coarse operators: at the defaults
+    # (solvePCGMGPolyGalerkin's spec; the symbol itself runs in test_gpu_galerkin_driver.py) and beside -l and -d, by -p and by -P
+    for head, byP in ((["-t", "pcg", "-p"], 0), (["-t", "bicgstab", "-P"], 1), (["-t", "gmres", "-P"], 1)):
+        for extra, levels, steps in (([], 0, 0), (["-l", "3"], 3, 0), (["-d", "1"], 0, 1), (["-l", "2", "-d", "4"], 2, 4)):
+            p = opts.accepted(head + ["mgpoly", "-g"] + extra + SIZE)
+            assert p.spec == (MGPOLY, levels, steps, G) and p.byP == byP and p.type == opts.TYPE[head[1]] and p.dims == (16, 16, 16)
+            assert opts.accepted(head + ["mgpoly"] + extra + SIZE).spec == (MGPOLY, levels, steps, 0)  # without it: the path of before
+    for args in (["-t", "pcg", "-p", "mgfw", "-g"], ["-t", "pcg", "-g"], ["-g"], ["-t", "pcg", "-p", "poly", "-g"]):
+        opts.refused(args + SIZE, "-g (Galerkin coarse operators) goes with -p mgpoly only\n")  # status 1, on stderr
+    opts.refused(["-t", "pcg", "-p", "mgpoly", "-g"] + SIZE, "PCG: double precision only", precision="single")
+    assert opts.no_device_was_touched()  # before the set-up: the parser has no way to a device

@@ -94,17 +94,42 @@ def test_hostapi_refusals_before_the_library_and_methods():
 
 
 def test_driver_help_names_P_for_gmres_and_the_refusals_are_in_place():
-    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-    help_text = "\n".join(re.findall(r'^\s+"(.*)"\s*;?\s*$', src.split("kHelp =")[1].split(";")[0], flags=re.M))
+    import driver_options as opts
+    help_text = opts.help_text()
     assert re.search(r"-P <sgs\|mg\|mgfw\|poly\|mgpoly>.*-t bicgstab", help_text)  # the line of before
     assert re.search(r"-t gmres.*-P jacobi", help_text)
     assert re.search(r"-r <int>   GMRES restart length", help_text)
-    assert "goes with -t bicgstab only, or as -P <jacobi|sgs|mg|mgfw|poly|mgpoly> with -t gmres" in src.replace('"\n                    "', "")
-    assert src.index("goes with -t bicgstab only") < src.index("commPrintBanner(&comm);")  # before the set-up
-    assert "Unknown preconditioner jacobi (-P <sgs|mg|mgfw|poly|mgpoly>)" in src  # -t bicgstab -P jacobi: refused as before
-    assert src.index("Unknown preconditioner jacobi") < src.index("commPrintBanner(&comm);")
-    assert "solveGMRESPrecond(&comm, &param, &sm, restart, precond)" in src and "sbh_solve_gmres_precond(" in src
-    assert "solveGMRES(&comm, &param, &sm, restart)" in src  # without -P: the call of before
+    size, K, C = ["-x", "8", "-y", "8", "-z", "8", "-i", "10"], opts.KIND, opts.COARSE
+    # every preconditioner at its defaults is solveGMRESPrecond's spec (the symbol itself runs in test_gpu_gmres_precond_driver.py);
+    # -l, -d, -g and -a are the other path; without -P: solveGMRES's call of before
+    for name in ("jacobi", "sgs", "mg", "mgfw", "poly", "mgpoly"):
+        p = opts.accepted(["-t", "gmres", "-r", "10", "-P", name] + size)
+        assert p.type == opts.TYPE["gmres"] and p.byP == 1 and p.spec == (K[name], 0, 0, 0) and p.restart == 10
+    for extra, spec in ((["-P", "mg", "-l", "2"], (K["mg"], 2, 0, 0)), (["-P", "mgfw", "-l", "3"], (K["mgfw"], 3, 0, 0)),
+                        (["-P", "poly", "-d", "3"], (K["poly"], 0, 3, 0)), (["-P", "mgpoly", "-l", "2", "-d", "1"], (K["mgpoly"], 2, 1, 0)),
+                        (["-P", "mgpoly", "-g", "-d", "1"], (K["mgpoly"], 0, 1, C["galerkin"])),
+                        (["-P", "mgpoly", "-a", "-d", "2"], (K["mgpoly"], 0, 2, C["aggregation"]))):
+        p = opts.accepted(["-t", "gmres"] + extra + size)
+        assert p.byP == 1 and p.spec == spec and p.restart == 30, extra
+    p = opts.accepted(["-t", "gmres", "-r", "12"] + size)
+    assert p.type == opts.TYPE["gmres"] and not p.byP and p.spec == (K[None], 0, 0, 0) and p.restart == 12
+    opts.refused(["-t", "cg", "-P", "sgs"] + size, "-P <sgs|mg|mgfw|poly|mgpoly> (the preconditioner of BiCGStab) goes with -t bicgstab only, or as "
+                 "-P <jacobi|sgs|mg|mgfw|poly|mgpoly> with -t gmres\n")
+    for args, msg in ((["-t", "gmres", "-p", "sgs"], "goes with -t pcg only"),
+                      (["-t", "pcg", "-P", "sgs"], "goes with -t bicgstab only"),
+                      (["-P", "poly"], "goes with -t bicgstab only"),
+                      (["-t", "pcg", "-P", "jacobi"], "Unknown preconditioner jacobi (-P <sgs|mg|mgfw|poly|mgpoly>)"),
+                      (["-t", "bicgstab", "-P", "jacobi"], "Unknown preconditioner jacobi (-P <sgs|mg|mgfw|poly|mgpoly>)"),  # refused as before
+                      (["-t", "gmres", "-P", "ilu"], "Unknown preconditioner ilu"),
+                      (["-t", "gmres", "-P", "sgs", "-d", "3"], "-d <int> (the steps) goes with -p poly only"),
+                      (["-t", "gmres", "-P", "jacobi", "-l", "2"], "-l <int> (the levels) goes with -p mg only"),
+                      (["-t", "gmres", "-P", "poly", "-g"], "-g (Galerkin coarse operators) goes with -p mgpoly only"),
+                      (["-t", "gmres", "-l", "2"], "-l <int> (the levels) goes with -p mg only"),
+                      (["-t", "gmres", "-P", "mgpoly", "-a", "-g"], "it does not go with -g"),
+                      (["-t", "gmres", "-P", "mgpoly", "-m", "some.mtx"], "-P mgpoly needs the grid")):
+        opts.refused(args + size, msg)
+    opts.refused(["-t", "gmres", "-P", "poly"] + size, "GMRES: double precision only", precision="single")
+    assert opts.no_device_was_touched()  # before the set-up: the parser has no way to a device
     solver = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_solver.c")).read()
     assert solver.count("sb_pcg_create_sgs(") == solver.count("sb_pcg_create_poly(") == solver.count("sb_pcg_create_mg(") == 1  # one builder
     assert "sb_gmres_create_pre(" in solver and solver.count("sb_gmres_solve(") == 1  # one runner for both

@@ -70,22 +70,30 @@ def test_driver_counts_are_the_goldens(gpu, name, args, tmp_path):
     assert re.search(r"^Solution performed %d iterations" % rec["k"], txt, re.M), txt[-2000:]
 
 
-def test_defaults_go_through_the_dropin_entry(gpu):
+def test_defaults_go_through_the_dropin_entry(gpu, tmp_path):
+    """solvePCGMGPolySA, run by a C caller of its own, and the driver with -a at the defaults: both the golden solve's lines"""
+    import driver_options
     hostapi.host()
-    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-    assert "k = solvePCGMGPolySA(&comm, &param, &sm);" in src
     rec = load_json("aggregation_hist.json")["solves"]["pcg_hpcg16_sell_64_256_steps2"]  # the default steps
+    eps = "%.17g" % float.fromhex(rec["eps"])
     for fmt, exe, order in (("crs", "sparseBench-CRS-HIP", []), ("scs", "sparseBench-SCS-HIP", ["-C", "64", "-s", "256"])):
         d = ctypes.CDLL(os.path.join(ROOT, "sparsebench_amd", "lib", "libsparsebench_%s.so" % fmt))
         assert hasattr(d, "solvePCGMGPolySA")
+        called, k = driver_options.run_dropin_symbol(tmp_path, fmt.upper(), "SOLVER_PCG_MGPOLY_SA", ["16", str(ac.ITERMAX), eps],
+                                                     env={"SPARSEBENCH_C": "64", "SPARSEBENCH_SIGMA": "256"} if order else None)
         out = run([os.path.join(BIN, exe), "-t", "pcg", "-p", "mgpoly", "-a", "-x", "16", "-y", "16", "-z", "16", "-i", str(ac.ITERMAX),
-                   "-e", "%.17g" % float.fromhex(rec["eps"])] + order)
-        txt = out.stdout.decode()
+                   "-e", eps] + order)
         assert out.returncode == 0, out.stderr.decode()[-2000:]
-        assert "smoothed-aggregation coarsening), levels = 3, steps = 2," in txt
-        if order:  # the golden case's own order: its count
-            assert re.search(r"^Solution performed %d iterations" % rec["k"], txt, re.M), txt[-2000:]
-        assert "Difference between computed and exact  = 0.0000" in txt
+        for txt in (called, out.stdout.decode()):
+            assert "smoothed-aggregation coarsening), levels = 3, steps = 2," in txt
+            if order:  # the golden case's own order: its levels and count
+                assert ROWS % (" ".join(map(str, rec["rows"])), "".join(" %d" % r for r in rec["rounds"])) in txt.split("\n"), txt[-2000:]
+                assert re.search(r"^Solution performed %d iterations" % rec["k"], txt, re.M), txt[-2000:]
+            assert "Difference between computed and exact  = 0.0000" in txt
+        assert not order or k == rec["k"]
+        lines = [[l for l in t.split("\n") if re.match(r"Preconditioner:|Aggregation on|Initial Residual|Iteration =", l)]
+                 for t in (called, out.stdout.decode())]
+        assert len(lines[0]) >= 3 and lines[0] == lines[1]  # the symbol and the driver: one solve
 
 
 def test_a_is_refused_with_g_and_without_mgpoly_before_the_set_up(gpu):

@@ -53,24 +53,28 @@ def test_driver_runs_mgpoly_pcg_on_galerkin_operators(gpu, exe, order, name):
     assert check_output(out.stdout.decode(), r, 2) != with_g
 
 
-def test_solvePCGMGPolyGalerkin_through_the_dropin_library(gpu):
+def test_solvePCGMGPolyGalerkin_through_the_dropin_library(gpu, tmp_path):
+    """the symbol, run by a C caller of its own, and the driver with -g at the defaults: both the golden count's depth and k"""
+    import driver_options
     from sparsebench_amd import hostapi
     hostapi.host()
-    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-    assert "k = solvePCGMGPolyGalerkin(&comm, &param, &sm);" in src
     count = load_json("mg_poly_hist.json")["counts"]["hpcg16_galerkin"]  # the deepest hierarchy, 2 steps, natural order
     assert cases.COUNT_CASES["hpcg16_galerkin"]["eps_rel"] == cases.CASES["hpcg16_crs_L3_galerkin"]["eps_rel"]  # the same eps: 1e-10 ||b||
     eps = float.fromhex(load_json("mg_poly_hist.json")["cases"]["hpcg16_crs_L3_galerkin"]["eps"])
     for fmt, exe in (("crs", "sparseBench-CRS-HIP"), ("scs", "sparseBench-SCS-HIP")):  # (Sell-64-1, the default: the natural order)
         d = ctypes.CDLL(os.path.join(ROOT, "sparsebench_amd", "lib", "libsparsebench_%s.so" % fmt))
         assert hasattr(d, "solvePCGMGPolyGalerkin")
+        called, k = driver_options.run_dropin_symbol(tmp_path, fmt.upper(), "SOLVER_PCG_MGPOLY_GALERKIN", ["16", "19", "%.17g" % eps])
+        assert k == count["k"]
         out = run([os.path.join(BIN, exe), "-t", "pcg", "-p", "mgpoly", "-g", "-i", "19", "-e", "%.17g" % eps] + SIZE)
-        txt = out.stdout.decode()
         assert out.returncode == 0, out.stderr.decode()[-2000:]
-        assert re.search(r"Galerkin coarse operators\), levels = %d, steps = 2," % count["L"], txt), txt[-2000:]
-        assert re.search(MS % ",".join(r" level %d: \d+\.\d{3} \+ \d+\.\d{3}" % l for l in range(1, count["L"])), txt, re.M), txt[-2000:]
-        assert re.search(r"^Solution performed %d iterations" % count["k"], txt, re.M), txt[-2000:]
-        assert "Difference between computed and exact  = 0.0000" in txt
+        for txt in (called, out.stdout.decode()):
+            assert re.search(r"^Preconditioner: MG .*Galerkin coarse operators\), levels = %d, steps = 2," % count["L"], txt, re.M), txt[-2000:]
+            assert re.search(MS % ",".join(r" level %d: \d+\.\d{3} \+ \d+\.\d{3}" % l for l in range(1, count["L"])), txt, re.M), txt[-2000:]
+            assert re.search(r"^Solution performed %d iterations" % count["k"], txt, re.M), txt[-2000:]
+            assert "Difference between computed and exact  = 0.0000" in txt
+        residuals = [[l for l in t.split("\n") if "Residual = " in l] for t in (called, out.stdout.decode())]
+        assert len(residuals[0]) == count["k"] and residuals[0] == residuals[1]  # (-i 19: a line per iteration)
 
 
 def test_g_is_refused_without_mgpoly_before_the_set_up(gpu):

@@ -66,24 +66,28 @@ def test_driver_in_a_permuted_order_shows_the_hierarchy_it_built(gpu):
     assert len(differing) >= 8, differing  # the depth shows in nearly every printed line
 
 
-def test_solvePCGMG_through_the_dropin_library(gpu):
-    """the drop-in entry at auto depth is what the driver without -l calls: the same k, here through the SCS driver with the
-    Sell-64-1 default and through the CRS one (test_driver_runs_mg_pcg) -- and the symbol is the library's own"""
+def test_solvePCGMG_through_the_dropin_library(gpu, tmp_path):
+    """the drop-in entry at auto depth, run by a C caller of its own, gives what the driver without -l gives: the same k and
+    lines, through the SCS library with the Sell-64-1 default and through the CRS one -- and the symbol is the library's own"""
     import ctypes
+    import driver_options
     from sparsebench_amd import hostapi
     hostapi.host()
     golden = load_json("mg_hist.json")["cases"]
     e, c = golden["hpcg16_crs_L4"], mg_cases.CASES["hpcg16_crs_L4"]
+    rr = [float.fromhex(v) for v in e["rr"]]
     for fmt, exe in (("crs", "sparseBench-CRS-HIP"), ("scs", "sparseBench-SCS-HIP")):
         d = ctypes.CDLL(os.path.join(ROOT, "sparsebench_amd", "lib", "libsparsebench_%s.so" % fmt))
         assert hasattr(d, "solvePCGMG")
         ldd = run(["ldd", os.path.join(BIN, exe)]).stdout.decode()
-        assert "libsparsebench_%s.so" % fmt in ldd  # the driver's solvePCGMG is this library's
-        src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-        assert "k = solvePCGMG(&comm, &param, &sm);" in src
+        assert "libsparsebench_%s.so" % fmt in ldd
+        called, k = driver_options.run_dropin_symbol(tmp_path, fmt.upper(), "SOLVER_PCG_MG", ["16"] + case_args(e, c)[1::2])
+        assert k == e["k"]
         txt = run([os.path.join(BIN, exe), "-t", "pcg", "-p", "mg"] + case_args(e, c) + SIZE).stdout.decode()
-        assert "levels = 4, nC = %d" % e["nC"][0] in txt
-        assert re.search(r"^Solution performed %d iterations" % e["k"], txt, re.M), txt[-2000:]
+        for out in (called, txt):
+            assert re.search(r"^Preconditioner: MG \(V-cycle, multicolour SGS smoother\), levels = 4, nC = %d$" % e["nC"][0], out, re.M), out[-2000:]
+            assert "Initial Residual = %E" % math.sqrt(rr[0]) in out and "Iteration = 15 Residual = %E" % math.sqrt(rr[14]) in out
+            assert re.search(r"^Solution performed %d iterations" % e["k"], out, re.M), out[-2000:]
 
 
 def test_switch_refusals(gpu, tmp_path):

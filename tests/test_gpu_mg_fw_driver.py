@@ -23,11 +23,12 @@ def run(cmd):
     return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
 
 
-def check_output(txt, e):
-    """the golden case's k, and with -i 19 (a line per iteration) the residual every iteration starts from, the last included"""
+def check_output(txt, e, head=r"^Test type: PCG\n(Generate .*\n)*"):
+    """the golden case's k, and with -i 19 (a line per iteration) the residual every iteration starts from, the last included;
+    head: what stands before the preconditioner's line (the driver's own lines; "^" for a caller that prints none)"""
     rr = [float.fromhex(v) for v in e["rr"]]
     assert 1 < e["k"] < 19 and len(rr) == e["k"] - 1
-    assert re.search(r"^Test type: PCG\n(Generate .*\n)*" + LINE % (e["L"], e["nC"][0]) + "$", txt, re.M), txt[-2000:]
+    assert re.search(head + LINE % (e["L"], e["nC"][0]) + "$", txt, re.M), txt[-2000:]
     lines = ["Initial Residual = %E" % math.sqrt(rr[0])] + ["Iteration = %d Residual = %E" % (j, math.sqrt(rr[j - 1])) for j in range(1, e["k"])]
     for line in lines:
         assert line in txt, (line, txt[-2000:])
@@ -52,17 +53,20 @@ def test_driver_runs_mgfw_pcg(gpu, exe, order, names):
     assert [a for a, b in zip(*printed) if a != b]  # the depth shows in the printed residuals, in the natural order too
 
 
-def test_solvePCGMGFW_through_the_dropin_library(gpu):
+def test_solvePCGMGFW_through_the_dropin_library(gpu, tmp_path):
+    """the symbol, run by a C caller of its own, and the driver at the defaults: both the golden case's lines"""
     import ctypes
+    import driver_options
     from sparsebench_amd import hostapi
     hostapi.host()
-    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-    assert "k = solvePCGMGFW(&comm, &param, &sm);" in src
     e = load_json("mg_fw_hist.json")["cases"]["hpcg16_crs_L4"]
     for fmt, exe in (("crs", "sparseBench-CRS-HIP"), ("scs", "sparseBench-SCS-HIP")):  # (Sell-64-1, the default: the natural order)
         d = ctypes.CDLL(os.path.join(ROOT, "sparsebench_amd", "lib", "libsparsebench_%s.so" % fmt))
         assert hasattr(d, "solvePCGMGFW")
         assert "libsparsebench_%s.so" % fmt in run(["ldd", os.path.join(BIN, exe)]).stdout.decode()
+        called, k = driver_options.run_dropin_symbol(tmp_path, fmt.upper(), "SOLVER_PCG_MGFW", ["16", "19", "%.17g" % float.fromhex(e["eps"])])
+        assert k == e["k"]
+        check_output(called, e, head="^")
         txt = run([os.path.join(BIN, exe), "-t", "pcg", "-p", "mgfw", "-i", "19", "-e", "%.17g" % float.fromhex(e["eps"])] + SIZE).stdout.decode()
         check_output(txt, e)
 

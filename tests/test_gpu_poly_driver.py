@@ -56,6 +56,27 @@ def test_driver_runs_polynomial_pcg(gpu, exe, fmt, where, tmp):
     p.free(), g.free()
 
 
+@pytest.mark.parametrize("fmt,sigma", [("CRS", 1), ("SCS", 1), ("SCS", 256)])
+def test_solvePCGPoly_through_the_dropin_library(gpu, fmt, sigma, tmp_path):
+    """the drop-in symbol, run by a C caller of its own, at the default 3 steps to eps = 1e-10 ||b||: in the natural order (CRS,
+    Sell-64-1) the k of tests/golden/poly_hist.json's counts, in the order of its case hpcg16_sell_64_256_eps that case's lines"""
+    import json
+    import driver_options
+    with open(os.path.join(ROOT, "tests", "golden", "poly_hist.json")) as f:
+        golden = json.load(f)
+    e = golden["cases"]["hpcg16_sell_64_256_eps"]
+    rr = [float.fromhex(v) for v in e["rr"]]
+    txt, k = driver_options.run_dropin_symbol(tmp_path, fmt, "SOLVER_PCG_POLY", ["16", "150", "%.17g" % float.fromhex(e["eps"])],
+                                              env={"SPARSEBENCH_C": "64", "SPARSEBENCH_SIGMA": str(sigma)})
+    assert k == (e["k"] if sigma == 256 else golden["counts"]["hpcg16"]["k_poly"]) and 15 < k < 150
+    assert re.search(r"^Preconditioner: Chebyshev polynomial, steps = 3, lambda in \[", txt, re.M), txt[-1500:]
+    assert "Initial Residual = %E" % np.sqrt(rr[0]) in txt  # (b.b of small integers: the same in every order)
+    if sigma == 256:
+        assert "Iteration = 15 Residual = %E" % np.sqrt(rr[14]) in txt  # itermax 150: every 15th iteration has a line
+    assert re.search(r"^Solution performed %d iterations and took \d+\.\d\ds$" % k, txt, re.M), txt[-1500:]
+    assert "Difference between computed and exact  = " in txt
+
+
 def test_switch_refusals(gpu):
     crs = os.path.join(BIN, "sparseBench-CRS-HIP")
     small = ["-x", "8", "-y", "8", "-z", "8", "-i", "10"]

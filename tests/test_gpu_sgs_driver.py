@@ -32,6 +32,15 @@ def want():
     return out
 
 
+def check_lines(txt, want, e):
+    assert "Initial Residual = %E" % np.sqrt(want["rr"][0]) in txt
+    freq = max(1, min(50, ITERMAX // 10))
+    for j in range(1, want["k"]):
+        if j % freq == 0 or j + 1 == ITERMAX:
+            assert "Iteration = %d Residual = %E" % (j, np.sqrt(want["rr"][0 if j == 1 else j - 1])) in txt, j
+    assert re.search(r"^Solution performed %d iterations and took \d+\.\d\ds$" % e["k"], txt, re.M)
+
+
 @pytest.mark.parametrize("exe", ["sparseBench-CRS-HIP", "sparseBench-SCS-HIP"])
 def test_driver_runs_sgs_pcg(gpu, exe, want):
     e = load_json("sgs_hist.json")["cases"]["hpcg16_sell_64_256"]
@@ -40,18 +49,25 @@ def test_driver_runs_sgs_pcg(gpu, exe, want):
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     txt = out.stdout.decode()
     assert re.search(r"^Test type: PCG\nPreconditioner: SGS .*nC = %d$" % e["nC"], txt, re.M)
-    assert "Initial Residual = %E" % np.sqrt(want["rr"][0]) in txt
-    freq = max(1, min(50, ITERMAX // 10))
-    for j in range(1, want["k"]):
-        if j % freq == 0 or j + 1 == ITERMAX:
-            assert "Iteration = %d Residual = %E" % (j, np.sqrt(want["rr"][0 if j == 1 else j - 1])) in txt, j
-    assert re.search(r"^Solution performed %d iterations and took \d+\.\d\ds$" % e["k"], txt, re.M)
+    check_lines(txt, want, e)
     assert "Difference between computed and exact  = " in txt
     # the default and -p jacobi are the Jacobi solve
     for extra in ([], ["-p", "jacobi"]):
         txt = run([os.path.join(BIN, exe), "-t", "pcg", "-i", "20"] + extra + SIZE).stdout.decode()
         assert re.search(r"^Test type: PCG\nPreconditioner: Jacobi .*nC = 0$", txt, re.M)
         assert re.search(r"^Solution performed 20 iterations", txt, re.M)
+
+
+@pytest.mark.parametrize("fmt", ["CRS", "SCS"])
+def test_solvePCGSGS_through_the_dropin_library(gpu, fmt, want, tmp_path):
+    """the drop-in symbol, run by a C caller of its own (Sell-64-1: the natural order): the golden k and colours, the restatement's lines"""
+    import driver_options
+    e = load_json("sgs_hist.json")["cases"]["hpcg16_sell_64_256"]
+    txt, k = driver_options.run_dropin_symbol(tmp_path, fmt, "SOLVER_PCG_SGS", ["16", str(ITERMAX), "0.0"])
+    assert k == want["k"] == e["k"] == ITERMAX
+    assert re.search(r"^Preconditioner: SGS \(multicolour symmetric Gauss-Seidel\), nC = %d$" % e["nC"], txt, re.M), txt[-2000:]
+    check_lines(txt, want, e)
+    assert "Difference between computed and exact  = " in txt
 
 
 def test_switch_refusals(gpu):

@@ -115,7 +115,17 @@ def test_the_librarys_refusals_name_the_level():
 
 
 def test_driver_help_names_mgfw():
-    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-    help_text = "".join(re.findall(r'^\s+"(.*)"\s*;?\s*$', src.split("kHelp =")[1].split(";")[0], flags=re.M))
+    import driver_options as opts
+    help_text = opts.help_text()
     assert re.search(r"-p mgfw\b", help_text) and re.search(r"-p mg\b", help_text) and re.search(r"-l <int>", help_text)
-    assert 'strcmp(optarg, "mgfw") == 0' in src and "k = solvePCGMGFW(&comm, &param, &sm);" in src
+    small, SIZE = ["-i", "10"], opts.SIZE
+    # the defaults are solvePCGMGFW's spec (the symbol itself runs in test_gpu_mg_fw_driver.py); -l is the other path
+    assert opts.accepted(["-t", "pcg", "-p", "mgfw"] + small + SIZE).spec == (opts.KIND["mgfw"], 0, 0, 0)
+    assert opts.accepted(["-t", "pcg", "-p", "mgfw", "-l", "3"] + small + SIZE).spec == (opts.KIND["mgfw"], 3, 0, 0)
+    opts.refused(["-t", "pcg", "-p", "mgfw", "-m", "tri.mtx"] + small, "-p mgfw needs the grid")
+    opts.refused(["-t", "pcg", "-p", "mgfw", "-l", "5"] + small + SIZE, "5 levels would give a coarse dimension smaller than 2")
+    opts.refused(["-t", "pcg", "-p", "mgfw", "-l", "2", "-x", "15", "-y", "16", "-z", "16"] + small, "2 levels need every dimension divisible by 2")
+    opts.refused(["-t", "cg", "-p", "mgfw"] + small + SIZE, "goes with -t pcg only")
+    opts.refused(["-t", "pcg", "-p", "mgfx"] + small + SIZE, "Unknown preconditioner mgfx")
+    opts.refused(["-t", "pcg", "-p", "mgfw"] + small + SIZE, "PCG: double precision only", precision="single")
+    assert opts.no_device_was_touched()

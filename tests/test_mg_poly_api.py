@@ -134,11 +134,25 @@ def test_mg_galerkin_refuses_what_it_cannot_coarsen():
 
 
 def test_driver_help_and_messages_name_mgpoly():
-    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-    help_text = "".join(re.findall(r'^\s+"(.*)"\s*;?\s*$', src.split("kHelp =")[1].split(";")[0], flags=re.M))
-    assert re.search(r"-p mgpoly\b", help_text) and re.search(r"-p mgpoly.*-l.*-d.*Default 2", help_text)
+    import driver_options as opts
+    help_text = opts.help_text()
+    assert re.search(r"-p mgpoly\b", help_text) and re.search(r"-p mgpoly.*-l.*-d.*Default 2", help_text, re.S)  # (the switch's two lines)
     assert re.search(r"-p <jacobi\|sgs>.*Default jacobi", help_text) and "-C <int>" in help_text  # the help text is still whole
-    assert 'strcmp(optarg, "mgpoly") == 0' in src
-    assert "-d <int> (the steps) goes with -p poly only, or with -p mgpoly" in src
-    assert "-l <int> (the levels) goes with -p mg only, or with -p mgfw or -p mgpoly" in src
-    assert "solvePCGMGPoly(&comm, &param, &sm)" in src and "sbh_solve_pcg_mgpoly(" in src
+    small, SIZE = ["-i", "10"], opts.SIZE
+    # the defaults are solvePCGMGPoly's spec (the symbol itself runs in test_gpu_mg_poly_driver.py); -l and -d are the other path
+    assert opts.accepted(["-t", "pcg", "-p", "mgpoly"] + small + SIZE).spec == (opts.KIND["mgpoly"], 0, 0, opts.COARSE["regenerated"])
+    assert opts.accepted(["-t", "pcg", "-p", "mgpoly", "-l", "3"] + small + SIZE).spec == (opts.KIND["mgpoly"], 3, 0, 0)
+    assert opts.accepted(["-t", "pcg", "-p", "mgpoly", "-d", "1"] + small + SIZE).spec == (opts.KIND["mgpoly"], 0, 1, 0)
+    p = opts.accepted(["-t", "pcg", "-p", "mgpoly", "-C", "64", "-s", "256", "-l", "3", "-d", "2"] + small + SIZE)
+    assert p.spec == (opts.KIND["mgpoly"], 3, 2, 0) and (p.scsC, p.scsSigma) == (64, 256)
+    opts.refused(["-t", "pcg", "-p", "mgpoly", "-m", "tri.mtx"] + small, "-p mgpoly needs the grid")
+    opts.refused(["-t", "pcg", "-p", "mgpoly", "-l", "5"] + small + SIZE, "5 levels would give a coarse dimension smaller than 2")
+    opts.refused(["-t", "pcg", "-p", "mgpoly", "-l", "2", "-x", "15", "-y", "16", "-z", "16"] + small, "2 levels need every dimension divisible by 2")
+    for bad in ("0", "17", "x"):
+        opts.refused(["-t", "pcg", "-p", "mgpoly", "-d", bad] + small + SIZE, "-d <int> (the steps of -p poly or -p mgpoly) must be 1 to 16")
+    opts.refused(["-t", "pcg", "-p", "mgfw", "-d", "2"] + small + SIZE, "-d <int> (the steps) goes with -p poly only, or with -p mgpoly\n")
+    opts.refused(["-t", "pcg", "-p", "sgs", "-l", "2"] + small + SIZE, "-l <int> (the levels) goes with -p mg only, or with -p mgfw or -p mgpoly\n")
+    opts.refused(["-t", "cg", "-p", "mgpoly"] + small + SIZE, "goes with -t pcg only")
+    opts.refused(["-t", "pcg", "-p", "mgpol"] + small + SIZE, "Unknown preconditioner mgpol")
+    opts.refused(["-t", "pcg", "-p", "mgpoly"] + small + SIZE, "PCG: double precision only", precision="single")
+    assert opts.no_device_was_touched()

@@ -56,8 +56,62 @@ def test_hostapi_pcg_refuses_single_precision_and_has_its_methods():
 
 
 def test_driver_help_names_pcg_and_the_sp_drivers_refuse_it():
-    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-    help_text = "".join(re.findall(r'^\s+"(.*)"\s*;?\s*$', src.split("kHelp =")[1].split(";")[0], flags=re.M))
-    assert re.search(r"-t <bench type>.*\bpcg\b", help_text)
-    assert 'strcmp(optarg, "pcg") == 0' in src and "PCG: double precision only" in src
-    assert 'strcmp(optarg, "cheb")' not in src  # still an unknown type
+    import driver_options as opts
+    size = ["-x", "8", "-y", "8", "-z", "8", "-i", "10"]
+    assert re.search(r"-t <bench type>.*\bpcg\b", opts.help_text())
+    p = opts.accepted(["-t", "pcg"] + size)
+    assert p.type == opts.TYPE["pcg"] and p.spec == (opts.KIND[None], 0, 0, 0) and not p.byP
+    assert (p.dims, p.itermax, p.filename, p.optind) == ((8, 8, 8), 10, "generate", 11)
+    opts.refused(["-t", "pcg"] + size, "PCG: double precision only\n", precision="single")
+    opts.refused(["-t", "pcg", "-h"], "PCG: double precision only\n", precision="single")  # refused at the -t, as the process ended there
+    opts.refused(["-t", "cheb"] + size, "Unknown solver type cheb\n", stream="stdout")  # still an unknown type
+    opts.refused(["-t", "pcg", "-n", "2"] + size, "-t cg only")
+    assert opts.no_device_was_touched()
+
+
+def test_driver_options_that_end_or_leave_the_parse():
+    """-h and -c end the parse where they stand, as they ended the process there: what came before is applied, what follows is
+    not looked at; an unknown option is refused; a stray word is left for the driver to name"""
+    import driver_options as opts
+    p = opts.parse(["-x", "8", "-h", "-t", "cheb", "-y", "9"])
+    assert (p.status, p.action, p.message) == (0, opts.HELP, "") and p.dims == (8, 100, 100)
+    p = opts.parse(["-i", "7", "-c", "a.mtx", "-t", "cheb"])
+    assert (p.status, p.action, p.convert, p.itermax) == (0, opts.CONVERT, "a.mtx", 7)
+    opts.refused(["-t", "cheb", "-h"], "Unknown solver type cheb\n", stream="stdout")  # the refusal came first
+    opts.refused(["-q"], "Unknown option `-q'.\n")
+    opts.refused(["-t"], "Unknown option `-t'.\n")  # (an option without its argument)
+    opts.refused(["-q", "stray"], "Unknown option `-q'.\n")
+    p = opts.accepted(["stray", "-t", "cg", "-i", "5"])
+    assert p.optind == 5 and p.itermax == 5  # one word behind the five that getopt moved ahead of it
+    p = opts.refused(["stray", "-t", "pcg", "-n", "2"], "-t cg only")
+    assert p.optind == 5  # refused behind the options: the driver names the stray word first
+    assert opts.refused(["-t", "pcg", "-p", "ilu", "stray"], "Unknown preconditioner ilu").optind == 6  # inside them: it names none
+    assert opts.no_device_was_touched()
+
+
+def test_option_parser_stands_alone_under_the_host_sanitizers(tmp_path):
+    """sbh_options.c with sbh_mg_levels and the parameter reader links without the device library (tests/c/options_driver.c, its
+    own main) and runs clean under AddressSanitizer and UBSan on accepted, refused, ended and permuted command lines"""
+    import subprocess
+    host = os.path.join(ROOT, "sparsebench_amd", "host")
+    exe = os.path.join(str(tmp_path), "options_driver")
+    subprocess.check_call(["gcc", "-std=gnu11", "-O1", "-g", "-Wall", "-Wextra", "-Wno-unused-parameter", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", "-ffunction-sections", "-fdata-sections", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "c", "options_driver.c")] + [os.path.join(host, f) for f in ("sbh_options.c", "sbh_mg.c", "sbh_base.c")] +
+                          ["-Wl,--gc-sections", "-o", exe, "-lm"])
+    par = tmp_path / "a.par"
+    par.write_text("filename generate7P \nnx 12\nitermax 7 # a comment\n")
+    lines = [["-t", "pcg", "-p", "mgpoly", "-l", "5", "-x", "16", "-y", "16", "-z", "16"], ["-h", "-t", "cheb"], ["-t", "cheb"], ["-q"], ["-t"],
+             ["stray", "-t", "cg", "more"], ["-t", "gmres", "-P", "mgpoly", "-a", "-m", "a.mtx"], ["-t", "pcg", "-p", "mg", "-m", "x" * 3000],
+             ["-f", str(par), "-t", "pcg", "-p", "mgfw", "-l", "2"], ["-c", "a.mtx"], ["-d", "17"], ["-l", "0"], []]
+    # (no leak check: a parameter file's filename is a strdup that lives as long as the process, as in the reference's reader)
+    out = subprocess.run([exe], input="".join("\t".join(l) + "\n" for l in lines).encode(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=60,
+                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert out.returncode == 0 and out.stderr == b"", out.stderr.decode()[-3000:]
+    got = out.stdout.decode().split("\n")
+    assert len(got) == len(lines) + 1 and got[-1] == ""
+    assert got[0].endswith("MG: 5 levels would give a coarse dimension smaller than 2 (the grid is 16 x 16 x 16, the coarsest 1 x 1 x 1)")
+    assert got[1].startswith("2: status 0 action 1 ") and got[2].endswith("stdout Unknown solver type cheb")
+    assert " optind 3 of 5 " in got[5] and got[6].startswith("7: status 0 action 0 type 2 precond 5 0 0 2 byP 1 ")
+    assert got[7].endswith("not -m " + "x" * 3000)  # the longest message has its room
+    assert got[8].startswith("9: status 0 action 0 type 3 precond 3 2 0 0 ") and " -m generate7P grid 12 100 100 " in got[8]

@@ -94,11 +94,20 @@ def test_hostapi_pcg_refuses_before_the_library_is_touched():
 
 
 def test_driver_help_names_the_polynomial_switches():
-    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-    help_text = "".join(re.findall(r'^\s+"(.*)"\s*;?\s*$', src.split("kHelp =")[1].split(";")[0], flags=re.M))
+    import driver_options as opts
+    help_text = opts.help_text()
     assert re.search(r"-p poly\b", help_text) and re.search(r"-d <int>.*-p poly.*Default 3", help_text)
     assert re.search(r"-p <jacobi\|sgs>.*Default jacobi", help_text) and "-C <int>" in help_text  # the help text is still whole
-    assert 'strcmp(optarg, "poly") == 0' in src
-    assert "-d <int> (the steps) goes with -p poly only" in src
-    assert "goes with -t pcg only" in src and "goes with -p mg only" in src
-    assert 'strcmp(optarg, "cheb")' not in src  # still an unknown type
+    small = ["-x", "8", "-y", "8", "-z", "8", "-i", "10"]
+    assert opts.accepted(["-t", "pcg", "-p", "poly"] + small).spec == (opts.KIND["poly"], 0, 0, 0)
+    assert opts.accepted(["-t", "pcg", "-p", "poly", "-d", "2"] + small).spec == (opts.KIND["poly"], 0, 2, 0)
+    for extra in (["-t", "pcg"], ["-t", "pcg", "-p", "jacobi"], ["-t", "pcg", "-p", "sgs"], ["-t", "pcg", "-p", "mg"], ["-t", "cg"], []):
+        opts.refused(["-d", "2"] + extra + small, "-d <int> (the steps) goes with -p poly only")
+    for bad in ("0", "17", "-3", "x"):
+        opts.refused(["-t", "pcg", "-p", "poly", "-d", bad] + small, "must be 1 to 16, got %s\n" % bad)
+    opts.refused(["-p", "poly"] + small, "goes with -t pcg only")  # the default type is cg
+    opts.refused(["-t", "pcg", "-p", "poly", "-l", "2"] + small, "goes with -p mg only")
+    opts.refused(["-t", "pcg", "-p", "cheb"] + small, "Unknown preconditioner cheb")
+    opts.refused(["-t", "cheb"] + small, "Unknown solver type cheb\n", stream="stdout")  # still an unknown type
+    opts.refused(["-t", "pcg", "-p", "poly"] + small, "PCG: double precision only", precision="single")
+    assert opts.no_device_was_touched()

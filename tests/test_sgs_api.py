@@ -72,10 +72,18 @@ def test_hostapi_pcg_refuses_before_the_library_is_touched():
 
 
 def test_driver_help_names_the_preconditioner_switch():
-    src = open(os.path.join(ROOT, "sparsebench_amd", "host", "sbh_main.c")).read()
-    help_text = "".join(re.findall(r'^\s+"(.*)"\s*;?\s*$', src.split("kHelp =")[1].split(";")[0], flags=re.M))
+    import driver_options as opts
+    help_text = opts.help_text()
     assert re.search(r"-p <jacobi\|sgs>.*Default jacobi", help_text)
     assert re.search(r"-t <bench type>.*\bpcg\b", help_text) and "-C <int>" in help_text  # the help text is still whole
-    assert 'strcmp(optarg, "sgs") == 0' in src and 'strcmp(optarg, "jacobi") == 0' in src
-    assert "goes with -t pcg only" in src
-    assert 'strcmp(optarg, "cheb")' not in src  # still an unknown type
+    small = ["-x", "8", "-y", "8", "-z", "8", "-i", "10"]
+    for name in ("sgs", "jacobi"):
+        p = opts.accepted(["-t", "pcg", "-p", name] + small)
+        assert p.type == opts.TYPE["pcg"] and p.spec == (opts.KIND[name], 0, 0, 0) and not p.byP
+    for t in ("cg", "gmres", "spmv", "bicgstab"):
+        opts.refused(["-t", t, "-p", "sgs"] + small, "goes with -t pcg only")
+    opts.refused(["-p", "sgs"] + small, "goes with -t pcg only")  # the default type is cg
+    opts.refused(["-t", "pcg", "-p", "ilu"] + small, "Unknown preconditioner ilu")
+    opts.refused(["-t", "pcg", "-p", "sgs"] + small, "PCG: double precision only", precision="single")
+    opts.refused(["-t", "cheb"] + small, "Unknown solver type cheb\n", stream="stdout")  # still an unknown type
+    assert opts.no_device_was_touched()
