@@ -533,16 +533,27 @@ void sb_cgb_counters(const sb_cgb* s, int c, int out[5]);
 /* ---- CG with a diagonal preconditioner ---------------------------------------------------------------- */
 /* solveCG's loop with z = r o dinv put back (HPCG's CG with its preconditioner): alpha = r.z / p.Ap, beta = r.z / (r.z)_old,
  * p = z + beta p; the loop test stays on sqrt(r.r) with solveCG's one-body lag, so dinv = 1.0 everywhere is sb_cg in the tree
- * order bit for bit (k, every r.r, every p.Ap, x; r.z == r.r).  Double precision, ONE rank, tree dot order; a halo with more
- * than one rank, a single-precision matrix, the seq order, a matrix row without a finite positive diagonal (Jacobi) and a
- * caller's dinv entry that is not finite and positive are fatal errors with file:line.  The SpMV is the one the matrix's
- * kernel mode selects (sb_matrix_use_packed), as sb_spmv_native_dot launches it. */
+ * order bit for bit (k, every r.r, every p.Ap, x; r.z == r.r).  Double precision, tree dot order; a single-precision matrix, the
+ * seq order, a matrix row without a finite positive diagonal (Jacobi) and a caller's dinv entry that is not finite and positive
+ * are fatal errors with file:line.  The SpMV is the one the matrix's kernel mode selects (sb_matrix_use_packed), as
+ * sb_spmv_native_dot launches it.
+ * ONE rank -- or, for sb_pcg_create and sb_pcg_create_poly alone, SEVERAL: the process is in a communicator of more
+ * than one rank and `halo` is the plan of this matrix (halo->nr == nr, nr + externalCount == nc; a plan that disagrees is a fatal
+ * error).  Then every call on the handle from create to free is collective, as sb_cg's are.  Each of p.Ap, r.z and r.r is the
+ * rank's own tree-order value, then the pairwise tree over ranks in rank order (sb_cg's all-reduce; r.z and r.r travel back to
+ * back); p's halo tail is filled ahead of every SpMV by the plan's push and pull launches or by pack | send / recv, never by a
+ * folded form: sb_comm_halo_fold and sb_comm_halo_push_inside do not apply to PCG.  Same bits on either data plane and as the
+ * P-rank restatement of the tests.  A failed wait on the peer-mapped plane ends the process in sb_pcg_finish with sb_cg's
+ * messages.  In every other case with halo columns, a halo plan of another rank count or several ranks the handles are refused:
+ * "PCG runs on one rank", as are the sweeps and the V-cycles (below), and a BiCGStab or GMRES handle that borrows a several-rank
+ * handle's preconditioner. */
 typedef struct sb_pcg sb_pcg;
 /* d_dev[i] = the sum, in storage order from +0.0, of row i's stored entries whose column is i; device pointer, nr doubles,
  * the device's row order (the permuted order for sigma > 1); stream-ordered */
 void sb_matrix_diagonal(const sb_matrix* m, double* d_dev);
-/* b_host, xexact_host (or NULL) as for sb_cg_create.  dinv_host NULL: Jacobi, dinv_i = 1.0 / d_i; else nr finite positive
- * doubles in ORIGINAL row order.  halo: NULL or a one-rank plan. */
+/* b_host, xexact_host (or NULL) as for sb_cg_create.  dinv_host NULL: Jacobi, dinv_i = 1.0 / d_i of the rank's own rows; else nr
+ * finite positive doubles in ORIGINAL row order (the rank's nr local entries).  halo: NULL or a one-rank plan; several ranks: the
+ * matrix's plan. */
 sb_pcg* sb_pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const double* dinv_host);
 void sb_pcg_free(sb_pcg* s);
 int sb_pcg_solve(sb_pcg* s, int itermax, double eps); /* blocking; returns k as solveCG does */
@@ -555,11 +566,16 @@ int sb_pcg_finish(sb_pcg* s);
  * sb_cg_history indexes its own.  Returns the number of rr (= rz) entries. */
 int sb_pcg_history(const sb_pcg* s, double* rr_out, int rr_cap, double* rz_out, int rz_cap, double* pAp_out, int pAp_cap, int* n_pAp);
 void sb_pcg_solution(const sb_pcg* s, double* x_host);   /* original row order */
-double sb_pcg_check_residual(const sb_pcg* s);           /* max|x - xexact|, 0.0 without an exact solution */
+double sb_pcg_check_residual(const sb_pcg* s);           /* max|x - xexact| (several ranks: over all of them), 0.0 without an exact solution */
 void sb_pcg_dinv(const sb_pcg* s, double* dinv_host);    /* the preconditioner in use, original row order */
 /* 5 (p update | SpMV with the p.Ap values | alpha | r update with z and the r.z, r.r values | beta); 6 where the selected SpMV
- * kernel has no fused dot (native CRS, C != 64: + the dot pass) */
+ * kernel has no fused dot (native CRS, C != 64: + the dot pass).  Several ranks add, as sb_cg_launches_per_body counts them: per
+ * halo exchange (one for p; the polynomial: one more per step behind the first) the push and the pull kernel on the peer-mapped
+ * plane, else the pack kernel; and 2 without the in-kernel all-reduce (local reduce | all-reduces | step, for alpha and for beta) */
 int sb_pcg_launches_per_body(const sb_pcg* s);
+/* communicator calls per body, as sb_cg_collectives_per_body: 3 all-reduces (p.Ap; r.z, r.r) without the in-kernel all-reduce, a
+ * send / recv group per halo exchange without the peer-mapped halo; 0 on one rank */
+int sb_pcg_collectives_per_body(const sb_pcg* s);
 double sb_pcg_loop_ms(const sb_pcg* s); /* GPU milliseconds between the end of sb_pcg_start and sb_pcg_finish */
 void sb_pcg_counters(const sb_pcg* s, int out[5]); /* stop, stop_next, iters, n_rr, n_pAp of the device control block */
 /* test entry for the fused kernel: r = r + nalpha * Ap, z = r o dinv and the ceil(n/256) level-1 values of r.z and of r.r;
@@ -569,6 +585,11 @@ void sb_pcg_update_r_native(uint32_t n, double nalpha, const double* Ap_dev, dou
 /* its launch over n rows: {workgroups, threads per workgroup, compute units of the device}; a wave owns whole 256-row groups
  * and strides over them by the number of waves in the grid */
 void sb_pcg_update_r_launch(uint32_t n, uint32_t out[3]);
+/* test entry for the several-rank loop's local reduce on the communicator's plane (pcg_local_reduce_k), in one process: the
+ * level-1 values of a.b and a.a over n rows (dot_l1_k), then the kernel; out: the block's two sums, preset to { -1.0, -2.0 }:
+ * out[0] = levels 1-2 of a.b, out[1] = of a.a where two != 0 and untouched else; stopped != 0: the control block says the loop
+ * has exited and both are untouched.  a, b: device vectors of n doubles, 16-byte aligned; blocking */
+void sb_pcg_local_reduce_native(uint32_t n, int two, int stopped, const double* a_dev, const double* b_dev, double out[2]);
 
 /* ---- symmetric Gauss-Seidel preconditioning by multicolouring ----
  * z = M^-1 r with M = (D + L) D^-1 (D + U) in a colour order: rows are adjacent when a_ij or a_ji is stored, off the diagonal
@@ -631,7 +652,11 @@ void sb_pcg_mg_fw_probe(sb_pcg* s, int l, const double* r_host, const double* z_
  * steps: 1 .. 16.  lmax <= 0.0: the bound max_i g_i, g_i the sum in storage order from +0.0 over row i's stored entries of
  * (|a_e| * sd_i) * sd[col_e], sd = sqrt(dinv): an absolute row sum of D^-1/2 A D^-1/2, computed on the device.  ratio == 0.0: 16.
  * Fatal errors: steps out of range, a ratio that is not finite and > 1, an lmax that is not finite, a bound that is not finite
- * and positive, and what sb_pcg_create refuses (a row without a finite positive diagonal names this preconditioner).  The handle
+ * and positive, and what sb_pcg_create refuses (a row without a finite positive diagonal names this preconditioner).
+ * Several ranks (as sb_pcg_create accepts them): steps, lmax and ratio are COLLECTIVE arguments, the same on every rank; the bound
+ * reads dinv at the halo columns (one halo exchange at set-up) and lmax is the MAX over ranks; z's halo tail is filled ahead of
+ * every step's SpMV; a rank must receive from exactly the ranks it sends to (a structurally symmetric matrix), else fatal;
+ * sb_pcg_poly_rowbound gives the rank's own rows, sb_pcg_apply_precond is collective.  The handle
  * is an sb_pcg: every other sb_pcg_* call works on it, sb_pcg_dinv gives 1 / diag(A), sb_pcg_launches_per_body gives
  * 5 + 2 (steps - 1) (+ 1 without a fused dot), sb_pcg_precond_bytes (steps - 1) * (sb_matrix_spmv_bytes + 56 per row) + 24 per row. */
 sb_pcg* sb_pcg_create_poly(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int steps, double lmax,

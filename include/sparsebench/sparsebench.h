@@ -402,6 +402,10 @@ typedef struct {
  * follows is not looked at.  Resets getopt's state, so it can be called again; param->filename may point into argv */
 int sbh_parse_options(int argc, char** argv, Parameter* param, sbh_options* o, char* msg, size_t cap);
 const char* sbh_help_text(void);
+/* What of the parsed options runs on `size` ranks, checked without a device as well: -t cg, -t spmv, and -t pcg with the Jacobi
+ * diagonal or -p poly [-d n].  Returns 0, or 1 with "<who>: runs on one rank\n" in msg for -p sgs ("SGS"), -p mg |
+ * mgfw | mgpoly with or without -g and -a ("MG"), -t gmres and -t bicgstab; size < 2: 0 */
+int sbh_check_ranks(const sbh_options* o, int size, char* msg, size_t cap);
 #if defined(CRS) || defined(SCS)
 /* the fmt, C, sigma arguments of the entries above that rebuild the matrix on coarser grids, for this build's Matrix */
 #ifdef SCS
@@ -424,8 +428,10 @@ int solveGMRES(Comm* comm, Parameter* param, Matrix* m, int restart);
 int solveCGBatch(Comm* comm, Parameter* param, Matrix* m, int nrhs);
 /* solveCG with the Jacobi preconditioner put back: z = r o (1 / diag(A)), alpha = r.z / p.Ap, beta = r.z / (r.z)_old,
  * the loop test on sqrt(r.r) as in solveCG.  Prints solveCG's lines from the recorded history and returns k as solveCG does.
- * A matrix row without a finite positive diagonal entry ends the process with a message.  One rank, tree dot order; the
- * single-precision libraries export it too and end the process with "PCG: double precision only". */
+ * A matrix row without a finite positive diagonal entry ends the process with a message.  Tree dot order; one rank or several
+ * (the Comm's halo plan fills p's halo ahead of every SpMV, each dot is the rank's tree-order value then the pairwise
+ * tree over ranks; collective like solveCG); the single-precision libraries export it too and end the process with "PCG: double
+ * precision only". */
 int solvePCG(Comm* comm, Parameter* param, Matrix* m);
 /* solvePCG with HPCG's own preconditioner, symmetric Gauss-Seidel, applied by multicolouring: z = M^-1 r with
  * M = (D + L) D^-1 (D + U) in a greedy colour order of the rows, one launch per colour and sweep.  Prints the preconditioner and
@@ -446,8 +452,9 @@ int solvePCGMGFW(Comm* comm, Parameter* param, Matrix* m);
 /* solvePCG with a Chebyshev polynomial preconditioner: z = q(D^-1 A) D^-1 r, three terms of the Chebyshev recurrence
  * on [lmax / 16, lmax], each term behind the first one SpMV of the matrix's own and a streaming kernel; no colouring, no set-up
  * beyond a row-sum bound for lmax.  Prints the preconditioner, its steps and interval, then solvePCG's lines; returns k as solveCG
- * does.  Square matrix, one rank, tree dot order; a row without a finite positive diagonal entry ends the process with a message;
- * the single-precision libraries export it too and end the process with "PCG: double precision only". */
+ * does.  Tree dot order; one rank (a square matrix) or several as solvePCG runs on them (lmax is then the MAX over ranks of the
+ * bound, and z's halo is filled ahead of every step's SpMV); a row without a finite positive diagonal entry ends the process with
+ * a message; the single-precision libraries export it too and end the process with "PCG: double precision only". */
 int solvePCGPoly(Comm* comm, Parameter* param, Matrix* m);
 /* solvePCGMGFW with that polynomial as the smoother of every level in the Gauss-Seidel sweeps' place: two steps
  * before and after on every level, omega = 0.25, every SpMV of the cycle the level's own; no colouring.  The same matrices and

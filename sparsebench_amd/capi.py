@@ -51,7 +51,7 @@ SYMBOLS = [
     "sb_cgb_counters",
     "sb_matrix_diagonal", "sb_pcg_create", "sb_pcg_free", "sb_pcg_solve", "sb_pcg_start", "sb_pcg_run_iters", "sb_pcg_finish",
     "sb_pcg_history", "sb_pcg_solution", "sb_pcg_check_residual", "sb_pcg_dinv", "sb_pcg_launches_per_body", "sb_pcg_loop_ms",
-    "sb_pcg_counters", "sb_pcg_update_r_native", "sb_pcg_update_r_launch",
+    "sb_pcg_counters", "sb_pcg_update_r_native", "sb_pcg_update_r_launch", "sb_pcg_collectives_per_body", "sb_pcg_local_reduce_native",
     "sb_pcg_create_sgs", "sb_pcg_precond", "sb_pcg_colours", "sb_pcg_colouring", "sb_pcg_apply_precond", "sb_pcg_precond_bytes",
     "sb_pcg_apply_precond_ms",
     "sb_pcg_create_mg", "sb_pcg_levels", "sb_pcg_level_rows", "sb_pcg_level_colours",
@@ -293,6 +293,8 @@ def load():
         "sb_pcg_counters": (None, [vp, vp]),
         "sb_pcg_update_r_native": (None, [u32, C.c_double, vp, vp, vp, vp, vp, vp]),
         "sb_pcg_update_r_launch": (None, [u32, vp]),
+        "sb_pcg_collectives_per_body": (C.c_int, [vp]),
+        "sb_pcg_local_reduce_native": (None, [u32, C.c_int, C.c_int, vp, vp, vp]),
         "sb_pcg_create_sgs": (vp, [vp, vp, vp, vp]),
         "sb_pcg_precond": (C.c_int, [vp]),
         "sb_pcg_colours": (C.c_int, [vp]),

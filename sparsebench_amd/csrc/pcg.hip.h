@@ -237,6 +237,110 @@ __global__ __launch_bounds__(1024) void pcg_scalar_k(uint32_t m, const double* _
 }
 
 // =============================================================================
+// The scalar steps on several ranks.  Each of p.Ap, r.z and r.r is the rank's own levels 1-2 value, then the
+// pairwise tree over ranks; every rank continues with identical bits.  PcgScalars and pcg_scalar_k stay as they are: what the
+// ranks add to the loop's state is a block of its own.
+// =============================================================================
+struct PcgRankSums {
+  double v[2];   // the communicator's plane: the rank's sums, all-reduced in place (MODE 2: v[0] = p.Ap; else v[0] = r.z, v[1] = r.r)
+  int p2p_error; // the peer-mapped plane: 1 a wait of an in-kernel all-reduce ran out here, 2 a peer has failed (CgScalars::p2p_error)
+};
+
+// pcg_scalar_k<MODE>'s step on the sums ta (p.Ap or r.z) and tb (r.r), statement for statement; one thread.  Its twin, to be
+// changed with it: with the step taken out into this function pcg_scalar_k<0> and <1> do not keep their code
+template <int MODE>
+__device__ __forceinline__ void pcg_apply(PcgScalars* S, const PcgScalars& in, double ta, double tb, double* __restrict__ rr_hist,
+    double* __restrict__ rz_hist, double* __restrict__ pAp_hist)
+{
+  if (MODE == 0) {
+    const int sn = !(sqrt(tb) > in.eps);
+    S->rr = tb, S->rz = ta, S->stop_next = sn;
+    if (in.n_rr < in.hist_cap) rr_hist[in.n_rr] = tb, rz_hist[in.n_rr] = ta;
+    S->n_rr = in.n_rr + 1;
+    if (1 < in.itermax && !sn) S->iters = 1;
+    else S->stop = 1;
+  } else if (MODE == 1) {
+    if (in.iters + 1 < in.itermax && !in.stop_next) {
+      S->rz_old    = in.rz;
+      S->rz        = ta;
+      S->rr        = tb;
+      S->beta      = ta / in.rz;
+      S->stop_next = !(sqrt(tb) > in.eps);
+      S->iters     = in.iters + 1;
+      if (in.n_rr < in.hist_cap) rr_hist[in.n_rr] = tb, rz_hist[in.n_rr] = ta;
+      S->n_rr = in.n_rr + 1;
+    } else {
+      S->stop = 1;
+    }
+    S->x_pending = 1;
+  } else {
+    S->x_pending    = 0;
+    S->pAp          = ta;
+    const double al = in.rz / ta;
+    S->alpha        = al;
+    S->neg_alpha    = -al;
+    if (in.n_pAp < in.hist_cap) pAp_hist[in.n_pAp] = ta;
+    S->n_pAp = in.n_pAp + 1;
+  }
+}
+
+// The peer-mapped plane: local levels 1-2, the exchange over the P2PView, the step -- one launch, as cg_scalar_p2p_k is for CG.
+// The alpha step carries one value.  The prologue's step and the beta step carry two: r.z travels as exchange `seq`, r.r as
+// `seq + 1`, back to back, on the two slot sets alternately (the host advances the shared counter by two).  A rank stores its
+// r.r only behind the barrier that ends its reads of every peer's r.z, and the next launch's first value only after every
+// peer's r.r has arrived: no rank is two exchanges ahead of a peer, which is all the two slot sets need.
+// A stopped loop skips the exchange on every rank; a raised error (R->p2p_error, or the halo plan's) poisons the slots.
+template <int MODE>
+__global__ __launch_bounds__(1024) void pcg_scalar_p2p_k(uint32_t m, const double* __restrict__ qa, const double* __restrict__ qb,
+    PcgScalars* S, double* __restrict__ rr_hist, double* __restrict__ rz_hist, double* __restrict__ pAp_hist, PcgRankSums* R,
+    const P2PView* __restrict__ pv, unsigned long long seq, const int* __restrict__ haloErr)
+{
+  __shared__ double ldsA[16], ldsB[16];
+  const PcgScalars in = pcg_fetch(S);
+  double ta           = reduce_final_1024(m, qa, ldsA, 1);
+  double tb           = MODE == 2 ? 0.0 : reduce_final_1024(m, qb, ldsB, 1);
+  if (in.stop) { // identical on every rank: all of them skip the exchange, or none -- unless one has failed
+    if (__hip_atomic_load(&R->p2p_error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) || (haloErr && *haloErr)) p2p_poison_allreduce(pv);
+    return;
+  }
+  __syncthreads(); // the LDS arrays are reused
+  ta = p2p_allreduce_sum(pv, ta, seq, ldsA, &R->p2p_error);
+  // (uniform: an error is raised before the barriers inside the exchange; a failed first exchange does not start the second)
+  if (MODE != 2 && !__hip_atomic_load(&R->p2p_error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+    tb = p2p_allreduce_sum(pv, tb, seq + 1ull, ldsB, &R->p2p_error);
+  if (__hip_atomic_load(&R->p2p_error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+    if (threadIdx.x == 0) S->stop = 1;
+    p2p_poison_allreduce(pv); // (and tell the others at once)
+    return;
+  }
+  if (threadIdx.x == 0) pcg_apply<MODE>(S, in, ta, tb, rr_hist, rz_hist, pAp_hist);
+}
+
+// The communicator's plane, as cg_scalar_k<MODE, true / false> splits it: the rank's sums into R->v | one all-reduce per
+// value, in place | the step on the reduced sums.  TWO: both arrays (the prologue's step and the beta step), else qa alone
+template <bool TWO>
+__global__ __launch_bounds__(1024) void pcg_local_reduce_k(uint32_t m, const double* __restrict__ qa, const double* __restrict__ qb,
+    const PcgScalars* __restrict__ S, PcgRankSums* R)
+{
+  __shared__ double ldsA[16], ldsB[16];
+  const int stopped = S->stop;
+  const double ta   = reduce_final_1024(m, qa, ldsA, 1);
+  const double tb   = TWO ? reduce_final_1024(m, qb, ldsB, 1) : 0.0;
+  if (stopped || threadIdx.x != 0) return;
+  R->v[0] = ta;
+  if (TWO) R->v[1] = tb;
+}
+template <int MODE>
+__global__ __launch_bounds__(64) void pcg_scalar_reduced_k(PcgScalars* S, const PcgRankSums* __restrict__ R, double* __restrict__ rr_hist,
+    double* __restrict__ rz_hist, double* __restrict__ pAp_hist)
+{
+  const PcgScalars in = pcg_fetch(S);
+  const double ta = R->v[0], tb = MODE == 2 ? 0.0 : R->v[1];
+  if (in.stop || threadIdx.x != 0) return;
+  pcg_apply<MODE>(S, in, ta, tb, rr_hist, rz_hist, pAp_hist);
+}
+
+// =============================================================================
 // The diagonal, in the device's row order: d_i = the sum, in storage order from +0.0, of row i's stored entries whose column
 // is i (both in device numbering; Sell-C-sigma padding is a stored +0.0 and adds +0.0 where its column happens to be the
 // row).  One thread per row; correctness kernels, run once per solver handle.  bad[0] counts the rows whose d is not a finite

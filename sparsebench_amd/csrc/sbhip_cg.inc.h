@@ -804,14 +804,14 @@ void sb_cg_run_iters(sb_cg* s, int iters)
 // a failed wait on the peer-mapped paths ends the process with the rank in the message (both precisions).  (A rank that fails
 // poisons what it would have published, so the others leave their waits at once with code 2: the rank that saw the CAUSE --
 // code 1 or 3 -- is the one whose message matters.)
-static void cg_comm_failures(const sb_cg* s, int p2pError)
+static void comm_failures(const sb_halo* halo, int p2pError)
 {
-  if (s->halo && s->halo->p2p) {
+  if (halo && halo->p2p) {
     int e = 0;
-    HIP_CHECK(hipMemcpy(&e, s->halo->err, sizeof e, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&e, halo->err, sizeof e, hipMemcpyDeviceToHost));
     if (e == 1)
       SB_FATAL("rank %d: a neighbour's halo block did not arrive within %lld ms (SB_P2P_TIMEOUT_MS raises the bound, "
-               "SB_P2P_HALO=0 selects RCCL)", g.rank, s->halo->push.timeoutTicks / P2P_TICKS_PER_MS);
+               "SB_P2P_HALO=0 selects RCCL)", g.rank, halo->push.timeoutTicks / P2P_TICKS_PER_MS);
     if (e && p2pError != 1) p2pError = 2;
   }
   if (p2pError == 2)
@@ -822,6 +822,7 @@ static void cg_comm_failures(const sb_cg* s, int p2pError)
              "(SB_P2P_TIMEOUT_MS raises the bound, SB_P2P=0 selects the RCCL all-reduce)", g.rank,
         g.p2pTimeoutTicks / P2P_TICKS_PER_MS);
 }
+static void cg_comm_failures(const sb_cg* s, int p2pError) { comm_failures(s->halo, p2pError); }
 
 // the end of a solve, both precisions (the stream is idle): the region table of a timed solve, and the latches are released
 static void cg_solve_over(sb_cg* s)

@@ -30,6 +30,7 @@ struct PrecondLevel {
   const sb_matrix* A = nullptr;
   uint32_t n = 0;
   double* dinv = nullptr;            // level 0: the handle's own
+  sb_halo* halo = nullptr;           // level 0 of a several-rank handle: fills z's halo tail ahead of every SpMV
   double *r = nullptr, *z = nullptr; // levels 1 ..: the restricted residual and the correction (level 0: the caller's)
   SgsPlan* sgs = nullptr;            // SMOOTH_SGS
   struct {
@@ -133,7 +134,7 @@ static void precond_cycle(const PrecondPlan* M, const double* r, double* t, doub
       if (l || !firstDone)
         hipLaunchKernelGGL(poly_first_k, dim3(stream_grid(V.n, 256)), dim3(256), 0, g.stream, V.n, rl, dinv, V.cheb.d, zl, V.cheb.c.c1,
             stop);
-      poly_steps(V.A, dinv, V.cheb.c, rl, zl, V.cheb.d, V.cheb.w, stop, L == 1 ? l1rz : nullptr);
+      poly_steps(V.A, dinv, V.cheb.c, rl, zl, V.cheb.d, V.cheb.w, stop, L == 1 ? l1rz : nullptr, V.halo);
       if (!rc) break;
       launch_spmv(V.A, zl, V.cheb.w, nullptr, stop);
       mgp_restrict(V, rl, V.cheb.w, rc, stop);
@@ -183,6 +184,7 @@ static int precond_cycle_launches(const PrecondPlan* M)
 void RightPrecond::need_borrowable(const sb_matrix* m, const sb_pcg* M, const char* fn)
 {
   if (!M) SB_FATAL("%s: no PCG handle to take the preconditioner from", fn);
+  if (M->halo) SB_FATAL("%s: the PCG handle runs on several ranks; a solver that borrows its preconditioner runs on one rank", fn);
   if (M->A != m) SB_FATAL("%s: the PCG handle was made over another matrix: its preconditioner is that matrix's", fn);
   RightPrecond{ M }.need_closed(fn);
 }

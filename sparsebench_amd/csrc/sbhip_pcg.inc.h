@@ -1,5 +1,6 @@
 // sbhip_pcg.inc.h -- part of the single translation unit sbhip.hip (textual include, shares its static context): CG with a
-// diagonal preconditioner (kernels: pcg.hip.h).  Double precision, one rank, tree dot order.  The SpMV is the
+// diagonal preconditioner (kernels: pcg.hip.h).  Double precision, tree dot order; one rank, or (the diagonal and the
+// polynomial alone) several ranks over a halo plan.  The SpMV is the
 // one the matrix's kernel mode selects (launch_spmv: the reference-layout stream or the masked row programs, with their
 // fused p.Ap values; native CRS and generic C are followed by dot_l1_k).  The loop's vectors are allocations of the handle's
 // own: the matrix's tuned arena (sb_matrix::vecArena) is laid out for sb_cg's vectors and stays with sb_cg.
@@ -22,6 +23,10 @@ struct sb_pcg {
   // owned; NULL: the diagonal, which rides in pcg_update_r_k.  Else the sweeps, the polynomial or a V-cycle of either in its
   // place (sbhip_mg.inc.h); dinv is then 1 / diag(A) and level 0's
   struct PrecondPlan* pre = nullptr;
+  // several ranks: the plan that fills the halo tail of every SpMV input, and the ranks' block (pcg.hip.h); NULL on
+  // one rank
+  sb_halo* halo  = nullptr;
+  PcgRankSums* R = nullptr;
 };
 // the diagonal in the device's row order; bad_dev: NULL, or two uint32 (rows without a finite positive diagonal, the first of
 // them) preset to {0, 0xFFFFFFFF}
@@ -64,6 +69,33 @@ void sb_pcg_update_r_native(uint32_t n, double nalpha, const double* Ap_dev, dou
   test_block_done(S);
 }
 
+// The communicator's plane's local reduce (pcg_local_reduce_k) in one process: the level-1 values of a.b and, two != 0, of a.a
+// over n rows by dot_l1_k, then the kernel; out: the block's two sums behind it, preset to { -1.0, -2.0 }: the kernel writes one
+// (two == 0), both, or (stopped != 0: the block says the loop has exited) neither
+void sb_pcg_local_reduce_native(uint32_t n, int two, int stopped, const double* a_dev, const double* b_dev, double out[2])
+{
+  need_init();
+  need_aligned16({ a_dev, b_dev }, "sb_pcg_local_reduce_native", "vectors");
+  const uint32_t m = (n + 255u) >> 8;
+  double *la = (double*)sb_malloc(((size_t)m + 4) * sizeof(double)), *lb = (double*)sb_malloc(((size_t)m + 4) * sizeof(double));
+  if (n) {
+    hipLaunchKernelGGL(dot_l1_k, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, a_dev, b_dev, la, (const int*)zero_flag());
+    hipLaunchKernelGGL(dot_l1_k, dim3(vec_stream_grid(n)), dim3(1024), 0, g.stream, n, a_dev, a_dev, lb, (const int*)zero_flag());
+  }
+  PcgScalars h = zeroed<PcgScalars>();
+  h.stop       = stopped ? 1 : 0;
+  PcgScalars* S = test_block(h);
+  PcgRankSums r = zeroed<PcgRankSums>();
+  r.v[0] = -1.0, r.v[1] = -2.0;
+  PcgRankSums* R = test_block(r);
+  if (two) hipLaunchKernelGGL(pcg_local_reduce_k<true>, dim3(1), dim3(1024), 0, g.stream, m, (const double*)la, (const double*)lb, (const PcgScalars*)S, R);
+  else hipLaunchKernelGGL(pcg_local_reduce_k<false>, dim3(1), dim3(1024), 0, g.stream, m, (const double*)la, (const double*)lb, (const PcgScalars*)S, R);
+  r = read_block(R);
+  out[0] = r.v[0], out[1] = r.v[1];
+  test_block_done(S);
+  sb_free(R), sb_free(la), sb_free(lb);
+}
+
 // precond: "Jacobi", or "SGS" / "MG (level l)", which have no caller's diagonal to fall back on
 static bool dinv_host_allowed(const char* precond) { return precond[0] == 'J'; }
 // dinv = 1 / diag(A) in the device's row order.  Rows without a finite positive diagonal are counted on the device, by
@@ -87,13 +119,25 @@ static void jacobi_dinv(const sb_matrix* m, double* dinv_dev, const char* fn, co
   HIP_CHECK(hipStreamSynchronize(g.stream));
 }
 
-// fn: the entry point as messages name it; precond: as jacobi_dinv takes it
+// Several ranks: the process is in a communicator of more than one rank and the caller gave the halo plan of this
+// matrix.  Everything else is one rank's business, or need_one_rank's refusal
+static bool pcg_several_ranks(const sb_matrix* m, const sb_halo* halo, const char* fn)
+{
+  if (!halo || !multi_rank() || sb_comm_size() < 2) return false;
+  if (halo->nr != m->nr) SB_FATAL("%s: the halo plan has %u rows, the matrix %u", fn, halo->nr, m->nr);
+  if (m->nr + (uint32_t)halo->externalCount != m->nc)
+    SB_FATAL("%s: the halo plan receives %d entries, the matrix has %u halo columns", fn, halo->externalCount, m->nc - m->nr);
+  return true;
+}
+
+// fn: the entry point as messages name it; precond: as jacobi_dinv takes it; ranksOk: the preconditioner runs on several ranks
 static sb_pcg* pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const double* dinv_host,
-    const char* fn, const char* precond)
+    const char* fn, const char* precond, bool ranksOk)
 {
   need_init();
   need_dp(m, fn, "PCG");
-  need_one_rank(m, halo, fn, "PCG");
+  const bool ranks = ranksOk && pcg_several_ranks(m, halo, fn);
+  if (!ranks) need_one_rank(m, halo, fn, "PCG");
   need_tree(fn, "PCG", "sb_cg");
   if (dinv_host)
     for (uint32_t i = 0; i < m->nr; i++)
@@ -117,6 +161,11 @@ static sb_pcg* pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_hos
   }
   s->S = (PcgScalars*)sb_malloc(sizeof(PcgScalars));
   HIP_CHECK(hipMemset(s->S, 0, sizeof(PcgScalars)));
+  if (ranks) {
+    s->halo = halo;
+    s->R    = (PcgRankSums*)sb_malloc(sizeof(PcgRankSums));
+    HIP_CHECK(hipMemset(s->R, 0, sizeof(PcgRankSums))); // never an uninitialised failure flag (sb_pcg_start points the push kernels at it)
+  }
   // p.Ap: sized as sb_cg sizes the array its SpMV kernels write (4 per 256 rows, tail +0.0)
   const size_t lb = (4 * (size_t)s->nGroups + 4) * sizeof(double);
   double** l1s[]  = { &s->l1pAp, &s->l1rz, &s->l1rr };
@@ -131,7 +180,7 @@ static sb_pcg* pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_hos
 
 sb_pcg* sb_pcg_create(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, const double* dinv_host)
 {
-  return pcg_create(m, halo, b_host, xexact_host, dinv_host, "sb_pcg_create", "Jacobi");
+  return pcg_create(m, halo, b_host, xexact_host, dinv_host, "sb_pcg_create", "Jacobi", true);
 }
 
 int sb_pcg_history(const sb_pcg* s, double* rr_out, int rr_cap, double* rz_out, int rz_cap, double* pAp_out, int pAp_cap, int* n_pAp)
@@ -157,11 +206,19 @@ void sb_pcg_dinv(const sb_pcg* s, double* dinv_host)
   download_original(s->A, s->dinv, dinv_host);
 }
 
-// max|x - xexact| (solverCheckResidual, src/CGSolver.c:40-60); 0.0 without an exact solution
+// max|x - xexact| (solverCheckResidual, src/CGSolver.c:40-60), over every rank as sb_cg_check_residual takes it; 0.0 without an
+// exact solution
 double sb_pcg_check_residual(const sb_pcg* s)
 {
   need_init();
-  return max_abs_diff_host(s->nr, s->x, s->xexact);
+  if (s->halo && (!s->xexact || s->nr == 0)) return 0.0; // (as sb_cg_check_residual: such a rank stays out of the reduction)
+  double m = max_abs_diff_host(s->nr, s->x, s->xexact);
+  if (s->halo) { // commReduction(&residual, MAX), src/CGSolver.c:55
+    sb_h2d(g.scalar, &m, sizeof m);
+    sb_comm_reduction(g.scalar, 0);
+    sb_d2h(&m, g.scalar, sizeof m);
+  }
+  return m;
 }
 
 double sb_pcg_loop_ms(const sb_pcg* s) { return (double)s->clock.ms; }

@@ -60,7 +60,7 @@ void sb_pcg_apply_precond(sb_pcg* s, const double* r_host, double* z_host)
   need_init();
   if (s->clock.open) SB_FATAL("sb_pcg_apply_precond between sb_pcg_start and sb_pcg_finish: the solve's vectors are in flight");
   if (!s->nr) return;
-  const size_t nb = (size_t)s->nr * sizeof(double) + 4096;
+  const size_t nb = (size_t)s->nc * sizeof(double) + 4096; // (nc: the polynomial's z is an SpMV operand; several ranks: collective)
   double *ar = (double*)sb_malloc(nb), *at = (double*)sb_malloc(nb), *az = (double*)sb_malloc(nb);
   upload_permuted(s->A, r_host, ar);
   precond_apply(s, ar, at, az, zero_flag());
@@ -75,7 +75,7 @@ double sb_pcg_apply_precond_ms(sb_pcg* s, int reps)
   need_init();
   if (s->clock.open) SB_FATAL("sb_pcg_apply_precond_ms between sb_pcg_start and sb_pcg_finish: the solve's vectors are in flight");
   if (!s->nr || reps < 1) return 0.0;
-  const size_t nb = (size_t)s->nr * sizeof(double) + 4096;
+  const size_t nb = (size_t)s->nc * sizeof(double) + 4096;
   double *ar = (double*)sb_malloc(nb), *at = (double*)sb_malloc(nb), *az = (double*)sb_malloc(nb);
   sb_d2d(ar, s->b, (size_t)s->nr * sizeof(double));
   LoopClock c;
@@ -97,6 +97,8 @@ void sb_pcg_free(sb_pcg* s)
   if (!s) return;
   HIP_CHECK(hipStreamSynchronize(g.stream));
   s->clock.destroy();
+  if (s->halo) halo_push_watch(s->halo, &s->R->p2p_error, false);
+  sb_free(s->R);
   precond_release(s);
   sb_free(s->r), sb_free(s->z), sb_free(s->p), sb_free(s->Ap), sb_free(s->x), sb_free(s->b), sb_free(s->dinv), sb_free(s->xexact);
   sb_free(s->S), sb_free(s->l1pAp), sb_free(s->l1rz), sb_free(s->l1rr), sb_free(s->rr_hist), sb_free(s->rz_hist), sb_free(s->pAp_hist);
@@ -107,16 +109,51 @@ void sb_pcg_free(sb_pcg* s)
 // selected SpMV kernel has a fused dot; native CRS and generic C add the dot pass: 6.  The polynomial's plan: the r update counts
 // among the cycle's launches, as level 0's step 1, and the cycle's last kernel makes the r.z values: 4 (+ 1) +
 // precond_cycle_launches.  The sweeps' plan: the r update makes no z, and the r.z pass follows the cycle: 6 (+ 1) +
-// precond_cycle_launches
+// precond_cycle_launches.
+// Several ranks add, as sb_cg_launches_per_body counts them for CG: per halo exchange -- one for p, one per
+// polynomial step behind the first -- the push and the pull (peer-mapped) or the pack kernel in front of the send / recv group;
+// and, without the in-kernel all-reduce, one more kernel per scalar step (local reduce | all-reduces | step).  The all-reduce and
+// send / recv calls themselves: sb_pcg_collectives_per_body
+static int pcg_halo_exchanges(const sb_pcg* s) { return !s->halo ? 0 : s->pre ? s->pre->lev[0].cheb.c.steps : 1; }
 int sb_pcg_launches_per_body(const sb_pcg* s)
 {
-  const int base = spmv_dot_kind(s->A) ? 5 : 6;
-  if (!s->pre) return base;
-  return base + (s->pre->smoother == SMOOTH_CHEB ? -1 : 1) + precond_cycle_launches(s->pre);
+  int n = spmv_dot_kind(s->A) ? 5 : 6;
+  if (s->pre) n += (s->pre->smoother == SMOOTH_CHEB ? -1 : 1) + precond_cycle_launches(s->pre);
+  if (!s->halo) return n;
+  const sb_halo* h = s->halo;
+  const int per    = halo_p2p_active(h) ? (h->totalSend ? 1 : 0) + (h->indegree ? 1 : 0) : h->totalSend ? 1 : 0;
+  return n + pcg_halo_exchanges(s) * per + (p2p_dots() ? 0 : 2);
+}
+// communicator calls per loop body (RCCL / transport): without the peer-mapped paths 3 all-reduces (p.Ap; r.z and r.r) and a
+// send / recv group per halo exchange; 0 on one rank
+int sb_pcg_collectives_per_body(const sb_pcg* s)
+{
+  if (!s->halo) return 0;
+  return (p2p_dots() ? 0 : 3) + (halo_p2p_active(s->halo) ? 0 : pcg_halo_exchanges(s));
 }
 
 template <int MODE> static void pcg_scalar_launch(sb_pcg* s)
 {
+  const double* qa = MODE == 2 ? s->l1pAp : s->l1rz;
+  if (s->halo && p2p_dots()) { // local reduce, the in-kernel all-reduce(s) and the step in ONE launch; two values: two exchanges
+    hipLaunchKernelGGL((pcg_scalar_p2p_k<MODE>), dim3(1), dim3(1024), 0, g.stream, s->nGroups, qa, (const double*)s->l1rr, s->S,
+        s->rr_hist, s->rz_hist, s->pAp_hist, s->R, (const P2PView*)g.p2pView, g.p2pSeq + 1ull,
+        (const int*)(s->halo->p2p ? s->halo->err : nullptr));
+    HIP_CHECK(hipGetLastError());
+    g.p2pSeq += MODE == 2 ? 1ull : 2ull; // (shared with sb_cg: solves of either kind alternate on one counter)
+    return;
+  }
+  if (s->halo) { // local reduce | one all-reduce per value, in place | the step on the reduced sums
+    hipLaunchKernelGGL((pcg_local_reduce_k<MODE != 2>), dim3(1), dim3(1024), 0, g.stream, s->nGroups, qa, (const double*)s->l1rr,
+        (const PcgScalars*)s->S, s->R);
+    HIP_CHECK(hipGetLastError());
+    sb_comm_reduction(&s->R->v[0], 1);
+    if (MODE != 2) sb_comm_reduction(&s->R->v[1], 1);
+    hipLaunchKernelGGL((pcg_scalar_reduced_k<MODE>), dim3(1), dim3(64), 0, g.stream, s->S, (const PcgRankSums*)s->R, s->rr_hist,
+        s->rz_hist, s->pAp_hist);
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
   hipLaunchKernelGGL((pcg_scalar_k<MODE>), dim3(1), dim3(1024), 0, g.stream, s->nGroups, (const double*)(MODE == 2 ? s->l1pAp : s->l1rz),
       (const double*)s->l1rr, s->S, s->rr_hist, s->rz_hist, s->pAp_hist);
   HIP_CHECK(hipGetLastError());
@@ -133,6 +170,9 @@ static void pcg_body(sb_pcg* s, int k)
         k == 1 ? 1 : 0);
     HIP_CHECK(hipGetLastError());
   }
+  // several ranks: p's halo tail, by the push and pull launches or by pack | send / recv.  No folded form (the fold, the push
+  // inside the SpMV, the pull inside the pattern SpMV): sb_comm_halo_fold and sb_comm_halo_push_inside do not apply to PCG
+  halo_exchange(s->halo, s->p, stop, nullptr, true);
   if (spmv_dot_kind(s->A)) {
     launch_spmv(s->A, s->p, s->Ap, s->l1pAp, stop);
   } else {
@@ -158,9 +198,14 @@ void sb_pcg_start(sb_pcg* s, int itermax, double eps)
   PcgScalars h = zeroed<PcgScalars>();
   h.itermax = itermax, h.eps = eps, h.hist_cap = s->hist_cap;
   write_block(s->S, &h);
+  if (s->halo) { // the push kernels of this solve look at ITS failure flag (halo_push_watch)
+    HIP_CHECK(hipMemset(s->R, 0, sizeof(PcgRankSums)));
+    halo_push_watch(s->halo, &s->R->p2p_error, true);
+  }
   // prologue: x0 = 0, p = 1.0 x + 0.0 x = 0, Ap = A p, r = 1.0 b + (-1.0) Ap, z = r o dinv, r.r, r.z, the loop test for k = 1
   HIP_CHECK(hipMemsetAsync(s->x, 0, (size_t)s->nr * sizeof(double), g.stream));
   HIP_CHECK(hipMemsetAsync(s->p, 0, (size_t)s->nc * sizeof(double), g.stream));
+  halo_exchange(s->halo, s->p, nullptr); // (as sb_cg's prologue: outside the loop's staging areas)
   launch_spmv(s->A, s->p, s->Ap, nullptr, nullptr);
   pcg_residual_and_z<1>(s);
   pcg_scalar_launch<0>(s);
@@ -188,6 +233,7 @@ int sb_pcg_finish(sb_pcg* s)
   }
   HIP_CHECK(hipStreamSynchronize(g.stream));
   s->clock.read();
+  if (s->halo) comm_failures(s->halo, read_block(s->R).p2p_error); // a failed wait ends the process with the rank in the message
   return read_block(s->S).iters + 1; // the value of k when the for loop exits
 }
 

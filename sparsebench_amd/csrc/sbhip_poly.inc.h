@@ -36,14 +36,16 @@ static PolyCoef poly_coeffs(int steps, double lmax, double ratio)
 
 // steps 2 .. steps behind step 1 (z = d = (r o dinv) * c1 from zero, or mgp_first from a guess): w = A z by the selected SpMV
 // without a fused dot, then poly_step_k.  z is an SpMV operand (nc entries and the padding the SpMV kernels expect); d, w: nr
-// doubles.  l1rz != NULL: the last step leaves the level-1 values of r.z there
+// doubles.  l1rz != NULL: the last step leaves the level-1 values of r.z there.  halo != NULL (several ranks): z's
+// halo tail is filled ahead of every SpMV, as sb_cg fills p's
 static void poly_steps(const sb_matrix* m, const double* dinv, const PolyCoef& c, const double* r, double* z, double* d, double* w,
-    const int* stop, double* l1rz)
+    const int* stop, double* l1rz, sb_halo* halo = nullptr)
 {
   const uint32_t n = m->nr;
   if (!n) return;
   const dim3 grid(vec_stream_grid(n)), block(1024);
   for (int j = 2; j <= c.steps; j++) {
+    if (halo) halo_exchange(halo, z, stop, nullptr, true);
     launch_spmv(m, z, w, nullptr, stop);
     if (j == c.steps && l1rz)
       hipLaunchKernelGGL(poly_step_k<1>, grid, block, 0, g.stream, n, r, (const double*)w, dinv, d, z, c.a[j], c.b[j], l1rz, stop);

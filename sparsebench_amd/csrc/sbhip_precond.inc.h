@@ -32,12 +32,12 @@ static void mg_check_hierarchy(const char* fn, const sb_matrix* m, int nCoarse, 
     for (int l = 0; l < nCoarse; l++) mg_fw_check(fn, *fw, l, l ? coarse[l - 1]->nr : m->nr, coarse[l]->nr);
 }
 
-// a handle whose plan has the levels' matrices and nothing else yet; level 0's dinv is the handle's.  who: the preconditioner as
-// the diagonal's refusal names it
+// a handle whose plan has the levels' matrices and nothing else yet; level 0's dinv is the handle's.
+// who: the preconditioner as the diagonal's refusal names it; ranksOk: as pcg_create takes it
 static sb_pcg* precond_create(const char* fn, const char* who, int kind, const sb_matrix* m, sb_halo* halo, const double* b_host,
-    const double* xexact_host, int nCoarse, const sb_matrix* const* coarse)
+    const double* xexact_host, int nCoarse, const sb_matrix* const* coarse, bool ranksOk = false)
 {
-  sb_pcg* s      = pcg_create(m, halo, b_host, xexact_host, nullptr, fn, who);
+  sb_pcg* s      = pcg_create(m, halo, b_host, xexact_host, nullptr, fn, who, ranksOk);
   PrecondPlan* M = new PrecondPlan();
   M->kind        = kind;
   M->lev.resize((size_t)nCoarse + 1);
@@ -118,7 +118,20 @@ static void cheb_level(PrecondLevel& V, int steps, double lmax, double ratio, co
   V.cheb.d = (double*)sb_malloc(nb), V.cheb.w = (double*)sb_malloc(nb);
 }
 
-// the polynomial alone: a cycle of one level, whose row bounds the handle keeps
+// Between two of the cycle's halo exchanges lies no all-reduce, so what keeps a rank from running two exchanges ahead of a
+// neighbour (the two staging areas' condition) is the pull itself: a rank pulls from every rank it pushes to.  That holds where
+// the ranks it sends to are the ranks it receives from, as a structurally symmetric matrix gives
+static void poly_need_mutual_neighbours(const sb_halo* h, const char* fn)
+{
+  std::vector<int> to(h->destinations), from(h->sources);
+  std::sort(to.begin(), to.end()), std::sort(from.begin(), from.end());
+  if (to != from)
+    SB_FATAL("%s: rank %d sends halo entries to %zu ranks and receives from %zu others: on several ranks the polynomial needs a "
+             "matrix whose ranks are each other's neighbours (a structurally symmetric one)", fn, g.rank, to.size(), from.size());
+}
+
+// the polynomial alone: a cycle of one level, whose row bounds the handle keeps.  Several ranks: steps, lmax and ratio are
+// collective arguments
 sb_pcg* sb_pcg_create_poly(const sb_matrix* m, sb_halo* halo, const double* b_host, const double* xexact_host, int steps, double lmax,
     double ratio)
 {
@@ -127,10 +140,22 @@ sb_pcg* sb_pcg_create_poly(const sb_matrix* m, sb_halo* halo, const double* b_ho
   if (ratio == 0.0) ratio = 16.0;
   if (!(ratio > 1.0 && ratio < INFINITY)) SB_FATAL("%s: ratio = %g: lmax / lmin must be finite and greater than 1", fn, ratio);
   if (!(lmax < INFINITY)) SB_FATAL("%s: lmax = %g: the caller's lmax must be finite (0.0 or less: the bound)", fn, lmax);
-  sb_pcg* s      = precond_create(fn, "Chebyshev polynomial", 4, m, halo, b_host, xexact_host, 0, nullptr);
+  sb_pcg* s      = precond_create(fn, "Chebyshev polynomial", 4, m, halo, b_host, xexact_host, 0, nullptr, true);
   PrecondPlan* M = s->pre;
   M->smoother = SMOOTH_CHEB, M->steps = M->coarseSteps = steps;
-  M->g        = poly_rowbound(m, s->dinv);
+  if (s->halo) { // several ranks: the row bound reads dinv at the halo columns; the cycle exchanges z ahead of its SpMVs
+    poly_need_mutual_neighbours(s->halo, fn);
+    halo_exchange(s->halo, s->dinv, nullptr);
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    M->lev[0].halo = s->halo;
+  }
+  M->g = poly_rowbound(m, s->dinv);
+  if (s->halo && !(lmax > 0.0)) { // the largest bound of any rank's rows: MAX is exact and order-free
+    lmax = poly_lmax_bound(M->g, fn, "");
+    sb_h2d(g.scalar, &lmax, sizeof lmax);
+    sb_comm_reduction(g.scalar, 0);
+    sb_d2h(&lmax, g.scalar, sizeof lmax);
+  }
   cheb_level(M->lev[0], steps, lmax, ratio, &M->g, fn, "");
   HIP_CHECK(hipStreamSynchronize(g.stream));
   return s;

@@ -24,7 +24,8 @@ int main(int argc, char** argv)
   initParameter(&param);
   sbh_options o;
   char msg[MAXLINE];
-  const int refused = sbh_parse_options(argc, argv, &param, &o, msg, sizeof msg);
+  int refused = sbh_parse_options(argc, argv, &param, &o, msg, sizeof msg);
+  if (!refused && o.action == SBH_ACT_RUN) refused = sbh_check_ranks(&o, comm.size, msg, sizeof msg); /* (the launcher's ranks) */
   if (o.action == SBH_ACT_HELP) {
     if (commIsMaster(&comm)) printf("%s", sbh_help_text());
     commAbort(&comm, "");

@@ -31,6 +31,8 @@ static const char* kHelp =
     "             -m irregular, generated). Forms its own Galerkin products (not with -g). Takes -l (default up to 4) and -d.\n"
     "  -P <sgs|mg|mgfw|poly|mgpoly>   One of those preconditioners for -t bicgstab in its diagonal's place, with -l, -d, -g, -a as for -p.\n"
     "             With -t gmres it is the right preconditioner of GMRES(m), and -P jacobi (the diagonal) is one more.\n"
+    "  Several ranks: -t cg, -t spmv, and -t pcg with -p jacobi or -p poly [-d n]; every other preconditioner, -g, -a,\n"
+    "             -t gmres and -t bicgstab run on one rank.\n"
     "  -r <int>   GMRES restart length. Default 30.\n"
     "  -n <int>   Number of right-hand sides for -t cg. Default 1.\n"
     "  -x <int>   Size in x for generated matrix, ignored if MM file is loaded. Default 100.\n"
@@ -168,4 +170,22 @@ int sbh_parse_options(int argc, char** argv, Parameter* param, sbh_options* o, c
     if (!sbh_mg_levels(param->nx, param->ny, param->nz, pc->levels, why, sizeof why)) return refuse(msg, cap, "%s\n", why);
   }
   return 0;
+}
+
+/* what of the parsed options runs on `size` ranks: -t cg, -t spmv, and -t pcg with the Jacobi diagonal or -p poly
+ * [-d n].  The sweeps, the V-cycles (with -g and -a), GMRES and BiCGStab are refused here with the messages of their solves */
+int sbh_check_ranks(const sbh_options* o, int size, char* msg, size_t cap)
+{
+  if (cap) msg[0] = '\0';
+  if (size < 2) return 0;
+  if (o->type == SBH_BENCH_GMRES) return refuse(msg, cap, "GMRES: runs on one rank\n");
+  if (o->type == SBH_BENCH_BICGSTAB) return refuse(msg, cap, "BiCGStab: runs on one rank\n");
+  if (o->type != SBH_BENCH_PCG) return 0;
+  switch (o->precond.kind) {
+  case SBH_PRECOND_SGS: return refuse(msg, cap, "SGS: runs on one rank\n");
+  case SBH_PRECOND_MG:
+  case SBH_PRECOND_MGFW:
+  case SBH_PRECOND_MGPOLY: return refuse(msg, cap, "MG: runs on one rank\n");
+  default: return 0; /* the diagonal and the polynomial */
+  }
 }

@@ -460,13 +460,14 @@ static sb_pcg* build_pcg(Comm* comm, Parameter* param, void* dev_matrix, const d
   const sb_matrix* m = (const sb_matrix*)dev_matrix;
   sb_pcg* s;
   switch (spec->kind) {
-  case SBH_PRECOND_JACOBI: return sb_pcg_create(m, NULL, b, xexact, NULL);
+  /* the diagonal and the polynomial run on several ranks: they take the Comm's halo plan, NULL on one rank */
+  case SBH_PRECOND_JACOBI: return sb_pcg_create(m, (sb_halo*)comm->dev, b, xexact, NULL);
   case SBH_PRECOND_SGS:
     s = sb_pcg_create_sgs(m, NULL, b, xexact);
     if (commIsMaster(comm)) printf("Preconditioner: SGS (multicolour symmetric Gauss-Seidel), nC = %d\n", sb_pcg_colours(s));
     return s;
   case SBH_PRECOND_POLY: {
-    s = sb_pcg_create_poly(m, NULL, b, xexact, spec->steps ? spec->steps : 3, 0.0, 0.0);
+    s = sb_pcg_create_poly(m, (sb_halo*)comm->dev, b, xexact, spec->steps ? spec->steps : 3, 0.0, 0.0);
     double iv[2];
     sb_pcg_poly_interval(s, iv);
     if (commIsMaster(comm))

@@ -427,6 +427,7 @@ class Problem:
         self.fdtype = np.float32 if precision == "single" else np.float64
         self.fmt = fmt
         self.upload = upload
+        self.rank, self.size = int(rank), int(size)
         # what a geometric hierarchy is regenerated from (PCG(precond="mg", levels=...))
         self.filename, self.dims, self.Cc, self.sigma_arg = os.fsdecode(filename), (int(nx), int(ny), int(nz)), Cc, sigma
         L = capi.load()
@@ -459,6 +460,7 @@ class Problem:
         self.H = host("double")
         self.precision, self.fdtype, self.fmt, self.upload = "double", np.float64, fmt, upload
         self.filename, self.dims, self.Cc, self.sigma_arg = "memory", (1, 1, 1), Cc, sigma
+        self.rank, self.size = 0, 1
         self.ptr = self.H.sbh_problem_create_csr(len(ptr) - 1, ptr.ctypes.data_as(vp), col.ctypes.data_as(vp), val.ctypes.data_as(vp),
                                                  0 if fmt == "crs" else 1, Cc, sigma, 1 if upload else 0)
         for i, name in enumerate(_SCALARS):
@@ -966,7 +968,9 @@ class PCG(_BodySolver):
     `galerkin=True` for mg_galerkin's coarse operators in the regenerated ones' place (`galerkin="device"`: the same operators formed on
     the device, DESIGN 4.17: no scipy, no files), or `coarse` as "mgfw" takes it; `coarsening="aggregation"` (with `theta`, `omega_s`
     and `levels`) for mg_aggregation's hierarchy made from the matrix alone, on any problem.  Double
-    precision, one rank, tree dot order."""
+    precision, tree dot order.  One rank -- or, for "jacobi" (with or without a caller's dinv: the rank's nr local entries) and
+    "poly" alone, a `Problem(..., rank=r, size=P)` of several: every call is then collective, steps, lmax and ratio
+    are the same on every rank, and the other preconditioners raise ValueError before the library is touched."""
 
     PREFIX, NAME = "sb_pcg", "PCG"
     COUNTERS = ("stop", "stop_next", "iters", "n_rr", "n_pAp")
@@ -974,6 +978,9 @@ class PCG(_BodySolver):
     def __init__(self, problem, dinv=None, precond="jacobi", levels=None, coarse=None, steps=None, lmax=None, ratio=None,
                  coarse_steps=None, galerkin=False, coarsening="geometric", theta=None, omega_s=None):
         self._need_double(problem)
+        if getattr(problem, "size", 1) > 1 and precond in ("sgs", "mg", "mgfw", "mgpoly"):
+            raise ValueError("PCG: precond=%r runs on one rank (the problem is rank %d of %d); 'jacobi' and 'poly' run on several"
+                             % (precond, problem.rank, problem.size))
         if coarsening not in ("geometric", "aggregation"):
             raise ValueError("coarsening must be 'geometric' or 'aggregation', got %r" % (coarsening,))
         if coarsening == "aggregation":
@@ -1031,6 +1038,10 @@ class PCG(_BodySolver):
             self.ptr = self.L.sb_pcg_create_poly(problem.matrix, problem.halo, _ptr(b), _ptr(xe), steps, lmax, ratio)
         else:
             self.ptr = self.L.sb_pcg_create(problem.matrix, problem.halo, _ptr(b), _ptr(xe), _ptr(self._dinv_arg(dinv)))
+
+    def collectives_per_body(self):
+        """communicator calls per loop body (sb_pcg_collectives_per_body); 0 on one rank"""
+        return self.L.sb_pcg_collectives_per_body(self.ptr)
 
     @staticmethod
     def _poly_args(steps, lmax, ratio, what="steps"):
