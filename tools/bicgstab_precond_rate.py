@@ -17,38 +17,14 @@ the regenerated hierarchy (generated problems only) and on device-formed Galerki
 On convection-diffusion GMRES(30) runs beside them.  No ratio is fixed in advance: `merge` records the range of every same-process
 ratio over the processes (between processes a loop moves with placement, DESIGN 4.1: only same-process ratios count).
 """
-import argparse
 import json
-import math
 import os
-import statistics
-import sys
 import tempfile
 
-import numpy as np
+import ratelib
+from ratelib import FMT, hostapi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-from sparsebench_amd import capi, hostapi, srchash  # noqa: E402
-from bicgstab_rate import find_k, to_eps, write_convdiff  # noqa: E402
-
-FMT = dict(fmt="scs", Cc=64, sigma=256)
-
-
-def galerkin_levels(p, dims, owned):
-    """[(Problem, P, 1.0), ...] of a FILE matrix on a known grid: the trilinear P and the device's P^T A P, to the depth the grid
-    allows (a generated problem takes PCG(galerkin="device"))"""
-    out, fine = [], p
-    for _ in range(hostapi.mg_levels(*dims) - 1):
-        P = hostapi.mg_trilinear(*dims)
-        dims = tuple(d // 2 for d in dims)
-        Ac, _ = hostapi.galerkin_product(fine, P, dims[0] * dims[1] * dims[2])
-        q = hostapi.Problem.from_csr(*Ac, **FMT)
-        owned.append(q)
-        out.append((q, P, 1.0))
-        fine = q
-    return out
+RATIOS = ("over_jacobi", "us_per_body", "apply_ms")
 
 
 def handles(p, generated, dims, owned):
@@ -60,20 +36,16 @@ def handles(p, generated, dims, owned):
         h["mgpoly_1_regenerated"] = hostapi.BiCGStab(p, precond="mgpoly", steps=1)
         h["mgpoly_1_galerkin"] = hostapi.BiCGStab(p, precond="mgpoly", steps=1, galerkin="device")
     else:
-        h["mgpoly_1_galerkin"] = hostapi.BiCGStab(p, precond="mgpoly", steps=1, coarse=galerkin_levels(p, dims, owned))
+        h["mgpoly_1_galerkin"] = hostapi.BiCGStab(p, precond="mgpoly", steps=1, coarse=ratelib.galerkin_levels(p, dims, owned))
         h["gmres30"] = hostapi.GMRES(p, restart=30)
     return h
 
 
 def measure(a, p, solvers, eps):
-    kind = lambda n: "gmres" if n == "gmres30" else "bicgstab"  # noqa: E731
-    ks = {n: find_k(kind(n), s, a.itermax, eps, a.piece) for n, s in solvers.items()}
-    reached = {n: 1 < k < a.itermax for n, k in ks.items()}
-    ms = {n: [] for n in solvers if reached[n]}
-    for _ in range(a.repeats):
-        for n in ms:
-            ms[n].append(to_eps(kind(n), solvers[n], ks[n], eps))
-    med = {n: statistics.median(v) for n, v in ms.items()}
+    ks = ratelib.find_ks(solvers, a, eps)
+    reached = ratelib.reached(ks, a.itermax)
+    ms = ratelib.to_eps_rounds(solvers, ks, eps, a.repeats, reached, named=True)
+    med = ratelib.medians(ms)
     out = {}
     for n, s in solvers.items():
         e = {"k": ks[n], "reached_eps": reached[n]}
@@ -89,20 +61,18 @@ def measure(a, p, solvers, eps):
 
 
 def run(a):
-    L = capi.init(0)
-    out = {"device": L.sb_device_name().decode(), "library": L.sb_version().decode(), "csrc_hash": srchash.csrc_hash(),
-           "format": "Sell-64-256", "eps_rel": 1e-10, "repeats": a.repeats}
+    L = ratelib.capi.init(0)
+    out = dict(ratelib.process_header(L), format="Sell-64-256", eps_rel=1e-10, repeats=a.repeats)
     owned = []
     if a.problem == "cd":
         with tempfile.TemporaryDirectory(prefix="bicgstab_precond_rate_") as d:
-            p = hostapi.Problem(write_convdiff(os.path.join(d, "cd_%d.mtx" % a.cd), a.cd), 1, 1, 1, **FMT)
+            p = hostapi.Problem(ratelib.write_convdiff(os.path.join(d, "cd_%d.mtx" % a.cd), a.cd), 1, 1, 1, **FMT)
         out["problem"], dims = "convection-diffusion %d^3" % a.cd, (a.cd,) * 3
     else:
         p = hostapi.Problem("generate", a.n, a.n, a.n, **FMT)
         out["problem"], dims = "hpcg%d" % a.n, (a.n,) * 3
     out["rows"] = p.nr
-    b = p.rhs()[0]
-    eps = 1e-10 * math.sqrt(float(np.dot(b, b)))
+    eps = ratelib.rel_eps(p)
     solvers = handles(p, a.problem == "hpcg", dims, owned)
     out["modes"] = {}
     for mode in sorted({p.use_packed(5), p.use_packed(0)}, reverse=True):
@@ -114,62 +84,27 @@ def run(a):
     for q in owned:
         q.free()
     p.free()
-    text = json.dumps(out)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    ratelib.emit(out, a.out)
 
 
 def merge(a):
-    runs = [json.load(open(f)) for f in a.files]
-    head = {k: runs[0][k] for k in ("library", "csrc_hash")}
-    if any({k: r[k] for k in head} != head for r in runs):
-        raise SystemExit("the runs do not describe the same build")
+    runs = ratelib.load_runs(a.files)
     ranges = {}
     for r in runs:
         for mode, rows in r["modes"].items():
             for name, e in rows.items():
-                slot = ranges.setdefault(r["problem"], {}).setdefault(mode, {}).setdefault(name, {"k": e["k"], "over_jacobi": [],
-                                                                                                 "us_per_body": [], "apply_ms": []})
-                if e["k"] != slot["k"]:
-                    raise SystemExit("k of %s differs between processes" % name)
-                for key in ("over_jacobi", "us_per_body", "apply_ms"):
-                    if key in e:
-                        slot[key].append(e[key])
-    for prob in ranges.values():
-        for rows in prob.values():
-            for slot in rows.values():
-                for key in ("over_jacobi", "us_per_body", "apply_ms"):
-                    slot[key] = [min(slot[key]), max(slot[key])] if slot[key] else None
-    out = dict(head, processes=len(runs), devices=sorted({r["device"] for r in runs}),
-               note="one entry per fresh process and problem; over_jacobi = loop time to eps = 1e-10 ||b|| over "
-                    "BiCGStab(precond='jacobi') of the same process and kernel mode (below 1: the preconditioner pays); ranges: "
-                    "[min, max] over the processes; no ratio was fixed in advance",
-               ranges=ranges, runs=runs)
-    with open(a.out, "w") as fo:
-        json.dump(out, fo, indent=1)
-        fo.write("\n")
+                ratelib.collect(ranges.setdefault(r["problem"], {}).setdefault(mode, {}), name, e, RATIOS)
+    ratelib.ranges([slot for prob in ranges.values() for rows in prob.values() for slot in rows.values()], RATIOS)
+    note = ("one entry per fresh process and problem; over_jacobi = loop time to eps = 1e-10 ||b|| over "
+            "BiCGStab(precond='jacobi') of the same process and kernel mode (below 1: the preconditioner pays); ranges: "
+            "[min, max] over the processes; no ratio was fixed in advance")
+    ratelib.dump(dict(ratelib.merge_head(runs, note), ranges=ranges, runs=runs), a.out)
     print(json.dumps(ranges, indent=1))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    sub = ap.add_subparsers(dest="cmd", required=True)
-    r = sub.add_parser("run")
-    r.add_argument("--problem", choices=("cd", "hpcg"), required=True)
-    r.add_argument("--n", type=int, default=128)
-    r.add_argument("--cd", type=int, default=64)
-    r.add_argument("--repeats", type=int, default=3)
-    r.add_argument("--itermax", type=int, default=2000)
-    r.add_argument("--piece", type=int, default=10)
-    r.add_argument("--out", default=None)
-    mg = sub.add_parser("merge")
-    mg.add_argument("files", nargs="+")
-    mg.add_argument("--out", required=True)
-    a = ap.parse_args()
-    (run if a.cmd == "run" else merge)(a)
+def main(parse=True):
+    return ratelib.cli(run, merge, lambda r: r.add_argument("--problem", choices=("cd", "hpcg"), required=True), parse,
+                       n=128, cd=64, repeats=3, itermax=2000, piece=10)
 
 
 if __name__ == "__main__":

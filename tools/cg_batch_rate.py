@@ -15,22 +15,18 @@ loop itself moves by up to 1.24 x with placement, so a gain counts 
 
 Byte model of one body: sb_matrix_spmmv_bytes(nv) + nv * 64 B/row (40 in the p update, 24 in the r update).
 """
-import argparse
 import json
-import os
 import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from sparsebench_amd import capi, hostapi, srchash  # noqa: E402
-from sparsebench_amd.capi import DeviceVector  # noqa: E402
+import ratelib
+from ratelib import PEAK, hostapi
 
-PEAK = 8.0e12
+DeviceVector = ratelib.capi.DeviceVector
 WIDTHS = (2, 4, 8)
 PLACEMENT_SPREAD = 1.24  # 141 / 114 us: what the single loop itself moves by between processes (DESIGN 4.1)
+SAME = ("problem", "format", "bodies_per_solve", "repeats", "timed_bodies_per_variant")
 
 
 def spmmv_alone_us(L, p, nv, launches=40):
@@ -62,16 +58,16 @@ def spmmv_alone_us(L, p, nv, launches=40):
 
 
 def run(a):
-    L = capi.init(0)
+    L = ratelib.capi.init(0)
     n = a.n
-    p = hostapi.Problem("generate", n, n, n, fmt="scs", Cc=64, sigma=256)
+    p = hostapi.Problem("generate", n, n, n, **ratelib.FMT)
     assert p.use_packed(0) == 0  # the single loop streams the reference layout, as the batched loop does
     solvers = {1: hostapi.CG(p, dot_order="tree")}
     for nv in WIDTHS:
         solvers[nv] = hostapi.BatchCG(p, nrhs=nv)
     bodies = a.bodies
 
-    def timed(nv):
+    def timed(nv):  # (ratelib.window_us with a body counter per right-hand side)
         s = solvers[nv]
         k = s.solve(bodies + 1, 0.0)
         c = s.counters() if nv == 1 else s.counters(0)
@@ -80,20 +76,14 @@ def run(a):
             raise RuntimeError("the timed loop did not run every body: nv=%d k=%d bodies run %r" % (nv, k, ran))
         return 1e3 * s.loop_ms() / bodies
 
-    for nv in solvers:  # warm-up
-        timed(nv)
-    us = {nv: [] for nv in solvers}
-    for _ in range(a.repeats):
-        for nv in solvers:
-            us[nv].append(timed(nv))
+    us = ratelib.alternate(list(solvers), a.repeats, timed)
     launches = {1: solvers[1].launches_per_body()}
     launches.update({nv: solvers[nv].launches_per_body() for nv in WIDTHS})
     for s in solvers.values():
         s.free()
     single = statistics.median(us[1])
-    out = {"problem": "hpcg%d" % n, "format": "Sell-64-256", "bodies_per_solve": bodies, "repeats": a.repeats,
-           "timed_bodies_per_variant": bodies * a.repeats, "device": L.sb_device_name().decode(), "library": L.sb_version().decode(),
-           "csrc_hash": srchash.csrc_hash(), "variants": {}}
+    out = dict({"problem": "hpcg%d" % n, "format": "Sell-64-256", "bodies_per_solve": bodies, "repeats": a.repeats,
+                "timed_bodies_per_variant": bodies * a.repeats}, **ratelib.process_header(L), variants={})
     for nv in solvers:
         model = L.sb_matrix_spmmv_bytes(p.matrix, nv) + nv * 64.0 * p.nr if nv > 1 else L.sb_matrix_spmv_bytes(p.matrix) + 64.0 * p.nr
         med = statistics.median(us[nv])
@@ -107,49 +97,27 @@ def run(a):
             "spmmv_kernel_us": round(k_us, 2), "spmmv_kernel_bytes": int(k_bytes),
             "spmmv_kernel_frac_of_8TBs": round(k_bytes / (k_us * 1e-6) / PEAK, 4)}
     p.free()
-    text = json.dumps(out)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    ratelib.emit(out, a.out)
 
 
 def merge(a):
-    runs = [json.load(open(f)) for f in a.files]
-    head = {k: runs[0][k] for k in ("problem", "format", "bodies_per_solve", "repeats", "timed_bodies_per_variant", "library", "csrc_hash")}
-    if any({k: r[k] for k in head} != head for r in runs):
-        raise SystemExit("the runs do not describe the same build and problem")
+    runs = ratelib.load_runs(a.files, SAME)
     gains4 = [r["variants"]["nrhs4"]["gain_per_rhs_over_single"] for r in runs]
-    out = dict(head, processes=len(runs), devices=sorted({r["device"] for r in runs}), variants={},
-               placement_spread_of_the_single_loop=PLACEMENT_SPREAD,
-               delivers=bool(all(g > PLACEMENT_SPREAD for g in gains4)),
-               note="per variant: one entry per fresh process (the median of its repeats); gain = the single loop's us per body of "
-                    "the SAME process / the variant's us per body and right-hand side; delivers = the gain at nrhs 4 exceeds the "
-                    "placement spread in every process")
+    note = ("per variant: one entry per fresh process (the median of its repeats); gain = the single loop's us per body of "
+            "the SAME process / the variant's us per body and right-hand side; delivers = the gain at nrhs 4 exceeds the "
+            "placement spread in every process")
+    out = ratelib.merge_head(runs, note, SAME, variants={}, placement_spread_of_the_single_loop=PLACEMENT_SPREAD,
+                             delivers=bool(all(g > PLACEMENT_SPREAD for g in gains4)))
     for v in runs[0]["variants"]:
         rows = [r["variants"][v] for r in runs]
         out["variants"][v] = {k: ([r[k] for r in rows] if k not in ("loop", "launches_per_body", "model_bytes_per_body", "spmmv_kernel_bytes")
                                   else rows[0][k]) for k in rows[0]}
-    with open(a.out, "w") as fo:
-        json.dump(out, fo, indent=1)
-        fo.write("\n")
+    ratelib.dump(out, a.out)
     print(json.dumps(out))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    sub = ap.add_subparsers(dest="cmd", required=True)
-    r = sub.add_parser("run")
-    r.add_argument("--n", type=int, default=128)
-    r.add_argument("--bodies", type=int, default=250)
-    r.add_argument("--repeats", type=int, default=4)
-    r.add_argument("--out", default=None)
-    mg = sub.add_parser("merge")
-    mg.add_argument("files", nargs="+")
-    mg.add_argument("--out", required=True)
-    a = ap.parse_args()
-    (run if a.cmd == "run" else merge)(a)
+def main(parse=True):
+    return ratelib.cli(run, merge, None, parse, n=128, bodies=250, repeats=4)
 
 
 if __name__ == "__main__":

@@ -22,22 +22,12 @@ device-formed Galerkin operators and on the aggregation hierarchy where it is ac
 No ratio is fixed in advance: `merge` records the range of every same-process ratio over the processes, losses included (between
 processes a loop moves with placement, DESIGN 4.1: only same-process ratios count).
 """
-import argparse
 import json
-import math
 import os
-import statistics
-import sys
 import tempfile
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-from sparsebench_amd import capi, hostapi, srchash  # noqa: E402
-from bicgstab_precond_rate import FMT, galerkin_levels  # noqa: E402
-from bicgstab_rate import find_k, to_eps, write_convdiff  # noqa: E402
+import ratelib
+from ratelib import FMT, hostapi
 
 RESTARTS = (10, 30)
 RATIOS = ("over_gmres30", "over_bicgstab", "us_per_step", "apply_ms")
@@ -51,7 +41,7 @@ def plans(p, generated, dims, owned, notes):
         M["mgpoly_1_regenerated"] = hostapi.PCG(p, precond="mgpoly", steps=1)
         M["mgpoly_1_galerkin"] = hostapi.PCG(p, precond="mgpoly", steps=1, galerkin="device")
     else:
-        M["mgpoly_1_galerkin"] = hostapi.PCG(p, precond="mgpoly", steps=1, coarse=galerkin_levels(p, dims, owned))
+        M["mgpoly_1_galerkin"] = hostapi.PCG(p, precond="mgpoly", steps=1, coarse=ratelib.galerkin_levels(p, dims, owned))
     try:
         M["mgpoly_1_aggregation"] = hostapi.PCG(p, precond="mgpoly", steps=1, coarsening="aggregation")
     except Exception as e:  # refused where a product's row outgrows its capacity: recorded, not hidden
@@ -60,32 +50,29 @@ def plans(p, generated, dims, owned, notes):
 
 
 def solvers_of(p, M):
-    """name -> (kind, handle): GMRES(m) under every plan, BiCGStab under every plan"""
+    """name -> handle: GMRES(m) under every plan, BiCGStab under every plan"""
     s = {}
     for name, pcg in M.items():
         for m in RESTARTS:
-            s["gmres%d_%s" % (m, name)] = ("gmres", hostapi.GMRES(p, restart=m) if pcg is None else hostapi.GMRES(p, restart=m, precond=pcg))
+            s["gmres%d_%s" % (m, name)] = hostapi.GMRES(p, restart=m) if pcg is None else hostapi.GMRES(p, restart=m, precond=pcg)
         if pcg is not None:
-            s["bicgstab_%s" % name] = ("bicgstab", hostapi.BiCGStab(p, precond=pcg))
+            s["bicgstab_%s" % name] = hostapi.BiCGStab(p, precond=pcg)
     return s
 
 
 def measure(a, solvers, M, eps):
-    ks = {n: find_k(kind, s, a.itermax, eps, a.piece) for n, (kind, s) in solvers.items()}
-    reached = {n: 1 < k < a.itermax for n, k in ks.items()}
+    ks = ratelib.find_ks(solvers, a, eps)
+    reached = ratelib.reached(ks, a.itermax)
     for yard in ("gmres30_none", "bicgstab_jacobi"):
         if not reached[yard]:
             raise RuntimeError("the yardstick %s did not reach eps within itermax = %d (k = %d)" % (yard, a.itermax, ks[yard]))
-    ms = {n: [] for n in solvers if reached[n]}
-    for _ in range(a.repeats):
-        for n in ms:
-            ms[n].append(to_eps(solvers[n][0], solvers[n][1], ks[n], eps))
-    med = {n: statistics.median(v) for n, v in ms.items()}
+    ms = ratelib.to_eps_rounds(solvers, ks, eps, a.repeats, reached, named=True)
+    med = ratelib.medians(ms)
     out = {}
-    for n, (kind, s) in solvers.items():
+    for n, s in solvers.items():
         e = {"k": ks[n], "steps": ks[n] - 1, "reached_eps": reached[n]}
         plan = n.split("_", 1)[1]
-        if kind == "gmres":
+        if ratelib.kind(s) == "gmres":
             m = s.restart()
             e.update(restart=m, mid_step_launches=s.launches_per_step(m // 2))
         else:
@@ -101,24 +88,22 @@ def measure(a, solvers, M, eps):
 
 
 def run(a):
-    L = capi.init(0)
-    out = {"device": L.sb_device_name().decode(), "library": L.sb_version().decode(), "csrc_hash": srchash.csrc_hash(),
-           "format": "Sell-64-256", "eps_rel": 1e-10, "repeats": a.repeats, "notes": {}}
+    L = ratelib.capi.init(0)
+    out = dict(ratelib.process_header(L), format="Sell-64-256", eps_rel=1e-10, repeats=a.repeats, notes={})
     owned = []
     if a.problem == "cd":
         with tempfile.TemporaryDirectory(prefix="gmres_precond_rate_") as d:
-            p = hostapi.Problem(write_convdiff(os.path.join(d, "cd_%d.mtx" % a.cd), a.cd), 1, 1, 1, **FMT)
+            p = hostapi.Problem(ratelib.write_convdiff(os.path.join(d, "cd_%d.mtx" % a.cd), a.cd), 1, 1, 1, **FMT)
         out["problem"], dims = "convection-diffusion %d^3" % a.cd, (a.cd,) * 3
     else:
         p = hostapi.Problem("generate", a.n, a.n, a.n, **FMT)
         out["problem"], dims = "hpcg%d" % a.n, (a.n,) * 3
     out["rows"], out["kernel_mode"] = p.nr, p.pack_info()["mode"]
-    b = p.rhs()[0]
-    eps = 1e-10 * math.sqrt(float(np.dot(b, b)))
+    eps = ratelib.rel_eps(p)
     M = plans(p, a.problem == "hpcg", dims, owned, out["notes"])
     solvers = solvers_of(p, M)
     out["solvers"] = measure(a, solvers, M, eps)
-    for _, s in solvers.values():
+    for s in solvers.values():
         s.free()
     for pcg in M.values():
         if pcg is not None:
@@ -126,59 +111,26 @@ def run(a):
     for q in owned:
         q.free()
     p.free()
-    text = json.dumps(out)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    ratelib.emit(out, a.out)
 
 
 def merge(a):
-    runs = [json.load(open(f)) for f in a.files]
-    head = {k: runs[0][k] for k in ("library", "csrc_hash")}
-    if any({k: r[k] for k in head} != head for r in runs):
-        raise SystemExit("the runs do not describe the same build")
+    runs = ratelib.load_runs(a.files)
     ranges = {}
     for r in runs:
         for name, e in r["solvers"].items():
-            slot = ranges.setdefault(r["problem"], {}).setdefault(name, dict({"k": e["k"]}, **{key: [] for key in RATIOS}))
-            if e["k"] != slot["k"]:
-                raise SystemExit("k of %s differs between processes" % name)
-            for key in RATIOS:
-                if key in e:
-                    slot[key].append(e[key])
-    for prob in ranges.values():
-        for slot in prob.values():
-            for key in RATIOS:
-                slot[key] = [min(slot[key]), max(slot[key])] if slot[key] else None
-    out = dict(head, processes=len(runs), devices=sorted({r["device"] for r in runs}),
-               note="one entry per fresh process and problem; over_gmres30 / over_bicgstab = loop time to eps = 1e-10 ||b|| over "
-                    "unpreconditioned GMRES(30)'s / BiCGStab(precond='jacobi')'s of the same process (below 1: it pays); ranges: "
-                    "[min, max] over the processes; no ratio was fixed in advance",
-               ranges=ranges, runs=runs)
-    with open(a.out, "w") as fo:
-        json.dump(out, fo, indent=1)
-        fo.write("\n")
+            ratelib.collect(ranges.setdefault(r["problem"], {}), name, e, RATIOS)
+    ratelib.ranges([slot for prob in ranges.values() for slot in prob.values()], RATIOS)
+    note = ("one entry per fresh process and problem; over_gmres30 / over_bicgstab = loop time to eps = 1e-10 ||b|| over "
+            "unpreconditioned GMRES(30)'s / BiCGStab(precond='jacobi')'s of the same process (below 1: it pays); ranges: "
+            "[min, max] over the processes; no ratio was fixed in advance")
+    ratelib.dump(dict(ratelib.merge_head(runs, note), ranges=ranges, runs=runs), a.out)
     print(json.dumps(ranges, indent=1))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    sub = ap.add_subparsers(dest="cmd", required=True)
-    r = sub.add_parser("run")
-    r.add_argument("--problem", choices=("cd", "hpcg"), required=True)
-    r.add_argument("--n", type=int, default=128)
-    r.add_argument("--cd", type=int, default=64)
-    r.add_argument("--repeats", type=int, default=3)
-    r.add_argument("--itermax", type=int, default=2000)
-    r.add_argument("--piece", type=int, default=10)
-    r.add_argument("--out", default=None)
-    mg = sub.add_parser("merge")
-    mg.add_argument("files", nargs="+")
-    mg.add_argument("--out", required=True)
-    a = ap.parse_args()
-    (run if a.cmd == "run" else merge)(a)
+def main(parse=True):
+    return ratelib.cli(run, merge, lambda r: r.add_argument("--problem", choices=("cd", "hpcg"), required=True), parse,
+                       n=128, cd=64, repeats=3, itermax=2000, piece=10)
 
 
 if __name__ == "__main__":

@@ -14,37 +14,37 @@ the range over the processes (the placement effect of DESIGN 4.1 moves the same 
 Byte model of one fused step at cycle position j: sb_matrix_stream_bytes + (3 (j + 1) + 7) * 8 n; averaged
 over a cycle: stream_bytes + (3 (m + 1) / 2 + 7) * 8 n.  `frac_of_8TBs` = model bytes / measured time / 8 TB/s.
 """
-import argparse
 import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from sparsebench_amd import capi, hostapi, srchash  # noqa: E402
+import ratelib
+from ratelib import PEAK, hostapi
 
-PEAK = 8.0e12
+SAME = ("problem", "format", "restart", "cycles_timed", "repeats")
 
 
 def time_variants(p, m, cycles, repeats):
     """us per step of the fused loop and of the op list, alternating, after a warm-up cycle of each"""
     solvers = {True: hostapi.GMRES(p, restart=m, fused=True), False: hostapi.GMRES(p, restart=m, fused=False)}
-    for s in solvers.values():
-        s.start(m + 2, 0.0)
-        s.run_steps(m)  # warm-up: one full cycle
-        s.finish()
     steps = cycles * m
-    us = {True: [], False: []}
-    for _ in range(repeats):
-        for fused, s in solvers.items():
-            s.start(steps + 2, 0.0)  # (one more than the steps taken: the last cycle closes inside the timed loop too)
-            s.run_steps(steps)
-            k = s.finish()
-            c = s.counters()
-            if k != steps + 1 or c["steps"] != steps or c["cycles"] != cycles:
-                raise RuntimeError("the timed loop did not run every step: k=%d counters=%r" % (k, c))
-            us[fused].append(1e3 * s.loop_ms() / steps)
+
+    def warm(fused):
+        s = solvers[fused]
+        s.start(m + 2, 0.0)
+        s.run_steps(m)  # one full cycle
+        s.finish()
+
+    def timed(fused):
+        s = solvers[fused]
+        s.start(steps + 2, 0.0)  # (one more than the steps taken: the last cycle closes inside the timed loop too)
+        s.run_steps(steps)
+        k = s.finish()
+        c = s.counters()
+        if k != steps + 1 or c["steps"] != steps or c["cycles"] != cycles:
+            raise RuntimeError("the timed loop did not run every step: k=%d counters=%r" % (k, c))
+        return 1e3 * s.loop_ms() / steps
+
+    us = ratelib.alternate(list(solvers), repeats, timed, warm)
     launches = [solvers[True].launches_per_step(j) for j in range(m)]
     for s in solvers.values():
         s.free()
@@ -52,11 +52,11 @@ def time_variants(p, m, cycles, repeats):
 
 
 def run(a):
-    L = capi.init(0)
+    L = ratelib.capi.init(0)
     n, m = a.n, a.restart
-    p = hostapi.Problem("generate", n, n, n, fmt="scs", Cc=64, sigma=256)
-    out = {"problem": "hpcg%d" % n, "format": "Sell-64-256", "restart": m, "cycles_timed": a.cycles, "repeats": a.repeats,
-           "device": L.sb_device_name().decode(), "library": L.sb_version().decode(), "csrc_hash": srchash.csrc_hash(), "modes": {}}
+    p = hostapi.Problem("generate", n, n, n, **ratelib.FMT)
+    out = dict({"problem": "hpcg%d" % n, "format": "Sell-64-256", "restart": m, "cycles_timed": a.cycles, "repeats": a.repeats},
+               **ratelib.process_header(L), modes={})
     for mode in (0, 5):
         got = p.use_packed(mode)
         stream = p.stream_bytes()
@@ -70,21 +70,12 @@ def run(a):
             "oplist_over_fused": round(o / f, 3), "fused_frac_of_8TBs_on_model_bytes": round(model / (f * 1e-6) / PEAK, 4),
             "launches_per_step_mean": round(sum(launches) / len(launches), 2), "launches_per_step": launches}
     p.free()
-    text = json.dumps(out)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    ratelib.emit(out, a.out)
 
 
 def merge(a):
-    runs = [json.load(open(f)) for f in a.files]
-    head = {k: runs[0][k] for k in ("problem", "format", "restart", "cycles_timed", "repeats", "library", "csrc_hash")}
-    if any({k: r[k] for k in head} != head for r in runs):
-        raise SystemExit("the runs do not describe the same build and problem")
-    out = dict(head, processes=len(runs), devices=sorted({r["device"] for r in runs}), modes={},
-               note="per variant: the median of each fresh process, and the range over the processes")
+    runs = ratelib.load_runs(a.files, SAME)
+    out = ratelib.merge_head(runs, "per variant: the median of each fresh process, and the range over the processes", SAME, modes={})
     for mode in runs[0]["modes"]:
         rows = [r["modes"][mode] for r in runs]
         f = [r["fused_us_per_step_median"] for r in rows]
@@ -98,26 +89,12 @@ def merge(a):
             "fused_frac_of_8TBs_on_model_bytes": [round(model / (v * 1e-6) / PEAK, 4) for v in f],
             "launches_per_step_mean": rows[0]["launches_per_step_mean"], "launches_per_step": rows[0]["launches_per_step"],
             "all_repeats_fused_us": [r["fused_us_per_step"] for r in rows], "all_repeats_oplist_us": [r["oplist_us_per_step"] for r in rows]}
-    with open(a.out, "w") as fo:
-        json.dump(out, fo, indent=1)
-        fo.write("\n")
+    ratelib.dump(out, a.out)
     print(json.dumps(out))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    sub = ap.add_subparsers(dest="cmd", required=True)
-    r = sub.add_parser("run")
-    r.add_argument("--n", type=int, default=128)
-    r.add_argument("--restart", type=int, default=30)
-    r.add_argument("--cycles", type=int, default=20)
-    r.add_argument("--repeats", type=int, default=3)
-    r.add_argument("--out", default=None)
-    mg = sub.add_parser("merge")
-    mg.add_argument("files", nargs="+")
-    mg.add_argument("--out", required=True)
-    a = ap.parse_args()
-    (run if a.cmd == "run" else merge)(a)
+def main(parse=True):
+    return ratelib.cli(run, merge, None, parse, n=128, restart=30, cycles=20, repeats=3)
 
 
 if __name__ == "__main__":

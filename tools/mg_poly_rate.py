@@ -18,35 +18,19 @@ handle and an mgpoly handle for steps in {1, 2, 3} on each hierarchy, and report
     apply of the regenerated hierarchy cut off at 1, 2, .. L levels, whose differences are what each further level adds.
 Nothing is gated: the tool says what the cycle costs and what it buys.  `merge` keeps every process's figures side by side.
 """
-import argparse
-import json
-import os
 import shutil
-import statistics
 import sys
 import tempfile
 import time
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-from sparsebench_amd import capi, hostapi, srchash  # noqa: E402
-from sgs_rate import find_k, spmv_us, to_eps  # noqa: E402
+import ratelib
+from ratelib import hostapi
 
 STEPS = (1, 2, 3)
 BASES = ("jacobi", "poly_s3_r16", "mgfw")
-
-
-def regenerated(p, nlev):
-    """the hierarchy PCG(precond="mgpoly", levels=...) makes for itself, made here so that its levels' kernel modes can be set"""
-    dims, out = p.dims, []
-    for _ in range(nlev - 1):
-        P = hostapi.mg_trilinear(*dims)
-        dims = tuple(d // 2 for d in dims)
-        out.append((hostapi.Problem("generate", *dims, fmt=p.fmt, Cc=p.Cc, sigma=p.sigma_arg), P, 0.25))
-    return out
+NOTE = ("one entry per fresh process; only ratios taken inside one process count (DESIGN 4.1).  Nothing is gated: the "
+        "figures say what a body of the Chebyshev-smoothed cycle costs against a Jacobi, a polynomial and an MGFW body "
+        "and what it buys in iterations")
 
 
 def measure(L, a, label, p, mode, hier):
@@ -76,7 +60,7 @@ def measure(L, a, label, p, mode, hier):
     # Such a handle gets a shorter window, well inside what it runs: the warm-up finds it
     window = {}
 
-    def timed(name):
+    def timed(name):  # (ratelib.window_us with the window of its name)
         s = solvers[name]
         n_b = window.get(name, bodies)
         k = s.solve(n_b + 1, 0.0)
@@ -88,15 +72,13 @@ def measure(L, a, label, p, mode, hier):
             raise RuntimeError("the timed loop did not run every body: %s k=%d bodies run %d of %d" % (name, k, ran, n_b))
         return 1e3 * s.loop_ms() / n_b
 
-    for name in names:  # warm-up, twice where the window was shortened
+    def warm(name):  # twice where the window was shortened
         timed(name)
         if window[name] != bodies:
             timed(name)
-    us = {name: [] for name in names}
-    for _ in range(a.repeats):
-        for name in names:
-            us[name].append(timed(name))
-    med = {name: statistics.median(v) for name, v in us.items()}
+
+    us = ratelib.alternate(names, a.repeats, timed, warm)
+    med = ratelib.medians(us)
     apply_us = {name: 1e3 * solvers[name].apply_ms(a.apply_reps) for name in names}
     by_depth = {}
     for steps in STEPS:  # the cycle cut off at 1 .. L levels: the differences are what each further level adds
@@ -106,33 +88,26 @@ def measure(L, a, label, p, mode, hier):
             row.append(round(1e3 * s.apply_ms(a.apply_reps), 2))
             s.free()
         by_depth["s%d" % steps] = row
-    mv_us = spmv_us(L, p, a.apply_reps)
-    b = p.rhs()[0]
-    eps = 1e-10 * float(np.linalg.norm(b))
-    ks = {name: find_k(s, a.itermax, eps, a.piece) for name, s in solvers.items()}
-    ms = {name: [] for name in names}
-    for _ in range(a.repeats):
-        for name, s in solvers.items():
-            if 1 < ks[name] < a.itermax:
-                ms[name].append(to_eps(s, ks[name], eps))
-    mmed = {name: (statistics.median(v) if v else None) for name, v in ms.items()}
-    over = lambda d, base: {name: (round(d[name] / d[base], 4) if d[name] and d[base] else None) for name in names}  # noqa: E731
+    mv_us = ratelib.spmv_us(L, p, a.apply_reps)
+    eps = ratelib.rel_eps(p)
+    ks = ratelib.find_ks(solvers, a, eps)
+    ms = ratelib.to_eps_rounds(solvers, ks, eps, a.repeats, ratelib.reached(ks, a.itermax))
+    mmed = ratelib.medians(ms)
+    over = lambda d, base: {name: ratelib.ratio(d[name], d[base]) for name in names}  # noqa: E731
     out = {"problem": label, "rows": p.nr, "kernel_mode": p.pack_info()["mode"], "level_kernel_modes": level_modes,
            "level_rows": [p.nr] + [c[0].nr for c in hier["regenerated"]],
            "setup_seconds": {"jacobi": round(t[1] - t[0], 4), "poly": round(t[2] - t[1], 4), "mgfw": round(t[3] - t[2], 4),
                              "mgpoly_each": round((t[4] - t[3]) / (len(STEPS) * len(hier)), 4)},
            "launches_per_body": {name: solvers[name].launches_per_body() for name in names},
            "bodies_per_window": dict(window),
-           "us_per_body": {name: [round(v, 2) for v in vals] for name, vals in us.items()},
-           "us_per_body_median": {name: round(v, 2) for name, v in med.items()},
+           "us_per_body": ratelib.rounded(us, 2), "us_per_body_median": ratelib.rounded(med, 2),
            "precond_bytes": {name: int(solvers[name].precond_bytes()) for name in names},
-           "apply_us": {name: round(v, 2) for name, v in apply_us.items()},
+           "apply_us": ratelib.rounded(apply_us, 2),
            "apply_TBps": {name: round(solvers[name].precond_bytes() / (1e6 * apply_us[name]), 3) for name in names},
            "mgpoly_regenerated_apply_us_by_depth": by_depth,
            "spmv_us": round(mv_us, 2), "spmv_stream_bytes": int(p.stream_bytes()),
            "eps_rel": 1e-10, "k": ks,
-           "loop_ms_to_eps": {name: [round(v, 3) for v in vals] for name, vals in ms.items()},
-           "loop_ms_to_eps_median": {name: (round(v, 3) if v is not None else None) for name, v in mmed.items()}}
+           "loop_ms_to_eps": ratelib.rounded(ms, 3), "loop_ms_to_eps_median": ratelib.rounded(mmed, 3)}
     for base in BASES:
         out["body_over_" + base] = over(med, base)
         out["time_to_eps_over_" + base] = over(mmed, base)
@@ -143,14 +118,14 @@ def measure(L, a, label, p, mode, hier):
 
 
 def run(a):
-    L = capi.init(0)
-    out = {"device": L.sb_device_name().decode(), "library": L.sb_version().decode(), "csrc_hash": srchash.csrc_hash(), "cases": []}
+    L = ratelib.capi.init(0)
+    out = dict(ratelib.process_header(L), cases=[])
     for n in [int(v) for v in a.sizes.split(",") if v]:
-        p = hostapi.Problem("generate", n, n, n, fmt="scs", Cc=64, sigma=256)
+        p = hostapi.Problem("generate", n, n, n, **ratelib.FMT)
         nlev = hostapi.mg_levels(n, n, n)
         tmp = tempfile.mkdtemp(prefix="mg_poly_rate_")
         t0 = time.perf_counter()
-        hier = {"regenerated": regenerated(p, nlev)}
+        hier = {"regenerated": ratelib.regenerated(p, nlev)}
         t1 = time.perf_counter()
         hier["galerkin"] = hostapi.mg_galerkin(p, nlev, tmp)
         t2 = time.perf_counter()
@@ -160,50 +135,19 @@ def run(a):
             case["hierarchy_seconds"] = {"regenerated": round(t1 - t0, 3), "galerkin_scipy_and_files": round(t2 - t1, 3)}
             out["cases"].append(case)
         for coarse in hier.values():
-            for q, _, _ in coarse:
-                q.free()
+            ratelib.free(coarse)
         shutil.rmtree(tmp, ignore_errors=True)
         p.free()
-    text = json.dumps(out)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    ratelib.emit(out, a.out)
 
 
 def merge(a):
-    runs = [json.load(open(f)) for f in a.files]
-    head = {k: runs[0][k] for k in ("library", "csrc_hash")}
-    if any({k: r[k] for k in head} != head for r in runs):
-        raise SystemExit("the runs do not describe the same build")
-    out = dict(head, processes=len(runs), devices=sorted({r["device"] for r in runs}),
-               note="one entry per fresh process; only ratios taken inside one process count (DESIGN 4.1).  Nothing is gated: the "
-                    "figures say what a body of the Chebyshev-smoothed cycle costs against a Jacobi, a polynomial and an MGFW body "
-                    "and what it buys in iterations",
-               runs=[r["cases"] for r in runs])
-    with open(a.out, "w") as fo:
-        json.dump(out, fo, indent=1)
-        fo.write("\n")
-    print(json.dumps(out))
+    ratelib.merge_cases(a, NOTE)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    sub = ap.add_subparsers(dest="cmd", required=True)
-    r = sub.add_parser("run")
-    r.add_argument("--sizes", default="64,128")
-    r.add_argument("--bodies", type=int, default=100)
-    r.add_argument("--repeats", type=int, default=3)
-    r.add_argument("--apply-reps", dest="apply_reps", type=int, default=20)
-    r.add_argument("--itermax", type=int, default=5000)
-    r.add_argument("--piece", type=int, default=10)
-    r.add_argument("--out", default=None)
-    mg = sub.add_parser("merge")
-    mg.add_argument("files", nargs="+")
-    mg.add_argument("--out", required=True)
-    a = ap.parse_args()
-    (run if a.cmd == "run" else merge)(a)
+def main(parse=True):
+    return ratelib.cli(run, merge, lambda r: r.add_argument("--sizes", default="64,128"), parse,
+                       bodies=100, repeats=3, apply_reps=20, itermax=5000, piece=10)
 
 
 if __name__ == "__main__":

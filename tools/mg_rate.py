@@ -14,21 +14,15 @@ the upload selects -- and reports for each, by tools/sgs_rate.py's method,
   - k and the loop time to eps = 1e-10 ||b|| of every handle, and MG's against both others.
 Nothing is gated: the tool says what MG costs and what it buys.  `merge` keeps every process's figures side by side.
 """
-import argparse
-import json
-import os
-import statistics
 import sys
 import time
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
-from sparsebench_amd import capi, hostapi, srchash  # noqa: E402
-from sgs_rate import find_k, to_eps  # noqa: E402
+import ratelib
+from ratelib import hostapi, ratio
 
 NAMES = ("jacobi", "sgs", "mg")
+NOTE = ("one entry per fresh process; only ratios taken inside one process count (DESIGN 4.1).  Nothing is gated: "
+        "the figures say what an MG body costs against an SGS and a Jacobi body and what it buys in iterations")
 
 
 def measure(L, a, label, p, mode):
@@ -41,49 +35,27 @@ def measure(L, a, label, p, mode):
         setup[name] = round(time.perf_counter() - t0, 3)
     mg = solvers["mg"]
     bodies = a.bodies
-
-    def timed(name):
-        s = solvers[name]
-        k = s.solve(bodies + 1, 0.0)
-        ran = s.counters()["n_pAp"]
-        if k != bodies + 1 or ran != bodies:
-            raise RuntimeError("the timed loop did not run every body: %s k=%d bodies run %d" % (name, k, ran))
-        return 1e3 * s.loop_ms() / bodies
-
-    for name in NAMES:  # warm-up
-        timed(name)
-    us = {name: [] for name in NAMES}
-    for _ in range(a.repeats):
-        for name in NAMES:
-            us[name].append(timed(name))
-    med = {name: statistics.median(v) for name, v in us.items()}
+    us = ratelib.body_windows(solvers, NAMES, bodies, a.repeats)
+    med = ratelib.medians(us)
     apply_us = {name: 1e3 * s.apply_ms(a.apply_reps) for name, s in solvers.items()}
-    b = p.rhs()[0]
-    eps = 1e-10 * float(np.linalg.norm(b))
-    ks = {name: find_k(s, a.itermax, eps, a.piece) for name, s in solvers.items()}
-    ms = {name: [] for name in NAMES}
-    if all(1 < k < a.itermax for k in ks.values()):
-        for _ in range(a.repeats):
-            for name, s in solvers.items():
-                ms[name].append(to_eps(s, ks[name], eps))
-    mmed = {name: (statistics.median(v) if v else None) for name, v in ms.items()}
-    ratio = lambda x, y: round(x / y, 4) if x and y else None  # noqa: E731
+    eps = ratelib.rel_eps(p)
+    ks = ratelib.find_ks(solvers, a, eps)
+    ms = ratelib.to_eps_rounds(solvers, ks, eps, a.repeats if all(ratelib.reached(ks, a.itermax).values()) else 0)
+    mmed = ratelib.medians(ms)
     nlev = mg.levels()
     out = {"problem": label, "rows": p.nr, "kernel_mode": p.pack_info()["mode"], "levels": nlev,
            "level_rows": [mg.level_rows(l) for l in range(nlev)], "level_colours": [mg.level_colours(l) for l in range(nlev)],
            "setup_seconds": setup,
            "launches_per_body": {name: s.launches_per_body() for name, s in solvers.items()},
            "bodies_per_window": bodies,
-           "us_per_body": {name: [round(v, 2) for v in vals] for name, vals in us.items()},
-           "us_per_body_median": {name: round(v, 2) for name, v in med.items()},
+           "us_per_body": ratelib.rounded(us, 2), "us_per_body_median": ratelib.rounded(med, 2),
            "mg_over_jacobi_body": ratio(med["mg"], med["jacobi"]), "mg_over_sgs_body": ratio(med["mg"], med["sgs"]),
            "precond_bytes": {name: int(s.precond_bytes()) for name, s in solvers.items()},
-           "apply_us": {name: round(v, 2) for name, v in apply_us.items()},
+           "apply_us": ratelib.rounded(apply_us, 2),
            "apply_TBps_of_the_model": {name: round(s.precond_bytes() / (1e6 * apply_us[name]), 3) for name, s in solvers.items()},
            "mg_over_sgs_apply": ratio(apply_us["mg"], apply_us["sgs"]),
            "eps_rel": 1e-10, "k": ks,
-           "loop_ms_to_eps": {name: [round(v, 3) for v in vals] for name, vals in ms.items()},
-           "loop_ms_to_eps_median": {name: (round(v, 3) if v is not None else None) for name, v in mmed.items()},
+           "loop_ms_to_eps": ratelib.rounded(ms, 3), "loop_ms_to_eps_median": ratelib.rounded(mmed, 3),
            "mg_over_jacobi_time_to_eps": ratio(mmed["mg"], mmed["jacobi"]), "mg_over_sgs_time_to_eps": ratio(mmed["mg"], mmed["sgs"])}
     for s in solvers.values():
         s.free()
@@ -92,57 +64,26 @@ def measure(L, a, label, p, mode):
 
 
 def run(a):
-    L = capi.init(0)
-    out = {"device": L.sb_device_name().decode(), "library": L.sb_version().decode(), "csrc_hash": srchash.csrc_hash(), "cases": []}
+    L = ratelib.capi.init(0)
+    out = dict(ratelib.process_header(L), cases=[])
     if a.n:
-        p = hostapi.Problem("generate", a.n, a.n, a.n, fmt="scs", Cc=64, sigma=256)
+        p = hostapi.Problem("generate", a.n, a.n, a.n, **ratelib.FMT)
         for mode in (5, 0):
             out["cases"].append(measure(L, a, "hpcg%d mode %d" % (a.n, mode), p, mode))
         p.free()
     if a.small:
-        p = hostapi.Problem("generate", a.small, a.small, a.small, fmt="scs", Cc=64, sigma=256)
+        p = hostapi.Problem("generate", a.small, a.small, a.small, **ratelib.FMT)
         out["cases"].append(measure(L, a, "hpcg%d" % a.small, p, None))
         p.free()
-    text = json.dumps(out)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    ratelib.emit(out, a.out)
 
 
 def merge(a):
-    runs = [json.load(open(f)) for f in a.files]
-    head = {k: runs[0][k] for k in ("library", "csrc_hash")}
-    if any({k: r[k] for k in head} != head for r in runs):
-        raise SystemExit("the runs do not describe the same build")
-    out = dict(head, processes=len(runs), devices=sorted({r["device"] for r in runs}),
-               note="one entry per fresh process; only ratios taken inside one process count (DESIGN 4.1).  Nothing is gated: "
-                    "the figures say what an MG body costs against an SGS and a Jacobi body and what it buys in iterations",
-               runs=[r["cases"] for r in runs])
-    with open(a.out, "w") as fo:
-        json.dump(out, fo, indent=1)
-        fo.write("\n")
-    print(json.dumps(out))
+    ratelib.merge_cases(a, NOTE)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    sub = ap.add_subparsers(dest="cmd", required=True)
-    r = sub.add_parser("run")
-    r.add_argument("--n", type=int, default=128)
-    r.add_argument("--small", type=int, default=64)
-    r.add_argument("--bodies", type=int, default=100)
-    r.add_argument("--repeats", type=int, default=3)
-    r.add_argument("--apply-reps", dest="apply_reps", type=int, default=20)
-    r.add_argument("--itermax", type=int, default=5000)
-    r.add_argument("--piece", type=int, default=10)
-    r.add_argument("--out", default=None)
-    mg = sub.add_parser("merge")
-    mg.add_argument("files", nargs="+")
-    mg.add_argument("--out", required=True)
-    a = ap.parse_args()
-    (run if a.cmd == "run" else merge)(a)
+def main(parse=True):
+    return ratelib.cli(run, merge, None, parse, n=128, small=64, bodies=100, repeats=3, apply_reps=20, itermax=5000, piece=10)
 
 
 if __name__ == "__main__":

@@ -17,22 +17,15 @@ and reports
     itermax = k: exactly the bodies that reach eps), and their ratios to Jacobi's.
 Nothing is gated: the tool says what the polynomial costs and what it buys.  `merge` keeps every process's figures side by side.
 """
-import argparse
-import json
-import os
-import statistics
 import sys
 import time
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-from sparsebench_amd import capi, hostapi, srchash  # noqa: E402
-from sgs_rate import find_k, spmv_us, to_eps  # noqa: E402
+import ratelib
+from ratelib import hostapi
 
 STEPS, RATIOS, DEFAULT_RATIO = (2, 3, 4), (4.0, 8.0, 16.0, 30.0), 16.0
+NOTE = ("one entry per fresh process; only ratios taken inside one process count (DESIGN 4.1).  Nothing is gated: "
+        "the figures say what a polynomial body costs against a Jacobi and an SGS body and what it buys in iterations")
 
 
 def measure(L, a, label, p, mode):
@@ -49,51 +42,30 @@ def measure(L, a, label, p, mode):
     t3 = time.perf_counter()
     body_names = ["jacobi", "sgs"] + ["poly_s%d_r%g" % (steps, DEFAULT_RATIO) for steps in STEPS]
     n, bodies = p.nr, a.bodies
-
-    def timed(name):
-        s = solvers[name]
-        k = s.solve(bodies + 1, 0.0)
-        ran = s.counters()["n_pAp"]
-        if k != bodies + 1 or ran != bodies:
-            raise RuntimeError("the timed loop did not run every body: %s k=%d bodies run %d" % (name, k, ran))
-        return 1e3 * s.loop_ms() / bodies
-
-    for name in body_names:  # warm-up
-        timed(name)
-    us = {name: [] for name in body_names}
-    for _ in range(a.repeats):
-        for name in body_names:
-            us[name].append(timed(name))
-    med = {name: statistics.median(v) for name, v in us.items()}
+    us = ratelib.body_windows(solvers, body_names, bodies, a.repeats)
+    med = ratelib.medians(us)
     apply_us = {name: 1e3 * solvers[name].apply_ms(a.apply_reps) for name in body_names}
-    mv_us = spmv_us(L, p, a.apply_reps)
-    b = p.rhs()[0]
-    eps = 1e-10 * float(np.linalg.norm(b))
-    ks = {name: find_k(s, a.itermax, eps, a.piece) for name, s in solvers.items()}
-    ms = {name: [] for name in solvers}
-    for _ in range(a.repeats):
-        for name, s in solvers.items():
-            if 1 < ks[name] < a.itermax:
-                ms[name].append(to_eps(s, ks[name], eps))
-    mmed = {name: (statistics.median(v) if v else None) for name, v in ms.items()}
-    ratio_to = lambda d, name: round(d[name] / d["jacobi"], 4) if d[name] and d["jacobi"] else None  # noqa: E731
+    mv_us = ratelib.spmv_us(L, p, a.apply_reps)
+    eps = ratelib.rel_eps(p)
+    ks = ratelib.find_ks(solvers, a, eps)
+    ms = ratelib.to_eps_rounds(solvers, ks, eps, a.repeats, ratelib.reached(ks, a.itermax))
+    mmed = ratelib.medians(ms)
+    ratio_to = lambda d, name: ratelib.ratio(d[name], d["jacobi"])  # noqa: E731
     best = min((name for name in solvers if name.startswith("poly") and mmed[name]), key=lambda name: mmed[name], default=None)
     out = {"problem": label, "rows": n, "kernel_mode": p.pack_info()["mode"], "nC": solvers["sgs"].colours(),
            "lambda_max_bound": solvers["poly_s3_r16"].interval()[1],
            "setup_seconds": {"jacobi": round(t1 - t0, 3), "sgs": round(t2 - t1, 3), "poly_each": round((t3 - t2) / (len(STEPS) * len(RATIOS)), 4)},
            "launches_per_body": {name: solvers[name].launches_per_body() for name in body_names},
            "bodies_per_window": bodies,
-           "us_per_body": {name: [round(v, 2) for v in vals] for name, vals in us.items()},
-           "us_per_body_median": {name: round(v, 2) for name, v in med.items()},
+           "us_per_body": ratelib.rounded(us, 2), "us_per_body_median": ratelib.rounded(med, 2),
            "body_over_jacobi": {name: ratio_to(med, name) for name in body_names},
            "precond_bytes": {name: int(solvers[name].precond_bytes()) for name in body_names},
-           "apply_us": {name: round(v, 2) for name, v in apply_us.items()},
+           "apply_us": ratelib.rounded(apply_us, 2),
            "apply_TBps": {name: round(solvers[name].precond_bytes() / (1e6 * apply_us[name]), 3) for name in body_names},
            "spmv_us": round(mv_us, 2), "spmv_stream_bytes": int(p.stream_bytes()),
            "spmv_TBps": round(p.stream_bytes() / (1e6 * mv_us), 3),
            "eps_rel": 1e-10, "k": ks,
-           "loop_ms_to_eps": {name: [round(v, 3) for v in vals] for name, vals in ms.items()},
-           "loop_ms_to_eps_median": {name: (round(v, 3) if v is not None else None) for name, v in mmed.items()},
+           "loop_ms_to_eps": ratelib.rounded(ms, 3), "loop_ms_to_eps_median": ratelib.rounded(mmed, 3),
            "time_to_eps_over_jacobi": {name: ratio_to(mmed, name) for name in solvers},
            "best_poly_to_eps": best}
     for s in solvers.values():
@@ -103,57 +75,27 @@ def measure(L, a, label, p, mode):
 
 
 def run(a):
-    L = capi.init(0)
-    out = {"device": L.sb_device_name().decode(), "library": L.sb_version().decode(), "csrc_hash": srchash.csrc_hash(), "cases": []}
+    L = ratelib.capi.init(0)
+    out = dict(ratelib.process_header(L), cases=[])
     for n in [int(v) for v in a.sizes.split(",") if v]:
-        p = hostapi.Problem("generate", n, n, n, fmt="scs", Cc=64, sigma=256)
+        p = hostapi.Problem("generate", n, n, n, **ratelib.FMT)
         for mode in (5, 0):
             out["cases"].append(measure(L, a, "hpcg%d mode %d" % (n, mode), p, mode))
         p.free()
     if a.nodes:
-        p = hostapi.Problem("irregular", a.nodes, a.nodes, a.nodes, fmt="scs", Cc=64, sigma=256)
+        p = hostapi.Problem("irregular", a.nodes, a.nodes, a.nodes, **ratelib.FMT)
         out["cases"].append(measure(L, a, "irregular, %d^3 nodes" % a.nodes, p, None))
         p.free()
-    text = json.dumps(out)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    ratelib.emit(out, a.out)
 
 
 def merge(a):
-    runs = [json.load(open(f)) for f in a.files]
-    head = {k: runs[0][k] for k in ("library", "csrc_hash")}
-    if any({k: r[k] for k in head} != head for r in runs):
-        raise SystemExit("the runs do not describe the same build")
-    out = dict(head, processes=len(runs), devices=sorted({r["device"] for r in runs}),
-               note="one entry per fresh process; only ratios taken inside one process count (DESIGN 4.1).  Nothing is gated: "
-                    "the figures say what a polynomial body costs against a Jacobi and an SGS body and what it buys in iterations",
-               runs=[r["cases"] for r in runs])
-    with open(a.out, "w") as fo:
-        json.dump(out, fo, indent=1)
-        fo.write("\n")
-    print(json.dumps(out))
+    ratelib.merge_cases(a, NOTE)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    sub = ap.add_subparsers(dest="cmd", required=True)
-    r = sub.add_parser("run")
-    r.add_argument("--sizes", default="64,128")
-    r.add_argument("--nodes", type=int, default=80)
-    r.add_argument("--bodies", type=int, default=100)
-    r.add_argument("--repeats", type=int, default=3)
-    r.add_argument("--apply-reps", dest="apply_reps", type=int, default=20)
-    r.add_argument("--itermax", type=int, default=5000)
-    r.add_argument("--piece", type=int, default=10)
-    r.add_argument("--out", default=None)
-    mg = sub.add_parser("merge")
-    mg.add_argument("files", nargs="+")
-    mg.add_argument("--out", required=True)
-    a = ap.parse_args()
-    (run if a.cmd == "run" else merge)(a)
+def main(parse=True):
+    return ratelib.cli(run, merge, lambda r: r.add_argument("--sizes", default="64,128"), parse,
+                       nodes=80, bodies=100, repeats=3, apply_reps=20, itermax=5000, piece=10)
 
 
 if __name__ == "__main__":
