@@ -482,6 +482,8 @@ void sb_gmres_counters(const sb_gmres* s, int out[5]); /* {stop, steps run, cycl
  * - h[nvec-1]*V[nvec-1][e]), ascending i, every product rounded before its subtraction.  Stream-ordered. */
 void sb_multidot(uint32_t n, int nvec, const double* V, size_t ldv, const double* w, double* h_dev);
 void sb_multiaxpy_sub(uint32_t n, int nvec, const double* V, size_t ldv, const double* h_dev, double* w);
+/* their launch over n rows: out = {workgroups, threads per workgroup, CUs} */
+void sb_gmres_group_launch(uint32_t n, uint32_t out[3]);
 /* test entry: sqrt_dev[e] = sqrt(a[e]), div_dev[e] = a[e] / b[e] as the scalar steps compute them (IEEE correctly rounded) */
 void sb_debug_sqrt_div(uint32_t n, const double* a_dev, const double* b_dev, double* sqrt_dev, double* div_dev);
 
@@ -529,6 +531,25 @@ double sb_cgb_check_residual(const sb_cgb* s, int c);         /* max|x_0 - xexac
 double sb_cgb_loop_ms(const sb_cgb* s); /* GPU milliseconds between the end of sb_cgb_start and sb_cgb_finish */
 /* c >= 0: {stop, stop_next, iters, n_rr, n_pAp} of column c; c = -1: {all stopped, columns stopped, bodies enqueued, 0, 0} */
 void sb_cgb_counters(const sb_cgb* s, int c, int out[5]);
+/* Blocking test entries: the loop's vector kernels alone, through the launch functions the loop uses.  Block vectors of n rows
+ * (device pointers, 16-byte aligned); neg_alpha / beta / alpha / stop / x_pending: nrhs HOST values, column c's at [c], put into
+ * zeroed control blocks; the global stop flag is clear.
+ * sb_block_vec_native, op 0: l1 = level-1 values of A_c . B_c.  op 1: R_c += neg_alpha_c * A_c and the level-1 values of
+ * R_c . R_c; a column with stop_c != 0 keeps its R_c and its l1 values (B_dev unused).  op 2: R_c = A_c + (-1.0) * B_c and the
+ * level-1 values of R_c . R_c (ops 0 and 2 read neither host array).  Column c's ceil(n/256) values at l1_dev + c * ceil(n/256).
+ * sb_cgb_update_p_native: P_c = R_c + beta_c * P_c (which != 0: R_c + 0.0 * R_c; beta and x_pending unused) after, where
+ * x_pending_c != 0 and which == 0, X_c += alpha_c * P_c on the old P_c; a column with stop_c != 0 keeps P_c and X_c.
+ * sb_cgb_x_finalize_native: X_c += alpha_c * P_c where x_pending_c != 0. */
+void sb_block_vec_native(int op, int nrhs, uint32_t n, const double* A_dev, const double* B_dev, double* R_dev,
+    const double* neg_alpha_host, const int* stop_host, double* l1_dev);
+void sb_cgb_update_p_native(int nrhs, uint32_t n, const double* R_dev, double* P_dev, double* X_dev, const double* beta_host,
+    const double* alpha_host, const int* stop_host, const int* x_pending_host, int which);
+void sb_cgb_x_finalize_native(int nrhs, uint32_t n, double* X_dev, const double* P_dev, const double* alpha_host,
+    const int* x_pending_host);
+/* their launches over n rows: out = {workgroups, threads per workgroup, CUs}; sb_block_vec_launch: sb_block_vec_native's,
+ * sb_cgb_rows_launch: the other two's */
+void sb_block_vec_launch(uint32_t n, uint32_t out[3]);
+void sb_cgb_rows_launch(uint32_t n, uint32_t out[3]);
 
 /* ---- CG with a diagonal preconditioner ---------------------------------------------------------------- */
 /* solveCG's loop with z = r o dinv put back (HPCG's CG with its preconditioner): alpha = r.z / p.Ap, beta = r.z / (r.z)_old,

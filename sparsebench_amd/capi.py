@@ -48,7 +48,8 @@ SYMBOLS = [
     "sb_spmmv_native", "sb_spmmv_native_dot", "sb_block_interleave", "sb_block_deinterleave", "sb_matrix_spmmv_bytes",
     "sb_cgb_create", "sb_cgb_free", "sb_cgb_nrhs", "sb_cgb_launches_per_body", "sb_cgb_solve", "sb_cgb_start", "sb_cgb_run_iters",
     "sb_cgb_finish", "sb_cgb_iterations", "sb_cgb_history", "sb_cgb_solution", "sb_cgb_check_residual", "sb_cgb_loop_ms",
-    "sb_cgb_counters",
+    "sb_cgb_counters", "sb_block_vec_native", "sb_block_vec_launch", "sb_cgb_update_p_native", "sb_cgb_x_finalize_native",
+    "sb_cgb_rows_launch", "sb_gmres_group_launch",
     "sb_matrix_diagonal", "sb_pcg_create", "sb_pcg_free", "sb_pcg_solve", "sb_pcg_start", "sb_pcg_run_iters", "sb_pcg_finish",
     "sb_pcg_history", "sb_pcg_solution", "sb_pcg_check_residual", "sb_pcg_dinv", "sb_pcg_launches_per_body", "sb_pcg_loop_ms",
     "sb_pcg_counters", "sb_pcg_update_r_native", "sb_pcg_update_r_launch", "sb_pcg_collectives_per_body", "sb_pcg_local_reduce_native",
@@ -276,6 +277,12 @@ def load():
         "sb_cgb_check_residual": (C.c_double, [vp, C.c_int]),
         "sb_cgb_loop_ms": (C.c_double, [vp]),
         "sb_cgb_counters": (None, [vp, C.c_int, vp]),
+        "sb_block_vec_native": (None, [C.c_int, C.c_int, u32, vp, vp, vp, vp, vp, vp]),
+        "sb_block_vec_launch": (None, [u32, vp]),
+        "sb_cgb_update_p_native": (None, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, C.c_int]),
+        "sb_cgb_x_finalize_native": (None, [C.c_int, u32, vp, vp, vp, vp]),
+        "sb_cgb_rows_launch": (None, [u32, vp]),
+        "sb_gmres_group_launch": (None, [u32, vp]),
         # CG with a diagonal preconditioner
         "sb_matrix_diagonal": (None, [vp, vp]),
         "sb_pcg_create": (vp, [vp, vp, vp, vp, vp]),

@@ -76,18 +76,41 @@ static void launch_spmmv(const sb_matrix* m, int nv, const double* X, double* Y,
   HIP_CHECK(hipGetLastError());
 }
 
+// grid of block_vec_k over n rows: a wave per 256-row group, four waves per workgroup, 8 workgroups per CU at most
+static uint32_t block_vec_grid(uint32_t n)
+{
+  const uint32_t nGroups = (n + 255u) >> 8;
+  return std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * 8u, (nGroups + 3u) / 4u));
+}
+// grid of the two row kernels (cgb_update_p, cgb_x_finalize) over n rows: a thread per row, strip-mined past the cap
+static uint32_t cgb_rows_grid(uint32_t n) { return stream_grid(n, 256); }
+
 // OP of block_vec_k over n rows
 static void launch_block_vec(int op, int nv, uint32_t n, const double* A, const double* B, double* R, const CgScalars* S, double* l1,
     const int* stop)
 {
   if (n == 0) return;
-  const uint32_t nGroups = (n + 255u) >> 8;
-  const dim3 grid(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * 8u, (nGroups + 3u) / 4u))), block(256);
+  const dim3 grid(block_vec_grid(n)), block(256);
   CGB_DISPATCH(nv, {
     if (op == 0) hipLaunchKernelGGL((block_vec_k<NV, 0>), grid, block, 0, g.stream, n, A, B, R, S, l1, stop);
     else if (op == 1) hipLaunchKernelGGL((block_vec_k<NV, 1>), grid, block, 0, g.stream, n, A, B, R, S, l1, stop);
     else hipLaunchKernelGGL((block_vec_k<NV, 2>), grid, block, 0, g.stream, n, A, B, R, S, l1, stop);
   });
+  HIP_CHECK(hipGetLastError());
+}
+
+// P_c = R_c + beta_c P_c (which != 0: R_c + 0.0 R_c) with the owed x update, over n rows
+static void launch_cgb_update_p(int nv, uint32_t n, const double* R, double* P, double* X, const CgScalars* S, int which, const int* stop)
+{
+  if (n == 0) return;
+  CGB_DISPATCH(nv, hipLaunchKernelGGL(cgb_update_p<NV>, dim3(cgb_rows_grid(n)), dim3(256), 0, g.stream, n, R, P, X, S, which, stop));
+  HIP_CHECK(hipGetLastError());
+}
+// the x update every column's last body left owing, over n rows
+static void launch_cgb_x_finalize(int nv, uint32_t n, double* X, const double* P, const CgScalars* S)
+{
+  if (n == 0) return;
+  CGB_DISPATCH(nv, hipLaunchKernelGGL(cgb_x_finalize<NV>, dim3(cgb_rows_grid(n)), dim3(256), 0, g.stream, n, X, P, S));
   HIP_CHECK(hipGetLastError());
 }
 
@@ -214,11 +237,7 @@ static void cgb_spmmv_and_pAp(sb_cgb* s, const int* stop)
 static void cgb_body(sb_cgb* s, int k)
 {
   const int* stop = &s->ctl->stop;
-  if (s->nr) {
-    CGB_DISPATCH(s->nv, hipLaunchKernelGGL(cgb_update_p<NV>, dim3(stream_grid(s->nr, 256)), dim3(256), 0, g.stream, s->nr,
-                            (const double*)s->r, s->p, s->x, (const CgScalars*)s->S, k == 1 ? 1 : 0, stop));
-    HIP_CHECK(hipGetLastError());
-  }
+  launch_cgb_update_p(s->nv, s->nr, s->r, s->p, s->x, s->S, k == 1 ? 1 : 0, stop);
   cgb_spmmv_and_pAp(s, stop);
   cgb_scalar_launch<2>(s, s->l1pAp, 0);
   launch_block_vec(1, s->nv, s->nr, s->Ap, nullptr, s->r, s->S, s->l1rr, stop);
@@ -260,8 +279,7 @@ int sb_cgb_finish(sb_cgb* s)
   s->clock.need_open("sb_cgb_finish", "sb_cgb_start");
   s->clock.end();
   if (s->nr) { // the x update every column's last body left to "the next p update": nobody comes after it
-    CGB_DISPATCH(s->nv, hipLaunchKernelGGL(cgb_x_finalize<NV>, dim3(stream_grid(s->nr, 256)), dim3(256), 0, g.stream, s->nr, s->x,
-                            (const double*)s->p, (const CgScalars*)s->S));
+    launch_cgb_x_finalize(s->nv, s->nr, s->x, s->p, s->S);
     hipLaunchKernelGGL(cgb_clear_pending, dim3(1), dim3(64), 0, g.stream, s->S, s->nv);
     HIP_CHECK(hipGetLastError());
   }
@@ -331,4 +349,75 @@ void sb_cgb_counters(const sb_cgb* s, int c, int out[5])
   }
   const CgbControl h = read_block(s->ctl);
   out[0] = h.stop, out[1] = h.nStopped, out[2] = s->k_next - 1, out[3] = 0, out[4] = 0;
+}
+
+// --- blocking test entries: the vector kernels of the loop alone, launched by the loop's own launch functions ------------------
+// grid of block_vec_k over n rows
+void sb_block_vec_launch(uint32_t n, uint32_t out[3])
+{
+  need_init();
+  out[0] = block_vec_grid(n), out[1] = 256u, out[2] = (uint32_t)g.prop.multiProcessorCount;
+}
+// grid of cgb_update_p and cgb_x_finalize over n rows
+void sb_cgb_rows_launch(uint32_t n, uint32_t out[3])
+{
+  need_init();
+  out[0] = cgb_rows_grid(n), out[1] = 256u, out[2] = (uint32_t)g.prop.multiProcessorCount;
+}
+
+// nrhs zeroed control blocks on the device, filled by `fill(block, column)`; freed by test_block_done
+template <class F> static CgScalars* cgb_test_blocks(int nrhs, F fill)
+{
+  std::vector<CgScalars> h(nrhs, zeroed<CgScalars>());
+  for (int c = 0; c < nrhs; c++) fill(h[c], c);
+  CgScalars* S = (CgScalars*)sb_malloc(sizeof(CgScalars) * nrhs);
+  write_block(S, h.data(), nrhs);
+  return S;
+}
+
+void sb_block_vec_native(int op, int nrhs, uint32_t n, const double* A_dev, const double* B_dev, double* R_dev, const double* neg_alpha_host,
+    const int* stop_host, double* l1_dev)
+{
+  need_init();
+  cgb_need_width(nrhs, "sb_block_vec_native");
+  if (op < 0 || op > 2) SB_FATAL("sb_block_vec_native: op = %d outside 0 .. 2", op);
+  if (n == 0) return;
+  need_aligned16({ A_dev, B_dev, R_dev }, "sb_block_vec_native", "block vectors");
+  if (op != 1) { // as sb_cgb_start and the dot pass launch it: no control blocks
+    launch_block_vec(op, nrhs, n, A_dev, B_dev, R_dev, nullptr, l1_dev, nullptr);
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    return;
+  }
+  CgScalars* S = cgb_test_blocks(nrhs, [&](CgScalars& h, int c) { h.neg_alpha = neg_alpha_host[c], h.stop = stop_host[c]; });
+  CgbControl* ctl = test_block(zeroed<CgbControl>());
+  launch_block_vec(1, nrhs, n, A_dev, nullptr, R_dev, S, l1_dev, &ctl->stop);
+  test_block_done(S);
+  sb_free(ctl);
+}
+
+void sb_cgb_update_p_native(int nrhs, uint32_t n, const double* R_dev, double* P_dev, double* X_dev, const double* beta_host,
+    const double* alpha_host, const int* stop_host, const int* x_pending_host, int which)
+{
+  need_init();
+  cgb_need_width(nrhs, "sb_cgb_update_p_native");
+  if (n == 0) return;
+  need_aligned16({ R_dev, P_dev, X_dev }, "sb_cgb_update_p_native", "block vectors");
+  CgScalars* S = cgb_test_blocks(nrhs, [&](CgScalars& h, int c) {
+    h.beta = beta_host[c], h.alpha = alpha_host[c], h.stop = stop_host[c], h.x_pending = x_pending_host[c];
+  });
+  CgbControl* ctl = test_block(zeroed<CgbControl>());
+  launch_cgb_update_p(nrhs, n, R_dev, P_dev, X_dev, S, which, &ctl->stop);
+  test_block_done(S);
+  sb_free(ctl);
+}
+
+void sb_cgb_x_finalize_native(int nrhs, uint32_t n, double* X_dev, const double* P_dev, const double* alpha_host, const int* x_pending_host)
+{
+  need_init();
+  cgb_need_width(nrhs, "sb_cgb_x_finalize_native");
+  if (n == 0) return;
+  need_aligned16({ X_dev, P_dev }, "sb_cgb_x_finalize_native", "block vectors");
+  CgScalars* S = cgb_test_blocks(nrhs, [&](CgScalars& h, int c) { h.alpha = alpha_host[c], h.x_pending = x_pending_host[c]; });
+  launch_cgb_x_finalize(nrhs, n, X_dev, P_dev, S);
+  test_block_done(S);
 }

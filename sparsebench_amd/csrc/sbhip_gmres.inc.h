@@ -329,6 +329,13 @@ void sb_gmres_counters(const sb_gmres* s, int out[5])
   out[0] = h.stop, out[1] = h.steps, out[2] = h.cycles, out[3] = h.n_res, out[4] = h.n_rr;
 }
 
+// grid of gm_multidot_k and gm_multiupdate_k over n rows: gm_group_grid
+void sb_gmres_group_launch(uint32_t n, uint32_t out[3])
+{
+  need_init();
+  out[0] = gm_group_grid((n + 255u) >> 8).x, out[1] = 256u, out[2] = (uint32_t)g.prop.multiProcessorCount;
+}
+
 void sb_multidot(uint32_t n, int nvec, const double* V, size_t ldv, const double* w, double* h_dev)
 {
   need_init();

@@ -13,7 +13,13 @@ LIB = os.path.join(ROOT, "sparsebench_amd", "lib")
 NEW = ["sb_spmmv_native", "sb_spmmv_native_dot", "sb_block_interleave", "sb_block_deinterleave", "sb_matrix_spmmv_bytes",
        "sb_cgb_create", "sb_cgb_free", "sb_cgb_nrhs", "sb_cgb_launches_per_body", "sb_cgb_solve", "sb_cgb_start", "sb_cgb_run_iters",
        "sb_cgb_finish", "sb_cgb_iterations", "sb_cgb_history", "sb_cgb_solution", "sb_cgb_check_residual", "sb_cgb_loop_ms",
-       "sb_cgb_counters"]
+       "sb_cgb_counters",
+       # the blocking test entries of the loop's vector kernels and the launch queries (tests/test_gpu_batch_vec_kernels.py,
+       # tests/test_gpu_gmres_kernels.py)
+       "sb_block_vec_native", "sb_block_vec_launch", "sb_cgb_update_p_native", "sb_cgb_x_finalize_native", "sb_cgb_rows_launch",
+       "sb_gmres_group_launch"]
+ARGS = {"sb_block_vec_native": 9, "sb_block_vec_launch": 2, "sb_cgb_update_p_native": 10, "sb_cgb_x_finalize_native": 6,
+        "sb_cgb_rows_launch": 2, "sb_gmres_group_launch": 2}
 
 
 def test_batch_symbols_declared_exported_and_listed():
@@ -25,6 +31,10 @@ def test_batch_symbols_declared_exported_and_listed():
         assert hasattr(L, n), "libsbhip.so does not export %s" % n
         assert n in capi.SYMBOLS
         assert getattr(L, n).argtypes is not None, "capi.load() gives %s no prototype" % n
+    for n, count in ARGS.items():  # the prototype has as many parameters as the header's declaration
+        decl = re.search(r"\b%s\s*\(([^)]*)\)" % n, header).group(1)
+        assert len(decl.split(",")) == count == len(getattr(L, n).argtypes), (n, decl)
+        assert getattr(L, n).restype is None
     assert L.sb_is_initialized() == 0  # loading touched no device
 
 

@@ -71,6 +71,42 @@ def test_multidot_and_multiaxpy_sub_bit_for_bit(gpu, n, kind):
             d.free()
 
 
+def second_trip_n(L):
+    """gm_multidot_k / gm_multiupdate_k: a wave per 256-row group, four waves per workgroup; one full group more than the capped
+    grid has waves, then 257 rows -- from the launch the library reports"""
+    out = np.zeros(3, dtype=np.uint32)
+    L.sb_gmres_group_launch(0x7FFFFF00, out.ctypes.data)
+    cap, threads, cus = int(out[0]), int(out[1]), int(out[2])
+    assert threads == 256 and cap >= cus >= 1
+    n = 256 * (cap * 4) + 257
+    L.sb_gmres_group_launch(n, out.ctypes.data)
+    assert int(out[0]) == cap  # the grid is at its cap: the groups `4 cap` and `4 cap + 1` are second trips, the last one partial
+    return n
+
+
+@pytest.mark.parametrize("nvec", [1, 5])
+@pytest.mark.parametrize("kind", ["random", "nonfinite"])
+def test_second_grid_stride_trip_bit_for_bit(gpu, kind, nvec):
+    """both kernels past the grid's cap, under and past the multidot's unroll"""
+    L = gpu
+    n = second_trip_n(L)
+    print("second grid-stride trip with a partial last group at n =", n)
+    V, w, h = make(n, nvec, kind, 77 * nvec + len(kind))
+    ldv = ((n + 1) // 2) * 2 + 6
+    dV, dw, dh = upload(V, ldv), capi.DeviceVector.from_host(w), capi.DeviceVector(nvec)
+    L.sb_multidot(n, nvec, dV.ptr, ldv, dw.ptr, dh.ptr)
+    got = dh.get()
+    want = np.array(gmres_ref.multidot(list(V), w))
+    assert bits_equal(got, want), (n, nvec, kind, got, want)
+    c = got if np.all(np.isfinite(got)) and kind != "nonfinite" else h
+    dc = capi.DeviceVector.from_host(c)
+    L.sb_multiaxpy_sub(n, nvec, dV.ptr, ldv, dc.ptr, dw.ptr)
+    assert bits_equal(dw.get(), gmres_ref.multiaxpy_sub(list(V), c, w)), (n, nvec, kind)
+    assert bits_equal(dV.get().reshape(nvec, ldv)[:, :n], V)  # V untouched
+    for d in (dV, dw, dh, dc):
+        d.free()
+
+
 def test_device_sqrt_and_divide_are_correctly_rounded(gpu):
     L = gpu
     rng = np.random.default_rng(7)
