@@ -442,6 +442,38 @@ int sb_cg_phase_ms(sb_cg* s, double ms_out[8], int count_out[8]);
 /* device control block: out = {stop, stop_next, iters, n_rr, n_pAp} (proof that the
  * timed iterations really ran) */
 void sb_cg_counters(const sb_cg* s, int out[5]);
+/* Blocking test entries: the loop's double-precision vector and scalar kernels alone, through the launch functions the loop
+ * uses.  Vectors, level-1 arrays, partials and histories are device pointers of the caller's (vectors 16-byte aligned); the
+ * layer's stream; synchronised before return.  The control block is plain host data in the order of the device's block,
+ * blk_d[9] = {rr, rr_old, pAp, alpha, beta, neg_alpha, local, eps, snap_rr} and blk_i[11] = {stop, stop_next, iters, n_rr,
+ * n_pAp, itermax, hist_cap, x_pending, p2p_error, snap_iters, snap_stop_next}: uploaded between guard words, handed to the
+ * kernel (its stop flag is the block's), and every field copied back into blk_d / blk_i; none is computed by the entry.
+ * Each returns the number of guard words around the device's block that changed (0 unless a kernel wrote outside it).
+ * sb_cg_update_p_native: mode 0 p = r + beta p (which != 0: r + 0.0 r) with, x_dev != NULL, which == 0 and x_pending, the
+ * owed x += alpha p on the old p; mode 1 / 2 (which == 0): with the beta step and loop test at its head, r.r from the m
+ * level-1 values l1_dev / from `local`, recorded into rr_hist_dev (hist_cap entries).
+ * sb_cg_update_r_native: mode 0 r += neg_alpha Ap; mode 1 / 2: with the alpha step at its head, p.Ap from the m level-1
+ * values l1in_dev / from `local`, recorded into pAp_hist_dev; the ceil(n/256) level-1 values of r.r go to l1out_dev.
+ * sb_cg_scalar_native: the scalar step `mode` (0 prologue, 1 beta / loop test, 2 alpha) as its own launch; reduce != 0: the
+ * sum of the m values q_dev (l1 != 0: level-1 values, else 4 m level-0 partials; to_local != 0: into `local`, no step),
+ * reduce == 0: the sum is `local`.
+ * sb_cg_x_finalize_native: x += alpha p where x_pending, p = p1_dev for an odd n_pAp, else p0_dev.
+ * sb_cg_dot_spans_native: op 1 x += alpha a, r -= alpha b, op 2 r = a - b; the 4 ceil(n/256) level-0 partials of r.r.
+ * sb_waxpby_sdev_native: w = x + alpha y (negative != 0: neg_alpha), the scalar read from the device's block. */
+int sb_cg_update_p_native(int mode, uint32_t n, const double* r_dev, double* p_dev, double* x_dev, int which, uint32_t m,
+    const double* l1_dev, double* rr_hist_dev, double* blk_d, int* blk_i);
+int sb_cg_update_r_native(int mode, uint32_t n, const double* Ap_dev, double* r_dev, double* l1out_dev, uint32_t m,
+    const double* l1in_dev, double* rr_hist_dev, double* pAp_hist_dev, double* blk_d, int* blk_i);
+int sb_cg_scalar_native(int mode, int reduce, uint32_t m, const double* q_dev, double* rr_hist_dev, double* pAp_hist_dev,
+    int to_local, int defer_x, int l1, double* blk_d, int* blk_i);
+int sb_cg_x_finalize_native(uint32_t n, double* x_dev, const double* p0_dev, const double* p1_dev, double* blk_d, int* blk_i);
+int sb_cg_dot_spans_native(int op, uint32_t n, const double* a_dev, const double* b_dev, double* x_dev, double* r_dev,
+    double* partials_dev, double* blk_d, int* blk_i);
+int sb_waxpby_sdev_native(uint32_t n, const double* x_dev, int negative, const double* y_dev, double* w_dev, double* blk_d,
+    int* blk_i);
+/* the launches of the two streaming kernels over n rows: out = {workgroups, threads per workgroup, CUs}; mode as above */
+void sb_cg_update_p_launch(uint32_t n, uint32_t out[3]);
+void sb_cg_update_r_launch(uint32_t n, int mode, uint32_t out[3]);
 
 /* ---- restarted GMRES(m) (the solver the reference's driver names and leaves empty: src/main.c:31,217-222) ------ */
 /* For matrices that are not symmetric positive definite.  Double precision, ONE rank; a single-precision matrix, several

@@ -33,6 +33,8 @@ SYMBOLS = [
     "sb_comm_data_plane", "sb_comm_data_plane_selected", "sb_comm_rccl_info", "sb_cg_phase_timing", "sb_cg_phase_ms",
     "sb_comm_halo_push_inside", "sb_comm_halo_fold", "sb_comm_halo_fold_selected", "sb_cg_halo_fold", "sb_lab_build", "sb_cg_collectives_per_body",
     "sb_cg_set_fuse_p", "sb_cg_fuse_p", "sb_cg_set_fuse_alpha", "sb_cg_set_fuse_beta",
+    "sb_cg_update_p_native", "sb_cg_update_r_native", "sb_cg_scalar_native", "sb_cg_x_finalize_native", "sb_cg_dot_spans_native",
+    "sb_waxpby_sdev_native", "sb_cg_update_p_launch", "sb_cg_update_r_launch",
     "sb_malloc_host_visible", "sb_host_visible_reason", "sb_malloc_pinned_host", "sb_free_pinned_host", "sb_copy_counters",
     "sb_region_begin", "sb_region_end", "sb_region_seconds", "sb_region_reset",
     "sb_is_pinned_host_ptr", "sb_mem_free_bytes",
@@ -153,6 +155,15 @@ def load():
         "sb_cg_spmv_ms": (C.c_double, [vp, C.POINTER(C.c_int)]),
         "sb_cg_spmv_us_series": (C.c_int, [vp, C.POINTER(C.c_float), C.c_int]),
         "sb_cg_counters": (None, [vp, vp]),
+        # the CG loop's kernels alone (blocking test entries) and the launches of its two streaming kernels
+        "sb_cg_update_p_native": (C.c_int, [C.c_int, u32, vp, vp, vp, C.c_int, u32, vp, vp, vp, vp]),
+        "sb_cg_update_r_native": (C.c_int, [C.c_int, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp]),
+        "sb_cg_scalar_native": (C.c_int, [C.c_int, C.c_int, u32, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "sb_cg_x_finalize_native": (C.c_int, [u32, vp, vp, vp, vp, vp]),
+        "sb_cg_dot_spans_native": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "sb_waxpby_sdev_native": (C.c_int, [u32, vp, C.c_int, vp, vp, vp, vp]),
+        "sb_cg_update_p_launch": (None, [u32, vp]),
+        "sb_cg_update_r_launch": (None, [u32, C.c_int, vp]),
         "sb_debug_stream_read_gbs": (C.c_double, [C.c_size_t, C.c_int]),
         "sb_matrix_pack_level": (C.c_int, [vp]),
         "sb_matrix_use_packed": (None, [vp, C.c_int]),

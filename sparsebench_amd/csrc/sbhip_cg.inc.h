@@ -201,6 +201,90 @@ void sb_cg_set_fused(sb_cg* s, int fused)
 }
 int sb_cg_vector_phase(sb_cg*) { return 0; } // (the one-launch vector phase: removed with fused level 2)
 
+// ---- the launches of the loop's vector and scalar kernels: the loop and the blocking test entries (below) share them ---------
+// workgroups of the two vector kernels: 1024 threads (512 workgroups to dispatch instead of 2048: +0.7 % it/s at 128^3,
+// measured back to back; SB_VEC_BLOCK=256|512 for comparison)
+static uint32_t cg_vec_block()
+{
+  static const uint32_t vb = getenv("SB_VEC_BLOCK") && atoi(getenv("SB_VEC_BLOCK")) >= 64 ? (uint32_t)atoi(getenv("SB_VEC_BLOCK")) & ~63u : 1024u;
+  return vb;
+}
+static uint32_t cg_vec_cap() { return (uint32_t)g.prop.multiProcessorCount * (2048u / cg_vec_block()); }
+// grid of cg_update_p (and cg_update_p_push) over n rows: a thread per two double2, strip-mined past the cap
+static uint32_t cg_update_p_grid(uint32_t n)
+{
+  const uint32_t vb = cg_vec_block();
+  return std::max(1u, std::min(cg_vec_cap(), (n / 2 + 1 + vb - 1) / vb));
+}
+// grid of cg_update_r_k<mode> over n rows: a wave per 256-row group; mode 1 (every workgroup reads all m level-1 values) runs
+// one workgroup per CU where the others run two
+static uint32_t cg_update_r_grid(uint32_t n, int mode)
+{
+  const uint32_t vb   = cg_vec_block();
+  const uint32_t grid = std::max(1u, std::min(cg_vec_cap(), (((n + 255u) >> 8) + vb / 64 - 1) / (vb / 64)));
+  if (mode != 1) return grid;
+  // one workgroup per CU (the separate r update runs two): every workgroup reads all m values, so half the workgroups is half
+  // that traffic -- 128^3, same box, alternating: 41.6 / 42.1 us per iteration against 42.4 / 42.7 with two (and 43.8 / 44.2
+  // with the separate alpha launch)
+  static const uint32_t perCu = getenv("SB_ALPHA_WG_PER_CU") ? (uint32_t)std::max(1, atoi(getenv("SB_ALPHA_WG_PER_CU"))) : 1u;
+  return std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * perCu, grid));
+}
+// cg_update_p<mode>: mode 0 p = r + beta p (which != 0: r + 0.0 r) with the owed x update; 1 / 2 with the beta step at its head,
+// from the m level-1 values l1 / from S->local
+static void launch_cg_update_p(int mode, uint32_t n, const double* r, double* p, double* x, CgScalars* S, int which, uint32_t m,
+    const double* l1, double* rr_hist)
+{
+  const dim3 grid(cg_update_p_grid(n)), block(cg_vec_block());
+  if (mode == 2) hipLaunchKernelGGL(cg_update_p<2>, grid, block, 0, g.stream, n, r, p, x, S, which, m, l1, rr_hist);
+  else if (mode == 1) hipLaunchKernelGGL(cg_update_p<1>, grid, block, 0, g.stream, n, r, p, x, S, which, m, l1, rr_hist);
+  else if (n) hipLaunchKernelGGL(cg_update_p<0>, grid, block, 0, g.stream, n, r, p, x, S, which, 0u, (const double*)nullptr, (double*)nullptr);
+  HIP_CHECK(hipGetLastError());
+}
+// cg_update_r_k<mode>: mode 0 r -= alpha Ap with the level-1 values of r.r into l1out; 1 / 2 with the alpha step at its head,
+// from the m level-1 values l1in / from S->local
+static void launch_cg_update_r(int mode, uint32_t n, const double* Ap, double* r, CgScalars* S, double* l1out, const int* stop, uint32_t m,
+    const double* l1in, double* rr_hist, double* pAp_hist)
+{
+  const dim3 grid(cg_update_r_grid(n, mode)), block(cg_vec_block());
+  if (mode == 2) hipLaunchKernelGGL(cg_update_r_k<2>, grid, block, 0, g.stream, n, Ap, r, S, l1out, stop, m, l1in, rr_hist, pAp_hist);
+  else if (mode == 1) hipLaunchKernelGGL(cg_update_r_k<1>, grid, block, 0, g.stream, n, Ap, r, S, l1out, stop, m, l1in, rr_hist, pAp_hist);
+  else
+    hipLaunchKernelGGL(cg_update_r_k<0>, grid, block, 0, g.stream, n, Ap, r, S, l1out, stop, 0u, (const double*)nullptr, (double*)nullptr,
+        (double*)nullptr);
+  HIP_CHECK(hipGetLastError());
+}
+// the x update the last body left owing, over n rows (p0 / p1: the buffers of the even / odd bodies)
+static void launch_cg_x_finalize(uint32_t n, double* x, const double* p0, const double* p1, const CgScalars* S)
+{
+  if (n == 0) return;
+  hipLaunchKernelGGL(cg_x_finalize, dim3(stream_grid(n, 256)), dim3(256), 0, g.stream, n, x, p0, p1, S);
+  HIP_CHECK(hipGetLastError());
+}
+// w = x + (*beta_dev) y of the reference-shaped op list (256-thread workgroups)
+static void launch_waxpby_sdev(uint32_t n, const double* x, const double* beta_dev, const double* y, double* w, const int* stop)
+{
+  if (n == 0) return;
+  hipLaunchKernelGGL(waxpby_sdev_k, dim3(stream_grid(n / 2 + 1, 256)), dim3(256), 0, g.stream, n, x, beta_dev, y, w, stop);
+  HIP_CHECK(hipGetLastError());
+}
+// cg_scalar_k<mode, reduce>: one workgroup
+static void launch_cg_scalar(int mode, bool reduce, uint32_t m, const double* q, CgScalars* S, double* rr_hist, double* pAp_hist, int to_local,
+    int defer_x, int l1)
+{
+  const dim3 grid(1), block(1024);
+#define SB_CG_SCALAR(MODE)                                                                                                          \
+  {                                                                                                                                \
+    if (reduce) hipLaunchKernelGGL((cg_scalar_k<MODE, true>), grid, block, 0, g.stream, m, q, S, rr_hist, pAp_hist, to_local, defer_x, l1); \
+    else hipLaunchKernelGGL((cg_scalar_k<MODE, false>), grid, block, 0, g.stream, m, q, S, rr_hist, pAp_hist, to_local, defer_x, l1);       \
+  }
+  if (mode == 0) SB_CG_SCALAR(0)
+  else if (mode == 1) SB_CG_SCALAR(1)
+  else if (mode == 2) SB_CG_SCALAR(2)
+  else SB_FATAL("launch_cg_scalar: unknown mode %d", mode);
+#undef SB_CG_SCALAR
+  HIP_CHECK(hipGetLastError());
+}
+
 template <int MODE> static void scalar_launch(sb_cg* s, int defer_x, const double* q, int l1 = 0);
 static int pAp_is_level1(const sb_cg* s);
 static int fusealpha_plan(sb_cg* s, int l1, uint32_t vb);
@@ -385,16 +469,12 @@ template <int MODE> static void scalar_launch(sb_cg* s, int defer_x, const doubl
     HIP_CHECK(hipGetLastError());
     return;
   }
-  hipLaunchKernelGGL((cg_scalar_k<MODE, true>), dim3(1), dim3(1024), 0, g.stream, m, q,
-      s->S, s->rr_hist, s->pAp_hist, multi_rank() ? 1 : 0, defer_x, l1);
-  HIP_CHECK(hipGetLastError());
+  launch_cg_scalar(MODE, true, m, q, s->S, s->rr_hist, s->pAp_hist, multi_rank() ? 1 : 0, defer_x, l1);
   if (multi_rank()) {
     mark(s, R_DDOT);
     sb_comm_reduction(&s->S->local, 1);
     mark(s, R_COMM);
-    hipLaunchKernelGGL((cg_scalar_k<MODE, false>), dim3(1), dim3(1024), 0, g.stream, s->nPartials, q,
-        s->S, s->rr_hist, s->pAp_hist, 0, defer_x, 0);
-    HIP_CHECK(hipGetLastError());
+    launch_cg_scalar(MODE, false, s->nPartials, q, s->S, s->rr_hist, s->pAp_hist, 0, defer_x, 0);
   }
 }
 
@@ -436,34 +516,23 @@ void sb_cg_set_fuse_beta(sb_cg* s, int on) { s->fuseBetaWant = on < 0 ? -1 : on 
 // (MPI_Allreduce of src/comm.c:659); the step itself is taken by the consumer (fold mode 2) or by cg_scalar_k<MODE, false>
 template <int MODE> static void scalar_reduce_only(sb_cg* s, const double* q, int l1)
 {
-  hipLaunchKernelGGL((cg_scalar_k<MODE, true>), dim3(1), dim3(1024), 0, g.stream, s->nPartials, q, s->S, s->rr_hist, s->pAp_hist, 1, 0, l1);
-  HIP_CHECK(hipGetLastError());
+  launch_cg_scalar(MODE, true, s->nPartials, q, s->S, s->rr_hist, s->pAp_hist, 1, 0, l1);
   mark(s, R_DDOT);
   sb_comm_reduction(&s->S->local, 1);
   mark(s, R_COMM);
 }
 
 // alpha step (src/CGSolver.c:124-126) and r -= alpha Ap + the r.r values of the next body (:128, :112): two launches, or one
-static void alpha_and_r_update(sb_cg* s, int l1, uint32_t capV, uint32_t vb, const int* stop)
+static void alpha_and_r_update(sb_cg* s, int l1, const int* stop)
 {
   const uint32_t n = s->nr;
-  const dim3 grid(std::max(1u, std::min(capV, (((n + 255u) >> 8) + vb / 64 - 1) / (vb / 64))));
-  const int mode = fusealpha_plan(s, l1, vb);
+  const int mode = fusealpha_plan(s, l1, cg_vec_block());
   if (mode) {
-    // one workgroup per CU (the separate r update runs two): every workgroup reads all m values, so half the workgroups is half
-    // that traffic -- 128^3, same box, alternating: 41.6 / 42.1 us per iteration against 42.4 / 42.7 with two (and 43.8 / 44.2
-    // with the separate alpha launch)
-    static const uint32_t perCu = getenv("SB_ALPHA_WG_PER_CU") ? (uint32_t)std::max(1, atoi(getenv("SB_ALPHA_WG_PER_CU"))) : 1u;
-    const dim3 gridA(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * perCu, grid.x)));
     if (mode == 2) {
       scalar_reduce_only<2>(s, s->partials, l1);
       phase_mark(s, PH_ALPHA);
-      hipLaunchKernelGGL(cg_update_r_k<2>, grid, dim3(vb), 0, g.stream, n, s->Ap, s->r, s->S, s->partials2, stop, s->nPartials,
-          (const double*)s->partials, s->rr_hist, s->pAp_hist);
-    } else
-      hipLaunchKernelGGL(cg_update_r_k<1>, gridA, dim3(vb), 0, g.stream, n, s->Ap, s->r, s->S, s->partials2, stop, s->nPartials,
-          (const double*)s->partials, s->rr_hist, s->pAp_hist);
-    HIP_CHECK(hipGetLastError());
+    }
+    launch_cg_update_r(mode, n, s->Ap, s->r, s->S, s->partials2, stop, s->nPartials, s->partials, s->rr_hist, s->pAp_hist);
     mark(s, R_WAXPBY);
     phase_mark(s, PH_R_UPDATE);
     return;
@@ -471,9 +540,7 @@ static void alpha_and_r_update(sb_cg* s, int l1, uint32_t capV, uint32_t vb, con
   scalar_launch<2>(s, 0, nullptr, l1);
   mark(s, R_DDOT);
   phase_mark(s, PH_ALPHA);
-  hipLaunchKernelGGL(cg_update_r_k<0>, grid, dim3(vb), 0, g.stream, n, s->Ap, s->r, s->S, s->partials2, stop, 0u,
-      (const double*)nullptr, (double*)nullptr, (double*)nullptr);
-  HIP_CHECK(hipGetLastError());
+  launch_cg_update_r(0, n, s->Ap, s->r, s->S, s->partials2, stop, 0u, nullptr, nullptr, nullptr);
   mark(s, R_WAXPBY);
   phase_mark(s, PH_R_UPDATE);
 }
@@ -496,9 +563,7 @@ static void flush_beta_fold(sb_cg* s)
 {
   if (!s->betaFold) return;
   if (s->betaFold == 2) { // r.r is in S->local already
-    hipLaunchKernelGGL((cg_scalar_k<1, false>), dim3(1), dim3(1024), 0, g.stream, s->nPartials, (const double*)s->partials2, s->S,
-        s->rr_hist, s->pAp_hist, 0, 1, 0);
-    HIP_CHECK(hipGetLastError());
+    launch_cg_scalar(1, false, s->nPartials, s->partials2, s->S, s->rr_hist, s->pAp_hist, 0, 1, 0);
   } else scalar_launch<1>(s, 1, s->partials2, 1);
   mark(s, R_DDOT);
   phase_mark(s, PH_BETA);
@@ -590,11 +655,7 @@ static void loop_body(sb_cg* s, int k)
 {
   const uint32_t n = s->nr;
   const int* stop  = &s->S->stop;
-  // workgroups of the two vector kernels: 1024 threads (512 workgroups to dispatch instead of 2048: +0.7 % it/s at 128^3,
-  // measured back to back; SB_VEC_BLOCK=256|512 for comparison)
-  static const uint32_t vb = getenv("SB_VEC_BLOCK") && atoi(getenv("SB_VEC_BLOCK")) >= 64 ? (uint32_t)atoi(getenv("SB_VEC_BLOCK")) & ~63u : 1024u;
-  const uint32_t capV = (uint32_t)g.prop.multiProcessorCount * (2048u / vb);
-  dim3 gridV(std::max(1u, std::min(capV, (n / 2 + 1 + vb - 1) / vb))), blockV(vb);
+  const uint32_t vb = cg_vec_block(); // (the two vector kernels' workgroups and grids: cg_vec_block, cg_update_p_grid, cg_update_r_grid)
   if (fusep_plan(s)) {
     // p = r + beta p (:114; k = 1: p = r, :109), the owed x update (:127), the halo exchange (:122) and Ap = A p with its p.Ap
     // values (:123-125) in ONE launch (+ the halo push on several ranks): body k reads p_{k-1} in pbuf[(k - 1) & 1] and writes
@@ -625,7 +686,7 @@ static void loop_body(sb_cg* s, int k)
     spmv_time_end(s);
     phase_mark(s, PH_SPMV);
     s->p = pnew; // (host-side view: the newest p; cg_x_finalize picks the buffer of the last body that RAN from the device counters)
-    alpha_and_r_update(s, 1, capV, vb, stop);
+    alpha_and_r_update(s, 1, stop);
     scalar_launch<1>(s, 1, s->partials2, 1);
     phase_mark(s, PH_BETA);
     return;
@@ -636,6 +697,7 @@ static void loop_body(sb_cg* s, int k)
     // (:122, receive side) | alpha | r update | beta
     sb_halo* h       = s->halo;
     const int which  = k == 1;
+    const dim3 gridV(cg_update_p_grid(n)), blockV(vb);
     const HaloFold& hf = halo_fold_send_plan(h, 0, gridV.x, vb);
     const unsigned long long seq = ++h->seq;
     hipLaunchKernelGGL(cg_update_p_push, gridV, blockV, 0, g.stream, h->push, hf, seq, n, (const double*)s->r, s->p,
@@ -650,12 +712,12 @@ static void loop_body(sb_cg* s, int k)
     spmv_time_end(s);
     mark(s, R_SPMVM);
     phase_mark(s, PH_SPMV);
-    alpha_and_r_update(s, 1, capV, vb, stop);
+    alpha_and_r_update(s, 1, stop);
     beta_step_or_owe(s, vb);
     return;
   }
   if (k == 1) {
-    if (n) hipLaunchKernelGGL(cg_update_p<0>, gridV, blockV, 0, g.stream, n, s->r, s->p, (double*)nullptr, s->S, 1, 0u, (const double*)nullptr, (double*)nullptr); // p = r (:109)
+    launch_cg_update_p(0, n, s->r, s->p, nullptr, s->S, 1, 0u, nullptr, nullptr); // p = r (:109)
     mark(s, R_WAXPBY);
     phase_mark(s, PH_P_UPDATE);
   } else {
@@ -668,13 +730,8 @@ static void loop_body(sb_cg* s, int k)
     }
     // p = r + beta p (:114); fused path: also the x update owed by the previous body (:127) -- and, where the previous body left
     // its beta step / loop test owing, that step at the head of this launch
-    if (s->betaFold == 2)
-      hipLaunchKernelGGL(cg_update_p<2>, gridV, blockV, 0, g.stream, n, s->r, s->p, s->x, s->S, 0, s->nPartials, (const double*)s->partials2, s->rr_hist);
-    else if (s->betaFold == 1)
-      hipLaunchKernelGGL(cg_update_p<1>, gridV, blockV, 0, g.stream, n, s->r, s->p, s->x, s->S, 0, s->nPartials, (const double*)s->partials2, s->rr_hist);
-    else if (n)
-      hipLaunchKernelGGL(cg_update_p<0>, gridV, blockV, 0, g.stream, n, s->r, s->p, s->fused ? s->x : (double*)nullptr, s->S, 0, 0u,
-          (const double*)nullptr, (double*)nullptr);
+    if (s->betaFold) launch_cg_update_p(s->betaFold, n, s->r, s->p, s->x, s->S, 0, s->nPartials, s->partials2, s->rr_hist);
+    else launch_cg_update_p(0, n, s->r, s->p, s->fused ? s->x : nullptr, s->S, 0, 0u, nullptr, nullptr);
     s->betaFold = 0;
     mark(s, R_WAXPBY);
     phase_mark(s, PH_P_UPDATE);
@@ -717,18 +774,16 @@ static void loop_body(sb_cg* s, int k)
   }
   if (s->fused) { // alpha; r -= alpha Ap (:128) + next r.r, beta, loop test; x += alpha p (:127) is owed
     // (level-1 values of r.r into partials2: `partials` keeps the layout the p.Ap producers write)
-    alpha_and_r_update(s, pAp_is_level1(s), capV, vb, stop);
+    alpha_and_r_update(s, pAp_is_level1(s), stop);
     beta_step_or_owe(s, vb);
     return;
   }
   scalar_launch<2>(s, 0, nullptr, pAp_is_level1(s));
   mark(s, R_DDOT);
   phase_mark(s, PH_ALPHA);
-  if (n) {
-    const dim3 gridW(stream_grid(n / 2 + 1, 256)), blockW(256); // (the reference-shaped ops keep their 256-thread workgroups)
-    hipLaunchKernelGGL(waxpby_sdev_k, gridW, blockW, 0, g.stream, n, s->x, &s->S->alpha, s->p, s->x, stop);
-    hipLaunchKernelGGL(waxpby_sdev_k, gridW, blockW, 0, g.stream, n, s->r, &s->S->neg_alpha, s->Ap, s->r, stop);
-    HIP_CHECK(hipGetLastError());
+  if (n) { // (the reference-shaped ops keep their 256-thread workgroups)
+    launch_waxpby_sdev(n, s->x, &s->S->alpha, s->p, s->x, stop);
+    launch_waxpby_sdev(n, s->r, &s->S->neg_alpha, s->Ap, s->r, stop);
     mark(s, R_WAXPBY);
     phase_mark(s, PH_R_UPDATE);
   }
@@ -849,9 +904,7 @@ int sb_cg_finish(sb_cg* s)
   if (s->nr) { // the x update the last body left to "the next p update": nobody comes after it
     // (fused p update: body k left p_k in pbuf[k & 1]; which body ran last is on the device -- n_pAp -- not on the host)
     const bool fp = fusep_plan(s);
-    hipLaunchKernelGGL(cg_x_finalize, dim3(stream_grid(s->nr, 256)), dim3(256), 0, g.stream, s->nr, s->x, fp ? s->pbuf[0] : s->p,
-        fp ? s->pbuf[1] : s->p, s->S);
-    HIP_CHECK(hipGetLastError());
+    launch_cg_x_finalize(s->nr, s->x, fp ? s->pbuf[0] : s->p, fp ? s->pbuf[1] : s->p, s->S);
     HIP_CHECK(hipMemsetAsync(&s->S->x_pending, 0, sizeof(int), g.stream));
   }
   HIP_CHECK(hipStreamSynchronize(g.stream));
@@ -940,4 +993,127 @@ double sb_cg_loop_ms(const sb_cg* s) { return (double)s->loop_ms; }
 void sb_cg_region_ms(const sb_cg* s, double out[4])
 {
   for (int i = 0; i < 4; i++) out[i] = s->region_ms[i];
+}
+
+// --- blocking test entries: the loop's vector and scalar kernels alone, launched by the loop's own launch functions -------------
+void sb_cg_update_p_launch(uint32_t n, uint32_t out[3])
+{
+  need_init();
+  out[0] = cg_update_p_grid(n), out[1] = cg_vec_block(), out[2] = (uint32_t)g.prop.multiProcessorCount;
+}
+void sb_cg_update_r_launch(uint32_t n, int mode, uint32_t out[3])
+{
+  need_init();
+  if (mode < 0 || mode > 2) SB_FATAL("sb_cg_update_r_launch: mode = %d outside 0 .. 2", mode);
+  out[0] = cg_update_r_grid(n, mode), out[1] = cg_vec_block(), out[2] = (uint32_t)g.prop.multiProcessorCount;
+}
+
+// The control block of a test entry: the caller's plain data (include/sbhip.h: d[9], i[11] in CgScalars' order) uploaded between
+// two runs of guard words, downloaded again field by field behind the launch.  Nothing in between is computed here.
+namespace {
+enum { CG_BLK_GUARD = 64 }; // guard words (8 bytes each) in front of the block and behind it
+struct CgTestBlock {
+  std::vector<unsigned long long> up;
+  char* raw    = nullptr;
+  CgScalars* S = nullptr;
+  CgTestBlock(const double* d, const int* i)
+  {
+    static_assert(sizeof(CgScalars) % 8 == 0, "the guard words follow the block without a gap");
+    CgScalars h = zeroed<CgScalars>();
+    h.rr = d[0], h.rr_old = d[1], h.pAp = d[2], h.alpha = d[3], h.beta = d[4], h.neg_alpha = d[5], h.local = d[6], h.eps = d[7], h.snap_rr = d[8];
+    h.stop = i[0], h.stop_next = i[1], h.iters = i[2], h.n_rr = i[3], h.n_pAp = i[4], h.itermax = i[5], h.hist_cap = i[6];
+    h.x_pending = i[7], h.p2p_error = i[8], h.snap_iters = i[9], h.snap_stop_next = i[10];
+    up.resize(2 * CG_BLK_GUARD + sizeof h / 8);
+    for (size_t k = 0; k < up.size(); k++) up[k] = 0x7FF8C0DE00000000ull | k; // quiet NaNs with a payload
+    memcpy(&up[CG_BLK_GUARD], &h, sizeof h);
+    raw = (char*)sb_malloc(up.size() * 8);
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    HIP_CHECK(hipMemcpy(raw, up.data(), up.size() * 8, hipMemcpyHostToDevice));
+    S = reinterpret_cast<CgScalars*>(raw + 8 * CG_BLK_GUARD);
+  }
+  // waits for the launch; every field back into d / i; returns the number of guard words that changed
+  int done(double* d, int* i)
+  {
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    std::vector<unsigned long long> back(up.size());
+    HIP_CHECK(hipMemcpy(back.data(), raw, back.size() * 8, hipMemcpyDeviceToHost));
+    sb_free(raw);
+    int changed = 0;
+    for (size_t k = 0; k < back.size(); k++)
+      if ((k < CG_BLK_GUARD || k >= back.size() - CG_BLK_GUARD) && back[k] != up[k]) changed++;
+    CgScalars h;
+    memcpy(&h, &back[CG_BLK_GUARD], sizeof h);
+    d[0] = h.rr, d[1] = h.rr_old, d[2] = h.pAp, d[3] = h.alpha, d[4] = h.beta, d[5] = h.neg_alpha, d[6] = h.local, d[7] = h.eps, d[8] = h.snap_rr;
+    i[0] = h.stop, i[1] = h.stop_next, i[2] = h.iters, i[3] = h.n_rr, i[4] = h.n_pAp, i[5] = h.itermax, i[6] = h.hist_cap;
+    i[7] = h.x_pending, i[8] = h.p2p_error, i[9] = h.snap_iters, i[10] = h.snap_stop_next;
+    return changed;
+  }
+};
+void cg_need_fold_block(int mode, const char* fn)
+{
+  if (mode < 0 || mode > 2) SB_FATAL("%s: mode = %d outside 0 .. 2", fn, mode);
+  if (mode && cg_vec_block() != 1024u) SB_FATAL("%s: the folded scalar steps need 1024-thread workgroups (SB_VEC_BLOCK = %u)", fn, cg_vec_block());
+}
+} // namespace
+
+int sb_cg_update_p_native(int mode, uint32_t n, const double* r_dev, double* p_dev, double* x_dev, int which, uint32_t m, const double* l1_dev,
+    double* rr_hist_dev, double* blk_d, int* blk_i)
+{
+  need_init();
+  cg_need_fold_block(mode, "sb_cg_update_p_native");
+  if (mode && which) SB_FATAL("sb_cg_update_p_native: mode %d takes which = 0 only", mode);
+  need_aligned16({ r_dev, p_dev, x_dev }, "sb_cg_update_p_native", "vectors");
+  CgTestBlock b(blk_d, blk_i);
+  launch_cg_update_p(mode, n, r_dev, p_dev, x_dev, b.S, which, m, l1_dev, rr_hist_dev);
+  return b.done(blk_d, blk_i);
+}
+
+int sb_cg_update_r_native(int mode, uint32_t n, const double* Ap_dev, double* r_dev, double* l1out_dev, uint32_t m, const double* l1in_dev,
+    double* rr_hist_dev, double* pAp_hist_dev, double* blk_d, int* blk_i)
+{
+  need_init();
+  cg_need_fold_block(mode, "sb_cg_update_r_native");
+  need_aligned16({ Ap_dev, r_dev }, "sb_cg_update_r_native", "vectors");
+  CgTestBlock b(blk_d, blk_i);
+  launch_cg_update_r(mode, n, Ap_dev, r_dev, b.S, l1out_dev, &b.S->stop, m, l1in_dev, rr_hist_dev, pAp_hist_dev);
+  return b.done(blk_d, blk_i);
+}
+
+int sb_cg_scalar_native(int mode, int reduce, uint32_t m, const double* q_dev, double* rr_hist_dev, double* pAp_hist_dev, int to_local, int defer_x,
+    int l1, double* blk_d, int* blk_i)
+{
+  need_init();
+  if (mode < 0 || mode > 2) SB_FATAL("sb_cg_scalar_native: mode = %d outside 0 .. 2", mode);
+  need_aligned16({ q_dev }, "sb_cg_scalar_native", "partials");
+  CgTestBlock b(blk_d, blk_i);
+  launch_cg_scalar(mode, reduce != 0, m, q_dev, b.S, rr_hist_dev, pAp_hist_dev, to_local, defer_x, l1);
+  return b.done(blk_d, blk_i);
+}
+
+int sb_cg_x_finalize_native(uint32_t n, double* x_dev, const double* p0_dev, const double* p1_dev, double* blk_d, int* blk_i)
+{
+  need_init();
+  CgTestBlock b(blk_d, blk_i);
+  launch_cg_x_finalize(n, x_dev, p0_dev, p1_dev, b.S);
+  return b.done(blk_d, blk_i);
+}
+
+int sb_cg_dot_spans_native(int op, uint32_t n, const double* a_dev, const double* b_dev, double* x_dev, double* r_dev, double* partials_dev,
+    double* blk_d, int* blk_i)
+{
+  need_init();
+  if (op != 1 && op != 2) SB_FATAL("sb_cg_dot_spans_native: op = %d, expected 1 or 2 (op 0 is sb_ddot_partials)", op);
+  CgTestBlock b(blk_d, blk_i);
+  launch_dot_spans(op, n, a_dev, b_dev, x_dev, r_dev, b.S, partials_dev, &b.S->stop);
+  return b.done(blk_d, blk_i);
+}
+
+int sb_waxpby_sdev_native(uint32_t n, const double* x_dev, int negative, const double* y_dev, double* w_dev, double* blk_d, int* blk_i)
+{
+  need_init();
+  need_aligned16({ x_dev, y_dev, w_dev }, "sb_waxpby_sdev_native", "vectors");
+  CgTestBlock b(blk_d, blk_i);
+  launch_waxpby_sdev(n, x_dev, negative ? &b.S->neg_alpha : &b.S->alpha, y_dev, w_dev, &b.S->stop);
+  return b.done(blk_d, blk_i);
 }
