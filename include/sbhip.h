@@ -475,6 +475,45 @@ int sb_waxpby_sdev_native(uint32_t n, const double* x_dev, int negative, const d
 void sb_cg_update_p_launch(uint32_t n, uint32_t out[3]);
 void sb_cg_update_r_launch(uint32_t n, int mode, uint32_t out[3]);
 
+/* ---- the same for the single-precision loop ----
+ * Blocking, one rank, through the launch functions the SP loop itself uses; device pointers of the caller's (vectors 16-byte
+ * aligned), the layer's stream, synchronised before return.  The control block is plain host data,
+ * blk_f[7] = {rr, rr_old, pAp, alpha, neg_alpha, eps, snap_rr}, blk_beta[1] (the double that carries the float quotient) and
+ * blk_i[10] = {stop, stop_next, iters, n_rr, n_pAp, itermax, hist_cap, x_pending, snap_iters, snap_stop_next}: uploaded between
+ * guard words, handed to the kernel, every field copied back; none is computed by the entry.  Each returns the number of guard
+ * words around what it uploaded that changed (0 unless a kernel wrote outside it).
+ * sb_cg_update_p_native_f32: mode 0 p = r + beta p (which != 0: r + 0.0 r) with, x_dev != NULL, which == 0 and x_pending, the
+ * owed x += alpha p on the old p; mode 1 (which == 0): with the beta step and loop test at its head, r.r from the m level-1
+ * values l1_dev, recorded into rr_hist_dev (hist_cap entries); launched at n = 0 too.
+ * sb_cg_update_r_native_f32: mode 0 r += neg_alpha Ap unless the block's stop flag is set; mode 1: with the alpha step at its
+ * head, p.Ap from the m level-1 values l1in_dev, recorded into pAp_hist_dev; the ceil(n/256) level-1 values of r.r to l1out_dev.
+ * sb_cg_scalar_native_f32: the scalar step `mode` (0 prologue, 1 beta / loop test, 2 alpha) on the sum of the m values q_dev
+ * (l1 != 0: level-1 values, else 4 m level-0 partials).  split 0: one launch; split 1: the sum alone (cg_local_f32_k) into
+ * *local, which keeps its value on a set stop flag; split 2: the step alone on the given *local (q_dev, m and l1 unused).
+ * sb_cg_x_finalize_native_f32: x += alpha p where x_pending; p1_dev == NULL: p = p0_dev, else p = p1_dev for an odd n_pAp.
+ * sb_axpy_sdev_native_f32: w = x + alpha y (negative != 0: neg_alpha), scalar and stop flag read from the device's block.
+ * sb_dot_l1_native_f32: the ceil(n/256) level-1 values of a . b; sb_waxpby_stop_native_f32: sb_waxpby_f32; both with a stop flag
+ * of their own on the device that holds `stopped`. */
+int sb_cg_update_p_native_f32(int mode, uint32_t n, const float* r_dev, float* p_dev, float* x_dev, int which, uint32_t m,
+    const float* l1_dev, float* rr_hist_dev, float* blk_f, double* blk_beta, int* blk_i);
+int sb_cg_update_r_native_f32(int mode, uint32_t n, const float* Ap_dev, float* r_dev, float* l1out_dev, uint32_t m,
+    const float* l1in_dev, float* rr_hist_dev, float* pAp_hist_dev, float* blk_f, double* blk_beta, int* blk_i);
+int sb_cg_scalar_native_f32(int mode, int split, uint32_t m, const float* q_dev, float* rr_hist_dev, float* pAp_hist_dev,
+    int defer_x, int l1, float* blk_f, double* blk_beta, int* blk_i, float* local);
+int sb_cg_x_finalize_native_f32(uint32_t n, float* x_dev, const float* p0_dev, const float* p1_dev, float* blk_f,
+    double* blk_beta, int* blk_i);
+int sb_axpy_sdev_native_f32(uint32_t n, const float* x_dev, int negative, const float* y_dev, float* w_dev, float* blk_f,
+    double* blk_beta, int* blk_i);
+int sb_dot_l1_native_f32(uint32_t n, const float* a_dev, const float* b_dev, float* l1out_dev, int stopped);
+int sb_waxpby_stop_native_f32(uint32_t n, float alpha, const float* x_dev, float beta, const float* y_dev, float* w_dev,
+    int stopped);
+/* their launches over n rows: out = {workgroups, threads per workgroup, CUs}; sb_stream_launch_f32: the 256-thread kernels'
+ * (axpy_sdev, waxpby, both x finalizes) */
+void sb_cg_update_p_launch_f32(uint32_t n, uint32_t out[3]);
+void sb_cg_update_r_launch_f32(uint32_t n, uint32_t out[3]);
+void sb_dot_l1_launch_f32(uint32_t n, uint32_t out[3]);
+void sb_stream_launch_f32(uint32_t n, uint32_t out[3]);
+
 /* ---- restarted GMRES(m) (the solver the reference's driver names and leaves empty: src/main.c:31,217-222) ------ */
 /* For matrices that are not symmetric positive definite.  Double precision, ONE rank; a single-precision matrix, several
  * ranks or restart < 1 are fatal errors with file:line.  The numerical contract is DESIGN 4.8: x0 = 0, b / xexact as

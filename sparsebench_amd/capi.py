@@ -43,7 +43,10 @@ SYMBOLS = [
     "sb_unpermute_f32", "sb_waxpby_f32", "sb_ddot_f32", "sb_ddot_partials_f32", "sb_reduce_final_f32", "sb_cg_create_f32",
     "sb_cg_solution_f32", "sb_comm_reduction_f32", "sb_rank_reduce_f32", "sb_halo_exchange_f32",
     "sb_set_sp_mirror", "sb_sp_mirror", "sb_matrix_all_row_programs",
-    "sb_matrix_place", "sb_matrix_place_at", "sb_matrix_place_home", "sb_placement_arena_bytes", "sb_placement_probe", "sb_matrix_place_fresh", "sb_matrix_place_commit", "sb_matrix_placement", "sb_matrix_placement_report", "sb_matrix_debug_ptrs", "sb_cg_debug_ptrs",
+    "sb_cg_update_p_native_f32", "sb_cg_update_r_native_f32", "sb_cg_scalar_native_f32", "sb_cg_x_finalize_native_f32",
+    "sb_axpy_sdev_native_f32", "sb_dot_l1_native_f32", "sb_waxpby_stop_native_f32", "sb_cg_update_p_launch_f32",
+    "sb_cg_update_r_launch_f32", "sb_dot_l1_launch_f32", "sb_stream_launch_f32",
+    "sb_matrix_place","sb_matrix_place_at", "sb_matrix_place_home", "sb_placement_arena_bytes", "sb_placement_probe", "sb_matrix_place_fresh", "sb_matrix_place_commit", "sb_matrix_placement", "sb_matrix_placement_report", "sb_matrix_debug_ptrs", "sb_cg_debug_ptrs",
     "sb_gmres_create", "sb_gmres_free", "sb_gmres_set_fused", "sb_gmres_restart", "sb_gmres_launches_per_step", "sb_gmres_solve",
     "sb_gmres_start", "sb_gmres_run_steps", "sb_gmres_finish", "sb_gmres_history", "sb_gmres_solution", "sb_gmres_check_residual",
     "sb_gmres_loop_ms", "sb_gmres_counters", "sb_multidot", "sb_multiaxpy_sub", "sb_debug_sqrt_div",
@@ -250,6 +253,17 @@ def load():
         "sb_set_sp_mirror": (None, [C.c_int]),
         "sb_sp_mirror": (C.c_int, []),
         "sb_matrix_all_row_programs": (C.c_int, [vp]),
+        "sb_cg_update_p_native_f32": (C.c_int, [C.c_int, u32, vp, vp, vp, C.c_int, u32, vp, vp, vp, vp, vp]),
+        "sb_cg_update_r_native_f32": (C.c_int, [C.c_int, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]),
+        "sb_cg_scalar_native_f32": (C.c_int, [C.c_int, C.c_int, u32, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+        "sb_cg_x_finalize_native_f32": (C.c_int, [u32, vp, vp, vp, vp, vp, vp]),
+        "sb_axpy_sdev_native_f32": (C.c_int, [u32, vp, C.c_int, vp, vp, vp, vp, vp]),
+        "sb_dot_l1_native_f32": (C.c_int, [u32, vp, vp, vp, C.c_int]),
+        "sb_waxpby_stop_native_f32": (C.c_int, [u32, C.c_float, vp, C.c_float, vp, vp, C.c_int]),
+        "sb_cg_update_p_launch_f32": (None, [u32, vp]),
+        "sb_cg_update_r_launch_f32": (None, [u32, vp]),
+        "sb_dot_l1_launch_f32": (None, [u32, vp]),
+        "sb_stream_launch_f32": (None, [u32, vp]),
         # restarted GMRES(m)
         "sb_gmres_create": (vp, [vp, vp, vp, vp, C.c_int]),
         "sb_gmres_free": (None, [vp]),

@@ -315,12 +315,18 @@ int sb_spmv_native_dot_f32(const sb_matrix* m, const float* x, float* y, float* 
   return 2;
 }
 
+// w = alpha x + beta y, waxpby's three branches (256-thread workgroups, stream_grid); stop != NULL: nothing on a set flag
+static void launch_sp_waxpby(uint32_t n, float alpha, const float* x, float beta, const float* y, float* w, const int* stop)
+{
+  if (n == 0) return;
+  hipLaunchKernelGGL(waxpby_f32_k, dim3(stream_grid(n, 256)), dim3(256), 0, g.stream, n, alpha, x, beta, y, w, stop);
+  HIP_CHECK(hipGetLastError());
+}
+
 void sb_waxpby_f32(uint32_t n, float alpha, const float* x, float beta, const float* y, float* w)
 {
   need_init();
-  if (n == 0) return;
-  hipLaunchKernelGGL(waxpby_f32_k, dim3(stream_grid(n, 256)), dim3(256), 0, g.stream, n, alpha, x, beta, y, w, (const int*)nullptr);
-  HIP_CHECK(hipGetLastError());
+  launch_sp_waxpby(n, alpha, x, beta, y, w, nullptr);
 }
 
 static void launch_dot_l0_f32(uint32_t n, const float* a, const float* b, float* partials, const int* stop)
@@ -462,6 +468,90 @@ static int sp_launches_per_body(const sb_cg* s)
   return n;
 }
 
+// ---- the launches of the loop's vector and scalar kernels, on plain pointers: the loop below and the blocking test entries at
+// the end of this file both go through them, so a test of an entry is a test of the loop's launch ----------------
+// cg_update_p_f32 / cg_update_p_push_f32: four floats per thread, 1024 threads, at most two workgroups per CU
+static uint32_t sp_update_p_grid(uint32_t n)
+{
+  const uint32_t vb = 1024u, capV = (uint32_t)g.prop.multiProcessorCount * 2u;
+  return std::max(1u, std::min(capV, (n / 4 + vb) / vb));
+}
+// a wave per aligned 256 rows, 16 waves per workgroup, at most wgPerCu workgroups per CU (cg_update_r_f32: 1, dot_l1_f32_k: 2)
+static uint32_t sp_groups_grid(uint32_t n, uint32_t wgPerCu)
+{
+  const uint32_t nG = (n + 255u) >> 8;
+  return std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount * wgPerCu, (nG + 15u) / 16u));
+}
+// cg_update_p_f32<mode>: mode 0 p = r + beta p (which != 0: r + 0.0 r) with the owed x update; mode 1 with the beta step at its
+// head, from the m level-1 values l1 -- launched at n = 0 too: the step is the loop's
+static void launch_sp_update_p(int mode, uint32_t n, const float* r, float* p, float* x, CgScalarsF* S, int which, uint32_t m,
+    const float* l1, float* rr_hist)
+{
+  const dim3 grid(sp_update_p_grid(n)), block(1024);
+  if (mode == 1) hipLaunchKernelGGL(cg_update_p_f32<1>, grid, block, 0, g.stream, n, r, p, x, S, which, m, l1, rr_hist);
+  else if (n) hipLaunchKernelGGL(cg_update_p_f32<0>, grid, block, 0, g.stream, n, r, p, x, S, which, 0u, (const float*)nullptr, (float*)nullptr);
+  HIP_CHECK(hipGetLastError());
+}
+// cg_update_r_f32<mode>: mode 0 r += neg_alpha Ap unless *stop; mode 1 with the alpha step at its head, from the m level-1 values
+// l1in; the level-1 values of r.r into l1out
+static void launch_sp_update_r(int mode, uint32_t n, const float* Ap, float* r, CgScalarsF* S, float* l1out, const int* stop, uint32_t m,
+    const float* l1in, float* rr_hist, float* pAp_hist)
+{
+  const dim3 grid(sp_groups_grid(n, 1)), block(1024);
+  if (mode == 1) hipLaunchKernelGGL(cg_update_r_f32<1>, grid, block, 0, g.stream, n, Ap, r, S, l1out, stop, m, l1in, rr_hist, pAp_hist);
+  else
+    hipLaunchKernelGGL(cg_update_r_f32<0>, grid, block, 0, g.stream, n, Ap, r, S, l1out, stop, 0u, (const float*)nullptr, (float*)nullptr,
+        (float*)nullptr);
+  HIP_CHECK(hipGetLastError());
+}
+// the level-1 values of a . b, one per aligned 256 elements
+static void launch_sp_dot_l1(uint32_t n, const float* a, const float* b, float* l1out, const int* stop)
+{
+  if (n == 0) return;
+  hipLaunchKernelGGL(dot_l1_f32_k, dim3(sp_groups_grid(n, 2)), dim3(1024), 0, g.stream, n, a, b, l1out, stop);
+  HIP_CHECK(hipGetLastError());
+}
+// w = x + (*a_dev) y of the reference-shaped op list
+static void launch_sp_axpy_sdev(uint32_t n, const float* x, const float* a_dev, const float* y, float* w, const int* stop)
+{
+  if (n == 0) return;
+  hipLaunchKernelGGL(axpy_sdev_f32_k, dim3(stream_grid(n, 256)), dim3(256), 0, g.stream, n, x, a_dev, y, w, stop);
+  HIP_CHECK(hipGetLastError());
+}
+// the x update the last body left owing; p1 != NULL: p double-buffered, p0 / p1 the buffers of the even / odd bodies
+static void launch_sp_x_finalize(uint32_t n, float* x, const float* p0, const float* p1, const CgScalarsF* S)
+{
+  if (n == 0) return;
+  if (p1) hipLaunchKernelGGL(cg_x_finalize2_f32, dim3(stream_grid(n, 256)), dim3(256), 0, g.stream, n, x, p0, p1, S);
+  else hipLaunchKernelGGL(cg_x_finalize_f32, dim3(stream_grid(n, 256)), dim3(256), 0, g.stream, n, x, p0, S);
+  HIP_CHECK(hipGetLastError());
+}
+// the scalar step `mode` on one rank: levels 1-2 of the dot in q + the step, one workgroup
+static void launch_sp_scalar(int mode, uint32_t m, const float* q, CgScalarsF* S, float* rr_hist, float* pAp_hist, int defer_x, int l1)
+{
+  const dim3 grid(1), block(1024);
+  if (mode == 0) hipLaunchKernelGGL((cg_scalar_f32_k<0>), grid, block, 0, g.stream, m, q, S, rr_hist, pAp_hist, defer_x, l1);
+  else if (mode == 1) hipLaunchKernelGGL((cg_scalar_f32_k<1>), grid, block, 0, g.stream, m, q, S, rr_hist, pAp_hist, defer_x, l1);
+  else if (mode == 2) hipLaunchKernelGGL((cg_scalar_f32_k<2>), grid, block, 0, g.stream, m, q, S, rr_hist, pAp_hist, defer_x, l1);
+  else SB_FATAL("launch_sp_scalar: unknown mode %d", mode);
+  HIP_CHECK(hipGetLastError());
+}
+// ... and split for the communicator's plane: levels 1-2 into X->local | (the all-reduce) | the step on X->local
+static void launch_sp_local(uint32_t m, const float* q, const CgScalarsF* S, CgCommF* X, int l1)
+{
+  hipLaunchKernelGGL(cg_local_f32_k, dim3(1), dim3(1024), 0, g.stream, m, q, S, X, l1);
+  HIP_CHECK(hipGetLastError());
+}
+static void launch_sp_apply_local(int mode, CgScalarsF* S, const CgCommF* X, float* rr_hist, float* pAp_hist, int defer_x)
+{
+  const dim3 grid(1), block(64);
+  if (mode == 0) hipLaunchKernelGGL((cg_apply_local_f32_k<0>), grid, block, 0, g.stream, S, X, rr_hist, pAp_hist, defer_x);
+  else if (mode == 1) hipLaunchKernelGGL((cg_apply_local_f32_k<1>), grid, block, 0, g.stream, S, X, rr_hist, pAp_hist, defer_x);
+  else if (mode == 2) hipLaunchKernelGGL((cg_apply_local_f32_k<2>), grid, block, 0, g.stream, S, X, rr_hist, pAp_hist, defer_x);
+  else SB_FATAL("launch_sp_apply_local: unknown mode %d", mode);
+  HIP_CHECK(hipGetLastError());
+}
+
 // one dot of the reference's op list into partialsF: tree level-0 partials, or (seq) the sequential sum in original row order
 static void sp_dot(sb_cg* s, const float* a, const float* b, const int* stop)
 {
@@ -475,8 +565,7 @@ template <int MODE> static void sp_scalar(sb_cg* s, const float* q, int l1, int 
   uint32_t m = s->nPartials;
   if (s->seqLatched > 0) m = 1, l1 = 1;
   if (!multi_rank()) {
-    hipLaunchKernelGGL((cg_scalar_f32_k<MODE>), dim3(1), dim3(1024), 0, g.stream, m, q, s->SF, s->rrHistF, s->pApHistF, defer_x, l1);
-    HIP_CHECK(hipGetLastError());
+    launch_sp_scalar(MODE, m, q, s->SF, s->rrHistF, s->pApHistF, defer_x, l1);
     return;
   }
   if (p2p_dots()) {
@@ -485,14 +574,11 @@ template <int MODE> static void sp_scalar(sb_cg* s, const float* q, int l1, int 
     HIP_CHECK(hipGetLastError());
     return;
   }
-  hipLaunchKernelGGL(cg_local_f32_k, dim3(1), dim3(1024), 0, g.stream, m, q, (const CgScalarsF*)s->SF, s->XF, l1);
-  HIP_CHECK(hipGetLastError());
+  launch_sp_local(m, q, s->SF, s->XF, l1);
   mark(s, R_DDOT);
   sb_comm_reduction_f32(&s->XF->local, 1);
   mark(s, R_COMM);
-  hipLaunchKernelGGL((cg_apply_local_f32_k<MODE>), dim3(1), dim3(64), 0, g.stream, s->SF, (const CgCommF*)s->XF, s->rrHistF,
-      s->pApHistF, defer_x);
-  HIP_CHECK(hipGetLastError());
+  launch_sp_apply_local(MODE, s->SF, s->XF, s->rrHistF, s->pApHistF, defer_x);
 }
 static void sp_flush_beta(sb_cg* s)
 {
@@ -505,16 +591,12 @@ static void sp_flush_beta(sb_cg* s)
 
 // several ranks: the all-reduced alpha step | r update (+ the level-1 values of r.r) | the all-reduced beta step / loop test
 // (x += alpha p stays owed)
-static void sp_alpha_r_beta(sb_cg* s, dim3 gridR)
+static void sp_alpha_r_beta(sb_cg* s)
 {
-  const uint32_t n = s->nr;
-  const int* stop  = &s->SF->stop;
   sp_scalar<2>(s, s->partialsF, 1, 0);
   mark(s, R_DDOT);
   phase_mark(s, PH_ALPHA);
-  hipLaunchKernelGGL(cg_update_r_f32<0>, gridR, dim3(1024), 0, g.stream, n, (const float*)s->Apf, s->rf, s->SF, s->partials2F,
-      stop, 0u, (const float*)nullptr, (float*)nullptr, (float*)nullptr);
-  HIP_CHECK(hipGetLastError());
+  launch_sp_update_r(0, s->nr, s->Apf, s->rf, s->SF, s->partials2F, &s->SF->stop, 0u, nullptr, nullptr, nullptr);
   mark(s, R_WAXPBY);
   phase_mark(s, PH_R_UPDATE);
   sp_scalar<1>(s, s->partials2F, 1, 1);
@@ -526,9 +608,6 @@ static void sp_loop_body(sb_cg* s, int k)
 {
   const uint32_t n = s->nr;
   const int* stop  = &s->SF->stop;
-  const uint32_t vb = 1024u, capV = (uint32_t)g.prop.multiProcessorCount * 2u;
-  const dim3 gridV(std::max(1u, std::min(capV, (n / 4 + vb) / vb))), blockV(vb);
-  const dim3 gridW(stream_grid(n, 256)), blockW(256);
   if (sp_fusep_plan(s)) {
     // p = r + beta p (:114; k = 1: p = r + 0.0 r, :109), the owed x update (:127) and Ap = A p with the p.Ap level-1 values
     // (:123-125) in ONE launch: body k reads p_{k-1} in buffer (k - 1) & 1 and writes p_k into buffer k & 1
@@ -540,11 +619,7 @@ static void sp_loop_body(sb_cg* s, int k)
     spmv_time_end(s);
     mark(s, R_SPMVM);
     phase_mark(s, PH_SPMV);
-    const uint32_t nG = (n + 255u) >> 8;
-    const dim3 gridR(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount, (nG + 15u) / 16u)));
-    hipLaunchKernelGGL(cg_update_r_f32<1>, gridR, dim3(1024), 0, g.stream, n, (const float*)s->Apf, s->rf, s->SF, s->partials2F,
-        stop, s->nPartials, (const float*)s->partialsF, s->rrHistF, s->pApHistF);
-    HIP_CHECK(hipGetLastError());
+    launch_sp_update_r(1, n, s->Apf, s->rf, s->SF, s->partials2F, stop, s->nPartials, s->partialsF, s->rrHistF, s->pApHistF);
     mark(s, R_WAXPBY);
     phase_mark(s, PH_R_UPDATE);
     sp_scalar<1>(s, s->partials2F, 1, 1); // the beta step / loop test: a launch of its own (the next SpMV's tiles all need beta)
@@ -557,6 +632,8 @@ static void sp_loop_body(sb_cg* s, int k)
     // wait and read the staging area (+ p.Ap level 1) | alpha | r update (+ r.r level 1) | beta -- 5 launches
     sb_halo* h         = s->halo;
     const int which    = k == 1;
+    const uint32_t vb  = 1024u;
+    const dim3 gridV(sp_update_p_grid(n)), blockV(vb); // (cg_update_p_f32's grid: the plan's owner map follows it)
     const HaloFold& hf = halo_fold_send_plan(h, 1, gridV.x, vb);
     const unsigned long long seq = ++h->seq;
     hipLaunchKernelGGL(cg_update_p_push_f32, gridV, blockV, 0, g.stream, h->push, hf, seq, n, (const float*)s->rf, s->pf,
@@ -574,32 +651,22 @@ static void sp_loop_body(sb_cg* s, int k)
     spmv_time_end(s);
     mark(s, R_SPMVM);
     phase_mark(s, PH_SPMV);
-    const uint32_t nG = (n + 255u) >> 8;
-    const dim3 gridR(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount, (nG + 15u) / 16u)));
-    sp_alpha_r_beta(s, gridR);
+    sp_alpha_r_beta(s);
     return;
   }
   if (k == 1) { // p = r + 0.0 r (:109)
-    if (n) hipLaunchKernelGGL(cg_update_p_f32<0>, gridV, blockV, 0, g.stream, n, s->rf, s->pf, (float*)nullptr, s->SF, 1, 0u,
-        (const float*)nullptr, (float*)nullptr);
+    launch_sp_update_p(0, n, s->rf, s->pf, nullptr, s->SF, 1, 0u, nullptr, nullptr);
   } else if (s->fused) { // beta step at the head, p = r + beta p, the owed x += alpha p (:111-116, :127)
-    if (s->betaFold) {
-      hipLaunchKernelGGL(cg_update_p_f32<1>, gridV, blockV, 0, g.stream, n, s->rf, s->pf, s->xf, s->SF, 0, s->nPartials,
-          (const float*)s->partials2F, s->rrHistF);
-      s->betaFold = 0;
-    } else if (n)
-      hipLaunchKernelGGL(cg_update_p_f32<0>, gridV, blockV, 0, g.stream, n, s->rf, s->pf, s->xf, s->SF, 0, 0u, (const float*)nullptr,
-          (float*)nullptr);
+    launch_sp_update_p(s->betaFold ? 1 : 0, n, s->rf, s->pf, s->xf, s->SF, 0, s->nPartials, s->partials2F, s->rrHistF);
+    s->betaFold = 0;
   } else { // rtrans = r.r ; beta ; p = r + beta p (:111-114)
     sp_dot(s, s->rf, s->rf, stop);
     phase_mark(s, PH_DOT_PASS);
     sp_scalar<1>(s, s->partialsF, 0, 0);
     mark(s, R_DDOT);
     phase_mark(s, PH_BETA);
-    if (n) hipLaunchKernelGGL(cg_update_p_f32<0>, gridV, blockV, 0, g.stream, n, s->rf, s->pf, (float*)nullptr, s->SF, 0, 0u,
-        (const float*)nullptr, (float*)nullptr);
+    launch_sp_update_p(0, n, s->rf, s->pf, nullptr, s->SF, 0, 0u, nullptr, nullptr);
   }
-  HIP_CHECK(hipGetLastError());
   mark(s, R_WAXPBY);
   phase_mark(s, PH_P_UPDATE);
   if (multi_rank() && s->halo) { // commExchange(&comm, p) (:122)
@@ -616,22 +683,15 @@ static void sp_loop_body(sb_cg* s, int k)
   phase_mark(s, PH_SPMV);
   if (s->fused) {
     if (!fusedDot && n) {
-      const uint32_t nG = (n + 255u) >> 8;
-      hipLaunchKernelGGL(dot_l1_f32_k, dim3(std::max(1u, std::min(capV, (nG + 15u) / 16u))), dim3(1024), 0, g.stream, n,
-          (const float*)s->pf, (const float*)s->Apf, s->partialsF, stop);
-      HIP_CHECK(hipGetLastError());
+      launch_sp_dot_l1(n, s->pf, s->Apf, s->partialsF, stop);
       phase_mark(s, PH_DOT_PASS);
     }
     // alpha (:126) inside the r update: r = r - alpha Ap (:128) + the level-1 values of the next r.r; x += alpha p is owed
-    const uint32_t nG = (n + 255u) >> 8;
-    const dim3 gridR(std::max(1u, std::min((uint32_t)g.prop.multiProcessorCount, (nG + 15u) / 16u)));
     if (multi_rank()) { // the all-reduced alpha step, r update, the all-reduced beta step / loop test (x += alpha p stays owed)
-      sp_alpha_r_beta(s, gridR);
+      sp_alpha_r_beta(s);
       return;
     }
-    hipLaunchKernelGGL(cg_update_r_f32<1>, gridR, dim3(1024), 0, g.stream, n, (const float*)s->Apf, s->rf, s->SF, s->partials2F,
-        stop, s->nPartials, (const float*)s->partialsF, s->rrHistF, s->pApHistF);
-    HIP_CHECK(hipGetLastError());
+    launch_sp_update_r(1, n, s->Apf, s->rf, s->SF, s->partials2F, stop, s->nPartials, s->partialsF, s->rrHistF, s->pApHistF);
     mark(s, R_WAXPBY);
     phase_mark(s, PH_R_UPDATE);
     s->betaFold = 1; // the beta step / loop test rides at the head of the next p update (sp_flush_beta where none follows)
@@ -643,11 +703,8 @@ static void sp_loop_body(sb_cg* s, int k)
   mark(s, R_DDOT);
   phase_mark(s, PH_ALPHA);
   if (n) { // x = x + alpha p ; r = r + (-alpha) Ap (:127-128)
-    hipLaunchKernelGGL(axpy_sdev_f32_k, gridW, blockW, 0, g.stream, n, (const float*)s->xf, (const float*)&s->SF->alpha,
-        (const float*)s->pf, s->xf, stop);
-    hipLaunchKernelGGL(axpy_sdev_f32_k, gridW, blockW, 0, g.stream, n, (const float*)s->rf, (const float*)&s->SF->neg_alpha,
-        (const float*)s->Apf, s->rf, stop);
-    HIP_CHECK(hipGetLastError());
+    launch_sp_axpy_sdev(n, s->xf, &s->SF->alpha, s->pf, s->xf, stop);
+    launch_sp_axpy_sdev(n, s->rf, &s->SF->neg_alpha, s->Apf, s->rf, stop);
     mark(s, R_WAXPBY);
     phase_mark(s, PH_R_UPDATE);
   }
@@ -684,17 +741,13 @@ static void sp_cg_start(sb_cg* s, int itermax, double eps)
   if (s->pf2) HIP_CHECK(hipMemsetAsync(s->pf2, 0, (size_t)s->nc * sizeof(float), g.stream));
   mark(s, -1);
   // prologue, src/CGSolver.c:94-100: p = x + 0.0 x ; Ap = A p ; r = b + (-1.0) Ap ; rtrans = r.r
-  const dim3 gridW(stream_grid(n, 256)), blockW(256);
-  if (n) hipLaunchKernelGGL(waxpby_f32_k, gridW, blockW, 0, g.stream, n, 1.0f, (const float*)s->xf, 0.0f, (const float*)s->xf, s->pf,
-      (const int*)nullptr);
+  launch_sp_waxpby(n, 1.0f, s->xf, 0.0f, s->xf, s->pf, nullptr);
   mark(s, R_WAXPBY);
   halo_exchange_f32(s->halo, s->pf, nullptr, false); // (:96)
   mark(s, R_COMM);
   launch_spmv_f32(s->A, s->pf, s->Apf, nullptr, nullptr);
   mark(s, R_SPMVM);
-  if (n) hipLaunchKernelGGL(waxpby_f32_k, gridW, blockW, 0, g.stream, n, 1.0f, (const float*)s->bf, -1.0f, (const float*)s->Apf,
-      s->rf, (const int*)nullptr);
-  HIP_CHECK(hipGetLastError());
+  launch_sp_waxpby(n, 1.0f, s->bf, -1.0f, s->Apf, s->rf, nullptr);
   mark(s, R_WAXPBY);
   sp_dot(s, s->rf, s->rf, nullptr);
   sp_scalar<0>(s, s->partialsF, 0, 0);
@@ -713,13 +766,7 @@ static int sp_cg_finish(sb_cg* s)
 {
   if (s->nr) {
     // (fused p update: body k left p_k in buffer k & 1; which body ran last is on the device -- n_pAp -- not on the host)
-    if (sp_fusep_plan(s))
-      hipLaunchKernelGGL(cg_x_finalize2_f32, dim3(stream_grid(s->nr, 256)), dim3(256), 0, g.stream, s->nr, s->xf, (const float*)s->pf,
-          (const float*)s->pf2, (const CgScalarsF*)s->SF);
-    else
-      hipLaunchKernelGGL(cg_x_finalize_f32, dim3(stream_grid(s->nr, 256)), dim3(256), 0, g.stream, s->nr, s->xf, (const float*)s->pf,
-          (const CgScalarsF*)s->SF);
-    HIP_CHECK(hipGetLastError());
+    launch_sp_x_finalize(s->nr, s->xf, s->pf, sp_fusep_plan(s) ? s->pf2 : nullptr, s->SF);
     HIP_CHECK(hipMemsetAsync(&s->SF->x_pending, 0, sizeof(int), g.stream));
   }
   HIP_CHECK(hipStreamSynchronize(g.stream));
@@ -784,4 +831,187 @@ static double sp_cg_check_residual(const sb_cg* s)
     sb_d2h(&m, d, sizeof m);
   }
   return (double)m;
+}
+
+// --- blocking test entries: the SP loop's vector and scalar kernels alone, launched by the loop's own launch functions (DESIGN
+// 4.4.1; the fp64 twins are at the end of sbhip_cg.inc.h) ----------------------------------------------------------------------
+void sb_cg_update_p_launch_f32(uint32_t n, uint32_t out[3])
+{
+  need_init();
+  out[0] = sp_update_p_grid(n), out[1] = 1024u, out[2] = (uint32_t)g.prop.multiProcessorCount;
+}
+void sb_cg_update_r_launch_f32(uint32_t n, uint32_t out[3])
+{
+  need_init();
+  out[0] = sp_groups_grid(n, 1), out[1] = 1024u, out[2] = (uint32_t)g.prop.multiProcessorCount;
+}
+void sb_dot_l1_launch_f32(uint32_t n, uint32_t out[3])
+{
+  need_init();
+  out[0] = sp_groups_grid(n, 2), out[1] = 1024u, out[2] = (uint32_t)g.prop.multiProcessorCount;
+}
+void sb_stream_launch_f32(uint32_t n, uint32_t out[3])
+{
+  need_init();
+  out[0] = stream_grid(n, 256), out[1] = 256u, out[2] = (uint32_t)g.prop.multiProcessorCount;
+}
+
+namespace {
+enum { SP_BLK_GUARD = 64 }; // guard words (8 bytes each) in front of a payload and behind it
+// `bytes` of plain host data (a multiple of 8) on the device between two runs of guard words
+struct SpGuarded {
+  std::vector<unsigned long long> up;
+  char* raw = nullptr;
+  size_t words;
+  SpGuarded(const void* payload, size_t bytes) : words(bytes / 8)
+  {
+    up.resize(2 * SP_BLK_GUARD + words);
+    for (size_t k = 0; k < up.size(); k++) up[k] = 0x7FF8C0DE00000000ull | k; // quiet NaNs with a payload, as doubles and as floats
+    memcpy(&up[SP_BLK_GUARD], payload, bytes);
+    raw = (char*)sb_malloc(up.size() * 8);
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    HIP_CHECK(hipMemcpy(raw, up.data(), up.size() * 8, hipMemcpyHostToDevice));
+  }
+  void* ptr() const { return raw + 8 * SP_BLK_GUARD; }
+  // waits for the launch; the payload back into `out`; returns the number of guard words that changed
+  int done(void* out)
+  {
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    std::vector<unsigned long long> back(up.size());
+    HIP_CHECK(hipMemcpy(back.data(), raw, back.size() * 8, hipMemcpyDeviceToHost));
+    sb_free(raw);
+    int changed = 0;
+    for (size_t k = 0; k < back.size(); k++)
+      if ((k < SP_BLK_GUARD || k >= back.size() - SP_BLK_GUARD) && back[k] != up[k]) changed++;
+    memcpy(out, &back[SP_BLK_GUARD], words * 8);
+    return changed;
+  }
+};
+// The control block of a test entry: the caller's plain data (include/sbhip.h: blk_f[7], blk_beta[1], blk_i[10]) as a
+// CgScalarsF between guard words, every field copied back behind the launch.  Nothing in between is computed here.
+struct SpTestBlock {
+  static CgScalarsF pack(const float* f, const double* beta, const int* i)
+  {
+    static_assert(sizeof(CgScalarsF) % 8 == 0, "the guard words follow the block without a gap");
+    CgScalarsF h = zeroed<CgScalarsF>();
+    h.rr = f[0], h.rr_old = f[1], h.pAp = f[2], h.alpha = f[3], h.neg_alpha = f[4], h.eps = f[5], h.snap_rr = f[6];
+    memcpy(&h.beta, beta, sizeof h.beta); // (bits, not values: a NaN keeps its payload)
+    h.stop = i[0], h.stop_next = i[1], h.iters = i[2], h.n_rr = i[3], h.n_pAp = i[4], h.itermax = i[5], h.hist_cap = i[6];
+    h.x_pending = i[7], h.snap_iters = i[8], h.snap_stop_next = i[9];
+    return h;
+  }
+  CgScalarsF h;
+  SpGuarded dev;
+  CgScalarsF* S;
+  SpTestBlock(const float* f, const double* beta, const int* i) : h(pack(f, beta, i)), dev(&h, sizeof h), S((CgScalarsF*)dev.ptr()) {}
+  int done(float* f, double* beta, int* i)
+  {
+    const int changed = dev.done(&h);
+    f[0] = h.rr, f[1] = h.rr_old, f[2] = h.pAp, f[3] = h.alpha, f[4] = h.neg_alpha, f[5] = h.eps, f[6] = h.snap_rr;
+    memcpy(beta, &h.beta, sizeof h.beta);
+    i[0] = h.stop, i[1] = h.stop_next, i[2] = h.iters, i[3] = h.n_rr, i[4] = h.n_pAp, i[5] = h.itermax, i[6] = h.hist_cap;
+    i[7] = h.x_pending, i[8] = h.snap_iters, i[9] = h.snap_stop_next;
+    return changed;
+  }
+};
+// a stop flag of its own on the device, between guard words
+struct SpTestFlag {
+  int h[2];
+  SpGuarded dev;
+  SpTestFlag(int stopped) : h{ stopped, 0 }, dev(h, sizeof h) {}
+  const int* flag() const { return (const int*)dev.ptr(); }
+  int done()
+  {
+    const int was = h[0];
+    const int changed = dev.done(h);
+    return changed + (h[0] != was || h[1] != 0 ? 1 : 0); // (the kernels only read it)
+  }
+};
+void sp_need_mode(int mode, int top, const char* fn)
+{
+  if (mode < 0 || mode > top) SB_FATAL("%s: mode = %d outside 0 .. %d", fn, mode, top);
+}
+} // namespace
+
+int sb_cg_update_p_native_f32(int mode, uint32_t n, const float* r_dev, float* p_dev, float* x_dev, int which, uint32_t m,
+    const float* l1_dev, float* rr_hist_dev, float* blk_f, double* blk_beta, int* blk_i)
+{
+  need_init();
+  sp_need_mode(mode, 1, "sb_cg_update_p_native_f32");
+  if (mode && which) SB_FATAL("sb_cg_update_p_native_f32: mode 1 takes which = 0 only");
+  need_aligned16({ r_dev, p_dev, x_dev }, "sb_cg_update_p_native_f32", "vectors");
+  SpTestBlock b(blk_f, blk_beta, blk_i);
+  launch_sp_update_p(mode, n, r_dev, p_dev, x_dev, b.S, which, m, l1_dev, rr_hist_dev);
+  return b.done(blk_f, blk_beta, blk_i);
+}
+
+int sb_cg_update_r_native_f32(int mode, uint32_t n, const float* Ap_dev, float* r_dev, float* l1out_dev, uint32_t m,
+    const float* l1in_dev, float* rr_hist_dev, float* pAp_hist_dev, float* blk_f, double* blk_beta, int* blk_i)
+{
+  need_init();
+  sp_need_mode(mode, 1, "sb_cg_update_r_native_f32");
+  need_aligned16({ Ap_dev, r_dev }, "sb_cg_update_r_native_f32", "vectors");
+  SpTestBlock b(blk_f, blk_beta, blk_i);
+  launch_sp_update_r(mode, n, Ap_dev, r_dev, b.S, l1out_dev, &b.S->stop, m, l1in_dev, rr_hist_dev, pAp_hist_dev);
+  return b.done(blk_f, blk_beta, blk_i);
+}
+
+int sb_cg_scalar_native_f32(int mode, int split, uint32_t m, const float* q_dev, float* rr_hist_dev, float* pAp_hist_dev, int defer_x,
+    int l1, float* blk_f, double* blk_beta, int* blk_i, float* local)
+{
+  need_init();
+  sp_need_mode(mode, 2, "sb_cg_scalar_native_f32");
+  if (split < 0 || split > 2) SB_FATAL("sb_cg_scalar_native_f32: split = %d outside 0 .. 2", split);
+  SpTestBlock b(blk_f, blk_beta, blk_i);
+  if (split == 0) {
+    launch_sp_scalar(mode, m, q_dev, b.S, rr_hist_dev, pAp_hist_dev, defer_x, l1);
+    return b.done(blk_f, blk_beta, blk_i);
+  }
+  CgCommF x = zeroed<CgCommF>();
+  x.local   = *local;
+  static_assert(sizeof(CgCommF) == 8, "one guarded word");
+  SpGuarded X(&x, sizeof x);
+  if (split == 1) launch_sp_local(m, q_dev, b.S, (CgCommF*)X.ptr(), l1);
+  else launch_sp_apply_local(mode, b.S, (const CgCommF*)X.ptr(), rr_hist_dev, pAp_hist_dev, defer_x);
+  int changed = b.done(blk_f, blk_beta, blk_i);
+  changed += X.done(&x);
+  if (x.p2p_error != 0) changed++; // (neither kernel writes it)
+  *local = x.local;
+  return changed;
+}
+
+int sb_cg_x_finalize_native_f32(uint32_t n, float* x_dev, const float* p0_dev, const float* p1_dev, float* blk_f, double* blk_beta,
+    int* blk_i)
+{
+  need_init();
+  SpTestBlock b(blk_f, blk_beta, blk_i);
+  launch_sp_x_finalize(n, x_dev, p0_dev, p1_dev, b.S);
+  return b.done(blk_f, blk_beta, blk_i);
+}
+
+int sb_axpy_sdev_native_f32(uint32_t n, const float* x_dev, int negative, const float* y_dev, float* w_dev, float* blk_f,
+    double* blk_beta, int* blk_i)
+{
+  need_init();
+  SpTestBlock b(blk_f, blk_beta, blk_i);
+  launch_sp_axpy_sdev(n, x_dev, negative ? &b.S->neg_alpha : &b.S->alpha, y_dev, w_dev, &b.S->stop);
+  return b.done(blk_f, blk_beta, blk_i);
+}
+
+int sb_dot_l1_native_f32(uint32_t n, const float* a_dev, const float* b_dev, float* l1out_dev, int stopped)
+{
+  need_init();
+  need_aligned16({ a_dev, b_dev }, "sb_dot_l1_native_f32", "vectors");
+  SpTestFlag f(stopped);
+  launch_sp_dot_l1(n, a_dev, b_dev, l1out_dev, f.flag());
+  return f.done();
+}
+
+int sb_waxpby_stop_native_f32(uint32_t n, float alpha, const float* x_dev, float beta, const float* y_dev, float* w_dev, int stopped)
+{
+  need_init();
+  SpTestFlag f(stopped);
+  launch_sp_waxpby(n, alpha, x_dev, beta, y_dev, w_dev, f.flag());
+  return f.done();
 }
