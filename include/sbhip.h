@@ -555,6 +555,45 @@ void sb_multidot(uint32_t n, int nvec, const double* V, size_t ldv, const double
 void sb_multiaxpy_sub(uint32_t n, int nvec, const double* V, size_t ldv, const double* h_dev, double* w);
 /* their launch over n rows: out = {workgroups, threads per workgroup, CUs} */
 void sb_gmres_group_launch(uint32_t n, uint32_t out[3]);
+/* the launch of the scale kernels (256 threads a workgroup, a row per thread and trip) and of the step-and-normalise kernels
+ * (min(CUs, ceil(n / 4096)) workgroups of 1 024 threads) over n rows: out = {workgroups, threads per workgroup, CUs} */
+void sb_gmres_scale_launch(uint32_t n, uint32_t out[3]);
+void sb_gmres_step_launch(uint32_t n, uint32_t out[3]);
+/* Test entries (blocking): every kernel of the GMRES loop alone on the caller's buffers, launched by the loop's own launch
+ * functions.  Each returns the number of guard words around its control block that the launch changed (0).
+ * Entries whose kernel reads a stop flag and nothing else of the block take `stopped`: the flag's value.  Entries whose kernel
+ * reads or writes the block take it as plain data,
+ *   blk_d[4] = {normr, eps, hn, rr}
+ *   blk_i[9] = {stop, k, j, itermax, n_res, n_rr, hist_cap, cycles, steps}
+ * in and out; use_stop: the launch is handed the block's own stop flag (1) or none (0).  dense_host, in and out: the dense
+ * state of a cycle of restart length m as the handle lays it out, m (m + 1) + 3 m + 6 (m + 1) doubles: H (column j at
+ * j (m + 1)), cs, sn, y (m each), g, h1, h2, nh1, nh2, hcol (m + 1 each).  V, ldv, mode, c1, dinv, d, z as in
+ * sb_multidot and the sb_gmres_pre_*_native entries.
+ * multidot: l1_dev[i nGroups + group] = level-1 value of dot(V[i], w), nGroups = (n + 255) / 256.
+ * finish_dots: workgroup i of nvec finishes dot i from q_dev + i qStride (l1 != 0: nGroups level-1 values, 0: 4 nGroups level-0
+ *   partials): out[i], nout[i] = -out[i], sum[i] = add[i] + out[i]; nout_dev, add_dev and sum_dev may be NULL.
+ * project: w -= c[i] V[i], ascending i; epi 1: l1_dev[group] of w . w, epi 2: l1_dev[i nGroups + group] of dot(V[i], w).
+ * multiadd, scale: sb_gmres_pre_multiupdate_native and sb_gmres_pre_scale_native with a stop flag (g0_dev may be NULL).
+ * rr: gm_rr_k<mode> (0 the prologue, 1 a close inside the loop, 2 the close of sb_gmres_finish) over nGroups values at q_dev.
+ * step: the scalar step at cycle position j.  scale 0: the op list's kernel over nGroups values at q_dev (l1 as in
+ *   finish_dots), mode -1.  scale 1: q_dev holds the (n + 255) / 256 level-1 values of w . w, vnext = w / hn and the first part
+ *   of M^-1 of it ride.  The kernel reads the block's stop flag itself.
+ * backsolve: y[0 .. nvec-1] of the dense state from g and H's first nvec columns. */
+int sb_gmres_multidot_native(uint32_t n, int nvec, const double* V_dev, size_t ldv, const double* w_dev, double* l1_dev, int stopped);
+int sb_gmres_finish_dots_native(uint32_t nGroups, int nvec, const double* q_dev, size_t qStride, int l1, double* out_dev, double* nout_dev,
+    const double* add_dev, double* sum_dev, int stopped);
+int sb_gmres_project_native(int epi, uint32_t n, int nvec, const double* V_dev, size_t ldv, const double* c_dev, double* w_dev, double* l1_dev,
+    int stopped);
+int sb_gmres_multiadd_native(uint32_t n, int mode, double c1, int nvec, const double* V_dev, size_t ldv, const double* c_dev, double* w_dev,
+    const double* dinv_dev, double* d_dev, double* z_dev, int stopped);
+int sb_gmres_scale_native(uint32_t n, int mode, double c1, const double* a_dev, const double* scalar_dev, double* out_dev, double* g0_dev,
+    const double* dinv_dev, double* d_dev, double* z_dev, int stopped);
+int sb_gmres_rr_native(int mode, uint32_t nGroups, const double* q_dev, int l1, double* res_hist_dev, double* rr_hist_dev, int use_stop,
+    double* blk_d, int* blk_i);
+int sb_gmres_step_native(int scale, int mode, double c1, uint32_t n, int j, int m, uint32_t nGroups, const double* q_dev, int l1,
+    const double* w_dev, double* vnext_dev, const double* dinv_dev, double* d_dev, double* z_dev, double* res_hist_dev, double* blk_d, int* blk_i,
+    double* dense_host);
+int sb_gmres_backsolve_native(int m, int nvec, int use_stop, double* blk_d, int* blk_i, double* dense_host);
 /* test entry: sqrt_dev[e] = sqrt(a[e]), div_dev[e] = a[e] / b[e] as the scalar steps compute them (IEEE correctly rounded) */
 void sb_debug_sqrt_div(uint32_t n, const double* a_dev, const double* b_dev, double* sqrt_dev, double* div_dev);
 

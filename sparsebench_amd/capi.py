@@ -55,6 +55,8 @@ SYMBOLS = [
     "sb_cgb_finish", "sb_cgb_iterations", "sb_cgb_history", "sb_cgb_solution", "sb_cgb_check_residual", "sb_cgb_loop_ms",
     "sb_cgb_counters", "sb_block_vec_native", "sb_block_vec_launch", "sb_cgb_update_p_native", "sb_cgb_x_finalize_native",
     "sb_cgb_rows_launch", "sb_gmres_group_launch",
+    "sb_gmres_scale_launch", "sb_gmres_step_launch", "sb_gmres_multidot_native", "sb_gmres_finish_dots_native", "sb_gmres_project_native",
+    "sb_gmres_multiadd_native", "sb_gmres_scale_native", "sb_gmres_rr_native", "sb_gmres_step_native", "sb_gmres_backsolve_native",
     "sb_matrix_diagonal", "sb_pcg_create", "sb_pcg_free", "sb_pcg_solve", "sb_pcg_start", "sb_pcg_run_iters", "sb_pcg_finish",
     "sb_pcg_history", "sb_pcg_solution", "sb_pcg_check_residual", "sb_pcg_dinv", "sb_pcg_launches_per_body", "sb_pcg_loop_ms",
     "sb_pcg_counters", "sb_pcg_update_r_native", "sb_pcg_update_r_launch", "sb_pcg_collectives_per_body", "sb_pcg_local_reduce_native",
@@ -308,6 +310,16 @@ def load():
         "sb_cgb_x_finalize_native": (None, [C.c_int, u32, vp, vp, vp, vp]),
         "sb_cgb_rows_launch": (None, [u32, vp]),
         "sb_gmres_group_launch": (None, [u32, vp]),
+        "sb_gmres_scale_launch": (None, [u32, vp]),
+        "sb_gmres_step_launch": (None, [u32, vp]),
+        "sb_gmres_multidot_native": (C.c_int, [u32, C.c_int, vp, C.c_size_t, vp, vp, C.c_int]),
+        "sb_gmres_finish_dots_native": (C.c_int, [u32, C.c_int, vp, C.c_size_t, C.c_int, vp, vp, vp, vp, C.c_int]),
+        "sb_gmres_project_native": (C.c_int, [C.c_int, u32, C.c_int, vp, C.c_size_t, vp, vp, vp, C.c_int]),
+        "sb_gmres_multiadd_native": (C.c_int, [u32, C.c_int, C.c_double, C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, C.c_int]),
+        "sb_gmres_scale_native": (C.c_int, [u32, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, C.c_int]),
+        "sb_gmres_rr_native": (C.c_int, [C.c_int, u32, vp, C.c_int, vp, vp, C.c_int, vp, vp]),
+        "sb_gmres_step_native": (C.c_int, [C.c_int, C.c_int, C.c_double, u32, C.c_int, C.c_int, u32, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sb_gmres_backsolve_native": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         # CG with a diagonal preconditioner
         "sb_matrix_diagonal": (None, [vp, vp]),
         "sb_pcg_create": (vp, [vp, vp, vp, vp, vp]),

@@ -62,12 +62,8 @@ void sb_gmres_dinv(const sb_gmres* s, double* dinv_host)
 }
 
 // --- the three riding kernels on a caller's vectors (blocking; tests), through the loop's gm_launch_* -------------------------
-// mode -1: the unpreconditioned kernel (dinv, d, z unused); 0: z = out o dinv; 1: d = z = (out o dinv) * c1
-static void gm_pre_native_args(int mode, const double* dinv, const double* d, const double* z, const char* fn)
-{
-  if (mode < -1 || mode > 1) SB_FATAL("%s: mode = %d (-1: the twin, 0: a diagonal, 1: Chebyshev)", fn, mode);
-  if (mode >= 0 && (!dinv || !z || (mode == 1 && !d))) SB_FATAL("%s: mode %d needs dinv_dev, z_dev%s", fn, mode, mode ? " and d_dev" : "");
-}
+// mode -1: the unpreconditioned kernel (dinv, d, z unused); 0: z = out o dinv; 1: d = z = (out o dinv) * c1 (the arguments are
+// checked by gm_pre_native_args, sbhip_gmres.inc.h)
 
 // out = a / *scalar_dev, *g0_dev = *scalar_dev
 void sb_gmres_pre_scale_native(uint32_t n, int mode, double c1, const double* a_dev, const double* scalar_dev, double* out_dev,
